@@ -6,7 +6,10 @@ in HBM) + the per-taxid table merge (RCCL all-reduce / bitmap all-gather when N 
 Weak scaling: every rank classifies `--reads` reads of its own slice of the global read stream against a
 full replica of the store.  Rank 0 prints ONE JSON line: `value` is configs[1].
 
-What the line carries besides the contract's fields (N = 1):
+A plain run sets up, warms up, times the steps, writes the outputs of the last timed step when --dump-outputs DIR is given
+(DIR/table.npy and DIR/dtable.npy: what gs_match_finish returned, as float64; the inputs are seeded, so two builds can be
+compared output for output) and prints the line.  Everything else the benchmark measures or checks runs with --full; what
+the line then carries besides the contract's fields (N = 1):
 
   roofline      resource fractions of the dominant kernel, every CEILING measured in this run (gs_calibrate: VALU / SALU
                 issue at the kernel's occupancy, random-line rate at the store's footprint) and every COUNTER collected in
@@ -18,8 +21,9 @@ What the line carries besides the contract's fields (N = 1):
   cpu_baseline  the oracle ("port") on the host cores, timed on that same pass
   large_store, huge_store, filter, table_only, reads_250bp, long_reads, end_to_end, striped_store, file_pipeline, db_build
                 the workloads the headline does not show, each with its own parity gate
+A plain run's `roofline` holds the kernel time of the timed steps only (`bound` says it is not priced).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--legs ...] [--pmc auto|off]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--dump-outputs DIR] [--full [--legs ...] [--pmc auto|off]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 `--gpus N` without a launcher (WORLD_SIZE unset) starts the N ranks itself, before any GPU call, and exits non-zero when
@@ -84,6 +88,17 @@ def _submit_reads(m, dseq, doff, first, n, read_len=None):
         m.submit(dseq, doff, first, n_reads=n)
     else:
         m.submit_fixed(dseq, READ_LEN if read_len is None else read_len, n, first)
+
+
+def _dump_outputs(out_dir, **arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64 (n_values rows each: a few hundred KB even for large stores).
+    The integer columns are counts, read numbers and base totals, exact in float64 below 2**53."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype.kind in "iu" and a.size and np.abs(a.astype(np.float64)).max() >= 2.0 ** 53:
+            raise SystemExit("--dump-outputs: %s holds integers that float64 cannot hold exactly" % name)
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
 
 
 class _DevArray:
@@ -470,7 +485,15 @@ def main():
     ap.add_argument("--pmc-seconds", type=int, default=420, help="time budget of the in-run PMC passes")
     ap.add_argument("--pmc-save", default="", help="directory for <workload>_pmc_summary.csv files of the in-run PMC passes (the format of profiles/rNN_*_pmc_summary.csv)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline: counters, ceilings and roofline, parity against "
+                         "the CPU oracle, the CPU baseline and the other workloads (--legs, --pmc*, --cpu-seconds, --check-reads "
+                         "apply only then)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (the per-taxid tables of gs_match_finish) to DIR/<name>.npy as float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.pmc_child:
         return _pmc_child()
     legs = set(args.legs.split(","))
@@ -488,7 +511,7 @@ def main():
 
     # ---- counters first: the PMC passes are child processes and must start before this process initialises the GPU
     pmc, pmc_note = None, "off (--pmc off)"
-    if world == 1 and args.pmc == "auto" and default_workload:
+    if world == 1 and args.pmc == "auto" and default_workload and args.full:
         import torch  # noqa: F401  (pages the libraries in before the children time out on a cold box)
         pmc, pmc_note = _pmc_collect(args.pmc_seconds, args.reads)
         if pmc is not None and args.pmc_save:
@@ -593,9 +616,11 @@ def main():
     t0 = time.perf_counter()
     table = None
     for _ in range(args.steps):
-        table, _ = step()
+        table, dtable = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, table=table, dtable=dtable)
     launches1, ms1 = m.kernel_time()
     if use_dist:
         te = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
@@ -633,7 +658,7 @@ def main():
     # ---- ceilings measured now, on this device (rank 0 of a one-GPU run: the roofline is a single-GPU statement)
     cal, cal_rep = (None, None)
     foot_main = int(info.rec_bytes + info.table_bytes + (info.mgate_bytes or info.gate_bytes))
-    if world == 1:
+    if world == 1 and args.full:
         cal, cal_rep = _calibrate(ga, {"lines_main": foot_main, "lines_1GiB": 1 << 30, "lines_filter": 226 << 20,
                                        "lines_cal": CAL_LINES_BYTES})
         if pmc and pmc.get("cal_lines"):
@@ -642,7 +667,7 @@ def main():
         cal["fetch_correction"] = corr
         cal_rep["fetch_size_calibration"] = corr_rep or "not taken (no in-run PMC pass): FETCH_SIZE used as reported (64-byte requests)"
     cnt, src = (None, None)
-    if world == 1 and default_workload:
+    if world == 1 and default_workload and args.full:
         if pmc and pmc.get("match"):
             cnt, src = pmc["match"], pmc_note
         else:
@@ -675,9 +700,16 @@ def main():
         roof.setdefault("traffic", None)
         roof["calibration"] = cal_rep
     else:
-        roof.update({"bound": "not priced at N > 1 (the roofline is the N = 1 line's)", "achieved": None, "peak": None, "unit": None,
-                     "frac": None, "traffic": None})
+        roof.update({"bound": "not priced at N > 1 (the roofline is the N = 1 line's)" if world > 1 else "not priced (bench.py --full)",
+                     "achieved": None, "peak": None, "unit": None, "frac": None, "traffic": None})
     out["roofline"] = roof
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- parity gate: the table of the TIMED steps against the CPU oracle over the same reads.
     # N > 1: every rank must hold the same merged table and rank 0 checks it against the oracle over ALL ranks' slices

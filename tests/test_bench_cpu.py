@@ -42,3 +42,16 @@ def test_fetch_correction_from_the_calibration_kernel():
     f, rec = bench._fetch_correction({"cal_lines": {"FETCH_SIZE": 1000.0, "lines": 16000.0}})
     assert abs(f - 16000.0 * 64 / (1000.0 * 1024)) < 1e-9 and rec["factor"] == 1.0
     assert bench._fetch_correction(None) == (1.0, None)
+
+
+def test_dump_outputs_writes_float64_and_refuses_what_it_cannot_hold(tmp_path):
+    import numpy as np
+    import pytest
+    table = np.array([[3, -1, 1_500_000_000], [0, 7, (1 << 53) - 1]], dtype=np.int64)
+    dtable = np.array([[0.25, 1e-3]])
+    bench._dump_outputs(str(tmp_path / "out"), table=table, dtable=dtable)
+    for name, want in (("table", table), ("dtable", dtable)):
+        got = np.load(tmp_path / "out" / (name + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, want)
+    with pytest.raises(SystemExit):
+        bench._dump_outputs(str(tmp_path / "big"), table=np.array([1 << 53], dtype=np.int64))

@@ -126,7 +126,7 @@ def test_one_process_per_gpu_bench_flow_over_rccl(mode):
     with n_gpus 2 whose merged table is bit-exact against the oracle over both ranks' reads"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "GS_BENCH_BACKEND")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--reads", "400000",
-           "--cpu-seconds", "0", "--mode", mode]
+           "--cpu-seconds", "0", "--mode", mode, "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])

@@ -299,7 +299,7 @@ def test_two_rank_bench_flow_over_gloo(mode):
     port = 29800 + (os.getpid() % 1500)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-           "--reads", "300000", "--check-reads", "50000", "--cpu-seconds", "0", "--mode", mode]
+           "--reads", "300000", "--check-reads", "50000", "--cpu-seconds", "0", "--mode", mode, "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [x for x in r.stdout.splitlines() if x.startswith("{")][-1]

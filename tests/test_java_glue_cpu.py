@@ -1,7 +1,8 @@
 """The reference-side Java glue (java/) cannot be compiled here -- no JDK in the image.  What can be checked is checked:
-* tools/check_java_glue.py: every reference class / member / constructor the glue uses exists in the reference's sources
-  with that name, arity and a visibility the glue can reach (needs /root/reference: build container only);
-* the checker itself flags the mistakes it is meant to catch (a deliberately broken class);
+* tools/check_java_glue.py (run by hand with --reference <the reference's checkout>: every reference class / member /
+  constructor the glue uses exists in the reference's sources with that name, arity and a visibility the glue can reach)
+  flags the mistakes it is meant to catch and nothing else: a deliberately broken class and a correct one, both against a
+  small library of the test's own standing in for the reference;
 * java/jni/gsgpu_jni.c passes `gcc -fsyntax-only` against a declarations-only jni.h and implements exactly the native
   methods GsGpuNative.java declares, with matching argument counts, calling only functions include/gsgpu.h declares."""
 import os
@@ -9,55 +10,98 @@ import re
 import subprocess
 import sys
 
-import pytest
-
 from conftest import ROOT
 
-REF = "/root/reference"
 CHECK = os.path.join(ROOT, "tools", "check_java_glue.py")
-needs_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "core", "src", "main", "java")),
-                               reason="the reference's sources exist in the build container only")
 
-
-@needs_ref
-def test_glue_uses_only_what_the_reference_declares():
-    r = subprocess.run([sys.executable, CHECK], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-4000:]
-    assert re.search(r"checked (\d+) glue classes", r.stdout) and int(re.search(r"checked (\d+) glue", r.stdout).group(1)) >= 6
-
-
-BROKEN = '''
-package org.metagene.genestrip.match;
+# the stand-in library: laid out as the checker looks for sources (core|base/src/main/java), one of each kind of
+# declaration the checks below need -- constructors of one arity, a final and an overridable hook, a private field, nested
+# classes, an interface method, enum constants
+LIBRARY = {
+    "core/src/main/java/org/example/lib/Matcher.java": '''
+package org.example.lib;
 
 import java.io.IOException;
-import org.metagene.genestrip.ExecutionContext;
-import org.metagene.genestrip.GSConfigKey;
-import org.metagene.genestrip.store.KMerStore;
-import org.metagene.genestrip.tax.SmallTaxTree;
-import org.metagene.genestrip.tax.SmallTaxTree.SmallTaxIdNode;
+import org.example.lib.store.Store;
 
-public class Broken extends FastqKMerMatcher {
-	public Broken(KMerStore<SmallTaxIdNode> store, ExecutionContext bundle, SmallTaxTree tree) {
-		super(store, 1, 2, bundle);                              // no such constructor arity
+public class Matcher {
+	protected final Store store;
+	private Object callback;
+
+	public Matcher(Store store, int threads, Context context) {
+		this.store = store;
+	}
+
+	protected final void nextEntry(Entry entry, int index) throws IOException {
+	}
+
+	protected boolean matchRead(Entry entry, int index) {
+		return false;
+	}
+
+	public static class Entry {
+		public void growBuffer(int n) {
+		}
+	}
+
+	public static class Counts {
+		public long reads;
+	}
+}
+''',
+    "core/src/main/java/org/example/lib/Context.java": '''
+package org.example.lib;
+
+public class Context {
+	public Context(int threads) {
+	}
+}
+''',
+    "base/src/main/java/org/example/lib/store/Store.java": '''
+package org.example.lib.store;
+
+public interface Store {
+	long getValues(int index);
+}
+''',
+    "base/src/main/java/org/example/lib/Key.java": '''
+package org.example.lib;
+
+public enum Key {
+	THREADS, LOG_LEVEL;
+}
+''',
+}
+
+BROKEN = '''
+package org.example.lib;
+
+import java.io.IOException;
+import org.example.lib.Key;
+import org.example.lib.store.Store;
+
+public class Broken extends Matcher {
+	public Broken(Store store, Context context) {
+		super(store, 1, 2, context);                             // no such constructor arity
 	}
 
 	@Override
-	protected void nextEntry(ReadEntry entry, int index) throws IOException {   // final in FastqKMerMatcher
+	protected void nextEntry(Entry entry, int index) throws IOException {   // final in Matcher
 	}
 
 	@Override
 	protected void noSuchHook(int x) {                           // nothing to override
 	}
 
-	void use(CountsPerTaxid stats, MatcherReadEntry e) {
+	void use(Counts stats, Entry e) {
 		stats.noSuchField = 1;                                   // unknown member
-		Object o = afterMatchCallback;                           // private field of the superclass
-		int n = kmerStore.getNValues(1, 2);                      // wrong arity
-		Object key = GSConfigKey.NO_SUCH_KEY;                    // unknown constant
-		e.growPrintBufferTypo(3);                                // unknown method on a reference type
-		FastqKMerMatcher m = new FastqKMerMatcher(kmerStore) {   // constructor arity + bogus override in an anonymous class
+		Object o = callback;                                     // private field of the superclass
+		long n = store.getValues(1, 2);                          // wrong arity
+		Object key = Key.NO_SUCH_KEY;                            // unknown constant
+		e.growBufferTypo(3);                                     // unknown method on a library type
+		Matcher m = new Matcher(store) {                         // constructor arity + bogus override in an anonymous class
 			@Override
-			protected boolean matchReadTypo(MatcherReadEntry entry, int index) {
+			protected boolean matchReadTypo(Entry entry, int index) {
 				return false;
 			}
 		};
@@ -65,19 +109,60 @@ public class Broken extends FastqKMerMatcher {
 }
 '''
 
+GOOD = '''
+package org.example.glue;
 
-@needs_ref
+import org.example.lib.Context;
+import org.example.lib.Key;
+import org.example.lib.Matcher;
+import org.example.lib.store.Store;
+
+public class Good extends Matcher {
+	private final Context own;
+
+	public Good(Store store, Context context) {
+		super(store, 2, context);
+		own = new Context(2);
+	}
+
+	@Override
+	protected boolean matchRead(Entry entry, int index) {
+		entry.growBuffer(index);
+		return store.getValues(index) > 0 && Key.THREADS != null;
+	}
+
+	long count(Counts stats) {
+		Matcher m = new Matcher(store, 1, own) {
+			@Override
+			protected boolean matchRead(Entry entry, int index) {
+				return true;
+			}
+		};
+		return stats.reads;
+	}
+}
+'''
+
+
 def test_checker_flags_what_it_is_meant_to_catch(tmp_path):
-    d = tmp_path / "org" / "metagene" / "genestrip" / "match"
-    d.mkdir(parents=True)
-    (d / "Broken.java").write_text(BROKEN)
-    r = subprocess.run([sys.executable, CHECK, "--glue", str(tmp_path)], capture_output=True, text=True)
+    ref = tmp_path / "ref"
+    for rel, text in LIBRARY.items():
+        (ref / rel).parent.mkdir(parents=True, exist_ok=True)
+        (ref / rel).write_text(text)
+    glue = tmp_path / "glue"
+    for pkg, name, text in (("lib", "Broken", BROKEN), ("glue", "Good", GOOD)):
+        d = glue / "org" / "example" / pkg
+        d.mkdir(parents=True)
+        (d / (name + ".java")).write_text(text)
+    r = subprocess.run([sys.executable, CHECK, "--reference", str(ref), "--glue", str(glue)], capture_output=True, text=True)
     assert r.returncode == 1
     out = r.stdout
+    assert re.search(r"checked 2 glue classes against %d reference files" % len(LIBRARY), out), out
     for needle in ("super(...) with 4 arguments", "@Override nextEntry", "is final", "@Override noSuchHook", "noSuchField",
-                   "afterMatchCallback is private", "getNValues(...): no overload takes 2", "NO_SUCH_KEY",
-                   "growPrintBufferTypo", "new FastqKMerMatcher(...) with 1 arguments", "@Override matchReadTypo"):
+                   "callback is private", "getValues(...): no overload takes 2", "NO_SUCH_KEY",
+                   "growBufferTypo", "new Matcher(...) with 1 arguments", "@Override matchReadTypo"):
         assert needle in out, (needle, out)
+    assert "Good" not in out, out
 
 
 def test_jni_shim_syntax_and_coverage():
