@@ -3192,6 +3192,7 @@ extern "C" int gs_match_merge(gs_run *const *runs, int n_runs) try {
             x.rec_bytes != i0.rec_bytes || x.n_in_records != i0.n_in_records || runs[i]->bitmap_words != r0->bitmap_words)
             return fail(GS_E_INVALID, "gs_match_merge needs runs on replicas of one store");
         if (runs[i]->cfg.count_unique != r0->cfg.count_unique) return fail(GS_E_INVALID, "runs differ in count_unique");
+        if ((runs[i]->d_hit_counts != nullptr) != (r0->d_hit_counts != nullptr)) return fail(GS_E_INVALID, "runs differ in max_kmer_res_counts");
     }
     const size_t nv = (size_t)i0.n_values;
     const bool uniq = r0->cfg.count_unique != 0;
@@ -3209,6 +3210,21 @@ extern "C" int gs_match_merge(gs_run *const *runs, int n_runs) try {
             if (xrc) return xrc;
         }
         HIP_TRY(hipStreamSynchronize(run->stream));
+    }
+    // per-k-mer hit counters (max_kmer_res_counts > 0, gs_match_max_counts): summed over all runs on the host and written back to
+    // every run (uint32 per slot, like the counters themselves; the Java-short wrap happens when they are read)
+    if (r0->d_hit_counts) {
+        const size_t n_hc = (size_t)(r0->db->n_slots() + r0->db->n_rec * GS_REC_SLOTS);
+        std::vector<uint32_t> total(n_hc, 0), part(n_hc);
+        for (int i = 0; i < n_runs; i++) {
+            HIP_TRY(hipSetDevice(runs[i]->db->device));
+            HIP_TRY(hipMemcpy(part.data(), runs[i]->d_hit_counts, n_hc * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            for (size_t j = 0; j < n_hc; j++) total[j] += part[j];
+        }
+        for (int i = 0; i < n_runs; i++) {
+            HIP_TRY(hipSetDevice(runs[i]->db->device));
+            HIP_TRY(hipMemcpy(runs[i]->d_hit_counts, total.data(), n_hc * sizeof(uint32_t), hipMemcpyHostToDevice));
+        }
     }
     // ---- stage A: the runs of one device into that device's first run (its leader)
     std::vector<int> devices;
@@ -3975,17 +3991,22 @@ extern "C" int gs_match_max_counts(gs_run *run, int16_t *out) {
     std::vector<u64> table(n_slots);
     std::vector<uint32_t> counts(n_slots);
     HIP_TRY(hipStreamSynchronize(run->stream));
-    if (run->db->striped()) {  // the slices of the table from their stripes, the seen bits from the run's bitmap
-        std::vector<uint32_t> tseen((n_slots + 31) / 32);
-        HIP_TRY(hipMemcpy(tseen.data(), run->d_bitmap, tseen.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    // the seen bits: a striped store's and a merged run's are in the run's bitmap (after gs_match_merge: the global one; the table's
+    // own bits only know this replica's reads), otherwise in the table
+    const bool own_bitmap = run->db->striped() || run->bitmap_merged;
+    if (run->db->striped()) {  // the slices of the table from their stripes
         for (int q = 0; q < run->db->n_parts; q++) {
             int64_t tfirst = 0, tlocal = 0;
             const u64 *tq = stripe_table(run->db, q, &tfirst, &tlocal);
             HIP_TRY(hipMemcpy(table.data() + (size_t)tfirst * GS_SLOTS_PER_BUCKET, tq, (size_t)tlocal * GS_SLOTS_PER_BUCKET * sizeof(u64), hipMemcpyDeviceToHost));
         }
-        for (size_t i = 0; i < n_slots; i++) table[i] = (table[i] & ~1ULL) | ((tseen[i >> 5] >> (i & 31)) & 1u);
     } else
         HIP_TRY(hipMemcpy(table.data(), run->db->d_table, n_slots * sizeof(u64), hipMemcpyDeviceToHost));
+    if (own_bitmap) {
+        std::vector<uint32_t> tseen((n_slots + 31) / 32);
+        HIP_TRY(hipMemcpy(tseen.data(), run->d_bitmap, tseen.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n_slots; i++) table[i] = (table[i] & ~1ULL) | ((tseen[i >> 5] >> (i & 31)) & 1u);
+    }
     HIP_TRY(hipMemcpy(counts.data(), run->d_hit_counts, n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost));
     std::fill(out, out + (nv + 1) * (size_t)N, (int16_t)0);
     const u64 vmask = ((u64)1 << run->db->dev.vbits) - 1;
@@ -4010,7 +4031,7 @@ extern "C" int gs_match_max_counts(gs_run *run, int16_t *out) {
         const size_t n_rec = (size_t)run->db->n_rec;
         std::vector<u64> rec(n_rec * GS_REC_WORDS);
         std::vector<uint32_t> rcounts(n_rec * GS_REC_SLOTS);
-        std::vector<uint32_t> rseen;  // striped store: the seen bits are the run's own (one word per record bucket)
+        std::vector<uint32_t> rseen;  // own_bitmap: the seen bits from the run's bitmap (one word per record bucket)
         const gs_db *db = run->db;
         if (db->striped()) {
             for (int q = 0; q < db->n_parts; q++) {
@@ -4018,14 +4039,16 @@ extern "C" int gs_match_max_counts(gs_run *run, int16_t *out) {
                 const size_t local = (size_t)gs_stripe_first(db->dev.rec_bits, (uint32_t)db->n_parts, (uint32_t)q + 1) - first;
                 HIP_TRY(hipMemcpy(rec.data() + first * GS_REC_WORDS, db->stripe_base[q], local * GS_REC_WORDS * sizeof(u64), hipMemcpyDeviceToHost));
             }
-            rseen.resize(n_rec);
-            HIP_TRY(hipMemcpy(rseen.data(), run->d_bitmap + (n_slots + 31) / 32, n_rec * sizeof(uint32_t), hipMemcpyDeviceToHost));
         } else
             HIP_TRY(hipMemcpy(rec.data(), run->db->d_rec, rec.size() * sizeof(u64), hipMemcpyDeviceToHost));
+        if (own_bitmap) {
+            rseen.resize(n_rec);
+            HIP_TRY(hipMemcpy(rseen.data(), run->d_bitmap + (n_slots + 31) / 32, n_rec * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        }
         HIP_TRY(hipMemcpy(rcounts.data(), run->d_hit_counts + n_slots, rcounts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         for (size_t b = 0; b < n_rec; b++) {
             const u64 *rp = rec.data() + b * GS_REC_WORDS;
-            uint32_t seen = (db->striped() ? rseen[b] : (uint32_t)(rp[0] >> GS_REC_WIN_BITS)) & (uint32_t)(rp[1] >> GS_REC_WIN_BITS);
+            uint32_t seen = (own_bitmap ? rseen[b] : (uint32_t)(rp[0] >> GS_REC_WIN_BITS)) & (uint32_t)(rp[1] >> GS_REC_WIN_BITS);
             for (; seen; seen &= seen - 1) {
                 const int j = __builtin_ctz(seen);
                 const size_t vi = (size_t)((rp[2 + j / 3] >> (GS_REC_VAL_BITS * (j % 3))) & (GS_REC_MAX_VALUES - 1));

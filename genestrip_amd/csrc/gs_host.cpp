@@ -975,13 +975,39 @@ struct TextJob {
 
     bool list_bgzf_members() { return bgzf_member_list(tr.map, tr.map_len, members_); }
 
-    // the chunk that was just submitted: first read number, reads; four_line: its descriptor lines can be fetched from the device
-    int chunk_submitted(int64_t first_no, int64_t n_reads, bool four_line) {
+    // the four-line FASTQ chunk that was just submitted: first read number, reads; its descriptor lines are fetched from the device
+    int chunk_submitted(int64_t first_no, int64_t n_reads) {
         if (!c.track_desc()) return GS_OK;
         gs_run *run = c.run;
-        if (!four_line) return c.update_max_contig(first_no, n_reads, nullptr);
         return c.update_max_contig(first_no, n_reads, [run](const int64_t *recs, int32_t m, uint8_t *out, int32_t stride) {
             return gs_match_text_descriptors(run, recs, m, out, stride);
+        });
+    }
+
+    // the same after a FASTA or general FASTQ chunk, whose text (n_lines whole lines) is still in host memory at `text`: the device
+    // gives the record geometry -- the newline offsets, and for general FASTQ the class of every line, as a '@' can also begin a
+    // quality line -- and the descriptor lines are taken from the text
+    int chunk_submitted_general(int64_t first_no, int64_t n_reads, const uint8_t *text, int64_t n_lines, bool is_fasta) {
+        if (!c.track_desc()) return GS_OK;
+        gs_run *run = c.run;
+        return c.update_max_contig(first_no, n_reads, [=](const int64_t *recs, int32_t m, uint8_t *out, int32_t stride) -> int {
+            std::vector<uint32_t> nl((size_t)std::max<int64_t>(n_lines, 1));
+            std::vector<uint8_t> cls((size_t)std::max<int64_t>(n_lines, 1));
+            int err = gs_match_text_newlines(run, nl.data());
+            if (!err && !is_fasta) err = gs_match_text_line_classes(run, cls.data());
+            if (err) return err;
+            auto line_start = [&nl](int64_t i) { return i ? (size_t)nl[(size_t)i - 1] + 1 : (size_t)0; };
+            std::vector<int64_t> head;  // descriptor line of every record (as outputs_general finds them)
+            for (int64_t i = 0; i < n_lines; i++)
+                if (is_fasta ? text[line_start(i)] == '>' && nl[(size_t)i] > line_start(i) : cls[(size_t)i] == 1) head.push_back(i);
+            if ((int64_t)head.size() != n_reads) return hfail(GS_E_INVALID, "text chunk: the descriptor lines do not match the device's record count");
+            for (int32_t j = 0; j < m; j++) {
+                const int64_t h = head[(size_t)recs[j]];
+                const size_t d0 = line_start(h), len = std::min<size_t>((size_t)nl[(size_t)h] - d0, (size_t)stride - 1);
+                memcpy(out + (size_t)j * (size_t)stride, text + d0, len);
+                out[(size_t)j * (size_t)stride + len] = 0;
+            }
+            return GS_OK;
         });
     }
 
@@ -1125,7 +1151,7 @@ struct TextJob {
             if (!err) err = rs.flags.resize((size_t)n_chunk);
             if (!err && !dev_f) err = tb.need((size_t)n_bytes);
             if (!err) err = gs_match_submit_text(c.run, text, n_bytes, n_lines, GS_MEM_DEVICE_TEXT, read_no + reads_in_file, rs.cls.data(), rs.flags.data(), &ticket);
-            if (!err) err = chunk_submitted(read_no + reads_in_file, n_chunk, true);
+            if (!err) err = chunk_submitted(read_no + reads_in_file, n_chunk);
             if (!err && !dev_f && gs_device_fetch(inf_device_, text, static_cast<uint8_t *>(tb.p), n_bytes) != GS_OK) err = hfail(GS_E_HIP, gs_inflate_last_error());
             if (!err) {
                 chunks.push_back({carry_file_off, reads_in_file, ticket});
@@ -1154,7 +1180,7 @@ struct TextJob {
         } else if (!err && n_lines > 0) {
             int64_t ticket = -1;
             err = gs_match_submit_text(c.run, text, n_bytes, n_lines, GS_MEM_DEVICE, read_no + reads_in_file, nullptr, nullptr, &ticket);
-            if (!err) err = chunk_submitted(read_no + reads_in_file, n_lines >> 2, true);
+            if (!err) err = chunk_submitted(read_no + reads_in_file, n_lines >> 2);
             if (!err) {
                 gz_ticket_ = ticket;
                 if (first_ticket < 0) first_ticket = ticket;
@@ -1235,7 +1261,7 @@ struct TextJob {
             if (!err) err = rs.flags.resize((size_t)n_chunk);
             if (!err && !dev_f) err = tb.need((size_t)n_bytes);
             if (!err) err = gs_match_submit_text(c.run, text, n_bytes, n_lines, GS_MEM_DEVICE_TEXT, read_no + reads_in_file, rs.cls.data(), rs.flags.data(), &ticket);
-            if (!err) err = chunk_submitted(read_no + reads_in_file, n_chunk, true);
+            if (!err) err = chunk_submitted(read_no + reads_in_file, n_chunk);
             if (!err && !dev_f && gs_inflater_fetch(inf_, static_cast<uint8_t *>(tb.p), n_bytes) != GS_OK) err = hfail(GS_E_HIP, gs_inflate_last_error());
             if (!err) {
                 chunks.push_back({carry_file_off, reads_in_file, ticket});
@@ -1264,7 +1290,7 @@ struct TextJob {
         } else if (!err && n_lines > 0) {
             int64_t ticket = -1;
             err = gs_match_submit_text(c.run, text, n_bytes, n_lines, GS_MEM_DEVICE, read_no + reads_in_file, nullptr, nullptr, &ticket);
-            if (!err) err = chunk_submitted(read_no + reads_in_file, n_lines >> 2, true);
+            if (!err) err = chunk_submitted(read_no + reads_in_file, n_lines >> 2);
             if (!err) {
                 dev_tickets_[slot] = ticket;
                 if (first_ticket < 0) first_ticket = ticket;
@@ -1345,7 +1371,7 @@ struct TextJob {
                 if (!err)
                     err = gs_match_submit_text(c.run, start, (int64_t)carry.size() + cut + 1, usable, GS_MEM_HOST, read_no + reads_in_file,
                                                per_read ? rs.cls.data() : nullptr, per_read ? rs.flags.data() : nullptr, &ticket);
-                if (!err) err = chunk_submitted(read_no + reads_in_file, usable >> 2, true);
+                if (!err) err = chunk_submitted(read_no + reads_in_file, usable >> 2);
                 const bool dev_f = per_read && device_filtered() && c.filtered.gzip();  // (a plain file: formatted from the reader's block, which is here anyway)
                 if (!err && per_read) {  // the writers need this chunk's results
                     chunks.push_back({carry_file_off, reads_in_file, ticket});
@@ -1448,7 +1474,7 @@ struct TextJob {
                     if (!err)
                         err = gs_match_submit_fasta(c.run, start, (int64_t)carry.size() + cut, lines, records, GS_MEM_HOST,
                                                     read_no + reads_in_file, kr ? rs.cls.data() : nullptr, kr ? rs.flags.data() : nullptr, &ticket);
-                    if (!err) err = chunk_submitted(read_no + reads_in_file, records, false);
+                    if (!err) err = chunk_submitted_general(read_no + reads_in_file, records, start, lines, true);
                     if (!err && kr && records > 0) {  // the per-read outputs of this chunk's records, before the block goes back
                         chunks.push_back({carry_file_off, reads_in_file, ticket});
                         err = check_refusal(&fallback_off, &fallback_reads);
@@ -1526,7 +1552,7 @@ struct TextJob {
                 if (!err)
                     err = gs_match_submit_fastq_ml(c.run, start, bytes, lines, GS_MEM_HOST, read_no + reads_in_file, kr ? rs.cls.data() : nullptr,
                                                    kr ? rs.flags.data() : nullptr, &n_rec, &used, &used_lines, &ticket);
-                if (!err && n_rec > 0) err = chunk_submitted(read_no + reads_in_file, n_rec, false);
+                if (!err && n_rec > 0) err = chunk_submitted_general(read_no + reads_in_file, n_rec, start, used_lines, false);
                 if (!err && kr && n_rec > 0) err = outputs_general(rs, start, used_lines, n_rec, false);
                 if (!err && n_rec < 0) {  // refused (NUL byte, a record of thousands of lines): the general parser from here
                     err = gs_match_text_clear_error(c.run);

@@ -265,8 +265,9 @@ int gs_match_or_bitmap(gs_run *run, const void *parts, int64_t n_parts);
  * Every run must work on a replica of the same store (same arrays through gs_db_create / the same store file).  Runs on
  * the same device are reduced by kernels, the devices among each other by RCCL collectives over xGMI (all-reduce SUM of
  * `sums` / `dsums`, all-reduce MAX of `max_keys`, all-gather + OR of the unique bitmaps; librccl is loaded on first
- * use).  Afterwards EVERY run holds the global state: gs_match_finish on any of them returns the table a single run
- * over all the reads would have produced (give the runs disjoint read numbers: first_read_no).  Synchronous. */
+ * use); the per-k-mer hit counters of runs begun with max_kmer_res_counts > 0 are summed through host memory.  Afterwards
+ * EVERY run holds the global state: gs_match_finish and gs_match_max_counts on any of them return what a single run over
+ * all the reads would have produced (give the runs disjoint read numbers: first_read_no).  Synchronous. */
 int gs_match_merge(gs_run *const *runs, int n_runs);
 
 /* ---------------------------------------------------------------------------------------------------

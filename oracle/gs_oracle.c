@@ -650,9 +650,9 @@ static void merge_path(const orc_db *db, consumer_t *c, int *used, int max_paths
     if (*used < max_paths) c->path_node[(*used)++] = node;
 }
 
-/* one read; returns ORC_F_* flags, *class_vi = entry.classNode */
+/* one read; returns ORC_F_* flags, *class_vi = entry.classNode; term (may be NULL) gets ORC_T_* of a counted read, cn -1 otherwise */
 static int match_read(orc_run *run, consumer_t *c, const uint8_t *read, int read_size, int64_t read_no,
-                      int32_t *class_vi_out) {
+                      int32_t *class_vi_out, int32_t *term) {
     const orc_db *db = run->db;
     const orc_match_cfg *cfg = &run->cfg;
     const int k = db->k;
@@ -722,9 +722,10 @@ static int match_read(orc_run *run, consumer_t *c, const uint8_t *read, int read
             if (cfg->count_unique) { /* KMerUniqueCounterBits.putInlined :117-143 */
 #pragma omp atomic
                 run->unique_bits[pos >> 6] |= 1ULL << (pos & 63);
-                if (run->hit_counts) { /* ++countsVector.shorts[index]: Java short arithmetic wraps (:134-140) */
-#pragma omp critical(orc_hit_counts)
-                    run->hit_counts[pos] = (int16_t)(uint16_t)((uint16_t)run->hit_counts[pos] + 1u);
+                if (run->hit_counts) { /* ++countsVector.shorts[index]: Java short arithmetic wraps (:134-140), as a 16-bit unsigned add does */
+                    uint16_t *hc = (uint16_t *)run->hit_counts + pos;
+#pragma omp atomic
+                    (*hc)++;
                 }
             }
         } else
@@ -776,6 +777,12 @@ static int match_read(orc_run *run, consumer_t *c, const uint8_t *read, int read
                     drow[ORC_D_CLASS_ERR_SUM] += cerr;
                     drow[ORC_D_CLASS_ERR_SQ_SUM] += cerr * cerr;
                     flags |= ORC_F_COUNTED;
+                    if (term) {
+                        term[ORC_T_CN] = cn;
+                        term[ORC_T_TAX_ERR] = tax_err;
+                        term[ORC_T_CLASS_ERR] = class_err;
+                        term[ORC_T_MAX] = max;
+                    }
                 }
             }
         }
@@ -786,6 +793,11 @@ static int match_read(orc_run *run, consumer_t *c, const uint8_t *read, int read
 
 int orc_match_submit(orc_run *run, const uint8_t *seq, const uint64_t *off, int64_t n, int64_t first_read_no,
                      int32_t *class_vi, uint8_t *flags, int threads) {
+    return orc_match_submit_terms(run, seq, off, n, first_read_no, class_vi, flags, NULL, threads);
+}
+
+int orc_match_submit_terms(orc_run *run, const uint8_t *seq, const uint64_t *off, int64_t n, int64_t first_read_no,
+                           int32_t *class_vi, uint8_t *flags, int32_t *terms, int threads) {
     if (threads < 1) threads = 1;
     if (run->n_consumers < threads) {
         run->cons = (consumer_t *)realloc(run->cons, sizeof(consumer_t) * (size_t)threads);
@@ -802,7 +814,9 @@ int orc_match_submit(orc_run *run, const uint8_t *seq, const uint64_t *off, int6
 #pragma omp for schedule(dynamic, 512)
         for (int64_t r = 0; r < n; r++) {
             int32_t cv;
-            int f = match_read(run, c, seq + off[r], (int)(off[r + 1] - off[r]), first_read_no + r, &cv);
+            int32_t *term = terms ? terms + (size_t)r * ORC_N_TERMS : NULL;
+            if (term) term[ORC_T_CN] = -1, term[ORC_T_TAX_ERR] = term[ORC_T_CLASS_ERR] = term[ORC_T_MAX] = 0;
+            int f = match_read(run, c, seq + off[r], (int)(off[r + 1] - off[r]), first_read_no + r, &cv, term);
             if (class_vi) class_vi[r] = cv;
             if (flags) flags[r] = (uint8_t)f;
         }

@@ -126,6 +126,12 @@ orc_run *orc_match_begin(const orc_db *db, const orc_match_cfg *cfg);
  * threads > 1 uses that many OpenMP threads (integer results are order independent, K4). */
 int orc_match_submit(orc_run *run, const uint8_t *seq, const uint64_t *offsets, int64_t n_reads,
                      int64_t first_read_no, int32_t *class_vi, uint8_t *flags, int threads);
+/* per-read terms of the double table (may be NULL): n_reads x ORC_N_TERMS int32.  A counted read (ORC_F_COUNTED) gets the
+ * row it is added to (cn = entry.classNode) and the integers its four dtable terms are formed from:
+ * tax_err / max and class_err / max, and their squares (FastqKMerMatcher.java:505-524); every other read gets cn = -1 and zeros. */
+enum { ORC_T_CN = 0, ORC_T_TAX_ERR, ORC_T_CLASS_ERR, ORC_T_MAX, ORC_N_TERMS };
+int orc_match_submit_terms(orc_run *run, const uint8_t *seq, const uint64_t *offsets, int64_t n_reads,
+                           int64_t first_read_no, int32_t *class_vi, uint8_t *flags, int32_t *terms, int threads);
 /* table: n_values x ORC_N_COLS int64 ; dtable: n_values x ORC_N_DCOLS double (may be NULL) */
 int orc_match_finish(orc_run *run, int64_t *table, double *dtable);
 void orc_match_destroy(orc_run *run);

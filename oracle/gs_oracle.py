@@ -17,6 +17,8 @@ N_DCOLS = 4
 (C_READS, C_READS_KMERS, C_KMERS, C_UNIQUE_KMERS, C_CONTIGS, C_CONTIG_LEN_SQ_SUM, C_MAX_CONTIG_LEN,
  C_READS_1KMER, C_READS_BPS, C_MAX_CONTIG_READ_NO) = range(N_COLS)
 F_FOUND, F_RETURNED, F_COUNTED = 1, 2, 4
+N_TERMS = 4
+T_CN, T_TAX_ERR, T_CLASS_ERR, T_MAX = range(N_TERMS)
 BLOOM_XOR, BLOOM_MURMUR, BLOOM_BLOCKED = 0, 1, 2
 
 
@@ -67,6 +69,7 @@ def lib():
         "orc_tree_is_ancestor_of": (C.c_int, [vp, i32, i32]),
         "orc_match_begin": (vp, [vp, vp]),
         "orc_match_submit": (C.c_int, [vp, vp, vp, i64, i64, vp, vp, C.c_int]),
+        "orc_match_submit_terms": (C.c_int, [vp, vp, vp, i64, i64, vp, vp, vp, C.c_int]),
         "orc_match_finish": (C.c_int, [vp, vp, vp]), "orc_match_destroy": (None, [vp]),
         "orc_match_bitmap_words": (i64, [vp]), "orc_match_export": (C.c_int, [vp, vp, vp]),
         "orc_match_import": (C.c_int, [vp, vp, vp]), "orc_match_max_counts": (C.c_int, [vp, vp]),
@@ -296,6 +299,18 @@ class MatchRun:
         fl = np.zeros(n, dtype=np.uint8) if per_read else None
         lib().orc_match_submit(self.h, _p(seq), _p(offsets), n, first_read_no, _p(cv), _p(fl), threads)
         return cv, fl
+
+    def submit_terms(self, seq, offsets, first_read_no=0, threads=1):
+        """submit() that also returns the per-read dtable terms: (class_vi, flags, terms int32[n, N_TERMS]); row r =
+        (cn, tax_err, class_err, max) of a counted read, (-1, 0, 0, 0) of any other"""
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        cv = np.full(n, -1, dtype=np.int32)
+        fl = np.zeros(n, dtype=np.uint8)
+        terms = np.zeros((n, N_TERMS), dtype=np.int32)
+        lib().orc_match_submit_terms(self.h, _p(seq), _p(offsets), n, first_read_no, _p(cv), _p(fl), _p(terms), threads)
+        return cv, fl, terms
 
     def submit_reads(self, reads, first_read_no=0, threads=1):
         seq, off = pack_reads(reads)

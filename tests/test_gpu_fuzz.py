@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import genestrip_amd as ga
+import matchcheck
 from oracle import gs_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -84,13 +85,13 @@ def test_random_scenario(seed):
     seq, off = orc.pack_reads(reads)
     first = int(rng.integers(0, 1 << 30))
     orun = orc.MatchRun(orc.DB(k, keys, vidx, n_values, parent), **cfg)
-    ocv, ofl = orun.submit(seq, off, first)
-    ot, _ = orun.finish()
+    ocv, ofl, oterms = orun.submit_terms(seq, off, first)
+    ot, od = orun.finish()
     assert int((ofl & orc.F_FOUND != 0).sum()) > 100  # the scenario is not vacuous
     store = ga.DeviceKMerStore(k, keys, vidx, n_values, parent)
     m = ga.FastqKMerMatcher(store, ga.MatchConfig(**cfg))
     gcv, gfl = m.match_reads(seq, off, first)
-    gt, _ = m.finish()
+    gt, gd = m.finish()
     # the same reads again as raw FASTQ text (device-side record scan), into a fresh state
     m.reset()
     text = b"".join(b"@x\n" + r + b"\n+\n" + b"#" * len(r) + b"\n" for r in reads)
@@ -99,10 +100,13 @@ def test_random_scenario(seed):
     m.submit_text(text, first_read_no=first, class_vi=cv2, flags=fl2)
     m.sync()
     assert m.text_status()[0] == -1
-    gt2, _ = m.finish()
+    gt2, gd2 = m.finish()
     m.close()
     store.close()
     what = (seed, k, n_values, cfg)
     assert np.array_equal(gt, ot), (what, np.argwhere(gt != ot)[:6])
     assert np.array_equal(gcv, ocv) and np.array_equal(gfl, ofl), what
     assert np.array_equal(gt2, ot) and np.array_equal(cv2, ocv) and np.array_equal(fl2, ofl), what
+    o = dict(table=ot, class_vi=ocv, flags=ofl, dtable=od, terms=oterms)
+    matchcheck.check_match(o, dict(table=gt, class_vi=gcv, flags=gfl, dtable=gd), f"{what} binary")
+    matchcheck.check_match(o, dict(table=gt2, class_vi=cv2, flags=fl2, dtable=gd2), f"{what} text")

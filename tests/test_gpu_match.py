@@ -7,6 +7,7 @@ import pytest
 
 import genestrip_amd as ga
 from genestrip_amd import synth
+import matchcheck
 from conftest import GOLDEN
 from oracle import gs_oracle as orc
 
@@ -24,11 +25,12 @@ def _k2_arrays(pairs):
 
 
 def _both(k, kmers, vidx, n_values, parent, reads, first_read_no=0, **cfg):
-    """run the same batch through the oracle and the GPU; returns ((table, class, flags) x 2)"""
+    """run the same batch through the oracle and the GPU; returns ((table, class, flags, dtable, per-read dtable terms),
+    (table, class, flags, dtable))"""
     seq, off = orc.pack_reads(reads) if not isinstance(reads, tuple) else reads
     odb = orc.DB(k, kmers, vidx, n_values, parent)
     orun = orc.MatchRun(odb, **cfg)
-    ocv, ofl = orun.submit(seq, off, first_read_no)
+    ocv, ofl, oterms = orun.submit_terms(seq, off, first_read_no)
     ot, od = orun.finish()
     store = ga.DeviceKMerStore(k, kmers, vidx, n_values, parent)
     m = ga.FastqKMerMatcher(store, ga.MatchConfig(**cfg))
@@ -36,17 +38,16 @@ def _both(k, kmers, vidx, n_values, parent, reads, first_read_no=0, **cfg):
     gt, gd = m.finish()
     m.close()
     store.close()
-    return (ot, ocv, ofl, od), (gt, gcv, gfl, gd)
+    return (ot, ocv, ofl, od, oterms), (gt, gcv, gfl, gd)
 
 
 def _assert_same(o, g):
-    ot, ocv, ofl, od = o
+    """integer table, class and flags bit-exact; every dtable cell within (n + 3) * 2^-53 of the exact sum of its terms
+    (tests/matchcheck.py: the order of the double sums is the device's, their value is not)"""
+    ot, ocv, ofl, od, oterms = o
     gt, gcv, gfl, gd = g
-    bad = np.argwhere(ot != gt)
-    assert bad.size == 0, f"table differs at (vi, col) {bad[:10].tolist()}: oracle {ot[tuple(bad[0])]} gpu {gt[tuple(bad[0])]}"
-    assert np.array_equal(ocv, gcv), f"class differs at reads {np.flatnonzero(ocv != gcv)[:10]}"
-    assert np.array_equal(ofl, gfl), f"flags differ at reads {np.flatnonzero(ofl != gfl)[:10]}"
-    assert np.allclose(od, gd, rtol=1e-9, atol=1e-9)  # double sums: order dependent, not part of the contract
+    matchcheck.check_match(dict(table=ot, class_vi=ocv, flags=ofl, dtable=od, terms=oterms),
+                           dict(table=gt, class_vi=gcv, flags=gfl, dtable=gd))
 
 
 # ------------------------------------------------------------------ reference KATs through the C ABI
