@@ -56,7 +56,10 @@ def main():
                                           taxids=db.taxids if args.kraken_out else None, with_probs=args.with_probs)
     print(f"{tot.reads} reads, {tot.bps} bases in {tot.seconds_total:.2f} s "
           f"({tot.bps / max(tot.seconds_total, 1e-9) / 1e9:.2f} Gbp/s end to end)")
-    db_kmers = np.bincount(db.value_idx, minlength=db.n_values).astype(np.int64)
+    if args.store and not args.demo:  # Database.getStats of the loaded store itself (gs_db_value_counts)
+        db_kmers = store.value_counts()
+    else:
+        db_kmers = np.bincount(db.value_idx, minlength=db.n_values).astype(np.int64)
     host.write_csv(args.csv, db.parent_vi, db.taxids, db_kmers, int(db_kmers.sum()), table, dtable, tot)
     print(f"wrote {args.csv}")
     for line in open(args.csv).read().split("\n")[:4]:

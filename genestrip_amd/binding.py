@@ -44,6 +44,8 @@ ABI_SYMBOLS = (
     "gs_match_get_device", "gs_inflate_members", "gs_inflater_create", "gs_inflater_feed", "gs_inflater_tail", "gs_gunzipper_open", "gs_gunzipper_reopen", "gs_gunzipper_next", "gs_gunzipper_info", "gs_gunzipper_first_span", "gs_gunzipper_park", "gs_gunzipper_close", "gs_gunzip_plan_device", "gs_gunzip_free", "gs_gunzip_device", "gs_text_cut_device", "gs_device_fetch", "gs_inflater_fetch", "gs_filter_get_device", "gs_inflater_reset", "gs_inflater_destroy", "gs_inflate_last_error",
     "gs_filter_compact_text", "gs_match_compact_text", "gs_deflater_create", "gs_deflater_pack", "gs_deflater_info", "gs_deflater_destroy", "gs_deflater_append", "gs_deflater_pending", "gs_deflater_flush",
     "gs_deflate_bound", "gs_deflate_host", "gs_deflate_host_reference", "gs_deflate_last_error", "gs_match_text_descriptors", "gs_match_submit_fixed",
+    "gs_db_value_counts", "gs_dbexport_create", "gs_dbexport_fetch", "gs_dbexport_get_device", "gs_dbexport_fastq_begin",
+    "gs_dbexport_fastq_next", "gs_dbexport_destroy",
 )
 
 
@@ -196,6 +198,13 @@ def lib():
         "gs_deflate_last_error": (C.c_char_p, []),
         "gs_match_text_descriptors": (ci, [vp, vp, i32, vp, i32]),
         "gs_match_submit_fixed": (ci, [vp, vp, i32, i64, i64, ci, vp, vp]),
+        "gs_db_value_counts": (ci, [vp, vp]),
+        "gs_dbexport_create": (ci, [vp, vp, i32, ci, vp]),
+        "gs_dbexport_fetch": (ci, [vp, vp, vp, ci]),
+        "gs_dbexport_get_device": (ci, [vp, vp]),
+        "gs_dbexport_fastq_begin": (ci, [vp, vp, C.c_char_p]),
+        "gs_dbexport_fastq_next": (ci, [vp, vp, vp, vp]),
+        "gs_dbexport_destroy": (ci, [vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -528,6 +537,27 @@ class DeviceKMerStore:
         i = DbInfo()
         _check(lib().gs_db_get_info(self.h, C.byref(i)))
         return i
+
+    def export(self, select=None, with_desc=True):
+        """KMerStore.visit (gs_dbexport_create + _fetch): the stored (k-mer, value index) pairs of this handle in ascending k-mer
+        order -> (kmers int64, value_idx int32).  select = a value index: only that value (with_desc=False) or its subtree
+        (with_desc=True); None: all.  What comes back is the n_stored pairs: reachable ones whose value has a tree node."""
+        x = C.c_void_p()
+        n = C.c_int64(0)
+        _check(lib().gs_dbexport_create(C.byref(x), self.h, -1 if select is None else int(select), int(bool(with_desc)), C.byref(n)))
+        try:
+            kmers = np.empty(n.value, dtype=np.int64)
+            vals = np.empty(n.value, dtype=np.int32)
+            _check(lib().gs_dbexport_fetch(x, kmers.ctypes.data_as(C.c_void_p), vals.ctypes.data_as(C.c_void_p), MEM_HOST))
+        finally:
+            lib().gs_dbexport_destroy(x)
+        return kmers, vals
+
+    def value_counts(self):
+        """Database.getStats per value index (gs_db_value_counts): stored k-mers of each value, int64[n_values]"""
+        out = np.zeros(self.info.n_values, dtype=np.int64)
+        _check(lib().gs_db_value_counts(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def close(self):
         if getattr(self, "h", None):

@@ -1953,6 +1953,285 @@ extern "C" int gs_db_destroy(gs_db *db) {
 }
 
 // ---------------------------------------------------------------------------------------------------
+// the store read back (gs_export.hip): KMerStore.visit, Database.getStats, KMerFastqGenerator
+// ---------------------------------------------------------------------------------------------------
+struct GsExportParams {  // (gs_export.hip)
+    const u64 *rec;
+    int64_t n_rec;
+    const u64 *tab;
+    int64_t tab_first, n_tab;
+    uint32_t bucket_bits, vbits;
+    int32_t k, n_values;
+    const int32_t *tin, *tout;
+    int32_t sel_vi, with_desc;
+    u64 *count, *keys;
+    uint32_t *vals;
+    u64 cap;
+    u64 *hist;
+};
+struct GsFastqParams {  // (gs_export.hip)
+    const u64 *keys;
+    const uint32_t *vals;
+    int64_t first, n;
+    int32_t k;
+    const uint8_t *project;
+    int32_t project_len;
+    const uint8_t *names;
+    const uint32_t *name_off;
+    uint32_t *len, *off;
+    uint8_t *text;
+};
+extern "C" hipError_t gs_launch_export_decode(const GsExportParams *P, int n_cu, hipStream_t stream);
+extern "C" hipError_t gs_launch_export_fastq(const GsFastqParams *P, void *scratch, size_t *scratch_bytes, int64_t *n_bytes, hipStream_t stream);
+extern "C" hipError_t gs_build_sort(u64 *keys, u64 *keys_alt, uint32_t *vals, uint32_t *vals_alt, int64_t n, int key_bits, u64 **keys_out,
+                                    uint32_t **vals_out, hipStream_t stream);
+
+// the part of the store this handle holds: all of it, a partition's table, or a stripe's record lines + table buckets
+static GsExportParams export_params(const gs_db *db, int32_t sel_vi, int with_desc) {
+    GsExportParams P{};
+    P.rec = db->d_rec;
+    P.n_rec = db->striped() ? db->rec_local : (db->d_rec ? db->n_rec : 0);
+    P.tab = db->d_table;
+    P.tab_first = db->striped() ? db->tab_first : 0;
+    P.n_tab = db->striped() ? db->tab_local : db->info.n_buckets;
+    P.bucket_bits = db->dev.bucket_bits;
+    P.vbits = db->dev.vbits;
+    P.k = db->info.k;
+    P.n_values = db->info.n_values;
+    P.tin = db->dev.tin;
+    P.tout = db->dev.tout;
+    P.sel_vi = sel_vi;
+    P.with_desc = with_desc;
+    return P;
+}
+
+struct gs_dbexport {
+    int device = 0, k = 0;
+    int32_t n_values = 0;
+    hipStream_t stream = nullptr;
+    int64_t n = 0;
+    u64 *d_keys = nullptr;      // ascending
+    uint32_t *d_vals = nullptr;
+    // FASTQ text (gs_dbexport_fastq_*)
+    uint8_t *d_names = nullptr, *d_project = nullptr, *d_text = nullptr;
+    uint32_t *d_name_off = nullptr, *d_len = nullptr, *d_off = nullptr;
+    void *d_scan = nullptr;
+    size_t scan_bytes = 0, text_cap = 0;
+    int64_t chunk_records = 0, next = -1;  // next record of the text (-1: gs_dbexport_fastq_begin first)
+    int32_t project_len = 0;
+};
+
+static void dbexport_free_text(gs_dbexport *x) {
+    for (void *p : {(void *)x->d_names, (void *)x->d_project, (void *)x->d_text, (void *)x->d_name_off, (void *)x->d_len, (void *)x->d_off, x->d_scan})
+        hipFree(p);
+    x->d_names = x->d_project = x->d_text = nullptr;
+    x->d_name_off = x->d_len = x->d_off = nullptr;
+    x->d_scan = nullptr;
+    x->next = -1;
+}
+
+static void dbexport_free(gs_dbexport *x) {
+    hipSetDevice(x->device);
+    if (x->stream) hipStreamSynchronize(x->stream);
+    dbexport_free_text(x);
+    hipFree(x->d_keys);
+    hipFree(x->d_vals);
+    if (x->stream) hipStreamDestroy(x->stream);
+    delete x;
+}
+
+extern "C" int gs_db_value_counts(gs_db *db, int64_t *counts) {
+    if (!db || !counts) return fail(GS_E_INVALID, "NULL argument");
+    HIP_TRY(hipSetDevice(db->device));
+    const int32_t nv = db->info.n_values;
+    hipStream_t stream = nullptr;
+    HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    u64 *d = nullptr;
+    hipError_t e = hipMalloc((void **)&d, sizeof(u64) * ((size_t)nv + 1));
+    GsExportParams P = export_params(db, -1, 0);
+    P.count = d;
+    P.hist = d + 1;
+    if (e == hipSuccess) e = hipMemsetAsync(d, 0, sizeof(u64) * ((size_t)nv + 1), stream);
+    if (e == hipSuccess) e = gs_launch_export_decode(&P, db->n_cu, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(counts, d + 1, sizeof(u64) * (size_t)nv, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    hipFree(d);
+    hipStreamDestroy(stream);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_db_value_counts: ") + hipGetErrorString(e));
+    return GS_OK;
+}
+
+extern "C" int gs_dbexport_create(gs_dbexport **out, gs_db *db, int32_t sel_vi, int with_desc, int64_t *n_kmers) try {
+    if (!out || !db) return fail(GS_E_INVALID, "NULL argument");
+    *out = nullptr;
+    if (sel_vi < -1 || sel_vi >= db->info.n_values) return fail(GS_E_INVALID, "sel_vi out of range");
+    HIP_TRY(hipSetDevice(db->device));
+    gs_dbexport *x = new gs_dbexport();
+    x->device = db->device;
+    x->k = db->info.k;
+    x->n_values = db->info.n_values;
+    GsExportParams P = export_params(db, sel_vi, with_desc ? 1 : 0);
+    u64 *d_count = nullptr, *keys_alt = nullptr;
+    uint32_t *vals_alt = nullptr;
+    u64 n = 0;
+    auto step = [&](hipError_t e) { return e == hipSuccess; };
+    hipError_t e = hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking);
+    // pass 1 counts (the stripe's / partition's share is not in the info), pass 2 writes exactly that many
+    if (step(e)) e = hipMalloc((void **)&d_count, sizeof(u64));
+    if (step(e)) e = hipMemsetAsync(d_count, 0, sizeof(u64), x->stream);
+    P.count = d_count;
+    if (step(e)) e = gs_launch_export_decode(&P, db->n_cu, x->stream);
+    if (step(e)) e = hipMemcpyAsync(&n, d_count, sizeof(u64), hipMemcpyDeviceToHost, x->stream);
+    if (step(e)) e = hipStreamSynchronize(x->stream);
+    const size_t m = n ? (size_t)n : 1;
+    if (step(e)) e = hipMalloc((void **)&x->d_keys, m * sizeof(u64));
+    if (step(e)) e = hipMalloc((void **)&x->d_vals, m * sizeof(uint32_t));
+    if (step(e)) e = hipMalloc((void **)&keys_alt, m * sizeof(u64));
+    if (step(e)) e = hipMalloc((void **)&vals_alt, m * sizeof(uint32_t));
+    if (step(e)) e = hipMemsetAsync(d_count, 0, sizeof(u64), x->stream);
+    P.keys = x->d_keys;
+    P.vals = x->d_vals;
+    P.cap = n;
+    u64 n2 = 0;
+    if (step(e)) e = gs_launch_export_decode(&P, db->n_cu, x->stream);
+    if (step(e)) e = hipMemcpyAsync(&n2, d_count, sizeof(u64), hipMemcpyDeviceToHost, x->stream);
+    if (step(e)) e = hipStreamSynchronize(x->stream);
+    u64 *ko = x->d_keys;
+    uint32_t *vo = x->d_vals;
+    if (step(e) && n2 == n) e = gs_build_sort(x->d_keys, keys_alt, x->d_vals, vals_alt, (int64_t)n, 2 * x->k, &ko, &vo, x->stream);
+    hipFree(d_count);
+    if (e == hipSuccess) {  // keep the buffers the sorted pairs ended up in
+        hipFree(ko == x->d_keys ? keys_alt : x->d_keys);
+        hipFree(vo == x->d_vals ? vals_alt : x->d_vals);
+        x->d_keys = ko;
+        x->d_vals = vo;
+    } else {
+        hipFree(keys_alt);
+        hipFree(vals_alt);
+    }
+    if (e != hipSuccess) {
+        dbexport_free(x);
+        return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbexport_create: ") + hipGetErrorString(e));
+    }
+    if (n2 != n) {
+        dbexport_free(x);
+        return fail(GS_E_HIP, "gs_dbexport_create: the two decode passes disagree");
+    }
+    x->n = (int64_t)n;
+    if (n_kmers) *n_kmers = x->n;
+    *out = x;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_dbexport_fetch(gs_dbexport *x, int64_t *kmers, int32_t *value_idx, int mem) {
+    if (!x || (x->n > 0 && (!kmers || !value_idx))) return fail(GS_E_INVALID, "NULL argument");
+    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    HIP_TRY(hipSetDevice(x->device));
+    if (x->n > 0) {
+        const hipMemcpyKind kind = mem == GS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        HIP_TRY(hipMemcpyAsync(kmers, x->d_keys, (size_t)x->n * sizeof(int64_t), kind, x->stream));
+        HIP_TRY(hipMemcpyAsync(value_idx, x->d_vals, (size_t)x->n * sizeof(int32_t), kind, x->stream));
+        HIP_TRY(hipStreamSynchronize(x->stream));
+    }
+    return GS_OK;
+}
+
+extern "C" int gs_dbexport_get_device(gs_dbexport *x, int *device) {
+    if (!x || !device) return fail(GS_E_INVALID, "NULL argument");
+    *device = x->device;
+    return GS_OK;
+}
+
+extern "C" int gs_dbexport_fastq_begin(gs_dbexport *x, const char *const *taxids, const char *project) try {
+    if (!x || !taxids || !project) return fail(GS_E_INVALID, "NULL argument");
+    HIP_TRY(hipSetDevice(x->device));
+    HIP_TRY(hipStreamSynchronize(x->stream));
+    dbexport_free_text(x);
+    std::vector<uint32_t> off((size_t)x->n_values + 1, 0);
+    std::string names;
+    size_t longest = 0;
+    for (int32_t v = 0; v < x->n_values; v++) {
+        const char *t = taxids[v] ? taxids[v] : "";
+        const size_t l = strlen(t);
+        names.append(t, l);
+        longest = std::max(longest, l);
+        if (names.size() >= ((size_t)1 << 32)) return fail(GS_E_INVALID, "taxid strings too long");
+        off[(size_t)v + 1] = (uint32_t)names.size();
+    }
+    const size_t plen = strlen(project);
+    if (plen > ((size_t)1 << 20) || longest > ((size_t)1 << 20)) return fail(GS_E_INVALID, "project name or taxid too long");
+    // chunks of at most GS_EXPORT_CHUNK_BYTES of text (default 256 MiB), sized by the longest record
+    size_t cap = (size_t)256 << 20;
+    if (const char *e = getenv("GS_EXPORT_CHUNK_BYTES")) cap = (size_t)std::max(1LL, atoll(e));
+    const size_t longest_rec = 20 + plen + longest + 20 + 2 * (size_t)x->k;
+    cap = std::min(std::max(cap, longest_rec), (size_t)1 << 31);
+    x->chunk_records = std::max<int64_t>(1, std::min<int64_t>((int64_t)(cap / longest_rec), std::max<int64_t>(x->n, 1)));
+    x->text_cap = (size_t)x->chunk_records * longest_rec;
+    x->project_len = (int32_t)plen;
+    GsFastqParams P{};
+    P.n = x->chunk_records;
+    hipError_t e = hipMalloc((void **)&x->d_names, names.size() + 1);
+    if (e == hipSuccess) e = hipMalloc((void **)&x->d_name_off, off.size() * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&x->d_project, plen + 1);
+    if (e == hipSuccess) e = hipMalloc((void **)&x->d_len, ((size_t)x->chunk_records + 1) * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&x->d_off, ((size_t)x->chunk_records + 1) * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&x->d_text, x->text_cap);
+    P.len = x->d_len;
+    P.off = x->d_off;
+    if (e == hipSuccess) e = gs_launch_export_fastq(&P, nullptr, &x->scan_bytes, nullptr, x->stream);
+    if (e == hipSuccess) e = hipMalloc(&x->d_scan, x->scan_bytes ? x->scan_bytes : 1);
+    if (e == hipSuccess && !names.empty()) e = hipMemcpy(x->d_names, names.data(), names.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(x->d_name_off, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess && plen) e = hipMemcpy(x->d_project, project, plen, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        dbexport_free_text(x);
+        return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbexport_fastq_begin: ") + hipGetErrorString(e));
+    }
+    x->next = 0;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_dbexport_fastq_next(gs_dbexport *x, const uint8_t **d_text, int64_t *n_bytes, int64_t *n_records) {
+    if (!x || !d_text || !n_bytes || !n_records) return fail(GS_E_INVALID, "NULL argument");
+    if (x->next < 0) return fail(GS_E_STATE, "gs_dbexport_fastq_begin first");
+    HIP_TRY(hipSetDevice(x->device));
+    *d_text = x->d_text;
+    *n_bytes = 0;
+    *n_records = std::min<int64_t>(x->chunk_records, x->n - x->next);
+    if (*n_records <= 0) {
+        *n_records = 0;
+        return GS_OK;
+    }
+    GsFastqParams P{};
+    P.keys = x->d_keys;
+    P.vals = x->d_vals;
+    P.first = x->next;
+    P.n = *n_records;
+    P.k = x->k;
+    P.project = x->d_project;
+    P.project_len = x->project_len;
+    P.names = x->d_names;
+    P.name_off = x->d_name_off;
+    P.len = x->d_len;
+    P.off = x->d_off;
+    int64_t bytes = 0;
+    HIP_TRY(gs_launch_export_fastq(&P, x->d_scan, &x->scan_bytes, &bytes, x->stream));  // lengths + offsets
+    if (bytes > (int64_t)x->text_cap) return fail(GS_E_HIP, "gs_dbexport_fastq_next: chunk larger than its buffer");
+    P.text = x->d_text;
+    HIP_TRY(gs_launch_export_fastq(&P, x->d_scan, &x->scan_bytes, &bytes, x->stream));  // the bytes
+    *n_bytes = bytes;
+    x->next += *n_records;
+    return GS_OK;
+}
+
+extern "C" int gs_dbexport_destroy(gs_dbexport *x) {
+    if (x) dbexport_free(x);
+    return GS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // match runs
 // ---------------------------------------------------------------------------------------------------
 // device state of the text mode (raw FASTQ chunk -> records, gs_text.hip); one per run / per filter handle

@@ -2820,3 +2820,42 @@ extern "C" int gs_host_release_pools(void) try {
 extern "C" int64_t gs_host_stat(int which) {
     return which == 0 ? g_ml_chunks.load() : (which == 1 ? g_filter_general_chunks.load() : -1);
 }
+
+// ---- db2fastq (C/goals/DB2FastqGoal.java -> KMerFastqGenerator.generateFastq): the text is made on the device chunk by chunk
+// (gs_dbexport_fastq_next) and leaves it as the file's bytes, compressed there for a .gz name (DeviceWriter, as the per-read writers)
+extern "C" int gs_host_db2fastq(gs_db *db, const char *const *taxids, const char *project, int32_t sel_vi, int with_desc, const char *path,
+                                int64_t *n_written) try {
+    if (!db || !taxids || !project || !path) return hfail(GS_E_INVALID, "NULL argument");
+    gs_dbexport *x = nullptr;
+    int64_t n = 0;
+    if (gs_dbexport_create(&x, db, sel_vi, with_desc, &n) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
+    std::unique_ptr<gs_dbexport, int (*)(gs_dbexport *)> hold(x, gs_dbexport_destroy);
+    int device = 0;
+    gs_dbexport_get_device(x, &device);
+    if (gs_dbexport_fastq_begin(x, taxids, project) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
+    OutFile out;
+    if (!out.open(path)) return hfail(GS_E_IO, std::string("cannot open ") + path);
+    int err = GS_OK;
+    {
+        DeviceWriter w;
+        w.begin(&out, device);
+        for (;;) {
+            const uint8_t *d_text = nullptr;
+            int64_t n_bytes = 0, n_records = 0;
+            if (gs_dbexport_fastq_next(x, &d_text, &n_bytes, &n_records) != GS_OK) {
+                err = hfail(GS_E_HIP, gs_last_error());
+                break;
+            }
+            if (n_records == 0) break;
+            if ((err = w.emit(0, d_text, n_bytes)) != GS_OK) break;
+        }
+        const int e = w.finish();
+        if (!err) err = e;
+    }
+    if (!out.close() && !err) err = hfail(GS_E_IO, std::string("writing ") + path + " failed");
+    if (err) return err;
+    if (n_written) *n_written = n;
+    return GS_OK;
+} catch (const std::exception &e) {
+    return hfail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
+}

@@ -32,7 +32,17 @@
 #define GS_HD static inline
 #endif
 
-GS_HD uint32_t gs_brev32(uint32_t x) { return __builtin_bitreverse32(x); }
+GS_HD uint32_t gs_brev32(uint32_t x) {
+#if defined(__clang__)
+    return __builtin_bitreverse32(x);
+#else  // (host tools built with g++ against this header)
+    x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
+    x = ((x >> 2) & 0x33333333u) | ((x & 0x33333333u) << 2);
+    x = ((x >> 4) & 0x0f0f0f0fu) | ((x & 0x0f0f0f0fu) << 4);
+    x = ((x >> 8) & 0x00ff00ffu) | ((x & 0x00ff00ffu) << 8);
+    return (x >> 16) | (x << 16);
+#endif
+}
 
 // representative orientation of the k-mer with forward planes (fhi, flo): planes of the larger (hi:lo) pair
 GS_HD void gs_rep_planes(uint32_t fhi, uint32_t flo, int k, uint32_t kmask, uint32_t &a, uint32_t &b) {
@@ -57,6 +67,36 @@ GS_HD uint64_t gs_mix_planes(uint32_t a, uint32_t b) {
     b ^= gs_fold31(a, 0x85EBCA77u);
     a ^= gs_fold31(b, 0xC2B2AE3Du);
     return ((uint64_t)a << GS_PLANE_SHIFT) | b;
+}
+
+// ... and its inverse: the three rounds backwards (what the store export decodes a table slot with: h = rem << bucket_bits | home)
+GS_HD void gs_unmix_planes(uint64_t h, uint32_t &a, uint32_t &b) {
+    a = (uint32_t)(h >> GS_PLANE_SHIFT);
+    b = (uint32_t)h & 0x7fffffffu;
+    a ^= gs_fold31(b, 0xC2B2AE3Du);
+    b ^= gs_fold31(a, 0x85EBCA77u);
+    a ^= gs_fold31(b, 0x9E3779B1u);
+}
+
+// bit i of v -> bit 2 i (v < 2^32)
+GS_HD uint64_t gs_spread2(uint32_t v) {
+    uint64_t x = v;
+    x = (x | (x << 16)) & 0x0000FFFF0000FFFFULL;
+    x = (x | (x << 8)) & 0x00FF00FF00FF00FFULL;
+    x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0FULL;
+    x = (x | (x << 2)) & 0x3333333333333333ULL;
+    x = (x | (x << 1)) & 0x5555555555555555ULL;
+    return x;
+}
+
+// planes of a k-mer in EITHER orientation -> the key the reference files it under: max(fwd, revcomp) of the interleaved
+// encoding, first base in the top bits (CGAT.java:145-147).  The planes read backwards give one strand's key, the planes as
+// they are with the low plane complemented give the other's.
+GS_HD uint64_t gs_planes_to_kmer(uint32_t hi, uint32_t lo, int k) {
+    const uint32_t kmask = (uint32_t)((1ULL << k) - 1);
+    const uint64_t a = (gs_spread2(gs_brev32(hi) >> (32 - k)) << 1) | gs_spread2(gs_brev32(lo) >> (32 - k));
+    const uint64_t b = (gs_spread2(hi) << 1) | gs_spread2((lo ^ kmask) & kmask);
+    return a > b ? a : b;
 }
 
 // Gate ("is this k-mer possibly in the store?"): a word-blocked Bloom filter, 4 bits per key inside one 64-bit

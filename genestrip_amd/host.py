@@ -55,6 +55,7 @@ def lib():
         "gs_host_release_pools": (ci, []),
         "gs_host_filter_files": (ci, [vp, ci, ci, C.c_double, vp, ci, C.c_char_p, C.c_char_p, ci, vp]),
         "gs_host_write_csv": (ci, [C.c_char_p, vp, vp, vp, vp]),
+        "gs_host_db2fastq": (ci, [vp, vp, C.c_char_p, C.c_int32, ci, C.c_char_p, vp]),
         "gs_host_last_error": (C.c_char_p, []), "gs_host_java_double": (ci, [C.c_double, vp, ci]),
         "gs_host_gunzip": (ci, [vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]),
         "gs_host_gunzip_parallel": (ci, [vp, C.c_size_t, vp, C.c_size_t, vp, ci, C.c_size_t, C.c_size_t]),
@@ -209,6 +210,19 @@ def write_csv(path, parent_vi, taxids, db_kmers, db_kmers_total, table, dtable, 
     d = np.ascontiguousarray(dtable, dtype=np.float64)
     _check(lib().gs_host_write_csv(str(path).encode(), C.byref(info), t.ctypes.data_as(C.c_void_p),
                                    d.ctypes.data_as(C.c_void_p), C.byref(totals)))
+
+
+def db2fastq(store, taxids, project, path, select=None, with_desc=True):
+    """the db2fastq goal (KMerFastqGenerator.generateFastq): the stored k-mers of value `select` (with_desc: and its subtree;
+    None: all, the goal's "total" file) as FASTQ, gzip (BGZF) when the name ends in .gz / .gzip.  taxids: the tax id string of
+    every value index.  Returns the number of records written."""
+    if len(taxids) != store.n_values:
+        raise ValueError("taxids must have one entry per value index")
+    tarr = _cstr_array(list(taxids))
+    n = C.c_int64(0)
+    _check(lib().gs_host_db2fastq(store.h, tarr, str(project).encode(), -1 if select is None else int(select), int(bool(with_desc)),
+                                  str(path).encode(), C.byref(n)))
+    return n.value
 
 
 def gunzip(data, expected_size, block=1 << 20):

@@ -110,6 +110,39 @@ int gs_db_save(gs_db *db, const char *path);
 int gs_db_load(gs_db **out, int device, const char *path);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The store read back (genestrip_amd/csrc/gs_export.hip): KMerStore.visit (C/store/KMerSortedArray.java:426-439),
+ * Database.getStats / getFixedNKmersPerTaxid (C/store/Database.java:159, AbstractKMerStore.java:364) and the db2fastq goal
+ * (C/goals/DB2FastqGoal.java, C/fastqgen/KMerFastqGenerator.java, FastQWriter.java).  Every record line and table bucket
+ * of the handle's store is decoded on the device (the layout is reversible); seen bits are masked, so these calls may run
+ * while a unique-counting run is alive on the store.
+ *
+ * What comes back is the n_stored pairs of the store: the pairs handed to gs_db_create (or built by gs_dbbuild) that are
+ * reachable (x >= revcomp(x): the reference only ever looks up max(fwd, revcomp), CGAT.java:145-147) and whose value has a
+ * tree node (parent_vi != -2).  The reference's visit also returns the pairs this store drops; nothing can bring those back.
+ * A partition store (gs_db_create_part) gives its own part, a stripe its record lines and its share of the table: the union
+ * over the parts / stripes is the whole store.
+ *
+ *   gs_db_value_counts     counts[n_values] (host) = stored k-mers per value index (the `db_kmers` of gs_host_write_csv)
+ *   gs_dbexport_create     decode + sort: the selected pairs, ascending by k-mer (KMerSortedArray.visit order).  sel_vi = -1:
+ *                          all; else value == sel_vi (with_desc == 0) or the value's node in the subtree of sel_vi (with_desc != 0)
+ *   gs_dbexport_fetch      kmers (reference encoding) + value_idx, *n_kmers entries each; mem = GS_MEM_HOST or GS_MEM_DEVICE
+ *   gs_dbexport_fastq_*    the pairs as FASTQ text on the device, what FastQWriter prints for KMerFastqGenerator.generateFastq
+ *                          (out, taxid, project + ":", withDesc): record i = 1, 2, .. is
+ *                          "@GENESTRIP:<project>::<taxids[value]>:<i>\n<k bases>\n+\n<'~' x k>\n" (CGAT.longToKMerStraight).
+ *                          _begin takes taxids[n_values] (host; NULL prints as empty) and the project name and rewinds; each
+ *                          _next returns the text of the next records in device memory (valid until the next call, at most
+ *                          GS_EXPORT_CHUNK_BYTES, default 256 MiB); *n_records = 0: the text is through.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct gs_dbexport gs_dbexport;
+int gs_db_value_counts(gs_db *db, int64_t *counts);
+int gs_dbexport_create(gs_dbexport **out, gs_db *db, int32_t sel_vi, int with_desc, int64_t *n_kmers);
+int gs_dbexport_fetch(gs_dbexport *x, int64_t *kmers, int32_t *value_idx, int mem);
+int gs_dbexport_get_device(gs_dbexport *x, int *device);
+int gs_dbexport_fastq_begin(gs_dbexport *x, const char *const *taxids, const char *project);
+int gs_dbexport_fastq_next(gs_dbexport *x, const uint8_t **d_text, int64_t *n_bytes, int64_t *n_records);
+int gs_dbexport_destroy(gs_dbexport *x);
+
+/* ---------------------------------------------------------------------------------------------------
  * match
  *
  * Replaces FastqKMerMatcher.runMatcher / matchRead (C/match/FastqKMerMatcher.java:181-235, :327-535)

@@ -108,6 +108,15 @@ int gs_host_filter_files(gs_bloom *bloom, int k, int min_pos_count, double posit
                          int n_paths, const char *filtered_path, const char *rest_path, int with_probs,
                          gs_host_totals *totals);
 
+/* ---- db2fastq (C/goals/DB2FastqGoal.java, C/fastqgen/KMerFastqGenerator.java): the stored k-mers selected as by
+ * gs_dbexport_create (sel_vi = -1: all -- the goal's "total" file; with_desc: the subtree of sel_vi -- a "taxid+" entry) written to
+ * `path` in ascending k-mer order, one FASTQ record each as FastQWriter prints it (gs_dbexport_fastq_begin; taxids[n_values] =
+ * SmallTaxIdNode.getTaxId per value index, project = the project name).  A name ending in .gz / .gzip is written as BGZF (gzip
+ * members + the EOF block) compressed by the device DEFLATE writer, else plain text; the text is made on the device and crosses
+ * to the host only as the file's bytes.  *n_written = records written. ---- */
+int gs_host_db2fastq(gs_db *db, const char *const *taxids, const char *project, int32_t sel_vi, int with_desc, const char *path,
+                     int64_t *n_written);
+
 /* ---- completeResults + CSV ---- */
 typedef struct {
     int32_t n_values;
