@@ -3062,7 +3062,10 @@ static size_t gs_stats_lds_bytes(int n_values) {
     return n_values <= GS_NV_TREE_LDS ? (size_t)n_values * 3 * 4 : 0;  // the tree alone
 }
 
-// GS_FORCE_GLOBAL_STATS=1 (developer knob): the kernels for stores with more values than the LDS counters hold, on any store
+// GS_FORCE_GLOBAL_STATS=1 (developer knob): the kernels for stores with more values than the LDS counters hold, on any store.
+// Read ONCE per process here (a static) but on every run by gs_match_begin (gs_api.cpp), which sizes the counters by it: set or
+// cleared after the first launch, the two disagree -- never change it inside a process (the tests reach these kernels through
+// real value counts instead)
 static bool gs_force_global_stats() {
     static const bool on = [] {
         const char *e = getenv("GS_FORCE_GLOBAL_STATS");

@@ -8,6 +8,7 @@ same for class_err), sorted by row and added with math.fsum (correctly rounded).
 summation lies within (n - 1) * 2^-53 * S of S (n = terms of the cell); the bound used is (n + 3) * 2^-53 * S, the + 3
 for how a device forms a term.  A cell without terms must be exactly 0.0.
 """
+import gzip
 import math
 
 import numpy as np
@@ -90,3 +91,103 @@ def check_match(o, g, what="match", ref=None):
     if o.get("dtable") is not None:
         check_dtable(o["terms"], nv, o["dtable"], what + " (oracle dtable)", ref=ref)
     return check_dtable(o["terms"], nv, g["dtable"], what, ref=ref)
+
+
+def sum_dtables(parts):
+    """the double tables of a result split over several runs (partition ranks, shards) added cell by cell in float64.
+    Every part holds sums of the same non-negative terms, so the total is one more summation tree over them: it stays
+    within (n - 1) * 2^-53 * S of the exact sum, and adding 0.0 is exact, so check_dtable's bound (n + 3) * 2^-53 * S
+    holds for the total unchanged -- a term left out of every part, or counted in two, still fails it."""
+    parts = [np.asarray(p, dtype=np.float64) for p in parts]
+    out = np.zeros_like(parts[0])
+    for p in parts:
+        assert p.shape == out.shape, (p.shape, out.shape)
+        out = out + p
+    return out
+
+
+ADD_COLS = [orc.C_READS, 1, 2, orc.C_UNIQUE_KMERS, 4, 5, 7, 8]  # the additive columns of the integer table
+
+
+def merge_tables(tables):
+    """the integer tables of runs over disjoint shards of the reads (DB-partitioned ranks: the unique counts of the partitions are
+    disjoint too) as one run gives it: additive columns added, the longest contig and its read number from the run that holds
+    the longest one (on ties the lowest read number)"""
+    out = np.zeros_like(tables[0])
+    for c in ADD_COLS:
+        out[:, c] = sum(t[:, c] for t in tables)
+    uq = np.stack([t[:, orc.C_UNIQUE_KMERS] for t in tables])
+    out[:, orc.C_UNIQUE_KMERS] = np.where(np.all(uq == -1, axis=0), -1, out[:, orc.C_UNIQUE_KMERS])  # (-1: not counted)
+    for v in range(out.shape[0]):
+        best = (0, -1)
+        for t in tables:
+            if t[v, 6] > best[0] or (t[v, 6] == best[0] and t[v, 6] > 0 and t[v, 9] < best[1]):
+                best = (int(t[v, 6]), int(t[v, 9]))
+        out[v, 6], out[v, 9] = best
+    return out
+
+
+def check_match_parts(o, parts, what="match", ref=None):
+    """check_match of a result split over runs: parts = the device results (dict(table, dtable, [class_vi, flags])) of each
+    run, in read order; tables merged (merge_tables), dtables added (sum_dtables), per-read outputs concatenated"""
+    g = dict(table=merge_tables([p["table"] for p in parts]), dtable=sum_dtables([p["dtable"] for p in parts]))
+    for key in ("class_vi", "flags"):
+        if all(p.get(key) is not None for p in parts):
+            g[key] = np.concatenate([np.asarray(p[key]) for p in parts])
+    return check_match(o, g, what, ref=ref)
+
+
+def _file_bytes(path):
+    data = open(path, "rb").read()
+    return gzip.decompress(data) if data[:2] == b"\x1f\x8b" else data  # (gzip and BGZF: members back to back)
+
+
+def oracle_files(odb, paths, threads=8, first_read_no=0, max_counts=False, **cfg):
+    """the oracle side of a file-level test: the records of `paths` (FASTQ, multi-line FASTQ or FASTA -- a file whose first byte
+    is '>' --, plain, gzip or BGZF) through one oracle run, in file order, read numbers running on over the files from
+    first_read_no.  Returns dict(table, dtable, terms, class_vi, flags, reads, kmers, bps[, max_counts]) for check_match."""
+    run = orc.MatchRun(odb, **cfg)
+    cvs, fls, terms = [], [], []
+    nr, nk, nb = 0, 0, 0
+    for path in paths:
+        data = _file_bytes(path)
+        p = orc.parse_fastq(data, fasta=data[:1] == b">", k=odb.k)
+        seq = p["seq"] if len(p["seq"]) else np.zeros(1, dtype=np.uint8)
+        cv, fl, te = run.submit_terms(seq, p["seq_off"], first_read_no + nr, threads=threads)
+        cvs.append(cv)
+        fls.append(fl)
+        terms.append(te)
+        nr, nk, nb = nr + int(p["n_reads"]), nk + int(p["total_kmers"]), nb + int(p["total_bps"])
+    t, d = run.finish()
+    o = dict(table=t, dtable=d, class_vi=np.concatenate(cvs) if cvs else np.zeros(0, np.int32),
+             flags=np.concatenate(fls) if fls else np.zeros(0, np.uint8),
+             terms=np.concatenate(terms) if terms else np.zeros((0, orc.N_TERMS), np.int32), reads=nr, kmers=nk, bps=nb)
+    if max_counts:
+        o["max_counts"] = run.max_counts()
+    run.close()
+    return o
+
+
+def oracle_batch(odb, seq, offsets, first_read_no=0, threads=8, max_counts=False, **cfg):
+    """one oracle run over one batch of reads: dict(table, dtable, terms, class_vi, flags[, max_counts]) for check_match"""
+    seq = np.asarray(seq, dtype=np.uint8)
+    run = orc.MatchRun(odb, **cfg)
+    cv, fl, terms = run.submit_terms(seq if len(seq) else np.zeros(1, dtype=np.uint8), offsets, first_read_no, threads=threads)
+    t, d = run.finish()
+    o = dict(table=t, dtable=d, class_vi=cv, flags=fl, terms=terms)
+    if max_counts:
+        o["max_counts"] = run.max_counts()
+    run.close()
+    return o
+
+
+def check_dtables_agree(a, b, n, what="dtables"):
+    """two device double tables over the same reads (summed in different orders, e.g. one batch against two): each cell is
+    within (n + 3) * 2^-53 * S of the same exact sum S, so they differ by at most 2 (n + 3) * 2^-53 * max(a, b); n = counted reads
+    per row (the READS column).  Cells of rows without counted reads must both be 0.0."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    assert a.shape == b.shape, (what, a.shape, b.shape)
+    n = np.asarray(n, dtype=np.float64)[:, None]
+    tol = 2.0 * (n + 3.0) * EPS * np.maximum(a, b)
+    bad = np.argwhere(np.abs(a - b) > tol)
+    assert bad.size == 0, f"{what}: {len(bad)} cells disagree, first (vi, col) {bad[0].tolist()}: {a[tuple(bad[0])]!r} vs {b[tuple(bad[0])]!r}"

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import genestrip_amd as ga
+import matchcheck
 from genestrip_amd import synth
 from conftest import GOLDEN
 from oracle import gs_oracle as orc
@@ -110,11 +111,11 @@ def test_device_build_reproduces_the_synthetic_store_and_serves_a_match():
     rs, ro = synth.reads_host(genomes, 4000, read_len=150, seed=9)
     m = ga.FastqKMerMatcher(store)
     m.submit(rs, ro.astype(np.uint64), 0)
-    table = m.finish()[0]
+    table, dtable = m.finish()
     odb = orc.DB(31, db.kmers, db.value_idx, db.n_values, db.parent_vi)
-    run = orc.MatchRun(odb)
-    run.submit(rs, ro, threads=8, per_read=False)
-    assert np.array_equal(table, run.finish()[0])
+    o = matchcheck.oracle_batch(odb, rs, ro)
+    assert np.array_equal(table, o["table"])
+    matchcheck.check_match(o, dict(table=table, dtable=dtable), "device-built arrays")
     m.close(), store.close(), odb.close()
 
 
@@ -135,12 +136,12 @@ def test_genomes_to_store_without_leaving_the_device():
     rs, ro = synth.reads_host(g, 4000, read_len=150, seed=9)
     m = ga.FastqKMerMatcher(store)
     m.submit(rs, ro.astype(np.uint64), 0)
-    table = m.finish()[0]
+    table, dtable = m.finish()
     m.close()
     odb = orc.DB(31, db.kmers, db.value_idx, db.n_values, db.parent_vi)
-    run = orc.MatchRun(odb)
-    run.submit(rs, ro, threads=8, per_read=False)
-    assert np.array_equal(table, run.finish()[0])
+    o = matchcheck.oracle_batch(odb, rs, ro)
+    assert np.array_equal(table, o["table"])
+    matchcheck.check_match(o, dict(table=table, dtable=dtable), "device-built store")
     odb.close()
     store.close()
 

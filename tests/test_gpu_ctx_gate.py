@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import genestrip_amd as ga
+import matchcheck
 from genestrip_amd import synth
 from oracle import gs_oracle as orc
 
@@ -14,12 +15,14 @@ pytestmark = pytest.mark.gpu
 def _check(store, db, k, seq, off, **cfg):
     m = ga.FastqKMerMatcher(store, ga.MatchConfig(**cfg))
     cv, fl = m.match_reads(seq, off)
-    t, _ = m.finish()
+    t, d = m.finish()
     m.close()
     orun = orc.MatchRun(orc.DB(k, db.kmers, db.value_idx, db.n_values, db.parent_vi), **cfg)
-    ocv, ofl = orun.submit(seq, off)
-    ot, _ = orun.finish()
+    ocv, ofl, oterms = orun.submit_terms(seq, off, threads=8)
+    ot, od = orun.finish()
     assert np.array_equal(t, ot) and np.array_equal(cv, ocv) and np.array_equal(fl, ofl)
+    matchcheck.check_match(dict(table=ot, dtable=od, class_vi=ocv, flags=ofl, terms=oterms),
+                           dict(table=t, dtable=d, class_vi=cv, flags=fl), f"k {k} {cfg}")
 
 
 @pytest.mark.parametrize("k", [31, 27, 22, 21])

@@ -7,8 +7,10 @@ import numpy as np
 import pytest
 
 import genestrip_amd as ga
+import matchcheck
 from genestrip_amd import host, synth
 from fastqgen import fastq_text, revcomp_np, stored_pairs, subtree
+from oracle import gs_oracle as orc
 
 pytestmark = pytest.mark.gpu
 
@@ -175,20 +177,26 @@ def test_export_during_a_unique_counting_run(sdb):
     seq, off = synth.reads_host(sdb.genomes, 6000, read_len=150, seed=41)
     seq2, off2 = synth.reads_host(sdb.genomes, 6000, read_len=150, seed=42)
     m = ga.FastqKMerMatcher(store)
-    m.match_reads(seq, off)
+    cv1, fl1 = m.match_reads(seq, off)
     during = store.export()  # seen bits are set in records and table now
     counts = store.value_counts()
-    m.match_reads(seq2, off2, first_read_no=6000)
-    t1, _ = m.finish()
+    cv2, fl2 = m.match_reads(seq2, off2, first_read_no=6000)
+    t1, d1 = m.finish()
     m.close()
     assert np.array_equal(during[0], before[0]) and np.array_equal(during[1], before[1])
     assert np.array_equal(counts, np.bincount(before[1], minlength=sdb.n_values))
     m2 = ga.FastqKMerMatcher(store)
     m2.match_reads(seq, off)
     m2.match_reads(seq2, off2, first_read_no=6000)
-    t2, _ = m2.finish()
+    t2, d2 = m2.finish()
     m2.close()
     assert t1[:, 3].sum() > 0 and np.array_equal(t1, t2)  # the unique column among them
+    odb = orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
+    both = (np.concatenate([seq, seq2]), np.concatenate([off, off[-1] + off2[1:]]))
+    o = matchcheck.oracle_batch(odb, *both)
+    for t, d in ((t1, d1), (t2, d2)):
+        matchcheck.check_match(o, dict(table=t, dtable=d, class_vi=np.concatenate([cv1, cv2]), flags=np.concatenate([fl1, fl2])),
+                               "export during the run")
     store.close()
 
 
@@ -236,6 +244,7 @@ def test_db2fastq_reads_match_back_to_their_taxid(sdb, tmp_path):
     for v in (int(sdb.species_vi[0]), int(genera[np.argmax(counts[genera])])):  # a leaf and the genus with the most k-mers
         p = tmp_path / f"v{v}.fastq"
         assert host.db2fastq(store, sdb.taxids, "proj", p, select=v, with_desc=False) == counts[v] > 0
+        # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
         table, _, tot = host.match_files(store, [str(p)])
         assert table[v, 2] == table[v, 3] == counts[v]  # kmers, unique kmers
         assert tot.reads == counts[v]

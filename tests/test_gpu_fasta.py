@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import genestrip_amd as ga
+import matchcheck
 from genestrip_amd import host, synth
 from oracle import gs_oracle as orc
 
@@ -40,16 +41,16 @@ def _fasta(sdb, n, seed, width=60, crlf=False):
 
 
 def _oracle(sdb, text, **cfg):
+    """(table, class, flags, parsed records, the whole oracle result for tests/matchcheck.py)"""
     rd = orc.parse_fastq(text, fasta=True, k=31)
-    run = orc.MatchRun(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), **cfg)
-    cv, fl = run.submit(rd["seq"], rd["seq_off"], threads=4)
-    return run.finish()[0], cv, fl, rd
+    o = matchcheck.oracle_batch(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), rd["seq"], rd["seq_off"], **cfg)
+    return o["table"], o["class_vi"], o["flags"], rd, o
 
 
 @pytest.mark.parametrize("seed,crlf", [(1, False), (2, False), (3, True)])
 def test_fasta_chunks_on_the_device(sdb, seed, crlf):
     text = _fasta(sdb, 3000, seed, crlf=crlf)
-    want, wcv, wfl, rd = _oracle(sdb, text)
+    want, wcv, wfl, rd, o = _oracle(sdb, text)
     n = rd["n_reads"]
     assert n == 3000
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
@@ -72,9 +73,10 @@ def test_fasta_chunks_on_the_device(sdb, seed, crlf):
     failed, bad, tot = m.text_status()
     assert failed == -1
     assert tot == (n, rd["total_kmers"], rd["total_bps"])
-    got, _ = m.finish()
+    got, gotd = m.finish()
     assert np.array_equal(got, want), np.argwhere(got != want)[:6]
     assert np.array_equal(cv, wcv) and np.array_equal(fl, wfl)
+    matchcheck.check_match(o, dict(table=got, dtable=gotd, class_vi=cv, flags=fl), "FASTA chunks")
     m.close()
     store.close()
 
@@ -123,19 +125,13 @@ def test_fasta_files_through_the_host_pipeline(sdb, tmp_path, monkeypatch, gz, b
         with (gzip.open(p, "wb", compresslevel=1) if gz else open(p, "wb")) as f:
             f.write(t)
         paths.append(p)
-    run = orc.MatchRun(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi))
-    reads = kmers = bps = 0
-    first = 0
-    for t in texts:
-        rd = orc.parse_fastq(t, fasta=True, k=31)
-        run.submit(rd["seq"], rd["seq_off"], first_read_no=first, threads=4, per_read=False)
-        first += rd["n_reads"]
-        reads, kmers, bps = reads + rd["n_reads"], kmers + rd["total_kmers"], bps + rd["total_bps"]
-    want, _ = run.finish()
+    o = matchcheck.oracle_files(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), paths)
+    want = o["table"]
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
-    table, _, tot = host.match_files(store, paths)
-    assert (tot.reads, tot.kmers, tot.bps) == (reads, kmers, bps)
+    table, dtable, tot = host.match_files(store, paths)
+    assert (tot.reads, tot.kmers, tot.bps) == (o["reads"], o["kmers"], o["bps"])
     assert np.array_equal(table, want), np.argwhere(table != want)[:6]
+    matchcheck.check_match(o, dict(table=table, dtable=dtable), "FASTA files")
     store.close()
 
 
@@ -166,6 +162,7 @@ def test_kraken_style_lines_of_fasta_files_from_the_device_path(sdb, tmp_path, m
         kr = str(tmp_path / ("k%s.out" % fast))
         fl = str(tmp_path / ("f%s.fastq" % fast))
         for write_all in (True, False):
+            # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
             table, _, tot = host.match_files(store, [str(p)], kraken_out_path=kr, filtered_path=fl, taxids=taxids, write_all=write_all,
                                              with_probs=write_all)
             outs[(fast, write_all)] = (open(kr, "rb").read(), table.copy(), tot.reads, open(fl, "rb").read(), tot.filtered_reads)

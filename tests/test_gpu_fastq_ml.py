@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import genestrip_amd as ga
+import matchcheck
 from genestrip_amd import host, synth
 from conftest import GOLDEN
 from oracle import gs_oracle as orc
@@ -51,17 +52,22 @@ def _multiline_fastq(sdb, n, seed, max_seq_lines=4, nasty=True):
     return b"".join(out)
 
 
-def _oracle_table(sdb, data):
+def _oracle_all(sdb, data):
+    """(the whole oracle result for tests/matchcheck.py, parsed records)"""
     rd = orc.parse_fastq(data, fasta=False, k=31)
-    run = orc.MatchRun(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi))
-    run.submit(rd["seq"], rd["seq_off"], threads=8, per_read=False)
-    return run.finish()[0], rd
+    return matchcheck.oracle_batch(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), rd["seq"], rd["seq_off"]), rd
+
+
+def _oracle_table(sdb, data):
+    o, rd = _oracle_all(sdb, data)
+    return o["table"], rd
 
 
 @pytest.mark.parametrize("piece", [1 << 30, 50_000, 7_001, 997])
 def test_multiline_chunks_against_the_parser_restatement(sdb, piece):
     data = _multiline_fastq(sdb, 3000, seed=5)
-    want, rd = _oracle_table(sdb, data)
+    o, rd = _oracle_all(sdb, data)
+    want = o["table"]
     assert rd["n_reads"] == 3000  # (the generator and the restatement agree on what a record is)
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
     m = ga.FastqKMerMatcher(store)
@@ -89,9 +95,10 @@ def test_multiline_chunks_against_the_parser_restatement(sdb, piece):
     m.sync()
     failed, bad, totals = m.text_status()
     assert failed < 0
-    table = m.finish()[0]
+    table, dtable = m.finish()
     assert done == 3000
     assert np.array_equal(table, want), np.argwhere(table != want)[:6]
+    matchcheck.check_match(o, dict(table=table, dtable=dtable), f"pieces of {piece}")
     m.close()
     store.close()
 
@@ -128,7 +135,8 @@ def test_multiline_fastq_files_go_through_the_device(sdb, tmp_path, monkeypatch,
     import gzip
     monkeypatch.setenv("GS_HOST_BLOCK_BYTES", str(1 << 16))  # many chunks, records across every block border
     data = _multiline_fastq(sdb, 6000, seed=9) + b"@last without a newline at the end\nACGTACGTAC\nGT\n+\nIIIIIIIIIIII"
-    want, rd = _oracle_table(sdb, data)
+    o, rd = _oracle_all(sdb, data)
+    want = o["table"]
     p = tmp_path / ("ml.fastq.gz" if gz else "ml.fastq")
     (gzip.open(p, "wb") if gz else open(p, "wb")).write(data)
     plain = tmp_path / "plain.fastq"  # a four-line file in the same call: the usual path, untouched
@@ -139,19 +147,25 @@ def test_multiline_fastq_files_go_through_the_device(sdb, tmp_path, monkeypatch,
             f.write(b"@p%d\n%s\n+\n%s\n" % (i, s, b"F" * len(s)))
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
     before = host.stat(0)
-    table, _, tot = host.match_files(store, [str(p)])
+    table, dtable, tot = host.match_files(store, [str(p)])
     assert host.stat(0) > before + 5  # chunks DID go through the device's record search
     assert np.array_equal(table, want), np.argwhere(table != want)[:6]
+    matchcheck.check_match(o, dict(table=table, dtable=dtable), "device record search")
     assert (tot.reads, tot.bps, tot.kmers) == (rd["n_reads"], int(rd["total_bps"]), int(rd["total_kmers"]))
     # the same through the reference-exact parser alone, and mixed with a four-line file
     monkeypatch.setenv("GS_HOST_ML", "0")
-    t2, _, tot2 = host.match_files(store, [str(p)])
+    t2, d2, tot2 = host.match_files(store, [str(p)])
     monkeypatch.delenv("GS_HOST_ML")
     assert np.array_equal(t2, want) and tot2.reads == tot.reads
+    matchcheck.check_match(o, dict(table=t2, dtable=d2), "parser alone")
     both = _oracle_table(sdb, data + b"\n" + open(plain, "rb").read())[0]
-    t3, _, tot3 = host.match_files(store, [str(p), str(plain)])
+    t3, d3, tot3 = host.match_files(store, [str(p), str(plain)])
     assert tot3.reads == rd["n_reads"] + 500
     assert np.array_equal(t3[:, [0, 1, 2, 3, 4, 5]], both[:, [0, 1, 2, 3, 4, 5]])
+    # (the double sums do not depend on read numbers: every counted read's terms, file by file)
+    o3 = matchcheck.oracle_files(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), [str(p), str(plain)])
+    assert np.array_equal(o3["table"][:, :6], both[:, :6])
+    matchcheck.check_dtable(o3["terms"], sdb.n_values, d3, "with a four-line file")
     store.close()
 
 
@@ -169,10 +183,12 @@ def test_kraken_style_lines_of_multiline_fastq_from_the_device_path(sdb, tmp_pat
         monkeypatch.setenv("GS_HOST_ML", ml)
         before = host.stat(0)
         kr = str(tmp_path / ("k%s.out" % ml))
+        # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
         table, _, tot = host.match_files(store, [str(p)], kraken_out_path=kr, taxids=taxids, write_all=True)
         outs[ml] = [open(kr, "rb").read(), table.copy(), tot.reads, host.stat(0) - before]
         for probs in (False, True):  # filtered reads, with '~' and with the record's own quality lines
             fl = str(tmp_path / ("f%s_%d.fastq" % (ml, probs)))
+            # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
             _, _, tot = host.match_files(store, [str(p)], filtered_path=fl, with_probs=probs)
             outs[ml] += [open(fl, "rb").read(), tot.filtered_reads]
     assert outs["1"][3] > 3 and outs["0"][3] == 0  # the device path did run (and did not with GS_HOST_ML=0)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import genestrip_amd as ga
+import matchcheck
 from genestrip_amd import host, synth
 from conftest import GOLDEN
 from oracle import gs_oracle as orc
@@ -43,27 +44,28 @@ def test_match_on_the_47m_kmer_store(big):
     assert info.table_bytes + info.rec_bytes >= 1 << 29  # HBM resident: beyond the 256 MiB Infinity Cache
     m = ga.FastqKMerMatcher(store)
     m.submit(dseq, doff, 0, n_reads=N_READS)
-    whole, _ = m.finish()
+    whole, whole_d = m.finish()
     # shards of uneven size with global read numbers: the table must not change (K4 of the reference, at size)
     m.reset()
     cuts = [0, 1, 700_001, 1_300_000, N_READS]
     for a, b in zip(cuts[:-1], cuts[1:]):
         m.submit(dseq, doff[a:].contiguous(), a, n_reads=b - a)
-    parts, _ = m.finish()
+    parts, parts_d = m.finish()
     assert np.array_equal(whole, parts)
+    matchcheck.check_dtables_agree(whole_d, parts_d, whole[:, orc.C_READS], "whole vs shards")
     # oracle (sorted array + Blocked-Bloom gate + binary search) on the first 100 k reads
     odb = orc.DB(31, db.kmers, db.value_idx, db.n_values, db.parent_vi, bloom_gate=True)
-    orun = orc.MatchRun(odb)
-    ocv, ofl = orun.submit(seq, off, threads=16)
-    ot, _ = orun.finish()
+    o = matchcheck.oracle_batch(odb, seq, off, threads=16)
+    ocv, ofl, ot = o["class_vi"], o["flags"], o["table"]
     m.reset()
     import torch
     cv = torch.empty(N_CHECK, dtype=torch.int32, device="cuda")
     fl = torch.empty(N_CHECK, dtype=torch.uint8, device="cuda")
     m.submit(dseq, doff, 0, n_reads=N_CHECK, class_vi=cv, flags=fl)
-    gt, _ = m.finish()
+    gt, gd = m.finish()
     assert np.array_equal(ot, gt)
     assert np.array_equal(cv.cpu().numpy(), ocv) and np.array_equal(fl.cpu().numpy(), ofl)
+    matchcheck.check_match(o, dict(table=gt, dtable=gd), "47 M store, checked sample")
     counts = np.bincount(db.value_idx, minlength=db.n_values)
     assert np.all(whole[:, 3] <= counts) and whole[:, 0].sum() > 0.4 * N_READS
     m.close()
@@ -78,7 +80,7 @@ def test_the_47m_kmer_store_striped_eight_ways(big):
     plain = ga.DeviceKMerStore(31, db.kmers, db.value_idx, db.n_values, db.parent_vi)
     m = ga.FastqKMerMatcher(plain)
     m.submit(dseq, doff, 0, n_reads=N_READS)
-    whole, _ = m.finish()
+    whole, whole_d = m.finish()
     m.close()
     pinfo = plain.info
     plain.close()
@@ -94,16 +96,17 @@ def test_the_47m_kmer_store_striped_eight_ways(big):
         r.submit(dseq, doff[a:].contiguous(), a, n_reads=b - a)
     binding.merge_runs(ms)
     for r in ms:
-        t, _ = r.finish()
+        t, d = r.finish()
         assert np.array_equal(t, whole), np.argwhere(t != whole)[:6]
+        matchcheck.check_dtables_agree(whole_d, d, whole[:, orc.C_READS], "plain store vs merged stripe runs")
     odb = orc.DB(31, db.kmers, db.value_idx, db.n_values, db.parent_vi, bloom_gate=True)
-    orun = orc.MatchRun(odb)
-    orun.submit(seq, off, threads=16, per_read=False)
-    ot, _ = orun.finish()
+    o = matchcheck.oracle_batch(odb, seq, off, threads=16)
+    ot = o["table"]
     ms[1].reset()
     ms[1].submit(dseq, doff, 0, n_reads=N_CHECK)
-    gt, _ = ms[1].finish()
+    gt, gd = ms[1].finish()
     assert np.array_equal(ot, gt)
+    matchcheck.check_match(o, dict(table=gt, dtable=gd), "8 stripes, checked sample")
     for r in ms:
         r.close()
     for s in stores:
@@ -171,11 +174,11 @@ def test_reference_sample_fastq_through_the_file_pipeline(tmp_path):
     table, dtable, tot = host.match_files(store, [path], kraken_out_path=kr, filtered_path=fq, taxids=taxids)
     assert (tot.reads, tot.bps, tot.kmers) == (6565, 658255, 461305)
     odb = orc.DB(31, keys, vals, 7, parent)
-    orun = orc.MatchRun(odb)
-    ocv, ofl = orun.submit(seq, off)
-    ot, _ = orun.finish()
+    o = matchcheck.oracle_batch(odb, seq, off)
+    ocv, ofl, ot = o["class_vi"], o["flags"], o["table"]
     assert ot[:, orc.C_KMERS].sum() > 50_000
     assert np.array_equal(table, ot)
+    matchcheck.check_match(o, dict(table=table, dtable=dtable), "file with outputs")
     desc = rd["desc"]
     doff_ = rd["desc_off"]
     names = {-1: "0", -2: "A"}
@@ -193,8 +196,9 @@ def test_reference_sample_fastq_through_the_file_pipeline(tmp_path):
     assert tot.filtered_reads == int((ofl & orc.F_RETURNED != 0).sum()) > 700
     assert open(fq).read().count("\n") == 4 * tot.filtered_reads
     # the same file again without per-read outputs (text mode end to end) and in sharded form must agree
-    table2, _, tot2 = host.match_files(store, [path])
+    table2, dtable2, tot2 = host.match_files(store, [path])
     assert np.array_equal(table2, ot) and (tot2.reads, tot2.bps, tot2.kmers) == (6565, 658255, 461305)
+    matchcheck.check_match(o, dict(table=table2, dtable=dtable2), "file in text mode")
     store.close()
 
 
@@ -223,26 +227,27 @@ def test_match_on_the_473m_kmer_store_built_on_the_device():
     synth.reads_device(gen, g.shape[0], g.shape[1], n, dseq, doff, seed=4242)
     m = ga.FastqKMerMatcher(store)
     m.submit(dseq, doff, 0, n_reads=n)
-    whole, _ = m.finish()
+    whole, whole_d = m.finish()
     m.reset()
     cuts = [0, 3, 1_500_001, n]
     for a, c in zip(cuts[:-1], cuts[1:]):
         m.submit(dseq, doff[a:].contiguous(), a, n_reads=c - a)
-    parts, _ = m.finish()
+    parts, parts_d = m.finish()
     assert np.array_equal(whole, parts)
+    matchcheck.check_dtables_agree(whole_d, parts_d, whole[:, orc.C_READS], "whole vs shards")
     seq, off = synth.reads_host(g, nchk, seed=4242)
     odb = orc.DB(31, kmers, vals, db.n_values, db.parent_vi)
-    orun = orc.MatchRun(odb)
-    ocv, ofl = orun.submit(seq, off, threads=16)
-    ot, _ = orun.finish()
+    o = matchcheck.oracle_batch(odb, seq, off, threads=16)
+    ocv, ofl, ot = o["class_vi"], o["flags"], o["table"]
     odb.close()
     m.reset()
     cv = torch.empty(nchk, dtype=torch.int32, device="cuda")
     fl = torch.empty(nchk, dtype=torch.uint8, device="cuda")
     m.submit(dseq, doff, 0, n_reads=nchk, class_vi=cv, flags=fl)
-    gt, _ = m.finish()
+    gt, gd = m.finish()
     assert np.array_equal(ot, gt)
     assert np.array_equal(cv.cpu().numpy(), ocv) and np.array_equal(fl.cpu().numpy(), ofl)
+    matchcheck.check_match(o, dict(table=gt, dtable=gd), "473 M store, checked sample")
     assert whole[:, 0].sum() > 0.4 * n
     m.close()
     store.close()

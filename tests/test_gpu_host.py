@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import genestrip_amd as ga
+import matchcheck
 from genestrip_amd import host, synth
 from conftest import GOLDEN
 from oracle import gs_oracle as orc
@@ -58,10 +59,10 @@ def test_match_files_two_inputs_table_kraken_filtered(sdb, tmp_path):
                                           batch_reads=1500)
     # oracle: same reads, global read numbers running over both files
     odb = orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
-    orun = orc.MatchRun(odb)
-    ocv, ofl = orun.submit(seq, off)
-    otable, _ = orun.finish()
+    o = matchcheck.oracle_batch(odb, seq, off)
+    ocv, ofl, otable = o["class_vi"], o["flags"], o["table"]
     assert np.array_equal(table, otable)
+    matchcheck.check_match(o, dict(table=table, dtable=dtable), "two files")
     assert (tot.reads, tot.kmers, tot.bps) == (7000, 7000 * 120, 7000 * 150)
     want = _oracle_kraken_lines(odb, sdb.taxids, seq, off, ocv)
     got = open(kr).read().rstrip("\n").split("\n")
@@ -85,6 +86,7 @@ def test_match_files_write_all_false_and_dengue_golden(tmp_path):
     junk.write_bytes(open(os.path.join(GOLDEN, "dengue1", "test.fastq"), "rb").read() +
                      b"@nohit\n" + b"ACGT" * 12 + b"\n+\n" + b"I" * 48 + b"\n@tiny\nACG\n+\nIII\n")
     kr = str(tmp_path / "k.out")
+    # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
     table, _, tot = host.match_files(store, [str(junk)], kraken_out_path=kr, taxids=["1"], write_all=False)
     assert open(kr).read() == open(os.path.join(GOLDEN, "dengue1", "test.out")).read()
     kr2 = str(tmp_path / "k2.out")
@@ -92,6 +94,7 @@ def test_match_files_write_all_false_and_dengue_golden(tmp_path):
     assert open(kr2).read().split("\n")[:2] == ["C\ttest\t1\t41\t0:2 1:7 0:2", "U\tnohit\t0\t48\t0:18"]
     assert tot.reads == 3 and table[0, 0] == 1
     # the reference's own FASTA fixture goes through the FASTA path (suffix) and every k-mer is found
+    # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
     t2, _, tot2 = host.match_files(store, [os.path.join(GOLDEN, "dengue1", "dengue1.fasta")])
     assert tot2.reads == 1 and tot2.bps == 10735 and t2[0, 2] == 10705 and t2[0, 3] == len(keys)
     store.close()
@@ -121,10 +124,8 @@ def _oracle_file(sdb, data):
     p = orc.parse_fastq(data, k=31)
     seq = p["seq"] if len(p["seq"]) else np.zeros(1, dtype=np.uint8)
     odb = orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
-    run = orc.MatchRun(odb)
-    run.submit(seq, p["seq_off"])
-    t, _ = run.finish()
-    return t, (int(p["n_reads"]), int(p["total_kmers"]), int(p["total_bps"]))
+    o = matchcheck.oracle_batch(odb, seq, p["seq_off"])
+    return o, (int(p["n_reads"]), int(p["total_kmers"]), int(p["total_bps"]))
 
 
 def _fastq_bytes(sdb, n, seed, nl=b"\n"):
@@ -162,16 +163,19 @@ def test_match_files_text_path_equals_reference_parser(sdb, tmp_path, monkeypatc
         data = b"".join(recs[:1])
     path = str(tmp_path / "in.fastq")
     open(path, "wb").write(data)
-    want_t, want_tot = _oracle_file(sdb, data)
+    o, want_tot = _oracle_file(sdb, data)
+    want_t = o["table"]
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
     if block:
         monkeypatch.setenv("GS_HOST_BLOCK_BYTES", str(block))
-    table, _, tot = host.match_files(store, [path])
+    table, dtable, tot = host.match_files(store, [path])
     assert (tot.reads, tot.kmers, tot.bps) == want_tot
     assert np.array_equal(table, want_t), np.argwhere(table != want_t)[:8]
+    matchcheck.check_match(o, dict(table=table, dtable=dtable), "text path")
     monkeypatch.setenv("GS_HOST_FAST", "0")
-    table2, _, tot2 = host.match_files(store, [path])
+    table2, dtable2, tot2 = host.match_files(store, [path])
     assert np.array_equal(table2, want_t) and (tot2.reads, tot2.kmers, tot2.bps) == want_tot
+    matchcheck.check_match(o, dict(table=table2, dtable=dtable2), "general parser")
     store.close()
 
 
@@ -184,10 +188,12 @@ def test_match_files_text_path_several_files_and_max_contig_order(sdb, tmp_path)
     with gzip.open(paths[1], "wb") as f:
         f.write(parts[1])
     open(paths[2], "wb").write(parts[2])
-    want_t, want_tot = _oracle_file(sdb, b"".join(parts))
+    o, want_tot = _oracle_file(sdb, b"".join(parts))
+    want_t = o["table"]
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
-    table, _, tot = host.match_files(store, paths)
+    table, dtable, tot = host.match_files(store, paths)
     assert np.array_equal(table, want_t)
+    matchcheck.check_match(o, dict(table=table, dtable=dtable), "three files")
     assert (tot.reads, tot.kmers, tot.bps) == want_tot
     store.close()
 
@@ -196,6 +202,7 @@ def test_match_files_empty_file(sdb, tmp_path):
     path = str(tmp_path / "empty.fastq")
     open(path, "wb").close()
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
+    # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
     table, _, tot = host.match_files(store, [path])
     assert tot.reads == 0 and not table[:, :9].any()
     store.close()
@@ -343,15 +350,18 @@ def test_match_files_gzip_files_side_by_side(sdb, tmp_path, monkeypatch, odd):
             with gzip.open(p, "wb", compresslevel=1 + i) as f:
                 f.write(part)
         paths.append(p)
-    want_t, want_tot = _oracle_file(sdb, b"".join(p + (b"\n" if odd and i == 1 else b"") for i, p in enumerate(parts)))
+    o, want_tot = _oracle_file(sdb, b"".join(p + (b"\n" if odd and i == 1 else b"") for i, p in enumerate(parts)))
+    want_t = o["table"]
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
     monkeypatch.setenv("GS_HOST_BLOCK_BYTES", str(70000))
-    t1, _, tot1 = host.match_files(store, paths)
+    t1, d1, tot1 = host.match_files(store, paths)
     monkeypatch.setenv("GS_HOST_PARALLEL_FILES", "0")
-    t0, _, tot0 = host.match_files(store, paths)
+    t0, d0, tot0 = host.match_files(store, paths)
     assert np.array_equal(t1, t0), np.argwhere(t1 != t0)[:8]
     assert (tot1.reads, tot1.kmers, tot1.bps) == (tot0.reads, tot0.kmers, tot0.bps) == want_tot
     assert np.array_equal(t0, want_t), np.argwhere(t0 != want_t)[:8]
+    matchcheck.check_match(o, dict(table=t1, dtable=d1), "gzip files side by side")
+    matchcheck.check_match(o, dict(table=t0, dtable=d0), "gzip files one by one")
     store.close()
 
 
@@ -377,6 +387,7 @@ def test_match_files_text_path_per_read_outputs(sdb, tmp_path, monkeypatch, bloc
         if block:
             monkeypatch.setenv("GS_HOST_BLOCK_BYTES", str(block))
         kr, fl = str(tmp_path / f"k{fast}.out"), str(tmp_path / f"f{fast}.fastq")
+        # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
         t, _, tot = host.match_files(store, [path], filtered_path=fl, kraken_out_path=kr, taxids=sdb.taxids, write_all=(block == 0))
         outs[fast] = (t, (tot.reads, tot.kmers, tot.bps, tot.filtered_reads), open(kr, "rb").read(), open(fl, "rb").read())
     assert np.array_equal(outs["1"][0], outs["0"][0])
@@ -394,6 +405,7 @@ def test_match_files_corrupt_gzip_is_an_error(sdb, tmp_path):
         f.write(data)
     raw = open(good, "rb").read()
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
+    # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
     t, _, tot = host.match_files(store, [good])
     assert tot.reads == 3000
     flipped = bytearray(raw)
@@ -435,9 +447,11 @@ def test_with_probs_keeps_the_quality_lines(sdb, tmp_path, monkeypatch, fast):
     keep = np.flatnonzero(ofl & orc.F_RETURNED)
     assert 500 < len(keep)
     flt = str(tmp_path / "f.fastq")
+    # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
     _, _, tot = host.match_files(store, [path], filtered_path=flt, with_probs=True)
     want = b"".join(b"@r%d\n" % i + reads[i] + b"\n+\n" + quals[i] + b"\n" for i in keep)
     assert open(flt, "rb").read() == want and tot.filtered_reads == len(keep)
+    # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
     _, _, tot = host.match_files(store, [path], filtered_path=flt)  # the default stays '~' x length
     want = b"".join(b"@r%d\n" % i + reads[i] + b"\n+\n" + b"~" * len(reads[i]) + b"\n" for i in keep)
     assert open(flt, "rb").read() == want
@@ -466,11 +480,13 @@ def test_bgzf_input_equals_plain_input(sdb, tmp_path):
     open(packed, "wb").write(bgzf(data))
     open(mixed, "wb").write(bgzf(data, eof_marker=False) + gzip.compress(more))
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
+    # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
     t0, _, tot0 = host.match_files(store, [plain], kraken_out_path=str(tmp_path / "k0"), taxids=sdb.taxids)
     t1, _, tot1 = host.match_files(store, [packed], kraken_out_path=str(tmp_path / "k1"), taxids=sdb.taxids)
     assert np.array_equal(t0, t1) and (tot0.reads, tot0.kmers, tot0.bps) == (tot1.reads, tot1.kmers, tot1.bps)
     assert open(str(tmp_path / "k0"), "rb").read() == open(str(tmp_path / "k1"), "rb").read()
     open(plain, "wb").write(data + more)
+    # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
     t2, _, tot2 = host.match_files(store, [plain])
     t3, _, tot3 = host.match_files(store, [mixed])
     assert np.array_equal(t2, t3) and tot2.reads == tot3.reads == 32000
@@ -490,6 +506,7 @@ def test_gzip_outputs_are_multi_member_and_round_trip(sdb, tmp_path):
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
     plain = dict(filtered_path=str(tmp_path / "f.fastq"), kraken_out_path=str(tmp_path / "k.out"))
     packed = dict(filtered_path=str(tmp_path / "f.fastq.gz"), kraken_out_path=str(tmp_path / "k.out.gz"))
+    # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
     t1, _, tot1 = host.match_files(store, [path], taxids=sdb.taxids, write_all=True, **plain)
     t2, _, tot2 = host.match_files(store, [path], taxids=sdb.taxids, write_all=True, **packed)
     assert np.array_equal(t1, t2) and tot1.filtered_reads == tot2.filtered_reads > 1000
@@ -500,6 +517,7 @@ def test_gzip_outputs_are_multi_member_and_round_trip(sdb, tmp_path):
         assert raw.endswith(bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000"))
         assert gzip.decompress(raw) == open(a, "rb").read()
         assert host.gunzip_parallel(raw, os.path.getsize(a), 4) == open(a, "rb").read()
+    # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
     t3, _, tot3 = host.match_files(store, [packed["filtered_path"]])
     assert tot3.reads == tot1.filtered_reads
     # nothing to write: still a valid (empty) gzip file
@@ -521,6 +539,7 @@ def test_output_write_failure_is_reported(sdb, tmp_path):
         host.match_files(store, [path], kraken_out_path="/dev/full", taxids=sdb.taxids, write_all=True)
     with pytest.raises(RuntimeError, match="write"):
         host.match_files(store, [path], filtered_path="/dev/full")
+    # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
     t, _, tot = host.match_files(store, [path])  # the store and the library are fine afterwards
     assert tot.reads == 5000
     store.close()
@@ -533,15 +552,17 @@ def test_match_files_few_blocks_many_readers(sdb, tmp_path, monkeypatch, readers
     data = b"".join(_fastq_bytes(sdb, 600, seed=47))
     path = str(tmp_path / "few.fastq")
     open(path, "wb").write(data)
-    want_t, want_tot = _oracle_file(sdb, data)
+    o, want_tot = _oracle_file(sdb, data)
+    want_t = o["table"]
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
     monkeypatch.setenv("GS_HOST_READERS", str(readers))
     for block in (len(data) // 5 + 7, len(data) // 2 + 3, len(data) + 100):
         monkeypatch.setenv("GS_HOST_BLOCK_BYTES", str(block))
         for _ in range(3):
-            t, _, tot = host.match_files(store, [path])
+            t, d, tot = host.match_files(store, [path])
             assert (tot.reads, tot.kmers, tot.bps) == want_tot
             assert np.array_equal(t, want_t)
+            matchcheck.check_match(o, dict(table=t, dtable=d), f"block {block}")
     store.close()
 
 
@@ -573,8 +594,10 @@ def test_refused_first_chunk_of_a_multi_batch_gz_while_its_upload_runs(sdb, tmp_
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
     monkeypatch.setenv("GS_GUNZIP_SLOTS", "16")        # 1 MiB of compressed data per batch: the upload outlives the first one
     monkeypatch.setenv("GS_HOST_GUNZIP_FIRST", "0")
+    # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
     table, _, tot = host.match_files(store, [path])
     monkeypatch.setenv("GS_DEVICE_INFLATE", "0")
+    # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
     want, _, tot2 = host.match_files(store, [path])
     assert tot.reads == n + 1 == tot2.reads and np.array_equal(table, want)
     # and the same file without the odd first record goes through the device decoder batch by batch
@@ -582,11 +605,10 @@ def test_refused_first_chunk_of_a_multi_batch_gz_while_its_upload_runs(sdb, tmp_
     z = zlib.compressobj(1, zlib.DEFLATED, 31)
     with open(path, "wb") as f:
         f.write(z.compress(text[len(first):]) + z.flush())
-    table2, _, tot3 = host.match_files(store, [path])
-    orun = orc.MatchRun(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi))
-    orun.submit(seq, off, threads=8, per_read=False)
-    otable, _ = orun.finish()
-    assert tot3.reads == n and np.array_equal(table2, otable)
+    table2, dtable2, tot3 = host.match_files(store, [path])
+    o = matchcheck.oracle_batch(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), seq, off)
+    assert tot3.reads == n and np.array_equal(table2, o["table"])
+    matchcheck.check_match(o, dict(table=table2, dtable=dtable2), "device decoder")
     store.close()
 
 
@@ -663,6 +685,7 @@ def test_match_filtered_fastq_written_from_the_device(sdb, tmp_path, monkeypatch
     for dev in ("0", "1"):
         monkeypatch.setenv("GS_DEVICE_OUTPUT", dev)
         f = str(tmp_path / f"flt{dev}.fastq.gz")
+        # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
         table, _, tot = host.match_files(store, [path], filtered_path=f)
         res[dev] = (table, tot.reads, tot.filtered_reads, gzip.decompress(open(f, "rb").read()))
     assert np.array_equal(res["0"][0], res["1"][0]) and res["0"][1:3] == res["1"][1:3] and 0 < res["1"][2] < 5000

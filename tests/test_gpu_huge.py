@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import genestrip_amd as ga
+import matchcheck
 from genestrip_amd import synth
 from oracle import gs_oracle as orc
 from test_gpu_match import _assert_same, _both
@@ -56,9 +57,8 @@ def test_many_reads_over_small_chunks(sdb, monkeypatch, chunk):
         _assert_same(o, g)
     # several submits of one run: the rows are clean again after every batch
     odb = orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
-    orun = orc.MatchRun(odb)
-    ocv, ofl = orun.submit(seq, off)
-    ot, _ = orun.finish()
+    o = matchcheck.oracle_batch(odb, seq, off)
+    ocv, ofl, ot = o["class_vi"], o["flags"], o["table"]
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
     m = ga.FastqKMerMatcher(store)
     at = 0
@@ -66,8 +66,9 @@ def test_many_reads_over_small_chunks(sdb, monkeypatch, chunk):
         cv, fl = m.match_reads(seq[int(off[at]):int(off[cut])], off[at:cut + 1] - off[at], at)
         assert np.array_equal(cv, ocv[at:cut]) and np.array_equal(fl, ofl[at:cut])
         at = cut
-    gt, _ = m.finish()
+    gt, gd = m.finish()
     assert np.array_equal(ot, gt)
+    matchcheck.check_match(o, dict(table=gt, dtable=gd), "several submits")
     m.close()
     store.close()
 
@@ -150,14 +151,14 @@ def test_chromosome_sized_record_in_a_fasta_file(sdb, tmp_path, gz):
     with (gzip.open(p, "wb", compresslevel=1) if gz else open(p, "wb")) as f:
         f.write(text)
     odb = orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
-    orun = orc.MatchRun(odb)
     seq, off = orc.pack_reads(recs)
-    ocv, _ = orun.submit(seq, off)
-    want, _ = orun.finish()
+    o = matchcheck.oracle_batch(odb, seq, off)
+    ocv, want = o["class_vi"], o["table"]
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
     kr = str(tmp_path / "kraken.out")
-    table, _, tot = host.match_files(store, [p], kraken_out_path=kr, taxids=sdb.taxids)
+    table, dtable, tot = host.match_files(store, [p], kraken_out_path=kr, taxids=sdb.taxids)
     assert np.array_equal(table, want) and tot.reads == len(recs) and tot.bps == sum(map(len, recs))
+    matchcheck.check_match(o, dict(table=table, dtable=dtable), "assembly file")
     names = {-1: "0", -2: "A"}
     lines = []
     for i, r in enumerate(recs):

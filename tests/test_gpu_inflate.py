@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import genestrip_amd as ga
+import matchcheck
 from conftest import GOLDEN, bgzf
 
 pytestmark = pytest.mark.gpu
@@ -258,15 +259,18 @@ def test_bgzf_files_through_the_device_inflater(tmp_path, monkeypatch, shape):
     path.write_bytes(bgzf(text, level=4))
     store = ga.DeviceKMerStore(31, db.kmers, db.value_idx, db.n_values, db.parent_vi)
     monkeypatch.setenv("GS_DEVICE_INFLATE", "1")
-    t_dev, _, tot_dev = host.match_files(store, [str(path)])
+    t_dev, d_dev, tot_dev = host.match_files(store, [str(path)])
     monkeypatch.setenv("GS_DEVICE_INFLATE", "0")
-    t_host, _, tot_host = host.match_files(store, [str(path)])
+    t_host, d_host, tot_host = host.match_files(store, [str(path)])
     assert np.array_equal(t_dev, t_host)
     assert (tot_dev.reads, tot_dev.kmers, tot_dev.bps) == (tot_host.reads, tot_host.kmers, tot_host.bps)
     if shape in ("plain", "small_feeds"):
-        orun = orc.MatchRun(orc.DB(31, db.kmers, db.value_idx, db.n_values, db.parent_vi))
-        orun.submit(seq, off, threads=8, per_read=False)
-        assert np.array_equal(t_dev, orun.finish()[0]) and tot_dev.reads == 30000
+        o = matchcheck.oracle_batch(orc.DB(31, db.kmers, db.value_idx, db.n_values, db.parent_vi), seq, off)
+        assert np.array_equal(t_dev, o["table"]) and tot_dev.reads == 30000
+        matchcheck.check_match(o, dict(table=t_dev, dtable=d_dev), "device inflater")
+        matchcheck.check_match(o, dict(table=t_host, dtable=d_host), "host inflater")
+    else:  # (the same text: the double sums of both decoders agree)
+        matchcheck.check_dtables_agree(d_dev, d_host, t_dev[:, orc.C_READS], "device vs host inflater")
     store.close()
 
 
@@ -289,6 +293,7 @@ def test_bgzf_files_with_per_read_outputs_through_the_device_inflater(tmp_path, 
     for dev in ("1", "0"):
         monkeypatch.setenv("GS_DEVICE_INFLATE", dev)
         fo, ko = tmp_path / f"filtered{dev}.fastq", tmp_path / f"kraken{dev}.txt"
+        # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
         t, _, tot = host.match_files(store, [str(path)], config=cfg, filtered_path=fo, kraken_out_path=ko, taxids=taxids)
         got[dev] = (t, (tot.reads, tot.kmers, tot.bps), fo.read_bytes(), ko.read_bytes())
     assert np.array_equal(got["1"][0], got["0"][0]) and got["1"][1] == got["0"][1]
@@ -534,6 +539,7 @@ def test_gzip_files_through_the_device_gunzip(tmp_path, monkeypatch, outputs, ba
         kw = {}
         if outputs:
             kw = dict(filtered_path=tmp_path / f"f{dev}.fastq", kraken_out_path=tmp_path / f"k{dev}.txt", taxids=[f"t{i}" for i in range(db.n_values)])
+        # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
         t, _, tot = host.match_files(store, [str(path)], **kw)
         files = tuple(open(p, "rb").read() for p in (kw.get("filtered_path"), kw.get("kraken_out_path")) if p)
         got[dev] = (t, (tot.reads, tot.kmers, tot.bps), files)
@@ -556,6 +562,7 @@ def test_two_gzip_members_in_one_file(tmp_path, monkeypatch):
     got = {}
     for dev in ("1", "0"):
         monkeypatch.setenv("GS_DEVICE_GUNZIP", dev)
+        # (reader / writer test: the match result is not its subject; the double table is held to the oracle elsewhere)
         t, _, tot = host.match_files(store, [str(path)])
         got[dev] = (t, (tot.reads, tot.kmers, tot.bps))
     assert np.array_equal(got["1"][0], got["0"][0]) and got["1"][1] == got["0"][1] and got["1"][1][0] == 9000

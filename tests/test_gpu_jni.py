@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import genestrip_amd as ga
+import matchcheck
 from genestrip_amd import host, synth
 from conftest import ROOT
 from oracle import gs_oracle as orc
@@ -111,11 +112,12 @@ def test_run_matcher_over_local_files_through_the_jni_shim(jni, sdb, tmp_path):
     for v in range(nv):
         r = int(table[v, ga.C_MAX_CONTIG_READ_NO]) if hasattr(ga, "C_MAX_CONTIG_READ_NO") else int(table[v, 9])
         assert names[v] == (b"read%d" % r if r >= 0 else b"")
-    # the oracle agrees with both
-    orun = orc.MatchRun(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi))
-    orun.submit(seq, off)
-    otable, _ = orun.finish()
-    assert np.array_equal(table, otable)
+    # the oracle agrees with both: the integer table, and the dtable buffer and totals the shim filled
+    o = matchcheck.oracle_files(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), paths)
+    assert np.array_equal(table, o["table"])
+    matchcheck.check_match(o, dict(table=table, dtable=dtable), "hostMatchFiles")
+    matchcheck.check_match(o, dict(table=want, dtable=wantd), "match_files")
+    assert [L.stub_long_array_get(totals, i) for i in range(3)] == [o["reads"], o["kmers"], o["bps"]]
     # hostMatchRun: into the matcher's own run (matchReset before, matchFinish after)
     m = ga.FastqKMerMatcher(store)
     descs2 = np.zeros((nv, 256), dtype=np.uint8)
@@ -123,8 +125,9 @@ def test_run_matcher_over_local_files_through_the_jni_shim(jni, sdb, tmp_path):
     getattr(L, PFX + "hostMatchRun")(L.stub_env(), None, m.h.value, store.h.value, _strings(L, paths), _str(L, f2), None, 1, _strings(L, sdb.taxids), 0,
                                      _buf(L, descs2), 256, totals)
     assert L.stub_take_exception() is None
-    t2, _ = m.finish()
+    t2, d2 = m.finish()
     assert np.array_equal(t2, want) and np.array_equal(descs2, descs)
+    matchcheck.check_match(o, dict(table=t2, dtable=d2), "hostMatchRun")
     assert gzip.decompress(open(f2, "rb").read()) == gzip.decompress(open(f0, "rb").read())
     # hostMatchInto: the files as files 0 and 1 of a sample
     m.reset()
@@ -134,12 +137,13 @@ def test_run_matcher_over_local_files_through_the_jni_shim(jni, sdb, tmp_path):
     getattr(L, PFX + "hostMatchInto")(L.stub_env(), None, m.h.value, store.h.value, _strings(L, paths), idx, rof, totals)
     assert L.stub_take_exception() is None
     assert [L.stub_long_array_get(rof, i) for i in range(2)] == [5000, 4000]
-    t3, _ = m.finish()
+    t3, d3 = m.finish()
     col = 9  # GS_C_MAX_CONTIG_READ_NO: (file << 32 | read) here
     conv = t3.copy()
     x = conv[:, col]
     conv[:, col] = np.where(x >= 0, (x >> 32) * 5000 + (x & 0xffffffff), x)
     assert np.array_equal(conv, want)
+    matchcheck.check_match(o, dict(table=conv, dtable=d3), "hostMatchInto")
     # a failure surfaces as the RuntimeException's message
     getattr(L, PFX + "hostMatchRun")(L.stub_env(), None, m.h.value, store.h.value, _strings(L, [str(tmp_path / "missing.fastq")]), None, None, 1, None, 0, None, 0, totals)
     msg = L.stub_take_exception()

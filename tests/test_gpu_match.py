@@ -193,15 +193,15 @@ def test_large_value_count_uses_global_counters(sdb):
 def test_multiple_submits_reset_and_device_batches(sdb):
     seq, off = synth.reads_host(sdb.genomes, 9000, read_len=150, seed=21)
     odb = orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
-    orun = orc.MatchRun(odb)
-    orun.submit(seq, off)
-    ot, _ = orun.finish()
+    o = matchcheck.oracle_batch(odb, seq, off)
+    ot = o["table"]
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
     m = ga.FastqKMerMatcher(store)
     for a, b in ((0, 3000), (3000, 3001), (3001, 9000)):  # host batches with rebased offsets
         m.submit(seq, off[a:b + 1].copy(), first_read_no=a, n_reads=b - a)
-    gt, _ = m.finish()
+    gt, gd = m.finish()
     assert np.array_equal(ot, gt)
+    matchcheck.check_match(o, dict(table=gt, dtable=gd), "host batches")
     m.reset()
     import torch
     dseq = torch.from_numpy(seq).cuda()
@@ -209,10 +209,11 @@ def test_multiple_submits_reset_and_device_batches(sdb):
     dcv = torch.empty(9000, dtype=torch.int32, device="cuda")
     dfl = torch.empty(9000, dtype=torch.uint8, device="cuda")
     m.submit(dseq, doff, 0, dcv, dfl, n_reads=9000)
-    gt2, _ = m.finish()
+    gt2, gd2 = m.finish()
     assert np.array_equal(ot, gt2)
     ocv, ofl = orc.MatchRun(odb).submit(seq, off)
     assert np.array_equal(dcv.cpu().numpy(), ocv) and np.array_equal(dfl.cpu().numpy(), ofl)
+    matchcheck.check_match(o, dict(table=gt2, dtable=gd2, class_vi=dcv.cpu().numpy(), flags=dfl.cpu().numpy()), "device batch")
     m.close()
     store.close()
 
@@ -230,25 +231,26 @@ def test_full_size_properties():
     synth.reads_device(gen, db.genomes.shape[0], db.genomes.shape[1], n, dseq, doff, seed=4242)
     m = ga.FastqKMerMatcher(store)
     m.submit(dseq, doff, 0, n_reads=n)
-    whole, _ = m.finish()
+    whole, whole_d = m.finish()
     m.reset()
     h = n // 2
     m.submit(dseq, doff, 0, n_reads=h)
     doff2 = doff[h:].contiguous()
     m.submit(dseq, doff2, h, n_reads=n - h)
-    parts, _ = m.finish()
+    parts, parts_d = m.finish()
     assert np.array_equal(whole, parts)
+    matchcheck.check_dtables_agree(whole_d, parts_d, whole[:, orc.C_READS], "whole vs two halves")
     # oracle spot check on the first 20k reads of the same stream
     seq, off = synth.reads_host(db.genomes, 20000, seed=4242)
     assert np.array_equal(dseq[:20000 * 150].cpu().numpy(), seq)
     odb = orc.DB(31, db.kmers, db.value_idx, db.n_values, db.parent_vi)
-    orun = orc.MatchRun(odb)
-    orun.submit(seq, off, threads=8)
-    ot, _ = orun.finish()
+    o = matchcheck.oracle_batch(odb, seq, off)
+    ot = o["table"]
     m.reset()
     m.submit(dseq, doff, 0, n_reads=20000)
-    gt, _ = m.finish()
+    gt, gd = m.finish()
     assert np.array_equal(ot, gt)
+    matchcheck.check_match(o, dict(table=gt, dtable=gd), "first 20k reads")
     counts = np.bincount(db.value_idx, minlength=db.n_values)
     assert np.all(whole[:, 3] <= counts) and whole[:, 3].sum() > 0.5 * db.n_entries
     assert whole[:, 0].sum() <= n and whole[:, 7].sum() >= whole[:, 0].sum()
@@ -263,17 +265,17 @@ def test_max_kmer_res_counts(sdb):
     hot = seq[:150].copy()
     seq = np.concatenate([seq, np.tile(hot, 40000)])
     off = np.concatenate([off, off[-1] + 150 * np.arange(1, 40001, dtype=np.uint64)])
-    o = orc.MatchRun(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), max_kmer_res_counts=5)
-    o.submit(seq, off, threads=4)
-    ot, _ = o.finish()
-    want = o.max_counts()
+    o = matchcheck.oracle_batch(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), seq, off, max_counts=True,
+                                max_kmer_res_counts=5)
+    ot, want = o["table"], o["max_counts"]
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
     m = ga.FastqKMerMatcher(store, ga.MatchConfig(max_kmer_res_counts=5))
     m.submit(seq, off, 0, n_reads=len(off) - 1)
-    gt, _ = m.finish()
+    gt, gd = m.finish()
     got = m.max_counts()
     assert np.array_equal(ot, gt)
     assert np.array_equal(want, got), (want[-1], got[-1])
+    matchcheck.check_match(o, dict(table=gt, dtable=gd, max_counts=got), "max counts")
     assert got[-1, 0] > 0
     m.close()
     m2 = ga.FastqKMerMatcher(store)
@@ -292,9 +294,8 @@ def test_async_host_batches_equal_the_synchronous_ones(pinned):
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
     seq, off = synth.reads_host(sdb.genomes, 9000, seed=77)
     off = off.astype(np.uint64)
-    run = orc.MatchRun(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi))
-    want_cv, want_fl = run.submit(seq, off)
-    want_t, _ = run.finish()
+    want_o = matchcheck.oracle_batch(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), seq, off)
+    want_cv, want_fl, want_t = want_o["class_vi"], want_o["flags"], want_o["table"]
 
     def hold(a):  # page-locked copies are what a C / Java host gets from gs_pinned_alloc
         return torch.from_numpy(a.copy()).pin_memory().numpy() if pinned else a.copy()
@@ -315,10 +316,11 @@ def test_async_host_batches_equal_the_synchronous_ones(pinned):
             pa, pb = cuts[len(tickets) - 2], cuts[len(tickets) - 1]
             assert np.array_equal(keep[-2][2], want_cv[pa:pb]) and np.array_equal(keep[-2][3], want_fl[pa:pb])
     m.wait(tickets[-1])
-    got_t, _ = m.finish()
+    got_t, got_d = m.finish()
     assert np.array_equal(got_t, want_t)
     assert np.array_equal(np.concatenate([k[2] for k in keep]), want_cv)
     assert np.array_equal(np.concatenate([k[3] for k in keep]), want_fl)
+    matchcheck.check_match(want_o, dict(table=got_t, dtable=got_d), "async batches")
     with pytest.raises(ga.GsError):
         m.wait(99)
     m.close()
@@ -341,12 +343,12 @@ def test_max_contig_reads_captured_per_batch_equal_the_final_answer(sdb):
         now = m.max_contig_reads()
         inside = (now >= a) & (now < b)
         captured[inside] = now[inside]
-    table, _ = m.finish()
+    table, dtable = m.finish()
     assert np.array_equal(captured, table[:, 9])
     assert (captured >= 0).sum() >= 5
-    orun = orc.MatchRun(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi))
-    orun.submit(seq, off, threads=4, per_read=False)
-    assert np.array_equal(orun.finish()[0], table)
+    o = matchcheck.oracle_batch(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), seq, off)
+    assert np.array_equal(o["table"], table)
+    matchcheck.check_match(o, dict(table=table, dtable=dtable), "batches with empty ones")
     m.close()
     store.close()
 
@@ -382,16 +384,17 @@ def test_many_long_reads_between_short_ones(sdb, monkeypatch, blocks_per_cu):
         _assert_same(o, g)
     # two submits of one run (the queue starts over with each), short-only batch in between
     odb = orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
-    orun = orc.MatchRun(odb)
-    orun.submit(seq, off)
-    ot, _ = orun.finish()
+    o = matchcheck.oracle_batch(odb, seq, off)
+    ot = o["table"]
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
     m = ga.FastqKMerMatcher(store)
     cut = 9000
-    m.match_reads(seq[:int(off[cut])], off[:cut + 1], 0)
-    m.match_reads(seq[int(off[cut]):], off[cut:] - off[cut], cut)
-    gt, _ = m.finish()
+    cv0, fl0 = m.match_reads(seq[:int(off[cut])], off[:cut + 1], 0)
+    cv1, fl1 = m.match_reads(seq[int(off[cut]):], off[cut:] - off[cut], cut)
+    gt, gd = m.finish()
     assert np.array_equal(ot, gt)
+    matchcheck.check_match(o, dict(table=gt, dtable=gd, class_vi=np.concatenate([cv0, cv1]), flags=np.concatenate([fl0, fl1])),
+                           "two submits")
     m.close()
     store.close()
 
@@ -408,15 +411,18 @@ def test_fixed_length_batches_without_offsets(sdb):
         seq[::977] = ord("N")
         m.reset()
         cv, fl = m.match_reads(seq, off)
-        want, _ = m.finish()
+        want, want_d = m.finish()
+        o = matchcheck.oracle_batch(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), seq, off)
+        matchcheck.check_match(o, dict(table=want, dtable=want_d, class_vi=cv, flags=fl), f"L {L} with offsets")
         for dev in (False, True):
             m.reset()
             s = torch.from_numpy(seq).cuda() if dev else seq
             c2 = torch.empty(n, dtype=torch.int32, device="cuda") if dev else np.zeros(n, dtype=np.int32)
             f2 = torch.empty(n, dtype=torch.uint8, device="cuda") if dev else np.zeros(n, dtype=np.uint8)
             m.submit_fixed(s, L, n, class_vi=c2, flags=f2)
-            got, _ = m.finish()
+            got, got_d = m.finish()
             assert np.array_equal(got, want), (L, dev)
+            matchcheck.check_match(o, dict(table=got, dtable=got_d), f"L {L} fixed (device memory {dev})")
             assert np.array_equal(c2.cpu().numpy() if dev else c2, cv) and np.array_equal(f2.cpu().numpy() if dev else f2, fl), (L, dev)
     m.close()
     store.close()

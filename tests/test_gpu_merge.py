@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import genestrip_amd as ga
+import matchcheck
 from genestrip_amd import binding, host, synth
 from oracle import gs_oracle as orc
 
@@ -17,10 +18,16 @@ def sdb():
     return synth.SynthDB(k=31, genera=3, species_per_genus=3, genome_len=20000, seed=11)
 
 
-def _oracle(sdb, seq, off, **cfg):
+def _oracle_all(sdb, seq, off, **cfg):
+    """the oracle's whole result for tests/matchcheck.py"""
     run = orc.MatchRun(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), **cfg)
-    run.submit(seq, off, threads=8, per_read=False)
-    return run.finish()[0]
+    cv, fl, terms = run.submit_terms(seq, off, 0, threads=8)
+    t, d = run.finish()
+    return dict(table=t, dtable=d, class_vi=cv, flags=fl, terms=terms)
+
+
+def _oracle(sdb, seq, off, **cfg):
+    return _oracle_all(sdb, seq, off, **cfg)["table"]
 
 
 @pytest.mark.parametrize("n_runs,force_rccl,cfg", [(1, False, {}), (3, False, {}), (2, True, {}), (1, True, {}),
@@ -31,21 +38,24 @@ def test_runs_of_one_process_merge_to_the_single_run_table(sdb, monkeypatch, n_r
     seq, off = synth.reads_host(sdb.genomes, 12000, read_len=150, seed=5)
     off = off.astype(np.uint64)
     # a tie for the longest contig between the shards: the same read at the start of every shard (first read number wins)
-    want = _oracle(sdb, seq, off, **cfg)
+    o = _oracle_all(sdb, seq, off, **cfg)
+    want = o["table"]
     stores = [ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi) for _ in range(n_runs)]
     ms = [ga.FastqKMerMatcher(s, ga.MatchConfig(**cfg)) for s in stores]
     cuts = np.linspace(0, 12000, n_runs + 1).astype(int)
     for m, a, b in zip(ms, cuts[:-1], cuts[1:]):
         m.submit(seq[int(off[a]):int(off[b])], off[a:b + 1] - off[a], int(a), n_reads=int(b - a))
     binding.merge_runs(ms)
-    tables = [m.finish()[0] for m in ms]
-    for t in tables:  # every run holds the global state
+    for i, m in enumerate(ms):  # every run holds the global state, the double table (f64 merge) included
+        t, d = m.finish()
         assert np.array_equal(t, want), np.argwhere(t != want)[:6]
+        matchcheck.check_match(o, dict(table=t, dtable=d), f"run {i} of {n_runs} (RCCL {force_rccl})")
     # merging is not a one-shot: a reset run starts from zero again
     ms[0].reset()
-    ms[0].submit(seq[:int(off[100])], off[:101], 0, n_reads=100)
-    again = ms[0].finish()[0]
-    assert np.array_equal(again, _oracle(sdb, seq[:int(off[100])], off[:101], **cfg))
+    cv, fl = ms[0].match_reads(seq[:int(off[100])], off[:101], 0)
+    t, d = ms[0].finish()
+    matchcheck.check_match(_oracle_all(sdb, seq[:int(off[100])], off[:101], **cfg), dict(table=t, dtable=d, class_vi=cv, flags=fl),
+                           "after reset")
     for m in ms:
         m.close()
     for s in stores:
@@ -83,12 +93,15 @@ def test_files_over_several_replicas_of_one_process(sdb, tmp_path, n_replicas):
         p = str(tmp_path / f"s{i}.fastq")
         _write_fastq(p, seq[int(off[a]):int(off[b])], off[a:b + 1] - off[a], a)
         paths.append(p)
-    want = _oracle(sdb, seq, off)
+    o = _oracle_all(sdb, seq, off)
+    want = o["table"]
     stores = [ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi) for _ in range(n_replicas)]
-    table, _, tot = host.match_files_multi(stores, paths)
+    table, dtable, tot = host.match_files_multi(stores, paths)
     assert (tot.reads, tot.bps, tot.kmers) == (15000, 15000 * 150, 15000 * 120)
     assert np.array_equal(table, want), np.argwhere(table != want)[:6]
-    single, _, _ = host.match_files(stores[0], paths)
+    matchcheck.check_match(o, dict(table=table, dtable=dtable), f"{n_replicas} replicas")
+    single, sd, _ = host.match_files(stores[0], paths)
     assert np.array_equal(single, want)
+    matchcheck.check_match(o, dict(table=single, dtable=sd), "one replica")
     for s in stores:
         s.close()

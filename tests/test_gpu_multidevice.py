@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import genestrip_amd as ga
+import matchcheck
 from genestrip_amd import binding, host, synth
 from oracle import gs_oracle as orc
 
@@ -25,9 +26,8 @@ def sdb():
 
 
 def _oracle(sdb, seq, off, **cfg):
-    run = orc.MatchRun(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), **cfg)
-    run.submit(seq, off, threads=8, per_read=False)
-    return run.finish()[0]
+    """the oracle's whole result for tests/matchcheck.py"""
+    return matchcheck.oracle_batch(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), seq, off, **cfg)
 
 
 def _devices():
@@ -41,16 +41,18 @@ def test_runs_on_distinct_devices_merge_over_rccl(sdb, cfg):
     n = 4000 * len(devs)
     seq, off = synth.reads_host(sdb.genomes, n, read_len=150, seed=5)
     off = off.astype(np.uint64)
-    want = _oracle(sdb, seq, off, **cfg)
+    o = _oracle(sdb, seq, off, **cfg)
+    want = o["table"]
     stores = [ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi, device=d) for d in devs]
     ms = [ga.FastqKMerMatcher(s, ga.MatchConfig(**cfg)) for s in stores]
     cuts = np.linspace(0, n, len(devs) + 1).astype(int)
     for m, a, b in zip(ms, cuts[:-1], cuts[1:]):
         m.submit(seq[int(off[a]):int(off[b])], off[a:b + 1] - off[a], int(a), n_reads=int(b - a))
     binding.merge_runs(ms)
-    for m in ms:
-        t = m.finish()[0]
+    for i, m in enumerate(ms):
+        t, d = m.finish()
         assert np.array_equal(t, want), np.argwhere(t != want)[:6]
+        matchcheck.check_match(o, dict(table=t, dtable=d), f"run on device {devs[i]}")
     for m in ms:
         m.close()
     for s in stores:
@@ -83,11 +85,13 @@ def test_files_dealt_to_replicas_on_distinct_devices(sdb, tmp_path, container):
             p += ".gz"
             open(p, "wb").write(gzip.compress(raw, 6, mtime=0) if container == "gzip" else bgzf(raw, block=30000, level=1))
         paths.append(p)
-    want = _oracle(sdb, seq, off)
+    o = _oracle(sdb, seq, off)
+    want = o["table"]
     stores = [ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi, device=d) for d in devs]
-    table, _, tot = host.match_files_multi(stores, paths)
+    table, dtable, tot = host.match_files_multi(stores, paths)
     assert (tot.reads, tot.bps, tot.kmers) == (15000, 15000 * 150, 15000 * 120)
     assert np.array_equal(table, want), np.argwhere(table != want)[:6]
+    matchcheck.check_match(o, dict(table=table, dtable=dtable), f"files over {len(devs)} devices")
     for s in stores:
         s.close()
 
@@ -110,9 +114,11 @@ def test_striped_store_over_distinct_devices_reads_foreign_lines_by_peer_access(
         ocv, ofl = orun.submit(sl, so, first_read_no=int(a))
         assert np.array_equal(cv, ocv) and np.array_equal(fl, ofl)
     binding.merge_runs(ms)
-    want = _oracle(sdb, seq, off)
+    o = _oracle(sdb, seq, off)
     for m in ms:
-        assert np.array_equal(m.finish()[0], want)
+        t, d = m.finish()
+        assert np.array_equal(t, o["table"])
+        matchcheck.check_match(o, dict(table=t, dtable=d), "merged")
     for m in ms:
         m.close()
     for s in stores:

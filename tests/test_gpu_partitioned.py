@@ -9,12 +9,12 @@ import pytest
 import torch
 
 import genestrip_amd as ga
+import matchcheck
 from genestrip_amd import distributed as gd
 from genestrip_amd import synth
 from oracle import gs_oracle as orc
 
 pytestmark = pytest.mark.gpu
-ADD = [0, 1, 2, 3, 4, 5, 7, 8]  # additive columns (unique counts of the partitions are disjoint)
 
 
 @pytest.fixture(scope="module")
@@ -39,23 +39,11 @@ def _reads(sdb, n):
 
 
 def _oracle(sdb, seq, off, **cfg):
+    """the oracle's whole result (tests/matchcheck.py) and, as before, (table, class, flags)"""
     run = orc.MatchRun(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), **cfg)
-    cv, fl = run.submit(seq, off)
-    t, _ = run.finish()
-    return t, cv, fl
-
-
-def _merge_tables(tables):
-    out = np.zeros_like(tables[0])
-    for c in ADD:
-        out[:, c] = sum(t[:, c] for t in tables)
-    for v in range(out.shape[0]):
-        best = (0, -1)
-        for t in tables:
-            if t[v, 6] > best[0] or (t[v, 6] == best[0] and t[v, 6] > 0 and t[v, 9] < best[1]):
-                best = (int(t[v, 6]), int(t[v, 9]))
-        out[v, 6], out[v, 9] = best
-    return out
+    cv, fl, terms = run.submit_terms(seq, off, 0, threads=8)
+    t, d = run.finish()
+    return dict(table=t, dtable=d, class_vi=cv, flags=fl, terms=terms), t, cv, fl
 
 
 @pytest.mark.parametrize("device_routing", [True, False])
@@ -63,7 +51,7 @@ def _merge_tables(tables):
 def test_partitioned_pipeline_emulated(sdb, world, device_routing):
     seq, off = _reads(sdb, 6000)
     n = len(off) - 1
-    want, wcv, wfl = _oracle(sdb, seq, off)
+    whole, want, wcv, wfl = _oracle(sdb, seq, off)
     dev = torch.device("cuda")
     stores = [ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi, n_parts=world, part=p, partition=True)
               for p in range(world)]
@@ -113,7 +101,7 @@ def test_partitioned_pipeline_emulated(sdb, world, device_routing):
             c = int(plans[i][4][j])
             node_back[i][j] = nodes[o:o + c]
             o += c
-    tables, cvs, fls = [], [], []
+    parts = []
     for r, (dseq, doff, nr, lo) in enumerate(shard):
         pos_off, nk, idx, _, _, keys, early = plans[r]
         back = torch.cat(node_back[r])
@@ -126,13 +114,12 @@ def test_partitioned_pipeline_emulated(sdb, world, device_routing):
         cv = torch.full((max(nr, 1),), -1, dtype=torch.int32, device=dev)
         fl = torch.zeros(max(nr, 1), dtype=torch.uint8, device=dev)
         ms[r].reduce(dseq, doff, pos_off, nodes, nr, first_read_no=lo, class_vi=cv, flags=fl)
-        t, _ = ms[r].finish()
-        tables.append(t)
-        cvs.append(cv[:nr].cpu().numpy())
-        fls.append(fl[:nr].cpu().numpy())
-    got = _merge_tables(tables)
+        t, d = ms[r].finish()
+        parts.append(dict(table=t, dtable=d, class_vi=cv[:nr].cpu().numpy(), flags=fl[:nr].cpu().numpy()))
+    # the ranks' tables merged, their double tables added (matchcheck.sum_dtables), class and flags in read order
+    got = matchcheck.merge_tables([p["table"] for p in parts])
     assert np.array_equal(got, want), np.argwhere(got != want)[:8]
-    assert np.array_equal(np.concatenate(cvs), wcv) and np.array_equal(np.concatenate(fls), wfl)
+    matchcheck.check_match_parts(whole, parts, f"world {world}")
     for m in ms:
         m.close()
     for s in stores:
@@ -149,7 +136,7 @@ def test_partitioned_collective_path_single_rank(sdb):
     try:
         seq, off = _reads(sdb, 3000)
         n = len(off) - 1
-        want, wcv, wfl = _oracle(sdb, seq, off)
+        o, want, wcv, wfl = _oracle(sdb, seq, off)
         store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi, n_parts=1, part=0, partition=True)
         m = ga.FastqKMerMatcher(store)
         dseq = torch.from_numpy(seq).to(dev)
@@ -165,9 +152,10 @@ def test_partitioned_collective_path_single_rank(sdb):
         sums = torch.as_tensor(V(st["sums"], sdb.n_values * ga.N_SUMS, "<i8"), device=dev)
         mx = torch.as_tensor(V(st["max_keys"], sdb.n_values, "<i8"), device=dev)
         ds = torch.as_tensor(V(st["dsums"], sdb.n_values * ga.N_DCOLS, "<f8"), device=dev)
-        table, _ = gd.partitioned_finish(m, sums, mx, ds)
+        table, dtable = gd.partitioned_finish(m, sums, mx, ds)
         assert np.array_equal(table, want)
         assert np.array_equal(cv.cpu().numpy(), wcv) and np.array_equal(fl.cpu().numpy(), wfl)
+        matchcheck.check_match(o, dict(table=table, dtable=dtable, class_vi=cv.cpu().numpy(), flags=fl.cpu().numpy()), "RCCL")
         m.close()
         store.close()
     finally:
@@ -259,7 +247,7 @@ def test_partitioned_batch_fused_unfused_and_overflow_fallback(sdb):
     try:
         seq, off = _reads(sdb, 3000)
         n = len(off) - 1
-        want, wcv, wfl = _oracle(sdb, seq, off)
+        o, want, wcv, wfl = _oracle(sdb, seq, off)
         store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi, n_parts=1, part=0, partition=True)
         dseq = torch.from_numpy(seq).to(dev)
         doff = torch.from_numpy(off.astype(np.int64)).to(dev)
@@ -276,9 +264,10 @@ def test_partitioned_batch_fused_unfused_and_overflow_fallback(sdb):
             assert gd.ROUTE_OVERFLOWS[0] - fell_back == (1 if how == "overflow" else 0), how
             waves, chunk = m.route_geometry(n)
             assert chunk == gd.ROUTE_CHUNK and waves % 4 == 0 and 4 <= waves <= torch.cuda.get_device_properties(dev).multi_processor_count * 32
-            table, _ = m.finish()
+            table, dtable = m.finish()
             assert np.array_equal(table, want), how
             assert np.array_equal(cv.cpu().numpy(), wcv) and np.array_equal(fl.cpu().numpy(), wfl), how
+            matchcheck.check_match(o, dict(table=table, dtable=dtable, class_vi=cv.cpu().numpy(), flags=fl.cpu().numpy()), how)
             m.close()
         store.close()
     finally:

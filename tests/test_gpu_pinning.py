@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import genestrip_amd as ga
+import matchcheck
 from genestrip_amd import synth
 from oracle import gs_oracle as orc
 
@@ -47,21 +48,23 @@ def test_store_filled_in_radix_visit_order(n_values, radix_bits):
     res = []
     for odb in (rdb, orc.DB(31, db.kmers, vals, n_values, parent, True)):
         run = orc.MatchRun(odb, **cfg)
-        cv, fl = run.submit(seq, off, threads=8)
+        cv, fl, terms = run.submit_terms(seq, off, threads=8)
         mc = run.max_counts()
-        res.append((run.finish()[0], cv, fl, mc))
+        t, d = run.finish()
+        res.append((t, cv, fl, mc, dict(table=t, dtable=d, class_vi=cv, flags=fl, terms=terms, max_counts=mc)))
     store = ga.DeviceKMerStore(31, vk, vv, n_values, parent)
     assert store.info.n_stored == len(vk)
     m = ga.FastqKMerMatcher(store, ga.MatchConfig(**cfg))
     gcv, gfl = m.match_reads(seq, off)
     gmc = m.max_counts()
-    gt, _ = m.finish()
+    gt, gd = m.finish()
     m.close()
     store.close()
     assert res[0][0][:, orc.C_KMERS].sum() > 300000
     for want in res:
         assert np.array_equal(gt, want[0]) and np.array_equal(gcv, want[1]) and np.array_equal(gfl, want[2])
         assert np.array_equal(gmc, want[3])
+        matchcheck.check_match(want[4], dict(table=gt, dtable=gd, class_vi=gcv, flags=gfl, max_counts=gmc), f"{n_values} values")
 
 
 def test_duplicate_kmers_are_refused_in_any_order():
@@ -84,12 +87,12 @@ def test_up_to_128_classification_paths(max_paths, threshold, fan):
     seq, off = _mixed_reads(db.genomes, 3000, 33)
     cfg = dict(max_paths=max_paths, threshold=threshold, max_read_class_err=0.95)
     orun = orc.MatchRun(orc.DB(31, db.kmers, vals, n_values, parent), **cfg)
-    ocv, ofl = orun.submit(seq, off, threads=8)
-    ot, _ = orun.finish()
+    ocv, ofl, oterms = orun.submit_terms(seq, off, threads=8)
+    ot, od = orun.finish()
     store = ga.DeviceKMerStore(31, db.kmers, vals, n_values, parent)
     m = ga.FastqKMerMatcher(store, ga.MatchConfig(**cfg))
     gcv, gfl = m.match_reads(seq, off)
-    gt, _ = m.finish()
+    gt, gd = m.finish()
     m.close()
     if max_paths == 128:  # the limit matters: 64 paths give another classification for some reads
         m64 = ga.FastqKMerMatcher(store, ga.MatchConfig(**dict(cfg, max_paths=64)))
@@ -100,6 +103,8 @@ def test_up_to_128_classification_paths(max_paths, threshold, fan):
     assert int((ocv >= 0).sum()) > 500
     assert np.array_equal(gt, ot), np.argwhere(gt != ot)[:6]
     assert np.array_equal(gcv, ocv) and np.array_equal(gfl, ofl)
+    matchcheck.check_match(dict(table=ot, dtable=od, class_vi=ocv, flags=ofl, terms=oterms),
+                           dict(table=gt, dtable=gd, class_vi=gcv, flags=gfl), f"{max_paths} paths")
 
 
 def test_max_paths_outside_the_reference_range_is_refused():
@@ -128,15 +133,17 @@ def test_long_read_serial_wrap(monkeypatch):
     vidx[moved] = 150 + (np.arange(len(moved)) % 150)  # leaves under the root that share reads with a species
     for cfg in (dict(), dict(threshold=3, max_paths=128)):
         orun = orc.MatchRun(orc.DB(31, db.kmers, vidx, n_values, parent), **cfg)
-        ocv, ofl = orun.submit(seq, off, threads=8)
-        ot, _ = orun.finish()
+        ocv, ofl, oterms = orun.submit_terms(seq, off, threads=8)
+        ot, od = orun.finish()
         store = ga.DeviceKMerStore(31, db.kmers, vidx, n_values, parent)
         m = ga.FastqKMerMatcher(store, ga.MatchConfig(**cfg))
         gcv, gfl = m.match_reads(seq, off)
-        gt, _ = m.finish()
+        gt, gd = m.finish()
         m.close()
         store.close()
         assert np.array_equal(gt, ot) and np.array_equal(gcv, ocv) and np.array_equal(gfl, ofl)
+        matchcheck.check_match(dict(table=ot, dtable=od, class_vi=ocv, flags=ofl, terms=oterms),
+                               dict(table=gt, dtable=gd, class_vi=gcv, flags=gfl), f"serial wrap {cfg}")
 
 
 def test_damaged_store_files_are_refused(tmp_path):
@@ -212,6 +219,7 @@ def test_device_and_host_layout_builds_are_reproducible_and_answer_alike(tmp_pat
     db = synth.SynthDB(k=31, genera=3, species_per_genus=4, genome_len=30000, seed=21)
     seq, off = synth.reads_host(db.genomes, 6000, read_len=150, seed=3)
     off = off.astype(np.uint64)
+    want_o = matchcheck.oracle_batch(orc.DB(31, db.kmers, db.value_idx, db.n_values, db.parent_vi), seq, off)
     images, tables = {}, {}
     for how in ("device", "device", "host", "host"):
         if how == "host":
@@ -222,10 +230,11 @@ def test_device_and_host_layout_builds_are_reproducible_and_answer_alike(tmp_pat
         p = tmp_path / ("%s_%d.gss" % (how, len(images)))
         store.save(p)
         m = ga.FastqKMerMatcher(store)
-        m.submit(seq, off, 0)
-        t = m.finish()[0]
+        cv, fl = m.match_reads(seq, off, 0)
+        t, d = m.finish()
         m.close()
         store.close()
+        matchcheck.check_match(want_o, dict(table=t, dtable=d, class_vi=cv, flags=fl), how)
         raw = p.read_bytes()
         if how in images:
             assert images[how] == raw, how  # the same bytes again
@@ -275,9 +284,8 @@ def test_device_layout_builder_on_awkward_stores(seed, monkeypatch):
     reads += [rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), 150).tobytes() for _ in range(20)]
     seq, off = orc.pack_reads(reads)
     odb = orc.DB(k, kk, vv, n_values, parent)
-    run = orc.MatchRun(odb)
-    wcv, wfl = run.submit(seq, off, threads=4)
-    want = run.finish()[0]
+    o = matchcheck.oracle_batch(odb, seq, off, threads=4)
+    wcv, wfl, want = o["class_vi"], o["flags"], o["table"]
     odb.close()
     for how in ("device", "host"):
         if how == "host":
@@ -288,8 +296,9 @@ def test_device_layout_builder_on_awkward_stores(seed, monkeypatch):
         assert store.info.n_stored == len(kk), how
         m = ga.FastqKMerMatcher(store)
         cv, fl = m.match_reads(seq, off, 0)
-        t = m.finish()[0]
+        t, d = m.finish()
         assert np.array_equal(t, want), (how, k, len(kk), np.argwhere(t != want)[:5])
         assert np.array_equal(cv, wcv) and np.array_equal(fl, wfl), how
+        matchcheck.check_match(o, dict(table=t, dtable=d, class_vi=cv, flags=fl), f"{how} layout, k {k}")
         m.close()
         store.close()

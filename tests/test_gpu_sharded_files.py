@@ -12,6 +12,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+import matchcheck
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
@@ -46,8 +47,9 @@ def _worker(rank, world, port, tmp):
     paths = sorted(os.path.join(tmp, x) for x in os.listdir(tmp) if x.startswith("s"))
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
     m = ga.FastqKMerMatcher(store)
-    table, _, tot = match_files_sharded(m, paths, via_host=True)
+    table, dtable, tot = match_files_sharded(m, paths, via_host=True)
     np.save(os.path.join(tmp, f"rank{rank}.npy"), table)
+    np.save(os.path.join(tmp, f"drank{rank}.npy"), dtable)
     np.save(os.path.join(tmp, f"tot{rank}.npy"), np.array(tot))
     m.close()
     store.close()
@@ -65,16 +67,17 @@ def test_two_processes_share_the_files_of_a_run(tmp_path):
     mp.spawn(_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
     # single process, same files in the same order
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
-    single, _, tot = host.match_files(store, paths)
+    single, sd, tot = host.match_files(store, paths)
     store.close()
     p = orc.parse_fastq(blob, k=31)
-    run = orc.MatchRun(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi))
-    run.submit(p["seq"], p["seq_off"])
-    want, _ = run.finish()
+    o = matchcheck.oracle_batch(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), p["seq"], p["seq_off"])
+    want = o["table"]
     assert np.array_equal(single, want)
+    matchcheck.check_match(o, dict(table=single, dtable=sd), "one process")
     for r in range(2):
         got = np.load(os.path.join(str(tmp_path), f"rank{r}.npy"))
         assert np.array_equal(got, want), np.argwhere(got != want)[:6]
+        matchcheck.check_match(o, dict(table=got, dtable=np.load(os.path.join(str(tmp_path), f"drank{r}.npy"))), f"rank {r}")
         assert tuple(np.load(os.path.join(str(tmp_path), f"tot{r}.npy"))) == (tot.reads, tot.kmers, tot.bps)
 
 
@@ -83,6 +86,7 @@ def test_single_rank_rccl_group(tmp_path):
     import genestrip_amd as ga
     from genestrip_amd import host, synth
     from genestrip_amd.distributed import match_files_sharded
+    from oracle import gs_oracle as orc
     sdb = synth.SynthDB(k=31, genera=3, species_per_genus=3, genome_len=20000, seed=11)
     paths, _ = _files(str(tmp_path), sdb, n_files=3, per_file=400)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -92,11 +96,14 @@ def test_single_rank_rccl_group(tmp_path):
     try:
         store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
         m = ga.FastqKMerMatcher(store)
-        table, _, tot = match_files_sharded(m, paths)
+        table, dtable, tot = match_files_sharded(m, paths)
         m.close()
-        single, _, stot = host.match_files(store, paths)
+        single, sd, stot = host.match_files(store, paths)
         store.close()
     finally:
         dist.destroy_process_group()
     assert np.array_equal(table, single)
+    o = matchcheck.oracle_files(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), paths)
+    matchcheck.check_match(o, dict(table=table, dtable=dtable), "RCCL group")
+    matchcheck.check_match(o, dict(table=single, dtable=sd), "one process")
     assert tot == (stot.reads, stot.kmers, stot.bps)

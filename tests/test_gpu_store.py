@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 import genestrip_amd as ga
+import matchcheck
 from genestrip_amd import synth
 from oracle import gs_oracle as orc
 
@@ -19,7 +20,9 @@ def test_store_file_round_trip(sdb, tmp_path):
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
     m = ga.FastqKMerMatcher(store)
     cv, fl = m.match_reads(seq, off)
-    want, _ = m.finish()
+    want, want_d = m.finish()
+    o = matchcheck.oracle_batch(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), seq, off)
+    matchcheck.check_match(o, dict(table=want, dtable=want_d, class_vi=cv, flags=fl), "before save")
     with pytest.raises(ga.GsError) as e:  # seen bits are set while a unique-counting run is alive
         store.save(tmp_path / "busy.gss")
     assert e.value.code == -5
@@ -33,8 +36,9 @@ def test_store_file_round_trip(sdb, tmp_path):
     assert (i1.k, i1.n_values, i1.n_stored, i1.n_buckets, i1.gate_bytes) == (i0.k, i0.n_values, i0.n_stored, i0.n_buckets, i0.gate_bytes)
     m2 = ga.FastqKMerMatcher(loaded)
     cv2, fl2 = m2.match_reads(seq, off)
-    got, _ = m2.finish()
+    got, got_d = m2.finish()
     assert np.array_equal(want, got) and np.array_equal(cv, cv2) and np.array_equal(fl, fl2)
+    matchcheck.check_match(o, dict(table=got, dtable=got_d, class_vi=cv2, flags=fl2), "loaded")
     m2.close()
     loaded.close()
     (tmp_path / "junk.gss").write_bytes(b"not a store")
@@ -62,8 +66,9 @@ def test_empty_and_tiny_stores():
     store = ga.DeviceKMerStore(31, np.zeros(0, np.int64), np.zeros(0, np.int32), 1, np.array([-1], np.int32))
     m = ga.FastqKMerMatcher(store)
     cv, fl = m.match_reads(seq, off)
-    t, _ = m.finish()
+    t, d = m.finish()
     assert not t.any() or t[0].tolist() == [0, 0, 0, 0, 0, 0, 0, 0, 0, -1]
+    assert not d.any()  # nothing counted: every double sum is exactly 0.0
     assert cv.tolist() == [-1, -1, -1] and fl.tolist() == [0, 0, 0]
     m.close()
     store.close()
@@ -72,11 +77,11 @@ def test_empty_and_tiny_stores():
     store = ga.DeviceKMerStore(31, [key], [0], 1, np.array([-1], np.int32))
     m = ga.FastqKMerMatcher(store)
     cv, fl = m.match_reads(seq, off)
-    t, _ = m.finish()
-    o = orc.MatchRun(orc.DB(31, [key], [0], 1, np.array([-1], np.int32)))
-    ocv, ofl = o.submit(seq, off)
-    ot, _ = o.finish()
+    t, d = m.finish()
+    o = matchcheck.oracle_batch(orc.DB(31, [key], [0], 1, np.array([-1], np.int32)), seq, off)
+    ocv, ofl, ot = o["class_vi"], o["flags"], o["table"]
     assert np.array_equal(t, ot) and np.array_equal(cv, ocv) and np.array_equal(fl, ofl) and t[0, 2] >= 1
+    matchcheck.check_match(o, dict(table=t, dtable=d), "single-entry store")
     m.close()
     store.close()
 
@@ -105,12 +110,12 @@ def test_small_k_against_oracle(k):
     store = ga.DeviceKMerStore(k, keys, vidx, 5, parent)
     m = ga.FastqKMerMatcher(store)
     cv, fl = m.match_reads(seq, off)
-    t, _ = m.finish()
-    o = orc.MatchRun(orc.DB(k, keys, vidx, 5, parent))
-    ocv, ofl = o.submit(seq, off)
-    ot, _ = o.finish()
+    t, d = m.finish()
+    o = matchcheck.oracle_batch(orc.DB(k, keys, vidx, 5, parent), seq, off)
+    ocv, ofl, ot = o["class_vi"], o["flags"], o["table"]
     assert np.array_equal(t, ot), np.argwhere(t != ot)[:5]
     assert np.array_equal(cv, ocv) and np.array_equal(fl, ofl)
+    matchcheck.check_match(o, dict(table=t, dtable=d), f"k {k}")
     m.close()
     store.close()
 

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import genestrip_amd as ga
+import matchcheck
 from genestrip_amd import binding, synth
 from oracle import gs_oracle as orc
 
@@ -25,17 +26,20 @@ def reads(sdb):
     return seq, off.astype(np.uint64)
 
 
-def _oracle(sdb, seq, off, per_read=False, **cfg):
+def _oracle_all(sdb, seq, off, **cfg):
+    """the oracle's whole result for tests/matchcheck.py"""
     run = orc.MatchRun(orc.DB(sdb.k, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), **cfg)
-    res = run.submit(seq, off, threads=8, per_read=per_read)
-    return run.finish(), res
+    cv, fl, terms = run.submit_terms(seq, off, 0, threads=8)
+    t, d = run.finish()
+    return dict(table=t, dtable=d, class_vi=cv, flags=fl, terms=terms)
 
 
 @pytest.mark.parametrize("n_stripes", [2, 3, 5, 8])
 @pytest.mark.parametrize("cfg", [{}, dict(count_unique=False, threshold=3), dict(max_paths=128)])
 def test_one_run_on_a_striped_store_equals_the_oracle(sdb, reads, n_stripes, cfg):
     seq, off = reads
-    (want, want_d), per = _oracle(sdb, seq, off, per_read=True, **cfg)
+    o = _oracle_all(sdb, seq, off, **cfg)
+    want = o["table"]
     stores = ga.DeviceKMerStore.striped(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi, devices=(0,) * n_stripes)
     infos = [s.info for s in stores]
     assert [i.stripe for i in infos] == list(range(n_stripes)) and all(i.n_stripes == n_stripes for i in infos)
@@ -46,13 +50,14 @@ def test_one_run_on_a_striped_store_equals_the_oracle(sdb, reads, n_stripes, cfg
         cls, flags = m.match_reads(seq, off, 0)
         table, dtable = m.finish()
         assert np.array_equal(table, want), np.argwhere(table != want)[:6]
-        assert np.allclose(dtable, want_d, rtol=1e-9, atol=1e-9)  # double sums: order dependent
-        assert np.array_equal(cls, per[0]) and np.array_equal(flags, per[1])
+        # double sums: order dependent, held to the exact sum of their terms
+        matchcheck.check_match(o, dict(table=table, dtable=dtable, class_vi=cls, flags=flags), f"{n_stripes} stripes")
         # a second batch after reset: the run's seen bits start from zero again
         m.reset()
-        m.submit(seq[:int(off[500])], off[:501], 0, n_reads=500)
-        again = m.finish()[0]
-        assert np.array_equal(again, _oracle(sdb, seq[:int(off[500])], off[:501], **cfg)[0][0])
+        cls, flags = m.match_reads(seq[:int(off[500])], off[:501], 0)
+        again, ad = m.finish()
+        matchcheck.check_match(_oracle_all(sdb, seq[:int(off[500])], off[:501], **cfg),
+                               dict(table=again, dtable=ad, class_vi=cls, flags=flags), "after reset")
         m.close()
     for s in stores:
         s.close()
@@ -62,16 +67,18 @@ def test_striped_runs_merge_like_replicas(sdb, reads):
     """one run per stripe handle (as with one GPU per stripe), each over its shard of the reads: gs_match_merge ORs the
     runs' seen bitmaps, and every run then holds the table of a single run over all reads"""
     seq, off = reads
-    want = _oracle(sdb, seq, off)[0][0]
+    o = _oracle_all(sdb, seq, off)
+    want = o["table"]
     stores = ga.DeviceKMerStore.striped(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi, devices=(0, 0, 0))
     ms = [ga.FastqKMerMatcher(s) for s in stores]
     cuts = np.linspace(0, len(off) - 1, 4).astype(int)
     for m, a, b in zip(ms, cuts[:-1], cuts[1:]):
         m.submit(seq[int(off[a]):int(off[b])], off[a:b + 1] - off[a], int(a), n_reads=int(b - a))
     binding.merge_runs(ms)
-    for m in ms:
-        t = m.finish()[0]
+    for i, m in enumerate(ms):
+        t, d = m.finish()
         assert np.array_equal(t, want), np.argwhere(t != want)[:6]
+        matchcheck.check_match(o, dict(table=t, dtable=d), f"stripe run {i}")
         m.close()
     for s in stores:
         s.close()
@@ -92,13 +99,16 @@ def test_files_over_the_handles_of_a_striped_store(sdb, tmp_path):
                 rd = seq[int(off[r]):int(off[r + 1])].tobytes()
                 f.write(b"@r%d\n%s\n+\n%s\n" % (r, rd, b"F" * len(rd)))
         paths.append(p)
-    want = _oracle(sdb, seq, off)[0][0]
+    o = _oracle_all(sdb, seq, off)
+    want = o["table"]
     stores = ga.DeviceKMerStore.striped(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi, devices=(0, 0, 0))
-    table, _, tot = host.match_files_multi(stores, paths)
+    table, dtable, tot = host.match_files_multi(stores, paths)
     assert tot.reads == 9000
     assert np.array_equal(table, want), np.argwhere(table != want)[:6]
-    single, _, _ = host.match_files(stores[2], paths)
+    matchcheck.check_match(o, dict(table=table, dtable=dtable), "files over the stripe handles")
+    single, sd, _ = host.match_files(stores[2], paths)
     assert np.array_equal(single, want)
+    matchcheck.check_match(o, dict(table=single, dtable=sd), "files over one stripe handle")
     for s in stores:
         s.close()
 
@@ -113,10 +123,16 @@ def test_striped_store_long_reads_segments_and_max_counts(sdb):
     a, b = ga.FastqKMerMatcher(plain, cfg), ga.FastqKMerMatcher(stores[1], cfg)
     a.submit(seq, off, 0)
     b.submit(seq, off, 0)
-    ta, tb = a.finish()[0], b.finish()[0]
+    (ta, da), (tb, db_) = a.finish(), b.finish()
     assert np.array_equal(ta, tb) and ta[:, 2].sum() > 0
-    assert np.array_equal(ta, _oracle(sdb, seq, off)[0][0])
+    o = _oracle_all(sdb, seq, off, max_kmer_res_counts=3)
+    assert np.array_equal(ta, o["table"])
     assert np.array_equal(a.max_counts(), b.max_counts())
+    mo = orc.MatchRun(orc.DB(sdb.k, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), max_kmer_res_counts=3)
+    mo.submit(seq, off, threads=8, per_read=False)
+    o["max_counts"] = mo.max_counts()
+    matchcheck.check_match(o, dict(table=ta, dtable=da, max_counts=a.max_counts()), "plain store")
+    matchcheck.check_match(o, dict(table=tb, dtable=db_, max_counts=b.max_counts()), "4 stripes")
     sa, sb = a.segments(seq, off), b.segments(seq, off)
     for x, y in zip(sa, sb):
         assert np.array_equal(x, y)
@@ -129,7 +145,8 @@ def test_a_store_file_loads_as_stripes(sdb, reads, tmp_path):
     """build once, save, load striped: the stripes of a store file serve the same tables as the store that was saved; a
     damaged file is refused before anything reaches HBM, as by gs_db_load"""
     seq, off = reads
-    want = _oracle(sdb, seq, off)[0][0]
+    o = _oracle_all(sdb, seq, off)
+    want = o["table"]
     plain = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
     path = tmp_path / "store.gss"
     plain.save(path)
@@ -140,8 +157,9 @@ def test_a_store_file_loads_as_stripes(sdb, reads, tmp_path):
     assert stores[2].info.n_in_records == pinfo.n_in_records and stores[2].info.n_stored == pinfo.n_stored
     m = ga.FastqKMerMatcher(stores[3])
     m.submit(seq, off, 0)
-    t = m.finish()[0]
+    t, d = m.finish()
     assert np.array_equal(t, want), np.argwhere(t != want)[:6]
+    matchcheck.check_match(o, dict(table=t, dtable=d), "stripes of a loaded file")
     m.close()
     for s in stores:
         s.close()

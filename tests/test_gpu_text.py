@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import genestrip_amd as ga
+import matchcheck
 from genestrip_amd import synth
 from oracle import gs_oracle as orc
 
@@ -61,17 +62,16 @@ def _oracle_on_text(sdb, text, first_read_no=0, **cfg):
     if len(seq) == 0:
         seq = np.zeros(1, dtype=np.uint8)
     odb = orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
-    run = orc.MatchRun(odb, **cfg)
-    cv, fl = run.submit(seq, off, first_read_no)
-    t, _ = run.finish()
-    return t, cv, fl, (int(p["n_reads"]), int(p["total_kmers"]), int(p["total_bps"]))
+    o = matchcheck.oracle_batch(odb, seq, off, first_read_no, **cfg)
+    return o, (int(p["n_reads"]), int(p["total_kmers"]), int(p["total_bps"]))
 
 
 @pytest.mark.parametrize("crlf", [False, True])
 def test_text_chunks_equal_reference_parse(sdb, store, crlf):
     recs = _records(sdb, 4000)
     text = _text(recs, crlf)
-    want_t, want_cv, want_fl, want_tot = _oracle_on_text(sdb, text)
+    o, want_tot = _oracle_on_text(sdb, text)
+    want_t, want_cv, want_fl = o["table"], o["class_vi"], o["flags"]
     m = ga.FastqKMerMatcher(store)
     # three chunks cut at record boundaries, read numbers running on
     cuts = [0, 1300, 1301, 4000]
@@ -88,18 +88,20 @@ def test_text_chunks_equal_reference_parse(sdb, store, crlf):
     failed, bad, tot = m.text_status()
     assert failed == -1 and bad == -1
     assert tot == want_tot
-    got_t, _ = m.finish()
+    got_t, got_d = m.finish()
     m.close()
     assert np.array_equal(got_t, want_t), np.argwhere(got_t != want_t)[:8]
     assert np.array_equal(np.concatenate(got_cv), want_cv)
     assert np.array_equal(np.concatenate(got_fl), want_fl)
+    matchcheck.check_match(o, dict(table=got_t, dtable=got_d, class_vi=np.concatenate(got_cv), flags=np.concatenate(got_fl)))
 
 
 def test_text_device_resident_chunk(sdb, store):
     import torch
     recs = _records(sdb, 1500, seed=9)
     text = _text(recs)
-    want_t, want_cv, want_fl, want_tot = _oracle_on_text(sdb, text)
+    o, want_tot = _oracle_on_text(sdb, text)
+    want_t, want_cv, want_fl = o["table"], o["class_vi"], o["flags"]
     m = ga.FastqKMerMatcher(store)
     d = torch.from_numpy(np.frombuffer(text, dtype=np.uint8).copy()).cuda()
     cv = torch.full((1500,), -7, dtype=torch.int32, device="cuda")
@@ -107,11 +109,12 @@ def test_text_device_resident_chunk(sdb, store):
     m.submit_text(d, n_lines=6000, class_vi=cv, flags=fl)
     m.sync()
     assert m.text_status() == (-1, -1, want_tot)
-    got_t, _ = m.finish()
+    got_t, got_d = m.finish()
     m.close()
     assert np.array_equal(got_t, want_t)
     assert np.array_equal(cv.cpu().numpy(), want_cv)
     assert np.array_equal(fl.cpu().numpy(), want_fl)
+    matchcheck.check_match(o, dict(table=got_t, dtable=got_d, class_vi=cv.cpu().numpy(), flags=fl.cpu().numpy()))
 
 
 def _bad_chunks(recs):
@@ -130,7 +133,8 @@ def test_text_refuses_what_is_not_four_line_fastq(sdb, store, what):
     good = _text(recs)
     bad = _bad_chunks(recs)[what]
     assert bad.count(b"\n") % 4 == 0
-    want_t, _, _, want_tot = _oracle_on_text(sdb, good)
+    o, want_tot = _oracle_on_text(sdb, good)
+    want_t = o["table"]
     m = ga.FastqKMerMatcher(store)
     t0 = m.submit_text(good)
     t1 = m.submit_text(bad, first_read_no=12)
@@ -143,8 +147,9 @@ def test_text_refuses_what_is_not_four_line_fastq(sdb, store, what):
         assert first_bad == {"multi-line sequence": 5, "short quality": 3, "no plus line": 1}[what]
     m.text_clear_error()
     assert m.text_status()[0] == -1
-    got_t, _ = m.finish()
+    got_t, got_d = m.finish()
     assert np.array_equal(got_t, want_t)  # only the first chunk was counted
+    matchcheck.check_match(o, dict(table=got_t, dtable=got_d), what)
     m.reset()
     assert m.text_status() == (-1, -1, (0, 0, 0))
     m.close()

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import genestrip_amd as ga
+import matchcheck
 from genestrip_amd import synth
 from oracle import gs_oracle as orc
 from test_gpu_huge import _chimera
@@ -21,20 +22,20 @@ def sdb():
 def _fixed(store_args, seq, L, n, first=0, **cfg):
     k, kmers, vidx, nv, parent = store_args
     off = np.arange(n + 1, dtype=np.uint64) * L
-    orun = orc.MatchRun(orc.DB(k, kmers, vidx, nv, parent), **cfg)
-    ocv, ofl = orun.submit(seq, off, first)
-    ot, _ = orun.finish()
+    o = matchcheck.oracle_batch(orc.DB(k, kmers, vidx, nv, parent), seq, off, first, **cfg)
+    ocv, ofl, ot = o["class_vi"], o["flags"], o["table"]
     store = ga.DeviceKMerStore(k, kmers, vidx, nv, parent)
     m = ga.FastqKMerMatcher(store, ga.MatchConfig(**cfg))
     cv, fl = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint8)
     m.submit_fixed(seq, L, n, first, class_vi=cv, flags=fl)
-    gt, _ = m.finish()
+    gt, gd = m.finish()
     m.close()
     store.close()
     bad = np.argwhere(ot != gt)
     assert bad.size == 0, (L, cfg, bad[:8].tolist())
     assert np.array_equal(cv, ocv), (L, cfg, np.flatnonzero(cv != ocv)[:8])
     assert np.array_equal(fl, ofl), (L, cfg, np.flatnonzero(fl != ofl)[:8])
+    matchcheck.check_match(o, dict(table=gt, dtable=gd, class_vi=cv, flags=fl), f"fixed {L} {cfg}")
     return ofl
 
 
@@ -126,10 +127,10 @@ def test_paired_end_lengths_from_a_fastq_file(sdb, tmp_path, gz):
     with (gzip.open(p, "wb", compresslevel=1) if gz else open(p, "wb")) as f:
         f.write(text)
     seq, off = orc.pack_reads(reads)
-    orun = orc.MatchRun(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi))
-    orun.submit(seq, off, threads=4, per_read=False)
-    want, _ = orun.finish()
+    o = matchcheck.oracle_batch(orc.DB(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi), seq, off)
+    want = o["table"]
     store = ga.DeviceKMerStore(31, sdb.kmers, sdb.value_idx, sdb.n_values, sdb.parent_vi)
-    table, _, tot = host.match_files(store, [p])
+    table, dtable, tot = host.match_files(store, [p])
     assert np.array_equal(table, want) and tot.reads == len(reads) and tot.bps == sum(map(len, reads))
+    matchcheck.check_match(o, dict(table=table, dtable=dtable), "paired-end file")
     store.close()

@@ -133,3 +133,73 @@ def test_an_empty_cell_must_be_exactly_zero_and_the_integers_exact():
     g["flags"][5] ^= orc.F_COUNTED
     with pytest.raises(AssertionError, match="flags differs"):
         matchcheck.check_match(o, g)
+
+
+def _parts(db, seq, off, cut):
+    """the batch as two runs over its halves (read numbers kept): per-part results and the whole run's oracle"""
+    o = _run(db, seq, off)
+    parts = []
+    for a, b in ((0, cut), (cut, len(off) - 1)):
+        s0 = int(off[a])
+        p = _run(db, seq[s0:int(off[b])], off[a:b + 1] - np.uint64(s0), first_read_no=a, count_unique=True)
+        parts.append(p)
+    return o, parts
+
+
+def test_summed_parts_pass_and_a_term_dropped_or_doubled_across_parts_fails():
+    rng = np.random.default_rng(10)
+    genomes, db = _random_store(rng)
+    seq, off = _random_reads(rng, genomes, 4000)
+    o, parts = _parts(db, seq, off, 1700)
+    # (two oracle runs each count the unique k-mers they see, which overlap: the integer table is held to the merged one)
+    whole = dict(o, table=matchcheck.merge_tables([p["table"] for p in parts]))
+    assert np.array_equal(whole["table"][:, orc.C_READS], o["table"][:, orc.C_READS])
+    assert matchcheck.check_match_parts(whole, parts) <= 1.0
+    r = _nonzero_read(parts[0])
+    v, tax, cls, mx = (int(x) for x in parts[0]["terms"][r])
+    t, c = tax / mx, cls / mx
+    for j, term in enumerate((t, t * t, c, c * c)):
+        dropped = [dict(parts[0], dtable=parts[0]["dtable"].copy()), parts[1]]
+        dropped[0]["dtable"][v, j] -= term
+        with pytest.raises(AssertionError, match="outside the bound"):
+            matchcheck.check_match_parts(whole, dropped)
+        doubled = [parts[0], dict(parts[1], dtable=parts[1]["dtable"].copy())]
+        doubled[1]["dtable"][v, j] += term  # the same read counted in the other part as well
+        with pytest.raises(AssertionError, match="outside|should be 0.0"):
+            matchcheck.check_match_parts(whole, doubled)
+    # per-read outputs are concatenated in part order
+    swapped = [parts[1], parts[0]]
+    with pytest.raises(AssertionError):
+        matchcheck.check_match_parts(whole, swapped)
+
+
+def test_oracle_files_equals_one_run_over_the_records(tmp_path):
+    """plain, gzip and BGZF FASTQ, multi-line FASTQ and FASTA: the same records in file order, read numbers running on"""
+    import gzip
+
+    from conftest import bgzf
+    rng = np.random.default_rng(11)
+    genomes, db = _random_store(rng)
+    seq, off = _random_reads(rng, genomes, 900)
+    reads = [seq[int(off[i]):int(off[i + 1])].tobytes() for i in range(len(off) - 1)]
+    fq = lambda rs, base: b"".join(b"@r%d\n%s\n+\n%s\n" % (base + i, r, b"F" * len(r)) for i, r in enumerate(rs))
+    ml = lambda rs: b"".join(b"@m\n%s\n%s\n+\n%s\n%s\n" % (r[:20], r[20:], b"F" * 20, b"F" * (len(r) - 20)) for r in rs)
+    fa = lambda rs: b"".join(b">f\n%s\n%s\n" % (r[:33], r[33:]) for r in rs)
+    chunks = [reads[i * 150:(i + 1) * 150] for i in range(6)]
+    files = [("a.fq", fq(chunks[0], 0)), ("b.fq.gz", gzip.compress(fq(chunks[1], 150))), ("c.fq.gz", bgzf(fq(chunks[2], 300))),
+             ("d.fq", ml([r for r in chunks[3] if len(r) > 20])), ("e.fa", fa([r for r in chunks[4] if len(r) > 33])),
+             ("f.fa.gz", bgzf(fa([r for r in chunks[5] if len(r) > 33])))]
+    paths = []
+    for name, data in files:
+        paths.append(str(tmp_path / name))
+        open(paths[-1], "wb").write(data)
+    got = matchcheck.oracle_files(db, paths, threads=4, first_read_no=7, max_counts=True, max_kmer_res_counts=2)
+    kept = chunks[0] + chunks[1] + chunks[2] + [r for r in chunks[3] if len(r) > 20] + [r for c in chunks[4:] for r in c if len(r) > 33]
+    s, o = orc.pack_reads(kept)
+    run = orc.MatchRun(db, max_kmer_res_counts=2)
+    cv, fl, terms = run.submit_terms(s, o, 7, threads=4)
+    t, d = run.finish()
+    assert got["reads"] == len(kept) and got["bps"] == sum(len(r) for r in kept)
+    assert np.array_equal(got["table"], t) and np.array_equal(got["class_vi"], cv) and np.array_equal(got["flags"], fl)
+    assert np.array_equal(got["terms"], terms) and np.array_equal(got["max_counts"], run.max_counts())
+    matchcheck.check_match(got, dict(table=t, dtable=d, class_vi=cv, flags=fl))
