@@ -18,6 +18,7 @@
 #include <utility>
 #include <vector>
 
+#include "gs_absmod.h"
 #include "gs_layout.h"
 #include "gs_params.h"
 
@@ -4537,18 +4538,6 @@ static int bloom_collect(gs_bloom *b) {
     return GS_OK;
 }
 
-// signed magic for floor-free truncated division by a positive 63-bit constant d:
-//   q = mulhi_u64(|v|, magic) >> shift  is exact for |v| < 2^63 when magic = ceil(2^(64+shift) / d)
-// computed with 128-bit arithmetic on the host (see gs_filter_kernel for the use).
-static void magic_u64(u64 d, u64 &magic, int &shift) {
-    // smallest l with 2^l >= d ; magic = floor(2^64 * (2^l - d) / d) + 1 ; q = (mulhi(n,magic) + ((n - mulhi)>>1)) >> (l-1)
-    int l = 0;
-    while (l < 64 && ((u64)1 << l) < d) l++;
-    unsigned __int128 num = ((unsigned __int128)((l == 64 ? 0 : ((u64)1 << l)) - d)) << 64;
-    magic = (u64)(num / d) + 1;
-    shift = l;
-}
-
 static int filter_launch(gs_bloom *b, int k, int min_pos_count, double positive_ratio, const uint8_t *d_seq,
                          const uint64_t *d_off, int64_t n_reads, uint8_t *d_acc, int off_stride, const uint32_t *d_skip,
                          int profile) {
@@ -4562,9 +4551,9 @@ static int filter_launch(gs_bloom *b, int k, int min_pos_count, double positive_
     P.words = b->d_words;
     P.factors = b->d_factors;
     {
-        u64 mg = 0;
+        uint64_t mg = 0;
         int sh = 0;
-        magic_u64((u64)b->bits, mg, sh);
+        gs_magic_u64((u64)b->bits, mg, sh);  // gs_absmod.h
         P.magic = mg;
         P.magic_shift = sh;
     }

@@ -24,6 +24,7 @@
 
 #include <algorithm>
 
+#include "gs_absmod.h"  // gs_absmod: the filter's bit index
 #include "gs_layout.h"
 #include "gs_params.h"
 
@@ -2873,15 +2874,6 @@ __device__ __forceinline__ int64_t gs_canonical_java(uint32_t fhi, uint32_t flo,
     const u64 fwd = (gs_spread32(rhi) << 1) | gs_spread32(rlo);                     // first base in the top bits
     const u64 rev = (gs_spread32(fhi) << 1) | gs_spread32((flo ^ kmask) & kmask);   // complement, reversed
     return (int64_t)(fwd > rev ? fwd : rev);
-}
-
-// |v| mod d for the reference's Math.abs(v % bits) (XORKMerBloomFilter.java:57-59); d < 2^63
-__device__ __forceinline__ u64 gs_absmod(int64_t v, u64 d, u64 magic, int shift) {
-    const u64 n = v < 0 ? (u64)0 - (u64)v : (u64)v;
-    if (shift == 0) return 0;  // d == 1
-    const u64 t = __umul64hi(magic, n);
-    const u64 q = (t + ((n - t) >> 1)) >> (shift - 1);
-    return n - q * d;
 }
 
 __device__ __forceinline__ int64_t gs_murmur64(int64_t data_, int64_t base) {  // MurmurHash3DropIn.java:60-87

@@ -191,6 +191,29 @@ orc_bloom *orc_bloom_create(int kind, int64_t n, double fpp) {
     return b;
 }
 
+/* a filter of any geometry (tests): XOR / Murmur: `bits` bits and `n_hashes` factors; Blocked: `bits` buckets, factors[0] = the
+ * seed.  words (n_words of them, see orc_bloom_n_words) may be NULL: the array is then calloc'd, so only the pages that put or
+ * contains touch become resident.  NULL on a bad argument. */
+orc_bloom *orc_bloom_create_raw(int kind, int64_t bits, int32_t n_hashes, const int64_t *factors, const uint64_t *words) {
+    if (kind < ORC_BLOOM_XOR || kind > ORC_BLOOM_BLOCKED || bits < 1 || !factors) return NULL;
+    if (kind != ORC_BLOOM_BLOCKED && n_hashes < 1) return NULL;
+    orc_bloom *b = (orc_bloom *)calloc(1, sizeof(*b));
+    b->kind = kind;
+    b->bits = bits;
+    b->hashes = kind == ORC_BLOOM_BLOCKED ? 0 : n_hashes;
+    const int nf = kind == ORC_BLOOM_BLOCKED ? 1 : n_hashes;
+    b->factors = (int64_t *)malloc(sizeof(int64_t) * (size_t)nf);
+    memcpy(b->factors, factors, sizeof(int64_t) * (size_t)nf);
+    b->n_words = kind == ORC_BLOOM_BLOCKED ? bits + 16 + 1 : (bits + 63) / 64;
+    b->words = (uint64_t *)calloc((size_t)b->n_words, sizeof(uint64_t));
+    if (!b->words) {
+        orc_bloom_destroy(b);
+        return NULL;
+    }
+    if (words) memcpy(b->words, words, sizeof(uint64_t) * (size_t)b->n_words);
+    return b;
+}
+
 void orc_bloom_destroy(orc_bloom *b) {
     if (!b) return;
     free(b->factors);

@@ -46,6 +46,8 @@ typedef struct orc_bloom orc_bloom;
  * hash factors from Random(42) (:78,:105-109).  Blocked: bits_per_key 10, seed Random(42).nextLong()
  * (BlockedKMerBloomFilter.java:92,:201-219); fpp ignored. */
 orc_bloom *orc_bloom_create(int kind, int64_t expected_insertions, double fpp);
+/* any geometry (tests): bits (Blocked: buckets), n_hashes factors (Blocked: factors[0] = seed), initial words or NULL */
+orc_bloom *orc_bloom_create_raw(int kind, int64_t bits, int32_t n_hashes, const int64_t *factors, const uint64_t *words);
 void orc_bloom_destroy(orc_bloom *b);
 void orc_bloom_put(orc_bloom *b, int64_t key);
 void orc_bloom_put_many(orc_bloom *b, const int64_t *keys, int64_t n);

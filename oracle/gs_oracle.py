@@ -55,6 +55,7 @@ def lib():
         "orc_next_straight": (i64, [i64, C.c_uint8, C.c_int]), "orc_next_reverse": (i64, [i64, C.c_uint8, C.c_int]),
         "orc_standard_kmer": (i64, [i64, i64]), "orc_kmer_canonical": (i64, [vp, C.c_int, C.c_int, vp]),
         "orc_bloom_create": (vp, [C.c_int, i64, dbl]), "orc_bloom_destroy": (None, [vp]),
+        "orc_bloom_create_raw": (vp, [C.c_int, i64, i32, vp, vp]),
         "orc_bloom_put": (None, [vp, i64]), "orc_bloom_contains": (C.c_int, [vp, i64]),
         "orc_bloom_put_many": (None, [vp, vp, i64]), "orc_bloom_put_many_mt": (None, [vp, vp, i64, C.c_int]),
         "orc_bloom_kind": (C.c_int, [vp]), "orc_bloom_bits": (i64, [vp]), "orc_bloom_hashes": (i32, [vp]),
@@ -162,6 +163,22 @@ class Bloom:
     def __init__(self, kind, expected, fpp=0.01):
         self.h = lib().orc_bloom_create(kind, expected, fpp)
         self.kind = kind
+
+    @classmethod
+    def raw(cls, kind, bits, n_hashes, factors, words=None):
+        """a filter of any geometry: `bits` bits (Blocked: buckets), `n_hashes` factors (Blocked: factors[0] = the seed) and
+        optionally initial words (n_words of them: (bits + 63) // 64, Blocked: bits + 17)"""
+        f = np.ascontiguousarray(factors, dtype=np.int64)
+        assert len(f) >= (1 if kind == BLOOM_BLOCKED else n_hashes)
+        w = None if words is None else np.ascontiguousarray(words, dtype=np.uint64)
+        if w is not None:
+            assert len(w) == (bits + 17 if kind == BLOOM_BLOCKED else (bits + 63) // 64)
+        self = cls.__new__(cls)
+        self.kind = kind
+        self.h = lib().orc_bloom_create_raw(kind, bits, n_hashes, _p(f), _p(w))
+        if not self.h:
+            raise ValueError("bad raw bloom geometry")
+        return self
 
     def close(self):
         if self.h:
