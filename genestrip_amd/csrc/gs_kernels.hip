@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "gs_absmod.h"  // gs_absmod: the filter's bit index
 #include "gs_layout.h"
@@ -409,6 +410,11 @@ __device__ __forceinline__ void gs_wave_minimizers(const u64 (&Bhi)[NS + 1], con
 }
 
 #define GS_ACT(m) __builtin_amdgcn_inverse_ballot_w64(m)  // a wave-level mask as a per-lane condition
+// the lanes below n as a wave-level mask: the positions of a sub-round that hold a k-mer, the lanes of a word that hold a base
+__device__ __forceinline__ u64 gs_low_mask(int n) { return n >= 64 ? ~0ULL : (n <= 0 ? 0ULL : ((1ULL << n) - 1ULL)); }
+// live: the positions of each sub-round that hold a k-mer, gs_low_mask(max - base - 64 s), from a caller that has them already -- they
+// depend on the read's length alone, and a batch of one length builds them once per wave (gs_match_kernel<.., FIXED = true>);
+// nullptr: derived here from base and max
 // CTX: is the gate keyed by gs_gate_ctx_key?  0 never (the launcher has looked), 1 always, 2 ask the store (GsDbDev::mgate_ctx)
 // AGG: the unique-k-mer marks of the k-mers that share a record line leave as ONE atomic per line.  A device-scope atomic is
 // executed on the memory side of the L2s (eight XCDs, eight L2s): every one is a request to the fabric, and on a store that does not
@@ -419,7 +425,7 @@ __device__ __forceinline__ void gs_wave_minimizers(const u64 (&Bhi)[NS + 1], con
 template <int KC, bool STRIPED, int CTX = 2, bool AGG = false, int NS = 2>
 __device__ __forceinline__ void gs_probe_planes(const GsDbDev &db, const u64 (&Bhi)[NS + 1], const u64 (&Blo)[NS + 1],
                                                 const u64 (&Bbad)[NS + 1], int base, int max, int lane, int (&node)[NS],
-                                                uint32_t *wave_g, const GsMark &mk) {
+                                                uint32_t *wave_g, const GsMark &mk, const u64 *live = nullptr) {
     static_assert(NS == 2 || !AGG, "the seen-bit accumulators are laid out for two sub-rounds");
     const int k = KC ? KC : db.k;  // KC = compile-time k of the specialised kernels (0: any k)
     const uint32_t kmask = (1u << k) - 1u;
@@ -437,8 +443,7 @@ __device__ __forceinline__ void gs_probe_planes(const GsDbDev &db, const u64 (&B
     u64 act[NS];
 #pragma unroll
     for (int s = 0; s < NS; s++) {
-        const int nv = max - base - 64 * s;  // valid positions of this sub-round
-        const u64 vm = nv >= 64 ? ~0ULL : (nv <= 0 ? 0ULL : ((1ULL << nv) - 1ULL));
+        const u64 vm = live != nullptr ? live[s] : gs_low_mask(max - base - 64 * s);  // valid positions of this sub-round
         fhi[s] = (uint32_t)gs_funnel(Bhi[s], Bhi[s + 1], lane) & kmask;
         flo[s] = (uint32_t)gs_funnel(Blo[s], Blo[s + 1], lane) & kmask;
         act[s] = vm;
@@ -630,12 +635,15 @@ __device__ __forceinline__ void gs_probe_planes(const GsDbDev &db, const u64 (&B
 // LONG = true: any length; tag/cnt are this wave's scratch rows of n_values ints, serial its read tag.
 // WIDE = true: maxClassificationPaths in 65..128 (C/GSConfigKey.java:350 allows 1..128): candidate path i lives in
 // lane i & 63 of register set i >> 6; with WIDE = false there is one set and lane = path.
+// FIXED = true (!LONG): the caller's reads all have ONE length with 65 .. 128 k-mer positions (gs_match_kernel): sub-round 0 is
+// full, and the live positions of sub-round 1 come as `live1`, built once per wave; nothing here tests the length.
 // ---------------------------------------------------------------------------------------------------
-template <bool LONG, bool FROM_NODES, int KC, bool WIDE, bool REC, bool STRIPED, int CTX = 2>
+template <bool LONG, bool FROM_NODES, int KC, bool WIDE, bool REC, bool STRIPED, int CTX = 2, bool FIXED = false>
 __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const GsStats &st, int64_t r, u64 off, int L,
                                                 int lane, int (*s_dvi)[128], int (*s_dcnt)[128], int wave_in_block,
                                                 int32_t *tag, int32_t *cnt, int serial, const uint32_t (&pre)[3],
-                                                uint32_t *wave_g, unsigned long long *cur) {
+                                                uint32_t *wave_g, unsigned long long *cur, u64 live1 = 0) {
+    static_assert(!FIXED || (!LONG && !FROM_NODES), "one iteration, probed here");
     const GsDbDev &db = P.db;
     const int k = KC ? KC : db.k;
     const int max = L - k + 1;
@@ -643,7 +651,7 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
     int out_class = -1;
     int out_flags = 0;
 
-    if (max > 0) {
+    if (FIXED || max > 0) {
         const int64_t read_no = P.first_read_no + r;
         const u64 key_lo = ((1ULL << 40) - 1) - ((u64)read_no & ((1ULL << 40) - 1));
         const int n_iter = LONG ? (max + 127) >> 7 : 1;
@@ -685,7 +693,9 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
                 for (int w = 0; w < 3; w++) {
                     if (w < nw) {
                         const int lo_bits = q - (base + 64 * w);  // positions of this word that are < q
-                        const u64 m_lo = lo_bits >= 64 ? ~0ULL : (lo_bits <= 0 ? 0ULL : ((1ULL << lo_bits) - 1));
+                        // (FIXED: 64 <= q < 128 -- word 0 whole, of word 1 one position fewer than are live, of word 2 none)
+                        const u64 m_lo = FIXED ? (w == 0 ? ~0ULL : (w == 1 ? live1 >> 1 : 0ULL))
+                                               : (lo_bits >= 64 ? ~0ULL : (lo_bits <= 0 ? 0ULL : ((1ULL << lo_bits) - 1)));
                         bad_lo += __popcll(Bbad[w] & m_lo);
                         bad_hi = bad_hi || ((Bbad[w] & ~m_lo) != 0);
                     }
@@ -713,7 +723,8 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
 #ifndef GS_AGG_ALL
 #define GS_AGG_ALL 0
 #endif
-                gs_probe_planes<KC, STRIPED, CTX, (REC || GS_AGG_ALL) && !LONG>(db, Bhi, Blo, Bbad, base, max, lane, node, wave_g, mk);
+                const u64 live[2] = {~0ULL, live1};
+                gs_probe_planes<KC, STRIPED, CTX, (REC || GS_AGG_ALL) && !LONG>(db, Bhi, Blo, Bbad, base, max, lane, node, wave_g, mk, FIXED ? live : nullptr);
             }
 
             if (!LONG) GS_STAMP(5, node[0] ^ node[1])
@@ -756,8 +767,8 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
                 // (positions >= max hold NONE: the first of them differs from its predecessor and is masked away; wave-level masks
                 // throughout, as in gs_probe_planes)
                 const int nv0 = max - base, nv1 = max - base - 64;
-                const u64 vm0 = nv0 >= 64 ? ~0ULL : (nv0 <= 0 ? 0ULL : ((1ULL << nv0) - 1ULL));
-                const u64 vm1 = nv1 >= 64 ? ~0ULL : (nv1 <= 0 ? 0ULL : ((1ULL << nv1) - 1ULL));
+                const u64 vm0 = FIXED ? ~0ULL : (nv0 >= 64 ? ~0ULL : (nv0 <= 0 ? 0ULL : ((1ULL << nv0) - 1ULL)));
+                const u64 vm1 = FIXED ? live1 : (nv1 >= 64 ? ~0ULL : (nv1 <= 0 ? 0ULL : ((1ULL << nv1) - 1ULL)));
                 const u64 chg0 = __ballot(node[0] != prev[0]) & vm0;
                 const u64 chg1 = __ballot(node[1] != prev[1]) & vm1;
                 // a hit contig left open by the previous iteration ends at the first change of this one
@@ -889,7 +900,7 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
             if (!LONG) GS_STAMP(6, node[0])
             {   // carry: node of the last valid position of this iteration
                 const int last_p = (max - 1 < base + 127) ? max - 1 : base + 127;
-                const int ls = (last_p - base) >> 6, ll = (last_p - base) & 63;
+                const int ls = FIXED ? 1 : (last_p - base) >> 6, ll = FIXED ? max - 65 : (last_p - base) & 63;  // (FIXED: 64 < max <= 128)
                 carry_last = gs_readlane(ls ? node[1] : node[0], ll);
             }
         }
@@ -1271,32 +1282,66 @@ __global__ __launch_bounds__(GS_BLOCK) __attribute__((amdgpu_waves_per_eu(GS_WAV
     // counter), the latency only moves; (2) the same requests issued behind the gate loads, the youngest at every later wait: the
     // waits for offsets and bases shrink from 3 250 to 1 650 wave cycles per read (tools/phase_times.sh) and every other phase
     // grows by as much: 7.62 ms, 47 M-k-mer store 9.22 -> 9.41 ms.  The SIMD is short of issue slots, not of overlap.)
-    const int64_t po_step = n_waves * P.off_stride;        // stride 1: running offsets; 2: (start, end) pairs
-    const uint64_t *po = P.off + wave_id * P.off_stride;   // offsets of the current read
-    for (int64_t r = wave_id; r < n_reads; r += n_waves, po += po_step) {
-        GsKernargPtr kp = kp0;
+    // A batch of ONE read length (gs_match_submit_fixed) pays for its length once: what the length alone decides -- which lanes of the
+    // third base word hold a base, which positions of sub-round 1 hold a k-mer, that words 0 and 1 and sub-round 0 are full, that
+    // the read is this kernel's at all -- is settled here, per wave, and the loop over the reads tests no length.  For lengths of
+    // 128 .. k + 127 bases (65 .. 128 positions at k <= 64); any other length, and any batch with offsets, takes the general loop.
+    // The empty asm below hides that fixed_len is loop invariant, so the compiler cannot do this itself.  Both loops are one body
+    // of code (`fixed` is a type: std::true_type / std::false_type), and they live in one kernel: an instantiation per
+    // (LDS_STATS, KC, CTX) is what the launchers, the occupancy query and the profiles' kernel names know.
+    constexpr bool CAN_FIX = !FROM_NODES && !WIDE && !STRIPED;
+    const int fixed_L = P.fixed_len;
+    const bool fixed_batch = CAN_FIX && P.off_stride == 0 && fixed_L >= 128 && fixed_L - k + 1 <= 128;
+    const u64 fixed_live1 = gs_low_mask(fixed_L - k + 1 - 64);
+    auto reads = [&](auto fixed) {
+        constexpr bool FIXED = decltype(fixed)::value;
+        const int64_t po_step = n_waves * P.off_stride;        // stride 1: running offsets; 2: (start, end) pairs
+        const uint64_t *po = P.off + wave_id * P.off_stride;   // offsets of the current read
+        for (int64_t r = wave_id; r < n_reads; r += n_waves, po += po_step) {
+            GsKernargPtr kp = kp0;
 #ifndef GS_KERNARG_HOISTED  // (experiment, DESIGN 8.1 "kernarg re-reads": let the compiler keep the parameters live across the loop)
-        asm volatile("" : "+s"(kp));
+            asm volatile("" : "+s"(kp));
 #endif
-        const GsMatchParams &Q = *(const GsMatchParams *)kp;
-        u64 off;
-        int L;
-        if (Q.off_stride == 0) {  // reads of one length, back to back: nothing to load
-            L = Q.fixed_len;
-            off = (u64)r * (u64)(uint32_t)L;
-        } else {
-            off = po[0];
-            L = (int)(po[1] - off);
-        }
-        GS_STAMP(0, L)
-        if (L - k + 1 > 128) continue;  // another kernel's: gs_classify_kernel has put it into that kernel's queue
-        uint32_t pre[3];
-        const uint8_t *rd = Q.seq + off;
+            const GsMatchParams &Q = *(const GsMatchParams *)kp;
+            u64 off;
+            int L;
+            if (FIXED) {
+                // (only the mask is kept across the loop.  The length itself comes from the kernarg segment like every other parameter:
+                // as a loop invariant, everything derived from it -- the clamped index, (double)max of the class-error gate -- is
+                // hoisted into registers that stay live across the loop, and the kernel spills: 8 -> 36 bytes of scratch)
+                L = Q.fixed_len;
+                off = (u64)r * (u64)(uint32_t)L;
+            } else if (Q.off_stride == 0) {  // reads of one length, back to back: nothing to load
+                L = Q.fixed_len;
+                off = (u64)r * (u64)(uint32_t)L;
+            } else {
+                off = po[0];
+                L = (int)(po[1] - off);
+            }
+            GS_STAMP(0, L)
+            if (!FIXED && L - k + 1 > 128) continue;  // another kernel's: gs_classify_kernel has put it into that kernel's queue
+            uint32_t pre[3];
+            const uint8_t *rd = Q.seq + off;
+            if (FIXED) {  // no exec-mask regions: two full words, and the third from a clamped address (inside the read) with a select
+                pre[0] = rd[lane];
+                pre[1] = rd[64 + lane];
+                const uint32_t c2 = rd[128 + lane < L ? 128 + lane : L - 1];
+                pre[2] = 128 + lane < L ? c2 : GS_FILL;
+            } else {
 #pragma unroll
-        for (int w = 0; w < 3; w++) pre[w] = 64 * w + lane < L ? rd[64 * w + lane] : GS_FILL;
-        gs_process_read<false, FROM_NODES, KC, WIDE, !LDS_STATS, STRIPED, CTX>(Q, st, r, off, L, lane, s_dvi, s_dcnt, wave_in_block, nullptr, nullptr, 0, pre,
-                                                     s_g[wave_in_block], s_cur[wave_in_block]);
-    }
+                for (int w = 0; w < 3; w++) pre[w] = 64 * w + lane < L ? rd[64 * w + lane] : GS_FILL;
+            }
+            gs_process_read<false, FROM_NODES, KC, WIDE, !LDS_STATS, STRIPED, CTX, FIXED>(Q, st, r, off, L, lane, s_dvi, s_dcnt, wave_in_block, nullptr, nullptr, 0,
+                                                                                          pre, s_g[wave_in_block], s_cur[wave_in_block], fixed_live1);
+        }
+    };
+    if constexpr (CAN_FIX) {
+        if (fixed_batch)  // (wave-uniform, from the kernel's arguments)
+            reads(std::true_type());
+        else
+            reads(std::false_type());
+    } else
+        reads(std::false_type());
 #if GS_PHASE
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     if (lane < 15) atomicAdd(&gs_phase_acc[lane], gs_phase_row()[lane]);
