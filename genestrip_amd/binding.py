@@ -46,6 +46,8 @@ ABI_SYMBOLS = (
     "gs_deflate_bound", "gs_deflate_host", "gs_deflate_host_reference", "gs_deflate_last_error", "gs_match_text_descriptors", "gs_match_submit_fixed",
     "gs_db_value_counts", "gs_dbexport_create", "gs_dbexport_fetch", "gs_dbexport_get_device", "gs_dbexport_fastq_begin",
     "gs_dbexport_fastq_next", "gs_dbexport_destroy",
+    "gs_dbquality_begin", "gs_dbquality_set_range", "gs_dbquality_add", "gs_dbquality_finish", "gs_dbquality_get_stats",
+    "gs_dbquality_destroy",
 )
 
 
@@ -132,6 +134,12 @@ def lib():
         "gs_dbbuild_fetch": (ci, [vp, vp, vp]),
         "gs_dbbuild_to_db": (ci, [vp, vp]),
         "gs_dbbuild_destroy": (ci, [vp]),
+        "gs_dbquality_begin": (ci, [vp, vp, ci, ci, ci]),
+        "gs_dbquality_set_range": (ci, [vp, C.c_uint64, C.c_uint64]),
+        "gs_dbquality_add": (ci, [vp, vp, vp, vp, i64, ci]),
+        "gs_dbquality_finish": (ci, [vp, vp, vp]),
+        "gs_dbquality_get_stats": (ci, [vp, vp]),
+        "gs_dbquality_destroy": (ci, [vp]),
         "gs_match_encode": (ci, [vp, vp, vp, i64, vp, vp]), "gs_match_probe_keys": (ci, [vp, vp, i64, vp]),
         "gs_match_encode_route": (ci, [vp, vp, vp, i64, vp, ci, i64, vp, vp, vp, vp, vp]),
         "gs_match_route_geometry": (ci, [vp, i64, vp, vp]),
@@ -633,6 +641,64 @@ class DeviceDbBuilder:
     def close(self):
         if getattr(self, "h", None):
             lib().gs_dbbuild_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DbQualityStats(C.Structure):
+    _fields_ = [("n_pairs", C.c_int64), ("n_distinct", C.c_int64), ("n_found", C.c_int64), ("n_store", C.c_int64),
+                ("ms_pairs", C.c_double), ("ms_sort", C.c_double), ("ms_decode", C.c_double), ("ms_join", C.c_double)]
+
+
+class DeviceDbQuality:
+    """gs_dbquality: per leaf value index tp / tp+fp / tp+fn of a store against its source genomes (the reference's dbqualcounts
+    goal, DBQualityCountsGoal.handleStore): k-mers are formed as in DeviceDbBuilder, de-duplicated exactly per (k-mer, leaf) and
+    looked up in the store on the device"""
+
+    def __init__(self, store, lower_case_bases=True, max_dust=-1, step_size=1):
+        self.store = store  # (the handle reads the store until close())
+        self.n_values = store.n_values
+        self.h = C.c_void_p()
+        _check(lib().gs_dbquality_begin(C.byref(self.h), store.h, int(lower_case_bases), max_dust, step_size))
+
+    def set_range(self, lo, hi):
+        """keep only the canonical k-mers in [lo, hi): before the first add of a pass; after finish() it starts the next pass
+        on this handle (one pass per range of kmer_ranges(); add the tp / tp+fn columns of the passes)"""
+        _check(lib().gs_dbquality_set_range(self.h, lo, hi))
+
+    def add(self, seq, offsets, leaf_vi):
+        """regions as for DeviceDbBuilder.add; leaf_vi: numpy int32[n], negative = the region counts nothing"""
+        ps, mem = _ptr(seq)
+        po, mem2 = _ptr(offsets)
+        assert mem == mem2, "seq and offsets must live in the same memory space"
+        lv = np.ascontiguousarray(leaf_vi, dtype=np.int32)
+        n = (offsets.shape[0] if hasattr(offsets, "shape") else len(offsets)) - 1
+        if len(lv) != n:
+            raise ValueError("leaf_vi must have one entry per region")
+        _ready(seq, offsets)
+        _check(lib().gs_dbquality_add(self.h, ps, po, lv.ctypes.data_as(C.c_void_p), n, mem))
+
+    def finish(self):
+        """-> (counts int64[n_values, 3]: tp, tp+fp, tp+fn; present uint8[n_values]): rows with present == 0 are absent"""
+        counts = np.zeros((self.n_values, 3), dtype=np.int64)
+        present = np.zeros(self.n_values, dtype=np.uint8)
+        _check(lib().gs_dbquality_finish(self.h, counts.ctypes.data_as(C.c_void_p), present.ctypes.data_as(C.c_void_p)))
+        return counts, present
+
+    def stats(self):
+        """sizes and phase times (ms) of the latest pass"""
+        st = DbQualityStats()
+        _check(lib().gs_dbquality_get_stats(self.h, C.byref(st)))
+        return st
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().gs_dbquality_destroy(self.h)
             self.h = None
 
     def __del__(self):

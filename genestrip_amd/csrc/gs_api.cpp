@@ -3881,6 +3881,311 @@ extern "C" int gs_dbbuild_destroy(gs_dbbuild *b) {
     return GS_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Store quality against its source genomes (gs_quality.hip; include/gsgpu.h "gs_dbquality")
+// ---------------------------------------------------------------------------------------------------
+struct GsQualityParams {  // (gs_quality.hip)
+    const u64 *keys;
+    const uint32_t *leaf;
+    int64_t n;
+    const u64 *skeys;
+    const uint32_t *svals;
+    int64_t m;
+    const int32_t *tin, *tout;
+    int32_t n_values;
+    u64 *counts;
+    u64 *stats;
+};
+extern "C" hipError_t gs_launch_quality_tag(uint32_t *vals, int64_t n, const uint32_t *leaf_of_region, int64_t n_regions, hipStream_t stream);
+extern "C" hipError_t gs_quality_sort_leaf(uint32_t *leaf, uint32_t *leaf_alt, u64 *keys, u64 *keys_alt, int64_t n, int bits, uint32_t **leaf_out,
+                                           u64 **keys_out, hipStream_t stream);
+extern "C" hipError_t gs_launch_quality_join(const GsQualityParams *P, int n_cu, hipStream_t stream);
+
+struct gs_dbquality {
+    gs_db *db = nullptr;
+    int device = 0, k = 0, lower = 1, step = 1, max_dust = -1;
+    int32_t n_values = 0;
+    hipStream_t stream = nullptr;
+    std::vector<int32_t> parent;  // the store's tree (host copy)
+    u64 *d_keys = nullptr;        // the (k-mer, leaf) pairs of this pass
+    uint32_t *d_vals = nullptr;
+    u64 *d_count = nullptr;
+    size_t cap = 0, n_pairs = 0;
+    u64 range_lo = 0, range_hi = ~0ULL;
+    uint8_t *d_seq = nullptr;  // staging of host input
+    size_t seq_cap = 0;
+    u64 *d_off = nullptr;
+    size_t off_cap = 0;
+    uint32_t *d_leaf = nullptr;  // leaf of each region of one add
+    size_t leaf_cap = 0;
+    int32_t one_leaf = -1;  // all regions so far carry this tag (-2: several)
+    bool added = false, finished = false;
+    gs_dbexport *store = nullptr;       // the store in ascending k-mer order, decoded once per handle
+    std::vector<int64_t> value_counts;  // gs_db_value_counts, once per handle
+    gs_dbquality_stats stats{};
+};
+
+static void dbquality_free_pass(gs_dbquality *q) {
+    for (void *p : {(void *)q->d_keys, (void *)q->d_vals, (void *)q->d_seq, (void *)q->d_off, (void *)q->d_leaf}) hipFree(p);
+    q->d_keys = nullptr;
+    q->d_vals = nullptr;
+    q->d_seq = nullptr;
+    q->d_off = nullptr;
+    q->d_leaf = nullptr;
+    q->cap = q->n_pairs = q->seq_cap = q->off_cap = q->leaf_cap = 0;
+}
+
+static void dbquality_free(gs_dbquality *q) {
+    hipSetDevice(q->device);
+    if (q->stream) hipStreamSynchronize(q->stream);
+    dbquality_free_pass(q);
+    hipFree(q->d_count);
+    if (q->store) gs_dbexport_destroy(q->store);
+    if (q->stream) hipStreamDestroy(q->stream);
+    delete q;
+}
+
+extern "C" int gs_dbquality_begin(gs_dbquality **out, gs_db *db, int lower_case_bases, int max_dust, int step_size) try {
+    if (!out) return fail(GS_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!db) return fail(GS_E_INVALID, "db is NULL");
+    if (step_size < 1) return fail(GS_E_INVALID, "stepSize must be >= 1 (C/GSConfigKey.java:236)");
+    if (max_dust > 32767) return fail(GS_E_INVALID, "maxDust > Short.MAX_VALUE (C/util/CGATLongBuffer.java:78-80)");
+    if (db->striped()) return fail(GS_E_UNSUPPORTED, "gs_dbquality needs the whole store on one device: this handle is a stripe");
+    HIP_TRY(hipSetDevice(db->device));
+    gs_dbquality *q = new gs_dbquality();
+    q->db = db;
+    q->device = db->device;
+    q->k = db->info.k;
+    q->n_values = db->info.n_values;
+    q->lower = lower_case_bases != 0;
+    q->step = step_size;
+    q->max_dust = max_dust < 0 ? -1 : max_dust;
+    q->parent.resize((size_t)q->n_values);
+    hipError_t e = hipStreamCreateWithFlags(&q->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc((void **)&q->d_count, sizeof(u64));
+    if (e == hipSuccess) e = hipMemset(q->d_count, 0, sizeof(u64));
+    if (e == hipSuccess) e = hipMemcpy(q->parent.data(), db->d_tree, sizeof(int32_t) * (size_t)q->n_values, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        dbquality_free(q);
+        return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbquality_begin: ") + hipGetErrorString(e));
+    }
+    *out = q;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_dbquality_set_range(gs_dbquality *q, uint64_t lo, uint64_t hi) {
+    if (!q || lo >= hi) return fail(GS_E_INVALID, "bad range");
+    if (q->added && !q->finished) return fail(GS_E_STATE, "gs_dbquality_set_range comes before the first gs_dbquality_add of a pass");
+    q->range_lo = lo;
+    q->range_hi = hi;
+    q->finished = false;  // (after gs_dbquality_finish: the next pass over the same store)
+    q->added = false;
+    q->one_leaf = -1;
+    q->stats.ms_pairs = 0;
+    return GS_OK;
+}
+
+extern "C" int gs_dbquality_add(gs_dbquality *q, const uint8_t *seq, const uint64_t *offsets, const int32_t *leaf_vi, int64_t n_regions,
+                                int mem) try {
+    if (!q || n_regions < 0 || (n_regions > 0 && (!seq || !offsets || !leaf_vi))) return fail(GS_E_INVALID, "bad argument");
+    if (q->finished) return fail(GS_E_STATE, "gs_dbquality_finish has been called (gs_dbquality_set_range starts another pass)");
+    if (n_regions == 0) return GS_OK;
+    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    if (n_regions >= ((int64_t)1 << 31)) return fail(GS_E_UNSUPPORTED, "more than 2^31 regions");
+    HIP_TRY(hipSetDevice(q->device));
+    // leaf_vi is a host array in both cases; negative or a value without a node: the region counts nothing (leafNode == null)
+    std::vector<uint32_t> leaf((size_t)n_regions);
+    int32_t one = q->one_leaf;
+    for (int64_t r = 0; r < n_regions; r++) {
+        const int32_t v = leaf_vi[r];
+        if (v >= q->n_values) return fail(GS_E_INVALID, "leaf_vi: not a value of the store");
+        const int32_t tag = (v < 0 || q->parent[(size_t)v] == -2) ? q->n_values : v;
+        leaf[(size_t)r] = (uint32_t)tag;
+        one = one == -1 ? tag : (one == tag ? one : -2);
+    }
+    std::vector<uint64_t> hoff;
+    const uint64_t *off_host = offsets;
+    if (mem == GS_MEM_DEVICE) {
+        hoff.resize((size_t)n_regions + 1);
+        HIP_TRY(hipMemcpy(hoff.data(), offsets, sizeof(uint64_t) * ((size_t)n_regions + 1), hipMemcpyDeviceToHost));
+        off_host = hoff.data();
+    }
+    if (off_host[0] != 0) return fail(GS_E_INVALID, "offsets[0] must be 0");
+    for (int64_t r = 0; r < n_regions; r++)
+        if (off_host[r + 1] < off_host[r]) return fail(GS_E_INVALID, "offsets must not decrease");
+    const int64_t total = (int64_t)off_host[n_regions];
+    const uint8_t *d_seq = seq;
+    const u64 *d_off = (const u64 *)offsets;
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = grow(&q->d_leaf, &q->leaf_cap, (size_t)n_regions, q->stream);
+    if (rc) return rc;
+    if (mem == GS_MEM_HOST) {
+        rc = grow(&q->d_seq, &q->seq_cap, (size_t)std::max<int64_t>(total, 1), q->stream);
+        if (!rc) rc = grow(&q->d_off, &q->off_cap, (size_t)n_regions + 1, q->stream);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(q->d_seq, seq, (size_t)total, hipMemcpyHostToDevice, q->stream));
+        HIP_TRY(hipMemcpyAsync(q->d_off, offsets, sizeof(u64) * ((size_t)n_regions + 1), hipMemcpyHostToDevice, q->stream));
+        d_seq = q->d_seq;
+        d_off = q->d_off;
+    }
+    HIP_TRY(hipMemcpyAsync(q->d_leaf, leaf.data(), sizeof(uint32_t) * (size_t)n_regions, hipMemcpyHostToDevice, q->stream));
+    if (q->n_pairs + (size_t)total > q->cap) {  // the pair buffers grow by doubling
+        size_t want = std::max(q->cap * 2, q->n_pairs + (size_t)total);
+        want = std::max<size_t>(want, 1 << 20);
+        u64 *nk = nullptr;
+        uint32_t *nvl = nullptr;
+        hipError_t e = hipMalloc((void **)&nk, want * sizeof(u64));
+        if (e == hipSuccess) e = hipMalloc((void **)&nvl, want * sizeof(uint32_t));
+        if (e == hipSuccess && q->n_pairs) e = hipMemcpyAsync(nk, q->d_keys, q->n_pairs * sizeof(u64), hipMemcpyDeviceToDevice, q->stream);
+        if (e == hipSuccess && q->n_pairs) e = hipMemcpyAsync(nvl, q->d_vals, q->n_pairs * sizeof(uint32_t), hipMemcpyDeviceToDevice, q->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(q->stream);
+        if (e != hipSuccess) {
+            hipFree(nk);
+            hipFree(nvl);
+            return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbquality_add: ") + hipGetErrorString(e));
+        }
+        hipFree(q->d_keys);
+        hipFree(q->d_vals);
+        q->d_keys = nk;
+        q->d_vals = nvl;
+        q->cap = want;
+    }
+    // the builder's kernel with region numbers from 0, then region -> leaf on the pairs it has just written
+    HIP_TRY(gs_launch_build_kmers(d_seq, d_off, n_regions, total, q->k, q->lower, q->step, q->max_dust, 0u, 0, q->range_lo, q->range_hi, q->d_keys,
+                                  q->d_vals, q->d_count, q->stream));
+    u64 have = 0;
+    HIP_TRY(hipMemcpyAsync(&have, q->d_count, sizeof(u64), hipMemcpyDeviceToHost, q->stream));
+    HIP_TRY(hipStreamSynchronize(q->stream));
+    if (have < q->n_pairs || have > q->cap) return fail(GS_E_HIP, "gs_dbquality_add: pair counter out of range");
+    HIP_TRY(gs_launch_quality_tag(q->d_vals + q->n_pairs, (int64_t)(have - q->n_pairs), q->d_leaf, n_regions, q->stream));
+    HIP_TRY(hipStreamSynchronize(q->stream));  // (the caller's arrays and the staging buffers are free again)
+    q->n_pairs = (size_t)have;
+    q->one_leaf = one;
+    q->added = true;
+    q->stats.ms_pairs += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_dbquality_finish(gs_dbquality *q, int64_t *counts, uint8_t *present) try {
+    if (!q || !counts || !present) return fail(GS_E_INVALID, "NULL argument");
+    if (q->finished) return fail(GS_E_STATE, "gs_dbquality_finish has been called (gs_dbquality_set_range starts another pass)");
+    HIP_TRY(hipSetDevice(q->device));
+    const int32_t nv = q->n_values;
+    const int64_t n = (int64_t)q->n_pairs;
+    using clk = std::chrono::steady_clock;
+    auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
+    int rc = GS_OK;
+    u64 *keys_alt = nullptr, *d_cnt = nullptr;
+    uint32_t *vals_alt = nullptr;
+    std::vector<u64> h_cnt(2 * (size_t)nv + 2, 0);
+    auto check = [&](hipError_t e, const char *what) {
+        if (e != hipSuccess && rc == GS_OK) rc = fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbquality_finish (") + what + "): " + hipGetErrorString(e));
+        return e == hipSuccess;
+    };
+    // the staging buffers make room for the sort
+    for (void *p : {(void *)q->d_seq, (void *)q->d_off, (void *)q->d_leaf}) hipFree(p);
+    q->d_seq = nullptr;
+    q->d_off = nullptr;
+    q->d_leaf = nullptr;
+    q->seq_cap = q->off_cap = q->leaf_cap = 0;
+    q->stats.n_pairs = n;
+    q->stats.n_distinct = q->stats.n_found = 0;
+    q->stats.ms_sort = q->stats.ms_join = 0;
+    // once per handle: the store in ascending k-mer order on the device, and its k-mers per value
+    if (!q->store) {
+        const auto t0 = clk::now();
+        int64_t m = 0;
+        rc = gs_dbexport_create(&q->store, q->db, -1, 0, &m);
+        if (rc == GS_OK) {
+            q->value_counts.assign((size_t)nv, 0);
+            rc = gs_db_value_counts(q->db, q->value_counts.data());
+        }
+        if (rc != GS_OK) {
+            if (q->store) gs_dbexport_destroy(q->store);
+            q->store = nullptr;
+            return rc;
+        }
+        HIP_TRY(hipSetDevice(q->device));
+        q->stats.ms_decode = ms_since(t0);
+        q->stats.n_store = m;
+    }
+    if (n > 0) {
+        u64 *ks = q->d_keys;
+        uint32_t *vs = q->d_vals;
+        auto t0 = clk::now();
+        bool ok = check(hipMalloc((void **)&keys_alt, (size_t)n * sizeof(u64)), "sort buffers") &&
+                  check(hipMalloc((void **)&vals_alt, (size_t)n * sizeof(uint32_t)), "sort buffers");
+        if (ok && q->one_leaf == -2) {  // several leaves: the leaf bits first, the stable k-mer sort keeps their order
+            int bits = 1;
+            while (((int64_t)1 << bits) <= (int64_t)nv) bits++;
+            ok = check(gs_quality_sort_leaf(q->d_vals, vals_alt, q->d_keys, keys_alt, n, bits, &vs, &ks, q->stream), "leaf sort");
+        }
+        if (ok) {
+            u64 *ka = ks == q->d_keys ? keys_alt : q->d_keys;
+            uint32_t *va = vs == q->d_vals ? vals_alt : q->d_vals;
+            ok = check(gs_build_sort(ks, ka, vs, va, n, 2 * q->k, &ks, &vs, q->stream), "sort");
+        }
+        q->stats.ms_sort = ms_since(t0);
+        t0 = clk::now();
+        if (ok) {
+            GsQualityParams P{};
+            P.keys = ks;
+            P.leaf = vs;
+            P.n = n;
+            P.skeys = q->store->d_keys;
+            P.svals = q->store->d_vals;
+            P.m = q->store->n;
+            P.tin = q->db->dev.tin;
+            P.tout = q->db->dev.tout;
+            P.n_values = nv;
+            ok = check(hipMalloc((void **)&d_cnt, h_cnt.size() * sizeof(u64)), "counts") &&
+                 check(hipMemsetAsync(d_cnt, 0, h_cnt.size() * sizeof(u64), q->stream), "counts");
+            P.counts = d_cnt;
+            P.stats = d_cnt + 2 * (size_t)nv;
+            ok = ok && check(gs_launch_quality_join(&P, q->db->n_cu, q->stream), "join") &&
+                 check(hipMemcpyAsync(h_cnt.data(), d_cnt, h_cnt.size() * sizeof(u64), hipMemcpyDeviceToHost, q->stream), "counts") &&
+                 check(hipStreamSynchronize(q->stream), "join");
+        }
+        q->stats.ms_join = ms_since(t0);
+    }
+    hipFree(keys_alt);
+    hipFree(vals_alt);
+    hipFree(d_cnt);
+    dbquality_free_pass(q);
+    HIP_TRY(hipMemset(q->d_count, 0, sizeof(u64)));
+    q->finished = true;  // (also after a failure: the pairs are gone)
+    if (rc != GS_OK) return rc;
+    q->stats.n_distinct = (int64_t)h_cnt[2 * (size_t)nv];
+    q->stats.n_found = (int64_t)h_cnt[2 * (size_t)nv + 1];
+    // tp+fp: the stored k-mers on the path leaf -> root (getPathSum, DBQualityCountsGoal.java:137-147, :315-321)
+    for (int32_t v = 0; v < nv; v++) {
+        int64_t *row = counts + 3 * (size_t)v;
+        row[0] = row[1] = row[2] = 0;
+        present[v] = 0;
+        if (h_cnt[2 * (size_t)v + 1] == 0) continue;
+        present[v] = 1;
+        row[0] = (int64_t)h_cnt[2 * (size_t)v];
+        row[2] = (int64_t)h_cnt[2 * (size_t)v + 1];
+        for (int32_t a = v; a >= 0; a = q->parent[(size_t)a]) row[1] += q->value_counts[(size_t)a];
+    }
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_dbquality_get_stats(gs_dbquality *q, gs_dbquality_stats *out) {
+    if (!q || !out) return fail(GS_E_INVALID, "NULL argument");
+    *out = q->stats;
+    return GS_OK;
+}
+
+extern "C" int gs_dbquality_destroy(gs_dbquality *q) {
+    if (q) dbquality_free(q);
+    return GS_OK;
+}
+
 // ---- DB-partitioned mode: encode / probe / reduce as separate steps (all pointers are device pointers)
 extern "C" int gs_match_encode(gs_run *run, const uint8_t *seq, const uint64_t *offsets, int64_t n_reads,
                                const uint64_t *pos_off, uint64_t *keys) {

@@ -11,26 +11,9 @@ extern "C" int gs_host_java_double(double v, char *buf, int cap) {
     return GS_OK;
 }
 
-// ---------------------------------------------------------------------------------------------------
-// completeResults + CSV
-// ---------------------------------------------------------------------------------------------------
-extern "C" int gs_host_write_csv(const char *path, const gs_host_tax_info *tax, const int64_t *table, const double *dtable,
-                                 const gs_host_totals *totals) try {
-    if (!path || !tax || !table || !totals || !tax->parent_vi || !tax->taxids || !tax->db_kmers)
-        return hfail(GS_E_INVALID, "NULL argument");
+// tree order (sortTaxidsViaTree, SmallTaxTree.iterator): by position; default pre-order over children in value-index order
+static std::vector<int> tree_positions(const gs_host_tax_info *tax) {
     const int nv = tax->n_values;
-    // rows: every value with a CountsPerTaxid (>= 1 hit k-mer or >= 1 classified read) plus all their ancestors
-    // (MatchingResult.java:88-98)
-    std::vector<char> present((size_t)nv, 0);
-    for (int v = 0; v < nv; v++) {
-        const int64_t *row = table + (size_t)v * GS_N_COLS;
-        if (tax->parent_vi[v] != -2 && (row[GS_C_READS] > 0 || row[GS_C_READS_1KMER] > 0)) present[(size_t)v] = 1;
-    }
-    for (int v = 0; v < nv; v++)
-        if (present[(size_t)v] == 1)
-            for (int a = tax->parent_vi[v]; a >= 0; a = tax->parent_vi[a])
-                if (!present[(size_t)a]) present[(size_t)a] = 2;
-    // tree order (sortTaxidsViaTree): by position; default pre-order over children in value-index order
     std::vector<int> pos((size_t)nv, 0);
     if (tax->position) {
         for (int v = 0; v < nv; v++) pos[(size_t)v] = tax->position[v];
@@ -52,6 +35,29 @@ extern "C" int gs_host_write_csv(const char *path, const gs_host_tax_info *tax, 
             for (auto it = kids[(size_t)v].rbegin(); it != kids[(size_t)v].rend(); ++it) stack.push_back(*it);
         }
     }
+    return pos;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// completeResults + CSV
+// ---------------------------------------------------------------------------------------------------
+extern "C" int gs_host_write_csv(const char *path, const gs_host_tax_info *tax, const int64_t *table, const double *dtable,
+                                 const gs_host_totals *totals) try {
+    if (!path || !tax || !table || !totals || !tax->parent_vi || !tax->taxids || !tax->db_kmers)
+        return hfail(GS_E_INVALID, "NULL argument");
+    const int nv = tax->n_values;
+    // rows: every value with a CountsPerTaxid (>= 1 hit k-mer or >= 1 classified read) plus all their ancestors
+    // (MatchingResult.java:88-98)
+    std::vector<char> present((size_t)nv, 0);
+    for (int v = 0; v < nv; v++) {
+        const int64_t *row = table + (size_t)v * GS_N_COLS;
+        if (tax->parent_vi[v] != -2 && (row[GS_C_READS] > 0 || row[GS_C_READS_1KMER] > 0)) present[(size_t)v] = 1;
+    }
+    for (int v = 0; v < nv; v++)
+        if (present[(size_t)v] == 1)
+            for (int a = tax->parent_vi[v]; a >= 0; a = tax->parent_vi[a])
+                if (!present[(size_t)a]) present[(size_t)a] = 2;
+    const std::vector<int> pos = tree_positions(tax);
     std::vector<int> rows;
     for (int v = 0; v < nv; v++)
         if (present[(size_t)v]) rows.push_back(v);
@@ -201,6 +207,116 @@ extern "C" int gs_host_write_csv(const char *path, const gs_host_tax_info *tax, 
         o.push_back('\n');
     }
     // the CSV is the bit-exact deliverable: a short write (full disk, I/O error) must not pass for a result
+    const bool written = fwrite(o.data(), 1, o.size(), f) == o.size();
+    const bool closed = fclose(f) == 0;
+    if (!written || !closed) return hfail(GS_E_IO, std::string("short write to ") + path);
+    return GS_OK;
+} catch (const std::bad_alloc &) {
+    return hfail(GS_E_NOMEM, "out of host memory");
+} catch (const std::exception &e) {  // (nothing may leave through the C ABI)
+    return hfail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
+}
+
+// ---------------------------------------------------------------------------------------------------
+// the dbquality goal's CSV: the rank aggregation of DBQualityCountsGoal.doMakeThis (:149-173, Counts.aggregate :427-434) and
+// DBQualityCSVGoal.makeFile (:89-128)
+// ---------------------------------------------------------------------------------------------------
+namespace {
+struct QualityCounts {  // DBQualityCountsGoal.Counts
+    int64_t tp = 0, tp_fp = 0, tp_fn = 0;
+    int aggregations = 0;
+    double agg_precision_sum = 0, agg_recall_sum = 0;
+    double precision() const { return (double)tp / (double)tp_fp; }
+    double recall() const { return (double)tp / (double)tp_fn; }
+    double avg_precision() const { return agg_precision_sum == 0 ? precision() : agg_precision_sum / aggregations; }
+    double avg_recall() const { return agg_recall_sum == 0 ? recall() : agg_recall_sum / aggregations; }
+    void aggregate(const QualityCounts &c) {
+        tp += c.tp;
+        tp_fp += c.tp_fp;
+        tp_fn += c.tp_fn;
+        aggregations++;
+        agg_precision_sum += c.avg_precision();
+        agg_recall_sum += c.avg_recall();
+    }
+};
+
+// DecimalFormat("0.00000000", Locale.US): 8 decimals, half-even on the exact binary value
+void append_df8(std::string &o, double v) {
+    if (std::isnan(v))
+        o += "NaN";
+    else if (std::isinf(v))
+        o += v < 0 ? "-\xe2\x88\x9e" : "\xe2\x88\x9e";
+    else {
+        char buf[400];
+        snprintf(buf, sizeof buf, "%.8f", v);
+        o += strcmp(buf, "-0.00000000") == 0 ? buf + 1 : buf;
+    }
+    o.push_back(';');
+}
+}  // namespace
+
+extern "C" int gs_host_write_quality_csv(const char *path, const gs_host_tax_info *tax, const int64_t *counts, const uint8_t *present) try {
+    if (!path || !tax || !counts || !present || !tax->parent_vi || !tax->taxids) return hfail(GS_E_INVALID, "NULL argument");
+    const int nv = tax->n_values;
+    for (int v = 0; v < nv; v++)
+        if (tax->parent_vi[v] < -2 || tax->parent_vi[v] >= nv) return hfail(GS_E_INVALID, "parent_vi out of range");
+    const std::vector<int> pos = tree_positions(tax);
+    std::vector<int> order;
+    for (int v = 0; v < nv; v++)
+        if (tax->parent_vi[v] != -2) order.push_back(v);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pos[(size_t)a] < pos[(size_t)b]; });
+    std::vector<QualityCounts> row((size_t)nv);
+    std::vector<char> has((size_t)nv, 0);  // 1: a row of its own, 2: aggregated
+    for (int v : order)
+        if (present[v]) {
+            has[(size_t)v] = 1;
+            row[(size_t)v].tp = counts[3 * (size_t)v];
+            row[(size_t)v].tp_fp = counts[3 * (size_t)v + 1];
+            row[(size_t)v].tp_fn = counts[3 * (size_t)v + 2];
+        }
+    static const char *agg_ranks[4] = {"cellular root", "acellular root", "species", "genus"};
+    if (tax->ranks)
+        for (int v : order) {
+            if (has[(size_t)v] != 1) continue;
+            for (const char *rank : agg_ranks) {
+                int a = v, steps = 0;
+                while (a >= 0 && !(tax->ranks[a] && strcmp(tax->ranks[a], rank) == 0)) {
+                    a = tax->parent_vi[a];
+                    if (++steps > nv) return hfail(GS_E_INVALID, "parent_vi contains a cycle");
+                }
+                if (a >= 0 && has[(size_t)a] != 1) {  // (no aggregation into nodes that have their own counts)
+                    has[(size_t)a] = 2;
+                    row[(size_t)a].aggregate(row[(size_t)v]);
+                }
+            }
+        }
+    std::string o = "taxid;name;rank;parent taxid;tp;tp+fp;tp+fn;precision;recall;weighted avg precision;weighted avg recall;\n";
+    for (int v : order) {
+        if (!has[(size_t)v]) continue;
+        const QualityCounts &c = row[(size_t)v];
+        o += tax->taxids[v] ? tax->taxids[v] : "null";
+        o.push_back(';');
+        o += (tax->names && tax->names[v]) ? tax->names[v] : "null";
+        o.push_back(';');
+        if (tax->ranks && tax->ranks[v]) o += tax->ranks[v];
+        o.push_back(';');
+        const int p = tax->parent_vi[v];
+        o += p >= 0 ? (tax->taxids[p] ? tax->taxids[p] : "null") : "null";
+        o.push_back(';');
+        append_int(o, c.tp);
+        o.push_back(';');
+        append_int(o, c.tp_fp);
+        o.push_back(';');
+        append_int(o, c.tp_fn);
+        o.push_back(';');
+        append_df8(o, c.avg_precision());  // (the reference's column order: the columns NAMED precision / recall are the averages)
+        append_df8(o, c.avg_recall());
+        append_df8(o, c.precision());
+        append_df8(o, c.recall());
+        o.push_back('\n');
+    }
+    FILE *f = fopen(path, "wb");
+    if (!f) return hfail(GS_E_INVALID, std::string("cannot open ") + path);
     const bool written = fwrite(o.data(), 1, o.size(), f) == o.size();
     const bool closed = fclose(f) == 0;
     if (!written || !closed) return hfail(GS_E_IO, std::string("short write to ") + path);

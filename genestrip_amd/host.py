@@ -55,6 +55,7 @@ def lib():
         "gs_host_release_pools": (ci, []),
         "gs_host_filter_files": (ci, [vp, ci, ci, C.c_double, vp, ci, C.c_char_p, C.c_char_p, ci, vp]),
         "gs_host_write_csv": (ci, [C.c_char_p, vp, vp, vp, vp]),
+        "gs_host_write_quality_csv": (ci, [C.c_char_p, vp, vp, vp]),
         "gs_host_db2fastq": (ci, [vp, vp, C.c_char_p, C.c_int32, ci, C.c_char_p, vp]),
         "gs_host_last_error": (C.c_char_p, []), "gs_host_java_double": (ci, [C.c_double, vp, ci]),
         "gs_host_gunzip": (ci, [vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]),
@@ -210,6 +211,22 @@ def write_csv(path, parent_vi, taxids, db_kmers, db_kmers_total, table, dtable, 
     d = np.ascontiguousarray(dtable, dtype=np.float64)
     _check(lib().gs_host_write_csv(str(path).encode(), C.byref(info), t.ctypes.data_as(C.c_void_p),
                                    d.ctypes.data_as(C.c_void_p), C.byref(totals)))
+
+
+def write_quality_csv(path, parent_vi, taxids, counts, present, names=None, ranks=None, position=None):
+    """the dbquality goal's CSV (DBQualityCountsGoal's rank aggregation + DBQualityCSVGoal.makeFile) from
+    DeviceDbQuality.finish(): counts int64[n_values, 3] = tp, tp+fp, tp+fn and present uint8[n_values]"""
+    pv = np.ascontiguousarray(parent_vi, dtype=np.int32)
+    c = np.ascontiguousarray(counts, dtype=np.int64)
+    pr = np.ascontiguousarray(present, dtype=np.uint8)
+    if c.shape != (len(pv), 3) or pr.shape != (len(pv),) or len(taxids) != len(pv):
+        raise ValueError("counts must be [n_values, 3], present and taxids [n_values]")
+    pos = None if position is None else np.ascontiguousarray(position, dtype=np.int32)
+    keep = [_cstr_array(taxids), _cstr_array(names), _cstr_array(ranks)]
+    info = _TaxInfo(len(pv), pv.ctypes.data_as(C.c_void_p), None if pos is None else pos.ctypes.data_as(C.c_void_p),
+                    keep[0], keep[1], keep[2], None, 0, None, None, 0)
+    _check(lib().gs_host_write_quality_csv(str(path).encode(), C.byref(info), c.ctypes.data_as(C.c_void_p),
+                                           pr.ctypes.data_as(C.c_void_p)))
 
 
 def db2fastq(store, taxids, project, path, select=None, with_desc=True):

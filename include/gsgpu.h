@@ -382,6 +382,64 @@ int gs_dbbuild_to_db(gs_dbbuild *b, gs_db **out);
 int gs_dbbuild_destroy(gs_dbbuild *b);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Store quality against its source genomes (genestrip_amd/csrc/gs_quality.hip): the compute core of the reference's
+ * dbqualcounts goal (ft/src/main/java/org/metagene/genestrip/finertree/goals/DBQualityCountsGoal.java, MyFastaReader.handleStore
+ * :250-289 and doMakeThis :137-147).  The genomes are walked again and every k-mer is looked up in the finished store; per
+ * leaf value index three counts come back:
+ *   tp      distinct k-mers of the leaf's genomes that are stored under the leaf's node or one of its ancestors
+ *   tp+fp   all k-mers stored on the path leaf -> root (the sum of gs_db_value_counts over that path)
+ *   tp+fn   distinct k-mers of the leaf's genomes that are stored at all (under a value that has a tree node)
+ * precision = tp / (tp+fp), recall = tp / (tp+fn) (gs_host_write_quality_csv, include/gshost.h).
+ *
+ *   gs_dbquality_begin      k, n_values and the tree are the store's; lower_case_bases / max_dust / step_size as for gs_dbbuild_begin:
+ *                           k-mers are formed exactly as there.  The store must stay alive until gs_dbquality_destroy.  A stripe
+ *                           of a striped store (gs_db_create_stripe, _striped, gs_db_load_stripe, _striped): GS_E_UNSUPPORTED.  A
+ *                           partition store (gs_db_create_part) is taken as the store it is: the counts are those of its part
+ *                           (tp and tp+fn of all parts add up to the whole store's).
+ *   gs_dbquality_add        regions as for gs_dbbuild_add (seq, offsets[n_regions + 1], `mem`); leaf_vi[n_regions] (host) = value
+ *                           index of each region's leaf node, the host's resolution of AbstractUpdateFastaReader.updateLeafNode
+ *                           (id node, file node or data child, else the tax node; an inner node of the tree is as good as a
+ *                           leaf).  leaf_vi < 0 or a value without a node (parent_vi == -2): the region counts nothing
+ *                           (leafNode == null).  leaf_vi >= n_values: GS_E_INVALID.  No work on the store here.
+ *   gs_dbquality_finish     sorts the (k-mer, leaf) pairs, joins the distinct ones with the store in ascending k-mer order (decoded
+ *                           on the device once per handle, as gs_dbexport_create does) and counts.  counts[n_values][3] = tp,
+ *                           tp+fp, tp+fn and present[n_values] (both host): a leaf with tp+fn > 0 has present = 1 and its three
+ *                           counts; every other row is absent (the reference's map has no entry): 0, 0, 0 and present = 0.
+ *                           The pairs' device memory is released here; the decoded store at gs_dbquality_destroy.
+ *   gs_dbquality_set_range  as gs_dbbuild_set_range: before the first gs_dbquality_add of a pass, keep only the canonical k-mers in
+ *                           [lo, hi).  tp and tp+fn are additive over disjoint ranges (the pairs partition by k-mer): a collection
+ *                           whose pairs do not fit the GPU (24 bytes per genome base at the peak) runs range by range and the
+ *                           caller adds the tp / tp+fn columns.  tp+fp does not depend on the range; it is filled for the leaves
+ *                           with tp+fn > 0 in THAT range.  Called after gs_dbquality_finish it starts the next pass on the same
+ *                           handle, which keeps the decoded store; without it a finished handle takes no further add or finish
+ *                           (GS_E_STATE).
+ *   gs_dbquality_get_stats  sizes and wall-clock phase times of the latest pass (tools/db_quality_rate.py).
+ *
+ * One difference to the reference: it removes duplicate (k-mer, leaf) pairs with an XOR Bloom filter (XORKMerIndexBloomFilter,
+ * ftBloomFilterFpp), so a false positive silently drops a pair that was never counted -- which pairs depends on the insertion
+ * order of its reader threads.  Here de-duplication is exact (sort + heads of runs): the result is the reference's at
+ * fpp -> 0, and it is deterministic.  (Compare the builder's note on putLong above.)  The store is only read, and seen bits are
+ * masked as in the export: these calls may run while a unique-counting run is alive on the store.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct gs_dbquality gs_dbquality;
+typedef struct {
+    int64_t n_pairs;    /* (k-mer, leaf) pairs enumerated in this pass                      */
+    int64_t n_distinct; /* distinct pairs of the leaves that count                          */
+    int64_t n_found;    /* ... whose k-mer is stored (the sum of the tp+fn column)          */
+    int64_t n_store;    /* k-mers of the decoded store                                      */
+    double ms_pairs;    /* gs_dbquality_add calls of this pass (copy + k-mer kernel)        */
+    double ms_sort;     /* leaf sort + k-mer sort                                           */
+    double ms_decode;   /* store decode + sort + per-value counts (paid by the first pass)  */
+    double ms_join;     /* join + classify + count                                          */
+} gs_dbquality_stats;
+int gs_dbquality_begin(gs_dbquality **out, gs_db *db, int lower_case_bases, int max_dust, int step_size);
+int gs_dbquality_set_range(gs_dbquality *q, uint64_t lo, uint64_t hi);
+int gs_dbquality_add(gs_dbquality *q, const uint8_t *seq, const uint64_t *offsets, const int32_t *leaf_vi, int64_t n_regions, int mem);
+int gs_dbquality_finish(gs_dbquality *q, int64_t *counts, uint8_t *present);
+int gs_dbquality_get_stats(gs_dbquality *q, gs_dbquality_stats *out);
+int gs_dbquality_destroy(gs_dbquality *q);
+
+/* ---------------------------------------------------------------------------------------------------
  * DB-partitioned match, the split pipeline of round 1 (kept: it also serves stores without records): the store is split
  * over the GPUs of a node by key hash (gs_db_create_part keeps the keys with (h >> 40) % n_parts == part, h = the library's mixed key), reads stay
  * on their home GPU.  Per batch: gs_match_encode (reads -> h of every k-mer position; ~0 marks a window with a

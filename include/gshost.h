@@ -13,6 +13,7 @@
  *   gs_host_filter_files  FastqBloomFilter.runFilter (C/bloom/FastqBloomFilter.java:80-105)
  *   gs_host_write_csv     MatchingResult.completeResults + ResultReporter.printMatchResult
  *                         (C/match/MatchingResult.java:84-118, C/match/ResultReporter.java:190-279)
+ *   gs_host_write_quality_csv  the dbquality goal's CSV (DBQualityCountsGoal's rank aggregation + DBQualityCSVGoal.makeFile)
  * (C/ = core/src/main/java/org/metagene/genestrip/, B/ = base/src/main/java/org/metagene/genestrip/)
  */
 #ifndef GSHOST_H
@@ -134,6 +135,19 @@ typedef struct {
 
 int gs_host_write_csv(const char *path, const gs_host_tax_info *tax, const int64_t *table, const double *dtable,
                       const gs_host_totals *totals);
+
+/* ---- the dbquality goal's CSV (ft/src/main/java/org/metagene/genestrip/finertree/goals/DBQualityCountsGoal.java:149-173 with
+ * Counts.aggregate and its getters, DBQualityCSVGoal.makeFile) from the output of gs_dbquality_finish (include/gsgpu.h):
+ * counts[n_values][3] = tp, tp+fp, tp+fn and present[n_values].  Every present node, in tree order (ascending `position`,
+ * pre-order when NULL), is aggregated into its nearest ancestor-or-self of each of the ranks "cellular root", "acellular root",
+ * "species", "genus" that has no row of its own: the three counts are added, and the row's precision and recall sums gain the
+ * child's values.  One line per node with a row, in tree order:
+ *   taxid;name;rank;parent taxid;tp;tp+fp;tp+fn;precision;recall;weighted avg precision;weighted avg recall;
+ * with `null` as the root's parent and the doubles as DecimalFormat("0.00000000") in Locale.US prints them.  As in the
+ * reference the columns named precision / recall hold the UNWEIGHTED average over the aggregated nodes (a row of its own: tp /
+ * (tp+fp), tp / (tp+fn)), the columns named weighted avg ... hold tp / (tp+fp) and tp / (tp+fn) of the added counts.  Of `tax`
+ * only n_values, parent_vi, position, taxids, names and ranks are read. ---- */
+int gs_host_write_quality_csv(const char *path, const gs_host_tax_info *tax, const int64_t *counts, const uint8_t *present);
 
 /* The host layer keeps page-locked blocks and the device decoders of gzip input (gigabytes of HBM) from call to call; this hands
  * them back (a long-lived JVM host before it loads a big store).  No other thread may be inside the host layer meanwhile. */

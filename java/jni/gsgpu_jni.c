@@ -93,6 +93,50 @@ JNIEXPORT jlong JNICALL JNAME(dbBuildToDb)(JNIEnv *env, jclass c, jlong builder)
 
 JNIEXPORT void JNICALL JNAME(dbBuildDestroy)(JNIEnv *env, jclass c, jlong builder) { gs_dbbuild_destroy((gs_dbbuild *)(intptr_t)builder); }
 
+/* ---- store quality, the gs_dbquality family: DBQualityCountsGoal.handleStore.  The capacities are ByteBuffer.capacity() of the buffer in front of them, handed
+ * in by the public wrappers of GsGpuNative: every array is checked against them before the library reads or writes it. ---- */
+static void throw_short(JNIEnv *env, const char *what) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "gsgpu: buffer too small or missing: %s", what);
+    (*env)->ThrowNew(env, (*env)->FindClass(env, "java/lang/IllegalArgumentException"), msg);
+}
+
+JNIEXPORT jlong JNICALL JNAME(dbQualityBegin)(JNIEnv *env, jclass c, jlong db, jboolean lowerCaseBases, jint maxDust, jint stepSize) {
+    gs_dbquality *q = NULL;
+    int rc = gs_dbquality_begin(&q, (gs_db *)(intptr_t)db, lowerCaseBases ? 1 : 0, maxDust, stepSize);
+    if (rc) throw_gs(env, rc);
+    return (jlong)(intptr_t)q;
+}
+
+JNIEXPORT void JNICALL JNAME(dbQualitySetRange)(JNIEnv *env, jclass c, jlong quality, jlong lo, jlong hi) {
+    int rc = gs_dbquality_set_range((gs_dbquality *)(intptr_t)quality, (uint64_t)lo, (uint64_t)hi);
+    if (rc) throw_gs(env, rc);
+}
+
+JNIEXPORT void JNICALL JNAME(dbQualityAdd0)(JNIEnv *env, jclass c, jlong quality, jobject bases, jlong basesCap, jobject offsets,
+                                            jlong offsetsCap, jobject leafVi, jlong leafViCap, jlong nRegions) {
+    const uint64_t *off = (const uint64_t *)addr(env, offsets);
+    if (nRegions < 0 || nRegions > (INT64_MAX >> 4)) return throw_short(env, "nRegions");
+    if (nRegions > 0) {
+        if (!off || offsetsCap < 8 * (nRegions + 1)) return throw_short(env, "offsets (nRegions + 1 x int64)");
+        if (!addr(env, leafVi) || leafViCap < 4 * nRegions) return throw_short(env, "leafVi (nRegions x int32)");
+        if (!addr(env, bases) || basesCap < 0 || off[nRegions] > (uint64_t)basesCap) return throw_short(env, "bases (offsets[nRegions] bytes)");
+    }
+    int rc = gs_dbquality_add((gs_dbquality *)(intptr_t)quality, (const uint8_t *)addr(env, bases), off, (const int32_t *)addr(env, leafVi),
+                              nRegions, GS_MEM_HOST);
+    if (rc) throw_gs(env, rc);
+}
+
+JNIEXPORT void JNICALL JNAME(dbQualityFinish0)(JNIEnv *env, jclass c, jlong quality, jint nValues, jobject counts, jlong countsCap,
+                                               jobject present, jlong presentCap) {
+    if (nValues < 0 || !addr(env, counts) || countsCap < 24 * (jlong)nValues) return throw_short(env, "counts (nValues x 3 x int64)");
+    if (!addr(env, present) || presentCap < (jlong)nValues) return throw_short(env, "present (nValues bytes)");
+    int rc = gs_dbquality_finish((gs_dbquality *)(intptr_t)quality, (int64_t *)addr(env, counts), (uint8_t *)addr(env, present));
+    if (rc) throw_gs(env, rc);
+}
+
+JNIEXPORT void JNICALL JNAME(dbQualityDestroy)(JNIEnv *env, jclass c, jlong quality) { gs_dbquality_destroy((gs_dbquality *)(intptr_t)quality); }
+
 JNIEXPORT void JNICALL JNAME(dbDestroy)(JNIEnv *env, jclass c, jlong db) { gs_db_destroy((gs_db *)(intptr_t)db); }
 
 JNIEXPORT void JNICALL JNAME(dbSave)(JNIEnv *env, jclass c, jlong db, jstring path) {

@@ -53,6 +53,33 @@ public final class GsGpuNative {
 
 	public static native void dbBuildDestroy(long builder);
 
+	/** gs_dbquality_begin: store quality against its source genomes (DBQualityCountsGoal.handleStore) on the store's device;
+	 * k, the values and the tree are the store's, the other arguments as for dbBuildBegin */
+	public static native long dbQualityBegin(long db, boolean lowerCaseBases, int maxDust, int stepSize);
+
+	/** gs_dbquality_set_range: only the canonical k-mers in [lo, hi); after dbQualityFinish it starts the next pass */
+	public static native void dbQualitySetRange(long quality, long lo, long hi);
+
+	/** gs_dbquality_add: regions as for dbBuildAdd; leafVi = nRegions x int32, the value index of each region's leaf node
+	 * (AbstractUpdateFastaReader.updateLeafNode), negative: the region counts nothing.  Direct buffers in native order. */
+	public static void dbQualityAdd(long quality, ByteBuffer bases, ByteBuffer offsets, ByteBuffer leafVi, long nRegions) {
+		dbQualityAdd0(quality, bases, bases.capacity(), offsets, offsets.capacity(), leafVi, leafVi.capacity(), nRegions);
+	}
+
+	/** gs_dbquality_finish: counts = nValues x 3 x int64 (tp, tp+fp, tp+fn per value index), present = nValues bytes (1: the value
+	 * has an entry in DBQualityCountsGoal's map) */
+	public static void dbQualityFinish(long quality, int nValues, ByteBuffer counts, ByteBuffer present) {
+		dbQualityFinish0(quality, nValues, counts, counts.capacity(), present, present.capacity());
+	}
+
+	public static native void dbQualityDestroy(long quality);
+
+	private static native void dbQualityAdd0(long quality, ByteBuffer bases, long basesCap, ByteBuffer offsets, long offsetsCap,
+			ByteBuffer leafVi, long leafViCap, long nRegions);
+
+	private static native void dbQualityFinish0(long quality, int nValues, ByteBuffer counts, long countsCap, ByteBuffer present,
+			long presentCap);
+
 	/** gs_db_save / gs_db_load: the native image of the device store */
 	public static native void dbSave(long db, String path);
 
