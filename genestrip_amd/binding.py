@@ -48,6 +48,8 @@ ABI_SYMBOLS = (
     "gs_dbexport_fastq_next", "gs_dbexport_destroy",
     "gs_dbquality_begin", "gs_dbquality_set_range", "gs_dbquality_add", "gs_dbquality_finish", "gs_dbquality_get_stats",
     "gs_dbquality_destroy",
+    "gs_dbupdate_begin", "gs_dbupdate_begin_db", "gs_dbupdate_begin_build", "gs_dbupdate_set_slice", "gs_dbupdate_add",
+    "gs_dbupdate_finish", "gs_dbupdate_fetch", "gs_dbupdate_to_db", "gs_dbupdate_get_stats", "gs_dbupdate_destroy",
 )
 
 
@@ -140,6 +142,16 @@ def lib():
         "gs_dbquality_finish": (ci, [vp, vp, vp]),
         "gs_dbquality_get_stats": (ci, [vp, vp]),
         "gs_dbquality_destroy": (ci, [vp]),
+        "gs_dbupdate_begin": (ci, [vp, ci, ci, i32, vp, ci, ci, ci, vp, vp, i64, ci]),
+        "gs_dbupdate_begin_db": (ci, [vp, vp, ci, ci, ci]),
+        "gs_dbupdate_begin_build": (ci, [vp, vp]),
+        "gs_dbupdate_set_slice": (ci, [vp, i64]),
+        "gs_dbupdate_add": (ci, [vp, vp, vp, vp, i64, ci]),
+        "gs_dbupdate_finish": (ci, [vp, vp]),
+        "gs_dbupdate_fetch": (ci, [vp, vp, vp]),
+        "gs_dbupdate_to_db": (ci, [vp, vp]),
+        "gs_dbupdate_get_stats": (ci, [vp, vp]),
+        "gs_dbupdate_destroy": (ci, [vp]),
         "gs_match_encode": (ci, [vp, vp, vp, i64, vp, vp]), "gs_match_probe_keys": (ci, [vp, vp, i64, vp]),
         "gs_match_encode_route": (ci, [vp, vp, vp, i64, vp, ci, i64, vp, vp, vp, vp, vp]),
         "gs_match_route_geometry": (ci, [vp, i64, vp, vp]),
@@ -699,6 +711,118 @@ class DeviceDbQuality:
     def close(self):
         if getattr(self, "h", None):
             lib().gs_dbquality_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DbUpdateStats(C.Structure):
+    _fields_ = [("n_store", C.c_int64), ("n_pairs", C.c_int64), ("n_found", C.c_int64), ("n_moved", C.c_int64),
+                ("store_bytes", C.c_int64), ("batch_bytes_peak", C.c_int64),
+                ("ms_begin", C.c_double), ("ms_kmers", C.c_double), ("ms_lookup", C.c_double), ("ms_finish", C.c_double)]
+
+
+class DeviceDbUpdater:
+    """gs_dbupdate: a finished store updated in batches (the reference's updatedb stage, DBGoal.MyFastaReader): every stored
+    k-mer that occurs in an added region gets value := LCA(value, node of the region).  The store stays on the device, the
+    regions stream past it in slices: memory does not grow with the number of add() calls, and their order does not matter."""
+
+    def __init__(self):
+        raise TypeError("use DeviceDbUpdater.from_arrays / from_store / from_builder")
+
+    @classmethod
+    def _new(cls, k, n_values, device):
+        self = cls.__new__(cls)
+        self.h = C.c_void_p()
+        self.k, self.n_values, self.device = k, n_values, device
+        return self
+
+    @classmethod
+    def from_arrays(cls, k, kmers, value_idx, n_values, parent_vi, device=0, lower_case_bases=True, max_dust=-1, step_size=1):
+        """the arrays DeviceDbBuilder.finish() returns / DeviceKMerStore takes: both numpy or both device tensors"""
+        pv = np.ascontiguousarray(parent_vi, dtype=np.int32)
+        if len(pv) != n_values:
+            raise ValueError("parent_vi must have n_values entries")
+        if isinstance(kmers, np.ndarray) or not hasattr(kmers, "data_ptr"):
+            kmers = np.ascontiguousarray(kmers, dtype=np.int64)
+            value_idx = np.ascontiguousarray(value_idx, dtype=np.int32)
+        n = kmers.shape[0]
+        if value_idx.shape[0] != n:
+            raise ValueError("kmers / value_idx length mismatch")
+        pk, mem = _ptr(kmers)
+        pvl, mem2 = _ptr(value_idx)
+        assert mem == mem2, "kmers and value_idx must live in the same memory space"
+        _ready(kmers, value_idx)
+        self = cls._new(k, n_values, device)
+        _check(lib().gs_dbupdate_begin(C.byref(self.h), device, k, n_values, pv.ctypes.data_as(C.c_void_p), int(lower_case_bases),
+                                       max_dust, step_size, pk, pvl, n, mem))
+        return self
+
+    @classmethod
+    def from_store(cls, store, lower_case_bases=True, max_dust=-1, step_size=1):
+        """the k-mers of a live DeviceKMerStore (decoded on the device; the store is only read and may be closed afterwards)"""
+        self = cls._new(store.k, store.n_values, store.device)
+        _check(lib().gs_dbupdate_begin_db(C.byref(self.h), store.h, int(lower_case_bases), max_dust, step_size))
+        return self
+
+    @classmethod
+    def from_builder(cls, builder, device=0):
+        """the result of a DeviceDbBuilder (finished here if it is not yet); its parameters are inherited and it keeps its own
+        arrays"""
+        builder.finish_count()
+        self = cls._new(builder.k, builder.n_values, device)
+        _check(lib().gs_dbupdate_begin_build(C.byref(self.h), builder.h))
+        return self
+
+    def set_slice(self, max_bases):
+        """a batch is worked off in slices of at most max_bases bases (at least k - 1 + step_size); results do not change"""
+        _check(lib().gs_dbupdate_set_slice(self.h, int(max_bases)))
+
+    def add(self, seq, offsets, node_vi):
+        """regions as for DeviceDbBuilder.add(..., update=True)"""
+        ps, mem = _ptr(seq)
+        po, mem2 = _ptr(offsets)
+        assert mem == mem2, "seq and offsets must live in the same memory space"
+        nv = np.ascontiguousarray(node_vi, dtype=np.int32)
+        n = (offsets.shape[0] if hasattr(offsets, "shape") else len(offsets)) - 1
+        if len(nv) != n:
+            raise ValueError("node_vi must have one entry per region")
+        _ready(seq, offsets)
+        _check(lib().gs_dbupdate_add(self.h, ps, po, nv.ctypes.data_as(C.c_void_p), n, mem))
+
+    def finish(self):
+        """-> the number of stored k-mers whose value differs from the value at the start; no add() afterwards"""
+        n = C.c_int64(0)
+        _check(lib().gs_dbupdate_finish(self.h, C.byref(n)))
+        return n.value
+
+    def fetch(self):
+        """-> (kmers int64 ascending, value_idx int32) after finish()"""
+        n = self.stats().n_store
+        kmers = np.zeros(n, dtype=np.int64)
+        vals = np.zeros(n, dtype=np.int32)
+        _check(lib().gs_dbupdate_fetch(self.h, kmers.ctypes.data_as(C.c_void_p), vals.ctypes.data_as(C.c_void_p)))
+        return kmers, vals
+
+    def to_store(self):
+        """gs_dbupdate_to_db: the store over the updated arrays, laid out on the device, nothing through the host"""
+        h = C.c_void_p()
+        _check(lib().gs_dbupdate_to_db(self.h, C.byref(h)))
+        return DeviceKMerStore._wrap(h, self.k, self.n_values, self.device)
+
+    def stats(self):
+        """counts so far, device bytes and phase times (ms)"""
+        st = DbUpdateStats()
+        _check(lib().gs_dbupdate_get_stats(self.h, C.byref(st)))
+        return st
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().gs_dbupdate_destroy(self.h)
             self.h = None
 
     def __del__(self):

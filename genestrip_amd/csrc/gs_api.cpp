@@ -3606,6 +3606,33 @@ extern "C" hipError_t gs_build_reduce(const u64 *keys, const uint32_t *vals, int
 extern "C" hipError_t gs_launch_build_scatter(const u64 *keys, const int32_t *value, const uint32_t *flag, const u64 *pos, int64_t n,
                                               int64_t *out_keys, int32_t *out_vals, hipStream_t stream);
 
+// depth of every value index by parent walks (-1: no node); exactly one root: TaxTree.getLowestCommonAncestor answers null for
+// nodes of different trees and the update then keeps the old value (DBGoal.java:243), which depends on the order of the regions
+static int build_tree_depths(int32_t n_values, const int32_t *parent_vi, std::vector<int32_t> &depth, const char *who) {
+    depth.assign((size_t)n_values, -1);
+    int roots = 0;
+    for (int32_t v = 0; v < n_values; v++) {
+        const int32_t p = parent_vi[v];
+        if (p < -2 || p >= n_values || p == v) return fail(GS_E_INVALID, "parent_vi out of range");
+        roots += p == -1;
+    }
+    if (roots != 1) return fail(GS_E_UNSUPPORTED, std::string(who) + " needs a tree with exactly one root");
+    for (int32_t v = 0; v < n_values; v++) {
+        if (parent_vi[v] == -2 || depth[(size_t)v] >= 0) continue;
+        std::vector<int32_t> path;
+        int32_t x = v;
+        while (x >= 0 && depth[(size_t)x] < 0) {
+            if (parent_vi[x] == -2) return fail(GS_E_INVALID, "parent_vi points at a value without a node");
+            path.push_back(x);
+            if ((int32_t)path.size() > n_values) return fail(GS_E_INVALID, "parent_vi contains a cycle");
+            x = parent_vi[x];
+        }
+        int32_t d = x >= 0 ? depth[(size_t)x] + 1 : 0;
+        for (size_t i = path.size(); i-- > 0;) depth[(size_t)path[i]] = d++;
+    }
+    return GS_OK;
+}
+
 struct gs_dbbuild {
     int device = 0, k = 0, lower = 1, step = 1, max_dust = -1;
     int32_t n_values = 0;
@@ -3652,30 +3679,10 @@ extern "C" int gs_dbbuild_begin(gs_dbbuild **out, int device, int k, int32_t n_v
     if (n_values < 1 || n_values > (1 << 24) || !parent_vi) return fail(GS_E_INVALID, "bad tree arrays (n_values must be in [1, 2^24])");
     if (step_size < 1) return fail(GS_E_INVALID, "stepSize must be >= 1 (C/GSConfigKey.java:236)");
     if (max_dust > 32767) return fail(GS_E_INVALID, "maxDust > Short.MAX_VALUE (C/util/CGATLongBuffer.java:78-80)");
-    // depths by parent walks; exactly one root: TaxTree.getLowestCommonAncestor answers null for nodes of different trees
-    // and the update then keeps the old value (DBGoal.java:243), which depends on the order of the regions
-    std::vector<int32_t> depth((size_t)n_values, -1);
-    int roots = 0;
-    for (int32_t v = 0; v < n_values; v++) {
-        const int32_t p = parent_vi[v];
-        if (p < -2 || p >= n_values || p == v) return fail(GS_E_INVALID, "parent_vi out of range");
-        roots += p == -1;
-    }
-    if (roots != 1) return fail(GS_E_UNSUPPORTED, "gs_dbbuild needs a tree with exactly one root");
-    for (int32_t v = 0; v < n_values; v++) {
-        if (parent_vi[v] == -2 || depth[(size_t)v] >= 0) continue;
-        std::vector<int32_t> path;
-        int32_t x = v;
-        while (x >= 0 && depth[(size_t)x] < 0) {
-            if (parent_vi[x] == -2) return fail(GS_E_INVALID, "parent_vi points at a value without a node");
-            path.push_back(x);
-            if ((int32_t)path.size() > n_values) return fail(GS_E_INVALID, "parent_vi contains a cycle");
-            x = parent_vi[x];
-        }
-        int32_t d = x >= 0 ? depth[(size_t)x] + 1 : 0;
-        for (size_t i = path.size(); i-- > 0;) depth[(size_t)path[i]] = d++;
-    }
-    int rc = use_device(device);
+    std::vector<int32_t> depth;
+    int rc = build_tree_depths(n_values, parent_vi, depth, "gs_dbbuild");
+    if (rc) return rc;
+    rc = use_device(device);
     if (rc) return rc;
     gs_dbbuild *b = new gs_dbbuild();
     b->device = device;
@@ -4183,6 +4190,478 @@ extern "C" int gs_dbquality_get_stats(gs_dbquality *q, gs_dbquality_stats *out) 
 
 extern "C" int gs_dbquality_destroy(gs_dbquality *q) {
     if (q) dbquality_free(q);
+    return GS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// A finished store updated in batches (gs_update.hip; include/gsgpu.h "gs_dbupdate")
+// ---------------------------------------------------------------------------------------------------
+struct GsUpdateParams {  // (gs_update.hip)
+    const u64 *skeys;
+    int32_t *svals;
+    int64_t m;
+    const void *dir;
+    int32_t dir_bits, wide, k;
+    const int32_t *parent, *depth;
+    const u64 *keys;
+    const uint32_t *region;
+    const u64 *n_pairs;
+    const int32_t *node_of_region;
+    u64 *stats;
+};
+extern "C" hipError_t gs_launch_update_check(const u64 *keys, const int32_t *vals, int64_t m, int k, int32_t n_values, uint32_t *flag, int n_cu,
+                                             hipStream_t stream);
+extern "C" hipError_t gs_launch_update_dir(const u64 *keys, int64_t m, int k, int dir_bits, int wide, void *dir, int n_cu, hipStream_t stream);
+extern "C" hipError_t gs_launch_update_lookup(const GsUpdateParams *P, int64_t max_pairs, int n_cu, hipStream_t stream);
+extern "C" hipError_t gs_launch_update_moved(const int32_t *vals, const int32_t *vals0, int64_t m, u64 *count, int n_cu, hipStream_t stream);
+
+#define GS_UPD_DEFAULT_SLICE ((int64_t)1 << 25)  // bases per slice: 13 bytes of working memory each (436 MB)
+
+struct gs_dbupdate {
+    int device = 0, k = 0, lower = 1, step = 1, max_dust = -1, n_cu = 256;
+    int32_t n_values = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    std::vector<int32_t> parent;
+    int32_t *d_tree = nullptr;  // parent | depth
+    // the store: lives as long as the handle
+    int64_t n = 0;
+    u64 *d_keys = nullptr;       // ascending, never written
+    int32_t *d_vals = nullptr;   // updated in place
+    int32_t *d_vals0 = nullptr;  // the values at begin (n_moved)
+    void *d_dir = nullptr;
+    int dir_bits = 1;
+    bool wide = false;
+    u64 *d_cnt = nullptr;  // [0] pairs of the slice (the k-mer kernel's counter), [1] pairs so far, [2] found so far, [3] moved; then the check flag
+    // one slice's working memory: sized by the largest slice so far, never by the number of calls
+    int64_t slice_bases = GS_UPD_DEFAULT_SLICE;
+    uint8_t *d_seq = nullptr;
+    u64 *d_off = nullptr;
+    int32_t *d_node = nullptr;
+    u64 *d_pkeys = nullptr;
+    uint32_t *d_pvals = nullptr;
+    size_t seq_cap = 0, off_cap = 0, node_cap = 0, pair_cap = 0;
+    bool finished = false;
+    bool failed = false;  // a device error in the middle of an add: the values are half-updated (sticky GS_E_STATE)
+    int64_t n_moved = 0;
+    gs_dbupdate_stats stats{};
+};
+
+static void dbupdate_free(gs_dbupdate *u) {
+    hipSetDevice(u->device);
+    if (u->stream) hipStreamSynchronize(u->stream);
+    for (void *p : {(void *)u->d_tree, (void *)u->d_keys, (void *)u->d_vals, (void *)u->d_vals0, u->d_dir, (void *)u->d_cnt, (void *)u->d_seq,
+                    (void *)u->d_off, (void *)u->d_node, (void *)u->d_pkeys, (void *)u->d_pvals})
+        hipFree(p);
+    for (hipEvent_t e : u->ev)
+        if (e) hipEventDestroy(e);
+    if (u->stream) hipStreamDestroy(u->stream);
+    delete u;
+}
+
+static int64_t dbupdate_max_regions(const gs_dbupdate *u) { return u->slice_bases / 8 + 64; }
+
+// the argument checks every way to begin shares; nothing here touches a device
+static int dbupdate_check_params(int k, int32_t n_values, const int32_t *parent_vi, int max_dust, int step_size, std::vector<int32_t> &depth) {
+    if (k < 1 || k > 31) return fail(GS_E_INVALID, "k must be in [1,31]");
+    if (n_values < 1 || n_values > (1 << 24) || !parent_vi) return fail(GS_E_INVALID, "bad tree arrays (n_values must be in [1, 2^24])");
+    if (step_size < 1) return fail(GS_E_INVALID, "stepSize must be >= 1 (C/GSConfigKey.java:236)");
+    if (max_dust > 32767) return fail(GS_E_INVALID, "maxDust > Short.MAX_VALUE (C/util/CGATLongBuffer.java:78-80)");
+    return build_tree_depths(n_values, parent_vi, depth, "gs_dbupdate");
+}
+
+// handle + stream + tree on the current device
+static int dbupdate_open(gs_dbupdate **out, int device, int k, int32_t n_values, const int32_t *parent_vi, const std::vector<int32_t> &depth, int lower,
+                         int max_dust, int step) {
+    gs_dbupdate *u = new gs_dbupdate();
+    u->device = device;
+    u->k = k;
+    u->lower = lower != 0;
+    u->step = step;
+    u->max_dust = max_dust < 0 ? -1 : max_dust;
+    u->n_values = n_values;
+    u->parent.assign(parent_vi, parent_vi + n_values);
+    int cu = 0;
+    if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) u->n_cu = cu;
+    hipError_t e = hipStreamCreateWithFlags(&u->stream, hipStreamNonBlocking);
+    for (int i = 0; i < 3 && e == hipSuccess; i++) e = hipEventCreate(&u->ev[i]);
+    if (e == hipSuccess) e = hipMalloc((void **)&u->d_cnt, 5 * sizeof(u64));
+    if (e == hipSuccess) e = hipMemsetAsync(u->d_cnt, 0, 5 * sizeof(u64), u->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(u->stream);
+    if (e == hipSuccess) e = hipMalloc((void **)&u->d_tree, sizeof(int32_t) * 2 * (size_t)n_values);
+    if (e == hipSuccess) e = hipMemcpy(u->d_tree, parent_vi, sizeof(int32_t) * (size_t)n_values, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(u->d_tree + n_values, depth.data(), sizeof(int32_t) * (size_t)n_values, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        dbupdate_free(u);
+        return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbupdate_begin: ") + hipGetErrorString(e));
+    }
+    *out = u;
+    return GS_OK;
+}
+
+// u->d_keys / u->d_vals / u->n are set: one pass checks them, then the copy of the values and the directory
+static int dbupdate_adopt(gs_dbupdate *u, bool check) {
+    const int64_t n = u->n;
+    if (check && n > 0) {
+        uint32_t flag = 0;
+        HIP_TRY(hipMemsetAsync(u->d_cnt + 4, 0, sizeof(u64), u->stream));
+        HIP_TRY(gs_launch_update_check(u->d_keys, u->d_vals, n, u->k, u->n_values, (uint32_t *)(u->d_cnt + 4), u->n_cu, u->stream));
+        HIP_TRY(hipMemcpyAsync(&flag, u->d_cnt + 4, sizeof(uint32_t), hipMemcpyDeviceToHost, u->stream));
+        HIP_TRY(hipStreamSynchronize(u->stream));
+        if (flag & 1u) return fail(GS_E_INVALID, "kmers must be ascending, distinct and below 4^k");
+        if (flag & 2u) return fail(GS_E_INVALID, "value_idx out of range");
+    }
+    // about two to four k-mers per bucket, never more buckets than 4^k
+    int bits = 1;
+    while (bits < 31 && bits < 2 * u->k && ((int64_t)2 << bits) <= n) bits++;
+    u->dir_bits = bits;
+    u->wide = n >= ((int64_t)1 << 32);
+    const size_t dir_bytes = (((size_t)1 << bits) + 1) * (u->wide ? 8 : 4);
+    HIP_TRY(hipMalloc((void **)&u->d_vals0, std::max<size_t>((size_t)n, 1) * sizeof(int32_t)));
+    HIP_TRY(hipMalloc(&u->d_dir, dir_bytes));
+    if (n > 0) HIP_TRY(hipMemcpyAsync(u->d_vals0, u->d_vals, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, u->stream));
+    HIP_TRY(gs_launch_update_dir(u->d_keys, n, u->k, bits, u->wide ? 1 : 0, u->d_dir, u->n_cu, u->stream));
+    HIP_TRY(hipStreamSynchronize(u->stream));
+    u->stats.n_store = n;
+    u->stats.store_bytes = (int64_t)((size_t)n * (sizeof(u64) + 2 * sizeof(int32_t)) + dir_bytes + sizeof(int32_t) * 2 * (size_t)u->n_values);
+    return GS_OK;
+}
+
+static double dbupdate_ms_since(std::chrono::steady_clock::time_point t) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
+
+extern "C" int gs_dbupdate_begin(gs_dbupdate **out, int device, int k, int32_t n_values, const int32_t *parent_vi, int lower_case_bases,
+                                 int max_dust, int step_size, const int64_t *kmers, const int32_t *value_idx, int64_t n_kmers, int mem) try {
+    if (!out) return fail(GS_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (n_kmers < 0 || (n_kmers > 0 && (!kmers || !value_idx))) return fail(GS_E_INVALID, "bad store arrays");
+    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    std::vector<int32_t> depth;
+    int rc = dbupdate_check_params(k, n_values, parent_vi, max_dust, step_size, depth);
+    if (rc) return rc;
+    rc = use_device(device);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    gs_dbupdate *u = nullptr;
+    rc = dbupdate_open(&u, device, k, n_values, parent_vi, depth, lower_case_bases, max_dust, step_size);
+    if (rc) return rc;
+    u->n = n_kmers;
+    const size_t m = std::max<size_t>((size_t)n_kmers, 1);
+    const hipMemcpyKind kind = mem == GS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    hipError_t e = hipMalloc((void **)&u->d_keys, m * sizeof(u64));
+    if (e == hipSuccess) e = hipMalloc((void **)&u->d_vals, m * sizeof(int32_t));
+    // (on the handle's stream: a device-to-device hipMemcpy need not be complete when it returns, and this stream does not wait for the null stream)
+    if (e == hipSuccess && n_kmers > 0) e = hipMemcpyAsync(u->d_keys, kmers, (size_t)n_kmers * sizeof(u64), kind, u->stream);
+    if (e == hipSuccess && n_kmers > 0) e = hipMemcpyAsync(u->d_vals, value_idx, (size_t)n_kmers * sizeof(int32_t), kind, u->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(u->stream);  // (the caller's arrays are free again)
+    if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbupdate_begin: ") + hipGetErrorString(e));
+    if (!rc) rc = dbupdate_adopt(u, true);
+    if (rc) {
+        dbupdate_free(u);
+        return rc;
+    }
+    u->stats.ms_begin = dbupdate_ms_since(t0);
+    *out = u;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_dbupdate_begin_db(gs_dbupdate **out, gs_db *db, int lower_case_bases, int max_dust, int step_size) try {
+    if (!out) return fail(GS_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!db) return fail(GS_E_INVALID, "db is NULL");
+    if (step_size < 1) return fail(GS_E_INVALID, "stepSize must be >= 1 (C/GSConfigKey.java:236)");
+    if (max_dust > 32767) return fail(GS_E_INVALID, "maxDust > Short.MAX_VALUE (C/util/CGATLongBuffer.java:78-80)");
+    if (db->striped()) return fail(GS_E_UNSUPPORTED, "gs_dbupdate needs the whole store on one device: this handle is a stripe");
+    HIP_TRY(hipSetDevice(db->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    const int32_t nv = db->info.n_values;
+    std::vector<int32_t> parent((size_t)nv), depth;
+    HIP_TRY(hipMemcpy(parent.data(), db->d_tree, sizeof(int32_t) * (size_t)nv, hipMemcpyDeviceToHost));
+    int rc = dbupdate_check_params(db->info.k, nv, parent.data(), max_dust, step_size, depth);
+    if (rc) return rc;
+    // the store in ascending k-mer order, decoded on the device (seen bits masked); its arrays move into the handle
+    gs_dbexport *x = nullptr;
+    int64_t m = 0;
+    rc = gs_dbexport_create(&x, db, -1, 0, &m);
+    if (rc) return rc;
+    gs_dbupdate *u = nullptr;
+    rc = dbupdate_open(&u, db->device, db->info.k, nv, parent.data(), depth, lower_case_bases, max_dust, step_size);
+    if (rc) {
+        gs_dbexport_destroy(x);
+        return rc;
+    }
+    u->n_cu = db->n_cu;
+    u->n = m;
+    u->d_keys = x->d_keys;
+    u->d_vals = (int32_t *)x->d_vals;
+    x->d_keys = nullptr;
+    x->d_vals = nullptr;
+    gs_dbexport_destroy(x);
+    rc = dbupdate_adopt(u, false);  // (the decode emits values below n_values only, and the sort made the order)
+    if (rc) {
+        dbupdate_free(u);
+        return rc;
+    }
+    u->stats.ms_begin = dbupdate_ms_since(t0);
+    *out = u;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_dbupdate_begin_build(gs_dbupdate **out, gs_dbbuild *b) try {
+    if (!out) return fail(GS_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!b) return fail(GS_E_INVALID, "builder is NULL");
+    if (!b->finished) return fail(GS_E_STATE, "gs_dbbuild_finish first");
+    HIP_TRY(hipSetDevice(b->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<int32_t> depth;
+    int rc = dbupdate_check_params(b->k, b->n_values, b->parent.data(), b->max_dust, b->step, depth);
+    if (rc) return rc;
+    gs_dbupdate *u = nullptr;
+    rc = dbupdate_open(&u, b->device, b->k, b->n_values, b->parent.data(), depth, b->lower, b->max_dust, b->step);
+    if (rc) return rc;
+    // device-to-device: the builder keeps its own arrays for gs_dbbuild_fetch / _to_db
+    u->n = b->n_out;
+    const size_t m = std::max<size_t>((size_t)b->n_out, 1);
+    hipError_t e = hipMalloc((void **)&u->d_keys, m * sizeof(u64));
+    if (e == hipSuccess) e = hipMalloc((void **)&u->d_vals, m * sizeof(int32_t));
+    if (e == hipSuccess && b->n_out > 0) e = hipMemcpyAsync(u->d_keys, b->d_out_keys, (size_t)b->n_out * sizeof(u64), hipMemcpyDeviceToDevice, u->stream);
+    if (e == hipSuccess && b->n_out > 0) e = hipMemcpyAsync(u->d_vals, b->d_out_vals, (size_t)b->n_out * sizeof(int32_t), hipMemcpyDeviceToDevice, u->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(u->stream);
+    if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbupdate_begin_build: ") + hipGetErrorString(e));
+    if (!rc) rc = dbupdate_adopt(u, false);
+    if (rc) {
+        dbupdate_free(u);
+        return rc;
+    }
+    u->stats.ms_begin = dbupdate_ms_since(t0);
+    *out = u;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_dbupdate_set_slice(gs_dbupdate *u, int64_t max_bases) {
+    if (!u) return fail(GS_E_INVALID, "NULL argument");
+    // a cut region goes on (k - 1) bases earlier and whole steps later: a slice must hold k - 1 + step_size bases
+    if (max_bases < (int64_t)u->k - 1 + u->step) return fail(GS_E_INVALID, "a slice holds at least k - 1 + step_size bases");
+    if (max_bases > ((int64_t)1 << 31)) return fail(GS_E_INVALID, "a slice holds at most 2^31 bases");
+    u->slice_bases = max_bases;
+    return GS_OK;
+}
+
+template <typename T>
+static hipError_t dbupdate_room(T **p, size_t *cap, size_t need) {
+    if (*cap >= need) return hipSuccess;
+    hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    const hipError_t e = hipMalloc((void **)p, need * sizeof(T));
+    if (e == hipSuccess) *cap = need;
+    return e;
+}
+
+extern "C" int gs_dbupdate_add(gs_dbupdate *u, const uint8_t *seq, const uint64_t *offsets, const int32_t *node_vi, int64_t n_regions,
+                               int mem) try {
+    if (!u || n_regions < 0 || (n_regions > 0 && (!seq || !offsets || !node_vi))) return fail(GS_E_INVALID, "bad argument");
+    if (u->failed) return fail(GS_E_STATE, "an earlier gs_dbupdate_add failed on the device: the values are half-updated (start over)");
+    if (u->finished) return fail(GS_E_STATE, "gs_dbupdate_finish has been called");
+    if (n_regions == 0) return GS_OK;
+    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    // node_vi is a host array in both cases (one entry per region)
+    for (int64_t r = 0; r < n_regions; r++)
+        if (node_vi[r] < 0 || node_vi[r] >= u->n_values || u->parent[(size_t)node_vi[r]] == -2) return fail(GS_E_INVALID, "node_vi: not a node of the tree");
+    HIP_TRY(hipSetDevice(u->device));
+    std::vector<uint64_t> hoff;
+    const uint64_t *off = offsets;
+    if (mem == GS_MEM_DEVICE) {
+        hoff.resize((size_t)n_regions + 1);
+        HIP_TRY(hipMemcpy(hoff.data(), offsets, sizeof(uint64_t) * ((size_t)n_regions + 1), hipMemcpyDeviceToHost));
+        off = hoff.data();
+    }
+    if (off[0] != 0) return fail(GS_E_INVALID, "offsets[0] must be 0");
+    for (int64_t r = 0; r < n_regions; r++)
+        if (off[r + 1] < off[r]) return fail(GS_E_INVALID, "offsets must not decrease");
+    const int64_t total = (int64_t)off[n_regions];
+    const int64_t slice = u->slice_bases, max_regions = dbupdate_max_regions(u);
+    // all of the call's working memory before any of its work: an out-of-memory leaves the values as they were
+    {
+        const size_t bases = (size_t)std::max<int64_t>(std::min(slice, total), 1), regions = (size_t)std::min(max_regions, n_regions);
+        HIP_TRY(hipStreamSynchronize(u->stream));
+        hipError_t e = mem == GS_MEM_HOST ? dbupdate_room(&u->d_seq, &u->seq_cap, bases) : hipSuccess;
+        if (e == hipSuccess) e = dbupdate_room(&u->d_off, &u->off_cap, regions + 1);
+        if (e == hipSuccess) e = dbupdate_room(&u->d_node, &u->node_cap, regions);
+        if (e == hipSuccess) {  // (both pair arrays under one capacity)
+            size_t c1 = u->pair_cap, c2 = u->pair_cap;
+            e = dbupdate_room(&u->d_pkeys, &c1, bases);
+            if (e == hipSuccess) e = dbupdate_room(&u->d_pvals, &c2, bases);
+            u->pair_cap = std::min(c1, c2);
+        }
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbupdate_add: ") + hipGetErrorString(e));
+        const int64_t bytes = (int64_t)(u->seq_cap + u->off_cap * sizeof(u64) + u->node_cap * sizeof(int32_t) + u->pair_cap * (sizeof(u64) + sizeof(uint32_t)));
+        u->stats.batch_bytes_peak = std::max(u->stats.batch_bytes_peak, bytes);
+    }
+    GsUpdateParams P{};
+    P.skeys = u->d_keys;
+    P.svals = u->d_vals;
+    P.m = u->n;
+    P.dir = u->d_dir;
+    P.dir_bits = u->dir_bits;
+    P.wide = u->wide ? 1 : 0;
+    P.k = u->k;
+    P.parent = u->d_tree;
+    P.depth = u->d_tree + u->n_values;
+    P.keys = u->d_pkeys;
+    P.region = u->d_pvals;
+    P.n_pairs = u->d_cnt;
+    P.node_of_region = u->d_node;
+    P.stats = u->d_cnt + 1;
+    // Slices: consecutive bytes [begin, begin + used) of the batch, cut into the pieces of regions they hold.  A region that
+    // does not fit is cut at a multiple of step_size behind its start (so that (bases of the region so far) % step_size is the
+    // same in the piece) and the slice ends there; the next piece starts k - 1 bases before the cut's end: every window lies
+    // in exactly one piece.
+    std::vector<uint64_t> soff;
+    std::vector<int32_t> snode;
+    int rc = GS_OK;
+    auto check = [&](hipError_t e, const char *what) {
+        if (e != hipSuccess && rc == GS_OK) rc = fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbupdate_add (") + what + "): " + hipGetErrorString(e));
+        return e == hipSuccess;
+    };
+    int64_t r = 0, c = 0;  // the next piece starts c bases into region r
+    while (r < n_regions && rc == GS_OK) {
+        soff.assign(1, 0);
+        snode.clear();
+        const int64_t begin = (int64_t)off[r] + c;
+        int64_t used = 0;
+        while (r < n_regions && (int64_t)snode.size() < max_regions) {
+            const int64_t rem = (int64_t)(off[r + 1] - off[r]) - c, room = slice - used;
+            if (rem <= room) {
+                used += rem;
+                soff.push_back((uint64_t)used);
+                snode.push_back(node_vi[r]);
+                r++;
+                c = 0;
+                continue;
+            }
+            const int64_t adv = room >= u->k - 1 + u->step ? (room - (u->k - 1)) / u->step * u->step : 0;
+            if (adv > 0) {
+                used += adv + u->k - 1;
+                soff.push_back((uint64_t)used);
+                snode.push_back(node_vi[r]);
+                c += adv;
+            }
+            break;
+        }
+        if (used == 0) continue;  // (empty regions only)
+        const int64_t n_sl = (int64_t)snode.size();
+        const uint8_t *d_seq = seq + begin;
+        if (mem == GS_MEM_HOST) {
+            check(hipMemcpyAsync(u->d_seq, seq + begin, (size_t)used, hipMemcpyHostToDevice, u->stream), "copy");
+            d_seq = u->d_seq;
+        }
+        bool ok = rc == GS_OK && check(hipMemcpyAsync(u->d_off, soff.data(), sizeof(u64) * ((size_t)n_sl + 1), hipMemcpyHostToDevice, u->stream), "copy") &&
+                  check(hipMemcpyAsync(u->d_node, snode.data(), sizeof(int32_t) * (size_t)n_sl, hipMemcpyHostToDevice, u->stream), "copy") &&
+                  check(hipMemsetAsync(u->d_cnt, 0, sizeof(u64), u->stream), "counter") && check(hipEventRecord(u->ev[0], u->stream), "event") &&
+                  check(gs_launch_build_kmers(d_seq, u->d_off, n_sl, used, u->k, u->lower, u->step, u->max_dust, 0u, 0, 0, ~0ULL, u->d_pkeys, u->d_pvals,
+                                              u->d_cnt, u->stream), "k-mers") &&
+                  check(hipEventRecord(u->ev[1], u->stream), "event") && check(gs_launch_update_lookup(&P, used, u->n_cu, u->stream), "lookup") &&
+                  check(hipEventRecord(u->ev[2], u->stream), "event") &&
+                  check(hipStreamSynchronize(u->stream), "slice");  // (the staging buffers and the host vectors are free again)
+        float ms = 0;
+        if (ok && hipEventElapsedTime(&ms, u->ev[0], u->ev[1]) == hipSuccess) u->stats.ms_kmers += ms;
+        if (ok && hipEventElapsedTime(&ms, u->ev[1], u->ev[2]) == hipSuccess) u->stats.ms_lookup += ms;
+    }
+    if (rc != GS_OK) {
+        u->failed = true;
+        return rc;
+    }
+    u64 cnt[2] = {0, 0};
+    HIP_TRY(hipMemcpy(cnt, u->d_cnt + 1, sizeof(cnt), hipMemcpyDeviceToHost));
+    u->stats.n_pairs = (int64_t)cnt[0];
+    u->stats.n_found = (int64_t)cnt[1];
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_dbupdate_finish(gs_dbupdate *u, int64_t *n_moved) try {
+    if (!u || !n_moved) return fail(GS_E_INVALID, "NULL argument");
+    if (u->failed) return fail(GS_E_STATE, "an earlier gs_dbupdate_add failed on the device: the values are half-updated (start over)");
+    if (u->finished) {
+        *n_moved = u->n_moved;
+        return GS_OK;
+    }
+    *n_moved = 0;
+    HIP_TRY(hipSetDevice(u->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    u64 moved = 0;
+    HIP_TRY(hipMemsetAsync(u->d_cnt + 3, 0, sizeof(u64), u->stream));
+    HIP_TRY(gs_launch_update_moved(u->d_vals, u->d_vals0, u->n, u->d_cnt + 3, u->n_cu, u->stream));
+    HIP_TRY(hipMemcpyAsync(&moved, u->d_cnt + 3, sizeof(u64), hipMemcpyDeviceToHost, u->stream));
+    HIP_TRY(hipStreamSynchronize(u->stream));
+    // the slice's working memory goes (gs_dbupdate_to_db needs the room); batch_bytes_peak keeps what it was
+    for (void *p : {(void *)u->d_seq, (void *)u->d_off, (void *)u->d_node, (void *)u->d_pkeys, (void *)u->d_pvals}) hipFree(p);
+    u->d_seq = nullptr;
+    u->d_off = nullptr;
+    u->d_node = nullptr;
+    u->d_pkeys = nullptr;
+    u->d_pvals = nullptr;
+    u->seq_cap = u->off_cap = u->node_cap = u->pair_cap = 0;
+    u->n_moved = (int64_t)moved;
+    u->stats.n_moved = u->n_moved;
+    u->stats.ms_finish = dbupdate_ms_since(t0);
+    u->finished = true;
+    *n_moved = u->n_moved;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_dbupdate_fetch(gs_dbupdate *u, int64_t *kmers, int32_t *value_idx) {
+    if (!u || (u->n > 0 && (!kmers || !value_idx))) return fail(GS_E_INVALID, "NULL argument");
+    if (!u->finished) return fail(GS_E_STATE, "gs_dbupdate_finish first");
+    HIP_TRY(hipSetDevice(u->device));
+    if (u->n > 0) {
+        HIP_TRY(hipMemcpy(kmers, u->d_keys, (size_t)u->n * sizeof(int64_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(value_idx, u->d_vals, (size_t)u->n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    return GS_OK;
+}
+
+extern "C" int gs_dbupdate_to_db(gs_dbupdate *u, gs_db **out) try {
+    if (!u || !out) return fail(GS_E_INVALID, "NULL argument");
+    *out = nullptr;
+    if (!u->finished) return fail(GS_E_STATE, "gs_dbupdate_finish first");
+    if (u->n <= 0 || u->k < GS_MIN_K || u->n_values > GS_REC_MAX_VALUES || u->n >= ((int64_t)1 << 31))
+        return fail(GS_E_UNSUPPORTED, "gs_dbupdate_to_db serves stores with records (k >= 19, at most 2^21 values, 1 .. 2^31 - 1 k-mers): fetch the arrays and call gs_db_create");
+    HIP_TRY(hipSetDevice(u->device));
+    std::vector<int32_t> parent, depth, tin, tout;
+    int rc = tree_arrays(u->n_values, u->parent.data(), parent, depth, tin, tout);
+    if (rc) return rc;
+    BuildTrace trace;
+    rc = db_create_on_device(out, u->device, u->k, u->n, (const int64_t *)u->d_keys, u->d_vals, u->n_values, parent, depth, tin, tout, trace, true);
+    if (rc == 0) return fail(GS_E_UNSUPPORTED, "gs_dbupdate_to_db: no k-mer of this store fits a record: fetch the arrays and call gs_db_create");
+    return rc < 0 ? rc : GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_dbupdate_get_stats(gs_dbupdate *u, gs_dbupdate_stats *out) {
+    if (!u || !out) return fail(GS_E_INVALID, "NULL argument");
+    *out = u->stats;
+    if (!u->finished && !u->failed && u->n > 0) {  // n_moved so far
+        if (hipSetDevice(u->device) != hipSuccess) return fail(GS_E_HIP, "hipSetDevice");
+        u64 moved = 0;
+        HIP_TRY(hipMemsetAsync(u->d_cnt + 3, 0, sizeof(u64), u->stream));
+        HIP_TRY(gs_launch_update_moved(u->d_vals, u->d_vals0, u->n, u->d_cnt + 3, u->n_cu, u->stream));
+        HIP_TRY(hipMemcpyAsync(&moved, u->d_cnt + 3, sizeof(u64), hipMemcpyDeviceToHost, u->stream));
+        HIP_TRY(hipStreamSynchronize(u->stream));
+        out->n_moved = (int64_t)moved;
+    }
+    return GS_OK;
+}
+
+extern "C" int gs_dbupdate_destroy(gs_dbupdate *u) {
+    if (u) dbupdate_free(u);
     return GS_OK;
 }
 

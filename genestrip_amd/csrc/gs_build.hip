@@ -17,6 +17,8 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
+#include "gs_build_dev.h"
+
 typedef unsigned long long u64;
 
 #define GS_BUILD_NONE 0xffffffffffffffffULL
@@ -151,17 +153,6 @@ __global__ __launch_bounds__(GS_BUILD_BLOCK) void gs_build_kmers_kernel(const ui
         }
         __syncthreads();  // (s_cnt / s_base are rewritten by the next step)
     }
-}
-
-// TaxTree.getLowestCommonAncestor (C/tax/TaxTree.java:160-187) over value indices; one tree (the API refuses forests)
-__device__ __forceinline__ int gs_build_lca(const int32_t *parent, const int32_t *depth, int a, int b) {
-    while (depth[a] > depth[b]) a = parent[a];
-    while (depth[b] > depth[a]) b = parent[b];
-    while (a != b) {
-        a = parent[a];
-        b = parent[b];
-    }
-    return a;
 }
 
 // the head of every run of equal keys folds its run: flag[i] = 1 and value[i] = node iff the k-mer is stored

@@ -440,6 +440,72 @@ int gs_dbquality_get_stats(gs_dbquality *q, gs_dbquality_stats *out);
 int gs_dbquality_destroy(gs_dbquality *q);
 
 /* ---------------------------------------------------------------------------------------------------
+ * A finished store updated in batches (genestrip_amd/csrc/gs_update.hip): the reference's updatedb stage in its own shape.
+ * DBGoal.MyFastaReader (C/goals/refseq/DBGoal.java:233-311) streams every region of the whole reference collection past the
+ * store that filldb / tempdb left behind; every stored k-mer that occurs in a region gets
+ *   value := LCA(value, node of the region)          (:240-254 -> KMerStore.update, TaxTree.getLowestCommonAncestor,
+ *                                                     C/tax/TaxTree.java:160-187)
+ * and a stored value without a tree node stays as it is (lastLCA = lcaNode != null ? ... : oldValue, :246-251).  gs_dbbuild
+ * folds fill and update into one sort, which keeps every pair resident (40 bytes per genome base at the peak) and takes
+ * updates only before its own finish.  Here the memory is the store (16 bytes per k-mer + the directory) plus one slice of
+ * input (13 bytes per base of the slice), whatever the size of the collection, and the store may come from anywhere.  LCA is
+ * associative, commutative and idempotent: the result does not depend on the order or the grouping of the add calls, and adding
+ * a region twice changes nothing.  The k-mer array never changes (no k-mer is added to a finished store).
+ *
+ *   gs_dbupdate_begin        the arrays of gs_dbbuild_fetch / gs_db_create: kmers ascending and distinct in the reference's
+ *                            encoding, value_idx in [0, n_values), both in host or device memory (`mem`); they are copied.  One
+ *                            device pass checks order, distinctness and ranges: GS_E_INVALID.  Tree, lower_case_bases, max_dust,
+ *                            step_size as for gs_dbbuild_begin (forests: GS_E_UNSUPPORTED): k-mers are formed by the builder's own
+ *                            kernel.  Every argument is checked before a device is touched.
+ *   gs_dbupdate_begin_db     the k-mers of a live store, decoded on the device as gs_dbexport_create does (seen bits masked); k,
+ *                            n_values and the tree are the store's.  The store is only read and may be destroyed after the call.
+ *                            A stripe of a striped store: GS_E_UNSUPPORTED.  A partition store (gs_db_create_part) is taken as
+ *                            the part it is: its k-mers are updated, the other parts' are not there.
+ *   gs_dbupdate_begin_build  the result arrays of a builder whose gs_dbbuild_finish has succeeded (else GS_E_STATE), copied device
+ *                            to device; the builder's k, tree, lower_case_bases, max_dust and step_size are inherited.  The
+ *                            builder stays valid and keeps answering gs_dbbuild_fetch / _to_db with its own, un-updated arrays.
+ *   gs_dbupdate_add          regions and node_vi as for gs_dbbuild_add(..., update = 1).  A node_vi that is not a node of the tree,
+ *                            or bad offsets: GS_E_INVALID, and the handle is as it was before the call.  The batch is worked off in
+ *                            slices of at most max_bases bases (gs_dbupdate_set_slice; default 2^25); a region that is longer
+ *                            is cut at multiples of step_size and consecutive pieces overlap by k - 1 bases, so that every window
+ *                            is formed exactly once and (bases of the region so far) % step_size counts from the region's start.
+ *                            Returns when the caller's arrays are free again.  The working memory of the call is allocated before
+ *                            any of its work: GS_E_NOMEM leaves the values as they were before the call.  Any other device error
+ *                            in the middle of a call marks the handle failed: every later add / finish / fetch is GS_E_STATE.
+ *   gs_dbupdate_set_slice    k - 1 + step_size <= max_bases <= 2^31, else GS_E_INVALID.  Slices do not change any result.
+ *   gs_dbupdate_finish       *n_moved = the stored k-mers whose value differs from the value at begin.  This is deterministic;
+ *                            the reference's getKMersMoved (C/store/AbstractKMerStore.java:237, logged at DBGoal.java:132) counts move EVENTS instead, which depends on the
+ *                            order of the regions (a value that climbs twice counts twice there, once here).  Afterwards the handle
+ *                            takes no further add (GS_E_STATE); a second finish repeats the count.
+ *   gs_dbupdate_fetch        kmers / value_idx (host, n_store entries: gs_dbupdate_get_stats) -- before finish: GS_E_STATE.
+ *   gs_dbupdate_to_db        the arrays into the device layout builder, as gs_dbbuild_to_db: nothing leaves the GPU.  Stores
+ *                            without records: GS_E_UNSUPPORTED (fetch + gs_db_create).  Before finish: GS_E_STATE.
+ *   gs_dbupdate_get_stats    counts so far and phase times (tools/db_update_rate.py).  batch_bytes_peak depends on the largest slice
+ *                            so far, never on the number of add calls.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct gs_dbupdate gs_dbupdate;
+typedef struct {
+    int64_t n_store;      /* k-mers of the store being updated                                   */
+    int64_t n_pairs;      /* (k-mer, region) pairs enumerated so far                             */
+    int64_t n_found;      /* ... whose k-mer is stored                                           */
+    int64_t n_moved;      /* stored k-mers whose value now differs from the value at begin       */
+    int64_t store_bytes;  /* device bytes that live as long as the handle (k-mers, values, index) */
+    int64_t batch_bytes_peak; /* largest device footprint of one slice's working memory          */
+    double ms_begin, ms_kmers, ms_lookup, ms_finish;
+} gs_dbupdate_stats;
+int gs_dbupdate_begin(gs_dbupdate **out, int device, int k, int32_t n_values, const int32_t *parent_vi, int lower_case_bases, int max_dust,
+                      int step_size, const int64_t *kmers, const int32_t *value_idx, int64_t n_kmers, int mem);
+int gs_dbupdate_begin_db(gs_dbupdate **out, gs_db *db, int lower_case_bases, int max_dust, int step_size);
+int gs_dbupdate_begin_build(gs_dbupdate **out, gs_dbbuild *finished_builder);
+int gs_dbupdate_set_slice(gs_dbupdate *u, int64_t max_bases);
+int gs_dbupdate_add(gs_dbupdate *u, const uint8_t *seq, const uint64_t *offsets, const int32_t *node_vi, int64_t n_regions, int mem);
+int gs_dbupdate_finish(gs_dbupdate *u, int64_t *n_moved);
+int gs_dbupdate_fetch(gs_dbupdate *u, int64_t *kmers, int32_t *value_idx);
+int gs_dbupdate_to_db(gs_dbupdate *u, gs_db **out);
+int gs_dbupdate_get_stats(gs_dbupdate *u, gs_dbupdate_stats *out);
+int gs_dbupdate_destroy(gs_dbupdate *u);
+
+/* ---------------------------------------------------------------------------------------------------
  * DB-partitioned match, the split pipeline of round 1 (kept: it also serves stores without records): the store is split
  * over the GPUs of a node by key hash (gs_db_create_part keeps the keys with (h >> 40) % n_parts == part, h = the library's mixed key), reads stay
  * on their home GPU.  Per batch: gs_match_encode (reads -> h of every k-mer position; ~0 marks a window with a

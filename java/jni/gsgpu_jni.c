@@ -137,6 +137,81 @@ JNIEXPORT void JNICALL JNAME(dbQualityFinish0)(JNIEnv *env, jclass c, jlong qual
 
 JNIEXPORT void JNICALL JNAME(dbQualityDestroy)(JNIEnv *env, jclass c, jlong quality) { gs_dbquality_destroy((gs_dbquality *)(intptr_t)quality); }
 
+/* ---- a finished store updated in batches, the gs_dbupdate family: DBGoal.MyFastaReader as a stream.  Capacities as for the dbQuality natives: every direct
+ * buffer is checked against the element counts before the library reads or writes it. ---- */
+JNIEXPORT jlong JNICALL JNAME(dbUpdateBegin0)(JNIEnv *env, jclass c, jint device, jint k, jint nValues, jobject parentVi, jlong parentViCap,
+                                              jboolean lowerCaseBases, jint maxDust, jint stepSize, jobject kmers, jlong kmersCap, jobject valueIdx,
+                                              jlong valueIdxCap, jlong nKmers) {
+    gs_dbupdate *u = NULL;
+    if (nValues < 0 || !addr(env, parentVi) || parentViCap < 4 * (jlong)nValues) return throw_short(env, "parentVi (nValues x int32)"), 0;
+    if (nKmers < 0 || nKmers > (INT64_MAX >> 4)) return throw_short(env, "nKmers"), 0;
+    if (nKmers > 0) {
+        if (!addr(env, kmers) || kmersCap < 8 * nKmers) return throw_short(env, "kmers (nKmers x int64)"), 0;
+        if (!addr(env, valueIdx) || valueIdxCap < 4 * nKmers) return throw_short(env, "valueIdx (nKmers x int32)"), 0;
+    }
+    int rc = gs_dbupdate_begin(&u, device, k, nValues, (const int32_t *)addr(env, parentVi), lowerCaseBases ? 1 : 0, maxDust, stepSize,
+                               (const int64_t *)addr(env, kmers), (const int32_t *)addr(env, valueIdx), nKmers, GS_MEM_HOST);
+    if (rc) throw_gs(env, rc);
+    return (jlong)(intptr_t)u;
+}
+
+JNIEXPORT jlong JNICALL JNAME(dbUpdateBeginDb)(JNIEnv *env, jclass c, jlong db, jboolean lowerCaseBases, jint maxDust, jint stepSize) {
+    gs_dbupdate *u = NULL;
+    int rc = gs_dbupdate_begin_db(&u, (gs_db *)(intptr_t)db, lowerCaseBases ? 1 : 0, maxDust, stepSize);
+    if (rc) throw_gs(env, rc);
+    return (jlong)(intptr_t)u;
+}
+
+JNIEXPORT void JNICALL JNAME(dbUpdateAdd0)(JNIEnv *env, jclass c, jlong updater, jobject bases, jlong basesCap, jobject offsets, jlong offsetsCap,
+                                           jobject nodeVi, jlong nodeViCap, jlong nRegions) {
+    const uint64_t *off = (const uint64_t *)addr(env, offsets);
+    if (nRegions < 0 || nRegions > (INT64_MAX >> 4)) return throw_short(env, "nRegions");
+    if (nRegions > 0) {
+        if (!off || offsetsCap < 8 * (nRegions + 1)) return throw_short(env, "offsets (nRegions + 1 x int64)");
+        if (!addr(env, nodeVi) || nodeViCap < 4 * nRegions) return throw_short(env, "nodeVi (nRegions x int32)");
+        if (!addr(env, bases) || basesCap < 0 || off[nRegions] > (uint64_t)basesCap) return throw_short(env, "bases (offsets[nRegions] bytes)");
+    }
+    int rc = gs_dbupdate_add((gs_dbupdate *)(intptr_t)updater, (const uint8_t *)addr(env, bases), off, (const int32_t *)addr(env, nodeVi), nRegions,
+                             GS_MEM_HOST);
+    if (rc) throw_gs(env, rc);
+}
+
+JNIEXPORT jlong JNICALL JNAME(dbUpdateFinish)(JNIEnv *env, jclass c, jlong updater) {
+    int64_t moved = 0;
+    int rc = gs_dbupdate_finish((gs_dbupdate *)(intptr_t)updater, &moved);
+    if (rc) throw_gs(env, rc);
+    return (jlong)moved;
+}
+
+JNIEXPORT jlong JNICALL JNAME(dbUpdateSize)(JNIEnv *env, jclass c, jlong updater) {
+    gs_dbupdate_stats st;
+    int rc = gs_dbupdate_get_stats((gs_dbupdate *)(intptr_t)updater, &st);
+    if (rc) return throw_gs(env, rc), 0;
+    return (jlong)st.n_store;
+}
+
+JNIEXPORT void JNICALL JNAME(dbUpdateFetch0)(JNIEnv *env, jclass c, jlong updater, jobject kmers, jlong kmersCap, jobject valueIdx,
+                                             jlong valueIdxCap) {
+    gs_dbupdate_stats st;
+    int rc = gs_dbupdate_get_stats((gs_dbupdate *)(intptr_t)updater, &st);
+    if (rc) return throw_gs(env, rc);
+    if (st.n_store > 0) {
+        if (!addr(env, kmers) || kmersCap < 8 * st.n_store) return throw_short(env, "kmers (dbUpdateSize x int64)");
+        if (!addr(env, valueIdx) || valueIdxCap < 4 * st.n_store) return throw_short(env, "valueIdx (dbUpdateSize x int32)");
+    }
+    rc = gs_dbupdate_fetch((gs_dbupdate *)(intptr_t)updater, (int64_t *)addr(env, kmers), (int32_t *)addr(env, valueIdx));
+    if (rc) throw_gs(env, rc);
+}
+
+JNIEXPORT jlong JNICALL JNAME(dbUpdateToDb)(JNIEnv *env, jclass c, jlong updater) {
+    gs_db *db = NULL;
+    int rc = gs_dbupdate_to_db((gs_dbupdate *)(intptr_t)updater, &db);
+    if (rc) throw_gs(env, rc);
+    return (jlong)(intptr_t)db;
+}
+
+JNIEXPORT void JNICALL JNAME(dbUpdateDestroy)(JNIEnv *env, jclass c, jlong updater) { gs_dbupdate_destroy((gs_dbupdate *)(intptr_t)updater); }
+
 JNIEXPORT void JNICALL JNAME(dbDestroy)(JNIEnv *env, jclass c, jlong db) { gs_db_destroy((gs_db *)(intptr_t)db); }
 
 JNIEXPORT void JNICALL JNAME(dbSave)(JNIEnv *env, jclass c, jlong db, jstring path) {

@@ -80,6 +80,50 @@ public final class GsGpuNative {
 	private static native void dbQualityFinish0(long quality, int nValues, ByteBuffer counts, long countsCap, ByteBuffer present,
 			long presentCap);
 
+	/** gs_dbupdate_begin: a finished store (kmers = nKmers x int64 ascending, valueIdx = nKmers x int32, as dbBuildFetch returns
+	 * them or as a KMerSortedArray holds them) goes to the device to be updated in batches (DBGoal.MyFastaReader as a stream);
+	 * the other arguments as for dbBuildBegin.  Direct buffers in native order; a buffer shorter than its element count:
+	 * IllegalArgumentException. */
+	public static long dbUpdateBegin(int device, int k, int nValues, ByteBuffer parentVi, boolean lowerCaseBases, int maxDust,
+			int stepSize, ByteBuffer kmers, ByteBuffer valueIdx, long nKmers) {
+		return dbUpdateBegin0(device, k, nValues, parentVi, parentVi.capacity(), lowerCaseBases, maxDust, stepSize, kmers,
+				kmers == null ? 0 : kmers.capacity(), valueIdx, valueIdx == null ? 0 : valueIdx.capacity(), nKmers);
+	}
+
+	/** gs_dbupdate_begin_db: the k-mers of a live store (dbCreate, dbLoad, dbBuildToDb); k, the values and the tree are the store's */
+	public static native long dbUpdateBeginDb(long db, boolean lowerCaseBases, int maxDust, int stepSize);
+
+	/** gs_dbupdate_add: regions as for dbBuildAdd(..., update = true): every stored k-mer of a region gets the LCA of its value and
+	 * the region's node.  Batches may come in any order and in any number. */
+	public static void dbUpdateAdd(long updater, ByteBuffer bases, ByteBuffer offsets, ByteBuffer nodeVi, long nRegions) {
+		dbUpdateAdd0(updater, bases, bases.capacity(), offsets, offsets.capacity(), nodeVi, nodeVi.capacity(), nRegions);
+	}
+
+	/** gs_dbupdate_finish: returns the number of stored k-mers whose value differs from the value at dbUpdateBegin */
+	public static native long dbUpdateFinish(long updater);
+
+	/** the number of k-mers of the store being updated: what dbUpdateFetch writes */
+	public static native long dbUpdateSize(long updater);
+
+	/** gs_dbupdate_fetch: kmers (dbUpdateSize x int64 ascending) and value indices (dbUpdateSize x int32) after dbUpdateFinish */
+	public static void dbUpdateFetch(long updater, ByteBuffer kmers, ByteBuffer valueIdx) {
+		dbUpdateFetch0(updater, kmers, kmers.capacity(), valueIdx, valueIdx.capacity());
+	}
+
+	/** gs_dbupdate_to_db: the store over the updated arrays, laid out on the device (returns a gs_db handle as dbCreate does) */
+	public static native long dbUpdateToDb(long updater);
+
+	public static native void dbUpdateDestroy(long updater);
+
+	private static native long dbUpdateBegin0(int device, int k, int nValues, ByteBuffer parentVi, long parentViCap,
+			boolean lowerCaseBases, int maxDust, int stepSize, ByteBuffer kmers, long kmersCap, ByteBuffer valueIdx,
+			long valueIdxCap, long nKmers);
+
+	private static native void dbUpdateAdd0(long updater, ByteBuffer bases, long basesCap, ByteBuffer offsets, long offsetsCap,
+			ByteBuffer nodeVi, long nodeViCap, long nRegions);
+
+	private static native void dbUpdateFetch0(long updater, ByteBuffer kmers, long kmersCap, ByteBuffer valueIdx, long valueIdxCap);
+
 	/** gs_db_save / gs_db_load: the native image of the device store */
 	public static native void dbSave(long db, String path);
 

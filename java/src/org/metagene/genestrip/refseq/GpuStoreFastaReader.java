@@ -23,6 +23,7 @@ import org.metagene.genestrip.tax.TaxTree.TaxIdNode;
 
 public class GpuStoreFastaReader extends AbstractRefSeqFastaReader {
 	private final long builder;
+	private long updater;
 	private final boolean update;
 	private final boolean allRegions;
 	private final Map<TaxIdNode, Integer> valueIndexOfNode;
@@ -55,6 +56,22 @@ public class GpuStoreFastaReader extends AbstractRefSeqFastaReader {
 		this.offsets = ByteBuffer.allocateDirect(8 * (maxRegions + 1)).order(ByteOrder.nativeOrder());
 		this.nodes = ByteBuffer.allocateDirect(4 * maxRegions).order(ByteOrder.nativeOrder());
 		this.offsets.putLong(0, 0L);
+	}
+
+	/**
+	 * The update pass as a stream past a finished store: the regions go to an updater handle (GsGpuNative.dbUpdateBegin /
+	 * dbUpdateBeginDb) in place of a builder handle, batch by batch; nothing stays on the device but the store.  Only for the
+	 * update pass: the reader is one with update = true.
+	 */
+	public static GpuStoreFastaReader forUpdater(long updater, boolean allRegions, Map<TaxIdNode, Integer> valueIndexOfNode,
+			int batchBytes, int bufferSize, Set<TaxIdNode> taxNodes, AccessionMap accessionMap, int k, int maxGenomesPerTaxId,
+			Rank maxGenomesPerTaxIdRank, long maxKmersPerTaxId, int stepSize, boolean completeGenomesOnly,
+			StringLong2DigitTrie regionsPerTaxid) {
+		GpuStoreFastaReader reader = new GpuStoreFastaReader(0L, true, allRegions, valueIndexOfNode, batchBytes, bufferSize, taxNodes,
+				accessionMap, k, maxGenomesPerTaxId, maxGenomesPerTaxIdRank, maxKmersPerTaxId, stepSize, completeGenomesOnly,
+				regionsPerTaxid);
+		reader.updater = updater;
+		return reader;
 	}
 
 	@Override
@@ -118,7 +135,11 @@ public class GpuStoreFastaReader extends AbstractRefSeqFastaReader {
 	/** hands the collected regions to the device (also called by the goal after the last file of a pass) */
 	public void flush() {
 		if (regions > 0) {
-			GsGpuNative.dbBuildAdd(builder, bases, offsets, nodes, regions, update);
+			if (updater != 0L) {
+				GsGpuNative.dbUpdateAdd(updater, bases, offsets, nodes, regions);
+			} else {
+				GsGpuNative.dbBuildAdd(builder, bases, offsets, nodes, regions, update);
+			}
 		}
 		bases.clear();
 		regions = 0;
