@@ -600,6 +600,19 @@ def kmer_ranges(k, n):
     return [(cuts[i], cuts[i + 1]) for i in range(n) if cuts[i] < cuts[i + 1]]
 
 
+def _region_args(seq, offsets, per_region, name):
+    """a batch of regions for gs_dbbuild_add / gs_dbquality_add / gs_dbupdate_add -> (seq pointer, offsets pointer, tags int32[n], n, mem)"""
+    ps, mem = _ptr(seq)
+    po, mem2 = _ptr(offsets)
+    assert mem == mem2, "seq and offsets must live in the same memory space"
+    tags = np.ascontiguousarray(per_region, dtype=np.int32)
+    n = (offsets.shape[0] if hasattr(offsets, "shape") else len(offsets)) - 1
+    if len(tags) != n:
+        raise ValueError(f"{name} must have one entry per region")
+    _ready(seq, offsets)
+    return ps, po, tags, n, mem
+
+
 class DeviceDbBuilder:
     """gs_dbbuild: distinct canonical k-mers of genome regions with the LCA of the nodes that hold them (FillDBGoal + DBGoal)"""
 
@@ -618,15 +631,8 @@ class DeviceDbBuilder:
 
     def add(self, seq, offsets, node_vi, update=False):
         """regions: seq (uint8) + offsets (uint64, n + 1, from 0), both numpy or both device tensors; node_vi: numpy int32[n]"""
-        ps, mem = _ptr(seq)
-        po, mem2 = _ptr(offsets)
-        assert mem == mem2, "seq and offsets must live in the same memory space"
-        nv = np.ascontiguousarray(node_vi, dtype=np.int32)
-        n = (offsets.shape[0] if hasattr(offsets, "shape") else len(offsets)) - 1
-        if len(nv) != n:
-            raise ValueError("node_vi must have one entry per region")
-        _ready(seq, offsets)
-        _check(lib().gs_dbbuild_add(self.h, ps, po, nv.ctypes.data_as(C.c_void_p), n, mem, int(update)))
+        ps, po, tags, n, mem = _region_args(seq, offsets, node_vi, "node_vi")
+        _check(lib().gs_dbbuild_add(self.h, ps, po, tags.ctypes.data_as(C.c_void_p), n, mem, int(update)))
 
     def finish(self):
         """-> (kmers int64 ascending, value_idx int32): what DeviceKMerStore takes"""
@@ -685,15 +691,8 @@ class DeviceDbQuality:
 
     def add(self, seq, offsets, leaf_vi):
         """regions as for DeviceDbBuilder.add; leaf_vi: numpy int32[n], negative = the region counts nothing"""
-        ps, mem = _ptr(seq)
-        po, mem2 = _ptr(offsets)
-        assert mem == mem2, "seq and offsets must live in the same memory space"
-        lv = np.ascontiguousarray(leaf_vi, dtype=np.int32)
-        n = (offsets.shape[0] if hasattr(offsets, "shape") else len(offsets)) - 1
-        if len(lv) != n:
-            raise ValueError("leaf_vi must have one entry per region")
-        _ready(seq, offsets)
-        _check(lib().gs_dbquality_add(self.h, ps, po, lv.ctypes.data_as(C.c_void_p), n, mem))
+        ps, po, tags, n, mem = _region_args(seq, offsets, leaf_vi, "leaf_vi")
+        _check(lib().gs_dbquality_add(self.h, ps, po, tags.ctypes.data_as(C.c_void_p), n, mem))
 
     def finish(self):
         """-> (counts int64[n_values, 3]: tp, tp+fp, tp+fn; present uint8[n_values]): rows with present == 0 are absent"""
@@ -784,15 +783,8 @@ class DeviceDbUpdater:
 
     def add(self, seq, offsets, node_vi):
         """regions as for DeviceDbBuilder.add(..., update=True)"""
-        ps, mem = _ptr(seq)
-        po, mem2 = _ptr(offsets)
-        assert mem == mem2, "seq and offsets must live in the same memory space"
-        nv = np.ascontiguousarray(node_vi, dtype=np.int32)
-        n = (offsets.shape[0] if hasattr(offsets, "shape") else len(offsets)) - 1
-        if len(nv) != n:
-            raise ValueError("node_vi must have one entry per region")
-        _ready(seq, offsets)
-        _check(lib().gs_dbupdate_add(self.h, ps, po, nv.ctypes.data_as(C.c_void_p), n, mem))
+        ps, po, tags, n, mem = _region_args(seq, offsets, node_vi, "node_vi")
+        _check(lib().gs_dbupdate_add(self.h, ps, po, tags.ctypes.data_as(C.c_void_p), n, mem))
 
     def finish(self):
         """-> the number of stored k-mers whose value differs from the value at the start; no add() afterwards"""

@@ -184,13 +184,29 @@ static int fail(int code, const std::string &msg) {
     return code;
 }
 
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess)                                                                           \
-            return fail(e_ == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP,                              \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                             \
+static int hip_fail(hipError_t e, const std::string &where) {
+    return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, where + ": " + hipGetErrorString(e));
+}
+
+#define HIP_TRY(expr)                                     \
+    do {                                                  \
+        hipError_t e_ = (expr);                           \
+        if (e_ != hipSuccess) return hip_fail(e_, #expr); \
     } while (0)
+
+// a chain of device steps joined by &&: the first failure is the call's error, `who (what): reason`
+struct HipSteps {
+    const char *who;
+    int rc = GS_OK;
+    bool operator()(hipError_t e, const char *what) {
+        if (e != hipSuccess && rc == GS_OK) rc = hip_fail(e, std::string(who) + " (" + what + ")");
+        return e == hipSuccess;
+    }
+};
+
+static double ms_since(std::chrono::steady_clock::time_point t) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
 
 extern "C" const char *gs_last_error(void) { return g_err.c_str(); }
 
@@ -471,7 +487,7 @@ static int store_upload(const StoreImage &im, int dev_no, int stripes, int part,
     if (e != hipSuccess) {
         if (stripes > 1) db->d_table = nullptr;  // (inside d_rec)
         db_free(db);
-        return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("store upload: ") + hipGetErrorString(e));
+        return hip_fail(e, "store upload");
     }
     db->info.k = im.k;
     db->info.n_values = n_values;
@@ -748,7 +764,7 @@ static int db_create_on_device(gs_db **out, int device, int k, int64_t n, const 
     hipStream_t stream = nullptr;
     DevPool pool;
     auto bad = [&](hipError_t e, const char *what) {
-        return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("device layout build (") + what + "): " + hipGetErrorString(e));
+        return hip_fail(e, std::string("device layout build (") + what + ")");
     };
 #define LB_TRY(expr, what)                                        \
     do {                                                          \
@@ -2058,7 +2074,7 @@ extern "C" int gs_db_value_counts(gs_db *db, int64_t *counts) {
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     hipFree(d);
     hipStreamDestroy(stream);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_db_value_counts: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return hip_fail(e, "gs_db_value_counts");
     return GS_OK;
 }
 
@@ -2112,7 +2128,7 @@ extern "C" int gs_dbexport_create(gs_dbexport **out, gs_db *db, int32_t sel_vi, 
     }
     if (e != hipSuccess) {
         dbexport_free(x);
-        return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbexport_create: ") + hipGetErrorString(e));
+        return hip_fail(e, "gs_dbexport_create");
     }
     if (n2 != n) {
         dbexport_free(x);
@@ -2187,7 +2203,7 @@ extern "C" int gs_dbexport_fastq_begin(gs_dbexport *x, const char *const *taxids
     if (e == hipSuccess && plen) e = hipMemcpy(x->d_project, project, plen, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         dbexport_free_text(x);
-        return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbexport_fastq_begin: ") + hipGetErrorString(e));
+        return hip_fail(e, "gs_dbexport_fastq_begin");
     }
     x->next = 0;
     return GS_OK;
@@ -2739,7 +2755,7 @@ extern "C" int gs_match_begin(gs_run **out, gs_db *db, const gs_match_cfg *cfg) 
         e = hipMalloc((void **)&run->d_hit_counts, sizeof(uint32_t) * (size_t)(db->n_slots() + db->n_rec * GS_REC_SLOTS));
     if (e != hipSuccess) {
         run_free(run);
-        return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("run alloc: ") + hipGetErrorString(e));
+        return hip_fail(e, "run alloc");
     }
     int occ = gs_match_occupancy(db->info.n_values);
     if (occ < 1) occ = 1;
@@ -3135,7 +3151,7 @@ extern "C" int gs_pinned_alloc(void **p, size_t bytes) {
     if (!p) return fail(GS_E_INVALID, "NULL argument");
     *p = nullptr;
     hipError_t e = hipHostMalloc(p, bytes ? bytes : 1, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("hipHostMalloc: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return hip_fail(e, "hipHostMalloc");
     return GS_OK;
 }
 
@@ -3240,7 +3256,7 @@ extern "C" int gs_match_text_descriptors(gs_run *run, const int64_t *records, in
     if (e == hipSuccess && !rc) e = hipStreamSynchronize(run->stream);
     hipFree(d_rec);
     hipFree(d_out);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_match_text_descriptors: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return hip_fail(e, "gs_match_text_descriptors");
     return rc;
 }
 
@@ -3633,22 +3649,208 @@ static int build_tree_depths(int32_t n_values, const int32_t *parent_vi, std::ve
     return GS_OK;
 }
 
-struct gs_dbbuild {
+// ---- The region stage: what gs_dbbuild, gs_dbquality and gs_dbupdate share in front of the builder's k-mer kernel.  All three
+// take batches of regions (seq, offsets, one tag per region, mem) under the same parameters and turn them into (k-mer, region)
+// pairs with gs_launch_build_kmers; their handles are a RegionStage plus what they do with the pairs.
+struct RegionStage {
     int device = 0, k = 0, lower = 1, step = 1, max_dust = -1;
     int32_t n_values = 0;
     hipStream_t stream = nullptr;
-    int32_t *d_tree = nullptr;  // parent | depth
-    u64 *d_keys = nullptr;      // the (k-mer, region | update bit) pairs handed in so far
-    uint32_t *d_vals = nullptr;
-    u64 *d_count = nullptr;     // their number, counted by the kernel
-    size_t cap = 0, n_pairs = 0;
-    u64 range_lo = 0, range_hi = ~0ULL;  // gs_dbbuild_set_range
-    std::vector<int32_t> node_of_region;
-    std::vector<int32_t> parent;
-    uint8_t *d_seq = nullptr;  // staging of host input
+    std::vector<int32_t> parent;  // the tree (host copy)
+    int32_t *d_tree = nullptr;    // parent | depth, for the handles that fold on the device
+    uint8_t *d_seq = nullptr;     // staging of host input
     size_t seq_cap = 0;
     u64 *d_off = nullptr;
     size_t off_cap = 0;
+};
+
+// the two parameters every begin takes from its caller; nothing here touches a device
+static int region_scan_check(int max_dust, int step_size) {
+    if (step_size < 1) return fail(GS_E_INVALID, "stepSize must be >= 1 (C/GSConfigKey.java:236)");
+    if (max_dust > 32767) return fail(GS_E_INVALID, "maxDust > Short.MAX_VALUE (C/util/CGATLongBuffer.java:78-80)");
+    return GS_OK;
+}
+
+// ... and all of them, with the tree's depths, for the begins that fold towards the common ancestor
+static int region_params_check(int k, int32_t n_values, const int32_t *parent_vi, int max_dust, int step_size, std::vector<int32_t> &depth,
+                               const char *who) {
+    if (k < 1 || k > 31) return fail(GS_E_INVALID, "k must be in [1,31]");
+    if (n_values < 1 || n_values > (1 << 24) || !parent_vi) return fail(GS_E_INVALID, "bad tree arrays (n_values must be in [1, 2^24])");
+    const int rc = region_scan_check(max_dust, step_size);
+    return rc ? rc : build_tree_depths(n_values, parent_vi, depth, who);
+}
+
+// parameters and stream on the current device; with depth the tree goes to the device.  A stage that fails here is still freed
+// by region_stage_free.
+static int region_stage_open(RegionStage *s, int device, int k, int32_t n_values, const int32_t *parent_vi, const int32_t *depth, int lower,
+                             int max_dust, int step, const char *who) {
+    s->device = device;
+    s->k = k;
+    s->lower = lower != 0;
+    s->step = step;
+    s->max_dust = max_dust < 0 ? -1 : max_dust;
+    s->n_values = n_values;
+    s->parent.assign(parent_vi, parent_vi + n_values);
+    hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
+    if (e == hipSuccess && depth) e = hipMalloc((void **)&s->d_tree, sizeof(int32_t) * 2 * (size_t)n_values);
+    if (e == hipSuccess && depth) e = hipMemcpy(s->d_tree, parent_vi, sizeof(int32_t) * (size_t)n_values, hipMemcpyHostToDevice);
+    if (e == hipSuccess && depth) e = hipMemcpy(s->d_tree + n_values, depth, sizeof(int32_t) * (size_t)n_values, hipMemcpyHostToDevice);
+    return e == hipSuccess ? GS_OK : hip_fail(e, std::string(who) + "_begin");
+}
+
+static void region_stage_drop_staging(RegionStage *s) {
+    hipFree(s->d_seq);
+    hipFree(s->d_off);
+    s->d_seq = nullptr;
+    s->d_off = nullptr;
+    s->seq_cap = s->off_cap = 0;
+}
+
+// the end of a handle: waits for the stream, frees the handle's own device buffers (more) and the stage's
+static void region_stage_free(RegionStage *s, std::initializer_list<void *> more) {
+    hipSetDevice(s->device);
+    if (s->stream) hipStreamSynchronize(s->stream);
+    for (void *p : more) hipFree(p);
+    hipFree(s->d_tree);
+    region_stage_drop_staging(s);
+    if (s->stream) hipStreamDestroy(s->stream);
+}
+
+// a store must be whole on its device to be walked in k-mer order; -> its tree's parents (host)
+static int db_whole_store_tree(gs_db *db, const char *who, std::vector<int32_t> &parent) {
+    if (db->striped()) return fail(GS_E_UNSUPPORTED, std::string(who) + " needs the whole store on one device: this handle is a stripe");
+    HIP_TRY(hipSetDevice(db->device));
+    parent.resize((size_t)db->info.n_values);
+    HIP_TRY(hipMemcpy(parent.data(), db->d_tree, sizeof(int32_t) * parent.size(), hipMemcpyDeviceToHost));
+    return GS_OK;
+}
+
+// the offsets of a batch as the host sees them (hoff: the copy of a device batch): from 0, never decreasing -> the batch's bases.
+// Every _add checks mem, then its tags, then this.
+static int region_batch_check(const uint64_t *offsets, int64_t n_regions, int mem, std::vector<uint64_t> &hoff, int64_t *total) {
+    const uint64_t *off = offsets;
+    if (mem == GS_MEM_DEVICE) {
+        hoff.resize((size_t)n_regions + 1);
+        HIP_TRY(hipMemcpy(hoff.data(), offsets, sizeof(uint64_t) * ((size_t)n_regions + 1), hipMemcpyDeviceToHost));
+        off = hoff.data();
+    }
+    if (off[0] != 0) return fail(GS_E_INVALID, "offsets[0] must be 0");
+    for (int64_t r = 0; r < n_regions; r++)
+        if (off[r + 1] < off[r]) return fail(GS_E_INVALID, "offsets must not decrease");
+    *total = (int64_t)off[n_regions];
+    return GS_OK;
+}
+
+// node_vi is a host array in both cases (one entry per region)
+static int region_nodes_check(const RegionStage *s, const int32_t *node_vi, int64_t n_regions) {
+    for (int64_t r = 0; r < n_regions; r++)
+        if (node_vi[r] < 0 || node_vi[r] >= s->n_values || s->parent[(size_t)node_vi[r]] == -2) return fail(GS_E_INVALID, "node_vi: not a node of the tree");
+    return GS_OK;
+}
+
+// a whole batch on the device: a host batch through the staging buffers, a device batch where it is
+static int region_stage_upload(RegionStage *s, const uint8_t *seq, const uint64_t *offsets, int64_t n_regions, int64_t total, int mem,
+                               const uint8_t **d_seq, const u64 **d_off) {
+    *d_seq = seq;
+    *d_off = (const u64 *)offsets;
+    if (mem != GS_MEM_HOST) return GS_OK;
+    int rc = grow(&s->d_seq, &s->seq_cap, (size_t)std::max<int64_t>(total, 1), s->stream);
+    if (!rc) rc = grow(&s->d_off, &s->off_cap, (size_t)n_regions + 1, s->stream);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(s->d_seq, seq, (size_t)total, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->d_off, offsets, sizeof(u64) * ((size_t)n_regions + 1), hipMemcpyHostToDevice, s->stream));
+    *d_seq = s->d_seq;
+    *d_off = s->d_off;
+    return GS_OK;
+}
+
+struct PairBuffer {  // the (k-mer, region | update bit) pairs handed in so far
+    u64 *keys = nullptr;
+    uint32_t *vals = nullptr;
+    size_t cap = 0, n = 0;
+    u64 *d_count = nullptr;  // n as the k-mer kernel counts it
+};
+
+static int pairs_open(PairBuffer *p, const char *who) {
+    hipError_t e = hipMalloc((void **)&p->d_count, sizeof(u64));
+    if (e == hipSuccess) e = hipMemset(p->d_count, 0, sizeof(u64));
+    return e == hipSuccess ? GS_OK : hip_fail(e, std::string(who) + "_begin");
+}
+
+static void pairs_drop(PairBuffer *p) {
+    hipFree(p->keys);
+    hipFree(p->vals);
+    p->keys = nullptr;
+    p->vals = nullptr;
+    p->cap = p->n = 0;
+}
+
+// room for `extra` more pairs: the pair buffers grow by doubling
+static int pairs_reserve(PairBuffer *p, size_t extra, hipStream_t stream, const char *who) {
+    if (p->n + extra <= p->cap) return GS_OK;
+    const size_t want = std::max<size_t>(std::max(p->cap * 2, p->n + extra), 1 << 20);
+    u64 *nk = nullptr;
+    uint32_t *nv = nullptr;
+    hipError_t e = hipMalloc((void **)&nk, want * sizeof(u64));
+    if (e == hipSuccess) e = hipMalloc((void **)&nv, want * sizeof(uint32_t));
+    if (e == hipSuccess && p->n) e = hipMemcpyAsync(nk, p->keys, p->n * sizeof(u64), hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess && p->n) e = hipMemcpyAsync(nv, p->vals, p->n * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) {
+        hipFree(nk);
+        hipFree(nv);
+        return hip_fail(e, who);
+    }
+    hipFree(p->keys);
+    hipFree(p->vals);
+    p->keys = nk;
+    p->vals = nv;
+    p->cap = want;
+    return GS_OK;
+}
+
+// the k-mers of a batch on the device behind the pairs so far (room for `total` more is reserved); regions count from first_region
+static int pairs_append(RegionStage *s, PairBuffer *p, const uint8_t *d_seq, const u64 *d_off, int64_t n_regions, int64_t total,
+                        uint32_t first_region, int update, u64 range_lo, u64 range_hi, const char *who) {
+    HIP_TRY(gs_launch_build_kmers(d_seq, d_off, n_regions, total, s->k, s->lower, s->step, s->max_dust, first_region, update, range_lo, range_hi,
+                                  p->keys, p->vals, p->d_count, s->stream));
+    u64 have = 0;
+    HIP_TRY(hipMemcpyAsync(&have, p->d_count, sizeof(u64), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));  // (the caller's arrays and the staging buffers are free again)
+    if (have < p->n || have > p->cap) return fail(GS_E_HIP, std::string(who) + ": pair counter out of range");
+    p->n = (size_t)have;
+    return GS_OK;
+}
+
+// finished arrays (ascending k-mers, their values) on the device: to the host ...
+static int sorted_store_fetch(int device, int64_t n, const void *d_keys, const void *d_vals, int64_t *kmers, int32_t *value_idx) {
+    HIP_TRY(hipSetDevice(device));
+    if (n > 0) {
+        HIP_TRY(hipMemcpy(kmers, d_keys, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(value_idx, d_vals, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    return GS_OK;
+}
+
+// ... or into a store laid out on the device
+static int sorted_store_to_db(int device, int k, int32_t n_values, const std::vector<int32_t> &parent_vi, int64_t n, const void *d_keys,
+                              const int32_t *d_vals, const char *who, gs_db **out) {
+    if (n <= 0 || k < GS_MIN_K || n_values > GS_REC_MAX_VALUES || n >= ((int64_t)1 << 31))
+        return fail(GS_E_UNSUPPORTED, std::string(who) + " serves stores with records (k >= 19, at most 2^21 values, 1 .. 2^31 - 1 k-mers): fetch the arrays and call gs_db_create");
+    HIP_TRY(hipSetDevice(device));
+    std::vector<int32_t> parent, depth, tin, tout;
+    int rc = tree_arrays(n_values, parent_vi.data(), parent, depth, tin, tout);
+    if (rc) return rc;
+    BuildTrace trace;
+    rc = db_create_on_device(out, device, k, n, (const int64_t *)d_keys, d_vals, n_values, parent, depth, tin, tout, trace, true);
+    if (rc == 0) return fail(GS_E_UNSUPPORTED, std::string(who) + ": no k-mer of these arrays fits a record: fetch the arrays and call gs_db_create");
+    return rc < 0 ? rc : GS_OK;
+}
+
+struct gs_dbbuild : RegionStage {
+    PairBuffer pairs;
+    u64 range_lo = 0, range_hi = ~0ULL;  // gs_dbbuild_set_range
+    std::vector<int32_t> node_of_region;
     int64_t *d_out_keys = nullptr;
     int32_t *d_out_vals = nullptr;
     int64_t n_out = 0, n_kmers_seen = 0;
@@ -3657,17 +3859,7 @@ struct gs_dbbuild {
 };
 
 static void dbbuild_free(gs_dbbuild *b) {
-    hipSetDevice(b->device);
-    if (b->stream) hipStreamSynchronize(b->stream);
-    hipFree(b->d_tree);
-    hipFree(b->d_keys);
-    hipFree(b->d_vals);
-    hipFree(b->d_count);
-    hipFree(b->d_seq);
-    hipFree(b->d_off);
-    hipFree(b->d_out_keys);
-    hipFree(b->d_out_vals);
-    if (b->stream) hipStreamDestroy(b->stream);
+    region_stage_free(b, {b->pairs.keys, b->pairs.vals, b->pairs.d_count, b->d_out_keys, b->d_out_vals});
     delete b;
 }
 
@@ -3675,32 +3867,17 @@ extern "C" int gs_dbbuild_begin(gs_dbbuild **out, int device, int k, int32_t n_v
                                 int max_dust, int step_size) try {
     if (!out) return fail(GS_E_INVALID, "out is NULL");
     *out = nullptr;
-    if (k < 1 || k > 31) return fail(GS_E_INVALID, "k must be in [1,31]");
-    if (n_values < 1 || n_values > (1 << 24) || !parent_vi) return fail(GS_E_INVALID, "bad tree arrays (n_values must be in [1, 2^24])");
-    if (step_size < 1) return fail(GS_E_INVALID, "stepSize must be >= 1 (C/GSConfigKey.java:236)");
-    if (max_dust > 32767) return fail(GS_E_INVALID, "maxDust > Short.MAX_VALUE (C/util/CGATLongBuffer.java:78-80)");
     std::vector<int32_t> depth;
-    int rc = build_tree_depths(n_values, parent_vi, depth, "gs_dbbuild");
+    int rc = region_params_check(k, n_values, parent_vi, max_dust, step_size, depth, "gs_dbbuild");
     if (rc) return rc;
     rc = use_device(device);
     if (rc) return rc;
     gs_dbbuild *b = new gs_dbbuild();
-    b->device = device;
-    b->k = k;
-    b->lower = lower_case_bases != 0;
-    b->step = step_size;
-    b->max_dust = max_dust < 0 ? -1 : max_dust;
-    b->n_values = n_values;
-    b->parent.assign(parent_vi, parent_vi + n_values);
-    hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_count, sizeof(u64));
-    if (e == hipSuccess) e = hipMemset(b->d_count, 0, sizeof(u64));
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_tree, sizeof(int32_t) * 2 * (size_t)n_values);
-    if (e == hipSuccess) e = hipMemcpy(b->d_tree, parent_vi, sizeof(int32_t) * (size_t)n_values, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(b->d_tree + n_values, depth.data(), sizeof(int32_t) * (size_t)n_values, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
+    rc = region_stage_open(b, device, k, n_values, parent_vi, depth.data(), lower_case_bases, max_dust, step_size, "gs_dbbuild");
+    if (!rc) rc = pairs_open(&b->pairs, "gs_dbbuild");
+    if (rc) {
         dbbuild_free(b);
-        return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbbuild_begin: ") + hipGetErrorString(e));
+        return rc;
     }
     *out = b;
     return GS_OK;
@@ -3715,58 +3892,17 @@ extern "C" int gs_dbbuild_add(gs_dbbuild *b, const uint8_t *seq, const uint64_t 
     if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
     HIP_TRY(hipSetDevice(b->device));
     if (b->node_of_region.size() + (size_t)n_regions >= ((size_t)1 << 31)) return fail(GS_E_UNSUPPORTED, "more than 2^31 regions");
-    // node_vi is a host array in both cases (one entry per region)
-    for (int64_t r = 0; r < n_regions; r++)
-        if (node_vi[r] < 0 || node_vi[r] >= b->n_values || b->parent[(size_t)node_vi[r]] == -2) return fail(GS_E_INVALID, "node_vi: not a node of the tree");
     std::vector<uint64_t> hoff;
-    const uint64_t *off_host = offsets;
-    if (mem == GS_MEM_DEVICE) {
-        hoff.resize((size_t)n_regions + 1);
-        HIP_TRY(hipMemcpy(hoff.data(), offsets, sizeof(uint64_t) * ((size_t)n_regions + 1), hipMemcpyDeviceToHost));
-        off_host = hoff.data();
-    }
-    if (off_host[0] != 0) return fail(GS_E_INVALID, "offsets[0] must be 0");
-    for (int64_t r = 0; r < n_regions; r++)
-        if (off_host[r + 1] < off_host[r]) return fail(GS_E_INVALID, "offsets must not decrease");
-    const int64_t total = (int64_t)off_host[n_regions];
-    const uint8_t *d_seq = seq;
-    const u64 *d_off = (const u64 *)offsets;
-    if (mem == GS_MEM_HOST) {
-        int rc = grow(&b->d_seq, &b->seq_cap, (size_t)std::max<int64_t>(total, 1), b->stream);
-        if (!rc) rc = grow(&b->d_off, &b->off_cap, (size_t)n_regions + 1, b->stream);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(b->d_seq, seq, (size_t)total, hipMemcpyHostToDevice, b->stream));
-        HIP_TRY(hipMemcpyAsync(b->d_off, offsets, sizeof(u64) * ((size_t)n_regions + 1), hipMemcpyHostToDevice, b->stream));
-        d_seq = b->d_seq;
-        d_off = b->d_off;
-    }
-    if (b->n_pairs + (size_t)total > b->cap) {  // the pair buffers grow by doubling
-        size_t want = std::max(b->cap * 2, b->n_pairs + (size_t)total);
-        want = std::max<size_t>(want, 1 << 20);
-        u64 *nk = nullptr;
-        uint32_t *nv = nullptr;
-        hipError_t e = hipMalloc((void **)&nk, want * sizeof(u64));
-        if (e == hipSuccess) e = hipMalloc((void **)&nv, want * sizeof(uint32_t));
-        if (e == hipSuccess && b->n_pairs) e = hipMemcpyAsync(nk, b->d_keys, b->n_pairs * sizeof(u64), hipMemcpyDeviceToDevice, b->stream);
-        if (e == hipSuccess && b->n_pairs) e = hipMemcpyAsync(nv, b->d_vals, b->n_pairs * sizeof(uint32_t), hipMemcpyDeviceToDevice, b->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
-        if (e != hipSuccess) {
-            hipFree(nk);
-            hipFree(nv);
-            return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbbuild_add: ") + hipGetErrorString(e));
-        }
-        hipFree(b->d_keys);
-        hipFree(b->d_vals);
-        b->d_keys = nk;
-        b->d_vals = nv;
-        b->cap = want;
-    }
-    HIP_TRY(gs_launch_build_kmers(d_seq, d_off, n_regions, total, b->k, b->lower, b->step, b->max_dust, (uint32_t)b->node_of_region.size(), update != 0,
-                                  b->range_lo, b->range_hi, b->d_keys, b->d_vals, b->d_count, b->stream));
-    u64 have = 0;
-    HIP_TRY(hipMemcpyAsync(&have, b->d_count, sizeof(u64), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));  // (the caller's arrays and the staging buffers are free again)
-    b->n_pairs = (size_t)have;
+    int64_t total = 0;
+    const uint8_t *d_seq = nullptr;
+    const u64 *d_off = nullptr;
+    int rc = region_nodes_check(b, node_vi, n_regions);
+    if (!rc) rc = region_batch_check(offsets, n_regions, mem, hoff, &total);
+    if (!rc) rc = region_stage_upload(b, seq, offsets, n_regions, total, mem, &d_seq, &d_off);
+    if (!rc) rc = pairs_reserve(&b->pairs, (size_t)total, b->stream, "gs_dbbuild_add");
+    if (!rc) rc = pairs_append(b, &b->pairs, d_seq, d_off, n_regions, total, (uint32_t)b->node_of_region.size(), update != 0, b->range_lo,
+                               b->range_hi, "gs_dbbuild_add");
+    if (rc) return rc;
     b->node_of_region.insert(b->node_of_region.end(), node_vi, node_vi + n_regions);
     return GS_OK;
 }
@@ -3774,7 +3910,7 @@ GS_API_CATCH
 
 extern "C" int gs_dbbuild_set_range(gs_dbbuild *b, uint64_t lo, uint64_t hi) {
     if (!b || lo >= hi) return fail(GS_E_INVALID, "bad range");
-    if (b->n_pairs > 0 || !b->node_of_region.empty()) return fail(GS_E_STATE, "gs_dbbuild_set_range comes before the first gs_dbbuild_add");
+    if (b->pairs.n > 0 || !b->node_of_region.empty()) return fail(GS_E_STATE, "gs_dbbuild_set_range comes before the first gs_dbbuild_add");
     b->range_lo = lo;
     b->range_hi = hi;
     return GS_OK;
@@ -3789,35 +3925,19 @@ extern "C" int gs_dbbuild_finish(gs_dbbuild *b, int64_t *n_kmers) try {
     }
     *n_kmers = 0;
     HIP_TRY(hipSetDevice(b->device));
-    hipFree(b->d_seq);
-    hipFree(b->d_off);
-    b->d_seq = nullptr;
-    b->d_off = nullptr;
-    b->seq_cap = b->off_cap = 0;
-    const int64_t n = (int64_t)b->n_pairs;
-    int rc = GS_OK;
+    region_stage_drop_staging(b);
+    const int64_t n = (int64_t)b->pairs.n;
     u64 *keys_alt = nullptr, *pos = nullptr;
     uint32_t *vals_alt = nullptr, *flag = nullptr;
     int32_t *value = nullptr, *d_nor = nullptr;
-    auto cleanup = [&] {
-        hipFree(keys_alt);
-        hipFree(vals_alt);
-        hipFree(pos);
-        hipFree(flag);
-        hipFree(value);
-        hipFree(d_nor);
-    };
-    auto check = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && rc == GS_OK) rc = fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbbuild_finish (") + what + "): " + hipGetErrorString(e));
-        return e == hipSuccess;
-    };
+    HipSteps check{"gs_dbbuild_finish"};
     if (n > 0) {
         u64 *ks = nullptr;
         uint32_t *vs = nullptr;
         const u64 n_valid = (u64)n;
         bool ok = check(hipMalloc((void **)&keys_alt, (size_t)n * sizeof(u64)), "sort buffers") &&
                   check(hipMalloc((void **)&vals_alt, (size_t)n * sizeof(uint32_t)), "sort buffers") &&
-                  check(gs_build_sort(b->d_keys, keys_alt, b->d_vals, vals_alt, n, 2 * b->k, &ks, &vs, b->stream), "sort");
+                  check(gs_build_sort(b->pairs.keys, keys_alt, b->pairs.vals, vals_alt, n, 2 * b->k, &ks, &vs, b->stream), "sort");
         b->n_kmers_seen = (int64_t)n_valid;
         if (ok && n_valid > 0) {
             const size_t nr = std::max<size_t>(b->node_of_region.size(), 1);
@@ -3834,20 +3954,16 @@ extern "C" int gs_dbbuild_finish(gs_dbbuild *b, int64_t *n_kmers) try {
                      check(hipStreamSynchronize(b->stream), "scatter");
         }
     }
-    cleanup();
-    hipFree(b->d_keys);
-    hipFree(b->d_vals);
-    b->d_keys = nullptr;
-    b->d_vals = nullptr;
-    b->cap = b->n_pairs = 0;
-    if (rc != GS_OK) {  // nothing half-built may be handed out later: no results, no second finish
+    for (void *p : {(void *)keys_alt, (void *)vals_alt, (void *)pos, (void *)flag, (void *)value, (void *)d_nor}) hipFree(p);
+    pairs_drop(&b->pairs);
+    if (check.rc != GS_OK) {  // nothing half-built may be handed out later: no results, no second finish
         hipFree(b->d_out_keys);
         hipFree(b->d_out_vals);
         b->d_out_keys = nullptr;
         b->d_out_vals = nullptr;
         b->n_out = 0;
         b->failed = true;
-        return rc;
+        return check.rc;
     }
     b->finished = true;
     *n_kmers = b->n_out;
@@ -3858,28 +3974,14 @@ GS_API_CATCH
 extern "C" int gs_dbbuild_fetch(gs_dbbuild *b, int64_t *kmers, int32_t *value_idx) {
     if (!b || (b->n_out > 0 && (!kmers || !value_idx))) return fail(GS_E_INVALID, "NULL argument");
     if (!b->finished) return fail(GS_E_STATE, "gs_dbbuild_finish first");
-    HIP_TRY(hipSetDevice(b->device));
-    if (b->n_out > 0) {
-        HIP_TRY(hipMemcpy(kmers, b->d_out_keys, (size_t)b->n_out * sizeof(int64_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(value_idx, b->d_out_vals, (size_t)b->n_out * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
-    return GS_OK;
+    return sorted_store_fetch(b->device, b->n_out, b->d_out_keys, b->d_out_vals, kmers, value_idx);
 }
 
 extern "C" int gs_dbbuild_to_db(gs_dbbuild *b, gs_db **out) try {
     if (!b || !out) return fail(GS_E_INVALID, "NULL argument");
     *out = nullptr;
     if (!b->finished) return fail(GS_E_STATE, "gs_dbbuild_finish first");
-    if (b->n_out <= 0 || b->k < GS_MIN_K || b->n_values > GS_REC_MAX_VALUES || b->n_out >= ((int64_t)1 << 31))
-        return fail(GS_E_UNSUPPORTED, "gs_dbbuild_to_db serves stores with records (k >= 19, at most 2^21 values, 1 .. 2^31 - 1 k-mers): fetch the arrays and call gs_db_create");
-    HIP_TRY(hipSetDevice(b->device));
-    std::vector<int32_t> parent, depth, tin, tout;
-    int rc = tree_arrays(b->n_values, b->parent.data(), parent, depth, tin, tout);
-    if (rc) return rc;
-    BuildTrace trace;
-    rc = db_create_on_device(out, b->device, b->k, b->n_out, b->d_out_keys, b->d_out_vals, b->n_values, parent, depth, tin, tout, trace, true);
-    if (rc == 0) return fail(GS_E_UNSUPPORTED, "gs_dbbuild_to_db: no k-mer of this build fits a record: fetch the arrays and call gs_db_create");
-    return rc < 0 ? rc : GS_OK;
+    return sorted_store_to_db(b->device, b->k, b->n_values, b->parent, b->n_out, b->d_out_keys, b->d_out_vals, "gs_dbbuild_to_db", out);
 }
 GS_API_CATCH
 
@@ -3908,21 +4010,10 @@ extern "C" hipError_t gs_quality_sort_leaf(uint32_t *leaf, uint32_t *leaf_alt, u
                                            u64 **keys_out, hipStream_t stream);
 extern "C" hipError_t gs_launch_quality_join(const GsQualityParams *P, int n_cu, hipStream_t stream);
 
-struct gs_dbquality {
+struct gs_dbquality : RegionStage {  // (parent: the store's tree; no d_tree, the join reads the store's own)
     gs_db *db = nullptr;
-    int device = 0, k = 0, lower = 1, step = 1, max_dust = -1;
-    int32_t n_values = 0;
-    hipStream_t stream = nullptr;
-    std::vector<int32_t> parent;  // the store's tree (host copy)
-    u64 *d_keys = nullptr;        // the (k-mer, leaf) pairs of this pass
-    uint32_t *d_vals = nullptr;
-    u64 *d_count = nullptr;
-    size_t cap = 0, n_pairs = 0;
+    PairBuffer pairs;  // the (k-mer, leaf) pairs of this pass
     u64 range_lo = 0, range_hi = ~0ULL;
-    uint8_t *d_seq = nullptr;  // staging of host input
-    size_t seq_cap = 0;
-    u64 *d_off = nullptr;
-    size_t off_cap = 0;
     uint32_t *d_leaf = nullptr;  // leaf of each region of one add
     size_t leaf_cap = 0;
     int32_t one_leaf = -1;  // all regions so far carry this tag (-2: several)
@@ -3932,23 +4023,9 @@ struct gs_dbquality {
     gs_dbquality_stats stats{};
 };
 
-static void dbquality_free_pass(gs_dbquality *q) {
-    for (void *p : {(void *)q->d_keys, (void *)q->d_vals, (void *)q->d_seq, (void *)q->d_off, (void *)q->d_leaf}) hipFree(p);
-    q->d_keys = nullptr;
-    q->d_vals = nullptr;
-    q->d_seq = nullptr;
-    q->d_off = nullptr;
-    q->d_leaf = nullptr;
-    q->cap = q->n_pairs = q->seq_cap = q->off_cap = q->leaf_cap = 0;
-}
-
 static void dbquality_free(gs_dbquality *q) {
-    hipSetDevice(q->device);
-    if (q->stream) hipStreamSynchronize(q->stream);
-    dbquality_free_pass(q);
-    hipFree(q->d_count);
+    region_stage_free(q, {q->pairs.keys, q->pairs.vals, q->pairs.d_count, q->d_leaf});
     if (q->store) gs_dbexport_destroy(q->store);
-    if (q->stream) hipStreamDestroy(q->stream);
     delete q;
 }
 
@@ -3956,26 +4033,17 @@ extern "C" int gs_dbquality_begin(gs_dbquality **out, gs_db *db, int lower_case_
     if (!out) return fail(GS_E_INVALID, "out is NULL");
     *out = nullptr;
     if (!db) return fail(GS_E_INVALID, "db is NULL");
-    if (step_size < 1) return fail(GS_E_INVALID, "stepSize must be >= 1 (C/GSConfigKey.java:236)");
-    if (max_dust > 32767) return fail(GS_E_INVALID, "maxDust > Short.MAX_VALUE (C/util/CGATLongBuffer.java:78-80)");
-    if (db->striped()) return fail(GS_E_UNSUPPORTED, "gs_dbquality needs the whole store on one device: this handle is a stripe");
-    HIP_TRY(hipSetDevice(db->device));
+    std::vector<int32_t> parent;
+    int rc = region_scan_check(max_dust, step_size);
+    if (!rc) rc = db_whole_store_tree(db, "gs_dbquality", parent);
+    if (rc) return rc;
     gs_dbquality *q = new gs_dbquality();
     q->db = db;
-    q->device = db->device;
-    q->k = db->info.k;
-    q->n_values = db->info.n_values;
-    q->lower = lower_case_bases != 0;
-    q->step = step_size;
-    q->max_dust = max_dust < 0 ? -1 : max_dust;
-    q->parent.resize((size_t)q->n_values);
-    hipError_t e = hipStreamCreateWithFlags(&q->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&q->d_count, sizeof(u64));
-    if (e == hipSuccess) e = hipMemset(q->d_count, 0, sizeof(u64));
-    if (e == hipSuccess) e = hipMemcpy(q->parent.data(), db->d_tree, sizeof(int32_t) * (size_t)q->n_values, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
+    rc = region_stage_open(q, db->device, db->info.k, db->info.n_values, parent.data(), nullptr, lower_case_bases, max_dust, step_size, "gs_dbquality");
+    if (!rc) rc = pairs_open(&q->pairs, "gs_dbquality");
+    if (rc) {
         dbquality_free(q);
-        return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbquality_begin: ") + hipGetErrorString(e));
+        return rc;
     }
     *out = q;
     return GS_OK;
@@ -4013,65 +4081,26 @@ extern "C" int gs_dbquality_add(gs_dbquality *q, const uint8_t *seq, const uint6
         one = one == -1 ? tag : (one == tag ? one : -2);
     }
     std::vector<uint64_t> hoff;
-    const uint64_t *off_host = offsets;
-    if (mem == GS_MEM_DEVICE) {
-        hoff.resize((size_t)n_regions + 1);
-        HIP_TRY(hipMemcpy(hoff.data(), offsets, sizeof(uint64_t) * ((size_t)n_regions + 1), hipMemcpyDeviceToHost));
-        off_host = hoff.data();
-    }
-    if (off_host[0] != 0) return fail(GS_E_INVALID, "offsets[0] must be 0");
-    for (int64_t r = 0; r < n_regions; r++)
-        if (off_host[r + 1] < off_host[r]) return fail(GS_E_INVALID, "offsets must not decrease");
-    const int64_t total = (int64_t)off_host[n_regions];
-    const uint8_t *d_seq = seq;
-    const u64 *d_off = (const u64 *)offsets;
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = grow(&q->d_leaf, &q->leaf_cap, (size_t)n_regions, q->stream);
+    int64_t total = 0;
+    const uint8_t *d_seq = nullptr;
+    const u64 *d_off = nullptr;
+    int rc = region_batch_check(offsets, n_regions, mem, hoff, &total);
     if (rc) return rc;
-    if (mem == GS_MEM_HOST) {
-        rc = grow(&q->d_seq, &q->seq_cap, (size_t)std::max<int64_t>(total, 1), q->stream);
-        if (!rc) rc = grow(&q->d_off, &q->off_cap, (size_t)n_regions + 1, q->stream);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(q->d_seq, seq, (size_t)total, hipMemcpyHostToDevice, q->stream));
-        HIP_TRY(hipMemcpyAsync(q->d_off, offsets, sizeof(u64) * ((size_t)n_regions + 1), hipMemcpyHostToDevice, q->stream));
-        d_seq = q->d_seq;
-        d_off = q->d_off;
-    }
+    const auto t0 = std::chrono::steady_clock::now();
+    rc = grow(&q->d_leaf, &q->leaf_cap, (size_t)n_regions, q->stream);
+    if (!rc) rc = region_stage_upload(q, seq, offsets, n_regions, total, mem, &d_seq, &d_off);
+    if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(q->d_leaf, leaf.data(), sizeof(uint32_t) * (size_t)n_regions, hipMemcpyHostToDevice, q->stream));
-    if (q->n_pairs + (size_t)total > q->cap) {  // the pair buffers grow by doubling
-        size_t want = std::max(q->cap * 2, q->n_pairs + (size_t)total);
-        want = std::max<size_t>(want, 1 << 20);
-        u64 *nk = nullptr;
-        uint32_t *nvl = nullptr;
-        hipError_t e = hipMalloc((void **)&nk, want * sizeof(u64));
-        if (e == hipSuccess) e = hipMalloc((void **)&nvl, want * sizeof(uint32_t));
-        if (e == hipSuccess && q->n_pairs) e = hipMemcpyAsync(nk, q->d_keys, q->n_pairs * sizeof(u64), hipMemcpyDeviceToDevice, q->stream);
-        if (e == hipSuccess && q->n_pairs) e = hipMemcpyAsync(nvl, q->d_vals, q->n_pairs * sizeof(uint32_t), hipMemcpyDeviceToDevice, q->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(q->stream);
-        if (e != hipSuccess) {
-            hipFree(nk);
-            hipFree(nvl);
-            return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbquality_add: ") + hipGetErrorString(e));
-        }
-        hipFree(q->d_keys);
-        hipFree(q->d_vals);
-        q->d_keys = nk;
-        q->d_vals = nvl;
-        q->cap = want;
-    }
     // the builder's kernel with region numbers from 0, then region -> leaf on the pairs it has just written
-    HIP_TRY(gs_launch_build_kmers(d_seq, d_off, n_regions, total, q->k, q->lower, q->step, q->max_dust, 0u, 0, q->range_lo, q->range_hi, q->d_keys,
-                                  q->d_vals, q->d_count, q->stream));
-    u64 have = 0;
-    HIP_TRY(hipMemcpyAsync(&have, q->d_count, sizeof(u64), hipMemcpyDeviceToHost, q->stream));
-    HIP_TRY(hipStreamSynchronize(q->stream));
-    if (have < q->n_pairs || have > q->cap) return fail(GS_E_HIP, "gs_dbquality_add: pair counter out of range");
-    HIP_TRY(gs_launch_quality_tag(q->d_vals + q->n_pairs, (int64_t)(have - q->n_pairs), q->d_leaf, n_regions, q->stream));
-    HIP_TRY(hipStreamSynchronize(q->stream));  // (the caller's arrays and the staging buffers are free again)
-    q->n_pairs = (size_t)have;
+    const size_t before = q->pairs.n;
+    rc = pairs_reserve(&q->pairs, (size_t)total, q->stream, "gs_dbquality_add");
+    if (!rc) rc = pairs_append(q, &q->pairs, d_seq, d_off, n_regions, total, 0u, 0, q->range_lo, q->range_hi, "gs_dbquality_add");
+    if (rc) return rc;
+    HIP_TRY(gs_launch_quality_tag(q->pairs.vals + before, (int64_t)(q->pairs.n - before), q->d_leaf, n_regions, q->stream));
+    HIP_TRY(hipStreamSynchronize(q->stream));  // (d_leaf is free again)
     q->one_leaf = one;
     q->added = true;
-    q->stats.ms_pairs += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    q->stats.ms_pairs += ms_since(t0);
     return GS_OK;
 }
 GS_API_CATCH
@@ -4081,23 +4110,16 @@ extern "C" int gs_dbquality_finish(gs_dbquality *q, int64_t *counts, uint8_t *pr
     if (q->finished) return fail(GS_E_STATE, "gs_dbquality_finish has been called (gs_dbquality_set_range starts another pass)");
     HIP_TRY(hipSetDevice(q->device));
     const int32_t nv = q->n_values;
-    const int64_t n = (int64_t)q->n_pairs;
+    const int64_t n = (int64_t)q->pairs.n;
     using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
-    int rc = GS_OK;
     u64 *keys_alt = nullptr, *d_cnt = nullptr;
     uint32_t *vals_alt = nullptr;
     std::vector<u64> h_cnt(2 * (size_t)nv + 2, 0);
-    auto check = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && rc == GS_OK) rc = fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbquality_finish (") + what + "): " + hipGetErrorString(e));
-        return e == hipSuccess;
-    };
-    // the staging buffers make room for the sort
-    for (void *p : {(void *)q->d_seq, (void *)q->d_off, (void *)q->d_leaf}) hipFree(p);
-    q->d_seq = nullptr;
-    q->d_off = nullptr;
+    HipSteps check{"gs_dbquality_finish"};
+    region_stage_drop_staging(q);  // the staging buffers make room for the sort
+    hipFree(q->d_leaf);
     q->d_leaf = nullptr;
-    q->seq_cap = q->off_cap = q->leaf_cap = 0;
+    q->leaf_cap = 0;
     q->stats.n_pairs = n;
     q->stats.n_distinct = q->stats.n_found = 0;
     q->stats.ms_sort = q->stats.ms_join = 0;
@@ -4105,7 +4127,7 @@ extern "C" int gs_dbquality_finish(gs_dbquality *q, int64_t *counts, uint8_t *pr
     if (!q->store) {
         const auto t0 = clk::now();
         int64_t m = 0;
-        rc = gs_dbexport_create(&q->store, q->db, -1, 0, &m);
+        int rc = gs_dbexport_create(&q->store, q->db, -1, 0, &m);
         if (rc == GS_OK) {
             q->value_counts.assign((size_t)nv, 0);
             rc = gs_db_value_counts(q->db, q->value_counts.data());
@@ -4120,19 +4142,19 @@ extern "C" int gs_dbquality_finish(gs_dbquality *q, int64_t *counts, uint8_t *pr
         q->stats.n_store = m;
     }
     if (n > 0) {
-        u64 *ks = q->d_keys;
-        uint32_t *vs = q->d_vals;
+        u64 *ks = q->pairs.keys;
+        uint32_t *vs = q->pairs.vals;
         auto t0 = clk::now();
         bool ok = check(hipMalloc((void **)&keys_alt, (size_t)n * sizeof(u64)), "sort buffers") &&
                   check(hipMalloc((void **)&vals_alt, (size_t)n * sizeof(uint32_t)), "sort buffers");
         if (ok && q->one_leaf == -2) {  // several leaves: the leaf bits first, the stable k-mer sort keeps their order
             int bits = 1;
             while (((int64_t)1 << bits) <= (int64_t)nv) bits++;
-            ok = check(gs_quality_sort_leaf(q->d_vals, vals_alt, q->d_keys, keys_alt, n, bits, &vs, &ks, q->stream), "leaf sort");
+            ok = check(gs_quality_sort_leaf(q->pairs.vals, vals_alt, q->pairs.keys, keys_alt, n, bits, &vs, &ks, q->stream), "leaf sort");
         }
         if (ok) {
-            u64 *ka = ks == q->d_keys ? keys_alt : q->d_keys;
-            uint32_t *va = vs == q->d_vals ? vals_alt : q->d_vals;
+            u64 *ka = ks == q->pairs.keys ? keys_alt : q->pairs.keys;
+            uint32_t *va = vs == q->pairs.vals ? vals_alt : q->pairs.vals;
             ok = check(gs_build_sort(ks, ka, vs, va, n, 2 * q->k, &ks, &vs, q->stream), "sort");
         }
         q->stats.ms_sort = ms_since(t0);
@@ -4161,10 +4183,10 @@ extern "C" int gs_dbquality_finish(gs_dbquality *q, int64_t *counts, uint8_t *pr
     hipFree(keys_alt);
     hipFree(vals_alt);
     hipFree(d_cnt);
-    dbquality_free_pass(q);
-    HIP_TRY(hipMemset(q->d_count, 0, sizeof(u64)));
+    pairs_drop(&q->pairs);
+    HIP_TRY(hipMemset(q->pairs.d_count, 0, sizeof(u64)));
     q->finished = true;  // (also after a failure: the pairs are gone)
-    if (rc != GS_OK) return rc;
+    if (check.rc != GS_OK) return check.rc;
     q->stats.n_distinct = (int64_t)h_cnt[2 * (size_t)nv];
     q->stats.n_found = (int64_t)h_cnt[2 * (size_t)nv + 1];
     // tp+fp: the stored k-mers on the path leaf -> root (getPathSum, DBQualityCountsGoal.java:137-147, :315-321)
@@ -4217,13 +4239,9 @@ extern "C" hipError_t gs_launch_update_moved(const int32_t *vals, const int32_t 
 
 #define GS_UPD_DEFAULT_SLICE ((int64_t)1 << 25)  // bases per slice: 13 bytes of working memory each (436 MB)
 
-struct gs_dbupdate {
-    int device = 0, k = 0, lower = 1, step = 1, max_dust = -1, n_cu = 256;
-    int32_t n_values = 0;
-    hipStream_t stream = nullptr;
+struct gs_dbupdate : RegionStage {
+    int n_cu = 256;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    std::vector<int32_t> parent;
-    int32_t *d_tree = nullptr;  // parent | depth
     // the store: lives as long as the handle
     int64_t n = 0;
     u64 *d_keys = nullptr;       // ascending, never written
@@ -4233,14 +4251,13 @@ struct gs_dbupdate {
     int dir_bits = 1;
     bool wide = false;
     u64 *d_cnt = nullptr;  // [0] pairs of the slice (the k-mer kernel's counter), [1] pairs so far, [2] found so far, [3] moved; then the check flag
-    // one slice's working memory: sized by the largest slice so far, never by the number of calls
+    // one slice's working memory (with the stage's d_seq / d_off, which hold a slice here and exactly that: dbupdate_room): sized
+    // by the largest slice so far, never by the number of calls
     int64_t slice_bases = GS_UPD_DEFAULT_SLICE;
-    uint8_t *d_seq = nullptr;
-    u64 *d_off = nullptr;
     int32_t *d_node = nullptr;
     u64 *d_pkeys = nullptr;
     uint32_t *d_pvals = nullptr;
-    size_t seq_cap = 0, off_cap = 0, node_cap = 0, pair_cap = 0;
+    size_t node_cap = 0, pair_cap = 0;
     bool finished = false;
     bool failed = false;  // a device error in the middle of an add: the values are half-updated (sticky GS_E_STATE)
     int64_t n_moved = 0;
@@ -4248,52 +4265,32 @@ struct gs_dbupdate {
 };
 
 static void dbupdate_free(gs_dbupdate *u) {
-    hipSetDevice(u->device);
-    if (u->stream) hipStreamSynchronize(u->stream);
-    for (void *p : {(void *)u->d_tree, (void *)u->d_keys, (void *)u->d_vals, (void *)u->d_vals0, u->d_dir, (void *)u->d_cnt, (void *)u->d_seq,
-                    (void *)u->d_off, (void *)u->d_node, (void *)u->d_pkeys, (void *)u->d_pvals})
-        hipFree(p);
+    region_stage_free(u, {u->d_keys, u->d_vals, u->d_vals0, u->d_dir, u->d_cnt, u->d_node, u->d_pkeys, u->d_pvals});
     for (hipEvent_t e : u->ev)
         if (e) hipEventDestroy(e);
-    if (u->stream) hipStreamDestroy(u->stream);
     delete u;
 }
 
 static int64_t dbupdate_max_regions(const gs_dbupdate *u) { return u->slice_bases / 8 + 64; }
 
-// the argument checks every way to begin shares; nothing here touches a device
-static int dbupdate_check_params(int k, int32_t n_values, const int32_t *parent_vi, int max_dust, int step_size, std::vector<int32_t> &depth) {
-    if (k < 1 || k > 31) return fail(GS_E_INVALID, "k must be in [1,31]");
-    if (n_values < 1 || n_values > (1 << 24) || !parent_vi) return fail(GS_E_INVALID, "bad tree arrays (n_values must be in [1, 2^24])");
-    if (step_size < 1) return fail(GS_E_INVALID, "stepSize must be >= 1 (C/GSConfigKey.java:236)");
-    if (max_dust > 32767) return fail(GS_E_INVALID, "maxDust > Short.MAX_VALUE (C/util/CGATLongBuffer.java:78-80)");
-    return build_tree_depths(n_values, parent_vi, depth, "gs_dbupdate");
-}
-
 // handle + stream + tree on the current device
 static int dbupdate_open(gs_dbupdate **out, int device, int k, int32_t n_values, const int32_t *parent_vi, const std::vector<int32_t> &depth, int lower,
                          int max_dust, int step) {
     gs_dbupdate *u = new gs_dbupdate();
-    u->device = device;
-    u->k = k;
-    u->lower = lower != 0;
-    u->step = step;
-    u->max_dust = max_dust < 0 ? -1 : max_dust;
-    u->n_values = n_values;
-    u->parent.assign(parent_vi, parent_vi + n_values);
+    int rc = region_stage_open(u, device, k, n_values, parent_vi, depth.data(), lower, max_dust, step, "gs_dbupdate");
     int cu = 0;
     if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) u->n_cu = cu;
-    hipError_t e = hipStreamCreateWithFlags(&u->stream, hipStreamNonBlocking);
-    for (int i = 0; i < 3 && e == hipSuccess; i++) e = hipEventCreate(&u->ev[i]);
-    if (e == hipSuccess) e = hipMalloc((void **)&u->d_cnt, 5 * sizeof(u64));
-    if (e == hipSuccess) e = hipMemsetAsync(u->d_cnt, 0, 5 * sizeof(u64), u->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(u->stream);
-    if (e == hipSuccess) e = hipMalloc((void **)&u->d_tree, sizeof(int32_t) * 2 * (size_t)n_values);
-    if (e == hipSuccess) e = hipMemcpy(u->d_tree, parent_vi, sizeof(int32_t) * (size_t)n_values, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(u->d_tree + n_values, depth.data(), sizeof(int32_t) * (size_t)n_values, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
+    if (!rc) {
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < 3 && e == hipSuccess; i++) e = hipEventCreate(&u->ev[i]);
+        if (e == hipSuccess) e = hipMalloc((void **)&u->d_cnt, 5 * sizeof(u64));
+        if (e == hipSuccess) e = hipMemsetAsync(u->d_cnt, 0, 5 * sizeof(u64), u->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(u->stream);
+        if (e != hipSuccess) rc = hip_fail(e, "gs_dbupdate_begin");
+    }
+    if (rc) {
         dbupdate_free(u);
-        return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbupdate_begin: ") + hipGetErrorString(e));
+        return rc;
     }
     *out = u;
     return GS_OK;
@@ -4327,8 +4324,20 @@ static int dbupdate_adopt(gs_dbupdate *u, bool check) {
     return GS_OK;
 }
 
-static double dbupdate_ms_since(std::chrono::steady_clock::time_point t) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+// the store's arrays copied into the handle (n_kmers pairs from either memory), then dbupdate_adopt; the handle goes on failure
+static int dbupdate_copy_in(gs_dbupdate *u, const void *kmers, const void *value_idx, int64_t n_kmers, hipMemcpyKind kind, bool check,
+                            const char *who) {
+    u->n = n_kmers;
+    const size_t m = std::max<size_t>((size_t)n_kmers, 1);
+    hipError_t e = hipMalloc((void **)&u->d_keys, m * sizeof(u64));
+    if (e == hipSuccess) e = hipMalloc((void **)&u->d_vals, m * sizeof(int32_t));
+    // (on the handle's stream: a device-to-device hipMemcpy need not be complete when it returns, and this stream does not wait for the null stream)
+    if (e == hipSuccess && n_kmers > 0) e = hipMemcpyAsync(u->d_keys, kmers, (size_t)n_kmers * sizeof(u64), kind, u->stream);
+    if (e == hipSuccess && n_kmers > 0) e = hipMemcpyAsync(u->d_vals, value_idx, (size_t)n_kmers * sizeof(int32_t), kind, u->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(u->stream);  // (the caller's arrays are free again)
+    const int rc = e != hipSuccess ? hip_fail(e, who) : dbupdate_adopt(u, check);
+    if (rc) dbupdate_free(u);
+    return rc;
 }
 
 extern "C" int gs_dbupdate_begin(gs_dbupdate **out, int device, int k, int32_t n_values, const int32_t *parent_vi, int lower_case_bases,
@@ -4338,30 +4347,16 @@ extern "C" int gs_dbupdate_begin(gs_dbupdate **out, int device, int k, int32_t n
     if (n_kmers < 0 || (n_kmers > 0 && (!kmers || !value_idx))) return fail(GS_E_INVALID, "bad store arrays");
     if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
     std::vector<int32_t> depth;
-    int rc = dbupdate_check_params(k, n_values, parent_vi, max_dust, step_size, depth);
+    int rc = region_params_check(k, n_values, parent_vi, max_dust, step_size, depth, "gs_dbupdate");
     if (rc) return rc;
     rc = use_device(device);
     if (rc) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     gs_dbupdate *u = nullptr;
     rc = dbupdate_open(&u, device, k, n_values, parent_vi, depth, lower_case_bases, max_dust, step_size);
+    if (!rc) rc = dbupdate_copy_in(u, kmers, value_idx, n_kmers, mem == GS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, true, "gs_dbupdate_begin");
     if (rc) return rc;
-    u->n = n_kmers;
-    const size_t m = std::max<size_t>((size_t)n_kmers, 1);
-    const hipMemcpyKind kind = mem == GS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    hipError_t e = hipMalloc((void **)&u->d_keys, m * sizeof(u64));
-    if (e == hipSuccess) e = hipMalloc((void **)&u->d_vals, m * sizeof(int32_t));
-    // (on the handle's stream: a device-to-device hipMemcpy need not be complete when it returns, and this stream does not wait for the null stream)
-    if (e == hipSuccess && n_kmers > 0) e = hipMemcpyAsync(u->d_keys, kmers, (size_t)n_kmers * sizeof(u64), kind, u->stream);
-    if (e == hipSuccess && n_kmers > 0) e = hipMemcpyAsync(u->d_vals, value_idx, (size_t)n_kmers * sizeof(int32_t), kind, u->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(u->stream);  // (the caller's arrays are free again)
-    if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbupdate_begin: ") + hipGetErrorString(e));
-    if (!rc) rc = dbupdate_adopt(u, true);
-    if (rc) {
-        dbupdate_free(u);
-        return rc;
-    }
-    u->stats.ms_begin = dbupdate_ms_since(t0);
+    u->stats.ms_begin = ms_since(t0);
     *out = u;
     return GS_OK;
 }
@@ -4371,15 +4366,13 @@ extern "C" int gs_dbupdate_begin_db(gs_dbupdate **out, gs_db *db, int lower_case
     if (!out) return fail(GS_E_INVALID, "out is NULL");
     *out = nullptr;
     if (!db) return fail(GS_E_INVALID, "db is NULL");
-    if (step_size < 1) return fail(GS_E_INVALID, "stepSize must be >= 1 (C/GSConfigKey.java:236)");
-    if (max_dust > 32767) return fail(GS_E_INVALID, "maxDust > Short.MAX_VALUE (C/util/CGATLongBuffer.java:78-80)");
-    if (db->striped()) return fail(GS_E_UNSUPPORTED, "gs_dbupdate needs the whole store on one device: this handle is a stripe");
-    HIP_TRY(hipSetDevice(db->device));
+    std::vector<int32_t> parent, depth;
+    int rc = region_scan_check(max_dust, step_size);
+    if (rc) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     const int32_t nv = db->info.n_values;
-    std::vector<int32_t> parent((size_t)nv), depth;
-    HIP_TRY(hipMemcpy(parent.data(), db->d_tree, sizeof(int32_t) * (size_t)nv, hipMemcpyDeviceToHost));
-    int rc = dbupdate_check_params(db->info.k, nv, parent.data(), max_dust, step_size, depth);
+    rc = db_whole_store_tree(db, "gs_dbupdate", parent);
+    if (!rc) rc = region_params_check(db->info.k, nv, parent.data(), max_dust, step_size, depth, "gs_dbupdate");
     if (rc) return rc;
     // the store in ascending k-mer order, decoded on the device (seen bits masked); its arrays move into the handle
     gs_dbexport *x = nullptr;
@@ -4404,7 +4397,7 @@ extern "C" int gs_dbupdate_begin_db(gs_dbupdate **out, gs_db *db, int lower_case
         dbupdate_free(u);
         return rc;
     }
-    u->stats.ms_begin = dbupdate_ms_since(t0);
+    u->stats.ms_begin = ms_since(t0);
     *out = u;
     return GS_OK;
 }
@@ -4418,26 +4411,14 @@ extern "C" int gs_dbupdate_begin_build(gs_dbupdate **out, gs_dbbuild *b) try {
     HIP_TRY(hipSetDevice(b->device));
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<int32_t> depth;
-    int rc = dbupdate_check_params(b->k, b->n_values, b->parent.data(), b->max_dust, b->step, depth);
+    int rc = region_params_check(b->k, b->n_values, b->parent.data(), b->max_dust, b->step, depth, "gs_dbupdate");
     if (rc) return rc;
     gs_dbupdate *u = nullptr;
     rc = dbupdate_open(&u, b->device, b->k, b->n_values, b->parent.data(), depth, b->lower, b->max_dust, b->step);
-    if (rc) return rc;
     // device-to-device: the builder keeps its own arrays for gs_dbbuild_fetch / _to_db
-    u->n = b->n_out;
-    const size_t m = std::max<size_t>((size_t)b->n_out, 1);
-    hipError_t e = hipMalloc((void **)&u->d_keys, m * sizeof(u64));
-    if (e == hipSuccess) e = hipMalloc((void **)&u->d_vals, m * sizeof(int32_t));
-    if (e == hipSuccess && b->n_out > 0) e = hipMemcpyAsync(u->d_keys, b->d_out_keys, (size_t)b->n_out * sizeof(u64), hipMemcpyDeviceToDevice, u->stream);
-    if (e == hipSuccess && b->n_out > 0) e = hipMemcpyAsync(u->d_vals, b->d_out_vals, (size_t)b->n_out * sizeof(int32_t), hipMemcpyDeviceToDevice, u->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(u->stream);
-    if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbupdate_begin_build: ") + hipGetErrorString(e));
-    if (!rc) rc = dbupdate_adopt(u, false);
-    if (rc) {
-        dbupdate_free(u);
-        return rc;
-    }
-    u->stats.ms_begin = dbupdate_ms_since(t0);
+    if (!rc) rc = dbupdate_copy_in(u, b->d_out_keys, b->d_out_vals, b->n_out, hipMemcpyDeviceToDevice, false, "gs_dbupdate_begin_build");
+    if (rc) return rc;
+    u->stats.ms_begin = ms_since(t0);
     *out = u;
     return GS_OK;
 }
@@ -4452,6 +4433,7 @@ extern "C" int gs_dbupdate_set_slice(gs_dbupdate *u, int64_t max_bases) {
     return GS_OK;
 }
 
+// exactly `need`, no slack (grow adds a quarter): batch_bytes_peak is a reported figure
 template <typename T>
 static hipError_t dbupdate_room(T **p, size_t *cap, size_t need) {
     if (*cap >= need) return hipSuccess;
@@ -4470,21 +4452,13 @@ extern "C" int gs_dbupdate_add(gs_dbupdate *u, const uint8_t *seq, const uint64_
     if (u->finished) return fail(GS_E_STATE, "gs_dbupdate_finish has been called");
     if (n_regions == 0) return GS_OK;
     if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
-    // node_vi is a host array in both cases (one entry per region)
-    for (int64_t r = 0; r < n_regions; r++)
-        if (node_vi[r] < 0 || node_vi[r] >= u->n_values || u->parent[(size_t)node_vi[r]] == -2) return fail(GS_E_INVALID, "node_vi: not a node of the tree");
     HIP_TRY(hipSetDevice(u->device));
     std::vector<uint64_t> hoff;
-    const uint64_t *off = offsets;
-    if (mem == GS_MEM_DEVICE) {
-        hoff.resize((size_t)n_regions + 1);
-        HIP_TRY(hipMemcpy(hoff.data(), offsets, sizeof(uint64_t) * ((size_t)n_regions + 1), hipMemcpyDeviceToHost));
-        off = hoff.data();
-    }
-    if (off[0] != 0) return fail(GS_E_INVALID, "offsets[0] must be 0");
-    for (int64_t r = 0; r < n_regions; r++)
-        if (off[r + 1] < off[r]) return fail(GS_E_INVALID, "offsets must not decrease");
-    const int64_t total = (int64_t)off[n_regions];
+    int64_t total = 0;
+    int rc = region_nodes_check(u, node_vi, n_regions);
+    if (!rc) rc = region_batch_check(offsets, n_regions, mem, hoff, &total);
+    if (rc) return rc;
+    const uint64_t *off = mem == GS_MEM_DEVICE ? hoff.data() : offsets;
     const int64_t slice = u->slice_bases, max_regions = dbupdate_max_regions(u);
     // all of the call's working memory before any of its work: an out-of-memory leaves the values as they were
     {
@@ -4499,7 +4473,7 @@ extern "C" int gs_dbupdate_add(gs_dbupdate *u, const uint8_t *seq, const uint64_
             if (e == hipSuccess) e = dbupdate_room(&u->d_pvals, &c2, bases);
             u->pair_cap = std::min(c1, c2);
         }
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbupdate_add: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return hip_fail(e, "gs_dbupdate_add");
         const int64_t bytes = (int64_t)(u->seq_cap + u->off_cap * sizeof(u64) + u->node_cap * sizeof(int32_t) + u->pair_cap * (sizeof(u64) + sizeof(uint32_t)));
         u->stats.batch_bytes_peak = std::max(u->stats.batch_bytes_peak, bytes);
     }
@@ -4524,13 +4498,9 @@ extern "C" int gs_dbupdate_add(gs_dbupdate *u, const uint8_t *seq, const uint64_
     // in exactly one piece.
     std::vector<uint64_t> soff;
     std::vector<int32_t> snode;
-    int rc = GS_OK;
-    auto check = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && rc == GS_OK) rc = fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_dbupdate_add (") + what + "): " + hipGetErrorString(e));
-        return e == hipSuccess;
-    };
+    HipSteps check{"gs_dbupdate_add"};
     int64_t r = 0, c = 0;  // the next piece starts c bases into region r
-    while (r < n_regions && rc == GS_OK) {
+    while (r < n_regions && check.rc == GS_OK) {
         soff.assign(1, 0);
         snode.clear();
         const int64_t begin = (int64_t)off[r] + c;
@@ -4561,7 +4531,7 @@ extern "C" int gs_dbupdate_add(gs_dbupdate *u, const uint8_t *seq, const uint64_
             check(hipMemcpyAsync(u->d_seq, seq + begin, (size_t)used, hipMemcpyHostToDevice, u->stream), "copy");
             d_seq = u->d_seq;
         }
-        bool ok = rc == GS_OK && check(hipMemcpyAsync(u->d_off, soff.data(), sizeof(u64) * ((size_t)n_sl + 1), hipMemcpyHostToDevice, u->stream), "copy") &&
+        bool ok = check.rc == GS_OK && check(hipMemcpyAsync(u->d_off, soff.data(), sizeof(u64) * ((size_t)n_sl + 1), hipMemcpyHostToDevice, u->stream), "copy") &&
                   check(hipMemcpyAsync(u->d_node, snode.data(), sizeof(int32_t) * (size_t)n_sl, hipMemcpyHostToDevice, u->stream), "copy") &&
                   check(hipMemsetAsync(u->d_cnt, 0, sizeof(u64), u->stream), "counter") && check(hipEventRecord(u->ev[0], u->stream), "event") &&
                   check(gs_launch_build_kmers(d_seq, u->d_off, n_sl, used, u->k, u->lower, u->step, u->max_dust, 0u, 0, 0, ~0ULL, u->d_pkeys, u->d_pvals,
@@ -4573,9 +4543,9 @@ extern "C" int gs_dbupdate_add(gs_dbupdate *u, const uint8_t *seq, const uint64_
         if (ok && hipEventElapsedTime(&ms, u->ev[0], u->ev[1]) == hipSuccess) u->stats.ms_kmers += ms;
         if (ok && hipEventElapsedTime(&ms, u->ev[1], u->ev[2]) == hipSuccess) u->stats.ms_lookup += ms;
     }
-    if (rc != GS_OK) {
+    if (check.rc != GS_OK) {
         u->failed = true;
-        return rc;
+        return check.rc;
     }
     u64 cnt[2] = {0, 0};
     HIP_TRY(hipMemcpy(cnt, u->d_cnt + 1, sizeof(cnt), hipMemcpyDeviceToHost));
@@ -4601,16 +4571,15 @@ extern "C" int gs_dbupdate_finish(gs_dbupdate *u, int64_t *n_moved) try {
     HIP_TRY(hipMemcpyAsync(&moved, u->d_cnt + 3, sizeof(u64), hipMemcpyDeviceToHost, u->stream));
     HIP_TRY(hipStreamSynchronize(u->stream));
     // the slice's working memory goes (gs_dbupdate_to_db needs the room); batch_bytes_peak keeps what it was
-    for (void *p : {(void *)u->d_seq, (void *)u->d_off, (void *)u->d_node, (void *)u->d_pkeys, (void *)u->d_pvals}) hipFree(p);
-    u->d_seq = nullptr;
-    u->d_off = nullptr;
+    region_stage_drop_staging(u);
+    for (void *p : {(void *)u->d_node, (void *)u->d_pkeys, (void *)u->d_pvals}) hipFree(p);
     u->d_node = nullptr;
     u->d_pkeys = nullptr;
     u->d_pvals = nullptr;
-    u->seq_cap = u->off_cap = u->node_cap = u->pair_cap = 0;
+    u->node_cap = u->pair_cap = 0;
     u->n_moved = (int64_t)moved;
     u->stats.n_moved = u->n_moved;
-    u->stats.ms_finish = dbupdate_ms_since(t0);
+    u->stats.ms_finish = ms_since(t0);
     u->finished = true;
     *n_moved = u->n_moved;
     return GS_OK;
@@ -4620,28 +4589,14 @@ GS_API_CATCH
 extern "C" int gs_dbupdate_fetch(gs_dbupdate *u, int64_t *kmers, int32_t *value_idx) {
     if (!u || (u->n > 0 && (!kmers || !value_idx))) return fail(GS_E_INVALID, "NULL argument");
     if (!u->finished) return fail(GS_E_STATE, "gs_dbupdate_finish first");
-    HIP_TRY(hipSetDevice(u->device));
-    if (u->n > 0) {
-        HIP_TRY(hipMemcpy(kmers, u->d_keys, (size_t)u->n * sizeof(int64_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(value_idx, u->d_vals, (size_t)u->n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
-    return GS_OK;
+    return sorted_store_fetch(u->device, u->n, u->d_keys, u->d_vals, kmers, value_idx);
 }
 
 extern "C" int gs_dbupdate_to_db(gs_dbupdate *u, gs_db **out) try {
     if (!u || !out) return fail(GS_E_INVALID, "NULL argument");
     *out = nullptr;
     if (!u->finished) return fail(GS_E_STATE, "gs_dbupdate_finish first");
-    if (u->n <= 0 || u->k < GS_MIN_K || u->n_values > GS_REC_MAX_VALUES || u->n >= ((int64_t)1 << 31))
-        return fail(GS_E_UNSUPPORTED, "gs_dbupdate_to_db serves stores with records (k >= 19, at most 2^21 values, 1 .. 2^31 - 1 k-mers): fetch the arrays and call gs_db_create");
-    HIP_TRY(hipSetDevice(u->device));
-    std::vector<int32_t> parent, depth, tin, tout;
-    int rc = tree_arrays(u->n_values, u->parent.data(), parent, depth, tin, tout);
-    if (rc) return rc;
-    BuildTrace trace;
-    rc = db_create_on_device(out, u->device, u->k, u->n, (const int64_t *)u->d_keys, u->d_vals, u->n_values, parent, depth, tin, tout, trace, true);
-    if (rc == 0) return fail(GS_E_UNSUPPORTED, "gs_dbupdate_to_db: no k-mer of this store fits a record: fetch the arrays and call gs_db_create");
-    return rc < 0 ? rc : GS_OK;
+    return sorted_store_to_db(u->device, u->k, u->n_values, u->parent, u->n, u->d_keys, u->d_vals, "gs_dbupdate_to_db", out);
 }
 GS_API_CATCH
 
@@ -5194,7 +5149,7 @@ extern "C" int gs_bloom_create(gs_bloom **out, int device, int kind, int64_t bit
     if (e == hipSuccess) e = hipMemcpy(b->d_factors, hash_factors, sizeof(int64_t) * (size_t)n_hashes, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         gs_bloom_destroy(b);
-        return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("bloom upload: ") + hipGetErrorString(e));
+        return hip_fail(e, "bloom upload");
     }
     *out = b;
     return GS_OK;
@@ -5269,7 +5224,7 @@ extern "C" int gs_bloom_build(gs_bloom **out, int device, int kind, const int64_
     hipFree(d_keys);
     if (e != hipSuccess) {
         gs_bloom_destroy(b);
-        return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, std::string("gs_bloom_build: ") + hipGetErrorString(e));
+        return hip_fail(e, "gs_bloom_build");
     }
     *out = b;
     return GS_OK;
