@@ -2327,6 +2327,12 @@ struct gs_run {
     int32_t *d_stat_vi = nullptr;      // the records' value indices as an array (stores with more values than one reduce pass takes)
     size_t stat_vi_cap = 0;
     bool use_stat_recs = false;
+    // gates and quotients of a batch of one read length (GsQuotTable): built for (positions, both gate settings), uploaded once from
+    // the page-locked copy and reused by every later batch of that length
+    GsQuotTable *d_quot = nullptr, *h_quot = nullptr;
+    hipEvent_t quot_copied = nullptr;  // the upload has left h_quot
+    int quot_max = 0;                  // what the table was built for: positions (0: none yet) and the two gate settings
+    double quot_tax = 0, quot_class = 0;
     int stat_copies = 1;         // > 1: global-atomic counters spread over several copies (GsMatchParams::stat_copies)
     bool stats_spread = false;   // some copy other than 0 may be non-zero: fold_stats() before reading
     uint32_t *d_hit_counts = nullptr;  // per slot, only when cfg.max_kmer_res_counts > 0
@@ -2668,6 +2674,9 @@ static void run_free(gs_run *run) {
     hipFree(run->d_stat_recs);
     hipFree(run->d_stat_vi);
     hipFree(run->d_stat_rec_count);
+    hipFree(run->d_quot);
+    hipHostFree(run->h_quot);
+    if (run->quot_copied) hipEventDestroy(run->quot_copied);
     hipFree(run->d_route_cursors);
     hipFree(run->d_bitmap);
     hipFree(run->d_hit_counts);
@@ -2875,6 +2884,40 @@ static int ensure_huge(gs_run *run, GsMatchParams *P) {
     return hipMemsetAsync(P->huge_count, 0, sizeof(unsigned int), run->stream) == hipSuccess ? GS_OK : fail(GS_E_HIP, "huge-read counter");
 }
 
+// The table of a batch of one read length with `max` k-mer positions (65 .. 128: what the FIXED loop of gs_match_kernel takes), keyed
+// by max and the run's two gate settings; every predicate and quotient is the general loop's expression (gs_process_read),
+// evaluated here for every error count the length allows.  One upload per change of length, on
+// the run's stream and from memory the run owns: batches of the same length copy nothing.
+static int ensure_quot(gs_run *run, int max) {
+    const double m = run->cfg.max_read_tax_err, mc = run->cfg.max_read_class_err;
+    if (run->quot_max == max && run->quot_tax == m && run->quot_class == mc) return GS_OK;
+    if (!run->d_quot) {
+        HIP_TRY(hipMalloc((void **)&run->d_quot, sizeof(GsQuotTable)));
+        HIP_TRY(hipHostMalloc((void **)&run->h_quot, sizeof(GsQuotTable), hipHostMallocDefault));
+        HIP_TRY(hipEventCreateWithFlags(&run->quot_copied, hipEventDisableTiming));
+    } else
+        HIP_TRY(hipEventSynchronize(run->quot_copied));  // (the previous length's upload reads h_quot)
+    run->quot_max = 0;
+    GsQuotTable &T = *run->h_quot;
+    memset(&T, 0, sizeof(T));
+    for (int i = 0; i <= max; i++) {
+        const int tax_err = i, class_err = i;
+        const double q = (double)i / (double)max;
+        T.e[i].q = q;
+        T.e[i].q2 = q * q;
+        const bool disabled = m >= 0 && ((m >= 1 && (double)tax_err > m) || ((double)tax_err > m * (double)max));
+        const bool counted = mc < 0 || (mc >= 1 && (double)class_err <= mc) || ((double)class_err <= mc * (double)max);
+        if (disabled) T.tax_disabled[i >> 5] |= 1u << (i & 31);
+        if (counted) T.class_counted[i >> 5] |= 1u << (i & 31);
+    }
+    HIP_TRY(hipMemcpyAsync(run->d_quot, run->h_quot, sizeof(GsQuotTable), hipMemcpyHostToDevice, run->stream));
+    HIP_TRY(hipEventRecord(run->quot_copied, run->stream));
+    run->quot_max = max;
+    run->quot_tax = m;
+    run->quot_class = mc;
+    return GS_OK;
+}
+
 static int launch_batch(gs_run *run, const uint8_t *d_seq, const uint64_t *d_off, int64_t n_reads, int64_t first_read_no,
                         int32_t *d_class, uint8_t *d_flags, const int32_t *d_nodes = nullptr,
                         const uint64_t *d_pos_off = nullptr, int off_stride = 1, const uint32_t *d_skip = nullptr, int fixed_len = 0) {
@@ -2910,6 +2953,11 @@ static int launch_batch(gs_run *run, const uint8_t *d_seq, const uint64_t *d_off
     P.off_stride = off_stride;
     P.fixed_len = fixed_len;
     P.skip = d_skip;
+    // (the batches whose waves take the FIXED loop of gs_match_kernel, and no others, need the table; that loop takes none without it)
+    if (off_stride == 0 && !d_nodes && fixed_len >= 128 && fixed_len - run->db->info.k + 1 <= GS_QUOT_ENTRIES - 1) {
+        if ((rc = ensure_quot(run, fixed_len - run->db->info.k + 1))) return rc;
+        P.quot = run->d_quot;
+    }
     int grid = (int)std::min<int64_t>(run->grid, (n_reads + (GS_BLOCK / 64) - 1) / (GS_BLOCK / 64));
     if (grid < 1) grid = 1;
     const int64_t rec_room = n_reads + (int64_t)grid * (GS_BLOCK / 64) * 64;  // every wave may leave one chunk of 64 partly used

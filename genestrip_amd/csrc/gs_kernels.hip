@@ -920,8 +920,18 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
             // ---- 4c. classification (:474-531)
             if (P.classify) {
                 const int tax_err = n_miss + bad_lo + (bad_hi ? 1 : 0);
-                const double m = P.max_read_tax_err;
-                const bool disabled = m >= 0 && ((m >= 1 && (double)tax_err > m) || ((double)tax_err > m * (double)max));
+                // FIXED: max is the batch's, so both gates are one bit per error count and both quotients one entry of the batch's table
+                // (GsQuotTable, built by launch_batch from the expressions below); the counts are wave-uniform, the table is read
+                // through the scalar cache and no double arithmetic is left in this loop
+                typedef const __attribute__((address_space(4))) GsQuotTable *GsQuotPtr;
+                const GsQuotPtr qt = FIXED ? (GsQuotPtr)P.quot : nullptr;
+                bool disabled;
+                if (FIXED) {
+                    disabled = ((qt->tax_disabled[tax_err >> 5] >> (tax_err & 31)) & 1u) != 0;
+                } else {
+                    const double m = P.max_read_tax_err;
+                    disabled = m >= 0 && ((m >= 1 && (double)tax_err > m) || ((double)tax_err > m * (double)max));
+                }
                 if (!disabled) {
                     int cn = -1, first_node = -1, best = 0;
                     // one distinct node v with c positions: the only candidate path is v, its sum is c, and the threshold
@@ -1043,14 +1053,32 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
                                 }
                             }
                         }
-                        const int class_err = max - read_kmers;
-                        const double mc = P.max_read_class_err;
-                        if (mc < 0 || (mc >= 1 && (double)class_err <= mc) || ((double)class_err <= mc * (double)max)) {
+                        const int class_err = FIXED ? gs_rfl(max - read_kmers) : max - read_kmers;
+                        bool counted;
+                        if (FIXED) {
+                            counted = ((qt->class_counted[class_err >> 5] >> (class_err & 31)) & 1u) != 0;
+                        } else {
+                            const double mc = P.max_read_class_err;
+                            counted = mc < 0 || (mc >= 1 && (double)class_err <= mc) || ((double)class_err <= mc * (double)max);
+                        }
+                        if (counted) {
                             out_flags |= GS_F_COUNTED;
                             if (REC && deferred) {  // (cn == one_vi: the only candidate)
                                 def_counted = 1;
                                 def_read_kmers = read_kmers;
                                 def_tax_err = tax_err;
+                            } else if (FIXED) {
+                                const double err = qt->e[tax_err].q, err_sq = qt->e[tax_err].q2;  // (16 bytes each: one scalar load)
+                                const double cerr = qt->e[class_err].q, cerr_sq = qt->e[class_err].q2;
+                                if (lane == 0) {
+                                    st.add(cn, GS_S_READS, 1);
+                                    st.add(cn, GS_S_READS_KMERS, (u64)read_kmers);
+                                    st.add(cn, GS_S_READS_BPS, (u64)L);
+                                    st.dadd(cn, GS_D_ERR_SUM, err);
+                                    st.dadd(cn, GS_D_ERR_SQ_SUM, err_sq);
+                                    st.dadd(cn, GS_D_CLASS_ERR_SUM, cerr);
+                                    st.dadd(cn, GS_D_CLASS_ERR_SQ_SUM, cerr_sq);
+                                }
                             } else if (lane == 0) {
                                 const double err = (double)tax_err / (double)max;
                                 const double cerr = (double)class_err / (double)max;
@@ -1084,9 +1112,9 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
             rec.counted = def_counted;
             rec.read_kmers = def_read_kmers;
             rec.read_len = L;
-            rec.pad = 0;
-            rec.err = (double)def_tax_err / (double)max;
-            rec.cerr = (double)(max - def_read_kmers) / (double)max;
+            rec.n_pos = max;
+            rec.tax_err = def_tax_err;
+            rec.pad[0] = rec.pad[1] = rec.pad[2] = 0;
             P.stat_recs[rbase + used] = rec;
         }
     }
@@ -1291,7 +1319,8 @@ __global__ __launch_bounds__(GS_BLOCK) __attribute__((amdgpu_waves_per_eu(GS_WAV
     // (LDS_STATS, KC, CTX) is what the launchers, the occupancy query and the profiles' kernel names know.
     constexpr bool CAN_FIX = !FROM_NODES && !WIDE && !STRIPED;
     const int fixed_L = P.fixed_len;
-    const bool fixed_batch = CAN_FIX && P.off_stride == 0 && fixed_L >= 128 && fixed_L - k + 1 <= 128;
+    // (launch_batch hands a GsQuotTable to exactly these batches; the FIXED loop reads its gates and quotients from it)
+    const bool fixed_batch = CAN_FIX && P.off_stride == 0 && fixed_L >= 128 && fixed_L - k + 1 <= 128 && P.quot != nullptr;
     const u64 fixed_live1 = gs_low_mask(fixed_L - k + 1 - 64);
     auto reads = [&](auto fixed) {
         constexpr bool FIXED = decltype(fixed)::value;
@@ -2268,10 +2297,13 @@ __global__ __launch_bounds__(1024) void gs_stat_reduce_kernel(const GsStatRec *r
             atomicAdd(&row[GS_S_READS], 1ULL);
             atomicAdd(&row[GS_S_READS_KMERS], (u64)rc.read_kmers);
             atomicAdd(&row[GS_S_READS_BPS], (u64)rc.read_len);
-            atomicAdd(&dr[GS_D_ERR_SUM], rc.err);
-            atomicAdd(&dr[GS_D_ERR_SQ_SUM], rc.err * rc.err);
-            atomicAdd(&dr[GS_D_CLASS_ERR_SUM], rc.cerr);
-            atomicAdd(&dr[GS_D_CLASS_ERR_SQ_SUM], rc.cerr * rc.cerr);
+            // (formed here, one thread per record, and not by lane 0 of the wave that wrote it)
+            const double err = (double)rc.tax_err / (double)rc.n_pos;
+            const double cerr = (double)(rc.n_pos - rc.read_kmers) / (double)rc.n_pos;
+            atomicAdd(&dr[GS_D_ERR_SUM], err);
+            atomicAdd(&dr[GS_D_ERR_SQ_SUM], err * err);
+            atomicAdd(&dr[GS_D_CLASS_ERR_SUM], cerr);
+            atomicAdd(&dr[GS_D_CLASS_ERR_SQ_SUM], cerr * cerr);
         }
     }
     __syncthreads();

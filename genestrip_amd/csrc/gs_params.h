@@ -24,8 +24,29 @@ struct GsStatRec {
     int32_t counted;     // 1: the read was classified to vi and passed the class-error gate
     int32_t read_kmers;
     int32_t read_len;
-    int32_t pad;
-    double err, cerr;
+    int32_t n_pos;       // k-mer positions of the read (`max` of matchRead)
+    // the error quotients tax_err / n_pos and (n_pos - read_kmers) / n_pos are formed by gs_stat_reduce_kernel, one thread per
+    // record: in the match kernel a division on lane 0 costs what 64 cost
+    int32_t tax_err;
+    int32_t pad[3];      // (64 bytes: a record never straddles two cache lines)
+};
+static_assert(sizeof(GsStatRec) == 64, "GsStatRec");
+
+// What a batch of ONE read length (gs_match_submit_fixed, the FIXED loop of gs_match_kernel) knows before its first read: with
+// max = read_len - k + 1 <= 128 positions, tax_err and class_err are integers in 0 .. max, so both error gates are one bit per
+// value and both quotients one table entry.  Built on the host (launch_batch) with the very expressions of the general loop, in
+// plain double arithmetic: i / max is the correctly rounded quotient on the host as on the device.
+// (tax_err <= max: a window with a bad base is INVALID, never a MISS, so n_miss + bad_lo counts every position below max - 1 at
+// most once, and a bad base behind them (bad_hi) makes the last window INVALID.  class_err = max - read_kmers, 1 <= read_kmers.)
+#define GS_QUOT_ENTRIES 129
+#define GS_QUOT_WORDS ((GS_QUOT_ENTRIES + 31) / 32)
+struct GsQuotEntry {
+    double q, q2;  // i / max and its square
+};
+struct GsQuotTable {
+    GsQuotEntry e[GS_QUOT_ENTRIES];
+    uint32_t tax_disabled[GS_QUOT_WORDS];   // bit i: tax_err == i fails the max_read_tax_err gate
+    uint32_t class_counted[GS_QUOT_WORDS];  // bit i: class_err == i passes the max_read_class_err gate
 };
 
 struct GsMatchParams {
@@ -61,6 +82,9 @@ struct GsMatchParams {
     // folded into copy 0 before anything reads the accumulators
     int32_t stat_copies;
     const uint32_t *skip;
+    // gates and quotients of this batch's one read length (the FIXED loop of gs_match_kernel reads nothing else of them), or nullptr:
+    // a batch with offsets, a length that loop does not take
+    const GsQuotTable *quot;
     GsStatRec *stat_recs;  // deferred statistics (global-atomic counters only) or nullptr: room for n_reads + 64 per wave
     unsigned long long *stat_rec_count;  // records handed out so far (waves take them 64 at a time)
     // Reads of huge_min k-mer positions and more (assembled contigs, chromosomes: the reference grows its read buffer for them,
