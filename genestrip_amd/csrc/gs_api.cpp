@@ -19,160 +19,9 @@
 #include <vector>
 
 #include "gs_absmod.h"
+#include "gs_launch.h"
 #include "gs_layout.h"
 #include "gs_params.h"
-
-typedef unsigned long long u64;
-
-// ---------------------------------------------------------------------------------------------------
-// Device blocks between calls.  A file-level call (gs_host_match_files: begin, a few submits, finish, destroy) allocates some twenty
-// buffers -- text banks, queues, result arrays -- and frees them 30 ms later; hipMalloc and hipFree of those cost 5.5 of the 30 ms
-// (GS_HOST_TRACE: the first submit 2.9 ms against 0.09 for the next ones, destroy 2.6).  Every hipMalloc / hipFree of THIS file goes
-// through a small cache instead: a freed block waits (per device, by exact size) for the next request of its size.  hipFree's
-// contract is kept -- the device is idle when it returns --, only the unmapping is saved.  At most GS_DEVICE_CACHE_MB (default 4096)
-// wait, the oldest go first; a block of more than a quarter of that (a big store) is never kept; when an allocation fails everything
-// that waits is freed and the allocation tried again; gs_device_cache_trim() frees it all (gs_host_release_pools calls it).
-// ---------------------------------------------------------------------------------------------------
-#include <deque>
-#include <mutex>
-#include <unordered_map>
-namespace gs_cache {
-struct Block {
-    void *p;
-    size_t n;
-    int dev;
-};
-struct State {
-    std::mutex mu;
-    std::unordered_map<void *, std::pair<size_t, int>> live;  // blocks handed out: size, device
-    std::deque<Block> idle;                                    // blocks that wait, oldest first
-    size_t idle_bytes = 0;
-};
-static State &state() {
-    static State *s = new State();  // (never destroyed: blocks may be freed from static destructors)
-    return *s;
-}
-static size_t cap_bytes() {
-    static const size_t v = [] {
-        const char *e = getenv("GS_DEVICE_CACHE_MB");
-        return (size_t)(e ? std::max(0, atoi(e)) : 4096) << 20;
-    }();
-    return v;
-}
-static void drop_idle_locked(State &st, size_t keep_bytes) {
-    int cur = 0;
-    const bool have = hipGetDevice(&cur) == hipSuccess;
-    while (!st.idle.empty() && st.idle_bytes > keep_bytes) {
-        const Block b = st.idle.front();
-        st.idle.pop_front();
-        st.idle_bytes -= b.n;
-        hipSetDevice(b.dev);
-        hipFree(b.p);
-    }
-    if (have) hipSetDevice(cur);
-}
-static hipError_t alloc(void **p, size_t n) {
-    State &st = state();
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    {
-        std::lock_guard<std::mutex> lk(st.mu);
-        for (auto it = st.idle.begin(); it != st.idle.end(); ++it)
-            if (it->n == n && it->dev == dev) {
-                *p = it->p;
-                st.idle_bytes -= n;
-                st.idle.erase(it);
-                st.live[*p] = {n, dev};
-                return hipSuccess;
-            }
-    }
-    static const bool trace = getenv("GS_CACHE_TRACE") != nullptr;  // (developer: which requests the cache could not serve)
-    if (trace) fprintf(stderr, "device cache: %zu bytes allocated\n", n);
-    e = hipMalloc(p, n);
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        {
-            std::lock_guard<std::mutex> lk(st.mu);
-            drop_idle_locked(st, 0);
-        }
-        e = hipMalloc(p, n);
-    }
-    if (e == hipSuccess && n != 0 && n <= cap_bytes() / 4) {
-        std::lock_guard<std::mutex> lk(st.mu);
-        st.live[*p] = {n, dev};
-    }
-    return e;
-}
-static hipError_t release(void *p) {
-    if (!p) return hipSuccess;
-    State &st = state();
-    std::unique_lock<std::mutex> lk(st.mu);
-    const auto it = st.live.find(p);
-    if (it == st.live.end()) {
-        lk.unlock();
-        return hipFree(p);
-    }
-    const Block b{p, it->second.first, it->second.second};
-    st.live.erase(it);
-    lk.unlock();
-    int cur = 0;
-    const bool have = hipGetDevice(&cur) == hipSuccess;
-    if (have && cur != b.dev) hipSetDevice(b.dev);
-    const hipError_t e = hipDeviceSynchronize();  // (what hipFree guarantees: nothing on the device uses the block any more)
-    if (have && cur != b.dev) hipSetDevice(cur);
-    lk.lock();
-    st.idle.push_back(b);
-    st.idle_bytes += b.n;
-    drop_idle_locked(st, cap_bytes());
-    return e;
-}
-static void trim() {
-    State &st = state();
-    std::lock_guard<std::mutex> lk(st.mu);
-    drop_idle_locked(st, 0);
-}
-}  // namespace gs_cache
-template <typename T>
-static inline hipError_t gs_cached_malloc(T **p, size_t n) {
-    return gs_cache::alloc(reinterpret_cast<void **>(p), n);
-}
-static inline hipError_t gs_cached_free(void *p) { return gs_cache::release(p); }
-#define hipMalloc gs_cached_malloc
-#define hipFree gs_cached_free
-
-extern "C" int gs_device_cache_trim(void) {
-    gs_cache::trim();
-    return GS_OK;
-}
-
-extern "C" hipError_t gs_launch_match(const GsMatchParams *P, int grid, hipStream_t stream);
-extern "C" hipError_t gs_launch_match_huge(const GsMatchParams *P, int grid, hipStream_t stream);
-extern "C" hipError_t gs_launch_match_wide(const GsMatchParams *P, int ns, int n_cu, hipStream_t stream);
-extern "C" int gs_match_wide_mask(const GsMatchParams *P);
-extern "C" hipError_t gs_launch_classify(const GsMatchParams *P, hipStream_t stream);
-extern "C" hipError_t gs_launch_fold_stats(long long *sums, unsigned long long *maxk, double *dsums, long long nv, int copies, hipStream_t stream);
-extern "C" hipError_t gs_launch_match_long(const GsMatchParams *P, int grid, int32_t *scratch, uint32_t *serial,
-                                           hipStream_t stream);
-extern "C" hipError_t gs_launch_unique_count(const u64 *table, const uint32_t *bitmap, int64_t n_slots, uint32_t vbits,
-                                              int32_t n_values, u64 *unique, const u64 *rec, int64_t n_rec, hipStream_t stream);
-extern "C" hipError_t gs_launch_rec_unique_count(const u64 *rec, const uint32_t *bitmap_rec, int64_t n_rec, int32_t n_values,
-                                                  u64 *unique, hipStream_t stream);
-extern "C" hipError_t gs_launch_clear_seen(u64 *table, int64_t n_slots, u64 *rec, int64_t n_rec, hipStream_t stream);
-extern "C" hipError_t gs_launch_bitmap_extract(const u64 *table, int64_t n_slots, uint32_t *bitmap, const u64 *rec, int64_t n_rec,
-                                                hipStream_t stream);
-extern "C" hipError_t gs_launch_bitmap_or(uint32_t *dst, const uint32_t *parts, int64_t n_words, int64_t n_parts,
-                                           hipStream_t stream);
-extern "C" hipError_t gs_launch_segments(const struct GsSegParams *P, int write, int grid, hipStream_t stream);
-extern "C" hipError_t gs_launch_encode(const struct GsEncodeParams *P, int grid, hipStream_t stream);
-extern "C" hipError_t gs_launch_probe_keys(const GsDbDev *db, const u64 *keys, int64_t n, int32_t *nodes, int count_unique,
-                                            hipStream_t stream);
-extern "C" hipError_t gs_launch_filter(const struct GsFilterParams *P, int grid, hipStream_t stream);
-extern "C" hipError_t gs_launch_stat_reduce(const GsStatRec *recs, const void *count, int64_t n_max, int n_values, void *sums, void *maxk,
-                                             void *dsums, int32_t *vi_scratch, hipStream_t stream);
-extern "C" int gs_match_occupancy(int n_values);
-extern "C" int gs_match_long_occupancy(int n_values);
-extern "C" int gs_filter_occupancy();
 
 // ---------------------------------------------------------------------------------------------------
 // errors
@@ -285,7 +134,7 @@ struct StripeGroup {
     ~StripeGroup() {
         for (auto &a : allocs) {
             hipSetDevice(a.first);
-            hipFree(a.second);
+            gs_dev_free(a.second);
         }
     }
 };
@@ -312,11 +161,11 @@ static const u64 *stripe_table(const gs_db *db, int q, int64_t *first, int64_t *
 static void db_free(gs_db *db) {
     hipSetDevice(db->device);
     for (void *p : db->ipc_opened) hipIpcCloseMemHandle(p);
-    if (!db->striped()) hipFree(db->d_table);  // (a stripe's table buckets live behind its record lines)
-    hipFree(db->d_gate);
-    hipFree(db->d_mgate);
-    if (!db->group) hipFree(db->d_rec);
-    hipFree(db->d_tree);
+    if (!db->striped()) gs_dev_free(db->d_table);  // (a stripe's table buckets live behind its record lines)
+    gs_dev_free(db->d_gate);
+    gs_dev_free(db->d_mgate);
+    if (!db->group) gs_dev_free(db->d_rec);
+    gs_dev_free(db->d_tree);
     delete db;
 }
 
@@ -466,18 +315,18 @@ static int store_upload(const StoreImage &im, int dev_no, int stripes, int part,
     const u64 *tsrc = im.table + (size_t)tfirst * GS_SLOTS_PER_BUCKET;
     hipError_t e = hipSuccess;
     if (stripes > 1) {
-        e = hipMalloc((void **)&db->d_rec, rbytes + tbytes);
+        e = gs_dev_alloc((void **)&db->d_rec, rbytes + tbytes);
         if (e == hipSuccess) e = hipMemcpy(db->d_rec, rsrc, rbytes, hipMemcpyDefault);
         if (e == hipSuccess) db->d_table = db->d_rec + (size_t)rlocal * GS_REC_WORDS;
     } else {
-        e = hipMalloc((void **)&db->d_table, tbytes);
-        if (e == hipSuccess && rbytes) e = hipMalloc((void **)&db->d_rec, rbytes);
+        e = gs_dev_alloc((void **)&db->d_table, tbytes);
+        if (e == hipSuccess && rbytes) e = gs_dev_alloc((void **)&db->d_rec, rbytes);
         if (e == hipSuccess && rbytes) e = hipMemcpy(db->d_rec, rsrc, rbytes, hipMemcpyDefault);
     }
-    if (e == hipSuccess) e = hipMalloc((void **)&db->d_tree, sizeof(int32_t) * 4 * (size_t)n_values);
-    if (e == hipSuccess && im.gate_words) e = hipMalloc((void **)&db->d_gate, im.gate_words * sizeof(u64));
+    if (e == hipSuccess) e = gs_dev_alloc((void **)&db->d_tree, sizeof(int32_t) * 4 * (size_t)n_values);
+    if (e == hipSuccess && im.gate_words) e = gs_dev_alloc((void **)&db->d_gate, im.gate_words * sizeof(u64));
     if (e == hipSuccess && im.gate_words) e = hipMemcpy(db->d_gate, im.gate, im.gate_words * sizeof(u64), hipMemcpyDefault);
-    if (e == hipSuccess && im.mgate_words) e = hipMalloc((void **)&db->d_mgate, im.mgate_words * sizeof(uint32_t));
+    if (e == hipSuccess && im.mgate_words) e = gs_dev_alloc((void **)&db->d_mgate, im.mgate_words * sizeof(uint32_t));
     if (e == hipSuccess && im.mgate_words) e = hipMemcpy(db->d_mgate, im.mgate, im.mgate_words * sizeof(uint32_t), hipMemcpyDefault);
     if (e == hipSuccess) e = hipMemcpy(db->d_table, tsrc, tbytes, hipMemcpyDefault);
     if (e == hipSuccess) e = hipMemcpy(db->d_tree, im.parent, sizeof(int32_t) * n_values, hipMemcpyDefault);
@@ -697,47 +546,18 @@ static int tree_arrays(int32_t n_values, const int32_t *parent_vi, std::vector<i
 // the layout built on the device (gs_layout_build.hip): same rules as the host builder below
 // ---------------------------------------------------------------------------------------------------
 enum { GS_LB_N_E = 0, GS_LB_N_T, GS_LB_N_M, GS_LB_N_H, GS_LB_IN_REC, GS_LB_OVERFLOW, GS_LB_MAX_DISP, GS_LB_N_WIN, GS_LB_N_CTX, GS_LB_N_HINT, GS_LB_COUNTERS };
-extern "C" hipError_t gs_lb_perkey(const int64_t *kmers, const int32_t *vidx, int64_t n, int k, const int32_t *parent, uint32_t *e_gh, uint32_t *e_ohi,
-                                   uint32_t *e_olo, uint32_t *e_vj, u64 *e_sort, u64 *e_sort2, u64 *t_key, int32_t *t_val, uint32_t *m_gh, uint32_t *h_gh, uint32_t *h_ctx,
-                                   u64 *cnt, hipStream_t stream);
-extern "C" hipError_t gs_lb_sort_entries(u64 *e_sort, u64 *e_sort2, u64 *sort_alt, uint32_t *perm, uint32_t *perm_alt, int64_t n, const uint32_t *e_gh,
-                                         const uint32_t *e_ohi, const uint32_t *e_olo, const uint32_t *e_vj, uint32_t *s_gh, uint32_t *s_ohi,
-                                         uint32_t *s_olo, uint32_t *s_vj, hipStream_t stream);
-extern "C" hipError_t gs_lb_groups(const uint32_t *s_gh, int64_t n, uint32_t *head, uint32_t *group, uint32_t *g_start, int64_t *n_groups,
-                                   hipStream_t stream);
-extern "C" hipError_t gs_lb_cluster(const uint32_t *s_gh, const uint32_t *s_ohi, const uint32_t *s_olo, const uint32_t *s_vj, const uint32_t *g_start,
-                                    int64_t n_groups, int k, uint8_t *assign, u64 *w_hi, u64 *w_lo, uint32_t *w_valid, uint32_t *w_gh, u64 *cnt,
-                                    hipStream_t stream);
-extern "C" hipError_t gs_lb_place(const uint32_t *w_valid, const uint32_t *w_gh, int64_t n_w, uint32_t rec_bits, int max_rounds, uint32_t *slot,
-                                  uint32_t *slot2, uint32_t *claim, uint32_t *state, uint32_t *win_bucket, u64 *changes, int *rounds_done,
-                                  hipStream_t stream);
-extern "C" hipError_t gs_lb_lines(const uint32_t *slot, uint32_t rec_bits, const u64 *w_hi, const u64 *w_lo, const uint32_t *w_valid, const uint32_t *s_gh,
-                                  const uint32_t *s_ohi, const uint32_t *s_olo, const uint32_t *s_vj, const uint32_t *group, const uint8_t *assign,
-                                  const uint32_t *win_bucket, int64_t n_e, int k, u64 *rec, u64 *t_key, int32_t *t_val, uint32_t *m_gh, u64 *cnt,
-                                  hipStream_t stream);
-extern "C" hipError_t gs_lb_more(const uint32_t *m_gh, int64_t n_m, uint32_t rec_bits, u64 *rec, hipStream_t stream);
-extern "C" hipError_t gs_lb_table(const u64 *t_key, const int32_t *t_val, int64_t n_t, int b, int vbits, u64 *rot_a, u64 *rot_b, int32_t *val_b,
-                                  int32_t *val_c, uint32_t *start, uint32_t *left, uint32_t *pos, uint32_t *perm, uint32_t *perm_alt, uint32_t *fill_a,
-                                  uint32_t *fill_b, u64 *table, int64_t *overflow, int *max_disp, hipStream_t stream);
-extern "C" hipError_t gs_lb_distinct(uint32_t *h_gh, uint32_t *h_alt, int64_t n_h, u64 *d_scratch, int64_t *distinct, uint32_t **sorted,
-                                     hipStream_t stream);
-extern "C" hipError_t gs_lb_gate(const uint32_t *h_gh, int64_t n_h, int ctx, uint32_t mgate_bits, uint32_t *mgate, hipStream_t stream);
-extern "C" hipError_t gs_lb_hint_collect(const uint32_t *w_valid, const uint32_t *w_gh, const u64 *w_hi, const u64 *w_lo, const uint32_t *win_bucket,
-                                         int64_t n_w, uint32_t rec_bits, int k, uint32_t *hint_gh, uint32_t *hint_cx, u64 *cnt, hipStream_t stream);
-extern "C" hipError_t gs_lb_hint(const uint32_t *hint_gh, const uint32_t *hint_cx, int64_t n, int ctx, uint32_t mgate_bits, uint32_t *mgate,
-                                 hipStream_t stream);
 
 // device scratch that goes when the build is over (or fails)
 struct DevPool {
     std::vector<void *> all;
     hipError_t err = hipSuccess;
     ~DevPool() {
-        for (void *p : all) hipFree(p);
+        for (void *p : all) gs_dev_free(p);
     }
     template <typename T>
     T *get(size_t count) {
         void *p = nullptr;
-        if (err == hipSuccess) err = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
+        if (err == hipSuccess) err = gs_dev_alloc(&p, std::max<size_t>(count, 1) * sizeof(T));
         if (err != hipSuccess) return nullptr;
         all.push_back(p);
         return (T *)p;
@@ -745,7 +565,7 @@ struct DevPool {
     void drop(void *p) {
         for (void *&x : all)
             if (x == p && p) {
-                hipFree(p);
+                gs_dev_free(p);
                 x = nullptr;
             }
     }
@@ -1972,37 +1792,6 @@ extern "C" int gs_db_destroy(gs_db *db) {
 // ---------------------------------------------------------------------------------------------------
 // the store read back (gs_export.hip): KMerStore.visit, Database.getStats, KMerFastqGenerator
 // ---------------------------------------------------------------------------------------------------
-struct GsExportParams {  // (gs_export.hip)
-    const u64 *rec;
-    int64_t n_rec;
-    const u64 *tab;
-    int64_t tab_first, n_tab;
-    uint32_t bucket_bits, vbits;
-    int32_t k, n_values;
-    const int32_t *tin, *tout;
-    int32_t sel_vi, with_desc;
-    u64 *count, *keys;
-    uint32_t *vals;
-    u64 cap;
-    u64 *hist;
-};
-struct GsFastqParams {  // (gs_export.hip)
-    const u64 *keys;
-    const uint32_t *vals;
-    int64_t first, n;
-    int32_t k;
-    const uint8_t *project;
-    int32_t project_len;
-    const uint8_t *names;
-    const uint32_t *name_off;
-    uint32_t *len, *off;
-    uint8_t *text;
-};
-extern "C" hipError_t gs_launch_export_decode(const GsExportParams *P, int n_cu, hipStream_t stream);
-extern "C" hipError_t gs_launch_export_fastq(const GsFastqParams *P, void *scratch, size_t *scratch_bytes, int64_t *n_bytes, hipStream_t stream);
-extern "C" hipError_t gs_build_sort(u64 *keys, u64 *keys_alt, uint32_t *vals, uint32_t *vals_alt, int64_t n, int key_bits, u64 **keys_out,
-                                    uint32_t **vals_out, hipStream_t stream);
-
 // the part of the store this handle holds: all of it, a partition's table, or a stripe's record lines + table buckets
 static GsExportParams export_params(const gs_db *db, int32_t sel_vi, int with_desc) {
     GsExportParams P{};
@@ -2040,7 +1829,7 @@ struct gs_dbexport {
 
 static void dbexport_free_text(gs_dbexport *x) {
     for (void *p : {(void *)x->d_names, (void *)x->d_project, (void *)x->d_text, (void *)x->d_name_off, (void *)x->d_len, (void *)x->d_off, x->d_scan})
-        hipFree(p);
+        gs_dev_free(p);
     x->d_names = x->d_project = x->d_text = nullptr;
     x->d_name_off = x->d_len = x->d_off = nullptr;
     x->d_scan = nullptr;
@@ -2051,8 +1840,8 @@ static void dbexport_free(gs_dbexport *x) {
     hipSetDevice(x->device);
     if (x->stream) hipStreamSynchronize(x->stream);
     dbexport_free_text(x);
-    hipFree(x->d_keys);
-    hipFree(x->d_vals);
+    gs_dev_free(x->d_keys);
+    gs_dev_free(x->d_vals);
     if (x->stream) hipStreamDestroy(x->stream);
     delete x;
 }
@@ -2064,7 +1853,7 @@ extern "C" int gs_db_value_counts(gs_db *db, int64_t *counts) {
     hipStream_t stream = nullptr;
     HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     u64 *d = nullptr;
-    hipError_t e = hipMalloc((void **)&d, sizeof(u64) * ((size_t)nv + 1));
+    hipError_t e = gs_dev_alloc((void **)&d, sizeof(u64) * ((size_t)nv + 1));
     GsExportParams P = export_params(db, -1, 0);
     P.count = d;
     P.hist = d + 1;
@@ -2072,7 +1861,7 @@ extern "C" int gs_db_value_counts(gs_db *db, int64_t *counts) {
     if (e == hipSuccess) e = gs_launch_export_decode(&P, db->n_cu, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(counts, d + 1, sizeof(u64) * (size_t)nv, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    hipFree(d);
+    gs_dev_free(d);
     hipStreamDestroy(stream);
     if (e != hipSuccess) return hip_fail(e, "gs_db_value_counts");
     return GS_OK;
@@ -2094,17 +1883,17 @@ extern "C" int gs_dbexport_create(gs_dbexport **out, gs_db *db, int32_t sel_vi, 
     auto step = [&](hipError_t e) { return e == hipSuccess; };
     hipError_t e = hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking);
     // pass 1 counts (the stripe's / partition's share is not in the info), pass 2 writes exactly that many
-    if (step(e)) e = hipMalloc((void **)&d_count, sizeof(u64));
+    if (step(e)) e = gs_dev_alloc((void **)&d_count, sizeof(u64));
     if (step(e)) e = hipMemsetAsync(d_count, 0, sizeof(u64), x->stream);
     P.count = d_count;
     if (step(e)) e = gs_launch_export_decode(&P, db->n_cu, x->stream);
     if (step(e)) e = hipMemcpyAsync(&n, d_count, sizeof(u64), hipMemcpyDeviceToHost, x->stream);
     if (step(e)) e = hipStreamSynchronize(x->stream);
     const size_t m = n ? (size_t)n : 1;
-    if (step(e)) e = hipMalloc((void **)&x->d_keys, m * sizeof(u64));
-    if (step(e)) e = hipMalloc((void **)&x->d_vals, m * sizeof(uint32_t));
-    if (step(e)) e = hipMalloc((void **)&keys_alt, m * sizeof(u64));
-    if (step(e)) e = hipMalloc((void **)&vals_alt, m * sizeof(uint32_t));
+    if (step(e)) e = gs_dev_alloc((void **)&x->d_keys, m * sizeof(u64));
+    if (step(e)) e = gs_dev_alloc((void **)&x->d_vals, m * sizeof(uint32_t));
+    if (step(e)) e = gs_dev_alloc((void **)&keys_alt, m * sizeof(u64));
+    if (step(e)) e = gs_dev_alloc((void **)&vals_alt, m * sizeof(uint32_t));
     if (step(e)) e = hipMemsetAsync(d_count, 0, sizeof(u64), x->stream);
     P.keys = x->d_keys;
     P.vals = x->d_vals;
@@ -2116,15 +1905,15 @@ extern "C" int gs_dbexport_create(gs_dbexport **out, gs_db *db, int32_t sel_vi, 
     u64 *ko = x->d_keys;
     uint32_t *vo = x->d_vals;
     if (step(e) && n2 == n) e = gs_build_sort(x->d_keys, keys_alt, x->d_vals, vals_alt, (int64_t)n, 2 * x->k, &ko, &vo, x->stream);
-    hipFree(d_count);
+    gs_dev_free(d_count);
     if (e == hipSuccess) {  // keep the buffers the sorted pairs ended up in
-        hipFree(ko == x->d_keys ? keys_alt : x->d_keys);
-        hipFree(vo == x->d_vals ? vals_alt : x->d_vals);
+        gs_dev_free(ko == x->d_keys ? keys_alt : x->d_keys);
+        gs_dev_free(vo == x->d_vals ? vals_alt : x->d_vals);
         x->d_keys = ko;
         x->d_vals = vo;
     } else {
-        hipFree(keys_alt);
-        hipFree(vals_alt);
+        gs_dev_free(keys_alt);
+        gs_dev_free(vals_alt);
     }
     if (e != hipSuccess) {
         dbexport_free(x);
@@ -2188,16 +1977,16 @@ extern "C" int gs_dbexport_fastq_begin(gs_dbexport *x, const char *const *taxids
     x->project_len = (int32_t)plen;
     GsFastqParams P{};
     P.n = x->chunk_records;
-    hipError_t e = hipMalloc((void **)&x->d_names, names.size() + 1);
-    if (e == hipSuccess) e = hipMalloc((void **)&x->d_name_off, off.size() * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&x->d_project, plen + 1);
-    if (e == hipSuccess) e = hipMalloc((void **)&x->d_len, ((size_t)x->chunk_records + 1) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&x->d_off, ((size_t)x->chunk_records + 1) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&x->d_text, x->text_cap);
+    hipError_t e = gs_dev_alloc((void **)&x->d_names, names.size() + 1);
+    if (e == hipSuccess) e = gs_dev_alloc((void **)&x->d_name_off, off.size() * sizeof(uint32_t));
+    if (e == hipSuccess) e = gs_dev_alloc((void **)&x->d_project, plen + 1);
+    if (e == hipSuccess) e = gs_dev_alloc((void **)&x->d_len, ((size_t)x->chunk_records + 1) * sizeof(uint32_t));
+    if (e == hipSuccess) e = gs_dev_alloc((void **)&x->d_off, ((size_t)x->chunk_records + 1) * sizeof(uint32_t));
+    if (e == hipSuccess) e = gs_dev_alloc((void **)&x->d_text, x->text_cap);
     P.len = x->d_len;
     P.off = x->d_off;
     if (e == hipSuccess) e = gs_launch_export_fastq(&P, nullptr, &x->scan_bytes, nullptr, x->stream);
-    if (e == hipSuccess) e = hipMalloc(&x->d_scan, x->scan_bytes ? x->scan_bytes : 1);
+    if (e == hipSuccess) e = gs_dev_alloc(&x->d_scan, x->scan_bytes ? x->scan_bytes : 1);
     if (e == hipSuccess && !names.empty()) e = hipMemcpy(x->d_names, names.data(), names.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(x->d_name_off, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
     if (e == hipSuccess && plen) e = hipMemcpy(x->d_project, project, plen, hipMemcpyHostToDevice);
@@ -2372,17 +2161,17 @@ struct gs_run {
 
 
 static void text_free_fasta(TextScan &t) {
-    hipFree(t.d_ml_next);
-    hipFree(t.d_ml_plus);
-    hipFree(t.d_ml_ja);
-    hipFree(t.d_ml_jb);
-    hipFree(t.d_ml_mark);
-    hipFree(t.d_ml_class);
-    hipFree(t.d_ml_out);
-    hipFree(t.d_fa_scan);
-    hipFree(t.d_fa_block);
-    hipFree(t.d_line_dst);
-    hipFree(t.d_fa_seq);
+    gs_dev_free(t.d_ml_next);
+    gs_dev_free(t.d_ml_plus);
+    gs_dev_free(t.d_ml_ja);
+    gs_dev_free(t.d_ml_jb);
+    gs_dev_free(t.d_ml_mark);
+    gs_dev_free(t.d_ml_class);
+    gs_dev_free(t.d_ml_out);
+    gs_dev_free(t.d_fa_scan);
+    gs_dev_free(t.d_fa_block);
+    gs_dev_free(t.d_line_dst);
+    gs_dev_free(t.d_fa_seq);
 }
 
 static void text_free(TextScan &t) {
@@ -2393,17 +2182,17 @@ static void text_free(TextScan &t) {
     }
     for (hipEvent_t ev : t.done)
         if (ev) hipEventDestroy(ev);
-    hipFree(t.d_buf[0]);
-    hipFree(t.d_buf[1]);
-    hipFree(t.d_tile);
-    hipFree(t.d_nl);
-    hipFree(t.d_off2);
-    hipFree(t.d_status);
-    hipFree(t.d_totals);
+    gs_dev_free(t.d_buf[0]);
+    gs_dev_free(t.d_buf[1]);
+    gs_dev_free(t.d_tile);
+    gs_dev_free(t.d_nl);
+    gs_dev_free(t.d_off2);
+    gs_dev_free(t.d_status);
+    gs_dev_free(t.d_totals);
     for (auto &w : t.d_compact)
-        for (uint8_t *q : w) hipFree(q);
-    hipFree(t.d_clen);
-    hipFree(t.d_cblocks);
+        for (uint8_t *q : w) gs_dev_free(q);
+    gs_dev_free(t.d_clen);
+    gs_dev_free(t.d_cblocks);
     if (t.h_ctotals) hipHostFree(t.h_ctotals);
     for (hipEvent_t ev : t.copied)
         if (ev) hipEventDestroy(ev);
@@ -2414,11 +2203,11 @@ template <typename T>
 static int grow(T **p, size_t *cap, size_t need, hipStream_t stream) {
     if (*cap >= need) return GS_OK;
     HIP_TRY(hipStreamSynchronize(stream));
-    hipFree(*p);
+    gs_dev_free(*p);
     *p = nullptr;
     *cap = 0;
     const size_t n = need + need / 4;
-    HIP_TRY(hipMalloc((void **)p, n * sizeof(T)));
+    HIP_TRY(gs_dev_alloc((void **)p, n * sizeof(T)));
     *cap = n;
     return GS_OK;
 }
@@ -2442,9 +2231,6 @@ static int text_reset(TextScan &t, bool totals, hipStream_t stream, bool all = f
     return GS_OK;
 }
 
-extern "C" hipError_t gs_launch_text_scan(const GsTextParams *P, uint32_t ticket, hipStream_t stream);
-extern "C" hipError_t gs_launch_text_ml(const GsTextParams *P, uint8_t *line_class, hipStream_t stream);
-
 // copies the chunk to the device and runs the record scan; *ticket identifies the chunk.  After it the (start, end)
 // pairs of the sequence lines are in t.d_off2, the newline offsets in t.d_nl and the skip flag in t.d_status.
 // fasta_records < 0: four-line FASTQ; >= 0: FASTA with that many header lines (gs_text.hip)
@@ -2466,8 +2252,8 @@ static int text_submit(TextScan &t, hipStream_t stream, const uint8_t *text, int
     if (n_bytes > ((int64_t)1 << 30)) return fail(GS_E_INVALID, "text chunks are limited to 1 GiB");
     if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
     if (!t.d_status) {
-        HIP_TRY(hipMalloc((void **)&t.d_status, sizeof(uint32_t) * GS_TS_WORDS * GS_TEXT_BANKS));
-        HIP_TRY(hipMalloc((void **)&t.d_totals, sizeof(u64) * 6 * GS_TEXT_BANKS));
+        HIP_TRY(gs_dev_alloc((void **)&t.d_status, sizeof(uint32_t) * GS_TS_WORDS * GS_TEXT_BANKS));
+        HIP_TRY(gs_dev_alloc((void **)&t.d_totals, sizeof(u64) * 6 * GS_TEXT_BANKS));
         int rc = text_reset(t, true, stream, true);
         if (rc) return rc;
         for (hipEvent_t &ev : t.copied) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -2498,7 +2284,7 @@ static int text_submit(TextScan &t, hipStream_t stream, const uint8_t *text, int
         if ((rc = grow(&t.d_ml_jb, &t.ml_jb_cap, nl1, stream))) return rc;
         if ((rc = grow(&t.d_ml_mark, &t.ml_mark_cap, nl1, stream))) return rc;
         if ((rc = grow(&t.d_ml_class, &t.ml_class_cap, nl1, stream))) return rc;
-        if (!t.d_ml_out) HIP_TRY(hipMalloc((void **)&t.d_ml_out, sizeof(u64) * 4));
+        if (!t.d_ml_out) HIP_TRY(gs_dev_alloc((void **)&t.d_ml_out, sizeof(u64) * 4));
     }
     t.d_text = t.d_buf[b];
     // the copy waits for the kernels of the chunk before last (they read this buffer), the scan for the copy
@@ -2578,10 +2364,6 @@ static int text_submit(TextScan &t, hipStream_t stream, const uint8_t *text, int
     return GS_OK;
 }
 
-extern "C" int gs_compact_records_device(hipStream_t stream, const uint8_t *d_text, const uint32_t *d_nl, int64_t n_records, const uint8_t *d_flags, int mask, int want,
-                                         int with_probs, uint8_t *d_out, uint32_t *d_len, u64 *d_blocks, u64 *h_totals);
-extern "C" const char *gs_deflate_last_error(void);
-
 static int text_touched(TextScan &t, hipStream_t stream);
 
 // the records of the last chunk whose flag says so, as ReadEntry.write writes them, into t.d_compact[which][slot]; synchronises
@@ -2646,6 +2428,23 @@ static int text_status(TextScan &t, hipStream_t stream, int64_t *failed_ticket, 
     return GS_OK;
 }
 
+// (start, end) of the reads of the most recent chunk, a FASTA one (`four_line`: the caller's words for the other kind); synchronises
+static int text_read_bounds(TextScan &t, hipStream_t stream, uint64_t *bounds, const char *four_line) {
+    if (t.tickets == 0) return fail(GS_E_STATE, "no text chunk has been submitted");
+    if (!t.last_fasta) return fail(GS_E_STATE, four_line);
+    HIP_TRY(hipMemcpyAsync(bounds, t.d_off2, sizeof(uint64_t) * ((size_t)t.last_reads + 1), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return GS_OK;
+}
+
+// the line classes of the most recent general FASTQ chunk; synchronises
+static int text_line_classes(TextScan &t, hipStream_t stream, uint8_t *classes) {
+    if (t.tickets == 0 || !t.d_ml_class) return fail(GS_E_STATE, "no general FASTQ chunk has been submitted");
+    if (t.last_lines > 0) HIP_TRY(hipMemcpyAsync(classes, t.d_ml_class, (size_t)t.last_lines, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return GS_OK;
+}
+
 static int run_clear(gs_run *run) {
     const size_t nv = (size_t)run->db->info.n_values;
     const size_t cp = (size_t)run->stat_copies;
@@ -2670,29 +2469,29 @@ static void run_free(gs_run *run) {
         hipEventDestroy(p.second);
     }
     hipHostFree(run->h_result);
-    hipFree(run->d_sums);  // (d_max, d_dsums, d_long_count lie inside)
-    hipFree(run->d_stat_recs);
-    hipFree(run->d_stat_vi);
-    hipFree(run->d_stat_rec_count);
-    hipFree(run->d_quot);
+    gs_dev_free(run->d_sums);  // (d_max, d_dsums, d_long_count lie inside)
+    gs_dev_free(run->d_stat_recs);
+    gs_dev_free(run->d_stat_vi);
+    gs_dev_free(run->d_stat_rec_count);
+    gs_dev_free(run->d_quot);
     hipHostFree(run->h_quot);
     if (run->quot_copied) hipEventDestroy(run->quot_copied);
-    hipFree(run->d_route_cursors);
-    hipFree(run->d_bitmap);
-    hipFree(run->d_hit_counts);
-    hipFree(run->d_unique);
-    hipFree(run->d_long_list);
-    hipFree(run->d_scratch);
-    hipFree(run->d_serial);
-    hipFree(run->d_huge);
-    hipFree(run->d_seq);
-    hipFree(run->d_off);
-    hipFree(run->d_class);
-    hipFree(run->d_flags);
-    hipFree(run->d_seg_count);
-    hipFree(run->d_seg_off);
-    hipFree(run->d_seg_code);
-    hipFree(run->d_seg_start);
+    gs_dev_free(run->d_route_cursors);
+    gs_dev_free(run->d_bitmap);
+    gs_dev_free(run->d_hit_counts);
+    gs_dev_free(run->d_unique);
+    gs_dev_free(run->d_long_list);
+    gs_dev_free(run->d_scratch);
+    gs_dev_free(run->d_serial);
+    gs_dev_free(run->d_huge);
+    gs_dev_free(run->d_seq);
+    gs_dev_free(run->d_off);
+    gs_dev_free(run->d_class);
+    gs_dev_free(run->d_flags);
+    gs_dev_free(run->d_seg_count);
+    gs_dev_free(run->d_seg_off);
+    gs_dev_free(run->d_seg_code);
+    gs_dev_free(run->d_seg_start);
     text_free(run->text);
     {
         BatchStage &g = run->stage;
@@ -2701,10 +2500,10 @@ static void run_free(gs_run *run) {
             hipStreamDestroy(g.copy_stream);
         }
         for (int b = 0; b < 2; b++) {
-            hipFree(g.d_seq[b]);
-            hipFree(g.d_off[b]);
-            hipFree(g.d_class[b]);
-            hipFree(g.d_flags[b]);
+            gs_dev_free(g.d_seq[b]);
+            gs_dev_free(g.d_off[b]);
+            gs_dev_free(g.d_class[b]);
+            gs_dev_free(g.d_flags[b]);
             if (g.copied[b]) hipEventDestroy(g.copied[b]);
         }
         for (hipEvent_t ev : g.finished)
@@ -2752,16 +2551,16 @@ extern "C" int gs_match_begin(gs_run **out, gs_db *db, const gs_match_cfg *cfg) 
     }
     const size_t cp = (size_t)run->stat_copies;
     // sums | max keys | double sums | long-read queue counters in ONE allocation: one memset clears them (gs_match_reset)
-    if (e == hipSuccess) e = hipMalloc((void **)&run->d_sums, sizeof(int64_t) * nv * (GS_N_SUMS + 1 + GS_N_DCOLS) * cp + 8 * sizeof(unsigned int));
+    if (e == hipSuccess) e = gs_dev_alloc((void **)&run->d_sums, sizeof(int64_t) * nv * (GS_N_SUMS + 1 + GS_N_DCOLS) * cp + 8 * sizeof(unsigned int));
     if (e == hipSuccess) {
         run->d_max = run->d_sums + nv * GS_N_SUMS * cp;
         run->d_dsums = reinterpret_cast<double *>(run->d_max + nv * cp);
         run->d_long_count = reinterpret_cast<unsigned int *>(run->d_dsums + nv * GS_N_DCOLS * cp);
     }
-    if (e == hipSuccess) e = hipMalloc((void **)&run->d_bitmap, sizeof(uint32_t) * (size_t)run->bitmap_words);
-    if (e == hipSuccess) e = hipMalloc((void **)&run->d_unique, sizeof(u64) * nv);
+    if (e == hipSuccess) e = gs_dev_alloc((void **)&run->d_bitmap, sizeof(uint32_t) * (size_t)run->bitmap_words);
+    if (e == hipSuccess) e = gs_dev_alloc((void **)&run->d_unique, sizeof(u64) * nv);
     if (e == hipSuccess && cfg->max_kmer_res_counts > 0)
-        e = hipMalloc((void **)&run->d_hit_counts, sizeof(uint32_t) * (size_t)(db->n_slots() + db->n_rec * GS_REC_SLOTS));
+        e = gs_dev_alloc((void **)&run->d_hit_counts, sizeof(uint32_t) * (size_t)(db->n_slots() + db->n_rec * GS_REC_SLOTS));
     if (e != hipSuccess) {
         run_free(run);
         return hip_fail(e, "run alloc");
@@ -2804,11 +2603,11 @@ static int ensure_long(gs_run *run, int64_t n_reads) {
     const int64_t room = n_reads + (int64_t)run->grid * (GS_BLOCK / 64) * 64;
     if (run->long_cap < room) {  // (three queues: long reads, reads for the three- and the four-sub-round kernel)
         HIP_TRY(hipStreamSynchronize(run->stream));
-        hipFree(run->d_long_list);
+        gs_dev_free(run->d_long_list);
         run->d_long_list = nullptr;
         run->long_cap = 0;
         int64_t cap = std::max<int64_t>(room, 1024);
-        HIP_TRY(hipMalloc((void **)&run->d_long_list, sizeof(uint32_t) * (size_t)cap * 3));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_long_list, sizeof(uint32_t) * (size_t)cap * 3));
         run->long_cap = cap;
     }
     if (!run->d_scratch) {
@@ -2829,8 +2628,8 @@ static int ensure_long(gs_run *run, int64_t n_reads) {
         while (grid > 8 && (size_t)grid * 4 * nv * 2 * sizeof(int32_t) > ((size_t)2 << 30)) grid /= 2;
         run->long_grid = grid;
         const size_t waves = (size_t)grid * (GS_BLOCK / 64);
-        HIP_TRY(hipMalloc((void **)&run->d_scratch, waves * nv * 2 * sizeof(int32_t)));
-        HIP_TRY(hipMalloc((void **)&run->d_serial, waves * sizeof(uint32_t)));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_scratch, waves * nv * 2 * sizeof(int32_t)));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_serial, waves * sizeof(uint32_t)));
         HIP_TRY(hipMemsetAsync(run->d_scratch, 0, waves * nv * 2 * sizeof(int32_t), run->stream));
         HIP_TRY(hipMemsetAsync(run->d_serial, 0, waves * sizeof(uint32_t), run->stream));
         if (const char *e = getenv("GS_TEST_LONG_SERIAL")) {
@@ -2855,7 +2654,7 @@ static int ensure_huge(gs_run *run, GsMatchParams *P) {
         const size_t fixed = 16 + sizeof(uint32_t) * GS_HUGE_SLOTS + sizeof(GsHugeHead) * GS_HUGE_SLOTS * GS_HUGE_COPIES;
         const size_t chunks = sizeof(GsHugeChunk) * (size_t)slots * GS_HUGE_MAX_CHUNKS, row = sizeof(uint32_t) * (size_t)slots * GS_HUGE_COPIES * nv;
         const size_t fold = sizeof(uint32_t) * (size_t)slots * 2 * nv;
-        HIP_TRY(hipMalloc((void **)&run->d_huge, fixed + chunks + 3 * row + fold));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_huge, fixed + chunks + 3 * row + fold));
         HIP_TRY(hipMemsetAsync(run->d_huge, 0, fixed + chunks + row, run->stream));
         HIP_TRY(hipMemsetAsync(run->d_huge + fixed + chunks + row, 0xff, row, run->stream));  // first positions: none
         HIP_TRY(hipMemsetAsync(run->d_huge + fixed + chunks + 3 * row, 0, fold, run->stream));
@@ -2892,7 +2691,7 @@ static int ensure_quot(gs_run *run, int max) {
     const double m = run->cfg.max_read_tax_err, mc = run->cfg.max_read_class_err;
     if (run->quot_max == max && run->quot_tax == m && run->quot_class == mc) return GS_OK;
     if (!run->d_quot) {
-        HIP_TRY(hipMalloc((void **)&run->d_quot, sizeof(GsQuotTable)));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_quot, sizeof(GsQuotTable)));
         HIP_TRY(hipHostMalloc((void **)&run->h_quot, sizeof(GsQuotTable), hipHostMallocDefault));
         HIP_TRY(hipEventCreateWithFlags(&run->quot_copied, hipEventDisableTiming));
     } else
@@ -2965,7 +2764,7 @@ static int launch_batch(gs_run *run, const uint8_t *d_seq, const uint64_t *d_off
         if ((rc = grow(&run->d_stat_recs, &run->stat_recs_cap, (size_t)rec_room, run->stream))) return rc;
         /* (640 = GS_REDUCE_VALUES, the values one pass of gs_stat_reduce_kernel takes) */
         if (run->db->info.n_values > 640 && (rc = grow(&run->d_stat_vi, &run->stat_vi_cap, (size_t)rec_room, run->stream))) return rc;
-        if (!run->d_stat_rec_count) HIP_TRY(hipMalloc((void **)&run->d_stat_rec_count, sizeof(u64)));
+        if (!run->d_stat_rec_count) HIP_TRY(gs_dev_alloc((void **)&run->d_stat_rec_count, sizeof(u64)));
         HIP_TRY(hipMemsetAsync(run->d_stat_rec_count, 0, sizeof(u64), run->stream));
         P.stat_recs = run->d_stat_recs;
         P.stat_rec_count = (unsigned long long *)run->d_stat_rec_count;
@@ -3030,24 +2829,24 @@ extern "C" int gs_match_submit(gs_run *run, const uint8_t *seq, const uint64_t *
     const size_t nbytes = (size_t)(offsets[n_reads] - offsets[0]);
     if (run->seq_cap < nbytes + 1) {
         HIP_TRY(hipStreamSynchronize(run->stream));
-        hipFree(run->d_seq);
+        gs_dev_free(run->d_seq);
         run->d_seq = nullptr;
         run->seq_cap = 0;
-        HIP_TRY(hipMalloc((void **)&run->d_seq, nbytes + 1));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_seq, nbytes + 1));
         run->seq_cap = nbytes + 1;
     }
     if (run->reads_cap < (size_t)n_reads) {
         HIP_TRY(hipStreamSynchronize(run->stream));
-        hipFree(run->d_off);
-        hipFree(run->d_class);
-        hipFree(run->d_flags);
+        gs_dev_free(run->d_off);
+        gs_dev_free(run->d_class);
+        gs_dev_free(run->d_flags);
         run->d_off = nullptr;
         run->d_class = nullptr;
         run->d_flags = nullptr;
         run->reads_cap = 0;
-        HIP_TRY(hipMalloc((void **)&run->d_off, sizeof(uint64_t) * ((size_t)n_reads + 1)));
-        HIP_TRY(hipMalloc((void **)&run->d_class, sizeof(int32_t) * (size_t)n_reads));
-        HIP_TRY(hipMalloc((void **)&run->d_flags, (size_t)n_reads));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_off, sizeof(uint64_t) * ((size_t)n_reads + 1)));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_class, sizeof(int32_t) * (size_t)n_reads));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_flags, (size_t)n_reads));
         run->reads_cap = (size_t)n_reads;
     }
     // offsets are rebased so that the staged slice starts at 0
@@ -3083,24 +2882,24 @@ extern "C" int gs_match_submit_fixed(gs_run *run, const uint8_t *seq, int32_t re
     const size_t nbytes = (size_t)n_reads * (size_t)read_len;
     if (run->seq_cap < nbytes + 1) {
         HIP_TRY(hipStreamSynchronize(run->stream));
-        hipFree(run->d_seq);
+        gs_dev_free(run->d_seq);
         run->d_seq = nullptr;
         run->seq_cap = 0;
-        HIP_TRY(hipMalloc((void **)&run->d_seq, nbytes + 1));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_seq, nbytes + 1));
         run->seq_cap = nbytes + 1;
     }
     if (run->reads_cap < (size_t)n_reads) {
         HIP_TRY(hipStreamSynchronize(run->stream));
-        hipFree(run->d_off);
-        hipFree(run->d_class);
-        hipFree(run->d_flags);
+        gs_dev_free(run->d_off);
+        gs_dev_free(run->d_class);
+        gs_dev_free(run->d_flags);
         run->d_off = nullptr;
         run->d_class = nullptr;
         run->d_flags = nullptr;
         run->reads_cap = 0;
-        HIP_TRY(hipMalloc((void **)&run->d_off, sizeof(uint64_t) * ((size_t)n_reads + 1)));
-        HIP_TRY(hipMalloc((void **)&run->d_class, sizeof(int32_t) * (size_t)n_reads));
-        HIP_TRY(hipMalloc((void **)&run->d_flags, (size_t)n_reads));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_off, sizeof(uint64_t) * ((size_t)n_reads + 1)));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_class, sizeof(int32_t) * (size_t)n_reads));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_flags, (size_t)n_reads));
         run->reads_cap = (size_t)n_reads;
     }
     HIP_TRY(hipMemcpyAsync(run->d_seq, seq, nbytes, hipMemcpyHostToDevice, run->stream));
@@ -3134,24 +2933,24 @@ extern "C" int gs_match_submit_async(gs_run *run, const uint8_t *seq, const uint
         HIP_TRY(hipStreamSynchronize(g.copy_stream));
         HIP_TRY(hipStreamSynchronize(run->stream));
         if (g.seq_cap[b] < nbytes + 1) {
-            hipFree(g.d_seq[b]);
+            gs_dev_free(g.d_seq[b]);
             g.d_seq[b] = nullptr;
             g.seq_cap[b] = 0;
-            HIP_TRY(hipMalloc((void **)&g.d_seq[b], nbytes + nbytes / 4 + 1));
+            HIP_TRY(gs_dev_alloc((void **)&g.d_seq[b], nbytes + nbytes / 4 + 1));
             g.seq_cap[b] = nbytes + nbytes / 4 + 1;
         }
         if (g.reads_cap[b] < (size_t)n_reads) {
-            hipFree(g.d_off[b]);
-            hipFree(g.d_class[b]);
-            hipFree(g.d_flags[b]);
+            gs_dev_free(g.d_off[b]);
+            gs_dev_free(g.d_class[b]);
+            gs_dev_free(g.d_flags[b]);
             g.d_off[b] = nullptr;
             g.d_class[b] = nullptr;
             g.d_flags[b] = nullptr;
             g.reads_cap[b] = 0;
             const size_t cap = (size_t)n_reads + (size_t)n_reads / 4;
-            HIP_TRY(hipMalloc((void **)&g.d_off[b], sizeof(uint64_t) * (cap + 1)));
-            HIP_TRY(hipMalloc((void **)&g.d_class[b], sizeof(int32_t) * cap));
-            HIP_TRY(hipMalloc((void **)&g.d_flags[b], cap));
+            HIP_TRY(gs_dev_alloc((void **)&g.d_off[b], sizeof(uint64_t) * (cap + 1)));
+            HIP_TRY(gs_dev_alloc((void **)&g.d_class[b], sizeof(int32_t) * cap));
+            HIP_TRY(gs_dev_alloc((void **)&g.d_flags[b], cap));
             g.reads_cap[b] = cap;
         }
     }
@@ -3248,16 +3047,16 @@ static int match_submit_text(gs_run *run, const uint8_t *text, int64_t n_bytes, 
     const bool dev_out = mem == GS_MEM_DEVICE;  // (GS_MEM_DEVICE_TEXT: the text is in HBM, class_vi / flags are host arrays)
     if ((class_vi || flags) && !dev_out && run->reads_cap < (size_t)n_reads) {
         HIP_TRY(hipStreamSynchronize(run->stream));
-        hipFree(run->d_off);
-        hipFree(run->d_class);
-        hipFree(run->d_flags);
+        gs_dev_free(run->d_off);
+        gs_dev_free(run->d_class);
+        gs_dev_free(run->d_flags);
         run->d_off = nullptr;
         run->d_class = nullptr;
         run->d_flags = nullptr;
         run->reads_cap = 0;
-        HIP_TRY(hipMalloc((void **)&run->d_off, sizeof(uint64_t) * ((size_t)n_reads + 1)));
-        HIP_TRY(hipMalloc((void **)&run->d_class, sizeof(int32_t) * (size_t)n_reads));
-        HIP_TRY(hipMalloc((void **)&run->d_flags, (size_t)n_reads));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_off, sizeof(uint64_t) * ((size_t)n_reads + 1)));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_class, sizeof(int32_t) * (size_t)n_reads));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_flags, (size_t)n_reads));
         run->reads_cap = (size_t)n_reads;
     }
     int32_t *dc = class_vi ? (dev_out ? class_vi : run->d_class) : nullptr;
@@ -3282,8 +3081,6 @@ extern "C" int gs_match_compact_text(gs_run *run, int with_probs, int slot, cons
     return text_compact(run->text, run->stream, GS_F_RETURNED, 1, 1, slot, with_probs, d_out, n_bytes, n_records);
 }
 
-extern "C" int gs_gather_descriptors_device(hipStream_t stream, const uint8_t *d_text, const uint32_t *d_nl, const int64_t *d_records, int n, uint8_t *d_out, int stride);
-
 // the descriptor lines (whole first lines, '@' included) of a few records of the last four-line chunk: out[i * stride ..], NUL-terminated
 extern "C" int gs_match_text_descriptors(gs_run *run, const int64_t *records, int32_t n, uint8_t *out, int32_t stride) {
     if (!run || n < 0 || (n > 0 && (!records || !out)) || stride < 2) return fail(GS_E_INVALID, "bad argument");
@@ -3295,15 +3092,15 @@ extern "C" int gs_match_text_descriptors(gs_run *run, const int64_t *records, in
     HIP_TRY(hipSetDevice(run->db->device));
     int64_t *d_rec = nullptr;
     uint8_t *d_out = nullptr;
-    hipError_t e = hipMalloc((void **)&d_rec, sizeof(int64_t) * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, (size_t)n * (size_t)stride);
+    hipError_t e = gs_dev_alloc((void **)&d_rec, sizeof(int64_t) * (size_t)n);
+    if (e == hipSuccess) e = gs_dev_alloc((void **)&d_out, (size_t)n * (size_t)stride);
     if (e == hipSuccess) e = hipMemcpyAsync(d_rec, records, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, run->stream);
     int rc = GS_OK;
     if (e == hipSuccess && gs_gather_descriptors_device(run->stream, t.d_text, t.d_nl, d_rec, n, d_out, stride) != GS_OK) rc = fail(GS_E_HIP, gs_deflate_last_error());
     if (e == hipSuccess && !rc) e = hipMemcpyAsync(out, d_out, (size_t)n * (size_t)stride, hipMemcpyDeviceToHost, run->stream);
     if (e == hipSuccess && !rc) e = hipStreamSynchronize(run->stream);
-    hipFree(d_rec);
-    hipFree(d_out);
+    gs_dev_free(d_rec);
+    gs_dev_free(d_out);
     if (e != hipSuccess) return hip_fail(e, "gs_match_text_descriptors");
     return rc;
 }
@@ -3334,9 +3131,6 @@ extern "C" int gs_match_text_clear_error(gs_run *run) {
     HIP_TRY(hipSetDevice(run->db->device));
     return text_reset(run->text, false, run->stream);
 }
-
-extern "C" hipError_t gs_launch_merge_i64(void *dst, const void *src, int64_t n, int op, hipStream_t stream);
-extern "C" hipError_t gs_launch_merge_f64(void *dst, const void *src, int64_t n, hipStream_t stream);
 
 // seen bits of the store -> the run's compact bitmap.  The kernels of a striped store write the bitmap themselves (the
 // store's memory, partly another GPU's, is never written).
@@ -3519,10 +3313,6 @@ extern "C" int gs_match_or_bitmap(gs_run *run, const void *parts, int64_t n_part
 }
 
 // ---- merge of runs that live in one process (gs_merge.hip)
-extern "C" int gs_rccl_merge_leaders(int n_dev, const int *devices, void *const *sums, void *const *maxk, void *const *dsums,
-                                     void *const *bitmap, void *const *gather, int64_t n_sums, int64_t n_max, int64_t n_dsums,
-                                     int64_t n_words, const hipStream_t *streams, const char **msg);
-
 extern "C" int gs_match_merge(gs_run *const *runs, int n_runs) try {
     if (!runs || n_runs < 1) return fail(GS_E_INVALID, "bad argument");
     for (int i = 0; i < n_runs; i++) {
@@ -3607,7 +3397,7 @@ extern "C" int gs_match_merge(gs_run *const *runs, int n_runs) try {
             st[(size_t)d] = L->stream;
             if (uniq) {
                 hipSetDevice(L->db->device);
-                if (hipMalloc(&pg[(size_t)d], sizeof(uint32_t) * (size_t)words * (size_t)n_dev) != hipSuccess)
+                if (gs_dev_alloc(&pg[(size_t)d], sizeof(uint32_t) * (size_t)words * (size_t)n_dev) != hipSuccess)
                     rc = fail(GS_E_NOMEM, "merge scratch");
             }
         }
@@ -3628,7 +3418,7 @@ extern "C" int gs_match_merge(gs_run *const *runs, int n_runs) try {
         for (int d = 0; d < n_dev; d++)
             if (pg[(size_t)d]) {
                 hipSetDevice(devices[(size_t)d]);
-                hipFree(pg[(size_t)d]);
+                gs_dev_free(pg[(size_t)d]);
             }
         if (rc != GS_OK) return rc;
     }
@@ -3660,16 +3450,6 @@ extern "C" int gs_match_merge(gs_run *const *runs, int n_runs) try {
 // ---------------------------------------------------------------------------------------------------
 // DB construction on the device (gs_build.hip; include/gsgpu.h "gs_dbbuild")
 // ---------------------------------------------------------------------------------------------------
-extern "C" hipError_t gs_launch_build_kmers(const uint8_t *seq, const u64 *off, int64_t n_regions, int64_t total, int k, int lower, int step,
-                                            int max_dust, uint32_t first_region, int update, u64 range_lo, u64 range_hi, u64 *keys, uint32_t *vals,
-                                            u64 *n_out, hipStream_t stream);
-extern "C" hipError_t gs_build_sort(u64 *keys, u64 *keys_alt, uint32_t *vals, uint32_t *vals_alt, int64_t n, int key_bits, u64 **keys_out,
-                                    uint32_t **vals_out, hipStream_t stream);
-extern "C" hipError_t gs_build_reduce(const u64 *keys, const uint32_t *vals, int64_t n, const int32_t *node_of_region, const int32_t *parent,
-                                      const int32_t *depth, uint32_t *flag, int32_t *value, u64 *pos, int64_t *n_out, hipStream_t stream);
-extern "C" hipError_t gs_launch_build_scatter(const u64 *keys, const int32_t *value, const uint32_t *flag, const u64 *pos, int64_t n,
-                                              int64_t *out_keys, int32_t *out_vals, hipStream_t stream);
-
 // depth of every value index by parent walks (-1: no node); exactly one root: TaxTree.getLowestCommonAncestor answers null for
 // nodes of different trees and the update then keeps the old value (DBGoal.java:243), which depends on the order of the regions
 static int build_tree_depths(int32_t n_values, const int32_t *parent_vi, std::vector<int32_t> &depth, const char *who) {
@@ -3740,15 +3520,15 @@ static int region_stage_open(RegionStage *s, int device, int k, int32_t n_values
     s->n_values = n_values;
     s->parent.assign(parent_vi, parent_vi + n_values);
     hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
-    if (e == hipSuccess && depth) e = hipMalloc((void **)&s->d_tree, sizeof(int32_t) * 2 * (size_t)n_values);
+    if (e == hipSuccess && depth) e = gs_dev_alloc((void **)&s->d_tree, sizeof(int32_t) * 2 * (size_t)n_values);
     if (e == hipSuccess && depth) e = hipMemcpy(s->d_tree, parent_vi, sizeof(int32_t) * (size_t)n_values, hipMemcpyHostToDevice);
     if (e == hipSuccess && depth) e = hipMemcpy(s->d_tree + n_values, depth, sizeof(int32_t) * (size_t)n_values, hipMemcpyHostToDevice);
     return e == hipSuccess ? GS_OK : hip_fail(e, std::string(who) + "_begin");
 }
 
 static void region_stage_drop_staging(RegionStage *s) {
-    hipFree(s->d_seq);
-    hipFree(s->d_off);
+    gs_dev_free(s->d_seq);
+    gs_dev_free(s->d_off);
     s->d_seq = nullptr;
     s->d_off = nullptr;
     s->seq_cap = s->off_cap = 0;
@@ -3758,8 +3538,8 @@ static void region_stage_drop_staging(RegionStage *s) {
 static void region_stage_free(RegionStage *s, std::initializer_list<void *> more) {
     hipSetDevice(s->device);
     if (s->stream) hipStreamSynchronize(s->stream);
-    for (void *p : more) hipFree(p);
-    hipFree(s->d_tree);
+    for (void *p : more) gs_dev_free(p);
+    gs_dev_free(s->d_tree);
     region_stage_drop_staging(s);
     if (s->stream) hipStreamDestroy(s->stream);
 }
@@ -3820,14 +3600,14 @@ struct PairBuffer {  // the (k-mer, region | update bit) pairs handed in so far
 };
 
 static int pairs_open(PairBuffer *p, const char *who) {
-    hipError_t e = hipMalloc((void **)&p->d_count, sizeof(u64));
+    hipError_t e = gs_dev_alloc((void **)&p->d_count, sizeof(u64));
     if (e == hipSuccess) e = hipMemset(p->d_count, 0, sizeof(u64));
     return e == hipSuccess ? GS_OK : hip_fail(e, std::string(who) + "_begin");
 }
 
 static void pairs_drop(PairBuffer *p) {
-    hipFree(p->keys);
-    hipFree(p->vals);
+    gs_dev_free(p->keys);
+    gs_dev_free(p->vals);
     p->keys = nullptr;
     p->vals = nullptr;
     p->cap = p->n = 0;
@@ -3839,18 +3619,18 @@ static int pairs_reserve(PairBuffer *p, size_t extra, hipStream_t stream, const 
     const size_t want = std::max<size_t>(std::max(p->cap * 2, p->n + extra), 1 << 20);
     u64 *nk = nullptr;
     uint32_t *nv = nullptr;
-    hipError_t e = hipMalloc((void **)&nk, want * sizeof(u64));
-    if (e == hipSuccess) e = hipMalloc((void **)&nv, want * sizeof(uint32_t));
+    hipError_t e = gs_dev_alloc((void **)&nk, want * sizeof(u64));
+    if (e == hipSuccess) e = gs_dev_alloc((void **)&nv, want * sizeof(uint32_t));
     if (e == hipSuccess && p->n) e = hipMemcpyAsync(nk, p->keys, p->n * sizeof(u64), hipMemcpyDeviceToDevice, stream);
     if (e == hipSuccess && p->n) e = hipMemcpyAsync(nv, p->vals, p->n * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) {
-        hipFree(nk);
-        hipFree(nv);
+        gs_dev_free(nk);
+        gs_dev_free(nv);
         return hip_fail(e, who);
     }
-    hipFree(p->keys);
-    hipFree(p->vals);
+    gs_dev_free(p->keys);
+    gs_dev_free(p->vals);
     p->keys = nk;
     p->vals = nv;
     p->cap = want;
@@ -3983,30 +3763,30 @@ extern "C" int gs_dbbuild_finish(gs_dbbuild *b, int64_t *n_kmers) try {
         u64 *ks = nullptr;
         uint32_t *vs = nullptr;
         const u64 n_valid = (u64)n;
-        bool ok = check(hipMalloc((void **)&keys_alt, (size_t)n * sizeof(u64)), "sort buffers") &&
-                  check(hipMalloc((void **)&vals_alt, (size_t)n * sizeof(uint32_t)), "sort buffers") &&
+        bool ok = check(gs_dev_alloc((void **)&keys_alt, (size_t)n * sizeof(u64)), "sort buffers") &&
+                  check(gs_dev_alloc((void **)&vals_alt, (size_t)n * sizeof(uint32_t)), "sort buffers") &&
                   check(gs_build_sort(b->pairs.keys, keys_alt, b->pairs.vals, vals_alt, n, 2 * b->k, &ks, &vs, b->stream), "sort");
         b->n_kmers_seen = (int64_t)n_valid;
         if (ok && n_valid > 0) {
             const size_t nr = std::max<size_t>(b->node_of_region.size(), 1);
-            ok = check(hipMalloc((void **)&d_nor, nr * sizeof(int32_t)), "regions") &&
+            ok = check(gs_dev_alloc((void **)&d_nor, nr * sizeof(int32_t)), "regions") &&
                  check(hipMemcpy(d_nor, b->node_of_region.data(), b->node_of_region.size() * sizeof(int32_t), hipMemcpyHostToDevice), "regions") &&
-                 check(hipMalloc((void **)&flag, (size_t)n_valid * sizeof(uint32_t)), "scratch") &&
-                 check(hipMalloc((void **)&value, (size_t)n_valid * sizeof(int32_t)), "scratch") &&
-                 check(hipMalloc((void **)&pos, (size_t)n_valid * sizeof(u64)), "scratch") &&
+                 check(gs_dev_alloc((void **)&flag, (size_t)n_valid * sizeof(uint32_t)), "scratch") &&
+                 check(gs_dev_alloc((void **)&value, (size_t)n_valid * sizeof(int32_t)), "scratch") &&
+                 check(gs_dev_alloc((void **)&pos, (size_t)n_valid * sizeof(u64)), "scratch") &&
                  check(gs_build_reduce(ks, vs, (int64_t)n_valid, d_nor, b->d_tree, b->d_tree + b->n_values, flag, value, pos, &b->n_out, b->stream), "reduce");
             if (ok && b->n_out > 0)
-                ok = check(hipMalloc((void **)&b->d_out_keys, (size_t)b->n_out * sizeof(int64_t)), "result") &&
-                     check(hipMalloc((void **)&b->d_out_vals, (size_t)b->n_out * sizeof(int32_t)), "result") &&
+                ok = check(gs_dev_alloc((void **)&b->d_out_keys, (size_t)b->n_out * sizeof(int64_t)), "result") &&
+                     check(gs_dev_alloc((void **)&b->d_out_vals, (size_t)b->n_out * sizeof(int32_t)), "result") &&
                      check(gs_launch_build_scatter(ks, value, flag, pos, (int64_t)n_valid, b->d_out_keys, b->d_out_vals, b->stream), "scatter") &&
                      check(hipStreamSynchronize(b->stream), "scatter");
         }
     }
-    for (void *p : {(void *)keys_alt, (void *)vals_alt, (void *)pos, (void *)flag, (void *)value, (void *)d_nor}) hipFree(p);
+    for (void *p : {(void *)keys_alt, (void *)vals_alt, (void *)pos, (void *)flag, (void *)value, (void *)d_nor}) gs_dev_free(p);
     pairs_drop(&b->pairs);
     if (check.rc != GS_OK) {  // nothing half-built may be handed out later: no results, no second finish
-        hipFree(b->d_out_keys);
-        hipFree(b->d_out_vals);
+        gs_dev_free(b->d_out_keys);
+        gs_dev_free(b->d_out_vals);
         b->d_out_keys = nullptr;
         b->d_out_vals = nullptr;
         b->n_out = 0;
@@ -4041,23 +3821,6 @@ extern "C" int gs_dbbuild_destroy(gs_dbbuild *b) {
 // ---------------------------------------------------------------------------------------------------
 // Store quality against its source genomes (gs_quality.hip; include/gsgpu.h "gs_dbquality")
 // ---------------------------------------------------------------------------------------------------
-struct GsQualityParams {  // (gs_quality.hip)
-    const u64 *keys;
-    const uint32_t *leaf;
-    int64_t n;
-    const u64 *skeys;
-    const uint32_t *svals;
-    int64_t m;
-    const int32_t *tin, *tout;
-    int32_t n_values;
-    u64 *counts;
-    u64 *stats;
-};
-extern "C" hipError_t gs_launch_quality_tag(uint32_t *vals, int64_t n, const uint32_t *leaf_of_region, int64_t n_regions, hipStream_t stream);
-extern "C" hipError_t gs_quality_sort_leaf(uint32_t *leaf, uint32_t *leaf_alt, u64 *keys, u64 *keys_alt, int64_t n, int bits, uint32_t **leaf_out,
-                                           u64 **keys_out, hipStream_t stream);
-extern "C" hipError_t gs_launch_quality_join(const GsQualityParams *P, int n_cu, hipStream_t stream);
-
 struct gs_dbquality : RegionStage {  // (parent: the store's tree; no d_tree, the join reads the store's own)
     gs_db *db = nullptr;
     PairBuffer pairs;  // the (k-mer, leaf) pairs of this pass
@@ -4165,7 +3928,7 @@ extern "C" int gs_dbquality_finish(gs_dbquality *q, int64_t *counts, uint8_t *pr
     std::vector<u64> h_cnt(2 * (size_t)nv + 2, 0);
     HipSteps check{"gs_dbquality_finish"};
     region_stage_drop_staging(q);  // the staging buffers make room for the sort
-    hipFree(q->d_leaf);
+    gs_dev_free(q->d_leaf);
     q->d_leaf = nullptr;
     q->leaf_cap = 0;
     q->stats.n_pairs = n;
@@ -4193,8 +3956,8 @@ extern "C" int gs_dbquality_finish(gs_dbquality *q, int64_t *counts, uint8_t *pr
         u64 *ks = q->pairs.keys;
         uint32_t *vs = q->pairs.vals;
         auto t0 = clk::now();
-        bool ok = check(hipMalloc((void **)&keys_alt, (size_t)n * sizeof(u64)), "sort buffers") &&
-                  check(hipMalloc((void **)&vals_alt, (size_t)n * sizeof(uint32_t)), "sort buffers");
+        bool ok = check(gs_dev_alloc((void **)&keys_alt, (size_t)n * sizeof(u64)), "sort buffers") &&
+                  check(gs_dev_alloc((void **)&vals_alt, (size_t)n * sizeof(uint32_t)), "sort buffers");
         if (ok && q->one_leaf == -2) {  // several leaves: the leaf bits first, the stable k-mer sort keeps their order
             int bits = 1;
             while (((int64_t)1 << bits) <= (int64_t)nv) bits++;
@@ -4218,7 +3981,7 @@ extern "C" int gs_dbquality_finish(gs_dbquality *q, int64_t *counts, uint8_t *pr
             P.tin = q->db->dev.tin;
             P.tout = q->db->dev.tout;
             P.n_values = nv;
-            ok = check(hipMalloc((void **)&d_cnt, h_cnt.size() * sizeof(u64)), "counts") &&
+            ok = check(gs_dev_alloc((void **)&d_cnt, h_cnt.size() * sizeof(u64)), "counts") &&
                  check(hipMemsetAsync(d_cnt, 0, h_cnt.size() * sizeof(u64), q->stream), "counts");
             P.counts = d_cnt;
             P.stats = d_cnt + 2 * (size_t)nv;
@@ -4228,9 +3991,9 @@ extern "C" int gs_dbquality_finish(gs_dbquality *q, int64_t *counts, uint8_t *pr
         }
         q->stats.ms_join = ms_since(t0);
     }
-    hipFree(keys_alt);
-    hipFree(vals_alt);
-    hipFree(d_cnt);
+    gs_dev_free(keys_alt);
+    gs_dev_free(vals_alt);
+    gs_dev_free(d_cnt);
     pairs_drop(&q->pairs);
     HIP_TRY(hipMemset(q->pairs.d_count, 0, sizeof(u64)));
     q->finished = true;  // (also after a failure: the pairs are gone)
@@ -4266,25 +4029,6 @@ extern "C" int gs_dbquality_destroy(gs_dbquality *q) {
 // ---------------------------------------------------------------------------------------------------
 // A finished store updated in batches (gs_update.hip; include/gsgpu.h "gs_dbupdate")
 // ---------------------------------------------------------------------------------------------------
-struct GsUpdateParams {  // (gs_update.hip)
-    const u64 *skeys;
-    int32_t *svals;
-    int64_t m;
-    const void *dir;
-    int32_t dir_bits, wide, k;
-    const int32_t *parent, *depth;
-    const u64 *keys;
-    const uint32_t *region;
-    const u64 *n_pairs;
-    const int32_t *node_of_region;
-    u64 *stats;
-};
-extern "C" hipError_t gs_launch_update_check(const u64 *keys, const int32_t *vals, int64_t m, int k, int32_t n_values, uint32_t *flag, int n_cu,
-                                             hipStream_t stream);
-extern "C" hipError_t gs_launch_update_dir(const u64 *keys, int64_t m, int k, int dir_bits, int wide, void *dir, int n_cu, hipStream_t stream);
-extern "C" hipError_t gs_launch_update_lookup(const GsUpdateParams *P, int64_t max_pairs, int n_cu, hipStream_t stream);
-extern "C" hipError_t gs_launch_update_moved(const int32_t *vals, const int32_t *vals0, int64_t m, u64 *count, int n_cu, hipStream_t stream);
-
 #define GS_UPD_DEFAULT_SLICE ((int64_t)1 << 25)  // bases per slice: 13 bytes of working memory each (436 MB)
 
 struct gs_dbupdate : RegionStage {
@@ -4331,7 +4075,7 @@ static int dbupdate_open(gs_dbupdate **out, int device, int k, int32_t n_values,
     if (!rc) {
         hipError_t e = hipSuccess;
         for (int i = 0; i < 3 && e == hipSuccess; i++) e = hipEventCreate(&u->ev[i]);
-        if (e == hipSuccess) e = hipMalloc((void **)&u->d_cnt, 5 * sizeof(u64));
+        if (e == hipSuccess) e = gs_dev_alloc((void **)&u->d_cnt, 5 * sizeof(u64));
         if (e == hipSuccess) e = hipMemsetAsync(u->d_cnt, 0, 5 * sizeof(u64), u->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(u->stream);
         if (e != hipSuccess) rc = hip_fail(e, "gs_dbupdate_begin");
@@ -4362,8 +4106,8 @@ static int dbupdate_adopt(gs_dbupdate *u, bool check) {
     u->dir_bits = bits;
     u->wide = n >= ((int64_t)1 << 32);
     const size_t dir_bytes = (((size_t)1 << bits) + 1) * (u->wide ? 8 : 4);
-    HIP_TRY(hipMalloc((void **)&u->d_vals0, std::max<size_t>((size_t)n, 1) * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&u->d_dir, dir_bytes));
+    HIP_TRY(gs_dev_alloc((void **)&u->d_vals0, std::max<size_t>((size_t)n, 1) * sizeof(int32_t)));
+    HIP_TRY(gs_dev_alloc(&u->d_dir, dir_bytes));
     if (n > 0) HIP_TRY(hipMemcpyAsync(u->d_vals0, u->d_vals, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, u->stream));
     HIP_TRY(gs_launch_update_dir(u->d_keys, n, u->k, bits, u->wide ? 1 : 0, u->d_dir, u->n_cu, u->stream));
     HIP_TRY(hipStreamSynchronize(u->stream));
@@ -4377,8 +4121,8 @@ static int dbupdate_copy_in(gs_dbupdate *u, const void *kmers, const void *value
                             const char *who) {
     u->n = n_kmers;
     const size_t m = std::max<size_t>((size_t)n_kmers, 1);
-    hipError_t e = hipMalloc((void **)&u->d_keys, m * sizeof(u64));
-    if (e == hipSuccess) e = hipMalloc((void **)&u->d_vals, m * sizeof(int32_t));
+    hipError_t e = gs_dev_alloc((void **)&u->d_keys, m * sizeof(u64));
+    if (e == hipSuccess) e = gs_dev_alloc((void **)&u->d_vals, m * sizeof(int32_t));
     // (on the handle's stream: a device-to-device hipMemcpy need not be complete when it returns, and this stream does not wait for the null stream)
     if (e == hipSuccess && n_kmers > 0) e = hipMemcpyAsync(u->d_keys, kmers, (size_t)n_kmers * sizeof(u64), kind, u->stream);
     if (e == hipSuccess && n_kmers > 0) e = hipMemcpyAsync(u->d_vals, value_idx, (size_t)n_kmers * sizeof(int32_t), kind, u->stream);
@@ -4485,10 +4229,10 @@ extern "C" int gs_dbupdate_set_slice(gs_dbupdate *u, int64_t max_bases) {
 template <typename T>
 static hipError_t dbupdate_room(T **p, size_t *cap, size_t need) {
     if (*cap >= need) return hipSuccess;
-    hipFree(*p);
+    gs_dev_free(*p);
     *p = nullptr;
     *cap = 0;
-    const hipError_t e = hipMalloc((void **)p, need * sizeof(T));
+    const hipError_t e = gs_dev_alloc((void **)p, need * sizeof(T));
     if (e == hipSuccess) *cap = need;
     return e;
 }
@@ -4620,7 +4364,7 @@ extern "C" int gs_dbupdate_finish(gs_dbupdate *u, int64_t *n_moved) try {
     HIP_TRY(hipStreamSynchronize(u->stream));
     // the slice's working memory goes (gs_dbupdate_to_db needs the room); batch_bytes_peak keeps what it was
     region_stage_drop_staging(u);
-    for (void *p : {(void *)u->d_node, (void *)u->d_pkeys, (void *)u->d_pvals}) hipFree(p);
+    for (void *p : {(void *)u->d_node, (void *)u->d_pkeys, (void *)u->d_pvals}) gs_dev_free(p);
     u->d_node = nullptr;
     u->d_pkeys = nullptr;
     u->d_pvals = nullptr;
@@ -4690,9 +4434,6 @@ extern "C" int gs_match_encode(gs_run *run, const uint8_t *seq, const uint64_t *
     return GS_OK;
 }
 
-extern "C" hipError_t gs_launch_encode_route(const GsEncodeParams *P, const GsRouteParams *R, int grid, hipStream_t stream);
-extern "C" hipError_t gs_launch_unroute_region(const uint32_t *idx, const int32_t *back, int64_t n, int32_t *nodes, hipStream_t stream);
-
 static int route_grid(const gs_run *run, int64_t n_reads) {  // workgroups of GS_BLOCK / 64 waves (one read per wave at a time)
     return (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)run->db->n_cu * 8, (n_reads + 3) / 4));
 }
@@ -4722,7 +4463,7 @@ extern "C" int gs_match_encode_route(gs_run *run, const uint8_t *seq, const uint
         HIP_TRY(hipStreamSynchronize(run->stream));
         if (n_pos >= 0xffffffffULL) return fail(GS_E_INVALID, "more than 2^32-2 k-mer positions in one batch: split the batch");
     }
-    if (!run->d_route_cursors) HIP_TRY(hipMalloc((void **)&run->d_route_cursors, sizeof(u64) * 65));
+    if (!run->d_route_cursors) HIP_TRY(gs_dev_alloc((void **)&run->d_route_cursors, sizeof(u64) * 65));
     HIP_TRY(hipMemsetAsync(run->d_route_cursors, 0, sizeof(u64) * 65, run->stream));
     GsEncodeParams P{};
     P.k = run->db->info.k;
@@ -4778,12 +4519,6 @@ extern "C" int gs_match_reduce(gs_run *run, const uint8_t *seq, const uint64_t *
     return launch_batch(run, seq, offsets, n_reads, first_read_no, class_vi, flags, nodes, pos_off);
 }
 
-extern "C" hipError_t gs_launch_route_count(const u64 *keys, int64_t n, int n_parts, u64 *counts, hipStream_t stream);
-extern "C" hipError_t gs_launch_route_scatter(const u64 *keys, int64_t n, int n_parts, u64 *cursors, u64 *send_keys,
-                                               uint32_t *idx, int32_t *nodes, hipStream_t stream);
-extern "C" hipError_t gs_launch_unroute(const u64 *keys, const uint32_t *idx, const int32_t *back, int64_t n_routed, int32_t *nodes,
-                                         int64_t n_keys, hipStream_t stream);
-
 // groups the valid keys by owner rank (counting sort on the device); counts[n_parts] is a HOST array
 extern "C" int gs_route_keys(gs_run *run, const uint64_t *keys, int64_t n_keys, int n_parts, uint64_t *send_keys,
                              uint32_t *idx, int64_t *counts, int32_t *nodes) {
@@ -4794,7 +4529,7 @@ extern "C" int gs_route_keys(gs_run *run, const uint64_t *keys, int64_t n_keys, 
     for (int i = 0; i < n_parts; i++) counts[i] = 0;
     if (n_keys <= 0) return GS_OK;
     u64 *d_counts = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_counts, sizeof(u64) * 64));
+    HIP_TRY(gs_dev_alloc((void **)&d_counts, sizeof(u64) * 64));
     hipError_t e = hipMemsetAsync(d_counts, 0, sizeof(u64) * 64, run->stream);
     if (e == hipSuccess) e = gs_launch_route_count((const u64 *)keys, n_keys, n_parts, d_counts, run->stream);
     u64 h[64];
@@ -4812,7 +4547,7 @@ extern "C" int gs_route_keys(gs_run *run, const uint64_t *keys, int64_t n_keys, 
     if (e == hipSuccess)
         e = gs_launch_route_scatter((const u64 *)keys, n_keys, n_parts, d_counts, (u64 *)send_keys, idx, nodes, run->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(run->stream);
-    hipFree(d_counts);
+    gs_dev_free(d_counts);
     if (e != hipSuccess) return fail(GS_E_HIP, std::string("gs_route_keys: ") + hipGetErrorString(e));
     return GS_OK;
 }
@@ -4840,23 +4575,23 @@ static int stage_batch(gs_run *run, const uint8_t *seq, const uint64_t *offsets,
     const size_t nbytes = (size_t)(offsets[n_reads] - offsets[0]);
     HIP_TRY(hipStreamSynchronize(run->stream));
     if (run->seq_cap < nbytes + 1) {
-        hipFree(run->d_seq);
+        gs_dev_free(run->d_seq);
         run->d_seq = nullptr;
         run->seq_cap = 0;
-        HIP_TRY(hipMalloc((void **)&run->d_seq, nbytes + 1));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_seq, nbytes + 1));
         run->seq_cap = nbytes + 1;
     }
     if (run->reads_cap < (size_t)n_reads) {
-        hipFree(run->d_off);
-        hipFree(run->d_class);
-        hipFree(run->d_flags);
+        gs_dev_free(run->d_off);
+        gs_dev_free(run->d_class);
+        gs_dev_free(run->d_flags);
         run->d_off = nullptr;
         run->d_class = nullptr;
         run->d_flags = nullptr;
         run->reads_cap = 0;
-        HIP_TRY(hipMalloc((void **)&run->d_off, sizeof(uint64_t) * ((size_t)n_reads + 1)));
-        HIP_TRY(hipMalloc((void **)&run->d_class, sizeof(int32_t) * (size_t)n_reads));
-        HIP_TRY(hipMalloc((void **)&run->d_flags, (size_t)n_reads));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_off, sizeof(uint64_t) * ((size_t)n_reads + 1)));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_class, sizeof(int32_t) * (size_t)n_reads));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_flags, (size_t)n_reads));
         run->reads_cap = (size_t)n_reads;
     }
     std::vector<uint64_t> rel((size_t)n_reads + 1);
@@ -4869,15 +4604,15 @@ static int stage_batch(gs_run *run, const uint8_t *seq, const uint64_t *offsets,
 }
 
 static int segments_core(gs_run *run, const uint8_t *d_seq, const uint64_t *d_off, int64_t n_reads, int off_stride, uint64_t *seg_off) {
-    hipFree(run->d_seg_count);
-    hipFree(run->d_seg_off);
-    hipFree(run->d_seg_code);
-    hipFree(run->d_seg_start);
+    gs_dev_free(run->d_seg_count);
+    gs_dev_free(run->d_seg_off);
+    gs_dev_free(run->d_seg_code);
+    gs_dev_free(run->d_seg_start);
     run->d_seg_count = nullptr;
     run->d_seg_off = nullptr;
     run->d_seg_code = run->d_seg_start = nullptr;
-    HIP_TRY(hipMalloc((void **)&run->d_seg_count, sizeof(uint32_t) * (size_t)n_reads));
-    HIP_TRY(hipMalloc((void **)&run->d_seg_off, sizeof(u64) * ((size_t)n_reads + 1)));
+    HIP_TRY(gs_dev_alloc((void **)&run->d_seg_count, sizeof(uint32_t) * (size_t)n_reads));
+    HIP_TRY(gs_dev_alloc((void **)&run->d_seg_off, sizeof(u64) * ((size_t)n_reads + 1)));
     GsSegParams P{};
     P.db = run->db->dev;
     P.seq = d_seq;
@@ -4904,8 +4639,8 @@ static int segments_core(gs_run *run, const uint8_t *d_seq, const uint64_t *d_of
         GsSegPiece *pieces = nullptr;
         GsSegPieceOut *out = nullptr;
         ~Dev() {
-            hipFree(pieces);
-            hipFree(out);
+            gs_dev_free(pieces);
+            gs_dev_free(out);
         }
     } dv;
     for (int64_t r = 0; r < n_reads; r++)
@@ -4927,8 +4662,8 @@ static int segments_core(gs_run *run, const uint8_t *d_seq, const uint64_t *d_of
             }
         }
         first_piece.push_back(pieces.size());
-        HIP_TRY(hipMalloc((void **)&dv.pieces, sizeof(GsSegPiece) * pieces.size()));
-        HIP_TRY(hipMalloc((void **)&dv.out, sizeof(GsSegPieceOut) * pieces.size()));
+        HIP_TRY(gs_dev_alloc((void **)&dv.pieces, sizeof(GsSegPiece) * pieces.size()));
+        HIP_TRY(gs_dev_alloc((void **)&dv.out, sizeof(GsSegPieceOut) * pieces.size()));
         HIP_TRY(hipMemcpyAsync(dv.pieces, pieces.data(), sizeof(GsSegPiece) * pieces.size(), hipMemcpyHostToDevice, run->stream));
         GsSegParams Q = P;
         Q.pieces = dv.pieces;
@@ -4957,8 +4692,8 @@ static int segments_core(gs_run *run, const uint8_t *d_seq, const uint64_t *d_of
     for (int64_t i = 0; i < n_reads; i++) seg_off[i + 1] = seg_off[i] + counts[(size_t)i];
     run->seg_total = (int64_t)seg_off[n_reads];
     if (run->seg_total > 0) {
-        HIP_TRY(hipMalloc((void **)&run->d_seg_code, sizeof(int32_t) * (size_t)run->seg_total));
-        HIP_TRY(hipMalloc((void **)&run->d_seg_start, sizeof(int32_t) * (size_t)run->seg_total));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_seg_code, sizeof(int32_t) * (size_t)run->seg_total));
+        HIP_TRY(gs_dev_alloc((void **)&run->d_seg_start, sizeof(int32_t) * (size_t)run->seg_total));
         HIP_TRY(hipMemcpyAsync(run->d_seg_off, seg_off, sizeof(u64) * ((size_t)n_reads + 1), hipMemcpyHostToDevice, run->stream));
         P.seg_off = run->d_seg_off;
         P.seg_code = run->d_seg_code;
@@ -5011,22 +4746,17 @@ extern "C" int gs_match_segments_text(gs_run *run, uint64_t *seg_off) {
 // newline offsets of the most recent text chunk (the record geometry for per-read writers); synchronises
 extern "C" int gs_match_text_read_bounds(gs_run *run, uint64_t *bounds) {
     if (!run || !bounds) return fail(GS_E_INVALID, "NULL argument");
-    if (run->text.tickets == 0) return fail(GS_E_STATE, "no text chunk has been submitted");
-    if (!run->text.last_fasta) return fail(GS_E_STATE, "the last chunk was four-line FASTQ: its reads lie in the text (gs_match_text_newlines)");
     HIP_TRY(hipSetDevice(run->db->device));
-    HIP_TRY(hipMemcpyAsync(bounds, run->text.d_off2, sizeof(uint64_t) * ((size_t)run->text.last_reads + 1), hipMemcpyDeviceToHost, run->stream));
-    HIP_TRY(hipStreamSynchronize(run->stream));
-    return collect_events(run);
+    const int rc = text_read_bounds(run->text, run->stream, bounds,
+                                    "the last chunk was four-line FASTQ: its reads lie in the text (gs_match_text_newlines)");
+    return rc ? rc : collect_events(run);
 }
 
 extern "C" int gs_match_text_line_classes(gs_run *run, uint8_t *classes) {
     if (!run || !classes) return fail(GS_E_INVALID, "NULL argument");
-    if (run->text.tickets == 0 || !run->text.d_ml_class) return fail(GS_E_STATE, "no general FASTQ chunk has been submitted");
     HIP_TRY(hipSetDevice(run->db->device));
-    if (run->text.last_lines > 0)
-        HIP_TRY(hipMemcpyAsync(classes, run->text.d_ml_class, (size_t)run->text.last_lines, hipMemcpyDeviceToHost, run->stream));
-    HIP_TRY(hipStreamSynchronize(run->stream));
-    return collect_events(run);
+    const int rc = text_line_classes(run->text, run->stream, classes);
+    return rc ? rc : collect_events(run);
 }
 
 extern "C" int gs_match_text_newlines(gs_run *run, uint32_t *newlines) {
@@ -5191,8 +4921,8 @@ extern "C" int gs_bloom_create(gs_bloom **out, int device, int kind, int64_t bit
     hipError_t e = hipGetDeviceProperties(&prop, device);
     if (e == hipSuccess) b->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_words, sizeof(u64) * (size_t)n_words);
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_factors, sizeof(int64_t) * (size_t)n_hashes);
+    if (e == hipSuccess) e = gs_dev_alloc((void **)&b->d_words, sizeof(u64) * (size_t)n_words);
+    if (e == hipSuccess) e = gs_dev_alloc((void **)&b->d_factors, sizeof(int64_t) * (size_t)n_hashes);
     if (e == hipSuccess) e = hipMemcpy(b->d_words, words, sizeof(u64) * (size_t)n_words, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(b->d_factors, hash_factors, sizeof(int64_t) * (size_t)n_hashes, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
@@ -5206,9 +4936,6 @@ extern "C" int gs_bloom_create(gs_bloom **out, int device, int kind, int64_t bit
 } catch (const std::exception &e) {  // (nothing may leave through the C ABI)
     return fail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
 }
-
-extern "C" hipError_t gs_launch_bloom_xor_put(const int64_t *keys, int64_t n, int64_t bits, const int64_t *factors, int n_hashes, int murmur,
-                                              u64 *words, hipStream_t stream);
 
 // java.util.Random (the hash factors of the reference's filters are its first nextLong() values for seed 42,
 // C/bloom/AbstractKMerBloomFilter.java:78,105-109)
@@ -5257,19 +4984,19 @@ extern "C" int gs_bloom_build(gs_bloom **out, int device, int kind, const int64_
     hipError_t e = hipGetDeviceProperties(&prop, device);
     if (e == hipSuccess) b->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_words, sizeof(u64) * (size_t)b->n_words);
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_factors, sizeof(int64_t) * (size_t)nh);
+    if (e == hipSuccess) e = gs_dev_alloc((void **)&b->d_words, sizeof(u64) * (size_t)b->n_words);
+    if (e == hipSuccess) e = gs_dev_alloc((void **)&b->d_factors, sizeof(int64_t) * (size_t)nh);
     if (e == hipSuccess) e = hipMemsetAsync(b->d_words, 0, sizeof(u64) * (size_t)b->n_words, b->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(b->d_factors, factors.data(), sizeof(int64_t) * (size_t)nh, hipMemcpyHostToDevice, b->stream);
     const int64_t *keys = kmers;
     if (e == hipSuccess && mem == GS_MEM_HOST && n_kmers > 0) {
-        e = hipMalloc((void **)&d_keys, sizeof(int64_t) * (size_t)n_kmers);
+        e = gs_dev_alloc((void **)&d_keys, sizeof(int64_t) * (size_t)n_kmers);
         if (e == hipSuccess) e = hipMemcpyAsync(d_keys, kmers, sizeof(int64_t) * (size_t)n_kmers, hipMemcpyHostToDevice, b->stream);
         keys = d_keys;
     }
     if (e == hipSuccess) e = gs_launch_bloom_xor_put(keys, n_kmers, bits, b->d_factors, (int)nh, kind == GS_BLOOM_MURMUR, b->d_words, b->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
-    hipFree(d_keys);
+    gs_dev_free(d_keys);
     if (e != hipSuccess) {
         gs_bloom_destroy(b);
         return hip_fail(e, "gs_bloom_build");
@@ -5301,11 +5028,11 @@ extern "C" int gs_bloom_destroy(gs_bloom *b) {
         hipEventDestroy(p.first);
         hipEventDestroy(p.second);
     }
-    hipFree(b->d_words);
-    hipFree(b->d_factors);
-    hipFree(b->d_seq);
-    hipFree(b->d_off);
-    hipFree(b->d_accept);
+    gs_dev_free(b->d_words);
+    gs_dev_free(b->d_factors);
+    gs_dev_free(b->d_seq);
+    gs_dev_free(b->d_off);
+    gs_dev_free(b->d_accept);
     text_free(b->text);
     if (b->stream) hipStreamDestroy(b->stream);
     delete b;
@@ -5387,21 +5114,21 @@ extern "C" int gs_filter_submit(gs_bloom *b, int k, int min_pos_count, double po
         const size_t nbytes = (size_t)(offsets[n_reads] - offsets[0]);
         if (b->seq_cap < nbytes + 1) {
             HIP_TRY(hipStreamSynchronize(b->stream));
-            hipFree(b->d_seq);
+            gs_dev_free(b->d_seq);
             b->d_seq = nullptr;
             b->seq_cap = 0;
-            HIP_TRY(hipMalloc((void **)&b->d_seq, nbytes + 1));
+            HIP_TRY(gs_dev_alloc((void **)&b->d_seq, nbytes + 1));
             b->seq_cap = nbytes + 1;
         }
         if (b->reads_cap < (size_t)n_reads) {
             HIP_TRY(hipStreamSynchronize(b->stream));
-            hipFree(b->d_off);
-            hipFree(b->d_accept);
+            gs_dev_free(b->d_off);
+            gs_dev_free(b->d_accept);
             b->d_off = nullptr;
             b->d_accept = nullptr;
             b->reads_cap = 0;
-            HIP_TRY(hipMalloc((void **)&b->d_off, sizeof(uint64_t) * ((size_t)n_reads + 1)));
-            HIP_TRY(hipMalloc((void **)&b->d_accept, (size_t)n_reads));
+            HIP_TRY(gs_dev_alloc((void **)&b->d_off, sizeof(uint64_t) * ((size_t)n_reads + 1)));
+            HIP_TRY(gs_dev_alloc((void **)&b->d_accept, (size_t)n_reads));
             b->reads_cap = (size_t)n_reads;
         }
         const uint64_t *hoff = offsets;
@@ -5452,13 +5179,13 @@ static int filter_submit_text(gs_bloom *b, int k, int min_pos_count, double posi
     const bool dev_out = mem == GS_MEM_DEVICE;  // (GS_MEM_DEVICE_TEXT: the text is in HBM, accept / newlines are host arrays)
     if (!dev_out && b->reads_cap < (size_t)n_reads) {
         HIP_TRY(hipStreamSynchronize(b->stream));
-        hipFree(b->d_off);
-        hipFree(b->d_accept);
+        gs_dev_free(b->d_off);
+        gs_dev_free(b->d_accept);
         b->d_off = nullptr;
         b->d_accept = nullptr;
         b->reads_cap = 0;
-        HIP_TRY(hipMalloc((void **)&b->d_off, sizeof(uint64_t) * ((size_t)n_reads + 1)));
-        HIP_TRY(hipMalloc((void **)&b->d_accept, (size_t)n_reads));
+        HIP_TRY(gs_dev_alloc((void **)&b->d_off, sizeof(uint64_t) * ((size_t)n_reads + 1)));
+        HIP_TRY(gs_dev_alloc((void **)&b->d_accept, (size_t)n_reads));
         b->reads_cap = (size_t)n_reads;
     }
     uint8_t *d_acc = dev_out ? accept : b->d_accept;
@@ -5509,22 +5236,16 @@ extern "C" int gs_filter_compact_text(gs_bloom *b, int which, int with_probs, in
 
 extern "C" int gs_filter_text_read_bounds(gs_bloom *b, uint64_t *bounds) {
     if (!b || !bounds) return fail(GS_E_INVALID, "NULL argument");
-    if (b->text.tickets == 0) return fail(GS_E_STATE, "no text chunk has been submitted");
-    if (!b->text.last_fasta) return fail(GS_E_STATE, "the last chunk was four-line FASTQ: its reads lie in the text (newlines)");
     HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipMemcpyAsync(bounds, b->text.d_off2, sizeof(uint64_t) * ((size_t)b->text.last_reads + 1), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return bloom_collect(b);
+    const int rc = text_read_bounds(b->text, b->stream, bounds, "the last chunk was four-line FASTQ: its reads lie in the text (newlines)");
+    return rc ? rc : bloom_collect(b);
 }
 
 extern "C" int gs_filter_text_line_classes(gs_bloom *b, uint8_t *classes) {
     if (!b || !classes) return fail(GS_E_INVALID, "NULL argument");
-    if (b->text.tickets == 0 || !b->text.d_ml_class) return fail(GS_E_STATE, "no general FASTQ chunk has been submitted");
     HIP_TRY(hipSetDevice(b->device));
-    if (b->text.last_lines > 0)
-        HIP_TRY(hipMemcpyAsync(classes, b->text.d_ml_class, (size_t)b->text.last_lines, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return bloom_collect(b);
+    const int rc = text_line_classes(b->text, b->stream, classes);
+    return rc ? rc : bloom_collect(b);
 }
 
 extern "C" int gs_filter_get_device(gs_bloom *b, int *device) {

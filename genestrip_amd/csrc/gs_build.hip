@@ -18,8 +18,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "gs_build_dev.h"
-
-typedef unsigned long long u64;
+#include "gs_launch.h"
 
 #define GS_BUILD_NONE 0xffffffffffffffffULL
 #define GS_BUILD_UPDATE 0x80000000u

@@ -37,8 +37,7 @@
 #include <vector>
 
 #include "../../include/gsgpu.h"
-
-typedef unsigned long long u64;
+#include "gs_launch.h"
 
 #define GD_PIECE 64512u   // most text bytes per member: 63 KiB = 64 slices of 1008 bytes (the CRC kernel's fast join wants a multiple of 1024)
 #define GD_PIECE_MIN 16384u  // a short text is cut finer, so that the device's wave slots have a piece each (a lone wave takes 2.4 ms for 63 KiB)
@@ -51,10 +50,6 @@ typedef unsigned long long u64;
 #define GD_PREFIX_WORDS 128
 #define GD_SAMPLE 2048         // ranges of the text the counting pass looks at ...
 #define GD_SAMPLE_BYTES 1008u  // ... of this many bytes each: one wave per range -- a chain of 16 steps (a whole piece: 1 000 steps, 2.4 ms; ranges of 4 032 bytes 0.15-0.57 ms)
-
-extern "C" int gs_crc_tiles_device(const uint8_t *d_text, int64_t n, uint32_t tile, uint32_t *d_crc, hipStream_t stream);
-extern "C" uint32_t gs_crc_init_term(uint64_t n);
-extern "C" const char *gs_inflate_last_error(void);
 
 // what a call's members share (device copy of GdCode's tables)
 struct GdTables {

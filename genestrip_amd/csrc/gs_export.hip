@@ -12,26 +12,8 @@
 
 #include <rocprim/device/device_scan.hpp>
 
+#include "gs_launch.h"
 #include "gs_layout.h"
-
-typedef unsigned long long u64;
-
-struct GsExportParams {
-    const u64 *rec;        // this handle's record lines (GS_REC_WORDS words each), n_rec of them
-    int64_t n_rec;
-    const u64 *tab;        // this handle's table buckets (GS_SLOTS_PER_BUCKET slots each): global buckets tab_first ..
-    int64_t tab_first, n_tab;
-    uint32_t bucket_bits, vbits;
-    int32_t k, n_values;
-    const int32_t *tin, *tout;
-    int32_t sel_vi;        // -1: every k-mer
-    int32_t with_desc;     // 0: value == sel_vi, else tin[sel_vi] <= tin[value] < tout[sel_vi]
-    u64 *count;            // k-mers emitted so far (one atomic per wave)
-    u64 *keys;             // nullptr: count only
-    uint32_t *vals;
-    u64 cap;               // room in keys / vals
-    u64 *hist;             // per value index, or nullptr
-};
 
 #define GS_EX_BLOCK 256
 #define GS_EX_MAX_PER_LANE 6  // a lane holds 16 bytes of a line: 6 record offsets or 2 table slots
@@ -163,19 +145,6 @@ extern "C" hipError_t gs_launch_export_decode(const GsExportParams *P, int n_cu,
 
 // ---- FASTQ text (FastQWriter.addRead as called by KMerFastqGenerator.generateFastq):
 //   "@GENESTRIP:" project ":" ":" taxid ":" n "\n" bases "\n" "+\n" '~' x k "\n"       n = 1, 2, .. over the file
-struct GsFastqParams {
-    const u64 *keys;
-    const uint32_t *vals;
-    int64_t first, n;            // records [first, first + n) of the export
-    int32_t k;
-    const uint8_t *project;      // project_len bytes
-    int32_t project_len;
-    const uint8_t *names;        // taxid of value v: names[name_off[v] .. name_off[v + 1])
-    const uint32_t *name_off;
-    uint32_t *len;               // n + 1 record lengths (the last one 0) ...
-    uint32_t *off;               // ... and their exclusive prefix: where each record starts, off[n] = the text's size
-    uint8_t *text;
-};
 
 __device__ __forceinline__ int gs_ex_digits(u64 x) {
     int d = 1;

@@ -47,9 +47,9 @@
 #include <vector>
 
 #include "../../include/gsgpu.h"
+#include "gs_launch.h"
 #include "gs_upload.h"
 
-typedef unsigned long long u64;
 struct __attribute__((aligned(16))) gs_u16x8 {
     uint16_t v[8];
 };
@@ -2299,8 +2299,6 @@ static int64_t gi_gzip_header(const uint8_t *gz, int64_t n) {
     if (flg & 2) hdr += 2;
     return hdr + 8 >= n ? -1 : hdr;
 }
-
-extern "C" int gs_gunzipper_reopen(gs_gunzipper *g, const uint8_t *gz, int64_t n);
 
 extern "C" int gs_gunzipper_open(gs_gunzipper **out, int device, const uint8_t *gz, int64_t n) {
     if (!out || !gz || n < 18) return gi_fail(GS_E_INVALID, "bad argument");

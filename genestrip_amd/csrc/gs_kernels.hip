@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "gs_absmod.h"  // gs_absmod: the filter's bit index
+#include "gs_launch.h"
 #include "gs_layout.h"
 #include "gs_params.h"
 
@@ -40,8 +41,6 @@
 #define GS_NODE_NONE (-3)
 #define GS_LONG_CHUNK 64           // entries of the long-read queue a wave reserves at a time (one atomic per chunk)
 #define GS_LONG_NONE 0xffffffffu   // padding of a chunk (a batch holds at most 2^32 - 1 reads)
-
-typedef unsigned long long u64;
 
 __device__ __forceinline__ int gs_lane() { return (int)__lane_id(); }
 __device__ __forceinline__ int gs_readlane(int v, int l) { return __builtin_amdgcn_readlane(v, l); }

@@ -20,9 +20,8 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
+#include "gs_launch.h"
 #include "gs_layout.h"
-
-typedef unsigned long long u64;
 
 #define GS_LB_EMPTY 0xffffffffu
 #define GS_LB_MAXWIN 8  // windows a minimizer's entries are clustered into; what fits none of them goes to the table

@@ -15,9 +15,8 @@
 #include <string>
 #include <vector>
 
+#include "gs_launch.h"
 #include "gs_params.h"
-
-typedef unsigned long long u64;
 
 __global__ __launch_bounds__(256) void gs_merge_i64_kernel(long long *dst, const long long *src, int64_t n, int op) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {

@@ -14,26 +14,13 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 
-typedef unsigned long long u64;
+#include "gs_launch.h"
 
 #define GS_QUAL_BLOCK 256
 #define GS_QUAL_ITEMS 4
 #define GS_QUAL_TILE (GS_QUAL_BLOCK * GS_QUAL_ITEMS)
 #define GS_QUAL_WINDOW 2048       // store keys of a tile held in LDS (16 KiB); wider windows are searched in global memory
 #define GS_QUAL_LDS_VALUES 2048   // per-workgroup count rows in LDS up to this many values (32 KiB), global atomics beyond
-
-struct GsQualityParams {  // (gs_api.cpp)
-    const u64 *keys;       // n pairs, ascending by (k-mer, leaf)
-    const uint32_t *leaf;  // leaf value index, n_values = "counts nothing"
-    int64_t n;
-    const u64 *skeys;      // the m stored k-mers, ascending
-    const uint32_t *svals;
-    int64_t m;
-    const int32_t *tin, *tout;
-    int32_t n_values;
-    u64 *counts;  // [n_values][2]: tp, tp+fn
-    u64 *stats;   // [2]: distinct pairs of counting leaves, those found in the store
-};
 
 // pairs [0, n): the region number the k-mer kernel wrote -> that region's leaf
 __global__ __launch_bounds__(256) void gs_quality_tag_kernel(uint32_t *vals, int64_t n, const uint32_t *leaf_of_region, int64_t n_regions) {

@@ -28,9 +28,8 @@
 
 #include <algorithm>
 
+#include "gs_launch.h"
 #include "gs_params.h"
-
-typedef unsigned long long u64;
 
 #define GS_TEXT_TILE 4096
 #define GS_TEXT_BLOCK 256

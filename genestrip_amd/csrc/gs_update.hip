@@ -20,25 +20,10 @@
 #include <stdint.h>
 
 #include "gs_build_dev.h"
-
-typedef unsigned long long u64;
+#include "gs_launch.h"
 
 #define GS_UPD_BLOCK 256
 #define GS_UPD_LINEAR 4  // buckets up to this many k-mers are walked, longer ones halved first
-
-struct GsUpdateParams {  // (gs_api.cpp)
-    const u64 *skeys;     // the m stored k-mers, ascending
-    int32_t *svals;       // their value indices: updated in place
-    int64_t m;
-    const void *dir;      // (1 << dir_bits) + 1 bucket starts, uint32_t or (wide) u64
-    int32_t dir_bits, wide, k;
-    const int32_t *parent, *depth;
-    const u64 *keys;      // the slice's pairs
-    const uint32_t *region;
-    const u64 *n_pairs;   // their number (device: written by the k-mer kernel)
-    const int32_t *node_of_region;
-    u64 *stats;           // [0] += pairs, [1] += pairs whose k-mer is stored
-};
 
 // key < 4^k.  Non-decreasing in key.
 __device__ __forceinline__ uint32_t gs_upd_bucket(u64 key, int k, int dir_bits) {

@@ -74,6 +74,36 @@ def test_product_package_does_not_import_the_oracle():
                 assert "gs_oracle" not in txt and "libgsoracle" not in txt, f
 
 
+def test_launchers_and_parameter_blocks_are_declared_once():
+    """gs_launch.h is the one place where a launcher or a kernel parameter block is declared: no Gs* struct is defined in two
+    files, no translation unit of libgsgpu.so holds an extern "C" prototype of its own, and gs_api.cpp names its device
+    allocations (gs_dev_alloc / gs_dev_free) instead of redefining hipMalloc / hipFree"""
+    csrc = os.path.join(ROOT, "genestrip_amd", "csrc")
+    src = {f: open(os.path.join(csrc, f), errors="replace").read() for f in sorted(os.listdir(csrc)) if f.endswith((".h", ".hip", ".cpp"))}
+    where = {}
+    for f, txt in src.items():
+        for name in set(re.findall(r"\bstruct (Gs\w+) \{", txt)):
+            where.setdefault(name, []).append(f)
+    for name in ("GsExportParams", "GsFastqParams", "GsQualityParams", "GsUpdateParams"):
+        assert where.get(name) == ["gs_launch.h"], (name, where.get(name))
+    twice = {n: fs for n, fs in where.items() if len(fs) > 1}
+    assert not twice, twice
+
+    obj = re.search(r"^OBJ := (.*)$", open(os.path.join(csrc, "Makefile")).read(), re.M).group(1)
+    units = {os.path.basename(o)[:-2] for o in obj.split()} | {"gs_devcache"}
+    files = [f for f in src if f.endswith((".hip", ".cpp")) and f.rsplit(".", 1)[0] in units]
+    assert len(files) == len(units) >= 13, (sorted(files), sorted(units))
+    for f in files:
+        protos = [" ".join(m.group(0).split()) for m in re.finditer(r'extern "C"[^;{]*;', src[f])]
+        assert not protos, (f, protos)
+
+    api = src["gs_api.cpp"]
+    assert not re.search(r"#\s*define\s+hip(Malloc|Free)\b", api)
+    bare = re.findall(r"\bhip(?:Malloc|Free)\(", api)
+    assert not bare, len(bare)
+    assert "hipHostMalloc(" in api and "gs_dev_alloc(" in api and "gs_dev_free(" in api
+
+
 def test_synth_reads_deterministic_and_shaped():
     from genestrip_amd import synth
     db = synth.SynthDB(k=31, genera=2, species_per_genus=2, genome_len=5000, seed=7)
