@@ -33,6 +33,12 @@ static int fail(int code, const std::string &msg) {
     return code;
 }
 
+// the fence of an entry point whose host allocations (std::vector, std::string) can throw: `int f(...) try { ... } GS_API_CATCH`
+// (nothing may leave through the C ABI)
+#define GS_API_CATCH                                                                  \
+    catch (const std::bad_alloc &) { return fail(GS_E_NOMEM, "out of host memory"); } \
+    catch (const std::exception &e) { return fail(GS_E_INVALID, std::string("unexpected exception: ") + e.what()); }
+
 static int hip_fail(hipError_t e, const std::string &where) {
     return fail(e == hipErrorOutOfMemory ? GS_E_NOMEM : GS_E_HIP, where + ": " + hipGetErrorString(e));
 }
@@ -201,21 +207,15 @@ static int db_self_check(gs_db *db);
 extern "C" int gs_db_create(gs_db **out, int device, int k, int64_t n, const int64_t *kmers, const int32_t *vidx,
                             int32_t n_values, const int32_t *parent_vi) try {
     return db_create_impl(out, device, k, n, kmers, vidx, n_values, parent_vi, 1, 0, true);
-} catch (const std::bad_alloc &) {
-    return fail(GS_E_NOMEM, "out of host memory");
-} catch (const std::exception &e) {  // (nothing may leave through the C ABI)
-    return fail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
 }
+GS_API_CATCH
 
 extern "C" int gs_db_create_part(gs_db **out, int device, int k, int64_t n, const int64_t *kmers, const int32_t *vidx,
                                  int32_t n_values, const int32_t *parent_vi, int n_parts, int part) try {
     if (n_parts < 1 || part < 0 || part >= n_parts) return fail(GS_E_INVALID, "bad partition");
     return db_create_impl(out, device, k, n, kmers, vidx, n_values, parent_vi, n_parts, part, false);
-} catch (const std::bad_alloc &) {
-    return fail(GS_E_NOMEM, "out of host memory");
-} catch (const std::exception &e) {  // (nothing may leave through the C ABI)
-    return fail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
 }
+GS_API_CATCH
 
 // ---- striped store (include/gsgpu.h)
 extern "C" int gs_db_create_striped(gs_db **out, const int *devices, int n_stripes, int k, int64_t n, const int64_t *kmers,
@@ -227,22 +227,16 @@ extern "C" int gs_db_create_striped(gs_db **out, const int *devices, int n_strip
         if (rc) return rc;
     }
     return db_create_impl(out, devices[0], k, n, kmers, vidx, n_values, parent_vi, 1, 0, true, n_stripes, devices, -1);
-} catch (const std::bad_alloc &) {
-    return fail(GS_E_NOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return fail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
 }
+GS_API_CATCH
 
 extern "C" int gs_db_create_stripe(gs_db **out, int device, int n_stripes, int stripe, int k, int64_t n, const int64_t *kmers,
                                    const int32_t *vidx, int32_t n_values, const int32_t *parent_vi) try {
     if (!out || n_stripes < 2 || n_stripes > GS_MAX_STRIPES || stripe < 0 || stripe >= n_stripes)
         return fail(GS_E_INVALID, "a striped store spans 2..8 devices");
     return db_create_impl(out, device, k, n, kmers, vidx, n_values, parent_vi, 1, 0, true, n_stripes, nullptr, stripe);
-} catch (const std::bad_alloc &) {
-    return fail(GS_E_NOMEM, "out of host memory");
-} catch (const std::exception &e) {
-    return fail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
 }
+GS_API_CATCH
 
 extern "C" int gs_db_stripe_export(gs_db *db, void *handle) {
     if (!db || !handle) return fail(GS_E_INVALID, "NULL argument");
@@ -1640,11 +1634,8 @@ extern "C" int gs_db_save(gs_db *db, const char *path) try {
          par_write(tree.data(), tree.size() * sizeof(int32_t));
     ok = (fclose(f) == 0) && ok;
     return ok ? GS_OK : fail(GS_E_IO, std::string("short write to ") + path);
-} catch (const std::bad_alloc &) {
-    return fail(GS_E_NOMEM, "out of host memory");
-} catch (const std::exception &e) {  // (nothing may leave through the C ABI)
-    return fail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
 }
+GS_API_CATCH
 
 // a store file into HBM: whole (stripes <= 1) or striped, as store_place
 static int db_load_impl(gs_db **out, int device, const char *path, int stripes, const int *stripe_devices, int stripe_only) {
@@ -1751,10 +1742,6 @@ static int db_load_impl(gs_db **out, int device, const char *path, int stripes, 
     im.tout = tree.data() + 3 * nv;
     return store_place(im, device, stripes, stripe_devices, stripe_only, out);
 }
-
-#define GS_API_CATCH                                                                  \
-    catch (const std::bad_alloc &) { return fail(GS_E_NOMEM, "out of host memory"); } \
-    catch (const std::exception &e) { return fail(GS_E_INVALID, std::string("unexpected exception: ") + e.what()); }
 
 extern "C" int gs_db_load(gs_db **out, int device, const char *path) try {
     return db_load_impl(out, device, path, 1, nullptr, -1);
@@ -2086,15 +2073,144 @@ struct TextScan {
 };
 enum { GS_TEXT_BANKS = 16 };
 
+// `n` elements in place of what *p held (the caller has seen to it that nothing on the device uses the old block any more)
+template <typename T>
+static int renew(T **p, size_t n) {
+    gs_dev_free(*p);
+    *p = nullptr;
+    HIP_TRY(gs_dev_alloc((void **)p, n * sizeof(T)));
+    return GS_OK;
+}
+
+// room for `need` elements: a buffer that is too small goes once `stream` has drained, the new one holds `slack` elements more
+template <typename T>
+static int grow(T **p, size_t *cap, size_t need, hipStream_t stream, size_t slack) {
+    if (*cap >= need) return GS_OK;
+    HIP_TRY(hipStreamSynchronize(stream));
+    *cap = 0;
+    const int rc = renew(p, need + slack);
+    if (!rc) *cap = need + slack;
+    return rc;
+}
+template <typename T>
+static int grow(T **p, size_t *cap, size_t need, hipStream_t stream) {
+    return grow(p, cap, need, stream, need / 4);
+}
+
+// device staging of a host batch (GS_MEM_HOST): the bases, the offsets and the per-read outputs.  One per filter handle, one per
+// run for its synchronous calls (submit, submit_fixed, segments, text chunks with host outputs: they share it), one per async bank.
+struct HostStage {
+    const bool with_class;  // the matcher's; the filter keeps no d_class
+    const bool slack;       // capacities: exactly the largest batch so far, or (the async banks, whose batches vary) a quarter on top
+    explicit HostStage(bool with_class_ = true, bool slack_ = false) : with_class(with_class_), slack(slack_) {}
+    uint8_t *d_seq = nullptr;
+    uint64_t *d_off = nullptr;
+    int32_t *d_class = nullptr;
+    uint8_t *d_flags = nullptr;  // the filter: accept
+    size_t seq_cap = 0, reads_cap = 0;  // reads_cap: entries of d_class / d_flags; d_off holds one more
+    std::vector<uint64_t> rel;   // offsets of a batch whose offsets[0] != 0, rebased: the upload reads them after stage_upload has returned
+};
+
+// room for the offsets and per-read outputs of n_reads reads (a text chunk with host outputs needs no more).  Like stage_room it
+// synchronises `stream` only when buffers have to go
+static int stage_room_reads(HostStage &s, size_t n_reads, hipStream_t stream) {
+    if (s.reads_cap >= n_reads) return GS_OK;
+    HIP_TRY(hipStreamSynchronize(stream));
+    s.reads_cap = 0;
+    const size_t cap = n_reads + (s.slack ? n_reads / 4 : 0);
+    int rc = renew(&s.d_off, cap + 1);
+    if (!rc && s.with_class) rc = renew(&s.d_class, cap);
+    if (!rc) rc = renew(&s.d_flags, cap);
+    if (!rc) s.reads_cap = cap;
+    return rc;
+}
+
+// room for a batch of n_reads reads of nbytes bases; `also`: a second stream that uses the buffers, drained as well before one goes
+static int stage_room(HostStage &s, size_t nbytes, size_t n_reads, hipStream_t stream, hipStream_t also = nullptr) {
+    if (also && (s.seq_cap < nbytes + 1 || s.reads_cap < n_reads)) HIP_TRY(hipStreamSynchronize(also));
+    const int rc = grow(&s.d_seq, &s.seq_cap, nbytes + 1, stream, s.slack ? nbytes / 4 : 0);
+    return rc ? rc : stage_room_reads(s, n_reads, stream);
+}
+
+// the batch into d_seq / d_off on `stream`, the offsets rebased so that the staged slice starts at 0
+static int stage_upload(HostStage &s, const uint8_t *seq, const uint64_t *offsets, int64_t n_reads, hipStream_t stream) {
+    const uint64_t *hoff = offsets;
+    if (offsets[0] != 0) {
+        s.rel.resize((size_t)n_reads + 1);
+        for (int64_t i = 0; i <= n_reads; i++) s.rel[(size_t)i] = offsets[i] - offsets[0];
+        hoff = s.rel.data();
+    }
+    HIP_TRY(hipMemcpyAsync(s.d_seq, seq + offsets[0], (size_t)(offsets[n_reads] - offsets[0]), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(s.d_off, hoff, sizeof(uint64_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice, stream));
+    return GS_OK;
+}
+
+// the per-read outputs the caller asked for, from the stage to its host arrays on `stream`
+static int stage_download(const HostStage &s, int32_t *class_vi, uint8_t *flags, int64_t n_reads, hipStream_t stream) {
+    if (class_vi) HIP_TRY(hipMemcpyAsync(class_vi, s.d_class, sizeof(int32_t) * (size_t)n_reads, hipMemcpyDeviceToHost, stream));
+    if (flags) HIP_TRY(hipMemcpyAsync(flags, s.d_flags, (size_t)n_reads, hipMemcpyDeviceToHost, stream));
+    return GS_OK;
+}
+
+static void stage_free(HostStage &s) {
+    gs_dev_free(s.d_seq);
+    gs_dev_free(s.d_off);
+    gs_dev_free(s.d_class);
+    gs_dev_free(s.d_flags);
+}
+
+// kernel time of a handle that profiles: an event pair around every timed launch, read out once the stream has passed it
+struct KernelTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;  // the pair of the launch under way
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
+    int64_t launches = 0;
+    double total_ms = 0;
+};
+
+static int timer_start(KernelTimer &t, bool on, hipStream_t stream) {
+    if (!on) return GS_OK;
+    if (!t.e0) HIP_TRY(hipEventCreate(&t.e0));  // (left over: a launch that failed between start and stop)
+    if (!t.e1) HIP_TRY(hipEventCreate(&t.e1));
+    HIP_TRY(hipEventRecord(t.e0, stream));
+    return GS_OK;
+}
+
+static int timer_stop(KernelTimer &t, bool on, hipStream_t stream) {
+    if (!on) return GS_OK;
+    HIP_TRY(hipEventRecord(t.e1, stream));
+    t.pending.push_back({t.e0, t.e1});
+    t.e0 = t.e1 = nullptr;
+    return GS_OK;
+}
+
+// adds up the pairs handed in so far; the stream must have passed them
+static int timer_collect(KernelTimer &t) {
+    for (auto &p : t.pending) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, p.first, p.second));
+        t.total_ms += ms;
+        t.launches++;
+        hipEventDestroy(p.first);
+        hipEventDestroy(p.second);
+    }
+    t.pending.clear();
+    return GS_OK;
+}
+
+static void timer_free(KernelTimer &t) {
+    for (auto &p : t.pending) {
+        hipEventDestroy(p.first);
+        hipEventDestroy(p.second);
+    }
+    if (t.e0) hipEventDestroy(t.e0);
+    if (t.e1) hipEventDestroy(t.e1);
+    t = KernelTimer();
+}
+
 // gs_match_submit_async: two sets of device staging buffers, filled by turns on a copy stream, so that the copy of
 // batch i+1 runs while the kernel of batch i works on the other set
 struct BatchStage {
-    uint8_t *d_seq[2] = {nullptr, nullptr};
-    uint64_t *d_off[2] = {nullptr, nullptr};
-    int32_t *d_class[2] = {nullptr, nullptr};
-    uint8_t *d_flags[2] = {nullptr, nullptr};
-    size_t seq_cap[2] = {0, 0}, reads_cap[2] = {0, 0};
-    std::vector<uint64_t> rel[2];  // rebased offsets of a batch whose offsets[0] != 0 (must outlive the copy)
+    HostStage bank[2] = {HostStage(true, true), HostStage(true, true)};
     hipStream_t copy_stream = nullptr;
     hipEvent_t copied[2] = {}, finished[4] = {};  // finished[t % 4]: everything of batch t is through
     int64_t tickets = 0;
@@ -2140,12 +2256,7 @@ struct gs_run {
     unsigned char *d_huge = nullptr;
     int huge_slots = 0, huge_min = GS_HUGE_MIN, huge_chunk_min = GS_HUGE_CHUNK_MIN;
     int long_grid = 0;
-    // host staging (GS_MEM_HOST)
-    uint8_t *d_seq = nullptr;
-    uint64_t *d_off = nullptr;
-    int32_t *d_class = nullptr;
-    uint8_t *d_flags = nullptr;
-    size_t seq_cap = 0, reads_cap = 0;
+    HostStage host;  // host batches of the synchronous calls (GS_MEM_HOST)
     int grid = 0;
     // Kraken-style segments of the last gs_match_segments call
     uint32_t *d_seg_count = nullptr;
@@ -2153,10 +2264,7 @@ struct gs_run {
     int32_t *d_seg_code = nullptr, *d_seg_start = nullptr;
     int64_t seg_total = 0;
     TextScan text;  // text mode (gs_match_submit_text)
-    // profiling
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
-    int64_t launches = 0;
-    double total_ms = 0;
+    KernelTimer timer;  // cfg.profile
 };
 
 
@@ -2197,19 +2305,6 @@ static void text_free(TextScan &t) {
     for (hipEvent_t ev : t.copied)
         if (ev) hipEventDestroy(ev);
     t = TextScan();
-}
-
-template <typename T>
-static int grow(T **p, size_t *cap, size_t need, hipStream_t stream) {
-    if (*cap >= need) return GS_OK;
-    HIP_TRY(hipStreamSynchronize(stream));
-    gs_dev_free(*p);
-    *p = nullptr;
-    *cap = 0;
-    const size_t n = need + need / 4;
-    HIP_TRY(gs_dev_alloc((void **)p, n * sizeof(T)));
-    *cap = n;
-    return GS_OK;
 }
 
 static int text_reset_bank(TextScan &t, int bank, bool totals, hipStream_t stream) {
@@ -2401,6 +2496,39 @@ static int text_touched(TextScan &t, hipStream_t stream) {
     return GS_OK;
 }
 
+// what a text chunk hands to the kernel of its handle (match or filter)
+struct TextBatch {
+    int64_t n_reads = 0;
+    bool fasta = false;               // the reads were gathered (FASTA, general FASTQ), not left in place
+    const uint8_t *d_seq = nullptr;   // FASTQ: the sequence lines in place, (start, end) pairs; FASTA: the gathered sequences, running offsets
+    int off_stride = 2;
+    const uint32_t *d_skip = nullptr; // the bank's skip flag: a refused chunk is not worked on
+    bool dev_out = false;             // the per-read outputs are device arrays (GS_MEM_DEVICE_TEXT: the text is in HBM, they are host arrays)
+};
+
+// front half of a text-mode submit: checks mem, copies and scans the chunk (text_submit) and says what to launch on; n_reads == 0: nothing
+static int text_batch(TextScan &t, hipStream_t stream, const uint8_t *text, int64_t n_bytes, int64_t n_lines, int mem, int k, int64_t *ticket,
+                      int64_t fasta_records, int64_t *ml_out, TextBatch *tb) {
+    tb->fasta = fasta_records >= 0 || ml_out != nullptr;
+    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE && mem != GS_MEM_DEVICE_TEXT) return fail(GS_E_INVALID, "bad mem");
+    const int rc = text_submit(t, stream, text, n_bytes, n_lines, mem == GS_MEM_HOST ? GS_MEM_HOST : GS_MEM_DEVICE, k, ticket, fasta_records, ml_out);
+    if (rc) return rc;
+    tb->n_reads = ml_out ? std::max<int64_t>(ml_out[0], 0) : (tb->fasta ? fasta_records : (n_lines >> 2));
+    tb->dev_out = mem == GS_MEM_DEVICE;
+    tb->d_seq = tb->fasta ? t.d_fa_seq : t.d_text;
+    tb->off_stride = tb->fasta ? 1 : 2;
+    tb->d_skip = t.d_status + (size_t)t.bank * GS_TS_WORDS + GS_TS_SKIP;
+    return GS_OK;
+}
+
+// what a general FASTQ chunk reports: complete records, the bytes and the lines they cover (text_submit's ml_out)
+static int ml_report(int rc, const int64_t out[3], int64_t *n_records, int64_t *consumed_bytes, int64_t *consumed_lines) {
+    *n_records = out[0];
+    *consumed_bytes = out[1];
+    if (consumed_lines) *consumed_lines = out[2];
+    return rc;
+}
+
 static int text_wait_copy(TextScan &t, int64_t ticket) {
     if (ticket < 0 || ticket >= t.tickets) return fail(GS_E_INVALID, "unknown ticket");
     if (ticket + 8 <= t.tickets) return GS_OK;  // its event has been re-recorded by a later submit: long done
@@ -2464,10 +2592,7 @@ static int run_clear(gs_run *run) {
 static void run_free(gs_run *run) {
     if (!run) return;
     hipSetDevice(run->db->device);
-    for (auto &p : run->pending) {
-        hipEventDestroy(p.first);
-        hipEventDestroy(p.second);
-    }
+    timer_free(run->timer);
     hipHostFree(run->h_result);
     gs_dev_free(run->d_sums);  // (d_max, d_dsums, d_long_count lie inside)
     gs_dev_free(run->d_stat_recs);
@@ -2484,10 +2609,7 @@ static void run_free(gs_run *run) {
     gs_dev_free(run->d_scratch);
     gs_dev_free(run->d_serial);
     gs_dev_free(run->d_huge);
-    gs_dev_free(run->d_seq);
-    gs_dev_free(run->d_off);
-    gs_dev_free(run->d_class);
-    gs_dev_free(run->d_flags);
+    stage_free(run->host);
     gs_dev_free(run->d_seg_count);
     gs_dev_free(run->d_seg_off);
     gs_dev_free(run->d_seg_code);
@@ -2500,10 +2622,7 @@ static void run_free(gs_run *run) {
             hipStreamDestroy(g.copy_stream);
         }
         for (int b = 0; b < 2; b++) {
-            gs_dev_free(g.d_seq[b]);
-            gs_dev_free(g.d_off[b]);
-            gs_dev_free(g.d_class[b]);
-            gs_dev_free(g.d_flags[b]);
+            stage_free(g.bank[b]);
             if (g.copied[b]) hipEventDestroy(g.copied[b]);
         }
         for (hipEvent_t ev : g.finished)
@@ -2582,19 +2701,6 @@ extern "C" int gs_match_begin(gs_run **out, gs_db *db, const gs_match_cfg *cfg) 
     if (cfg->count_unique && !db->striped()) db->unique_owner = run;  // (a striped store is read-only: any number of runs)
     db->live_runs++;
     *out = run;
-    return GS_OK;
-}
-
-static int collect_events(gs_run *run) {
-    for (auto &p : run->pending) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, p.first, p.second));
-        run->total_ms += ms;
-        run->launches++;
-        hipEventDestroy(p.first);
-        hipEventDestroy(p.second);
-    }
-    run->pending.clear();
     return GS_OK;
 }
 
@@ -2773,12 +2879,7 @@ static int launch_batch(gs_run *run, const uint8_t *d_seq, const uint64_t *d_off
     // (reads of one short length each, or nodes that came from other ranks: nothing for the huge-read kernels)
     const bool huge = !d_nodes && (off_stride != 0 || fixed_len - run->db->info.k + 1 >= run->huge_min);
     if (huge && (rc = ensure_huge(run, &P))) return rc;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (run->cfg.profile) {
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, run->stream));
-    }
+    if ((rc = timer_start(run->timer, run->cfg.profile != 0, run->stream))) return rc;
     if (run->cfg.count_unique && !d_nodes) {
         run->seen_dirty = true;
         run->bitmap_merged = false;
@@ -2798,10 +2899,7 @@ static int launch_batch(gs_run *run, const uint8_t *d_seq, const uint64_t *d_off
     if (P.stat_recs && !all_long)  // (into copy 0 of the counters; part of the timed region)
         HIP_TRY(gs_launch_stat_reduce(P.stat_recs, run->d_stat_rec_count, rec_room, run->db->info.n_values, run->d_sums, run->d_max,
                                       run->d_dsums, run->d_stat_vi, run->stream));
-    if (run->cfg.profile) {
-        HIP_TRY(hipEventRecord(e1, run->stream));
-        run->pending.push_back({e0, e1});
-    }
+    if ((rc = timer_stop(run->timer, run->cfg.profile != 0, run->stream))) return rc;
     const int pos_fixed = fixed_len - run->db->info.k + 1;
     if (all_long && pos_fixed <= 256 && ((P.wide_mask >> (pos_fixed <= 192 ? 0 : 1)) & 1)) {  // the whole batch in trips of three / four sub-rounds
         HIP_TRY(gs_launch_match_wide(&P, pos_fixed <= 192 ? 3 : 4, run->db->n_cu, run->stream));
@@ -2818,7 +2916,7 @@ static int launch_batch(gs_run *run, const uint8_t *d_seq, const uint64_t *d_off
 }
 
 extern "C" int gs_match_submit(gs_run *run, const uint8_t *seq, const uint64_t *offsets, int64_t n_reads,
-                               int64_t first_read_no, int mem, int32_t *class_vi, uint8_t *flags) {
+                               int64_t first_read_no, int mem, int32_t *class_vi, uint8_t *flags) try {
     if (!run) return fail(GS_E_INVALID, "run is NULL");
     if (n_reads < 0 || (n_reads > 0 && (!seq || !offsets))) return fail(GS_E_INVALID, "bad batch arrays");
     if (n_reads == 0) return GS_OK;
@@ -2826,52 +2924,20 @@ extern "C" int gs_match_submit(gs_run *run, const uint8_t *seq, const uint64_t *
     if (mem == GS_MEM_DEVICE) return launch_batch(run, seq, offsets, n_reads, first_read_no, class_vi, flags);
     if (mem != GS_MEM_HOST) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
     // host batch: stage to HBM (synchronous)
-    const size_t nbytes = (size_t)(offsets[n_reads] - offsets[0]);
-    if (run->seq_cap < nbytes + 1) {
-        HIP_TRY(hipStreamSynchronize(run->stream));
-        gs_dev_free(run->d_seq);
-        run->d_seq = nullptr;
-        run->seq_cap = 0;
-        HIP_TRY(gs_dev_alloc((void **)&run->d_seq, nbytes + 1));
-        run->seq_cap = nbytes + 1;
-    }
-    if (run->reads_cap < (size_t)n_reads) {
-        HIP_TRY(hipStreamSynchronize(run->stream));
-        gs_dev_free(run->d_off);
-        gs_dev_free(run->d_class);
-        gs_dev_free(run->d_flags);
-        run->d_off = nullptr;
-        run->d_class = nullptr;
-        run->d_flags = nullptr;
-        run->reads_cap = 0;
-        HIP_TRY(gs_dev_alloc((void **)&run->d_off, sizeof(uint64_t) * ((size_t)n_reads + 1)));
-        HIP_TRY(gs_dev_alloc((void **)&run->d_class, sizeof(int32_t) * (size_t)n_reads));
-        HIP_TRY(gs_dev_alloc((void **)&run->d_flags, (size_t)n_reads));
-        run->reads_cap = (size_t)n_reads;
-    }
-    // offsets are rebased so that the staged slice starts at 0
-    std::vector<uint64_t> rel;
-    const uint64_t *hoff = offsets;
-    if (offsets[0] != 0) {
-        rel.resize((size_t)n_reads + 1);
-        for (int64_t i = 0; i <= n_reads; i++) rel[(size_t)i] = offsets[i] - offsets[0];
-        hoff = rel.data();
-    }
-    HIP_TRY(hipMemcpyAsync(run->d_seq, seq + offsets[0], nbytes, hipMemcpyHostToDevice, run->stream));
-    HIP_TRY(hipMemcpyAsync(run->d_off, hoff, sizeof(uint64_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice, run->stream));
-    int rc = launch_batch(run, run->d_seq, run->d_off, n_reads, first_read_no, class_vi ? run->d_class : nullptr,
-                          flags ? run->d_flags : nullptr);
+    HostStage &h = run->host;
+    int rc = stage_room(h, (size_t)(offsets[n_reads] - offsets[0]), (size_t)n_reads, run->stream);
+    if (!rc) rc = stage_upload(h, seq, offsets, n_reads, run->stream);
+    if (!rc) rc = launch_batch(run, h.d_seq, h.d_off, n_reads, first_read_no, class_vi ? h.d_class : nullptr, flags ? h.d_flags : nullptr);
+    if (!rc) rc = stage_download(h, class_vi, flags, n_reads, run->stream);
     if (rc) return rc;
-    if (class_vi)
-        HIP_TRY(hipMemcpyAsync(class_vi, run->d_class, sizeof(int32_t) * (size_t)n_reads, hipMemcpyDeviceToHost, run->stream));
-    if (flags) HIP_TRY(hipMemcpyAsync(flags, run->d_flags, (size_t)n_reads, hipMemcpyDeviceToHost, run->stream));
     HIP_TRY(hipStreamSynchronize(run->stream));
-    return collect_events(run);
+    return timer_collect(run->timer);
 }
+GS_API_CATCH
 
 // reads of ONE length, back to back, without an offsets array (what a sequencer's FASTQ gives once parsed: `read_len` bases each)
 extern "C" int gs_match_submit_fixed(gs_run *run, const uint8_t *seq, int32_t read_len, int64_t n_reads, int64_t first_read_no, int mem,
-                                     int32_t *class_vi, uint8_t *flags) {
+                                     int32_t *class_vi, uint8_t *flags) try {
     if (!run) return fail(GS_E_INVALID, "run is NULL");
     if (n_reads < 0 || read_len < 0 || (n_reads > 0 && !seq)) return fail(GS_E_INVALID, "bad batch arrays");
     if (n_reads == 0) return GS_OK;
@@ -2879,38 +2945,19 @@ extern "C" int gs_match_submit_fixed(gs_run *run, const uint8_t *seq, int32_t re
     if (mem == GS_MEM_DEVICE)
         return launch_batch(run, seq, nullptr, n_reads, first_read_no, class_vi, flags, nullptr, nullptr, 0, nullptr, read_len);
     if (mem != GS_MEM_HOST) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    HostStage &h = run->host;
     const size_t nbytes = (size_t)n_reads * (size_t)read_len;
-    if (run->seq_cap < nbytes + 1) {
-        HIP_TRY(hipStreamSynchronize(run->stream));
-        gs_dev_free(run->d_seq);
-        run->d_seq = nullptr;
-        run->seq_cap = 0;
-        HIP_TRY(gs_dev_alloc((void **)&run->d_seq, nbytes + 1));
-        run->seq_cap = nbytes + 1;
-    }
-    if (run->reads_cap < (size_t)n_reads) {
-        HIP_TRY(hipStreamSynchronize(run->stream));
-        gs_dev_free(run->d_off);
-        gs_dev_free(run->d_class);
-        gs_dev_free(run->d_flags);
-        run->d_off = nullptr;
-        run->d_class = nullptr;
-        run->d_flags = nullptr;
-        run->reads_cap = 0;
-        HIP_TRY(gs_dev_alloc((void **)&run->d_off, sizeof(uint64_t) * ((size_t)n_reads + 1)));
-        HIP_TRY(gs_dev_alloc((void **)&run->d_class, sizeof(int32_t) * (size_t)n_reads));
-        HIP_TRY(gs_dev_alloc((void **)&run->d_flags, (size_t)n_reads));
-        run->reads_cap = (size_t)n_reads;
-    }
-    HIP_TRY(hipMemcpyAsync(run->d_seq, seq, nbytes, hipMemcpyHostToDevice, run->stream));
-    int rc = launch_batch(run, run->d_seq, nullptr, n_reads, first_read_no, class_vi ? run->d_class : nullptr, flags ? run->d_flags : nullptr, nullptr, nullptr,
-                          0, nullptr, read_len);
+    int rc = stage_room(h, nbytes, (size_t)n_reads, run->stream);
     if (rc) return rc;
-    if (class_vi) HIP_TRY(hipMemcpyAsync(class_vi, run->d_class, sizeof(int32_t) * (size_t)n_reads, hipMemcpyDeviceToHost, run->stream));
-    if (flags) HIP_TRY(hipMemcpyAsync(flags, run->d_flags, (size_t)n_reads, hipMemcpyDeviceToHost, run->stream));
+    HIP_TRY(hipMemcpyAsync(h.d_seq, seq, nbytes, hipMemcpyHostToDevice, run->stream));  // (no offsets: nothing to rebase)
+    rc = launch_batch(run, h.d_seq, nullptr, n_reads, first_read_no, class_vi ? h.d_class : nullptr, flags ? h.d_flags : nullptr, nullptr, nullptr,
+                      0, nullptr, read_len);
+    if (!rc) rc = stage_download(h, class_vi, flags, n_reads, run->stream);
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(run->stream));
-    return collect_events(run);
+    return timer_collect(run->timer);
 }
+GS_API_CATCH
 
 // the asynchronous form of a host batch: returns when the work is queued; gs_match_wait(ticket) returns when the
 // batch's per-read outputs are in place and its input arrays may be reused.  Two batches can be under way.
@@ -2927,60 +2974,26 @@ extern "C" int gs_match_submit_async(gs_run *run, const uint8_t *seq, const uint
     }
     const int64_t tk = g.tickets;
     const int b = (int)(tk & 1);
-    const size_t nbytes = (size_t)(offsets[n_reads] - offsets[0]);
-    if (tk >= 2) HIP_TRY(hipEventSynchronize(g.copied[b]));  // rel[b] of the batch before last is free (long done)
-    if (g.seq_cap[b] < nbytes + 1 || g.reads_cap[b] < (size_t)n_reads) {
-        HIP_TRY(hipStreamSynchronize(g.copy_stream));
-        HIP_TRY(hipStreamSynchronize(run->stream));
-        if (g.seq_cap[b] < nbytes + 1) {
-            gs_dev_free(g.d_seq[b]);
-            g.d_seq[b] = nullptr;
-            g.seq_cap[b] = 0;
-            HIP_TRY(gs_dev_alloc((void **)&g.d_seq[b], nbytes + nbytes / 4 + 1));
-            g.seq_cap[b] = nbytes + nbytes / 4 + 1;
-        }
-        if (g.reads_cap[b] < (size_t)n_reads) {
-            gs_dev_free(g.d_off[b]);
-            gs_dev_free(g.d_class[b]);
-            gs_dev_free(g.d_flags[b]);
-            g.d_off[b] = nullptr;
-            g.d_class[b] = nullptr;
-            g.d_flags[b] = nullptr;
-            g.reads_cap[b] = 0;
-            const size_t cap = (size_t)n_reads + (size_t)n_reads / 4;
-            HIP_TRY(gs_dev_alloc((void **)&g.d_off[b], sizeof(uint64_t) * (cap + 1)));
-            HIP_TRY(gs_dev_alloc((void **)&g.d_class[b], sizeof(int32_t) * cap));
-            HIP_TRY(gs_dev_alloc((void **)&g.d_flags[b], cap));
-            g.reads_cap[b] = cap;
-        }
-    }
-    const uint64_t *hoff = offsets;
-    if (offsets[0] != 0) {  // the staged slice starts at 0
-        g.rel[b].resize((size_t)n_reads + 1);
-        for (int64_t i = 0; i <= n_reads; i++) g.rel[b][(size_t)i] = offsets[i] - offsets[0];
-        hoff = g.rel[b].data();
-    }
+    HostStage &h = g.bank[b];
+    if (tk >= 2) HIP_TRY(hipEventSynchronize(g.copied[b]));  // h.rel of the batch before last is free (long done)
+    int rc = stage_room(h, (size_t)(offsets[n_reads] - offsets[0]), (size_t)n_reads, run->stream, g.copy_stream);
+    if (rc) return rc;
     // the batch before last must be through (its kernel read these buffers, its outputs left from them).  Waited for
     // on the host: a copy that has to wait for an event on the device was seen to start only after the kernel of the
     // previous batch had ended (rocprofv3 --memory-copy-trace), i.e. not to overlap at all
     if (tk >= 2) HIP_TRY(hipEventSynchronize(g.finished[(tk - 2) & 3]));
-    HIP_TRY(hipMemcpyAsync(g.d_seq[b], seq + offsets[0], nbytes, hipMemcpyHostToDevice, g.copy_stream));
-    HIP_TRY(hipMemcpyAsync(g.d_off[b], hoff, sizeof(uint64_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice, g.copy_stream));
+    if ((rc = stage_upload(h, seq, offsets, n_reads, g.copy_stream))) return rc;
     HIP_TRY(hipEventRecord(g.copied[b], g.copy_stream));
     HIP_TRY(hipStreamWaitEvent(run->stream, g.copied[b], 0));
-    int rc = launch_batch(run, g.d_seq[b], g.d_off[b], n_reads, first_read_no, class_vi ? g.d_class[b] : nullptr,
-                          flags ? g.d_flags[b] : nullptr);
+    rc = launch_batch(run, h.d_seq, h.d_off, n_reads, first_read_no, class_vi ? h.d_class : nullptr, flags ? h.d_flags : nullptr);
+    if (!rc) rc = stage_download(h, class_vi, flags, n_reads, run->stream);
     if (rc) return rc;
-    if (class_vi)
-        HIP_TRY(hipMemcpyAsync(class_vi, g.d_class[b], sizeof(int32_t) * (size_t)n_reads, hipMemcpyDeviceToHost, run->stream));
-    if (flags) HIP_TRY(hipMemcpyAsync(flags, g.d_flags[b], (size_t)n_reads, hipMemcpyDeviceToHost, run->stream));
     HIP_TRY(hipEventRecord(g.finished[tk & 3], run->stream));
     g.tickets = tk + 1;
     *ticket = tk;
     return GS_OK;
-} catch (const std::bad_alloc &) {
-    return fail(GS_E_NOMEM, "out of host memory");
 }
+GS_API_CATCH
 
 extern "C" int gs_match_wait(gs_run *run, int64_t ticket) {
     if (!run) return fail(GS_E_INVALID, "run is NULL");
@@ -3012,66 +3025,44 @@ static int match_submit_text(gs_run *run, const uint8_t *text, int64_t n_bytes, 
 
 extern "C" int gs_match_submit_fastq_ml(gs_run *run, const uint8_t *text, int64_t n_bytes, int64_t n_lines, int mem, int64_t first_read_no,
                                         int32_t *class_vi, uint8_t *flags, int64_t *n_records, int64_t *consumed_bytes, int64_t *consumed_lines,
-                                        int64_t *ticket) {
+                                        int64_t *ticket) try {
     if (!n_records || !consumed_bytes) return fail(GS_E_INVALID, "NULL argument");
     int64_t out[3] = {0, 0, 0};
     const int rc = match_submit_text(run, text, n_bytes, n_lines, mem, first_read_no, class_vi, flags, ticket, -1, out);
-    *n_records = out[0];
-    *consumed_bytes = out[1];
-    if (consumed_lines) *consumed_lines = out[2];
-    return rc;
+    return ml_report(rc, out, n_records, consumed_bytes, consumed_lines);
 }
+GS_API_CATCH
 
 extern "C" int gs_match_submit_text(gs_run *run, const uint8_t *text, int64_t n_bytes, int64_t n_lines, int mem,
-                                    int64_t first_read_no, int32_t *class_vi, uint8_t *flags, int64_t *ticket) {
+                                    int64_t first_read_no, int32_t *class_vi, uint8_t *flags, int64_t *ticket) try {
     return match_submit_text(run, text, n_bytes, n_lines, mem, first_read_no, class_vi, flags, ticket, -1);
 }
+GS_API_CATCH
 
 extern "C" int gs_match_submit_fasta(gs_run *run, const uint8_t *text, int64_t n_bytes, int64_t n_lines, int64_t n_records, int mem,
-                                     int64_t first_read_no, int32_t *class_vi, uint8_t *flags, int64_t *ticket) {
+                                     int64_t first_read_no, int32_t *class_vi, uint8_t *flags, int64_t *ticket) try {
     if (n_records < 0) return fail(GS_E_INVALID, "n_records < 0");
     return match_submit_text(run, text, n_bytes, n_lines, mem, first_read_no, class_vi, flags, ticket, n_records);
 }
+GS_API_CATCH
 
 static int match_submit_text(gs_run *run, const uint8_t *text, int64_t n_bytes, int64_t n_lines, int mem, int64_t first_read_no,
                              int32_t *class_vi, uint8_t *flags, int64_t *ticket, int64_t fasta_records, int64_t *ml_out) {
     if (!run) return fail(GS_E_INVALID, "run is NULL");
     HIP_TRY(hipSetDevice(run->db->device));
-    const bool fasta = fasta_records >= 0 || ml_out != nullptr;
-    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE && mem != GS_MEM_DEVICE_TEXT) return fail(GS_E_INVALID, "bad mem");
-    int rc = text_submit(run->text, run->stream, text, n_bytes, n_lines, mem == GS_MEM_HOST ? GS_MEM_HOST : GS_MEM_DEVICE, run->db->info.k, ticket,
-                         fasta_records, ml_out);
-    if (rc) return rc;
-    const int64_t n_reads = ml_out ? std::max<int64_t>(ml_out[0], 0) : (fasta ? fasta_records : (n_lines >> 2));
-    if (n_reads == 0) return GS_OK;
-    const bool dev_out = mem == GS_MEM_DEVICE;  // (GS_MEM_DEVICE_TEXT: the text is in HBM, class_vi / flags are host arrays)
-    if ((class_vi || flags) && !dev_out && run->reads_cap < (size_t)n_reads) {
-        HIP_TRY(hipStreamSynchronize(run->stream));
-        gs_dev_free(run->d_off);
-        gs_dev_free(run->d_class);
-        gs_dev_free(run->d_flags);
-        run->d_off = nullptr;
-        run->d_class = nullptr;
-        run->d_flags = nullptr;
-        run->reads_cap = 0;
-        HIP_TRY(gs_dev_alloc((void **)&run->d_off, sizeof(uint64_t) * ((size_t)n_reads + 1)));
-        HIP_TRY(gs_dev_alloc((void **)&run->d_class, sizeof(int32_t) * (size_t)n_reads));
-        HIP_TRY(gs_dev_alloc((void **)&run->d_flags, (size_t)n_reads));
-        run->reads_cap = (size_t)n_reads;
-    }
-    int32_t *dc = class_vi ? (dev_out ? class_vi : run->d_class) : nullptr;
-    uint8_t *df = flags ? (dev_out ? flags : run->d_flags) : nullptr;
-    // FASTQ: the sequence lines in place, (start, end) pairs; FASTA: the gathered sequences, running offsets
-    rc = launch_batch(run, fasta ? run->text.d_fa_seq : run->text.d_text, (const uint64_t *)run->text.d_off2, n_reads, first_read_no, dc,
-                      df, nullptr, nullptr, fasta ? 1 : 2, run->text.d_status + (size_t)run->text.bank * GS_TS_WORDS + GS_TS_SKIP);
+    TextBatch tb;
+    int rc = text_batch(run->text, run->stream, text, n_bytes, n_lines, mem, run->db->info.k, ticket, fasta_records, ml_out, &tb);
+    if (rc || tb.n_reads == 0) return rc;
+    // host outputs land in the run's stage (its capacity is shared with the host batches: d_off grows with it)
+    HostStage &h = run->host;
+    if ((class_vi || flags) && !tb.dev_out && (rc = stage_room_reads(h, (size_t)tb.n_reads, run->stream))) return rc;
+    int32_t *dc = class_vi ? (tb.dev_out ? class_vi : h.d_class) : nullptr;
+    uint8_t *df = flags ? (tb.dev_out ? flags : h.d_flags) : nullptr;
+    rc = launch_batch(run, tb.d_seq, (const uint64_t *)run->text.d_off2, tb.n_reads, first_read_no, dc, df, nullptr, nullptr, tb.off_stride, tb.d_skip);
     if (rc) return rc;
     if ((rc = text_touched(run->text, run->stream))) return rc;
     run->text.d_last_flags = df;
-    if (!dev_out) {  // complete after gs_match_sync
-        if (class_vi) HIP_TRY(hipMemcpyAsync(class_vi, run->d_class, sizeof(int32_t) * (size_t)n_reads, hipMemcpyDeviceToHost, run->stream));
-        if (flags) HIP_TRY(hipMemcpyAsync(flags, run->d_flags, (size_t)n_reads, hipMemcpyDeviceToHost, run->stream));
-    }
-    return GS_OK;
+    return tb.dev_out ? GS_OK : stage_download(h, class_vi, flags, tb.n_reads, run->stream);  // (complete after gs_match_sync)
 }
 
 // the reads matchRead() returned true for (GS_F_RETURNED), as afterMatch writes them (FastqKMerMatcher.java:304-307)
@@ -3116,7 +3107,7 @@ extern "C" int gs_match_text_status(gs_run *run, int64_t *failed_ticket, int64_t
     HIP_TRY(hipSetDevice(run->db->device));
     int rc = text_status(run->text, run->stream, failed_ticket, first_bad_record, totals);
     if (rc) return rc;
-    return collect_events(run);
+    return timer_collect(run->timer);
 }
 
 extern "C" int gs_match_text_select(gs_run *run, int bank) {
@@ -3181,7 +3172,7 @@ extern "C" int gs_match_sync(gs_run *run) {
     if (!run) return fail(GS_E_INVALID, "run is NULL");
     HIP_TRY(hipSetDevice(run->db->device));
     HIP_TRY(hipStreamSynchronize(run->stream));
-    return collect_events(run);
+    return timer_collect(run->timer);
 }
 
 extern "C" int gs_match_finish(gs_run *run, int64_t *table, double *dtable) {
@@ -3215,7 +3206,7 @@ extern "C" int gs_match_finish(gs_run *run, int64_t *table, double *dtable) {
     if (dtable) HIP_TRY(hipMemcpyAsync(dsums, run->d_dsums, sizeof(double) * nv * GS_N_DCOLS, hipMemcpyDeviceToHost, run->stream));
     HIP_TRY(hipStreamSynchronize(run->stream));
     if (dtable) memcpy(dtable, dsums, sizeof(double) * nv * GS_N_DCOLS);
-    int rc = collect_events(run);
+    int rc = timer_collect(run->timer);
     if (rc) return rc;
     for (size_t v = 0; v < nv; v++) {
         int64_t *row = table + v * GS_N_COLS;
@@ -3246,7 +3237,7 @@ extern "C" int gs_match_max_contig_reads(gs_run *run, int64_t *read_no) {
     }
     HIP_TRY(hipMemcpyAsync(maxk.data(), run->d_max, sizeof(int64_t) * nv, hipMemcpyDeviceToHost, run->stream));
     HIP_TRY(hipStreamSynchronize(run->stream));
-    int rc = collect_events(run);
+    int rc = timer_collect(run->timer);
     if (rc) return rc;
     for (size_t v = 0; v < nv; v++) {
         const u64 key = (u64)maxk[v];
@@ -3258,8 +3249,8 @@ extern "C" int gs_match_max_contig_reads(gs_run *run, int64_t *read_no) {
 extern "C" int gs_match_reset(gs_run *run) {
     if (!run) return fail(GS_E_INVALID, "run is NULL");
     HIP_TRY(hipSetDevice(run->db->device));
-    if (!run->pending.empty()) HIP_TRY(hipStreamSynchronize(run->stream));
-    int rc = collect_events(run);
+    if (!run->timer.pending.empty()) HIP_TRY(hipStreamSynchronize(run->stream));
+    int rc = timer_collect(run->timer);
     if (rc) return rc;
     rc = run_clear(run);  // kernel-time counters stay cumulative over the life of the handle
     if (rc) return rc;
@@ -3442,9 +3433,8 @@ extern "C" int gs_match_merge(gs_run *const *runs, int n_runs) try {
         HIP_TRY(hipStreamSynchronize(L->stream));
     }
     return GS_OK;
-} catch (const std::bad_alloc &) {
-    return fail(GS_E_NOMEM, "out of host memory");
 }
+GS_API_CATCH
 
 
 // ---------------------------------------------------------------------------------------------------
@@ -4572,35 +4562,13 @@ static int stage_batch(gs_run *run, const uint8_t *seq, const uint64_t *offsets,
         return GS_OK;
     }
     if (mem != GS_MEM_HOST) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
-    const size_t nbytes = (size_t)(offsets[n_reads] - offsets[0]);
-    HIP_TRY(hipStreamSynchronize(run->stream));
-    if (run->seq_cap < nbytes + 1) {
-        gs_dev_free(run->d_seq);
-        run->d_seq = nullptr;
-        run->seq_cap = 0;
-        HIP_TRY(gs_dev_alloc((void **)&run->d_seq, nbytes + 1));
-        run->seq_cap = nbytes + 1;
-    }
-    if (run->reads_cap < (size_t)n_reads) {
-        gs_dev_free(run->d_off);
-        gs_dev_free(run->d_class);
-        gs_dev_free(run->d_flags);
-        run->d_off = nullptr;
-        run->d_class = nullptr;
-        run->d_flags = nullptr;
-        run->reads_cap = 0;
-        HIP_TRY(gs_dev_alloc((void **)&run->d_off, sizeof(uint64_t) * ((size_t)n_reads + 1)));
-        HIP_TRY(gs_dev_alloc((void **)&run->d_class, sizeof(int32_t) * (size_t)n_reads));
-        HIP_TRY(gs_dev_alloc((void **)&run->d_flags, (size_t)n_reads));
-        run->reads_cap = (size_t)n_reads;
-    }
-    std::vector<uint64_t> rel((size_t)n_reads + 1);
-    for (int64_t i = 0; i <= n_reads; i++) rel[(size_t)i] = offsets[i] - offsets[0];
-    HIP_TRY(hipMemcpy(run->d_seq, seq + offsets[0], nbytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(run->d_off, rel.data(), sizeof(uint64_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice));
-    *d_seq = run->d_seq;
-    *d_off = run->d_off;
-    return GS_OK;
+    // (on the run's stream, like the kernels that read it; segments_core synchronises before it returns, so h.rel is free by then)
+    HostStage &h = run->host;
+    int rc = stage_room(h, (size_t)(offsets[n_reads] - offsets[0]), (size_t)n_reads, run->stream);
+    if (!rc) rc = stage_upload(h, seq, offsets, n_reads, run->stream);
+    *d_seq = h.d_seq;
+    *d_off = h.d_off;
+    return rc;
 }
 
 static int segments_core(gs_run *run, const uint8_t *d_seq, const uint64_t *d_off, int64_t n_reads, int off_stride, uint64_t *seg_off) {
@@ -4713,7 +4681,7 @@ static int segments_core(gs_run *run, const uint8_t *d_seq, const uint64_t *d_of
 }
 
 extern "C" int gs_match_segments(gs_run *run, const uint8_t *seq, const uint64_t *offsets, int64_t n_reads, int mem,
-                                 uint64_t *seg_off) {
+                                 uint64_t *seg_off) try {
     if (!run || !seg_off) return fail(GS_E_INVALID, "NULL argument");
     if (n_reads < 0 || (n_reads > 0 && (!seq || !offsets))) return fail(GS_E_INVALID, "bad batch arrays");
     HIP_TRY(hipSetDevice(run->db->device));
@@ -4726,9 +4694,10 @@ extern "C" int gs_match_segments(gs_run *run, const uint8_t *seq, const uint64_t
     if (rc) return rc;
     return segments_core(run, d_seq, d_off, n_reads, 1, seg_off);
 }
+GS_API_CATCH
 
 // the same for the reads of the most recent text chunk (which must not have been refused: gs_match_text_status)
-extern "C" int gs_match_segments_text(gs_run *run, uint64_t *seg_off) {
+extern "C" int gs_match_segments_text(gs_run *run, uint64_t *seg_off) try {
     if (!run || !seg_off) return fail(GS_E_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(run->db->device));
     seg_off[0] = 0;
@@ -4742,6 +4711,7 @@ extern "C" int gs_match_segments_text(gs_run *run, uint64_t *seg_off) {
     if (rc) return rc;
     return text_touched(run->text, run->stream);
 }
+GS_API_CATCH
 
 // newline offsets of the most recent text chunk (the record geometry for per-read writers); synchronises
 extern "C" int gs_match_text_read_bounds(gs_run *run, uint64_t *bounds) {
@@ -4749,14 +4719,14 @@ extern "C" int gs_match_text_read_bounds(gs_run *run, uint64_t *bounds) {
     HIP_TRY(hipSetDevice(run->db->device));
     const int rc = text_read_bounds(run->text, run->stream, bounds,
                                     "the last chunk was four-line FASTQ: its reads lie in the text (gs_match_text_newlines)");
-    return rc ? rc : collect_events(run);
+    return rc ? rc : timer_collect(run->timer);
 }
 
 extern "C" int gs_match_text_line_classes(gs_run *run, uint8_t *classes) {
     if (!run || !classes) return fail(GS_E_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(run->db->device));
     const int rc = text_line_classes(run->text, run->stream, classes);
-    return rc ? rc : collect_events(run);
+    return rc ? rc : timer_collect(run->timer);
 }
 
 extern "C" int gs_match_text_newlines(gs_run *run, uint32_t *newlines) {
@@ -4766,7 +4736,7 @@ extern "C" int gs_match_text_newlines(gs_run *run, uint32_t *newlines) {
     if (run->text.last_lines > 0)
         HIP_TRY(hipMemcpyAsync(newlines, run->text.d_nl, sizeof(uint32_t) * (size_t)run->text.last_lines, hipMemcpyDeviceToHost, run->stream));
     HIP_TRY(hipStreamSynchronize(run->stream));
-    return collect_events(run);
+    return timer_collect(run->timer);
 }
 
 extern "C" int gs_match_segments_fetch(gs_run *run, int32_t *codes, int32_t *starts) {
@@ -4865,10 +4835,10 @@ extern "C" int gs_match_kernel_time(gs_run *run, int64_t *launches, double *tota
     if (!run) return fail(GS_E_INVALID, "run is NULL");
     HIP_TRY(hipSetDevice(run->db->device));
     HIP_TRY(hipStreamSynchronize(run->stream));
-    int rc = collect_events(run);
+    int rc = timer_collect(run->timer);
     if (rc) return rc;
-    if (launches) *launches = run->launches;
-    if (total_ms) *total_ms = run->total_ms;
+    if (launches) *launches = run->timer.launches;
+    if (total_ms) *total_ms = run->timer.total_ms;
     return GS_OK;
 }
 
@@ -4885,14 +4855,9 @@ struct gs_bloom {
     int64_t *d_factors = nullptr;
     hipStream_t stream = nullptr;
     int n_cu = 256;
-    uint8_t *d_seq = nullptr;
-    uint64_t *d_off = nullptr;
-    uint8_t *d_accept = nullptr;
-    size_t seq_cap = 0, reads_cap = 0;
-    TextScan text;  // text mode (gs_filter_submit_text)
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
-    int64_t launches = 0;
-    double total_ms = 0;
+    HostStage host{false};  // host batches (GS_MEM_HOST); d_flags is accept, d_class stays empty
+    TextScan text;   // text mode (gs_filter_submit_text)
+    KernelTimer timer;
 };
 
 extern "C" int gs_bloom_create(gs_bloom **out, int device, int kind, int64_t bits, int32_t n_hashes,
@@ -4931,11 +4896,8 @@ extern "C" int gs_bloom_create(gs_bloom **out, int device, int kind, int64_t bit
     }
     *out = b;
     return GS_OK;
-} catch (const std::bad_alloc &) {
-    return fail(GS_E_NOMEM, "out of host memory");
-} catch (const std::exception &e) {  // (nothing may leave through the C ABI)
-    return fail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
 }
+GS_API_CATCH
 
 // java.util.Random (the hash factors of the reference's filters are its first nextLong() values for seed 42,
 // C/bloom/AbstractKMerBloomFilter.java:78,105-109)
@@ -5024,31 +4986,13 @@ extern "C" int gs_bloom_destroy(gs_bloom *b) {
     if (!b) return GS_OK;
     hipSetDevice(b->device);
     if (b->stream) hipStreamSynchronize(b->stream);
-    for (auto &p : b->pending) {
-        hipEventDestroy(p.first);
-        hipEventDestroy(p.second);
-    }
+    timer_free(b->timer);
     gs_dev_free(b->d_words);
     gs_dev_free(b->d_factors);
-    gs_dev_free(b->d_seq);
-    gs_dev_free(b->d_off);
-    gs_dev_free(b->d_accept);
+    stage_free(b->host);
     text_free(b->text);
     if (b->stream) hipStreamDestroy(b->stream);
     delete b;
-    return GS_OK;
-}
-
-static int bloom_collect(gs_bloom *b) {
-    for (auto &p : b->pending) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, p.first, p.second));
-        b->total_ms += ms;
-        b->launches++;
-        hipEventDestroy(p.first);
-        hipEventDestroy(p.second);
-    }
-    b->pending.clear();
     return GS_OK;
 }
 
@@ -5085,81 +5029,37 @@ static int filter_launch(gs_bloom *b, int k, int min_pos_count, double positive_
     }
     int grid = (int)std::min<int64_t>((int64_t)b->n_cu * occ, (n_reads + 3) / 4);
     if (grid < 1) grid = 1;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (profile) {
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, b->stream));
-    }
+    const int rc = timer_start(b->timer, profile != 0, b->stream);
+    if (rc) return rc;
     HIP_TRY(gs_launch_filter(&P, grid, b->stream));
-    if (profile) {
-        HIP_TRY(hipEventRecord(e1, b->stream));
-        b->pending.push_back({e0, e1});
-    }
-    return GS_OK;
+    return timer_stop(b->timer, profile != 0, b->stream);
 }
 
 extern "C" int gs_filter_submit(gs_bloom *b, int k, int min_pos_count, double positive_ratio, const uint8_t *seq,
-                                const uint64_t *offsets, int64_t n_reads, int mem, uint8_t *accept, int profile) {
+                                const uint64_t *offsets, int64_t n_reads, int mem, uint8_t *accept, int profile) try {
     if (!b) return fail(GS_E_INVALID, "bloom is NULL");
     if (k < 1 || k > 31) return fail(GS_E_INVALID, "k must be in [1,31]");
     if (n_reads < 0 || (n_reads > 0 && (!seq || !offsets || !accept))) return fail(GS_E_INVALID, "bad batch arrays");
     if (n_reads == 0) return GS_OK;
     HIP_TRY(hipSetDevice(b->device));
-    const uint8_t *d_seq = seq;
-    const uint64_t *d_off = offsets;
-    uint8_t *d_acc = accept;
-    std::vector<uint64_t> rel;
-    if (mem == GS_MEM_HOST) {
-        const size_t nbytes = (size_t)(offsets[n_reads] - offsets[0]);
-        if (b->seq_cap < nbytes + 1) {
-            HIP_TRY(hipStreamSynchronize(b->stream));
-            gs_dev_free(b->d_seq);
-            b->d_seq = nullptr;
-            b->seq_cap = 0;
-            HIP_TRY(gs_dev_alloc((void **)&b->d_seq, nbytes + 1));
-            b->seq_cap = nbytes + 1;
-        }
-        if (b->reads_cap < (size_t)n_reads) {
-            HIP_TRY(hipStreamSynchronize(b->stream));
-            gs_dev_free(b->d_off);
-            gs_dev_free(b->d_accept);
-            b->d_off = nullptr;
-            b->d_accept = nullptr;
-            b->reads_cap = 0;
-            HIP_TRY(gs_dev_alloc((void **)&b->d_off, sizeof(uint64_t) * ((size_t)n_reads + 1)));
-            HIP_TRY(gs_dev_alloc((void **)&b->d_accept, (size_t)n_reads));
-            b->reads_cap = (size_t)n_reads;
-        }
-        const uint64_t *hoff = offsets;
-        if (offsets[0] != 0) {
-            rel.resize((size_t)n_reads + 1);
-            for (int64_t i = 0; i <= n_reads; i++) rel[(size_t)i] = offsets[i] - offsets[0];
-            hoff = rel.data();
-        }
-        HIP_TRY(hipMemcpyAsync(b->d_seq, seq + offsets[0], nbytes, hipMemcpyHostToDevice, b->stream));
-        HIP_TRY(hipMemcpyAsync(b->d_off, hoff, sizeof(uint64_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice, b->stream));
-        d_seq = b->d_seq;
-        d_off = b->d_off;
-        d_acc = b->d_accept;
-    } else if (mem != GS_MEM_DEVICE)
-        return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
-
-    int rc = filter_launch(b, k, min_pos_count, positive_ratio, d_seq, d_off, n_reads, d_acc, 1, nullptr, profile);
+    if (mem == GS_MEM_DEVICE) return filter_launch(b, k, min_pos_count, positive_ratio, seq, offsets, n_reads, accept, 1, nullptr, profile);
+    if (mem != GS_MEM_HOST) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    HostStage &h = b->host;
+    int rc = stage_room(h, (size_t)(offsets[n_reads] - offsets[0]), (size_t)n_reads, b->stream);
+    if (!rc) rc = stage_upload(h, seq, offsets, n_reads, b->stream);
+    if (!rc) rc = filter_launch(b, k, min_pos_count, positive_ratio, h.d_seq, h.d_off, n_reads, h.d_flags, 1, nullptr, profile);
+    if (!rc) rc = stage_download(h, nullptr, accept, n_reads, b->stream);
     if (rc) return rc;
-    if (mem == GS_MEM_HOST) {
-        HIP_TRY(hipMemcpyAsync(accept, b->d_accept, (size_t)n_reads, hipMemcpyDeviceToHost, b->stream));
-        HIP_TRY(hipStreamSynchronize(b->stream));
-        return bloom_collect(b);
-    }
-    return GS_OK;
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return timer_collect(b->timer);
 }
+GS_API_CATCH
 
 extern "C" int gs_filter_sync(gs_bloom *b) {
     if (!b) return fail(GS_E_INVALID, "bloom is NULL");
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipStreamSynchronize(b->stream));
-    return bloom_collect(b);
+    return timer_collect(b->timer);
 }
 
 // ---- text mode of the filter (see gs_match_submit_text) ----
@@ -5170,62 +5070,48 @@ static int filter_submit_text(gs_bloom *b, int k, int min_pos_count, double posi
     if (k < 1 || k > 31) return fail(GS_E_INVALID, "k must be in [1,31]");
     if (n_lines > 0 && !accept) return fail(GS_E_INVALID, "accept is NULL");
     HIP_TRY(hipSetDevice(b->device));
-    const bool fasta = fasta_records >= 0 || ml_out != nullptr;  // the reads are gathered, not in place
-    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE && mem != GS_MEM_DEVICE_TEXT) return fail(GS_E_INVALID, "bad mem");
-    int rc = text_submit(b->text, b->stream, text, n_bytes, n_lines, mem == GS_MEM_HOST ? GS_MEM_HOST : GS_MEM_DEVICE, k, ticket, fasta_records, ml_out);
-    if (rc) return rc;
-    const int64_t n_reads = ml_out ? std::max<int64_t>(ml_out[0], 0) : (fasta ? fasta_records : (n_lines >> 2));
-    if (n_reads == 0) return GS_OK;
-    const bool dev_out = mem == GS_MEM_DEVICE;  // (GS_MEM_DEVICE_TEXT: the text is in HBM, accept / newlines are host arrays)
-    if (!dev_out && b->reads_cap < (size_t)n_reads) {
-        HIP_TRY(hipStreamSynchronize(b->stream));
-        gs_dev_free(b->d_off);
-        gs_dev_free(b->d_accept);
-        b->d_off = nullptr;
-        b->d_accept = nullptr;
-        b->reads_cap = 0;
-        HIP_TRY(gs_dev_alloc((void **)&b->d_off, sizeof(uint64_t) * ((size_t)n_reads + 1)));
-        HIP_TRY(gs_dev_alloc((void **)&b->d_accept, (size_t)n_reads));
-        b->reads_cap = (size_t)n_reads;
-    }
-    uint8_t *d_acc = dev_out ? accept : b->d_accept;
+    TextBatch tb;
+    int rc = text_batch(b->text, b->stream, text, n_bytes, n_lines, mem, k, ticket, fasta_records, ml_out, &tb);
+    if (rc || tb.n_reads == 0) return rc;
+    HostStage &h = b->host;
+    if (!tb.dev_out && (rc = stage_room_reads(h, (size_t)tb.n_reads, b->stream))) return rc;
+    uint8_t *d_acc = tb.dev_out ? accept : h.d_flags;
     // a refused chunk leaves `accept` untouched: zero it so that stale flags never look like results
-    HIP_TRY(hipMemsetAsync(d_acc, 0, (size_t)n_reads, b->stream));
-    rc = filter_launch(b, k, min_pos_count, positive_ratio, fasta ? b->text.d_fa_seq : b->text.d_text, (const uint64_t *)b->text.d_off2,
-                       n_reads, d_acc, fasta ? 1 : 2, b->text.d_status + (size_t)b->text.bank * GS_TS_WORDS + GS_TS_SKIP, profile);
+    HIP_TRY(hipMemsetAsync(d_acc, 0, (size_t)tb.n_reads, b->stream));
+    rc = filter_launch(b, k, min_pos_count, positive_ratio, tb.d_seq, (const uint64_t *)b->text.d_off2, tb.n_reads, d_acc, tb.off_stride, tb.d_skip, profile);
     if (rc) return rc;
     if ((rc = text_touched(b->text, b->stream))) return rc;
-    if (!fasta) b->text.d_last_flags = d_acc;
-    const hipMemcpyKind kind = dev_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (!dev_out) HIP_TRY(hipMemcpyAsync(accept, b->d_accept, (size_t)n_reads, kind, b->stream));
-    if (newlines) HIP_TRY(hipMemcpyAsync(newlines, b->text.d_nl, sizeof(uint32_t) * (size_t)n_lines, kind, b->stream));
+    if (!tb.fasta) b->text.d_last_flags = d_acc;
+    if (!tb.dev_out && (rc = stage_download(h, nullptr, accept, tb.n_reads, b->stream))) return rc;
+    if (newlines)
+        HIP_TRY(hipMemcpyAsync(newlines, b->text.d_nl, sizeof(uint32_t) * (size_t)n_lines, tb.dev_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, b->stream));
     return GS_OK;
 }
 
 extern "C" int gs_filter_submit_text(gs_bloom *b, int k, int min_pos_count, double positive_ratio, const uint8_t *text,
                                      int64_t n_bytes, int64_t n_lines, int mem, uint8_t *accept, uint32_t *newlines,
-                                     int profile, int64_t *ticket) {
+                                     int profile, int64_t *ticket) try {
     return filter_submit_text(b, k, min_pos_count, positive_ratio, text, n_bytes, n_lines, mem, accept, newlines, profile, ticket, -1, nullptr);
 }
+GS_API_CATCH
 
 extern "C" int gs_filter_submit_fasta(gs_bloom *b, int k, int min_pos_count, double positive_ratio, const uint8_t *text,
                                       int64_t n_bytes, int64_t n_lines, int64_t n_records, int mem, uint8_t *accept,
-                                      uint32_t *newlines, int64_t *ticket) {
+                                      uint32_t *newlines, int64_t *ticket) try {
     if (n_records < 0) return fail(GS_E_INVALID, "n_records < 0");
     return filter_submit_text(b, k, min_pos_count, positive_ratio, text, n_bytes, n_lines, mem, accept, newlines, 0, ticket, n_records, nullptr);
 }
+GS_API_CATCH
 
 extern "C" int gs_filter_submit_fastq_ml(gs_bloom *b, int k, int min_pos_count, double positive_ratio, const uint8_t *text,
                                          int64_t n_bytes, int64_t n_lines, int mem, uint8_t *accept, uint32_t *newlines,
-                                         int64_t *n_records, int64_t *consumed_bytes, int64_t *consumed_lines, int64_t *ticket) {
+                                         int64_t *n_records, int64_t *consumed_bytes, int64_t *consumed_lines, int64_t *ticket) try {
     if (!n_records || !consumed_bytes) return fail(GS_E_INVALID, "NULL argument");
     int64_t out[3] = {0, 0, 0};
     const int rc = filter_submit_text(b, k, min_pos_count, positive_ratio, text, n_bytes, n_lines, mem, accept, newlines, 0, ticket, -1, out);
-    *n_records = out[0];
-    *consumed_bytes = out[1];
-    if (consumed_lines) *consumed_lines = out[2];
-    return rc;
+    return ml_report(rc, out, n_records, consumed_bytes, consumed_lines);
 }
+GS_API_CATCH
 
 // nextEntry's rewriteInput on the device (FastqBloomFilter.java:92-105): the accepted (which != 0) or the other records of the last chunk
 extern "C" int gs_filter_compact_text(gs_bloom *b, int which, int with_probs, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_records) {
@@ -5238,14 +5124,14 @@ extern "C" int gs_filter_text_read_bounds(gs_bloom *b, uint64_t *bounds) {
     if (!b || !bounds) return fail(GS_E_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(b->device));
     const int rc = text_read_bounds(b->text, b->stream, bounds, "the last chunk was four-line FASTQ: its reads lie in the text (newlines)");
-    return rc ? rc : bloom_collect(b);
+    return rc ? rc : timer_collect(b->timer);
 }
 
 extern "C" int gs_filter_text_line_classes(gs_bloom *b, uint8_t *classes) {
     if (!b || !classes) return fail(GS_E_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(b->device));
     const int rc = text_line_classes(b->text, b->stream, classes);
-    return rc ? rc : bloom_collect(b);
+    return rc ? rc : timer_collect(b->timer);
 }
 
 extern "C" int gs_filter_get_device(gs_bloom *b, int *device) {
@@ -5265,7 +5151,7 @@ extern "C" int gs_filter_text_status(gs_bloom *b, int64_t *failed_ticket, int64_
     HIP_TRY(hipSetDevice(b->device));
     int rc = text_status(b->text, b->stream, failed_ticket, first_bad_record, totals);
     if (rc) return rc;
-    return bloom_collect(b);
+    return timer_collect(b->timer);
 }
 
 extern "C" int gs_filter_text_reset(gs_bloom *b, int clear_totals) {
@@ -5277,7 +5163,7 @@ extern "C" int gs_filter_text_reset(gs_bloom *b, int clear_totals) {
 extern "C" int gs_filter_kernel_time(gs_bloom *b, int64_t *launches, double *total_ms) {
     int rc = gs_filter_sync(b);
     if (rc) return rc;
-    if (launches) *launches = b->launches;
-    if (total_ms) *total_ms = b->total_ms;
+    if (launches) *launches = b->timer.launches;
+    if (total_ms) *total_ms = b->timer.total_ms;
     return GS_OK;
 }

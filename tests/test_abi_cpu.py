@@ -104,6 +104,16 @@ def test_launchers_and_parameter_blocks_are_declared_once():
     assert "hipHostMalloc(" in api and "gs_dev_alloc(" in api and "gs_dev_free(" in api
 
 
+def test_host_staging_timer_and_fence_are_written_once():
+    """gs_api.cpp holds one exception fence (the GS_API_CATCH macro), one rebase of a host batch's offsets (the staging type's
+    upload) and one read-out of a kernel timer's event pairs: plain text counts, so a pasted copy shows"""
+    api = open(os.path.join(ROOT, "genestrip_amd", "csrc", "gs_api.cpp"), errors="replace").read()
+    assert api.count("catch (const std::bad_alloc") == 1
+    assert api.count("#define GS_API_CATCH") == 1 and api.index("#define GS_API_CATCH") < api.index("catch (const std::bad_alloc")
+    assert api.count("offsets[i] - offsets[0]") == 1
+    assert api.count("hipEventElapsedTime(&ms, p.first, p.second)") == 1
+
+
 def test_synth_reads_deterministic_and_shaped():
     from genestrip_amd import synth
     db = synth.SynthDB(k=31, genera=2, species_per_genus=2, genome_len=5000, seed=7)
