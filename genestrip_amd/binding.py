@@ -50,6 +50,8 @@ ABI_SYMBOLS = (
     "gs_dbquality_destroy",
     "gs_dbupdate_begin", "gs_dbupdate_begin_db", "gs_dbupdate_begin_build", "gs_dbupdate_set_slice", "gs_dbupdate_add",
     "gs_dbupdate_finish", "gs_dbupdate_fetch", "gs_dbupdate_to_db", "gs_dbupdate_get_stats", "gs_dbupdate_destroy",
+    "gs_dbsize_begin", "gs_dbsize_set_range", "gs_dbsize_add", "gs_dbsize_counts", "gs_dbsize_distinct", "gs_dbsize_get_stats",
+    "gs_dbsize_destroy", "gs_dbsize_plan",
 )
 
 
@@ -152,6 +154,14 @@ def lib():
         "gs_dbupdate_to_db": (ci, [vp, vp]),
         "gs_dbupdate_get_stats": (ci, [vp, vp]),
         "gs_dbupdate_destroy": (ci, [vp]),
+        "gs_dbsize_begin": (ci, [vp, ci, ci, i32, ci, ci, ci, ci, ci, ci]),
+        "gs_dbsize_set_range": (ci, [vp, C.c_uint64, C.c_uint64]),
+        "gs_dbsize_add": (ci, [vp, vp, vp, vp, i64, ci]),
+        "gs_dbsize_counts": (ci, [vp, vp, vp, vp]),
+        "gs_dbsize_distinct": (ci, [vp, vp, vp]),
+        "gs_dbsize_get_stats": (ci, [vp, vp]),
+        "gs_dbsize_destroy": (ci, [vp]),
+        "gs_dbsize_plan": (ci, [vp, ci, ci, i64, vp, ci, vp]),
         "gs_match_encode": (ci, [vp, vp, vp, i64, vp, vp]), "gs_match_probe_keys": (ci, [vp, vp, i64, vp]),
         "gs_match_encode_route": (ci, [vp, vp, vp, i64, vp, ci, i64, vp, vp, vp, vp, vp]),
         "gs_match_route_geometry": (ci, [vp, i64, vp, vp]),
@@ -593,15 +603,36 @@ class DeviceKMerStore:
 
 def kmer_ranges(k, n):
     """n ranges [lo, hi) of the canonical k-mer with about equal shares of the k-mers (a canonical k-mer is the larger of
-    two strands: P(x <= t) ~ (t / 4^k)^2): for gs_dbbuild_set_range"""
+    two strands: P(x <= t) ~ (t / 4^k)^2): for gs_dbbuild_set_range.  This assumes k-mers spread evenly over the key space and
+    needs no pass over the data: good for a first cut or for random sequence.  Genomes are not like that (poly-A, repeats, GC
+    skew), and n itself is a guess: when the collection can be walked once first, prefer plan_ranges() over the histogram of a
+    DeviceDbSizer, which bounds every range by what it really holds."""
     import math
     top = 1 << (2 * k)
     cuts = [math.isqrt(top * top * i // n) for i in range(n)] + [top]
     return [(cuts[i], cuts[i + 1]) for i in range(n) if cuts[i] < cuts[i + 1]]
 
 
+def plan_ranges(hist, hist_bits, k, max_pairs):
+    """gs_dbsize_plan: the fewest ranges [lo, hi) of the canonical k-mer, cut at the bins of a DeviceDbSizer histogram, that
+    hold at most max_pairs k-mers each (max_pairs = the device memory granted / 40 for DeviceDbBuilder, / 24 for
+    DeviceDbQuality).  Histograms are additive: add those of fill and update regions first.  Needs no device.  A single bin above
+    max_pairs raises GsError (more hist_bits split it)."""
+    if not 1 <= k <= 31 or not 1 <= hist_bits <= 12:
+        raise ValueError("k must be in [1, 31] and hist_bits in [1, 12]")
+    bins = 1 << min(hist_bits, 2 * k)
+    h = np.ascontiguousarray(hist, dtype=np.int64)
+    if h.shape != (bins,):
+        raise ValueError(f"hist must have {bins} entries")
+    bounds = np.zeros(bins + 1, dtype=np.uint64)
+    n = C.c_int(0)
+    _check(lib().gs_dbsize_plan(h.ctypes.data_as(C.c_void_p), hist_bits, k, int(max_pairs), bounds.ctypes.data_as(C.c_void_p), bins,
+                                C.byref(n)))
+    return [(int(bounds[i]), int(bounds[i + 1])) for i in range(n.value)]
+
+
 def _region_args(seq, offsets, per_region, name):
-    """a batch of regions for gs_dbbuild_add / gs_dbquality_add / gs_dbupdate_add -> (seq pointer, offsets pointer, tags int32[n], n, mem)"""
+    """a batch of regions for gs_dbbuild_add / gs_dbquality_add / gs_dbupdate_add / gs_dbsize_add -> (seq pointer, offsets pointer, tags int32[n], n, mem)"""
     ps, mem = _ptr(seq)
     po, mem2 = _ptr(offsets)
     assert mem == mem2, "seq and offsets must live in the same memory space"
@@ -815,6 +846,78 @@ class DeviceDbUpdater:
     def close(self):
         if getattr(self, "h", None):
             lib().gs_dbupdate_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DbSizeTotals(C.Structure):
+    _fields_ = [("total", C.c_int64), ("dust", C.c_int64), ("included", C.c_int64)]
+
+
+class DbSizeStats(C.Structure):
+    _fields_ = [("n_bases", C.c_int64), ("n_regions", C.c_int64), ("n_keys", C.c_int64), ("n_distinct", C.c_int64),
+                ("bytes_fixed", C.c_int64), ("batch_bytes_peak", C.c_int64), ("bytes_peak", C.c_int64),
+                ("ms_add", C.c_double), ("ms_count", C.c_double), ("ms_sort", C.c_double), ("ms_heads", C.c_double),
+                ("n_values", C.c_int32), ("hist_bins", C.c_int32), ("radix_bits", C.c_int32), ("keep_keys", C.c_int32)]
+
+
+class DeviceDbSizer:
+    """gs_dbsize: a genome collection sized before it is built (the reference's fillsize and tempindex walks, FillSizeGoal +
+    FillBloomFilterGoal): k-mers with duplicates, those the DUST gate drops, those that remain, per tag and as a histogram of
+    the canonical k-mer's top bits (plan_ranges); with keep_keys the distinct k-mers, exactly, in total and per radix bucket.
+    K-mers are formed as in DeviceDbBuilder; the handle takes no tree, tags are plain indices in [0, n_values)."""
+
+    def __init__(self, k, n_values=1, device=0, lower_case_bases=True, max_dust=-1, step_size=1, hist_bits=12, radix_bits=0,
+                 keep_keys=False):
+        if not 1 <= hist_bits <= 12:
+            raise ValueError("hist_bits must be in [1, 12]")
+        if radix_bits != 0 and not 16 <= radix_bits <= 24:
+            raise ValueError("radix_bits must be 0 or in [16, 24]")
+        self.h = C.c_void_p()
+        self.k, self.n_values, self.hist_bits = k, n_values, hist_bits
+        self.radix_bits = radix_bits if keep_keys else 0
+        _check(lib().gs_dbsize_begin(C.byref(self.h), device, k, n_values, int(lower_case_bases), max_dust, step_size, hist_bits,
+                                     radix_bits, int(keep_keys)))
+
+    def set_range(self, lo, hi):
+        """retain only the canonical k-mers in [lo, hi) (the counts always cover every k-mer): before the first add, or after
+        counts() / distinct() to start the next pass on this handle with every counter at zero"""
+        _check(lib().gs_dbsize_set_range(self.h, lo, hi))
+
+    def add(self, seq, offsets, tag_vi):
+        """regions as for DeviceDbBuilder.add; tag_vi: numpy int32[n] in [0, n_values)"""
+        ps, po, tags, n, mem = _region_args(seq, offsets, tag_vi, "tag_vi")
+        _check(lib().gs_dbsize_add(self.h, ps, po, tags.ctypes.data_as(C.c_void_p), n, mem))
+
+    def counts(self):
+        """-> (DbSizeTotals: total, dust, included; per_value int64[n_values]; hist int64[1 << min(hist_bits, 2k)])"""
+        t = DbSizeTotals()
+        per_value = np.zeros(self.n_values, dtype=np.int64)
+        hist = np.zeros(1 << min(self.hist_bits, 2 * self.k), dtype=np.int64)
+        _check(lib().gs_dbsize_counts(self.h, C.byref(t), per_value.ctypes.data_as(C.c_void_p), hist.ctypes.data_as(C.c_void_p)))
+        return t, per_value, hist
+
+    def distinct(self):
+        """-> (number of distinct retained k-mers, bucket_sizes int64[1 << radix_bits] or None); releases the keys"""
+        n = C.c_int64(0)
+        buckets = np.zeros(1 << self.radix_bits, dtype=np.int64) if self.radix_bits else None
+        _check(lib().gs_dbsize_distinct(self.h, C.byref(n), None if buckets is None else buckets.ctypes.data_as(C.c_void_p)))
+        return n.value, buckets
+
+    def stats(self):
+        """sizes, device bytes and phase times (ms) of the pass"""
+        st = DbSizeStats()
+        _check(lib().gs_dbsize_get_stats(self.h, C.byref(st)))
+        return st
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().gs_dbsize_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -3508,7 +3508,7 @@ static int region_stage_open(RegionStage *s, int device, int k, int32_t n_values
     s->step = step;
     s->max_dust = max_dust < 0 ? -1 : max_dust;
     s->n_values = n_values;
-    s->parent.assign(parent_vi, parent_vi + n_values);
+    if (parent_vi) s->parent.assign(parent_vi, parent_vi + n_values);  // (gs_dbsize takes no tree)
     hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
     if (e == hipSuccess && depth) e = gs_dev_alloc((void **)&s->d_tree, sizeof(int32_t) * 2 * (size_t)n_values);
     if (e == hipSuccess && depth) e = hipMemcpy(s->d_tree, parent_vi, sizeof(int32_t) * (size_t)n_values, hipMemcpyHostToDevice);
@@ -4401,6 +4401,316 @@ extern "C" int gs_dbupdate_destroy(gs_dbupdate *u) {
     if (u) dbupdate_free(u);
     return GS_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------
+// A collection sized before it is built (gs_size.hip; include/gsgpu.h "gs_dbsize")
+// ---------------------------------------------------------------------------------------------------
+struct gs_dbsize : RegionStage {
+    int n_cu = 256;
+    int hb = 1, radix_bits = 0;  // hb = min(hist_bits, 2k)
+    bool keep = false;
+    u64 range_lo = 0, range_hi = ~0ULL;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    // the counter block: total, dust, included, keys retained, distinct; then per_value[n_values]; then hist[1 << hb]
+    u64 *d_cnt = nullptr;
+    size_t n_cnt = 0;
+    u64 *d_buckets = nullptr;  // 1 << radix_bits (a keeping handle with radix_bits > 0)
+    int32_t *d_tag = nullptr;
+    size_t tag_cap = 0;
+    u64 *d_keys = nullptr;  // the retained keys of this pass
+    size_t key_cap = 0, n_keys = 0;
+    int64_t n_adds = 0;      // of this pass
+    bool read = false;       // a counts / distinct since the last add: gs_dbsize_set_range may start the next pass
+    bool distinct_done = false;
+    bool failed = false;     // a device error in the middle of a call (sticky GS_E_STATE)
+    int64_t n_distinct = 0;
+    gs_dbsize_stats stats{};
+};
+enum { GS_SIZE_TOTALS = 0, GS_SIZE_NKEYS = 3, GS_SIZE_NDISTINCT = 4, GS_SIZE_HEAD = 5 };
+
+static void dbsize_free(gs_dbsize *s) {
+    region_stage_free(s, {s->d_cnt, s->d_buckets, s->d_tag, s->d_keys});
+    for (hipEvent_t e : s->ev)
+        if (e) hipEventDestroy(e);
+    delete s;
+}
+
+static const char *const DBSIZE_FAILED = "an earlier gs_dbsize call failed on the device: the counters are incomplete (start over)";
+
+// every counter of the pass back to zero
+static hipError_t dbsize_clear(gs_dbsize *s) {
+    hipError_t e = hipMemsetAsync(s->d_cnt, 0, s->n_cnt * sizeof(u64), s->stream);
+    if (e == hipSuccess && s->d_buckets) e = hipMemsetAsync(s->d_buckets, 0, sizeof(u64) << s->radix_bits, s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    return e;
+}
+
+static void dbsize_peak(gs_dbsize *s, size_t sort_bytes) {
+    s->stats.bytes_peak = std::max(s->stats.bytes_peak, (int64_t)(s->key_cap * sizeof(u64) + sort_bytes));
+}
+
+extern "C" int gs_dbsize_begin(gs_dbsize **out, int device, int k, int32_t n_values, int lower_case_bases, int max_dust, int step_size,
+                               int hist_bits, int radix_bits, int keep_keys) try {
+    if (!out) return fail(GS_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (k < 1 || k > 31) return fail(GS_E_INVALID, "k must be in [1,31]");
+    if (n_values < 1 || n_values > (1 << 24)) return fail(GS_E_INVALID, "n_values must be in [1, 2^24]");
+    // (no upper limit on max_dust here: a score can exceed Short.MAX_VALUE -- (AC)^15 A scores fib(29) -- and a sizing pass may
+    // ask what a gate at such a score would drop; the builder's begin refuses it with the reference)
+    int rc = region_scan_check(std::min(max_dust, 32767), step_size);
+    if (rc) return rc;
+    if (hist_bits < 1 || hist_bits > 12) return fail(GS_E_INVALID, "hist_bits must be in [1,12]");
+    if (radix_bits != 0 && (radix_bits < 16 || radix_bits > 24)) return fail(GS_E_INVALID, "radix_bits must be 0 or in [16,24] (GSConfigKey.RADIX_STORE_BITS)");
+    rc = use_device(device);
+    if (rc) return rc;
+    gs_dbsize *s = new gs_dbsize();
+    rc = region_stage_open(s, device, k, n_values, nullptr, nullptr, lower_case_bases, max_dust, step_size, "gs_dbsize");
+    int cu = 0;
+    if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) s->n_cu = cu;
+    s->hb = std::min(hist_bits, 2 * k);
+    s->keep = keep_keys != 0;
+    s->radix_bits = s->keep ? radix_bits : 0;
+    s->n_cnt = GS_SIZE_HEAD + (size_t)n_values + ((size_t)1 << s->hb);
+    if (!rc) {
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreate(&s->ev[i]);
+        if (e == hipSuccess) e = gs_dev_alloc(&s->d_cnt, s->n_cnt * sizeof(u64));
+        if (e == hipSuccess && s->radix_bits > 0) e = gs_dev_alloc(&s->d_buckets, sizeof(u64) << s->radix_bits);
+        if (e == hipSuccess) e = dbsize_clear(s);
+        if (e != hipSuccess) rc = hip_fail(e, "gs_dbsize_begin");
+    }
+    if (rc) {
+        dbsize_free(s);
+        return rc;
+    }
+    s->stats.bytes_fixed = (int64_t)(s->n_cnt * sizeof(u64) + (s->d_buckets ? sizeof(u64) << s->radix_bits : 0));
+    s->stats.n_values = n_values;
+    s->stats.hist_bins = 1 << s->hb;
+    s->stats.radix_bits = s->radix_bits;
+    s->stats.keep_keys = s->keep ? 1 : 0;
+    *out = s;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_dbsize_set_range(gs_dbsize *s, uint64_t lo, uint64_t hi) {
+    if (!s || lo >= hi) return fail(GS_E_INVALID, "bad range");
+    if (s->failed) return fail(GS_E_STATE, DBSIZE_FAILED);
+    if (s->n_adds > 0 && !s->read) return fail(GS_E_STATE, "gs_dbsize_set_range comes before the first gs_dbsize_add, or after gs_dbsize_counts / gs_dbsize_distinct");
+    if (s->n_adds > 0 || s->distinct_done) {  // the next pass
+        HIP_TRY(hipSetDevice(s->device));
+        const hipError_t e = dbsize_clear(s);
+        if (e != hipSuccess) {
+            s->failed = true;
+            return hip_fail(e, "gs_dbsize_set_range");
+        }
+        s->n_keys = 0;
+        s->n_adds = 0;
+        s->n_distinct = 0;
+        s->read = s->distinct_done = false;
+        s->stats.n_bases = s->stats.n_regions = s->stats.n_keys = s->stats.n_distinct = 0;
+        s->stats.ms_add = s->stats.ms_count = s->stats.ms_sort = s->stats.ms_heads = 0;
+    }
+    s->range_lo = lo;
+    s->range_hi = hi;
+    return GS_OK;
+}
+
+extern "C" int gs_dbsize_add(gs_dbsize *s, const uint8_t *seq, const uint64_t *offsets, const int32_t *tag_vi, int64_t n_regions, int mem) try {
+    if (!s || n_regions < 0 || (n_regions > 0 && (!seq || !offsets || !tag_vi))) return fail(GS_E_INVALID, "bad argument");
+    if (s->failed) return fail(GS_E_STATE, DBSIZE_FAILED);
+    if (s->distinct_done) return fail(GS_E_STATE, "gs_dbsize_distinct has released the keys of this pass: gs_dbsize_set_range starts the next one");
+    if (n_regions == 0) return GS_OK;
+    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    HIP_TRY(hipSetDevice(s->device));
+    for (int64_t r = 0; r < n_regions; r++)
+        if (tag_vi[r] < 0 || tag_vi[r] >= s->n_values) return fail(GS_E_INVALID, "tag_vi: not a value index");
+    std::vector<uint64_t> hoff;
+    int64_t total = 0;
+    int rc = region_batch_check(offsets, n_regions, mem, hoff, &total);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    // all of the call's memory before any of its work: an out-of-memory leaves the counters and the keys as they were
+    const uint8_t *d_seq = nullptr;
+    const u64 *d_off = nullptr;
+    {
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        hipError_t e = mem == GS_MEM_HOST ? dbupdate_room(&s->d_seq, &s->seq_cap, (size_t)std::max<int64_t>(total, 1)) : hipSuccess;
+        if (e == hipSuccess && mem == GS_MEM_HOST) e = dbupdate_room(&s->d_off, &s->off_cap, (size_t)n_regions + 1);
+        if (e == hipSuccess) e = dbupdate_room(&s->d_tag, &s->tag_cap, (size_t)n_regions);
+        if (e == hipSuccess && s->keep && s->n_keys + (size_t)total > s->key_cap) {
+            // a slot per position of the batch behind the keys so far; half again while the buffer grows call by call
+            const size_t want = std::max(s->n_keys + (size_t)total, s->n_keys ? s->key_cap + s->key_cap / 2 : 0);
+            u64 *nk = nullptr;
+            e = gs_dev_alloc(&nk, want * sizeof(u64));
+            if (e == hipSuccess && s->n_keys) e = hipMemcpyAsync(nk, s->d_keys, s->n_keys * sizeof(u64), hipMemcpyDeviceToDevice, s->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+            if (e == hipSuccess) {
+                gs_dev_free(s->d_keys);
+                s->d_keys = nk;
+                s->key_cap = want;
+            } else
+                gs_dev_free(nk);
+        }
+        if (e != hipSuccess) return hip_fail(e, "gs_dbsize_add");
+        const int64_t bytes = (int64_t)(s->seq_cap + s->off_cap * sizeof(u64) + s->tag_cap * sizeof(int32_t));
+        s->stats.batch_bytes_peak = std::max(s->stats.batch_bytes_peak, bytes);
+        dbsize_peak(s, 0);
+    }
+    GsSizeParams P{};
+    P.tag = s->d_tag;
+    P.n_regions = n_regions;
+    P.total = total;
+    P.k = s->k;
+    P.lower = s->lower;
+    P.step = s->step;
+    P.max_dust = s->max_dust;
+    P.hist_shift = 2 * s->k - s->hb;
+    P.hist_bins = 1 << s->hb;
+    P.range_lo = s->range_lo;
+    P.range_hi = s->range_hi;
+    P.totals = s->d_cnt + GS_SIZE_TOTALS;
+    P.per_value = s->d_cnt + GS_SIZE_HEAD;
+    P.hist = s->d_cnt + GS_SIZE_HEAD + s->n_values;
+    P.keys = s->keep ? s->d_keys : nullptr;
+    P.n_keys = s->d_cnt + GS_SIZE_NKEYS;
+    P.keys_cap = s->key_cap;
+    HipSteps check{"gs_dbsize_add"};
+    u64 have = 0;
+    rc = region_stage_upload(s, seq, offsets, n_regions, total, mem, &d_seq, &d_off);
+    P.seq = d_seq;
+    P.off = d_off;
+    const bool ok = !rc && check(hipMemcpyAsync(s->d_tag, tag_vi, sizeof(int32_t) * (size_t)n_regions, hipMemcpyHostToDevice, s->stream), "copy") &&
+                    check(hipEventRecord(s->ev[0], s->stream), "event") && check(gs_launch_size_count(&P, s->n_cu, s->stream), "count") &&
+                    check(hipEventRecord(s->ev[1], s->stream), "event") &&
+                    check(hipMemcpyAsync(&have, s->d_cnt + GS_SIZE_NKEYS, sizeof(u64), hipMemcpyDeviceToHost, s->stream), "counter") &&
+                    check(hipStreamSynchronize(s->stream), "count");  // (the caller's arrays and the staging buffers are free again)
+    if (!ok || have < s->n_keys || have > s->key_cap) {
+        s->failed = true;
+        return rc ? rc : check.rc != GS_OK ? check.rc : fail(GS_E_HIP, "gs_dbsize_add: key counter out of range");
+    }
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->stats.ms_count += ms;
+    s->n_keys = (size_t)have;
+    s->n_adds++;
+    s->read = false;
+    s->stats.n_bases += total;
+    s->stats.n_regions += n_regions;
+    s->stats.n_keys = (int64_t)s->n_keys;
+    s->stats.ms_add += ms_since(t0);
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_dbsize_counts(gs_dbsize *s, gs_dbsize_totals *t, int64_t *per_value, int64_t *hist) try {
+    if (!s || !t) return fail(GS_E_INVALID, "NULL argument");
+    if (s->failed) return fail(GS_E_STATE, DBSIZE_FAILED);
+    HIP_TRY(hipSetDevice(s->device));
+    std::vector<u64> h(s->n_cnt);
+    HIP_TRY(hipMemcpyAsync(h.data(), s->d_cnt, s->n_cnt * sizeof(u64), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    t->total = (int64_t)h[GS_SIZE_TOTALS];
+    t->dust = (int64_t)h[GS_SIZE_TOTALS + 1];
+    t->included = (int64_t)h[GS_SIZE_TOTALS + 2];
+    if (per_value) memcpy(per_value, h.data() + GS_SIZE_HEAD, sizeof(int64_t) * (size_t)s->n_values);
+    if (hist) memcpy(hist, h.data() + GS_SIZE_HEAD + s->n_values, sizeof(int64_t) << s->hb);
+    s->read = true;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_dbsize_distinct(gs_dbsize *s, int64_t *n_distinct, int64_t *bucket_sizes) try {
+    if (!s || !n_distinct) return fail(GS_E_INVALID, "NULL argument");
+    if (s->failed) return fail(GS_E_STATE, DBSIZE_FAILED);
+    if (!s->keep) return fail(GS_E_STATE, "this handle keeps no keys (gs_dbsize_begin with keep_keys = 0): it counts only");
+    if (s->radix_bits > 0 && !bucket_sizes) return fail(GS_E_INVALID, "NULL argument");
+    HIP_TRY(hipSetDevice(s->device));
+    if (!s->distinct_done) {
+        const int64_t n = (int64_t)s->n_keys;
+        region_stage_drop_staging(s);
+        gs_dev_free(s->d_tag);
+        s->d_tag = nullptr;
+        s->tag_cap = 0;
+        u64 *alt = nullptr, *sorted = nullptr, cnt = 0;
+        void *tmp = nullptr;
+        size_t tmp_bytes = 0;
+        HipSteps check{"gs_dbsize_distinct"};
+        auto t0 = std::chrono::steady_clock::now();
+        bool ok = true;
+        if (n > 0) {
+            ok = check(gs_size_sort_bytes(n, 2 * s->k, &tmp_bytes), "sort") && check(gs_dev_alloc(&alt, (size_t)n * sizeof(u64)), "sort buffers") &&
+                 check(gs_dev_alloc(&tmp, std::max<size_t>(tmp_bytes, 1)), "sort buffers");
+            if (ok) dbsize_peak(s, (size_t)n * sizeof(u64) + tmp_bytes);
+            ok = ok && check(gs_size_sort(s->d_keys, alt, n, 2 * s->k, tmp, tmp_bytes, &sorted, s->stream), "sort") &&
+                 check(hipStreamSynchronize(s->stream), "sort");
+            s->stats.ms_sort = ms_since(t0);
+            t0 = std::chrono::steady_clock::now();
+            ok = ok && check(gs_launch_size_heads(sorted, n, s->radix_bits, s->d_cnt + GS_SIZE_NDISTINCT, s->d_buckets, s->n_cu, s->stream), "heads");
+        }
+        ok = ok && check(hipMemcpyAsync(&cnt, s->d_cnt + GS_SIZE_NDISTINCT, sizeof(u64), hipMemcpyDeviceToHost, s->stream), "heads") &&
+             check(hipStreamSynchronize(s->stream), "heads");
+        s->stats.ms_heads = n > 0 ? ms_since(t0) : 0;
+        gs_dev_free(alt);
+        gs_dev_free(tmp);
+        gs_dev_free(s->d_keys);  // the retained keys go here
+        s->d_keys = nullptr;
+        s->key_cap = s->n_keys = 0;
+        if (!ok) {
+            s->failed = true;
+            return check.rc;
+        }
+        s->n_distinct = (int64_t)cnt;
+        s->stats.n_distinct = s->n_distinct;
+        s->distinct_done = true;
+    }
+    *n_distinct = s->n_distinct;
+    if (s->radix_bits > 0) HIP_TRY(hipMemcpy(bucket_sizes, s->d_buckets, sizeof(u64) << s->radix_bits, hipMemcpyDeviceToHost));
+    s->read = true;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_dbsize_get_stats(gs_dbsize *s, gs_dbsize_stats *out) {
+    if (!s || !out) return fail(GS_E_INVALID, "NULL argument");
+    *out = s->stats;
+    return GS_OK;
+}
+
+extern "C" int gs_dbsize_destroy(gs_dbsize *s) {
+    if (s) dbsize_free(s);
+    return GS_OK;
+}
+
+// host arithmetic only: maximal greedy runs of consecutive bins whose sum stays within max_pairs
+extern "C" int gs_dbsize_plan(const int64_t *hist, int hist_bits, int k, int64_t max_pairs, uint64_t *bounds, int cap, int *n_ranges) try {
+    if (!hist || !bounds || !n_ranges) return fail(GS_E_INVALID, "NULL argument");
+    *n_ranges = 0;
+    if (k < 1 || k > 31) return fail(GS_E_INVALID, "k must be in [1,31]");
+    if (hist_bits < 1 || hist_bits > 12) return fail(GS_E_INVALID, "hist_bits must be in [1,12]");
+    if (max_pairs < 1 || cap < 1) return fail(GS_E_INVALID, "max_pairs and cap must be >= 1");
+    const int hb = std::min(hist_bits, 2 * k), shift = 2 * k - hb;
+    const int64_t bins = (int64_t)1 << hb;
+    int n = 0;
+    int64_t sum = 0;
+    bounds[0] = 0;
+    for (int64_t b = 0; b < bins; b++) {
+        const int64_t h = hist[b];
+        if (h < 0) return fail(GS_E_INVALID, "gs_dbsize_plan: bin " + std::to_string(b) + " is negative");
+        if (h > max_pairs)
+            return fail(GS_E_INVALID, "gs_dbsize_plan: bin " + std::to_string(b) + " holds " + std::to_string(h) + " k-mers, more than max_pairs = " +
+                                          std::to_string(max_pairs) + ": no range of bins fits (more hist_bits split it)");
+        if (sum + h > max_pairs) {  // the run ends in front of this bin
+            if (n + 1 >= cap) return fail(GS_E_INVALID, "gs_dbsize_plan: more than cap = " + std::to_string(cap) + " ranges");
+            bounds[++n] = (uint64_t)b << shift;
+            sum = 0;
+        }
+        sum += h;
+    }
+    bounds[++n] = (uint64_t)1 << (2 * k);
+    *n_ranges = n;
+    return GS_OK;
+}
+GS_API_CATCH
 
 // ---- DB-partitioned mode: encode / probe / reduce as separate steps (all pointers are device pointers)
 extern "C" int gs_match_encode(gs_run *run, const uint8_t *seq, const uint64_t *offsets, int64_t n_reads,

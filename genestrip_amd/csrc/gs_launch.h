@@ -69,6 +69,22 @@ struct GsUpdateParams {
     u64 *stats;           // [0] += pairs, [1] += pairs whose k-mer is stored
 };
 
+struct GsSizeParams {
+    const uint8_t *seq;    // the batch: total bases in n_regions regions, off[n_regions + 1]
+    const u64 *off;
+    const int32_t *tag;    // value index of each region
+    int64_t n_regions, total;
+    int32_t k, lower, step, max_dust;
+    int32_t hist_shift, hist_bins;  // bin = canonical k-mer >> hist_shift, hist_bins <= 4096
+    u64 range_lo, range_hi;         // what is retained (keys != nullptr)
+    u64 *totals;           // [3]: total, dust, included
+    u64 *per_value;        // per value index
+    u64 *hist;             // hist_bins
+    u64 *keys;             // nullptr: count only
+    u64 *n_keys;           // keys retained so far
+    u64 keys_cap;          // room in keys
+};
+
 extern "C" {
 
 // ---- gs_kernels.hip
@@ -184,6 +200,12 @@ hipError_t gs_launch_update_check(const u64 *keys, const int32_t *vals, int64_t 
 hipError_t gs_launch_update_dir(const u64 *keys, int64_t m, int k, int dir_bits, int wide, void *dir, int n_cu, hipStream_t stream);
 hipError_t gs_launch_update_lookup(const GsUpdateParams *P, int64_t max_pairs, int n_cu, hipStream_t stream);
 hipError_t gs_launch_update_moved(const int32_t *vals, const int32_t *vals0, int64_t m, u64 *count, int n_cu, hipStream_t stream);
+
+// ---- gs_size.hip
+hipError_t gs_launch_size_count(const GsSizeParams *P, int n_cu, hipStream_t stream);
+hipError_t gs_size_sort_bytes(int64_t n, int key_bits, size_t *tmp_bytes);
+hipError_t gs_size_sort(u64 *keys, u64 *keys_alt, int64_t n, int key_bits, void *tmp, size_t tmp_bytes, u64 **keys_out, hipStream_t stream);
+hipError_t gs_launch_size_heads(const u64 *keys, int64_t n, int radix_bits, u64 *n_distinct, u64 *buckets, int n_cu, hipStream_t stream);
 
 }  // extern "C"
 

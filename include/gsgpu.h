@@ -506,6 +506,98 @@ int gs_dbupdate_get_stats(gs_dbupdate *u, gs_dbupdate_stats *out);
 int gs_dbupdate_destroy(gs_dbupdate *u);
 
 /* ---------------------------------------------------------------------------------------------------
+ * A genome collection sized before it is built (genestrip_amd/csrc/gs_size.hip): the two walks the reference makes in front of
+ * filldb, on the device.
+ *   fillsize   (C/goals/refseq/FillSizeGoal.java:80-105 over C/refseq/AbstractStoreFastaReader.java:87-115): the k-mers of the
+ *              collection with duplicates, how many of them the low-complexity gate drops (dustCounter), how many remain
+ *   tempindex  (C/goals/refseq/FillBloomFilterGoal.java:154-195, :260-271): the DISTINCT k-mers, in total and per radix bucket
+ *              (RadixKMerStore.radixOf = the low radixStoreBits bits); C/goals/refseq/FillDBGoal.java:107-117 sizes its store
+ *              from this DBSize
+ * and, for this library's own builder, a histogram of the canonical k-mer's top bits from which the passes of a build that does
+ * not fit the GPU are planned (the builder's set_range call, gs_dbsize_plan below) instead of guessed.
+ *
+ * K-mers are formed exactly as the builder's add call forms them (the "DB construction" section above; lower_case_bases /
+ * max_dust / step_size as for its begin).  For the bases b[0..len) of a region after the optional upper-casing, the window
+ * [s, s + k) counts iff all k bytes are C, G, A or T and (s + k) % step_size == 0.  For every counting window:
+ *   total += 1;
+ *   if max_dust >= 0 and the window's score exceeds it: dust += 1 and nothing else;
+ *   otherwise included += 1, per_value[tag of the region] += 1 and hist[canon >> (2k - hb)] += 1, canon = CGAT.standardKMer of the
+ *   window, hb = min(hist_bits, 2k); a handle that keeps keys retains canon as well if lo <= canon < hi.
+ * `included` is the number FillSizeGoal sets; total and dust are what it logs as the dust ratio.  Counts and histogram always
+ * cover the whole key space: the range restricts only what is retained.  All counters are 64-bit sums over the add calls of the
+ * current pass; they depend neither on how the collection is cut into batches nor on `mem`.
+ *
+ *   gs_dbsize_begin      n_values = number of tags (per_value's length; a caller without tax ids passes 1); the handle takes no
+ *                        tree.  max_dust has no upper limit here (the builder's begin refuses values above Short.MAX_VALUE
+ *                        with the reference; a score can exceed it -- (AC)^15 A scores fib(29) = 832040 -- and a sizing pass
+ *                        may ask what a gate at such a score would drop).  hist_bits 1 .. 12.  radix_bits 0 (no bucket sizes) or 16 .. 24 (GSConfigKey.RADIX_STORE_BITS).
+ *                        keep_keys = 0: the pure counting handle -- its device memory is the staged batch plus the counter
+ *                        block, and gs_dbsize_distinct answers GS_E_STATE.  Without a GPU: GS_E_NODEVICE.
+ *   gs_dbsize_add        regions as for the builder's add call (seq, offsets[n_regions + 1], `mem`); tag_vi[n_regions] (host) = a
+ *                        value index in [0, n_values) per region, anything else: GS_E_INVALID and nothing changes.  The memory
+ *                        of the call is allocated before any of its work: GS_E_NOMEM leaves the handle as it was.  Any other
+ *                        device error marks the handle failed: every later call but destroy is GS_E_STATE.
+ *   gs_dbsize_counts     t, per_value[n_values] and hist[1 << hb] (host; per_value and hist may be NULL) of the pass so far.
+ *   gs_dbsize_distinct   sorts the retained keys (rocPRIM radix sort over 2k bits) and counts the heads of runs into *n_distinct;
+ *                        each head adds one to bucket_sizes[key & (2^radix_bits - 1)] (host, 1 << radix_bits entries; ignored
+ *                        when radix_bits = 0).  Distinct counts and bucket sizes are additive over disjoint ranges.  The
+ *                        retained keys are released here; no add follows in this pass.
+ *   gs_dbsize_set_range  before the first add: the range [lo, hi) of the first pass.  After a counts or distinct call it starts the
+ *                        next pass on the same handle and clears every counter.  Any other order: GS_E_STATE.
+ *   gs_dbsize_get_stats  sizes and phase times of the pass (tools/db_size_rate.py).  bytes_peak is what the retained keys cost at
+ *                        the peak: 8 bytes per key slot (one slot per base of the batch being added, plus up to half again while
+ *                        the buffer grows over several add calls) + 8 bytes per retained key for the sort's second buffer + the
+ *                        sort's temporary storage -- 16 bytes per key when the pass is one add call, against the builder's 40.
+ *   gs_dbsize_plan       host arithmetic, needs no device: ranges for the set_range calls from a histogram.  bounds[0 .. *n_ranges]
+ *                        are bin boundaries, bounds[i] = bin << (2k - hb), bounds[0] = 0, bounds[*n_ranges] = 4^k, strictly
+ *                        increasing; range i is [bounds[i], bounds[i + 1]).  The ranges are maximal greedy runs of consecutive bins
+ *                        whose histogram sum is <= max_pairs (for a contiguous partition under a cap also the fewest); empty bins
+ *                        join a neighbour, an all-zero histogram gives one range.  A single bin above max_pairs: GS_E_INVALID,
+ *                        the message names the bin and its count (the cure is more hist_bits); more than `cap` ranges (bounds
+ *                        holds cap + 1 entries): GS_E_INVALID.  Histograms are additive: a caller who builds fill and update
+ *                        regions adds the two arrays before planning.  max_pairs = the device memory the caller grants / 40 for
+ *                        the builder, / 24 for the quality pass, / (bytes_peak per key) for the distinct pass.
+ *
+ * One difference to the reference: FillBloomFilterGoal counts a k-mer as new when its temporary Bloom filter does not hold it
+ * yet, and divides the result by (1 - tempBloomFilterFpp) to make up for false positives; which k-mers are miscounted depends
+ * on the order of its reader threads.  Here the count is exact (sort + heads of runs): it is the reference's DBSize(size,
+ * bucketSizes) at tempBloomFilterFpp -> 0, needs no correction, and is deterministic.  (Compare the quality section's note on
+ * its Bloom filter.)  maxKMersPerTaxid / maxGenomesPerTaxid stay the host's business, as in the builder: per_value is what that
+ * business needs.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct gs_dbsize gs_dbsize;
+typedef struct {
+    int64_t total;    /* counting windows                                        */
+    int64_t dust;     /* ... dropped by the low-complexity gate (dustCounter)    */
+    int64_t included; /* ... that remain: what FillSizeGoal sets                 */
+} gs_dbsize_totals;
+typedef struct {
+    int64_t n_bases;          /* bases handed in during this pass                                    */
+    int64_t n_regions;        /* regions handed in during this pass                                  */
+    int64_t n_keys;           /* keys retained in this pass                                          */
+    int64_t n_distinct;       /* distinct keys of this pass (after the distinct call)                */
+    int64_t bytes_fixed;      /* counter block + bucket array: lives as long as the handle           */
+    int64_t batch_bytes_peak; /* largest staged batch (bases, offsets, tags)                         */
+    int64_t bytes_peak;       /* largest footprint of the retained keys with their sort buffers      */
+    double ms_add;            /* add calls of this pass, wall clock (copy + kernel)                  */
+    double ms_count;          /* ... the counting kernel alone (device events)                       */
+    double ms_sort, ms_heads; /* the distinct call's phases                                          */
+    int32_t n_values;         /* entries of per_value                                                */
+    int32_t hist_bins;        /* entries of hist: 1 << min(hist_bits, 2k)                            */
+    int32_t radix_bits;       /* bucket_sizes holds 1 << radix_bits entries; 0: none                 */
+    int32_t keep_keys;
+} gs_dbsize_stats;
+int gs_dbsize_begin(gs_dbsize **out, int device, int k, int32_t n_values, int lower_case_bases, int max_dust, int step_size, int hist_bits,
+                    int radix_bits, int keep_keys);
+int gs_dbsize_set_range(gs_dbsize *s, uint64_t lo, uint64_t hi);
+int gs_dbsize_add(gs_dbsize *s, const uint8_t *seq, const uint64_t *offsets, const int32_t *tag_vi, int64_t n_regions, int mem);
+int gs_dbsize_counts(gs_dbsize *s, gs_dbsize_totals *t, int64_t *per_value, int64_t *hist);
+int gs_dbsize_distinct(gs_dbsize *s, int64_t *n_distinct, int64_t *bucket_sizes);
+int gs_dbsize_get_stats(gs_dbsize *s, gs_dbsize_stats *out);
+int gs_dbsize_destroy(gs_dbsize *s);
+int gs_dbsize_plan(const int64_t *hist, int hist_bits, int k, int64_t max_pairs, uint64_t *bounds, int cap, int *n_ranges);
+
+/* ---------------------------------------------------------------------------------------------------
  * DB-partitioned match, the split pipeline of round 1 (kept: it also serves stores without records): the store is split
  * over the GPUs of a node by key hash (gs_db_create_part keeps the keys with (h >> 40) % n_parts == part, h = the library's mixed key), reads stay
  * on their home GPU.  Per batch: gs_match_encode (reads -> h of every k-mer position; ~0 marks a window with a

@@ -212,6 +212,78 @@ JNIEXPORT jlong JNICALL JNAME(dbUpdateToDb)(JNIEnv *env, jclass c, jlong updater
 
 JNIEXPORT void JNICALL JNAME(dbUpdateDestroy)(JNIEnv *env, jclass c, jlong updater) { gs_dbupdate_destroy((gs_dbupdate *)(intptr_t)updater); }
 
+/* ---- a collection sized before it is built, the gs_dbsize family: FillSizeGoal + FillBloomFilterGoal.  Capacities as for the dbQuality natives: every direct
+ * buffer is checked against the element counts before the library reads or writes it. ---- */
+JNIEXPORT jlong JNICALL JNAME(dbSizeBegin)(JNIEnv *env, jclass c, jint device, jint k, jint nValues, jboolean lowerCaseBases, jint maxDust,
+                                           jint stepSize, jint histBits, jint radixBits, jboolean keepKeys) {
+    gs_dbsize *s = NULL;
+    int rc = gs_dbsize_begin(&s, device, k, nValues, lowerCaseBases ? 1 : 0, maxDust, stepSize, histBits, radixBits, keepKeys ? 1 : 0);
+    if (rc) throw_gs(env, rc);
+    return (jlong)(intptr_t)s;
+}
+
+JNIEXPORT void JNICALL JNAME(dbSizeSetRange)(JNIEnv *env, jclass c, jlong sizer, jlong lo, jlong hi) {
+    int rc = gs_dbsize_set_range((gs_dbsize *)(intptr_t)sizer, (uint64_t)lo, (uint64_t)hi);
+    if (rc) throw_gs(env, rc);
+}
+
+JNIEXPORT void JNICALL JNAME(dbSizeAdd0)(JNIEnv *env, jclass c, jlong sizer, jobject bases, jlong basesCap, jobject offsets, jlong offsetsCap,
+                                         jobject tagVi, jlong tagViCap, jlong nRegions) {
+    const uint64_t *off = (const uint64_t *)addr(env, offsets);
+    if (nRegions < 0 || nRegions > (INT64_MAX >> 4)) return throw_short(env, "nRegions");
+    if (nRegions > 0) {
+        if (!off || offsetsCap < 8 * (nRegions + 1)) return throw_short(env, "offsets (nRegions + 1 x int64)");
+        if (!addr(env, tagVi) || tagViCap < 4 * nRegions) return throw_short(env, "tagVi (nRegions x int32)");
+        if (!addr(env, bases) || basesCap < 0 || off[nRegions] > (uint64_t)basesCap) return throw_short(env, "bases (offsets[nRegions] bytes)");
+    }
+    int rc = gs_dbsize_add((gs_dbsize *)(intptr_t)sizer, (const uint8_t *)addr(env, bases), off, (const int32_t *)addr(env, tagVi), nRegions,
+                           GS_MEM_HOST);
+    if (rc) throw_gs(env, rc);
+}
+
+/* totals: total, dust, included (3 x int64); perValue: nValues x int64; hist: 2^min(histBits, 2k) x int64 -- the sizes the handle was opened with */
+JNIEXPORT void JNICALL JNAME(dbSizeCounts0)(JNIEnv *env, jclass c, jlong sizer, jobject totals, jlong totalsCap, jobject perValue, jlong perValueCap,
+                                            jobject hist, jlong histCap) {
+    gs_dbsize_totals t;
+    gs_dbsize_stats st;
+    int rc = gs_dbsize_get_stats((gs_dbsize *)(intptr_t)sizer, &st);
+    if (rc) return throw_gs(env, rc);
+    if (!addr(env, totals) || totalsCap < 24) return throw_short(env, "totals (3 x int64)");
+    if (!addr(env, perValue) || perValueCap < 8 * (jlong)st.n_values) return throw_short(env, "perValue (nValues x int64)");
+    if (!addr(env, hist) || histCap < 8 * (jlong)st.hist_bins) return throw_short(env, "hist (2^min(histBits, 2k) x int64)");
+    rc = gs_dbsize_counts((gs_dbsize *)(intptr_t)sizer, &t, (int64_t *)addr(env, perValue), (int64_t *)addr(env, hist));
+    if (rc) return throw_gs(env, rc);
+    memcpy(addr(env, totals), &t, sizeof(t));
+}
+
+/* bucketSizes: 2^radixBits x int64 (null for a handle opened with radixBits 0); returns the number of distinct k-mers */
+JNIEXPORT jlong JNICALL JNAME(dbSizeDistinct0)(JNIEnv *env, jclass c, jlong sizer, jobject bucketSizes, jlong bucketSizesCap) {
+    int64_t n = 0;
+    gs_dbsize_stats st;
+    int rc = gs_dbsize_get_stats((gs_dbsize *)(intptr_t)sizer, &st);
+    if (rc) return throw_gs(env, rc), 0;
+    if (st.radix_bits > 0 && (!addr(env, bucketSizes) || bucketSizesCap < ((jlong)8 << st.radix_bits)))
+        return throw_short(env, "bucketSizes (2^radixBits x int64)"), 0;
+    rc = gs_dbsize_distinct((gs_dbsize *)(intptr_t)sizer, &n, st.radix_bits > 0 ? (int64_t *)addr(env, bucketSizes) : NULL);
+    if (rc) return throw_gs(env, rc), 0;
+    return (jlong)n;
+}
+
+/* hist: 2^min(histBits, 2k) x int64; bounds: room for cap + 1 x int64; returns the number of ranges */
+JNIEXPORT jint JNICALL JNAME(dbSizePlan0)(JNIEnv *env, jclass c, jobject hist, jlong histCap, jint histBits, jint k, jlong maxPairs, jobject bounds,
+                                          jlong boundsCap, jint cap) {
+    int n = 0;
+    const int hb = histBits < 2 * k ? histBits : 2 * k;
+    if (histBits < 1 || histBits > 12 || k < 1 || k > 31) return throw_short(env, "histBits / k"), 0;
+    if (!addr(env, hist) || histCap < ((jlong)8 << hb)) return throw_short(env, "hist (2^min(histBits, 2k) x int64)"), 0;
+    if (cap < 1 || !addr(env, bounds) || boundsCap < 8 * ((jlong)cap + 1)) return throw_short(env, "bounds (cap + 1 x int64)"), 0;
+    int rc = gs_dbsize_plan((const int64_t *)addr(env, hist), histBits, k, maxPairs, (uint64_t *)addr(env, bounds), cap, &n);
+    if (rc) return throw_gs(env, rc), 0;
+    return n;
+}
+
+JNIEXPORT void JNICALL JNAME(dbSizeDestroy)(JNIEnv *env, jclass c, jlong sizer) { gs_dbsize_destroy((gs_dbsize *)(intptr_t)sizer); }
+
 JNIEXPORT void JNICALL JNAME(dbDestroy)(JNIEnv *env, jclass c, jlong db) { gs_db_destroy((gs_db *)(intptr_t)db); }
 
 JNIEXPORT void JNICALL JNAME(dbSave)(JNIEnv *env, jclass c, jlong db, jstring path) {

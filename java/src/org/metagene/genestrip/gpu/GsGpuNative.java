@@ -124,6 +124,52 @@ public final class GsGpuNative {
 
 	private static native void dbUpdateFetch0(long updater, ByteBuffer kmers, long kmersCap, ByteBuffer valueIdx, long valueIdxCap);
 
+	/** gs_dbsize_begin: a collection sized before it is built (FillSizeGoal + FillBloomFilterGoal on the device): nValues tags,
+	 * no tree; histBits 1 .. 12; radixBits 0 or GSConfigKey.RADIX_STORE_BITS; keepKeys false: counts only (no dbSizeDistinct) */
+	public static native long dbSizeBegin(int device, int k, int nValues, boolean lowerCaseBases, int maxDust, int stepSize, int histBits,
+			int radixBits, boolean keepKeys);
+
+	/** gs_dbsize_set_range: only the canonical k-mers in [lo, hi) are retained; after dbSizeCounts / dbSizeDistinct it starts the
+	 * next pass with every counter at zero */
+	public static native void dbSizeSetRange(long sizer, long lo, long hi);
+
+	/** gs_dbsize_add: regions as for dbBuildAdd; tagVi = nRegions x int32 in [0, nValues).  Direct buffers in native order; a
+	 * buffer shorter than its element count: IllegalArgumentException. */
+	public static void dbSizeAdd(long sizer, ByteBuffer bases, ByteBuffer offsets, ByteBuffer tagVi, long nRegions) {
+		dbSizeAdd0(sizer, bases, bases.capacity(), offsets, offsets.capacity(), tagVi, tagVi.capacity(), nRegions);
+	}
+
+	/** gs_dbsize_counts: totals = 3 x int64 (k-mers with duplicates, dropped by the dust gate, included: what FillSizeGoal sets),
+	 * perValue = nValues x int64, hist = 2^min(histBits, 2k) x int64, with nValues and histBits as given to dbSizeBegin */
+	public static void dbSizeCounts(long sizer, ByteBuffer totals, ByteBuffer perValue, ByteBuffer hist) {
+		dbSizeCounts0(sizer, totals, totals.capacity(), perValue, perValue.capacity(), hist, hist.capacity());
+	}
+
+	/** gs_dbsize_distinct: returns the number of distinct retained k-mers; bucketSizes = 2^radixBits x int64 (null with
+	 * radixBits 0): FillBloomFilterGoal's DBSize(size, bucketSizes), exact */
+	public static long dbSizeDistinct(long sizer, ByteBuffer bucketSizes) {
+		return dbSizeDistinct0(sizer, bucketSizes, bucketSizes == null ? 0 : bucketSizes.capacity());
+	}
+
+	/** gs_dbsize_plan: ranges of the canonical k-mer that hold at most maxPairs k-mers each, from a dbSizeCounts histogram;
+	 * bounds = room for cap + 1 x int64, range i is [bounds[i], bounds[i + 1]); returns the number of ranges.  Needs no device. */
+	public static int dbSizePlan(ByteBuffer hist, int histBits, int k, long maxPairs, ByteBuffer bounds, int cap) {
+		return dbSizePlan0(hist, hist.capacity(), histBits, k, maxPairs, bounds, bounds.capacity(), cap);
+	}
+
+	public static native void dbSizeDestroy(long sizer);
+
+	private static native void dbSizeAdd0(long sizer, ByteBuffer bases, long basesCap, ByteBuffer offsets, long offsetsCap,
+			ByteBuffer tagVi, long tagViCap, long nRegions);
+
+	private static native void dbSizeCounts0(long sizer, ByteBuffer totals, long totalsCap, ByteBuffer perValue, long perValueCap,
+			ByteBuffer hist, long histCap);
+
+	private static native long dbSizeDistinct0(long sizer, ByteBuffer bucketSizes, long bucketSizesCap);
+
+	private static native int dbSizePlan0(ByteBuffer hist, long histCap, int histBits, int k, long maxPairs, ByteBuffer bounds,
+			long boundsCap, int cap);
+
 	/** gs_db_save / gs_db_load: the native image of the device store */
 	public static native void dbSave(long db, String path);
 

@@ -24,6 +24,7 @@ import org.metagene.genestrip.tax.TaxTree.TaxIdNode;
 public class GpuStoreFastaReader extends AbstractRefSeqFastaReader {
 	private final long builder;
 	private long updater;
+	private long sizer;
 	private final boolean update;
 	private final boolean allRegions;
 	private final Map<TaxIdNode, Integer> valueIndexOfNode;
@@ -71,6 +72,21 @@ public class GpuStoreFastaReader extends AbstractRefSeqFastaReader {
 				accessionMap, k, maxGenomesPerTaxId, maxGenomesPerTaxIdRank, maxKmersPerTaxId, stepSize, completeGenomesOnly,
 				regionsPerTaxid);
 		reader.updater = updater;
+		return reader;
+	}
+
+	/**
+	 * The sizing walks in front of the fill pass (FillSizeGoal, FillBloomFilterGoal): the regions of the requested taxa go to a
+	 * sizer handle (GsGpuNative.dbSizeBegin) in place of a builder handle, tagged with their node's value index; the goal reads
+	 * GsGpuNative.dbSizeCounts / dbSizeDistinct after the last file.  The reader is one with update = false.
+	 */
+	public static GpuStoreFastaReader forSizer(long sizer, Map<TaxIdNode, Integer> valueIndexOfNode, int batchBytes, int bufferSize,
+			Set<TaxIdNode> taxNodes, AccessionMap accessionMap, int k, int maxGenomesPerTaxId, Rank maxGenomesPerTaxIdRank,
+			long maxKmersPerTaxId, int stepSize, boolean completeGenomesOnly, StringLong2DigitTrie regionsPerTaxid) {
+		GpuStoreFastaReader reader = new GpuStoreFastaReader(0L, false, false, valueIndexOfNode, batchBytes, bufferSize, taxNodes,
+				accessionMap, k, maxGenomesPerTaxId, maxGenomesPerTaxIdRank, maxKmersPerTaxId, stepSize, completeGenomesOnly,
+				regionsPerTaxid);
+		reader.sizer = sizer;
 		return reader;
 	}
 
@@ -135,7 +151,9 @@ public class GpuStoreFastaReader extends AbstractRefSeqFastaReader {
 	/** hands the collected regions to the device (also called by the goal after the last file of a pass) */
 	public void flush() {
 		if (regions > 0) {
-			if (updater != 0L) {
+			if (sizer != 0L) {
+				GsGpuNative.dbSizeAdd(sizer, bases, offsets, nodes, regions);
+			} else if (updater != 0L) {
 				GsGpuNative.dbUpdateAdd(updater, bases, offsets, nodes, regions);
 			} else {
 				GsGpuNative.dbBuildAdd(builder, bases, offsets, nodes, regions, update);
