@@ -52,6 +52,10 @@ ABI_SYMBOLS = (
     "gs_dbupdate_finish", "gs_dbupdate_fetch", "gs_dbupdate_to_db", "gs_dbupdate_get_stats", "gs_dbupdate_destroy",
     "gs_dbsize_begin", "gs_dbsize_set_range", "gs_dbsize_add", "gs_dbsize_counts", "gs_dbsize_distinct", "gs_dbsize_get_stats",
     "gs_dbsize_destroy", "gs_dbsize_plan",
+    "gs_reads_create", "gs_reads_destroy", "gs_reads_get_device", "gs_reads_sync", "gs_reads_select_text", "gs_reads_select_fasta",
+    "gs_reads_select_fastq_ml", "gs_reads_compact_text", "gs_reads_fasta2fastq", "gs_reads_text_read_bounds", "gs_reads_text_line_classes",
+    "gs_reads_text_wait_copy", "gs_reads_text_status", "gs_reads_text_reset", "gs_reads_kernel_time",
+    "gs_reads_phase_times",
 )
 
 
@@ -235,6 +239,15 @@ def lib():
         "gs_dbexport_fastq_begin": (ci, [vp, vp, C.c_char_p]),
         "gs_dbexport_fastq_next": (ci, [vp, vp, vp, vp]),
         "gs_dbexport_destroy": (ci, [vp]),
+        "gs_reads_create": (ci, [vp, ci]), "gs_reads_destroy": (ci, [vp]), "gs_reads_get_device": (ci, [vp, vp]), "gs_reads_sync": (ci, [vp]),
+        "gs_reads_select_text": (ci, [vp, ci, vp, i64, i64, ci, vp, i32, vp, vp, vp]),
+        "gs_reads_select_fasta": (ci, [vp, ci, vp, i64, i64, i64, ci, vp, i32, vp, vp, vp]),
+        "gs_reads_select_fastq_ml": (ci, [vp, ci, vp, i64, i64, ci, vp, i32, vp, vp, vp, vp, vp, vp]),
+        "gs_reads_compact_text": (ci, [vp, ci, ci, vp, vp, vp]),
+        "gs_reads_fasta2fastq": (ci, [vp, vp, i64, i64, i64, ci, ci, vp, vp, vp, vp]),
+        "gs_reads_text_read_bounds": (ci, [vp, vp]), "gs_reads_text_line_classes": (ci, [vp, vp]),
+        "gs_reads_text_wait_copy": (ci, [vp, i64]), "gs_reads_text_status": (ci, [vp, vp, vp, vp]), "gs_reads_text_reset": (ci, [vp, ci]),
+        "gs_reads_kernel_time": (ci, [vp, ci, vp, vp]), "gs_reads_phase_times": (ci, [vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1362,3 +1375,99 @@ class FastqBloomFilter:
         n, ms = C.c_int64(0), C.c_double(0)
         _check(lib().gs_filter_kernel_time(self.bloom.h, C.byref(n), C.byref(ms)))
         return n.value, ms.value
+
+
+def _text_counts(text):
+    """(uint8 array, newlines, header lines) of a chunk of text"""
+    t = np.frombuffer(bytes(text), dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
+    if t.shape[0] == 0:
+        return np.zeros(1, dtype=np.uint8), 0, 0, 0
+    return t, int(t.shape[0]), int((t == 10).sum()), int(np.count_nonzero((t == 62) & np.concatenate(([True], t[:-1] == 10))))
+
+
+class DeviceReads:
+    """gs_reads: the text stage without a store or a filter -- the extract goal's selection by descriptor prefix and the
+    fasta2fastq goal's text, both on the device"""
+
+    def __init__(self, device=0, k=31):
+        self.h = C.c_void_p()
+        self.device, self.k = int(device), int(k)
+        _check(lib().gs_reads_create(C.byref(self.h), self.device))
+
+    def close(self):
+        if self.h:
+            lib().gs_reads_destroy(self.h)
+            self.h = C.c_void_p()
+
+    __del__ = close
+
+    @staticmethod
+    def _key(key):
+        key = bytes(key)
+        return np.frombuffer(key, dtype=np.uint8) if key else np.zeros(1, dtype=np.uint8), len(key)
+
+    def select_text(self, text, key):
+        """four-line FASTQ text of whole records -> accept flag per record"""
+        t, nb, nl, _ = _text_counts(text)
+        kb, kl = self._key(key)
+        acc = np.zeros(max(nl // 4, 1), dtype=np.uint8)
+        _check(lib().gs_reads_select_text(self.h, self.k, _ptr(t)[0], nb, nl, MEM_HOST, _ptr(kb)[0], kl, _ptr(acc)[0], None, None))
+        _check(lib().gs_reads_sync(self.h))
+        return acc[:nl // 4]
+
+    def select_fasta(self, text, key):
+        """FASTA text of whole records -> accept flag per record"""
+        t, nb, nl, nr = _text_counts(text)
+        kb, kl = self._key(key)
+        acc = np.zeros(max(nr, 1), dtype=np.uint8)
+        _check(lib().gs_reads_select_fasta(self.h, self.k, _ptr(t)[0], nb, nl, nr, MEM_HOST, _ptr(kb)[0], kl, _ptr(acc)[0], None, None))
+        _check(lib().gs_reads_sync(self.h))
+        return acc[:nr]
+
+    def select_fastq_ml(self, text, key):
+        """general FASTQ text starting at a descriptor line -> (records or -1 when refused, bytes they cover, accept flags)"""
+        t, nb, nl, _ = _text_counts(text)
+        kb, kl = self._key(key)
+        acc = np.zeros(nl // 4 + 2, dtype=np.uint8)
+        n_rec, used = C.c_int64(0), C.c_int64(0)
+        _check(lib().gs_reads_select_fastq_ml(self.h, self.k, _ptr(t)[0], nb, nl, MEM_HOST, _ptr(kb)[0], kl, _ptr(acc)[0], None, C.byref(n_rec),
+                                              C.byref(used), None, None))
+        _check(lib().gs_reads_sync(self.h))
+        return n_rec.value, used.value, acc[:max(n_rec.value, 0)]
+
+    def compact_text(self, with_probs=True, slot=0):
+        """the selected records of the last four-line or FASTA chunk as ReadEntry.write writes them -> (bytes, records)"""
+        p, nb, nr = C.c_void_p(), C.c_int64(0), C.c_int64(0)
+        _check(lib().gs_reads_compact_text(self.h, int(with_probs), int(slot), C.byref(p), C.byref(nb), C.byref(nr)))
+        return _fetch_device(self.device, p, nb.value), nr.value
+
+    def fasta2fastq(self, text, n_lines=None, n_records=None, slot=0):
+        """the fasta2fastq goal's text of a FASTA chunk -> (bytes as numpy uint8, lines of 65 534 bytes and more); a refused chunk
+        gives no bytes and shows in text_status()"""
+        t, nb, nl, nr = _text_counts(text)
+        p, n_out, long_lines = C.c_void_p(), C.c_int64(0), C.c_int64(0)
+        _check(lib().gs_reads_fasta2fastq(self.h, _ptr(t)[0], nb, nl if n_lines is None else int(n_lines), nr if n_records is None else int(n_records),
+                                          MEM_HOST, int(slot), C.byref(p), C.byref(n_out), C.byref(long_lines), None))
+        return _fetch_device(self.device, p, n_out.value), long_lines.value
+
+    def text_status(self):
+        ft, fb = C.c_int64(-1), C.c_int64(-1)
+        tot = (C.c_int64 * 3)()
+        _check(lib().gs_reads_text_status(self.h, C.byref(ft), C.byref(fb), tot))
+        return ft.value, fb.value, tuple(tot)
+
+    def text_reset(self, clear_totals=False):
+        _check(lib().gs_reads_text_reset(self.h, int(clear_totals)))
+
+    def kernel_time(self, profile=True):
+        """(launches, milliseconds) of the FASTA -> FASTQ text kernels so far; switches their timing on or off"""
+        n, ms = C.c_int64(0), C.c_double(0)
+        _check(lib().gs_reads_kernel_time(self.h, int(profile), C.byref(n), C.byref(ms)))
+        return n.value, ms.value
+
+    def phase_times(self):
+        """{phase: (launches, milliseconds)} of a profiling handle so far: "select" (a chunk from its submission to its flags),
+        "gather" (the four-line gather of compact_text), "rewrite" (the FASTA -> FASTQ text kernels, as kernel_time)"""
+        n, ms = (C.c_int64 * 3)(), (C.c_double * 3)()
+        _check(lib().gs_reads_phase_times(self.h, n, ms))
+        return {name: (n[i], ms[i]) for i, name in enumerate(("select", "gather", "rewrite"))}

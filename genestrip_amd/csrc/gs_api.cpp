@@ -2331,8 +2331,10 @@ static int text_reset(TextScan &t, bool totals, hipStream_t stream, bool all = f
 // fasta_records < 0: four-line FASTQ; >= 0: FASTA with that many header lines (gs_text.hip)
 // ml_out != nullptr: general FASTQ -- the record structure is found on the device first (this call then waits for it) and
 // ml_out[0] = complete records (-1: the chunk was refused), ml_out[1] = bytes, ml_out[2] = lines they cover
+// goal != nullptr (fasta2fastq, with fasta_records): only the newlines are found here, the lines are read under the goal's own
+// rule (gs_rewrite.hip, goal mode) -- the shared fields of *goal are filled in -- and the chunk is committed
 static int text_submit(TextScan &t, hipStream_t stream, const uint8_t *text, int64_t n_bytes, int64_t n_lines, int mem, int k,
-                       int64_t *ticket, int64_t fasta_records = -1, int64_t *ml_out = nullptr) {
+                       int64_t *ticket, int64_t fasta_records = -1, int64_t *ml_out = nullptr, GsRewriteParams *goal = nullptr) {
     const bool ml = ml_out != nullptr;
     const bool fasta = fasta_records >= 0 || ml;
     if (ml) {
@@ -2446,7 +2448,23 @@ static int text_submit(TextScan &t, hipStream_t stream, const uint8_t *text, int
         T.line_class = t.d_ml_class;
         n_lines = lines_done;
     }
-    HIP_TRY(gs_launch_text_scan(&T, (uint32_t)tk, stream));
+    if (goal) {
+        goal->text = T.text;
+        goal->nl = T.nl;
+        goal->fa_scan = T.fa_scan;
+        goal->fa_block = T.fa_block;
+        goal->line_dst = T.line_dst;
+        goal->fa_seq = T.fa_seq;
+        goal->off2 = T.off2;
+        goal->status = T.status;
+        goal->gate = T.status + GS_TS_CHUNK_ERR;
+        HIP_TRY(gs_launch_text_lines(&T, stream));
+        HIP_TRY(gs_launch_rewrite_lines(goal, stream));
+        HIP_TRY(gs_launch_text_commit(&T, (uint32_t)tk, stream));
+        goal->gate = T.status + GS_TS_SKIP;
+    } else {
+        HIP_TRY(gs_launch_text_scan(&T, (uint32_t)tk, stream));
+    }
     HIP_TRY(hipEventRecord(t.done[b], stream));
     t.done_valid[b] = true;
     t.tickets = tk + 1;
@@ -5476,4 +5494,331 @@ extern "C" int gs_filter_kernel_time(gs_bloom *b, int64_t *launches, double *tot
     if (launches) *launches = b->timer.launches;
     if (total_ms) *total_ms = b->timer.total_ms;
     return GS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// reads: the text stage without a store or a filter -- extract and fasta2fastq (gs_rewrite.hip)
+// ---------------------------------------------------------------------------------------------------
+struct gs_reads {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int n_cu = 256;
+    TextScan text;
+    uint8_t *d_accept = nullptr, *d_key = nullptr;  // the flags of a chunk whose caller wants them in host memory; the key
+    size_t accept_cap = 0, key_cap = 0;
+    std::string key;  // what d_key holds: the caller's key is copied here first, so its memory is free again when a select call returns
+    uint32_t *d_rec_line = nullptr, *d_piece = nullptr;
+    u64 *d_rec_out = nullptr, *d_rec_block = nullptr;
+    size_t rec_line_cap = 0, piece_cap = 0, rec_out_cap = 0, rec_block_cap = 0;
+    u64 *d_tot = nullptr, *h_tot = nullptr;  // GsRewriteParams::totals and their page-locked landing area
+    uint8_t *d_out[2] = {nullptr, nullptr};  // the FASTA -> FASTQ text, two slots
+    size_t out_cap[2] = {0, 0};
+    const uint8_t *d_last_accept = nullptr;  // where the flags of the last chunk, a FASTA one, lie on the device
+    bool last_ml = false;
+    bool last_select = false;  // the last chunk came through a select call that took it (a chunk of 0 records included)
+    bool profile = false;  // gs_reads_kernel_time: the FASTA -> FASTQ text kernels (sizes, offsets, copy) between events
+    KernelTimer timer;
+    KernelTimer select_timer, gather_timer;  // gs_reads_phase_times: a chunk from its submission to its flags; the four-line gather
+};
+
+extern "C" int gs_reads_destroy(gs_reads *h) {
+    if (!h) return GS_OK;
+    hipSetDevice(h->device);
+    if (h->stream) hipStreamSynchronize(h->stream);
+    timer_free(h->timer);
+    timer_free(h->select_timer);
+    timer_free(h->gather_timer);
+    text_free(h->text);
+    gs_dev_free(h->d_accept);
+    gs_dev_free(h->d_key);
+    gs_dev_free(h->d_rec_line);
+    gs_dev_free(h->d_piece);
+    gs_dev_free(h->d_rec_out);
+    gs_dev_free(h->d_rec_block);
+    gs_dev_free(h->d_tot);
+    if (h->h_tot) hipHostFree(h->h_tot);
+    gs_dev_free(h->d_out[0]);
+    gs_dev_free(h->d_out[1]);
+    if (h->stream) hipStreamDestroy(h->stream);
+    delete h;
+    return GS_OK;
+}
+
+extern "C" int gs_reads_create(gs_reads **out, int device) try {
+    if (!out) return fail(GS_E_INVALID, "out is NULL");
+    *out = nullptr;
+    int rc = use_device(device);
+    if (rc) return rc;
+    gs_reads *h = new gs_reads();
+    h->device = device;
+    hipDeviceProp_t prop;
+    hipError_t e = hipGetDeviceProperties(&prop, device);
+    if (e == hipSuccess) h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = gs_dev_alloc((void **)&h->d_tot, sizeof(u64) * 4);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&h->h_tot, sizeof(u64) * 4);
+    if (e != hipSuccess) {
+        gs_reads_destroy(h);
+        return hip_fail(e, "gs_reads_create");
+    }
+    *out = h;
+    return GS_OK;
+}
+GS_API_CATCH
+
+// what the rewrite kernels take from the text stage's latest chunk (ReadEntry mode; text_submit fills the same fields in goal mode)
+static void reads_params(gs_reads *h, GsRewriteParams *R) {
+    TextScan &t = h->text;
+    R->text = t.d_text;
+    R->n_lines = t.last_lines;
+    R->n_records = t.last_reads;
+    R->nl = t.d_nl;
+    R->fa_scan = (unsigned long long *)t.d_fa_scan;
+    R->fa_block = (unsigned long long *)t.d_fa_block;
+    R->line_dst = t.d_line_dst;
+    R->fa_seq = t.d_fa_seq;
+    R->off2 = (unsigned long long *)t.d_off2;
+    R->status = t.d_status + (size_t)t.bank * GS_TS_WORDS;
+    R->gate = R->status + GS_TS_SKIP;
+    R->rec_line = h->d_rec_line;
+    R->rec_out = (unsigned long long *)h->d_rec_out;
+    R->rec_block = (unsigned long long *)h->d_rec_block;
+    R->piece_rec = h->d_piece;
+    R->totals = (unsigned long long *)h->d_tot;
+}
+
+// room for the per-record arrays of n_records records and for `bound` bytes of text in slot `slot` (slot < 0: none)
+static int reads_room(gs_reads *h, int64_t n_records, int slot, size_t bound) {
+    int rc;
+    if ((rc = grow(&h->d_rec_line, &h->rec_line_cap, (size_t)n_records + 1, h->stream))) return rc;
+    if (slot < 0) return GS_OK;
+    if ((rc = grow(&h->d_rec_out, &h->rec_out_cap, (size_t)n_records + 1, h->stream))) return rc;
+    if ((rc = grow(&h->d_rec_block, &h->rec_block_cap, (size_t)n_records / 256 + 2, h->stream))) return rc;
+    if ((rc = grow(&h->d_piece, &h->piece_cap, bound / 4096 + 2, h->stream))) return rc;
+    return grow(&h->d_out[slot], &h->out_cap[slot], bound, h->stream);
+}
+
+// the text of a chunk's records is at most twice the chunk and five bytes per record; a multiple of 16 with room behind the text
+static size_t reads_bound(int64_t n_bytes, int64_t n_records) { return ((2 * (size_t)n_bytes + 5 * (size_t)n_records + 15) & ~(size_t)15) + 64; }
+
+static int reads_select(gs_reads *h, int k, const uint8_t *text, int64_t n_bytes, int64_t n_lines, int mem, const uint8_t *key, int32_t key_len,
+                        uint8_t *accept, uint32_t *newlines, int64_t *ticket, int64_t fasta_records, int64_t *ml_out) {
+    if (!h) return fail(GS_E_INVALID, "reads is NULL");
+    if (k < 1 || k > 31) return fail(GS_E_INVALID, "k must be in [1,31]");
+    if (!key || key_len < 1) return fail(GS_E_INVALID, "the key is empty");
+    for (int32_t i = 0; i < key_len; i++)  // (Java compares byte != char: a byte >= 0x80 never matches; a NUL ends the descriptor)
+        if (key[i] == 0 || key[i] >= 0x80) return fail(GS_E_INVALID, "the key holds a NUL byte or a byte >= 0x80");
+    if (n_lines > 0 && !accept) return fail(GS_E_INVALID, "accept is NULL");
+    HIP_TRY(hipSetDevice(h->device));
+    TextScan &t = h->text;
+    TextBatch tb;
+    int rc = timer_start(h->select_timer, h->profile, h->stream);
+    if (rc) return rc;
+    rc = text_batch(t, h->stream, text, n_bytes, n_lines, mem, k, ticket, fasta_records, ml_out, &tb);
+    h->d_last_accept = nullptr;
+    h->last_ml = ml_out != nullptr;
+    h->last_select = rc == GS_OK;
+    if (rc || tb.n_reads == 0) return rc;
+    if (!h->d_key || h->key.size() != (size_t)key_len || memcmp(h->key.data(), key, (size_t)key_len) != 0) {
+        if ((rc = grow(&h->d_key, &h->key_cap, (size_t)key_len, h->stream))) return rc;
+        h->key.assign((const char *)key, (size_t)key_len);
+        HIP_TRY(hipMemcpyAsync(h->d_key, h->key.data(), (size_t)key_len, hipMemcpyHostToDevice, h->stream));
+    }
+    if (!tb.dev_out && (rc = grow(&h->d_accept, &h->accept_cap, (size_t)tb.n_reads, h->stream))) return rc;
+    uint8_t *d_acc = tb.dev_out ? accept : h->d_accept;
+    // a refused chunk leaves `accept` untouched: zero it so that stale flags never look like results
+    HIP_TRY(hipMemsetAsync(d_acc, 0, (size_t)tb.n_reads, h->stream));
+    if (tb.fasta) {  // the descriptor line of every record
+        if ((rc = reads_room(h, tb.n_reads, -1, 0))) return rc;
+        GsRewriteParams R{};
+        reads_params(h, &R);
+        R.n_records = tb.n_reads;
+        R.line_class = ml_out ? t.d_ml_class : nullptr;
+        HIP_TRY(gs_launch_rewrite_heads(&R, h->stream));
+    }
+    HIP_TRY(gs_launch_select(t.d_text, t.d_nl, tb.fasta ? h->d_rec_line : nullptr, tb.n_reads, h->d_key, key_len, tb.d_skip, d_acc, h->stream));
+    if ((rc = timer_stop(h->select_timer, h->profile, h->stream))) return rc;
+    if ((rc = text_touched(t, h->stream))) return rc;
+    if (!tb.fasta)
+        t.d_last_flags = d_acc;
+    else if (!ml_out)
+        h->d_last_accept = d_acc;
+    if (!tb.dev_out) HIP_TRY(hipMemcpyAsync(accept, d_acc, (size_t)tb.n_reads, hipMemcpyDeviceToHost, h->stream));
+    if (newlines)
+        HIP_TRY(hipMemcpyAsync(newlines, t.d_nl, sizeof(uint32_t) * (size_t)t.last_lines, tb.dev_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+    return GS_OK;
+}
+
+extern "C" int gs_reads_select_text(gs_reads *h, int k, const uint8_t *text, int64_t n_bytes, int64_t n_lines, int mem, const uint8_t *key, int32_t key_len,
+                                    uint8_t *accept, uint32_t *newlines, int64_t *ticket) try {
+    return reads_select(h, k, text, n_bytes, n_lines, mem, key, key_len, accept, newlines, ticket, -1, nullptr);
+}
+GS_API_CATCH
+
+extern "C" int gs_reads_select_fasta(gs_reads *h, int k, const uint8_t *text, int64_t n_bytes, int64_t n_lines, int64_t n_records, int mem,
+                                     const uint8_t *key, int32_t key_len, uint8_t *accept, uint32_t *newlines, int64_t *ticket) try {
+    if (n_records < 0) return fail(GS_E_INVALID, "n_records < 0");
+    return reads_select(h, k, text, n_bytes, n_lines, mem, key, key_len, accept, newlines, ticket, n_records, nullptr);
+}
+GS_API_CATCH
+
+extern "C" int gs_reads_select_fastq_ml(gs_reads *h, int k, const uint8_t *text, int64_t n_bytes, int64_t n_lines, int mem, const uint8_t *key,
+                                        int32_t key_len, uint8_t *accept, uint32_t *newlines, int64_t *n_records, int64_t *consumed_bytes,
+                                        int64_t *consumed_lines, int64_t *ticket) try {
+    if (!n_records || !consumed_bytes) return fail(GS_E_INVALID, "NULL argument");
+    int64_t out[3] = {0, 0, 0};
+    const int rc = reads_select(h, k, text, n_bytes, n_lines, mem, key, key_len, accept, newlines, ticket, -1, out);
+    return ml_report(rc, out, n_records, consumed_bytes, consumed_lines);
+}
+GS_API_CATCH
+
+// sizes, offsets, text (gs_launch_rewrite_copy) of the latest chunk's records into slot `slot`, then waits for the totals
+static int reads_rewrite(gs_reads *h, GsRewriteParams *R, int slot, size_t bound, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_records,
+                         int64_t *long_lines) {
+    R->out = h->d_out[slot];
+    int rc = timer_start(h->timer, h->profile, h->stream);
+    if (rc) return rc;
+    HIP_TRY(gs_launch_rewrite_copy(R, (int64_t)bound - 64, h->n_cu, h->stream));
+    if ((rc = timer_stop(h->timer, h->profile, h->stream))) return rc;
+    if ((rc = text_touched(h->text, h->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(h->h_tot, h->d_tot, sizeof(u64) * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    *n_bytes = (int64_t)h->h_tot[0];
+    if (n_records) *n_records = (int64_t)h->h_tot[1];
+    if (long_lines) *long_lines = (int64_t)h->h_tot[2];
+    *d_out = *n_bytes > 0 ? h->d_out[slot] : nullptr;
+    return GS_OK;
+}
+
+// ExtractGoal's readStruct.write on the device: the selected records of the last chunk, four-line FASTQ or FASTA
+extern "C" int gs_reads_compact_text(gs_reads *h, int with_probs, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_records) try {
+    if (!h) return fail(GS_E_INVALID, "reads is NULL");
+    HIP_TRY(hipSetDevice(h->device));
+    TextScan &t = h->text;
+    const bool empty = h->last_select && t.last_reads == 0;  // a selected chunk without records: nothing to flag, nothing to write
+    if (!empty && (t.tickets == 0 || t.last_four_line)) {
+        int rc = timer_start(h->gather_timer, h->profile, h->stream);
+        if (rc) return rc;
+        if ((rc = text_compact(t, h->stream, 0xff, 1, 0, slot, with_probs, d_out, n_bytes, n_records))) return rc;
+        return timer_stop(h->gather_timer, h->profile, h->stream);
+    }
+    if (!d_out || !n_bytes || !n_records) return fail(GS_E_INVALID, "NULL argument");
+    *d_out = nullptr;
+    *n_bytes = *n_records = 0;
+    if (slot < 0 || slot > 1) return fail(GS_E_INVALID, "slot must be 0 or 1");
+    if (h->last_ml) return fail(GS_E_UNSUPPORTED, "records of a general FASTQ chunk are written by the host");
+    if (empty) return GS_OK;
+    if (!h->d_last_accept) return fail(GS_E_STATE, "the last chunk was submitted without per-read flags");
+    if (t.last_reads == 0) return GS_OK;
+    const size_t bound = reads_bound(t.last_bytes, t.last_reads);
+    int rc = reads_room(h, t.last_reads, slot, bound);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(h->d_tot, 0, sizeof(u64) * 4, h->stream));
+    GsRewriteParams R{};
+    reads_params(h, &R);
+    R.accept = h->d_last_accept;
+    return reads_rewrite(h, &R, slot, bound, d_out, n_bytes, n_records, nullptr);
+}
+GS_API_CATCH
+
+extern "C" int gs_reads_fasta2fastq(gs_reads *h, const uint8_t *text, int64_t n_bytes, int64_t n_lines, int64_t n_records, int mem, int slot,
+                                    const uint8_t **d_out, int64_t *n_bytes_out, int64_t *long_lines, int64_t *ticket) try {
+    if (!h || !d_out || !n_bytes_out) return fail(GS_E_INVALID, "NULL argument");
+    *d_out = nullptr;
+    *n_bytes_out = 0;
+    if (long_lines) *long_lines = 0;
+    if (slot < 0 || slot > 1) return fail(GS_E_INVALID, "slot must be 0 or 1");
+    if (n_records < 0 || n_bytes < 0 || n_lines < 0 || n_bytes > ((int64_t)1 << 30) || n_records >= ((int64_t)1 << 24))
+        return fail(GS_E_INVALID, "bad FASTA chunk (at most 1 GiB and 2^24 - 1 records)");
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t bound = reads_bound(n_bytes, n_records);
+    int rc = reads_room(h, n_records, slot, bound);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(h->d_tot, 0, sizeof(u64) * 4, h->stream));
+    GsRewriteParams R{};
+    R.n_lines = n_lines;
+    R.n_records = n_records;
+    R.goal_mode = 1;
+    R.rec_line = h->d_rec_line;
+    R.rec_out = (unsigned long long *)h->d_rec_out;
+    R.rec_block = (unsigned long long *)h->d_rec_block;
+    R.piece_rec = h->d_piece;
+    R.totals = (unsigned long long *)h->d_tot;
+    h->d_last_accept = nullptr;
+    h->last_ml = false;
+    h->last_select = false;
+    if ((rc = text_submit(h->text, h->stream, text, n_bytes, n_lines, mem, 1, ticket, n_records, nullptr, &R))) return rc;
+    return reads_rewrite(h, &R, slot, bound, d_out, n_bytes_out, nullptr, long_lines);
+}
+GS_API_CATCH
+
+extern "C" int gs_reads_sync(gs_reads *h) {
+    if (!h) return fail(GS_E_INVALID, "reads is NULL");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return GS_OK;
+}
+
+// profile != 0: from now on the text kernels of gs_reads_compact_text (FASTA chunks) and gs_reads_fasta2fastq run between events;
+// launches / total_ms (either may be NULL): what they add up to so far
+extern "C" int gs_reads_kernel_time(gs_reads *h, int profile, int64_t *launches, double *total_ms) {
+    int rc = gs_reads_sync(h);
+    if (rc) return rc;
+    if ((rc = timer_collect(h->timer))) return rc;
+    h->profile = profile != 0;
+    if (launches) *launches = h->timer.launches;
+    if (total_ms) *total_ms = h->timer.total_ms;
+    return GS_OK;
+}
+
+// what a profiling handle (gs_reads_kernel_time) has measured so far, phase by phase, as time on its stream between events:
+// [0] select calls, from the chunk's submission to its flags (the chunk's way in, record search, descriptor compare);
+// [1] the four-line gather of gs_reads_compact_text; [2] the FASTA -> FASTQ text kernels (what gs_reads_kernel_time reports)
+extern "C" int gs_reads_phase_times(gs_reads *h, int64_t launches[3], double total_ms[3]) {
+    if (!launches || !total_ms) return fail(GS_E_INVALID, "NULL argument");
+    int rc = gs_reads_sync(h);
+    if (rc) return rc;
+    KernelTimer *timers[3] = {&h->select_timer, &h->gather_timer, &h->timer};
+    for (int i = 0; i < 3; i++) {
+        if ((rc = timer_collect(*timers[i]))) return rc;
+        launches[i] = timers[i]->launches;
+        total_ms[i] = timers[i]->total_ms;
+    }
+    return GS_OK;
+}
+
+extern "C" int gs_reads_get_device(gs_reads *h, int *device) {
+    if (!h || !device) return fail(GS_E_INVALID, "NULL argument");
+    *device = h->device;
+    return GS_OK;
+}
+
+extern "C" int gs_reads_text_read_bounds(gs_reads *h, uint64_t *bounds) {
+    if (!h || !bounds) return fail(GS_E_INVALID, "NULL argument");
+    HIP_TRY(hipSetDevice(h->device));
+    return text_read_bounds(h->text, h->stream, bounds, "the last chunk was four-line FASTQ: its reads lie in the text (newlines)");
+}
+
+extern "C" int gs_reads_text_line_classes(gs_reads *h, uint8_t *classes) {
+    if (!h || !classes) return fail(GS_E_INVALID, "NULL argument");
+    HIP_TRY(hipSetDevice(h->device));
+    return text_line_classes(h->text, h->stream, classes);
+}
+
+extern "C" int gs_reads_text_wait_copy(gs_reads *h, int64_t ticket) {
+    if (!h) return fail(GS_E_INVALID, "reads is NULL");
+    HIP_TRY(hipSetDevice(h->device));
+    return text_wait_copy(h->text, ticket);
+}
+
+extern "C" int gs_reads_text_status(gs_reads *h, int64_t *failed_ticket, int64_t *first_bad_record, int64_t totals[3]) {
+    if (!h) return fail(GS_E_INVALID, "reads is NULL");
+    HIP_TRY(hipSetDevice(h->device));
+    return text_status(h->text, h->stream, failed_ticket, first_bad_record, totals);
+}
+
+extern "C" int gs_reads_text_reset(gs_reads *h, int clear_totals) {
+    if (!h) return fail(GS_E_INVALID, "reads is NULL");
+    HIP_TRY(hipSetDevice(h->device));
+    return text_reset(h->text, clear_totals != 0, h->stream);
 }

@@ -2063,9 +2063,49 @@ namespace {
 
 struct FilterCtx {
     gs_bloom *bloom = nullptr;
+    // the extract goal (gs_host_extract_files): no filter -- nextEntry is ByteArrayUtil.startsWith(readDescriptor, 1, key)
+    // (C/goals/ExtractGoal.java:93), the same text stage on a gs_reads handle, everything else as the filter goal
+    gs_reads *rd = nullptr;  // (reads: the counter below)
+    std::string key;
     int k = 31, min_pos_count = 1;
     double positive_ratio = 0.2;
     bool with_probs = false;
+    bool extract() const { return bloom == nullptr; }
+    int get_device(int *device) { return extract() ? gs_reads_get_device(rd, device) : gs_filter_get_device(bloom, device); }
+    int text_reset() { return extract() ? gs_reads_text_reset(rd, 1) : gs_filter_text_reset(bloom, 1); }
+    int text_status(int64_t *failed, int64_t *bad, int64_t tot[3]) {
+        return extract() ? gs_reads_text_status(rd, failed, bad, tot) : gs_filter_text_status(bloom, failed, bad, tot);
+    }
+    const uint8_t *key_bytes() const { return reinterpret_cast<const uint8_t *>(key.data()); }
+    int submit_text(const uint8_t *text, int64_t n_bytes, int64_t n_lines, int mem, uint8_t *acc, uint32_t *nl, int profile, int64_t *ticket) {
+        if (extract()) return gs_reads_select_text(rd, k, text, n_bytes, n_lines, mem, key_bytes(), (int32_t)key.size(), acc, nl, ticket);
+        return gs_filter_submit_text(bloom, k, min_pos_count, positive_ratio, text, n_bytes, n_lines, mem, acc, nl, profile, ticket);
+    }
+    int submit_fasta(const uint8_t *text, int64_t n_bytes, int64_t n_lines, int64_t n_records, int mem, uint8_t *acc, uint32_t *nl, int64_t *ticket) {
+        if (extract()) return gs_reads_select_fasta(rd, k, text, n_bytes, n_lines, n_records, mem, key_bytes(), (int32_t)key.size(), acc, nl, ticket);
+        return gs_filter_submit_fasta(bloom, k, min_pos_count, positive_ratio, text, n_bytes, n_lines, n_records, mem, acc, nl, ticket);
+    }
+    int submit_fastq_ml(const uint8_t *text, int64_t n_bytes, int64_t n_lines, int mem, uint8_t *acc, uint32_t *nl, int64_t *n_records, int64_t *used,
+                        int64_t *lines, int64_t *ticket) {
+        if (extract())
+            return gs_reads_select_fastq_ml(rd, k, text, n_bytes, n_lines, mem, key_bytes(), (int32_t)key.size(), acc, nl, n_records, used, lines, ticket);
+        return gs_filter_submit_fastq_ml(bloom, k, min_pos_count, positive_ratio, text, n_bytes, n_lines, mem, acc, nl, n_records, used, lines, ticket);
+    }
+    int compact_text(int which, int probs, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_records) {
+        if (extract()) return gs_reads_compact_text(rd, probs, slot, d_out, n_bytes, n_records);  // (no rest file: which == 1)
+        return gs_filter_compact_text(bloom, which, probs, slot, d_out, n_bytes, n_records);
+    }
+    int read_bounds(uint64_t *bounds) { return extract() ? gs_reads_text_read_bounds(rd, bounds) : gs_filter_text_read_bounds(bloom, bounds); }
+    int line_classes(uint8_t *cls) { return extract() ? gs_reads_text_line_classes(rd, cls) : gs_filter_text_line_classes(bloom, cls); }
+    // a parsed batch: the filter kernel, or the key against the descriptors where they lie
+    int submit_batch(Batch &b, int64_t n) {
+        if (!extract()) return gs_filter_submit(bloom, k, min_pos_count, positive_ratio, b.seq.data(), b.seq_off.data(), n, GS_MEM_HOST, accept.data(), 0);
+        for (int64_t i = 0; i < n; i++) {
+            const uint64_t d0 = b.desc_off[(size_t)i], d1 = b.desc_off[(size_t)i + 1];
+            accept[(size_t)i] = d1 - d0 >= key.size() + 1 && memcmp(b.desc.data() + d0 + 1, key.data(), key.size()) == 0;
+        }
+        return GS_OK;
+    }
     OutFile acc_out, rest_out;
     std::vector<uint8_t> accept;
     int64_t accepted = 0, reads = 0, kmers = 0, bps = 0;
@@ -2106,8 +2146,7 @@ int filter_parsed_source(FilterCtx &c, const std::string &path, int64_t offset, 
         c.accept.resize((size_t)n);
         if (b->seq.empty()) b->seq.push_back(0);
         const double t0 = now_s();
-        err = gs_filter_submit(c.bloom, c.k, c.min_pos_count, c.positive_ratio, b->seq.data(), b->seq_off.data(), n, GS_MEM_HOST,
-                               c.accept.data(), 0);
+        err = c.submit_batch(*b, n);
         c.t_gpu += now_s() - t0;
         if (err) continue;
         std::vector<FilterPart> parts((size_t)c.pool.threads());
@@ -2151,6 +2190,7 @@ void filter_reader_shape(bool gzip, size_t *block, int *readers) {
 }
 
 int filter_general_file(FilterCtx &c, const std::string &path, bool gzip, bool fasta);
+int filter_files(FilterCtx &c, const char *const *paths, int n_paths, int extract_device, gs_host_totals *totals);
 
 // the records of one chunk of four-line FASTQ to the writers: nextEntry (FastqBloomFilter.java:92-105), input order
 void format_text_chunk(FilterCtx &c, const uint8_t *start, const uint8_t *h_acc, const uint32_t *h_nl, int64_t n_reads) {
@@ -2191,7 +2231,7 @@ int filter_bgzf_file(FilterCtx &c, const std::string &path, bool *handled) {
     const uint8_t *gz_text = nullptr;  // the current batch
     int64_t gz_n = 0, gz_off = 0;
     int gz_last = 0;
-    if (err || tr.map_len < 18 || gs_filter_get_device(c.bloom, &device) != GS_OK) {
+    if (err || tr.map_len < 18 || c.get_device(&device) != GS_OK) {
         tr.close();
         return GS_OK;
     }
@@ -2213,7 +2253,7 @@ int filter_bgzf_file(FilterCtx &c, const std::string &path, bool *handled) {
     }
     const bool whole = inf == nullptr;
     *handled = true;
-    err = gs_filter_text_reset(c.bloom, 1);
+    err = c.text_reset();
     PooledBuf text_sets[2], nl_sets[2];
     PinnedVec<uint8_t> acc_sets[2];
     std::future<void> formatting;
@@ -2298,8 +2338,8 @@ int filter_bgzf_file(FilterCtx &c, const std::string &path, bool *handled) {
             int64_t ticket = -1;
             static const bool trace = getenv("GS_HOST_TRACE") != nullptr;
             const double t1 = now_s();
-            err = gs_filter_submit_text(c.bloom, c.k, c.min_pos_count, c.positive_ratio, text, n_bytes, n_lines, GS_MEM_DEVICE_TEXT, h_acc, nullptr, 0, &ticket);
-            if (!err) err = gs_filter_text_status(c.bloom, &failed, &bad, tot);  // synchronises: results are needed now
+            err = c.submit_text(text, n_bytes, n_lines, GS_MEM_DEVICE_TEXT, h_acc, nullptr, 0, &ticket);
+            if (!err) err = c.text_status(&failed, &bad, tot);  // synchronises: results are needed now
             const double t2 = now_s();
             c.t_gpu += t2 - tg;
             if (err) break;
@@ -2309,8 +2349,8 @@ int filter_bgzf_file(FilterCtx &c, const std::string &path, bool *handled) {
             }
             const uint8_t *d_a = nullptr, *d_r = nullptr;
             int64_t nb_a = 0, nr_a = 0, nb_r = 0, nr_r = 0;
-            if (c.acc_out.active()) err = gs_filter_compact_text(c.bloom, 1, c.with_probs ? 1 : 0, set, &d_a, &nb_a, &nr_a);
-            if (!err && c.rest_out.active()) err = gs_filter_compact_text(c.bloom, 0, c.with_probs ? 1 : 0, set, &d_r, &nb_r, &nr_r);
+            if (c.acc_out.active()) err = c.compact_text(1, c.with_probs ? 1 : 0, set, &d_a, &nb_a, &nr_a);
+            if (!err && c.rest_out.active()) err = c.compact_text(0, c.with_probs ? 1 : 0, set, &d_r, &nb_r, &nr_r);
             if (err) break;
             if (c.acc_out.active())
                 c.accepted += nr_a;
@@ -2345,12 +2385,12 @@ int filter_bgzf_file(FilterCtx &c, const std::string &path, bool *handled) {
             int64_t ticket = -1;
             static const bool trace = getenv("GS_HOST_TRACE") != nullptr;
             const double t1 = now_s();
-            err = gs_filter_submit_text(c.bloom, c.k, c.min_pos_count, c.positive_ratio, text, n_bytes, n_lines, GS_MEM_DEVICE_TEXT, h_acc, h_nl, 0, &ticket);
+            err = c.submit_text(text, n_bytes, n_lines, GS_MEM_DEVICE_TEXT, h_acc, h_nl, 0, &ticket);
             const double t2 = now_s();
             if (!err && (whole ? gs_device_fetch(device, text, h_text, n_bytes) : gs_inflater_fetch(inf, h_text, n_bytes)) != GS_OK)
                 err = hfail(GS_E_HIP, gs_inflate_last_error());  // (while the kernel runs)
             const double t3 = now_s();
-            if (!err) err = gs_filter_text_status(c.bloom, &failed, &bad, tot);  // synchronises: results are needed now
+            if (!err) err = c.text_status(&failed, &bad, tot);  // synchronises: results are needed now
             const double t4 = now_s();
             c.t_gpu += t4 - tg;
             if (err) break;
@@ -2400,7 +2440,7 @@ int filter_bgzf_file(FilterCtx &c, const std::string &path, bool *handled) {
     c.kmers += tot[1];
     c.bps += tot[2];
     if (fallback_off >= 0) {
-        err = gs_filter_text_reset(c.bloom, 1);
+        err = c.text_reset();
         if (err) return err;
         // not four lines per record from the very first chunk: once more with the records found on the device, as filter_text_file
         bool ml = fallback_off == 0;
@@ -2423,7 +2463,7 @@ int filter_text_file(FilterCtx &c, const std::string &path, bool gzip) {
         tr.close();
         return err;
     }
-    err = gs_filter_text_reset(c.bloom, 1);
+    err = c.text_reset();
     // results of a chunk land in pinned memory: accept flags + newline offsets; two sets, so that the writers can work
     // on one chunk (on a thread of their own) while the device is busy with the next
     PinnedVec<uint8_t> acc_sets[2];
@@ -2433,7 +2473,7 @@ int filter_text_file(FilterCtx &c, const std::string &path, bool gzip) {
     // (plain outputs from a plain file are formatted from the reader's page-locked block, which is on the host anyway)
     int device = 0;
     const bool dev_out = device_output() && ((c.acc_out.active() && c.acc_out.gzip()) || (c.rest_out.active() && c.rest_out.gzip())) &&
-                         gs_filter_get_device(c.bloom, &device) == GS_OK;
+                         c.get_device(&device) == GS_OK;
     c.acc_dev.begin(&c.acc_out, device);
     c.rest_dev.begin(&c.rest_out, device);
     int64_t n_formatted = 0;
@@ -2470,9 +2510,9 @@ int filter_text_file(FilterCtx &c, const std::string &path, bool gzip) {
             uint32_t *h_nl = nl_sets[n_formatted & 1].data();
             int64_t ticket = -1;
             const double tg = now_s();
-            err = gs_filter_submit_text(c.bloom, c.k, c.min_pos_count, c.positive_ratio, start, (int64_t)carry.size() + cut + 1,
+            err = c.submit_text(start, (int64_t)carry.size() + cut + 1,
                                         usable, GS_MEM_HOST, h_acc, h_nl, 0, &ticket);
-            if (!err) err = gs_filter_text_status(c.bloom, &failed, &bad, tot);  // synchronises: results are needed now
+            if (!err) err = c.text_status(&failed, &bad, tot);  // synchronises: results are needed now
             c.t_gpu += now_s() - tg;
             if (err) break;
             if (failed >= 0) {  // not four-line FASTQ from here on: the general parser continues at this chunk
@@ -2483,8 +2523,8 @@ int filter_text_file(FilterCtx &c, const std::string &path, bool gzip) {
                 const int set = (int)(n_formatted & 1);
                 const uint8_t *d_a = nullptr, *d_r = nullptr;
                 int64_t nb_a = 0, nr_a = 0, nb_r = 0, nr_r = 0;
-                if (c.acc_out.active()) err = gs_filter_compact_text(c.bloom, 1, c.with_probs ? 1 : 0, set, &d_a, &nb_a, &nr_a);
-                if (!err && c.rest_out.active()) err = gs_filter_compact_text(c.bloom, 0, c.with_probs ? 1 : 0, set, &d_r, &nb_r, &nr_r);
+                if (c.acc_out.active()) err = c.compact_text(1, c.with_probs ? 1 : 0, set, &d_a, &nb_a, &nr_a);
+                if (!err && c.rest_out.active()) err = c.compact_text(0, c.with_probs ? 1 : 0, set, &d_r, &nb_r, &nr_r);
                 if (err) break;
                 c.accepted += c.acc_out.active() ? nr_a : n_reads - nr_r;
                 carry_file_off = i * (int64_t)tr.block + cut + 1;
@@ -2536,7 +2576,7 @@ int filter_text_file(FilterCtx &c, const std::string &path, bool gzip) {
     c.kmers += tot[1];
     c.bps += tot[2];
     if (fallback_off >= 0) {
-        err = gs_filter_text_reset(c.bloom, 1);
+        err = c.text_reset();
         if (err) return err;
         // not four lines per record from the very first chunk: once more with the records found on the device (GS_HOST_ML=0:
         // straight to the reference-exact parser, which also takes over whatever that pass refuses)
@@ -2563,7 +2603,7 @@ int filter_general_file(FilterCtx &c, const std::string &path, bool gzip, bool f
         tr.close();
         return err;
     }
-    err = gs_filter_text_reset(c.bloom, 1);
+    err = c.text_reset();
     // two result sets: the records of chunk i are formatted and handed to the writers on a thread of their own while chunk i + 1 is
     // on the device (as the four-line path does; the chunk's block goes back to its reader when the formatting is through)
     struct Res {
@@ -2621,20 +2661,20 @@ int filter_general_file(FilterCtx &c, const std::string &path, bool gzip, bool f
                 if ((err = nls.resize((size_t)std::max<int64_t>(lines, 1)))) break;
                 const double tg = now_s();
                 if (fasta) {
-                    err = gs_filter_submit_fasta(c.bloom, c.k, c.min_pos_count, c.positive_ratio, start, bytes, lines, records, GS_MEM_HOST,
+                    err = c.submit_fasta(start, bytes, lines, records, GS_MEM_HOST,
                                                  acc.data(), nls.data(), &ticket);
                 } else {
                     int64_t all_lines = lines;
-                    err = gs_filter_submit_fastq_ml(c.bloom, c.k, c.min_pos_count, c.positive_ratio, start, bytes, all_lines, GS_MEM_HOST,
+                    err = c.submit_fastq_ml(start, bytes, all_lines, GS_MEM_HOST,
                                                     acc.data(), nls.data(), &records, &used, &lines, &ticket);
                     carry_lines = all_lines - lines;  // (lines the records did not cover)
                 }
-                if (!err) err = gs_filter_text_status(c.bloom, &failed, &bad, tot);  // synchronises: results are needed now
+                if (!err) err = c.text_status(&failed, &bad, tot);  // synchronises: results are needed now
                 if (!err && failed < 0 && records > 0) {
                     bounds.resize((size_t)records + 1);
                     cls.resize((size_t)lines);
-                    err = gs_filter_text_read_bounds(c.bloom, bounds.data());
-                    if (!err && !fasta) err = gs_filter_text_line_classes(c.bloom, cls.data());
+                    err = c.read_bounds(bounds.data());
+                    if (!err && !fasta) err = c.line_classes(cls.data());
                 }
                 c.t_gpu += now_s() - tg;
                 if (err) break;
@@ -2717,7 +2757,7 @@ int filter_general_file(FilterCtx &c, const std::string &path, bool gzip, bool f
     c.kmers += tot[1];
     c.bps += tot[2];
     if (fallback_off >= 0) {
-        err = gs_filter_text_reset(c.bloom, 1);
+        err = c.text_reset();
         if (err) return err;
         return filter_parsed_source(c, path, fallback_off, nullptr, 0);
     }
@@ -2738,11 +2778,28 @@ extern "C" int gs_host_filter_files(gs_bloom *bloom, int k, int min_pos_count, d
     c.min_pos_count = min_pos_count;
     c.positive_ratio = positive_ratio;
     if (!c.acc_out.open(filtered_path) || !c.rest_out.open(rest_path)) return hfail(GS_E_INVALID, "cannot open output file");
+    return filter_files(c, paths, n_paths, -1, totals);
+} catch (const std::bad_alloc &) {
+    return hfail(GS_E_NOMEM, "out of host memory");
+} catch (const std::exception &e) {  // (nothing may leave through the C ABI)
+    return hfail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
+}
+
+namespace {
+// the files in order through the text pipelines (GS_HOST_FAST=0: all of them through the reference-exact parser); extract_device
+// >= 0: the extract goal, whose gs_reads handle is made here when the first file needs it -- the parser's path needs no device
+int filter_files(FilterCtx &c, const char *const *paths, int n_paths, int extract_device, gs_host_totals *totals) {
     const double t_start = now_s();
+    const bool trace = getenv("GS_HOST_TRACE") != nullptr;
     bool fast = true;
     if (const char *e = getenv("GS_HOST_FAST")) fast = atoi(e) != 0;
     int err = GS_OK;
     for (int f = 0; f < n_paths && !err; f++) {
+        if (fast && extract_device >= 0 && !c.rd && gs_reads_create(&c.rd, extract_device) != GS_OK) {
+            err = hfail(GS_E_HIP, gs_last_error());
+            break;
+        }
+        if (trace && c.rd) gs_reads_kernel_time(c.rd, 1, nullptr, nullptr);  // (the handle's phases between events from here on)
         const std::string path(paths[f]);
         const int kind = fast ? text_path_kind(path) : 0;
         if (kind >= 3)
@@ -2758,7 +2815,16 @@ extern "C" int gs_host_filter_files(gs_bloom *bloom, int k, int min_pos_count, d
     const double tc0 = now_s();
     const bool wrote = c.acc_out.close() & c.rest_out.close();
     if (!err) err = c.acc_dev.late_err ? c.acc_dev.late_err : c.rest_dev.late_err;
-    if (getenv("GS_HOST_TRACE") != nullptr) fprintf(stderr, "filter files: %.2f ms before the outputs were closed, closing %.2f ms\n", (tc0 - t_start) * 1e3, (now_s() - tc0) * 1e3);
+    if (trace) fprintf(stderr, "filter files: %.2f ms before the outputs were closed, closing %.2f ms\n", (tc0 - t_start) * 1e3, (now_s() - tc0) * 1e3);
+    if (trace && c.rd) {  // the extract goal, phase by phase
+        int64_t n[3] = {0, 0, 0};
+        double ms[3] = {0, 0, 0};
+        if (gs_reads_phase_times(c.rd, n, ms) == GS_OK)
+            fprintf(stderr,
+                    "extract phases: files %.2f ms (device calls %.2f ms of them), closing the output %.2f ms; on the stream: select %lld chunks %.3f ms, "
+                    "four-line gather %lld calls %.3f ms, FASTA text %lld calls %.3f ms\n",
+                    (tc0 - t_start) * 1e3, c.t_gpu * 1e3, (now_s() - tc0) * 1e3, (long long)n[0], ms[0], (long long)n[1], ms[1], (long long)n[2], ms[2]);
+    }
     if (!err && !wrote) err = hfail(GS_E_IO, "write to an output file failed");
     if (totals) {
         totals->reads = c.reads;
@@ -2770,11 +2836,8 @@ extern "C" int gs_host_filter_files(gs_bloom *bloom, int k, int min_pos_count, d
         totals->seconds_gpu = c.t_gpu;
     }
     return err;
-} catch (const std::bad_alloc &) {
-    return hfail(GS_E_NOMEM, "out of host memory");
-} catch (const std::exception &e) {  // (nothing may leave through the C ABI)
-    return hfail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
 }
+}  // namespace
 
 // The pools above keep page-locked blocks and the device decoders' buffers (a parked gunzipper holds up to a quarter of the free
 // HBM) for the life of the process.  A long-lived host -- a JVM that next loads a big store -- hands them back with this call;
@@ -2856,6 +2919,260 @@ extern "C" int gs_host_db2fastq(gs_db *db, const char *const *taxids, const char
     if (err) return err;
     if (n_written) *n_written = n;
     return GS_OK;
+} catch (const std::exception &e) {
+    return hfail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
+}
+
+namespace {
+// the gs_reads handle of a goal's context goes on every way out of the call, an exception included; declared behind the context,
+// so the handle is gone before the context's writers are
+struct ReadsGuard {
+    gs_reads *&rd;
+    ~ReadsGuard() {
+        if (rd) gs_reads_destroy(rd);
+        rd = nullptr;
+    }
+};
+}  // namespace
+
+// ---- extract (C/goals/ExtractGoal.java:73-129): every read whose descriptor starts with the key -> out_path, written as
+// ReadEntry.write with the goal's withProbs = true; files, readers, inflaters and writers are the filter goal's (filter_files)
+extern "C" int gs_host_extract_files(int device, const char *key, int k, const char *const *paths, int n_paths, const char *out_path,
+                                     gs_host_totals *totals) try {
+    if (!key || !paths || n_paths < 0 || !out_path) return hfail(GS_E_INVALID, "NULL argument");
+    if (k < 1 || k > 31) return hfail(GS_E_INVALID, "k must be in [1,31]");
+    FilterCtx c;
+    ReadsGuard guard{c.rd};
+    c.key = key;
+    if (c.key.empty()) return hfail(GS_E_INVALID, "the key is empty");
+    for (unsigned char ch : c.key)  // (Java compares byte != char: a byte >= 0x80 never matches)
+        if (ch >= 0x80) return hfail(GS_E_INVALID, "the key holds a byte >= 0x80");
+    c.k = k;
+    c.with_probs = true;
+    if (!c.acc_out.open(out_path)) return hfail(GS_E_IO, std::string("cannot open ") + out_path);
+    return filter_files(c, paths, n_paths, device, totals);
+} catch (const std::bad_alloc &) {
+    return hfail(GS_E_NOMEM, "out of host memory");
+} catch (const std::exception &e) {
+    return hfail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
+}
+
+// ---- fasta2fastq (C/goals/Fasta2FastqGoal.java:92-165)
+namespace {
+
+struct F2fCtx {
+    gs_reads *reads = nullptr;
+    int device = 0;
+    OutFile out;
+    int64_t records = 0;
+    double t_read = 0, t_dev = 0, t_emit = 0, t_cpu = 0;  // waiting for blocks (read, inflate); device calls; handing text to the writer; f2f_cpu
+    DeviceWriter dev;  // (declared behind the file: it waits for its writes before the file closes)
+};
+
+// PrintStream.print((char) b) of a UTF-8 stream: a byte >= 0x80 is sign-extended to the char 0xFF80 .. 0xFFFF and leaves as three bytes
+void f2f_print(std::vector<uint8_t> &o, const uint8_t *p, size_t n) {
+    for (size_t i = 0; i < n; i++) {
+        if (p[i] < 0x80) {
+            o.push_back(p[i]);
+        } else {
+            const unsigned ch = 0xFF00u | p[i];
+            o.push_back(0xEF);
+            o.push_back((uint8_t)(0x80 | ((ch >> 6) & 0x3F)));
+            o.push_back((uint8_t)(0x80 | (ch & 0x3F)));
+        }
+    }
+}
+
+// The goal's loop, line by line: AbstractFastaReader.readFasta (C/fasta/AbstractFastaReader.java:97-130) with the FastqWriter of
+// Fasta2FastqGoal.java:118-165 over BufferedLineReader.nextLine (LineReader: NUL bytes dropped, the '\n' part of the line).  The
+// file from `offset` on, or a memory range.  Text in front of a first header is printed raw, without a record; a final header
+// line without '\n' loses its last byte (size - 1), a final data line without '\n' keeps all of its bytes.
+int f2f_cpu(F2fCtx &c, const std::string &path, int64_t offset, const uint8_t *mem, size_t mem_n) {
+    const double t_begin = now_s();
+    LineReader lr;
+    if (path.empty())
+        lr.open_mem(mem, mem_n);
+    else if (!lr.open(path, offset))
+        return hfail(GS_E_IO, "cannot open " + path);
+    std::vector<uint8_t> line, o = c.out.take();
+    bool first = true;
+    int64_t data_size = 0;
+    auto end_region = [&] {
+        o.push_back('\n');
+        o.push_back('+');
+        o.push_back('\n');
+        o.insert(o.end(), (size_t)data_size, (uint8_t)'~');
+        o.push_back('\n');
+    };
+    for (;;) {
+        line.clear();
+        const size_t size = lr.next_line(line);
+        if (size == 0) break;
+        if (size >= 65534) return hfail(GS_E_INVALID, "buffer is too small for data line in fasta file " + path);  // (a target of 65 535 bytes, :104-106)
+        if (line[0] == '>') {
+            if (!first) end_region();
+            first = false;
+            data_size = 0;
+            c.records++;
+            o.push_back('@');
+            f2f_print(o, line.data() + 1, size >= 2 ? size - 2 : 0);  // println(target, 1, size - 1)
+            o.push_back('\n');
+        } else {
+            size_t end = size;
+            while (end > 0 && (line[end - 1] == '\n' || line[end - 1] == '\r')) end--;
+            f2f_print(o, line.data(), end);
+            data_size += (int64_t)end;
+        }
+        if (o.size() >= ((size_t)4 << 20)) {
+            c.out.write(std::move(o));
+            o = c.out.take();
+        }
+    }
+    if (!first) end_region();
+    c.out.write(std::move(o));
+    c.t_cpu += now_s() - t_begin;
+    return GS_OK;
+}
+
+bool f2f_high_bytes(const uint8_t *p, size_t n) {
+    uint8_t any = 0;
+    for (size_t i = 0; i < n; i++) any |= p[i];
+    return (any & 0x80) != 0;
+}
+
+// One file through the device: chunks of whole records, cut in front of a header line (fasta_cut), become FASTQ text there
+// (gs_reads_fasta2fastq) and leave it as the output file's bytes (DeviceWriter).  What the device refuses -- text in front of a
+// first header, a NUL byte --, a record that does not fit a block, bytes >= 0x80 (the reference widens them) and the tail of a
+// file without a final newline go through f2f_cpu from the start of that chunk.
+int f2f_device_file(F2fCtx &c, const std::string &path, bool gzip) {
+    size_t block;
+    int readers;
+    filter_reader_shape(gzip, &block, &readers);
+    TextReader tr;
+    int err = tr.open(path, block, readers, gzip);
+    if (err) {
+        tr.close();
+        return err;
+    }
+    if (gs_reads_text_reset(c.reads, 1) != GS_OK) err = hfail(GS_E_HIP, gs_last_error());
+    std::vector<uint8_t> carry;
+    int64_t carry_lines = 0, carry_headers = 0, carry_file_off = 0, fallback_off = -1, n_chunks = 0;
+    if (!err) tr.start();
+    for (int64_t i = 0; !err; i++) {
+        const double tw = now_s();
+        TextSlot &sl = tr.wait_full(i);
+        c.t_read += now_s() - tw;
+        if (sl.io_error || !tr.verify_gzip(sl)) {
+            err = hfail(tr.gz ? GS_E_INVALID : GS_E_IO, (tr.gz ? "corrupt gzip stream in " : "read error on ") + path);
+            break;
+        }
+        uint8_t *blk = sl.buf + tr.headroom;
+        const int64_t n = (int64_t)sl.n;
+        const bool eof = sl.eof;
+        const FastaCut fc = fasta_cut(blk, n, eof, carry);
+        if (f2f_high_bytes(blk, (size_t)n)) {
+            fallback_off = carry_file_off;
+        } else if (fc.cut < 0) {  // no boundary in this block: keep everything
+            carry.insert(carry.end(), blk, blk + n);
+            carry_lines += sl.newlines;
+            carry_headers += fc.headers;
+            if (carry.size() > tr.headroom && !eof) fallback_off = carry_file_off;  // a record longer than a block
+        } else if (carry.size() > tr.headroom) {
+            fallback_off = carry_file_off;
+        } else {
+            uint8_t *start = blk - carry.size();
+            if (!carry.empty()) memcpy(start, carry.data(), carry.size());
+            const int64_t bytes = (int64_t)carry.size() + fc.cut, lines = carry_lines + sl.newlines - fc.tail_lines, records = carry_headers + fc.cut_headers;
+            if (records >= ((int64_t)1 << 24)) {
+                fallback_off = carry_file_off;
+            } else if (bytes > 0) {
+                const uint8_t *d_text = nullptr;
+                int64_t n_out = 0, long_lines = 0, failed = -1, bad = -1, tot[3] = {0, 0, 0};
+                const double td = now_s();
+                if (gs_reads_fasta2fastq(c.reads, start, bytes, lines, records, GS_MEM_HOST, (int)(n_chunks & 1), &d_text, &n_out, &long_lines, nullptr) != GS_OK ||
+                    gs_reads_text_status(c.reads, &failed, &bad, tot) != GS_OK) {
+                    err = hfail(GS_E_HIP, gs_last_error());
+                    break;
+                }
+                c.t_dev += now_s() - td;
+                if (failed >= 0) {
+                    fallback_off = carry_file_off;
+                } else if (long_lines > 0) {
+                    err = hfail(GS_E_INVALID, "buffer is too small for data line in fasta file " + path);
+                    break;
+                } else {
+                    const double te = now_s();
+                    err = c.dev.emit((int)(n_chunks & 1), d_text, n_out);
+                    c.t_emit += now_s() - te;
+                    if (err) break;
+                    n_chunks++;
+                    c.records += records;
+                }
+            }
+            if (fallback_off < 0) {
+                carry_file_off += bytes;
+                carry.assign(blk + fc.cut, blk + n);
+                carry_lines = fc.tail_lines;
+                carry_headers = fc.headers - fc.cut_headers;
+            }
+        }
+        tr.release(i);
+        if (eof || fallback_off >= 0) break;
+    }
+    tr.close();
+    if (err) return err;
+    if (fallback_off >= 0) {
+        if (gs_reads_text_reset(c.reads, 1) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
+        return f2f_cpu(c, path, fallback_off, nullptr, 0);
+    }
+    if (!carry.empty()) return f2f_cpu(c, std::string(), 0, carry.data(), carry.size());
+    return GS_OK;
+}
+
+}  // namespace
+
+extern "C" int gs_host_fasta2fastq(int device, const char *const *paths, int n_paths, const char *out_path, int64_t *n_records) try {
+    if (!paths || n_paths < 0 || !out_path) return hfail(GS_E_INVALID, "NULL argument");
+    bool fast = true;
+    if (const char *e = getenv("GS_HOST_FAST")) fast = atoi(e) != 0;
+    int err = GS_OK;
+    int64_t records = 0;
+    bool wrote = true;
+    {
+        F2fCtx c;
+        ReadsGuard guard{c.reads};
+        c.device = device;
+        if (!c.out.open(out_path)) return hfail(GS_E_IO, std::string("cannot open ") + out_path);
+        if (fast && gs_reads_create(&c.reads, device) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
+        const bool trace = getenv("GS_HOST_TRACE") != nullptr;
+        if (trace && c.reads) gs_reads_kernel_time(c.reads, 1, nullptr, nullptr);  // (the text kernels between events from here on)
+        c.dev.begin(&c.out, device);
+        const double t_start = now_s();
+        for (int f = 0; f < n_paths && !err; f++) {  // (all resources into ONE file, Fasta2FastqGoal.java:96-102)
+            const std::string path(paths[f]);
+            const int kind = fast ? text_path_kind(path) : 0;
+            err = kind ? f2f_device_file(c, path, kind == 2 || kind == 4) : f2f_cpu(c, path, 0, nullptr, 0);
+        }
+        const double tc0 = now_s();
+        const int e2 = c.dev.finish();
+        if (!err) err = e2;
+        wrote = c.out.close();
+        if (trace) {  // the goal, phase by phase
+            int64_t n[3] = {0, 0, 0};
+            double ms[3] = {0, 0, 0};
+            if (c.reads) gs_reads_phase_times(c.reads, n, ms);
+            fprintf(stderr,
+                    "fasta2fastq phases: files %.2f ms (waiting for blocks %.2f ms, device calls %.2f ms, to the writer %.2f ms, line-by-line loop %.2f ms), "
+                    "closing the output %.2f ms; on the stream: text kernels %lld chunks %.3f ms\n",
+                    (tc0 - t_start) * 1e3, c.t_read * 1e3, c.t_dev * 1e3, c.t_emit * 1e3, c.t_cpu * 1e3, (now_s() - tc0) * 1e3, (long long)n[2], ms[2]);
+        }
+        records = c.records;
+    }
+    if (!err && !wrote) err = hfail(GS_E_IO, std::string("writing ") + out_path + " failed");
+    if (n_records) *n_records = records;
+    return err;
+} catch (const std::bad_alloc &) {
+    return hfail(GS_E_NOMEM, "out of host memory");
 } catch (const std::exception &e) {
     return hfail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
 }

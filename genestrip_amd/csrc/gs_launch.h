@@ -122,6 +122,15 @@ int gs_filter_occupancy();
 // ---- gs_text.hip
 hipError_t gs_launch_text_scan(const GsTextParams *P, uint32_t ticket, hipStream_t stream);
 hipError_t gs_launch_text_ml(const GsTextParams *P, uint8_t *line_class, hipStream_t stream);
+hipError_t gs_launch_text_lines(const GsTextParams *P, hipStream_t stream);
+hipError_t gs_launch_text_commit(const GsTextParams *P, uint32_t ticket, hipStream_t stream);
+
+// ---- gs_rewrite.hip: extract and fasta2fastq
+hipError_t gs_launch_rewrite_lines(const GsRewriteParams *P, hipStream_t stream);
+hipError_t gs_launch_rewrite_heads(const GsRewriteParams *P, hipStream_t stream);
+hipError_t gs_launch_rewrite_copy(const GsRewriteParams *P, int64_t out_bound, int n_cu, hipStream_t stream);
+hipError_t gs_launch_select(const uint8_t *text, const uint32_t *nl, const uint32_t *rec_line, int64_t n_records, const uint8_t *key, int32_t key_len,
+                            const uint32_t *skip, uint8_t *accept, hipStream_t stream);
 
 // ---- gs_merge.hip: merge of runs that live in one process
 hipError_t gs_launch_merge_i64(void *dst, const void *src, int64_t n, int op, hipStream_t stream);

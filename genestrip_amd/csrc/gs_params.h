@@ -158,6 +158,29 @@ struct GsTextParams {
 #define GS_ML_MAX_LINES 4096  // lines one record may span before the chunk is refused (the host parser takes over)
 #define GS_FA_BLOCK 256
 
+// extract and fasta2fastq (gs_rewrite.hip): the text of FASTA records as four-line FASTQ, behind the record search of gs_text.hip
+// (ReadEntry mode) or behind the newline scan alone (goal mode, goal_mode != 0)
+struct GsRewriteParams {
+    const uint8_t *text;              // the chunk, as GsTextParams
+    int64_t n_lines, n_records;
+    const uint32_t *nl;
+    const uint8_t *line_class;        // general FASTQ (header lines for the selection only) or nullptr
+    unsigned long long *fa_scan, *fa_block;  // as GsTextParams: read in ReadEntry mode, written in goal mode
+    uint32_t *line_dst;               // goal mode: destination of a data line's kept bytes in fa_seq, ~0: none
+    uint8_t *fa_seq;                  // the sequences back to back; off2[0 .. n_records] = their bounds
+    unsigned long long *off2;
+    uint32_t *status;                 // the bank's GS_TS_WORDS words
+    const uint32_t *gate;             // the launch does nothing when *gate != 0: the chunk error word in front of the commit, the skip flag behind it
+    int32_t goal_mode, pad;
+    const uint8_t *accept;            // per record, nullptr: every record
+    uint32_t *rec_line;               // n_records + 1: the header line of every record, then n_lines
+    unsigned long long *rec_out;      // n_records + 1: where the text of every record starts
+    unsigned long long *rec_block;    // per block of 256 records
+    uint32_t *piece_rec;              // per 4096 bytes of the text: the record that holds the first of them
+    unsigned long long *totals;       // [0] bytes of text [1] records written [2] lines of 65 534 bytes and more [3] scratch
+    uint8_t *out;
+};
+
 struct GsFilterParams {
     int32_t kind;           // GS_BLOOM_*
     int32_t k;

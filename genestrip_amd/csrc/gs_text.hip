@@ -426,15 +426,29 @@ __global__ void gs_text_commit_kernel(GsTextParams P, uint32_t ticket) {
     P.status[GS_TS_CHUNK_ERR] = 0;
 }
 
+// newline offsets alone (NUL and count checks included): the front of both launchers below, and all that a caller with a record
+// rule of its own (gs_rewrite.hip: fasta2fastq) takes from this file -- together with the commit of its chunk
+extern "C" hipError_t gs_launch_text_lines(const GsTextParams *P, hipStream_t stream) {
+    const int64_t n_tiles = (P->n_bytes + GS_TEXT_TILE - 1) / GS_TEXT_TILE;
+    if (n_tiles <= 0) return hipSuccess;
+    hipLaunchKernelGGL(gs_text_count_kernel, dim3((unsigned)n_tiles), dim3(GS_TEXT_BLOCK), 0, stream, *P);
+    hipLaunchKernelGGL(gs_text_scan_kernel, dim3(1), dim3(1024), 0, stream, *P, n_tiles);
+    hipLaunchKernelGGL(gs_text_lines_kernel, dim3((unsigned)n_tiles), dim3(GS_TEXT_BLOCK), 0, stream, *P);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t gs_launch_text_commit(const GsTextParams *P, uint32_t ticket, hipStream_t stream) {
+    hipLaunchKernelGGL(gs_text_commit_kernel, dim3(1), dim3(64), 0, stream, *P, ticket);
+    return hipGetLastError();
+}
+
 // general FASTQ, first half: newline offsets + record structure.  ml_out: [0] = 0, [1] = n_lines before the launch; afterwards
 // [0] complete records, [1] the lines they cover (the caller reads them back, sets n_lines / n_records / line_class and calls
 // gs_launch_text_scan for the second half with lines_done = 1)
 extern "C" hipError_t gs_launch_text_ml(const GsTextParams *P, uint8_t *line_class, hipStream_t stream) {
     const int64_t n_tiles = (P->n_bytes + GS_TEXT_TILE - 1) / GS_TEXT_TILE;
     if (n_tiles <= 0 || P->n_lines <= 0) return hipSuccess;
-    hipLaunchKernelGGL(gs_text_count_kernel, dim3((unsigned)n_tiles), dim3(GS_TEXT_BLOCK), 0, stream, *P);
-    hipLaunchKernelGGL(gs_text_scan_kernel, dim3(1), dim3(1024), 0, stream, *P, n_tiles);
-    hipLaunchKernelGGL(gs_text_lines_kernel, dim3((unsigned)n_tiles), dim3(GS_TEXT_BLOCK), 0, stream, *P);
+    gs_launch_text_lines(P, stream);
     const unsigned g = (unsigned)((P->n_lines + 255) / 256);
     hipLaunchKernelGGL(gs_ml_next_kernel, dim3(g), dim3(256), 0, stream, *P);
     hipLaunchKernelGGL(gs_ml_orbit_init_kernel, dim3(g), dim3(256), 0, stream, *P);
@@ -450,11 +464,7 @@ extern "C" hipError_t gs_launch_text_ml(const GsTextParams *P, uint8_t *line_cla
 extern "C" hipError_t gs_launch_text_scan(const GsTextParams *P, uint32_t ticket, hipStream_t stream) {
     const int64_t n_tiles = (P->n_bytes + GS_TEXT_TILE - 1) / GS_TEXT_TILE;
     if (n_tiles > 0) {
-        if (P->line_class == nullptr) {  // (general FASTQ: gs_launch_text_ml has found the newlines already)
-            hipLaunchKernelGGL(gs_text_count_kernel, dim3((unsigned)n_tiles), dim3(GS_TEXT_BLOCK), 0, stream, *P);
-            hipLaunchKernelGGL(gs_text_scan_kernel, dim3(1), dim3(1024), 0, stream, *P, n_tiles);
-            hipLaunchKernelGGL(gs_text_lines_kernel, dim3((unsigned)n_tiles), dim3(GS_TEXT_BLOCK), 0, stream, *P);
-        }
+        if (P->line_class == nullptr) gs_launch_text_lines(P, stream);  // (general FASTQ: gs_launch_text_ml has found the newlines already)
         if (P->n_records >= 0) {  // FASTA, general FASTQ
             const int64_t n_blocks = (P->n_lines + GS_FA_BLOCK - 1) / GS_FA_BLOCK;
             if (n_blocks > 0) {
@@ -473,6 +483,5 @@ extern "C" hipError_t gs_launch_text_scan(const GsTextParams *P, uint32_t ticket
                                    dim3(GS_TEXT_BLOCK), 0, stream, *P);
         }
     }
-    hipLaunchKernelGGL(gs_text_commit_kernel, dim3(1), dim3(64), 0, stream, *P, ticket);
-    return hipGetLastError();
+    return gs_launch_text_commit(P, ticket, stream);
 }

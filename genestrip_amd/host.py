@@ -54,6 +54,8 @@ def lib():
         "gs_host_stat": (C.c_int64, [ci]),
         "gs_host_release_pools": (ci, []),
         "gs_host_filter_files": (ci, [vp, ci, ci, C.c_double, vp, ci, C.c_char_p, C.c_char_p, ci, vp]),
+        "gs_host_extract_files": (ci, [ci, C.c_char_p, ci, vp, ci, C.c_char_p, vp]),
+        "gs_host_fasta2fastq": (ci, [ci, vp, ci, C.c_char_p, vp]),
         "gs_host_write_csv": (ci, [C.c_char_p, vp, vp, vp, vp]),
         "gs_host_write_quality_csv": (ci, [C.c_char_p, vp, vp, vp]),
         "gs_host_db2fastq": (ci, [vp, vp, C.c_char_p, C.c_int32, ci, C.c_char_p, vp]),
@@ -194,6 +196,24 @@ def filter_files(bloom, k, paths, min_pos_count=1, positive_ratio=0.2, filtered_
                                       None if rest_path is None else str(rest_path).encode(), int(with_probs),
                                       C.byref(tot)))
     return tot
+
+
+def extract_files(key, paths, out_path, k=31, device=0):
+    """the extract goal: every read of the files whose descriptor starts with `key` -> out_path (.gz: BGZF), written as
+    ReadEntry.write with qualities; -> Totals (filtered_reads = reads written)"""
+    parr = _cstr_array(list(paths))
+    tot = Totals()
+    _check(lib().gs_host_extract_files(int(device), key if isinstance(key, bytes) else str(key).encode(), int(k), parr, len(paths),
+                                       str(out_path).encode(), C.byref(tot)))
+    return tot
+
+
+def fasta2fastq(paths, out_path, device=0):
+    """the fasta2fastq goal: the FASTA files, in order, as one four-line FASTQ file with '~' qualities (.gz: BGZF); -> records"""
+    parr = _cstr_array(list(paths))
+    n = C.c_int64(0)
+    _check(lib().gs_host_fasta2fastq(int(device), parr, len(paths), str(out_path).encode(), C.byref(n)))
+    return n.value
 
 
 def write_csv(path, parent_vi, taxids, db_kmers, db_kmers_total, table, dtable, totals, names=None, ranks=None,

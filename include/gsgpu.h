@@ -847,6 +847,58 @@ int gs_deflate_host_reference(const uint8_t *text, int64_t n, uint8_t *out, int6
 const char *gs_deflate_last_error(void);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Read streams without a store or a filter (genestrip_amd/csrc/gs_rewrite.hip): the extract goal (C/goals/ExtractGoal.java:73-129)
+ * and the fasta2fastq goal (C/goals/Fasta2FastqGoal.java:92-165).  A gs_reads handle owns the same text stage as a run or a filter:
+ * its own stream, staging, status words and totals; chunk contracts, refusal rules and status reporting of the three select calls
+ * are those of gs_filter_submit_text / _fasta / _fastq_ml (k only feeds the totals).
+ *
+ * gs_reads_select_*: accept[r] = 1 iff the descriptor line of record r behind its first byte -- up to but excluding the '\n', a
+ * '\r' included -- holds at least key_len bytes and starts with the key (ByteArrayUtil.startsWith(readDescriptor, 1, key),
+ * ExtractGoal.java:93); FASTA records use their header line the same way.  key_len < 1, a NUL byte or a byte >= 0x80 in the key:
+ * GS_E_INVALID (the goal does nothing for an empty key; Java compares byte != char, such a byte never matches).
+ * gs_reads_compact_text: the selected records of the most recent chunk as ReadEntry.write writes them (as gs_filter_compact_text
+ * with which = 1): of a four-line chunk by the gather of gs_deflate_dev.hip, of a FASTA chunk by the FASTA -> FASTQ kernel in its
+ * ReadEntry mode ('@' header[1:] '\n' sequence "\n+\n" '~' x L '\n', the sequence = the data lines without their '\n', '\r'
+ * kept; with_probs changes nothing: FASTA has no qualities).  General FASTQ chunks: GS_E_UNSUPPORTED (the host's writers).
+ * gs_reads_fasta2fastq: the FASTQ text of ALL records of a FASTA chunk of whole records as the fasta2fastq goal prints them:
+ * the header from byte 1 up to the '\n' ('\r' stays), every data line without its trailing '\r's and '\n' (empty lines are data
+ * lines of zero bytes), '~' x the bytes kept; a record without data gives "@h\n\n+\n\n".  The chunk starts with '>', ends with
+ * '\n', n_lines / n_records are its newlines and header lines; mem: GS_MEM_HOST or GS_MEM_DEVICE.  Refused (gs_reads_text_status;
+ * *d_out = NULL, *n_bytes_out = 0) are only chunks that do not start with '>', hold a NUL byte (the reference's line reader
+ * drops those) or whose counts are wrong.  *long_lines (may be NULL) = lines of 65 534 bytes or more incl. the newline: the
+ * reference throws there (AbstractFastaReader.java:104-106), the text is made all the same.  Bytes >= 0x80 are copied as they
+ * are (the reference's PrintStream widens them: the host layer's case).  *d_out: a device buffer of the handle's, valid until
+ * the next call with the same slot (0 / 1).  Synchronises the handle's stream, as gs_reads_compact_text does.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct gs_reads gs_reads;
+int gs_reads_create(gs_reads **out, int device);
+int gs_reads_destroy(gs_reads *reads);
+int gs_reads_get_device(gs_reads *reads, int *device);
+int gs_reads_sync(gs_reads *reads);
+/* profile != 0: from now on the FASTA -> FASTQ text kernels (sizes, offsets, copy) of gs_reads_compact_text and gs_reads_fasta2fastq
+ * run between events; launches / total_ms (may be NULL) = what they add up to so far.  Synchronises. */
+int gs_reads_kernel_time(gs_reads *reads, int profile, int64_t *launches, double *total_ms);
+/* What a profiling handle has measured so far, phase by phase, as time on its stream between events: [0] the select calls, from a
+ * chunk's submission to its flags (its way in, the record search, the descriptor compare); [1] the four-line gather of
+ * gs_reads_compact_text; [2] the FASTA -> FASTQ text kernels (as gs_reads_kernel_time).  Synchronises. */
+int gs_reads_phase_times(gs_reads *reads, int64_t launches[3], double total_ms[3]);
+int gs_reads_select_text(gs_reads *reads, int k, const uint8_t *text, int64_t n_bytes, int64_t n_lines, int mem, const uint8_t *key,
+                         int32_t key_len, uint8_t *accept, uint32_t *newlines, int64_t *ticket);
+int gs_reads_select_fasta(gs_reads *reads, int k, const uint8_t *text, int64_t n_bytes, int64_t n_lines, int64_t n_records, int mem,
+                          const uint8_t *key, int32_t key_len, uint8_t *accept, uint32_t *newlines, int64_t *ticket);
+int gs_reads_select_fastq_ml(gs_reads *reads, int k, const uint8_t *text, int64_t n_bytes, int64_t n_lines, int mem, const uint8_t *key,
+                             int32_t key_len, uint8_t *accept, uint32_t *newlines, int64_t *n_records, int64_t *consumed_bytes,
+                             int64_t *consumed_lines, int64_t *ticket);
+int gs_reads_compact_text(gs_reads *reads, int with_probs, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_records);
+int gs_reads_fasta2fastq(gs_reads *reads, const uint8_t *text, int64_t n_bytes, int64_t n_lines, int64_t n_records, int mem, int slot,
+                         const uint8_t **d_out, int64_t *n_bytes_out, int64_t *long_lines, int64_t *ticket);
+int gs_reads_text_read_bounds(gs_reads *reads, uint64_t *bounds);
+int gs_reads_text_line_classes(gs_reads *reads, uint8_t *classes);
+int gs_reads_text_wait_copy(gs_reads *reads, int64_t ticket);
+int gs_reads_text_status(gs_reads *reads, int64_t *failed_ticket, int64_t *first_bad_record, int64_t totals[3]);
+int gs_reads_text_reset(gs_reads *reads, int clear_totals);
+
+/* ---------------------------------------------------------------------------------------------------
  * Measurement support (no reference counterpart; not on the data path): the ceilings of the device the kernels run on,
  * measured with small calibration kernels at the match kernel's occupancy (8 waves per SIMD), so that a benchmark prices
  * its kernels against numbers taken in the same process on the same chip (bench.py `roofline`).

@@ -109,6 +109,23 @@ int gs_host_filter_files(gs_bloom *bloom, int k, int min_pos_count, double posit
                          int n_paths, const char *filtered_path, const char *rest_path, int with_probs,
                          gs_host_totals *totals);
 
+/* ---- extract (C/goals/ExtractGoal.java:73-129): every read of the files (in order; FASTQ or FASTA by suffix; plain, gzip or BGZF)
+ * whose descriptor behind its first byte starts with `key` (ByteArrayUtil.startsWith(readDescriptor, 1, key), :93) is written to
+ * out_path as ReadEntry.write does with the goal's withProbs = true; a name ending in .gz / .gzip is written as BGZF.  Readers,
+ * device inflaters and writers are those of gs_host_filter_files, the selection runs on the device (gs_reads_select_*); with
+ * GS_HOST_FAST=0 everything goes through the reference-exact parser and no device is used.  An empty key or a byte >= 0x80 in
+ * it: GS_E_INVALID.  totals: reads / kmers / bps as for the filter (k only feeds them), filtered_reads = reads written. ---- */
+int gs_host_extract_files(int device, const char *key, int k, const char *const *paths, int n_paths, const char *out_path,
+                          gs_host_totals *totals);
+
+/* ---- fasta2fastq (C/goals/Fasta2FastqGoal.java:92-165): the FASTA files, in order, into ONE four-line FASTQ file with '~'
+ * qualities (.gz / .gzip: BGZF).  Chunks of whole records are rewritten on the device (gs_reads_fasta2fastq); a record that does
+ * not fit a chunk, a file that does not start with '>', a NUL byte or a byte >= 0x80 (the reference's PrintStream widens those),
+ * the tail of a file without a final newline and everything under GS_HOST_FAST=0 (no device is used then) go through a plain loop
+ * that follows the reference line by line.  A line of 65 534 bytes or more: GS_E_INVALID (the reference throws).  *n_records
+ * (may be NULL) = header lines seen. ---- */
+int gs_host_fasta2fastq(int device, const char *const *paths, int n_paths, const char *out_path, int64_t *n_records);
+
 /* ---- db2fastq (C/goals/DB2FastqGoal.java, C/fastqgen/KMerFastqGenerator.java): the stored k-mers selected as by
  * gs_dbexport_create (sel_vi = -1: all -- the goal's "total" file; with_desc: the subtree of sel_vi -- a "taxid+" entry) written to
  * `path` in ascending k-mer order, one FASTQ record each as FastQWriter prints it (gs_dbexport_fastq_begin; taxids[n_values] =

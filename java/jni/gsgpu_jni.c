@@ -601,6 +601,38 @@ JNIEXPORT void JNICALL JNAME(hostFilterFiles)(JNIEnv *env, jclass c, jlong bloom
         put_totals(env, totals, &t);
 }
 
+/* gs_host_extract_files: the extract goal over local files (ExtractGoal.doMakeThis with writeFilteredFastq); totals[3] = reads written */
+JNIEXPORT void JNICALL JNAME(hostExtractFiles)(JNIEnv *env, jclass c, jint device, jstring key, jint k, jobjectArray paths, jstring outPath,
+                                               jlongArray totals) {
+    StrArray p = {0, NULL, NULL};
+    int rc = get_strings(env, paths, &p);
+    const char *ky = key ? (*env)->GetStringUTFChars(env, key, NULL) : NULL;
+    const char *out = outPath ? (*env)->GetStringUTFChars(env, outPath, NULL) : NULL;
+    gs_host_totals t;
+    memset(&t, 0, sizeof(t));
+    if (!rc) rc = gs_host_extract_files(device, ky, k, p.c, (int)p.n, out, &t);
+    if (ky) (*env)->ReleaseStringUTFChars(env, key, ky);
+    if (out) (*env)->ReleaseStringUTFChars(env, outPath, out);
+    free_strings(env, &p);
+    if (rc)
+        throw_host(env, rc);
+    else
+        put_totals(env, totals, &t);
+}
+
+/* gs_host_fasta2fastq: Fasta2FastqGoal.makeFile over local files; returns the records written */
+JNIEXPORT jlong JNICALL JNAME(hostFasta2Fastq)(JNIEnv *env, jclass c, jint device, jobjectArray paths, jstring outPath) {
+    StrArray p = {0, NULL, NULL};
+    int rc = get_strings(env, paths, &p);
+    const char *out = outPath ? (*env)->GetStringUTFChars(env, outPath, NULL) : NULL;
+    int64_t n = 0;
+    if (!rc) rc = gs_host_fasta2fastq(device, p.c, (int)p.n, out, &n);
+    if (out) (*env)->ReleaseStringUTFChars(env, outPath, out);
+    free_strings(env, &p);
+    if (rc) throw_host(env, rc);
+    return (jlong)n;
+}
+
 /* gs_host_last_error */
 JNIEXPORT jstring JNICALL JNAME(hostLastError)(JNIEnv *env, jclass c) { return (*env)->NewStringUTF(env, gs_host_last_error()); }
 

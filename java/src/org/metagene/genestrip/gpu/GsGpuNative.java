@@ -275,6 +275,15 @@ public final class GsGpuNative {
 	public static native void hostFilterFiles(long bloom, int k, int minPosCount, double positiveRatio, String[] paths,
 			String filteredPath, String restPath, boolean withProbs, long[] totals);
 
+	/** gs_host_extract_files: the extract goal over local files (FASTQ or FASTA by suffix; plain, gzip, BGZF): every read whose
+	 *  descriptor behind its first character starts with key goes to outPath (.gz = gzip) with its qualities; totals as above
+	 *  (totals[3] = reads written) */
+	public static native void hostExtractFiles(int device, String key, int k, String[] paths, String outPath, long[] totals);
+
+	/** gs_host_fasta2fastq: the fasta2fastq goal over local files: all of them into ONE four-line FASTQ file with '~' qualities
+	 *  (.gz = gzip); returns the records written */
+	public static native long hostFasta2Fastq(int device, String[] paths, String outPath);
+
 	/** gs_host_last_error: the message of the last failure inside the host layer on this thread */
 	public static native String hostLastError();
 
