@@ -1,9 +1,10 @@
 // gs_host.cpp -- C++ host layer above the C ABI (include/gshost.h): the runMatcher / runFilter file pipelines -- raw
 // text blocks to the device where the file allows it (TextJob), the reference-exact parser otherwise and as the
 // fallback -- with the Kraken-style and filtered-FASTQ writers.  The byte-level side (readers, parser, gzip decoder)
-// is in gs_ingest.h / gs_inflate.h, the CSV report in gs_report.cpp.  Plain C++17 + zlib; all GPU work goes through the
-// C ABI of include/gsgpu.h.
+// is in gs_ingest.h / gs_inflate.h, the cut of reader blocks into chunks of whole records in gs_chunk.h, the CSV report
+// in gs_report.cpp.  Plain C++17 + zlib; all GPU work goes through the C ABI of include/gsgpu.h.
 #include "gs_ingest.h"
+#include "gs_chunk.h"
 
 using namespace gs_host;
 
@@ -735,46 +736,43 @@ void append_general_record(std::vector<uint8_t> &o, const uint8_t *text, const u
     o.push_back('\n');
 }
 
-// Where a FASTA chunk may end inside a block: header lines ('>' at a line start) are counted by memchr over the block ('>' is
-// rare); the chunk ends in front of the block's last header line -- everything up to there is whole records --, at the end of
-// the file behind the final newline.  cut < 0: no record boundary in this block.
-struct FastaCut {
-    int64_t headers = 0;      // header lines that start inside the block
-    int64_t cut = -1;         // the chunk ends here (exclusive, offset in the block)
-    int64_t cut_headers = 0;  // headers in front of `cut`
-    int64_t tail_lines = 0;   // newlines at or behind `cut`
-};
+// `job` on a thread of its own, its result in `fut`; on this thread where no thread is to be had
+template <class T, class F>
+void run_behind(std::future<T> &fut, F job) {
+    try {
+        fut = std::async(std::launch::async, job);
+    } catch (const std::system_error &) {
+        fut = std::async(std::launch::deferred, job);
+        fut.wait();
+    }
+}
 
-FastaCut fasta_cut(const uint8_t *blk, int64_t n, bool last, const std::vector<uint8_t> &carry) {
-    FastaCut fc;
-    const bool at_line_start = carry.empty() || carry.back() == '\n';
-    int64_t last_hdr = -1;
-    for (const uint8_t *p = blk, *end = blk + n; p < end;) {
-        const uint8_t *q = (const uint8_t *)memchr(p, '>', (size_t)(end - p));
-        if (!q) break;
-        if (q == blk ? at_line_start : q[-1] == '\n') {
-            fc.headers++;
-            last_hdr = q - blk;
-        }
-        p = q + 1;
+// block size and reader / inflating threads of the text pipelines (GS_HOST_BLOCK_BYTES, GS_HOST_READERS); readers > 0 on entry: the
+// caller's own default.  Measured on the MI355X box (tools/file_rate_sweep.sh, 5 GB file in the page cache): 8 readers x 8 MiB blocks
+// 24.8 GB/s of file, 4 x 32 MiB 10.6 GB/s, 8 x 128 MiB 9.1 GB/s -- blocks that stay in the CPU caches between pread and the newline
+// count win
+void reader_shape(bool gzip, size_t *block, int *readers) {
+    *block = (size_t)8 << 20;
+    if (const char *e = getenv("GS_HOST_BLOCK_BYTES")) {
+        const long long v = atoll(e);
+        if (v >= 64 && v <= ((long long)1 << 29)) *block = (size_t)v;
     }
-    if (last && n > 0 && blk[n - 1] == '\n') {
-        fc.cut = n;
-        fc.cut_headers = fc.headers;
-    } else if (last && n == 0 && !carry.empty() && carry.back() == '\n') {
-        fc.cut = 0;
-    } else if (last_hdr > 0 || (last_hdr == 0 && !carry.empty())) {
-        fc.cut = last_hdr;
-        fc.cut_headers = fc.headers - 1;
+    if (*readers <= 0) *readers = (int)std::min<unsigned>(gzip ? 16 : 8, std::max<unsigned>(2, std::thread::hardware_concurrency() / 2));
+    if (const char *e = getenv("GS_HOST_READERS")) {
+        const int v = atoi(e);
+        if (v >= 1 && v <= 32) *readers = v;
     }
-    if (fc.cut >= 0)
-        for (const uint8_t *p = blk + fc.cut, *end = blk + n; p < end;) {
-            const uint8_t *q = (const uint8_t *)memchr(p, '\n', (size_t)(end - p));
-            if (!q) break;
-            fc.tail_lines++;
-            p = q + 1;
-        }
-    return fc;
+}
+
+// GS_OK, or what went wrong with the block the reader has just delivered
+int block_error(TextReader &tr, const TextSlot &sl, const std::string &path) {
+    if (!sl.io_error && tr.verify_gzip(sl)) return GS_OK;
+    return hfail(tr.gz ? GS_E_INVALID : GS_E_IO, (tr.gz ? "corrupt gzip stream in " : "read error on ") + path);
+}
+
+// the next chunk of a file out of reader block `sl` (ChunkCutter::next)
+ChunkCutter::Cut cut_block(ChunkCutter &cut, const TextReader &tr, const TextSlot &sl) {
+    return cut.next(sl.buf + tr.headroom, (int64_t)sl.n, sl.newlines, sl.last4, sl.eof, tr.headroom);
 }
 
 // device inflaters are kept for the life of the process, per device: their buffers (two text buffers, two staging buffers, page-locked
@@ -902,50 +900,187 @@ inline int64_t bgzf_text_target() {
     return t;
 }
 
+// What a device-inflated source hands out per call: n_lines whole four-line lines in n_bytes of text that lies on the device.
+struct DevText {
+    const uint8_t *text = nullptr;
+    int64_t n_bytes = 0, n_lines = 0;
+    bool last = false;   // the file is through: what lies behind the text is the leftover
+    bool stuck = false;  // no whole record and no end in sight: the general parser from here
+};
+
+// Block-gzip (BGZF) input: the members are listed from their headers, runs of them go to the device COMPRESSED and are inflated
+// there (gs_inflater_feed, one wave per member); the inflater keeps what lies behind a feed's last whole record for the next one.
+struct BgzfFeeds {
+    gs_inflater *inf = nullptr;
+    int device = 0;
+    const uint8_t *map = nullptr;
+    std::vector<gs_inflate_member> members;
+    size_t next_member = 0;
+    int64_t n_feeds = 0, tail = 0;
+    // the run of members from `from` whose text stays within the target (one member at least)
+    size_t run_end(size_t from, int64_t text_target) const {
+        int64_t sum = 0;
+        size_t e = from;
+        while (e < members.size() && (e == from || sum + members[e].isize <= text_target)) sum += members[e++].isize;
+        return e;
+    }
+    // the next run, and a look ahead at the one behind it (its compressed bytes are uploaded meanwhile)
+    int next(int64_t text_target, const std::string &path, DevText *t) {
+        const size_t a = next_member, b = run_end(a, text_target), b2 = run_end(b, text_target);
+        int64_t next_lo = 0, next_hi = 0;
+        if (b2 > b) {
+            next_lo = members[b].payload_offset;
+            next_hi = members[b2 - 1].payload_offset + (int64_t)members[b2 - 1].payload_len;
+        }
+        *t = DevText{};
+        t->last = b == members.size();
+        n_feeds++;
+        next_member = b;
+        if (gs_inflater_feed(inf, map, members.data() + a, (int64_t)(b - a), next_lo, next_hi, t->last ? 1 : 0, &t->text, &t->n_bytes, &t->n_lines, &tail) != GS_OK)
+            return hfail(GS_E_INVALID, std::string("corrupt gzip stream in ") + path + ": " + gs_inflate_last_error());
+        t->stuck = t->n_lines == 0 && tail > ((int64_t)256 << 20) && !t->last;  // no record boundary in a quarter of a gigabyte
+        return GS_OK;
+    }
+    int fetch_text(uint8_t *dst, int64_t n_bytes) { return gs_inflater_fetch(inf, dst, n_bytes) == GS_OK ? (int)GS_OK : hfail(GS_E_HIP, gs_inflate_last_error()); }
+    // what is left behind the last whole record
+    int fetch_tail(std::vector<uint8_t> &carry) {
+        int64_t n = 0;
+        carry.resize((size_t)tail);
+        return tail == 0 || gs_inflater_tail(inf, carry.data(), tail, &n) == GS_OK ? (int)GS_OK : hfail(GS_E_HIP, gs_inflate_last_error());
+    }
+    void close() {
+        if (inf) inflater_pool().put(device, inf);
+        inf = nullptr;
+    }
+};
+
+// A gzip stream inflated on the device as a whole (gs_gunzip_plan_device: block starts found speculatively, segments decoded side by
+// side, windows resolved in a second pass; members behind one another each with their own CRC-32 / ISIZE): its text lies in HBM,
+// batch after batch (gs_gunzipper_next), and is handed on in slices of whole four-line records.
+struct GunzipSlices {
+    gs_gunzipper *gzr = nullptr;
+    int device = 0;
+    const uint8_t *gz_text = nullptr;  // the current batch
+    int64_t gz_n = 0, gz_off = 0;
+    int gz_last = 0;  // 1: the current batch is the file's last
+    // The next slice: whole records up to the feed size, from this batch or with the next one behind what is left of this.  A new
+    // batch replaces the text of the last: before_replace() (may be null) waits for whoever still reads that.  *refused: a batch the
+    // device path does not take -- the host decoders from the start of what was left.
+    int next(int64_t text_target, const std::string &path, const std::function<int()> &before_replace, DevText *t, bool *refused) {
+        *t = DevText{};
+        *refused = false;
+        for (;;) {
+            const int64_t rest = gz_n - gz_off, look = std::min(rest, text_target);
+            t->n_lines = t->n_bytes = 0;
+            if (look > 0 && gs_text_cut_device(device, gz_text + gz_off, look, &t->n_lines, &t->n_bytes) != GS_OK) return hfail(GS_E_HIP, gs_inflate_last_error());
+            if (t->n_lines > 0 || gz_last || look < rest) break;  // (look < rest: a full slice without a record -- `stuck`, below)
+            if (before_replace) {
+                const int err = before_replace();
+                if (err) return err;
+            }
+            const int grc = gs_gunzipper_next(gzr, rest, &gz_text, &gz_n, &gz_last);
+            gz_off = 0;
+            if (grc == GS_E_UNSUPPORTED || grc == GS_E_NOMEM) {  // (the tail that was kept belongs to the host decoders as well)
+                gz_n = 0;
+                *refused = true;
+                return GS_OK;
+            }
+            if (grc != GS_OK) return hfail(GS_E_INVALID, std::string("corrupt gzip stream in ") + path + ": " + gs_inflate_last_error());
+        }
+        const int64_t rest = gz_n - gz_off;
+        t->last = gz_last != 0 && std::min(rest, text_target) == rest;
+        t->stuck = t->n_lines == 0 && !t->last;
+        t->text = gz_text + gz_off;
+        gz_off += t->n_bytes;
+        return GS_OK;
+    }
+    int fetch_text(const DevText &t, uint8_t *dst) { return gs_device_fetch(device, t.text, dst, t.n_bytes) == GS_OK ? (int)GS_OK : hfail(GS_E_HIP, gs_inflate_last_error()); }
+    // what is left behind the last slice
+    int fetch_leftover(std::vector<uint8_t> &carry) {
+        const int64_t n = gz_n - gz_off;
+        carry.resize((size_t)n);
+        return n == 0 || gs_device_fetch(device, gz_text + gz_off, carry.data(), n) == GS_OK ? (int)GS_OK : hfail(GS_E_HIP, gs_inflate_last_error());
+    }
+    // Back to the pool, which parks the upload thread: it copies from the mapped file (a stream of up to 16 GiB is uploaded whole
+    // while the batches run), so this comes BEFORE the file is unmapped -- and after everybody is through with the device text.
+    void close() {
+        if (gzr) gunzipper_pool().put(device, gzr);
+        gzr = nullptr;
+        gz_text = nullptr;
+        gz_n = gz_off = 0;
+    }
+};
+
+// Whether and how a gzip file of four-line FASTQ is inflated on the device: block-gzip by its members, any other stream as a whole,
+// or not at all -- GS_DEVICE_INFLATE=0, GS_DEVICE_GUNZIP=0 (whole streams), no pooled object to be had, or a stream the device path
+// does not take (a damaged one too): the host decoders then inflate it as before, and report it.  close() before the file is unmapped.
+struct DeviceInflate {
+    BgzfFeeds feeds;
+    GunzipSlices slices;
+    bool bgzf() const { return feeds.inf != nullptr; }
+    bool whole() const { return slices.gzr != nullptr; }
+    // first_span: compressed bytes of a whole stream's first batch, the only one that waits for its bytes to cross PCIe
+    void open(const uint8_t *map, size_t map_len, int device, int64_t first_span) {
+        bool want = true, want_whole = true;
+        if (const char *e = getenv("GS_DEVICE_INFLATE")) want = atoi(e) != 0;
+        if (const char *e = getenv("GS_DEVICE_GUNZIP")) want_whole = atoi(e) != 0;
+        if (!want || map_len < 18) return;
+        if (map_len >= 28 && bgzf_member_list(map, map_len, feeds.members)) {
+            feeds.inf = inflater_pool().get(device);
+            feeds.device = device;
+            feeds.map = map;
+            return;
+        }
+        feeds.members.clear();
+        if (!want_whole) return;
+        static const bool trace = getenv("GS_HOST_TRACE") != nullptr;
+        const double tg = now_s();
+        slices.device = device;
+        int grc = gunzipper_pool().open(&slices.gzr, device, map, (int64_t)map_len);
+        if (grc == GS_OK) grc = gs_gunzipper_first_span(slices.gzr, first_span);
+        if (grc == GS_OK) grc = gs_gunzipper_next(slices.gzr, 0, &slices.gz_text, &slices.gz_n, &slices.gz_last);  // (the first batch now: a stream this path does not take shows here)
+        if (trace)
+            fprintf(stderr, "gunzip on the device: rc %d, first batch %lld bytes of text, %.2f ms%s%s\n", grc, (long long)slices.gz_n, (now_s() - tg) * 1e3, grc ? ": " : "",
+                    grc ? gs_inflate_last_error() : "");
+        if (grc != GS_OK) slices.close();
+    }
+    void close() {
+        slices.close();
+        feeds.close();
+    }
+};
+
 struct TextJob {
     MatchCtx &c;
     std::string path;
     int bank;
     int64_t read_no;  // number of the next read of this file
     TextReader tr;
-    std::vector<uint8_t> carry;
+    // The reader's blocks into chunks of whole records; cut_.carry is what lies behind the last chunk and cut_.file_off where it
+    // starts, for the device-inflated sources too (their leftover comes to the host once, at the end of the file).
+    // FASTA files (AbstractFastqReader.doReadFasta): chunks are cut in front of a header line, the device finds the records
+    // (gs_match_submit_fasta).  General FASTQ (sequence / quality over several lines): chunks of whole lines that start at a record's
+    // descriptor line; the device finds the records (gs_match_submit_fastq_ml) and says how much of the chunk they cover, the rest is
+    // carried into the next one.  A FASTQ file whose first chunk is not four-line FASTQ is read again this way (finish()).
+    ChunkCutter cut_;
     std::vector<TextChunk> chunks;
-    int64_t carry_lines = 0, reads_in_file = 0, carry_file_off = 0, first_ticket = -1, next_block = 0;
+    int64_t reads_in_file = 0, first_ticket = -1, next_block = 0;
     int64_t base_tot[3] = {0, 0, 0}, tot[3] = {0, 0, 0};
     bool done = false;
     double t0 = 0;
     std::future<void> formatting;  // per-read outputs of the previous chunk on their way to the writers
     int64_t n_formatted = 0;
     int64_t held_ticket = -1, held_block = -1;
-    // FASTA files (AbstractFastqReader.doReadFasta): chunks are cut in front of a header line, the device finds the
-    // records (gs_match_submit_fasta); no per-read outputs on this path
-    bool fasta = false;
-    int64_t carry_headers = 0;
-    // general FASTQ (sequence / quality over several lines): chunks of whole lines that start at a record's descriptor line; the
-    // device finds the records (gs_match_submit_fastq_ml) and says how much of the chunk they cover, the rest is carried into the
-    // next one.  A FASTQ file whose first chunk is not four-line FASTQ is read again this way (finish()); no per-read outputs.
-    bool general = false;
+    bool fasta = false, general = false;
     bool gz_ = false;
     int readers_ = 2;
-    // block-gzip (BGZF) input: the members are listed from their headers, the COMPRESSED bytes go to the device and are inflated
-    // there (gs_inflater_feed, one wave per member); without per-read outputs the text never exists on the host, with them
-    // (Kraken-style lines, filtered FASTQ) it comes back once per feed, page-locked, for the writers.  What the device path cannot
-    // take (a chunk the record scan refuses, the unterminated tail of the file) goes the usual way.
-    bool dev_bgzf = false;
-    gs_inflater *inf_ = nullptr;
-    int inf_device_ = 0;
-    std::vector<gs_inflate_member> members_;
-    size_t next_member_ = 0;
-    int64_t dev_tickets_[2] = {-1, -1};
-    int64_t n_feeds_ = 0;
-    PooledBuf dev_text_[2];  // the text of a feed on the host, for the per-read writers
-    // a single-member gzip file inflated on the device as a whole (gs_gunzip_plan_device): its text lies in HBM, step_gunzip hands it
-    // to the record scan in slices of whole records
-    bool dev_gz = false;
-    gs_gunzipper *gzr_ = nullptr;
-    const uint8_t *gz_text_ = nullptr;  // the current batch (gs_gunzipper_next)
-    int64_t gz_n_ = 0, gz_off_ = 0, gz_ticket_ = -1;
-    int gz_last_ = 0;                   // 1: the file is through (members behind one another are decoded on the device, each with its own CRC-32 / ISIZE)
+    // gzip input of four-line FASTQ inflated on the device (DeviceInflate): without per-read outputs the text never exists on the host,
+    // with them (Kraken-style lines, filtered FASTQ) it comes back once per chunk, page-locked, for the writers.  What the device path
+    // cannot take (a chunk the record scan refuses, the unterminated tail of the file) goes the usual way.
+    DeviceInflate dev_;
+    int64_t dev_tickets_[2] = {-1, -1};  // BGZF: the record scan's copy out of the feed's text
+    int64_t gz_ticket_ = -1;             // whole stream: ... out of the batch's text
+    PooledBuf dev_text_[2];              // the text of a chunk on the host, for the per-read writers
 
     TextJob(MatchCtx &ctx, const std::string &p, int bank_, int64_t first_read_no, bool fasta_ = false)
         : c(ctx), path(p), bank(bank_), read_no(first_read_no), fasta(fasta_) {}
@@ -956,24 +1091,15 @@ struct TextJob {
         release_held();
         release_gunzipper();  // (before the file is unmapped: its upload thread reads the mapping)
         tr.close();
-        if (inf_) {
-            inflater_pool().put(inf_device_, inf_);
-            inf_ = nullptr;
-        }
+        dev_.close();
     }
-    // The device gunzipper goes back to its pool -- which parks its upload thread -- BEFORE tr.close() unmaps the file the thread
-    // is copying from (a stream of up to 16 GiB is uploaded whole while the batches run; finish() is reached mid-stream by every
-    // refusal or fallback).  Its device text stays valid until the object is reopened.
+    // The device gunzipper goes back to its pool BEFORE tr.close() unmaps the file (GunzipSlices::close; finish() is reached
+    // mid-stream by every refusal or fallback).  Its device text stays valid until the object is reopened.
     void release_gunzipper() {
-        if (!gzr_) return;
+        if (!dev_.whole()) return;
         gs_match_sync(c.run);  // (the record scan may still be copying out of its text)
-        gunzipper_pool().put(inf_device_, gzr_);
-        gzr_ = nullptr;
-        gz_text_ = nullptr;
-        gz_n_ = gz_off_ = 0;
+        dev_.slices.close();
     }
-
-    bool list_bgzf_members() { return bgzf_member_list(tr.map, tr.map_len, members_); }
 
     // the four-line FASTQ chunk that was just submitted: first read number, reads; its descriptor lines are fetched from the device
     int chunk_submitted(int64_t first_no, int64_t n_reads) {
@@ -1030,286 +1156,148 @@ struct TextJob {
             const int e = c.filtered_dev.emit(set, d, nb);
             if (e) dev_err_ = e;
         };
-        try {
-            formatting = std::async(std::launch::async, job);
-        } catch (const std::system_error &) {  // no thread to be had: on this one
-            job();
-        }
+        run_behind(formatting, job);
         return GS_OK;
     }
 
     int open(bool gzip, int readers) {
-        // measured on the MI355X box (tools/file_rate_sweep.sh, 5 GB file in the page cache): 8 readers x 8 MiB blocks
-        // 24.8 GB/s of file, 4 x 32 MiB 10.6 GB/s, 8 x 128 MiB 9.1 GB/s -- blocks that stay in the CPU caches between
-        // pread and the newline count win
-        size_t block = (size_t)8 << 20;
-        if (const char *e = getenv("GS_HOST_BLOCK_BYTES")) {
-            const long long v = atoll(e);
-            if (v >= 64 && v <= ((long long)1 << 29)) block = (size_t)v;
-        }
-        if (const char *e = getenv("GS_HOST_READERS")) {
-            const int v = atoi(e);
-            if (v >= 1 && v <= 32) readers = v;
-        }
+        size_t block;
+        reader_shape(gzip, &block, &readers);
         t0 = now_s();
         gz_ = gzip;
         readers_ = readers;
+        cut_.mode = general ? ChunkCutter::GENERAL : (fasta ? ChunkCutter::FASTA : ChunkCutter::FOUR_LINE);
         int err = tr.open(path, block, readers, gzip);
         if (!err) err = gs_match_text_select(c.run, bank);
         int64_t failed = -1, bad = -1;
         if (!err) err = gs_match_text_status(c.run, &failed, &bad, base_tot);  // totals this bank has seen before
-        if (!err && gzip && !fasta && !general) {
-            bool want = true;
-            if (const char *e = getenv("GS_DEVICE_INFLATE")) want = atoi(e) != 0;
-            if (want && tr.map_len >= 28 && list_bgzf_members()) {
-                int device = 0;
-                if (gs_match_get_device(c.run, &device) == GS_OK && (inf_ = inflater_pool().get(device)) != nullptr) {
-                    inf_device_ = device;
-                    dev_bgzf = true;
-                }
-            }
-        }
-        if (!err && gzip && !fasta && !general && !dev_bgzf && tr.map_len >= 18) {
-            // not block-gzip: a single-member stream (gzip, pigz) is inflated on the device as a whole -- block starts found speculatively,
-            // segments decoded side by side, windows resolved in a second pass.  Whatever that path does not take (several members, a
-            // damaged stream: the host decoders report it) is inflated on the host as before.
-            bool want = true;
-            if (const char *e = getenv("GS_DEVICE_INFLATE")) want = atoi(e) != 0;
-            if (const char *e = getenv("GS_DEVICE_GUNZIP")) want = want && atoi(e) != 0;
-            int device = 0;
-            if (want && gs_match_get_device(c.run, &device) == GS_OK) {
-                static const bool trace = getenv("GS_HOST_TRACE") != nullptr;
-                const double tg = now_s();
-                int grc = gunzipper_pool().open(&gzr_, device, tr.map, (int64_t)tr.map_len);
-                // (writers behind this job: a small first batch, so that they start after 10 ms and not after the 27 a full batch takes)
-                if (grc == GS_OK) grc = gs_gunzipper_first_span(gzr_, (c.filtered.active() || c.kraken.active()) ? gunzip_first_span() : gunzip_first_span_match());
-                if (grc == GS_OK) grc = gs_gunzipper_next(gzr_, 0, &gz_text_, &gz_n_, &gz_last_);  // (the first batch now: a stream this path does not take shows here)
-                if (trace) fprintf(stderr, "gunzip on the device: rc %d, first batch %lld bytes of text, %.2f ms%s%s\n", grc, (long long)gz_n_, (now_s() - tg) * 1e3, grc ? ": " : "", grc ? gs_inflate_last_error() : "");
-                if (grc == GS_OK) {
-                    dev_gz = true;
-                    inf_device_ = device;
-                } else if (gzr_) {
-                    gunzipper_pool().put(device, gzr_);
-                    gzr_ = nullptr;
-                    gz_text_ = nullptr;
-                    gz_n_ = 0;
-                }
-            }
-        }
-        if (!err && c.filtered.active()) {
-            int device = 0;
-            if (gs_match_get_device(c.run, &device) == GS_OK) c.filtered_dev.begin(&c.filtered, device);
-        }
-        if (!err && !dev_bgzf && !dev_gz) tr.start();
+        int device = 0;
+        // (writers behind this job: a small first batch, so that they start after 10 ms and not after the 27 a full batch takes)
+        if (!err && gzip && !fasta && !general && gs_match_get_device(c.run, &device) == GS_OK)
+            dev_.open(tr.map, tr.map_len, device, (c.filtered.active() || c.kraken.active()) ? gunzip_first_span() : gunzip_first_span_match());
+        if (!err && c.filtered.active() && gs_match_get_device(c.run, &device) == GS_OK) c.filtered_dev.begin(&c.filtered, device);
+        if (!err && !dev_.bgzf() && !dev_.whole()) tr.start();
         return err;
     }
 
-    // the next slice of the device text: whole four-line records up to the feed size, the leftover of the last slice to the host
-    int step_gunzip(int *err_out) {
-        int err = GS_OK;
+    // text per chunk of a device-inflated source (GS_HOST_BGZF_TEXT): a wave inflates a member in ~6 ms whatever else runs, so the
+    // rate is the number of members under way -- 512 MiB are ~8000 members, two rounds over the device's wave slots; with writers
+    // behind it a chunk is 128 MiB of text: they start four times earlier (as filter_bgzf_file)
+    int64_t device_text_target() const {
         const bool per_read = c.filtered.active() || c.kraken.active();
-        const int64_t text_target = per_read && !getenv("GS_HOST_BGZF_TEXT") ? ((int64_t)128 << 20) : bgzf_text_target();
+        return per_read && !getenv("GS_HOST_BGZF_TEXT") ? ((int64_t)128 << 20) : bgzf_text_target();
+    }
+    void fall_back(int64_t *fallback_off, int64_t *fallback_reads) const {
+        *fallback_off = cut_.file_off;
+        *fallback_reads = reads_in_file;
+    }
+
+    // A four-line chunk whose text lies on the device, through the match kernel.  With per-read outputs the writers need the chunk's
+    // results and its text: class / flags come to host arrays (GS_MEM_DEVICE_TEXT), fetch_text(dst) brings the text while the match
+    // kernel runs, then the chunk is formatted on a thread of its own.  Without them the record scan takes its own copy of the text
+    // (device to device): *scan_ticket, the caller's, says when that copy is through.
+    int device_chunk(const DevText &t, const std::function<int(uint8_t *)> &fetch_text, int64_t *scan_ticket, int64_t *fallback_off, int64_t *fallback_reads) {
+        const int64_t n_chunk = t.n_lines >> 2, first_no = read_no + reads_in_file;
+        int64_t ticket = -1;
+        if (!(c.filtered.active() || c.kraken.active())) {
+            int err = gs_match_submit_text(c.run, t.text, t.n_bytes, t.n_lines, GS_MEM_DEVICE, first_no, nullptr, nullptr, &ticket);
+            if (!err) err = chunk_submitted(first_no, n_chunk);
+            if (err) return err;
+            *scan_ticket = ticket;
+            if (first_ticket < 0) first_ticket = ticket;
+            chunks.push_back({cut_.file_off, reads_in_file, ticket});
+            reads_in_file += n_chunk;
+            cut_.file_off += t.n_bytes;
+            return chunks.size() == 1 || (chunks.size() & 15) == 0 ? check_refusal(fallback_off, fallback_reads) : (int)GS_OK;
+        }
+        MatchCtx::Results &rs = c.res[n_formatted & 1];  // (the set of the chunk before last: its writers are done)
+        PooledBuf &tb = dev_text_[n_formatted & 1];
+        const bool dev_f = device_filtered();
+        int err = rs.cls.resize((size_t)n_chunk);
+        if (!err) err = rs.flags.resize((size_t)n_chunk);
+        if (!err && !dev_f) err = tb.need((size_t)t.n_bytes);
+        if (!err) err = gs_match_submit_text(c.run, t.text, t.n_bytes, t.n_lines, GS_MEM_DEVICE_TEXT, first_no, rs.cls.data(), rs.flags.data(), &ticket);
+        if (!err) err = chunk_submitted(first_no, n_chunk);
+        if (!err && !dev_f) err = fetch_text(static_cast<uint8_t *>(tb.p));
+        if (err) return err;
+        chunks.push_back({cut_.file_off, reads_in_file, ticket});
+        err = check_refusal(fallback_off, fallback_reads);  // (synchronises: the results are needed now)
+        if (!err && *fallback_off < 0 && !dev_f) err = fetch_chunk_results(rs, n_chunk);
+        if (err || *fallback_off >= 0) {
+            chunks.pop_back();
+            return err;
+        }
+        if (first_ticket < 0) first_ticket = ticket;
+        reads_in_file += n_chunk;
+        cut_.file_off += t.n_bytes;
+        if (dev_f) return emit_filtered_device();
+        drain();  // one chunk at a time: output order, and the other result set becomes free
+        n_formatted++;
+        const uint8_t *h_text = static_cast<const uint8_t *>(tb.p);
+        run_behind(formatting, [this, &rs, h_text, n_chunk] { format_chunk(rs, h_text, n_chunk, -1); });
+        return GS_OK;
+    }
+
+    // the next slice of the device text: whole four-line records up to the chunk size, the leftover of the last slice to the host
+    int step_gunzip(int *err_out) {
         int64_t fallback_off = -1, fallback_reads = 0;
-        int64_t n_lines = 0, n_bytes = 0;
         static const bool trace = getenv("GS_HOST_TRACE") != nullptr;
         const double ts0 = now_s();
-        for (;;) {  // a slice with a whole record in it: from this batch, or with the next one behind what is left of this
-            const int64_t rest = gz_n_ - gz_off_, look = std::min(rest, text_target);
-            n_lines = n_bytes = 0;
-            if (look > 0 && gs_text_cut_device(inf_device_, gz_text_ + gz_off_, look, &n_lines, &n_bytes) != GS_OK) err = hfail(GS_E_HIP, gs_inflate_last_error());
-            if (err || n_lines > 0 || gz_last_ || look < rest) break;  // (look < rest: a full slice without a record -- the general parser, below)
-            if (gz_ticket_ >= 0) {  // the scan's copy out of this batch's text must be through before the text is replaced
-                err = gs_match_text_wait_copy(c.run, gz_ticket_);
-                gz_ticket_ = -1;
-                if (err) break;
-            }
-            const int grc = gs_gunzipper_next(gzr_, rest, &gz_text_, &gz_n_, &gz_last_);
-            gz_off_ = 0;
-            if (grc == GS_E_UNSUPPORTED || grc == GS_E_NOMEM) {  // from here on the host decoders (the tail that was kept belongs to them as well)
-                fallback_off = carry_file_off;
-                fallback_reads = reads_in_file;
-                gz_n_ = 0;
-                break;
-            }
-            if (grc != GS_OK) {
-                err = hfail(GS_E_INVALID, std::string("corrupt gzip stream in ") + path + ": " + gs_inflate_last_error());
-                break;
-            }
-        }
-        const int64_t rest = gz_n_ - gz_off_;
-        const bool last = gz_last_ != 0 && std::min(rest, text_target) == rest;
-        const uint8_t *text = gz_text_ + gz_off_;
+        DevText t;
+        bool refused = false;
+        // (the scan's copy out of a batch's text must be through before the text is replaced)
+        int err = dev_.slices.next(device_text_target(), path, [this] {
+            const int e = gz_ticket_ >= 0 ? gs_match_text_wait_copy(c.run, gz_ticket_) : (int)GS_OK;
+            gz_ticket_ = -1;
+            return e;
+        }, &t, &refused);
         const double ts1 = now_s();
         if (!err) err = gs_match_text_select(c.run, bank);
-        if (!err && n_lines > 0 && per_read) {
-            const int64_t n_chunk = n_lines >> 2;
-            MatchCtx::Results &rs = c.res[n_formatted & 1];  // (the set of the chunk before last: its writers are done)
-            PooledBuf &tb = dev_text_[n_formatted & 1];
-            int64_t ticket = -1;
-            const bool dev_f = device_filtered();
-            err = rs.cls.resize((size_t)n_chunk);
-            if (!err) err = rs.flags.resize((size_t)n_chunk);
-            if (!err && !dev_f) err = tb.need((size_t)n_bytes);
-            if (!err) err = gs_match_submit_text(c.run, text, n_bytes, n_lines, GS_MEM_DEVICE_TEXT, read_no + reads_in_file, rs.cls.data(), rs.flags.data(), &ticket);
-            if (!err) err = chunk_submitted(read_no + reads_in_file, n_chunk);
-            if (!err && !dev_f && gs_device_fetch(inf_device_, text, static_cast<uint8_t *>(tb.p), n_bytes) != GS_OK) err = hfail(GS_E_HIP, gs_inflate_last_error());
-            if (!err) {
-                chunks.push_back({carry_file_off, reads_in_file, ticket});
-                err = check_refusal(&fallback_off, &fallback_reads);  // (synchronises: the results are needed now)
-                if (!err && fallback_off < 0 && !dev_f) err = fetch_chunk_results(rs, n_chunk);
-                if (err || fallback_off >= 0) chunks.pop_back();
-            }
-            if (!err && fallback_off < 0 && dev_f) {
-                if (first_ticket < 0) first_ticket = ticket;
-                reads_in_file += n_chunk;
-                carry_file_off += n_bytes;
-                err = emit_filtered_device();
-            } else if (!err && fallback_off < 0) {
-                if (first_ticket < 0) first_ticket = ticket;
-                reads_in_file += n_chunk;
-                carry_file_off += n_bytes;
-                drain();  // one chunk at a time: output order, and the other result set becomes free
-                n_formatted++;
-                const uint8_t *h_text = static_cast<const uint8_t *>(tb.p);
-                try {
-                    formatting = std::async(std::launch::async, [this, &rs, h_text, n_chunk] { format_chunk(rs, h_text, n_chunk, -1); });
-                } catch (const std::system_error &) {  // no thread to be had: on this one
-                    format_chunk(rs, h_text, n_chunk, -1);
-                }
-            }
-        } else if (!err && n_lines > 0) {
-            int64_t ticket = -1;
-            err = gs_match_submit_text(c.run, text, n_bytes, n_lines, GS_MEM_DEVICE, read_no + reads_in_file, nullptr, nullptr, &ticket);
-            if (!err) err = chunk_submitted(read_no + reads_in_file, n_lines >> 2);
-            if (!err) {
-                gz_ticket_ = ticket;
-                if (first_ticket < 0) first_ticket = ticket;
-                chunks.push_back({carry_file_off, reads_in_file, ticket});
-                reads_in_file += n_lines >> 2;
-                carry_file_off += n_bytes;
-                if (chunks.size() == 1 || (chunks.size() & 15) == 0) err = check_refusal(&fallback_off, &fallback_reads);
-            }
-        } else if (!err && fallback_off < 0 && !last) {  // not one whole record in a full slice: the general parser
-            fallback_off = carry_file_off;
-            fallback_reads = reads_in_file;
+        if (!err && (refused || t.stuck))
+            fall_back(&fallback_off, &fallback_reads);
+        else if (!err && t.n_lines > 0) {
+            GunzipSlices &sl = dev_.slices;
+            err = device_chunk(t, [&sl, &t](uint8_t *dst) { return sl.fetch_text(t, dst); }, &gz_ticket_, &fallback_off, &fallback_reads);
         }
-        if (!err && fallback_off < 0) gz_off_ += n_bytes;
         const double ts2 = now_s();
-        if (err || last || fallback_off >= 0) {
-            if (!err && fallback_off < 0 && gz_off_ < gz_n_) {  // what is left behind the last whole record
-                carry.resize((size_t)(gz_n_ - gz_off_));
-                if (gs_device_fetch(inf_device_, gz_text_ + gz_off_, carry.data(), gz_n_ - gz_off_) != GS_OK) err = hfail(GS_E_HIP, gs_inflate_last_error());
-            }
+        if (err || t.last || fallback_off >= 0) {
+            if (!err && fallback_off < 0) err = dev_.slices.fetch_leftover(cut_.carry);  // what is left behind the last whole record
             err = finish(err, fallback_off, fallback_reads);
         }
         if (trace)
-            fprintf(stderr, "gunzip slice: %lld bytes, %lld lines: cut (+ next batch) %.2f ms, submit %.2f ms, finish %.2f ms\n", (long long)n_bytes, (long long)n_lines, (ts1 - ts0) * 1e3,
-                    (ts2 - ts1) * 1e3, (now_s() - ts2) * 1e3);
+            fprintf(stderr, "gunzip slice: %lld bytes, %lld lines: cut (+ next batch) %.2f ms, submit %.2f ms, finish %.2f ms\n", (long long)t.n_bytes, (long long)t.n_lines,
+                    (ts1 - ts0) * 1e3, (ts2 - ts1) * 1e3, (now_s() - ts2) * 1e3);
         *err_out = err;
         return 1;
     }
 
     // one run of members: inflate on the device, submit the whole records, carry the rest (on the device)
     int step_bgzf(int *err_out) {
-        int err = GS_OK;
-        // text per feed: a wave inflates a member in ~6 ms whatever else runs, so the rate is the number of members under way --
-        // 512 MiB are ~8000 members, two rounds over the device's wave slots
-        const bool per_read = c.filtered.active() || c.kraken.active();
-        // (with writers behind it a feed is 128 MiB of text, not 512: they start four times earlier -- as filter_bgzf_file)
-        const int64_t text_target = per_read && !getenv("GS_HOST_BGZF_TEXT") ? ((int64_t)128 << 20) : bgzf_text_target();
-        auto run_end = [&](size_t from) {
-            int64_t sum = 0;
-            size_t e = from;
-            while (e < members_.size() && (e == from || sum + members_[e].isize <= text_target)) sum += members_[e++].isize;
-            return e;
-        };
-        const size_t a = next_member_, b = run_end(a), b2 = run_end(b);
-        const bool last = b == members_.size();
-        int64_t next_lo = 0, next_hi = 0;
-        if (b2 > b) {
-            next_lo = members_[b].payload_offset;
-            next_hi = members_[b2 - 1].payload_offset + (int64_t)members_[b2 - 1].payload_len;
-        }
         // The previous feed's text went to the device scan, which takes its own copy (device to device, a fraction of a
         // millisecond): that copy must be through before this feed runs -- the feed ends by moving its leftover into the OTHER
         // text buffer, which is the one the scan is copying from.
-        const int slot = 0;
-        if (dev_tickets_[slot] >= 0) {
-            err = gs_match_text_wait_copy(c.run, dev_tickets_[slot]);
-            dev_tickets_[slot] = -1;
+        int err = GS_OK;
+        if (dev_tickets_[0] >= 0) {
+            err = gs_match_text_wait_copy(c.run, dev_tickets_[0]);
+            dev_tickets_[0] = -1;
         }
-        const uint8_t *text = nullptr;
-        int64_t n_bytes = 0, n_lines = 0, tail = 0;
         int64_t fallback_off = -1, fallback_reads = 0;
         static const bool trace = getenv("GS_HOST_TRACE") != nullptr;
         const double tt0 = now_s();
-        if (!err && gs_inflater_feed(inf_, tr.map, members_.data() + a, (int64_t)(b - a), next_lo, next_hi, last ? 1 : 0, &text, &n_bytes, &n_lines, &tail) != GS_OK)
-            err = hfail(GS_E_INVALID, std::string("corrupt gzip stream in ") + path + ": " + gs_inflate_last_error());
-        n_feeds_++;
-        next_member_ = b;
+        BgzfFeeds &fd = dev_.feeds;
+        DevText t;
+        if (!err) err = fd.next(device_text_target(), path, &t);
         const double tt1 = now_s();
         if (!err) err = gs_match_text_select(c.run, bank);
-        if (!err && n_lines > 0 && per_read) {
-            // the writers need the chunk's results and its text: class / flags come to host arrays (GS_MEM_DEVICE_TEXT), the text of
-            // the feed is fetched while the match kernel runs, then the chunk is formatted on a thread of its own
-            const int64_t n_chunk = n_lines >> 2;
-            MatchCtx::Results &rs = c.res[n_formatted & 1];  // (the set of the chunk before last: its writers are done)
-            PooledBuf &tb = dev_text_[n_formatted & 1];
-            int64_t ticket = -1;
-            const bool dev_f = device_filtered();
-            err = rs.cls.resize((size_t)n_chunk);
-            if (!err) err = rs.flags.resize((size_t)n_chunk);
-            if (!err && !dev_f) err = tb.need((size_t)n_bytes);
-            if (!err) err = gs_match_submit_text(c.run, text, n_bytes, n_lines, GS_MEM_DEVICE_TEXT, read_no + reads_in_file, rs.cls.data(), rs.flags.data(), &ticket);
-            if (!err) err = chunk_submitted(read_no + reads_in_file, n_chunk);
-            if (!err && !dev_f && gs_inflater_fetch(inf_, static_cast<uint8_t *>(tb.p), n_bytes) != GS_OK) err = hfail(GS_E_HIP, gs_inflate_last_error());
-            if (!err) {
-                chunks.push_back({carry_file_off, reads_in_file, ticket});
-                err = check_refusal(&fallback_off, &fallback_reads);  // (synchronises: the results are needed now)
-                if (!err && fallback_off < 0 && !dev_f) err = fetch_chunk_results(rs, n_chunk);
-                if (err || fallback_off >= 0) chunks.pop_back();
-            }
-            if (!err && fallback_off < 0 && dev_f) {
-                if (first_ticket < 0) first_ticket = ticket;
-                reads_in_file += n_chunk;
-                carry_file_off += n_bytes;
-                err = emit_filtered_device();
-            } else if (!err && fallback_off < 0) {
-                if (first_ticket < 0) first_ticket = ticket;
-                reads_in_file += n_chunk;
-                carry_file_off += n_bytes;
-                drain();  // one chunk at a time: output order, and the other result set becomes free
-                n_formatted++;
-                const uint8_t *h_text = static_cast<const uint8_t *>(tb.p);
-                try {
-                    formatting = std::async(std::launch::async, [this, &rs, h_text, n_chunk] { format_chunk(rs, h_text, n_chunk, -1); });
-                } catch (const std::system_error &) {  // no thread to be had: on this one
-                    format_chunk(rs, h_text, n_chunk, -1);
-                }
-            }
-        } else if (!err && n_lines > 0) {
-            int64_t ticket = -1;
-            err = gs_match_submit_text(c.run, text, n_bytes, n_lines, GS_MEM_DEVICE, read_no + reads_in_file, nullptr, nullptr, &ticket);
-            if (!err) err = chunk_submitted(read_no + reads_in_file, n_lines >> 2);
-            if (!err) {
-                dev_tickets_[slot] = ticket;
-                if (first_ticket < 0) first_ticket = ticket;
-                chunks.push_back({carry_file_off, reads_in_file, ticket});
-                reads_in_file += n_lines >> 2;
-                carry_file_off += n_bytes;
-                if (chunks.size() == 1 || (chunks.size() & 15) == 0) err = check_refusal(&fallback_off, &fallback_reads);
-            }
-            if (trace) fprintf(stderr, "bgzf feed %lld: members %zu, feed %.2f ms, submit+check %.2f ms, %lld bytes %lld lines tail %lld\n", (long long)n_feeds_, b - a, (tt1 - tt0) * 1e3, (now_s() - tt1) * 1e3, (long long)n_bytes, (long long)n_lines, (long long)tail);
-        } else if (!err && tail > ((int64_t)256 << 20) && !last) {  // no record boundary in a quarter of a gigabyte: the general parser
-            fallback_off = carry_file_off;
-            fallback_reads = reads_in_file;
-        }
-        if (err || last || fallback_off >= 0) {
-            if (!err && fallback_off < 0) {  // what is left behind the last whole record
-                int64_t n = 0;
-                carry.resize((size_t)tail);
-                if (tail > 0 && gs_inflater_tail(inf_, carry.data(), tail, &n) != GS_OK) err = hfail(GS_E_HIP, gs_inflate_last_error());
-            }
+        if (!err && t.n_lines > 0)
+            err = device_chunk(t, [&fd, &t](uint8_t *dst) { return fd.fetch_text(dst, t.n_bytes); }, &dev_tickets_[0], &fallback_off, &fallback_reads);
+        else if (!err && t.stuck)
+            fall_back(&fallback_off, &fallback_reads);
+        if (trace)
+            fprintf(stderr, "bgzf feed %lld: members up to %zu, feed %.2f ms, submit+check %.2f ms, %lld bytes %lld lines tail %lld\n", (long long)fd.n_feeds, fd.next_member,
+                    (tt1 - tt0) * 1e3, (now_s() - tt1) * 1e3, (long long)t.n_bytes, (long long)t.n_lines, (long long)fd.tail);
+        if (err || t.last || fallback_off >= 0) {
+            if (!err && fallback_off < 0) err = fd.fetch_tail(cut_.carry);  // what is left behind the last whole record
             for (int q = 0; q < 2; q++)
                 if (dev_tickets_[q] >= 0) {
                     const int e2 = gs_match_text_wait_copy(c.run, dev_tickets_[q]);
@@ -1324,258 +1312,154 @@ struct TextJob {
 
     // 1: a block was handled, 0: none ready (blocking = false only); `done` is set when the file is through
     int step(bool blocking, int *err_out) {
-        if (dev_bgzf) return step_bgzf(err_out);
-        if (dev_gz) return step_gunzip(err_out);
-        if (general) return step_general(blocking, err_out);
-        if (fasta) return step_fasta(blocking, err_out);
-        int err = GS_OK;
+        if (dev_.bgzf()) return step_bgzf(err_out);
+        if (dev_.whole()) return step_gunzip(err_out);
         const int64_t i = next_block;
-        bool keep_block = false;
         if (!blocking && !tr.is_full(i)) return 0;
         TextSlot &sl = tr.wait_full(i);
         int64_t fallback_off = -1, fallback_reads = 0;
-        bool last = false;
-        if (sl.io_error || !tr.verify_gzip(sl)) {
-            err = hfail(tr.gz ? GS_E_INVALID : GS_E_IO, (tr.gz ? "corrupt gzip stream in " : "read error on ") + path);
-        } else {
-            err = gs_match_text_select(c.run, bank);
-            uint8_t *blk = sl.buf + tr.headroom;
-            const int64_t total = carry_lines + sl.newlines;
-            const int64_t rem = total & 3, usable = total - rem;
-            last = sl.eof;
-            if (err) {
-                // (the bank could not be selected: reported below)
-            } else if (usable == 0) {  // not one whole record yet: keep everything
-                carry.insert(carry.end(), blk, blk + sl.n);
-                carry_lines = total;
-                if (carry.size() > tr.headroom && !last) {  // a record longer than a block: the general parser takes over
-                    fallback_off = carry_file_off;
-                    fallback_reads = reads_in_file;
-                }
-            } else if (carry.size() > tr.headroom) {
-                fallback_off = carry_file_off;
-                fallback_reads = reads_in_file;
-            } else {
-                const int64_t cut = sl.last4[rem];  // the newline with `rem` newlines behind it ends the last whole record
-                uint8_t *start = blk - carry.size();
-                if (!carry.empty()) memcpy(start, carry.data(), carry.size());
-                int64_t ticket = -1;
-                bool format_it = false;
-                const bool per_read = c.filtered.active() || c.kraken.active();
-                const int64_t n_chunk = usable >> 2;
-                MatchCtx::Results &rs = c.res[n_formatted & 1];  // (the set of the chunk before last: its writers are done)
-                if (per_read) {
-                    err = rs.cls.resize((size_t)n_chunk);
-                    if (!err) err = rs.flags.resize((size_t)n_chunk);
-                }
-                if (!err)
-                    err = gs_match_submit_text(c.run, start, (int64_t)carry.size() + cut + 1, usable, GS_MEM_HOST, read_no + reads_in_file,
-                                               per_read ? rs.cls.data() : nullptr, per_read ? rs.flags.data() : nullptr, &ticket);
-                if (!err) err = chunk_submitted(read_no + reads_in_file, usable >> 2);
-                const bool dev_f = per_read && device_filtered() && c.filtered.gzip();  // (a plain file: formatted from the reader's block, which is here anyway)
-                if (!err && per_read) {  // the writers need this chunk's results
-                    chunks.push_back({carry_file_off, reads_in_file, ticket});
-                    err = check_refusal(&fallback_off, &fallback_reads);
-                    chunks.pop_back();
-                    if (!err && fallback_off < 0 && !dev_f) err = fetch_chunk_results(rs, n_chunk);
-                    format_it = !err && fallback_off < 0 && !dev_f;
-                    if (!err && fallback_off < 0 && dev_f) err = emit_filtered_device();
-                }
-                if (!err && fallback_off < 0) {
-                    if (first_ticket < 0) first_ticket = ticket;
-                    chunks.push_back({carry_file_off, reads_in_file, ticket});
-                    reads_in_file += usable >> 2;
-                    carry_file_off = i * (int64_t)tr.block + cut + 1;
-                    carry.assign(blk + cut + 1, blk + sl.n);
-                    carry_lines = rem;
-                    if (format_it) {
-                        err = gs_match_text_wait_copy(c.run, ticket);  // (the writers hand the block back, below)
-                    } else {
-                        // the pinned block goes back to its reader when its copy is through: looked at one chunk later,
-                        // so that this thread is already submitting the next copy while this one runs
-                        err = release_held();
-                        held_ticket = ticket;
-                        held_block = i;
-                        keep_block = true;
-                    }
-                }
-                if (format_it && !err) {
-                    // (only now: the block returns to its reader when the writers are through with it, and the
-                    // carry above had to be taken out first)
-                    drain();  // one chunk at a time: output order, and the other result set becomes free
-                    n_formatted++;
-                    keep_block = true;
-                    try {
-                        formatting = std::async(std::launch::async, [this, &rs, start, n_chunk, i] { format_chunk(rs, start, n_chunk, i); });
-                    } catch (const std::system_error &) {  // no thread to be had: on this one
-                        format_chunk(rs, start, n_chunk, i);
-                    }
-                }
-                // a file that is not four-line FASTQ fails in its first chunk: look early, then now and again
-                if (!err && fallback_off < 0 && !per_read && (chunks.size() == 1 || (chunks.size() & 15) == 0))
-                    err = check_refusal(&fallback_off, &fallback_reads);
-            }
+        const bool last = sl.eof;
+        bool keep_block = false;
+        int err = block_error(tr, sl, path);
+        if (!err) err = gs_match_text_select(c.run, bank);
+        if (!err) switch (cut_block(cut_, tr, sl)) {
+            case ChunkCutter::ABSORBED: break;
+            case ChunkCutter::FALLBACK: fall_back(&fallback_off, &fallback_reads); break;  // the general parser takes over
+            case ChunkCutter::CHUNK:
+                err = general ? chunk_general(&fallback_off, &fallback_reads)
+                              : (fasta ? chunk_fasta(i, &keep_block, &fallback_off, &fallback_reads) : chunk_four_line(i, &keep_block, &fallback_off, &fallback_reads));
         }
-        if (!keep_block) tr.release(i);  // (else: format_chunk releases it)
+        if (!keep_block) tr.release(i);  // (else: release_held or format_chunk releases it)
         next_block = i + 1;
         if (err || last || fallback_off >= 0) err = finish(err, fallback_off, fallback_reads);
         *err_out = err;
         return 1;
     }
 
-    // The FASTA form of step(): the chunk ends in front of the block's last header line (everything up to there is whole
-    // records), the rest is carried into the next block.  Headers and newlines are counted here (memchr over the block:
-    // '>' is rare, the tail behind the last header is one record), the device checks the counts.
-    int step_fasta(bool blocking, int *err_out) {
+    // the chunk of four-line FASTQ that cut_ has just made of block i
+    int chunk_four_line(int64_t i, bool *keep_block, int64_t *fallback_off, int64_t *fallback_reads) {
+        uint8_t *start = cut_.start;
+        int64_t ticket = -1;
+        bool format_it = false;
+        const bool per_read = c.filtered.active() || c.kraken.active();
+        const int64_t n_chunk = cut_.lines >> 2, first_no = read_no + reads_in_file;
+        MatchCtx::Results &rs = c.res[n_formatted & 1];  // (the set of the chunk before last: its writers are done)
         int err = GS_OK;
-        const int64_t i = next_block;
-        bool keep_block = false;
-        if (!blocking && !tr.is_full(i)) return 0;
-        TextSlot &sl = tr.wait_full(i);
-        int64_t fallback_off = -1, fallback_reads = 0;
-        bool last = false;
-        if (sl.io_error || !tr.verify_gzip(sl)) {
-            err = hfail(tr.gz ? GS_E_INVALID : GS_E_IO, (tr.gz ? "corrupt gzip stream in " : "read error on ") + path);
-        } else {
-            err = gs_match_text_select(c.run, bank);
-            uint8_t *blk = sl.buf + tr.headroom;
-            const int64_t n = (int64_t)sl.n;
-            last = sl.eof;
-            const FastaCut fc = fasta_cut(blk, n, last, carry);
-            const int64_t headers = fc.headers, cut = fc.cut, cut_headers = fc.cut_headers, tail_lines = fc.tail_lines;
-            if (err) {
-                // (the bank could not be selected: reported below)
-            } else if (cut < 0) {  // no record boundary in this block: keep everything
-                carry.insert(carry.end(), blk, blk + n);
-                carry_lines += sl.newlines;
-                carry_headers += headers;
-                if (carry.size() > tr.headroom && !last) {  // a record longer than a block: the general parser takes over
-                    fallback_off = carry_file_off;
-                    fallback_reads = reads_in_file;
-                }
-            } else if (carry.size() > tr.headroom) {
-                fallback_off = carry_file_off;
-                fallback_reads = reads_in_file;
+        if (per_read) {
+            err = rs.cls.resize((size_t)n_chunk);
+            if (!err) err = rs.flags.resize((size_t)n_chunk);
+        }
+        if (!err)
+            err = gs_match_submit_text(c.run, start, cut_.bytes, cut_.lines, GS_MEM_HOST, first_no, per_read ? rs.cls.data() : nullptr,
+                                       per_read ? rs.flags.data() : nullptr, &ticket);
+        if (!err) err = chunk_submitted(first_no, n_chunk);
+        const bool dev_f = per_read && device_filtered() && c.filtered.gzip();  // (a plain file: formatted from the reader's block, which is here anyway)
+        if (!err && per_read) {  // the writers need this chunk's results
+            chunks.push_back({cut_.file_off, reads_in_file, ticket});
+            err = check_refusal(fallback_off, fallback_reads);
+            chunks.pop_back();
+            if (!err && *fallback_off < 0 && !dev_f) err = fetch_chunk_results(rs, n_chunk);
+            format_it = !err && *fallback_off < 0 && !dev_f;
+            if (!err && *fallback_off < 0 && dev_f) err = emit_filtered_device();
+        }
+        if (!err && *fallback_off < 0) {
+            if (first_ticket < 0) first_ticket = ticket;
+            chunks.push_back({cut_.file_off, reads_in_file, ticket});
+            reads_in_file += n_chunk;
+            cut_.commit();
+            if (format_it) {
+                err = gs_match_text_wait_copy(c.run, ticket);  // (the writers hand the block back, below)
             } else {
-                const int64_t lines = carry_lines + sl.newlines - tail_lines, records = carry_headers + cut_headers;
-                uint8_t *start = blk - carry.size();
-                if (!carry.empty()) memcpy(start, carry.data(), carry.size());
-                int64_t ticket = -1;
-                if (records >= ((int64_t)1 << 24)) {  // (more records than one chunk may hold: the general parser)
-                    fallback_off = carry_file_off;
-                    fallback_reads = reads_in_file;
-                } else if ((int64_t)carry.size() + cut > 0) {
-                    const bool kr = c.kraken.active() || c.filtered.active();
-                    MatchCtx::Results &rs = c.res[0];
-                    if (kr) {
-                        err = rs.cls.resize((size_t)std::max<int64_t>(records, 1));
-                        if (!err) err = rs.flags.resize((size_t)std::max<int64_t>(records, 1));
-                    }
-                    if (!err)
-                        err = gs_match_submit_fasta(c.run, start, (int64_t)carry.size() + cut, lines, records, GS_MEM_HOST,
-                                                    read_no + reads_in_file, kr ? rs.cls.data() : nullptr, kr ? rs.flags.data() : nullptr, &ticket);
-                    if (!err) err = chunk_submitted_general(read_no + reads_in_file, records, start, lines, true);
-                    if (!err && kr && records > 0) {  // the per-read outputs of this chunk's records, before the block goes back
-                        chunks.push_back({carry_file_off, reads_in_file, ticket});
-                        err = check_refusal(&fallback_off, &fallback_reads);
-                        chunks.pop_back();
-                        if (!err && fallback_off < 0) err = outputs_general(rs, start, lines, records, true);
-                    }
-                }
-                if (!err && fallback_off < 0) {
-                    if (ticket >= 0) {
-                        if (first_ticket < 0) first_ticket = ticket;
-                        chunks.push_back({carry_file_off, reads_in_file, ticket});
-                    }
-                    reads_in_file += records;
-                    carry_file_off = i * (int64_t)tr.block + cut;
-                    carry.assign(blk + cut, blk + n);
-                    carry_lines = tail_lines;
-                    carry_headers = headers - cut_headers;
-                    if (ticket >= 0) {
-                        err = release_held();
-                        held_ticket = ticket;
-                        held_block = i;
-                        keep_block = true;
-                    }
-                }
-                if (!err && fallback_off < 0 && (chunks.size() == 1 || (chunks.size() & 15) == 0))
-                    err = check_refusal(&fallback_off, &fallback_reads);
+                // the pinned block goes back to its reader when its copy is through: looked at one chunk later,
+                // so that this thread is already submitting the next copy while this one runs
+                err = release_held();
+                held_ticket = ticket;
+                held_block = i;
+                *keep_block = true;
             }
         }
-        if (!keep_block) tr.release(i);
-        next_block = i + 1;
-        if (err || last || fallback_off >= 0) err = finish(err, fallback_off, fallback_reads);
-        *err_out = err;
-        return 1;
+        if (format_it && !err) {
+            // (only now: the block returns to its reader when the writers are through with it, and the
+            // carry above had to be taken out first)
+            drain();  // one chunk at a time: output order, and the other result set becomes free
+            n_formatted++;
+            *keep_block = true;
+            run_behind(formatting, [this, &rs, start, n_chunk, i] { format_chunk(rs, start, n_chunk, i); });
+        }
+        // a file that is not four-line FASTQ fails in its first chunk: look early, then now and again
+        if (!err && *fallback_off < 0 && !per_read && (chunks.size() == 1 || (chunks.size() & 15) == 0)) err = check_refusal(fallback_off, fallback_reads);
+        return err;
     }
 
-    // The general form of step(): everything up to the block's last newline goes to the device together with what the last chunk
-    // left over; the device reports how many records END in it and how many bytes they cover.
-    int step_general(bool blocking, int *err_out) {
+    // The FASTA form: the chunk ends in front of the block's last header line (everything up to there is whole records), the rest
+    // is carried into the next block.  Headers and newlines were counted on the host (ChunkCutter), the device checks the counts.
+    int chunk_fasta(int64_t i, bool *keep_block, int64_t *fallback_off, int64_t *fallback_reads) {
+        const int64_t records = cut_.records, first_no = read_no + reads_in_file;
+        int64_t ticket = -1;
         int err = GS_OK;
-        const int64_t i = next_block;
-        if (!blocking && !tr.is_full(i)) return 0;
-        TextSlot &sl = tr.wait_full(i);
-        int64_t fallback_off = -1, fallback_reads = 0;
-        bool last = false;
-        if (sl.io_error || !tr.verify_gzip(sl)) {
-            err = hfail(tr.gz ? GS_E_INVALID : GS_E_IO, (tr.gz ? "corrupt gzip stream in " : "read error on ") + path);
-        } else {
-            err = gs_match_text_select(c.run, bank);
-            uint8_t *blk = sl.buf + tr.headroom;
-            const int64_t n = (int64_t)sl.n;
-            last = sl.eof;
-            if (err) {
-                // (the bank could not be selected: reported below)
-            } else if (sl.newlines == 0) {  // not one whole line: keep everything
-                carry.insert(carry.end(), blk, blk + n);
-                if (carry.size() > tr.headroom && !last) {
-                    fallback_off = carry_file_off;
-                    fallback_reads = reads_in_file;
-                }
-            } else if (carry.size() > tr.headroom) {  // a record longer than a block: the general parser takes over
-                fallback_off = carry_file_off;
-                fallback_reads = reads_in_file;
-            } else {
-                const int64_t cut = (int64_t)sl.last4[0] + 1;  // behind the block's last newline
-                uint8_t *start = blk - carry.size();
-                if (!carry.empty()) memcpy(start, carry.data(), carry.size());
-                const int64_t bytes = (int64_t)carry.size() + cut, lines = carry_lines + sl.newlines;
-                int64_t n_rec = 0, used = 0, used_lines = 0, ticket = -1;
-                const bool kr = c.kraken.active() || c.filtered.active();
-                MatchCtx::Results &rs = c.res[0];
-                if (kr) {
-                    err = rs.cls.resize((size_t)(lines / 4 + 2));
-                    if (!err) err = rs.flags.resize((size_t)(lines / 4 + 2));
-                }
-                if (!err)
-                    err = gs_match_submit_fastq_ml(c.run, start, bytes, lines, GS_MEM_HOST, read_no + reads_in_file, kr ? rs.cls.data() : nullptr,
-                                                   kr ? rs.flags.data() : nullptr, &n_rec, &used, &used_lines, &ticket);
-                if (!err && n_rec > 0) err = chunk_submitted_general(read_no + reads_in_file, n_rec, start, used_lines, false);
-                if (!err && kr && n_rec > 0) err = outputs_general(rs, start, used_lines, n_rec, false);
-                if (!err && n_rec < 0) {  // refused (NUL byte, a record of thousands of lines): the general parser from here
-                    err = gs_match_text_clear_error(c.run);
-                    fallback_off = carry_file_off;
-                    fallback_reads = reads_in_file;
-                } else if (!err) {
-                    g_ml_chunks.fetch_add(1);
-                    if (first_ticket < 0) first_ticket = ticket;
-                    reads_in_file += n_rec;
-                    carry_file_off += used;
-                    // what the records did not cover + what lies behind the last newline (the text has been copied)
-                    std::vector<uint8_t> rest(start + used, start + bytes);
-                    rest.insert(rest.end(), blk + cut, blk + n);
-                    carry.swap(rest);
-                    carry_lines = lines - used_lines;
-                }
+        if (cut_.bytes > 0) {
+            const bool kr = c.kraken.active() || c.filtered.active();
+            MatchCtx::Results &rs = c.res[0];
+            if (kr) {
+                err = rs.cls.resize((size_t)std::max<int64_t>(records, 1));
+                if (!err) err = rs.flags.resize((size_t)std::max<int64_t>(records, 1));
+            }
+            if (!err)
+                err = gs_match_submit_fasta(c.run, cut_.start, cut_.bytes, cut_.lines, records, GS_MEM_HOST, first_no, kr ? rs.cls.data() : nullptr,
+                                            kr ? rs.flags.data() : nullptr, &ticket);
+            if (!err) err = chunk_submitted_general(first_no, records, cut_.start, cut_.lines, true);
+            if (!err && kr && records > 0) {  // the per-read outputs of this chunk's records, before the block goes back
+                chunks.push_back({cut_.file_off, reads_in_file, ticket});
+                err = check_refusal(fallback_off, fallback_reads);
+                chunks.pop_back();
+                if (!err && *fallback_off < 0) err = outputs_general(rs, cut_.start, cut_.lines, records, true);
             }
         }
-        tr.release(i);
-        next_block = i + 1;
-        if (err || last || fallback_off >= 0) err = finish(err, fallback_off, fallback_reads);
-        *err_out = err;
-        return 1;
+        if (!err && *fallback_off < 0) {
+            if (ticket >= 0) {
+                if (first_ticket < 0) first_ticket = ticket;
+                chunks.push_back({cut_.file_off, reads_in_file, ticket});
+            }
+            reads_in_file += records;
+            cut_.commit();
+            if (ticket >= 0) {
+                err = release_held();
+                held_ticket = ticket;
+                held_block = i;
+                *keep_block = true;
+            }
+        }
+        if (!err && *fallback_off < 0 && (chunks.size() == 1 || (chunks.size() & 15) == 0)) err = check_refusal(fallback_off, fallback_reads);
+        return err;
+    }
+
+    // The general form: everything up to the block's last newline goes to the device together with what the last chunk left over;
+    // the device reports how many records END in it and how many bytes they cover.
+    int chunk_general(int64_t *fallback_off, int64_t *fallback_reads) {
+        const int64_t first_no = read_no + reads_in_file;
+        int64_t n_rec = 0, used = 0, used_lines = 0, ticket = -1;
+        const bool kr = c.kraken.active() || c.filtered.active();
+        MatchCtx::Results &rs = c.res[0];
+        int err = GS_OK;
+        if (kr) {
+            err = rs.cls.resize((size_t)(cut_.lines / 4 + 2));
+            if (!err) err = rs.flags.resize((size_t)(cut_.lines / 4 + 2));
+        }
+        if (!err)
+            err = gs_match_submit_fastq_ml(c.run, cut_.start, cut_.bytes, cut_.lines, GS_MEM_HOST, first_no, kr ? rs.cls.data() : nullptr, kr ? rs.flags.data() : nullptr,
+                                           &n_rec, &used, &used_lines, &ticket);
+        if (!err && n_rec > 0) err = chunk_submitted_general(first_no, n_rec, cut_.start, used_lines, false);
+        if (!err && kr && n_rec > 0) err = outputs_general(rs, cut_.start, used_lines, n_rec, false);
+        if (!err && n_rec < 0) {  // refused (NUL byte, a record of thousands of lines): the general parser from here
+            err = gs_match_text_clear_error(c.run);
+            fall_back(fallback_off, fallback_reads);
+        } else if (!err) {
+            g_ml_chunks.fetch_add(1);
+            if (first_ticket < 0) first_ticket = ticket;
+            reads_in_file += n_rec;
+            cut_.commit(used, used_lines);  // (the text has been copied)
+        }
+        return err;
     }
 
     // Per-read outputs of a FASTA or general FASTQ chunk that has just been matched.  Record geometry: the newline offsets from the
@@ -1737,7 +1621,7 @@ private:
         }
         read_no += reads_in_file;
         // what is left after the last whole four-line group (no final newline, truncated record): the general parser
-        if (!carry.empty()) return parsed_source(c, std::string(), 0, carry.data(), carry.size(), read_no, fasta);
+        if (!cut_.carry.empty()) return parsed_source(c, std::string(), 0, cut_.carry.data(), cut_.carry.size(), read_no, fasta);
         return GS_OK;
     }
 };
@@ -2175,20 +2059,6 @@ int filter_parsed_source(FilterCtx &c, const std::string &path, int64_t offset, 
     return err;
 }
 
-// block size and reader / inflating threads of the filter goal's text pipelines (GS_HOST_BLOCK_BYTES, GS_HOST_READERS)
-void filter_reader_shape(bool gzip, size_t *block, int *readers) {
-    *block = (size_t)8 << 20;
-    if (const char *e = getenv("GS_HOST_BLOCK_BYTES")) {
-        const long long v = atoll(e);
-        if (v >= 64 && v <= ((long long)1 << 29)) *block = (size_t)v;
-    }
-    *readers = (int)std::min<unsigned>(gzip ? 16 : 8, std::max<unsigned>(2, std::thread::hardware_concurrency() / 2));
-    if (const char *e = getenv("GS_HOST_READERS")) {
-        const int v = atoi(e);
-        if (v >= 1 && v <= 32) *readers = v;
-    }
-}
-
 int filter_general_file(FilterCtx &c, const std::string &path, bool gzip, bool fasta);
 int filter_files(FilterCtx &c, const char *const *paths, int n_paths, int extract_device, gs_host_totals *totals);
 
@@ -2211,49 +2081,90 @@ void format_text_chunk(FilterCtx &c, const uint8_t *start, const uint8_t *h_acc,
     write_filter_parts(c, parts);
 }
 
-// Block-gzip (BGZF) FASTQ: the members are listed from their headers, the COMPRESSED bytes go to the device and are inflated there
-// (gs_inflater_feed), the filter runs on the text where it lies (GS_MEM_DEVICE_TEXT), and the text comes back ONCE, page-locked, for
-// the writers -- while the filter kernel runs.  *handled = false: not (only) BGZF, or no inflater: the caller takes its usual path.
+// The back half of a four-line chunk of the filter / extract goal whose accept flags are in, device output: the writers' side stays
+// on the device -- the records each file wants are gathered there (gs_filter_compact_text), a .gz file's are compressed there
+// (DeviceWriter::emit -> gs_deflater_pack), and only what the files will hold crosses PCIe, on a thread of its own (dev_job) while
+// the next chunk is read or inflated and filtered.  The chunk's text is on the device already: its block may go back at once.
+int filter_emit_device(FilterCtx &c, int set, int64_t n_reads, const uint8_t *h_acc, std::future<int> &dev_job) {
+    static const bool trace = getenv("GS_HOST_TRACE") != nullptr;
+    const double t0 = now_s();
+    const uint8_t *d_a = nullptr, *d_r = nullptr;
+    int64_t nb_a = 0, nr_a = 0, nb_r = 0, nr_r = 0;
+    int err = GS_OK;
+    if (c.acc_out.active()) err = c.compact_text(1, c.with_probs ? 1 : 0, set, &d_a, &nb_a, &nr_a);
+    if (!err && c.rest_out.active()) err = c.compact_text(0, c.with_probs ? 1 : 0, set, &d_r, &nb_r, &nr_r);
+    if (err) return err;
+    if (c.acc_out.active())
+        c.accepted += nr_a;
+    else if (c.rest_out.active())
+        c.accepted += n_reads - nr_r;
+    else
+        for (int64_t r = 0; r < n_reads; r++) c.accepted += h_acc[r] != 0;
+    const double t1 = now_s();
+    if (dev_job.valid() && (err = dev_job.get())) return err;  // one chunk at a time: output order
+    if (trace)
+        fprintf(stderr, "filter chunk (device output): gather %.2f ms (%lld + %lld bytes), writers of the chunk before %.2f\n", (t1 - t0) * 1e3, (long long)nb_a, (long long)nb_r,
+                (now_s() - t1) * 1e3);
+    run_behind(dev_job, [&c, set, d_a, nb_a, d_r, nb_r]() -> int {
+        const int e1 = c.acc_dev.emit(set, d_a, nb_a);
+        const int e2 = c.rest_dev.emit(set, d_r, nb_r);
+        return e1 ? e1 : e2;
+    });
+    return GS_OK;
+}
+
+// ... host output: the chunk's text, accept flags and newline offsets are on the host; the records are formatted and handed to the
+// writers on a thread of their own (`formatting`), which ends with release() -- what gives the text's block back, if anything
+void filter_emit_host(FilterCtx &c, const uint8_t *text, const uint8_t *h_acc, const uint32_t *h_nl, int64_t n_reads, std::future<void> &formatting,
+                      std::function<void()> release) {
+    static const bool trace = getenv("GS_HOST_TRACE") != nullptr;
+    const double t0 = now_s();
+    if (formatting.valid()) formatting.get();  // one chunk at a time: output order, the other result set is free
+    if (trace) fprintf(stderr, "filter chunk (host output): writers of the chunk before %.2f ms\n", (now_s() - t0) * 1e3);
+    run_behind(formatting, [&c, text, h_acc, h_nl, n_reads, release] {
+        format_text_chunk(c, text, h_acc, h_nl, n_reads);
+        if (release) release();
+    });
+}
+
+// The end of a file of the filter / extract goal whose text pipeline stopped without an error: the totals of the chunks the device
+// took, then the rest -- from fallback_off on (>= 0: a chunk was refused, or cannot be cut) or what the last chunk left over.
+// general_allowed: a FASTQ file that is not four lines per record from its very first chunk goes once more with the records found
+// on the device (GS_HOST_ML=0: straight to the reference-exact parser, which also takes over whatever that pass refuses).
+int filter_file_end(FilterCtx &c, const std::string &path, bool gzip, const int64_t tot[3], int64_t fallback_off, const std::vector<uint8_t> &carry, bool general_allowed,
+                    bool fasta) {
+    c.reads += tot[0];
+    c.kmers += tot[1];
+    c.bps += tot[2];
+    if (fallback_off >= 0) {
+        const int err = c.text_reset();
+        if (err) return err;
+        bool ml = general_allowed && fallback_off == 0;
+        if (const char *e = getenv("GS_HOST_ML")) ml = ml && atoi(e) != 0;
+        if (ml) return filter_general_file(c, path, gzip, false);
+        return filter_parsed_source(c, path, fallback_off, nullptr, 0);
+    }
+    if (!carry.empty()) return filter_parsed_source(c, std::string(), 0, carry.data(), carry.size(), fasta);
+    return GS_OK;
+}
+
+// Gzip FASTQ inflated on the device (DeviceInflate: block-gzip by its members, any other stream as a whole): the COMPRESSED bytes go
+// to the device, the filter runs on the text where it lies (GS_MEM_DEVICE_TEXT), and the text comes back ONCE, page-locked, for the
+// writers -- while the filter kernel runs -- or not at all (device output).  *handled = false: the caller takes its usual path.
 int filter_bgzf_file(FilterCtx &c, const std::string &path, bool *handled) {
     *handled = false;
-    if (const char *e = getenv("GS_DEVICE_INFLATE"))
-        if (atoi(e) == 0) return GS_OK;
     size_t block;
-    int readers;
-    filter_reader_shape(true, &block, &readers);
+    int readers = 0, device = 0;
+    reader_shape(true, &block, &readers);
     TextReader tr;  // (for the mapping only: its readers are never started)
-    int err = tr.open(path, block, readers, true);
-    std::vector<gs_inflate_member> members;
-    int device = 0;
-    gs_inflater *inf = nullptr;
-    // (not block-gzip: a single-member stream is inflated on the device as a whole, gs_gunzip_plan_device, and handed on in slices)
-    gs_gunzipper *gzr = nullptr;
-    const uint8_t *gz_text = nullptr;  // the current batch
-    int64_t gz_n = 0, gz_off = 0;
-    int gz_last = 0;
-    if (err || tr.map_len < 18 || c.get_device(&device) != GS_OK) {
+    DeviceInflate dev;
+    if (tr.open(path, block, readers, true) == GS_OK && c.get_device(&device) == GS_OK) dev.open(tr.map, tr.map_len, device, gunzip_first_span());
+    if (!dev.bgzf() && !dev.whole()) {
         tr.close();
         return GS_OK;
     }
-    if (tr.map_len >= 28 && bgzf_member_list(tr.map, tr.map_len, members)) {
-        if ((inf = inflater_pool().get(device)) == nullptr) {
-            tr.close();
-            return GS_OK;
-        }
-    } else {
-        members.clear();
-        bool want = true;
-        if (const char *e = getenv("GS_DEVICE_GUNZIP")) want = atoi(e) != 0;
-        if (!want || gunzipper_pool().open(&gzr, device, tr.map, (int64_t)tr.map_len) != GS_OK || gs_gunzipper_first_span(gzr, gunzip_first_span()) != GS_OK ||
-            gs_gunzipper_next(gzr, 0, &gz_text, &gz_n, &gz_last) != GS_OK) {
-            gunzipper_pool().put(device, gzr);
-            tr.close();
-            return GS_OK;  // (a stream this path does not take, a damaged one: the host decoders take it -- and report it)
-        }
-    }
-    const bool whole = inf == nullptr;
     *handled = true;
-    err = c.text_reset();
+    int err = c.text_reset();
     PooledBuf text_sets[2], nl_sets[2];
     PinnedVec<uint8_t> acc_sets[2];
     std::future<void> formatting;
@@ -2270,125 +2181,30 @@ int filter_bgzf_file(FilterCtx &c, const std::string &path, bool *handled) {
     // 11.2 Gbp/s gz -> gz at 16 M reads)
     const bool dev_out = device_output();
     const int64_t text_target = getenv("GS_HOST_BGZF_TEXT") ? bgzf_text_target() : ((int64_t)(dev_out ? 256 : 128) << 20);
-    auto run_end = [&](size_t from) {
-        int64_t sum = 0;
-        size_t e = from;
-        while (e < members.size() && (e == from || sum + members[e].isize <= text_target)) sum += members[e++].isize;
-        return e;
-    };
-    for (size_t a = 0; !err && (whole || a < members.size());) {
-        bool last = false;
-        const uint8_t *text = nullptr;
-        int64_t n_bytes = 0, n_lines = 0, tail = 0;
+    static const bool trace = getenv("GS_HOST_TRACE") != nullptr;
+    while (!err) {
+        DevText t;
+        bool refused = false;
         const double tg = now_s();
-        if (whole) {  // the next slice of the device text: whole records up to the feed size
-            bool refused = false;
-            for (;;) {  // (a slice with a whole record in it: from this batch, or with the next one behind what is left of this)
-                const int64_t rest = gz_n - gz_off, look = std::min(rest, text_target);
-                n_lines = n_bytes = 0;
-                if (look > 0 && gs_text_cut_device(device, gz_text + gz_off, look, &n_lines, &n_bytes) != GS_OK) {
-                    err = hfail(GS_E_HIP, gs_inflate_last_error());
-                    break;
-                }
-                if (n_lines > 0 || gz_last || look < rest) break;
-                const int grc = gs_gunzipper_next(gzr, rest, &gz_text, &gz_n, &gz_last);  // (every earlier slice has been waited for: gs_filter_text_status)
-                gz_off = 0;
-                if (grc == GS_E_UNSUPPORTED || grc == GS_E_NOMEM) {
-                    refused = true;
-                    gz_n = 0;
-                    break;
-                }
-                if (grc != GS_OK) {
-                    err = hfail(GS_E_INVALID, std::string("corrupt gzip stream in ") + path + ": " + gs_inflate_last_error());
-                    break;
-                }
-            }
-            if (err) break;
-            const int64_t rest = gz_n - gz_off;
-            last = gz_last != 0 && std::min(rest, text_target) == rest;
-            text = gz_text + gz_off;
-            tail = last ? rest - n_bytes : (n_lines > 0 ? 0 : ((int64_t)1 << 40));  // (no record in a full slice: the general parser, below)
-            if (refused) {  // the host decoders from here: a batch the device path does not take
-                fallback_off = text_off;
-                break;
-            }
-            gz_off += n_bytes;
-        } else {
-            const size_t b = run_end(a), b2 = run_end(b);
-            last = b == members.size();
-            int64_t next_lo = 0, next_hi = 0;
-            if (b2 > b) {
-                next_lo = members[b].payload_offset;
-                next_hi = members[b2 - 1].payload_offset + (int64_t)members[b2 - 1].payload_len;
-            }
-            if (gs_inflater_feed(inf, tr.map, members.data() + a, (int64_t)(b - a), next_lo, next_hi, last ? 1 : 0, &text, &n_bytes, &n_lines, &tail) != GS_OK) {
-                err = hfail(GS_E_INVALID, std::string("corrupt gzip stream in ") + path + ": " + gs_inflate_last_error());
-                break;
-            }
-            a = b;
+        // (whole stream: every earlier slice has been waited for, gs_filter_text_status -- nothing reads the text a new batch replaces)
+        err = dev.whole() ? dev.slices.next(text_target, path, nullptr, &t, &refused) : dev.feeds.next(text_target, path, &t);
+        if (err) break;
+        if (refused || t.stuck) {  // the host decoders / the general parser from here
+            fallback_off = text_off;
+            break;
         }
-        if (n_lines > 0 && dev_out) {
-            // The writers' side stays on the device: the records each file wants are gathered there (gs_filter_compact_text), a .gz
-            // file's are compressed there (DeviceWriter::emit -> gs_deflater_pack), and only what the files will hold crosses PCIe --
-            // on a thread of its own, while the next feed is inflated and filtered.
-            const int64_t n_reads = n_lines >> 2;
-            const int set = (int)(n_formatted & 1);
-            if ((err = acc_sets[set].resize((size_t)n_reads))) break;
-            uint8_t *h_acc = acc_sets[set].data();
-            int64_t ticket = -1;
-            static const bool trace = getenv("GS_HOST_TRACE") != nullptr;
-            const double t1 = now_s();
-            err = c.submit_text(text, n_bytes, n_lines, GS_MEM_DEVICE_TEXT, h_acc, nullptr, 0, &ticket);
-            if (!err) err = c.text_status(&failed, &bad, tot);  // synchronises: results are needed now
-            const double t2 = now_s();
-            c.t_gpu += t2 - tg;
-            if (err) break;
-            if (failed >= 0) {  // not four-line FASTQ from here on: the general parser continues at this chunk
-                fallback_off = text_off;
-                break;
-            }
-            const uint8_t *d_a = nullptr, *d_r = nullptr;
-            int64_t nb_a = 0, nr_a = 0, nb_r = 0, nr_r = 0;
-            if (c.acc_out.active()) err = c.compact_text(1, c.with_probs ? 1 : 0, set, &d_a, &nb_a, &nr_a);
-            if (!err && c.rest_out.active()) err = c.compact_text(0, c.with_probs ? 1 : 0, set, &d_r, &nb_r, &nr_r);
-            if (err) break;
-            if (c.acc_out.active())
-                c.accepted += nr_a;
-            else if (c.rest_out.active())
-                c.accepted += n_reads - nr_r;
-            else
-                for (int64_t r = 0; r < n_reads; r++) c.accepted += h_acc[r] != 0;
-            const double t3 = now_s();
-            if (dev_job.valid() && (err = dev_job.get())) break;  // one chunk at a time: output order
-            if (trace)
-                fprintf(stderr, "filter feed (device output): %lld bytes, inflate %.2f ms, filter %.2f, gather %.2f (%lld + %lld bytes), writers of the chunk before %.2f\n",
-                        (long long)n_bytes, (t1 - tg) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (long long)nb_a, (long long)nb_r, (now_s() - t3) * 1e3);
-            n_formatted++;
-            auto job = [&c, set, d_a, nb_a, d_r, nb_r]() -> int {
-                const int e1 = c.acc_dev.emit(set, d_a, nb_a);
-                const int e2 = c.rest_dev.emit(set, d_r, nb_r);
-                return e1 ? e1 : e2;
-            };
-            try {
-                dev_job = std::async(std::launch::async, job);
-            } catch (const std::system_error &) {  // no thread to be had: on this one
-                if ((err = job())) break;
-            }
-            text_off += n_bytes;
-        } else if (n_lines > 0) {
-            const int64_t n_reads = n_lines >> 2;
+        if (t.n_lines > 0) {
+            const int64_t n_reads = t.n_lines >> 2;
             const int set = (int)(n_formatted & 1);  // (the set of the chunk before last: its writers are through)
-            if ((err = acc_sets[set].resize((size_t)n_reads)) || (err = nl_sets[set].need(sizeof(uint32_t) * (size_t)n_lines)) || (err = text_sets[set].need((size_t)n_bytes)))
-                break;
+            if ((err = acc_sets[set].resize((size_t)n_reads))) break;
+            if (!dev_out && ((err = nl_sets[set].need(sizeof(uint32_t) * (size_t)t.n_lines)) || (err = text_sets[set].need((size_t)t.n_bytes)))) break;
             uint8_t *h_acc = acc_sets[set].data(), *h_text = static_cast<uint8_t *>(text_sets[set].p);
             uint32_t *h_nl = static_cast<uint32_t *>(nl_sets[set].p);
             int64_t ticket = -1;
-            static const bool trace = getenv("GS_HOST_TRACE") != nullptr;
             const double t1 = now_s();
-            err = c.submit_text(text, n_bytes, n_lines, GS_MEM_DEVICE_TEXT, h_acc, h_nl, 0, &ticket);
+            err = c.submit_text(t.text, t.n_bytes, t.n_lines, GS_MEM_DEVICE_TEXT, h_acc, dev_out ? nullptr : h_nl, 0, &ticket);
             const double t2 = now_s();
-            if (!err && (whole ? gs_device_fetch(device, text, h_text, n_bytes) : gs_inflater_fetch(inf, h_text, n_bytes)) != GS_OK)
-                err = hfail(GS_E_HIP, gs_inflate_last_error());  // (while the kernel runs)
+            if (!err && !dev_out) err = dev.whole() ? dev.slices.fetch_text(t, h_text) : dev.feeds.fetch_text(h_text, t.n_bytes);  // (while the kernel runs)
             const double t3 = now_s();
             if (!err) err = c.text_status(&failed, &bad, tot);  // synchronises: results are needed now
             const double t4 = now_s();
@@ -2398,27 +2214,18 @@ int filter_bgzf_file(FilterCtx &c, const std::string &path, bool *handled) {
                 fallback_off = text_off;
                 break;
             }
-            if (formatting.valid()) formatting.get();  // one chunk at a time: output order, the other set is free
             if (trace)
-                fprintf(stderr, "filter bgzf feed: %lld bytes, inflate + buffers %.2f ms, submit %.2f, text back %.2f, status %.2f, writers of the chunk before %.2f\n",
-                        (long long)n_bytes, (t1 - tg) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3, (now_s() - t4) * 1e3);
+                fprintf(stderr, "filter feed: %lld bytes, inflate + buffers %.2f ms, submit %.2f, text back %.2f, status %.2f\n", (long long)t.n_bytes, (t1 - tg) * 1e3,
+                        (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3);
+            if (dev_out) {
+                if ((err = filter_emit_device(c, set, n_reads, h_acc, dev_job))) break;
+            } else
+                filter_emit_host(c, h_text, h_acc, h_nl, n_reads, formatting, nullptr);
             n_formatted++;
-            auto write_chunk = [&c, h_text, h_acc, h_nl, n_reads] { format_text_chunk(c, h_text, h_acc, h_nl, n_reads); };
-            try {
-                formatting = std::async(std::launch::async, write_chunk);
-            } catch (const std::system_error &) {  // no thread to be had: on this one
-                write_chunk();
-            }
-            text_off += n_bytes;
-        } else if (tail > ((int64_t)256 << 20) && !last) {  // no record boundary in a quarter of a gigabyte: the general parser
-            fallback_off = text_off;
-            break;
+            text_off += t.n_bytes;
         }
-        if (last) {  // what is left behind the last whole record
-            int64_t n = 0;
-            carry.resize((size_t)tail);
-            if (tail > 0 && (whole ? gs_device_fetch(device, gz_text + gz_off, carry.data(), tail) : gs_inflater_tail(inf, carry.data(), tail, &n)) != GS_OK)
-                err = hfail(GS_E_HIP, gs_inflate_last_error());
+        if (t.last) {  // what is left behind the last whole record
+            err = dev.whole() ? dev.slices.fetch_leftover(carry) : dev.feeds.fetch_tail(carry);
             break;
         }
     }
@@ -2429,34 +2236,20 @@ int filter_bgzf_file(FilterCtx &c, const std::string &path, bool *handled) {
         if (!err) err = e2;
     }
     const double te1 = now_s();
-    if (inf) inflater_pool().put(device, inf);
-    if (gzr) gunzipper_pool().put(device, gzr);  // (every slice's filter run has been waited for: gs_filter_text_status)
+    dev.close();  // (every slice's filter run has been waited for: gs_filter_text_status)
     tr.close();
-    if (getenv("GS_HOST_TRACE") != nullptr)
+    if (trace)
         fprintf(stderr, "filter bgzf: loop %.2f ms (from open), last writers %.2f, inflater back + unmap %.2f\n", (te0 - t0) * 1e3, (te1 - te0) * 1e3, (now_s() - te1) * 1e3);
     c.t_parse += now_s() - t0;
     if (err) return err;
-    c.reads += tot[0];
-    c.kmers += tot[1];
-    c.bps += tot[2];
-    if (fallback_off >= 0) {
-        err = c.text_reset();
-        if (err) return err;
-        // not four lines per record from the very first chunk: once more with the records found on the device, as filter_text_file
-        bool ml = fallback_off == 0;
-        if (const char *e = getenv("GS_HOST_ML")) ml = ml && atoi(e) != 0;
-        if (ml) return filter_general_file(c, path, true, false);
-        return filter_parsed_source(c, path, fallback_off, nullptr, 0);
-    }
-    if (!carry.empty()) return filter_parsed_source(c, std::string(), 0, carry.data(), carry.size());
-    return GS_OK;
+    return filter_file_end(c, path, true, tot, fallback_off, carry, true, false);
 }
 
 // plain FASTQ: raw text blocks to the device (gs_filter_submit_text); accept flags and record geometry come back
 int filter_text_file(FilterCtx &c, const std::string &path, bool gzip) {
     size_t block;
-    int readers;
-    filter_reader_shape(gzip, &block, &readers);
+    int readers = 0;
+    reader_shape(gzip, &block, &readers);
     TextReader tr;
     int err = tr.open(path, block, readers, gzip);
     if (err) {
@@ -2476,89 +2269,44 @@ int filter_text_file(FilterCtx &c, const std::string &path, bool gzip) {
                          c.get_device(&device) == GS_OK;
     c.acc_dev.begin(&c.acc_out, device);
     c.rest_dev.begin(&c.rest_out, device);
-    int64_t n_formatted = 0;
-    std::vector<uint8_t> carry;
-    int64_t carry_lines = 0, carry_file_off = 0, fallback_off = -1;
+    int64_t n_formatted = 0, fallback_off = -1;
+    ChunkCutter cut;
     int64_t tot[3] = {0, 0, 0}, failed = -1, bad = -1;
     const double t0 = now_s();
     if (!err) tr.start();
     for (int64_t i = 0; !err; i++) {
         TextSlot &sl = tr.wait_full(i);
-        if (sl.io_error || !tr.verify_gzip(sl)) {
-            err = hfail(tr.gz ? GS_E_INVALID : GS_E_IO, (tr.gz ? "corrupt gzip stream in " : "read error on ") + path);
-            break;
-        }
-        uint8_t *blk = sl.buf + tr.headroom;
-        const int64_t total = carry_lines + sl.newlines;
-        const int64_t rem = total & 3, usable = total - rem;
+        if ((err = block_error(tr, sl, path))) break;
         const bool eof = sl.eof;
         bool keep_block = false;
-        if (usable == 0) {
-            carry.insert(carry.end(), blk, blk + sl.n);
-            carry_lines = total;
-            if (carry.size() > tr.headroom && !eof) fallback_off = carry_file_off;
-        } else if (carry.size() > tr.headroom) {
-            fallback_off = carry_file_off;
-        } else {
-            const int64_t cut = sl.last4[rem];
-            uint8_t *start = blk - carry.size();
-            if (!carry.empty()) memcpy(start, carry.data(), carry.size());
-            const int64_t n_reads = usable >> 2;
-            if ((err = acc_sets[n_formatted & 1].resize((size_t)n_reads))) break;  // (the set of the chunk before last)
-            if ((err = nl_sets[n_formatted & 1].resize((size_t)usable))) break;
-            uint8_t *h_acc = acc_sets[n_formatted & 1].data();
-            uint32_t *h_nl = nl_sets[n_formatted & 1].data();
+        const ChunkCutter::Cut what = cut_block(cut, tr, sl);
+        if (what == ChunkCutter::FALLBACK) {
+            fallback_off = cut.file_off;
+        } else if (what == ChunkCutter::CHUNK) {
+            const int64_t n_reads = cut.lines >> 2;
+            const int set = (int)(n_formatted & 1);  // (the set of the chunk before last)
+            if ((err = acc_sets[set].resize((size_t)n_reads))) break;
+            if ((err = nl_sets[set].resize((size_t)cut.lines))) break;
+            uint8_t *h_acc = acc_sets[set].data();
+            uint32_t *h_nl = nl_sets[set].data();
             int64_t ticket = -1;
             const double tg = now_s();
-            err = c.submit_text(start, (int64_t)carry.size() + cut + 1,
-                                        usable, GS_MEM_HOST, h_acc, h_nl, 0, &ticket);
+            err = c.submit_text(cut.start, cut.bytes, cut.lines, GS_MEM_HOST, h_acc, h_nl, 0, &ticket);
             if (!err) err = c.text_status(&failed, &bad, tot);  // synchronises: results are needed now
             c.t_gpu += now_s() - tg;
             if (err) break;
             if (failed >= 0) {  // not four-line FASTQ from here on: the general parser continues at this chunk
-                fallback_off = carry_file_off;
-            } else if (dev_out) {
-                // a .gz output: the records are gathered and compressed on the device (the chunk's text is there already), the block
-                // goes straight back to its reader
-                const int set = (int)(n_formatted & 1);
-                const uint8_t *d_a = nullptr, *d_r = nullptr;
-                int64_t nb_a = 0, nr_a = 0, nb_r = 0, nr_r = 0;
-                if (c.acc_out.active()) err = c.compact_text(1, c.with_probs ? 1 : 0, set, &d_a, &nb_a, &nr_a);
-                if (!err && c.rest_out.active()) err = c.compact_text(0, c.with_probs ? 1 : 0, set, &d_r, &nb_r, &nr_r);
-                if (err) break;
-                c.accepted += c.acc_out.active() ? nr_a : n_reads - nr_r;
-                carry_file_off = i * (int64_t)tr.block + cut + 1;
-                carry.assign(blk + cut + 1, blk + sl.n);
-                carry_lines = rem;
-                if (dev_job.valid() && (err = dev_job.get())) break;  // one chunk at a time: output order
-                n_formatted++;
-                auto job = [&c, set, d_a, nb_a, d_r, nb_r]() -> int {
-                    const int e1 = c.acc_dev.emit(set, d_a, nb_a);
-                    const int e2 = c.rest_dev.emit(set, d_r, nb_r);
-                    return e1 ? e1 : e2;
-                };
-                try {
-                    dev_job = std::async(std::launch::async, job);
-                } catch (const std::system_error &) {  // no thread to be had: on this one
-                    if ((err = job())) break;
-                }
+                fallback_off = cut.file_off;
             } else {
-                // (the carry is taken out first: the block returns to its reader when the writers are through with it)
-                carry_file_off = i * (int64_t)tr.block + cut + 1;
-                carry.assign(blk + cut + 1, blk + sl.n);
-                carry_lines = rem;
-                if (formatting.valid()) formatting.get();  // one chunk at a time: output order, the other set is free
-                n_formatted++;
-                keep_block = true;
-                auto write_chunk = [&c, &tr, h_acc, h_nl, start, n_reads, i] {
-                    format_text_chunk(c, start, h_acc, h_nl, n_reads);
-                    tr.release(i);  // the block goes back to its reader
-                };
-                try {
-                    formatting = std::async(std::launch::async, write_chunk);
-                } catch (const std::system_error &) {  // no thread to be had: on this one
-                    write_chunk();
+                const uint8_t *start = cut.start;
+                cut.commit();  // (the carry is taken out first: the block returns to its reader when the writers are through with it)
+                if (dev_out) {  // a .gz output: the block goes straight back to its reader
+                    if ((err = filter_emit_device(c, set, n_reads, h_acc, dev_job))) break;
+                } else {
+                    keep_block = true;
+                    filter_emit_host(c, start, h_acc, h_nl, n_reads, formatting, [&tr, i] { tr.release(i); });
                 }
+                n_formatted++;
             }
         }
         if (!keep_block) tr.release(i);
@@ -2572,21 +2320,7 @@ int filter_text_file(FilterCtx &c, const std::string &path, bool gzip) {
     tr.close();
     c.t_parse += now_s() - t0;
     if (err) return err;
-    c.reads += tot[0];
-    c.kmers += tot[1];
-    c.bps += tot[2];
-    if (fallback_off >= 0) {
-        err = c.text_reset();
-        if (err) return err;
-        // not four lines per record from the very first chunk: once more with the records found on the device (GS_HOST_ML=0:
-        // straight to the reference-exact parser, which also takes over whatever that pass refuses)
-        bool ml = fallback_off == 0;
-        if (const char *e = getenv("GS_HOST_ML")) ml = ml && atoi(e) != 0;
-        if (ml) return filter_general_file(c, path, gzip, false);
-        return filter_parsed_source(c, path, fallback_off, nullptr, 0);
-    }
-    if (!carry.empty()) return filter_parsed_source(c, std::string(), 0, carry.data(), carry.size());
-    return GS_OK;
+    return filter_file_end(c, path, gzip, tot, fallback_off, cut.carry, true, false);
 }
 
 // FASTA and general FASTQ (sequence / quality over several lines): chunks of whole records (FASTA: cut in front of a header
@@ -2595,8 +2329,8 @@ int filter_text_file(FilterCtx &c, const std::string &path, bool gzip) {
 // refuses and the tail of the file go through the reference-exact parser.
 int filter_general_file(FilterCtx &c, const std::string &path, bool gzip, bool fasta) {
     size_t block;
-    int readers;
-    filter_reader_shape(gzip, &block, &readers);
+    int readers = 0;
+    reader_shape(gzip, &block, &readers);
     TextReader tr;
     int err = tr.open(path, block, readers, gzip);
     if (err) {
@@ -2614,37 +2348,21 @@ int filter_general_file(FilterCtx &c, const std::string &path, bool gzip, bool f
         std::vector<int64_t> head;
     } res[2];
     std::future<void> formatting;
-    int64_t n_chunks = 0;
-    std::vector<uint8_t> carry;
-    int64_t carry_lines = 0, carry_headers = 0, carry_file_off = 0, fallback_off = -1;
+    int64_t n_chunks = 0, fallback_off = -1;
+    ChunkCutter cut;
+    cut.mode = fasta ? ChunkCutter::FASTA : ChunkCutter::GENERAL;
     int64_t tot[3] = {0, 0, 0}, failed = -1, bad = -1;
     const double t0 = now_s();
     if (!err) tr.start();
     for (int64_t i = 0; !err; i++) {
         TextSlot &sl = tr.wait_full(i);
-        if (sl.io_error || !tr.verify_gzip(sl)) {
-            err = hfail(tr.gz ? GS_E_INVALID : GS_E_IO, (tr.gz ? "corrupt gzip stream in " : "read error on ") + path);
-            break;
-        }
-        uint8_t *blk = sl.buf + tr.headroom;
-        const int64_t n = (int64_t)sl.n;
+        if ((err = block_error(tr, sl, path))) break;
         const bool eof = sl.eof;
-        // the chunk: [start, start + bytes) = the carry + the block up to `cut`; `rest` = what stays for the next block
-        FastaCut fc;
-        if (fasta)
-            fc = fasta_cut(blk, n, eof, carry);
-        else if (sl.newlines > 0)
-            fc.cut = (int64_t)sl.last4[0] + 1;  // behind the block's last newline
-        if (fc.cut < 0) {  // no boundary in this block: keep everything
-            carry.insert(carry.end(), blk, blk + n);
-            carry_lines += sl.newlines;
-            carry_headers += fc.headers;
-            if (carry.size() > tr.headroom && !eof) fallback_off = carry_file_off;  // a record longer than a block
-        } else if (carry.size() > tr.headroom) {
-            fallback_off = carry_file_off;
-        } else {
-            uint8_t *start = blk - carry.size();
-            if (!carry.empty()) memcpy(start, carry.data(), carry.size());
+        const ChunkCutter::Cut what = cut_block(cut, tr, sl);
+        if (what == ChunkCutter::FALLBACK) {  // a record longer than a block, more records than one chunk may hold
+            fallback_off = cut.file_off;
+        } else if (what == ChunkCutter::CHUNK) {
+            const uint8_t *start = cut.start;
             Res &rs = res[n_chunks & 1];
             PinnedVec<uint8_t> &acc = rs.acc;
             PinnedVec<uint32_t> &nls = rs.nls;
@@ -2652,23 +2370,16 @@ int filter_general_file(FilterCtx &c, const std::string &path, bool gzip, bool f
             std::vector<uint8_t> &cls = rs.cls;
             std::vector<int64_t> &head = rs.head;
             std::function<void()> format_job;
-            const int64_t bytes = (int64_t)carry.size() + fc.cut;
-            int64_t lines = carry_lines + sl.newlines - fc.tail_lines, records = carry_headers + fc.cut_headers, used = bytes, ticket = -1;
-            if (fasta && records >= ((int64_t)1 << 24)) {  // (more records than one chunk may hold)
-                fallback_off = carry_file_off;
-            } else if (bytes > 0) {
+            const int64_t bytes = cut.bytes;
+            int64_t lines = cut.lines, records = cut.records, used = bytes, ticket = -1;
+            if (bytes > 0) {
                 if ((err = acc.resize((size_t)(fasta ? std::max<int64_t>(records, 1) : lines / 4 + 2)))) break;
                 if ((err = nls.resize((size_t)std::max<int64_t>(lines, 1)))) break;
                 const double tg = now_s();
-                if (fasta) {
-                    err = c.submit_fasta(start, bytes, lines, records, GS_MEM_HOST,
-                                                 acc.data(), nls.data(), &ticket);
-                } else {
-                    int64_t all_lines = lines;
-                    err = c.submit_fastq_ml(start, bytes, all_lines, GS_MEM_HOST,
-                                                    acc.data(), nls.data(), &records, &used, &lines, &ticket);
-                    carry_lines = all_lines - lines;  // (lines the records did not cover)
-                }
+                if (fasta)
+                    err = c.submit_fasta(start, bytes, lines, records, GS_MEM_HOST, acc.data(), nls.data(), &ticket);
+                else  // (the device says what its records cover: `used` bytes, `lines` lines)
+                    err = c.submit_fastq_ml(start, bytes, cut.lines, GS_MEM_HOST, acc.data(), nls.data(), &records, &used, &lines, &ticket);
                 if (!err) err = c.text_status(&failed, &bad, tot);  // synchronises: results are needed now
                 if (!err && failed < 0 && records > 0) {
                     bounds.resize((size_t)records + 1);
@@ -2679,7 +2390,7 @@ int filter_general_file(FilterCtx &c, const std::string &path, bool gzip, bool f
                 c.t_gpu += now_s() - tg;
                 if (err) break;
                 if (failed >= 0 || records < 0) {  // refused: the general parser continues at this chunk
-                    fallback_off = carry_file_off;
+                    fallback_off = cut.file_off;
                 } else if (records > 0) {
                     g_filter_general_chunks.fetch_add(1);
                     const uint32_t *nl = nls.p;
@@ -2719,29 +2430,14 @@ int filter_general_file(FilterCtx &c, const std::string &path, bool gzip, bool f
                     };
                 }
             }
-            if (fallback_off < 0) {
-                carry_file_off += used;
-                // what the records did not cover + what lies behind the cut
-                std::vector<uint8_t> rest(start + used, start + bytes);
-                rest.insert(rest.end(), blk + fc.cut, blk + n);
-                carry.swap(rest);
-                if (fasta) {
-                    carry_lines = fc.tail_lines;
-                    carry_headers = fc.headers - fc.cut_headers;
-                }
-            }
+            if (fallback_off < 0) cut.commit(used, lines);  // (general FASTQ: what the records did not cover is carried as well)
             if (format_job) {  // (the carry has been taken out of the block: the formatting thread may hand it back)
                 if (formatting.valid()) formatting.get();  // one chunk at a time: output order, and the other result set is free again
                 n_chunks++;
-                try {
-                    formatting = std::async(std::launch::async, [format_job, &tr, i] {
-                        format_job();
-                        tr.release(i);
-                    });
-                } catch (const std::system_error &) {  // no thread to be had: on this one
+                run_behind(formatting, [format_job, &tr, i] {
                     format_job();
                     tr.release(i);
-                }
+                });
                 if (eof || fallback_off >= 0) break;
                 continue;
             }
@@ -2753,16 +2449,7 @@ int filter_general_file(FilterCtx &c, const std::string &path, bool gzip, bool f
     tr.close();
     c.t_parse += now_s() - t0;
     if (err) return err;
-    c.reads += tot[0];
-    c.kmers += tot[1];
-    c.bps += tot[2];
-    if (fallback_off >= 0) {
-        err = c.text_reset();
-        if (err) return err;
-        return filter_parsed_source(c, path, fallback_off, nullptr, 0);
-    }
-    if (!carry.empty()) return filter_parsed_source(c, std::string(), 0, carry.data(), carry.size(), fasta);
-    return GS_OK;
+    return filter_file_end(c, path, gzip, tot, fallback_off, cut.carry, false, fasta);
 }
 
 }  // namespace
@@ -3046,8 +2733,8 @@ bool f2f_high_bytes(const uint8_t *p, size_t n) {
 // file without a final newline go through f2f_cpu from the start of that chunk.
 int f2f_device_file(F2fCtx &c, const std::string &path, bool gzip) {
     size_t block;
-    int readers;
-    filter_reader_shape(gzip, &block, &readers);
+    int readers = 0;
+    reader_shape(gzip, &block, &readers);
     TextReader tr;
     int err = tr.open(path, block, readers, gzip);
     if (err) {
@@ -3055,37 +2742,24 @@ int f2f_device_file(F2fCtx &c, const std::string &path, bool gzip) {
         return err;
     }
     if (gs_reads_text_reset(c.reads, 1) != GS_OK) err = hfail(GS_E_HIP, gs_last_error());
-    std::vector<uint8_t> carry;
-    int64_t carry_lines = 0, carry_headers = 0, carry_file_off = 0, fallback_off = -1, n_chunks = 0;
+    ChunkCutter cut;
+    cut.mode = ChunkCutter::FASTA;
+    int64_t fallback_off = -1, n_chunks = 0;
     if (!err) tr.start();
     for (int64_t i = 0; !err; i++) {
         const double tw = now_s();
         TextSlot &sl = tr.wait_full(i);
         c.t_read += now_s() - tw;
-        if (sl.io_error || !tr.verify_gzip(sl)) {
-            err = hfail(tr.gz ? GS_E_INVALID : GS_E_IO, (tr.gz ? "corrupt gzip stream in " : "read error on ") + path);
-            break;
-        }
-        uint8_t *blk = sl.buf + tr.headroom;
-        const int64_t n = (int64_t)sl.n;
+        if ((err = block_error(tr, sl, path))) break;
         const bool eof = sl.eof;
-        const FastaCut fc = fasta_cut(blk, n, eof, carry);
-        if (f2f_high_bytes(blk, (size_t)n)) {
-            fallback_off = carry_file_off;
-        } else if (fc.cut < 0) {  // no boundary in this block: keep everything
-            carry.insert(carry.end(), blk, blk + n);
-            carry_lines += sl.newlines;
-            carry_headers += fc.headers;
-            if (carry.size() > tr.headroom && !eof) fallback_off = carry_file_off;  // a record longer than a block
-        } else if (carry.size() > tr.headroom) {
-            fallback_off = carry_file_off;
-        } else {
-            uint8_t *start = blk - carry.size();
-            if (!carry.empty()) memcpy(start, carry.data(), carry.size());
-            const int64_t bytes = (int64_t)carry.size() + fc.cut, lines = carry_lines + sl.newlines - fc.tail_lines, records = carry_headers + fc.cut_headers;
-            if (records >= ((int64_t)1 << 24)) {
-                fallback_off = carry_file_off;
-            } else if (bytes > 0) {
+        // (bytes >= 0x80 are looked for before the cut: the line-by-line loop starts in front of the carry)
+        const ChunkCutter::Cut what = f2f_high_bytes(sl.buf + tr.headroom, sl.n) ? ChunkCutter::FALLBACK : cut_block(cut, tr, sl);
+        if (what == ChunkCutter::FALLBACK) {  // (also: a record longer than a block, more records than one chunk may hold)
+            fallback_off = cut.file_off;
+        } else if (what == ChunkCutter::CHUNK) {
+            const uint8_t *start = cut.start;
+            const int64_t bytes = cut.bytes, lines = cut.lines, records = cut.records;
+            if (bytes > 0) {
                 const uint8_t *d_text = nullptr;
                 int64_t n_out = 0, long_lines = 0, failed = -1, bad = -1, tot[3] = {0, 0, 0};
                 const double td = now_s();
@@ -3096,7 +2770,7 @@ int f2f_device_file(F2fCtx &c, const std::string &path, bool gzip) {
                 }
                 c.t_dev += now_s() - td;
                 if (failed >= 0) {
-                    fallback_off = carry_file_off;
+                    fallback_off = cut.file_off;
                 } else if (long_lines > 0) {
                     err = hfail(GS_E_INVALID, "buffer is too small for data line in fasta file " + path);
                     break;
@@ -3109,12 +2783,7 @@ int f2f_device_file(F2fCtx &c, const std::string &path, bool gzip) {
                     c.records += records;
                 }
             }
-            if (fallback_off < 0) {
-                carry_file_off += bytes;
-                carry.assign(blk + fc.cut, blk + n);
-                carry_lines = fc.tail_lines;
-                carry_headers = fc.headers - fc.cut_headers;
-            }
+            if (fallback_off < 0) cut.commit();
         }
         tr.release(i);
         if (eof || fallback_off >= 0) break;
@@ -3125,7 +2794,7 @@ int f2f_device_file(F2fCtx &c, const std::string &path, bool gzip) {
         if (gs_reads_text_reset(c.reads, 1) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
         return f2f_cpu(c, path, fallback_off, nullptr, 0);
     }
-    if (!carry.empty()) return f2f_cpu(c, std::string(), 0, carry.data(), carry.size());
+    if (!cut.carry.empty()) return f2f_cpu(c, std::string(), 0, cut.carry.data(), cut.carry.size());
     return GS_OK;
 }
 

@@ -336,6 +336,26 @@ def test_writers_under_sanitizers(tmp_path, sanitizer):
     assert "WARNING: ThreadSanitizer" not in r.stderr and "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
 
 
+def test_chunk_cutter_under_sanitizers(tmp_path):
+    """the block cutter of the file loops (genestrip_amd/csrc/gs_chunk.h: carry, cut, commit, fallback) on its own under
+    AddressSanitizer / UBSan (single-threaded: no ThreadSanitizer): four-line, CRLF, no final newline, FASTA and general FASTQ texts
+    in blocks of 64 to 4096 bytes -- chunks + rest are the input, every chunk is whole records, counts equal a recount"""
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    src = os.path.join(os.path.dirname(__file__), "native", "chunk_cut_check.cpp")
+    exe = str(tmp_path / "chunk_cut_check")
+    flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize=alignment", "-std=c++17", "-Wall"]
+    b = subprocess.run(["g++", *flags, "-o", exe, src], capture_output=True, text=True)
+    if b.returncode != 0 and "sanitize" in b.stderr:
+        pytest.skip("sanitizer runtime not installed")
+    assert b.returncode == 0, b.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "fails 0" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
+
+
 @pytest.mark.parametrize("sanitizer", ["thread", "address,undefined"])
 def test_gunzipper_upload_threads_under_sanitizers(tmp_path, sanitizer):
     """the host threads of the DEVICE gunzip (gs_gunzipper_*: the staged copy and the upload thread, genestrip_amd/csrc/gs_upload.h)
