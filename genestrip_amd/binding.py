@@ -42,7 +42,7 @@ ABI_SYMBOLS = (
     "gs_bloom_create", "gs_bloom_build", "gs_bloom_get", "gs_bloom_destroy", "gs_filter_submit", "gs_filter_sync", "gs_filter_kernel_time",
     "gs_calibrate",
     "gs_match_get_device", "gs_inflate_members", "gs_inflater_create", "gs_inflater_feed", "gs_inflater_tail", "gs_gunzipper_open", "gs_gunzipper_reopen", "gs_gunzipper_next", "gs_gunzipper_info", "gs_gunzipper_first_span", "gs_gunzipper_park", "gs_gunzipper_close", "gs_gunzip_plan_device", "gs_gunzip_free", "gs_gunzip_device", "gs_text_cut_device", "gs_device_fetch", "gs_inflater_fetch", "gs_filter_get_device", "gs_inflater_reset", "gs_inflater_destroy", "gs_inflate_last_error",
-    "gs_filter_compact_text", "gs_match_compact_text", "gs_deflater_create", "gs_deflater_pack", "gs_deflater_info", "gs_deflater_destroy", "gs_deflater_append", "gs_deflater_pending", "gs_deflater_flush",
+    "gs_filter_compact_text", "gs_match_compact_text", "gs_match_set_taxids", "gs_match_kraken_text", "gs_match_kraken_time", "gs_deflater_create", "gs_deflater_pack", "gs_deflater_info", "gs_deflater_destroy", "gs_deflater_append", "gs_deflater_pending", "gs_deflater_flush",
     "gs_deflate_bound", "gs_deflate_host", "gs_deflate_host_reference", "gs_deflate_last_error", "gs_match_text_descriptors", "gs_match_submit_fixed",
     "gs_db_value_counts", "gs_dbexport_create", "gs_dbexport_fetch", "gs_dbexport_get_device", "gs_dbexport_fastq_begin",
     "gs_dbexport_fastq_next", "gs_dbexport_destroy",
@@ -219,6 +219,8 @@ def lib():
         "gs_inflate_last_error": (C.c_char_p, []),
         "gs_filter_compact_text": (ci, [vp, ci, ci, ci, vp, vp, vp]),
         "gs_match_compact_text": (ci, [vp, ci, ci, vp, vp, vp]),
+        "gs_match_set_taxids": (ci, [vp, vp]), "gs_match_kraken_text": (ci, [vp, ci, ci, vp, vp, vp]),
+        "gs_match_kraken_time": (ci, [vp, vp, vp]),
         "gs_deflater_create": (ci, [vp, ci]),
         "gs_deflater_pack": (ci, [vp, vp, i64, vp, i64, vp]),
         "gs_deflater_info": (ci, [vp, vp]),
@@ -1032,6 +1034,7 @@ class FastqKMerMatcher:
         _ready(text, class_vi, flags)
         ticket = C.c_int64(-1)
         self._text_keep = text  # the copy is asynchronous
+        self._text_reads = int(n_lines) // 4
         _check(lib().gs_match_submit_text(self.h, pt, n_bytes, int(n_lines), mem, first_read_no, pc, pf, C.byref(ticket)))
         return ticket.value
 
@@ -1076,6 +1079,45 @@ class FastqKMerMatcher:
         _check(lib().gs_match_compact_text(self.h, int(with_probs), int(slot), C.byref(p), C.byref(nb), C.byref(nr)))
         _check(lib().gs_match_get_device(self.h, C.byref(d)))
         return _fetch_device(d.value, p, nb.value), nr.value
+
+    def set_taxids(self, taxids):
+        """gs_match_set_taxids: the taxid string of every value index (str or bytes), for kraken_text; may be called again"""
+        raw = [t.encode() if isinstance(t, str) else bytes(t) for t in taxids]
+        assert len(raw) == self.store.n_values, "one taxid string per value index"
+        arr = (C.c_char_p * max(len(raw), 1))(*raw)
+        _check(lib().gs_match_set_taxids(self.h, arr))
+
+    def kraken_text(self, write_all=True, slot=0):
+        """gs_match_kraken_text: the Kraken-style lines of the last four-line chunk (submitted with a class array), written on the
+        device -> bytes.  To be called before the next submit; segments_fetch-style calls see this chunk's segments afterwards."""
+        p, nb, nl, d = C.c_void_p(), C.c_int64(0), C.c_int64(0), C.c_int(0)
+        _check(lib().gs_match_kraken_text(self.h, int(bool(write_all)), int(slot), C.byref(p), C.byref(nb), C.byref(nl)))
+        _check(lib().gs_match_get_device(self.h, C.byref(d)))
+        self.kraken_lines = nl.value
+        return _fetch_device(d.value, p, nb.value).tobytes()
+
+    def text_segments(self):
+        """Kraken-style segments of the last text chunk (gs_match_segments_text + gs_match_segments_fetch):
+        (seg_off uint64[n + 1], codes int32[], starts int32[])"""
+        seg_off = np.zeros(int(self._text_reads) + 1, dtype=np.uint64)
+        _check(lib().gs_match_segments_text(self.h, seg_off.ctypes.data_as(C.c_void_p)))
+        codes, starts = self.segments_fetch(int(seg_off[-1]))
+        return seg_off, codes, starts
+
+    def segments_fetch(self, total):
+        """gs_match_segments_fetch alone: (codes, starts) of the `total` segments the last segments call -- or kraken_text, which
+        computes them -- has left on the device"""
+        codes = np.zeros(max(int(total), 1), dtype=np.int32)
+        starts = np.zeros(max(int(total), 1), dtype=np.int32)
+        _check(lib().gs_match_segments_fetch(self.h, codes.ctypes.data_as(C.c_void_p), starts.ctypes.data_as(C.c_void_p)))
+        return codes[:int(total)], starts[:int(total)]
+
+    def kraken_time(self):
+        """gs_match_kraken_time: (event pairs, device ms) of the text kernels of kraken_text so far -- a pair around the size pass and
+        one around the write pass of every call (MatchConfig(profile=True))"""
+        n, ms = C.c_int64(0), C.c_double(0.0)
+        _check(lib().gs_match_kraken_time(self.h, C.byref(n), C.byref(ms)))
+        return n.value, ms.value
 
     def text_wait_copy(self, ticket):
         _check(lib().gs_match_text_wait_copy(self.h, ticket))

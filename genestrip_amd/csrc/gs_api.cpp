@@ -2068,6 +2068,7 @@ struct TextScan {
     u64 *d_cblocks = nullptr, *h_ctotals = nullptr;
     size_t clen_cap = 0, cblocks_cap = 0;
     const uint8_t *d_last_flags = nullptr;
+    const int32_t *d_last_class = nullptr;  // the same for its classes (gs_match_kraken_text)
     int64_t last_bytes = 0;
     bool last_four_line = false;
 };
@@ -2265,6 +2266,17 @@ struct gs_run {
     int64_t seg_total = 0;
     TextScan text;  // text mode (gs_match_submit_text)
     KernelTimer timer;  // cfg.profile
+    // Kraken-style lines as device text (gs_match_kraken_text): the taxid strings, the per-read arrays of the text kernels, the text
+    // of the last call per slot, page-locked totals (bytes, lines)
+    uint8_t *d_tax_bytes = nullptr;
+    uint32_t *d_tax_off = nullptr;
+    uint32_t *d_kr_name = nullptr;
+    u64 *d_kr_rec = nullptr, *d_kr_blocks = nullptr, *d_kr_totals = nullptr, *h_kr_totals = nullptr;
+    size_t kr_name_cap = 0, kr_rec_cap = 0, kr_blocks_cap = 0;
+    uint8_t *d_kr_out[2] = {nullptr, nullptr};
+    size_t kr_out_cap[2] = {0, 0};
+    std::vector<uint64_t> kr_seg_off;
+    KernelTimer kraken_timer;  // cfg.profile: the text kernels alone
 };
 
 
@@ -2473,6 +2485,7 @@ static int text_submit(TextScan &t, hipStream_t stream, const uint8_t *text, int
     t.last_bytes = n_bytes;
     t.last_four_line = !fasta;
     t.d_last_flags = nullptr;
+    t.d_last_class = nullptr;
     if (ticket) *ticket = tk;
     return GS_OK;
 }
@@ -2632,6 +2645,16 @@ static void run_free(gs_run *run) {
     gs_dev_free(run->d_seg_off);
     gs_dev_free(run->d_seg_code);
     gs_dev_free(run->d_seg_start);
+    timer_free(run->kraken_timer);
+    gs_dev_free(run->d_tax_bytes);
+    gs_dev_free(run->d_tax_off);
+    gs_dev_free(run->d_kr_name);
+    gs_dev_free(run->d_kr_rec);
+    gs_dev_free(run->d_kr_blocks);
+    gs_dev_free(run->d_kr_totals);
+    hipHostFree(run->h_kr_totals);
+    gs_dev_free(run->d_kr_out[0]);
+    gs_dev_free(run->d_kr_out[1]);
     text_free(run->text);
     {
         BatchStage &g = run->stage;
@@ -3080,6 +3103,7 @@ static int match_submit_text(gs_run *run, const uint8_t *text, int64_t n_bytes, 
     if (rc) return rc;
     if ((rc = text_touched(run->text, run->stream))) return rc;
     run->text.d_last_flags = df;
+    run->text.d_last_class = dc;
     return tb.dev_out ? GS_OK : stage_download(h, class_vi, flags, tb.n_reads, run->stream);  // (complete after gs_match_sync)
 }
 
@@ -5074,6 +5098,117 @@ extern "C" int gs_match_segments_fetch(gs_run *run, int32_t *codes, int32_t *sta
         HIP_TRY(hipMemcpy(codes, run->d_seg_code, sizeof(int32_t) * (size_t)run->seg_total, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(starts, run->d_seg_start, sizeof(int32_t) * (size_t)run->seg_total, hipMemcpyDeviceToHost));
     }
+    return GS_OK;
+}
+
+// ---- Kraken-style lines of a four-line chunk as device text (gs_kraken.hip)
+extern "C" int gs_match_set_taxids(gs_run *run, const char *const *taxids) try {
+    if (!run || !taxids) return fail(GS_E_INVALID, "NULL argument");
+    const size_t nv = (size_t)run->db->info.n_values;
+    std::vector<uint32_t> off(nv + 1, 0);
+    for (size_t v = 0; v < nv; v++) {
+        if (!taxids[v]) return fail(GS_E_INVALID, "NULL taxid string");
+        const size_t len = strlen(taxids[v]);
+        if (len > 0xffffffffu - off[v]) return fail(GS_E_INVALID, "taxid strings of 4 GiB and more");
+        off[v + 1] = off[v] + (uint32_t)len;
+    }
+    std::vector<uint8_t> bytes((size_t)off[nv] + 1);
+    for (size_t v = 0; v < nv; v++) memcpy(bytes.data() + off[v], taxids[v], off[v + 1] - off[v]);
+    HIP_TRY(hipSetDevice(run->db->device));
+    HIP_TRY(hipStreamSynchronize(run->stream));  // (nothing reads the earlier set any more)
+    int rc = renew(&run->d_tax_bytes, bytes.size());
+    if (!rc) rc = renew(&run->d_tax_off, nv + 1);
+    if (rc) {
+        gs_dev_free(run->d_tax_off);
+        run->d_tax_off = nullptr;
+        return rc;
+    }
+    HIP_TRY(hipMemcpy(run->d_tax_bytes, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(run->d_tax_off, off.data(), sizeof(uint32_t) * (nv + 1), hipMemcpyHostToDevice));
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_match_kraken_text(gs_run *run, int write_all, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_lines) try {
+    if (!run || !d_out || !n_bytes || !n_lines) return fail(GS_E_INVALID, "NULL argument");
+    *d_out = nullptr;
+    *n_bytes = *n_lines = 0;
+    if (slot < 0 || slot > 1) return fail(GS_E_INVALID, "slot must be 0 or 1");
+    TextScan &t = run->text;
+    if (t.tickets == 0) return fail(GS_E_STATE, "no text chunk has been submitted");
+    if (!t.last_four_line) return fail(GS_E_STATE, "the last chunk was not four-line FASTQ");
+    if (!run->d_tax_off) return fail(GS_E_STATE, "no taxid strings are set (gs_match_set_taxids)");
+    const int64_t n = t.last_reads;
+    if (n > 0 && !t.d_last_class) return fail(GS_E_STATE, "the last chunk was submitted without a class array");
+    HIP_TRY(hipSetDevice(run->db->device));
+    uint32_t skip = 0;
+    HIP_TRY(hipMemcpyAsync(&skip, t.d_status + (size_t)t.bank * GS_TS_WORDS + GS_TS_SKIP, sizeof(skip), hipMemcpyDeviceToHost, run->stream));
+    HIP_TRY(hipStreamSynchronize(run->stream));
+    if (skip) return fail(GS_E_STATE, "the last chunk was refused (gs_match_text_status)");
+    run->seg_total = 0;
+    if (n == 0) return GS_OK;
+    run->kr_seg_off.resize((size_t)n + 1);
+    run->kr_seg_off[0] = 0;
+    int rc = segments_core(run, t.d_text, (const uint64_t *)t.d_off2, n, 2, run->kr_seg_off.data());
+    if (rc) return rc;
+    const size_t n_blocks = ((size_t)n + 255) / 256;
+    if ((rc = grow(&run->d_kr_name, &run->kr_name_cap, (size_t)n, run->stream))) return rc;
+    if ((rc = grow(&run->d_kr_rec, &run->kr_rec_cap, (size_t)n + 1, run->stream))) return rc;
+    if ((rc = grow(&run->d_kr_blocks, &run->kr_blocks_cap, n_blocks + 1, run->stream))) return rc;
+    if (!run->d_kr_totals) HIP_TRY(gs_dev_alloc(&run->d_kr_totals, 2 * sizeof(u64)));
+    if (!run->h_kr_totals) HIP_TRY(hipHostMalloc((void **)&run->h_kr_totals, 2 * sizeof(u64)));
+    GsKrakenParams P{};
+    P.text = t.d_text;
+    P.nl = t.d_nl;
+    P.n_reads = n;
+    P.k = run->db->info.k;
+    P.write_all = write_all != 0;
+    P.cls = t.d_last_class;
+    P.seg_off = run->d_seg_off;
+    P.seg_code = run->d_seg_code;
+    P.seg_start = run->d_seg_start;
+    P.tax_bytes = run->d_tax_bytes;
+    P.tax_off = run->d_tax_off;
+    P.name_len = run->d_kr_name;
+    P.rec_out = run->d_kr_rec;
+    P.rec_block = run->d_kr_blocks;
+    P.totals = run->d_kr_totals;
+    const bool profile = run->cfg.profile != 0;
+    HIP_TRY(hipMemsetAsync(run->d_kr_totals, 0, 2 * sizeof(u64), run->stream));
+    if (run->seg_total == 0)  // (no read has a segment: no line; the segment arrays do not exist)
+        run->h_kr_totals[0] = run->h_kr_totals[1] = 0;
+    else {  // an event pair per pass: the read-back of the total between them is not kernel time
+        if ((rc = timer_start(run->kraken_timer, profile, run->stream))) return rc;
+        HIP_TRY(gs_launch_kraken_size(&P, run->stream));
+        if ((rc = timer_stop(run->kraken_timer, profile, run->stream))) return rc;
+        HIP_TRY(hipMemcpyAsync(run->h_kr_totals, run->d_kr_totals, 2 * sizeof(u64), hipMemcpyDeviceToHost, run->stream));
+        HIP_TRY(hipStreamSynchronize(run->stream));  // the text's size: the buffer is made for exactly that
+    }
+    const u64 total = run->h_kr_totals[0];
+    if (total > 0) {
+        if ((rc = grow(&run->d_kr_out[slot], &run->kr_out_cap[slot], (size_t)total + 16, run->stream))) return rc;
+        P.out = run->d_kr_out[slot];
+        if ((rc = timer_start(run->kraken_timer, profile, run->stream))) return rc;
+        HIP_TRY(gs_launch_kraken_write(&P, run->stream));
+        if ((rc = timer_stop(run->kraken_timer, profile, run->stream))) return rc;
+    }
+    if ((rc = text_touched(t, run->stream))) return rc;
+    HIP_TRY(hipStreamSynchronize(run->stream));
+    *d_out = total > 0 ? run->d_kr_out[slot] : nullptr;
+    *n_bytes = (int64_t)total;
+    *n_lines = (int64_t)run->h_kr_totals[1];
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_match_kraken_time(gs_run *run, int64_t *launches, double *total_ms) {
+    if (!run) return fail(GS_E_INVALID, "run is NULL");
+    HIP_TRY(hipSetDevice(run->db->device));
+    HIP_TRY(hipStreamSynchronize(run->stream));
+    int rc = timer_collect(run->kraken_timer);
+    if (rc) return rc;
+    if (launches) *launches = run->kraken_timer.launches;
+    if (total_ms) *total_ms = run->kraken_timer.total_ms;
     return GS_OK;
 }
 

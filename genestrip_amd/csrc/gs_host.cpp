@@ -347,6 +347,14 @@ inline bool device_output() {
     return true;
 }
 
+// GS_DEVICE_KRAKEN=0: the Kraken-style lines are formatted on host threads (and with them the filtered file of the same call, as
+// before the lines were made on the device); everything else stays as it is
+inline bool device_kraken() {
+    if (!device_output()) return false;
+    if (const char *e = getenv("GS_DEVICE_KRAKEN")) return atoi(e) != 0;
+    return true;
+}
+
 // The device side of one output file of the filter / match goal: the records the file wants have been gathered on the device
 // (gs_filter_compact_text / gs_match_compact_text); emit() compresses them there when the file is gzip (gs_deflater_pack: BGZF
 // members, what OutFile::pack makes with zlib on host threads) or fetches them as they are, into one of two page-locked buffers,
@@ -469,7 +477,9 @@ struct MatchCtx {
     int64_t global_read_no = 0, filtered_reads = 0;  // read numbers run over all files of the call (file order)
     int64_t reads = 0, kmers = 0, bps = 0;
     double t_gpu = 0, t_parse = 0;
-    DeviceWriter filtered_dev;  // the filtered file fed from the device (TextJob::emit_filtered_device)
+    DeviceWriter filtered_dev;  // the filtered file fed from the device (TextJob::emit_device)
+    DeviceWriter kraken_dev;    // the Kraken-style lines made on the device (gs_match_kraken_text), a deflater of its own
+    bool taxids_on_device = false;  // gs_match_set_taxids has been called for this run
     // CountsPerTaxid.maxContigDescriptor for a host that never sees the reads (opts->max_contig_desc): after every chunk the device
     // names the read that holds each tax id's longest contig (gs_match_max_contig_reads); a holder that lies in the chunk just
     // submitted gets its name fetched while the chunk's text is at hand.  A maximum only moves to a later read by beating it, so
@@ -670,6 +680,7 @@ int parsed_source(MatchCtx &c, const std::string &path, int64_t offset, const ui
 
 std::atomic<int64_t> g_ml_chunks{0};  // chunks matched through the general FASTQ device path (gs_host_stat(0))
 std::atomic<int64_t> g_filter_general_chunks{0};  // FASTA / general FASTQ chunks filtered on the device (gs_host_stat(1))
+std::atomic<int64_t> g_kraken_device_chunks{0};  // chunks whose Kraken-style lines were written on the device (gs_host_stat(2))
 
 struct TextChunk {
     int64_t file_off;  // of the chunk's first byte
@@ -1137,23 +1148,36 @@ struct TextJob {
         });
     }
 
-    // Filtered FASTQ without Kraken-style lines: the reads matchRead returned true for (afterMatch, FastqKMerMatcher.java:304-307) are
-    // gathered on the device and -- for a .gz file -- compressed there; the chunk's text never comes to the host.
-    bool device_filtered() const { return device_output() && c.filtered.active() && !c.kraken.active(); }
+    // Per-read outputs of a four-line chunk made on the device: the reads matchRead returned true for (afterMatch,
+    // FastqKMerMatcher.java:304-307) are gathered there, the Kraken-style lines (:308-314) are written there behind the segments kernel,
+    // and -- for a .gz file -- both are compressed there; the chunk's text, its newline offsets and its segments never come to the host.
+    // GS_DEVICE_KRAKEN=0 takes the lines, and with them the filtered file, back to the host formatter.
+    bool device_filtered() const { return device_output() && c.filtered.active() && (!c.kraken.active() || device_kraken()); }
+    bool device_lines() const { return c.kraken.active() && device_kraken(); }
+    bool device_per_read() const { return device_filtered() || device_lines(); }
     int dev_err_ = GS_OK;
-    // after the chunk's flags are in (check_refusal has synchronised): gather now, compress / fetch / write on a thread of its own
-    int emit_filtered_device() {
+    // after the chunk's flags are in (check_refusal has synchronised): gather and write the lines now, compress / fetch / write on a
+    // thread of its own
+    int emit_device() {
         const int set = (int)(n_formatted & 1);
-        const uint8_t *d = nullptr;
-        int64_t nb = 0, nr = 0;
-        int err = gs_match_compact_text(c.run, c.opts->with_probs != 0, set, &d, &nb, &nr);
+        const uint8_t *d = nullptr, *kd = nullptr;
+        int64_t nb = 0, nr = 0, knb = 0, knl = 0;
+        int err = GS_OK;
+        if (c.filtered.active()) err = gs_match_compact_text(c.run, c.opts->with_probs != 0, set, &d, &nb, &nr);
+        if (!err && c.kraken.active()) {
+            if (!c.taxids_on_device) err = gs_match_set_taxids(c.run, c.opts->taxids);
+            c.taxids_on_device = !err;
+            if (!err) err = gs_match_kraken_text(c.run, c.opts->write_all != 0, set, &kd, &knb, &knl);
+            if (!err) g_kraken_device_chunks.fetch_add(1);
+        }
         if (err) return err;
         c.filtered_reads += nr;
         drain();  // one chunk at a time: output order
         if (dev_err_) return dev_err_;
         n_formatted++;
-        auto job = [this, set, d, nb] {
-            const int e = c.filtered_dev.emit(set, d, nb);
+        auto job = [this, set, d, nb, kd, knb] {
+            int e = c.filtered_dev.emit(set, d, nb);
+            if (!e) e = c.kraken_dev.emit(set, kd, knb);
             if (e) dev_err_ = e;
         };
         run_behind(formatting, job);
@@ -1176,6 +1200,7 @@ struct TextJob {
         if (!err && gzip && !fasta && !general && gs_match_get_device(c.run, &device) == GS_OK)
             dev_.open(tr.map, tr.map_len, device, (c.filtered.active() || c.kraken.active()) ? gunzip_first_span() : gunzip_first_span_match());
         if (!err && c.filtered.active() && gs_match_get_device(c.run, &device) == GS_OK) c.filtered_dev.begin(&c.filtered, device);
+        if (!err && c.kraken.active() && gs_match_get_device(c.run, &device) == GS_OK) c.kraken_dev.begin(&c.kraken, device);
         if (!err && !dev_.bgzf() && !dev_.whole()) tr.start();
         return err;
     }
@@ -1212,7 +1237,7 @@ struct TextJob {
         }
         MatchCtx::Results &rs = c.res[n_formatted & 1];  // (the set of the chunk before last: its writers are done)
         PooledBuf &tb = dev_text_[n_formatted & 1];
-        const bool dev_f = device_filtered();
+        const bool dev_f = device_per_read();
         int err = rs.cls.resize((size_t)n_chunk);
         if (!err) err = rs.flags.resize((size_t)n_chunk);
         if (!err && !dev_f) err = tb.need((size_t)t.n_bytes);
@@ -1230,7 +1255,7 @@ struct TextJob {
         if (first_ticket < 0) first_ticket = ticket;
         reads_in_file += n_chunk;
         cut_.file_off += t.n_bytes;
-        if (dev_f) return emit_filtered_device();
+        if (dev_f) return emit_device();
         drain();  // one chunk at a time: output order, and the other result set becomes free
         n_formatted++;
         const uint8_t *h_text = static_cast<const uint8_t *>(tb.p);
@@ -1353,14 +1378,16 @@ struct TextJob {
             err = gs_match_submit_text(c.run, start, cut_.bytes, cut_.lines, GS_MEM_HOST, first_no, per_read ? rs.cls.data() : nullptr,
                                        per_read ? rs.flags.data() : nullptr, &ticket);
         if (!err) err = chunk_submitted(first_no, n_chunk);
-        const bool dev_f = per_read && device_filtered() && c.filtered.gzip();  // (a plain file: formatted from the reader's block, which is here anyway)
+        // (a plain filtered file alone: formatted from the reader's block, which is here anyway; the lines need the segments, which
+        // are on the device)
+        const bool dev_f = per_read && device_per_read() && (device_lines() || c.filtered.gzip());
         if (!err && per_read) {  // the writers need this chunk's results
             chunks.push_back({cut_.file_off, reads_in_file, ticket});
             err = check_refusal(fallback_off, fallback_reads);
             chunks.pop_back();
             if (!err && *fallback_off < 0 && !dev_f) err = fetch_chunk_results(rs, n_chunk);
             format_it = !err && *fallback_off < 0 && !dev_f;
-            if (!err && *fallback_off < 0 && dev_f) err = emit_filtered_device();
+            if (!err && *fallback_off < 0 && dev_f) err = emit_device();
         }
         if (!err && *fallback_off < 0) {
             if (first_ticket < 0) first_ticket = ticket;
@@ -1766,6 +1793,7 @@ extern "C" int gs_host_match_files(gs_db *db, const gs_match_cfg *cfg, const cha
     gs_match_destroy(c.run);
     const bool wrote = c.filtered.close() & c.kraken.close();  // (both are flushed before the clock stops)
     if (!err) err = c.filtered_dev.late_err;
+    if (!err) err = c.kraken_dev.late_err;
     if (getenv("GS_HOST_TRACE") != nullptr)
         fprintf(stderr, "match files: begin %.2f ms, files %.2f, finish %.2f, destroy + close %.2f\n", (t_start - t_begin) * 1e3, (t_files - t_start) * 1e3, (t_fin - t_files) * 1e3,
                 (now_s() - t_fin) * 1e3);
@@ -1816,6 +1844,7 @@ extern "C" int gs_host_match_run(gs_run *run, gs_db *db, const char *const *path
     if (!err) err = gs_match_sync(run);
     const bool wrote = c.filtered.close() & c.kraken.close();
     if (!err) err = c.filtered_dev.late_err;
+    if (!err) err = c.kraken_dev.late_err;
     if (!err && !wrote) err = hfail(GS_E_IO, "write to an output file failed");
     if (totals) {
         totals->reads = c.reads;
@@ -2568,7 +2597,12 @@ extern "C" int gs_host_release_pools(void) try {
 }
 
 extern "C" int64_t gs_host_stat(int which) {
-    return which == 0 ? g_ml_chunks.load() : (which == 1 ? g_filter_general_chunks.load() : -1);
+    switch (which) {
+        case 0: return g_ml_chunks.load();
+        case 1: return g_filter_general_chunks.load();
+        case 2: return g_kraken_device_chunks.load();
+        default: return -1;
+    }
 }
 
 // ---- db2fastq (C/goals/DB2FastqGoal.java -> KMerFastqGenerator.generateFastq): the text is made on the device chunk by chunk

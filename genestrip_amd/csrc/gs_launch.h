@@ -131,6 +131,11 @@ hipError_t gs_launch_rewrite_heads(const GsRewriteParams *P, hipStream_t stream)
 hipError_t gs_launch_rewrite_copy(const GsRewriteParams *P, int64_t out_bound, int n_cu, hipStream_t stream);
 hipError_t gs_launch_select(const uint8_t *text, const uint32_t *nl, const uint32_t *rec_line, int64_t n_records, const uint8_t *key, int32_t key_len,
                             const uint32_t *skip, uint8_t *accept, hipStream_t stream);
+hipError_t gs_launch_scan_blocks(u64 *blocks, int64_t n_blocks, u64 *total_out, hipStream_t stream);
+
+// ---- gs_kraken.hip: Kraken-style lines as device text
+hipError_t gs_launch_kraken_size(const GsKrakenParams *P, hipStream_t stream);
+hipError_t gs_launch_kraken_write(const GsKrakenParams *P, hipStream_t stream);
 
 // ---- gs_merge.hip: merge of runs that live in one process
 hipError_t gs_launch_merge_i64(void *dst, const void *src, int64_t n, int op, hipStream_t stream);

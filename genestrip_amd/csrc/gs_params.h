@@ -181,6 +181,25 @@ struct GsRewriteParams {
     uint8_t *out;
 };
 
+// Kraken-style lines of a four-line chunk as device text (gs_kraken.hip), behind the segments of the chunk's reads
+struct GsKrakenParams {
+    const uint8_t *text;              // the chunk and its newline offsets, as GsTextParams
+    const uint32_t *nl;
+    int64_t n_reads;
+    int32_t k, write_all;
+    const int32_t *cls;               // per read: value index of its class, < 0: unclassified
+    const unsigned long long *seg_off;  // n_reads + 1; the segments of read r: [seg_off[r], seg_off[r + 1])
+    const int32_t *seg_code;          // value index, -1: no hit, -2: a window with a bad base
+    const int32_t *seg_start;
+    const uint8_t *tax_bytes;         // taxid of value v: tax_bytes[tax_off[v] .. tax_off[v + 1])
+    const uint32_t *tax_off;
+    uint32_t *name_len;               // per read: bytes of its name (descriptor behind its first byte, up to the first blank)
+    unsigned long long *rec_out;      // n_reads + 1: where the line of every read starts (a read without a line: an empty one)
+    unsigned long long *rec_block;    // per block of 256 reads
+    unsigned long long *totals;       // [0] bytes of text [1] lines
+    uint8_t *out;
+};
+
 struct GsFilterParams {
     int32_t kind;           // GS_BLOOM_*
     int32_t k;

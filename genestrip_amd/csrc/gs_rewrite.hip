@@ -35,10 +35,11 @@
 
 #include "gs_launch.h"
 #include "gs_params.h"
+#include "gs_scan.h"
 
 #define RW_HDR (1ULL << 40)
 #define RW_LEN_MASK (RW_HDR - 1)
-#define RW_BLOCK 256
+#define RW_BLOCK GS_SCAN_BLOCK
 #define RW_PIECE (RW_BLOCK * 16)  // output bytes per block and step of the copy
 #define RW_LONG_LINE 65534        // bytes incl. the newline from which AbstractFastaReader.readFasta throws (a buffer of 65 535)
 
@@ -51,26 +52,6 @@ __device__ __forceinline__ uint32_t rw_line_start(const GsRewriteParams &P, int6
 __device__ __forceinline__ uint32_t rw_kept(const uint8_t *text, uint32_t start, uint32_t len) {
     while (len > 0 && text[(size_t)start + len - 1] == '\r') len--;
     return len;
-}
-
-// exclusive prefix of v over the block (RW_BLOCK threads, every one of them arrives); *total: the block's sum
-__device__ __forceinline__ u64 rw_block_scan(u64 v, u64 *s_wave, u64 *total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    u64 inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u64 x = __shfl_up(inc, d);
-        if (lane >= d) inc += x;
-    }
-    if (lane == 63) s_wave[wv] = inc;
-    __syncthreads();
-    u64 before = 0, all = 0;
-    for (int w = 0; w < RW_BLOCK / 64; w++) {
-        if (w < wv) before += s_wave[w];
-        all += s_wave[w];
-    }
-    *total = all;
-    return before + inc - v;
 }
 
 __global__ __launch_bounds__(RW_BLOCK) void rw_lines_kernel(GsRewriteParams P) {
@@ -89,7 +70,7 @@ __global__ __launch_bounds__(RW_BLOCK) void rw_lines_kernel(GsRewriteParams P) {
         v = hdr ? RW_HDR : (u64)rw_kept(P.text, start, len);
     }
     u64 total;
-    const u64 ex = rw_block_scan(v, s_wave, &total);
+    const u64 ex = gs_block_scan(v, s_wave, &total);
     if (i < P.n_lines) P.fa_scan[i] = ex;
     if (threadIdx.x == 0) P.fa_block[blockIdx.x] = total;
 }
@@ -165,7 +146,7 @@ __global__ __launch_bounds__(RW_BLOCK) void rw_size_kernel(GsRewriteParams P) {
     const u64 wanted = __ballot(sz != 0);
     if ((threadIdx.x & 63) == 0 && wanted) atomicAdd(&P.totals[1], (u64)__popcll(wanted));
     u64 total;
-    const u64 ex = rw_block_scan(sz, s_wave, &total);
+    const u64 ex = gs_block_scan(sz, s_wave, &total);
     if (r < P.n_records) P.rec_out[r] = ex;
     if (threadIdx.x == 0) P.rec_block[blockIdx.x] = total;
 }
@@ -302,6 +283,12 @@ extern "C" hipError_t gs_launch_rewrite_copy(const GsRewriteParams *P, int64_t o
     hipLaunchKernelGGL(rw_pieces_kernel, dim3((unsigned)((pieces + RW_BLOCK - 1) / RW_BLOCK)), dim3(RW_BLOCK), 0, stream, *P);
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(pieces, (int64_t)n_cu * 8));
     hipLaunchKernelGGL(rw_copy_kernel, dim3(grid), dim3(RW_BLOCK), 0, stream, *P);
+    return hipGetLastError();
+}
+
+// blocks[0 .. n_blocks) -> their exclusive prefix in place, *total_out = the sum (one block of 1024 threads)
+extern "C" hipError_t gs_launch_scan_blocks(u64 *blocks, int64_t n_blocks, u64 *total_out, hipStream_t stream) {
+    hipLaunchKernelGGL(rw_scan_kernel, dim3(1), dim3(1024), 0, stream, blocks, n_blocks, total_out, (int64_t)-1, (uint32_t *)nullptr);
     return hipGetLastError();
 }
 

@@ -157,7 +157,8 @@ def match_files(store, paths, config=None, filtered_path=None, kraken_out_path=N
 
 
 def stat(which=0):
-    """gs_host_stat: 0 = chunks that went through the general (multi-line) FASTQ device path in this process so far"""
+    """gs_host_stat: 0 = chunks that went through the general (multi-line) FASTQ device path in this process so far; 1 = FASTA / general
+    FASTQ chunks the filter goal handled on the device; 2 = chunks whose Kraken-style lines were written on the device"""
     return int(lib().gs_host_stat(which))
 
 

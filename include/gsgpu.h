@@ -834,6 +834,22 @@ const char *gs_inflate_last_error(void);
 typedef struct gs_deflater gs_deflater;
 int gs_filter_compact_text(gs_bloom *bloom, int which, int with_probs, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_records);
 int gs_match_compact_text(gs_run *run, int with_probs, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_records);
+
+/* ---- Kraken-style lines of a four-line chunk as device text (gs_kraken.hip) -------------------------------------------------
+ * taxid string per value index (SmallTaxIdNode.getTaxId), copied to the run's device: bytes back to back + n_values + 1 offsets.
+ * NULL entries: GS_E_INVALID.  Any bytes, any length (0 included).  May be called again; replaces the earlier set. */
+int gs_match_set_taxids(gs_run *run, const char *const *taxids);
+/* The Kraken-style lines (FastqKMerMatcher.java:308-314, :597-611, :723-756) of the most recent FOUR-LINE text chunk of the run,
+ * in read order, as device text.  *d_out: a buffer of the run's, valid until the next call with the same slot (0 / 1);
+ * *n_bytes, *n_lines: what was written.  Synchronises the run's stream, as gs_match_compact_text does.
+ * To be called before the next submit on the run.  GS_E_STATE: no chunk submitted, the last one was FASTA or general FASTQ, was
+ * refused, was submitted without a class array, or no taxids are set.  Afterwards gs_match_segments_fetch returns this chunk's
+ * segments (the call computes them as gs_match_segments_text does). */
+int gs_match_kraken_text(gs_run *run, int write_all, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_lines);
+/* accumulated device time of the text kernels of gs_match_kraken_text since gs_match_begin (cfg.profile != 0): one event pair
+ * around the size pass (sizes, prefix, offsets) and one around the write pass of every call -- `launches` counts the pairs; neither
+ * the segments nor the read-back of the text's size between the two passes is in it */
+int gs_match_kraken_time(gs_run *run, int64_t *launches, double *total_ms);
 int gs_deflater_create(gs_deflater **out, int device);
 int gs_deflater_pack(gs_deflater *d, const uint8_t *d_text, int64_t n, uint8_t *out, int64_t out_cap, int64_t *n_out);
 int gs_deflater_info(const gs_deflater *d, int64_t info[3]);
