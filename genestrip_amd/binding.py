@@ -42,7 +42,7 @@ ABI_SYMBOLS = (
     "gs_bloom_create", "gs_bloom_build", "gs_bloom_get", "gs_bloom_destroy", "gs_filter_submit", "gs_filter_sync", "gs_filter_kernel_time",
     "gs_calibrate",
     "gs_match_get_device", "gs_inflate_members", "gs_inflater_create", "gs_inflater_feed", "gs_inflater_tail", "gs_gunzipper_open", "gs_gunzipper_reopen", "gs_gunzipper_next", "gs_gunzipper_info", "gs_gunzipper_first_span", "gs_gunzipper_park", "gs_gunzipper_close", "gs_gunzip_plan_device", "gs_gunzip_free", "gs_gunzip_device", "gs_text_cut_device", "gs_device_fetch", "gs_inflater_fetch", "gs_filter_get_device", "gs_inflater_reset", "gs_inflater_destroy", "gs_inflate_last_error",
-    "gs_filter_compact_text", "gs_match_compact_text", "gs_match_set_taxids", "gs_match_kraken_text", "gs_match_kraken_time", "gs_deflater_create", "gs_deflater_pack", "gs_deflater_info", "gs_deflater_destroy", "gs_deflater_append", "gs_deflater_pending", "gs_deflater_flush",
+    "gs_filter_compact_text", "gs_match_compact_text", "gs_filter_compact_records", "gs_match_compact_records", "gs_match_kraken_records", "gs_match_set_taxids", "gs_match_kraken_text", "gs_match_kraken_time", "gs_deflater_create", "gs_deflater_pack", "gs_deflater_info", "gs_deflater_destroy", "gs_deflater_append", "gs_deflater_pending", "gs_deflater_flush",
     "gs_deflate_bound", "gs_deflate_host", "gs_deflate_host_reference", "gs_deflate_last_error", "gs_match_text_descriptors", "gs_match_submit_fixed",
     "gs_db_value_counts", "gs_dbexport_create", "gs_dbexport_fetch", "gs_dbexport_get_device", "gs_dbexport_fastq_begin",
     "gs_dbexport_fastq_next", "gs_dbexport_destroy",
@@ -53,7 +53,7 @@ ABI_SYMBOLS = (
     "gs_dbsize_begin", "gs_dbsize_set_range", "gs_dbsize_add", "gs_dbsize_counts", "gs_dbsize_distinct", "gs_dbsize_get_stats",
     "gs_dbsize_destroy", "gs_dbsize_plan",
     "gs_reads_create", "gs_reads_destroy", "gs_reads_get_device", "gs_reads_sync", "gs_reads_select_text", "gs_reads_select_fasta",
-    "gs_reads_select_fastq_ml", "gs_reads_compact_text", "gs_reads_fasta2fastq", "gs_reads_text_read_bounds", "gs_reads_text_line_classes",
+    "gs_reads_select_fastq_ml", "gs_reads_compact_text", "gs_reads_compact_records", "gs_reads_fasta2fastq", "gs_reads_text_read_bounds", "gs_reads_text_line_classes",
     "gs_reads_text_wait_copy", "gs_reads_text_status", "gs_reads_text_reset", "gs_reads_kernel_time",
     "gs_reads_phase_times",
 )
@@ -219,6 +219,9 @@ def lib():
         "gs_inflate_last_error": (C.c_char_p, []),
         "gs_filter_compact_text": (ci, [vp, ci, ci, ci, vp, vp, vp]),
         "gs_match_compact_text": (ci, [vp, ci, ci, vp, vp, vp]),
+        "gs_filter_compact_records": (ci, [vp, ci, ci, ci, vp, vp, vp]),
+        "gs_match_compact_records": (ci, [vp, ci, ci, vp, vp, vp]),
+        "gs_match_kraken_records": (ci, [vp, ci, ci, vp, vp, vp]),
         "gs_match_set_taxids": (ci, [vp, vp]), "gs_match_kraken_text": (ci, [vp, ci, ci, vp, vp, vp]),
         "gs_match_kraken_time": (ci, [vp, vp, vp]),
         "gs_deflater_create": (ci, [vp, ci]),
@@ -246,6 +249,7 @@ def lib():
         "gs_reads_select_fasta": (ci, [vp, ci, vp, i64, i64, i64, ci, vp, i32, vp, vp, vp]),
         "gs_reads_select_fastq_ml": (ci, [vp, ci, vp, i64, i64, ci, vp, i32, vp, vp, vp, vp, vp, vp]),
         "gs_reads_compact_text": (ci, [vp, ci, ci, vp, vp, vp]),
+        "gs_reads_compact_records": (ci, [vp, ci, ci, vp, vp, vp]),
         "gs_reads_fasta2fastq": (ci, [vp, vp, i64, i64, i64, ci, ci, vp, vp, vp, vp]),
         "gs_reads_text_read_bounds": (ci, [vp, vp]), "gs_reads_text_line_classes": (ci, [vp, vp]),
         "gs_reads_text_wait_copy": (ci, [vp, i64]), "gs_reads_text_status": (ci, [vp, vp, vp, vp]), "gs_reads_text_reset": (ci, [vp, ci]),
@@ -1059,17 +1063,22 @@ class FastqKMerMatcher:
                                            C.byref(ticket)))
         return ticket.value
 
-    def submit_fastq_ml(self, text, n_lines=None, first_read_no=0):
+    def submit_fastq_ml(self, text, n_lines=None, first_read_no=0, class_vi=None, flags=None):
         """general FASTQ text (sequence / quality over any number of lines) starting at a descriptor line: -> (records matched,
-        bytes they cover); the rest belongs in front of the next chunk (gs_match_submit_fastq_ml)"""
+        bytes they cover); the rest belongs in front of the next chunk (gs_match_submit_fastq_ml).  class_vi / flags: room for
+        n_lines // 4 + 1 records"""
         pt, mem = _ptr(text)
         n_bytes = int(text.shape[0] if hasattr(text, "shape") else len(text))
         if n_lines is None:
             n_lines = int(np.count_nonzero(np.asarray(text) == 10)) if mem == MEM_HOST else int((text == 10).sum().item())
         n_rec, used, ticket = C.c_int64(0), C.c_int64(0), C.c_int64(-1)
-        _ready(text)
-        _check(lib().gs_match_submit_fastq_ml(self.h, pt, n_bytes, n_lines, mem, first_read_no, None, None, C.byref(n_rec), C.byref(used),
+        pc, _ = _ptr(class_vi)
+        pf, _ = _ptr(flags)
+        _ready(text, class_vi, flags)
+        self._text_keep = text
+        _check(lib().gs_match_submit_fastq_ml(self.h, pt, n_bytes, n_lines, mem, first_read_no, pc, pf, C.byref(n_rec), C.byref(used),
                                               None, C.byref(ticket)))
+        self._text_reads = max(n_rec.value, 0)
         return max(n_rec.value, 0), used.value
 
     def compact_text(self, with_probs=False, slot=0):
@@ -1077,6 +1086,13 @@ class FastqKMerMatcher:
         gathered on the device -> (bytes as numpy uint8, records)"""
         p, nb, nr, d = C.c_void_p(), C.c_int64(0), C.c_int64(0), C.c_int(0)
         _check(lib().gs_match_compact_text(self.h, int(with_probs), int(slot), C.byref(p), C.byref(nb), C.byref(nr)))
+        _check(lib().gs_match_get_device(self.h, C.byref(d)))
+        return _fetch_device(d.value, p, nb.value), nr.value
+
+    def compact_records(self, with_probs=False, slot=0):
+        """gs_match_compact_records: the same for the last FASTA or general FASTQ chunk -> (bytes as numpy uint8, records)"""
+        p, nb, nr, d = C.c_void_p(), C.c_int64(0), C.c_int64(0), C.c_int(0)
+        _check(lib().gs_match_compact_records(self.h, int(with_probs), int(slot), C.byref(p), C.byref(nb), C.byref(nr)))
         _check(lib().gs_match_get_device(self.h, C.byref(d)))
         return _fetch_device(d.value, p, nb.value), nr.value
 
@@ -1092,6 +1108,14 @@ class FastqKMerMatcher:
         device -> bytes.  To be called before the next submit; segments_fetch-style calls see this chunk's segments afterwards."""
         p, nb, nl, d = C.c_void_p(), C.c_int64(0), C.c_int64(0), C.c_int(0)
         _check(lib().gs_match_kraken_text(self.h, int(bool(write_all)), int(slot), C.byref(p), C.byref(nb), C.byref(nl)))
+        _check(lib().gs_match_get_device(self.h, C.byref(d)))
+        self.kraken_lines = nl.value
+        return _fetch_device(d.value, p, nb.value).tobytes()
+
+    def kraken_records(self, write_all=True, slot=0):
+        """gs_match_kraken_records: the same for the last FASTA or general FASTQ chunk -> bytes"""
+        p, nb, nl, d = C.c_void_p(), C.c_int64(0), C.c_int64(0), C.c_int(0)
+        _check(lib().gs_match_kraken_records(self.h, int(bool(write_all)), int(slot), C.byref(p), C.byref(nb), C.byref(nl)))
         _check(lib().gs_match_get_device(self.h, C.byref(d)))
         self.kraken_lines = nl.value
         return _fetch_device(d.value, p, nb.value).tobytes()
@@ -1398,6 +1422,12 @@ class FastqBloomFilter:
         _check(lib().gs_filter_compact_text(self.bloom.h, int(which), int(with_probs), int(slot), C.byref(p), C.byref(nb), C.byref(nr)))
         return _fetch_device(self.bloom.device, p, nb.value), nr.value
 
+    def compact_records(self, which=1, with_probs=False, slot=0):
+        """gs_filter_compact_records: the same for the last FASTA or general FASTQ chunk -> (bytes as numpy uint8, records)"""
+        p, nb, nr = C.c_void_p(), C.c_int64(0), C.c_int64(0)
+        _check(lib().gs_filter_compact_records(self.bloom.h, int(which), int(with_probs), int(slot), C.byref(p), C.byref(nb), C.byref(nr)))
+        return _fetch_device(self.bloom.device, p, nb.value), nr.value
+
     def text_reset(self, clear_totals=False):
         _check(lib().gs_filter_text_reset(self.bloom.h, int(clear_totals)))
 
@@ -1481,6 +1511,13 @@ class DeviceReads:
         """the selected records of the last four-line or FASTA chunk as ReadEntry.write writes them -> (bytes, records)"""
         p, nb, nr = C.c_void_p(), C.c_int64(0), C.c_int64(0)
         _check(lib().gs_reads_compact_text(self.h, int(with_probs), int(slot), C.byref(p), C.byref(nb), C.byref(nr)))
+        return _fetch_device(self.device, p, nb.value), nr.value
+
+    def compact_records(self, with_probs=True, slot=0):
+        """the selected records of the last FASTA or general FASTQ chunk as ReadEntry.write writes them, the latter with their
+        quality lines if with_probs -> (bytes, records)"""
+        p, nb, nr = C.c_void_p(), C.c_int64(0), C.c_int64(0)
+        _check(lib().gs_reads_compact_records(self.h, int(with_probs), int(slot), C.byref(p), C.byref(nb), C.byref(nr)))
         return _fetch_device(self.device, p, nb.value), nr.value
 
     def fasta2fastq(self, text, n_lines=None, n_records=None, slot=0):

@@ -2071,6 +2071,19 @@ struct TextScan {
     const int32_t *d_last_class = nullptr;  // the same for its classes (gs_match_kraken_text)
     int64_t last_bytes = 0;
     bool last_four_line = false;
+    bool last_ml = false;  // the last chunk was general FASTQ
+    // the writers' text of FASTA and general FASTQ chunks (gs_*_compact_records, gs_rewrite.hip): the descriptor line of every record,
+    // the quality lines gathered (scan words, per-block sums, destinations, bytes, bounds), offsets of the records' text, the text per
+    // slot, totals and their page-locked landing area; the ticket of the chunk whose descriptor lines / qualities are in place
+    uint32_t *d_rt_line = nullptr, *d_rt_piece = nullptr, *d_rt_qdst = nullptr;
+    u64 *d_rt_out = nullptr, *d_rt_block = nullptr, *d_rt_qscan = nullptr, *d_rt_qblock = nullptr, *d_rt_qoff = nullptr;
+    uint8_t *d_rt_qseq = nullptr;
+    size_t rt_line_cap = 0, rt_piece_cap = 0, rt_qdst_cap = 0, rt_out_cap = 0, rt_block_cap = 0, rt_qscan_cap = 0, rt_qblock_cap = 0, rt_qoff_cap = 0,
+           rt_qseq_cap = 0;
+    u64 *d_rt_tot = nullptr, *h_rt_tot = nullptr;
+    uint8_t *d_rt_text[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // [which][slot], as d_compact
+    size_t rt_text_cap[2][2] = {{0, 0}, {0, 0}};
+    int64_t rt_heads_ticket = -1, rt_quals_ticket = -1;
 };
 enum { GS_TEXT_BANKS = 16 };
 
@@ -2314,6 +2327,19 @@ static void text_free(TextScan &t) {
     gs_dev_free(t.d_clen);
     gs_dev_free(t.d_cblocks);
     if (t.h_ctotals) hipHostFree(t.h_ctotals);
+    gs_dev_free(t.d_rt_line);
+    gs_dev_free(t.d_rt_piece);
+    gs_dev_free(t.d_rt_qdst);
+    gs_dev_free(t.d_rt_out);
+    gs_dev_free(t.d_rt_block);
+    gs_dev_free(t.d_rt_qscan);
+    gs_dev_free(t.d_rt_qblock);
+    gs_dev_free(t.d_rt_qoff);
+    gs_dev_free(t.d_rt_qseq);
+    gs_dev_free(t.d_rt_tot);
+    if (t.h_rt_tot) hipHostFree(t.h_rt_tot);
+    for (auto &w : t.d_rt_text)
+        for (uint8_t *q : w) gs_dev_free(q);
     for (hipEvent_t ev : t.copied)
         if (ev) hipEventDestroy(ev);
     t = TextScan();
@@ -2484,6 +2510,7 @@ static int text_submit(TextScan &t, hipStream_t stream, const uint8_t *text, int
     t.last_lines = n_lines;
     t.last_bytes = n_bytes;
     t.last_four_line = !fasta;
+    t.last_ml = ml;
     t.d_last_flags = nullptr;
     t.d_last_class = nullptr;
     if (ticket) *ticket = tk;
@@ -2549,6 +2576,122 @@ static int text_batch(TextScan &t, hipStream_t stream, const uint8_t *text, int6
     tb->d_seq = tb->fasta ? t.d_fa_seq : t.d_text;
     tb->off_stride = tb->fasta ? 1 : 2;
     tb->d_skip = t.d_status + (size_t)t.bank * GS_TS_WORDS + GS_TS_SKIP;
+    return GS_OK;
+}
+
+// the text of a chunk's records is at most twice the chunk and five bytes per record (descriptor and read stand in the chunk, the
+// tail is as long as the read or stands in the chunk as well); a multiple of 16 with room behind the text
+static size_t reads_bound(int64_t n_bytes, int64_t n_records) { return ((2 * (size_t)n_bytes + 5 * (size_t)n_records + 15) & ~(size_t)15) + 64; }
+
+// GS_OK when the last chunk is one whose records lie gathered (FASTA, general FASTQ) and was not refused; synchronises
+static int records_state(TextScan &t, hipStream_t stream) {
+    if (t.tickets == 0) return fail(GS_E_STATE, "no text chunk has been submitted");
+    if (t.last_four_line) return fail(GS_E_STATE, "the last chunk was four-line FASTQ");
+    uint32_t skip = 0;
+    HIP_TRY(hipMemcpyAsync(&skip, t.d_status + (size_t)t.bank * GS_TS_WORDS + GS_TS_SKIP, sizeof(skip), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (skip) return fail(GS_E_STATE, "the last chunk was refused");
+    return GS_OK;
+}
+
+// what the rewrite kernels take from the latest chunk, a FASTA or general FASTQ one (ReadEntry mode)
+static void records_params(TextScan &t, GsRewriteParams *R) {
+    R->text = t.d_text;
+    R->n_lines = t.last_lines;  // (general FASTQ: the lines of its whole records)
+    R->n_records = t.last_reads;
+    R->nl = t.d_nl;
+    R->line_class = t.last_ml ? t.d_ml_class : nullptr;
+    R->fa_scan = (unsigned long long *)t.d_fa_scan;
+    R->fa_block = (unsigned long long *)t.d_fa_block;
+    R->line_dst = t.d_line_dst;
+    R->fa_seq = t.d_fa_seq;
+    R->off2 = (unsigned long long *)t.d_off2;
+    R->status = t.d_status + (size_t)t.bank * GS_TS_WORDS;
+    R->gate = R->status + GS_TS_SKIP;
+    R->keep_first = t.last_ml ? 1 : 0;
+    R->rec_line = t.d_rt_line;
+    R->rec_out = (unsigned long long *)t.d_rt_out;
+    R->rec_block = (unsigned long long *)t.d_rt_block;
+    R->piece_rec = t.d_rt_piece;
+    R->totals = (unsigned long long *)t.d_rt_tot;
+}
+
+// the descriptor line of every record of the latest chunk in t.d_rt_line (once per chunk)
+static int records_heads(TextScan &t, hipStream_t stream) {
+    if (t.rt_heads_ticket == t.tickets) return GS_OK;
+    int rc = grow(&t.d_rt_line, &t.rt_line_cap, (size_t)t.last_reads + 1, stream);
+    if (rc) return rc;
+    GsRewriteParams R{};
+    records_params(t, &R);
+    HIP_TRY(gs_launch_rewrite_heads(&R, stream));
+    t.rt_heads_ticket = t.tickets;
+    return GS_OK;
+}
+
+// the records of the last chunk, a FASTA or general FASTQ one, whose flag says so -- ((flags[r] & mask) != 0) == (want != 0) -- as
+// ReadEntry.write writes them, into t.d_rt_text[which][slot] (which: the filter's two files, which are written side by side);
+// synchronises.  timer (may be nullptr): the launches run between its events
+static int text_records(TextScan &t, hipStream_t stream, int n_cu, int mask, int want, int which, int with_probs, int slot, KernelTimer *timer, bool profile,
+                        const uint8_t **d_out, int64_t *n_bytes, int64_t *n_records) {
+    if (!d_out || !n_bytes || !n_records) return fail(GS_E_INVALID, "NULL argument");
+    *d_out = nullptr;
+    *n_bytes = *n_records = 0;
+    if (slot < 0 || slot > 1) return fail(GS_E_INVALID, "slot must be 0 or 1");
+    int rc = records_state(t, stream);
+    if (rc) return rc;
+    const int64_t n = t.last_reads;
+    if (n == 0) return GS_OK;
+    if (!t.d_last_flags) return fail(GS_E_STATE, "the last chunk was submitted without per-read flags");
+    const bool quals = with_probs != 0 && t.last_ml;  // (a FASTA record has no qualities: '~' either way)
+    const size_t bound = reads_bound(t.last_bytes, n);
+    if ((rc = grow(&t.d_rt_line, &t.rt_line_cap, (size_t)n + 1, stream))) return rc;
+    if ((rc = grow(&t.d_rt_out, &t.rt_out_cap, (size_t)n + 1, stream))) return rc;
+    if ((rc = grow(&t.d_rt_block, &t.rt_block_cap, (size_t)n / 256 + 2, stream))) return rc;
+    if ((rc = grow(&t.d_rt_piece, &t.rt_piece_cap, bound / 4096 + 2, stream))) return rc;
+    if ((rc = grow(&t.d_rt_text[which][slot], &t.rt_text_cap[which][slot], bound, stream))) return rc;
+    if (!t.d_rt_tot) HIP_TRY(gs_dev_alloc((void **)&t.d_rt_tot, sizeof(u64) * 4));
+    if (!t.h_rt_tot) HIP_TRY(hipHostMalloc((void **)&t.h_rt_tot, sizeof(u64) * 4));
+    const bool gather = quals && t.rt_quals_ticket != t.tickets;
+    if (gather) {
+        const size_t nl1 = (size_t)t.last_lines + 1;
+        if ((rc = grow(&t.d_rt_qscan, &t.rt_qscan_cap, nl1, stream))) return rc;
+        if ((rc = grow(&t.d_rt_qblock, &t.rt_qblock_cap, nl1 / 256 + 2, stream))) return rc;
+        if ((rc = grow(&t.d_rt_qdst, &t.rt_qdst_cap, nl1, stream))) return rc;
+        if ((rc = grow(&t.d_rt_qseq, &t.rt_qseq_cap, (size_t)t.last_bytes + 256, stream))) return rc;
+        if ((rc = grow(&t.d_rt_qoff, &t.rt_qoff_cap, (size_t)n + 1, stream))) return rc;
+    }
+    HIP_TRY(hipMemsetAsync(t.d_rt_tot, 0, sizeof(u64) * 4, stream));
+    GsRewriteParams R{};
+    records_params(t, &R);
+    if (timer && (rc = timer_start(*timer, profile, stream))) return rc;
+    if (gather) {  // the quality lines; the pass finds the descriptor lines too
+        GsRewriteParams Q = R;
+        Q.goal_mode = 2;
+        Q.fa_scan = (unsigned long long *)t.d_rt_qscan;
+        Q.fa_block = (unsigned long long *)t.d_rt_qblock;
+        Q.line_dst = t.d_rt_qdst;
+        Q.fa_seq = t.d_rt_qseq;
+        Q.off2 = (unsigned long long *)t.d_rt_qoff;
+        HIP_TRY(gs_launch_rewrite_lines(&Q, stream));
+        t.rt_quals_ticket = t.rt_heads_ticket = t.tickets;
+    } else if ((rc = records_heads(t, stream)))
+        return rc;
+    if (quals) {
+        R.q_seq = t.d_rt_qseq;
+        R.q_off = (const unsigned long long *)t.d_rt_qoff;
+    }
+    R.flags = t.d_last_flags;
+    R.flag_mask = (uint32_t)mask;
+    R.flag_want = want != 0;
+    R.out = t.d_rt_text[which][slot];
+    HIP_TRY(gs_launch_rewrite_copy(&R, (int64_t)bound - 64, n_cu, stream));
+    if (timer && (rc = timer_stop(*timer, profile, stream))) return rc;
+    if ((rc = text_touched(t, stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(t.h_rt_tot, t.d_rt_tot, sizeof(u64) * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    *n_bytes = (int64_t)t.h_rt_tot[0];
+    *n_records = (int64_t)t.h_rt_tot[1];
+    *d_out = *n_bytes > 0 ? t.d_rt_text[which][slot] : nullptr;
     return GS_OK;
 }
 
@@ -3113,6 +3256,14 @@ extern "C" int gs_match_compact_text(gs_run *run, int with_probs, int slot, cons
     HIP_TRY(hipSetDevice(run->db->device));
     return text_compact(run->text, run->stream, GS_F_RETURNED, 1, 1, slot, with_probs, d_out, n_bytes, n_records);
 }
+
+// the same for the records of a FASTA or general FASTQ chunk (gs_rewrite.hip)
+extern "C" int gs_match_compact_records(gs_run *run, int with_probs, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_records) try {
+    if (!run) return fail(GS_E_INVALID, "run is NULL");
+    HIP_TRY(hipSetDevice(run->db->device));
+    return text_records(run->text, run->stream, run->db->n_cu, GS_F_RETURNED, 1, 1, with_probs, slot, nullptr, false, d_out, n_bytes, n_records);
+}
+GS_API_CATCH
 
 // the descriptor lines (whole first lines, '@' included) of a few records of the last four-line chunk: out[i * stride ..], NUL-terminated
 extern "C" int gs_match_text_descriptors(gs_run *run, const int64_t *records, int32_t n, uint8_t *out, int32_t stride) {
@@ -5129,14 +5280,16 @@ extern "C" int gs_match_set_taxids(gs_run *run, const char *const *taxids) try {
 }
 GS_API_CATCH
 
-extern "C" int gs_match_kraken_text(gs_run *run, int write_all, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_lines) try {
+// records: the last chunk must be FASTA or general FASTQ (gs_match_kraken_records), else four-line FASTQ (gs_match_kraken_text)
+static int kraken_lines(gs_run *run, bool records, int write_all, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_lines) {
     if (!run || !d_out || !n_bytes || !n_lines) return fail(GS_E_INVALID, "NULL argument");
     *d_out = nullptr;
     *n_bytes = *n_lines = 0;
     if (slot < 0 || slot > 1) return fail(GS_E_INVALID, "slot must be 0 or 1");
     TextScan &t = run->text;
     if (t.tickets == 0) return fail(GS_E_STATE, "no text chunk has been submitted");
-    if (!t.last_four_line) return fail(GS_E_STATE, "the last chunk was not four-line FASTQ");
+    if (!records && !t.last_four_line) return fail(GS_E_STATE, "the last chunk was not four-line FASTQ");
+    if (records && t.last_four_line) return fail(GS_E_STATE, "the last chunk was four-line FASTQ");
     if (!run->d_tax_off) return fail(GS_E_STATE, "no taxid strings are set (gs_match_set_taxids)");
     const int64_t n = t.last_reads;
     if (n > 0 && !t.d_last_class) return fail(GS_E_STATE, "the last chunk was submitted without a class array");
@@ -5149,8 +5302,9 @@ extern "C" int gs_match_kraken_text(gs_run *run, int write_all, int slot, const 
     if (n == 0) return GS_OK;
     run->kr_seg_off.resize((size_t)n + 1);
     run->kr_seg_off[0] = 0;
-    int rc = segments_core(run, t.d_text, (const uint64_t *)t.d_off2, n, 2, run->kr_seg_off.data());
+    int rc = segments_core(run, records ? t.d_fa_seq : t.d_text, (const uint64_t *)t.d_off2, n, records ? 1 : 2, run->kr_seg_off.data());
     if (rc) return rc;
+    if (records && (rc = records_heads(t, run->stream))) return rc;
     const size_t n_blocks = ((size_t)n + 255) / 256;
     if ((rc = grow(&run->d_kr_name, &run->kr_name_cap, (size_t)n, run->stream))) return rc;
     if ((rc = grow(&run->d_kr_rec, &run->kr_rec_cap, (size_t)n + 1, run->stream))) return rc;
@@ -5160,6 +5314,10 @@ extern "C" int gs_match_kraken_text(gs_run *run, int write_all, int slot, const 
     GsKrakenParams P{};
     P.text = t.d_text;
     P.nl = t.d_nl;
+    if (records) {
+        P.rec_line = t.d_rt_line;
+        P.off2 = (const unsigned long long *)t.d_off2;
+    }
     P.n_reads = n;
     P.k = run->db->info.k;
     P.write_all = write_all != 0;
@@ -5198,6 +5356,15 @@ extern "C" int gs_match_kraken_text(gs_run *run, int write_all, int slot, const 
     *n_bytes = (int64_t)total;
     *n_lines = (int64_t)run->h_kr_totals[1];
     return GS_OK;
+}
+
+extern "C" int gs_match_kraken_text(gs_run *run, int write_all, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_lines) try {
+    return kraken_lines(run, false, write_all, slot, d_out, n_bytes, n_lines);
+}
+GS_API_CATCH
+
+extern "C" int gs_match_kraken_records(gs_run *run, int write_all, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_lines) try {
+    return kraken_lines(run, true, write_all, slot, d_out, n_bytes, n_lines);
 }
 GS_API_CATCH
 
@@ -5544,7 +5711,7 @@ static int filter_submit_text(gs_bloom *b, int k, int min_pos_count, double posi
     rc = filter_launch(b, k, min_pos_count, positive_ratio, tb.d_seq, (const uint64_t *)b->text.d_off2, tb.n_reads, d_acc, tb.off_stride, tb.d_skip, profile);
     if (rc) return rc;
     if ((rc = text_touched(b->text, b->stream))) return rc;
-    if (!tb.fasta) b->text.d_last_flags = d_acc;
+    b->text.d_last_flags = d_acc;
     if (!tb.dev_out && (rc = stage_download(h, nullptr, accept, tb.n_reads, b->stream))) return rc;
     if (newlines)
         HIP_TRY(hipMemcpyAsync(newlines, b->text.d_nl, sizeof(uint32_t) * (size_t)n_lines, tb.dev_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, b->stream));
@@ -5582,6 +5749,14 @@ extern "C" int gs_filter_compact_text(gs_bloom *b, int which, int with_probs, in
     HIP_TRY(hipSetDevice(b->device));
     return text_compact(b->text, b->stream, 0xff, which != 0, which != 0, slot, with_probs, d_out, n_bytes, n_records);
 }
+
+// the same for the records of a FASTA or general FASTQ chunk (gs_rewrite.hip)
+extern "C" int gs_filter_compact_records(gs_bloom *b, int which, int with_probs, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_records) try {
+    if (!b) return fail(GS_E_INVALID, "bloom is NULL");
+    HIP_TRY(hipSetDevice(b->device));
+    return text_records(b->text, b->stream, b->n_cu, 0xff, which != 0, which != 0, with_probs, slot, nullptr, false, d_out, n_bytes, n_records);
+}
+GS_API_CATCH
 
 extern "C" int gs_filter_text_read_bounds(gs_bloom *b, uint64_t *bounds) {
     if (!b || !bounds) return fail(GS_E_INVALID, "NULL argument");
@@ -5733,9 +5908,6 @@ static int reads_room(gs_reads *h, int64_t n_records, int slot, size_t bound) {
     return grow(&h->d_out[slot], &h->out_cap[slot], bound, h->stream);
 }
 
-// the text of a chunk's records is at most twice the chunk and five bytes per record; a multiple of 16 with room behind the text
-static size_t reads_bound(int64_t n_bytes, int64_t n_records) { return ((2 * (size_t)n_bytes + 5 * (size_t)n_records + 15) & ~(size_t)15) + 64; }
-
 static int reads_select(gs_reads *h, int k, const uint8_t *text, int64_t n_bytes, int64_t n_lines, int mem, const uint8_t *key, int32_t key_len,
                         uint8_t *accept, uint32_t *newlines, int64_t *ticket, int64_t fasta_records, int64_t *ml_out) {
     if (!h) return fail(GS_E_INVALID, "reads is NULL");
@@ -5774,10 +5946,8 @@ static int reads_select(gs_reads *h, int k, const uint8_t *text, int64_t n_bytes
     HIP_TRY(gs_launch_select(t.d_text, t.d_nl, tb.fasta ? h->d_rec_line : nullptr, tb.n_reads, h->d_key, key_len, tb.d_skip, d_acc, h->stream));
     if ((rc = timer_stop(h->select_timer, h->profile, h->stream))) return rc;
     if ((rc = text_touched(t, h->stream))) return rc;
-    if (!tb.fasta)
-        t.d_last_flags = d_acc;
-    else if (!ml_out)
-        h->d_last_accept = d_acc;
+    t.d_last_flags = d_acc;
+    if (tb.fasta && !ml_out) h->d_last_accept = d_acc;
     if (!tb.dev_out) HIP_TRY(hipMemcpyAsync(accept, d_acc, (size_t)tb.n_reads, hipMemcpyDeviceToHost, h->stream));
     if (newlines)
         HIP_TRY(hipMemcpyAsync(newlines, t.d_nl, sizeof(uint32_t) * (size_t)t.last_lines, tb.dev_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
@@ -5851,8 +6021,18 @@ extern "C" int gs_reads_compact_text(gs_reads *h, int with_probs, int slot, cons
     HIP_TRY(hipMemsetAsync(h->d_tot, 0, sizeof(u64) * 4, h->stream));
     GsRewriteParams R{};
     reads_params(h, &R);
-    R.accept = h->d_last_accept;
+    R.flags = h->d_last_accept;
+    R.flag_mask = 0xff;
+    R.flag_want = 1;
     return reads_rewrite(h, &R, slot, bound, d_out, n_bytes, n_records, nullptr);
+}
+GS_API_CATCH
+
+// the same for the selected records of a FASTA or general FASTQ chunk, the latter with its quality lines where with_probs asks for them
+extern "C" int gs_reads_compact_records(gs_reads *h, int with_probs, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_records) try {
+    if (!h) return fail(GS_E_INVALID, "reads is NULL");
+    HIP_TRY(hipSetDevice(h->device));
+    return text_records(h->text, h->stream, h->n_cu, 0xff, 1, 1, with_probs, slot, &h->timer, h->profile, d_out, n_bytes, n_records);
 }
 GS_API_CATCH
 

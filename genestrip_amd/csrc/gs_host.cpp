@@ -355,6 +355,13 @@ inline bool device_kraken() {
     return true;
 }
 
+// GS_DEVICE_RECORDS=0: the per-read outputs of FASTA and general FASTQ chunks are formatted on host threads (four-line chunks stay
+// as GS_DEVICE_OUTPUT / GS_DEVICE_KRAKEN say)
+inline bool device_records() {
+    if (const char *e = getenv("GS_DEVICE_RECORDS")) return atoi(e) != 0;
+    return true;
+}
+
 // The device side of one output file of the filter / match goal: the records the file wants have been gathered on the device
 // (gs_filter_compact_text / gs_match_compact_text); emit() compresses them there when the file is gzip (gs_deflater_pack: BGZF
 // members, what OutFile::pack makes with zlib on host threads) or fetches them as they are, into one of two page-locked buffers,
@@ -681,6 +688,7 @@ int parsed_source(MatchCtx &c, const std::string &path, int64_t offset, const ui
 std::atomic<int64_t> g_ml_chunks{0};  // chunks matched through the general FASTQ device path (gs_host_stat(0))
 std::atomic<int64_t> g_filter_general_chunks{0};  // FASTA / general FASTQ chunks filtered on the device (gs_host_stat(1))
 std::atomic<int64_t> g_kraken_device_chunks{0};  // chunks whose Kraken-style lines were written on the device (gs_host_stat(2))
+std::atomic<int64_t> g_record_device_chunks{0};  // FASTA / general FASTQ chunks whose per-read output was written on the device (gs_host_stat(3))
 
 struct TextChunk {
     int64_t file_off;  // of the chunk's first byte
@@ -1158,19 +1166,25 @@ struct TextJob {
     int dev_err_ = GS_OK;
     // after the chunk's flags are in (check_refusal has synchronised): gather and write the lines now, compress / fetch / write on a
     // thread of its own
-    int emit_device() {
+    // records: the chunk is FASTA or general FASTQ (gs_match_compact_records / gs_match_kraken_records)
+    int emit_device(bool records = false) {
         const int set = (int)(n_formatted & 1);
         const uint8_t *d = nullptr, *kd = nullptr;
         int64_t nb = 0, nr = 0, knb = 0, knl = 0;
         int err = GS_OK;
-        if (c.filtered.active()) err = gs_match_compact_text(c.run, c.opts->with_probs != 0, set, &d, &nb, &nr);
+        if (c.filtered.active())
+            err = records ? gs_match_compact_records(c.run, c.opts->with_probs != 0, set, &d, &nb, &nr)
+                          : gs_match_compact_text(c.run, c.opts->with_probs != 0, set, &d, &nb, &nr);
         if (!err && c.kraken.active()) {
             if (!c.taxids_on_device) err = gs_match_set_taxids(c.run, c.opts->taxids);
             c.taxids_on_device = !err;
-            if (!err) err = gs_match_kraken_text(c.run, c.opts->write_all != 0, set, &kd, &knb, &knl);
-            if (!err) g_kraken_device_chunks.fetch_add(1);
+            if (!err)
+                err = records ? gs_match_kraken_records(c.run, c.opts->write_all != 0, set, &kd, &knb, &knl)
+                              : gs_match_kraken_text(c.run, c.opts->write_all != 0, set, &kd, &knb, &knl);
+            if (!err && !records) g_kraken_device_chunks.fetch_add(1);
         }
         if (err) return err;
+        if (records) g_record_device_chunks.fetch_add(1);
         c.filtered_reads += nr;
         drain();  // one chunk at a time: output order
         if (dev_err_) return dev_err_;
@@ -1493,7 +1507,9 @@ struct TextJob {
     // device and a class per line (1 descriptor, 2 sequence, 0 '+' / quality) -- from the device for general FASTQ, by the
     // first byte for FASTA.  Kraken-style lines (MatcherReadEntry.writeMatchDetails, :723-756): descriptor up to the first blank
     // without its first character, class, length, runs.  Filtered FASTQ: append_general_record.
+    // On the device under the condition of the four-line chunks (device_filtered / device_lines; GS_DEVICE_RECORDS=0: here).
     int outputs_general(MatchCtx::Results &rs, const uint8_t *text, int64_t n_lines, int64_t n_records, bool is_fasta) {
+        if (device_records() && device_per_read() && (device_lines() || c.filtered.gzip())) return emit_device(true);
         std::vector<uint64_t> bounds((size_t)n_records + 1);
         std::vector<uint8_t> cls((size_t)std::max<int64_t>(n_lines, 1));
         int err = gs_match_text_read_bounds(c.run, bounds.data());  // (waits for the chunk: cls / flags are complete)
@@ -1537,6 +1553,7 @@ struct TextJob {
             }
             p.pack(cc.kraken, cc.filtered);
         });
+        drain();  // (a chunk whose device text is still on its way out comes first)
         write_parts(c, parts);
         return GS_OK;
     }
@@ -2004,7 +2021,12 @@ struct FilterCtx {
             return gs_reads_select_fastq_ml(rd, k, text, n_bytes, n_lines, mem, key_bytes(), (int32_t)key.size(), acc, nl, n_records, used, lines, ticket);
         return gs_filter_submit_fastq_ml(bloom, k, min_pos_count, positive_ratio, text, n_bytes, n_lines, mem, acc, nl, n_records, used, lines, ticket);
     }
-    int compact_text(int which, int probs, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_records) {
+    // records: the last chunk was FASTA or general FASTQ
+    int compact_text(int which, int probs, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_records, bool records = false) {
+        if (records) {
+            if (extract()) return gs_reads_compact_records(rd, probs, slot, d_out, n_bytes, n_records);
+            return gs_filter_compact_records(bloom, which, probs, slot, d_out, n_bytes, n_records);
+        }
         if (extract()) return gs_reads_compact_text(rd, probs, slot, d_out, n_bytes, n_records);  // (no rest file: which == 1)
         return gs_filter_compact_text(bloom, which, probs, slot, d_out, n_bytes, n_records);
     }
@@ -2114,14 +2136,15 @@ void format_text_chunk(FilterCtx &c, const uint8_t *start, const uint8_t *h_acc,
 // on the device -- the records each file wants are gathered there (gs_filter_compact_text), a .gz file's are compressed there
 // (DeviceWriter::emit -> gs_deflater_pack), and only what the files will hold crosses PCIe, on a thread of its own (dev_job) while
 // the next chunk is read or inflated and filtered.  The chunk's text is on the device already: its block may go back at once.
-int filter_emit_device(FilterCtx &c, int set, int64_t n_reads, const uint8_t *h_acc, std::future<int> &dev_job) {
+// records: a FASTA or general FASTQ chunk (gs_filter_compact_records / gs_reads_compact_records), the same way out.
+int filter_emit_device(FilterCtx &c, int set, int64_t n_reads, const uint8_t *h_acc, std::future<int> &dev_job, bool records = false) {
     static const bool trace = getenv("GS_HOST_TRACE") != nullptr;
     const double t0 = now_s();
     const uint8_t *d_a = nullptr, *d_r = nullptr;
     int64_t nb_a = 0, nr_a = 0, nb_r = 0, nr_r = 0;
     int err = GS_OK;
-    if (c.acc_out.active()) err = c.compact_text(1, c.with_probs ? 1 : 0, set, &d_a, &nb_a, &nr_a);
-    if (!err && c.rest_out.active()) err = c.compact_text(0, c.with_probs ? 1 : 0, set, &d_r, &nb_r, &nr_r);
+    if (c.acc_out.active()) err = c.compact_text(1, c.with_probs ? 1 : 0, set, &d_a, &nb_a, &nr_a, records);
+    if (!err && c.rest_out.active()) err = c.compact_text(0, c.with_probs ? 1 : 0, set, &d_r, &nb_r, &nr_r, records);
     if (err) return err;
     if (c.acc_out.active())
         c.accepted += nr_a;
@@ -2377,6 +2400,14 @@ int filter_general_file(FilterCtx &c, const std::string &path, bool gzip, bool f
         std::vector<int64_t> head;
     } res[2];
     std::future<void> formatting;
+    // device output under the condition of the four-line chunks of filter_text_file (GS_DEVICE_RECORDS=0: the host's formatter): the
+    // records each file wants are written on the device, the chunk's block goes straight back to its reader
+    std::future<int> dev_job;
+    int device = 0;
+    const bool dev_out = device_records() && device_output() &&
+                         ((c.acc_out.active() && c.acc_out.gzip()) || (c.rest_out.active() && c.rest_out.gzip())) && c.get_device(&device) == GS_OK;
+    c.acc_dev.begin(&c.acc_out, device);
+    c.rest_dev.begin(&c.rest_out, device);
     int64_t n_chunks = 0, fallback_off = -1;
     ChunkCutter cut;
     cut.mode = fasta ? ChunkCutter::FASTA : ChunkCutter::GENERAL;
@@ -2410,7 +2441,7 @@ int filter_general_file(FilterCtx &c, const std::string &path, bool gzip, bool f
                 else  // (the device says what its records cover: `used` bytes, `lines` lines)
                     err = c.submit_fastq_ml(start, bytes, cut.lines, GS_MEM_HOST, acc.data(), nls.data(), &records, &used, &lines, &ticket);
                 if (!err) err = c.text_status(&failed, &bad, tot);  // synchronises: results are needed now
-                if (!err && failed < 0 && records > 0) {
+                if (!err && failed < 0 && records > 0 && !dev_out) {
                     bounds.resize((size_t)records + 1);
                     cls.resize((size_t)lines);
                     err = c.read_bounds(bounds.data());
@@ -2420,6 +2451,11 @@ int filter_general_file(FilterCtx &c, const std::string &path, bool gzip, bool f
                 if (err) break;
                 if (failed >= 0 || records < 0) {  // refused: the general parser continues at this chunk
                     fallback_off = cut.file_off;
+                } else if (records > 0 && dev_out) {
+                    g_filter_general_chunks.fetch_add(1);
+                    if ((err = filter_emit_device(c, (int)(n_chunks & 1), records, acc.data(), dev_job, true))) break;
+                    g_record_device_chunks.fetch_add(1);
+                    n_chunks++;
                 } else if (records > 0) {
                     g_filter_general_chunks.fetch_add(1);
                     const uint32_t *nl = nls.p;
@@ -2475,6 +2511,10 @@ int filter_general_file(FilterCtx &c, const std::string &path, bool gzip, bool f
         if (eof || fallback_off >= 0) break;
     }
     if (formatting.valid()) formatting.get();
+    if (dev_job.valid()) {
+        const int e2 = dev_job.get();
+        if (!err) err = e2;
+    }
     tr.close();
     c.t_parse += now_s() - t0;
     if (err) return err;
@@ -2601,6 +2641,7 @@ extern "C" int64_t gs_host_stat(int which) {
         case 0: return g_ml_chunks.load();
         case 1: return g_filter_general_chunks.load();
         case 2: return g_kraken_device_chunks.load();
+        case 3: return g_record_device_chunks.load();
         default: return -1;
     }
 }

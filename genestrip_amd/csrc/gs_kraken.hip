@@ -1,8 +1,10 @@
-// gs_kraken.hip -- the Kraken-style lines of a four-line FASTQ chunk as device text (FastqKMerMatcher.java:308-314, :597-611,
+// gs_kraken.hip -- the Kraken-style lines of a FASTQ or FASTA chunk as device text (FastqKMerMatcher.java:308-314, :597-611,
 // MatcherReadEntry.writeMatchDetails :723-756; what kraken_line of gs_host.cpp prints on the host), behind the segments kernel.
 //
 // Per read r of the chunk (nl = newline offsets): descriptor = text[d0, d1) with d0 = r ? nl[4r-1] + 1 : 0 and d1 = nl[4r],
-// L = nl[4r+1] - d1 - 1 (a '\r' counts), max = L - k + 1.  No line when the read has no segment or !(write_all || class >= 0), else
+// L = nl[4r+1] - d1 - 1 (a '\r' counts), max = L - k + 1.  A FASTA or general FASTQ chunk (P.rec_line != nullptr, the kernels'
+// REC instantiation): the descriptor is line rec_line[r], L = off2[r+1] - off2[r], the gathered read.  No line when the read has
+// no segment or !(write_all || class >= 0), else
 //   'C' | 'U'  TAB  name  TAB  taxid(class) | '0'  TAB  L  TAB  seg ' ' seg ...  '\n'
 // name = the descriptor behind its first byte up to the first blank, seg = taxid(code) | '0' (-1) | 'A' (-2)  ':'  count, count = the
 // next segment's start - this one's, for the last one max - start.
@@ -42,12 +44,20 @@ struct KrRead {
     int64_t maxp;
     u64 s0, s1;            // its segments
 };
+template <bool REC>
 __device__ __forceinline__ KrRead kr_read(const GsKrakenParams &P, int64_t r) {
     KrRead g;
-    g.d0 = r ? P.nl[4 * r - 1] + 1u : 0u;
-    const uint32_t d1 = P.nl[4 * r];
-    g.dlen = d1 - g.d0;
-    g.L = P.nl[4 * r + 1] - d1 - 1u;
+    if (REC) {
+        const int64_t i = P.rec_line[r];
+        g.d0 = i ? P.nl[i - 1] + 1u : 0u;
+        g.dlen = P.nl[i] - g.d0;
+        g.L = (uint32_t)(P.off2[r + 1] - P.off2[r]);
+    } else {
+        g.d0 = r ? P.nl[4 * r - 1] + 1u : 0u;
+        const uint32_t d1 = P.nl[4 * r];
+        g.dlen = d1 - g.d0;
+        g.L = P.nl[4 * r + 1] - d1 - 1u;
+    }
     g.maxp = (int64_t)g.L - P.k + 1;
     g.cl = P.cls[r];
     g.s0 = P.seg_off[r];
@@ -141,6 +151,7 @@ __device__ __forceinline__ void kr_put_line(const S &s, typename S::Pos pos, con
     s.put(pos, '\n');
 }
 
+template <bool REC>
 __global__ __launch_bounds__(KR_BLOCK) void kr_size_kernel(GsKrakenParams P) {
     __shared__ u64 s_wave[KR_BLOCK / 64];
     const int lane = threadIdx.x & 63;
@@ -149,7 +160,7 @@ __global__ __launch_bounds__(KR_BLOCK) void kr_size_kernel(GsKrakenParams P) {
     uint32_t name_len = 0;
     bool by_wave = false;
     if (r < P.n_reads) {
-        const KrRead g = kr_read(P, r);
+        const KrRead g = kr_read<REC>(P, r);
         if (kr_wanted(P, g)) {
             sz = kr_frame_len(P, g);
             by_wave = g.s1 - g.s0 > KR_WAVE_SEGS || g.dlen > KR_WAVE_DESC;
@@ -165,7 +176,7 @@ __global__ __launch_bounds__(KR_BLOCK) void kr_size_kernel(GsKrakenParams P) {
     }
     for (u64 todo = __ballot(by_wave); todo; todo &= todo - 1) {  // the whole wave on one read after the other
         const int src = __ffsll((long long)todo) - 1;
-        const KrRead g = kr_read(P, r - lane + src);
+        const KrRead g = kr_read<REC>(P, r - lane + src);
         uint32_t nm = g.dlen > 1 ? g.dlen - 1 : 0;
         for (uint32_t base = 1; base < g.dlen; base += 64) {
             const uint32_t j = base + (uint32_t)lane;
@@ -224,8 +235,9 @@ __device__ __forceinline__ void kr_range(const GsKrakenParams &P, uint8_t *s_til
 }
 
 // one long line by the whole block, straight to the output
+template <bool REC>
 __device__ __forceinline__ void kr_big_line(const GsKrakenParams &P, u64 *s_wave, int64_t r) {
-    const KrRead g = kr_read(P, r);
+    const KrRead g = kr_read<REC>(P, r);
     const uint32_t name_len = P.name_len[r];
     const u64 at = P.rec_out[r], end = P.rec_out[r + 1];
     const KrOut s{P.out};
@@ -251,6 +263,7 @@ __device__ __forceinline__ void kr_big_line(const GsKrakenParams &P, u64 *s_wave
     }
 }
 
+template <bool REC>
 __global__ __launch_bounds__(KR_BLOCK) void kr_write_kernel(GsKrakenParams P) {
     __shared__ __attribute__((aligned(16))) uint8_t s_tile[KR_TILE];
     __shared__ u64 s_wave[KR_BLOCK / 64];
@@ -265,7 +278,7 @@ __global__ __launch_bounds__(KR_BLOCK) void kr_write_kernel(GsKrakenParams P) {
         at = P.rec_out[r];
         sz = P.rec_out[r + 1] - at;
         if (sz != 0) {
-            g = kr_read(P, r);
+            g = kr_read<REC>(P, r);
             name_len = P.name_len[r];
         }
     }
@@ -279,7 +292,7 @@ __global__ __launch_bounds__(KR_BLOCK) void kr_write_kernel(GsKrakenParams P) {
             const int64_t rb = r0 + w * 64 + (__ffsll((long long)m) - 1);
             const u64 b0 = P.rec_out[rb], b1 = P.rec_out[rb + 1];
             kr_range(P, s_tile, cur, b0, small && at >= cur && at < b0, at, sz, g, name_len);
-            kr_big_line(P, s_wave, rb);
+            kr_big_line<REC>(P, s_wave, rb);
             cur = b1;
         }
     kr_range(P, s_tile, cur, last, small && at >= cur, at, sz, g, name_len);
@@ -290,7 +303,10 @@ __global__ __launch_bounds__(KR_BLOCK) void kr_write_kernel(GsKrakenParams P) {
 extern "C" hipError_t gs_launch_kraken_size(const GsKrakenParams *P, hipStream_t stream) {
     const int64_t n_blocks = (P->n_reads + KR_BLOCK - 1) / KR_BLOCK;
     if (n_blocks <= 0) return hipSuccess;
-    hipLaunchKernelGGL(kr_size_kernel, dim3((unsigned)n_blocks), dim3(KR_BLOCK), 0, stream, *P);
+    if (P->rec_line != nullptr)
+        hipLaunchKernelGGL(kr_size_kernel<true>, dim3((unsigned)n_blocks), dim3(KR_BLOCK), 0, stream, *P);
+    else
+        hipLaunchKernelGGL(kr_size_kernel<false>, dim3((unsigned)n_blocks), dim3(KR_BLOCK), 0, stream, *P);
     hipError_t e = gs_launch_scan_blocks(P->rec_block, n_blocks, P->totals, stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kr_offsets_kernel, dim3((unsigned)n_blocks), dim3(KR_BLOCK), 0, stream, *P);
@@ -301,6 +317,9 @@ extern "C" hipError_t gs_launch_kraken_size(const GsKrakenParams *P, hipStream_t
 extern "C" hipError_t gs_launch_kraken_write(const GsKrakenParams *P, hipStream_t stream) {
     const int64_t n_blocks = (P->n_reads + KR_BLOCK - 1) / KR_BLOCK;
     if (n_blocks <= 0) return hipSuccess;
-    hipLaunchKernelGGL(kr_write_kernel, dim3((unsigned)n_blocks), dim3(KR_BLOCK), 0, stream, *P);
+    if (P->rec_line != nullptr)
+        hipLaunchKernelGGL(kr_write_kernel<true>, dim3((unsigned)n_blocks), dim3(KR_BLOCK), 0, stream, *P);
+    else
+        hipLaunchKernelGGL(kr_write_kernel<false>, dim3((unsigned)n_blocks), dim3(KR_BLOCK), 0, stream, *P);
     return hipGetLastError();
 }

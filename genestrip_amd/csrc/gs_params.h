@@ -171,8 +171,12 @@ struct GsRewriteParams {
     unsigned long long *off2;
     uint32_t *status;                 // the bank's GS_TS_WORDS words
     const uint32_t *gate;             // the launch does nothing when *gate != 0: the chunk error word in front of the commit, the skip flag behind it
-    int32_t goal_mode, pad;
-    const uint8_t *accept;            // per record, nullptr: every record
+    int32_t goal_mode;                // 0: ReadEntry mode; 1: fasta2fastq; 2: the quality lines of a general FASTQ chunk (line_class set) -> fa_seq / off2
+    int32_t keep_first;               // the descriptor line keeps its first byte (general FASTQ); 0: it becomes '@' (FASTA)
+    const uint8_t *flags;             // per record, nullptr: every record; else a record is wanted iff ((flags[r] & flag_mask) != 0) == flag_want
+    uint32_t flag_mask, flag_want;
+    const uint8_t *q_seq;             // the quality characters of every record back to back, q_off[0 .. n_records] = their bounds
+    const unsigned long long *q_off;  // (the gather of a goal_mode 2 pass); nullptr: the tail is '~' x L
     uint32_t *rec_line;               // n_records + 1: the header line of every record, then n_lines
     unsigned long long *rec_out;      // n_records + 1: where the text of every record starts
     unsigned long long *rec_block;    // per block of 256 records
@@ -181,7 +185,7 @@ struct GsRewriteParams {
     uint8_t *out;
 };
 
-// Kraken-style lines of a four-line chunk as device text (gs_kraken.hip), behind the segments of the chunk's reads
+// Kraken-style lines of a chunk as device text (gs_kraken.hip), behind the segments of the chunk's reads
 struct GsKrakenParams {
     const uint8_t *text;              // the chunk and its newline offsets, as GsTextParams
     const uint32_t *nl;
@@ -198,6 +202,9 @@ struct GsKrakenParams {
     unsigned long long *rec_block;    // per block of 256 reads
     unsigned long long *totals;       // [0] bytes of text [1] lines
     uint8_t *out;
+    // (behind the fields of the four-line form, whose kernel arguments keep their places)
+    const uint32_t *rec_line;         // FASTA, general FASTQ: the descriptor line of every read; nullptr: four lines per read
+    const unsigned long long *off2;   // with rec_line: n_reads + 1 bounds of the gathered reads (their lengths)
 };
 
 struct GsFilterParams {

@@ -5,7 +5,8 @@
 // (ByteArrayUtil.startsWith, B/util/ByteArrayUtil.java:115-126): selected iff the line holds at least key_len bytes there and
 // they equal the key; a '\r' in front of the '\n' belongs to the line.
 //
-// FASTA -> FASTQ text: per wanted record '@' header[1:] '\n' sequence "\n+\n" '~' x L '\n', back to back in record order.
+// FASTA -> FASTQ text: per wanted record '@' header[1:] '\n' sequence "\n+\n" '~' x L '\n', back to back in record order; the
+// records of general FASTQ chunks the same way, with their own first byte and, where asked for, their quality lines as the tail.
 //   ReadEntry mode (AbstractFastqReader.java:375-438, :570-584): the FASTA record search of gs_text.hip has run -- the sequences
 //     lie gathered in fa_seq ('\r' kept), off2 holds their bounds, fa_scan / fa_block the prefix over the lines; only the header
 //     line of every record is looked up here (rw_emit_kernel), and only records with accept != 0 are written.
@@ -14,16 +15,22 @@
 //     refuses empty lines and keeps '\r'): kept length per line by a backward look, the same two-level prefix over the lines, the
 //     kept bytes gathered into fa_seq.  A line of 65 534 bytes or more (newline included) is counted, not refused: the reference
 //     throws there (AbstractFastaReader.java:104-106), which is the host's to report.
-// Then, for both modes: the size of every record's text, len(header) + 2 L + 5, an exclusive prefix over the records (64-bit: a
-// chunk's output is about twice its input) and the copy.  Records range from 30 bytes to a chromosome, so the copy is cut by
+//   Quality mode (goal_mode 2, general FASTQ with qualities, ReadEntry.write with withProbs): the same per-line pass under the
+//     line classes of the record search.  A line of class 0 behind a sequence line is the record's '+' line, every further line
+//     of class 0 a quality line, kept whole ('\r' included); they are gathered into a buffer of their own (the caller passes it
+//     as fa_seq / off2 of this pass and as q_seq / q_off of the copy), so the tail of a record is one run of bytes as its read is.
+// General FASTQ records keep the first byte of their descriptor line (keep_first), FASTA records get '@' there.
+// Then, for all modes: the size of every record's text, len(header) + L + Q + 5 (Q = L without qualities), an exclusive prefix
+// over the records (64-bit: a chunk's output is about twice its input) and the copy.  Records range from 30 bytes to a chromosome, so the copy is cut by
 // OUTPUT bytes: a thread owns 16 aligned output bytes, a block 4096; the record of every piece's first byte is found by binary
 // search over the offsets (rw_pieces_kernel, all pieces at once), a thread finds its own record between its piece's and the
-// next one's.  16 bytes inside one sequence or one '~' run -- nearly all of them -- are one 16-byte load and one 16-byte store.
+// next one's.  16 bytes inside one sequence, one '~' run or one quality run -- nearly all of them -- are one 16-byte load and one
+// 16-byte store.  Which records are wanted: a per-record byte under a mask and a wanted value, as the four-line gather takes them.
 //
-//   rw_lines_kernel    goal mode, per line: header? kept length; exclusive scan inside blocks of GS_FA_BLOCK lines
+//   rw_lines_kernel    goal and quality mode, per line: header? kept length; exclusive scan inside blocks of GS_FA_BLOCK lines
 //   rw_scan_kernel     one block: exclusive prefix over per-block totals (lines, then records), optional header count check
 //   rw_emit_kernel     per line: header line of every record (both modes); goal mode: off2, destination of the kept bytes
-//   rw_gather_kernel   goal mode, one wave per data line: kept bytes -> fa_seq
+//   rw_gather_kernel   goal and quality mode, one wave per data line: kept bytes -> fa_seq
 //   rw_size_kernel     per record: size of its text (0: not wanted), exclusive scan inside blocks of 256 records, records wanted
 //   rw_offsets_kernel  per record: + its block's prefix
 //   rw_pieces_kernel   per piece of 4096 output bytes: the record of its first byte
@@ -54,6 +61,16 @@ __device__ __forceinline__ uint32_t rw_kept(const uint8_t *text, uint32_t start,
     return len;
 }
 
+// the per-line pass's view of line i: a header line?  Else the bytes of it that are gathered (goal mode: without trailing '\r's;
+// quality mode: a quality line whole, nothing of sequence and '+' lines)
+__device__ __forceinline__ bool rw_is_header(const GsRewriteParams &P, int64_t i, uint32_t start, uint32_t len) {
+    return P.line_class != nullptr ? P.line_class[i] == 1 : (len > 0 && P.text[start] == '>');
+}
+__device__ __forceinline__ uint32_t rw_data_len(const GsRewriteParams &P, int64_t i, uint32_t start, uint32_t len) {
+    if (P.goal_mode == 2) return i > 0 && P.line_class[i] == 0 && P.line_class[i - 1] == 0 ? len : 0u;
+    return rw_kept(P.text, start, len);
+}
+
 __global__ __launch_bounds__(RW_BLOCK) void rw_lines_kernel(GsRewriteParams P) {
     __shared__ u64 s_wave[RW_BLOCK / 64];
     const int64_t i = (int64_t)blockIdx.x * RW_BLOCK + threadIdx.x;
@@ -61,13 +78,13 @@ __global__ __launch_bounds__(RW_BLOCK) void rw_lines_kernel(GsRewriteParams P) {
     u64 v = 0;
     if (live) {
         const uint32_t start = rw_line_start(P, i), len = P.nl[i] - start;
-        const bool hdr = len > 0 && P.text[start] == '>';
-        if (i == 0 && !hdr) {  // text in front of the first header: printed raw by the goal, the host path's case
+        const bool hdr = rw_is_header(P, i, start, len);
+        if (P.goal_mode == 1 && i == 0 && !hdr) {  // text in front of the first header: printed raw by the goal, the host path's case
             atomicOr(&P.status[GS_TS_CHUNK_ERR], GS_TE_SHAPE);
             atomicMin(&P.status[GS_TS_FIRST_BAD], 0u);
         }
-        if (len + 1u >= RW_LONG_LINE) atomicAdd(&P.totals[2], 1ULL);
-        v = hdr ? RW_HDR : (u64)rw_kept(P.text, start, len);
+        if (P.goal_mode == 1 && len + 1u >= RW_LONG_LINE) atomicAdd(&P.totals[2], 1ULL);
+        v = hdr ? RW_HDR : (u64)rw_data_len(P, i, start, len);
     }
     u64 total;
     const u64 ex = gs_block_scan(v, s_wave, &total);
@@ -108,7 +125,7 @@ __global__ __launch_bounds__(RW_BLOCK) void rw_emit_kernel(GsRewriteParams P) {
     const int64_t i = (int64_t)blockIdx.x * RW_BLOCK + threadIdx.x;
     if (i >= P.n_lines || *P.gate != 0) return;
     const uint32_t start = rw_line_start(P, i), len = P.nl[i] - start;
-    const bool hdr = P.line_class != nullptr ? P.line_class[i] == 1 : (len > 0 && P.text[start] == '>');
+    const bool hdr = rw_is_header(P, i, start, len);
     const u64 pre = P.fa_scan[i] + P.fa_block[blockIdx.x];
     if (i == 0) P.rec_line[P.n_records] = (uint32_t)P.n_lines;
     if (hdr) P.rec_line[pre >> 40] = (uint32_t)i;  // (the header count was checked: pre >> 40 < n_records)
@@ -118,7 +135,7 @@ __global__ __launch_bounds__(RW_BLOCK) void rw_emit_kernel(GsRewriteParams P) {
         P.off2[pre >> 40] = pre & RW_LEN_MASK;
         P.line_dst[i] = 0xffffffffu;
     } else {
-        P.line_dst[i] = rw_kept(P.text, start, len) ? (uint32_t)(pre & RW_LEN_MASK) : 0xffffffffu;
+        P.line_dst[i] = rw_data_len(P, i, start, len) ? (uint32_t)(pre & RW_LEN_MASK) : 0xffffffffu;
     }
 }
 
@@ -129,7 +146,7 @@ __global__ __launch_bounds__(256) void rw_gather_kernel(GsRewriteParams P) {
     for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < P.n_lines; i += n_waves) {
         const uint32_t dst = P.line_dst[i];
         if (dst == 0xffffffffu) continue;
-        const uint32_t start = rw_line_start(P, i), kept = rw_kept(P.text, start, P.nl[i] - start);
+        const uint32_t start = rw_line_start(P, i), kept = rw_data_len(P, i, start, P.nl[i] - start);
         for (uint32_t j = (uint32_t)lane; j < kept; j += 64) P.fa_seq[(size_t)dst + j] = P.text[(size_t)start + j];
     }
 }
@@ -138,10 +155,10 @@ __global__ __launch_bounds__(RW_BLOCK) void rw_size_kernel(GsRewriteParams P) {
     __shared__ u64 s_wave[RW_BLOCK / 64];
     const int64_t r = (int64_t)blockIdx.x * RW_BLOCK + threadIdx.x;
     u64 sz = 0;
-    if (r < P.n_records && *P.gate == 0 && (P.accept == nullptr || P.accept[r] != 0)) {
+    if (r < P.n_records && *P.gate == 0 && (P.flags == nullptr || (uint32_t)((P.flags[r] & P.flag_mask) != 0u) == P.flag_want)) {
         const int64_t i = P.rec_line[r];
         const u64 hl = P.nl[i] - rw_line_start(P, i), L = P.off2[r + 1] - P.off2[r];
-        sz = hl + 2 * L + 5;
+        sz = hl + L + (P.q_off != nullptr ? P.q_off[r + 1] - P.q_off[r] : L) + 5;
     }
     const u64 wanted = __ballot(sz != 0);
     if ((threadIdx.x & 63) == 0 && wanted) atomicAdd(&P.totals[1], (u64)__popcll(wanted));
@@ -171,8 +188,8 @@ __device__ __forceinline__ int64_t rw_find(const u64 *off, int64_t lo, int64_t h
 }
 
 struct RwRec {
-    u64 base, size, hl, L;  // where its text starts, its bytes; header line without '\n', sequence length
-    size_t hsrc, ssrc;      // header line in text, sequence in fa_seq
+    u64 base, size, hl, L, Q;  // where its text starts, its bytes; header line without '\n', sequence length, bytes of its tail
+    size_t hsrc, ssrc, qsrc;   // header line in text, sequence in fa_seq, qualities in q_seq
 };
 __device__ __forceinline__ RwRec rw_record(const GsRewriteParams &P, int64_t r) {
     RwRec g;
@@ -183,15 +200,17 @@ __device__ __forceinline__ RwRec rw_record(const GsRewriteParams &P, int64_t r) 
     g.hl = P.nl[i] - g.hsrc;
     g.ssrc = P.off2[r];
     g.L = P.off2[r + 1] - g.ssrc;
+    g.qsrc = P.q_off != nullptr ? P.q_off[r] : 0;
+    g.Q = P.q_off != nullptr ? P.q_off[r + 1] - g.qsrc : g.L;
     return g;
 }
 __device__ __forceinline__ uint8_t rw_byte(const GsRewriteParams &P, const RwRec &g, u64 rel) {
-    if (rel == 0) return '@';
-    if (rel < g.hl) return P.text[g.hsrc + rel];
-    const u64 s = rel - g.hl;  // '\n' sequence '\n' '+' '\n' '~' x L '\n'
-    if (s == 0 || s == g.L + 1 || s == g.L + 3 || s == 2 * g.L + 4) return '\n';
+    if (rel < g.hl) return rel == 0 && !P.keep_first ? '@' : P.text[g.hsrc + rel];  // (an empty descriptor line: hl = 0)
+    const u64 s = rel - g.hl;  // '\n' sequence '\n' '+' '\n' tail (Q bytes) '\n'
+    if (s == 0 || s == g.L + 1 || s == g.L + 3 || s == g.L + g.Q + 4) return '\n';
     if (s <= g.L) return P.fa_seq[g.ssrc + s - 1];
-    return s == g.L + 2 ? '+' : '~';
+    if (s == g.L + 2) return '+';
+    return P.q_seq != nullptr ? P.q_seq[g.qsrc + s - (g.L + 4)] : '~';
 }
 
 // the record that holds the first byte of every piece of the text: one search over all records per piece, every piece at once
@@ -215,8 +234,11 @@ __global__ __launch_bounds__(RW_BLOCK) void rw_copy_kernel(GsRewriteParams P) {
         const u64 seq0 = g.hl + 1, til0 = g.hl + g.L + 4;
         if (rel >= seq0 && rel + 16 <= seq0 + g.L) {
             __builtin_memcpy(&v, P.fa_seq + g.ssrc + (rel - seq0), 16);
-        } else if (rel >= til0 && rel + 16 <= til0 + g.L) {
-            v.x = v.y = v.z = v.w = 0x7e7e7e7eu;
+        } else if (rel >= til0 && rel + 16 <= til0 + g.Q) {
+            if (P.q_seq != nullptr)
+                __builtin_memcpy(&v, P.q_seq + g.qsrc + (rel - til0), 16);
+            else
+                v.x = v.y = v.z = v.w = 0x7e7e7e7eu;
         } else {
             uint32_t w[4] = {0, 0, 0, 0};
 #pragma unroll
@@ -254,11 +276,14 @@ __global__ __launch_bounds__(RW_BLOCK) void rw_select_kernel(const uint8_t *text
 
 // goal mode, in front of the commit of the chunk (P.gate = the bank's chunk error word): lines, header count, header lines and
 // sequence bounds, kept bytes -> fa_seq.  The newline offsets are there (gs_launch_text_lines); totals[2] has been zeroed.
+// Quality mode, behind the commit of a general FASTQ chunk (P.gate = the bank's skip flag, n_lines = the lines its whole records
+// cover, n_records = their number, which the record search has made the number of class-1 lines): the same for the quality lines.
 extern "C" hipError_t gs_launch_rewrite_lines(const GsRewriteParams *P, hipStream_t stream) {
     const int64_t n_blocks = (P->n_lines + RW_BLOCK - 1) / RW_BLOCK;
     if (n_blocks <= 0) return hipSuccess;
     hipLaunchKernelGGL(rw_lines_kernel, dim3((unsigned)n_blocks), dim3(RW_BLOCK), 0, stream, *P);
-    hipLaunchKernelGGL(rw_scan_kernel, dim3(1), dim3(1024), 0, stream, P->fa_block, n_blocks, P->totals + 3, P->n_records, P->status);
+    hipLaunchKernelGGL(rw_scan_kernel, dim3(1), dim3(1024), 0, stream, P->fa_block, n_blocks, P->totals + 3, P->goal_mode == 1 ? P->n_records : (int64_t)-1,
+                       P->status);
     hipLaunchKernelGGL(rw_emit_kernel, dim3((unsigned)n_blocks), dim3(RW_BLOCK), 0, stream, *P);
     hipLaunchKernelGGL(rw_gather_kernel, dim3((unsigned)std::min<int64_t>((P->n_lines + 3) / 4, 8192)), dim3(256), 0, stream, *P);
     return hipGetLastError();

@@ -158,7 +158,8 @@ def match_files(store, paths, config=None, filtered_path=None, kraken_out_path=N
 
 def stat(which=0):
     """gs_host_stat: 0 = chunks that went through the general (multi-line) FASTQ device path in this process so far; 1 = FASTA / general
-    FASTQ chunks the filter goal handled on the device; 2 = chunks whose Kraken-style lines were written on the device"""
+    FASTQ chunks the filter goal handled on the device; 2 = four-line chunks whose Kraken-style lines were written on the device; 3 = FASTA /
+    general FASTQ chunks of any goal whose per-read output was written on the device (GS_DEVICE_RECORDS=0 keeps them on the host)"""
     return int(lib().gs_host_stat(which))
 
 

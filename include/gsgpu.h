@@ -834,6 +834,16 @@ const char *gs_inflate_last_error(void);
 typedef struct gs_deflater gs_deflater;
 int gs_filter_compact_text(gs_bloom *bloom, int which, int with_probs, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_records);
 int gs_match_compact_text(gs_run *run, int with_probs, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_records);
+/* The same for the handle's most recent FASTA or general FASTQ chunk (gs_*_submit_fasta / _fastq_ml, gs_reads_select_fasta /
+ * _fastq_ml), by the kernels of gs_rewrite.hip: the descriptor line (FASTA: its first byte replaced by '@'), '\n', the read in ONE
+ * line ('\r's of its lines kept), "\n+\n", then '~' x length or -- with_probs on a general FASTQ chunk -- every line of the record
+ * behind its '+' line, joined (at least as many bytes as the read), '\n'.  Only the records that END in a general FASTQ chunk count.
+ * Which records: filter: as `which` says; match: GS_F_RETURNED set; reads: selected.  *d_out: a buffer of the handle's, valid until
+ * the next call with the same slot (0 / 1) and, for the filter, the same `which`.  Synchronises the handle's stream; to be called before the next submit.  A chunk of
+ * zero records: GS_OK and 0 bytes.  GS_E_STATE: no chunk submitted, the last one was four-line FASTQ, was refused or was submitted
+ * without per-read flags. */
+int gs_filter_compact_records(gs_bloom *bloom, int which, int with_probs, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_records);
+int gs_match_compact_records(gs_run *run, int with_probs, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_records);
 
 /* ---- Kraken-style lines of a four-line chunk as device text (gs_kraken.hip) -------------------------------------------------
  * taxid string per value index (SmallTaxIdNode.getTaxId), copied to the run's device: bytes back to back + n_values + 1 offsets.
@@ -846,7 +856,12 @@ int gs_match_set_taxids(gs_run *run, const char *const *taxids);
  * refused, was submitted without a class array, or no taxids are set.  Afterwards gs_match_segments_fetch returns this chunk's
  * segments (the call computes them as gs_match_segments_text does). */
 int gs_match_kraken_text(gs_run *run, int write_all, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_lines);
-/* accumulated device time of the text kernels of gs_match_kraken_text since gs_match_begin (cfg.profile != 0): one event pair
+/* The same for the most recent FASTA or general FASTQ chunk of the run: the name comes from the record's descriptor line (behind its
+ * first byte, '>' or '@' alike, up to the first blank), the length is that of the gathered read; a record without a k-mer position
+ * (a FASTA header without sequence lines) has no line.  GS_E_STATE: no chunk submitted, the last one was four-line FASTQ, was
+ * refused, was submitted without a class array, or no taxids are set.  Shares the slots and buffers of gs_match_kraken_text. */
+int gs_match_kraken_records(gs_run *run, int write_all, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_lines);
+/* accumulated device time of the text kernels of gs_match_kraken_text / _records since gs_match_begin (cfg.profile != 0): one event pair
  * around the size pass (sizes, prefix, offsets) and one around the write pass of every call -- `launches` counts the pairs; neither
  * the segments nor the read-back of the text's size between the two passes is in it */
 int gs_match_kraken_time(gs_run *run, int64_t *launches, double *total_ms);
@@ -906,6 +921,9 @@ int gs_reads_select_fastq_ml(gs_reads *reads, int k, const uint8_t *text, int64_
                              int32_t key_len, uint8_t *accept, uint32_t *newlines, int64_t *n_records, int64_t *consumed_bytes,
                              int64_t *consumed_lines, int64_t *ticket);
 int gs_reads_compact_text(gs_reads *reads, int with_probs, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_records);
+/* the selected records of the most recent FASTA or general FASTQ chunk, the latter with its quality lines where with_probs asks for
+ * them: see gs_filter_compact_records.  Its launches count in gs_reads_kernel_time and in [2] of gs_reads_phase_times. */
+int gs_reads_compact_records(gs_reads *reads, int with_probs, int slot, const uint8_t **d_out, int64_t *n_bytes, int64_t *n_records);
 int gs_reads_fasta2fastq(gs_reads *reads, const uint8_t *text, int64_t n_bytes, int64_t n_lines, int64_t n_records, int mem, int slot,
                          const uint8_t **d_out, int64_t *n_bytes_out, int64_t *long_lines, int64_t *ticket);
 int gs_reads_text_read_bounds(gs_reads *reads, uint64_t *bounds);

@@ -102,7 +102,10 @@ int gs_host_match_files_multi(gs_db *const *dbs, int n_dbs, const gs_match_cfg *
 
 /* diagnostics: which = 0: chunks of text that went through the general (multi-line) FASTQ device path of the match goal in this
  * process so far; 1: FASTA / general FASTQ chunks that the filter goal handled on the device; 2: chunks of the match goal whose
- * Kraken-style lines were written on the device (gs_match_kraken_text; GS_DEVICE_KRAKEN=0 keeps them on the host) */
+ * Kraken-style lines were written on the device (gs_match_kraken_text; GS_DEVICE_KRAKEN=0 keeps them on the host; four-line chunks
+ * only); 3: FASTA / general FASTQ chunks of any goal (match, filter, extract) whose per-read output -- filtered file, accepted / rest
+ * file, selected records, Kraken-style lines -- was written on the device (gs_*_compact_records, gs_match_kraken_records;
+ * GS_DEVICE_RECORDS=0 keeps them on the host) */
 int64_t gs_host_stat(int which);
 
 /* ---- runFilter: accepted reads -> filtered_path, the rest -> rest_path (either may be NULL); with_probs as above ---- */

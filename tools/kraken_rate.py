@@ -1,7 +1,10 @@
 """end-to-end rate of gs_host_match_files with per-read outputs (Kraken-style lines, filtered FASTQ), and the device time of the
 text kernels that write the lines (developer tool)
 
-    kraken_rate.py [reads] [gz] [--repeats N]
+    kraken_rate.py [reads] [gz] [--repeats N] [--shape four-line|fasta|multi-line]
+
+--shape: the input file's records -- four lines each (the default), FASTA with the read over two lines, or general FASTQ with the read
+and its qualities over two lines each (per-read outputs of the last two: the record kernels, GS_DEVICE_RECORDS=0 the host formatter).
 
 Every row is run N times (the rows by turns); the summary gives the fastest run and the spread (slowest - fastest) of each row."""
 import argparse
@@ -21,6 +24,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("reads", nargs="?", type=int, default=2_000_000)
 ap.add_argument("gz", nargs="?", default="", help="'gz': compressed outputs (multi-member gzip)")
 ap.add_argument("--repeats", type=int, default=1)
+ap.add_argument("--shape", choices=("four-line", "fasta", "multi-line"), default="four-line")
 args = ap.parse_args()
 n = args.reads
 gz = ".gz" if args.gz == "gz" else ""
@@ -28,10 +32,16 @@ db = synth.SynthDB()
 store = ga.DeviceKMerStore(31, db.kmers, db.value_idx, db.n_values, db.parent_vi)
 seq, off = synth.reads_host(db.genomes, n)
 d = tempfile.mkdtemp(prefix="gskr")
-path = os.path.join(d, "reads.fastq")
+path = os.path.join(d, "reads.fasta" if args.shape == "fasta" else "reads.fastq")
 L = 150
+H = L // 2
 blk = seq.tobytes()
-record = lambda i: b"@r%d\n" % i + blk[i * L:(i + 1) * L] + b"\n+\n" + b"I" * L + b"\n"
+if args.shape == "fasta":
+    record = lambda i: b">r%d\n" % i + blk[i * L:i * L + H] + b"\n" + blk[i * L + H:(i + 1) * L] + b"\n"
+elif args.shape == "multi-line":
+    record = lambda i: b"@r%d\n" % i + blk[i * L:i * L + H] + b"\n" + blk[i * L + H:(i + 1) * L] + b"\n+\n" + b"I" * H + b"\n" + b"I" * (L - H) + b"\n"
+else:
+    record = lambda i: b"@r%d\n" % i + blk[i * L:(i + 1) * L] + b"\n+\n" + b"I" * L + b"\n"
 with open(path, "wb") as f:
     f.write(b"".join(record(i) for i in range(n)))
 rows = (("table only", {}), ("kraken out", dict(kraken_out_path=os.path.join(d, "k.out" + gz), taxids=db.taxids)),
@@ -55,12 +65,17 @@ m = ga.FastqKMerMatcher(store, ga.MatchConfig(profile=True))
 m.set_taxids(db.taxids)
 nc = min(n, 1 << 20)
 chunk = np.frombuffer(b"".join(record(i) for i in range(nc)), dtype=np.uint8)
-cv, fl = np.zeros(nc, dtype=np.int32), np.zeros(nc, dtype=np.uint8)
+cv, fl = np.zeros(2 * nc + 2, dtype=np.int32), np.zeros(2 * nc + 2, dtype=np.uint8)
 calls = 5
 k0 = m0 = 0.0
 for call in range(calls + 1):  # (the first call sizes the buffers and is left out)
-    m.submit_text(chunk, n_lines=4 * nc, class_vi=cv, flags=fl)
-    text = m.kraken_text(True)
+    if args.shape == "fasta":
+        m.submit_fasta(chunk, n_lines=3 * nc, n_records=nc, class_vi=cv, flags=fl)
+    elif args.shape == "multi-line":
+        m.submit_fastq_ml(chunk, n_lines=6 * nc, class_vi=cv, flags=fl)
+    else:
+        m.submit_text(chunk, n_lines=4 * nc, class_vi=cv, flags=fl)
+    text = m.kraken_text(True) if args.shape == "four-line" else m.kraken_records(True)
     if call == 0:
         k0, m0 = m.kraken_time()[1], m.kernel_time()[1]
 k_ms, m_ms = (m.kraken_time()[1] - k0) / calls, (m.kernel_time()[1] - m0) / calls

@@ -1,6 +1,6 @@
 """Rates of the two read-stream goals, extract and fasta2fastq.
 
-    python tools/stream_goal_rate.py [reads]
+    python tools/stream_goal_rate.py [reads] [--records]
 
 * the FASTA -> FASTQ text kernels alone (sizes, offsets, copy between events: gs_reads_kernel_time), goal mode and ReadEntry
   mode, as GB/s of text written -- and, as a yardstick in the same session, the wall time of the existing four-line gather
@@ -9,7 +9,11 @@
 * both goals end to end for plain, gzip and BGZF input into a .gz output, device path against the host layer's reference-exact
   path (GS_HOST_FAST=0) of the same build, alternating -- and, from one further run of the device path in a process of its own
   with GS_HOST_TRACE set, where the time goes: the phases of the host layer's file loop and, between events on the handle's
-  stream, the select stage, the four-line gather and the FASTA -> FASTQ text kernels (gs_reads_phase_times)."""
+  stream, the select stage, the four-line gather and the FASTA -> FASTQ text kernels (gs_reads_phase_times);
+* extract of a plain FASTA file and of a plain general FASTQ file (sequence and quality over two lines each) into a .gz output,
+  the records written on the device against GS_DEVICE_RECORDS=0 (the host's formatter and zlib), alternating, three runs each --
+  and the text kernels of gs_reads_compact_records between events for both chunk kinds beside the four-line gather of text of the
+  same size.  --records: these rows only."""
 import ctypes as C
 import gzip
 import os
@@ -32,13 +36,61 @@ READ = 150
 def texts(n):
     rng = np.random.default_rng(5)
     seq = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, n * READ)].reshape(n, READ)
-    fq, fa = [], []
+    fq, fa, ml = [], [], []
     for i in range(n):
         s = seq[i].tobytes()
         d = b"s%d:%d run" % (i % 8, i)
         fq.append(b"@" + d + b"\n" + s + b"\n+\n" + b"I" * READ + b"\n")
         fa.append(b">" + d + b"\n" + s[:75] + b"\n" + s[75:] + b"\n")
-    return b"".join(fq), b"".join(fa)
+        ml.append(b"@" + d + b"\n" + s[:75] + b"\n" + s[75:] + b"\n+\n" + b"I" * 75 + b"\n" + b"J" * 75 + b"\n")
+    return b"".join(fq), b"".join(fa), b"".join(ml)
+
+
+def record_rows(n, fq, fa, ml, tmp):
+    """extract of FASTA and general FASTQ into .gz, device records against GS_DEVICE_RECORDS=0; the text kernels between events"""
+    gbp = n * READ / 1e9
+    for kind, data in (("fasta", fa), ("multi-line fastq", ml)):
+        src = os.path.join(tmp, "records." + ("fasta" if kind == "fasta" else "fastq"))
+        open(src, "wb").write(data)
+        t = {"device": [], "host": []}
+        for _ in range(3):
+            for mode in ("device", "host"):
+                if mode == "host":
+                    os.environ["GS_DEVICE_RECORDS"] = "0"
+                before = host.stat(3)
+                t0 = time.perf_counter()
+                run_goal("extract", src, os.path.join(tmp, f"records_{mode}.fastq.gz"))
+                t[mode].append(time.perf_counter() - t0)
+                assert (host.stat(3) > before) == (mode == "device")
+                os.environ.pop("GS_DEVICE_RECORDS", None)
+        same = gzip.open(os.path.join(tmp, "records_device.fastq.gz")).read() == gzip.open(os.path.join(tmp, "records_host.fastq.gz")).read()
+        fmt = lambda ts: " / ".join(f"{x * 1e3:.0f}" for x in ts)
+        print(f"extract plain {kind} -> .gz: records on the device {fmt(t['device'])} ms ({gbp / min(t['device']):.2f} Gbp/s), "
+              f"GS_DEVICE_RECORDS=0 {fmt(t['host'])} ms ({gbp / min(t['host']):.2f} Gbp/s), same text: {same}")
+        print("  " + phases("extract", src, os.path.join(tmp, "records_traced.fastq.gz")))
+    # the text kernels: every record selected, qualities on
+    reads = ga.DeviceReads(k=31)
+    reads.kernel_time(True)
+    for kind, select, data in (("FASTA", reads.select_fasta, fa), ("multi-line FASTQ, qualities gathered", reads.select_fastq_ml, ml)):
+        select(data, b"s")
+        nbytes = len(reads.compact_records(True)[0])
+        n0, ms0 = reads.kernel_time(True)
+        for i in range(5):
+            select(data, b"s")  # (a new chunk: the quality gather runs once per chunk)
+            reads.compact_records(True, i & 1)
+        n1, ms1 = reads.kernel_time(True)
+        per = (ms1 - ms0) / (n1 - n0)
+        print(f"gs_reads_compact_records, {kind}: text kernels {per:.3f} ms = {nbytes / per / 1e6:.1f} GB/s of {nbytes / 1e6:.1f} MB written")
+    reads.select_text(fq, b"s")
+    L = ga.lib()
+    p, nb, nr = C.c_void_p(), C.c_int64(0), C.c_int64(0)
+
+    def gather():
+        assert L.gs_reads_compact_text(reads.h, 1, 0, C.byref(p), C.byref(nb), C.byref(nr)) == 0
+
+    gather()
+    t = min(best(gather, 3)[0] for _ in range(3))
+    print(f"yardstick, four-line gather (gs_reads_compact_text): {nb.value / 1e6:.1f} MB, call wall min {t * 1e3:.3f} ms = {nb.value / t / 1e9:.1f} GB/s")
 
 
 def bgzf(data, block=65280):
@@ -82,9 +134,13 @@ def main():
         for _ in range(2):  # (the second run is the one reported: the first one of a process pays for its allocations)
             run_goal(*sys.argv[2:])
         return
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
-    fq, fa = texts(n)
-    print(f"{n} reads of {READ} bases: FASTQ {len(fq) / 1e6:.1f} MB, FASTA {len(fa) / 1e6:.1f} MB")
+    args = [a for a in sys.argv[1:] if a != "--records"]
+    n = int(args[0]) if args else 1_000_000
+    fq, fa, ml = texts(n)
+    print(f"{n} reads of {READ} bases: FASTQ {len(fq) / 1e6:.1f} MB, FASTA {len(fa) / 1e6:.1f} MB, multi-line FASTQ {len(ml) / 1e6:.1f} MB")
+    if "--records" in sys.argv[1:]:
+        record_rows(n, fq, fa, ml, tempfile.mkdtemp())
+        return
     L = ga.lib()
     reads = ga.DeviceReads(k=31)
     reads.kernel_time(True)
@@ -162,11 +218,7 @@ def main():
             print(f"{goal_name} {kind} -> .gz: device {gbp / min(t['device']):.2f} Gbp/s ({min(t['device']) * 1e3:.0f} ms), "
                   f"cpu path {gbp / min(t['cpu']):.2f} Gbp/s ({min(t['cpu']) * 1e3:.0f} ms), same text: {same}")
             print("  " + phases(goal_name, src, os.path.join(tmp, f"{goal_name}_traced.fastq.gz")))
-        if kind == "plain":  # extract on FASTA input: records flagged on the device, written by the host writers
-            t0 = time.perf_counter()
-            run_goal("extract", pa, os.path.join(tmp, "extract_fasta.fastq.gz"))
-            print(f"extract plain FASTA -> .gz: device {gbp / (time.perf_counter() - t0):.2f} Gbp/s (one run)")
-            print("  " + phases("extract", pa, os.path.join(tmp, "extract_fasta_traced.fastq.gz")))
+    record_rows(n, fq, fa, ml, tmp)
 
 
 if __name__ == "__main__":
