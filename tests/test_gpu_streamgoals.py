@@ -1,6 +1,8 @@
 """extract and fasta2fastq on the device: gs_reads_fasta2fastq, the three gs_reads_select_* calls with gs_reads_compact_text, and
 both goals file by file (gs_host_extract_files, gs_host_fasta2fastq), byte-equal to the two Java loops restated in
-tests/streamgoals.py.  Small shapes: every lane, tile and block edge of the kernels, nothing of the workload's size."""
+tests/streamgoals.py.  Small shapes: every lane, tile and block edge of the kernels, nothing of the workload's size -- the second
+level of the block scans (more than 262 144 lines or records, text beyond 64 MiB, output beyond the copy grid) is the subject of
+tests/test_gpu_chunk_scale.py."""
 import gzip
 import os
 
