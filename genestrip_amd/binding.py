@@ -56,6 +56,9 @@ ABI_SYMBOLS = (
     "gs_reads_select_fastq_ml", "gs_reads_compact_text", "gs_reads_compact_records", "gs_reads_fasta2fastq", "gs_reads_text_read_bounds", "gs_reads_text_line_classes",
     "gs_reads_text_wait_copy", "gs_reads_text_status", "gs_reads_text_reset", "gs_reads_kernel_time",
     "gs_reads_phase_times",
+    "gs_krakencount_create", "gs_krakencount_destroy", "gs_krakencount_get_device", "gs_krakencount_geometry", "gs_krakencount_submit",
+    "gs_krakencount_chunk", "gs_krakencount_status", "gs_krakencount_reset", "gs_krakencount_fetch", "gs_krakencount_counters",
+    "gs_krakencount_kernel_time",
 )
 
 
@@ -254,6 +257,11 @@ def lib():
         "gs_reads_text_read_bounds": (ci, [vp, vp]), "gs_reads_text_line_classes": (ci, [vp, vp]),
         "gs_reads_text_wait_copy": (ci, [vp, i64]), "gs_reads_text_status": (ci, [vp, vp, vp, vp]), "gs_reads_text_reset": (ci, [vp, ci]),
         "gs_reads_kernel_time": (ci, [vp, ci, vp, vp]), "gs_reads_phase_times": (ci, [vp, vp, vp]),
+        "gs_krakencount_create": (ci, [vp, ci, i64]), "gs_krakencount_destroy": (ci, [vp]), "gs_krakencount_get_device": (ci, [vp, vp]),
+        "gs_krakencount_geometry": (ci, [vp, vp]), "gs_krakencount_submit": (ci, [vp, vp, i64, ci, vp]),
+        "gs_krakencount_chunk": (ci, [vp, i64, vp]), "gs_krakencount_status": (ci, [vp, vp, vp, vp, vp]), "gs_krakencount_reset": (ci, [vp]),
+        "gs_krakencount_fetch": (ci, [vp, vp, vp, i64, vp]), "gs_krakencount_counters": (ci, [vp, vp]),
+        "gs_krakencount_kernel_time": (ci, [vp, ci, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1550,3 +1558,76 @@ class DeviceReads:
         n, ms = (C.c_int64 * 3)(), (C.c_double * 3)()
         _check(lib().gs_reads_phase_times(self.h, n, ms))
         return {name: (n[i], ms[i]) for i, name in enumerate(("select", "gather", "rewrite"))}
+
+
+class KrakenCounter:
+    """gs_krakencount: Kraken-style output lines counted per tax id on the device (the krakencount goal).  A chunk outside the
+    device's grammar is refused and adds nothing: genestrip_amd.host.kraken_count_files hands such chunks to the reference-exact
+    parser; here the caller sees the refusal in the chunk's report."""
+
+    def __init__(self, device=0, max_taxids=1 << 16):
+        self.h = C.c_void_p()
+        self.device = int(device)
+        _check(lib().gs_krakencount_create(C.byref(self.h), self.device, int(max_taxids)))
+
+    def close(self):
+        if self.h:
+            lib().gs_krakencount_destroy(self.h)
+            self.h = C.c_void_p()
+
+    __del__ = close
+
+    def geometry(self):
+        g = (C.c_int64 * 6)()
+        _check(lib().gs_krakencount_geometry(self.h, g))
+        return {"tile_bytes": g[0], "lds_slots": g[1], "global_slots": g[2], "scan_levels": g[3], "scan_block_bytes": g[4],
+                "level3_blocks": g[5]}
+
+    def submit(self, text):
+        """a chunk of whole lines (bytes, a uint8 array, or a uint8 tensor on the handle's device) -> its ticket"""
+        if isinstance(text, (bytes, bytearray)):
+            text = np.frombuffer(bytes(text), dtype=np.uint8)
+        n = int(text.shape[0])
+        _ready(text)
+        p, mem = _ptr(text) if n else (None, MEM_HOST)
+        ticket = C.c_int64()
+        _check(lib().gs_krakencount_submit(self.h, p, n, mem, C.byref(ticket)))
+        return ticket.value
+
+    def chunk(self, ticket):
+        """what became of a chunk: refused (0 counted, 1 outside the grammar, 2 table full), its first bad line, the offset of its
+        first empty line (-1: none), the table's rows behind it, its own totals"""
+        r = (C.c_int64 * 8)()
+        _check(lib().gs_krakencount_chunk(self.h, int(ticket), r))
+        return {"refused": r[0], "first_bad_line": r[1], "first_empty_offset": r[2], "rows": r[3], "totals": tuple(r[4:8])}
+
+    def status(self):
+        """(first refused ticket or -1, its first bad line, first-empty-line offset of the latest chunk, totals = lines, counted
+        tokens, skipped 'A' tokens, long lines)"""
+        ft, fb, fe = C.c_int64(), C.c_int64(), C.c_int64()
+        tot = (C.c_int64 * 4)()
+        _check(lib().gs_krakencount_status(self.h, C.byref(ft), C.byref(fb), C.byref(fe), tot))
+        return ft.value, fb.value, fe.value, tuple(tot)
+
+    def reset(self):
+        _check(lib().gs_krakencount_reset(self.h))
+
+    def fetch(self):
+        """(taxids int32[n], counts int64[n, 3] = reads, kmers, kmers in matching reads), rows in the reference's order"""
+        n = C.c_int64()
+        _check(lib().gs_krakencount_fetch(self.h, None, None, 0, C.byref(n)))
+        ids = np.zeros(max(n.value, 1), dtype=np.int32)
+        cnt = np.zeros((max(n.value, 1), 3), dtype=np.int64)
+        _check(lib().gs_krakencount_fetch(self.h, _ptr(ids)[0], _ptr(cnt)[0], n.value, C.byref(n)))
+        return ids[:n.value], cnt[:n.value]
+
+    def counters(self):
+        """(global atomics issued by the accumulation, tokens whose key found no room in a workgroup's table)"""
+        c = (C.c_int64 * 2)()
+        _check(lib().gs_krakencount_counters(self.h, c))
+        return c[0], c[1]
+
+    def kernel_time(self, profile=True):
+        n, ms = C.c_int64(), C.c_double()
+        _check(lib().gs_krakencount_kernel_time(self.h, int(profile), C.byref(n), C.byref(ms)))
+        return n.value, ms.value

@@ -6137,3 +6137,282 @@ extern "C" int gs_reads_text_reset(gs_reads *h, int clear_totals) {
     HIP_TRY(hipSetDevice(h->device));
     return text_reset(h->text, clear_totals != 0, h->stream);
 }
+
+// ---------------------------------------------------------------------------------------------------
+// krakencount: Kraken-style lines counted per tax id (gs_krakencount.hip)
+// ---------------------------------------------------------------------------------------------------
+#define KC_RING 64  // chunk reports kept
+struct gs_krakencount {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t copied = nullptr;
+    int64_t max_taxids = 0;
+    uint32_t n_slots = 0, slot_bits = 0;
+    uint8_t *d_text = nullptr;
+    size_t text_cap = 0;
+    u64 *d_tile_lt = nullptr, *d_tile_c = nullptr;
+    size_t tile_lt_cap = 0, tile_c_cap = 0;
+    uint32_t *d_line = nullptr;  // line_end | line_c4 | line_key, line_cap entries each
+    size_t line_cap = 0;
+    uint32_t *d_keys = nullptr, *d_present = nullptr;
+    u64 *d_acc = nullptr, *d_delta = nullptr;
+    u64 *d_small = nullptr;  // status, totals, counters, the chunk's report (kc_params)
+    u64 *h_res = nullptr;    // KC_RING reports of GS_KC_R_WORDS words, page-locked
+    int64_t tickets = 0, absorbed = 0;
+    int64_t failed_ticket = -1, failed_line = -1, last_empty = -1;
+    int64_t totals[4] = {0, 0, 0, 0};
+    bool profile = false;
+    KernelTimer timer;
+};
+
+enum { KC_S_STATUS = 0, KC_S_CHUNK = 2, KC_S_RUN = 8, KC_S_NKEYS = 12, KC_S_COUNTERS = 13, KC_S_SCAN = 15, KC_S_RESULT = 17, KC_S_WORDS = KC_S_RESULT + GS_KC_R_WORDS };
+
+static void kc_params(gs_krakencount *h, GsKrakenCountParams *P) {
+    P->text = h->d_text;
+    P->tile_lt = (unsigned long long *)h->d_tile_lt;
+    P->tile_c = (unsigned long long *)h->d_tile_c;
+    P->scan_tot = (unsigned long long *)h->d_small + KC_S_SCAN;
+    P->line_end = h->d_line;
+    P->line_c4 = h->d_line + h->line_cap;
+    P->line_key = h->d_line + 2 * h->line_cap;
+    P->line_cap = (int64_t)h->line_cap;
+    P->status = (uint32_t *)(h->d_small + KC_S_STATUS);
+    P->chunk_tot = (unsigned long long *)h->d_small + KC_S_CHUNK;
+    P->run_tot = (unsigned long long *)h->d_small + KC_S_RUN;
+    P->keys = h->d_keys;
+    P->present = h->d_present;
+    P->acc = (unsigned long long *)h->d_acc;
+    P->delta = (unsigned long long *)h->d_delta;
+    P->n_slots = h->n_slots;
+    P->slot_bits = h->slot_bits;
+    P->max_keys = (uint32_t)h->max_taxids;
+    P->n_keys = (uint32_t *)(h->d_small + KC_S_NKEYS);
+    P->counters = (unsigned long long *)h->d_small + KC_S_COUNTERS;
+    P->result = (unsigned long long *)h->d_small + KC_S_RESULT;
+}
+
+extern "C" int gs_krakencount_destroy(gs_krakencount *h) {
+    if (!h) return GS_OK;
+    hipSetDevice(h->device);
+    if (h->stream) hipStreamSynchronize(h->stream);
+    timer_free(h->timer);
+    gs_dev_free(h->d_text);
+    gs_dev_free(h->d_tile_lt);
+    gs_dev_free(h->d_tile_c);
+    gs_dev_free(h->d_line);
+    gs_dev_free(h->d_keys);
+    gs_dev_free(h->d_present);
+    gs_dev_free(h->d_acc);
+    gs_dev_free(h->d_delta);
+    gs_dev_free(h->d_small);
+    if (h->h_res) hipHostFree(h->h_res);
+    if (h->copied) hipEventDestroy(h->copied);
+    if (h->stream) hipStreamDestroy(h->stream);
+    delete h;
+    return GS_OK;
+}
+
+static int kc_clear(gs_krakencount *h) {
+    GsKrakenCountParams P{};
+    kc_params(h, &P);
+    HIP_TRY(gs_launch_krakencount_reset(&P, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->absorbed = h->tickets;
+    h->failed_ticket = h->failed_line = h->last_empty = -1;
+    for (int i = 0; i < 4; i++) h->totals[i] = 0;
+    return GS_OK;
+}
+
+extern "C" int gs_krakencount_create(gs_krakencount **out, int device, int64_t max_taxids) try {
+    if (!out) return fail(GS_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (max_taxids < 1 || max_taxids > ((int64_t)1 << 26)) return fail(GS_E_INVALID, "max_taxids must be in [1, 2^26]");
+    int rc = use_device(device);
+    if (rc) return rc;
+    gs_krakencount *h = new gs_krakencount();
+    h->device = device;
+    h->max_taxids = max_taxids;
+    h->slot_bits = 6;  // at most half full
+    while (((int64_t)1 << h->slot_bits) < 2 * max_taxids) h->slot_bits++;
+    h->n_slots = 1u << h->slot_bits;
+    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->copied, hipEventDisableTiming);
+    if (e == hipSuccess) e = gs_dev_alloc(&h->d_keys, sizeof(uint32_t) * h->n_slots);
+    if (e == hipSuccess) e = gs_dev_alloc(&h->d_present, sizeof(uint32_t) * h->n_slots);
+    if (e == hipSuccess) e = gs_dev_alloc(&h->d_acc, sizeof(u64) * 3 * h->n_slots);
+    if (e == hipSuccess) e = gs_dev_alloc(&h->d_delta, sizeof(u64) * 3 * h->n_slots);
+    if (e == hipSuccess) e = gs_dev_alloc(&h->d_small, sizeof(u64) * KC_S_WORDS);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&h->h_res, sizeof(u64) * KC_RING * GS_KC_R_WORDS);
+    if (e != hipSuccess) {
+        gs_krakencount_destroy(h);
+        return hip_fail(e, "gs_krakencount_create");
+    }
+    if ((rc = kc_clear(h))) {
+        gs_krakencount_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_krakencount_get_device(gs_krakencount *h, int *device) {
+    if (!h || !device) return fail(GS_E_INVALID, "NULL argument");
+    *device = h->device;
+    return GS_OK;
+}
+
+extern "C" int gs_krakencount_geometry(gs_krakencount *h, int64_t geometry[6]) {
+    if (!h || !geometry) return fail(GS_E_INVALID, "NULL argument");
+    geometry[0] = (int64_t)GS_KC_TILE * GS_KC_GROUP;
+    geometry[1] = GS_KC_LDS_SLOTS;
+    geometry[2] = h->n_slots;
+    geometry[3] = 3;
+    geometry[4] = GS_KC_TILE;
+    geometry[5] = 1025;  // (gs_launch_scan_blocks: one block of 1024 threads)
+    return GS_OK;
+}
+
+// the reports the stream has written since the last look (the caller has synchronised it)
+static void kc_absorb(gs_krakencount *h) {
+    for (; h->absorbed < h->tickets; h->absorbed++) {
+        const u64 *R = h->h_res + (size_t)(h->absorbed % KC_RING) * GS_KC_R_WORDS;
+        if (R[GS_KC_R_REFUSED] != 0 && h->failed_ticket < 0) {
+            h->failed_ticket = h->absorbed;
+            h->failed_line = (int64_t)R[GS_KC_R_BAD_LINE];
+        }
+        h->last_empty = (int64_t)R[GS_KC_R_EMPTY_OFF];
+        for (int i = 0; i < 4; i++) h->totals[i] = (int64_t)R[GS_KC_R_RUN + i];
+    }
+}
+
+static int kc_sync(gs_krakencount *h) {
+    if (!h) return fail(GS_E_INVALID, "krakencount is NULL");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    kc_absorb(h);
+    return timer_collect(h->timer);
+}
+
+extern "C" int gs_krakencount_submit(gs_krakencount *h, const uint8_t *text, int64_t n_bytes, int mem, int64_t *ticket) try {
+    if (!h) return fail(GS_E_INVALID, "krakencount is NULL");
+    if (n_bytes < 0 || n_bytes > ((int64_t)1 << 30)) return fail(GS_E_INVALID, "a chunk holds at most 1 GiB");
+    if (n_bytes > 0 && !text) return fail(GS_E_INVALID, "text is NULL");
+    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    HIP_TRY(hipSetDevice(h->device));
+    int rc;
+    if (h->tickets - h->absorbed >= KC_RING - 1 && (rc = kc_sync(h))) return rc;
+    u64 *res = h->h_res + (size_t)(h->tickets % KC_RING) * GS_KC_R_WORDS;
+    if (n_bytes == 0) {  // nothing to count: the report of the chunk in front of it, without its own lines
+        if ((rc = kc_sync(h))) return rc;
+        const u64 rows = h->tickets ? h->h_res[(size_t)((h->tickets - 1) % KC_RING) * GS_KC_R_WORDS + GS_KC_R_ROWS] : 0;
+        for (int i = 0; i < GS_KC_R_WORDS; i++) res[i] = 0;
+        res[GS_KC_R_BAD_LINE] = res[GS_KC_R_EMPTY_OFF] = ~0ULL;
+        res[GS_KC_R_ROWS] = rows;
+        for (int i = 0; i < 4; i++) res[GS_KC_R_RUN + i] = (u64)h->totals[i];
+        if (ticket) *ticket = h->tickets;
+        h->tickets++;
+        return GS_OK;
+    }
+    const int64_t n_tiles = (n_bytes + GS_KC_TILE - 1) / GS_KC_TILE;
+    const size_t padded = (size_t)n_tiles * GS_KC_TILE + 64;
+    if ((rc = grow(&h->d_text, &h->text_cap, padded, h->stream))) return rc;
+    if ((rc = grow(&h->d_tile_lt, &h->tile_lt_cap, (size_t)n_tiles + 1, h->stream))) return rc;
+    if ((rc = grow(&h->d_tile_c, &h->tile_c_cap, (size_t)n_tiles + 1, h->stream))) return rc;
+    const size_t lines = (size_t)n_bytes / 7 + 2;  // (a line of the grammar has 7 bytes and more)
+    if (h->line_cap < lines) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->line_cap = 0;
+        if ((rc = renew(&h->d_line, 3 * (lines + lines / 4)))) return rc;
+        h->line_cap = lines + lines / 4;
+    }
+    HIP_TRY(hipMemcpyAsync(h->d_text, text, (size_t)n_bytes, mem == GS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(h->d_text + n_bytes, 0, padded - (size_t)n_bytes, h->stream));
+    if (mem == GS_MEM_HOST) {  // the caller's memory is free again on return
+        HIP_TRY(hipEventRecord(h->copied, h->stream));
+        HIP_TRY(hipEventSynchronize(h->copied));
+    }
+    GsKrakenCountParams P{};
+    kc_params(h, &P);
+    P.n_bytes = n_bytes;
+    P.n_tiles = n_tiles;
+    if ((rc = timer_start(h->timer, h->profile, h->stream))) return rc;
+    HIP_TRY(gs_launch_krakencount(&P, h->stream));
+    if ((rc = timer_stop(h->timer, h->profile, h->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(res, h->d_small + KC_S_RESULT, sizeof(u64) * GS_KC_R_WORDS, hipMemcpyDeviceToHost, h->stream));
+    if (ticket) *ticket = h->tickets;
+    h->tickets++;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_krakencount_chunk(gs_krakencount *h, int64_t ticket, int64_t report[8]) {
+    if (!h || !report) return fail(GS_E_INVALID, "NULL argument");
+    if (ticket < 0 || ticket >= h->tickets || ticket < h->tickets - (KC_RING - 1)) return fail(GS_E_INVALID, "no report is kept for this ticket");
+    int rc = kc_sync(h);
+    if (rc) return rc;
+    const u64 *R = h->h_res + (size_t)(ticket % KC_RING) * GS_KC_R_WORDS;
+    for (int i = 0; i < 8; i++) report[i] = (int64_t)R[i];
+    return GS_OK;
+}
+
+extern "C" int gs_krakencount_status(gs_krakencount *h, int64_t *failed_ticket, int64_t *first_bad_line, int64_t *first_empty_offset, int64_t totals[4]) {
+    int rc = kc_sync(h);
+    if (rc) return rc;
+    if (failed_ticket) *failed_ticket = h->failed_ticket;
+    if (first_bad_line) *first_bad_line = h->failed_line;
+    if (first_empty_offset) *first_empty_offset = h->last_empty;
+    if (totals)
+        for (int i = 0; i < 4; i++) totals[i] = h->totals[i];
+    return GS_OK;
+}
+
+extern "C" int gs_krakencount_reset(gs_krakencount *h) {
+    int rc = kc_sync(h);
+    if (rc) return rc;
+    return kc_clear(h);
+}
+
+extern "C" int gs_krakencount_fetch(gs_krakencount *h, int32_t *taxids, int64_t *counts, int64_t cap, int64_t *n_rows) try {
+    if (!n_rows) return fail(GS_E_INVALID, "n_rows is NULL");
+    int rc = kc_sync(h);
+    if (rc) return rc;
+    std::vector<uint32_t> keys(h->n_slots), present(h->n_slots);
+    std::vector<u64> acc((size_t)h->n_slots * 3);
+    HIP_TRY(hipMemcpy(keys.data(), h->d_keys, sizeof(uint32_t) * h->n_slots, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(present.data(), h->d_present, sizeof(uint32_t) * h->n_slots, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(acc.data(), h->d_acc, sizeof(u64) * 3 * h->n_slots, hipMemcpyDeviceToHost));
+    std::vector<std::pair<std::string, uint32_t>> rows;  // (decimal string, slot): DigitTrie.collect visits a prefix before its extensions
+    for (uint32_t s = 0; s < h->n_slots; s++)
+        if (keys[s] != GS_KC_EMPTY && present[s]) rows.push_back({std::to_string(keys[s]), s});
+    std::sort(rows.begin(), rows.end());
+    *n_rows = (int64_t)rows.size();
+    if (cap < *n_rows) return GS_OK;
+    if (!rows.empty() && (!taxids || !counts)) return fail(GS_E_INVALID, "NULL argument");
+    for (size_t i = 0; i < rows.size(); i++) {
+        taxids[i] = (int32_t)keys[rows[i].second];
+        for (int j = 0; j < 3; j++) counts[3 * i + j] = (int64_t)acc[(size_t)rows[i].second * 3 + j];
+    }
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_krakencount_counters(gs_krakencount *h, int64_t counters[2]) {
+    if (!counters) return fail(GS_E_INVALID, "NULL argument");
+    int rc = kc_sync(h);
+    if (rc) return rc;
+    u64 c[2];
+    HIP_TRY(hipMemcpy(c, h->d_small + KC_S_COUNTERS, sizeof(c), hipMemcpyDeviceToHost));
+    counters[0] = (int64_t)c[0];
+    counters[1] = (int64_t)c[1];
+    return GS_OK;
+}
+
+extern "C" int gs_krakencount_kernel_time(gs_krakencount *h, int profile, int64_t *launches, double *total_ms) {
+    int rc = kc_sync(h);
+    if (rc) return rc;
+    h->profile = profile != 0;
+    if (launches) *launches = h->timer.launches;
+    if (total_ms) *total_ms = h->timer.total_ms;
+    return GS_OK;
+}

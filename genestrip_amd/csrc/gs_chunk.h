@@ -54,11 +54,12 @@ inline FastaCut fasta_cut(const uint8_t *blk, int64_t n, bool last, const std::v
 // it lies.  The chunk ends
 //   FOUR_LINE  behind the last newline that closes a group of four lines,
 //   FASTA      in front of the block's last header line (fasta_cut),
-//   GENERAL    behind the block's last newline; the device then says how much of the chunk its records cover (commit).
+//   GENERAL    behind the block's last newline; the device then says how much of the chunk its records cover (commit),
+//   LINES      behind the block's last newline: every line is a record of its own.
 // A chunk the device took is committed -- only then does the carry move on; one it refused is not, and the general parser takes
 // the file from file_off, the chunk's first byte.  The same offset serves when next() gives up (FALLBACK).
 struct ChunkCutter {
-    enum Mode { FOUR_LINE, FASTA, GENERAL };
+    enum Mode { FOUR_LINE, FASTA, GENERAL, LINES };
     enum Cut {
         ABSORBED,  // nothing whole yet: the block went into the carry
         FALLBACK,  // a record longer than the headroom, or a FASTA chunk of 2^24 records or more: the general parser from file_off

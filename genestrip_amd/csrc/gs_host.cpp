@@ -5,6 +5,7 @@
 // in gs_report.cpp.  Plain C++17 + zlib; all GPU work goes through the C ABI of include/gsgpu.h.
 #include "gs_ingest.h"
 #include "gs_chunk.h"
+#include "gs_krakenparse.h"
 
 using namespace gs_host;
 
@@ -688,6 +689,7 @@ int parsed_source(MatchCtx &c, const std::string &path, int64_t offset, const ui
 std::atomic<int64_t> g_ml_chunks{0};  // chunks matched through the general FASTQ device path (gs_host_stat(0))
 std::atomic<int64_t> g_filter_general_chunks{0};  // FASTA / general FASTQ chunks filtered on the device (gs_host_stat(1))
 std::atomic<int64_t> g_kraken_device_chunks{0};  // chunks whose Kraken-style lines were written on the device (gs_host_stat(2))
+std::atomic<int64_t> g_krakencount_chunks{0};  // chunks of Kraken-style lines counted on the device (gs_host_stat(5))
 std::atomic<int64_t> g_record_device_chunks{0};  // FASTA / general FASTQ chunks whose per-read output was written on the device (gs_host_stat(3))
 
 struct TextChunk {
@@ -2639,6 +2641,7 @@ extern "C" int gs_host_release_pools(void) try {
 extern "C" int64_t gs_host_stat(int which) {
     switch (which) {
         case 0: return g_ml_chunks.load();
+        case 5: return g_krakencount_chunks.load();
         case 1: return g_filter_general_chunks.load();
         case 2: return g_kraken_device_chunks.load();
         case 3: return g_record_device_chunks.load();
@@ -2915,6 +2918,205 @@ extern "C" int gs_host_fasta2fastq(int device, const char *const *paths, int n_p
     if (!err && !wrote) err = hfail(GS_E_IO, std::string("writing ") + out_path + " failed");
     if (n_records) *n_records = records;
     return err;
+} catch (const std::bad_alloc &) {
+    return hfail(GS_E_NOMEM, "out of host memory");
+} catch (const std::exception &e) {
+    return hfail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
+}
+
+// ---- krakencount (C/goals/kraken/KrakenResCountGoal.java:133-157)
+namespace {
+
+struct KcGuard {
+    gs_krakencount *&kc;
+    ~KcGuard() {
+        if (kc) gs_krakencount_destroy(kc);
+        kc = nullptr;
+    }
+};
+
+struct KcCtx {
+    gs_krakencount *kc = nullptr;
+    KrakenExact exact;  // rows of what the line-by-line loop took; its lines / tokens
+    int64_t dev_tot[4] = {0, 0, 0, 0};
+    int64_t device_chunks = 0, host_chunks = 0;
+};
+
+int kc_format_error(const KcCtx &c, const std::string &path) {
+    return hfail(GS_E_INVALID, path + ": line " + std::to_string((long long)c.exact.line_no) + ": " + c.exact.error);
+}
+
+// the rest of a stream, line by line: the file from `offset` on, or a memory range that ends the stream
+int kc_cpu(KcCtx &c, const std::string &path, int64_t offset, const uint8_t *mem, size_t mem_n) {
+    c.host_chunks++;
+    if (mem) return c.exact.feed(mem, mem_n, true) ? (int)GS_OK : kc_format_error(c, path);
+    LineReader lr;
+    if (!lr.open(path, offset)) return hfail(GS_E_IO, "cannot open " + path);
+    std::vector<uint8_t> text;
+    for (bool eof = false; !eof && !c.exact.ended;) {  // whole lines, some MiB at a time
+        text.clear();
+        while (text.size() < ((size_t)4 << 20)) {
+            if (lr.next_line(text) == 0) {
+                eof = true;
+                break;
+            }
+        }
+        // (next_line drops NUL bytes as the parser would; a final line without its newline is the stream's last)
+        if (!text.empty() && text.back() != '\n') eof = true;
+        if (!c.exact.feed(text.data(), text.size(), eof)) return kc_format_error(c, path);
+    }
+    return GS_OK;
+}
+
+// One file through the device: chunks that end behind a newline are counted there; one that the device refuses goes through
+// the line-by-line loop, and the stream goes on behind it on the device.  A line that does not fit a block sends the rest of the
+// file through that loop; so does the unterminated tail.
+int kc_device_file(KcCtx &c, const std::string &path, bool gzip) {
+    size_t block;
+    int readers = 0;
+    reader_shape(gzip, &block, &readers);
+    TextReader tr;
+    int err = tr.open(path, block, readers, gzip);
+    if (err) {
+        tr.close();
+        return err;
+    }
+    ChunkCutter cut;
+    cut.mode = ChunkCutter::LINES;
+    int64_t fallback_off = -1;
+    tr.start();
+    for (int64_t i = 0; !err; i++) {
+        TextSlot &sl = tr.wait_full(i);
+        if ((err = block_error(tr, sl, path))) break;
+        const bool eof = sl.eof;
+        const ChunkCutter::Cut what = cut_block(cut, tr, sl);
+        if (what == ChunkCutter::FALLBACK) {
+            fallback_off = cut.file_off;
+        } else if (what == ChunkCutter::CHUNK && cut.bytes > 0) {
+            int64_t ticket = 0, rep[8];
+            if (gs_krakencount_submit(c.kc, cut.start, cut.bytes, GS_MEM_HOST, &ticket) != GS_OK || gs_krakencount_chunk(c.kc, ticket, rep) != GS_OK) {
+                err = hfail(GS_E_HIP, gs_last_error());
+                break;
+            }
+            if (rep[0] != 0) {  // refused: this chunk line by line
+                c.host_chunks++;
+                if (!c.exact.feed(cut.start, (size_t)cut.bytes, false)) err = kc_format_error(c, path);
+            } else {
+                c.device_chunks++;
+                g_krakencount_chunks++;
+                for (int j = 0; j < 4; j++) c.dev_tot[j] += rep[4 + j];
+                if (rep[2] >= 0) {
+                    c.exact.ended = true;  // an empty line: the stream ends there
+                } else {
+                    c.exact.line_no += cut.lines;
+                    // (a later line without a class field has the class of the line before it, wherever that line was counted)
+                    const uint8_t *e = cut.start + cut.bytes - 1, *b = e;
+                    while (b > cut.start && b[-1] != '\n') b--;
+                    c.exact.set_class_of(b, (size_t)(e - b));
+                }
+            }
+            cut.commit();
+        } else if (what == ChunkCutter::CHUNK) {
+            cut.commit();
+        }
+        tr.release(i);
+        if (eof || fallback_off >= 0 || c.exact.ended) break;
+    }
+    tr.close();
+    if (err || c.exact.ended) return err;
+    if (fallback_off >= 0) return kc_cpu(c, path, fallback_off, nullptr, 0);
+    if (!cut.carry.empty()) return kc_cpu(c, path, 0, cut.carry.data(), cut.carry.size());
+    return GS_OK;
+}
+
+}  // namespace
+
+extern "C" int gs_host_kraken_count_files(int device, const char *const *paths, int n_paths, const char *const *only_taxids, int n_only,
+                                          const char *csv_path, char *keys, int32_t key_stride, int64_t *counts, int64_t cap_rows, int64_t *n_rows,
+                                          gs_host_kraken_totals *totals) try {
+    if (!paths || n_paths < 0 || !n_rows || n_only < 0 || (n_only > 0 && !only_taxids)) return hfail(GS_E_INVALID, "NULL argument");
+    *n_rows = 0;
+    bool fast = true;
+    if (const char *e = getenv("GS_HOST_FAST")) fast = atoi(e) != 0;
+    int64_t max_taxids = (int64_t)1 << 18;
+    if (const char *e = getenv("GS_KRAKEN_MAX_TAXIDS")) max_taxids = std::max<long long>(1, atoll(e));
+    const double t_start = now_s();
+    KcCtx c;
+    KcGuard guard{c.kc};
+    c.exact.filtered = n_only > 0;
+    if (fast && gs_krakencount_create(&c.kc, device, max_taxids) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
+    std::map<std::string, KrakenRow> rows;
+    for (int f = 0; f < n_paths; f++) {
+        const std::string path(paths[f]);
+        c.exact.ended = false;  // every file is a stream of its own, all of them count into one table
+        c.exact.line_no = 0;
+        c.exact.forget_class();
+        const int kind = fast ? text_path_kind(path) : 0;
+        const int err = kind ? kc_device_file(c, path, kind == 2 || kind == 4) : kc_cpu(c, path, 0, nullptr, 0);
+        if (err) return err;
+    }
+    rows = c.exact.rows;
+    if (c.kc) {
+        int64_t n = 0;
+        if (gs_krakencount_fetch(c.kc, nullptr, nullptr, 0, &n) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
+        std::vector<int32_t> ids((size_t)n + 1);
+        std::vector<int64_t> cnt(3 * (size_t)n + 3);
+        if (gs_krakencount_fetch(c.kc, ids.data(), cnt.data(), n, &n) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
+        for (int64_t i = 0; i < n; i++) {  // a device row's key is its decimal string
+            KrakenRow &r = rows[std::to_string(ids[(size_t)i])];
+            r.reads += cnt[3 * (size_t)i];
+            r.kmers += cnt[3 * (size_t)i + 1];
+            r.kimr += cnt[3 * (size_t)i + 2];
+        }
+    }
+    if (n_only > 0) {
+        std::map<std::string, KrakenRow> kept;
+        for (int i = 0; i < n_only; i++) {
+            if (!only_taxids[i]) return hfail(GS_E_INVALID, "NULL tax id");
+            const auto it = rows.find(only_taxids[i]);
+            if (it != rows.end()) kept.insert(*it);
+        }
+        rows.swap(kept);
+    }
+    if (totals) {
+        totals->lines = c.exact.lines + c.dev_tot[0];
+        totals->counted_tokens = c.exact.counted + c.dev_tot[1];
+        totals->a_tokens = c.exact.a_tokens + c.dev_tot[2];
+        totals->long_lines = c.exact.long_lines + c.dev_tot[3];
+        totals->device_chunks = c.device_chunks;
+        totals->host_chunks = c.host_chunks;
+    }
+    *n_rows = (int64_t)rows.size();
+    size_t longest = 0;
+    for (const auto &kv : rows) longest = std::max(longest, kv.first.size());
+    std::vector<char> k2;
+    std::vector<int64_t> c2;
+    const int32_t stride = (int32_t)longest + 1;
+    if (csv_path) {
+        k2.assign(rows.size() * (size_t)stride + 1, 0);
+        c2.reserve(3 * rows.size() + 3);
+        size_t i = 0;
+        for (const auto &kv : rows) {
+            memcpy(k2.data() + i++ * (size_t)stride, kv.first.data(), kv.first.size());
+            c2.insert(c2.end(), {kv.second.reads, kv.second.kmers, kv.second.kimr});
+        }
+        const int err = gs_host_write_kraken_csv(csv_path, k2.data(), stride, c2.data(), (int64_t)rows.size());
+        if (err) return err;
+    }
+    if (totals) totals->seconds_total = now_s() - t_start;
+    if (cap_rows < *n_rows || (!rows.empty() && (!keys || !counts || (size_t)key_stride <= longest)))
+        return hfail(GS_E_INVALID, "no room for " + std::to_string((long long)*n_rows) + " rows with keys of up to " + std::to_string(longest) + " bytes");
+    size_t i = 0;
+    for (const auto &kv : rows) {
+        char *k = keys + i * (size_t)key_stride;
+        memset(k, 0, (size_t)key_stride);
+        memcpy(k, kv.first.data(), kv.first.size());
+        counts[3 * i] = kv.second.reads;
+        counts[3 * i + 1] = kv.second.kmers;
+        counts[3 * i + 2] = kv.second.kimr;
+        i++;
+    }
+    return GS_OK;
 } catch (const std::bad_alloc &) {
     return hfail(GS_E_NOMEM, "out of host memory");
 } catch (const std::exception &e) {

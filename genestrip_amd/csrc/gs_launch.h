@@ -137,6 +137,10 @@ hipError_t gs_launch_scan_blocks(u64 *blocks, int64_t n_blocks, u64 *total_out, 
 hipError_t gs_launch_kraken_size(const GsKrakenParams *P, hipStream_t stream);
 hipError_t gs_launch_kraken_write(const GsKrakenParams *P, hipStream_t stream);
 
+// ---- gs_krakencount.hip: Kraken-style lines counted per tax id
+hipError_t gs_launch_krakencount(const GsKrakenCountParams *P, hipStream_t stream);
+hipError_t gs_launch_krakencount_reset(const GsKrakenCountParams *P, hipStream_t stream);
+
 // ---- gs_merge.hip: merge of runs that live in one process
 hipError_t gs_launch_merge_i64(void *dst, const void *src, int64_t n, int op, hipStream_t stream);
 hipError_t gs_launch_merge_f64(void *dst, const void *src, int64_t n, hipStream_t stream);

@@ -284,3 +284,44 @@ struct GsRouteParams {
     uint32_t *send_idx;
     int32_t *nodes;                // per k-mer position: node of the positions that are not routed
 };
+
+// ---- gs_krakencount.hip: Kraken-style lines counted per tax id (the krakencount goal)
+#define GS_KC_TILE 4096        // bytes per scan block: GS_SCAN_BLOCK threads, 16 bytes each
+#define GS_KC_GROUP 8          // scan blocks per workgroup of the accumulation: its LDS table is flushed once per GS_KC_TILE * GS_KC_GROUP bytes
+#define GS_KC_LDS_SLOTS 512    // slots of that table (28 bytes each)
+#define GS_KC_LDS_PROBES 32    // a key that finds no slot within this many steps goes straight to the global table
+#define GS_KC_EMPTY 0xffffffffu  // no key (accepted tax ids have at most 9 digits), no line
+#define GS_KC_LONG_LINE 65536  // bytes incl. the newline beyond which KrakenResultProcessor (a line buffer of 65 536) fails
+enum { GS_KC_READS = 0, GS_KC_KMERS = 1, GS_KC_KIMR = 2 };  // the three counters of a row, in the order of the CSV
+// chunk status words: reset by the finish kernel for the next chunk
+enum { GS_KC_BAD_LINE = 0,    // first line outside the grammar (GS_KC_EMPTY: none)
+       GS_KC_EMPTY_LINE = 1,  // first empty line ...
+       GS_KC_EMPTY_OFF = 2,   // ... and its byte offset
+       GS_KC_FULL = 3,        // the table cannot take the chunk's new tax ids
+       GS_KC_WORDS = 4 };
+// what the finish kernel reports per chunk
+enum { GS_KC_R_REFUSED = 0,   // 0: counted; 1: outside the grammar; 2: table full
+       GS_KC_R_BAD_LINE = 1, GS_KC_R_EMPTY_OFF = 2, GS_KC_R_ROWS = 3,  // (~0: none); rows of the table
+       GS_KC_R_CHUNK = 4,     // [4] lines, counted tokens, 'A' tokens, long lines of this chunk (zeros if refused)
+       GS_KC_R_RUN = 8,       // [4] the same since the last reset
+       GS_KC_R_WORDS = 12 };
+struct GsKrakenCountParams {
+    const uint8_t *text;      // n_bytes of whole lines, zero bytes behind them up to n_tiles * GS_KC_TILE + 64
+    int64_t n_bytes, n_tiles;
+    unsigned long long *tile_lt;  // per scan block: newlines | tabs << 32, then their exclusive prefix (gs_launch_scan_blocks)
+    unsigned long long *tile_c;   // the same for token candidates (a digit behind a blank or a tab)
+    unsigned long long *scan_tot; // [2] the sums
+    uint32_t *line_end;       // per line (line_cap of them): offset of its newline ...
+    uint32_t *line_c4;        // ... candidates in front of its fourth tab ...
+    uint32_t *line_key;       // ... and its class tax id
+    int64_t line_cap;
+    uint32_t *status;         // GS_KC_WORDS
+    unsigned long long *chunk_tot, *run_tot;  // lines, counted tokens, 'A' tokens, long lines (chunk_tot: and the two of `counters`)
+    uint32_t *keys;           // the table: n_slots keys (GS_KC_EMPTY: free), open addressing, linear probing
+    uint32_t *present;        // 1: the row exists; 0 with a key: claimed by the chunk under way
+    unsigned long long *acc, *delta;  // 3 counters per slot: the committed rows, what the chunk under way adds
+    uint32_t n_slots, slot_bits, max_keys, pad;
+    uint32_t *n_keys;         // [0] rows committed [1] rows committed + claimed
+    unsigned long long *counters;  // [0] global atomics of the accumulation [1] tokens whose key went straight to the global table
+    unsigned long long *result;    // GS_KC_R_WORDS
+};

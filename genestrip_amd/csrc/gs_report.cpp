@@ -326,3 +326,24 @@ extern "C" int gs_host_write_quality_csv(const char *path, const gs_host_tax_inf
 } catch (const std::exception &e) {  // (nothing may leave through the C ABI)
     return hfail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
 }
+
+// KrakenResFileGoal.print (C/goals/kraken/KrakenResFileGoal.java:95-107)
+extern "C" int gs_host_write_kraken_csv(const char *path, const char *keys, int32_t key_stride, const int64_t *counts, int64_t n_rows) try {
+    if (!path || n_rows < 0 || (n_rows > 0 && (!keys || !counts || key_stride < 1))) return hfail(GS_E_INVALID, "NULL argument");
+    OutFile f;
+    if (!f.open(path)) return hfail(GS_E_IO, std::string("cannot open ") + path);
+    std::string o = "taxid;reads;kmers;kmers in matching reads\n";
+    for (int64_t i = 0; i < n_rows; i++) {
+        const char *k = keys + (size_t)i * key_stride;
+        o.append(k, strnlen(k, (size_t)key_stride));
+        for (int j = 0; j < 3; j++) o += ';' + std::to_string((long long)counts[3 * i + j]);
+        o += ";\n";
+    }
+    f.write(o.data(), o.size());
+    if (!f.close()) return hfail(GS_E_IO, std::string("short write to ") + path);
+    return GS_OK;
+} catch (const std::bad_alloc &) {
+    return hfail(GS_E_NOMEM, "out of host memory");
+} catch (const std::exception &e) {
+    return hfail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
+}

@@ -58,6 +58,8 @@ def lib():
         "gs_host_fasta2fastq": (ci, [ci, vp, ci, C.c_char_p, vp]),
         "gs_host_write_csv": (ci, [C.c_char_p, vp, vp, vp, vp]),
         "gs_host_write_quality_csv": (ci, [C.c_char_p, vp, vp, vp]),
+        "gs_host_kraken_count_files": (ci, [ci, vp, ci, vp, ci, C.c_char_p, vp, C.c_int32, vp, i64, vp, vp]),
+        "gs_host_write_kraken_csv": (ci, [C.c_char_p, vp, C.c_int32, vp, i64]),
         "gs_host_db2fastq": (ci, [vp, vp, C.c_char_p, C.c_int32, ci, C.c_char_p, vp]),
         "gs_host_last_error": (C.c_char_p, []), "gs_host_java_double": (ci, [C.c_double, vp, ci]),
         "gs_host_gunzip": (ci, [vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]),
@@ -159,7 +161,8 @@ def match_files(store, paths, config=None, filtered_path=None, kraken_out_path=N
 def stat(which=0):
     """gs_host_stat: 0 = chunks that went through the general (multi-line) FASTQ device path in this process so far; 1 = FASTA / general
     FASTQ chunks the filter goal handled on the device; 2 = four-line chunks whose Kraken-style lines were written on the device; 3 = FASTA /
-    general FASTQ chunks of any goal whose per-read output was written on the device (GS_DEVICE_RECORDS=0 keeps them on the host)"""
+    general FASTQ chunks of any goal whose per-read output was written on the device (GS_DEVICE_RECORDS=0 keeps them on the host); 5 = chunks
+    of Kraken-style lines that kraken_count_files counted on the device"""
     return int(lib().gs_host_stat(which))
 
 
@@ -288,3 +291,47 @@ def java_double(v):
     buf = C.create_string_buffer(64)
     _check(lib().gs_host_java_double(float(v), buf, 64))
     return buf.value.decode()
+
+
+class KrakenTotals(C.Structure):
+    _fields_ = [("lines", C.c_int64), ("counted_tokens", C.c_int64), ("a_tokens", C.c_int64), ("long_lines", C.c_int64),
+                ("device_chunks", C.c_int64), ("host_chunks", C.c_int64), ("seconds_total", C.c_double)]
+
+
+_KRAKEN_KEY_STRIDE = 24
+
+
+def kraken_count_files(paths, only=None, csv=None, device=0):
+    """The krakencount goal over Kraken-style output files (plain or gzip; ours, Kraken's, KrakenUniq's), all into one table:
+    (rows, totals) with rows = [(tax id bytes, reads, kmers, kmers in matching reads)] in the reference's order.  only: keep the rows
+    of these tax ids; csv: also write the krakenres CSV there (.gz: gzip).  Chunks of whole lines are counted on the device, what it
+    refuses by a line-by-line restatement of the reference; GS_HOST_FAST=0 sends everything through the latter."""
+    parr = _cstr_array([os.fspath(p) for p in paths])
+    oarr = _cstr_array(list(only)) if only is not None else None
+    tot = KrakenTotals()
+    n = C.c_int64(0)
+    cap, stride = 1 << 12, _KRAKEN_KEY_STRIDE
+    csv_b = None if csv is None else os.fspath(csv).encode()
+    while True:
+        keys = np.zeros((cap, stride), dtype=np.uint8)
+        cnt = np.zeros((cap, 3), dtype=np.int64)
+        rc = lib().gs_host_kraken_count_files(int(device), parr, len(paths), oarr, 0 if only is None else len(oarr), csv_b,
+                                              keys.ctypes.data_as(C.c_void_p), stride, cnt.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(tot))
+        if rc != 0 and n.value > 0 and (n.value > cap or stride < 4096) and b"no room" in (lib().gs_host_last_error() or b""):
+            cap, stride = max(cap, n.value), (stride if n.value > cap else stride * 16)  # (more rows than guessed, or very long keys)
+            continue
+        _check(rc)
+        break
+    rows = [(bytes(keys[i]).split(b"\0", 1)[0], int(cnt[i, 0]), int(cnt[i, 1]), int(cnt[i, 2])) for i in range(n.value)]
+    return rows, {f: getattr(tot, f) for f, _ in KrakenTotals._fields_}
+
+
+def write_kraken_csv(path, rows):
+    """taxid;reads;kmers;kmers in matching reads -- the krakenres file of rows as kraken_count_files returns them"""
+    stride = max([len(r[0]) for r in rows] + [0]) + 1
+    keys = np.zeros((max(len(rows), 1), stride), dtype=np.uint8)
+    cnt = np.zeros((max(len(rows), 1), 3), dtype=np.int64)
+    for i, (k, *v) in enumerate(rows):
+        keys[i, :len(k)] = np.frombuffer(bytes(k), dtype=np.uint8)
+        cnt[i] = v
+    _check(lib().gs_host_write_kraken_csv(os.fspath(path).encode(), keys.ctypes.data_as(C.c_void_p), stride, cnt.ctypes.data_as(C.c_void_p), len(rows)))

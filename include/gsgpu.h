@@ -949,6 +949,46 @@ enum {
 };
 int gs_calibrate(int device, int what, int64_t arg, double out[4]);
 
+/* ---------------------------------------------------------------------------------------------------
+ * krakencount: Kraken-style output lines counted per tax id (genestrip_amd/csrc/gs_krakencount.hip)
+ *
+ * Replaces KrakenResultProcessor.process (C/kraken/KrakenResultProcessor.java:74-179) under the listener of KrakenResCountGoal
+ * (C/goals/kraken/KrakenResCountGoal.java:133-157) for chunks of whole lines inside the grammar stated at the head of
+ * gs_krakencount.hip.  A chunk outside it -- or one whose new tax ids the table cannot take -- is REFUSED: it adds nothing, the
+ * caller counts it with the reference-exact parser (include/gshost.h).  A refusal is not sticky: the next chunk is taken on its
+ * own merits.  An empty line is no refusal: the lines in front of it count, the chunk reports its byte offset (the reference stops
+ * reading there).  Deliberate difference: a line of more than 65 536 bytes with its newline makes the reference fail (array
+ * index); here it counts like any other and is reported in the long-lines total.
+ *
+ * A handle owns its stream, its staging and its table of up to max_taxids rows (open addressing over the tax id as uint32).
+ * gs_krakencount_geometry: [0] bytes per tile (one workgroup, one flush of its LDS table), [1] slots of that LDS table, [2] slots
+ * of the global table, [3] the highest level of the prefix sums in use (1: inside a scan block, 2: one thread per block sum,
+ * 3: a run of block sums per thread), [4] bytes per scan block, [5] scan blocks from which level 3 is in play.
+ * gs_krakencount_submit: text = n_bytes (at most 1 GiB) of whole lines, the last byte a newline; mem: GS_MEM_HOST (free again on
+ * return) or GS_MEM_DEVICE (free again after the next synchronising call).  *ticket: 0, 1, ... in submission order.
+ * gs_krakencount_chunk: what became of one of the last 64 chunks: [0] 0 counted / 1 outside the grammar / 2 table full, [1] its
+ * first bad line (0-based, -1: none), [2] the offset of its first empty line (-1), [3] rows of the table behind it, [4..7] its
+ * lines, counted tokens, skipped 'A' tokens, long lines.  Synchronises, as do _status, _fetch, _counters and _kernel_time.
+ * gs_krakencount_status: the first refused chunk since the last reset (-1: none) and its first bad line (-1 for a full table),
+ * the first-empty-line offset of the most recent chunk, totals = lines, counted tokens, skipped 'A' tokens, long lines.
+ * gs_krakencount_fetch: *n_rows rows (all of them are written if cap >= *n_rows, else none) in the order of DigitTrie.collect
+ * (C/util/DigitTrie.java:294-305) over the decimal strings; counts[3 * i ..] = reads, kmers, kmers in matching reads.
+ * gs_krakencount_counters: [0] global atomics issued by the accumulation, [1] tokens whose key found no room in a workgroup's table.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct gs_krakencount gs_krakencount;
+int gs_krakencount_create(gs_krakencount **out, int device, int64_t max_taxids);
+int gs_krakencount_destroy(gs_krakencount *kc);
+int gs_krakencount_get_device(gs_krakencount *kc, int *device);
+int gs_krakencount_geometry(gs_krakencount *kc, int64_t geometry[6]);
+int gs_krakencount_submit(gs_krakencount *kc, const uint8_t *text, int64_t n_bytes, int mem, int64_t *ticket);
+int gs_krakencount_chunk(gs_krakencount *kc, int64_t ticket, int64_t report[8]);
+int gs_krakencount_status(gs_krakencount *kc, int64_t *failed_ticket, int64_t *first_bad_line, int64_t *first_empty_offset, int64_t totals[4]);
+int gs_krakencount_reset(gs_krakencount *kc);
+int gs_krakencount_fetch(gs_krakencount *kc, int32_t *taxids, int64_t *counts, int64_t cap, int64_t *n_rows);
+int gs_krakencount_counters(gs_krakencount *kc, int64_t counters[2]);
+/* profile != 0: from now on the kernels of every chunk run between events; launches / total_ms: what they add up to so far */
+int gs_krakencount_kernel_time(gs_krakencount *kc, int profile, int64_t *launches, double *total_ms);
+
 #ifdef __cplusplus
 }
 #endif

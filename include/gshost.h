@@ -13,6 +13,7 @@
  *   gs_host_filter_files  FastqBloomFilter.runFilter (C/bloom/FastqBloomFilter.java:80-105)
  *   gs_host_write_csv     MatchingResult.completeResults + ResultReporter.printMatchResult
  *                         (C/match/MatchingResult.java:84-118, C/match/ResultReporter.java:190-279)
+ *   gs_host_kraken_count_files  the krakencount goal: Kraken-style output files -> reads / k-mers per tax id
  *   gs_host_write_quality_csv  the dbquality goal's CSV (DBQualityCountsGoal's rank aggregation + DBQualityCSVGoal.makeFile)
  * (C/ = core/src/main/java/org/metagene/genestrip/, B/ = base/src/main/java/org/metagene/genestrip/)
  */
@@ -105,7 +106,7 @@ int gs_host_match_files_multi(gs_db *const *dbs, int n_dbs, const gs_match_cfg *
  * Kraken-style lines were written on the device (gs_match_kraken_text; GS_DEVICE_KRAKEN=0 keeps them on the host; four-line chunks
  * only); 3: FASTA / general FASTQ chunks of any goal (match, filter, extract) whose per-read output -- filtered file, accepted / rest
  * file, selected records, Kraken-style lines -- was written on the device (gs_*_compact_records, gs_match_kraken_records;
- * GS_DEVICE_RECORDS=0 keeps them on the host) */
+ * GS_DEVICE_RECORDS=0 keeps them on the host); 5: chunks of Kraken-style lines that gs_host_kraken_count_files counted on the device (4 is no counter: -1) */
 int64_t gs_host_stat(int which);
 
 /* ---- runFilter: accepted reads -> filtered_path, the rest -> rest_path (either may be NULL); with_probs as above ---- */
@@ -169,6 +170,31 @@ int gs_host_write_csv(const char *path, const gs_host_tax_info *tax, const int64
  * (tp+fp), tp / (tp+fn)), the columns named weighted avg ... hold tp / (tp+fp) and tp / (tp+fn) of the added counts.  Of `tax`
  * only n_values, parent_vi, position, taxids, names and ranks are read. ---- */
 int gs_host_write_quality_csv(const char *path, const gs_host_tax_info *tax, const int64_t *counts, const uint8_t *present);
+
+/* ---- krakencount / krakenres (C/goals/kraken/KrakenResCountGoal.java:133-157 over C/kraken/KrakenResultProcessor.java:74-179;
+ * the CSV of C/goals/kraken/KrakenResFileGoal.java:95-107): per tax id of Kraken-style output files -- ours, Kraken's,
+ * KrakenUniq's -- the reads, the k-mers and the k-mers in matching reads.  Each file (plain or gzip, BGZF included) is one stream
+ * under the reference's rules: it ends at its first empty line, an unterminated last line loses its last byte; all files go into
+ * one table.  Chunks of whole lines are counted on the device (gs_krakencount); a chunk it refuses, the unterminated tail of a
+ * file, a line that does not fit a block and everything under GS_HOST_FAST=0 (no device is used then) go through a line-by-line
+ * restatement of the reference (genestrip_amd/csrc/gs_krakenparse.h); both give the same rows for every file.
+ * only_taxids (n_only > 0): rows of other keys are dropped, as by the goal's tax id set.
+ * Rows come in the order of DigitTrie.collect: keys[i * key_stride ..] NUL-terminated, counts[3 * i ..] = reads, kmers, kmers in
+ * matching reads.  *n_rows is always set; rows are written if cap_rows >= *n_rows and every key fits key_stride, else the call
+ * fails with GS_E_INVALID after the CSV (csv_path != NULL: gs_host_write_kraken_csv) has been written.
+ * Two deliberate differences: a line of more than 65 536 bytes with its newline (the reference fails: array index) counts like any
+ * other and is reported in long_lines; where the reference throws -- a non-digit in a count, a read size or a class -- the call
+ * fails with GS_E_INVALID, gs_host_last_error() names the file and the 1-based line, and nothing is written. ---- */
+typedef struct {
+    int64_t lines, counted_tokens, a_tokens, long_lines;  /* lines read; tokens counted; 'A' tokens skipped; lines > 65 536 bytes */
+    int64_t device_chunks, host_chunks;                   /* chunks the device counted; chunks and tails the line-by-line loop took */
+    double seconds_total;
+} gs_host_kraken_totals;
+int gs_host_kraken_count_files(int device, const char *const *paths, int n_paths, const char *const *only_taxids, int n_only,
+                               const char *csv_path, char *keys, int32_t key_stride, int64_t *counts, int64_t cap_rows, int64_t *n_rows,
+                               gs_host_kraken_totals *totals);
+/* taxid;reads;kmers;kmers in matching reads -- then key;reads;kmers;kimr; per row, '\n' line ends; .gz / .gzip: gzip */
+int gs_host_write_kraken_csv(const char *path, const char *keys, int32_t key_stride, const int64_t *counts, int64_t n_rows);
 
 /* The host layer keeps page-locked blocks and the device decoders of gzip input (gigabytes of HBM) from call to call; this hands
  * them back (a long-lived JVM host before it loads a big store).  No other thread may be inside the host layer meanwhile. */
