@@ -1205,6 +1205,7 @@ __device__ bool gi_header_plausible(const uint8_t *in, uint32_t in_len, u64 o, u
 // (The first version: sieves 1 + 2 in one step for every offset, from memory, and gi_dynamic_header for each of the ~40 survivors
 // per chunk, up to the chunk's first block start only: 5.9 ms for 4 096 chunks of 58 KB.  This one reads the whole stream.)
 #define GI_FIND_MAX 16
+#define GI_MIRAGE_ROUNDS 64  // rounds of segments decoded on behind a false block start, per batch (gs_gunzipper_next)
 #define GI_FIND_LAUNCHES 64  // finder launches per batch at most (each has a work counter of its own; what is left when they are used up goes into the last one)
 __global__ __launch_bounds__(64 * GI_WAVES) __attribute__((amdgpu_waves_per_eu(5, 5))) void gi_find_kernel(const uint8_t *in, uint32_t in_len, uint32_t chunk_bytes,
                                                                                                         int64_t first, int64_t n_chunks, u64 *start_bit, unsigned long long *next_chunk,
@@ -2540,13 +2541,17 @@ extern "C" int gs_gunzipper_next(gs_gunzipper *g, int64_t keep_tail, const uint8
     u64 sym_used = sym_total;
     const u64 sym_room = sym_total + sym_total / 8 + ((u64)64 << 20);  // slack for segments that are decoded again (mirages, below)
     if ((rc = gu_grow(&g->d_sym, &g->sym_cap, (size_t)sym_room + 64, 0))) return rc;
-    if (g->seg_cap < (size_t)n_segs) {
+    auto seg_room = [&](size_t n) -> int {  // the per-segment arrays for n segments (their contents are not kept: every user uploads its own)
+        if (g->seg_cap >= n) return GS_OK;
         size_t c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0;
-        if ((rc = gu_grow(&g->d_segs, &c1, (size_t)n_segs)) || (rc = gu_grow(&g->d_status, &c2, (size_t)n_segs)) || (rc = gu_grow(&g->d_len, &c3, (size_t)n_segs)) ||
-            (rc = gu_grow(&g->d_end, &c4, (size_t)n_segs)) || (rc = gu_grow(&g->d_off, &c5, (size_t)n_segs)))
-            return rc;
+        int r;
+        if ((r = gu_grow(&g->d_segs, &c1, n)) || (r = gu_grow(&g->d_status, &c2, n)) || (r = gu_grow(&g->d_len, &c3, n)) || (r = gu_grow(&g->d_end, &c4, n)) ||
+            (r = gu_grow(&g->d_off, &c5, n)))
+            return r;
         g->seg_cap = std::min(std::min(c1, c2), std::min(std::min(c3, c4), c5));
-    }
+        return GS_OK;
+    };
+    if ((rc = seg_room((size_t)n_segs))) return rc;
     GI_TRY(hipMemcpy(g->d_segs, segs.data(), sizeof(GiSeg) * (size_t)n_segs, hipMemcpyHostToDevice));
     GI_TRY(hipMemset(g->d_q + 1, 0, sizeof(u64)));
     hipLaunchKernelGGL(gi_segment_kernel, dim3((unsigned)std::min<int64_t>((n_segs + GI_WAVES - 1) / GI_WAVES, wgs)), dim3(64 * GI_WAVES), 0, 0, d_in, in_len, g->d_segs,
@@ -2560,11 +2565,16 @@ extern "C" int gs_gunzipper_next(gs_gunzipper *g, int64_t keep_tail, const uint8
     GI_TRY(hipMemcpy(endb.data(), g->d_end, sizeof(u64) * (size_t)n_segs, hipMemcpyDeviceToHost));
     const double t_seg = gi_now_ms();
     // A block start that was a mirage (a bit pattern that parses as a complete dynamic header: about one per 100 MB of compressed
-    // data without the text test) shows as the segment IN FRONT of it running past it: that segment is decoded again up to the start
-    // after the mirage, into the slack behind the symbols (the mirage's own segment is dropped); for the batch's last segment the
-    // next of the starts behind the batch takes the mirage's place.  A few rounds: two mirages may follow each other.
+    // data without the text test; every block of a gzip file that lies inside the stored blocks of another) shows as the segment IN
+    // FRONT of it running past it, to the first real block boundary behind it.  That segment's text is good as it stands: it ends
+    // where it stopped, the segments that start in front of that boundary are dropped, and -- unless one starts exactly there -- a new
+    // segment is decoded from the boundary to the next start that was found, into the slack behind the symbols.  Behind the batch's
+    // last segment the batch simply ends at that boundary (in the stream's last batch the starts found behind the segments, then the
+    // final block, take the place of the next segment).  One round per mirage that follows another inside the new segments (a stored
+    // block full of them: one round per stored block); a batch that needs more than GI_MIRAGE_ROUNDS goes to the host decoders.
+    // Whatever is kept in the end is a chain from the batch's first block: every segment ended exactly where the next one starts.
     bool member_end = false;
-    for (int round = 0; round < 6; round++) {
+    for (int round = 0; round < GI_MIRAGE_ROUNDS; round++) {
         {   // the member's final block inside a segment (another member follows): that segment is the last one -- once nothing in front
             // of it is in doubt; what the batch decoded behind it belongs to the next member and is decoded again from its first block
             size_t f = segs.size(), y = segs.size();
@@ -2587,34 +2597,57 @@ extern "C" int gs_gunzipper_next(gs_gunzipper *g, int64_t keep_tail, const uint8
         std::vector<int32_t> kst;
         std::vector<uint32_t> klen;
         std::vector<u64> kend;
+        bool ended_early = false;  // a segment was taken as it ended without anything to decode behind it
         for (size_t i = 0; i < segs.size(); i++) {
-            const bool is_last = i + 1 == segs.size();
-            if (st[i] == GI_E_SYNC && !member_end && (!is_last || (!segs[i].to_final && (stop_at + 1 < stops.size() || to_end)))) {
-                GiSeg m = segs[i];
-                u64 cap = m.out_cap;
-                if (!is_last) {
-                    const GiSeg &gone = segs[i + 1];
-                    m.stop_bit = gone.stop_bit;
-                    m.to_final = gone.to_final;
-                    cap += gone.out_cap;
-                } else {
-                    stop_at++;
-                    m.to_final = stop_at >= stops.size();
-                    m.stop_bit = m.to_final ? 0 : stops[stop_at];
-                }
-                if (cap > 0xffff0000ull || sym_used + GI_WINDOW + cap > sym_room) return gi_fail(GS_E_UNSUPPORTED, "no room to decode a segment again: host decoders");
-                m.out_cap = (uint32_t)cap;
-                sym_used += GI_WINDOW;
-                m.out_off = sym_used;
-                sym_used += cap;
-                redo.push_back(m);
-                redo_at.push_back(kept.size());
-                kept.push_back(m);
+            if (st[i] == GI_E_SYNC && !member_end && !segs[i].to_final && endb[i] > segs[i].stop_bit) {
+                const u64 at = endb[i];  // a block boundary: the first one at or behind the start the segment was to stop at
+                GiSeg done_seg = segs[i];
+                done_seg.stop_bit = at;
+                kept.push_back(done_seg);
                 kst.push_back(GI_OK);
-                klen.push_back(0);
-                kend.push_back(0);
-                g->n_mirages++;
-                if (!is_last) i++;  // (the segment behind the mirage is gone)
+                klen.push_back(len[i]);
+                kend.push_back(at);
+                size_t j = i + 1;
+                while (j < segs.size() && segs[j].start_bit < at) j++;  // (the mirages' own segments are gone)
+                g->n_mirages += (int64_t)(j - i - 1);
+                GiSeg m{};
+                m.start_bit = at;
+                bool more = true;
+                if (j < segs.size()) {
+                    m.stop_bit = segs[j].start_bit;
+                    more = m.stop_bit != at;
+                } else {
+                    while (stop_at < stops.size() && stops[stop_at] < at) {
+                        stop_at++;
+                        g->n_mirages++;
+                    }
+                    if (!to_end)
+                        // the batch ends here and the next one starts at this boundary: a segment from here to a start found behind the
+                        // batch may have to run on beyond the bytes the batch holds (a mirage in the last stored block of its span)
+                        more = false;
+                    else if (stop_at < stops.size()) {
+                        m.stop_bit = stops[stop_at];
+                        more = m.stop_bit != at;
+                    } else
+                        m.to_final = 1;
+                }
+                if (more) {
+                    const u64 end = m.to_final ? (u64)in_len * 8u : m.stop_bit;
+                    const u64 cap = (((end - at) / 8u + 1u) * g->ratio + 65536u + 7u) & ~(u64)7;
+                    if (cap > 0xffff0000ull || sym_used + GI_WINDOW + cap > sym_room) return gi_fail(GS_E_UNSUPPORTED, "no room to decode on behind a false block start: host decoders");
+                    m.out_cap = (uint32_t)cap;
+                    sym_used += GI_WINDOW;
+                    m.out_off = sym_used;
+                    sym_used += cap;
+                    redo.push_back(m);
+                    redo_at.push_back(kept.size());
+                    kept.push_back(m);
+                    kst.push_back(GI_OK);
+                    klen.push_back(0);
+                    kend.push_back(0);
+                } else
+                    ended_early = true;
+                i = j - 1;  // (the loop goes on behind the dropped segments)
             } else if (st[i] == GI_E_OVERRUN && (u64)segs[i].out_cap * 8u <= 0xffff0000ull && sym_used + GI_WINDOW + (u64)segs[i].out_cap * 8u <= sym_room) {
                 // a segment that expands more than the room it was given (a run of one base, of one quality): once more with eight times the room
                 GiSeg m = segs[i];
@@ -2635,8 +2668,17 @@ extern "C" int gs_gunzipper_next(gs_gunzipper *g, int64_t keep_tail, const uint8
                 kend.push_back(endb[i]);
             }
         }
-        if (redo.empty()) break;
+        if (redo.empty()) {
+            if (kept.size() != segs.size() || ended_early) {  // (segments were dropped or end elsewhere, nothing is left to decode)
+                segs.swap(kept);
+                st.swap(kst);
+                len.swap(klen);
+                endb.swap(kend);
+            }
+            break;
+        }
         const int64_t n_redo = (int64_t)redo.size();
+        if ((rc = seg_room(kept.size()))) return rc;  // (a segment that ran past a mirage has become two)
         GI_TRY(hipMemcpy(g->d_segs, redo.data(), sizeof(GiSeg) * (size_t)n_redo, hipMemcpyHostToDevice));  // (the master copy goes back below)
         GI_TRY(hipMemset(g->d_q + 1, 0, sizeof(u64)));
         hipLaunchKernelGGL(gi_segment_kernel, dim3((unsigned)std::min<int64_t>((n_redo + GI_WAVES - 1) / GI_WAVES, wgs)), dim3(64 * GI_WAVES), 0, 0, d_in, in_len, g->d_segs,
@@ -2659,6 +2701,7 @@ extern "C" int gs_gunzipper_next(gs_gunzipper *g, int64_t keep_tail, const uint8
         endb.swap(kend);
     }
     const int64_t n_fin = (int64_t)segs.size();
+    if ((rc = seg_room((size_t)n_fin))) return rc;
     GI_TRY(hipMemcpy(g->d_segs, segs.data(), sizeof(GiSeg) * (size_t)n_fin, hipMemcpyHostToDevice));
     GI_TRY(hipMemcpy(g->d_len, len.data(), sizeof(uint32_t) * (size_t)n_fin, hipMemcpyHostToDevice));
     std::vector<u64> off((size_t)n_fin + 1, 0);

@@ -1,8 +1,12 @@
 // Sanitizer harness for the gzip decoders of the ingest path (tests/test_host_cpu.py builds it with -fsanitize=thread
 // and with -fsanitize=address,undefined): several decodes with different thread counts and chunkings, plus a decoder that
-// is abandoned in the middle of the stream.
+// is abandoned in the middle of the stream.  With arguments -- pairs of files, a gzip stream and its text ("-": a damaged stream that
+// must be refused) -- it decodes those instead (tests/test_inflate_cases_cpu.py: streams that zlib does not write).
 #include "../../genestrip_amd/csrc/gs_inflate.h"
+#include <algorithm>
 #include <cstdio>
+#include <cstring>
+#include <memory>
 #include <vector>
 #include <random>
 #include <string>
@@ -18,7 +22,18 @@ static std::vector<uint8_t> bgzf(const std::vector<uint8_t>&in){ std::vector<uin
     for(int i=0;i<4;i++)out.push_back((uint8_t)(crc>>(8*i))); for(int i=0;i<4;i++)out.push_back((uint8_t)(isz>>(8*i)));
     if(n==0)break; }
   return out;}
-int main(){ auto in=fastq(6000000,1); auto c=gz(in,6); int fails=0;
+static std::vector<uint8_t> slurp(const char*path){ std::vector<uint8_t> v; FILE*f=fopen(path,"rb"); if(!f)return v; uint8_t b[65536]; size_t n; while((n=fread(b,1,sizeof b,f))>0)v.insert(v.end(),b,b+n); fclose(f); return v;}
+// one stream from a file through the serial decoder (small and large output blocks) and the parallel one (1 and 3 threads, two chunk sizes)
+static int from_file(const char*gz_path,const char*text_path){ const bool bad=!strcmp(text_path,"-"); auto c=slurp(gz_path); std::vector<uint8_t> want; if(!bad)want=slurp(text_path); int fails=0; if(c.empty())return 1;
+  for(size_t block:{333ul,70000ul}){ std::unique_ptr<GsInflate> inf(new GsInflate()); inf->init(c.data(),c.size(),true); std::vector<uint8_t> out(want.size()+70000); size_t total=0; bool ok=false;
+    for(;;){ size_t p=0; const size_t room=std::min(block,out.size()-total); auto st=inf->decode(out.data()+total,room,total,&p); total+=p; if(st==GsInflate::CORRUPT)break; if(st==GsInflate::DONE){ok=true;break;} if(room==0)break; }
+    out.resize(total); if(bad?ok:(!ok||out!=want))fails++; }
+  for(int threads:{1,3}) for(size_t chunk:{4096ul,65536ul}){ GsParallelGunzip pg; pg.start(c.data(),c.size(),threads,chunk); std::vector<uint8_t> got,buf(50000); bool done=false,ok=true; while(!done){size_t p=0; if(!pg.read(buf.data(),buf.size(),&p,nullptr,&done)){ok=false;break;} got.insert(got.end(),buf.begin(),buf.begin()+p); if(got.size()>want.size()+(1u<<20)){ok=false;break;}}
+    if(bad?ok:(!ok||got!=want))fails++; }
+  return fails; }
+int main(int argc,char**argv){
+  if(argc>1){ int fails=0; for(int i=1;i+1<argc;i+=2){ const int f=from_file(argv[i],argv[i+1]); if(f)printf("%s: %d\n",argv[i],f); fails+=f; } printf("fails %d\n",fails); return fails; }
+  auto in=fastq(6000000,1); auto c=gz(in,6); int fails=0;
   { auto b=bgzf(in); for(int threads:{1,3,8}) for(size_t room:{200000ul,65536ul,70001ul}){ GsBgzfReader br(b.data(),b.size(),threads); std::vector<uint8_t> got,buf(room); bool done=false; while(!done){size_t p=0; if(!br.read(buf.data(),buf.size(),&p,&done)){fails++;break;} got.insert(got.end(),buf.begin(),buf.begin()+p);} if(got!=in||br.rest_offset()!=b.size())fails++; } }
   for(int rep=0;rep<3;rep++) for(int threads:{2,5}) for(size_t chunk:{65536ul,300000ul}){ GsParallelGunzip pg; pg.start(c.data(),c.size(),threads,chunk); std::vector<uint8_t> got,buf(200000); bool done=false; while(!done){size_t p=0; if(!pg.read(buf.data(),buf.size(),&p,nullptr,&done)){fails++;break;} got.insert(got.end(),buf.begin(),buf.begin()+p);} if(got!=in)fails++; }
   { GsParallelGunzip pg; pg.start(c.data(),c.size(),4,65536); std::vector<uint8_t> buf(100000); size_t p; bool done; pg.read(buf.data(),buf.size(),&p,nullptr,&done); /* abandon mid-stream: destructor must stop cleanly */ }

@@ -577,10 +577,11 @@ def _tool(name):
     return mod
 
 
-@pytest.mark.parametrize("mode", ["", "bgzf"])
+@pytest.mark.parametrize("mode", ["", "bgzf", "foreign"])
 def test_randomised_streams_equal_zlib(mode):
     """a short run of tools/gunzip_fuzz.py (texts of several kinds, every level / strategy, flushes, several members, the decoder's
-    geometry drawn at random): zlib's text, or a refusal to the host decoders -- never other text"""
+    geometry drawn at random): zlib's text, or a refusal to the host decoders -- never other text.  foreign: random tokens under random
+    complete codes from the test-side writer, where a refusal fails as well"""
     assert _tool("gunzip_fuzz").main(40 if mode == "" else 20, 11, mode) == 0
 
 
