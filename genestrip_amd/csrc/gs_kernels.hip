@@ -45,6 +45,17 @@
 __device__ __forceinline__ int gs_lane() { return (int)__lane_id(); }
 __device__ __forceinline__ int gs_readlane(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
 __device__ __forceinline__ int gs_rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// x without bit `bit`, both wave-uniform: one scalar instruction where `x &= x - 1` is three
+__device__ __forceinline__ unsigned long long gs_bitset0(unsigned long long x, int bit) {
+    asm("s_bitset0_b64 %0, %1" : "+s"(x) : "s"(bit));
+    return x;
+}
+// `old` with lane LANE replaced by the wave-uniform v (v_writelane_b32: scalar source, no exec region, no select)
+template <int LANE>
+__device__ __forceinline__ int gs_writelane(int old, int v) {
+    asm("v_writelane_b32 %0, %1, %2" : "+v"(old) : "s"(v), "n"(LANE));
+    return old;
+}
 
 // developer instrumentation (tools/phase_times.sh: -DGS_PHASE=1): wave cycles per phase of the short-read path, summed over all
 // waves (s_memtime at the phase boundaries; `dep` is a value the phase produces, so the stamp sits behind the wait for it)
@@ -665,6 +676,11 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
         bool deferred = false;                                     // REC: its statistics go into a GsStatRec (P.stat_recs)
         int def_contigs = 0, def_max = 0, def_sq = 0;              // (at most 128 positions: 128^2 fits)
         int def_counted = 0, def_read_kmers = 0, def_tax_err = 0;
+        // counters in LDS, FIXED loop: a read with ONE distinct hit node books nothing on the way.  Its contigs are the runs of its
+        // hit masks, added up in scalar registers, and its statistics are one row of `sums`, one max key and one row of `dsums`:
+        // three LDS instructions at the end of the read
+        constexpr bool SN = FIXED && !REC && !WIDE && (GS_ABLATE & 1) == 0;
+        bool sn = false;
         constexpr int NP = WIDE ? 2 : 1;
         int path[NP], ptin[NP], ptout[NP], used = 0;            // candidate paths: path i in lane i & 63 of set i >> 6
 #pragma unroll
@@ -754,7 +770,109 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
                 GS_FIRST_NODE()
                 deferred = (m0 | m1) == 0 && P.stat_recs != nullptr;  // one tax id, counters in HBM: no atomics, one record
             }
-            if ((GS_ABLATE & 1) == 0 && ((hit0 | hit1) != 0 || carry_last >= 0)) {
+            if (SN && (hit0 | hit1) != 0) {  // (as above: decided before anything is booked)
+                // (the first node again under names of this block's own: what the block shares with the code below is live on
+                // every path through the loop and costs the read that hits nothing a dozen scalar moves)
+                const int j1 = hit0 ? __builtin_ctzll(hit0) : 64 + __builtin_ctzll(hit1);
+                const int vi1 = j1 < 64 ? gs_readlane(node[0], j1) : gs_readlane(node[1], j1 - 64);
+                if (((hit0 & ~__ballot(node[0] == vi1)) | (hit1 & ~__ballot(node[1] == vi1))) == 0) {
+                    sn = true;
+                    const int one_vi = vi1, one_cnt = __popcll(hit0) + __popcll(hit1);  // (shadow the general path's)
+                    // every hit position holds one_vi, so a contig is a maximal run of set bits over the 128 positions (positions >= max
+                    // hold NONE and are no hits; the run that reaches max - 1 is the tail flush).  First and last position of every run,
+                    // per word; a run that crosses from word 0 into word 1 has its first position in s0 and its last in e1, so run i
+                    // of word 0 goes from the i-th bit of s0 to the i-th bit of e0 as long as e0 lasts, then comes the crossing run,
+                    // if s0 still holds its first position, then word 1 in the same way.  Lengths are taken one short (last - first):
+                    // sum (l + 1)^2 = sum l^2 + 2 sum l + n with sum l = one_cnt - n.  2 .. 3 trips on a read with 1 % errors
+                    u64 s0 = hit0 & ~(hit0 << 1), s1 = hit1 & ~((hit1 << 1) | (hit0 >> 63));
+                    u64 e0 = hit0 & ~((hit0 >> 1) | (hit1 << 63)), e1 = hit1 & ~(hit1 >> 1);
+                    const int sn_contigs = __popcll(s0) + __popcll(s1);
+                    int sq = 0, lmax = 0;
+#define GS_RUN(first, last)                \
+    {                                      \
+        const int l = (last) - (first);    \
+        sq += l * l;                       \
+        lmax = l > lmax ? l : lmax;        \
+    }
+                    while (e0 != 0) {
+                        const int ps = __builtin_ctzll(s0), pe = __builtin_ctzll(e0);
+                        s0 = gs_bitset0(s0, ps);
+                        e0 = gs_bitset0(e0, pe);
+                        GS_RUN(ps, pe)
+                    }
+                    if (s0 != 0) {
+                        const int ps = __builtin_ctzll(s0), pe = __builtin_ctzll(e1);
+                        e1 = gs_bitset0(e1, pe);
+                        GS_RUN(ps, 64 + pe)
+                    }
+                    while (e1 != 0) {
+                        const int ps = __builtin_ctzll(s1), pe = __builtin_ctzll(e1);
+                        s1 = gs_bitset0(s1, ps);
+                        e1 = gs_bitset0(e1, pe);
+                        GS_RUN(ps, pe)
+                    }
+#undef GS_RUN
+                    const int sn_sq = sq + 2 * one_cnt - sn_contigs, sn_max = lmax + 1;
+                    // classification in closed form, as in 4c below for a read of one node: the only candidate path is one_vi, its
+                    // sum is one_cnt, read_kmers is one_cnt
+                    out_flags = GS_F_FOUND | GS_F_RETURNED;
+                    int counted = 0, tax_err = 0, class_err = 0;
+                    typedef const __attribute__((address_space(4))) GsQuotTable *GsQuotPtr;
+                    const GsQuotPtr qt = (GsQuotPtr)P.quot;
+                    if (P.classify) {
+                        // (n_miss, bad_lo and bad_hi again, from masks the compiler cannot match with theirs: with a second use up
+                        // here their popcounts are no longer sunk into the classification below, and every read that hits nothing
+                        // pays some twenty scalar instructions for them.  FIXED: word 0 whole, of word 1 live1 >> 1, of word 2 none)
+                        u64 q0 = __ballot(node[0] == GS_NODE_MISS), q1 = __ballot(node[1] == GS_NODE_MISS), b0 = Bbad[0], b1 = Bbad[1], b2 = Bbad[2];
+                        asm volatile("" : "+s"(q0), "+s"(q1), "+s"(b0), "+s"(b1), "+s"(b2));
+                        const u64 lo1 = live1 >> 1;
+                        tax_err = __popcll(q0) + __popcll(q1) + __popcll(b0) + __popcll(b1 & lo1) + ((((b1 & ~lo1) | b2) != 0) ? 1 : 0);
+                        if (((qt->tax_disabled[tax_err >> 5] >> (tax_err & 31)) & 1u) == 0) {
+                            out_class = (P.threshold <= 1 || one_cnt >= P.threshold) ? one_vi : -1;
+                            if (out_class < 0) {
+                                out_flags &= ~GS_F_RETURNED;
+                            } else {
+                                class_err = max - one_cnt;
+                                counted = (int)((qt->class_counted[class_err >> 5] >> (class_err & 31)) & 1u);
+                                if (counted) out_flags |= GS_F_COUNTED;
+                            }
+                        }
+                    }
+                    // the read's row: lane c holds column c of `sums` (v_writelane from the scalar totals), lanes 0 .. 6 add it with
+                    // one ds_add_u64; lane 7 takes the max key; lanes 0 .. 3 add the four doubles of a counted read.  The lane number
+                    // the addresses are built from is hidden from the compiler: with an address it can prove to be the same in every
+                    // active lane, each atomic is wrapped into the scaffold that elects one lane and multiplies by the number of
+                    // active ones
+                    int lz = lane;
+                    asm volatile("" : "+v"(lz));
+                    int row = 0;
+                    row = gs_writelane<GS_S_READS>(row, counted);
+                    row = gs_writelane<GS_S_READS_KMERS>(row, counted ? one_cnt : 0);
+                    row = gs_writelane<GS_S_KMERS>(row, one_cnt);
+                    row = gs_writelane<GS_S_CONTIGS>(row, sn_contigs);
+                    row = gs_writelane<GS_S_CONTIG_LEN_SQ_SUM>(row, sn_sq);
+                    row = gs_writelane<GS_S_READS_1KMER>(row, 1);
+                    row = gs_writelane<GS_S_READS_BPS>(row, counted ? L : 0);
+                    if (GS_ACT((1ULL << GS_N_SUMS) - 1ULL)) st.add(one_vi, lz, (u64)(uint32_t)row);
+                    if (GS_ACT(1ULL << GS_N_SUMS)) st.max(one_vi + lz - GS_N_SUMS, ((u64)sn_max << 40) | key_lo);
+                    if (counted) {
+                        int dlo = 0, dhi = 0;
+#define GS_DCOL(c, val)                                             \
+    {                                                               \
+        const u64 b = (u64)__double_as_longlong(val);               \
+        dlo = gs_writelane<c>(dlo, (int)(uint32_t)b);               \
+        dhi = gs_writelane<c>(dhi, (int)(uint32_t)(b >> 32));       \
+    }
+                        GS_DCOL(GS_D_ERR_SUM, qt->e[tax_err].q)
+                        GS_DCOL(GS_D_ERR_SQ_SUM, qt->e[tax_err].q2)
+                        GS_DCOL(GS_D_CLASS_ERR_SUM, qt->e[class_err].q)
+                        GS_DCOL(GS_D_CLASS_ERR_SQ_SUM, qt->e[class_err].q2)
+#undef GS_DCOL
+                        if (GS_ACT((1ULL << GS_N_DCOLS) - 1ULL)) st.dadd(one_vi, lz, __longlong_as_double((long long)(((u64)(uint32_t)dhi << 32) | (u64)(uint32_t)dlo)));
+                    }
+                }
+            }
+            if ((GS_ABLATE & 1) == 0 && !(SN && sn) && ((hit0 | hit1) != 0 || carry_last >= 0)) {
                 int prev[2];
                 {
                     const int up0 = __shfl_up(node[0], 1);
@@ -904,7 +1022,7 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
             }
         }
 
-        if ((GS_ABLATE & 1) == 0 && found) {
+        if ((GS_ABLATE & 1) == 0 && found && !(SN && sn)) {
             out_flags = GS_F_FOUND | GS_F_RETURNED;
             // tail flush (:455-473): the last contig if it is a hit contig
             if (carry_last >= 0) {

@@ -1,7 +1,8 @@
 """kernel time of gs_match_kernel per read stream (developer tool): the bench stream (half of the reads from the store), a
 hit-only stream (every read from the store, 1 % substitutions) and a miss-only stream (reads from other genomes), on the
 config-2 store or, with --large, the 47 M-k-mer store.  With library paths as arguments every library (a build variant,
-tools/ablate.sh) is timed in a child process:   python tools/stream_times.py [--large] [lib.so ...]"""
+tools/ablate.sh) is timed in a child process:   python tools/stream_times.py [--large] [--fixed] [lib.so ...]
+--fixed submits with gs_match_submit_fixed (the FIXED loop of the kernel) instead of an offsets array."""
 import os
 import subprocess
 import sys
@@ -10,11 +11,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 large = "--large" in sys.argv
+fixed = "--fixed" in sys.argv
 only = next((a.split("=")[1] for a in sys.argv if a.startswith("--stream=")), None)  # bench | hit | miss (for profiling)
 if args and os.environ.get("GS_STREAM_CHILD") != "1":
     for lib in args:
         env = dict(os.environ, GS_LIBGSGPU=os.path.abspath(lib), GS_STREAM_CHILD="1")
-        out = subprocess.run([sys.executable, os.path.abspath(__file__)] + (["--large"] if large else []), env=env,
+        out = subprocess.run([sys.executable, os.path.abspath(__file__)] + (["--large"] if large else []) + (["--fixed"] if fixed else []), env=env,
                              capture_output=True, text=True)
         print(f"{os.path.basename(lib):24s} {out.stdout.strip() or out.stderr.strip()[-300:]}", flush=True)
     sys.exit(0)
@@ -34,15 +36,22 @@ doff = torch.empty(n + 1, dtype=torch.int64, device="cuda")
 m = ga.FastqKMerMatcher(store, ga.MatchConfig(profile=True))
 
 
+def submit():
+    if fixed:
+        m.submit_fixed(dseq, 150, n)
+    else:
+        m.submit(dseq, doff, 0, n_reads=n)
+
+
 def timed():
     for _ in range(2):
         m.reset()
-        m.submit(dseq, doff, 0, n_reads=n)
+        submit()
     m.sync()
     l0, t0 = m.kernel_time()
     for _ in range(4):
         m.reset()
-        m.submit(dseq, doff, 0, n_reads=n)
+        submit()
     m.sync()
     l1, t1 = m.kernel_time()
     return (t1 - t0) / (l1 - l0)
