@@ -1,4 +1,4 @@
-// gs_kernels.hip -- hand-written gfx950 (CDNA4, wave64) kernels of the match / filter hot path.
+// gs_kernels.hip -- hand-written gfx950 (CDNA4, wave64) kernels of the match hot path.
 //
 // match: ONE WAVE PER READ.  Lane p owns k-mer start position p; an "iteration" covers 128 positions as two
 // sub-rounds of 64, so a 150 bp read at k=31 (120 k-mers) is exactly one iteration.  Per iteration:
@@ -16,72 +16,21 @@
 //   #INVALID iterations = popcount(bad bases at positions <= max-2) + (any bad base at >= max-1).
 // Reads with more than 128 k-mer positions are queued and drained by gs_match_long_kernel, the same code
 // iterating with carried state and per-wave scratch counters in HBM instead of in-register lists.
-//
-// filter: one wave per read, lanes = k-mer positions, the reference's exact Bloom hashes; accept is the
-// closed form  #(member k-mers) >= max(posThreshold, 1)  of FastqBloomFilter.isAcceptRead (:120-161).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 #include <type_traits>
 
-#include "gs_absmod.h"  // gs_absmod: the filter's bit index
 #include "gs_launch.h"
 #include "gs_layout.h"
 #include "gs_params.h"
+#include "gs_wave.h"
 
-// developer ablations (tools/ablate.sh): 1 = no per-read reduce, 2 = no record / table probe, 4 = no gate either,
-// 8 = no statistics atomics
-#ifndef GS_ABLATE
-#define GS_ABLATE 0
-#endif
-
-#define GS_NODE_MISS (-1)
-#define GS_NODE_INVALID (-2)
-#define GS_NODE_NONE (-3)
 #define GS_LONG_CHUNK 64           // entries of the long-read queue a wave reserves at a time (one atomic per chunk)
 #define GS_LONG_NONE 0xffffffffu   // padding of a chunk (a batch holds at most 2^32 - 1 reads)
 
-__device__ __forceinline__ int gs_lane() { return (int)__lane_id(); }
-__device__ __forceinline__ int gs_readlane(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
-__device__ __forceinline__ int gs_rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
-// x without bit `bit`, both wave-uniform: one scalar instruction where `x &= x - 1` is three
-__device__ __forceinline__ unsigned long long gs_bitset0(unsigned long long x, int bit) {
-    asm("s_bitset0_b64 %0, %1" : "+s"(x) : "s"(bit));
-    return x;
-}
-// `old` with lane LANE replaced by the wave-uniform v (v_writelane_b32: scalar source, no exec region, no select)
-template <int LANE>
-__device__ __forceinline__ int gs_writelane(int old, int v) {
-    asm("v_writelane_b32 %0, %1, %2" : "+v"(old) : "s"(v), "n"(LANE));
-    return old;
-}
-
-// developer instrumentation (tools/phase_times.sh: -DGS_PHASE=1): wave cycles per phase of the short-read path, summed over all
-// waves (s_memtime at the phase boundaries; `dep` is a value the phase produces, so the stamp sits behind the wait for it)
-#ifndef GS_PHASE
-#define GS_PHASE 0
-#endif
-#if GS_PHASE
-__device__ unsigned long long gs_phase_acc[16];
-__device__ __forceinline__ unsigned long long *gs_phase_row() {
-    __shared__ unsigned long long ph[4][16];
-    return ph[threadIdx.x >> 6];
-}
-__device__ __forceinline__ void gs_stamp(int i) {
-    const unsigned long long t = __builtin_readcyclecounter();
-    if (gs_lane() == 0) {
-        unsigned long long *p = gs_phase_row();
-        const unsigned long long last = p[15];
-        p[15] = t;
-        if (i >= 0) p[i] += t - last;
-    }
-}
-#define GS_STAMP(i, dep)                \
-    {                                   \
-        asm volatile("" ::"v"(dep));    \
-        gs_stamp(i);                    \
-    }
+#if GS_PHASE  // (tools/phase_times.sh; the stamps: gs_wave.h)
 extern "C" int gs_debug_phase(unsigned long long *out, int reset) {
     if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(gs_phase_acc), sizeof(unsigned long long) * 16) != hipSuccess) return -1;
     if (reset) {
@@ -90,33 +39,7 @@ extern "C" int gs_debug_phase(unsigned long long *out, int reset) {
     }
     return 0;
 }
-#else
-#define GS_STAMP(i, dep) {}
 #endif
-
-// bits [s, s+64) of the 128-bit string (b:a), s in 0..63
-__device__ __forceinline__ u64 gs_funnel(u64 a, u64 b, int s) { return (a >> s) | ((b << 1) << (63 - s)); }
-
-// ASCII bases -> ballot planes of the reference's 2-bit codes (C0 G1 A2 T3, upper case only: CGAT.java:66-69), from a byte that was
-// loaded earlier; lanes beyond the read hold GS_FILL ('C': code 0, valid -- planes 0 and not bad, without a range test).
-// Straight-line, every ballot one integer compare: x = bits 1..2 of the byte (A 0, C 1, T 2, G 3), d = byte ^ the one upper-case
-// letter with that x (a byte permute), code-hi = x even, code-lo = bit 2 of the byte; a byte that is not its letter (N, lower
-// case, CR, NUL) has d != 0: planes 0 -- every window that holds such a byte is INVALID whatever its planes say -- and bad.
-#define GS_FILL 0x43u
-__device__ __forceinline__ void gs_word_from_byte(uint32_t c, u64 &hi, u64 &lo, u64 &bad) {
-    const uint32_t x = (c >> 1) & 3u;
-    const uint32_t d = c ^ __builtin_amdgcn_perm(0u, 0x47544341u, x | 0x0c0c0c00u);
-    hi = __ballot(((x & 1u) | d) == 0u);
-    lo = __ballot((((c ^ 4u) & 4u) | d) == 0u);
-    bad = __ballot(d != 0u);
-}
-
-// one 64-base word of a read -> ballot planes
-__device__ __forceinline__ void gs_load_word(const uint8_t *rd, int L, int w, int lane, u64 &hi, u64 &lo, u64 &bad) {
-    const int j = 64 * w + lane;
-    const uint32_t c = j < L ? rd[j] : GS_FILL;
-    gs_word_from_byte(c, hi, lo, bad);
-}
 
 // ---------------------------------------------------------------------------------------------------
 // statistics sinks: LDS-privatised (n_values <= GS_NV_LDS) or direct global atomics
@@ -152,116 +75,6 @@ struct GsStats {
 };
 
 // ---------------------------------------------------------------------------------------------------
-// store probe
-// ---------------------------------------------------------------------------------------------------
-typedef unsigned long long gs_u64x2 __attribute__((ext_vector_type(2)));
-
-// The fused kernels look at the first half of a bucket first (two loads, four compares, half the registers) and run
-// at 8 waves per SIMD with 64 VGPRs.  Measured against whole-bucket probes at 6 waves: bench stream equal (10.26 ms),
-// miss-only stream 5.94 -> 5.56 ms, 47 M-k-mer store 16.3 -> 16.0 ms.
-#ifndef GS_HALF_BUCKETS
-#define GS_HALF_BUCKETS 1
-#endif
-#ifndef GS_WAVES
-#define GS_WAVES 8
-#endif
-
-// (Software pipelining across the reads of a wave -- offsets two reads ahead, bases one read ahead -- was measured on
-// MI355X in round 1 and again in round 2 on the record layout, also on the HBM-resident 47 M-k-mer store: within noise
-// (7.67 / 7.79 ms, 10.45 / 10.53 ms) while costing 4 more spilled VGPRs; the code is gone.)
-
-#ifndef GS_NT_TABLE
-// Measured on MI355X: non-temporal bucket loads stop the four dwordx4 loads of one 64-byte line from sharing a
-// single L2 request (the match kernel ran 2.2x slower), so the default is plain loads.
-#define GS_NT_TABLE 0
-#endif
-
-struct GsBucket {
-    gs_u64x2 q[4];
-};
-
-__device__ __forceinline__ void gs_load_bucket(const u64 *table, u64 bkt, GsBucket &b) {
-    const gs_u64x2 *p = reinterpret_cast<const gs_u64x2 *>(table + bkt * GS_SLOTS_PER_BUCKET);
-#if GS_NT_TABLE
-    b.q[0] = __builtin_nontemporal_load(p);
-    b.q[1] = __builtin_nontemporal_load(p + 1);
-    b.q[2] = __builtin_nontemporal_load(p + 2);
-    b.q[3] = __builtin_nontemporal_load(p + 3);
-#else
-    b.q[0] = p[0];
-    b.q[1] = p[1];
-    b.q[2] = p[2];
-    b.q[3] = p[3];
-#endif
-}
-
-// returns true when the probe is finished (hit, or miss proven by a non-full bucket).
-// slot = rem << (vbits+3) | disp << (vbits+1) | (vi+1) << 1 | seen, with vbits+3 < 32: a match has an equal high
-// dword and a low dword that differs from `want` (value and seen fields 0) by x = 2(vi+1) + seen, i.e.
-// 0 <= x-2 < 2*vmask.  On a hit vs = 2*vi + seen.  Buckets fill front to back, so "full" is "slot 7 is occupied".
-__device__ __forceinline__ bool gs_match_bucket(const GsBucket &b, u64 want, uint32_t vmask2, int &vs, int &slot) {
-    const u64 s[8] = {b.q[0].x, b.q[0].y, b.q[1].x, b.q[1].y, b.q[2].x, b.q[2].y, b.q[3].x, b.q[3].y};
-    // two instructions per slot: mask the value/seen field away and compare all 64 bits.  An empty slot (0) can only
-    // "match" want == 0 and is told apart afterwards by its zero value field.
-    const u64 keep = ~(u64)(vmask2 + 1u);  // vmask2 + 1 = 2^(vbits+1) - 1: the (vi+1, seen) field
-    int hit = -1;
-    uint32_t low = 0;
-#pragma unroll
-    for (int j = 7; j >= 0; j--) {  // buckets fill front to back: the lowest match is the real entry
-        const bool m = (s[j] & keep) == want;
-        low = m ? (uint32_t)s[j] : low;
-        hit = m ? j : hit;
-    }
-    const int x = (int)(low & (vmask2 + 1u)) - 2;  // 2 vi + seen, or < 0 for the empty slot
-    if (hit >= 0 && x >= 0) {
-        vs = x;
-        slot = hit;
-        return true;
-    }
-    return s[7] == 0;
-}
-
-// Half a bucket (slots 0-3 or 4-7, 32 bytes).  Buckets fill front to back and hold 1.5 .. 3 keys on average, so the
-// first half answers most probes with two load instructions, four slot compares and half the registers.
-struct GsHalf {
-    gs_u64x2 q[2];
-};
-
-__device__ __forceinline__ void gs_load_half(const u64 *table, u64 bkt, int half, GsHalf &b) {
-    const gs_u64x2 *p = reinterpret_cast<const gs_u64x2 *>(table + bkt * GS_SLOTS_PER_BUCKET) + 2 * half;
-    b.q[0] = p[0];
-    b.q[1] = p[1];
-}
-
-// as gs_match_bucket over four slots; finished = hit, or the half's last slot is empty (nothing can follow it)
-__device__ __forceinline__ bool gs_match_half(const GsHalf &b, u64 want, uint32_t vmask2, int &vs, int &slot) {
-    const u64 s[4] = {b.q[0].x, b.q[0].y, b.q[1].x, b.q[1].y};
-    const u64 keep = ~(u64)(vmask2 + 1u);
-    int hit = -1;
-    uint32_t low = 0;
-#pragma unroll
-    for (int j = 3; j >= 0; j--) {
-        const bool m = (s[j] & keep) == want;
-        low = m ? (uint32_t)s[j] : low;
-        hit = m ? j : hit;
-    }
-    const int x = (int)(low & (vmask2 + 1u)) - 2;
-    if (hit >= 0 && x >= 0) {
-        vs = x;
-        slot = hit;
-        return true;
-    }
-    return s[3] == 0;
-}
-
-// table hash of the k-mer whose forward planes are (fhi, flo): representative orientation, then the Feistel mix
-__device__ __forceinline__ u64 gs_kmer_hash(uint32_t fhi, uint32_t flo, int k, uint32_t kmask) {
-    uint32_t a, b;
-    gs_rep_planes(fhi, flo, k, kmask, a, b);
-    return gs_mix_planes(a, b);
-}
-
-// ---------------------------------------------------------------------------------------------------
 // tree helpers (value index == node id; tin/tout pre-order interval)
 // ---------------------------------------------------------------------------------------------------
 // is `a` an ancestor-or-self of `x`  (SmallTaxTree.isAncestorOf(x, a), SmallTaxTree.java:242-252)
@@ -279,366 +92,6 @@ __device__ __forceinline__ int gs_lca(const Tree &t, int a, int b) {  // SmallTa
 // per-wave scratch of the long-read kernel, always accessed at agent scope (L1 bypass)
 __device__ __forceinline__ int gs_sc_load(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void gs_sc_store(int32_t *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// ---------------------------------------------------------------------------------------------------
-// 128 k-mer positions [base, base+128) of one read: planes -> minimizer -> gate -> record line (or bucket line) -> node.
-// node[s] for position base + 64 s + lane: value index (hit), GS_NODE_MISS, GS_NODE_INVALID (window holds a
-// non-CGAT byte) or GS_NODE_NONE (position >= max).  Hits are marked on the spot (mk): the unique-k-mer "seen" bit of
-// the slot / record offset that was just read (KMerUniqueCounterBits.putInlined; a k-mer that is already marked costs
-// nothing, a stale copy only repeats the atomic) and the per-k-mer hit counter (maxKMerResCounts > 0).
-// ---------------------------------------------------------------------------------------------------
-struct GsMark {
-    int count_unique;
-    uint32_t *hit_counts;  // [table slots | GS_REC_SLOTS per record bucket] or nullptr
-    // striped store: the store's memory is read-only (foreign stripes belong to other GPUs); the seen bits are this run's
-    uint32_t *tab_seen;    // one bit per table slot
-    uint32_t *rec_seen;    // one word per record bucket
-};
-
-// where a striped store keeps the pointers of its stripes: behind the two hash rows of the wave's LDS block
-// (GS_STRIPE_TABLE): GS_MAX_STRIPES record stripes, then GS_MAX_STRIPES table stripes, all biased (gs_layout.h)
-#define GS_ROW 160  // one LDS row: 128 + 16 positions, padded
-#define GS_STRIPE_WORDS (4 * GS_MAX_STRIPES)
-__device__ __forceinline__ const u64 *gs_rec_stripe(const GsDbDev &db, const uint32_t *wave_g, uint32_t bucket) {
-    return reinterpret_cast<const u64 *const *>(wave_g + 2 * GS_ROW)[(bucket * db.n_parts) >> db.rec_bits];
-}
-__device__ __forceinline__ const u64 *gs_tab_stripe(const GsDbDev &db, const uint32_t *wave_g, uint32_t bucket) {
-    return reinterpret_cast<const u64 *const *>(wave_g + 2 * GS_ROW)[GS_MAX_STRIPES + (((bucket >> 2) * db.n_parts) >> (db.bucket_bits - 2))];
-}
-
-template <bool STRIPED>
-__device__ __forceinline__ void gs_take_hit(const GsDbDev &db, uint32_t slot, int vs, int &node, const GsMark &mk) {
-    node = vs >> 1;
-    if (STRIPED) {
-        if (mk.count_unique) {
-            uint32_t *w = mk.tab_seen + (slot >> 5);
-            const uint32_t bit = 1u << (slot & 31);
-            if ((*w & bit) == 0) atomicOr(w, bit);
-        }
-    } else if (mk.count_unique && (vs & 1) == 0)
-        atomicOr(const_cast<u64 *>(db.table) + slot, 1ULL);
-    if (mk.hit_counts != nullptr) atomicAdd(mk.hit_counts + slot, 1u);
-}
-
-// the rest of a table lookup for the lanes in `pending` (their k-mer was not decided by the first half of its home
-// bucket, or that half has not been looked at yet: FIRST): second half, then the displaced buckets
-template <bool FIRST, bool STRIPED>
-__device__ __forceinline__ void gs_lookup_rest(const GsDbDev &db, uint32_t bkt, u64 want, uint32_t vmask2, bool pending, int &node,
-                                               const GsMark &mk, const uint32_t *wave_g) {
-    const uint32_t bmask = (uint32_t)db.bucket_mask;
-#pragma unroll
-    for (int half = FIRST ? 0 : 1; half < 2; half++) {
-        if (__ballot(pending) != 0) {  // (second half: more than four entries in the home bucket)
-            if (pending) {
-                GsHalf t;
-                gs_load_half(STRIPED ? gs_tab_stripe(db, wave_g, bkt) : db.table, bkt, half, t);
-                int vs = -1, sl = 0;
-                const bool done = gs_match_half(t, want, vmask2, vs, sl);
-                if (vs >= 0) gs_take_hit<STRIPED>(db, bkt * GS_SLOTS_PER_BUCKET + 4 * half + sl, vs, node, mk);
-                pending = !done;
-            }
-        }
-    }
-    // rare: home bucket full without a match -> walk the displaced buckets
-    for (int disp = 1; disp <= GS_MAX_DISP && __ballot(pending) != 0; disp++) {
-        if (pending) {
-            const uint32_t b2 = (bkt + (uint32_t)disp) & bmask;
-            GsBucket t;
-            gs_load_bucket(STRIPED ? gs_tab_stripe(db, wave_g, b2) : db.table, b2, t);
-            int vs = -1, sl = 0;
-            const bool done = gs_match_bucket(t, want | ((u64)disp << (db.vbits + 1)), vmask2, vs, sl);
-            if (vs >= 0) gs_take_hit<STRIPED>(db, b2 * GS_SLOTS_PER_BUCKET + sl, vs, node, mk);
-            pending = !done;
-        }
-    }
-}
-
-// minimizer of the k-mers at positions base + 64 s + lane through the wave's LDS row: rank of every 15-mer of
-// positions base .. base+143, then per lane the minimum over its k-14 positions (one min3 chain; the rank carries the
-// row index, so the minimum is the position as well).  Returns the offset of the chosen 15-mer inside the lane's k-mer.
-// wave_g: two rows of GS_ROW words per wave -- the ranks, and behind them (canonical 15-mer << 1 | strand) of every position,
-// which the lane that picks a position reads back instead of recomputing it.  cf[s] = that word for the lane's minimizer.
-// NS: sub-rounds of 64 positions per trip (2: the kernels' iteration of 128 positions; 3, 4: gs_match_wide_kernel, reads of up to
-// 192 / 256 positions in ONE trip).  The rank carries its row index in eight bits, so beyond two sub-rounds there are TWO rank rows:
-// A for positions 0 .. 143 (read by sub-rounds 0 and 1), B for positions 128 .. 64 NS + 15 with the index counted from 128 (read by
-// sub-rounds 2 and 3); the 16 positions both need are written twice.  Layout of the wave's words: [A: GS_ROW][B: GS_ROW, NS > 2 only]
-// [canonical 15-mers of all positions: 64 NS + 16].
-#define GS_WIDE_WORDS(NS) (2 * GS_ROW + 64 * (NS) + 32)
-template <int KC, int NS = 2>
-__device__ __forceinline__ void gs_wave_minimizers(const u64 (&Bhi)[NS + 1], const u64 (&Blo)[NS + 1], const uint32_t (&fhi)[NS],
-                                                   const uint32_t (&flo)[NS], const uint32_t (&rhi)[NS], const uint32_t (&rlo)[NS], int k,
-                                                   int lane, uint32_t *wave_g, int (&p)[NS], uint32_t (&cf)[NS]) {
-    static_assert(NS >= 2 && NS <= 4, "two rank rows of 144 positions");
-    constexpr bool TWO = NS > 2;
-    constexpr int ROWB = GS_ROW, CAN = TWO ? 2 * GS_ROW : GS_ROW;
-#pragma unroll
-    for (int s = 0; s < NS; s++) {
-        // gs_lmer_canon of the k-mer's first 15-mer; its reverse complement is the top 15 bases of the k-mer's (rhi, rlo: the
-        // orientation step needs them anyway), and "the smaller of f and r, low bit = f was it" is min(2f + 1, 2r)
-        const uint32_t f = ((fhi[s] & 0x7fffu) << GS_MIN_L) | (flo[s] & 0x7fffu);
-        const uint32_t rr = ((rhi[s] >> (k - GS_MIN_L)) << GS_MIN_L) | (rlo[s] >> (k - GS_MIN_L));
-        const uint32_t c = min((f << 1) | 1u, rr << 1);
-        const uint32_t h = gs_canon_hash(c >> 1);
-        if (!TWO || s < 2) wave_g[64 * s + lane] = gs_lmer_rank(h, (uint32_t)(64 * s + lane));
-        if (TWO && s >= 2) wave_g[ROWB + 64 * (s - 2) + lane] = gs_lmer_rank(h, (uint32_t)(64 * (s - 2) + lane));
-        if (TWO && s == 2 && lane < 16) wave_g[128 + lane] = gs_lmer_rank(h, (uint32_t)(128 + lane));
-        wave_g[CAN + 64 * s + lane] = c;
-    }
-    if (lane < 16) {
-        const uint32_t c = gs_lmer_canon((uint32_t)(Bhi[NS] >> lane) & 0x7fffu, (uint32_t)(Blo[NS] >> lane) & 0x7fffu);
-        const uint32_t h = gs_canon_hash(c >> 1);
-        if (!TWO)
-            wave_g[64 * NS + lane] = gs_lmer_rank(h, (uint32_t)(64 * NS + lane));
-        else
-            wave_g[ROWB + 64 * (NS - 2) + lane] = gs_lmer_rank(h, (uint32_t)(64 * (NS - 2) + lane));
-        wave_g[CAN + 64 * NS + lane] = c;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const int w = k - GS_MIN_L + 1;
-    // The ranks of a lane's k - 14 positions are read in ONE batch per sub-round (the loads are independent; left to itself the
-    // compiler waits after every ds_read2 because of the 64-register budget: nine LDS round trips in a row per sub-round), then
-    // folded with min3.
-    constexpr int ND = KC ? KC - GS_MIN_L + 1 : 32 - GS_MIN_L;
-#pragma unroll
-    for (int s = 0; s < NS; s++) {
-        const uint32_t *row = (TWO && s >= 2) ? wave_g + ROWB + 64 * (s - 2) + lane : wave_g + 64 * s + lane;
-        uint32_t g[ND];
-#pragma unroll
-        for (int d = 0; d < ND; d++) g[d] = (KC || d < w) ? row[d] : 0xffffffffu;
-        __builtin_amdgcn_sched_group_barrier(0x100, (ND + 1) / 2, 0);  // the DS reads first ...
-        uint32_t mn = g[0];
-#pragma unroll
-        for (int d = 1; d < ND; d++) mn = g[d] < mn ? g[d] : mn;
-        __builtin_amdgcn_sched_group_barrier(0x002, ND, 0);            // ... then the min chain
-        const int idx = (int)(mn & 0xffu) + ((TWO && s >= 2) ? 128 : 0);
-        cf[s] = wave_g[CAN + idx];
-        p[s] = idx - (64 * s + lane);
-    }
-    __builtin_amdgcn_wave_barrier();  // the rows are rewritten by the next iteration / read
-}
-
-#define GS_ACT(m) __builtin_amdgcn_inverse_ballot_w64(m)  // a wave-level mask as a per-lane condition
-// the lanes below n as a wave-level mask: the positions of a sub-round that hold a k-mer, the lanes of a word that hold a base
-__device__ __forceinline__ u64 gs_low_mask(int n) { return n >= 64 ? ~0ULL : (n <= 0 ? 0ULL : ((1ULL << n) - 1ULL)); }
-// live: the positions of each sub-round that hold a k-mer, gs_low_mask(max - base - 64 s), from a caller that has them already -- they
-// depend on the read's length alone, and a batch of one length builds them once per wave (gs_match_kernel<.., FIXED = true>);
-// nullptr: derived here from base and max
-// CTX: is the gate keyed by gs_gate_ctx_key?  0 never (the launcher has looked), 1 always, 2 ask the store (GsDbDev::mgate_ctx)
-// AGG: the unique-k-mer marks of the k-mers that share a record line leave as ONE atomic per line.  A device-scope atomic is
-// executed on the memory side of the L2s (eight XCDs, eight L2s): every one is a request to the fabric, and on a store that does not
-// fit the caches they were HALF of the kernel's fabric requests (473 M k-mers: 30 read + 36 write requests per read, 61 writes per
-// read from the store -- one per first-seen k-mer; tools/huge_lines.py), with the fabric's line rate the bound (0.89).  The lanes of
-// a minimizer run OR their offset bits into a word of the wave's LDS rows (free again after the minimizer scan), the lane that owns
-// the lowest bit sends the word: ~13 atomics per read from the store instead of ~60.
-template <int KC, bool STRIPED, int CTX = 2, bool AGG = false, int NS = 2>
-__device__ __forceinline__ void gs_probe_planes(const GsDbDev &db, const u64 (&Bhi)[NS + 1], const u64 (&Blo)[NS + 1],
-                                                const u64 (&Bbad)[NS + 1], int base, int max, int lane, int (&node)[NS],
-                                                uint32_t *wave_g, const GsMark &mk, const u64 *live = nullptr) {
-    static_assert(NS == 2 || !AGG, "the seen-bit accumulators are laid out for two sub-rounds");
-    const int k = KC ? KC : db.k;  // KC = compile-time k of the specialised kernels (0: any k)
-    const uint32_t kmask = (1u << k) - 1u;
-    const uint32_t vmask2 = 2u * ((1u << db.vbits) - 1u);
-    const int shift_rem = (int)db.vbits + 3;
-    const uint32_t bmask = (uint32_t)db.bucket_mask;  // n_buckets <= 2^29
-    bool any_bad = false;
-#pragma unroll
-    for (int w = 0; w <= NS; w++) any_bad = any_bad || Bbad[w] != 0;
-    uint32_t fhi[NS], flo[NS];
-    // Which lanes hold a live k-mer is kept as a wave-level MASK (a scalar register pair), not as a per-lane flag: "position < max"
-    // is a mask the scalar unit builds from the read length, every later condition is one vector compare whose result is a
-    // mask already, and a mask conditions a lane directly (inverse ballot) -- no flag is materialised in a vector register and
-    // compared again.
-    u64 act[NS];
-#pragma unroll
-    for (int s = 0; s < NS; s++) {
-        const u64 vm = live != nullptr ? live[s] : gs_low_mask(max - base - 64 * s);  // valid positions of this sub-round
-        fhi[s] = (uint32_t)gs_funnel(Bhi[s], Bhi[s + 1], lane) & kmask;
-        flo[s] = (uint32_t)gs_funnel(Blo[s], Blo[s + 1], lane) & kmask;
-        act[s] = vm;
-        node[s] = GS_ACT(vm) ? GS_NODE_MISS : GS_NODE_NONE;
-        if (any_bad) {  // almost every read is clean: the per-lane window test sits behind a wave-uniform branch
-            const u64 wb = __ballot(((uint32_t)gs_funnel(Bbad[s], Bbad[s + 1], lane) & kmask) != 0u) & vm;
-            act[s] = vm & ~wb;
-            node[s] = GS_ACT(wb) ? GS_NODE_INVALID : node[s];
-        }
-    }
-    if (db.mgate != nullptr) {
-        // minimizer gate: lanes that share a minimizer read the same gate word -> one request
-        int mp[NS];
-        uint32_t cf[NS];
-        GS_STAMP(2, fhi[1] ^ flo[1])
-        uint32_t rhi[NS], rlo[NS];  // reverse complement of the k-mer
-#pragma unroll
-        for (int s = 0; s < NS; s++) {
-            rhi[s] = __brev(fhi[s]) >> (32 - k);
-            rlo[s] = (__brev(flo[s]) >> (32 - k)) ^ kmask;
-        }
-        gs_wave_minimizers<KC, NS>(Bhi, Blo, fhi, flo, rhi, rlo, k, lane, wave_g, mp, cf);
-        GS_STAMP(3, cf[0] ^ cf[1])
-        uint32_t gh[NS], ohi[NS], olo[NS];
-        int j[NS];
-#pragma unroll
-        for (int s = 0; s < NS; s++) gs_min_oriented_cf(cf[s], fhi[s], flo[s], rhi[s], rlo[s], k, mp[s], gh[s], ohi[s], olo[s], j[s]);
-        // Lanes that look into their minimizer's second bucket as well.  Every store carries the hint bits (gs_mgate_hint); they
-        // are USED where a record line is dear -- a context-keyed store (hundreds of millions of k-mers, lines from HBM) and a
-        // striped one (lines over xGMI) --: on a store whose records sit in the caches the second line costs less than the
-        // test (measured on configs[1]: 6.74 ms without, 6.94 ms with it; 47 M store 8.66 / 8.68; 473 M store 15.39 / 15.03).
-        const bool use_hint = STRIPED || CTX == 1 || (CTX == 2 && db.mgate_ctx);
-        u64 two[NS];
-#pragma unroll
-        for (int s = 0; s < NS; s++) two[s] = ~0ULL;
-        if ((GS_ABLATE & 4) == 0) {
-            // the gate words of both sub-rounds are requested together (lanes without a live k-mer read word 0): one round
-            // trip, no exec-mask regions
-            uint32_t gw[NS];
-            uint32_t gk[NS];  // what the gate is keyed by: the minimizer, or (big stores) the minimizer + four bases next to it
-#pragma unroll
-            for (int s = 0; s < NS; s++) gk[s] = (CTX == 1 || (CTX == 2 && db.mgate_ctx)) ? gs_gate_ctx_key(gh[s], ohi[s], olo[s], j[s], k) : gh[s];
-#pragma unroll
-            for (int s = 0; s < NS; s++)
-                gw[s] = db.mgate[GS_ACT(act[s]) ? ((CTX == 1 || (CTX == 2 && db.mgate_ctx)) ? gs_mgate_word_ctx(gk[s], db.mgate_bits) : gs_mgate_word(gk[s], db.mgate_bits)) : 0u];
-#pragma unroll
-            for (int s = 0; s < NS; s++) {
-                const uint32_t bits = gs_mgate_bits(gk[s]);
-                act[s] &= __ballot((gw[s] & bits) == bits);  // no false negatives
-                if (use_hint) two[s] = __ballot((gw[s] & gs_mgate_hint(gk[s])) != 0u);  // a window of this key may sit in the second bucket
-            }
-            GS_STAMP(4, gw[0] ^ gw[1])
-        }
-        if (GS_ABLATE & 6) {  // keep the values alive, look nothing up
-#pragma unroll
-            for (int s = 0; s < NS; s++)
-                if (GS_ACT(act[s]) && (gh[s] ^ ohi[s] ^ olo[s] ^ (uint32_t)j[s]) == 0x12345u) node[s] = 0;
-            return;
-        }
-        if (STRIPED || db.rec != nullptr) {
-            // ---- super-k-mer records: per candidate bucket of the minimizer one 16-byte load of the window planes + the
-            // 8-byte word that holds this offset's value.  The first bucket always; the second one only where the gate word
-            // carries the key's hint bit (two windows in three sit in their first bucket: a third fewer line requests, which
-            // is what bounds a store that does not fit the caches).  Both loads of a sub-round are in flight together and the
-            // compares are straight-line code (bitwise, no short-circuit branches: every branch is an exec-mask save /
-            // restore on the scalar unit, which this kernel keeps as busy as the vector unit)
-            u64 any_act = 0;
-#pragma unroll
-            for (int s = 0; s < NS; s++) any_act |= act[s];
-            if (any_act == 0) return;  // nothing passed the gate: a read that is not from the store
-            if (AGG && mk.count_unique) {  // accumulators of the seen bits: 80 minimizer positions x 2 buckets per sub-round
-#pragma unroll
-                for (int q = 0; q < 5; q++) wave_g[64 * q + lane] = 0u;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            }
-            // (Tried in round 3 and dropped, twice: touching sub-round 1's lines -- one dword each -- before sub-round 0's loads go
-            // out, so that the second record round trip (3 400 + 3 200 of 24 900 wave cycles per read on the 473 M-k-mer store,
-            // tools/phase_times.sh huge) is an L2 hit.  With plain loads, which the compiler is free to sink: configs[1] 6.80 ->
-            // 7.05 ms, 47 M store 8.72 -> 9.08, 473 M store 15.0 -> 15.2.  With loads the compiler does not see (inline asm, issued
-            // first for certain; big stores only): 473 M store 15.0 -> 15.2 ms, striped 7.24 -> 7.40.  The round trip that was
-            // taken out does not come off the kernel's time.)
-#pragma unroll
-            for (int s = 0; s < NS; s++) {
-                bool pending = false;
-                if (GS_ACT(act[s])) {
-                    const uint32_t jj = (uint32_t)j[s];
-                    const int jw = (int)(jj * 11u) >> 5;  // j / 3 for j <= 16
-                    const uint32_t b0 = gs_rec_bucket(gh[s], db.rec_bits, 0), b1 = gs_rec_bucket(gh[s], db.rec_bits, 1);
-                    // the stripe's (biased) base pointer from the wave's copy of the table, behind the hash rows
-                    const u64 *r0 = (STRIPED ? gs_rec_stripe(db, wave_g, b0) : db.rec) + (u64)b0 * GS_REC_WORDS;
-                    gs_u64x2 A1 = {0, 0};  // (no valid bit: matches nothing)
-                    u64 V1 = 0;
-                    if (!use_hint || GS_ACT(two[s])) {
-                        const u64 *r1 = (STRIPED ? gs_rec_stripe(db, wave_g, b1) : db.rec) + (u64)b1 * GS_REC_WORDS;
-                        A1 = *reinterpret_cast<const gs_u64x2 *>(r1);
-                        V1 = r1[2 + jw];
-                    }
-                    const gs_u64x2 A0 = *reinterpret_cast<const gs_u64x2 *>(r0);
-                    const u64 V0 = r0[2 + jw];
-                    // window bits [j, j + k) of a plane: j + k <= 2k - 15, so the seen / valid bits above the window stay out
-                    // of the low k bits of the shifted word; one 32-bit funnel shift (j <= 16) per plane
-                    const uint32_t x0 = __builtin_amdgcn_alignbit((uint32_t)(A0.x >> 32), (uint32_t)A0.x, jj);
-                    const uint32_t y0 = __builtin_amdgcn_alignbit((uint32_t)(A0.y >> 32), (uint32_t)A0.y, jj);
-                    const uint32_t x1 = __builtin_amdgcn_alignbit((uint32_t)(A1.x >> 32), (uint32_t)A1.x, jj);
-                    const uint32_t y1 = __builtin_amdgcn_alignbit((uint32_t)(A1.y >> 32), (uint32_t)A1.y, jj);
-                    const uint32_t fbit = 1u << (GS_REC_WIN_BITS - 32 + jj);  // seen (w0) / valid (w1) bit of offset j, high dword
-                    const bool ok0 = ((((x0 ^ ohi[s]) | (y0 ^ olo[s])) & kmask) == 0) & (((uint32_t)(A0.y >> 32) & fbit) != 0);
-                    const bool ok1 = ((((x1 ^ ohi[s]) | (y1 ^ olo[s])) & kmask) == 0) & (((uint32_t)(A1.y >> 32) & fbit) != 0);
-                    const bool hit = ok0 | ok1;  // (an eligible k-mer is filed in exactly one window)
-                    const u64 V = ok0 ? V0 : V1;
-                    const uint32_t seen_hi = ok0 ? (uint32_t)(A0.x >> 32) : (uint32_t)(A1.x >> 32);
-                    const uint32_t rb = ok0 ? b0 : b1;
-                    const int val = (int)((V >> (GS_REC_VAL_BITS * ((int)jj - 3 * jw))) & (GS_REC_MAX_VALUES - 1));
-                    node[s] = hit ? val : node[s];
-                    if (hit) {
-                        if (STRIPED && AGG) {
-                            if (mk.count_unique && ((mk.rec_seen[rb] >> jj) & 1u) == 0) {
-                                uint32_t *acc = wave_g + GS_ROW * s + 2 * (mp[s] + lane) + (ok0 ? 0 : 1);
-                                atomicOr(acc, 1u << jj);
-                                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                                const uint32_t w = *(volatile uint32_t *)acc;
-                                if ((w & (0u - w)) == (1u << jj)) atomicOr(mk.rec_seen + rb, w);
-                            }
-                        } else if (STRIPED) {
-                            if (mk.count_unique && ((mk.rec_seen[rb] >> jj) & 1u) == 0) atomicOr(mk.rec_seen + rb, 1u << jj);
-                        } else if (AGG) {
-                            if (mk.count_unique && (seen_hi & fbit) == 0) {
-                                // (the lanes of a minimizer occurrence share both buckets; occurrence = mp + lane inside the sub-round, < 80)
-                                uint32_t *acc = wave_g + GS_ROW * s + 2 * (mp[s] + lane) + (ok0 ? 0 : 1);
-                                atomicOr(acc, 1u << jj);
-                                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                                const uint32_t w = *(volatile uint32_t *)acc;
-                                if ((w & (0u - w)) == (1u << jj))  // the owner of the lowest bit sends the run's bits
-                                    atomicOr(const_cast<u64 *>(db.rec) + (u64)rb * GS_REC_WORDS, (u64)w << GS_REC_WIN_BITS);
-                            }
-                        } else if (mk.count_unique && (seen_hi & fbit) == 0)
-                            atomicOr(const_cast<u64 *>(db.rec) + (u64)rb * GS_REC_WORDS, 1ULL << (GS_REC_WIN_BITS + jj));
-                        if (mk.hit_counts != nullptr)
-                            atomicAdd(mk.hit_counts + ((u64)(bmask + 1u) * GS_SLOTS_PER_BUCKET + (u64)rb * GS_REC_SLOTS + (u64)jj), 1u);
-                    }
-                    pending = !hit & (((V0 | V1) & GS_REC_MORE) != 0);
-                }
-                GS_STAMP(8 + 2 * s, node[s])  // (phase 8 / 10: the record lines of sub-round 0 / 1)
-                // a k-mer whose window found no bucket (or that has two strand views) lives in the table
-                if (__ballot(pending) != 0) {
-                    const u64 h = gs_kmer_hash(ohi[s], olo[s], k, kmask);
-                    gs_lookup_rest<true, STRIPED>(db, (uint32_t)h & bmask, (h >> db.bucket_bits) << shift_rem, vmask2, pending, node[s], mk, wave_g);
-                }
-                GS_STAMP(9 + 2 * s, node[s])  // (phase 9 / 11: its walk of the overflow table)
-            }
-            return;
-        }
-    }
-    // ---- the ordinary table: one 64-byte bucket line per k-mer (stores without records: k < 19, partitions, > 2^21 values)
-    uint32_t bkt[NS];
-    u64 want[NS];
-    GsHalf bk[NS];
-#pragma unroll
-    for (int s = 0; s < NS; s++) {
-        const u64 h = gs_kmer_hash(fhi[s], flo[s], k, kmask);
-        bkt[s] = (uint32_t)h & bmask;
-        want[s] = (h >> db.bucket_bits) << shift_rem;
-        if (db.mgate == nullptr && db.gate != nullptr) {  // word gate (L2-resident), no false negatives
-            bool pass = false;
-            if (GS_ACT(act[s])) {
-                const u64 gbits = gs_gate_field_bits((uint32_t)(h >> GS_GATE_FIELD_SHIFT));
-                pass = (db.gate[(h >> db.bucket_bits) & db.gate_mask] & gbits) == gbits;
-            }
-            act[s] = __ballot(pass);
-        }
-        if (GS_ACT(act[s])) gs_load_half(db.table, bkt[s], 0, bk[s]);  // both sub-rounds' loads in flight together
-    }
-#pragma unroll
-    for (int s = 0; s < NS; s++) {
-        bool pending = false;
-        if (GS_ACT(act[s])) {
-            int vs = -1, sl = 0;
-            const bool done = gs_match_half(bk[s], want[s], vmask2, vs, sl);
-            if (vs >= 0) gs_take_hit<false>(db, bkt[s] * GS_SLOTS_PER_BUCKET + sl, vs, node[s], mk);
-            pending = !done;
-        }
-        gs_lookup_rest<false, false>(db, bkt[s], want[s], vmask2, pending, node[s], mk, wave_g);
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------
 // one read on one wave.  LONG = false: max <= 128 (one iteration, distinct nodes kept in registers).
@@ -1302,17 +755,6 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
             if (s_max[i]) atomicMax((u64 *)P.max_keys + ecopy * (size_t)nv + i, s_max[i]);            \
         for (int i = threadIdx.x; i < nv * GS_N_DCOLS; i += blockDim.x)                               \
             if (s_d[i] != 0.0) atomicAdd(P.dsums + ecopy * (size_t)nv * GS_N_DCOLS + i, s_d[i]);      \
-    }
-
-// STRIPED: the record table is split over several devices (GsDbDev::rec_biased); every wave keeps the stripe pointers in
-// LDS behind its hash rows, where a lane picks the one of its bucket with a single ds_read
-#define GS_STRIPE_TABLE(kernarg)                                                                                        \
-    if (STRIPED) {                                                                                                       \
-        if (lane < 2 * GS_MAX_STRIPES)                                                                                   \
-            reinterpret_cast<const u64 **>(s_g[wave_in_block] + 2 * GS_ROW)[lane] =                                      \
-                lane < GS_MAX_STRIPES ? (kernarg)->db.rec_biased[lane] : (kernarg)->db.tab_biased[lane - GS_MAX_STRIPES]; \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                                           \
-        __builtin_amdgcn_wave_barrier();                                                                                 \
     }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2452,795 +1894,6 @@ extern "C" hipError_t gs_launch_stat_reduce(const GsStatRec *recs, const void *c
 }
 
 // ---------------------------------------------------------------------------------------------------
-// DB-partitioned mode: the fused kernel is split into
-//   gs_encode_kernel      reads -> mixed key h of every k-mer position (GS_KEY_INVALID for windows with a bad base,
-//                         GS_KEY_MISS for k-mers the store-wide minimizer gate rules out)
-//   gs_probe_keys_kernel  keys -> node (value index / miss), run by the rank that OWNS the key's table partition
-//   gs_match_kernel<.., FROM_NODES = true>   per-read reduce over the routed-back node stream
-// with two all-to-all exchanges in between (genestrip_amd/distributed.py).
-// ---------------------------------------------------------------------------------------------------
-#define GS_KEY_INVALID (~0ULL)
-#define GS_KEY_MISS (~0ULL - 1)  // the minimizer gate already says "not stored": never routed, node = MISS
-#define GS_KEY_ROUTED(h) ((h) < GS_KEY_MISS)
-
-template <int KC>
-__global__ __launch_bounds__(GS_BLOCK) void gs_encode_kernel(GsEncodeParams P) {
-    __shared__ uint32_t s_g[GS_BLOCK / 64][2 * GS_ROW];  // 15-mer order hashes of the wave's current 128 + 16 positions
-    const int lane = gs_lane();
-    uint32_t *wave_g = s_g[threadIdx.x >> 6];
-    const int64_t wave_id = (int64_t)blockIdx.x * (GS_BLOCK / 64) + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * (GS_BLOCK / 64);
-    const int k = KC ? KC : P.k;  // KC = compile-time k (0: any k)
-    const uint32_t kmask = (1u << k) - 1u;
-    // software pipeline over the wave's reads: the first 192 bases of the next read are loaded while the current
-    // one is hashed (a read is a chain of dependent loads: offsets -> bases -> gate word)
-    u64 off = 0, pb = 0;
-    int L = 0;
-    uint32_t c[3] = {0, 0, 0};
-    if (wave_id < P.n_reads) {
-        off = P.off[wave_id];
-        L = (int)(P.off[wave_id + 1] - off);
-        pb = P.pos_off[wave_id];
-#pragma unroll
-        for (int i = 0; i < 3; i++) c[i] = 64 * i + lane < L ? P.seq[off + 64 * i + lane] : GS_FILL;
-    }
-    for (int64_t r = wave_id; r < P.n_reads; r += n_waves) {
-        const int max = L - k + 1;
-        const uint8_t *rd = P.seq + off;
-        const int64_t rn = r + n_waves;
-        u64 offN = 0, pbN = 0;
-        int LN = 0;
-        if (rn < P.n_reads) {
-            offN = P.off[rn];
-            LN = (int)(P.off[rn + 1] - offN);
-            pbN = P.pos_off[rn];
-        }
-        uint32_t cN[3] = {0, 0, 0};
-        for (int base = 0; base < max || base == 0; base += 128) {
-            u64 Bhi[3], Blo[3], Bbad[3];
-#pragma unroll
-            for (int i = 0; i < 3; i++) {
-                if (base == 0)
-                    gs_word_from_byte(c[i], Bhi[i], Blo[i], Bbad[i]);
-                else
-                    gs_load_word(rd, L, (base >> 6) + i, lane, Bhi[i], Blo[i], Bbad[i]);
-            }
-            if (base == 0 && rn < P.n_reads) {
-#pragma unroll
-                for (int i = 0; i < 3; i++) cN[i] = 64 * i + lane < LN ? P.seq[offN + 64 * i + lane] : GS_FILL;
-            }
-            if (max <= 0) break;
-            u64 key[2];
-            uint32_t fhi[2], flo[2];
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-                fhi[s] = (uint32_t)gs_funnel(Bhi[s], Bhi[s + 1], lane) & kmask;
-                flo[s] = (uint32_t)gs_funnel(Blo[s], Blo[s + 1], lane) & kmask;
-                const uint32_t wbad = (uint32_t)gs_funnel(Bbad[s], Bbad[s + 1], lane) & kmask;
-                key[s] = wbad ? GS_KEY_INVALID : gs_kmer_hash(fhi[s], flo[s], k, kmask);
-            }
-            if (P.mgate != nullptr) {
-                // the store's minimizer gate (which covers the keys of every partition) as in gs_probe_planes: k-mers
-                // it rules out are not routed at all
-                int mp[2];
-                uint32_t cf[2];
-                uint32_t rhi[2], rlo[2];
-#pragma unroll
-                for (int s = 0; s < 2; s++) {
-                    rhi[s] = __brev(fhi[s]) >> (32 - k);
-                    rlo[s] = (__brev(flo[s]) >> (32 - k)) ^ kmask;
-                }
-                gs_wave_minimizers<KC>(Bhi, Blo, fhi, flo, rhi, rlo, k, lane, wave_g, mp, cf);
-#pragma unroll
-                for (int s = 0; s < 2; s++) {
-                    if (base + 64 * s + lane < max && key[s] != GS_KEY_INVALID) {
-                        const uint32_t gh = gs_canon_hash(cf[s] >> 1);  // only the minimizer's hash is needed
-                        const uint32_t bits = gs_mgate_bits(gh);
-                        if ((P.mgate[gs_mgate_word(gh, P.mgate_bits)] & bits) != bits) key[s] = GS_KEY_MISS;
-                    }
-                }
-            }
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-                const int p = base + 64 * s + lane;
-                if (p < max) P.keys[pb + (u64)p] = key[s];
-            }
-        }
-        off = offN;
-        L = LN;
-        pb = pbN;
-#pragma unroll
-        for (int i = 0; i < 3; i++) c[i] = cN[i];
-    }
-}
-
-// ---- encode and routing in one pass: what gs_encode_kernel + gs_route_count_kernel + gs_route_scatter_kernel do through
-// an 8-byte key per k-mer POSITION that is written once and read twice.  Here a wave appends the keys of its reads
-// straight to the owners' send regions: it holds one chunk of GS_ROUTE_CHUNK slots per owner (cursor in LDS), takes a
-// new one with a single global atomic when the chunk cannot take a sub-round's keys (the rest of the old chunk becomes
-// sentinels), and pads its open chunks at the end.  Keys leave in no particular order inside an owner's region.
-template <int KC>
-__global__ __launch_bounds__(GS_BLOCK) void gs_encode_route_kernel(GsEncodeParams P, GsRouteParams R) {
-    __shared__ uint32_t s_g[GS_BLOCK / 64][2 * GS_ROW];
-    __shared__ unsigned long long s_base[GS_BLOCK / 64][64];  // per wave and owner: base of the chunk in hand
-    __shared__ uint32_t s_used[GS_BLOCK / 64][64];            // slots used in it (GS_ROUTE_CHUNK: none in hand)
-    const int lane = gs_lane();
-    const int wv = threadIdx.x >> 6;
-    uint32_t *wave_g = s_g[wv];
-    const int64_t wave_id = (int64_t)blockIdx.x * (GS_BLOCK / 64) + wv;
-    const int64_t n_waves = (int64_t)gridDim.x * (GS_BLOCK / 64);
-    const int k = KC ? KC : P.k;
-    const uint32_t kmask = (1u << k) - 1u;
-    const int n_parts = R.n_parts;
-    if (lane < n_parts) {
-        s_base[wv][lane] = 0;
-        s_used[wv][lane] = GS_ROUTE_CHUNK;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    for (int64_t r = wave_id; r < P.n_reads; r += n_waves) {
-        const u64 off = P.off[r];
-        const int L = (int)(P.off[r + 1] - off);
-        const u64 pb = P.pos_off[r];
-        const int max = L - k + 1;
-        const uint8_t *rd = P.seq + off;
-        for (int base = 0; base < max; base += 128) {
-            u64 Bhi[3], Blo[3], Bbad[3];
-#pragma unroll
-            for (int i = 0; i < 3; i++) gs_load_word(rd, L, (base >> 6) + i, lane, Bhi[i], Blo[i], Bbad[i]);
-            u64 key[2];
-            uint32_t fhi[2], flo[2];
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-                fhi[s] = (uint32_t)gs_funnel(Bhi[s], Bhi[s + 1], lane) & kmask;
-                flo[s] = (uint32_t)gs_funnel(Blo[s], Blo[s + 1], lane) & kmask;
-                const uint32_t wbad = (uint32_t)gs_funnel(Bbad[s], Bbad[s + 1], lane) & kmask;
-                key[s] = wbad ? GS_KEY_INVALID : gs_kmer_hash(fhi[s], flo[s], k, kmask);
-            }
-            if (P.mgate != nullptr) {
-                int mp[2];
-                uint32_t cf[2];
-                uint32_t rhi[2], rlo[2];
-#pragma unroll
-                for (int s = 0; s < 2; s++) {
-                    rhi[s] = __brev(fhi[s]) >> (32 - k);
-                    rlo[s] = (__brev(flo[s]) >> (32 - k)) ^ kmask;
-                }
-                gs_wave_minimizers<KC>(Bhi, Blo, fhi, flo, rhi, rlo, k, lane, wave_g, mp, cf);
-#pragma unroll
-                for (int s = 0; s < 2; s++) {
-                    if (base + 64 * s + lane < max && key[s] != GS_KEY_INVALID) {
-                        const uint32_t gh = gs_canon_hash(cf[s] >> 1);
-                        const uint32_t bits = gs_mgate_bits(gh);
-                        if ((P.mgate[gs_mgate_word(gh, P.mgate_bits)] & bits) != bits) key[s] = GS_KEY_MISS;
-                    }
-                }
-            }
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-                const int p = base + 64 * s + lane;
-                const bool in = p < max;
-                const bool routed = in && GS_KEY_ROUTED(key[s]);
-                if (in) R.nodes[pb + (u64)p] = key[s] == GS_KEY_INVALID ? GS_NODE_INVALID : GS_NODE_MISS;  // (routed: overwritten later)
-                const int owner = routed ? (int)((key[s] >> GS_OWNER_SHIFT) % (u64)n_parts) : -1;
-                u64 todo = __ballot(routed);
-                while (todo) {  // one owner after the other
-                    const int o = gs_readlane(owner, __builtin_ctzll(todo));
-                    const u64 mine = __ballot(owner == o);
-                    const uint32_t cnt = (uint32_t)__popcll(mine);
-                    uint32_t used = s_used[wv][o];
-                    u64 cbase = s_base[wv][o];
-                    if (used + cnt > GS_ROUTE_CHUNK) {
-                        // the rest of the chunk in hand becomes sentinels; a new chunk
-                        if (used < GS_ROUTE_CHUNK && cbase + GS_ROUTE_CHUNK <= R.cap)
-                            for (uint32_t j = used + (uint32_t)lane; j < GS_ROUTE_CHUNK; j += 64) {
-                                R.send_keys[(u64)o * R.cap + cbase + j] = GS_KEY_INVALID;
-                                R.send_idx[(u64)o * R.cap + cbase + j] = 0xffffffffu;
-                            }
-                        u64 nb = 0;
-                        if (lane == 0) nb = atomicAdd(&R.cursors[o], (u64)GS_ROUTE_CHUNK);
-                        cbase = ((u64)(uint32_t)gs_rfl((int)(nb >> 32)) << 32) | (uint32_t)gs_rfl((int)nb);
-                        used = 0;
-                        if (lane == 0) s_base[wv][o] = cbase;
-                    }
-                    const bool fits = cbase + GS_ROUTE_CHUNK <= R.cap;  // (else: the region is full, the host falls back)
-                    if (!fits && lane == 0) R.cursors[64] = 1;
-                    if (owner == o && fits) {
-                        const u64 at = (u64)o * R.cap + cbase + used + (u64)__popcll(mine & ((1ULL << lane) - 1));
-                        R.send_keys[at] = key[s];
-                        R.send_idx[at] = (uint32_t)(pb + (u64)p);
-                    }
-                    if (lane == 0) s_used[wv][o] = used + cnt;
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    todo &= ~mine;
-                }
-            }
-        }
-    }
-    // pad the chunks that are still open
-    for (int o = 0; o < n_parts; o++) {
-        const uint32_t used = s_used[wv][o];
-        const u64 cbase = s_base[wv][o];
-        if (used < GS_ROUTE_CHUNK && cbase + GS_ROUTE_CHUNK <= R.cap)
-            for (uint32_t j = used + (uint32_t)lane; j < GS_ROUTE_CHUNK; j += 64) {
-                R.send_keys[(u64)o * R.cap + cbase + j] = GS_KEY_INVALID;
-                R.send_idx[(u64)o * R.cap + cbase + j] = 0xffffffffu;
-            }
-    }
-}
-
-// scatter of the answers of one owner region: nodes[idx[i]] = back[i] (sentinel slots skipped)
-__global__ __launch_bounds__(256) void gs_unroute_region_kernel(const uint32_t *idx, const int32_t *back, int64_t n, int32_t *nodes) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t at = idx[i];
-        if (at != 0xffffffffu) nodes[at] = back[i];
-    }
-}
-
-extern "C" hipError_t gs_launch_encode_route(const GsEncodeParams *P, const GsRouteParams *R, int grid, hipStream_t stream) {
-    if (P->k == 31)
-        hipLaunchKernelGGL(gs_encode_route_kernel<31>, dim3(grid), dim3(GS_BLOCK), 0, stream, *P, *R);
-    else
-        hipLaunchKernelGGL(gs_encode_route_kernel<0>, dim3(grid), dim3(GS_BLOCK), 0, stream, *P, *R);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t gs_launch_unroute_region(const uint32_t *idx, const int32_t *back, int64_t n, int32_t *nodes, hipStream_t stream) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(gs_unroute_region_kernel, dim3((int)std::min<int64_t>((n + 255) / 256, 256 * 16)), dim3(256), 0, stream, idx, back, n, nodes);
-    return hipGetLastError();
-}
-
-// ---- routing of the keys to their owner ranks (counting sort by owner; order inside an owner group is arbitrary,
-// idx remembers where every routed key came from)
-__global__ __launch_bounds__(256) void gs_route_count_kernel(const u64 *keys, int64_t n, int n_parts, u64 *counts) {
-    __shared__ unsigned int s_cnt[64];
-    const int lane = gs_lane();
-    if (threadIdx.x < 64) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t base = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) & ~63LL; base < n; base += stride) {
-        const int64_t i = base + lane;
-        const u64 h = i < n ? keys[i] : GS_KEY_INVALID;
-        const int owner = GS_KEY_ROUTED(h) ? (int)((h >> GS_OWNER_SHIFT) % (u64)n_parts) : -1;
-        u64 todo = __ballot(owner >= 0);
-        while (todo) {  // one LDS atomic per wave and distinct owner
-            const int o = gs_readlane(owner, __builtin_ctzll(todo));
-            const u64 mine = __ballot(owner == o);
-            if (lane == 0) atomicAdd(&s_cnt[o], (unsigned int)__popcll(mine));
-            todo &= ~mine;
-        }
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < n_parts && s_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (u64)s_cnt[threadIdx.x]);
-}
-
-// tiles of 4096 keys per workgroup: ranks inside the tile come from LDS counters (one LDS atomic per wave and owner),
-// then ONE global atomic per owner and tile reserves the output range -- a single hot cursor would serialise the chip
-#define GS_ROUTE_T 16
-// nodes (may be NULL): the positions that are not routed get their node here already (miss / invalid window), so that
-// gs_unroute_kernel only has to scatter what comes back
-__global__ __launch_bounds__(256) void gs_route_scatter_kernel(const u64 *keys, int64_t n, int n_parts, u64 *cursors,
-                                                              u64 *send_keys, uint32_t *idx, int32_t *nodes) {
-    __shared__ unsigned int s_cnt[64];
-    __shared__ u64 s_base[64];
-    const int lane = gs_lane();
-    const int64_t tile = 256 * GS_ROUTE_T;
-    for (int64_t t0 = (int64_t)blockIdx.x * tile; t0 < n; t0 += (int64_t)gridDim.x * tile) {
-        if (threadIdx.x < 64) s_cnt[threadIdx.x] = 0;
-        __syncthreads();
-        u64 h[GS_ROUTE_T];
-        int owner[GS_ROUTE_T];
-        unsigned int lp[GS_ROUTE_T];
-#pragma unroll
-        for (int j = 0; j < GS_ROUTE_T; j++) {
-            const int64_t i = t0 + (int64_t)j * 256 + threadIdx.x;
-            h[j] = i < n ? keys[i] : GS_KEY_INVALID;
-            owner[j] = GS_KEY_ROUTED(h[j]) ? (int)((h[j] >> GS_OWNER_SHIFT) % (u64)n_parts) : -1;
-            if (nodes != nullptr && i < n && owner[j] < 0) nodes[i] = h[j] == GS_KEY_MISS ? GS_NODE_MISS : GS_NODE_INVALID;
-            lp[j] = 0;
-            u64 todo = __ballot(owner[j] >= 0);
-            while (todo) {
-                const int first = __builtin_ctzll(todo);
-                const int o = gs_readlane(owner[j], first);
-                const u64 mine = __ballot(owner[j] == o);
-                unsigned int b = 0;
-                if (lane == first) b = atomicAdd(&s_cnt[o], (unsigned int)__popcll(mine));
-                b = (unsigned int)gs_readlane((int)b, first);
-                if (owner[j] == o) lp[j] = b + (unsigned int)__popcll(mine & ((1ULL << lane) - 1));
-                todo &= ~mine;
-            }
-        }
-        __syncthreads();
-        if ((int)threadIdx.x < n_parts) s_base[threadIdx.x] = s_cnt[threadIdx.x] ? atomicAdd(&cursors[threadIdx.x], (u64)s_cnt[threadIdx.x]) : 0;
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < GS_ROUTE_T; j++) {
-            if (owner[j] >= 0) {
-                const u64 p = s_base[owner[j]] + lp[j];
-                send_keys[p] = h[j];
-                idx[p] = (uint32_t)(t0 + (int64_t)j * 256 + threadIdx.x);
-            }
-        }
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(256) void gs_unroute_kernel(const u64 *keys, const uint32_t *idx, const int32_t *back,
-                                                        int64_t n_routed, int32_t *nodes, int64_t n_keys, int phase) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    if (phase == 0)  // positions that were never routed: windows with a bad base, k-mers the gate ruled out
-                     // (only when gs_route_scatter_kernel has not written them already)
-        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_keys; i += stride)
-            nodes[i] = keys[i] == GS_KEY_MISS ? GS_NODE_MISS : GS_NODE_INVALID;
-    else
-        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_routed; i += stride) nodes[idx[i]] = back[i];
-}
-
-// one lane per key; marks the slot's seen bit like the fused kernel does
-__global__ __launch_bounds__(256) void gs_probe_keys_kernel(GsDbDev db, const u64 *keys, int64_t n, int32_t *nodes,
-                                                           int count_unique) {
-    const uint32_t vmask2 = 2u * ((1u << db.vbits) - 1u);
-    const int shift_rem = (int)db.vbits + 3;
-    const uint32_t bmask = (uint32_t)db.bucket_mask;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const u64 h = keys[i];
-        int node = h == GS_KEY_MISS ? GS_NODE_MISS : GS_NODE_INVALID;
-        if (GS_KEY_ROUTED(h)) {
-            node = GS_NODE_MISS;
-            bool cand = true;
-            if (db.gate != nullptr) {
-                const u64 g = gs_gate_bits(h);
-                cand = (db.gate[(h >> db.bucket_bits) & db.gate_mask] & g) == g;
-            }
-            const uint32_t home = (uint32_t)h & bmask;
-            const u64 want = (h >> db.bucket_bits) << shift_rem;
-            for (int disp = 0; cand && disp <= GS_MAX_DISP; disp++) {
-                const uint32_t b = (home + (uint32_t)disp) & bmask;
-                GsBucket bk;
-                gs_load_bucket(db.table, b, bk);
-                int vs = -1, sl = 0;
-                const bool done = gs_match_bucket(bk, want | ((u64)disp << (db.vbits + 1)), vmask2, vs, sl);
-                if (vs >= 0) {
-                    node = vs >> 1;
-                    if (count_unique && (vs & 1) == 0)
-                        atomicOr(const_cast<u64 *>(db.table) + (size_t)b * GS_SLOTS_PER_BUCKET + sl, 1ULL);
-                }
-                if (done) break;
-            }
-        }
-        nodes[i] = node;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Kraken-style segments (FastqKMerMatcher.printKrakenStyleOut, :597-611 / :391-394 / :452-454): the maximal runs
-// of equal node over the k-mer positions of a read.  WRITE = false counts them per read; WRITE = true stores
-// (code, start) of every run at seg_off[r] + i (code = value index, -1 miss "0", -2 INVALID "A").
-// ---------------------------------------------------------------------------------------------------
-// iterations [it0, it1) of one read: runs that start there, written behind out_base when WRITE; carry_last: node in front of it0
-template <bool WRITE, bool STRIPED>
-__device__ __forceinline__ uint32_t gs_segments_span(const GsSegParams &P, const uint8_t *rd, int L, int max, int it0, int it1, int &carry_last, u64 out_base,
-                                                     int lane, uint32_t *wave_g, int &first_node) {
-    const GsMark nomark = {0, nullptr, nullptr, nullptr};
-    uint32_t nseg = 0;
-    for (int it = it0; it < it1; it++) {
-        const int base = it << 7;
-        u64 Bhi[3], Blo[3], Bbad[3];
-#pragma unroll
-        for (int w = 0; w < 3; w++) gs_load_word(rd, L, 2 * it + w, lane, Bhi[w], Blo[w], Bbad[w]);
-        int node[2];
-        gs_probe_planes<0, STRIPED>(P.db, Bhi, Blo, Bbad, base, max, lane, node, wave_g, nomark);
-        if (it == it0) first_node = gs_readlane(node[0], 0);
-        const int up0 = __shfl_up(node[0], 1), up1 = __shfl_up(node[1], 1);
-        const int last0 = gs_readlane(node[0], 63);
-        const int prev[2] = {lane == 0 ? carry_last : up0, lane == 0 ? last0 : up1};
-#pragma unroll
-        for (int s = 0; s < 2; s++) {
-            const bool head = node[s] != GS_NODE_NONE && node[s] != prev[s];
-            const u64 H = __ballot(head);
-            if (WRITE && head) {
-                const u64 idx = out_base + nseg + (u64)__popcll(H & ((1ULL << lane) - 1));
-                P.seg_code[idx] = node[s];
-                P.seg_start[idx] = base + 64 * s + lane;
-            }
-            nseg += (uint32_t)__popcll(H);
-        }
-        const int last_p = (max - 1 < base + 127) ? max - 1 : base + 127;
-        carry_last = gs_readlane(((last_p - base) >> 6) ? node[1] : node[0], (last_p - base) & 63);
-    }
-    return nseg;
-}
-
-template <bool WRITE, bool STRIPED>
-__global__ __launch_bounds__(GS_BLOCK) void gs_segments_kernel(GsSegParams P) {
-    __shared__ __attribute__((aligned(8))) uint32_t s_g[GS_BLOCK / 64][2 * GS_ROW + (STRIPED ? GS_STRIPE_WORDS : 0)];
-    const GsDbDev &db = P.db;
-    const int lane = gs_lane();
-    const int wave_in_block = (int)(threadIdx.x >> 6);
-    GS_STRIPE_TABLE(&P)
-    const int64_t wave_id = (int64_t)blockIdx.x * (GS_BLOCK / 64) + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * (GS_BLOCK / 64);
-    const int k = db.k;
-    if (P.pieces != nullptr) {  // the pieces of the reads that were left out
-        for (int64_t i = wave_id; i < P.n_pieces; i += n_waves) {
-            const GsSegPiece pc = P.pieces[i];
-            const uint64_t *po = P.off + (int64_t)pc.read * P.off_stride;
-            const u64 off = po[0];
-            const int L = (int)(po[1] - off);
-            int carry_last = WRITE ? pc.carry : GS_NODE_NONE, first_node = GS_NODE_NONE;
-            const uint32_t nseg = gs_segments_span<WRITE, STRIPED>(P, P.seq + off, L, L - k + 1, pc.it0, pc.it0 + pc.n_iter, carry_last,
-                                                                   WRITE ? P.seg_off[pc.read] + pc.out_off : 0, lane, s_g[wave_in_block], first_node);
-            if (!WRITE && lane == 0) {
-                GsSegPieceOut o = {first_node, carry_last, nseg, 0};
-                P.piece_out[i] = o;
-            }
-        }
-        return;
-    }
-    for (int64_t r = wave_id; r < P.n_reads; r += n_waves) {
-        const uint64_t *po = P.off + r * P.off_stride;
-        const u64 off = po[0];
-        const int L = (int)(po[1] - off);
-        const int max = L - k + 1;
-        if (max >= P.huge_min) {
-            if (!WRITE && lane == 0) P.seg_count[r] = GS_SEG_HUGE;
-            continue;
-        }
-        int carry_last = GS_NODE_NONE, first_node;
-        const uint32_t nseg = gs_segments_span<WRITE, STRIPED>(P, P.seq + off, L, max, 0, max > 0 ? (max + 127) >> 7 : 0, carry_last, WRITE ? P.seg_off[r] : 0, lane,
-                                                               s_g[wave_in_block], first_node);
-        if (!WRITE && lane == 0) P.seg_count[r] = nseg;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// unique k-mers per value: scan the bitmap, look the set slots up in the table
-// (KMerUniqueCounterBits.getUniqueKmerCounts, C/store/KMerUniqueCounterBits.java:146-163)
-// ---------------------------------------------------------------------------------------------------
-#define GS_UNIQ_LDS 8192  // value indices whose unique counters are privatised per workgroup
-__global__ __launch_bounds__(256) void gs_unique_count_kernel(const u64 *table, const uint32_t *bitmap, int64_t n_slots,
-                                                             uint32_t vbits, int32_t n_values, u64 *unique) {
-    __shared__ unsigned int s_cnt[GS_UNIQ_LDS];
-    const bool lds = n_values <= GS_UNIQ_LDS;
-    if (lds) {
-        for (int i = threadIdx.x; i < n_values; i += blockDim.x) s_cnt[i] = 0;
-        __syncthreads();
-    }
-    const u64 vmask = (1ULL << vbits) - 1;
-    const int64_t n_words = (n_slots + 31) / 32;
-    for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n_words; w += (int64_t)gridDim.x * blockDim.x) {
-        uint32_t bits = bitmap[w];
-        while (bits) {
-            const int b = __builtin_ctz(bits);
-            bits &= bits - 1;
-            const u64 s = table[w * 32 + b];
-            const int vi = (int)((s >> 1) & vmask) - 1;
-            if (vi >= 0) {
-                if (lds)
-                    atomicAdd(&s_cnt[vi], 1u);
-                else
-                    atomicAdd(&unique[vi], 1ULL);
-            }
-        }
-    }
-    if (lds) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < n_values; i += blockDim.x)
-            if (s_cnt[i]) atomicAdd(&unique[i], (u64)s_cnt[i]);
-    }
-}
-
-// seen bits of the slots -> compact bitmap (bit i = slot i); one wave per 64 slots
-__global__ __launch_bounds__(256) void gs_bitmap_extract_kernel(const u64 *table, int64_t n_slots, uint32_t *bitmap) {
-    const int lane = gs_lane();
-    for (int64_t base = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) & ~63LL; base < n_slots;
-         base += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i = base + lane;
-        const u64 m = __ballot(i < n_slots && (table[i] & 1ULL));
-        if (lane == 0) bitmap[base >> 5] = (uint32_t)m;
-        if (lane == 1 && base + 32 < n_slots) bitmap[(base >> 5) + 1] = (uint32_t)(m >> 32);
-    }
-}
-
-__global__ __launch_bounds__(256) void gs_clear_seen_kernel(u64 *table, int64_t n_slots) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_slots; i += (int64_t)gridDim.x * blockDim.x) {
-        const u64 s = table[i];
-        if (s & 1ULL) table[i] = s & ~1ULL;
-    }
-}
-
-// ---- the same three sweeps over the super-k-mer records: the compact bitmap holds one 32-bit word per record bucket
-// (bit j = seen bit of offset j) behind the words of the table slots.  The sweeps stream the record lines with 16-byte
-// loads of consecutive threads (a thread per line and 8 bytes of it costs one 64-byte request per lane: ~4x slower on a
-// 9 GB table); thread 4 b holds words 0 and 1 of bucket b.
-__global__ __launch_bounds__(256) void gs_rec_bitmap_extract_kernel(const u64 *rec, int64_t n_rec, uint32_t *bitmap_rec) {
-    const int64_t n = n_rec * (GS_REC_WORDS / 2);
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
-        const gs_u64x2 v = reinterpret_cast<const gs_u64x2 *>(rec)[t];
-        if ((t & 3) == 0) bitmap_rec[t >> 2] = (uint32_t)(v.x >> GS_REC_WIN_BITS);
-    }
-}
-
-// 8 lanes per bucket: lane g holds word g of the line (one coalesced 64-byte request per bucket, only for buckets with a
-// seen bit); lanes 2..7 look at the three value fields of their word
-__global__ __launch_bounds__(256) void gs_rec_unique_count_kernel(const u64 *rec, const uint32_t *bitmap_rec, int64_t n_rec,
-                                                                 int32_t n_values, u64 *unique) {
-    __shared__ unsigned int s_cnt[GS_UNIQ_LDS];
-    const bool lds = n_values <= GS_UNIQ_LDS;
-    if (lds) {
-        for (int i = threadIdx.x; i < n_values; i += blockDim.x) s_cnt[i] = 0;
-        __syncthreads();
-    }
-    const int g = (int)(threadIdx.x & 7);
-    const int64_t groups = ((int64_t)gridDim.x * blockDim.x) >> 3;
-    // eight lanes per bucket; four buckets per group and iteration with their loads in flight together (the loop is bound by
-    // the latency of bitmap word -> record line, not by bytes)
-    for (int64_t b0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 3; b0 < n_rec; b0 += 4 * groups) {
-        uint32_t bits[4];
-        u64 w[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int64_t bb = b0 + u * groups;
-            bits[u] = bb < n_rec ? bitmap_rec[bb] : 0u;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) w[u] = bits[u] ? rec[(b0 + u * groups) * GS_REC_WORDS + g] : 0;
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const u64 w1 = __shfl(w[u], 1, 8);
-            const uint32_t bt = bits[u] & (uint32_t)(w1 >> GS_REC_WIN_BITS);  // only offsets that hold a k-mer (a merged bitmap comes from other ranks)
-            if (g >= 2 && bt) {
-                // the three k-mers of a value word usually carry the same value index: one atomic for them together
-                int v[3], c[3];
-#pragma unroll
-                for (int i = 0; i < 3; i++) {
-                    const int vi = (int)((w[u] >> (GS_REC_VAL_BITS * i)) & (GS_REC_MAX_VALUES - 1));
-                    v[i] = (((bt >> (3 * (g - 2) + i)) & 1u) && vi < n_values) ? vi : -1;
-                    c[i] = 1;
-                }
-                if (v[1] >= 0 && v[1] == v[0]) {
-                    c[0]++;
-                    v[1] = -1;
-                }
-                if (v[2] >= 0 && v[2] == v[0]) {
-                    c[0]++;
-                    v[2] = -1;
-                } else if (v[2] >= 0 && v[2] == v[1]) {
-                    c[1]++;
-                    v[2] = -1;
-                }
-#pragma unroll
-                for (int i = 0; i < 3; i++) {
-                    if (v[i] >= 0) {
-                        if (lds)
-                            atomicAdd(&s_cnt[v[i]], (unsigned int)c[i]);
-                        else
-                            atomicAdd(&unique[v[i]], (u64)c[i]);
-                    }
-                }
-            }
-        }
-    }
-    if (lds) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < n_values; i += blockDim.x)
-            if (s_cnt[i]) atomicAdd(&unique[i], (u64)s_cnt[i]);
-    }
-}
-
-__global__ __launch_bounds__(256) void gs_rec_clear_seen_kernel(u64 *rec, int64_t n_rec) {
-    const u64 M47 = (1ULL << GS_REC_WIN_BITS) - 1;
-    const int64_t n = n_rec * (GS_REC_WORDS / 2);
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
-        const gs_u64x2 v = reinterpret_cast<const gs_u64x2 *>(rec)[t];
-        if ((t & 3) == 0 && (v.x >> GS_REC_WIN_BITS)) rec[2 * t] = v.x & M47;
-    }
-}
-
-__global__ __launch_bounds__(256) void gs_bitmap_or_kernel(uint32_t *dst, const uint32_t *parts, int64_t n_words, int64_t n_parts) {
-    for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n_words; w += (int64_t)gridDim.x * blockDim.x) {
-        uint32_t v = dst[w];
-        for (int64_t p = 0; p < n_parts; p++) v |= parts[p * n_words + w];
-        dst[w] = v;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// filter
-// ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 gs_spread32(uint32_t v) {  // bit i -> bit 2i
-    u64 x = v;
-    x = (x | (x << 16)) & 0x0000FFFF0000FFFFULL;
-    x = (x | (x << 8)) & 0x00FF00FF00FF00FFULL;
-    x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0FULL;
-    x = (x | (x << 2)) & 0x3333333333333333ULL;
-    x = (x | (x << 1)) & 0x5555555555555555ULL;
-    return x;
-}
-
-// canonical k-mer in the REFERENCE's interleaved encoding (the value the Bloom hashes see)
-__device__ __forceinline__ int64_t gs_canonical_java(uint32_t fhi, uint32_t flo, int k, uint32_t kmask) {
-    const uint32_t rhi = __brev(fhi) >> (32 - k);
-    const uint32_t rlo = __brev(flo) >> (32 - k);
-    const u64 fwd = (gs_spread32(rhi) << 1) | gs_spread32(rlo);                     // first base in the top bits
-    const u64 rev = (gs_spread32(fhi) << 1) | gs_spread32((flo ^ kmask) & kmask);   // complement, reversed
-    return (int64_t)(fwd > rev ? fwd : rev);
-}
-
-__device__ __forceinline__ int64_t gs_murmur64(int64_t data_, int64_t base) {  // MurmurHash3DropIn.java:60-87
-    const u64 data = (u64)data_;
-    u64 hash = (u64)base;
-    u64 kk = __builtin_bswap64(data);
-    kk *= 0x87c37b91114253d5ULL;
-    kk = (kk << 31) | (kk >> 33);
-    kk *= 0x4cf5ad432745937fULL;
-    hash ^= kk;
-    hash = ((hash << 27) | (hash >> 37)) * 5 + 0x52dce729ULL;
-    hash ^= 8;
-    hash ^= hash >> 33;
-    hash *= 0xff51afd7ed558ccdULL;
-    hash ^= hash >> 33;
-    hash *= 0xc4ceb9fe1a85ec53ULL;
-    hash ^= hash >> 33;
-    return (int64_t)(hash ^ data);
-}
-
-// bit `i`-th hash of `key` in the filter (XOR or Murmur kind); factors come from the block's LDS copy
-__device__ __forceinline__ bool gs_filter_bit(const GsFilterParams &P, const uint32_t *words32, const int64_t *factors,
-                                              int64_t key, int i) {
-    const int64_t f = factors[i];
-    const int64_t h = P.kind == GS_BLOOM_XOR ? (f ^ key) : gs_murmur64(key, f);
-    const u64 idx = gs_absmod(h, P.bits, P.magic, P.magic_shift);
-    return ((words32[(uint32_t)(idx >> 5)] >> (idx & 31)) & 1u) != 0;
-}
-
-#define GS_FILTER_MAX_HASHES 128
-
-__global__ __launch_bounds__(GS_BLOCK) __attribute__((amdgpu_waves_per_eu(GS_WAVES, GS_WAVES))) void gs_filter_kernel(GsFilterParams P) {
-    __shared__ u64 s_fkey[GS_BLOCK / 64][16];
-    __shared__ u64 s_fcand[GS_BLOCK / 64][64];
-    __shared__ int64_t s_factors[GS_FILTER_MAX_HASHES];
-    for (int i = threadIdx.x; i < P.n_hashes && i < GS_FILTER_MAX_HASHES; i += blockDim.x) s_factors[i] = P.factors[i];
-    __syncthreads();
-    const int lane = gs_lane();
-    const int wave_in_block = threadIdx.x >> 6;
-    const int64_t wave_id = (int64_t)blockIdx.x * (GS_BLOCK / 64) + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * (GS_BLOCK / 64);
-    const int k = P.k;
-    const uint32_t kmask = (1u << k) - 1u;
-    // bit i of the filter = bit (i & 31) of 32-bit word i >> 5 (little endian): a dword load with a scalar base and a
-    // 32-bit lane offset is the cheapest scattered load there is (XOR / Murmur filters are limited to 2^37 bits)
-    const uint32_t *words32 = reinterpret_cast<const uint32_t *>(P.words);
-    const int64_t n_reads = (P.skip != nullptr && *P.skip != 0) ? 0 : P.n_reads;
-    for (int64_t r = wave_id; r < n_reads; r += n_waves) {
-        const uint64_t *po = P.off + r * P.off_stride;
-        const u64 off = po[0];
-        const int L = (int)(po[1] - off);
-        const int max = L - k + 1;
-        const uint8_t *rd = P.seq + off;
-        int accept = 0;
-        if (max > 0) {
-            const int pos_thr = P.min_pos_count > 0 ? P.min_pos_count : (int)((double)max * P.positive_ratio);
-            const int need = pos_thr > 1 ? pos_thr : 1;
-            int members = 0;
-            u64 hi0, lo0, bad0;
-            gs_load_word(rd, L, 0, lane, hi0, lo0, bad0);
-            for (int round = 0; round * 64 < max && members < need; round++) {
-                u64 hi1, lo1, bad1;
-                gs_load_word(rd, L, round + 1, lane, hi1, lo1, bad1);
-                const int p = 64 * round + lane;
-                const uint32_t fhi = (uint32_t)gs_funnel(hi0, hi1, lane) & kmask;
-                const uint32_t flo = (uint32_t)gs_funnel(lo0, lo1, lane) & kmask;
-                const uint32_t wbad = (uint32_t)gs_funnel(bad0, bad1, lane) & kmask;
-                const bool valid_lane = p < max && wbad == 0;
-                const int64_t key = gs_canonical_java(fhi, flo, k, kmask);
-                // A read that comes from the indexed genomes is accepted by its first few k-mers, so the first round
-                // looks at every 8th position before it pays for all of them: an accepted read then costs ~60 filter
-                // lines instead of ~250, a rejected one pays one extra round trip.  Every position is still examined
-                // at most once and accept <=> #members >= need is unchanged.
-                for (int pass = round == 0 ? 0 : 1; pass < 2 && members < need; pass++) {
-                    bool alive = valid_lane && (round != 0 || (((lane & 7) == 0) == (pass == 0)));
-                    if (P.kind == GS_BLOOM_BLOCKED) {
-                        if (alive) {  // BlockedKMerBloomFilter.containsLong :181-199
-                            const int64_t h0 = P.factors[0] ^ key;
-                            const u64 start = gs_absmod(h0, P.bits, P.magic, P.magic_shift);
-                            u64 uh = (u64)h0;
-                            uh ^= (uh << 32) | (uh >> 32);
-                            const int64_t sh = (int64_t)uh;
-                            const u64 m1 = (1ULL << (sh & 63)) | (1ULL << ((sh >> 6) & 63));
-                            const u64 m2 = (1ULL << ((sh >> 12) & 63)) | (1ULL << ((sh >> 18) & 63));
-                            const u64 a = P.words[start];
-                            const u64 b = P.words[start + 1 + (uh >> 60)];
-                            alive = ((m1 & a) == m1) && ((m2 & b) == m2);
-                        }
-                    } else {
-                        // AbstractKMerBloomFilter.containsLong :209-216.  accept <=> #members >= need, and a member is a
-                        // k-mer whose n_hashes bits are all set; in which order the bits are looked at is free.  A
-                        // scattered load costs the CU about the same whether 1 or 64 lanes take part, so the work is
-                        // arranged to keep the lanes of every load busy:
-                        //   1. hashes 0..2 per lane (drops ~88 % of the non-members of a half-full filter),
-                        //   2. the survivors, 16 at a time, are spread over the wave: 4 lanes per survivor look at
-                        //      hashes 3..6 in ONE load (keys travel through LDS),
-                        //   3. what is still alive is a candidate: the lanes look at the next 8 hashes of one
-                        //      candidate in one load (a false candidate rarely gets further), then at all the rest,
-                        //      candidate after candidate until `need` members are confirmed.
-                        // Measured on the 47 M-key index filter: 58 -> 12 load instructions and 153 -> ~180 filter
-                        // lines per read, 59.8 -> 38.3 ms per 10 M reads; the kernel now runs at the fabric's
-                        // random-line rate instead of at the CU's rate of (mostly empty) load instructions.
-                        const int nh = P.n_hashes;
-                        const int S = 3;  // per-lane steps
-                        for (int i = 0; i < S && i < nh && __ballot(alive) != 0; i++) {
-                            if (alive) alive = gs_filter_bit(P, words32, s_factors, key, i);
-                        }
-                        u64 rem = __ballot(alive);
-                        int confirmed = 0;
-                        if (nh <= S) {
-                            confirmed = __popcll(rem);
-                            rem = 0;
-                        }
-                        const int T = nh - S < 4 ? nh - S : 4;
-                        int nc = 0, cdone = 0;
-                        u64 *fkey = s_fkey[wave_in_block], *fcand = s_fcand[wave_in_block];
-                        while (rem != 0 && members + confirmed < need) {
-                            const int rank = __popcll(rem & ((1ULL << lane) - 1));
-                            const bool in_batch = ((rem >> lane) & 1ULL) && rank < 16;
-                            const u64 batch = __ballot(in_batch);
-                            const int nb = __popcll(batch);
-                            if (in_batch) fkey[rank] = (u64)key;
-                            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                            __builtin_amdgcn_wave_barrier();
-                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                            const int j = lane >> 2, t = lane & 3;
-                            const bool active = j < nb && t < T;
-                            bool bit = true;
-                            u64 jkey = 0;
-                            if (j < nb) jkey = fkey[j];
-                            if (active) bit = gs_filter_bit(P, words32, s_factors, (int64_t)jkey, S + t);
-                            const u64 okm = __ballot(bit);
-                            u64 pass4 = okm & (okm >> 1) & (okm >> 2) & (okm >> 3) & 0x1111111111111111ULL;
-                            pass4 &= nb >= 16 ? ~0ULL : ((1ULL << (4 * nb)) - 1);  // groups beyond the batch are idle
-                            if (((pass4 >> lane) & 1ULL) != 0) fcand[nc + __popcll(pass4 & ((1ULL << lane) - 1))] = jkey;
-                            nc += __popcll(pass4);
-                            rem &= ~batch;
-                            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                            __builtin_amdgcn_wave_barrier();
-                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                            while (cdone < nc && members + confirmed < need) {
-                                const int64_t ckey = (int64_t)fcand[cdone++];
-                                bool all = true;
-                                {
-                                    const int i = S + T + lane;  // a first slice of 8 hashes
-                                    const bool b = (lane < 8 && i < nh) ? gs_filter_bit(P, words32, s_factors, ckey, i) : true;
-                                    all = __ballot(b) == ~0ULL;
-                                }
-                                for (int base = S + T + 8; base < nh && all; base += 64) {
-                                    const int i = base + lane;
-                                    const bool b = i < nh ? gs_filter_bit(P, words32, s_factors, ckey, i) : true;
-                                    all = __ballot(b) == ~0ULL;
-                                }
-                                confirmed += all ? 1 : 0;
-                            }
-                            __builtin_amdgcn_wave_barrier();  // fkey / fcand are rewritten by the next batch
-                        }
-                        members += confirmed;
-                        alive = false;  // already counted
-                    }
-                    members += __popcll(__ballot(alive));
-                }
-                hi0 = hi1;
-                lo0 = lo1;
-                bad0 = bad1;
-            }
-            accept = members >= need;
-        }
-        if (lane == 0) P.accept[r] = (uint8_t)accept;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
 // launchers (called from gs_api.cpp)
 // ---------------------------------------------------------------------------------------------------
 static size_t gs_stats_lds_bytes(int n_values) {
@@ -3467,123 +2120,4 @@ extern "C" int gs_match_long_occupancy(int n_values) {
                        ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gs_match_long_kernel<true, false, true, true>, GS_BLOCK, gs_stats_lds_bytes(n_values))
                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gs_match_long_kernel<false, false, true, true>, GS_BLOCK, gs_stats_lds_bytes(n_values));
     return e == hipSuccess ? n : 0;
-}
-
-extern "C" int gs_filter_occupancy() {
-    int n = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gs_filter_kernel, GS_BLOCK, 0);
-    return e == hipSuccess ? n : 0;
-}
-
-// the compact bitmap: (n_slots + 31) / 32 words for the table slots, then one word per record bucket (rec may be NULL)
-extern "C" hipError_t gs_launch_unique_count(const u64 *table, const uint32_t *bitmap, int64_t n_slots, uint32_t vbits,
-                                              int32_t n_values, u64 *unique, const u64 *rec, int64_t n_rec, hipStream_t stream) {
-    int64_t n_words = (n_slots + 31) / 32;
-    int grid = (int)((n_words + 255) / 256);
-    if (grid > 4096) grid = 4096;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(gs_unique_count_kernel, dim3(grid), dim3(256), 0, stream, table, bitmap, n_slots, vbits, n_values, unique);
-    if (rec != nullptr && n_rec > 0) {
-        grid = (int)std::min<int64_t>((n_rec * 8 + 255) / 256, 2048);
-        hipLaunchKernelGGL(gs_rec_unique_count_kernel, dim3(grid), dim3(256), 0, stream, rec, bitmap + n_words, n_rec, n_values, unique);
-    }
-    return hipGetLastError();
-}
-
-// one stripe of a striped store: `rec` = the stripe's lines, `bitmap_rec` = the bitmap words of ITS buckets
-extern "C" hipError_t gs_launch_rec_unique_count(const u64 *rec, const uint32_t *bitmap_rec, int64_t n_rec, int32_t n_values,
-                                                  u64 *unique, hipStream_t stream) {
-    if (n_rec <= 0) return hipSuccess;
-    const int grid = (int)std::min<int64_t>((n_rec * 8 + 255) / 256, 2048);
-    hipLaunchKernelGGL(gs_rec_unique_count_kernel, dim3(grid), dim3(256), 0, stream, rec, bitmap_rec, n_rec, n_values, unique);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t gs_launch_bitmap_extract(const u64 *table, int64_t n_slots, uint32_t *bitmap, const u64 *rec, int64_t n_rec,
-                                                hipStream_t stream) {
-    hipLaunchKernelGGL(gs_bitmap_extract_kernel, dim3(4096), dim3(256), 0, stream, table, n_slots, bitmap);
-    if (rec != nullptr && n_rec > 0)
-        hipLaunchKernelGGL(gs_rec_bitmap_extract_kernel, dim3((int)std::min<int64_t>((n_rec * 4 + 255) / 256, 8192)), dim3(256), 0, stream,
-                           rec, n_rec, bitmap + (n_slots + 31) / 32);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t gs_launch_clear_seen(u64 *table, int64_t n_slots, u64 *rec, int64_t n_rec, hipStream_t stream) {
-    hipLaunchKernelGGL(gs_clear_seen_kernel, dim3(4096), dim3(256), 0, stream, table, n_slots);
-    if (rec != nullptr && n_rec > 0)
-        hipLaunchKernelGGL(gs_rec_clear_seen_kernel, dim3((int)std::min<int64_t>((n_rec * 4 + 255) / 256, 8192)), dim3(256), 0, stream, rec, n_rec);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t gs_launch_bitmap_or(uint32_t *dst, const uint32_t *parts, int64_t n_words, int64_t n_parts,
-                                           hipStream_t stream) {
-    int grid = (int)((n_words + 255) / 256);
-    if (grid > 4096) grid = 4096;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(gs_bitmap_or_kernel, dim3(grid), dim3(256), 0, stream, dst, parts, n_words, n_parts);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t gs_launch_encode(const GsEncodeParams *P, int grid, hipStream_t stream) {
-    if (P->k == 31)
-        hipLaunchKernelGGL(gs_encode_kernel<31>, dim3(grid), dim3(GS_BLOCK), 0, stream, *P);
-    else
-        hipLaunchKernelGGL(gs_encode_kernel<0>, dim3(grid), dim3(GS_BLOCK), 0, stream, *P);
-    return hipGetLastError();
-}
-
-static int gs_stream_grid(int64_t n) {
-    int grid = (int)std::min<int64_t>((n + 255) / 256, 256 * 16);
-    return grid < 1 ? 1 : grid;
-}
-
-extern "C" hipError_t gs_launch_route_count(const u64 *keys, int64_t n, int n_parts, u64 *counts, hipStream_t stream) {
-    hipLaunchKernelGGL(gs_route_count_kernel, dim3(gs_stream_grid(n)), dim3(256), 0, stream, keys, n, n_parts, counts);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t gs_launch_route_scatter(const u64 *keys, int64_t n, int n_parts, u64 *cursors, u64 *send_keys,
-                                               uint32_t *idx, int32_t *nodes, hipStream_t stream) {
-    int grid = (int)std::min<int64_t>((n + 256 * GS_ROUTE_T - 1) / (256 * GS_ROUTE_T), 256 * 8);
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(gs_route_scatter_kernel, dim3(grid), dim3(256), 0, stream, keys, n, n_parts, cursors, send_keys, idx,
-                       nodes);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t gs_launch_unroute(const u64 *keys, const uint32_t *idx, const int32_t *back, int64_t n_routed,
-                                         int32_t *nodes, int64_t n_keys, hipStream_t stream) {
-    if (keys != nullptr)  // (NULL: gs_route_scatter_kernel has filled in the unrouted positions)
-        hipLaunchKernelGGL(gs_unroute_kernel, dim3(gs_stream_grid(n_keys)), dim3(256), 0, stream, keys, idx, back, n_routed,
-                           nodes, n_keys, 0);
-    if (n_routed > 0)
-        hipLaunchKernelGGL(gs_unroute_kernel, dim3(gs_stream_grid(n_routed)), dim3(256), 0, stream, keys, idx, back,
-                           n_routed, nodes, n_keys, 1);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t gs_launch_probe_keys(const GsDbDev *db, const u64 *keys, int64_t n, int32_t *nodes, int count_unique,
-                                            hipStream_t stream) {
-    int grid = (int)std::min<int64_t>((n + 255) / 256, 256 * 24);
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(gs_probe_keys_kernel, dim3(grid), dim3(256), 0, stream, *db, keys, n, nodes, count_unique);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t gs_launch_segments(const GsSegParams *P, int write, int grid, hipStream_t stream) {
-    if (P->db.n_parts > 1) {
-        if (write)
-            hipLaunchKernelGGL((gs_segments_kernel<true, true>), dim3(grid), dim3(GS_BLOCK), 0, stream, *P);
-        else
-            hipLaunchKernelGGL((gs_segments_kernel<false, true>), dim3(grid), dim3(GS_BLOCK), 0, stream, *P);
-    } else if (write)
-        hipLaunchKernelGGL((gs_segments_kernel<true, false>), dim3(grid), dim3(GS_BLOCK), 0, stream, *P);
-    else
-        hipLaunchKernelGGL((gs_segments_kernel<false, false>), dim3(grid), dim3(GS_BLOCK), 0, stream, *P);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t gs_launch_filter(const GsFilterParams *P, int grid, hipStream_t stream) {
-    hipLaunchKernelGGL(gs_filter_kernel, dim3(grid), dim3(GS_BLOCK), 0, stream, *P);
-    return hipGetLastError();
 }

@@ -22,7 +22,8 @@
 // This file is also compiled for the HOST, by tests/native/kraken_emulate.cpp (tests/test_krakenlines_cpu.py): g++ with a stand-in
 // for <hip/hip_runtime.h> in which a block is 256 real threads, under AddressSanitizer.  Keep to the constructs that stand-in knows
 // (tests/native/kraken_emulate_hip.h: ballot, shuffles, __syncthreads, atomicAdd on u64, __shared__ arrays inside a kernel) or
-// extend it with the kernel; the same holds for what gs_launch.h, gs_params.h and gs_scan.h pull in.
+// extend it with the kernel; the same holds for what gs_launch.h, gs_params.h and gs_scan.h pull in (gs_wave.h, the wave helpers of the
+// match, route, segments, seen and filter units, is not among it and is not written for the stand-in).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

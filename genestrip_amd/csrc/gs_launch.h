@@ -10,7 +10,7 @@
 
 typedef unsigned long long u64;
 
-// ---- parameter blocks (the ones of gs_kernels.hip and gs_text.hip: gs_params.h)
+// ---- parameter blocks (the ones of gs_kernels.hip, gs_route.hip, gs_segments.hip, gs_filter.hip and gs_text.hip: gs_params.h)
 struct GsExportParams {
     const u64 *rec;        // this handle's record lines (GS_REC_WORDS words each), n_rec of them
     int64_t n_rec;
@@ -87,7 +87,7 @@ struct GsSizeParams {
 
 extern "C" {
 
-// ---- gs_kernels.hip
+// ---- gs_kernels.hip: the match kernels and their statistics
 hipError_t gs_launch_match(const GsMatchParams *P, int grid, hipStream_t stream);
 hipError_t gs_launch_match_huge(const GsMatchParams *P, int grid, hipStream_t stream);
 hipError_t gs_launch_match_wide(const GsMatchParams *P, int ns, int n_cu, hipStream_t stream);
@@ -95,14 +95,12 @@ int gs_match_wide_mask(const GsMatchParams *P);
 hipError_t gs_launch_classify(const GsMatchParams *P, hipStream_t stream);
 hipError_t gs_launch_fold_stats(long long *sums, unsigned long long *maxk, double *dsums, long long nv, int copies, hipStream_t stream);
 hipError_t gs_launch_match_long(const GsMatchParams *P, int grid, int32_t *scratch, uint32_t *serial, hipStream_t stream);
-hipError_t gs_launch_unique_count(const u64 *table, const uint32_t *bitmap, int64_t n_slots, uint32_t vbits, int32_t n_values, u64 *unique,
-                                  const u64 *rec, int64_t n_rec, hipStream_t stream);
-hipError_t gs_launch_rec_unique_count(const u64 *rec, const uint32_t *bitmap_rec, int64_t n_rec, int32_t n_values, u64 *unique,
-                                      hipStream_t stream);
-hipError_t gs_launch_clear_seen(u64 *table, int64_t n_slots, u64 *rec, int64_t n_rec, hipStream_t stream);
-hipError_t gs_launch_bitmap_extract(const u64 *table, int64_t n_slots, uint32_t *bitmap, const u64 *rec, int64_t n_rec, hipStream_t stream);
-hipError_t gs_launch_bitmap_or(uint32_t *dst, const uint32_t *parts, int64_t n_words, int64_t n_parts, hipStream_t stream);
-hipError_t gs_launch_segments(const GsSegParams *P, int write, int grid, hipStream_t stream);
+hipError_t gs_launch_stat_reduce(const GsStatRec *recs, const void *count, int64_t n_max, int n_values, void *sums, void *maxk, void *dsums,
+                                 int32_t *vi_scratch, hipStream_t stream);
+int gs_match_occupancy(int n_values);
+int gs_match_long_occupancy(int n_values);
+
+// ---- gs_route.hip: the DB-partitioned mode
 hipError_t gs_launch_encode(const GsEncodeParams *P, int grid, hipStream_t stream);
 hipError_t gs_launch_encode_route(const GsEncodeParams *P, const GsRouteParams *R, int grid, hipStream_t stream);
 hipError_t gs_launch_unroute_region(const uint32_t *idx, const int32_t *back, int64_t n, int32_t *nodes, hipStream_t stream);
@@ -112,11 +110,21 @@ hipError_t gs_launch_route_scatter(const u64 *keys, int64_t n, int n_parts, u64 
 hipError_t gs_launch_unroute(const u64 *keys, const uint32_t *idx, const int32_t *back, int64_t n_routed, int32_t *nodes, int64_t n_keys,
                              hipStream_t stream);
 hipError_t gs_launch_probe_keys(const GsDbDev *db, const u64 *keys, int64_t n, int32_t *nodes, int count_unique, hipStream_t stream);
+
+// ---- gs_segments.hip
+hipError_t gs_launch_segments(const GsSegParams *P, int write, int grid, hipStream_t stream);
+
+// ---- gs_seen.hip: the seen bits of a store
+hipError_t gs_launch_unique_count(const u64 *table, const uint32_t *bitmap, int64_t n_slots, uint32_t vbits, int32_t n_values, u64 *unique,
+                                  const u64 *rec, int64_t n_rec, hipStream_t stream);
+hipError_t gs_launch_rec_unique_count(const u64 *rec, const uint32_t *bitmap_rec, int64_t n_rec, int32_t n_values, u64 *unique,
+                                      hipStream_t stream);
+hipError_t gs_launch_clear_seen(u64 *table, int64_t n_slots, u64 *rec, int64_t n_rec, hipStream_t stream);
+hipError_t gs_launch_bitmap_extract(const u64 *table, int64_t n_slots, uint32_t *bitmap, const u64 *rec, int64_t n_rec, hipStream_t stream);
+hipError_t gs_launch_bitmap_or(uint32_t *dst, const uint32_t *parts, int64_t n_words, int64_t n_parts, hipStream_t stream);
+
+// ---- gs_filter.hip
 hipError_t gs_launch_filter(const GsFilterParams *P, int grid, hipStream_t stream);
-hipError_t gs_launch_stat_reduce(const GsStatRec *recs, const void *count, int64_t n_max, int n_values, void *sums, void *maxk, void *dsums,
-                                 int32_t *vi_scratch, hipStream_t stream);
-int gs_match_occupancy(int n_values);
-int gs_match_long_occupancy(int n_values);
 int gs_filter_occupancy();
 
 // ---- gs_text.hip

@@ -1,4 +1,4 @@
-// gs_params.h -- kernel parameter blocks and launch constants shared by gs_kernels.hip and gs_api.cpp
+// gs_params.h -- kernel parameter blocks and launch constants shared by the kernel units and gs_api.cpp
 #pragma once
 #include <stdint.h>
 

@@ -76,8 +76,8 @@ def test_product_package_does_not_import_the_oracle():
 
 def test_launchers_and_parameter_blocks_are_declared_once():
     """gs_launch.h is the one place where a launcher or a kernel parameter block is declared: no Gs* struct is defined in two
-    files, no translation unit of libgsgpu.so holds an extern "C" prototype of its own, and gs_api.cpp names its device
-    allocations (gs_dev_alloc / gs_dev_free) instead of redefining hipMalloc / hipFree"""
+    files, no translation unit of libgsgpu.so holds an extern "C" prototype of its own, every kernel is defined in the one unit of
+    its family, and gs_api.cpp names its device allocations (gs_dev_alloc / gs_dev_free) instead of redefining hipMalloc / hipFree"""
     csrc = os.path.join(ROOT, "genestrip_amd", "csrc")
     src = {f: open(os.path.join(csrc, f), errors="replace").read() for f in sorted(os.listdir(csrc)) if f.endswith((".h", ".hip", ".cpp"))}
     where = {}
@@ -96,6 +96,21 @@ def test_launchers_and_parameter_blocks_are_declared_once():
     for f in files:
         protos = [" ".join(m.group(0).split()) for m in re.finditer(r'extern "C"[^;{]*;', src[f])]
         assert not protos, (f, protos)
+
+    # one unit per kernel family: every gs_*_kernel is defined in one file, gs_kernels.hip is the match unit alone, and the units
+    # split off from it share their wave helpers through gs_wave.h
+    kernels = {}
+    for f, txt in src.items():
+        for name in re.findall(r"__global__[^;{]*?\bvoid (gs_\w+_kernel)\(", txt):
+            kernels.setdefault(name, []).append(f)
+    assert len(kernels) >= 25 and kernels["gs_match_kernel"] == ["gs_kernels.hip"], sorted(kernels)
+    twice = {n: fs for n, fs in kernels.items() if len(fs) > 1}
+    assert not twice, twice
+    moved = ("gs_filter", "gs_encode", "gs_route", "gs_unroute", "gs_probe_keys", "gs_segments", "gs_unique", "gs_bitmap", "gs_clear_seen", "gs_rec_")
+    stray = [n for n, fs in kernels.items() if fs == ["gs_kernels.hip"] and n.startswith(moved)]
+    assert not stray, stray
+    for f in ("gs_route.hip", "gs_segments.hip", "gs_seen.hip", "gs_filter.hip"):
+        assert f in files and '#include "gs_wave.h"' in src[f], f
 
     api = src["gs_api.cpp"]
     assert not re.search(r"#\s*define\s+hip(Malloc|Free)\b", api)

@@ -1,4 +1,4 @@
-"""gs_filter_kernel (gs_kernels.hip) at every hash count, fill, k, read length, threshold and filter geometry, byte for byte against
+"""gs_filter_kernel (gs_filter.hip) at every hash count, fill, k, read length, threshold and filter geometry, byte for byte against
 the oracle's FastqBloomFilter.isAcceptRead (orc.Bloom.filter_batch) or, for filters of 2^31 .. 2^37 bits, the sparse host
 reference (tests/bloomref.py SparseBloom).  Every cell asserts with the host reference that its edge happened.
 
