@@ -2259,7 +2259,10 @@ struct gs_run {
     int64_t bitmap_words = 0;
     bool seen_dirty = false;    // some slot may carry a seen bit
     bool bitmap_merged = false; // d_bitmap holds a merged (multi-rank) bitmap: do not re-extract
-    u64 *d_unique = nullptr;
+    bool bitmap_written = false; // d_bitmap of a store that is not striped may hold set bits (an extract, a merge)
+    bool bitmap_stale = false;   // ... from before the last reset, which did not clear them (run_clear)
+    u64 *d_result = nullptr;     // h_result's layout on the device: what gs_match_finish copies, in one piece
+    u64 *d_unique = nullptr;     // (the unique counts inside d_result)
     unsigned int *d_long_count = nullptr;
     uint32_t *d_long_list = nullptr;
     int64_t long_cap = 0;
@@ -2753,7 +2756,16 @@ static int run_clear(gs_run *run) {
     // (sums, max keys, double sums and the long-read queue counters [queue length, consumer cursor] are one block)
     HIP_TRY(hipMemsetAsync(run->d_sums, 0, sizeof(int64_t) * nv * (GS_N_SUMS + 1 + GS_N_DCOLS) * cp + 2 * sizeof(unsigned int), run->stream));
     run->stats_spread = false;
-    HIP_TRY(hipMemsetAsync(run->d_bitmap, 0, sizeof(uint32_t) * (size_t)run->bitmap_words, run->stream));
+    // The compact bitmap of a store that is not striped is a COPY of the seen bits in the store: whoever reads it (gs_match_finish,
+    // gs_match_device_state, gs_match_merge) first has an extract sweep write every one of its words, unless bitmap_merged says
+    // that it holds a merge -- and bitmap_merged is cleared below.  So the bits of an earlier round are never read and need no
+    // clearing here (one word per 32 slots and per record bucket: 512 MiB on a 473 M-k-mer store).  The one reader that does
+    // not extract, gs_match_or_bitmap, clears a stale bitmap itself (bitmap_settle).  The kernels of a striped store write
+    // their seen bits into the bitmap: there it is the state itself and is cleared.
+    if (run->db->striped())
+        HIP_TRY(hipMemsetAsync(run->d_bitmap, 0, sizeof(uint32_t) * (size_t)run->bitmap_words, run->stream));
+    else
+        run->bitmap_stale = run->bitmap_written;
     if (run->d_hit_counts)
         HIP_TRY(hipMemsetAsync(run->d_hit_counts, 0, sizeof(uint32_t) * (size_t)(run->db->n_slots() + run->db->n_rec * GS_REC_SLOTS), run->stream));
     if (run->seen_dirty && !run->db->striped())  // (a striped store's seen bits are the bitmap that was just cleared)
@@ -2778,7 +2790,7 @@ static void run_free(gs_run *run) {
     gs_dev_free(run->d_route_cursors);
     gs_dev_free(run->d_bitmap);
     gs_dev_free(run->d_hit_counts);
-    gs_dev_free(run->d_unique);
+    gs_dev_free(run->d_result);  // (d_unique lies inside)
     gs_dev_free(run->d_long_list);
     gs_dev_free(run->d_scratch);
     gs_dev_free(run->d_serial);
@@ -2861,7 +2873,10 @@ extern "C" int gs_match_begin(gs_run **out, gs_db *db, const gs_match_cfg *cfg) 
         run->d_long_count = reinterpret_cast<unsigned int *>(run->d_dsums + nv * GS_N_DCOLS * cp);
     }
     if (e == hipSuccess) e = gs_dev_alloc((void **)&run->d_bitmap, sizeof(uint32_t) * (size_t)run->bitmap_words);
-    if (e == hipSuccess) e = gs_dev_alloc((void **)&run->d_unique, sizeof(u64) * nv);
+    if (e == hipSuccess && !db->striped())  // (run_clear clears a striped store's bitmap, and no other)
+        e = hipMemsetAsync(run->d_bitmap, 0, sizeof(uint32_t) * (size_t)run->bitmap_words, run->stream);
+    if (e == hipSuccess) e = gs_dev_alloc((void **)&run->d_result, sizeof(u64) * nv * (GS_N_SUMS + 2 + GS_N_DCOLS));
+    if (e == hipSuccess) run->d_unique = run->d_result + nv * (GS_N_SUMS + 1);
     if (e == hipSuccess && cfg->max_kmer_res_counts > 0)
         e = gs_dev_alloc((void **)&run->d_hit_counts, sizeof(uint32_t) * (size_t)(db->n_slots() + db->n_rec * GS_REC_SLOTS));
     if (e != hipSuccess) {
@@ -3059,9 +3074,14 @@ static int launch_batch(gs_run *run, const uint8_t *d_seq, const uint64_t *d_off
         P.stat_recs = run->d_stat_recs;
         P.stat_rec_count = (unsigned long long *)run->d_stat_rec_count;
     }
-    HIP_TRY(hipMemsetAsync(run->d_long_count, 0, 6 * sizeof(unsigned int), run->stream));
+    // Reads of one length with at most 128 k-mer positions, not from nodes: gs_classify_kernel does not run, and it alone writes the
+    // queues of the wide and the long-read kernels -- which return at once on an empty queue and keep nothing else from launch to
+    // launch (the cursors and queue lengths are cleared right here by every batch that launches them, the long-read kernel's
+    // serials move only with a read it takes).  So such a batch launches none of them and leaves the queue counters alone.
     // (reads of one short length each, or nodes that came from other ranks: nothing for the huge-read kernels)
     const bool huge = !d_nodes && (off_stride != 0 || fixed_len - run->db->info.k + 1 >= run->huge_min);
+    const bool no_queues = off_stride == 0 && !d_nodes && fixed_len - run->db->info.k + 1 <= 128 && !huge;
+    if (!no_queues) HIP_TRY(hipMemsetAsync(run->d_long_count, 0, 6 * sizeof(unsigned int), run->stream));
     if (huge && (rc = ensure_huge(run, &P))) return rc;
     if ((rc = timer_start(run->timer, run->cfg.profile != 0, run->stream))) return rc;
     if (run->cfg.count_unique && !d_nodes) {
@@ -3089,6 +3109,7 @@ static int launch_batch(gs_run *run, const uint8_t *d_seq, const uint64_t *d_off
         HIP_TRY(gs_launch_match_wide(&P, pos_fixed <= 192 ? 3 : 4, run->db->n_cu, run->stream));
         return GS_OK;
     }
+    if (no_queues) return GS_OK;
     if (!all_long && P.wide_mask) {  // what gs_match_kernel put into queues 1 and 2 (the kernels return at once when their queue is empty)
         if (P.wide_mask & 1) HIP_TRY(gs_launch_match_wide(&P, 3, run->db->n_cu, run->stream));
         if (P.wide_mask & 2) HIP_TRY(gs_launch_match_wide(&P, 4, run->db->n_cu, run->stream));
@@ -3321,6 +3342,16 @@ extern "C" int gs_match_text_clear_error(gs_run *run) {
 static int run_extract_bitmap(gs_run *run) {
     if (run->db->striped()) return GS_OK;
     HIP_TRY(gs_launch_bitmap_extract(run->db->d_table, run->db->n_slots(), run->d_bitmap, run->db->d_rec, run->db->n_rec, run->stream));
+    run->bitmap_written = true;
+    run->bitmap_stale = false;
+    return GS_OK;
+}
+
+// before a read of the bitmap that no extract precedes: the bits that the last reset left in it (run_clear) go
+static int bitmap_settle(gs_run *run) {
+    if (!run->bitmap_stale) return GS_OK;
+    HIP_TRY(hipMemsetAsync(run->d_bitmap, 0, sizeof(uint32_t) * (size_t)run->bitmap_words, run->stream));
+    run->bitmap_stale = run->bitmap_written = false;
     return GS_OK;
 }
 
@@ -3348,9 +3379,12 @@ static int run_unique_counts(gs_run *run) {
 }
 
 // the copies of the global-atomic counters into copy 0 (the others start from zero again)
-static int fold_stats(gs_run *run) {
-    if (!run->stats_spread) return GS_OK;
-    HIP_TRY(gs_launch_fold_stats((long long *)run->d_sums, (unsigned long long *)run->d_max, run->d_dsums, (long long)run->db->info.n_values, run->stat_copies, run->stream));
+// to_result (gs_match_finish): the totals also into d_result, its unique counts zeroed -- the same launch, also when there is
+// nothing to fold
+static int fold_stats(gs_run *run, bool to_result = false) {
+    if (!run->stats_spread && !to_result) return GS_OK;
+    HIP_TRY(gs_launch_fold_stats((long long *)run->d_sums, (unsigned long long *)run->d_max, run->d_dsums, (long long)run->db->info.n_values,
+                                 run->stats_spread ? run->stat_copies : 1, to_result ? run->d_result : nullptr, run->stream));
     run->stats_spread = false;
     return GS_OK;
 }
@@ -3372,31 +3406,32 @@ extern "C" int gs_match_finish(gs_run *run, int64_t *table, double *dtable) {
     if (!run || !table) return fail(GS_E_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(run->db->device));
     const size_t nv = (size_t)run->db->info.n_values;
-    // the four result arrays land in page-locked memory (a copy into pageable memory is staged by the runtime: ~20 us each,
-    // one after the other -- a third of the time between two batches of the bench)
+    // the result lands in page-locked memory (a copy into pageable memory is staged by the runtime: ~20 us, a third of the time
+    // between two batches of the bench), and in ONE copy: the fold leaves the four arrays side by side in d_result
     if (!run->h_result) HIP_TRY(hipHostMalloc((void **)&run->h_result, sizeof(u64) * nv * (GS_N_SUMS + 2 + GS_N_DCOLS), hipHostMallocDefault));
     int64_t *sums = reinterpret_cast<int64_t *>(run->h_result);
     int64_t *maxk = sums + nv * GS_N_SUMS;
     u64 *uniq = reinterpret_cast<u64 *>(maxk + nv);
     double *dsums = reinterpret_cast<double *>(uniq + nv);
     {
-        const int frc = fold_stats(run);
+        const int frc = fold_stats(run, true);
         if (frc) return frc;
     }
     if (run->cfg.count_unique) {
-        if (!run->bitmap_merged) {
-            const int xrc = run_extract_bitmap(run);
-            if (xrc) return xrc;
-        }
-        {
+        const gs_db *db = run->db;
+        if (!db->striped() && !run->bitmap_merged) {
+            // the run's own seen bits: bitmap and counts in one pass over the store (d_unique: zeroed by the fold)
+            HIP_TRY(gs_launch_seen_sweep(db->d_table, db->n_slots(), db->dev.vbits, db->d_rec, db->n_rec, run->d_bitmap, db->info.n_values,
+                                         run->d_unique, run->stream));
+            run->bitmap_written = true;
+            run->bitmap_stale = false;
+        } else {  // a merged bitmap, or the one that the kernels of a striped store write
             const int urc = run_unique_counts(run);
             if (urc) return urc;
         }
-        HIP_TRY(hipMemcpyAsync(uniq, run->d_unique, sizeof(u64) * nv, hipMemcpyDeviceToHost, run->stream));
     }
-    HIP_TRY(hipMemcpyAsync(sums, run->d_sums, sizeof(int64_t) * nv * GS_N_SUMS, hipMemcpyDeviceToHost, run->stream));
-    HIP_TRY(hipMemcpyAsync(maxk, run->d_max, sizeof(int64_t) * nv, hipMemcpyDeviceToHost, run->stream));
-    if (dtable) HIP_TRY(hipMemcpyAsync(dsums, run->d_dsums, sizeof(double) * nv * GS_N_DCOLS, hipMemcpyDeviceToHost, run->stream));
+    HIP_TRY(hipMemcpyAsync(run->h_result, run->d_result, sizeof(u64) * nv * (GS_N_SUMS + 2 + (dtable ? GS_N_DCOLS : 0)), hipMemcpyDeviceToHost,
+                           run->stream));
     HIP_TRY(hipStreamSynchronize(run->stream));
     if (dtable) memcpy(dtable, dsums, sizeof(double) * nv * GS_N_DCOLS);
     int rc = timer_collect(run->timer);
@@ -3490,7 +3525,12 @@ extern "C" int gs_match_device_state(gs_run *run, void **sums, void **max_keys, 
 extern "C" int gs_match_or_bitmap(gs_run *run, const void *parts, int64_t n_parts) {
     if (!run || !parts || n_parts < 1) return fail(GS_E_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(run->db->device));
+    {
+        const int src = bitmap_settle(run);
+        if (src) return src;
+    }
     HIP_TRY(gs_launch_bitmap_or(run->d_bitmap, (const uint32_t *)parts, run->bitmap_words, n_parts, run->stream));
+    run->bitmap_written = true;
     HIP_TRY(hipStreamSynchronize(run->stream));
     run->bitmap_merged = true;  // gs_match_finish counts from this merged bitmap
     return GS_OK;
@@ -3620,6 +3660,7 @@ extern "C" int gs_match_merge(gs_run *const *runs, int n_runs) try {
             if (uniq) HIP_TRY(hipMemcpyAsync(run->d_bitmap, L->d_bitmap, sizeof(uint32_t) * (size_t)words, hipMemcpyDeviceToDevice, L->stream));
         }
         run->bitmap_merged = uniq;  // gs_match_finish counts from the merged bitmap
+        run->bitmap_written = run->bitmap_written || uniq;
     }
     for (gs_run *L : leader) {
         HIP_TRY(hipSetDevice(L->db->device));

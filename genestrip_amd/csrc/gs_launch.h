@@ -93,7 +93,8 @@ hipError_t gs_launch_match_huge(const GsMatchParams *P, int grid, hipStream_t st
 hipError_t gs_launch_match_wide(const GsMatchParams *P, int ns, int n_cu, hipStream_t stream);
 int gs_match_wide_mask(const GsMatchParams *P);
 hipError_t gs_launch_classify(const GsMatchParams *P, hipStream_t stream);
-hipError_t gs_launch_fold_stats(long long *sums, unsigned long long *maxk, double *dsums, long long nv, int copies, hipStream_t stream);
+hipError_t gs_launch_fold_stats(long long *sums, unsigned long long *maxk, double *dsums, long long nv, int copies, unsigned long long *result,
+                                hipStream_t stream);
 hipError_t gs_launch_match_long(const GsMatchParams *P, int grid, int32_t *scratch, uint32_t *serial, hipStream_t stream);
 hipError_t gs_launch_stat_reduce(const GsStatRec *recs, const void *count, int64_t n_max, int n_values, void *sums, void *maxk, void *dsums,
                                  int32_t *vi_scratch, hipStream_t stream);
@@ -121,6 +122,8 @@ hipError_t gs_launch_rec_unique_count(const u64 *rec, const uint32_t *bitmap_rec
                                       hipStream_t stream);
 hipError_t gs_launch_clear_seen(u64 *table, int64_t n_slots, u64 *rec, int64_t n_rec, hipStream_t stream);
 hipError_t gs_launch_bitmap_extract(const u64 *table, int64_t n_slots, uint32_t *bitmap, const u64 *rec, int64_t n_rec, hipStream_t stream);
+hipError_t gs_launch_seen_sweep(const u64 *table, int64_t n_slots, uint32_t vbits, const u64 *rec, int64_t n_rec, uint32_t *bitmap,
+                                int32_t n_values, u64 *unique, hipStream_t stream);
 hipError_t gs_launch_bitmap_or(uint32_t *dst, const uint32_t *parts, int64_t n_words, int64_t n_parts, hipStream_t stream);
 
 // ---- gs_filter.hip
