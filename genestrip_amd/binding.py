@@ -39,7 +39,8 @@ ABI_SYMBOLS = (
     "gs_pinned_alloc", "gs_pinned_free",
     "gs_filter_submit_text", "gs_filter_text_wait_copy", "gs_filter_text_status", "gs_filter_text_reset",
     "gs_filter_submit_fasta", "gs_filter_submit_fastq_ml", "gs_filter_text_read_bounds", "gs_filter_text_line_classes",
-    "gs_bloom_create", "gs_bloom_build", "gs_bloom_get", "gs_bloom_destroy", "gs_filter_submit", "gs_filter_sync", "gs_filter_kernel_time",
+    "gs_bloom_create", "gs_bloom_build", "gs_bloom_get", "gs_bloom_destroy",
+    "gs_bloom_build_db", "gs_bloom_get_info", "gs_bloom_save", "gs_bloom_load", "gs_filter_submit", "gs_filter_sync", "gs_filter_kernel_time",
     "gs_calibrate",
     "gs_match_get_device", "gs_inflate_members", "gs_inflater_create", "gs_inflater_feed", "gs_inflater_tail", "gs_gunzipper_open", "gs_gunzipper_reopen", "gs_gunzipper_next", "gs_gunzipper_info", "gs_gunzipper_first_span", "gs_gunzipper_park", "gs_gunzipper_close", "gs_gunzip_plan_device", "gs_gunzip_free", "gs_gunzip_device", "gs_text_cut_device", "gs_device_fetch", "gs_inflater_fetch", "gs_filter_get_device", "gs_inflater_reset", "gs_inflater_destroy", "gs_inflate_last_error",
     "gs_filter_compact_text", "gs_match_compact_text", "gs_filter_compact_records", "gs_match_compact_records", "gs_match_kraken_records", "gs_match_set_taxids", "gs_match_kraken_text", "gs_match_kraken_time", "gs_deflater_create", "gs_deflater_pack", "gs_deflater_info", "gs_deflater_destroy", "gs_deflater_append", "gs_deflater_pending", "gs_deflater_flush",
@@ -195,6 +196,8 @@ def lib():
         "gs_bloom_create": (ci, [vp, ci, ci, i64, i32, vp, vp, i64]),
         "gs_bloom_build": (ci, [vp, ci, ci, vp, i64, ci, i64, C.c_double]),
         "gs_bloom_get": (ci, [vp, vp, vp, vp, vp, i64]), "gs_bloom_destroy": (ci, [vp]),
+        "gs_bloom_build_db": (ci, [vp, vp, ci, vp, i64, C.c_double, vp]), "gs_bloom_get_info": (ci, [vp, vp]),
+        "gs_bloom_save": (ci, [vp, C.c_char_p]), "gs_bloom_load": (ci, [vp, ci, C.c_char_p]),
         "gs_filter_submit": (ci, [vp, ci, ci, dbl, vp, vp, i64, ci, vp, ci]), "gs_filter_sync": (ci, [vp]),
         "gs_filter_kernel_time": (ci, [vp, vp, vp]),
         "gs_calibrate": (ci, [ci, ci, i64, vp]),
@@ -1298,6 +1301,22 @@ class FastqKMerMatcher:
             pass
 
 
+class BloomInfo(C.Structure):
+    """gs_bloom_info: k = 0, expected_insertions / n_inserted = -1 and fpp = 0 stand for "unknown" """
+    _fields_ = [("kind", C.c_int32), ("k", C.c_int32), ("n_hashes", C.c_int32), ("pad", C.c_int32), ("bits", C.c_int64),
+                ("n_words", C.c_int64), ("expected_insertions", C.c_int64), ("n_inserted", C.c_int64), ("fpp", C.c_double)]
+
+
+def requested_mask(taxids, requested_taxids):
+    """uint8[len(taxids)] for DeviceBloomFilter.from_store: 1 where the value's tax id (taxids[value index], strings) is one of
+    `requested_taxids`.  A requested tax id the store does not know is an error, as a mistyped one would build an empty index."""
+    want = {str(t) for t in requested_taxids}
+    unknown = want - {str(t) for t in taxids}
+    if unknown:
+        raise ValueError(f"tax ids not in the store: {sorted(unknown)}")
+    return np.array([str(t) in want for t in taxids], dtype=np.uint8)
+
+
 class DeviceBloomFilter:
     """device copy of a reference index filter (bits + hash factors replicated exactly)."""
 
@@ -1322,6 +1341,36 @@ class DeviceBloomFilter:
         _check(lib().gs_bloom_build(C.byref(self.h), device, kind, pk, n, mem, int(expected_insertions or max(n, 1)), float(fpp)))
         return self
 
+    @classmethod
+    def from_store(cls, store, requested, kind=BLOOM_XOR, fpp=1e-8, expected_insertions=None):
+        """gs_bloom_build_db, the index goal (BloomIndexGoal): the filter of `kind` over the stored k-mers of `store` whose value
+        is requested (bool / uint8 [n_values], the per-node flag: see requested_mask), sized for their count (or for
+        expected_insertions) like the reference's and filled on the device.  The count is info().n_inserted."""
+        req = np.ascontiguousarray(np.asarray(requested) != 0, dtype=np.uint8)
+        if req.ndim != 1 or len(req) != store.info.n_values:
+            raise ValueError(f"requested has shape {req.shape}, the store has {store.info.n_values} values")
+        self = cls.__new__(cls)
+        self.h = C.c_void_p()
+        _check(lib().gs_bloom_build_db(C.byref(self.h), store.h, kind, req.ctypes.data_as(C.c_void_p),
+                                       -1 if expected_insertions is None else int(expected_insertions), float(fpp), None))
+        return self
+
+    @classmethod
+    def load(cls, path, device=0):
+        """open a native index file written by save() (gs_bloom_load)"""
+        self = cls.__new__(cls)
+        self.h = C.c_void_p()
+        _check(lib().gs_bloom_load(C.byref(self.h), device, str(path).encode()))
+        return self
+
+    def save(self, path):
+        _check(lib().gs_bloom_save(self.h, str(path).encode()))
+
+    def info(self):
+        i = BloomInfo()
+        _check(lib().gs_bloom_get_info(self.h, C.byref(i)))
+        return i
+
     @property
     def device(self):
         d = C.c_int(0)
@@ -1333,7 +1382,7 @@ class DeviceBloomFilter:
         bits, nh = C.c_int64(0), C.c_int32(0)
         _check(lib().gs_bloom_get(self.h, C.byref(bits), C.byref(nh), None, None, 0))
         hf = np.zeros(nh.value, dtype=np.int64)
-        words = np.zeros((bits.value + 63) // 64, dtype=np.uint64) if with_words else None
+        words = np.zeros(self.info().n_words, dtype=np.uint64) if with_words else None
         _check(lib().gs_bloom_get(self.h, None, None, hf.ctypes.data_as(C.c_void_p),
                                   None if words is None else words.ctypes.data_as(C.c_void_p), 0 if words is None else len(words)))
         return bits.value, hf, words

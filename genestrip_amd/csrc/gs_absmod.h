@@ -1,5 +1,6 @@
 // gs_absmod.h -- the Bloom filters' bit index Math.abs(v % bits) (C/bloom/XORKMerBloomFilter.java:57-59) by a magic-number
-// division, shared by the host (gs_api.cpp makes the magic, g++ checks it in tests/native/absmod_check.cpp) and the filter kernel.
+// division, shared by the host (gs_api.cpp makes the magic, g++ checks it in tests/native/absmod_check.cpp), the filter kernel and
+// the index kernel (gs_index.hip); and the Murmur hash those two kernels share.
 #pragma once
 #include <stdint.h>
 
@@ -23,6 +24,25 @@ static inline void gs_magic_u64(uint64_t d, uint64_t &magic, int &shift) {
     const unsigned __int128 num = ((unsigned __int128)((l == 64 ? 0 : ((uint64_t)1 << l)) - d)) << 64;
     magic = (uint64_t)(num / d) + 1;
     shift = l;
+}
+
+// MurmurKMerBloomFilter.hash: MurmurHash3DropIn.hash64(data, base) (C/util/MurmurHash3DropIn.java:60-87)
+GS_HD int64_t gs_murmur64(int64_t data_, int64_t base) {
+    const uint64_t data = (uint64_t)data_;
+    uint64_t hash = (uint64_t)base;
+    uint64_t kk = __builtin_bswap64(data);
+    kk *= 0x87c37b91114253d5ULL;
+    kk = (kk << 31) | (kk >> 33);
+    kk *= 0x4cf5ad432745937fULL;
+    hash ^= kk;
+    hash = ((hash << 27) | (hash >> 37)) * 5 + 0x52dce729ULL;
+    hash ^= 8;
+    hash ^= hash >> 33;
+    hash *= 0xff51afd7ed558ccdULL;
+    hash ^= hash >> 33;
+    hash *= 0xc4ceb9fe1a85ec53ULL;
+    hash ^= hash >> 33;
+    return (int64_t)(hash ^ data);
 }
 
 // |v| mod d = Math.abs(v % d) for d < 2^63 (Java's % truncates, so |v % d| = |v| mod d; |INT64_MIN| = 2^63 is exact in u64)

@@ -19,6 +19,8 @@
 #include <vector>
 
 #include "gs_absmod.h"
+#include "gs_checksum.h"
+#include "gs_indexfile.h"
 #include "gs_launch.h"
 #include "gs_layout.h"
 #include "gs_params.h"
@@ -1419,43 +1421,7 @@ struct GsStoreFileHeader {
     uint64_t gate_words;
     uint64_t mgate_words;  // 32-bit words, a power of two
     uint64_t rec_buckets;  // super-k-mer record buckets (GS_REC_WORDS words each), a power of two or 0
-    uint64_t checksum;     // store_checksum over table | gate | mgate | records | tree
-};
-
-// two running 64-bit sums over the payload's 32-bit words (Fletcher style): position sensitive, one pass
-struct StoreChecksum {
-    uint64_t a = 1, b = 0;
-    // a and b after the words of [p, p + bytes): slices are summed by all cores with a = b = 0 -- S = sum of the words, T = sum
-    // of their prefix sums -- and chained: a' = a + S, b' = b + n * a + T (the same numbers as the word-by-word loop, mod 2^64)
-    void add(const void *p, size_t bytes) {
-        const uint32_t *w = (const uint32_t *)p;
-        const size_t n = bytes / 4;
-        int n_thr = n < ((size_t)1 << 22) ? 1 : (int)std::min<unsigned>(32, std::max<unsigned>(1, std::thread::hardware_concurrency()));
-        std::vector<uint64_t> S((size_t)n_thr, 0), T((size_t)n_thr, 0);
-        auto part = [&](int t) {
-            const size_t lo = n * (size_t)t / (size_t)n_thr, hi = n * ((size_t)t + 1) / (size_t)n_thr;
-            uint64_t sa = 0, sb = 0;
-            for (size_t i = lo; i < hi; i++) {
-                sa += w[i];
-                sb += sa;
-            }
-            S[(size_t)t] = sa;
-            T[(size_t)t] = sb;
-        };
-        if (n_thr == 1)
-            part(0);
-        else {
-            std::vector<std::thread> th;
-            for (int t = 0; t < n_thr; t++) th.emplace_back(part, t);
-            for (auto &x : th) x.join();
-        }
-        for (int t = 0; t < n_thr; t++) {
-            const size_t lo = n * (size_t)t / (size_t)n_thr, hi = n * ((size_t)t + 1) / (size_t)n_thr;
-            b += (uint64_t)(hi - lo) * a + T[(size_t)t];
-            a += S[(size_t)t];
-        }
-    }
-    uint64_t value() const { return a ^ (b << 1) ^ (b >> 63); }
+    uint64_t checksum;     // StoreChecksum (gs_checksum.h) over table | gate | mgate | records | tree
 };
 
 // what the kernels index with: every field of a store image that came from a file is checked before it reaches HBM
@@ -5522,6 +5488,9 @@ struct gs_bloom {
     int64_t bits = 0;
     int32_t n_hashes = 0;
     int64_t n_words = 0;
+    int32_t k = 0;                                        // what gs_bloom_get_info reports beyond the geometry: 0 / -1 / 0 = unknown
+    int64_t expected_insertions = -1, n_inserted = -1;
+    double fpp = 0.0;
     u64 *d_words = nullptr;
     int64_t *d_factors = nullptr;
     hipStream_t stream = nullptr;
@@ -5612,6 +5581,9 @@ extern "C" int gs_bloom_build(gs_bloom **out, int device, int kind, const int64_
     b->bits = bits;
     b->n_hashes = (int32_t)nh;
     b->n_words = (bits + 63) / 64;
+    b->expected_insertions = expected_insertions;
+    b->n_inserted = n_kmers;
+    b->fpp = fpp;
     hipDeviceProp_t prop;
     int64_t *d_keys = nullptr;
     hipError_t e = hipGetDeviceProperties(&prop, device);
@@ -5634,6 +5606,212 @@ extern "C" int gs_bloom_build(gs_bloom **out, int device, int kind, const int64_
         gs_bloom_destroy(b);
         return hip_fail(e, "gs_bloom_build");
     }
+    *out = b;
+    return GS_OK;
+}
+GS_API_CATCH
+
+// ensureExpectedSize(n, false) of the three filter kinds, n >= 0 (AbstractKMerBloomFilter.java:96-113,172-185;
+// BlockedKMerBloomFilter: 10 bits per key); the limits are those of gs_bloom_create / gs_bloom_build
+static int bloom_geometry(int kind, int64_t n, double fpp, int64_t &bits, int64_t &nh, int64_t &n_words) {
+    if (kind == GS_BLOOM_BLOCKED) {
+        const int64_t entries = n < 1 ? 1 : n;
+        if (entries > ((int64_t)1 << 40)) return fail(GS_E_UNSUPPORTED, "blocked filters above 2^40 keys are not supported");
+        bits = (entries * 10 + 63) / 64;
+        nh = 1;
+        n_words = bits + 17;
+        return GS_OK;
+    }
+    if (n == 0) {  // (Math.round(+Inf) cast to int is -1, max(1, -1) = 1)
+        bits = nh = n_words = 1;
+        return GS_OK;
+    }
+    const double dbits = -(double)n * std::log(fpp) / (std::log(2.0) * std::log(2.0));
+    if (!(dbits < 1.0e18)) return fail(GS_E_UNSUPPORTED, "filters above 2^37 bits (16 GiB) are not supported");
+    bits = (int64_t)dbits;
+    if (bits < 1) bits = 1;
+    if (bits > ((int64_t)1 << 37)) return fail(GS_E_UNSUPPORTED, "filters above 2^37 bits (16 GiB) are not supported");
+    nh = (int64_t)std::floor((double)bits / (double)n * std::log(2.0) + 0.5);  // Math.round
+    if (nh < 1) nh = 1;
+    if (nh > 64) return fail(GS_E_UNSUPPORTED, "more than 64 hash functions");
+    n_words = (bits + 63) / 64;
+    return GS_OK;
+}
+
+// The index goal on a device store (gs_index.hip): a count pass of the walk sizes the filter, the put pass fills it and counts
+// again.  Beyond the store and the filter the call holds the requested bitmap (n_values bits) and two counters.
+extern "C" int gs_bloom_build_db(gs_bloom **out, gs_db *db, int kind, const uint8_t *requested, int64_t expected_insertions, double fpp,
+                                 int64_t *n_inserted) try {
+    if (!out) return fail(GS_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (kind < GS_BLOOM_XOR || kind > GS_BLOOM_BLOCKED) return fail(GS_E_INVALID, "unknown bloom kind");
+    if (expected_insertions == 0) return fail(GS_E_INVALID, "expected_insertions must be >= 1, or negative for the count");
+    if (kind != GS_BLOOM_BLOCKED && !(fpp > 0.0 && fpp < 1.0)) return fail(GS_E_INVALID, "fpp must be in (0, 1)");
+    if (!db) return fail(GS_E_INVALID, "db is NULL");
+    if (!requested) return fail(GS_E_INVALID, "requested is NULL");
+    if (db->striped()) return fail(GS_E_UNSUPPORTED, "gs_bloom_build_db: a stripe holds a share of the k-mers; build the index from the whole store");
+    const int32_t nv = db->info.n_values;
+    std::vector<uint32_t> bitmap(((size_t)nv + 31) / 32, 0u);
+    for (int32_t v = 0; v < nv; v++)
+        if (requested[v]) bitmap[(size_t)v >> 5] |= 1u << (v & 31);
+    HIP_TRY(hipSetDevice(db->device));
+    gs_bloom *b = new gs_bloom();
+    b->device = db->device;
+    b->kind = kind;
+    b->k = db->info.k;
+    b->n_cu = db->n_cu;
+    const GsExportParams S = export_params(db, -1, 0);
+    GsIndexParams P{};
+    P.rec = S.rec;
+    P.n_rec = S.n_rec;
+    P.tab = S.tab;
+    P.tab_first = S.tab_first;
+    P.n_tab = S.n_tab;
+    P.bucket_bits = S.bucket_bits;
+    P.vbits = S.vbits;
+    P.k = S.k;
+    P.n_values = nv;
+    P.kind = kind;
+    uint32_t *d_bitmap = nullptr;
+    u64 *d_count = nullptr;  // [0]: the count pass, [1]: the put pass
+    u64 counts[2] = {0, 0};
+    HipSteps step{"gs_bloom_build_db"};
+    int rc = GS_OK;
+    int64_t bits = 0, nh = 0;
+    // GS_INDEX_TRACE=1: the two passes between events, on stderr (developer aid, tools/index_build_rate.py)
+    const bool trace = getenv("GS_INDEX_TRACE") != nullptr && atoi(getenv("GS_INDEX_TRACE")) != 0;
+    KernelTimer t_count, t_put;
+    std::vector<int64_t> factors;  // (read by an asynchronous copy: lives until the handle's stream has been drained)
+    bool ok = step(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking), "stream") &&
+              step(gs_dev_alloc((void **)&d_bitmap, sizeof(uint32_t) * bitmap.size()), "bitmap") &&
+              step(gs_dev_alloc((void **)&d_count, sizeof(counts)), "counters") &&
+              step(hipMemsetAsync(d_count, 0, sizeof(counts), b->stream), "counters") &&
+              step(hipMemcpyAsync(d_bitmap, bitmap.data(), sizeof(uint32_t) * bitmap.size(), hipMemcpyHostToDevice, b->stream), "bitmap");
+    if (ok) {
+        P.requested = d_bitmap;
+        P.count = d_count;
+        ok = timer_start(t_count, trace, b->stream) == GS_OK && step(gs_launch_index(&P, db->n_cu, b->stream), "count pass") &&
+             timer_stop(t_count, trace, b->stream) == GS_OK && step(hipMemcpyAsync(&counts[0], d_count, sizeof(u64), hipMemcpyDeviceToHost, b->stream), "count") &&
+             step(hipStreamSynchronize(b->stream), "count pass");
+    }
+    if (ok) {
+        b->n_inserted = (int64_t)counts[0];
+        b->expected_insertions = expected_insertions < 0 ? b->n_inserted : expected_insertions;
+        b->fpp = kind == GS_BLOOM_BLOCKED ? 0.0 : fpp;
+        rc = bloom_geometry(kind, b->expected_insertions, fpp, bits, nh, b->n_words);
+        ok = rc == GS_OK;
+    }
+    if (ok) {
+        b->bits = bits;
+        b->n_hashes = (int32_t)nh;
+        factors.resize((size_t)nh);
+        JavaRandom rnd(42);
+        for (int64_t i = 0; i < nh; i++) factors[(size_t)i] = rnd.next_long();
+        uint64_t mg = 0;
+        int sh = 0;
+        gs_magic_u64((u64)bits, mg, sh);  // gs_absmod.h
+        ok = step(gs_dev_alloc((void **)&b->d_words, sizeof(u64) * (size_t)b->n_words), "filter words") &&
+             step(gs_dev_alloc((void **)&b->d_factors, sizeof(int64_t) * (size_t)nh), "hash factors") &&
+             step(hipMemsetAsync(b->d_words, 0, sizeof(u64) * (size_t)b->n_words, b->stream), "filter words") &&
+             step(hipMemcpyAsync(b->d_factors, factors.data(), sizeof(int64_t) * (size_t)nh, hipMemcpyHostToDevice, b->stream), "hash factors");
+        P.put = 1;
+        P.n_hashes = (int32_t)nh;
+        P.hash_inv = nh >= 2 ? (uint32_t)((((uint64_t)1 << 32) + (uint64_t)nh - 1) / (uint64_t)nh) : 0u;
+        P.bits = (u64)bits;
+        P.magic = mg;
+        P.magic_shift = sh;
+        P.factors = b->d_factors;
+        P.words = b->d_words;
+        P.count = d_count + 1;
+        ok = ok && timer_start(t_put, trace, b->stream) == GS_OK &&
+             (counts[0] == 0 || step(gs_launch_index(&P, db->n_cu, b->stream), "put pass")) && timer_stop(t_put, trace, b->stream) == GS_OK &&
+             step(hipMemcpyAsync(&counts[1], d_count + 1, sizeof(u64), hipMemcpyDeviceToHost, b->stream), "count") &&
+             step(hipStreamSynchronize(b->stream), "put pass");
+    }
+    if (!ok && b->stream) hipStreamSynchronize(b->stream);
+    if (ok && trace && timer_collect(t_count) == GS_OK && timer_collect(t_put) == GS_OK)
+        fprintf(stderr, "[gs_bloom_build_db] kind %d, %lld k-mers, %lld hashes: count pass %.3f ms, put pass %.3f ms\n", kind, (long long)counts[0],
+                (long long)nh, t_count.total_ms, t_put.total_ms);
+    timer_free(t_count);
+    timer_free(t_put);
+    gs_dev_free(d_bitmap);
+    gs_dev_free(d_count);
+    if (ok && counts[1] != counts[0])
+        rc = fail(GS_E_HIP, "gs_bloom_build_db: the put pass inserted " + std::to_string(counts[1]) + " k-mers, the count pass found " +
+                                std::to_string(counts[0]));
+    else if (!ok && rc == GS_OK)
+        rc = step.rc ? step.rc : GS_E_HIP;  // (a trace event that could not be made: its message stands)
+    if (rc) {
+        gs_bloom_destroy(b);
+        return rc;
+    }
+    if (n_inserted) *n_inserted = b->n_inserted;
+    *out = b;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_bloom_get_info(gs_bloom *b, gs_bloom_info *info) {
+    if (!b || !info) return fail(GS_E_INVALID, "NULL argument");
+    *info = gs_bloom_info{};
+    info->kind = b->kind;
+    info->k = b->k;
+    info->n_hashes = b->n_hashes;
+    info->bits = b->bits;
+    info->n_words = b->n_words;
+    info->expected_insertions = b->expected_insertions;
+    info->n_inserted = b->n_inserted;
+    info->fpp = b->fpp;
+    return GS_OK;
+}
+
+// ---- native index file (include/gsgpu.h): the header, its checks and the reader are host code of their own (gs_indexfile.h)
+extern "C" int gs_bloom_save(gs_bloom *b, const char *path) try {
+    if (!b || !path) return fail(GS_E_INVALID, "NULL argument");
+    GsIndexFileHeader h{};
+    memcpy(h.magic, "GSINDEX1", 8);
+    h.kind = b->kind;
+    h.k = b->k;
+    h.n_hashes = b->n_hashes;
+    h.bits = b->bits;
+    h.n_words = b->kind == GS_BLOOM_BLOCKED ? b->bits + 17 : (b->bits + 63) / 64;  // (gs_bloom_create takes longer arrays: the file holds the filter's own)
+    h.expected_insertions = b->expected_insertions;
+    h.n_inserted = b->n_inserted;
+    h.fpp = b->fpp;
+    if (const char *why = gs_index_header_defect(h)) return fail(GS_E_UNSUPPORTED, std::string("gs_bloom_save: ") + why);
+    std::vector<int64_t> factors((size_t)b->n_hashes);
+    std::vector<u64> words((size_t)h.n_words);
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipMemcpy(factors.data(), b->d_factors, factors.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(words.data(), b->d_words, words.size() * sizeof(u64), hipMemcpyDeviceToHost));
+    h.checksum = gs_index_checksum(factors, words);
+    FILE *f = fopen(path, "wb");
+    if (!f) return fail(GS_E_IO, std::string("cannot open ") + path);
+    bool ok = fwrite(&h, sizeof(h), 1, f) == 1 && fwrite(factors.data(), sizeof(int64_t), factors.size(), f) == factors.size() &&
+              fwrite(words.data(), sizeof(u64), words.size(), f) == words.size();
+    ok = (fclose(f) == 0) && ok;
+    return ok ? GS_OK : fail(GS_E_IO, std::string("short write to ") + path);
+}
+GS_API_CATCH
+
+extern "C" int gs_bloom_load(gs_bloom **out, int device, const char *path) try {
+    if (!out) return fail(GS_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!path) return fail(GS_E_INVALID, "path is NULL");
+    GsIndexFileHeader h{};
+    std::vector<int64_t> factors;
+    std::vector<u64> words;
+    std::string why;
+    const int got = gs_index_file_read(path, h, factors, words, why);  // every check of the file, before a device is touched
+    if (got != GS_INDEXFILE_OK) return fail(got == GS_INDEXFILE_IO ? GS_E_IO : GS_E_INVALID, why);
+    gs_bloom *b = nullptr;
+    const int rc = gs_bloom_create(&b, device, h.kind, h.bits, h.n_hashes, factors.data(), (const uint64_t *)words.data(), h.n_words);
+    if (rc) return rc;
+    b->k = h.k;
+    b->expected_insertions = h.expected_insertions;
+    b->n_inserted = h.n_inserted;
+    b->fpp = h.fpp;
     *out = b;
     return GS_OK;
 }

@@ -12,17 +12,12 @@
 
 #include <rocprim/device/device_scan.hpp>
 
+#include "gs_decode.h"  // the walk's loads and field decoders, shared with gs_index.hip
 #include "gs_launch.h"
 #include "gs_layout.h"
 
 #define GS_EX_BLOCK 256
-#define GS_EX_MAX_PER_LANE 6  // a lane holds 16 bytes of a line: 6 record offsets or 2 table slots
 #define GS_EX_LDS_BINS 16384  // value counts privatised in LDS up to this many values (64 KiB)
-
-// value index of record offset 6 (q - 1) + i in the lane's two value words (three 21-bit fields each, `more` in bit 63)
-__device__ __forceinline__ int32_t gs_ex_rec_value(u64 x0, u64 x1, int i) {
-    return (int32_t)(((i < 3 ? x0 : x1) >> (GS_REC_VAL_BITS * (i % 3))) & (GS_REC_MAX_VALUES - 1));
-}
 
 __device__ __forceinline__ bool gs_ex_selected(const GsExportParams &P, int32_t v) {
     if (P.sel_vi < 0) return true;
@@ -31,11 +26,8 @@ __device__ __forceinline__ bool gs_ex_selected(const GsExportParams &P, int32_t 
     return P.tin[P.sel_vi] <= t && t < P.tout[P.sel_vi];
 }
 
-// Four lanes per 64-byte line (record line or table bucket): lane q of the quad loads bytes [16 q, 16 q + 16) with one 16-byte
-// load, so that a wave's load instruction covers 16 whole lines.  Record line: lane 0 holds the window planes (w0, w1), lane q =
-// 1..3 the value words w(2q), w(2q+1) = offsets j in [6 (q - 1), 6 q) and decodes those from the planes it takes from lane 0.
-// Table bucket: lane q decodes slots 2q, 2q + 1.  Each lane emits at most GS_EX_MAX_PER_LANE k-mers; the wave places them through a
-// ballot prefix over the three bits of the per-lane count and one atomic add.
+// The walk of gs_decode.h: four lanes per 64-byte line.  Each lane emits at most GS_EX_MAX_PER_LANE k-mers; the wave places them
+// through a ballot prefix over the three bits of the per-lane count and one atomic add.
 __global__ __launch_bounds__(GS_EX_BLOCK) void gs_ex_decode_kernel(GsExportParams P) {
     extern __shared__ unsigned int lds_hist[];
     const bool lds = P.hist && P.n_values <= GS_EX_LDS_BINS;
@@ -48,26 +40,20 @@ __global__ __launch_bounds__(GS_EX_BLOCK) void gs_ex_decode_kernel(GsExportParam
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const uint32_t kmask = (uint32_t)((1ULL << P.k) - 1);
     const uint32_t vmask = (1u << P.vbits) - 1u;
-    const u64 bmask = (1ULL << P.bucket_bits) - 1;
     // (the loop bound is uniform per wave: lines are whole quads, a quad never straddles a wave)
     for (int64_t t0 = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63); t0 < 4 * n_lines; t0 += stride) {
         const int64_t t = t0 + lane;
         const int64_t line = t >> 2;
-        u64 x0 = 0, x1 = 0;
+        u64 x0, x1;
         const bool is_rec = line < P.n_rec;
-        if (line < n_lines) {
-            const uint4 w = is_rec ? *reinterpret_cast<const uint4 *>(P.rec + (size_t)line * GS_REC_WORDS + 2 * q)
-                                   : *reinterpret_cast<const uint4 *>(P.tab + (size_t)(line - P.n_rec) * GS_SLOTS_PER_BUCKET + 2 * q);
-            x0 = ((u64)w.y << 32) | w.x;
-            x1 = ((u64)w.w << 32) | w.z;
-        }
+        gs_ex_load_quad(P.rec, P.tab, P.n_rec, n_lines, line, q, x0, x1);
         const int src = lane & ~3;
         const u64 w0 = __shfl(x0, src), w1 = __shfl(x1, src);
         // which of the lane's (up to six) entries it emits: bit i = record offset 6 (q - 1) + i / table slot 2 q + i
         uint32_t sel = 0;
         if (line < n_lines) {
             if (is_rec) {
-                const uint32_t valid = q > 0 ? (uint32_t)(w1 >> GS_REC_WIN_BITS) >> (6 * (q - 1)) : 0u;
+                const uint32_t valid = gs_ex_rec_valid(w1, q);
                 for (int i = 0; i < GS_EX_MAX_PER_LANE; i++)
                     if ((valid >> i) & 1u) {
                         const int32_t v = gs_ex_rec_value(x0, x1, i);
@@ -75,43 +61,29 @@ __global__ __launch_bounds__(GS_EX_BLOCK) void gs_ex_decode_kernel(GsExportParam
                     }
             } else {
                 for (int i = 0; i < 2; i++) {
-                    const int32_t v = (int32_t)((uint32_t)((i ? x1 : x0) >> 1) & vmask) - 1;
+                    const int32_t v = gs_ex_tab_value(i ? x1 : x0, vmask);
                     if (v >= 0 && v < P.n_values && gs_ex_selected(P, v)) sel |= 1u << i;
                 }
             }
         }
         // wave prefix of the per-lane counts (0..6) from three ballots, one atomic per wave
-        const int c = __popc(sel);
-        const u64 lt = (1ULL << lane) - 1ULL;
-        int before = 0, total = 0;
-        for (int bit = 0; bit < 3; bit++) {
-            const u64 m = __ballot((c >> bit) & 1);
-            before += __popcll(m & lt) << bit;
-            total += __popcll(m) << bit;
-        }
+        int before, total;
+        gs_ex_wave_prefix(__popc(sel), lane, before, total);
         if (total == 0) continue;
         u64 base = 0;
         if (lane == 0) base = atomicAdd(P.count, (u64)total);
         base = __shfl(base, 0) + (u64)before;
-        const u64 whi = w0 & ((1ULL << GS_REC_WIN_BITS) - 1), wlo = w1 & ((1ULL << GS_REC_WIN_BITS) - 1);
         for (uint32_t m = sel; m; m &= m - 1, base++) {
             const int i = __builtin_ctz(m);
             uint32_t v;
             u64 key = 0;
             if (is_rec) {
-                const int j = 6 * (q - 1) + i;
                 v = (uint32_t)gs_ex_rec_value(x0, x1, i);
-                if (P.keys) key = gs_planes_to_kmer((uint32_t)(whi >> j) & kmask, (uint32_t)(wlo >> j) & kmask, P.k);
+                if (P.keys) key = gs_ex_rec_key(w0, w1, 6 * (q - 1) + i, P.k, kmask);
             } else {
                 const u64 s = i ? x1 : x0;
-                v = ((uint32_t)(s >> 1) & vmask) - 1u;
-                if (P.keys) {
-                    const u64 bucket = (u64)(P.tab_first + (line - P.n_rec));
-                    const u64 disp = (s >> (P.vbits + 1)) & 3u, rem = s >> (P.vbits + 3);
-                    uint32_t a, b;
-                    gs_unmix_planes((rem << P.bucket_bits) | ((bucket - disp) & bmask), a, b);
-                    key = gs_planes_to_kmer(a & kmask, b & kmask, P.k);
-                }
+                v = (uint32_t)gs_ex_tab_value(s, vmask);
+                if (P.keys) key = gs_ex_tab_key(s, (u64)(P.tab_first + (line - P.n_rec)), P.vbits, P.bucket_bits, P.k, kmask);
             }
             if (P.keys && base < P.cap) {
                 P.keys[base] = key;

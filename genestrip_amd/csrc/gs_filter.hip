@@ -5,7 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gs_absmod.h"  // gs_absmod: the filter's bit index
+#include "gs_absmod.h"  // gs_absmod: the filter's bit index; gs_murmur64
 #include "gs_launch.h"
 #include "gs_layout.h"
 #include "gs_params.h"
@@ -31,24 +31,6 @@ __device__ __forceinline__ int64_t gs_canonical_java(uint32_t fhi, uint32_t flo,
     const u64 fwd = (gs_spread32(rhi) << 1) | gs_spread32(rlo);                     // first base in the top bits
     const u64 rev = (gs_spread32(fhi) << 1) | gs_spread32((flo ^ kmask) & kmask);   // complement, reversed
     return (int64_t)(fwd > rev ? fwd : rev);
-}
-
-__device__ __forceinline__ int64_t gs_murmur64(int64_t data_, int64_t base) {  // MurmurHash3DropIn.java:60-87
-    const u64 data = (u64)data_;
-    u64 hash = (u64)base;
-    u64 kk = __builtin_bswap64(data);
-    kk *= 0x87c37b91114253d5ULL;
-    kk = (kk << 31) | (kk >> 33);
-    kk *= 0x4cf5ad432745937fULL;
-    hash ^= kk;
-    hash = ((hash << 27) | (hash >> 37)) * 5 + 0x52dce729ULL;
-    hash ^= 8;
-    hash ^= hash >> 33;
-    hash *= 0xff51afd7ed558ccdULL;
-    hash ^= hash >> 33;
-    hash *= 0xc4ceb9fe1a85ec53ULL;
-    hash ^= hash >> 33;
-    return (int64_t)(hash ^ data);
 }
 
 // bit `i`-th hash of `key` in the filter (XOR or Murmur kind); factors come from the block's LDS copy

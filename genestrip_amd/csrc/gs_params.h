@@ -228,6 +228,28 @@ struct GsFilterParams {
     const uint32_t *skip;   // text mode: the launch does nothing when *skip != 0
 };
 
+// gs_index.hip: the index filter built from a handle's store (BloomIndexGoal).  The store part is what GsExportParams holds.
+struct GsIndexParams {
+    const unsigned long long *rec;  // this handle's record lines, n_rec of them
+    int64_t n_rec;
+    const unsigned long long *tab;  // this handle's table buckets: global buckets tab_first ..
+    int64_t tab_first, n_tab;
+    uint32_t bucket_bits, vbits;
+    int32_t k, n_values;
+    const uint32_t *requested;      // one bit per value index: bit (v & 31) of word v >> 5
+    int32_t put;                    // 0: count the selected k-mers only
+    int32_t kind;                   // GS_BLOOM_*
+    int32_t n_hashes;
+    uint32_t hash_inv;              // ceil(2^32 / n_hashes) for n_hashes >= 2: pair p -> key p / n_hashes without a division
+    uint64_t bits;                  // XOR/Murmur: bit count ; Blocked: bucket count
+    uint64_t magic;                 // gs_absmod.h: unsigned division by `bits`
+    int32_t magic_shift;
+    int32_t pad;
+    const int64_t *factors;         // n_hashes hash factors; Blocked: factors[0] = the seed
+    unsigned long long *words;
+    unsigned long long *count;      // selected k-mers (one atomic per wave)
+};
+
 struct GsSegParams {
     GsDbDev db;
     const uint8_t *seq;

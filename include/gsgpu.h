@@ -694,6 +694,49 @@ int gs_bloom_build(gs_bloom **out, int device, int kind, const int64_t *kmers, i
                    double fpp);
 int gs_bloom_get(gs_bloom *bloom, int64_t *bits, int32_t *n_hashes, int64_t *hash_factors, uint64_t *words, int64_t n_words);
 int gs_bloom_destroy(gs_bloom *bloom);
+
+/* The index goal: BloomIndexGoal.doMakeThis (C/goals/refseq/BloomIndexGoal.java:66-113) on a device store, in one call.
+ * requested[n_values] (host): != 0 = the value's node is requested (the per-node flag: any set of values, no subtree implied).
+ * The selected k-mers are the store's n_stored pairs (the contract of gs_dbexport_create: reachable, value has a tree node)
+ * whose value is requested.  The filter is sized by ensureExpectedSize(count, false) of its kind and filled with putLong of every
+ * selected k-mer, bit for bit what the reference builds from the same pairs.  Nothing is exported or sorted on the way.
+ *   kind GS_BLOOM_XOR / GS_BLOOM_MURMUR: geometry from (count, fpp), AbstractKMerBloomFilter.java:96-113,172-185;
+ *        count == 0 gives bits = 1, n_hashes = 1 (Math.round(+Inf) cast to int is -1, max(1, -1) = 1), no bit set.
+ *   kind GS_BLOOM_BLOCKED: BlockedKMerBloomFilter(10 bits per key, seed = Random(42).nextLong()),
+ *        buckets = (max(1, count) * 10 + 63) / 64, buckets + 17 words, putLong :109-125; fpp is ignored.
+ *   expected_insertions < 0: the count (what the goal does); >= 1: size for this many instead
+ *        (hosts that must reproduce a filter sized elsewhere; tests).  0: GS_E_INVALID.
+ *   *n_inserted (may be NULL) = the count.
+ * Seen bits and `more` bits are masked, so the call may run while a unique-counting run is alive on the store.
+ * A partition store (gs_db_create_part) is taken as the part it is.  A stripe of a striped store: GS_E_UNSUPPORTED.
+ * More than 64 hashes or more than 2^37 bits: GS_E_UNSUPPORTED, as gs_bloom_build.
+ * Every argument is checked before a device is touched. */
+int gs_bloom_build_db(gs_bloom **out, gs_db *db, int kind, const uint8_t *requested,
+                      int64_t expected_insertions, double fpp, int64_t *n_inserted);
+
+/* What a filter handle knows about itself (gs_bloom_get returns factors and words). */
+typedef struct {
+    int32_t kind, k;          /* k = 0: unknown (gs_bloom_create, gs_bloom_build)        */
+    int32_t n_hashes, pad;
+    int64_t bits, n_words;    /* BLOCKED: bits = buckets, n_words = buckets + 17          */
+    int64_t expected_insertions, n_inserted;   /* -1: unknown                             */
+    double  fpp;              /* 0: unknown                                               */
+} gs_bloom_info;
+int gs_bloom_get_info(gs_bloom *bloom, gs_bloom_info *info);
+
+/* Native index file, so that a later process filters without rebuilding the index:
+ *   header (72 bytes, little endian): magic "GSINDEX1" | int32 kind, k, n_hashes, pad | int64 bits, n_words,
+ *       expected_insertions, n_inserted | double fpp | uint64 checksum
+ *   hash factors: n_hashes int64 (BLOCKED: n_hashes = 1, the seed)
+ *   words: n_words uint64
+ * The checksum runs over factors and words (the store file's: over their 32-bit words w, a = 1, b = 0, a += w, b += a,
+ * checksum = a ^ (b << 1) ^ (b >> 63), all mod 2^64).  Not portable across versions.  Load checks magic, kind,
+ * 1 <= n_hashes <= 64, n_words against bits and kind, the exact file length and the checksum BEFORE a device is touched.
+ * A defect: GS_E_INVALID, and the message names the path and the defect.
+ * A file that cannot be opened, read or written: GS_E_IO. */
+int gs_bloom_save(gs_bloom *bloom, const char *path);
+int gs_bloom_load(gs_bloom **out, int device, const char *path);
+
 /* accept[i] = isAcceptRead(read i) ? 1 : 0.  profile != 0 records kernel time (gs_filter_kernel_time). */
 int gs_filter_submit(gs_bloom *bloom, int k, int min_pos_count, double positive_ratio, const uint8_t *seq,
                      const uint64_t *offsets, int64_t n_reads, int mem, uint8_t *accept, int profile);
