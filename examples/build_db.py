@@ -21,23 +21,24 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import genestrip_amd as ga  # noqa: E402
-from genestrip_amd import synth  # noqa: E402
+from genestrip_amd import host, synth  # noqa: E402
 
 
-def read_fasta(path):
-    """-> [(header without '>', sequence bytes without line ends)]"""
-    out, name, parts = [], None, []
-    with open(path, "rb") as f:
-        for line in f:
-            if line.startswith(b">"):
-                if name is not None:
-                    out.append((name, b"".join(parts)))
-                name, parts = line[1:].strip().decode("latin1"), []
-            elif name is not None:
-                parts.append(line.rstrip(b"\r\n"))
-    if name is not None:
-        out.append((name, b"".join(parts)))
-    return out
+def header_taxid(header):
+    """this example's rule: the first field of `>taxid|...` (a header line as the device hands it out: '>' first, no line end)"""
+    name = header[1:].strip().decode("latin1")
+    fields = name.split("|")[0].split()
+    return fields[0] if fields else ""
+
+
+def add_files(builder, paths, vi, by_file, update):
+    """one walk over the FASTA files (plain, gzip or BGZF): the records are found and their bases gathered on the device
+    (host.genome_files), this callback decides from the header lines which of them count and for which node -> GenomeTotals"""
+    def resolve(file, _first_record, headers):
+        tax_of_file = os.path.splitext(os.path.basename(paths[file]))[0]
+        return [vi.get(tax_of_file if by_file else header_taxid(h), -1) for h in headers]
+
+    return host.genome_files(paths, resolve, lambda seq, off, nodes: builder.add(seq, off, nodes, update=update))
 
 
 def main():
@@ -69,31 +70,36 @@ def main():
         vi = {t: i for i, t in enumerate(ids)}
         parent_vi = np.array([vi[parents[t]] if parents[t] is not None else -1 for t in ids], dtype=np.int32)
         n_values, taxids = len(ids), ids
-        regions = []
-        for path in args.fasta:
-            for name, seq in read_fasta(path):
-                tax = os.path.splitext(os.path.basename(path))[0] if args.by_file else name.split("|")[0].split()[0]
-                if tax in vi:
-                    regions.append((seq, vi[tax]))
     t_read = time.time() - t0
 
-    seq = np.frombuffer(b"".join(s for s, _ in regions), dtype=np.uint8)
-    off = np.cumsum([0] + [len(s) for s, _ in regions]).astype(np.uint64)
-    nodes = np.array([n for _, n in regions], dtype=np.int32)
     t0 = time.time()
     b = ga.DeviceDbBuilder(args.k, n_values, parent_vi, max_dust=args.max_dust)
-    b.add(seq, off, nodes, update=False)  # FillDBGoal: the k-mers of these regions are stored ...
-    b.add(seq, off, nodes, update=True)   # ... DBGoal: and every region moves the k-mers it shares towards the common ancestor
+    if args.demo:
+        seq = np.frombuffer(b"".join(s for s, _ in regions), dtype=np.uint8)
+        off = np.cumsum([0] + [len(s) for s, _ in regions]).astype(np.uint64)
+        nodes = np.array([n for _, n in regions], dtype=np.int32)
+        n_regions, n_bases = len(regions), len(seq)
+        b.add(seq, off, nodes, update=False)  # FillDBGoal: the k-mers of these regions are stored ...
+        b.add(seq, off, nodes, update=True)   # ... DBGoal: and every region moves the k-mers it shares towards the common ancestor
+    else:  # the same two walks over the files, as the reference makes them; the text never becomes Python objects
+        t = add_files(b, args.fasta, vi, args.by_file, update=False)
+        add_files(b, args.fasta, vi, args.by_file, update=True)
+        n_regions, n_bases = t.kept_records, t.kept_bases
+        t_walks = time.time() - t0
     n_kmers = b.finish_count()
     store = b.to_store()                  # the layout (records, overflow table, gate) without leaving the GPU
     b.close()
     t_build = time.time() - t0
     info = store.info
     store.save(args.out)
-    print("%d regions, %.1f Mbases read in %.2f s; %d distinct k-mers with LCA values + store layout in %.2f s "
-          "(%.0f Mbases/s); %d k-mers in records, %d in the overflow table; %s written (%.1f MB)" %
-          (len(regions), len(seq) / 1e6, t_read, n_kmers, t_build, len(seq) / t_build / 1e6, info.n_in_records,
-           info.n_stored - info.n_in_records, args.out, os.path.getsize(args.out) / 1e6))
+    if args.demo:
+        head = "%d regions, %.1f Mbases read in %.2f s; %d distinct k-mers with LCA values + store layout in %.2f s " % (
+            n_regions, n_bases / 1e6, t_read, n_kmers, t_build)
+    else:  # (the files are read inside the two walks: their time is part of the build's)
+        head = "%d regions, %.1f Mbases; two walks over the files, %d distinct k-mers with LCA values and store layout in %.2f s, %.2f s of it the walks " % (
+            n_regions, n_bases / 1e6, n_kmers, t_build, t_walks)
+    print(head + "(%.0f Mbases/s); %d k-mers in records, %d in the overflow table; %s written (%.1f MB)" %
+          (n_bases / t_build / 1e6, info.n_in_records, info.n_stored - info.n_in_records, args.out, os.path.getsize(args.out) / 1e6))
     if args.demo:  # the store answers reads drawn from its genomes
         rs, ro = synth.reads_host(db.genomes, 20000, read_len=150, seed=1)
         m = ga.FastqKMerMatcher(store)

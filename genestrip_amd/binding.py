@@ -60,6 +60,8 @@ ABI_SYMBOLS = (
     "gs_krakencount_create", "gs_krakencount_destroy", "gs_krakencount_get_device", "gs_krakencount_geometry", "gs_krakencount_submit",
     "gs_krakencount_chunk", "gs_krakencount_status", "gs_krakencount_reset", "gs_krakencount_fetch", "gs_krakencount_counters",
     "gs_krakencount_kernel_time",
+    "gs_genomes_create", "gs_genomes_scan", "gs_genomes_headers", "gs_genomes_gather", "gs_genomes_regions", "gs_genomes_kernel_time",
+    "gs_genomes_destroy",
 )
 
 
@@ -265,6 +267,9 @@ def lib():
         "gs_krakencount_chunk": (ci, [vp, i64, vp]), "gs_krakencount_status": (ci, [vp, vp, vp, vp, vp]), "gs_krakencount_reset": (ci, [vp]),
         "gs_krakencount_fetch": (ci, [vp, vp, vp, i64, vp]), "gs_krakencount_counters": (ci, [vp, vp]),
         "gs_krakencount_kernel_time": (ci, [vp, ci, vp, vp]),
+        "gs_genomes_create": (ci, [vp, ci]), "gs_genomes_scan": (ci, [vp, vp, i64, ci, ci, vp, vp, vp, vp]),
+        "gs_genomes_headers": (ci, [vp, vp, vp]), "gs_genomes_gather": (ci, [vp, vp, vp, vp]), "gs_genomes_regions": (ci, [vp, vp, vp]),
+        "gs_genomes_kernel_time": (ci, [vp, vp, vp]), "gs_genomes_destroy": (ci, [vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -471,6 +476,8 @@ def _ready(*bufs):
     if torch is None:
         return
     for b in bufs:
+        if isinstance(b, DeviceView):  # (memory of one of the library's own handles: complete when the handle hands it out)
+            continue
         if b is not None and getattr(b, "is_cuda", False):
             torch.cuda.current_stream(b.device).synchronize()
             return
@@ -948,6 +955,92 @@ class DeviceDbSizer:
     def close(self):
         if getattr(self, "h", None):
             lib().gs_dbsize_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceView:
+    """a device array that belongs to a handle of the library: what _ptr / _region_args take in place of a tensor (is_cuda says
+    where it lives; no torch stream is involved, the handle has synchronised its own)"""
+    is_cuda = True
+
+    def __init__(self, ptr, n, dtype, device):
+        self.ptr, self.shape, self.dtype, self.device = ptr, (n,), np.dtype(dtype), device
+
+    def data_ptr(self):
+        return self.ptr
+
+    def numpy(self):
+        """a host copy"""
+        raw = _fetch_device(self.device, C.c_void_p(self.ptr), self.shape[0] * self.dtype.itemsize)
+        return raw.view(self.dtype).copy()
+
+
+class DeviceGenomes:
+    """gs_genomes: genome FASTA text to the regions of a build.  scan() finds the records of a chunk, headers() hands their header
+    lines to the caller, gather() takes one keep flag per record and leaves the bases of the kept records on the device, regions()
+    is what DeviceDbBuilder / DeviceDbSizer / DeviceDbUpdater / DeviceDbQuality .add take.  A chunk with a NUL byte or a run of
+    more than 64 '\r' raises GsError(-4): it belongs to the host parser (host.genome_files does that)."""
+
+    def __init__(self, device=0):
+        self.h = C.c_void_p()
+        self.device = device
+        self.n_records = self.n_regions = self.n_bases = self.header_bytes = 0
+        _check(lib().gs_genomes_create(C.byref(self.h), device))
+
+    def scan(self, text, last=True):
+        """text: bytes, numpy uint8 or a device tensor of uint8 -> (n_records, consumed_bytes, header_bytes, max_line_bytes)"""
+        if isinstance(text, (bytes, bytearray, memoryview)):
+            text = np.frombuffer(text, dtype=np.uint8)
+        n = int(text.shape[0])
+        p, mem = _ptr(text) if n else (None, MEM_HOST)
+        _ready(text)
+        out = [C.c_int64(0) for _ in range(4)]
+        self.n_records = self.n_regions = self.n_bases = self.header_bytes = 0
+        _check(lib().gs_genomes_scan(self.h, p, n, mem, int(bool(last)), *[C.byref(o) for o in out]))
+        self.n_records, self.header_bytes = out[0].value, out[2].value
+        return tuple(o.value for o in out)
+
+    def headers(self):
+        """-> (headers uint8, header_off uint64[n_records + 1])"""
+        hdr = np.zeros(max(self.header_bytes, 1), dtype=np.uint8)
+        off = np.zeros(self.n_records + 1, dtype=np.uint64)
+        _check(lib().gs_genomes_headers(self.h, hdr.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p)))
+        return hdr[:self.header_bytes], off
+
+    def gather(self, keep=None):
+        """keep: one flag per record (None: all) -> (n_regions, n_bases)"""
+        pk = None
+        if keep is not None:
+            keep = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+            if len(keep) != self.n_records:
+                raise ValueError("keep must have one entry per record")
+            pk = keep.ctypes.data_as(C.c_void_p)
+        nr, nb = C.c_int64(0), C.c_int64(0)
+        _check(lib().gs_genomes_gather(self.h, pk, C.byref(nr), C.byref(nb)))
+        self.n_regions, self.n_bases = nr.value, nb.value
+        return nr.value, nb.value
+
+    def regions(self):
+        """-> (seq, offsets) on the device, valid until the next scan / gather / close"""
+        ps, po = C.c_void_p(), C.c_void_p()
+        _check(lib().gs_genomes_regions(self.h, C.byref(ps), C.byref(po)))
+        return DeviceView(ps.value, self.n_bases, np.uint8, self.device), DeviceView(po.value, self.n_regions + 1, np.uint64, self.device)
+
+    def kernel_time(self):
+        """-> (ms of the scan kernels, ms of the select and gather kernels) so far"""
+        a, b = C.c_double(0), C.c_double(0)
+        _check(lib().gs_genomes_kernel_time(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().gs_genomes_destroy(self.h)
             self.h = None
 
     def __del__(self):

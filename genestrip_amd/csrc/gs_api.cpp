@@ -4912,6 +4912,265 @@ extern "C" int gs_dbsize_plan(const int64_t *hist, int hist_bits, int k, int64_t
 }
 GS_API_CATCH
 
+// ---- Genome FASTA text to regions (gs_genomes.hip; include/gsgpu.h "gs_genomes"): the text work in front of the region stage.
+// A handle owns its stream and every buffer; the text is copied into its own padded buffer, so the caller's is free on return.
+struct gs_genomes {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int state = 0;  // 0: no chunk; 1: scanned; 2: gathered
+    uint8_t *d_text = nullptr;
+    size_t text_cap = 0;
+    u64 *d_tile = nullptr;  // tile_hl | tile_c, tile_cap entries each
+    size_t tile_cap = 0;
+    uint32_t *d_line = nullptr;  // nl | cnl, line_cap entries each
+    size_t line_cap = 0;
+    uint32_t *d_rec32 = nullptr;  // rec_start | rec_line | base_start | base_cnt, rec_cap entries each
+    u64 *d_rec64 = nullptr;       // hdr_off | sel | off | rec_block, rec_cap entries each
+    uint8_t *d_keep = nullptr;
+    size_t rec_cap = 0;
+    uint8_t *d_hdr = nullptr, *d_seq = nullptr;
+    size_t hdr_cap = 0, seq_cap = 0;
+    u64 *d_small = nullptr;  // status (GS_GN_WORDS words of 32 bits), res
+    int last = 0;
+    int64_t n_bytes = 0, n_tiles = 0, n_hdr = 0, n_nl = 0, n_records = 0, cut = 0, hdr_bytes = 0, max_line = 0, n_kept = 0, n_bases = 0;
+    KernelTimer t_scan, t_gather;
+};
+enum { GN_S_STATUS = 0, GN_S_RES = GS_GN_WORDS / 2, GN_S_WORDS = GN_S_RES + GS_GN_R_WORDS };
+
+static void gn_params(gs_genomes *g, GsGenomesParams *P) {
+    P->text = g->d_text;
+    P->n_bytes = g->n_bytes;
+    P->n_tiles = g->n_tiles;
+    P->last = g->last;
+    P->tile_hl = (unsigned long long *)g->d_tile;
+    P->tile_c = (unsigned long long *)g->d_tile + g->tile_cap;
+    P->status = (uint32_t *)(g->d_small + GN_S_STATUS);
+    P->res = (unsigned long long *)g->d_small + GN_S_RES;
+    P->n_hdr = g->n_hdr;
+    P->n_nl = g->n_nl;
+    P->n_records = g->n_records;
+    P->nl = g->d_line;
+    P->cnl = g->d_line + g->line_cap;
+    P->rec_start = g->d_rec32;
+    P->rec_line = g->d_rec32 + g->rec_cap;
+    P->base_start = g->d_rec32 + 2 * g->rec_cap;
+    P->base_cnt = g->d_rec32 + 3 * g->rec_cap;
+    P->hdr_off = (unsigned long long *)g->d_rec64;
+    P->sel = (unsigned long long *)g->d_rec64 + g->rec_cap;
+    P->off = (unsigned long long *)g->d_rec64 + 2 * g->rec_cap;
+    P->rec_block = (unsigned long long *)g->d_rec64 + 3 * g->rec_cap;
+    P->hdr_out = g->d_hdr;
+    P->keep = nullptr;
+    P->seq = g->d_seq;
+}
+
+extern "C" int gs_genomes_destroy(gs_genomes *g) {
+    if (!g) return GS_OK;
+    hipSetDevice(g->device);
+    if (g->stream) hipStreamSynchronize(g->stream);
+    timer_free(g->t_scan);
+    timer_free(g->t_gather);
+    for (void *p : {(void *)g->d_text, (void *)g->d_tile, (void *)g->d_line, (void *)g->d_rec32, (void *)g->d_rec64, (void *)g->d_keep, (void *)g->d_hdr,
+                    (void *)g->d_seq, (void *)g->d_small})
+        gs_dev_free(p);
+    if (g->stream) hipStreamDestroy(g->stream);
+    delete g;
+    return GS_OK;
+}
+
+extern "C" int gs_genomes_create(gs_genomes **out, int device) try {
+    if (!out) return fail(GS_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (device < 0) return fail(GS_E_INVALID, "device index out of range");
+    int rc = use_device(device);
+    if (rc) return rc;
+    gs_genomes *g = new gs_genomes();
+    g->device = device;
+    hipError_t e = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = gs_dev_alloc(&g->d_small, sizeof(u64) * GN_S_WORDS);
+    if (e != hipSuccess) {
+        gs_genomes_destroy(g);
+        return hip_fail(e, "gs_genomes_create");
+    }
+    *out = g;
+    return GS_OK;
+}
+GS_API_CATCH
+
+// the buffers grow by doubling: a collection's chunks are of one size, its records are not
+template <typename T>
+static int gn_grow(T **p, size_t *cap, size_t need, size_t arrays, hipStream_t stream) {
+    if (*cap >= need) return GS_OK;
+    HIP_TRY(hipStreamSynchronize(stream));
+    *cap = 0;
+    const int rc = renew(p, 2 * need * arrays);
+    if (!rc) *cap = 2 * need;
+    return rc;
+}
+
+// the per-record arrays, all of one capacity
+static int gn_record_room(gs_genomes *g, size_t need) {
+    if (g->rec_cap >= need) return GS_OK;
+    int rc = gn_grow(&g->d_rec32, &g->rec_cap, need, 4, g->stream);
+    if (!rc) rc = renew(&g->d_rec64, 4 * g->rec_cap);
+    if (!rc) rc = renew(&g->d_keep, g->rec_cap);
+    if (rc) g->rec_cap = 0;
+    return rc;
+}
+
+extern "C" int gs_genomes_scan(gs_genomes *g, const uint8_t *text, int64_t n_bytes, int mem, int last, int64_t *n_records, int64_t *consumed_bytes,
+                               int64_t *header_bytes, int64_t *max_line_bytes) try {
+    if (!g) return fail(GS_E_INVALID, "genomes is NULL");
+    if (n_bytes < 0 || (n_bytes > 0 && !text)) return fail(GS_E_INVALID, "text is NULL or n_bytes is negative");
+    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    if (!n_records || !consumed_bytes || !header_bytes || !max_line_bytes) return fail(GS_E_INVALID, "NULL output argument");
+    *n_records = *consumed_bytes = *header_bytes = *max_line_bytes = 0;
+    g->state = 0;
+    if (n_bytes > ((int64_t)1 << 30)) return fail(GS_E_UNSUPPORTED, "a chunk holds at most 1 GiB: a record that does not fit is the host parser's");
+    HIP_TRY(hipSetDevice(g->device));
+    g->n_bytes = n_bytes;
+    g->n_tiles = (n_bytes + GS_GN_TILE - 1) / GS_GN_TILE;
+    g->last = last != 0;
+    g->n_hdr = g->n_nl = g->n_records = g->cut = g->hdr_bytes = g->max_line = g->n_kept = g->n_bases = 0;
+    int rc;
+    if ((rc = gn_record_room(g, 1))) return rc;  // (a chunk without records still has off[0])
+    if (n_bytes == 0) {
+        g->state = 1;
+        return GS_OK;
+    }
+    const size_t padded = (size_t)g->n_tiles * GS_GN_TILE + GS_GN_PAD;
+    if ((rc = gn_grow(&g->d_text, &g->text_cap, padded, 1, g->stream))) return rc;
+    if ((rc = gn_grow(&g->d_tile, &g->tile_cap, (size_t)g->n_tiles + 1, 2, g->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(g->d_text, text, (size_t)n_bytes, mem == GS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, g->stream));
+    HIP_TRY(hipMemsetAsync(g->d_text + n_bytes, '\n', padded - (size_t)n_bytes, g->stream));
+    HIP_TRY(hipMemsetAsync(g->d_small, 0, sizeof(u64) * GN_S_WORDS, g->stream));
+    HIP_TRY(hipMemsetAsync(g->d_small + GN_S_STATUS, 0xff, 2 * sizeof(uint32_t), g->stream));  // GS_GN_NUL, GS_GN_CR: none
+    GsGenomesParams P{};
+    gn_params(g, &P);
+    if ((rc = timer_start(g->t_scan, true, g->stream))) return rc;
+    HIP_TRY(gs_launch_genomes_count(&P, g->stream));
+    if ((rc = timer_stop(g->t_scan, true, g->stream))) return rc;
+    uint32_t status[GS_GN_WORDS];
+    u64 sums[2];
+    HIP_TRY(hipMemcpyAsync(status, g->d_small + GN_S_STATUS, sizeof(status), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(&sums[0], P.tile_hl + g->n_tiles, sizeof(u64), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(&sums[1], P.tile_c + g->n_tiles, sizeof(u64), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));  // (the caller's text is free again)
+    if (status[GS_GN_NUL] != 0xffffffffu || status[GS_GN_CR] != 0xffffffffu) {
+        const bool nul = status[GS_GN_NUL] < status[GS_GN_CR];
+        return fail(GS_E_UNSUPPORTED, std::string("gs_genomes_scan: ") + (nul ? "a NUL byte" : "a run of more than " + std::to_string(GS_GN_CR_CAP) + " '\\r'") +
+                                          " at byte offset " + std::to_string(nul ? status[GS_GN_NUL] : status[GS_GN_CR]) + ": this chunk is the host parser's");
+    }
+    g->n_hdr = (int64_t)(sums[0] >> 32);
+    g->n_nl = (int64_t)(sums[0] & 0xffffffffu);
+    if (g->n_hdr >= GS_GN_MAX_RECORDS)  // (the selection scan keeps the kept records in the 24 bits above bit 40)
+        return fail(GS_E_UNSUPPORTED, "gs_genomes_scan: " + std::to_string((long long)g->n_hdr) + " header lines in one chunk: at most 2^24 - 1 (cut the chunk)");
+    g->n_records = g->last ? g->n_hdr : std::max<int64_t>(g->n_hdr - 1, 0);
+    if ((rc = gn_grow(&g->d_line, &g->line_cap, (size_t)g->n_nl + 1, 2, g->stream))) return rc;
+    if ((rc = gn_record_room(g, (size_t)g->n_hdr + 1))) return rc;
+    gn_params(g, &P);
+    if ((rc = timer_start(g->t_scan, true, g->stream))) return rc;
+    HIP_TRY(gs_launch_genomes_records(&P, g->stream));
+    if ((rc = timer_stop(g->t_scan, true, g->stream))) return rc;
+    u64 res[GS_GN_R_WORDS];
+    HIP_TRY(hipMemcpyAsync(status, g->d_small + GN_S_STATUS, sizeof(status), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(res, g->d_small + GN_S_RES, sizeof(res), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    if ((rc = timer_collect(g->t_scan))) return rc;
+    g->cut = (int64_t)res[GS_GN_R_CUT];
+    g->hdr_bytes = (int64_t)res[GS_GN_R_HDR_BYTES];
+    g->max_line = status[GS_GN_MAXLINE];
+    g->state = 1;
+    *n_records = g->n_records;
+    *consumed_bytes = g->cut;
+    *header_bytes = g->hdr_bytes;
+    *max_line_bytes = g->max_line;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_genomes_headers(gs_genomes *g, uint8_t *headers, uint64_t *header_off) try {
+    if (!g || !header_off) return fail(GS_E_INVALID, "NULL argument");
+    if (g->state < 1) return fail(GS_E_STATE, "gs_genomes_headers comes behind a gs_genomes_scan that took its chunk");
+    if (g->hdr_bytes > 0 && !headers) return fail(GS_E_INVALID, "headers is NULL");
+    header_off[0] = 0;
+    if (g->n_records == 0) return GS_OK;
+    HIP_TRY(hipSetDevice(g->device));
+    int rc = gn_grow(&g->d_hdr, &g->hdr_cap, (size_t)std::max<int64_t>(g->hdr_bytes, 1), 1, g->stream);
+    if (rc) return rc;
+    GsGenomesParams P{};
+    gn_params(g, &P);
+    HIP_TRY(gs_launch_genomes_headers(&P, g->stream));
+    if (g->hdr_bytes > 0) HIP_TRY(hipMemcpyAsync(headers, g->d_hdr, (size_t)g->hdr_bytes, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(header_off, P.hdr_off, sizeof(u64) * ((size_t)g->n_records + 1), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_genomes_gather(gs_genomes *g, const uint8_t *keep, int64_t *n_regions, int64_t *n_bases) try {
+    if (!g || !n_regions || !n_bases) return fail(GS_E_INVALID, "NULL argument");
+    *n_regions = *n_bases = 0;
+    if (g->state < 1) return fail(GS_E_STATE, "gs_genomes_gather comes behind a gs_genomes_scan that took its chunk");
+    HIP_TRY(hipSetDevice(g->device));
+    g->state = 1;
+    g->n_kept = g->n_bases = 0;
+    GsGenomesParams P{};
+    gn_params(g, &P);
+    int rc;
+    if (g->n_records == 0) {
+        HIP_TRY(hipMemsetAsync(P.off, 0, sizeof(u64), g->stream));
+    } else {
+        if (keep) {
+            HIP_TRY(hipMemcpyAsync(g->d_keep, keep, (size_t)g->n_records, hipMemcpyHostToDevice, g->stream));
+            P.keep = g->d_keep;
+        }
+        HIP_TRY(hipMemsetAsync(P.res + GS_GN_R_KEPT, 0, sizeof(u64), g->stream));
+        if ((rc = timer_start(g->t_gather, true, g->stream))) return rc;
+        HIP_TRY(gs_launch_genomes_select(&P, g->stream));
+        if ((rc = timer_stop(g->t_gather, true, g->stream))) return rc;
+        u64 kept = 0;
+        HIP_TRY(hipMemcpyAsync(&kept, P.res + GS_GN_R_KEPT, sizeof(u64), hipMemcpyDeviceToHost, g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));  // (the caller's flags are free again)
+        g->n_kept = (int64_t)(kept >> 40);
+        g->n_bases = (int64_t)(kept & ((1ULL << 40) - 1));
+    }
+    if ((rc = gn_grow(&g->d_seq, &g->seq_cap, (size_t)g->n_bases + 16, 1, g->stream))) return rc;
+    P.seq = g->d_seq;
+    if (g->n_bases > 0) {
+        if ((rc = timer_start(g->t_gather, true, g->stream))) return rc;
+        HIP_TRY(gs_launch_genomes_gather(&P, (g->cut + GS_GN_TILE - 1) / GS_GN_TILE, g->stream));
+        if ((rc = timer_stop(g->t_gather, true, g->stream))) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(g->stream));  // (the regions are complete: an _add call on its own stream may read them)
+    if ((rc = timer_collect(g->t_gather))) return rc;
+    g->state = 2;
+    *n_regions = g->n_kept;
+    *n_bases = g->n_bases;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_genomes_regions(gs_genomes *g, const uint8_t **d_seq, const uint64_t **d_off) {
+    if (!g || !d_seq || !d_off) return fail(GS_E_INVALID, "NULL argument");
+    if (g->state < 2) return fail(GS_E_STATE, "gs_genomes_regions comes behind gs_genomes_gather");
+    *d_seq = g->d_seq;
+    *d_off = (const uint64_t *)(g->d_rec64 + 2 * g->rec_cap);
+    return GS_OK;
+}
+
+extern "C" int gs_genomes_kernel_time(gs_genomes *g, double *ms_scan, double *ms_gather) {
+    if (!g || !ms_scan || !ms_gather) return fail(GS_E_INVALID, "NULL argument");
+    HIP_TRY(hipSetDevice(g->device));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    int rc = timer_collect(g->t_scan);
+    if (!rc) rc = timer_collect(g->t_gather);
+    if (rc) return rc;
+    *ms_scan = g->t_scan.total_ms;
+    *ms_gather = g->t_gather.total_ms;
+    return GS_OK;
+}
+
 // ---- DB-partitioned mode: encode / probe / reduce as separate steps (all pointers are device pointers)
 extern "C" int gs_match_encode(gs_run *run, const uint8_t *seq, const uint64_t *offsets, int64_t n_reads,
                                const uint64_t *pos_off, uint64_t *keys) {

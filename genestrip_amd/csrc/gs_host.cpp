@@ -6,6 +6,7 @@
 #include "gs_ingest.h"
 #include "gs_chunk.h"
 #include "gs_krakenparse.h"
+#include "gs_genomeparse.h"
 
 using namespace gs_host;
 
@@ -3117,6 +3118,227 @@ extern "C" int gs_host_kraken_count_files(int device, const char *const *paths, 
         i++;
     }
     return GS_OK;
+} catch (const std::bad_alloc &) {
+    return hfail(GS_E_NOMEM, "out of host memory");
+} catch (const std::exception &e) {
+    return hfail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
+}
+
+// ---- genome FASTA files to regions (AbstractFastaReader.readFasta under the store readers; gs_genomes on the device)
+namespace {
+
+struct GnGuard {
+    gs_genomes *&g;
+    ~GnGuard() {
+        if (g) gs_genomes_destroy(g);
+        g = nullptr;
+    }
+};
+
+struct GnCtx {
+    gs_genomes *g = nullptr;
+    gs_genome_resolve_fn resolve = nullptr;
+    gs_genome_sink_fn sink = nullptr;
+    void *resolve_user = nullptr, *sink_user = nullptr;
+    int file = 0;
+    int64_t first_record = 0;  // records of the file in front of the chunk
+    gs_host_genome_totals tot{};
+    std::vector<uint8_t> hdr, keep, kseq;
+    std::vector<uint64_t> hoff, koff;
+    std::vector<int32_t> vi, kvi;
+    GenomeRecords rec;
+};
+
+// the caller's decision for the n records of a chunk -> keep[n], kvi (vi of the kept ones); a callback's own code comes back as it is
+int gn_resolve(GnCtx &c, int64_t n, const uint8_t *hdr, const uint64_t *hoff) {
+    c.vi.assign((size_t)n, -1);
+    c.keep.assign((size_t)n, 0);
+    c.kvi.clear();
+    if (n == 0) return 0;
+    const int rc = c.resolve(c.resolve_user, c.file, c.first_record, n, hdr, hoff, c.vi.data());
+    if (rc) return rc;
+    for (int64_t i = 0; i < n; i++)
+        if (c.vi[(size_t)i] >= 0) {
+            c.keep[(size_t)i] = 1;
+            c.kvi.push_back(c.vi[(size_t)i]);
+        }
+    c.first_record += n;
+    c.tot.records += n;
+    c.tot.kept_records += (int64_t)c.kvi.size();
+    return 0;
+}
+
+// [p, p + n) line by line; last: the stream ends behind it.  *consumed: the bytes its whole records cover
+int gn_host_chunk(GnCtx &c, const uint8_t *p, size_t n, bool last, size_t *consumed) {
+    genome_parse(p, n, last, &c.rec);
+    *consumed = c.rec.consumed;
+    c.tot.chunks++;
+    c.tot.host_chunks++;
+    c.tot.text_bytes += (int64_t)c.rec.consumed;
+    c.tot.max_line_bytes = std::max(c.tot.max_line_bytes, c.rec.max_line);
+    const int64_t nr = c.rec.records();
+    int rc = gn_resolve(c, nr, c.rec.headers.data(), c.rec.header_off.data());
+    if (rc || c.kvi.empty()) return rc;
+    c.kseq.clear();
+    c.koff.assign(1, 0);
+    for (int64_t i = 0; i < nr; i++)
+        if (c.keep[(size_t)i]) {
+            c.kseq.insert(c.kseq.end(), c.rec.seq.begin() + (long)c.rec.off[(size_t)i], c.rec.seq.begin() + (long)c.rec.off[(size_t)i + 1]);
+            c.koff.push_back(c.kseq.size());
+        }
+    c.tot.kept_bases += (int64_t)c.kseq.size();
+    if (c.kseq.empty()) c.kseq.push_back(0);  // (regions of no bases: a pointer all the same)
+    return c.sink(c.sink_user, c.kseq.data(), c.koff.data(), c.kvi.data(), (int64_t)c.kvi.size(), GS_MEM_HOST);
+}
+
+// a chunk of whole records through the device; refused (or larger than the device takes): line by line
+int gn_chunk(GnCtx &c, const uint8_t *p, int64_t n) {
+    int64_t nr = 0, used = 0, hb = 0, ml = 0;
+    int rc = c.g ? gs_genomes_scan(c.g, p, n, GS_MEM_HOST, 1, &nr, &used, &hb, &ml) : (int)GS_E_UNSUPPORTED;
+    if (rc == GS_E_UNSUPPORTED) {
+        size_t all = 0;
+        return gn_host_chunk(c, p, (size_t)n, true, &all);
+    }
+    if (rc) return hfail(rc, gs_last_error());
+    c.tot.chunks++;
+    c.tot.text_bytes += used;
+    c.tot.max_line_bytes = std::max(c.tot.max_line_bytes, ml);
+    c.hdr.resize((size_t)hb + 1);
+    c.hoff.resize((size_t)nr + 1);
+    if ((rc = gs_genomes_headers(c.g, c.hdr.data(), c.hoff.data()))) return hfail(rc, gs_last_error());
+    if ((rc = gn_resolve(c, nr, c.hdr.data(), c.hoff.data())) || c.kvi.empty()) return rc;
+    int64_t n_regions = 0, n_bases = 0;
+    const uint8_t *d_seq = nullptr;
+    const uint64_t *d_off = nullptr;
+    if ((rc = gs_genomes_gather(c.g, c.keep.data(), &n_regions, &n_bases)) || (rc = gs_genomes_regions(c.g, &d_seq, &d_off)))
+        return hfail(rc, gs_last_error());
+    c.tot.kept_bases += n_bases;
+    return c.sink(c.sink_user, d_seq, d_off, c.kvi.data(), n_regions, GS_MEM_DEVICE);
+}
+
+// the file from `offset` on (in its text), line by line: some MiB of whole lines at a time, cut in front of the buffer's last header
+// line.  Where that line starts is noted as the lines come in, so a record of any length is looked at once, not once per turn.
+int gn_host_stream(GnCtx &c, const std::string &path, int64_t offset) {
+    LineReader lr;
+    if (!lr.open(path, offset)) return hfail(GS_E_IO, "cannot open " + path);
+    std::vector<uint8_t> text;
+    size_t want = (size_t)4 << 20;
+    for (bool eof = false; !eof;) {
+        size_t last_hdr = 0;  // start of the last header line behind the buffer's first byte (0: none)
+        while (text.size() < want) {
+            const size_t at = text.size();
+            if (lr.next_line(text) == 0) {
+                eof = true;
+                break;
+            }
+            if (at > 0 && text[at] == '>') last_hdr = at;
+        }
+        // the records that END in the buffer: all of it at the end of the stream, else what lies in front of its last header line;
+        // without one the buffer is one record that goes on (more of it), or whole lines that belong to no record
+        const size_t n = eof ? text.size() : last_hdr ? last_hdr : (!text.empty() && text[0] == '>') ? 0 : text.size();
+        if (n > 0) {
+            size_t used = 0;
+            const int rc = gn_host_chunk(c, text.data(), n, true, &used);
+            if (rc) return rc;
+            text.erase(text.begin(), text.begin() + (long)n);
+        }
+        want = text.size() + ((size_t)4 << 20);
+    }
+    return GS_OK;
+}
+
+// One pass over a file with reader blocks of `block` bytes, for the records from text offset `from` on (a plain file is read from
+// there; a gzip stream cannot be entered in the middle: it is inflated from its start and what lies in front of `from` -- whole
+// records, worked off by an earlier pass -- is passed over).  The blocks are cut in front of their last header line, so a chunk is
+// whole records and every one of them ends in it; what lies behind the last cut at the end of the file (no final newline) is one
+// more chunk.  *fallback_off >= 0: a record that does not fit the headroom of a block starts there.
+int gn_device_pass(GnCtx &c, const std::string &path, bool gzip, size_t block, int readers, int64_t from, int64_t *fallback_off) {
+    TextReader tr;
+    int err = tr.open(path, block, readers, gzip);
+    if (err) {
+        tr.close();
+        return err;
+    }
+    const int64_t base = gzip ? 0 : from;  // text offset of the pass's first byte
+    tr.start_off = base;
+    ChunkCutter cut;
+    cut.mode = ChunkCutter::FASTA;
+    // [p, p + n) lies at text offset `at`: its part from `from` on (`from` is where a chunk of an earlier pass started: a header line)
+    const auto chunk_from = [&](const uint8_t *p, int64_t n, int64_t at) {
+        const int64_t d = std::min<int64_t>(std::max<int64_t>(from - at, 0), n);
+        return n - d > 0 ? gn_chunk(c, p + d, n - d) : (int)GS_OK;
+    };
+    tr.start();
+    for (int64_t i = 0; !err; i++) {
+        TextSlot &sl = tr.wait_full(i);
+        if ((err = block_error(tr, sl, path))) break;
+        const bool eof = sl.eof;
+        const ChunkCutter::Cut what = cut_block(cut, tr, sl);
+        if (what == ChunkCutter::FALLBACK) {
+            *fallback_off = std::max(from, base + cut.file_off);
+        } else if (what == ChunkCutter::CHUNK) {
+            err = chunk_from(cut.start, cut.bytes, base + cut.file_off);
+            if (!err) cut.commit();
+        }
+        tr.release(i);
+        if (eof || *fallback_off >= 0) break;
+    }
+    tr.close();
+    if (err || *fallback_off >= 0) return err;
+    return chunk_from(cut.carry.data(), (int64_t)cut.carry.size(), base + cut.file_off);
+}
+
+// One file through the device.  A record longer than a block: the file goes on from that record with blocks twice as large, up to
+// 512 MiB (a chunk -- the carry and a block -- holds at most 1 GiB); a record beyond that size is the line-by-line loop's, with the
+// rest of its file.  The readers pin 2 x readers blocks of twice the block size (gzip: 4 of them): the readers of a plain file are
+// cut down as the blocks grow so that they stay within 1 GiB of page-locked memory (2 GiB at 512 MiB; gzip: 0.5 GiB at the default
+// block, 4 GiB at 512 MiB), and the idle blocks of the smaller size go back before a pass with larger ones starts.
+int gn_device_file(GnCtx &c, const std::string &path, bool gzip) {
+    size_t block;
+    int readers = 0;
+    reader_shape(gzip, &block, &readers);
+    if (!getenv("GS_HOST_BLOCK_BYTES")) block = (size_t)64 << 20;  // (genomes, not reads: a record is megabytes)
+    const size_t largest = (size_t)512 << 20;
+    for (int64_t from = 0;;) {
+        const int fit = (int)std::max<size_t>(1, ((size_t)256 << 20) / block);
+        int64_t fallback_off = -1;
+        const int err = gn_device_pass(c, path, gzip, block, gzip ? readers : std::min(readers, fit), from, &fallback_off);
+        if (err || fallback_off < 0) return err;
+        if (block >= largest) return gn_host_stream(c, path, fallback_off);
+        block = std::min(block * 2, largest);
+        from = fallback_off;
+        gs_host::pinned_pool().release_all();  // (the readers' blocks: gs_ingest.h)
+    }
+}
+
+}  // namespace
+
+extern "C" int gs_host_genome_files(const char *const *paths, int n_paths, int device, gs_genome_resolve_fn resolve, void *resolve_user,
+                                    gs_genome_sink_fn sink, void *sink_user, gs_host_genome_totals *totals) try {
+    if (!paths || n_paths < 0 || !resolve || !sink) return hfail(GS_E_INVALID, "NULL argument");
+    for (int f = 0; f < n_paths; f++)
+        if (!paths[f]) return hfail(GS_E_INVALID, "NULL path");
+    bool fast = true;
+    if (const char *e = getenv("GS_HOST_FAST")) fast = atoi(e) != 0;
+    const double t_start = now_s();
+    GnCtx c;
+    GnGuard guard{c.g};
+    c.resolve = resolve;
+    c.resolve_user = resolve_user;
+    c.sink = sink;
+    c.sink_user = sink_user;
+    if (fast && gs_genomes_create(&c.g, device) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
+    int err = GS_OK;
+    for (int f = 0; f < n_paths && !err; f++) {
+        const std::string path(paths[f]);
+        c.file = f;
+        c.first_record = 0;
+        const int kind = fast ? text_path_kind(path) : 0;
+        err = kind ? gn_device_file(c, path, kind == 2 || kind == 4) : gn_host_stream(c, path, 0);
+    }
+    c.tot.seconds_total = now_s() - t_start;
+    if (totals) *totals = c.tot;
+    return err;
 } catch (const std::bad_alloc &) {
     return hfail(GS_E_NOMEM, "out of host memory");
 } catch (const std::exception &e) {

@@ -233,6 +233,13 @@ hipError_t gs_launch_update_dir(const u64 *keys, int64_t m, int k, int dir_bits,
 hipError_t gs_launch_update_lookup(const GsUpdateParams *P, int64_t max_pairs, int n_cu, hipStream_t stream);
 hipError_t gs_launch_update_moved(const int32_t *vals, const int32_t *vals0, int64_t m, u64 *count, int n_cu, hipStream_t stream);
 
+// ---- gs_genomes.hip: genome FASTA text -> regions
+hipError_t gs_launch_genomes_count(const GsGenomesParams *P, hipStream_t stream);
+hipError_t gs_launch_genomes_records(const GsGenomesParams *P, hipStream_t stream);
+hipError_t gs_launch_genomes_headers(const GsGenomesParams *P, hipStream_t stream);
+hipError_t gs_launch_genomes_select(const GsGenomesParams *P, hipStream_t stream);
+hipError_t gs_launch_genomes_gather(const GsGenomesParams *P, int64_t cut_tiles, hipStream_t stream);
+
 // ---- gs_size.hip
 hipError_t gs_launch_size_count(const GsSizeParams *P, int n_cu, hipStream_t stream);
 hipError_t gs_size_sort_bytes(int64_t n, int key_bits, size_t *tmp_bytes);

@@ -347,3 +347,38 @@ struct GsKrakenCountParams {
     unsigned long long *counters;  // [0] global atomics of the accumulation [1] tokens whose key went straight to the global table
     unsigned long long *result;    // GS_KC_R_WORDS
 };
+
+// ---- gs_genomes.hip: genome FASTA text -> regions of the kept records
+#define GS_GN_TILE 4096   // bytes per tile: GS_SCAN_BLOCK threads, 16 bytes each; the piece of the gather
+#define GS_GN_CR_CAP 64   // a run of more '\r' than this refuses the chunk (the look-ahead behind a '\r' is bounded by it)
+#define GS_GN_MAX_RECORDS (1 << 24)  // header lines of a chunk stay below this: the selection scan packs kept records << 40 | bases
+#define GS_GN_PAD 128     // '\n' bytes behind the last tile of the text: the look-ahead reads up to GS_GN_CR_CAP + 1 bytes on
+enum { GS_GN_NUL = 0,      // status: offset of the first NUL byte (~0: none)
+       GS_GN_CR = 1,       // offset of the first run of more than GS_GN_CR_CAP '\r' (~0: none)
+       GS_GN_MAXLINE = 2,  // the longest line in front of the cut, its newline included
+       GS_GN_WORDS = 4 };
+enum { GS_GN_R_CUT = 0,        // res: bytes the records that end inside the chunk cover
+       GS_GN_R_HDR_BYTES = 1,  // bytes of their header lines
+       GS_GN_R_KEPT = 2,       // kept records << 40 | their bases
+       GS_GN_R_WORDS = 4 };
+struct GsGenomesParams {
+    const uint8_t *text;          // n_bytes, then '\n' up to n_tiles * GS_GN_TILE + GS_GN_PAD
+    int64_t n_bytes, n_tiles;
+    int32_t last, pad;            // last != 0: the stream ends with this chunk
+    unsigned long long *tile_hl;  // n_tiles + 1: header lines << 32 | newlines per tile, then their exclusive prefix and the sum
+    unsigned long long *tile_c;   // the same for content bytes
+    uint32_t *status;             // GS_GN_WORDS
+    unsigned long long *res;      // GS_GN_R_WORDS
+    int64_t n_hdr, n_nl;          // header lines and newlines of the chunk (the sums, read back by the caller)
+    int64_t n_records;            // records that end inside the chunk: n_hdr, without `last` one less
+    uint32_t *nl, *cnl;           // per newline: its offset, the content bytes in front of it
+    uint32_t *rec_start, *rec_line;   // per header line: its offset, its line number
+    uint32_t *base_start, *base_cnt;  // per record: content index of its first base, its bases
+    unsigned long long *hdr_off;      // n_records + 1: where its header line goes in hdr_out
+    unsigned long long *rec_block;    // per block of GS_SCAN_BLOCK records: the sums of the scans over the records
+    uint8_t *hdr_out;
+    const uint8_t *keep;          // n_records flags, or nullptr: every record
+    unsigned long long *sel;      // n_records + 1: kept records << 40 | their bases in front of each record
+    unsigned long long *off;      // kept + 1: the regions' offsets
+    uint8_t *seq;                 // their bases
+};

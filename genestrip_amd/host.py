@@ -59,6 +59,7 @@ def lib():
         "gs_host_write_csv": (ci, [C.c_char_p, vp, vp, vp, vp]),
         "gs_host_write_quality_csv": (ci, [C.c_char_p, vp, vp, vp]),
         "gs_host_kraken_count_files": (ci, [ci, vp, ci, vp, ci, C.c_char_p, vp, C.c_int32, vp, i64, vp, vp]),
+        "gs_host_genome_files": (ci, [vp, ci, ci, vp, vp, vp, vp, vp]),
         "gs_host_write_kraken_csv": (ci, [C.c_char_p, vp, C.c_int32, vp, i64]),
         "gs_host_db2fastq": (ci, [vp, vp, C.c_char_p, C.c_int32, ci, C.c_char_p, vp]),
         "gs_host_last_error": (C.c_char_p, []), "gs_host_java_double": (ci, [C.c_double, vp, ci]),
@@ -335,3 +336,68 @@ def write_kraken_csv(path, rows):
         keys[i, :len(k)] = np.frombuffer(bytes(k), dtype=np.uint8)
         cnt[i] = v
     _check(lib().gs_host_write_kraken_csv(os.fspath(path).encode(), keys.ctypes.data_as(C.c_void_p), stride, cnt.ctypes.data_as(C.c_void_p), len(rows)))
+
+
+class GenomeTotals(C.Structure):
+    _fields_ = [("records", C.c_int64), ("kept_records", C.c_int64), ("text_bytes", C.c_int64), ("kept_bases", C.c_int64),
+                ("chunks", C.c_int64), ("host_chunks", C.c_int64), ("max_line_bytes", C.c_int64), ("seconds_total", C.c_double)]
+
+
+_RESOLVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
+_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int)
+_CALLBACK_RAISED = -1000
+
+
+def genome_files(paths, resolve, sink, device=0):
+    """gs_host_genome_files: genome FASTA files (plain, gzip, BGZF) -> the regions of a build.  resolve(file, first_record, headers)
+    gets the header lines (a list of bytes, '>' included) of a batch of records and returns one value index per record (< 0: skip),
+    or a non-zero int as its error code; sink(seq, offsets, vi) gets the kept regions -- seq / offsets as device views or numpy
+    arrays, in both cases what DeviceDbBuilder.add, DeviceDbSizer.add, DeviceDbUpdater.add and DeviceDbQuality.add take, valid
+    until it returns -- and may return a non-zero int as well.  Such a code ends the walk and comes back as GsError(code); use
+    POSITIVE codes: -1 .. -7 are the library's own GS_E_* codes and are reported with the library's last message.  An exception
+    raised inside a callback ends the walk and is raised again.  -> GenomeTotals"""
+    raised = []
+
+    def _resolve(_user, file, first, n, hdr, hoff, vi):
+        try:
+            off = np.ctypeslib.as_array(C.cast(hoff, C.POINTER(C.c_uint64)), (n + 1,))
+            raw = C.string_at(hdr, int(off[n]))
+            got = resolve(file, first, [raw[int(off[i]):int(off[i + 1])] for i in range(n)])
+            if isinstance(got, (int, np.integer)) and not isinstance(got, bool):
+                return int(got)
+            got = np.ascontiguousarray(got, dtype=np.int32)
+            if len(got) != n:
+                raise ValueError("resolve must return one value index per record")
+            C.memmove(vi, got.ctypes.data, 4 * n)
+            return 0
+        except BaseException as e:  # noqa: BLE001 -- nothing may leave through the C frames
+            raised.append(e)
+            return _CALLBACK_RAISED
+
+    def _sink(_user, seq, off, vi, n, mem):
+        try:
+            v = np.ctypeslib.as_array(C.cast(vi, C.POINTER(C.c_int32)), (n,)).copy()
+            if mem == _b.MEM_DEVICE:
+                o = _b.DeviceView(off, n + 1, np.uint64, device)
+                total = int(o.numpy()[-1])
+                s = _b.DeviceView(seq, total, np.uint8, device)
+            else:
+                o = np.ctypeslib.as_array(C.cast(off, C.POINTER(C.c_uint64)), (n + 1,))
+                s = np.ctypeslib.as_array(C.cast(seq, C.POINTER(C.c_uint8)), (max(int(o[n]), 1),))[:int(o[n])]
+            got = sink(s, o, v)
+            return int(got) if isinstance(got, (int, np.integer)) and not isinstance(got, bool) else 0
+        except BaseException as e:  # noqa: BLE001
+            raised.append(e)
+            return _CALLBACK_RAISED
+
+    paths = [os.fspath(p) for p in paths]
+    arr, n = _cstr_array(paths), len(paths)
+    t = GenomeTotals()
+    r_fn, s_fn = _RESOLVE_FN(_resolve), _SINK_FN(_sink)
+    rc = lib().gs_host_genome_files(arr, n, device, r_fn, None, s_fn, None, C.byref(t))
+    if raised:
+        raise raised[0]
+    if rc > 0 or rc < -7:
+        raise _b.GsError(rc, "a callback of genome_files ended the walk with this code")
+    _check(rc)
+    return t

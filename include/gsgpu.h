@@ -1032,6 +1032,56 @@ int gs_krakencount_counters(gs_krakencount *kc, int64_t counters[2]);
 /* profile != 0: from now on the kernels of every chunk run between events; launches / total_ms: what they add up to so far */
 int gs_krakencount_kernel_time(gs_krakencount *kc, int profile, int64_t *launches, double *total_ms);
 
+/* ---------------------------------------------------------------------------------------------------
+ * genomes: genome FASTA text to the regions of a build (genestrip_amd/csrc/gs_genomes.hip)
+ *
+ * Replaces the line walk of AbstractFastaReader.readFasta (C/fasta/AbstractFastaReader.java:97-130) over
+ * BufferedLineReader.nextLine (B/io/BufferedLineReader.java:160-182) and the strip of AbstractStoreFastaReader.dataLine
+ * (C/refseq/AbstractStoreFastaReader.java:87-114) in front of gs_dbsize_add / gs_dbbuild_add / gs_dbupdate_add / gs_dbquality_add.
+ * The device does the text work only: which records count, and for which node, is the caller's decision (accession map, tree,
+ * limits), taken from the header lines the scan hands out and given back as one flag per record.
+ *
+ * A record is a header line (first byte '>') and the data lines up to the next header line.  Of a data line the trailing run of
+ * '\n' / '\r' is stripped, every other byte is a base of the region ('\r' with a byte of its line behind its run, lower case and
+ * '>' inside a line included); empty lines give nothing; a header line without data lines is a region of 0 bases; data lines in
+ * front of the first header line of the text belong to no region.  The last line may lack its newline.
+ *
+ * gs_genomes_scan     text: n_bytes (at most 1 GiB, more: GS_E_UNSUPPORTED) in host or device memory (mem), free again on return
+ *                     (the handle works on a copy).  last != 0: the stream ends with this chunk.  *n_records: the records that
+ *                     END inside the chunk -- those in front of its last header line, with `last` all of them; *consumed_bytes:
+ *                     the bytes they cover (the offset of that last header line; without any header line: behind the last
+ *                     newline; with `last`: n_bytes).  The caller puts text[*consumed_bytes ..] in front of the next chunk; if
+ *                     nothing was consumed it grows the chunk, and a record that does not fit 1 GiB is the host parser's.
+ *                     *header_bytes: bytes of the records' header lines ('>' up to but excluding the '\n', a '\r' included).
+ *                     *max_line_bytes: the longest line in front of the cut with its newline (the reference throws when a line
+ *                     reaches fastaLineSizeBytes - 1; here that is the caller's to report).
+ *                     REFUSED with GS_E_UNSUPPORTED -- the message names the first bad byte offset -- is a chunk with a NUL byte
+ *                     (the reference drops it before it looks at the line) or with a run of more than 64 '\r' (the look-ahead of
+ *                     the strip rule is bounded): such a chunk belongs to the host parser (include/gshost.h); the handle stays
+ *                     usable and holds no chunk.
+ *                     A chunk of 2^24 header lines or more is GS_E_UNSUPPORTED as well (the message gives the count; the
+ *                     selection keeps the kept records in 24 bits): the caller cuts it; nothing was consumed.
+ * gs_genomes_headers  the header lines back to back and header_off[n_records + 1] (host arrays, header_bytes / n_records + 1).
+ * gs_genomes_gather   keep[n_records] (host; != 0: kept; NULL: every record) -> the bases of the kept records alone, in order, as
+ *                     seq / off[*n_regions + 1] (uint64 from 0) on the device.  May be called again with other flags.
+ * gs_genomes_regions  the device arrays of the last gather, in the form every _add call takes with GS_MEM_DEVICE.  Valid until the
+ *                     next scan, gather or destroy on this handle.  They are complete when gather returns (it synchronises),
+ *                     and all four _add calls synchronise their own stream before they return, so an _add that has returned
+ *                     no longer reads them: no fence is needed between _add and the next scan.
+ * gs_genomes_kernel_time  time between events on the handle's stream so far: the scan kernels, the select and gather kernels.
+ * Call order: scan, then headers / gather in any order and number, regions behind a gather; anything else: GS_E_STATE, as after a
+ * refused scan.  NULL or negative arguments: GS_E_INVALID, before any device call.  Device buffers grow by doubling.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct gs_genomes gs_genomes;
+int gs_genomes_create(gs_genomes **out, int device);
+int gs_genomes_scan(gs_genomes *g, const uint8_t *text, int64_t n_bytes, int mem, int last, int64_t *n_records, int64_t *consumed_bytes,
+                    int64_t *header_bytes, int64_t *max_line_bytes);
+int gs_genomes_headers(gs_genomes *g, uint8_t *headers, uint64_t *header_off);
+int gs_genomes_gather(gs_genomes *g, const uint8_t *keep, int64_t *n_regions, int64_t *n_bases);
+int gs_genomes_regions(gs_genomes *g, const uint8_t **d_seq, const uint64_t **d_off);
+int gs_genomes_kernel_time(gs_genomes *g, double *ms_scan, double *ms_gather);
+int gs_genomes_destroy(gs_genomes *g);
+
 #ifdef __cplusplus
 }
 #endif

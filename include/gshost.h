@@ -15,6 +15,8 @@
  *                         (C/match/MatchingResult.java:84-118, C/match/ResultReporter.java:190-279)
  *   gs_host_kraken_count_files  the krakencount goal: Kraken-style output files -> reads / k-mers per tax id
  *   gs_host_write_quality_csv  the dbquality goal's CSV (DBQualityCountsGoal's rank aggregation + DBQualityCSVGoal.makeFile)
+ *   gs_host_genome_files  genome FASTA files -> the regions of a build (the walk of AbstractFastaReader.readFasta under the
+ *                         store readers), records found and bases gathered on the device, the selection left to a callback
  * (C/ = core/src/main/java/org/metagene/genestrip/, B/ = base/src/main/java/org/metagene/genestrip/)
  */
 #ifndef GSHOST_H
@@ -195,6 +197,33 @@ int gs_host_kraken_count_files(int device, const char *const *paths, int n_paths
                                gs_host_kraken_totals *totals);
 /* taxid;reads;kmers;kmers in matching reads -- then key;reads;kmers;kimr; per row, '\n' line ends; .gz / .gzip: gzip */
 int gs_host_write_kraken_csv(const char *path, const char *keys, int32_t key_stride, const int64_t *counts, int64_t n_rows);
+
+/* ---- genome FASTA files to the regions of a build (the walk of AbstractFastaReader.readFasta that fillsize, tempindex / filldb,
+ * updatedb and dbqualcounts each repeat): every file (plain or gzip, BGZF included), in order, is cut into chunks of whole records;
+ * gs_genomes (include/gsgpu.h) finds the records of a chunk on the device, `resolve` sees their header lines and says per record
+ * which value index it counts for (vi[i] < 0: skip -- accession map, tree, limits are the caller's), the bases of the kept records
+ * are gathered on the device and handed to `sink` as (seq, off[n_regions + 1], vi[n_regions]) with vi compacted to the kept
+ * regions: exactly what gs_dbsize_add / gs_dbbuild_add / gs_dbupdate_add / gs_dbquality_add take, with `mem` saying where seq and
+ * off live.  They are valid until the sink returns.  A record longer than a reader block (GS_HOST_BLOCK_BYTES; this loop's default
+ * is 64 MiB): the file goes on from that record with blocks twice as large, up to the 1 GiB a chunk may hold (a gzip stream is
+ * inflated from its start again, what has been worked off is passed over); a record beyond that size, with the rest of its file,
+ * goes through a line-by-line restatement of the reference
+ * (genestrip_amd/csrc/gs_genomeparse.h), as do a chunk the device refuses (a NUL byte, a run of more than 64 '\r') and everything
+ * under GS_HOST_FAST=0 (no device is used then); they reach the same sink with mem = GS_MEM_HOST.  first_record counts the records of `file` (an index into paths) in front of the batch.  A callback's
+ * non-zero return ends the walk and is returned (positive codes keep it apart from the GS_E_* codes of the call itself).  Blocks are read and gzip is inflated by the threads of the text readers the
+ * other goals use; the text of a chunk is staged to the device by gs_genomes_scan. ---- */
+typedef int (*gs_genome_resolve_fn)(void *user, int file, int64_t first_record, int64_t n_records, const uint8_t *headers,
+                                    const uint64_t *header_off, int32_t *vi);
+typedef int (*gs_genome_sink_fn)(void *user, const uint8_t *seq, const uint64_t *off, const int32_t *vi, int64_t n_regions, int mem);
+typedef struct {
+    int64_t records, kept_records;       /* records seen; records the resolver kept                                        */
+    int64_t text_bytes, kept_bases;      /* bytes of FASTA text walked; bases handed to the sink                           */
+    int64_t chunks, host_chunks;         /* chunks in all; chunks (and rests of files) the line-by-line parser took        */
+    int64_t max_line_bytes;              /* the longest line with its newline (the reference throws from fastaLineSizeBytes - 1 on) */
+    double seconds_total;
+} gs_host_genome_totals;
+int gs_host_genome_files(const char *const *paths, int n_paths, int device, gs_genome_resolve_fn resolve, void *resolve_user,
+                         gs_genome_sink_fn sink, void *sink_user, gs_host_genome_totals *totals);
 
 /* The host layer keeps page-locked blocks and the device decoders of gzip input (gigabytes of HBM) from call to call; this hands
  * them back (a long-lived JVM host before it loads a big store).  No other thread may be inside the host layer meanwhile. */
