@@ -135,6 +135,8 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
         constexpr bool SN = FIXED && !REC && !WIDE && (GS_ABLATE & 1) == 0;
         bool sn = false;
         constexpr int NP = WIDE ? 2 : 1;
+// "lane 0" on the paths the FIXED loop takes: a literal mask there (a compare's result is kept across the loop in a scalar pair)
+#define GS_LANE0 (FIXED ? GS_ACT(1ULL) : lane == 0)
         int path[NP], ptin[NP], ptout[NP], used = 0;            // candidate paths: path i in lane i & 63 of set i >> 6
 #pragma unroll
         for (int h = 0; h < NP; h++) {
@@ -151,6 +153,8 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
             for (int w = 0; w < 3; w++) {
                 if (LONG)
                     gs_load_word(rd, L, 2 * it + w, lane, Bhi[w], Blo[w], Bbad[w]);
+                else if (FIXED)
+                    gs_word_from_byte_fixed(pre[w], Bhi[w], Blo[w], Bbad[w]);
                 else
                     gs_word_from_byte(pre[w], Bhi[w], Blo[w], Bbad[w]);
             }
@@ -192,7 +196,7 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
 #define GS_AGG_ALL 0
 #endif
                 const u64 live[2] = {~0ULL, live1};
-                gs_probe_planes<KC, STRIPED, CTX, (REC || GS_AGG_ALL) && !LONG>(db, Bhi, Blo, Bbad, base, max, lane, node, wave_g, mk, FIXED ? live : nullptr);
+                gs_probe_planes<KC, STRIPED, CTX, (REC || GS_AGG_ALL) && !LONG, 2, FIXED>(db, Bhi, Blo, Bbad, base, max, lane, node, wave_g, mk, FIXED ? live : nullptr);
             }
 
             if (!LONG) GS_STAMP(5, node[0] ^ node[1])
@@ -276,9 +280,14 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
                         // (n_miss, bad_lo and bad_hi again, from masks the compiler cannot match with theirs: with a second use up
                         // here their popcounts are no longer sunk into the classification below, and every read that hits nothing
                         // pays some twenty scalar instructions for them.  FIXED: word 0 whole, of word 1 live1 >> 1, of word 2 none)
-                        u64 q0 = __ballot(node[0] == GS_NODE_MISS), q1 = __ballot(node[1] == GS_NODE_MISS), b0 = Bbad[0], b1 = Bbad[1], b2 = Bbad[2];
-                        asm volatile("" : "+s"(q0), "+s"(q1), "+s"(b0), "+s"(b1), "+s"(b2));
-                        const u64 lo1 = live1 >> 1;
+                        // The miss masks are hidden by their compare VALUE, not as masks: a ballot whose compare lives in another block
+                        // comes back through the vector unit (v_cndmask 0/1 + v_cmp_ne per mask).  live1 is hidden too: its shifted
+                        // copy and the complement are otherwise built in front of the loop, spilled and read back lane by lane
+                        int miss = GS_NODE_MISS;
+                        u64 b0 = Bbad[0], b1 = Bbad[1], b2 = Bbad[2], l1 = live1;
+                        asm volatile("" : "+s"(miss), "+s"(b0), "+s"(b1), "+s"(b2), "+s"(l1));
+                        const u64 q0 = __ballot(node[0] == miss), q1 = __ballot(node[1] == miss);
+                        const u64 lo1 = l1 >> 1;
                         tax_err = __popcll(q0) + __popcll(q1) + __popcll(b0) + __popcll(b1 & lo1) + ((((b1 & ~lo1) | b2) != 0) ? 1 : 0);
                         if (((qt->tax_disabled[tax_err >> 5] >> (tax_err & 31)) & 1u) == 0) {
                             out_class = (P.threshold <= 1 || one_cnt >= P.threshold) ? one_vi : -1;
@@ -331,8 +340,8 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
                     const int up0 = __shfl_up(node[0], 1);
                     const int up1 = __shfl_up(node[1], 1);
                     const int last0 = gs_readlane(node[0], 63);
-                    prev[0] = lane == 0 ? carry_last : up0;
-                    prev[1] = lane == 0 ? last0 : up1;
+                    prev[0] = GS_LANE0 ? carry_last : up0;
+                    prev[1] = GS_LANE0 ? last0 : up1;
                 }
                 // (positions >= max hold NONE: the first of them differs from its predecessor and is masked away; wave-level masks
                 // throughout, as in gs_probe_planes)
@@ -384,14 +393,14 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
                 // the candidate-path state is set up only if a second node follows)
                 if (!LONG) {
                     if (!REC) GS_FIRST_NODE()
-                    if (!(REC && deferred) && lane == 0) st.add(one_vi, GS_S_READS_1KMER, 1);  // first k-mer of this tax id in the read (:434-439)
+                    if (!(REC && deferred) && GS_LANE0) st.add(one_vi, GS_S_READS_1KMER, 1);  // first k-mer of this tax id in the read (:434-439)
                     if ((m0 | m1) != 0) {
-                        if (lane == 0) {
+                        if (GS_LANE0) {
                             dviA = one_vi;
                             dcntA = one_cnt;
                         }
                         if (P.classify) {  // mergeReadTaxidPath into the empty list (max_paths >= 1)
-                            if (lane == 0) {
+                            if (GS_LANE0) {
                                 path[0] = one_vi;
                                 ptin[0] = st.tin[one_vi];
                                 ptout[0] = st.tout[one_vi];
@@ -430,7 +439,7 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
                     }
                     if (first) {
                         // first k-mer of this tax id in the read (:434-439)
-                        if (lane == 0) st.add(nvj, GS_S_READS_1KMER, 1);
+                        if (GS_LANE0) st.add(nvj, GS_S_READS_1KMER, 1);
                         if (P.classify) {  // mergeReadTaxidPath (:568-586)
                             const int ntin = st.tin[nvj], ntout = st.tout[nvj];
                             bool related = false;  // the first path (in path order) that is an ancestor or a descendant
@@ -484,7 +493,7 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
                     def_contigs++;
                     def_sq += len * len;
                     def_max = len > def_max ? len : def_max;
-                } else if (lane == 0)
+                } else if (GS_LANE0)
                     st.contig(carry_last, len, key_lo);
             }
             // ---- 4c. classification (:474-531)
@@ -640,7 +649,7 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
                             } else if (FIXED) {
                                 const double err = qt->e[tax_err].q, err_sq = qt->e[tax_err].q2;  // (16 bytes each: one scalar load)
                                 const double cerr = qt->e[class_err].q, cerr_sq = qt->e[class_err].q2;
-                                if (lane == 0) {
+                                if (GS_LANE0) {
                                     st.add(cn, GS_S_READS, 1);
                                     st.add(cn, GS_S_READS_KMERS, (u64)read_kmers);
                                     st.add(cn, GS_S_READS_BPS, (u64)L);
@@ -688,12 +697,22 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
             P.stat_recs[rbase + used] = rec;
         }
     }
-    if (lane == 0) {
+    if (FIXED) {
+        // one wave-uniform test for "no per-read output at all" (a resident batch that only wants the tables) in front of the lane-0
+        // region, both pointers fetched together, lane 0 as a literal mask
+        int32_t *const cv = P.class_vi;
+        uint8_t *const fl = P.flags;
+        if (((uintptr_t)cv | (uintptr_t)fl) != 0 && GS_ACT(1ULL)) {
+            if (cv) cv[r] = out_class;
+            if (fl) fl[r] = (uint8_t)out_flags;
+        }
+    } else if (lane == 0) {
         if (P.class_vi) P.class_vi[r] = out_class;
         if (P.flags) P.flags[r] = (uint8_t)out_flags;
     }
     if (!LONG) GS_STAMP(7, out_class)
 }
+#undef GS_LANE0
 
 // ---------------------------------------------------------------------------------------------------
 // kernels
@@ -885,7 +904,11 @@ __global__ __launch_bounds__(GS_BLOCK) __attribute__((amdgpu_waves_per_eu(GS_WAV
         constexpr bool FIXED = decltype(fixed)::value;
         const int64_t po_step = n_waves * P.off_stride;        // stride 1: running offsets; 2: (start, end) pairs
         const uint64_t *po = P.off + wave_id * P.off_stride;   // offsets of the current read
-        for (int64_t r = wave_id; r < n_reads; r += n_waves, po += po_step) {
+        // FIXED: the wave's trips are counted down on the scalar unit (gfx9 has no scalar 64-bit ordered compare: `r < n_reads` is two
+        // spill-lane reads, a vector compare and a branch on vcc per read).  A batch holds fewer than 2^32 reads (launch_batch)
+        uint32_t trips = 0;
+        if (FIXED && wave_id < n_reads) trips = (uint32_t)(n_reads - wave_id - 1) / (uint32_t)n_waves + 1u;
+        for (int64_t r = wave_id; FIXED ? trips != 0 : r < n_reads; r += n_waves, po += po_step, trips--) {
             GsKernargPtr kp = kp0;
 #ifndef GS_KERNARG_HOISTED  // (experiment, DESIGN 8.1 "kernarg re-reads": let the compiler keep the parameters live across the loop)
             asm volatile("" : "+s"(kp));

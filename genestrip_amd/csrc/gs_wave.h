@@ -82,6 +82,25 @@ __device__ __forceinline__ void gs_word_from_byte(uint32_t c, u64 &hi, u64 &lo, 
     lo = __ballot((((c ^ 4u) & 4u) | d) == 0u);
     bad = __ballot(d != 0u);
 }
+// The same for the FIXED loop of gs_match_kernel, without the forced zero: the planes of a byte that is not its letter are whatever
+// its bits 1 and 2 say (four vector instructions fewer per word).  A letter and the fill byte get the planes they get above: hi =
+// "x even" is bit 1 clear, lo is bit 2, and GS_FILL has bit 1 set and bit 2 clear.  Nobody can tell the planes of a bad byte b:
+//  - a window that holds b is INVALID by `bad` alone (gs_probe_planes: the funnel over Bbad), and the census counts `bad` alone;
+//  - ranks: the k-mer at position p reads the ranks of the 15-mers at p .. p + k - 15, whose bases are p .. p + k - 1, its own.  A
+//    15-mer that holds b is read by windows that hold b only, all of them INVALID.  A rank carries its row index in its low eight
+//    bits whatever the hash was, so the index a dead lane takes from a wrong minimum is still one of the row's 144;
+//  - the 15-mer read back (cf) is the one at the chosen index: inside a valid window's own bases, anything in a dead lane, where
+//    the gate key, the oriented planes and the record offset made from it are computed and never used: a dead lane reads gate word 0
+//    (the address select is by `act`), and the record loads, the table walk and every mark sit behind `act`;
+//  - the tail round (positions 128 .. 143) reads word 2 alone: its lanes beyond the read hold GS_FILL, planes 0 as before, and a
+//    bad byte there is again seen by windows that hold it only.
+__device__ __forceinline__ void gs_word_from_byte_fixed(uint32_t c, u64 &hi, u64 &lo, u64 &bad) {
+    const uint32_t x = (c >> 1) & 3u;
+    const uint32_t d = c ^ __builtin_amdgcn_perm(0u, 0x47544341u, x | 0x0c0c0c00u);
+    hi = __ballot((c & 2u) == 0u);
+    lo = __ballot((c & 4u) != 0u);
+    bad = __ballot(d != 0u);
+}
 
 // one 64-base word of a read -> ballot planes
 __device__ __forceinline__ void gs_load_word(const uint8_t *rd, int L, int w, int lane, u64 &hi, u64 &lo, u64 &bad) {
@@ -283,8 +302,11 @@ __device__ __forceinline__ void gs_lookup_rest(const GsDbDev &db, uint32_t bkt, 
 // A for positions 0 .. 143 (read by sub-rounds 0 and 1), B for positions 128 .. 64 NS + 15 with the index counted from 128 (read by
 // sub-rounds 2 and 3); the 16 positions both need are written twice.  Layout of the wave's words: [A: GS_ROW][B: GS_ROW, NS > 2 only]
 // [canonical 15-mers of all positions: 64 NS + 16].
+// LIT: the tail round's "lane < 16" as a literal mask (the FIXED loop of gs_match_kernel: a lane predicate costs a compare whose
+// result the compiler keeps across the loop in a spilled scalar pair and reads back per read)
 #define GS_WIDE_WORDS(NS) (2 * GS_ROW + 64 * (NS) + 32)
-template <int KC, int NS = 2>
+#define GS_ACT(m) __builtin_amdgcn_inverse_ballot_w64(m)  // a wave-level mask as a per-lane condition
+template <int KC, int NS = 2, bool LIT = false>
 __device__ __forceinline__ void gs_wave_minimizers(const u64 (&Bhi)[NS + 1], const u64 (&Blo)[NS + 1], const uint32_t (&fhi)[NS],
                                                    const uint32_t (&flo)[NS], const uint32_t (&rhi)[NS], const uint32_t (&rlo)[NS], int k,
                                                    int lane, uint32_t *wave_g, int (&p)[NS], uint32_t (&cf)[NS]) {
@@ -304,7 +326,7 @@ __device__ __forceinline__ void gs_wave_minimizers(const u64 (&Bhi)[NS + 1], con
         if (TWO && s == 2 && lane < 16) wave_g[128 + lane] = gs_lmer_rank(h, (uint32_t)(128 + lane));
         wave_g[CAN + 64 * s + lane] = c;
     }
-    if (lane < 16) {
+    if (LIT ? GS_ACT(0xffffULL) : lane < 16) {
         const uint32_t c = gs_lmer_canon((uint32_t)(Bhi[NS] >> lane) & 0x7fffu, (uint32_t)(Blo[NS] >> lane) & 0x7fffu);
         const uint32_t h = gs_canon_hash(c >> 1);
         if (!TWO)
@@ -339,7 +361,6 @@ __device__ __forceinline__ void gs_wave_minimizers(const u64 (&Bhi)[NS + 1], con
     __builtin_amdgcn_wave_barrier();  // the rows are rewritten by the next iteration / read
 }
 
-#define GS_ACT(m) __builtin_amdgcn_inverse_ballot_w64(m)  // a wave-level mask as a per-lane condition
 // the lanes below n as a wave-level mask: the positions of a sub-round that hold a k-mer, the lanes of a word that hold a base
 __device__ __forceinline__ u64 gs_low_mask(int n) { return n >= 64 ? ~0ULL : (n <= 0 ? 0ULL : ((1ULL << n) - 1ULL)); }
 // live: the positions of each sub-round that hold a k-mer, gs_low_mask(max - base - 64 s), from a caller that has them already -- they
@@ -352,7 +373,8 @@ __device__ __forceinline__ u64 gs_low_mask(int n) { return n >= 64 ? ~0ULL : (n 
 // read from the store -- one per first-seen k-mer; tools/huge_lines.py), with the fabric's line rate the bound (0.89).  The lanes of
 // a minimizer run OR their offset bits into a word of the wave's LDS rows (free again after the minimizer scan), the lane that owns
 // the lowest bit sends the word: ~13 atomics per read from the store instead of ~60.
-template <int KC, bool STRIPED, int CTX = 2, bool AGG = false, int NS = 2>
+// LIT: the caller is the FIXED loop -- lane predicates that are constants of the wave are written as literal masks
+template <int KC, bool STRIPED, int CTX = 2, bool AGG = false, int NS = 2, bool LIT = false>
 __device__ __forceinline__ void gs_probe_planes(const GsDbDev &db, const u64 (&Bhi)[NS + 1], const u64 (&Blo)[NS + 1],
                                                 const u64 (&Bbad)[NS + 1], int base, int max, int lane, int (&node)[NS],
                                                 uint32_t *wave_g, const GsMark &mk, const u64 *live = nullptr) {
@@ -395,7 +417,7 @@ __device__ __forceinline__ void gs_probe_planes(const GsDbDev &db, const u64 (&B
             rhi[s] = __brev(fhi[s]) >> (32 - k);
             rlo[s] = (__brev(flo[s]) >> (32 - k)) ^ kmask;
         }
-        gs_wave_minimizers<KC, NS>(Bhi, Blo, fhi, flo, rhi, rlo, k, lane, wave_g, mp, cf);
+        gs_wave_minimizers<KC, NS, LIT>(Bhi, Blo, fhi, flo, rhi, rlo, k, lane, wave_g, mp, cf);
         GS_STAMP(3, cf[0] ^ cf[1])
         uint32_t gh[NS], ohi[NS], olo[NS];
         int j[NS];
