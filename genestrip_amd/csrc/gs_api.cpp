@@ -77,6 +77,7 @@ extern "C" const char *gs_strerror(int code) {
     case GS_E_STATE: return "invalid call order";
     case GS_E_NODEVICE: return "no usable gfx950 device";
     case GS_E_IO: return "file input/output failed";
+    case GS_E_CANCELLED: return "cancelled";
     default: return "unknown error";
     }
 }

@@ -8,7 +8,200 @@
 #include "gs_krakenparse.h"
 #include "gs_genomeparse.h"
 
+#include "gs_control.h"
+
+#include <cstddef>
+#include <map>
+
 using namespace gs_host;
+
+// ---------------------------------------------------------------------------------------------------
+// progress and cancellation (include/gshost.h: gs_host_control_*)
+// ---------------------------------------------------------------------------------------------------
+static_assert(sizeof(gs_host_progress) == sizeof(gs_control::Record) && offsetof(gs_host_progress, file_reads) == offsetof(gs_control::Record, file_reads) &&
+                  offsetof(gs_host_progress, seconds_total) == offsetof(gs_control::Record, seconds_total),
+              "gs_host_progress and gs_control::Record are one layout");
+
+struct gs_host_control {
+    gs_host_progress_fn fn;
+    void *user;
+    gs_control::Control ctl;
+    static int call(void *self, const gs_control::Record *r) {
+        gs_host_control *h = static_cast<gs_host_control *>(self);
+        gs_host_progress p;
+        memcpy(&p, r, sizeof p);
+        return h->fn(h->user, &p);
+    }
+    gs_host_control(gs_host_progress_fn f, void *u, int32_t every_ms) : fn(f), user(u), ctl(f ? &gs_host_control::call : nullptr, this, every_ms) {}
+};
+
+namespace {
+
+// the live handles: a destroyed one is refused by address, and a call that runs with one keeps it alive until it returns
+std::mutex g_control_m;
+std::map<gs_host_control *, std::shared_ptr<gs_host_control>> &live_controls() {
+    static auto *m = new std::map<gs_host_control *, std::shared_ptr<gs_host_control>>();
+    return *m;
+}
+std::shared_ptr<gs_host_control> live_control(gs_host_control *c) {
+    std::lock_guard<std::mutex> l(g_control_m);
+    const auto it = live_controls().find(c);
+    return it == live_controls().end() ? nullptr : it->second;
+}
+// (weak: a handle that was destroyed is not mistaken for a later one at the same address)
+thread_local std::weak_ptr<gs_host_control> t_attached;
+
+inline int cancelled_rc() { return hfail(GS_E_CANCELLED, "cancelled"); }
+
+// What one file-level call reports: per file the bytes and reads (records, lines) so far.  Without a control attached to the calling
+// thread every method is one test of a pointer.  All of it runs on the calling thread.
+struct Tracker {
+    std::shared_ptr<gs_host_control> hold;
+    gs_control::Control *ctl = nullptr;
+    std::vector<int64_t> size, done, reads;
+    std::vector<double> t_file;
+    int files_done = 0;
+    double t0 = 0;
+    bool on() const { return ctl != nullptr; }
+    void begin(const char *const *paths, int n) {
+        if (n < 0 || !paths) return;
+        hold = t_attached.lock();
+        if (!hold || live_control(hold.get()) != hold) return;  // (none attached, or destroyed since)
+        ctl = &hold->ctl;
+        size.assign((size_t)n, 0);
+        done.assign((size_t)n, 0);
+        reads.assign((size_t)n, 0);
+        t_file.assign((size_t)n, 0);
+        for (int i = 0; i < n; i++) {
+            struct stat sb;
+            if (paths[i] && stat(paths[i], &sb) == 0) size[(size_t)i] = (int64_t)sb.st_size;
+        }
+        t0 = now_s();
+    }
+    gs_control::Record record(int f, bool file_done) const {
+        gs_control::Record r;
+        r.n_files = (int32_t)size.size();
+        r.files_done = files_done;
+        for (size_t i = 0; i < size.size(); i++) {
+            r.total_bytes_done += done[i];
+            r.total_bytes_total += size[i];
+            r.total_reads += reads[i];
+        }
+        const double now = now_s();
+        r.seconds_total = now - t0;
+        if (f >= 0 && (size_t)f < size.size()) {
+            r.file = f;
+            r.file_done = file_done ? 1 : 0;
+            r.file_bytes_done = done[(size_t)f];
+            r.file_bytes_total = size[(size_t)f];
+            r.file_reads = reads[(size_t)f];
+            r.seconds_file = now - t_file[(size_t)f];
+        }
+        return r;
+    }
+    bool cancelled() const { return ctl && ctl->cancelled(); }
+    // the first record of a file (the reference's start()); true: stop
+    bool file_start(int f) {
+        if (!ctl) return false;
+        t_file[(size_t)f] = now_s();
+        return ctl->publish(record(f, false), true);
+    }
+    // After a chunk or batch whose results are in the state: pos = where the loop stands in the file, in its text (gz: a gzip stream
+    // whose stored position nobody knows -- text / 4) or as stored; n = the reads of the file so far.  true: stop
+    bool chunk(int f, int64_t pos, bool gz, int64_t n) {
+        if (!ctl) return false;
+        const int64_t total = size[(size_t)f];
+        int64_t at = gz ? std::min(pos / 4, std::max<int64_t>(total - 1, 0)) : pos;
+        at = std::min(at, total);
+        done[(size_t)f] = std::max(done[(size_t)f], at);
+        reads[(size_t)f] = std::max(reads[(size_t)f], n);
+        return ctl->publish(record(f, false), false);
+    }
+    // the last record of a file; true: stop (everything of the file is in the state all the same).  ask = false: the call is being
+    // stopped already (another file read side by side saw the flag) -- the record goes out, its answer no longer matters
+    bool file_end(int f, int64_t n, bool ask = true) {
+        if (!ctl) return false;
+        done[(size_t)f] = size[(size_t)f];
+        reads[(size_t)f] = n;
+        files_done++;
+        return ctl->publish(record(f, true), true, ask);
+    }
+    // the closing record (allDone()): the totals once more, beside the last file's last record
+    bool close() {
+        if (!ctl) return false;
+        return ctl->publish(size.empty() ? record(-1, false) : record((int)size.size() - 1, true), true);
+    }
+    // the record of a stop: n = exactly the reads of file f that the state covers.  Called when nothing of the file is in flight any
+    // more and before its blocks, device text and decoders are released.
+    void stopped(int f, int64_t n) {
+        if (!ctl) return;
+        reads[(size_t)f] = n;
+        ctl->publish(record(f, false), true, false);
+    }
+};
+thread_local Tracker *t_tracker = nullptr;
+inline Tracker &trk() {
+    static Tracker none;  // (never begun: every method returns at its first test)
+    return t_tracker ? *t_tracker : none;
+}
+// the tracker of one file-level call, found by the loops of this thread through trk()
+struct TrackerScope {
+    Tracker t;
+    Tracker *prev;
+    TrackerScope(const char *const *paths, int n) : prev(t_tracker) {
+        t.begin(paths, n);
+        t_tracker = &t;
+    }
+    ~TrackerScope() { t_tracker = prev; }
+};
+
+}  // namespace
+
+extern "C" int gs_host_control_create(gs_host_control **out, gs_host_progress_fn fn, void *user, int32_t every_ms) try {
+    if (!out) return hfail(GS_E_INVALID, "NULL argument");
+    auto h = std::make_shared<gs_host_control>(fn, user, every_ms);
+    std::lock_guard<std::mutex> l(g_control_m);
+    live_controls()[h.get()] = h;
+    *out = h.get();
+    return GS_OK;
+} catch (const std::exception &) {
+    return hfail(GS_E_NOMEM, "out of host memory");
+}
+
+extern "C" int gs_host_control_destroy(gs_host_control *c) {
+    std::shared_ptr<gs_host_control> last;  // (dies outside the lock)
+    std::lock_guard<std::mutex> l(g_control_m);
+    const auto it = live_controls().find(c);
+    if (!c || it == live_controls().end()) return hfail(GS_E_INVALID, "not a live control handle");
+    last = it->second;
+    live_controls().erase(it);
+    return GS_OK;
+}
+
+extern "C" int gs_host_control_cancel(gs_host_control *c) {
+    const auto h = live_control(c);
+    if (!h) return hfail(GS_E_INVALID, "not a live control handle");
+    h->ctl.cancel();
+    return GS_OK;
+}
+
+extern "C" int gs_host_control_snapshot(gs_host_control *c, gs_host_progress *out, int32_t *cancelled) {
+    const auto h = live_control(c);
+    if (!h || !out) return hfail(GS_E_INVALID, h ? "NULL argument" : "not a live control handle");
+    gs_control::Record r;
+    bool stop = false;
+    h->ctl.snapshot(&r, &stop);
+    memcpy(out, &r, sizeof r);
+    if (cancelled) *cancelled = stop ? 1 : 0;
+    return GS_OK;
+}
+
+extern "C" int gs_host_control_attach(gs_host_control *c) {
+    const auto h = c ? live_control(c) : nullptr;
+    if (c && !h) return hfail(GS_E_INVALID, "not a live control handle");
+    t_attached = h;
+    return GS_OK;
+}
 
 namespace {
 
@@ -197,6 +390,7 @@ struct Producer {
     int64_t reads = 0, kmers = 0, bps = 0;
     double seconds = 0;
     std::string error;
+    std::atomic<bool> stop{false};  // a stop on request: no further batch is parsed (the consumer drains what is queued)
     // path from byte `offset` on, or the memory range [mem, mem + mem_n) when path is empty
     void start(const std::string &path, int64_t offset, const uint8_t *mem, size_t mem_n, int k, int64_t batch_reads, bool mem_fasta = false) {
         th = std::thread([this, path, offset, mem, mem_n, k, batch_reads, mem_fasta] {
@@ -209,12 +403,13 @@ struct Producer {
             if (!ok_open) {
                 error = "cannot open " + path;
             } else {
-                for (;;) {
+                while (!stop.load()) {
                     auto b = std::make_unique<Batch>();
                     const double t0 = now_s();
                     const bool ok = parser.parse(*b, batch_reads, (int64_t)1 << 30);
                     seconds += now_s() - t0;
                     if (!ok) break;
+                    b->src_pos = parser.raw_pos();
                     q.push(std::move(b));
                 }
                 reads = parser.reads_;  // totalReads += reads (AbstractLoggingFastqStreamer.java:123-125)
@@ -489,6 +684,9 @@ struct MatchCtx {
     DeviceWriter filtered_dev;  // the filtered file fed from the device (TextJob::emit_device)
     DeviceWriter kraken_dev;    // the Kraken-style lines made on the device (gs_match_kraken_text), a deflater of its own
     bool taxids_on_device = false;  // gs_match_set_taxids has been called for this run
+    // progress records of the general parser (parsed_source): the file it works for, and the number of that file's first read
+    int prog_file = 0;
+    int64_t prog_base = 0;
     // CountsPerTaxid.maxContigDescriptor for a host that never sees the reads (opts->max_contig_desc): after every chunk the device
     // names the read that holds each tax id's longest contig (gs_match_max_contig_reads); a holder that lies in the chunk just
     // submitted gets its name fetched while the chunk's text is at hand.  A maximum only moves to a later read by beating it, so
@@ -672,13 +870,38 @@ int parsed_source(MatchCtx &c, const std::string &path, int64_t offset, const ui
     Producer prod;
     prod.start(path, offset, mem, mem_n, c.info.k, c.opts->batch_reads > 0 ? c.opts->batch_reads : (int64_t)1 << 20, mem_fasta);
     int err = GS_OK;
+    Tracker &tk = trk();
+    int64_t seen[3] = {0, 0, 0};  // reads, k-mers, bases of the batches that went through (what counts after a stop)
+    bool stopped = false;
     for (;;) {
         std::unique_ptr<Batch> b = prod.q.pop();
         if (!b) break;
         if (err) continue;  // keep draining so the producer can finish
         err = consume_batch(c, *b, read_no);
+        if (!err && tk.on()) {
+            for (int64_t i = 0; i < b->n(); i++) {
+                const int64_t L = (int64_t)(b->seq_off[(size_t)i + 1] - b->seq_off[(size_t)i]);
+                seen[1] += L >= c.info.k ? L - c.info.k + 1 : 0;
+                seen[2] += L;
+            }
+            seen[0] += b->n();
+            if (tk.chunk(c.prog_file, path.empty() ? 0 : b->src_pos, false, read_no - c.prog_base)) {
+                prod.stop.store(true);  // (what it has parsed beyond this batch is dropped, above)
+                stopped = true;
+                err = GS_E_CANCELLED;
+            }
+        }
     }
     prod.th.join();
+    if (stopped) {  // every batch was waited for (consume_batch); the run holds exactly the reads in front of read_no
+        c.reads += seen[0];
+        c.kmers += seen[1];
+        c.bps += seen[2];
+        c.t_parse += prod.seconds;
+        gs_match_sync(c.run);
+        tk.stopped(c.prog_file, read_no - c.prog_base);
+        return cancelled_rc();
+    }
     if (!err && !prod.error.empty()) err = hfail(GS_E_INVALID, prod.error);
     c.reads += prod.reads;
     c.kmers += prod.kmers;
@@ -1104,8 +1327,12 @@ struct TextJob {
     int64_t gz_ticket_ = -1;             // whole stream: ... out of the batch's text
     PooledBuf dev_text_[2];              // the text of a chunk on the host, for the per-read writers
 
-    TextJob(MatchCtx &ctx, const std::string &p, int bank_, int64_t first_read_no, bool fasta_ = false)
-        : c(ctx), path(p), bank(bank_), read_no(first_read_no), fasta(fasta_) {}
+    int file_idx = 0;       // progress records: the file's index in the call, and the number of its first read
+    int64_t file_base = 0;
+    bool stopped_on_request = false;  // this job (or the pass that re-read its file, or its parser) stopped and published the record of that
+
+    TextJob(MatchCtx &ctx, const std::string &p, int bank_, int64_t first_read_no, bool fasta_ = false, int file_idx_ = 0)
+        : c(ctx), path(p), bank(bank_), read_no(first_read_no), fasta(fasta_), file_idx(file_idx_), file_base(first_read_no) {}
     ~TextJob() { abort(); }
     // stops the readers (after the writers of the last chunk are through with its block)
     void abort() {
@@ -1352,8 +1579,69 @@ struct TextJob {
         return 1;
     }
 
-    // 1: a block was handled, 0: none ready (blocking = false only); `done` is set when the file is through
+    // 1: a block was handled, 0: none ready (blocking = false only); `done` is set when the file is through.  With a control attached
+    // to the thread every block that leaves the file unfinished ends with a progress record and a look at the cancel flag.
     int step(bool blocking, int *err_out) {
+        const int r = step_block(blocking, err_out);
+        if (r > 0 && *err_out == GS_E_CANCELLED) stopped_on_request = true;  // (the file's end stopped: its parser, or the pass that re-read it)
+        if (r > 0 && !*err_out && !done && trk().on()) {
+            int64_t pos = cut_.file_off;
+            bool text_pos = gz_;
+            if (dev_.bgzf()) {  // (the members say where they lie in the file)
+                const BgzfFeeds &fd = dev_.feeds;
+                pos = fd.next_member < fd.members.size() ? fd.members[fd.next_member].payload_offset : (int64_t)tr.map_len;
+                text_pos = false;
+            }
+            if (trk().chunk(file_idx, pos, text_pos, read_no - file_base + reads_in_file)) *err_out = stop_on_request();
+        }
+        return r;
+    }
+
+    // A stop on request: nothing more is submitted.  The writers of the last chunk finish, the copies out of the held block and out of
+    // device text complete, every chunk of the run completes (gs_match_sync) and is counted -- a chunk the device refused, and those
+    // behind it, never reached the state: the file's prefix ends in front of it.  The record of the stop is published, and only then
+    // do the blocks go back to their readers, the readers stop and the device decoders return to their pools.
+    int stop_on_request() {
+        done = true;
+        stopped_on_request = true;
+        drain();
+        int err = dev_err_;
+        auto keep = [&err](int e) {
+            if (!err) err = e;
+        };
+        if (held_ticket >= 0) keep(gs_match_text_wait_copy(c.run, held_ticket));
+        for (int q = 0; q < 2; q++)
+            if (dev_tickets_[q] >= 0) {
+                keep(gs_match_text_wait_copy(c.run, dev_tickets_[q]));
+                dev_tickets_[q] = -1;
+            }
+        if (gz_ticket_ >= 0) keep(gs_match_text_wait_copy(c.run, gz_ticket_));
+        gz_ticket_ = -1;
+        keep(gs_match_sync(c.run));
+        keep(gs_match_text_select(c.run, bank));
+        int64_t fallback_off = -1, fallback_reads = 0;
+        if (!err) err = check_refusal(&fallback_off, &fallback_reads);  // also fetches the totals
+        if (!err && fallback_off >= 0) {
+            int64_t failed = -1, bad = -1;
+            err = gs_match_text_status(c.run, &failed, &bad, tot);  // (read after the refusal: exactly the accepted chunks)
+            reads_in_file = fallback_reads;
+        }
+        if (!err) {
+            c.reads += tot[0] - base_tot[0];
+            c.kmers += tot[1] - base_tot[1];
+            c.bps += tot[2] - base_tot[2];
+            read_no += reads_in_file;
+            trk().stopped(file_idx, read_no - file_base);
+        }
+        release_held();
+        release_gunzipper();
+        tr.close();
+        dev_.close();
+        c.t_parse += now_s() - t0;
+        return err ? err : cancelled_rc();
+    }
+
+    int step_block(bool blocking, int *err_out) {
         if (dev_.bgzf()) return step_bgzf(err_out);
         if (dev_.whole()) return step_gunzip(err_out);
         const int64_t i = next_block;
@@ -1655,8 +1943,11 @@ private:
             // device (GS_HOST_ML=0: straight to the reference-exact parser, which also takes over whatever that pass refuses)
             bool ml = fallback_off == 0 && fallback_reads == 0 && !fasta && !general;
             if (const char *e = getenv("GS_HOST_ML")) ml = ml && atoi(e) != 0;
+            c.prog_file = file_idx;
+            c.prog_base = file_base;
             if (ml) {
-                TextJob g(c, path, bank, read_no, false);
+                TextJob g(c, path, bank, read_no, false, file_idx);
+                g.file_base = file_base;
                 g.general = true;
                 int gerr = g.open(gz_, readers_);
                 while (!gerr && !g.done) g.step(true, &gerr);
@@ -1667,6 +1958,8 @@ private:
             return parsed_source(c, path, fallback_off, nullptr, 0, read_no);
         }
         read_no += reads_in_file;
+        c.prog_file = file_idx;
+        c.prog_base = file_base;
         // what is left after the last whole four-line group (no final newline, truncated record): the general parser
         if (!cut_.carry.empty()) return parsed_source(c, std::string(), 0, cut_.carry.data(), cut_.carry.size(), read_no, fasta);
         return GS_OK;
@@ -1705,20 +1998,31 @@ int run_files(MatchCtx &c, const char *const *paths, int n_paths, const int32_t 
     side_by_side = side_by_side && allow_side_by_side;
     if (file_index) side_by_side = true;  // read numbers are (file << 32 | read): the files are independent anyway
     std::vector<int64_t> reads_of_file((size_t)n_paths, 0);
+    Tracker &tk = trk();
     if (!side_by_side) {
         int64_t read_no = 0;
         for (int i = 0; i < n_paths && !err; i++) {
             const std::string path(paths[i]);
+            const int64_t first_no = read_no;
+            if (tk.file_start(i)) {
+                tk.stopped(i, 0);
+                err = cancelled_rc();
+                break;
+            }
             if (kind[(size_t)i]) {
                 const bool gz = kind[(size_t)i] == 2 || kind[(size_t)i] == 4;
-                TextJob job(c, path, 0, read_no, kind[(size_t)i] >= 3);
+                TextJob job(c, path, 0, read_no, kind[(size_t)i] >= 3, i);
                 err = job.open(gz, gz ? gzip_threads : default_readers);
                 while (!err && !job.done) job.step(true, &err);
                 if (!job.done) job.abort();
                 read_no = job.read_no;
             } else {
+                c.prog_file = i;
+                c.prog_base = read_no;
                 err = parsed_source(c, path, 0, nullptr, 0, read_no);
             }
+            reads_of_file[(size_t)i] = read_no - first_no;
+            if (!err && tk.file_end(i, read_no - first_no)) err = cancelled_rc();
         }
     } else {
         std::vector<std::unique_ptr<TextJob>> active;
@@ -1727,6 +2031,11 @@ int run_files(MatchCtx &c, const char *const *paths, int n_paths, const int32_t 
         while (!err && (next < n_paths || !active.empty())) {
             while (!err && next < n_paths && (int)active.size() < 8) {
                 const int64_t base = (int64_t)(file_index ? file_index[next] : next) << 32;
+                if (tk.file_start(next)) {
+                    tk.stopped(next, 0);
+                    err = cancelled_rc();
+                    break;
+                }
                 if (kind[(size_t)next]) {
                     int bank = 0;  // a free bank
                     for (;; bank++) {
@@ -1734,14 +2043,17 @@ int run_files(MatchCtx &c, const char *const *paths, int n_paths, const int32_t 
                         for (auto &j : active) used = used || j->bank == bank;
                         if (!used) break;
                     }
-                    auto job = std::make_unique<TextJob>(c, std::string(paths[next]), bank, base, kind[(size_t)next] >= 3);
+                    auto job = std::make_unique<TextJob>(c, std::string(paths[next]), bank, base, kind[(size_t)next] >= 3, next);
                     err = job->open(kind[(size_t)next] == 2 || kind[(size_t)next] == 4, std::max(2, 2 * default_readers / std::min(n_paths, 8)));
                     active.push_back(std::move(job));
                     file_of.push_back(next);
                 } else {  // FASTA etc.: the general parser, on its own
                     int64_t read_no = base;
+                    c.prog_file = next;
+                    c.prog_base = base;
                     err = parsed_source(c, std::string(paths[next]), 0, nullptr, 0, read_no);
                     reads_of_file[(size_t)next] = read_no - base;
+                    if (!err && tk.file_end(next, read_no - base)) err = cancelled_rc();
                 }
                 next++;
             }
@@ -1752,6 +2064,11 @@ int run_files(MatchCtx &c, const char *const *paths, int n_paths, const int32_t 
                     reads_of_file[(size_t)file_of[j]] = active[j]->read_no - ((int64_t)(file_index ? file_index[file_of[j]] : file_of[j]) << 32);
                     if (reads_of_file[(size_t)file_of[j]] >= ((int64_t)1 << 32) && !err)
                         err = hfail(GS_E_UNSUPPORTED, "more than 2^32 reads in one of several files read side by side (set GS_HOST_PARALLEL_FILES=0)");
+                    if (!err && tk.file_end(file_of[j], reads_of_file[(size_t)file_of[j]])) err = cancelled_rc();
+                    // a file that went through its last block in the sweep in which another file saw the flag: all of it is in
+                    // the state, and the records say so (a job that stopped itself has published the record of its stop)
+                    else if (err == GS_E_CANCELLED && !active[j]->stopped_on_request)
+                        tk.file_end(file_of[j], reads_of_file[(size_t)file_of[j]], false);
                     active.erase(active.begin() + (long)j);
                     file_of.erase(file_of.begin() + (long)j);
                 } else
@@ -1759,8 +2076,17 @@ int run_files(MatchCtx &c, const char *const *paths, int n_paths, const int32_t 
             }
             if (!progressed && !active.empty()) std::this_thread::sleep_for(std::chrono::microseconds(50));
         }
-        for (auto &j : active) j->abort();
+        // a stop on request: the files that were still being read stop the same way, each with the record of its own prefix
+        for (size_t j = 0; j < active.size(); j++) {
+            if (err == GS_E_CANCELLED && !active[j]->done) {
+                const int e = active[j]->stop_on_request();
+                if (e != GS_E_CANCELLED) err = e;
+                reads_of_file[(size_t)file_of[j]] = active[j]->read_no - active[j]->file_base;
+            }
+            active[j]->abort();
+        }
     }
+    if (!err && tk.close()) err = cancelled_rc();
     reads_of_file_out = reads_of_file;
     *composite = side_by_side;
     return err;
@@ -1798,7 +2124,10 @@ extern "C" int gs_host_match_files(gs_db *db, const gs_match_cfg *cfg, const cha
     const double t_start = now_s();
     std::vector<int64_t> reads_of_file;
     bool side_by_side = false;
+    TrackerScope progress(paths, n_paths);
     int err = run_files(c, paths, n_paths, nullptr, reads_of_file, &side_by_side);
+    const bool stopped = err == GS_E_CANCELLED;  // a stop on request: the table over the reads of the last records, then the code
+    if (stopped) err = GS_OK;
     const double t_files = now_s();
     if (!err) err = gs_match_finish(c.run, table, dtable);
     const double t_fin = now_s();
@@ -1827,7 +2156,7 @@ extern "C" int gs_host_match_files(gs_db *db, const gs_match_cfg *cfg, const cha
         totals->seconds_parse = c.t_parse;
         totals->seconds_gpu = c.t_gpu;
     }
-    return err;
+    return !err && stopped ? cancelled_rc() : err;
 } catch (const std::bad_alloc &) {
     return hfail(GS_E_NOMEM, "out of host memory");
 } catch (const std::exception &e) {  // (nothing may leave through the C ABI)
@@ -1860,7 +2189,10 @@ extern "C" int gs_host_match_run(gs_run *run, gs_db *db, const char *const *path
     const double t_start = now_s();
     std::vector<int64_t> reads_of_file;
     bool composite = false;
+    TrackerScope progress(paths, n_paths);
     int err = run_files(c, paths, n_paths, nullptr, reads_of_file, &composite, false);  // (one file after the other: running read numbers)
+    const bool stopped = err == GS_E_CANCELLED;  // a stop on request: the outputs are closed as after a whole run, then the code
+    if (stopped) err = GS_OK;
     if (!err) err = gs_match_sync(run);
     const bool wrote = c.filtered.close() & c.kraken.close();
     if (!err) err = c.filtered_dev.late_err;
@@ -1875,7 +2207,7 @@ extern "C" int gs_host_match_run(gs_run *run, gs_db *db, const char *const *path
         totals->seconds_parse = c.t_parse;
         totals->seconds_gpu = c.t_gpu;
     }
-    return err;
+    return !err && stopped ? cancelled_rc() : err;
 } catch (const std::bad_alloc &) {
     return hfail(GS_E_NOMEM, "out of host memory");
 } catch (const std::exception &e) {  // (nothing may leave through the C ABI)
@@ -1974,6 +2306,7 @@ extern "C" int gs_host_match_into(gs_run *run, gs_db *db, const char *const *pat
     const double t_start = now_s();
     std::vector<int64_t> rof;
     bool composite = false;
+    TrackerScope progress(paths, n_paths);
     const int err = run_files(c, paths, n_paths, file_index, rof, &composite);
     for (int i = 0; i < n_paths && (size_t)i < rof.size(); i++) reads_of_file[i] = rof[(size_t)i];
     if (totals) {
@@ -2047,6 +2380,17 @@ struct FilterCtx {
     OutFile acc_out, rest_out;
     std::vector<uint8_t> accept;
     int64_t accepted = 0, reads = 0, kmers = 0, bps = 0;
+    // progress records: the file being read and `reads` when it began; tot0 = reads of the file's accepted text chunks so far
+    int prog_file = 0;
+    int64_t prog_reads0 = 0;
+    int64_t file_reads(int64_t tot0) const { return reads - prog_reads0 + tot0; }
+    // a stop on request, when nothing of the file is in flight any more: the chunks the device took are counted, the record goes out
+    void stop_record(const int64_t tot[3]) {
+        reads += tot[0];
+        kmers += tot[1];
+        bps += tot[2];
+        trk().stopped(prog_file, reads - prog_reads0);
+    }
     double t_gpu = 0, t_parse = 0;
     FormatPool pool{format_threads()};
     DeviceWriter acc_dev, rest_dev;  // (declared behind the files: they wait for their writes before the files close)
@@ -2071,11 +2415,23 @@ void write_filter_parts(FilterCtx &c, std::vector<FilterPart> &parts) {
     }
 }
 
+// reads per batch of the reference-exact parser in the filter / extract goal (GS_HOST_BATCH_READS; the match goal: batch_reads)
+inline int64_t parser_batch_reads() {
+    if (const char *e = getenv("GS_HOST_BATCH_READS")) {
+        const long long v = atoll(e);
+        if (v >= 1) return (int64_t)v;
+    }
+    return (int64_t)1 << 20;
+}
+
 // the general path for one source (file from `offset`, or a memory range): reference parser -> batches -> GPU -> writers
 int filter_parsed_source(FilterCtx &c, const std::string &path, int64_t offset, const uint8_t *mem, size_t mem_n, bool mem_fasta = false) {
     Producer prod;
-    prod.start(path, offset, mem, mem_n, c.k, (int64_t)1 << 20, mem_fasta);
+    prod.start(path, offset, mem, mem_n, c.k, parser_batch_reads(), mem_fasta);
     int err = GS_OK;
+    Tracker &tk = trk();
+    int64_t seen[3] = {0, 0, 0};  // reads, k-mers, bases of the batches that went through (what counts after a stop)
+    bool stopped = false;
     for (;;) {
         std::unique_ptr<Batch> b = prod.q.pop();
         if (!b) break;
@@ -2103,8 +2459,26 @@ int filter_parsed_source(FilterCtx &c, const std::string &path, int64_t offset, 
             p.pack(c.acc_out, c.rest_out);
         });
         write_filter_parts(c, parts);
+        if (tk.on()) {
+            for (int64_t i = 0; i < n; i++) {
+                const int64_t L = (int64_t)(bb.seq_off[(size_t)i + 1] - bb.seq_off[(size_t)i]);
+                seen[1] += L >= c.k ? L - c.k + 1 : 0;
+                seen[2] += L;
+            }
+            seen[0] += n;
+            if (tk.chunk(c.prog_file, path.empty() ? 0 : bb.src_pos, false, c.file_reads(seen[0]))) {
+                prod.stop.store(true);  // (what it has parsed beyond this batch is dropped, above)
+                stopped = true;
+                err = GS_E_CANCELLED;
+            }
+        }
     }
     prod.th.join();
+    if (stopped) {
+        c.t_parse += prod.seconds;
+        c.stop_record(seen);
+        return cancelled_rc();
+    }
     if (!err && !prod.error.empty()) err = hfail(GS_E_INVALID, prod.error);
     c.reads += prod.reads;
     c.kmers += prod.kmers;
@@ -2228,6 +2602,7 @@ int filter_bgzf_file(FilterCtx &c, const std::string &path, bool *handled) {
     c.rest_dev.begin(&c.rest_out, device);
     int64_t n_formatted = 0, text_off = 0, fallback_off = -1;
     int64_t tot[3] = {0, 0, 0}, failed = -1, bad = -1;
+    bool stopped = false;  // a stop on request: the record goes out when the writers are through, before the decoder is handed back
     std::vector<uint8_t> carry;
     const double t0 = now_s();
     // (feeds of 128 MiB here, not 512: the writers get their first chunk four times earlier, and what they have not written when
@@ -2278,6 +2653,11 @@ int filter_bgzf_file(FilterCtx &c, const std::string &path, bool *handled) {
                 filter_emit_host(c, h_text, h_acc, h_nl, n_reads, formatting, nullptr);
             n_formatted++;
             text_off += t.n_bytes;
+            const bool members = dev.bgzf() && dev.feeds.next_member < dev.feeds.members.size();  // (they say where they lie in the file)
+            if (trk().chunk(c.prog_file, members ? dev.feeds.members[dev.feeds.next_member].payload_offset : text_off, !members, c.file_reads(tot[0]))) {
+                stopped = true;
+                break;
+            }
         }
         if (t.last) {  // what is left behind the last whole record
             err = dev.whole() ? dev.slices.fetch_leftover(carry) : dev.feeds.fetch_tail(carry);
@@ -2291,12 +2671,14 @@ int filter_bgzf_file(FilterCtx &c, const std::string &path, bool *handled) {
         if (!err) err = e2;
     }
     const double te1 = now_s();
+    if (stopped && !err) c.stop_record(tot);
     dev.close();  // (every slice's filter run has been waited for: gs_filter_text_status)
     tr.close();
     if (trace)
         fprintf(stderr, "filter bgzf: loop %.2f ms (from open), last writers %.2f, inflater back + unmap %.2f\n", (te0 - t0) * 1e3, (te1 - te0) * 1e3, (now_s() - te1) * 1e3);
     c.t_parse += now_s() - t0;
     if (err) return err;
+    if (stopped) return cancelled_rc();
     return filter_file_end(c, path, true, tot, fallback_off, carry, true, false);
 }
 
@@ -2327,6 +2709,7 @@ int filter_text_file(FilterCtx &c, const std::string &path, bool gzip) {
     int64_t n_formatted = 0, fallback_off = -1;
     ChunkCutter cut;
     int64_t tot[3] = {0, 0, 0}, failed = -1, bad = -1;
+    bool stopped = false;  // a stop on request: the record goes out when the writers are through, before the readers are stopped
     const double t0 = now_s();
     if (!err) tr.start();
     for (int64_t i = 0; !err; i++) {
@@ -2362,6 +2745,8 @@ int filter_text_file(FilterCtx &c, const std::string &path, bool gzip) {
                     filter_emit_host(c, start, h_acc, h_nl, n_reads, formatting, [&tr, i] { tr.release(i); });
                 }
                 n_formatted++;
+                stopped = trk().chunk(c.prog_file, cut.file_off, gzip, c.file_reads(tot[0]));
+                if (stopped) break;  // (a block that nobody formats from stays where it is until the readers are stopped)
             }
         }
         if (!keep_block) tr.release(i);
@@ -2372,9 +2757,11 @@ int filter_text_file(FilterCtx &c, const std::string &path, bool gzip) {
         const int e2 = dev_job.get();
         if (!err) err = e2;
     }
+    if (stopped && !err) c.stop_record(tot);
     tr.close();
     c.t_parse += now_s() - t0;
     if (err) return err;
+    if (stopped) return cancelled_rc();
     return filter_file_end(c, path, gzip, tot, fallback_off, cut.carry, true, false);
 }
 
@@ -2415,6 +2802,7 @@ int filter_general_file(FilterCtx &c, const std::string &path, bool gzip, bool f
     ChunkCutter cut;
     cut.mode = fasta ? ChunkCutter::FASTA : ChunkCutter::GENERAL;
     int64_t tot[3] = {0, 0, 0}, failed = -1, bad = -1;
+    bool stopped = false;  // a stop on request: the record goes out when the writers are through, before the readers are stopped
     const double t0 = now_s();
     if (!err) tr.start();
     for (int64_t i = 0; !err; i++) {
@@ -2506,9 +2894,12 @@ int filter_general_file(FilterCtx &c, const std::string &path, bool gzip, bool f
                     format_job();
                     tr.release(i);
                 });
-                if (eof || fallback_off >= 0) break;
+                stopped = trk().chunk(c.prog_file, cut.file_off, gzip, c.file_reads(tot[0]));
+                if (eof || fallback_off >= 0 || stopped) break;
                 continue;
             }
+            stopped = fallback_off < 0 && trk().chunk(c.prog_file, cut.file_off, gzip, c.file_reads(tot[0]));
+            if (stopped) break;  // (the block stays where it is until the readers are stopped)
         }
         tr.release(i);
         if (eof || fallback_off >= 0) break;
@@ -2518,9 +2909,11 @@ int filter_general_file(FilterCtx &c, const std::string &path, bool gzip, bool f
         const int e2 = dev_job.get();
         if (!err) err = e2;
     }
+    if (stopped && !err) c.stop_record(tot);
     tr.close();
     c.t_parse += now_s() - t0;
     if (err) return err;
+    if (stopped) return cancelled_rc();
     return filter_file_end(c, path, gzip, tot, fallback_off, cut.carry, false, fasta);
 }
 
@@ -2553,7 +2946,16 @@ int filter_files(FilterCtx &c, const char *const *paths, int n_paths, int extrac
     bool fast = true;
     if (const char *e = getenv("GS_HOST_FAST")) fast = atoi(e) != 0;
     int err = GS_OK;
+    TrackerScope progress(paths, n_paths);
+    Tracker &tk = progress.t;
     for (int f = 0; f < n_paths && !err; f++) {
+        c.prog_file = f;
+        c.prog_reads0 = c.reads;
+        if (tk.file_start(f)) {
+            tk.stopped(f, 0);
+            err = cancelled_rc();
+            break;
+        }
         if (fast && extract_device >= 0 && !c.rd && gs_reads_create(&c.rd, extract_device) != GS_OK) {
             err = hfail(GS_E_HIP, gs_last_error());
             break;
@@ -2570,7 +2972,11 @@ int filter_files(FilterCtx &c, const char *const *paths, int n_paths, int extrac
         }
         else
             err = filter_parsed_source(c, path, 0, nullptr, 0);
+        if (!err && tk.file_end(f, c.reads - c.prog_reads0)) err = cancelled_rc();
     }
+    if (!err && tk.close()) err = cancelled_rc();
+    const bool stopped = err == GS_E_CANCELLED;  // a stop on request: the outputs are closed as after a whole run, then the code
+    if (stopped) err = GS_OK;
     const double tc0 = now_s();
     const bool wrote = c.acc_out.close() & c.rest_out.close();
     if (!err) err = c.acc_dev.late_err ? c.acc_dev.late_err : c.rest_dev.late_err;
@@ -2594,7 +3000,7 @@ int filter_files(FilterCtx &c, const char *const *paths, int n_paths, int extrac
         totals->seconds_parse = c.t_parse;
         totals->seconds_gpu = c.t_gpu;
     }
-    return err;
+    return !err && stopped ? cancelled_rc() : err;
 }
 }  // namespace
 
@@ -2731,6 +3137,8 @@ struct F2fCtx {
     int device = 0;
     OutFile out;
     int64_t records = 0;
+    int prog_file = 0;           // progress records: the file being read, `records` when it began, `records` at the last record
+    int64_t prog_records0 = 0, prog_mark = 0;
     double t_read = 0, t_dev = 0, t_emit = 0, t_cpu = 0;  // waiting for blocks (read, inflate); device calls; handing text to the writer; f2f_cpu
     DeviceWriter dev;  // (declared behind the file: it waits for its writes before the file closes)
 };
@@ -2763,6 +3171,20 @@ int f2f_cpu(F2fCtx &c, const std::string &path, int64_t offset, const uint8_t *m
     std::vector<uint8_t> line, o = c.out.take();
     bool first = true;
     int64_t data_size = 0;
+    Tracker &tk = trk();
+    const int64_t step = parser_batch_reads();  // records per progress record (GS_HOST_BATCH_READS)
+    // between two records: what has been printed goes to the writer, a progress record goes out; true: stop
+    // (the buffer goes to the writer where it would without a control -- when it is full, at the end of the source -- or when the
+    // call stops: a .gz output is packed buffer by buffer, and a control that is not cancelled must not move a member boundary)
+    auto report = [&](bool last) {
+        c.prog_mark = c.records;
+        if (last) c.out.write(std::move(o));
+        if (!tk.chunk(c.prog_file, path.empty() ? 0 : lr.raw_pos(), false, c.records - c.prog_records0)) return false;
+        if (!last) c.out.write(std::move(o));
+        tk.stopped(c.prog_file, c.records - c.prog_records0);
+        c.t_cpu += now_s() - t_begin;
+        return true;
+    };
     auto end_region = [&] {
         o.push_back('\n');
         o.push_back('+');
@@ -2777,6 +3199,7 @@ int f2f_cpu(F2fCtx &c, const std::string &path, int64_t offset, const uint8_t *m
         if (size >= 65534) return hfail(GS_E_INVALID, "buffer is too small for data line in fasta file " + path);  // (a target of 65 535 bytes, :104-106)
         if (line[0] == '>') {
             if (!first) end_region();
+            if (tk.on() && !first && c.records - c.prog_mark >= step && report(false)) return cancelled_rc();
             first = false;
             data_size = 0;
             c.records++;
@@ -2795,6 +3218,7 @@ int f2f_cpu(F2fCtx &c, const std::string &path, int64_t offset, const uint8_t *m
         }
     }
     if (!first) end_region();
+    if (tk.on()) return report(true) ? cancelled_rc() : (c.t_cpu += now_s() - t_begin, (int)GS_OK);
     c.out.write(std::move(o));
     c.t_cpu += now_s() - t_begin;
     return GS_OK;
@@ -2824,6 +3248,7 @@ int f2f_device_file(F2fCtx &c, const std::string &path, bool gzip) {
     ChunkCutter cut;
     cut.mode = ChunkCutter::FASTA;
     int64_t fallback_off = -1, n_chunks = 0;
+    bool stopped = false;  // a stop on request: the record goes out before the readers are stopped
     if (!err) tr.start();
     for (int64_t i = 0; !err; i++) {
         const double tw = now_s();
@@ -2862,13 +3287,20 @@ int f2f_device_file(F2fCtx &c, const std::string &path, bool gzip) {
                     c.records += records;
                 }
             }
-            if (fallback_off < 0) cut.commit();
+            if (fallback_off < 0) {
+                cut.commit();
+                c.prog_mark = c.records;
+                stopped = trk().chunk(c.prog_file, cut.file_off, gzip, c.records - c.prog_records0);
+                if (stopped) break;  // (every chunk's text has left the device for the writer: DeviceWriter::emit)
+            }
         }
         tr.release(i);
         if (eof || fallback_off >= 0) break;
     }
+    if (stopped && !err) trk().stopped(c.prog_file, c.records - c.prog_records0);
     tr.close();
     if (err) return err;
+    if (stopped) return cancelled_rc();
     if (fallback_off >= 0) {
         if (gs_reads_text_reset(c.reads, 1) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
         return f2f_cpu(c, path, fallback_off, nullptr, 0);
@@ -2885,7 +3317,9 @@ extern "C" int gs_host_fasta2fastq(int device, const char *const *paths, int n_p
     if (const char *e = getenv("GS_HOST_FAST")) fast = atoi(e) != 0;
     int err = GS_OK;
     int64_t records = 0;
-    bool wrote = true;
+    bool wrote = true, stopped = false;
+    TrackerScope progress(paths, n_paths);
+    Tracker &tk = progress.t;
     {
         F2fCtx c;
         ReadsGuard guard{c.reads};
@@ -2898,9 +3332,20 @@ extern "C" int gs_host_fasta2fastq(int device, const char *const *paths, int n_p
         const double t_start = now_s();
         for (int f = 0; f < n_paths && !err; f++) {  // (all resources into ONE file, Fasta2FastqGoal.java:96-102)
             const std::string path(paths[f]);
+            c.prog_file = f;
+            c.prog_records0 = c.prog_mark = c.records;
+            if (tk.file_start(f)) {
+                tk.stopped(f, 0);
+                err = cancelled_rc();
+                break;
+            }
             const int kind = fast ? text_path_kind(path) : 0;
             err = kind ? f2f_device_file(c, path, kind == 2 || kind == 4) : f2f_cpu(c, path, 0, nullptr, 0);
+            if (!err && tk.file_end(f, c.records - c.prog_records0)) err = cancelled_rc();
         }
+        if (!err && tk.close()) err = cancelled_rc();
+        stopped = err == GS_E_CANCELLED;  // a stop on request: the output is closed as after a whole run, then the code
+        if (stopped) err = GS_OK;
         const double tc0 = now_s();
         const int e2 = c.dev.finish();
         if (!err) err = e2;
@@ -2918,7 +3363,7 @@ extern "C" int gs_host_fasta2fastq(int device, const char *const *paths, int n_p
     }
     if (!err && !wrote) err = hfail(GS_E_IO, std::string("writing ") + out_path + " failed");
     if (n_records) *n_records = records;
-    return err;
+    return !err && stopped ? cancelled_rc() : err;
 } catch (const std::bad_alloc &) {
     return hfail(GS_E_NOMEM, "out of host memory");
 } catch (const std::exception &e) {
@@ -2941,6 +3386,15 @@ struct KcCtx {
     KrakenExact exact;  // rows of what the line-by-line loop took; its lines / tokens
     int64_t dev_tot[4] = {0, 0, 0, 0};
     int64_t device_chunks = 0, host_chunks = 0;
+    int prog_file = 0;  // progress records: the file being read, and the lines counted when it began
+    int64_t prog_lines0 = 0;
+    int64_t file_lines() const { return exact.lines + dev_tot[0] - prog_lines0; }
+    // after a chunk; true: stop -- the chunk has been waited for (gs_krakencount_chunk) or was counted here, the record is out
+    bool report(int64_t pos, bool gz) {
+        if (!trk().chunk(prog_file, pos, gz, file_lines())) return false;
+        trk().stopped(prog_file, file_lines());
+        return true;
+    }
 };
 
 int kc_format_error(const KcCtx &c, const std::string &path) {
@@ -2950,7 +3404,10 @@ int kc_format_error(const KcCtx &c, const std::string &path) {
 // the rest of a stream, line by line: the file from `offset` on, or a memory range that ends the stream
 int kc_cpu(KcCtx &c, const std::string &path, int64_t offset, const uint8_t *mem, size_t mem_n) {
     c.host_chunks++;
-    if (mem) return c.exact.feed(mem, mem_n, true) ? (int)GS_OK : kc_format_error(c, path);
+    if (mem) {
+        if (!c.exact.feed(mem, mem_n, true)) return kc_format_error(c, path);
+        return c.report(0, false) ? cancelled_rc() : (int)GS_OK;
+    }
     LineReader lr;
     if (!lr.open(path, offset)) return hfail(GS_E_IO, "cannot open " + path);
     std::vector<uint8_t> text;
@@ -2965,6 +3422,7 @@ int kc_cpu(KcCtx &c, const std::string &path, int64_t offset, const uint8_t *mem
         // (next_line drops NUL bytes as the parser would; a final line without its newline is the stream's last)
         if (!text.empty() && text.back() != '\n') eof = true;
         if (!c.exact.feed(text.data(), text.size(), eof)) return kc_format_error(c, path);
+        if (c.report(lr.raw_pos(), false)) return cancelled_rc();
     }
     return GS_OK;
 }
@@ -3017,6 +3475,7 @@ int kc_device_file(KcCtx &c, const std::string &path, bool gzip) {
                 }
             }
             cut.commit();
+            if (!err && c.report(cut.file_off, gzip)) err = cancelled_rc();  // (the record is out: the block may go back)
         } else if (what == ChunkCutter::CHUNK) {
             cut.commit();
         }
@@ -3047,15 +3506,31 @@ extern "C" int gs_host_kraken_count_files(int device, const char *const *paths, 
     c.exact.filtered = n_only > 0;
     if (fast && gs_krakencount_create(&c.kc, device, max_taxids) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
     std::map<std::string, KrakenRow> rows;
-    for (int f = 0; f < n_paths; f++) {
+    TrackerScope progress(paths, n_paths);
+    Tracker &tk = progress.t;
+    bool stopped = false;  // a stop on request: the rows of the lines counted so far are fetched all the same, no CSV is written
+    for (int f = 0; f < n_paths && !stopped; f++) {
         const std::string path(paths[f]);
         c.exact.ended = false;  // every file is a stream of its own, all of them count into one table
         c.exact.line_no = 0;
         c.exact.forget_class();
+        c.prog_file = f;
+        c.prog_lines0 = c.exact.lines + c.dev_tot[0];
+        if (tk.file_start(f)) {
+            tk.stopped(f, 0);
+            stopped = true;
+            break;
+        }
         const int kind = fast ? text_path_kind(path) : 0;
         const int err = kind ? kc_device_file(c, path, kind == 2 || kind == 4) : kc_cpu(c, path, 0, nullptr, 0);
+        if (err == GS_E_CANCELLED) {
+            stopped = true;
+            break;
+        }
         if (err) return err;
+        stopped = tk.file_end(f, c.file_lines());
     }
+    if (!stopped) stopped = tk.close();
     rows = c.exact.rows;
     if (c.kc) {
         int64_t n = 0;
@@ -3093,7 +3568,7 @@ extern "C" int gs_host_kraken_count_files(int device, const char *const *paths, 
     std::vector<char> k2;
     std::vector<int64_t> c2;
     const int32_t stride = (int32_t)longest + 1;
-    if (csv_path) {
+    if (csv_path && !stopped) {
         k2.assign(rows.size() * (size_t)stride + 1, 0);
         c2.reserve(3 * rows.size() + 3);
         size_t i = 0;
@@ -3117,7 +3592,7 @@ extern "C" int gs_host_kraken_count_files(int device, const char *const *paths, 
         counts[3 * i + 2] = kv.second.kimr;
         i++;
     }
-    return GS_OK;
+    return stopped ? cancelled_rc() : (int)GS_OK;
 } catch (const std::bad_alloc &) {
     return hfail(GS_E_NOMEM, "out of host memory");
 } catch (const std::exception &e) {
@@ -3147,6 +3622,12 @@ struct GnCtx {
     std::vector<uint64_t> hoff, koff;
     std::vector<int32_t> vi, kvi;
     GenomeRecords rec;
+    // after a chunk whose regions the sink has taken; true: stop -- nothing is in flight (the sink has returned), the record is out
+    bool report(int64_t pos, bool gz) {
+        if (!trk().chunk(file, pos, gz, first_record)) return false;
+        trk().stopped(file, first_record);
+        return true;
+    }
 };
 
 // the caller's decision for the n records of a chunk -> keep[n], kvi (vi of the kept ones); a callback's own code comes back as it is
@@ -3240,6 +3721,7 @@ int gn_host_stream(GnCtx &c, const std::string &path, int64_t offset) {
             size_t used = 0;
             const int rc = gn_host_chunk(c, text.data(), n, true, &used);
             if (rc) return rc;
+            if (c.report(lr.raw_pos(), false)) return cancelled_rc();
             text.erase(text.begin(), text.begin() + (long)n);
         }
         want = text.size() + ((size_t)4 << 20);
@@ -3279,13 +3761,16 @@ int gn_device_pass(GnCtx &c, const std::string &path, bool gzip, size_t block, i
         } else if (what == ChunkCutter::CHUNK) {
             err = chunk_from(cut.start, cut.bytes, base + cut.file_off);
             if (!err) cut.commit();
+            if (!err && c.report(base + cut.file_off, gzip)) err = cancelled_rc();  // (the record is out: the block may go back)
         }
         tr.release(i);
         if (eof || *fallback_off >= 0) break;
     }
     tr.close();
     if (err || *fallback_off >= 0) return err;
-    return chunk_from(cut.carry.data(), (int64_t)cut.carry.size(), base + cut.file_off);
+    err = chunk_from(cut.carry.data(), (int64_t)cut.carry.size(), base + cut.file_off);
+    if (!err && !cut.carry.empty() && c.report(base + cut.file_off, gzip)) err = cancelled_rc();
+    return err;
 }
 
 // One file through the device.  A record longer than a block: the file goes on from that record with blocks twice as large, up to
@@ -3329,13 +3814,22 @@ extern "C" int gs_host_genome_files(const char *const *paths, int n_paths, int d
     c.sink_user = sink_user;
     if (fast && gs_genomes_create(&c.g, device) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
     int err = GS_OK;
+    TrackerScope progress(paths, n_paths);
+    Tracker &tk = progress.t;
     for (int f = 0; f < n_paths && !err; f++) {
         const std::string path(paths[f]);
         c.file = f;
         c.first_record = 0;
+        if (tk.file_start(f)) {
+            tk.stopped(f, 0);
+            err = cancelled_rc();
+            break;
+        }
         const int kind = fast ? text_path_kind(path) : 0;
         err = kind ? gn_device_file(c, path, kind == 2 || kind == 4) : gn_host_stream(c, path, 0);
+        if (!err && tk.file_end(f, c.first_record)) err = cancelled_rc();
     }
+    if (!err && tk.close()) err = cancelled_rc();
     c.tot.seconds_total = now_s() - t_start;
     if (totals) *totals = c.tot;
     return err;

@@ -83,6 +83,8 @@ public:
         if (gz_) gzclose(gz_);
     }
     // appends the next line (incl. '\n', NULs dropped) to out; returns the number of bytes appended (0 at EOF)
+    // how far the underlying file has been read, in its stored bytes (a memory range: 0) -- ahead of the lines by the buffers
+    int64_t raw_pos() const { return gz_ ? (int64_t)gzoffset(gz_) : 0; }
     size_t next_line(std::vector<uint8_t> &out) {
         const size_t start = out.size();
         for (;;) {
@@ -123,6 +125,7 @@ struct Batch {
     std::vector<uint8_t> seq, desc, qual;
     std::vector<uint64_t> seq_off{0}, desc_off{0}, qual_off{0};
     int64_t first_read_no = 0;
+    int64_t src_pos = 0;   // stored bytes of the source read when the batch was complete (Producer; progress records)
     bool has_qual = true;  // false for FASTA records (readProbsSize = -1, AbstractFastqReader.java:417)
     int64_t n() const { return (int64_t)seq_off.size() - 1; }
     void clear() {
@@ -142,6 +145,7 @@ public:
     FastqParser(int k, bool fasta) : k_(k), fasta_(fasta) {}
     bool open(const std::string &path, int64_t offset = 0) { return lr_.open(path, offset); }
     void open_mem(const uint8_t *p, size_t n) { lr_.open_mem(p, n); }
+    int64_t raw_pos() const { return lr_.raw_pos(); }
 
     // appends up to max_reads records / max_bytes sequence bytes to b; returns false at end of file
     bool parse(Batch &b, int64_t max_reads, int64_t max_bytes) {

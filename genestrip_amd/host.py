@@ -2,6 +2,7 @@
 the reference's record semantics, the runMatcher / runFilter file pipelines and the CSV report."""
 import ctypes as C
 import os
+import threading
 
 import numpy as np
 
@@ -65,6 +66,9 @@ def lib():
         "gs_host_last_error": (C.c_char_p, []), "gs_host_java_double": (ci, [C.c_double, vp, ci]),
         "gs_host_gunzip": (ci, [vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]),
         "gs_host_gunzip_parallel": (ci, [vp, C.c_size_t, vp, C.c_size_t, vp, ci, C.c_size_t, C.c_size_t]),
+        "gs_host_control_create": (ci, [vp, vp, vp, C.c_int32]), "gs_host_control_destroy": (ci, [vp]),
+        "gs_host_control_cancel": (ci, [vp]), "gs_host_control_snapshot": (ci, [vp, vp, vp]),
+        "gs_host_control_attach": (ci, [vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -73,12 +77,115 @@ def lib():
     return L
 
 
-def _check(rc):
+def _check(rc, **partial):
+    """raises for a non-zero status; GS_E_CANCELLED (-8) as Cancelled, carrying `partial` -- what the wrapper would have returned"""
+    if rc == CANCELLED:
+        raise Cancelled(**partial)
     if rc != 0:
         msg = (lib().gs_host_last_error() or b"").decode(errors="replace")
         if not msg:
             msg = (_b.lib().gs_last_error() or b"").decode(errors="replace")
         raise _b.GsError(rc, msg)
+
+
+CANCELLED = -8  # GS_E_CANCELLED
+
+
+class Cancelled(_b.GsError):
+    """a file-level call was stopped on request (Control): the partial results the wrapper would have returned -- table, dtable,
+    totals, ... -- are attributes; they cover exactly the reads of the last progress records"""
+
+    def __init__(self, **partial):
+        super().__init__(CANCELLED, "cancelled")
+        self.partial = partial
+        for name, value in partial.items():
+            setattr(self, name, value)
+
+
+class Progress(C.Structure):
+    """gs_host_progress"""
+    _fields_ = [("file", C.c_int32), ("n_files", C.c_int32), ("file_done", C.c_int32), ("files_done", C.c_int32),
+                ("file_bytes_done", C.c_int64), ("file_bytes_total", C.c_int64), ("file_reads", C.c_int64),
+                ("total_bytes_done", C.c_int64), ("total_bytes_total", C.c_int64), ("total_reads", C.c_int64),
+                ("seconds_file", C.c_double), ("seconds_total", C.c_double)]
+
+    def copy(self):
+        r = Progress()
+        C.memmove(C.byref(r), C.byref(self), C.sizeof(Progress))
+        return r
+
+    def __repr__(self):
+        return "Progress(" + ", ".join(f"{f}={getattr(self, f)}" for f, _ in self._fields_) + ")"
+
+
+_PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(Progress))
+_THREAD = threading.local()
+
+
+def _attached():
+    """the Controls this thread has entered, innermost last"""
+    if not hasattr(_THREAD, "stack"):
+        _THREAD.stack = []
+    return _THREAD.stack
+
+
+class Control:
+    """Progress and cancellation of the file-level calls (match_files, match_run, match_files_into, filter_files, extract_files,
+    fasta2fastq, kraken_count_files, genome_files) that THIS thread makes inside the `with` block:
+
+        with host.Control(callback=lambda p: p.total_reads > 10**9, every_ms=200) as ctl:
+            table, dtable, tot = host.match_files(store, paths)
+
+    callback(record) runs on the calling thread with a Progress (a copy: keep it if you like); a true return value stops the call,
+    .cancel() does the same from any thread, .snapshot() -> (Progress, cancelled) reads the latest record from any thread.  A
+    stopped call raises Cancelled, which carries the partial results.  An exception raised by the callback stops the call and is
+    raised again when the block is left."""
+
+    def __init__(self, callback=None, every_ms=0):
+        self.callback, self.every_ms = callback, int(every_ms)
+        self.h = None
+        self._raised = None
+        self._fn = _PROGRESS_FN(self._call) if callback is not None else None
+
+    def _call(self, _user, p):
+        try:
+            return 1 if self.callback(p.contents.copy()) else 0
+        except BaseException as e:  # noqa: BLE001 -- nothing may leave through the C frames
+            self._raised = e
+            return 1
+
+    def __enter__(self):
+        h = C.c_void_p()
+        _check(lib().gs_host_control_create(C.byref(h), C.cast(self._fn, C.c_void_p) if self._fn else None, None, self.every_ms))
+        rc = lib().gs_host_control_attach(h)
+        if rc != 0:
+            lib().gs_host_control_destroy(h)
+            _check(rc)
+        self.h = h
+        stack = _attached()
+        stack.append(self)
+        return self
+
+    def __exit__(self, etype, exc, tb):
+        stack = _attached()
+        if self in stack:
+            stack.remove(self)
+        outer = stack[-1].h if stack else None  # (a Control inside another: the outer one is this thread's again)
+        lib().gs_host_control_attach(outer)
+        h, self.h = self.h, None
+        _check(lib().gs_host_control_destroy(h))
+        if self._raised is not None and (etype is None or issubclass(etype, Cancelled)):
+            raised, self._raised = self._raised, None
+            raise raised
+        return False
+
+    def cancel(self):
+        _check(lib().gs_host_control_cancel(self.h))
+
+    def snapshot(self):
+        p, flag = Progress(), C.c_int32(0)
+        _check(lib().gs_host_control_snapshot(self.h, C.byref(p), C.byref(flag)))
+        return p, bool(flag.value)
 
 
 def _cstr_array(items):
@@ -153,10 +260,25 @@ def match_files(store, paths, config=None, filtered_path=None, kraken_out_path=N
     dtable = np.zeros((nv, _b.N_DCOLS), dtype=np.float64)
     tot = Totals()
     _check(lib().gs_host_match_files(store.h, C.byref(cfg), parr, len(paths), C.byref(opts),
-                                     table.ctypes.data_as(C.c_void_p), dtable.ctypes.data_as(C.c_void_p), C.byref(tot)))
+                                     table.ctypes.data_as(C.c_void_p), dtable.ctypes.data_as(C.c_void_p), C.byref(tot)),
+           table=table, dtable=dtable, totals=tot)
     if descs is not None:
         return table, dtable, tot, [bytes(row).split(b"\0", 1)[0] for row in descs]
     return table, dtable, tot
+
+
+def match_run(matcher, paths, filtered_path=None, kraken_out_path=None, write_all=True, taxids=None, batch_reads=0,
+              with_probs=False):
+    """gs_host_match_run: the files into `matcher`'s own run (no finish: matcher.finish() gives the table, matcher.reset() clears
+    it), per-read outputs included, one file after the other with running read numbers; -> Totals"""
+    parr = _cstr_array(list(paths))
+    tarr = _cstr_array(taxids)
+    opts = _MatchOpts(None if filtered_path is None else str(filtered_path).encode(),
+                      None if kraken_out_path is None else str(kraken_out_path).encode(), int(write_all),
+                      tarr, batch_reads, int(with_probs), None, 0)
+    tot = Totals()
+    _check(lib().gs_host_match_run(matcher.h, matcher.store.h, parr, len(paths), C.byref(opts), C.byref(tot)), totals=tot)
+    return tot
 
 
 def stat(which=0):
@@ -189,7 +311,7 @@ def match_files_into(matcher, paths, file_index):
     counts = np.zeros(max(len(fi), 1), dtype=np.int64)
     tot = Totals()
     _check(lib().gs_host_match_into(matcher.h, matcher.store.h, parr, len(fi), fi.ctypes.data_as(C.c_void_p),
-                                    counts.ctypes.data_as(C.c_void_p), C.byref(tot)))
+                                    counts.ctypes.data_as(C.c_void_p), C.byref(tot)), reads_of_file=counts[:len(fi)], totals=tot)
     return counts[:len(fi)], tot
 
 
@@ -200,7 +322,7 @@ def filter_files(bloom, k, paths, min_pos_count=1, positive_ratio=0.2, filtered_
     _check(lib().gs_host_filter_files(bloom.h, k, min_pos_count, positive_ratio, parr, len(paths),
                                       None if filtered_path is None else str(filtered_path).encode(),
                                       None if rest_path is None else str(rest_path).encode(), int(with_probs),
-                                      C.byref(tot)))
+                                      C.byref(tot)), totals=tot)
     return tot
 
 
@@ -210,7 +332,7 @@ def extract_files(key, paths, out_path, k=31, device=0):
     parr = _cstr_array(list(paths))
     tot = Totals()
     _check(lib().gs_host_extract_files(int(device), key if isinstance(key, bytes) else str(key).encode(), int(k), parr, len(paths),
-                                       str(out_path).encode(), C.byref(tot)))
+                                       str(out_path).encode(), C.byref(tot)), totals=tot)
     return tot
 
 
@@ -218,7 +340,8 @@ def fasta2fastq(paths, out_path, device=0):
     """the fasta2fastq goal: the FASTA files, in order, as one four-line FASTQ file with '~' qualities (.gz: BGZF); -> records"""
     parr = _cstr_array(list(paths))
     n = C.c_int64(0)
-    _check(lib().gs_host_fasta2fastq(int(device), parr, len(paths), str(out_path).encode(), C.byref(n)))
+    rc = lib().gs_host_fasta2fastq(int(device), parr, len(paths), str(out_path).encode(), C.byref(n))
+    _check(rc, records=n.value)
     return n.value
 
 
@@ -321,10 +444,13 @@ def kraken_count_files(paths, only=None, csv=None, device=0):
         if rc != 0 and n.value > 0 and (n.value > cap or stride < 4096) and b"no room" in (lib().gs_host_last_error() or b""):
             cap, stride = max(cap, n.value), (stride if n.value > cap else stride * 16)  # (more rows than guessed, or very long keys)
             continue
-        _check(rc)
+        if rc != CANCELLED:
+            _check(rc)
         break
     rows = [(bytes(keys[i]).split(b"\0", 1)[0], int(cnt[i, 0]), int(cnt[i, 1]), int(cnt[i, 2])) for i in range(n.value)]
-    return rows, {f: getattr(tot, f) for f, _ in KrakenTotals._fields_}
+    totals = {f: getattr(tot, f) for f, _ in KrakenTotals._fields_}
+    _check(rc, rows=rows, totals=totals)
+    return rows, totals
 
 
 def write_kraken_csv(path, rows):
@@ -354,7 +480,7 @@ def genome_files(paths, resolve, sink, device=0):
     or a non-zero int as its error code; sink(seq, offsets, vi) gets the kept regions -- seq / offsets as device views or numpy
     arrays, in both cases what DeviceDbBuilder.add, DeviceDbSizer.add, DeviceDbUpdater.add and DeviceDbQuality.add take, valid
     until it returns -- and may return a non-zero int as well.  Such a code ends the walk and comes back as GsError(code); use
-    POSITIVE codes: -1 .. -7 are the library's own GS_E_* codes and are reported with the library's last message.  An exception
+    POSITIVE codes: -1 .. -8 are the library's own GS_E_* codes and are reported with the library's last message.  An exception
     raised inside a callback ends the walk and is raised again.  -> GenomeTotals"""
     raised = []
 
@@ -397,7 +523,7 @@ def genome_files(paths, resolve, sink, device=0):
     rc = lib().gs_host_genome_files(arr, n, device, r_fn, None, s_fn, None, C.byref(t))
     if raised:
         raise raised[0]
-    if rc > 0 or rc < -7:
+    if rc > 0 or rc < CANCELLED:
         raise _b.GsError(rc, "a callback of genome_files ended the walk with this code")
-    _check(rc)
+    _check(rc, totals=t)
     return t

@@ -39,7 +39,8 @@ enum {
     GS_E_UNSUPPORTED = -4,
     GS_E_STATE = -5,     /* call order violated                            */
     GS_E_NODEVICE = -6,  /* no usable gfx950 device                        */
-    GS_E_IO = -7         /* reading or writing a file failed (host layer)  */
+    GS_E_IO = -7,        /* reading or writing a file failed (host layer)  */
+    GS_E_CANCELLED = -8  /* a file-level call was stopped on request (gs_host_control, include/gshost.h) */
 };
 
 enum { GS_MEM_HOST = 0, GS_MEM_DEVICE = 1, GS_MEM_DEVICE_TEXT = 2 /* gs_match_submit_text / gs_filter_submit_text: the text in HBM, the per-read results to host memory */ };

@@ -17,6 +17,8 @@
  *   gs_host_write_quality_csv  the dbquality goal's CSV (DBQualityCountsGoal's rank aggregation + DBQualityCSVGoal.makeFile)
  *   gs_host_genome_files  genome FASTA files -> the regions of a build (the walk of AbstractFastaReader.readFasta under the
  *                         store readers), records found and bases gathered on the device, the selection left to a callback
+ *   gs_host_control_*     progress records and cancellation of the file-level calls above (ExecutionContext.setFastqProgress /
+ *                         setTotalProgress, FastqReaderInterruptedException), through a control attached to the calling thread
  * (C/ = core/src/main/java/org/metagene/genestrip/, B/ = base/src/main/java/org/metagene/genestrip/)
  */
 #ifndef GSHOST_H
@@ -224,6 +226,52 @@ typedef struct {
 } gs_host_genome_totals;
 int gs_host_genome_files(const char *const *paths, int n_paths, int device, gs_genome_resolve_fn resolve, void *resolve_user,
                          gs_genome_sink_fn sink, void *sink_user, gs_host_genome_totals *totals);
+
+/* ---- progress and cancellation of the file-level calls (what the reference does through ExecutionContext.setFastqProgress /
+ * setTotalProgress, C/fastq/AbstractLoggingFastqStreamer.java:161-209,247-252, and FastqReaderInterruptedException).
+ * A control is attached to a THREAD (gs_host_control_attach); the file-level calls that thread makes afterwards -- gs_host_match_files,
+ * _match_run, _match_into, _filter_files, _extract_files, _fasta2fastq, _kraken_count_files, _genome_files -- publish records to it and
+ * look at its cancel flag after every chunk.  Their signatures are unchanged, and a thread without a control behaves as before.
+ * Records: one at the start of each file (file_bytes_done = 0), one after every chunk or batch whose results are in the handle's
+ * state, a last one per file (file_done = 1, file_bytes_done == file_bytes_total) and a closing one (files_done == n_files).  Files
+ * read side by side interleave their records; `file` says whose a record is.  The match goal without per-read outputs keeps up to two
+ * chunks on the device and looks for a refusal (text that is not what it was submitted as) only now and then: its chunk records count
+ * the chunks SUBMITTED.  Should the device refuse one later, the chunk and those behind it are parsed again on the host and the count
+ * stands still meanwhile; the record of a stop is exact all the same and may then report fewer reads than a record before it.
+ * file_bytes_done counts bytes of the file as stored and
+ * never decreases; for block-gzip input inflated on the device it is the offset of the next member, for other gzip streams -- whose
+ * decoders run ahead of the loop on threads of their own -- an estimate (text / 4, kept below the file's size until the file is
+ * through).  The callback runs on the calling thread, inside the call, never concurrently with itself; every_ms > 0 drops calls that
+ * come sooner than that after the last, but never a file's first or last record, the closing record or the record of a stop.  The
+ * snapshot follows every record.
+ * A stop (the callback returned non-zero, or gs_host_control_cancel from any thread): nothing more is submitted, what is on the device
+ * completes, writer / reader / inflating threads are joined, one more record gives the final counts (none behind a file's last record
+ * or the closing one, when the stop was the answer to that: it holds them already) -- published before any
+ * page-locked block, device text or pooled decoder is released -- and the call returns GS_E_CANCELLED with its totals filled.  The
+ * state covers exactly the reads of that record, per file a prefix of the file's reads under the numbers they would have had; output
+ * files are closed and hold exactly those reads' output (a .gz output ends at a member boundary, with its end-of-file block).
+ * gs_host_match_run / _into leave the run usable (gs_match_finish: the table over those reads; gs_match_reset clears it);
+ * gs_host_match_files runs its finish and fills table / dtable, gs_host_kraken_count_files fetches its rows (no CSV is written), the
+ * sink of gs_host_genome_files has seen exactly the records reported.
+ * Out of scope: gs_host_match_files_multi (its replicas run on threads of their own) and gs_host_db2fastq ignore an attached control;
+ * the JNI shim's direct buffers are not bounds-checked (the stand-in jni.h has no GetDirectBufferCapacity). ---- */
+typedef struct {
+    int32_t file, n_files;        /* index of the file this record is about, and how many the call has      */
+    int32_t file_done;            /* 1: the last record of this file                                          */
+    int32_t files_done;           /* files completed so far                                                   */
+    int64_t file_bytes_done, file_bytes_total;   /* bytes of the file as stored (compressed, if it is)        */
+    int64_t file_reads;           /* reads (records, lines: the unit of the goal) of this file in the state   */
+    int64_t total_bytes_done, total_bytes_total, total_reads;
+    double  seconds_file, seconds_total;
+} gs_host_progress;
+typedef int (*gs_host_progress_fn)(void *user, const gs_host_progress *p);   /* non-zero: cancel */
+typedef struct gs_host_control gs_host_control;
+/* fn may be NULL (snapshots and the flag only).  A NULL or destroyed handle: GS_E_INVALID from every call below. */
+int gs_host_control_create(gs_host_control **out, gs_host_progress_fn fn, void *user, int32_t every_ms);
+int gs_host_control_destroy(gs_host_control *c);   /* a call that runs with it keeps it alive until it returns */
+int gs_host_control_cancel(gs_host_control *c);                              /* any thread                    */
+int gs_host_control_snapshot(gs_host_control *c, gs_host_progress *out, int32_t *cancelled);  /* any thread */
+int gs_host_control_attach(gs_host_control *c);   /* this thread's file-level calls use c until detached; NULL detaches */
 
 /* The host layer keeps page-locked blocks and the device decoders of gzip input (gigabytes of HBM) from call to call; this hands
  * them back (a long-lived JVM host before it loads a big store).  No other thread may be inside the host layer meanwhile. */

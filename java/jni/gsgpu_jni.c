@@ -457,7 +457,12 @@ JNIEXPORT void JNICALL JNAME(filterSubmit)(JNIEnv *env, jclass c, jlong b, jint 
 static void throw_host(JNIEnv *env, int rc) {
     char msg[640];
     const char *h = gs_host_last_error();
-    snprintf(msg, sizeof(msg), "gsgpu error %d (%s): %s", rc, gs_strerror(rc), (h && h[0]) ? h : gs_last_error());
+    /* a call stopped on request (GS_E_CANCELLED): the message starts with "cancelled" -- the reference's FastqReaderInterruptedException
+     * has no constructor that takes a message, which ThrowNew needs; the Java callers turn this one into it */
+    if (rc == GS_E_CANCELLED)
+        snprintf(msg, sizeof(msg), "cancelled: gsgpu status %d", rc);
+    else
+        snprintf(msg, sizeof(msg), "gsgpu error %d (%s): %s", rc, gs_strerror(rc), (h && h[0]) ? h : gs_last_error());
     (*env)->ThrowNew(env, (*env)->FindClass(env, "java/lang/RuntimeException"), msg);
 }
 
@@ -530,10 +535,8 @@ JNIEXPORT void JNICALL JNAME(hostMatchFiles)(JNIEnv *env, jclass c, jlong db, jb
     if (kr) (*env)->ReleaseStringUTFChars(env, krakenOutPath, kr);
     free_strings(env, &p);
     free_strings(env, &tax);
-    if (rc)
-        throw_host(env, rc);
-    else
-        put_totals(env, totals, &t);
+    if (!rc || rc == GS_E_CANCELLED) put_totals(env, totals, &t);  /* (a stopped call has filled them: in front of the throw) */
+    if (rc) throw_host(env, rc);
 }
 
 /* gs_host_match_run: the same into the matcher's own run (matchReset before, matchFinish after) */
@@ -556,10 +559,8 @@ JNIEXPORT void JNICALL JNAME(hostMatchRun)(JNIEnv *env, jclass c, jlong run, jlo
     if (kr) (*env)->ReleaseStringUTFChars(env, krakenOutPath, kr);
     free_strings(env, &p);
     free_strings(env, &tax);
-    if (rc)
-        throw_host(env, rc);
-    else
-        put_totals(env, totals, &t);
+    if (!rc || rc == GS_E_CANCELLED) put_totals(env, totals, &t);  /* (a stopped call has filled them: in front of the throw) */
+    if (rc) throw_host(env, rc);
 }
 
 /* gs_host_match_into: some of the files of a sample into a run that is merged with others (matchMerge) before matchFinish */
@@ -574,12 +575,11 @@ JNIEXPORT void JNICALL JNAME(hostMatchInto)(JNIEnv *env, jclass c, jlong run, jl
     if (!rc && (!idx || !rof || (*env)->GetArrayLength(env, fileIndex) < p.n || (*env)->GetArrayLength(env, readsOfFile) < p.n)) rc = GS_E_INVALID;
     if (!rc) rc = gs_host_match_into((gs_run *)(intptr_t)run, (gs_db *)(intptr_t)db, p.c, (int)p.n, (const int32_t *)idx, (int64_t *)rof, &t);
     if (idx) (*env)->ReleaseIntArrayElements(env, fileIndex, idx, JNI_ABORT);
-    if (rof) (*env)->ReleaseLongArrayElements(env, readsOfFile, rof, rc ? JNI_ABORT : 0);
+    /* (a stopped call has filled the per-file prefixes: the caller needs them to convert the max-contig read numbers) */
+    if (rof) (*env)->ReleaseLongArrayElements(env, readsOfFile, rof, rc && rc != GS_E_CANCELLED ? JNI_ABORT : 0);
     free_strings(env, &p);
-    if (rc)
-        throw_host(env, rc);
-    else
-        put_totals(env, totals, &t);
+    if (!rc || rc == GS_E_CANCELLED) put_totals(env, totals, &t);  /* (a stopped call has filled them: in front of the throw) */
+    if (rc) throw_host(env, rc);
 }
 
 /* gs_host_filter_files: one call = one runFilter over local files */
@@ -595,10 +595,8 @@ JNIEXPORT void JNICALL JNAME(hostFilterFiles)(JNIEnv *env, jclass c, jlong bloom
     if (flt) (*env)->ReleaseStringUTFChars(env, filteredPath, flt);
     if (rest) (*env)->ReleaseStringUTFChars(env, restPath, rest);
     free_strings(env, &p);
-    if (rc)
-        throw_host(env, rc);
-    else
-        put_totals(env, totals, &t);
+    if (!rc || rc == GS_E_CANCELLED) put_totals(env, totals, &t);  /* (a stopped call has filled them: in front of the throw) */
+    if (rc) throw_host(env, rc);
 }
 
 /* gs_host_extract_files: the extract goal over local files (ExtractGoal.doMakeThis with writeFilteredFastq); totals[3] = reads written */
@@ -614,10 +612,8 @@ JNIEXPORT void JNICALL JNAME(hostExtractFiles)(JNIEnv *env, jclass c, jint devic
     if (ky) (*env)->ReleaseStringUTFChars(env, key, ky);
     if (out) (*env)->ReleaseStringUTFChars(env, outPath, out);
     free_strings(env, &p);
-    if (rc)
-        throw_host(env, rc);
-    else
-        put_totals(env, totals, &t);
+    if (!rc || rc == GS_E_CANCELLED) put_totals(env, totals, &t);  /* (a stopped call has filled them: in front of the throw) */
+    if (rc) throw_host(env, rc);
 }
 
 /* gs_host_fasta2fastq: Fasta2FastqGoal.makeFile over local files; returns the records written */
@@ -635,6 +631,48 @@ JNIEXPORT jlong JNICALL JNAME(hostFasta2Fastq)(JNIEnv *env, jclass c, jint devic
 
 /* gs_host_last_error */
 JNIEXPORT jstring JNICALL JNAME(hostLastError)(JNIEnv *env, jclass c) { return (*env)->NewStringUTF(env, gs_host_last_error()); }
+
+/* ---- progress and cancellation (include/gshost.h, gs_host_control_*).  The stand-in jni.h of the test-suite has no method-call
+ * functions, so nothing calls back into Java: the handle is made without a callback, a Java thread polls hostControlSnapshot and
+ * calls hostControlCancel.  hostControlAttach is per thread: the thread that attaches makes the file-level call. ---- */
+JNIEXPORT jlong JNICALL JNAME(hostControlCreate)(JNIEnv *env, jclass c) {
+    gs_host_control *h = NULL;
+    int rc = gs_host_control_create(&h, NULL, NULL, 0);
+    if (rc) throw_host(env, rc);
+    return (jlong)(intptr_t)h;
+}
+
+JNIEXPORT void JNICALL JNAME(hostControlDestroy)(JNIEnv *env, jclass c, jlong control) {
+    int rc = gs_host_control_destroy((gs_host_control *)(intptr_t)control);
+    if (rc) throw_host(env, rc);
+}
+
+JNIEXPORT void JNICALL JNAME(hostControlCancel)(JNIEnv *env, jclass c, jlong control) {
+    int rc = gs_host_control_cancel((gs_host_control *)(intptr_t)control);
+    if (rc) throw_host(env, rc);
+}
+
+/* control = 0 detaches */
+JNIEXPORT void JNICALL JNAME(hostControlAttach)(JNIEnv *env, jclass c, jlong control) {
+    int rc = gs_host_control_attach((gs_host_control *)(intptr_t)control);
+    if (rc) throw_host(env, rc);
+}
+
+/* out[13]: file, n_files, file_done, files_done, file_bytes_done, file_bytes_total, file_reads, total_bytes_done, total_bytes_total,
+ * total_reads, the file's and the call's time in milliseconds, cancelled (0 / 1) */
+JNIEXPORT void JNICALL JNAME(hostControlSnapshot)(JNIEnv *env, jclass c, jlong control, jlongArray out) {
+    gs_host_progress p;
+    int32_t cancelled = 0;
+    int rc = gs_host_control_snapshot((gs_host_control *)(intptr_t)control, &p, &cancelled);
+    if (!rc && (!out || (*env)->GetArrayLength(env, out) < 13)) rc = GS_E_INVALID;
+    if (rc) {
+        throw_host(env, rc);
+        return;
+    }
+    const jlong v[13] = {p.file, p.n_files, p.file_done, p.files_done, p.file_bytes_done, p.file_bytes_total, p.file_reads, p.total_bytes_done,
+                         p.total_bytes_total, p.total_reads, (jlong)(p.seconds_file * 1e3), (jlong)(p.seconds_total * 1e3), cancelled};
+    (*env)->SetLongArrayRegion(env, out, 0, 13, v);
+}
 
 /* gs_host_release_pools */
 JNIEXPORT void JNICALL JNAME(hostReleasePools)(JNIEnv *env, jclass c) {

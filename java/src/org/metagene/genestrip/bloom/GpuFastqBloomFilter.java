@@ -31,6 +31,7 @@ import java.util.List;
 
 import org.metagene.genestrip.DefaultExecutionContext;
 import org.metagene.genestrip.ExecutionContext;
+import org.metagene.genestrip.gpu.GpuProgress;
 import org.metagene.genestrip.gpu.GsGpuNative;
 import org.metagene.genestrip.io.StreamProvider;
 import org.metagene.genestrip.io.StreamingFileResource;
@@ -52,11 +53,16 @@ public class GpuFastqBloomFilter extends FastqBloomFilter {
 	// descriptor / read / quality copies of the batch, for the rewrite in input order
 	private final List<byte[][]> pending = new ArrayList<>();
 	private OutputStream accepted, rejected;
+	// FILES flow: the caller's context (the base class got one without consumers) takes the progress of the native call, polled
+	// every progressBarUpdateMs (GSConfigKey.PROGRESS_BAR_UPDATE; its default unless the goal sets it)
+	private final ExecutionContext progressBundle;
+	private int progressBarUpdateMs = 1000;
 
 	public GpuFastqBloomFilter(int k, AbstractKMerBloomFilter filter, int minPosCount, double positiveRatio,
 			int initialReadSize, int maxQueueSize, ExecutionContext bundle, boolean withProbs, int device) {
 		super(k, filter, minPosCount, positiveRatio, initialReadSize, maxQueueSize,
 				new DefaultExecutionContext(Thread.currentThread(), 0, bundle.getLogUpdateCycle()), withProbs);
+		this.progressBundle = bundle;
 		this.kk = k;
 		this.minPos = minPosCount;
 		this.ratio = positiveRatio;
@@ -83,13 +89,34 @@ public class GpuFastqBloomFilter extends FastqBloomFilter {
 		return paths.toArray(new String[0]);
 	}
 
+	/** the interval of the progress reports of the FILES flow (the goal's progressBarUpdateMs) */
+	public void setProgressBarUpdateMs(int ms) {
+		progressBarUpdateMs = ms;
+	}
+
 	@Override
 	public void runFilter(StreamingResourceStream fastqs, File filteredFile, File restFile) throws IOException {
 		String[] files = localFiles(fastqs);
 		if (files != null) { // FILES flow: FastqBloomFilter.runFilter (:80-89) in one native call
 			long[] totals = new long[4];
-			GsGpuNative.hostFilterFiles(bloom, kk, minPos, ratio, files, filteredFile == null ? null : filteredFile.getPath(),
-					restFile == null ? null : restFile.getPath(), keepQualities, totals);
+			// progress and interruption cross the seam through a control that a daemon thread polls (gpu/GpuProgress.java); a call
+			// stopped that way throws what the reference's readers throw, and the output files hold the reads of the last report
+			List<StreamingResource> all = new ArrayList<>();
+			for (StreamingResource r : fastqs) {
+				all.add(r);
+			}
+			GpuProgress progress = progressBundle.isRequiresProgress()
+					? new GpuProgress(progressBundle, all.toArray(new StreamingResource[0]), progressBarUpdateMs) : null;
+			try {
+				GsGpuNative.hostFilterFiles(bloom, kk, minPos, ratio, files, filteredFile == null ? null : filteredFile.getPath(),
+						restFile == null ? null : restFile.getPath(), keepQualities, totals);
+			} catch (RuntimeException e) {
+				throw GpuProgress.translate(e);
+			} finally {
+				if (progress != null) {
+					progress.close();
+				}
+			}
 			totalReads = totals[0];
 			totalKMers = totals[1];
 			totalBPs = totals[2];

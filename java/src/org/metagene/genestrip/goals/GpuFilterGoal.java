@@ -64,6 +64,7 @@ public class GpuFilterGoal<P extends GSProject> extends FilterGoal<P> {
 					return getKey().getName();
 				}
 			};
+			f.setProgressBarUpdateMs(intConfigValue(GSConfigKey.PROGRESS_BAR_UPDATE)); // (the FILES flow reports at this interval)
 			f.runFilter(resources, file, dumpFile);
 		} finally {
 			if (f != null) {

@@ -38,7 +38,7 @@ public class GpuMatchResultGoal<P extends GSProject> extends MatchResultGoal<P> 
 	@Override
 	protected FastqKMerMatcher createMatcher(KMerStore<SmallTaxIdNode> store, SmallTaxTree taxTree,
 			ExecutionContext bundle, boolean withProbs, String dbMD5) {
-		return new GpuFastqKMerMatcher(store, intConfigValue(GSConfigKey.INITIAL_READ_SIZE_BYTES),
+		GpuFastqKMerMatcher matcher = new GpuFastqKMerMatcher(store, intConfigValue(GSConfigKey.INITIAL_READ_SIZE_BYTES),
 				intConfigValue(GSConfigKey.THREAD_QUEUE_SIZE), bundle, withProbs,
 				intConfigValue(GSConfigKey.MAX_KMER_RES_COUNTS), taxTree,
 				intConfigValue(GSConfigKey.MAX_CLASSIFICATION_PATHS),
@@ -55,5 +55,7 @@ public class GpuMatchResultGoal<P extends GSProject> extends MatchResultGoal<P> 
 				return getKey().getName();
 			}
 		};
+		matcher.setProgressBarUpdateMs(intConfigValue(GSConfigKey.PROGRESS_BAR_UPDATE)); // (the FILES flow reports at this interval)
+		return matcher;
 	}
 }

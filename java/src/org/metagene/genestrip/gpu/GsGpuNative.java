@@ -287,6 +287,32 @@ public final class GsGpuNative {
 	/** gs_host_last_error: the message of the last failure inside the host layer on this thread */
 	public static native String hostLastError();
 
+	/** gs_host_control_create without a callback: the handle of a progress / cancel control.  A file-level call (hostMatchFiles,
+	 *  hostMatchRun, hostMatchInto, hostFilterFiles, hostExtractFiles, hostFasta2Fastq) made by the thread that attached it publishes
+	 *  its records there and stops when it is cancelled: the call then throws a RuntimeException whose message starts with
+	 *  "cancelled" (its totals are filled), and the state and outputs cover exactly the reads of the last snapshot. */
+	public static native long hostControlCreate();
+
+	public static native void hostControlDestroy(long control);
+
+	/** any thread */
+	public static native void hostControlCancel(long control);
+
+	/** the calling thread's file-level calls use the control until hostControlAttach(0) */
+	public static native void hostControlAttach(long control);
+
+	/** any thread; out[SNAPSHOT_LEN]: the latest record -- indices S_* -- and the cancel flag */
+	public static native void hostControlSnapshot(long control, long[] out);
+
+	public static final int S_FILE = 0, S_N_FILES = 1, S_FILE_DONE = 2, S_FILES_DONE = 3, S_FILE_BYTES_DONE = 4, S_FILE_BYTES_TOTAL = 5,
+			S_FILE_READS = 6, S_TOTAL_BYTES_DONE = 7, S_TOTAL_BYTES_TOTAL = 8, S_TOTAL_READS = 9, S_FILE_MS = 10, S_TOTAL_MS = 11,
+			S_CANCELLED = 12, SNAPSHOT_LEN = 13;
+
+	/** true for the exception of a call that was stopped through its control */
+	public static boolean isCancelled(RuntimeException e) {
+		return e.getMessage() != null && e.getMessage().startsWith("cancelled");
+	}
+
 	/** gs_host_release_pools: page-locked blocks and device decoders the host layer keeps from call to call go back to the system */
 	public static native void hostReleasePools();
 

@@ -37,6 +37,7 @@ import org.metagene.genestrip.DefaultExecutionContext;
 import org.metagene.genestrip.ExecutionContext;
 import org.metagene.genestrip.gpu.GsGpuNative;
 import org.metagene.genestrip.io.StreamingFileResource;
+import org.metagene.genestrip.gpu.GpuProgress;
 import org.metagene.genestrip.io.StreamingResource;
 import org.metagene.genestrip.io.StreamingResourceStream;
 import org.metagene.genestrip.store.KMerStore;
@@ -93,6 +94,10 @@ public class GpuFastqKMerMatcher extends FastqKMerMatcher {
 	private final byte[][] maxContigDescriptor; // per value index: descriptor of the read that holds the longest contig
 	// FILES flow: the output files of the current runMatcher call (written below the JVM)
 	private File nativeFiltered, nativeKraken;
+	// FILES flow: the caller's context (the base class got one without consumers) takes the progress of the native call, polled
+	// every progressBarUpdateMs (GSConfigKey.PROGRESS_BAR_UPDATE; its default unless the goal sets it)
+	private final ExecutionContext progressBundle;
+	private int progressBarUpdateMs = 1000;
 
 	public GpuFastqKMerMatcher(KMerStore<SmallTaxIdNode> kmerStore, int initialReadSize, int maxQueueSize,
 			ExecutionContext bundle, boolean withProbs, int maxKmerResCounts, SmallTaxTree taxTree, int maxPaths,
@@ -103,6 +108,7 @@ public class GpuFastqKMerMatcher extends FastqKMerMatcher {
 				new DefaultExecutionContext(Thread.currentThread(), 0, bundle.getLogUpdateCycle()), withProbs,
 				maxKmerResCounts, taxTree, maxPaths, maxReadTaxErrorCount, maxReadClassErrorCount, writeAll, threshold,
 				dbMD5);
+		progressBundle = bundle;
 		nValues = kmerStore.getNValues();
 		keepQualities = withProbs;
 		nodeOfValue = new SmallTaxIdNode[nValues];
@@ -175,6 +181,19 @@ public class GpuFastqKMerMatcher extends FastqKMerMatcher {
 		return paths.toArray(new String[0]);
 	}
 
+	/** the interval of the progress reports of the FILES flow (the goal's progressBarUpdateMs) */
+	public void setProgressBarUpdateMs(int ms) {
+		progressBarUpdateMs = ms;
+	}
+
+	private static StreamingResource[] resources(StreamingResourceStream fastqs) {
+		java.util.List<StreamingResource> all = new java.util.ArrayList<>();
+		for (StreamingResource r : fastqs) {
+			all.add(r);
+		}
+		return all.toArray(new StreamingResource[0]);
+	}
+
 	private static boolean hasFastaName(String name) {
 		String n = name.toLowerCase();
 		for (String gz : new String[] { ".gzip", ".gz" }) {
@@ -226,9 +245,21 @@ public class GpuFastqKMerMatcher extends FastqKMerMatcher {
 			// FILES flow: one native call does what the loop of AbstractLoggingFastqStreamer.processFastqStreams (:95-131) does
 			ByteBuffer descs = direct((long) nValues * DESC_STRIDE);
 			long[] totals = new long[4];
-			GsGpuNative.hostMatchRun(run, db, files, nativeFiltered == null ? null : nativeFiltered.getPath(),
-					nativeKraken == null ? null : nativeKraken.getPath(), writeAll, taxidStrings, keepQualities, descs,
-					DESC_STRIDE, totals);
+			// progress and interruption cross the seam through a control that a daemon thread polls (gpu/GpuProgress.java); a call
+			// stopped that way throws what the reference's readers throw, and the run holds the reads of the last report
+			GpuProgress progress = progressBundle.isRequiresProgress()
+					? new GpuProgress(progressBundle, resources(fastqs), progressBarUpdateMs) : null;
+			try {
+				GsGpuNative.hostMatchRun(run, db, files, nativeFiltered == null ? null : nativeFiltered.getPath(),
+						nativeKraken == null ? null : nativeKraken.getPath(), writeAll, taxidStrings, keepQualities, descs,
+						DESC_STRIDE, totals);
+			} catch (RuntimeException e) {
+				throw GpuProgress.translate(e);
+			} finally {
+				if (progress != null) {
+					progress.close();
+				}
+			}
 			totalReads = totals[0];
 			totalKMers = totals[1];
 			totalBPs = totals[2];
