@@ -62,6 +62,8 @@ ABI_SYMBOLS = (
     "gs_krakencount_kernel_time",
     "gs_genomes_create", "gs_genomes_scan", "gs_genomes_headers", "gs_genomes_gather", "gs_genomes_regions", "gs_genomes_kernel_time",
     "gs_genomes_destroy",
+    "gs_accmap_create", "gs_accmap_submit", "gs_accmap_append", "gs_accmap_finish", "gs_accmap_fetch", "gs_accmap_lookup",
+    "gs_accmap_lookup_genomes", "gs_accmap_get_device", "gs_accmap_kernel_time", "gs_accmap_destroy",
 )
 
 
@@ -267,6 +269,10 @@ def lib():
         "gs_krakencount_chunk": (ci, [vp, i64, vp]), "gs_krakencount_status": (ci, [vp, vp, vp, vp, vp]), "gs_krakencount_reset": (ci, [vp]),
         "gs_krakencount_fetch": (ci, [vp, vp, vp, i64, vp]), "gs_krakencount_counters": (ci, [vp, vp]),
         "gs_krakencount_kernel_time": (ci, [vp, ci, vp, vp]),
+        "gs_accmap_create": (ci, [vp, ci, vp]), "gs_accmap_submit": (ci, [vp, vp, i64, ci, ci, vp]),
+        "gs_accmap_append": (ci, [vp, vp, vp, i64, i64]), "gs_accmap_finish": (ci, [vp, vp]), "gs_accmap_fetch": (ci, [vp, vp, vp, vp]),
+        "gs_accmap_lookup": (ci, [vp, vp, vp, i64, ci, ci, vp]), "gs_accmap_lookup_genomes": (ci, [vp, vp, ci, vp]),
+        "gs_accmap_get_device": (ci, [vp, vp]), "gs_accmap_kernel_time": (ci, [vp, ci, vp, vp]), "gs_accmap_destroy": (ci, [vp]),
         "gs_genomes_create": (ci, [vp, ci]), "gs_genomes_scan": (ci, [vp, vp, i64, ci, ci, vp, vp, vp, vp]),
         "gs_genomes_headers": (ci, [vp, vp, vp]), "gs_genomes_gather": (ci, [vp, vp, vp, vp]), "gs_genomes_regions": (ci, [vp, vp, vp]),
         "gs_genomes_kernel_time": (ci, [vp, vp, vp]), "gs_genomes_destroy": (ci, [vp]),
@@ -1772,4 +1778,145 @@ class KrakenCounter:
     def kernel_time(self, profile=True):
         n, ms = C.c_int64(), C.c_double()
         _check(lib().gs_krakencount_kernel_time(self.h, int(profile), C.byref(n), C.byref(ms)))
+        return n.value, ms.value
+
+
+class _AccmapCfg(C.Structure):
+    _fields_ = [("dna", C.c_int32), ("rna", C.c_int32), ("mrna", C.c_int32), ("n_categories", C.c_int32), ("n_statuses", C.c_int32),
+                ("n_nodes", C.c_int32), ("categories", C.POINTER(C.c_char_p)), ("statuses", C.POINTER(C.c_char_p)),
+                ("known_taxids", C.c_void_p), ("reserve_entries", C.c_int64)]
+
+
+def accession_slots(keys):
+    """accessions (bytes, at most 31 each, all below 0x80) -> their 32-byte slots as uint8[n, 32]: length, bytes, zeros"""
+    out = np.zeros((len(keys), 32), dtype=np.uint8)
+    for i, k in enumerate(keys):
+        if len(k) > 31:
+            raise ValueError("an accession slot holds at most 31 bytes")
+        out[i, 0] = len(k)
+        out[i, 1:1 + len(k)] = np.frombuffer(bytes(k), dtype=np.uint8)
+    return out
+
+
+def slot_accessions(slots):
+    """uint8[n, 32] slots -> list of accessions (bytes)"""
+    return [bytes(s[1:1 + int(s[0])]) for s in np.asarray(slots, dtype=np.uint8).reshape(-1, 32)]
+
+
+class DeviceAccessionMap:
+    """gs_accmap: the lines of a RefSeq catalog to the accession map on the device (the accmapsize and accmap goals).  A node is an
+    index into known_taxids (ascending, distinct, positive), -1 is none.  submit() takes chunks of whole lines; a chunk outside the
+    device's grammar is refused and leaves the map as it was: the caller parses it and hands its entries in through append().
+    Among equal accessions a lookup answers with the one that came first in the input."""
+
+    SEQ_TYPES = {"GENOMIC": (1, 0, 0), "RNA": (0, 1, 0), "M_RNA": (0, 0, 1), "ALL_RNA": (0, 1, 1), "ALL": (1, 1, 1)}
+
+    @classmethod
+    def config(cls, known_taxids, categories, statuses, seq_type="GENOMIC", reserve_entries=0):
+        """-> (gs_accmap_cfg, known_taxids as int32): the structure keeps the arrays it points to alive"""
+        known = np.ascontiguousarray(known_taxids, dtype=np.int32)
+        dna, rna, mrna = cls.SEQ_TYPES[seq_type] if isinstance(seq_type, str) else seq_type
+        cats = [c.encode() if isinstance(c, str) else bytes(c) for c in categories]
+        stats = [s.encode() if isinstance(s, str) else bytes(s) for s in statuses]
+        cfg = _AccmapCfg(int(bool(dna)), int(bool(rna)), int(bool(mrna)), len(cats), len(stats), len(known),
+                         (C.c_char_p * max(len(cats), 1))(*cats), (C.c_char_p * max(len(stats), 1))(*stats),
+                         known.ctypes.data_as(C.c_void_p) if len(known) else None, int(reserve_entries))
+        cfg._known = known
+        return cfg, known
+
+    def __init__(self, known_taxids, categories, statuses, seq_type="GENOMIC", device=0, reserve_entries=0):
+        """seq_type: one of SEQ_TYPES or a (dna, rna, mrna) triple; categories / statuses: strings searched for as substrings;
+        device -1: a host-only map (append, finish, fetch and lookups of host memory; no device is touched)"""
+        self.h = C.c_void_p()
+        self.device = int(device)
+        cfg, self.known = self.config(known_taxids, categories, statuses, seq_type, reserve_entries)
+        self.n_entries = self.n_passing = self.n_duplicates = self.n_conflicts = 0
+        _check(lib().gs_accmap_create(C.byref(self.h), self.device, C.byref(cfg)))
+
+    @classmethod
+    def _wrap(cls, handle, known_taxids):
+        """a finished map that the host layer made (host.accmap_files); its device is -1 if it is a host-only one"""
+        m = cls.__new__(cls)
+        m.h = handle
+        m.known = np.ascontiguousarray(known_taxids, dtype=np.int32)
+        dev = C.c_int(0)
+        _check(lib().gs_accmap_get_device(m.h, C.byref(dev)))
+        m.device = dev.value
+        m.n_entries = m.n_passing = m.n_duplicates = m.n_conflicts = 0
+        return m
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().gs_accmap_destroy(self.h)
+            self.h = C.c_void_p()
+
+    __del__ = close
+
+    def submit(self, text, last=False):
+        """a chunk of whole lines (bytes, a uint8 array, or a uint8 tensor on the handle's device); last: the stream ends here and
+        its final line need not be terminated -> its report"""
+        if isinstance(text, (bytes, bytearray, memoryview)):
+            text = np.frombuffer(bytes(text), dtype=np.uint8)
+        n = int(text.shape[0])
+        _ready(text)
+        p, mem = _ptr(text) if n else (None, MEM_HOST)
+        r = (C.c_int64 * 8)()
+        _check(lib().gs_accmap_submit(self.h, p, n, mem, int(bool(last)), r))
+        return {"lines": r[0], "passing": r[1], "put": r[2], "refused": r[3], "first_bad_line": r[4], "longest_line": r[5]}
+
+    def append(self, keys, nodes, n_passing=None):
+        """entries made elsewhere, in input order: keys (accessions as bytes, or uint8[n, 32] slots), nodes; n_passing: the passing
+        entries of the same lines, those without a node included (default: len(keys))"""
+        slots = np.ascontiguousarray(keys, dtype=np.uint8).reshape(-1, 32) if isinstance(keys, np.ndarray) else accession_slots(keys)
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+        if len(nodes) != len(slots):
+            raise ValueError("one node per key")
+        n = len(slots)
+        _check(lib().gs_accmap_append(self.h, _ptr(slots)[0] if n else None, _ptr(nodes)[0] if n else None, n, n if n_passing is None else int(n_passing)))
+
+    def finish(self):
+        """sorts -> (entries, passing entries in all = the accmapsize count, duplicates, conflicts)"""
+        info = (C.c_int64 * 4)()
+        _check(lib().gs_accmap_finish(self.h, info))
+        self.n_entries, self.n_passing, self.n_duplicates, self.n_conflicts = tuple(info)
+        return tuple(info)
+
+    def fetch(self):
+        """-> (slots uint8[entries, 32] in the map's order, nodes int32[entries], regions int32[n_nodes])"""
+        slots = np.zeros((max(self.n_entries, 1), 32), dtype=np.uint8)
+        nodes = np.zeros(max(self.n_entries, 1), dtype=np.int32)
+        regions = np.zeros(max(len(self.known), 1), dtype=np.int32)
+        _check(lib().gs_accmap_fetch(self.h, _ptr(slots)[0], _ptr(nodes)[0], _ptr(regions)[0]))
+        return slots[:self.n_entries], nodes[:self.n_entries], regions[:len(self.known)]
+
+    def lookup(self, headers, header_off=None, complete_only=False):
+        """headers: a list of header lines (bytes), or the lines back to back (uint8 array or device tensor) with header_off
+        (uint64[n + 1], in the same memory) -> node per line: int32 array, or a device tensor if the input was one"""
+        if header_off is None:
+            lens = np.array([len(x) for x in headers], dtype=np.uint64)
+            header_off = np.concatenate([np.zeros(1, np.uint64), np.cumsum(lens, dtype=np.uint64)])
+            headers = np.frombuffer(b"".join(bytes(x) for x in headers) or b"\0", dtype=np.uint8)
+        n = int(header_off.shape[0]) - 1
+        _ready(headers, header_off)
+        (ph, mem), (po, mem_off) = _ptr(headers), _ptr(header_off)
+        if mem != mem_off:
+            raise ValueError("headers and header_off must live in the same memory")
+        if mem == MEM_DEVICE:
+            import torch
+            out = torch.empty(max(n, 1), dtype=torch.int32, device=headers.device)
+        else:
+            out = np.zeros(max(n, 1), dtype=np.int32)
+        _check(lib().gs_accmap_lookup(self.h, ph, po, n, mem, int(bool(complete_only)), _ptr(out)[0]))
+        return out[:n]
+
+    def lookup_genomes(self, genomes, complete_only=False):
+        """the header lines of the chunk a DeviceGenomes has scanned, looked up where they are -> node per record (int32)"""
+        out = np.zeros(max(genomes.n_records, 1), dtype=np.int32)
+        _check(lib().gs_accmap_lookup_genomes(self.h, genomes.h, int(bool(complete_only)), _ptr(out)[0]))
+        return out[:genomes.n_records]
+
+    def kernel_time(self, profile=True):
+        """(launches, milliseconds) of the scan, finish and lookup kernels so far; switches their timing on or off"""
+        n, ms = C.c_int64(), C.c_double()
+        _check(lib().gs_accmap_kernel_time(self.h, int(profile), C.byref(n), C.byref(ms)))
         return n.value, ms.value

@@ -5090,18 +5090,26 @@ extern "C" int gs_genomes_scan(gs_genomes *g, const uint8_t *text, int64_t n_byt
 }
 GS_API_CATCH
 
+// the header lines of the scanned chunk back to back in g->d_hdr, P->hdr_off[n_records + 1] beside them (g->n_records > 0); the
+// stream has the work, nothing waits for it
+static int gn_device_headers(gs_genomes *g, GsGenomesParams *P) {
+    HIP_TRY(hipSetDevice(g->device));
+    int rc = gn_grow(&g->d_hdr, &g->hdr_cap, (size_t)std::max<int64_t>(g->hdr_bytes, 1), 1, g->stream);
+    if (rc) return rc;
+    gn_params(g, P);
+    HIP_TRY(gs_launch_genomes_headers(P, g->stream));
+    return GS_OK;
+}
+
 extern "C" int gs_genomes_headers(gs_genomes *g, uint8_t *headers, uint64_t *header_off) try {
     if (!g || !header_off) return fail(GS_E_INVALID, "NULL argument");
     if (g->state < 1) return fail(GS_E_STATE, "gs_genomes_headers comes behind a gs_genomes_scan that took its chunk");
     if (g->hdr_bytes > 0 && !headers) return fail(GS_E_INVALID, "headers is NULL");
     header_off[0] = 0;
     if (g->n_records == 0) return GS_OK;
-    HIP_TRY(hipSetDevice(g->device));
-    int rc = gn_grow(&g->d_hdr, &g->hdr_cap, (size_t)std::max<int64_t>(g->hdr_bytes, 1), 1, g->stream);
-    if (rc) return rc;
     GsGenomesParams P{};
-    gn_params(g, &P);
-    HIP_TRY(gs_launch_genomes_headers(&P, g->stream));
+    int rc = gn_device_headers(g, &P);
+    if (rc) return rc;
     if (g->hdr_bytes > 0) HIP_TRY(hipMemcpyAsync(headers, g->d_hdr, (size_t)g->hdr_bytes, hipMemcpyDeviceToHost, g->stream));
     HIP_TRY(hipMemcpyAsync(header_off, P.hdr_off, sizeof(u64) * ((size_t)g->n_records + 1), hipMemcpyDeviceToHost, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
@@ -6895,3 +6903,475 @@ extern "C" int gs_krakencount_kernel_time(gs_krakencount *h, int profile, int64_
     if (total_ms) *total_ms = h->timer.total_ms;
     return GS_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------
+// accmap: RefSeq catalog lines to the accession map (gs_accmap.hip)
+// ---------------------------------------------------------------------------------------------------
+struct gs_accmap {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool finished = false;
+    int32_t dna = 0, rna = 0, mrna = 0, n_cat = 0, n_stat = 0, n_nodes = 0;
+    GsAccmapPatterns *d_pat = nullptr;
+    int32_t *d_known = nullptr, *d_regions = nullptr;
+    uint8_t *d_text = nullptr;
+    size_t text_cap = 0;
+    u64 *d_tile = nullptr;  // tile_lt | tile_put, tile_cap entries each
+    uint32_t *d_tail = nullptr;
+    size_t tile_cap = 0;
+    uint8_t *d_keys = nullptr;  // entry_cap slots of 32 bytes; sorted once finished
+    int32_t *d_nodes = nullptr;
+    size_t entry_cap = 0;
+    int64_t n_entries = 0, n_passing = 0;
+    std::vector<int32_t> host_regions;  // the entries that came in through gs_accmap_append, per node
+    bool host_only = false;             // device == -1: no device is touched; the entries live in h_keys / h_nodes, sorted once finished
+    std::vector<uint8_t> h_keys;
+    std::vector<int32_t> h_nodes;
+    u64 *d_small = nullptr;             // status, chunk counters, scan sums, finish counts, flag (AM_S_*)
+    bool profile = false;
+    KernelTimer timer;
+};
+enum { AM_S_STATUS = 0, AM_S_CHUNK = 1, AM_S_SCAN = AM_S_CHUNK + GS_AM_C_WORDS, AM_S_COUNTS = AM_S_SCAN + 2, AM_S_FLAG = AM_S_COUNTS + 2, AM_S_WORDS };
+static_assert(GS_AM_WORDS == 2, "the status words fill one 64-bit word of d_small");
+
+extern "C" int gs_accmap_destroy(gs_accmap *h) try {
+    if (!h) return GS_OK;
+    if (h->host_only) {
+        delete h;
+        return GS_OK;
+    }
+    hipSetDevice(h->device);
+    if (h->stream) hipStreamSynchronize(h->stream);
+    timer_free(h->timer);
+    for (void *p : {(void *)h->d_pat, (void *)h->d_known, (void *)h->d_regions, (void *)h->d_text, (void *)h->d_tile, (void *)h->d_tail, (void *)h->d_keys,
+                    (void *)h->d_nodes, (void *)h->d_small})
+        gs_dev_free(p);
+    if (h->stream) hipStreamDestroy(h->stream);
+    delete h;
+    return GS_OK;
+}
+GS_API_CATCH
+
+// room for `need` entries in all; what is there stays
+static int am_entry_room(gs_accmap *h, size_t need) {
+    if (need <= h->entry_cap) return GS_OK;
+    if (need > ((size_t)1 << 31)) return fail(GS_E_UNSUPPORTED, "an accession map holds at most 2^31 entries");
+    const size_t cap = std::max(need, 2 * h->entry_cap);
+    uint8_t *keys = nullptr;
+    int32_t *nodes = nullptr;
+    hipError_t e = gs_dev_alloc(&keys, cap * 32);
+    if (e == hipSuccess) e = gs_dev_alloc(&nodes, cap * sizeof(int32_t));
+    if (e == hipSuccess && h->n_entries) e = hipMemcpyAsync(keys, h->d_keys, (size_t)h->n_entries * 32, hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess && h->n_entries) e = hipMemcpyAsync(nodes, h->d_nodes, (size_t)h->n_entries * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        gs_dev_free(keys);
+        gs_dev_free(nodes);
+        return hip_fail(e, "gs_accmap: growing the entry arrays");
+    }
+    gs_dev_free(h->d_keys);
+    gs_dev_free(h->d_nodes);
+    h->d_keys = keys;
+    h->d_nodes = nodes;
+    h->entry_cap = cap;
+    return GS_OK;
+}
+
+extern "C" int gs_accmap_create(gs_accmap **out, int device, const gs_accmap_cfg *cfg) try {
+    if (!out) return fail(GS_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!cfg) return fail(GS_E_INVALID, "cfg is NULL");
+    if (cfg->n_categories < 1 || cfg->n_categories > GS_AM_MAX_PATTERNS || cfg->n_statuses < 1 || cfg->n_statuses > GS_AM_MAX_PATTERNS)
+        return fail(GS_E_INVALID, "1 to 16 category strings and 1 to 16 status strings");
+    if (!cfg->categories || !cfg->statuses) return fail(GS_E_INVALID, "categories or statuses is NULL");
+    if (cfg->n_nodes < 0 || (cfg->n_nodes > 0 && !cfg->known_taxids)) return fail(GS_E_INVALID, "known_taxids is NULL or n_nodes < 0");
+    if (cfg->reserve_entries < 0 || cfg->reserve_entries > ((int64_t)1 << 31)) return fail(GS_E_INVALID, "reserve_entries must be in [0, 2^31]");
+    for (int32_t i = 0; i < cfg->n_nodes; i++)
+        if (cfg->known_taxids[i] <= 0 || (i && cfg->known_taxids[i] <= cfg->known_taxids[i - 1]))
+            return fail(GS_E_INVALID, "known_taxids must be positive, ascending and distinct");
+    GsAccmapPatterns pat{};
+    for (int kind = 0; kind < 2; kind++) {
+        const int n = kind ? cfg->n_statuses : cfg->n_categories;
+        for (int i = 0; i < n; i++) {
+            const char *s = (kind ? cfg->statuses : cfg->categories)[i];
+            const size_t len = s ? strnlen(s, GS_AM_MAX_PATTERN + 1) : 0;
+            if (len < 1 || len > GS_AM_MAX_PATTERN) return fail(GS_E_INVALID, "a category or status string has 1 to 32 bytes");
+            pat.len[kind * GS_AM_MAX_PATTERNS + i] = (uint8_t)len;
+            memcpy(pat.text[kind * GS_AM_MAX_PATTERNS + i], s, len);
+        }
+    }
+    int rc = device == -1 ? (int)GS_OK : use_device(device);
+    if (rc) return rc;
+    gs_accmap *h = new gs_accmap();
+    h->device = device;
+    h->host_only = device == -1;
+    h->dna = cfg->dna != 0;
+    h->rna = cfg->rna != 0;
+    h->mrna = cfg->mrna != 0;
+    h->n_cat = cfg->n_categories;
+    h->n_stat = cfg->n_statuses;
+    h->n_nodes = cfg->n_nodes;
+    h->host_regions.assign((size_t)cfg->n_nodes, 0);
+    if (h->host_only) {
+        *out = h;
+        return GS_OK;
+    }
+    const size_t nodes = (size_t)std::max(cfg->n_nodes, 1);
+    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = gs_dev_alloc(&h->d_pat, sizeof(GsAccmapPatterns));
+    if (e == hipSuccess) e = gs_dev_alloc(&h->d_known, sizeof(int32_t) * nodes);
+    if (e == hipSuccess) e = gs_dev_alloc(&h->d_regions, sizeof(int32_t) * nodes);
+    if (e == hipSuccess) e = gs_dev_alloc(&h->d_small, sizeof(u64) * AM_S_WORDS);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->d_pat, &pat, sizeof(pat), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && cfg->n_nodes) e = hipMemcpyAsync(h->d_known, cfg->known_taxids, sizeof(int32_t) * nodes, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(h->d_regions, 0, sizeof(int32_t) * nodes, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // (pat is a local)
+    if (e != hipSuccess) {
+        gs_accmap_destroy(h);
+        return hip_fail(e, "gs_accmap_create");
+    }
+    if ((rc = am_entry_room(h, (size_t)std::max<int64_t>(cfg->reserve_entries, 1)))) {
+        gs_accmap_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_accmap_get_device(gs_accmap *h, int *device) try {
+    if (!h || !device) return fail(GS_E_INVALID, "NULL argument");
+    *device = h->device;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_accmap_submit(gs_accmap *h, const uint8_t *text, int64_t n_bytes, int mem, int last, int64_t report[8]) try {
+    if (!h || !report) return fail(GS_E_INVALID, "NULL argument");
+    if (n_bytes < 0 || n_bytes > ((int64_t)1 << 30)) return fail(GS_E_INVALID, "a chunk holds at most 1 GiB");
+    if (n_bytes > 0 && !text) return fail(GS_E_INVALID, "text is NULL");
+    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    if (h->finished) return fail(GS_E_STATE, "gs_accmap_submit comes in front of gs_accmap_finish");
+    if (h->host_only) return fail(GS_E_UNSUPPORTED, "a host-only accession map (device -1) takes entries through gs_accmap_append alone");
+    for (int i = 0; i < 8; i++) report[i] = 0;
+    report[4] = -1;
+    if (n_bytes == 0) return GS_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t n_tiles = (n_bytes + GS_AM_TILE - 1) / GS_AM_TILE;
+    const size_t padded = (size_t)n_tiles * GS_AM_TILE + 64;
+    int rc;
+    if ((rc = grow(&h->d_text, &h->text_cap, padded, h->stream))) return rc;
+    if (h->tile_cap < (size_t)n_tiles + 1) {
+        const size_t cap = (size_t)n_tiles + 1 + (size_t)n_tiles / 4;
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->tile_cap = 0;
+        if ((rc = renew(&h->d_tile, 2 * cap))) return rc;
+        if ((rc = renew(&h->d_tail, cap))) return rc;
+        h->tile_cap = cap;
+    }
+    HIP_TRY(hipMemcpyAsync(h->d_text, text, (size_t)n_bytes, mem == GS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(h->d_text + n_bytes, 0, padded - (size_t)n_bytes, h->stream));
+    u64 small[AM_S_SCAN] = {};
+    small[AM_S_STATUS] = (u64)GS_AM_NONE;  // bad line: none; longest line: 0
+    HIP_TRY(hipMemcpy(h->d_small, small, sizeof(small), hipMemcpyHostToDevice));  // (the stream is idle between calls)
+    GsAccmapParams P{};
+    P.text = h->d_text;
+    P.n_bytes = n_bytes;
+    P.n_tiles = n_tiles;
+    P.last = last != 0;
+    P.dna = h->dna;
+    P.rna = h->rna;
+    P.mrna = h->mrna;
+    P.n_cat = h->n_cat;
+    P.n_stat = h->n_stat;
+    P.pat = h->d_pat;
+    P.known = h->d_known;
+    P.n_nodes = h->n_nodes;
+    P.tile_lt = (unsigned long long *)h->d_tile;
+    P.tile_put = (unsigned long long *)h->d_tile + h->tile_cap;
+    P.tile_tail = h->d_tail;
+    P.scan_tot = (unsigned long long *)h->d_small + AM_S_SCAN;
+    P.status = (uint32_t *)(h->d_small + AM_S_STATUS);
+    P.chunk = (unsigned long long *)h->d_small + AM_S_CHUNK;
+    P.regions = h->d_regions;
+    if ((rc = timer_start(h->timer, h->profile, h->stream))) return rc;
+    HIP_TRY(gs_launch_accmap_count(&P, h->stream));
+    if ((rc = timer_stop(h->timer, h->profile, h->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(small, h->d_small, sizeof(small), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));  // the one wait of a chunk: its verdict and its counts, between the passes
+    const uint32_t bad = (uint32_t)small[AM_S_STATUS];
+    report[0] = (int64_t)small[AM_S_CHUNK + GS_AM_C_LINES];
+    report[5] = (int64_t)(small[AM_S_STATUS] >> 32);
+    if (bad != GS_AM_NONE) {
+        report[3] = 1;
+        report[4] = (int64_t)bad;
+        return timer_collect(h->timer);
+    }
+    const int64_t n_put = (int64_t)small[AM_S_CHUNK + GS_AM_C_PUT];
+    report[1] = (int64_t)small[AM_S_CHUNK + GS_AM_C_PASSING];
+    report[2] = n_put;
+    if (n_put > 0) {
+        if ((rc = am_entry_room(h, (size_t)(h->n_entries + n_put)))) return rc;
+        P.keys = h->d_keys;
+        P.nodes = h->d_nodes;
+        P.first_entry = h->n_entries;
+        P.entry_cap = (int64_t)h->entry_cap;
+        if ((rc = timer_start(h->timer, h->profile, h->stream))) return rc;
+        HIP_TRY(gs_launch_accmap_write(&P, h->stream));
+        if ((rc = timer_stop(h->timer, h->profile, h->stream))) return rc;
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    h->n_entries += n_put;
+    h->n_passing += report[1];
+    return timer_collect(h->timer);
+}
+GS_API_CATCH
+
+extern "C" int gs_accmap_append(gs_accmap *h, const uint8_t *keys32, const int32_t *nodes, int64_t n, int64_t n_passing) try {
+    if (!h) return fail(GS_E_INVALID, "accmap is NULL");
+    if (n < 0 || n_passing < n) return fail(GS_E_INVALID, "n < 0 or n_passing < n");
+    if (n > 0 && (!keys32 || !nodes)) return fail(GS_E_INVALID, "NULL argument");
+    if (h->finished) return fail(GS_E_STATE, "gs_accmap_append comes in front of gs_accmap_finish");
+    for (int64_t i = 0; i < n; i++) {
+        if (nodes[i] < 0 || nodes[i] >= h->n_nodes) return fail(GS_E_INVALID, "a node is no index into known_taxids");
+        const uint8_t *k = keys32 + 32 * i;
+        bool ok = k[0] <= GS_AM_MAX_KEY;
+        for (int j = 1; j < 32 && ok; j++) ok = j <= k[0] ? k[j] < 0x80 : k[j] == 0;
+        if (!ok) return fail(GS_E_INVALID, "a slot is a length of 0..31, that many bytes below 0x80, and zeros");
+    }
+    if (n > 0 && h->host_only) {
+        h->h_keys.insert(h->h_keys.end(), keys32, keys32 + 32 * n);
+        h->h_nodes.insert(h->h_nodes.end(), nodes, nodes + n);
+        for (int64_t i = 0; i < n; i++) h->host_regions[(size_t)nodes[i]]++;
+        h->n_entries += n;
+    } else if (n > 0) {
+        HIP_TRY(hipSetDevice(h->device));
+        int rc = am_entry_room(h, (size_t)(h->n_entries + n));
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(h->d_keys + (size_t)h->n_entries * 32, keys32, (size_t)n * 32, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->d_nodes + h->n_entries, nodes, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        for (int64_t i = 0; i < n; i++) h->host_regions[(size_t)nodes[i]]++;
+        h->n_entries += n;
+    }
+    h->n_passing += n_passing;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_accmap_finish(gs_accmap *h, int64_t info[4]) try {
+    if (!h || !info) return fail(GS_E_INVALID, "NULL argument");
+    if (h->finished) return fail(GS_E_STATE, "gs_accmap_finish was called before");
+    if (h->host_only) {  // the same order: bytes below 0x80, so the slots compare as their big-endian words do
+        const int64_t n = h->n_entries;
+        std::vector<uint32_t> seq((size_t)n);
+        for (int64_t i = 0; i < n; i++) seq[(size_t)i] = (uint32_t)i;
+        const uint8_t *k = h->h_keys.data();
+        std::stable_sort(seq.begin(), seq.end(), [k](uint32_t a, uint32_t b) { return memcmp(k + 32 * (size_t)a, k + 32 * (size_t)b, 32) < 0; });
+        std::vector<uint8_t> keys((size_t)n * 32);
+        std::vector<int32_t> nodes((size_t)n);
+        info[2] = info[3] = 0;
+        for (int64_t i = 0; i < n; i++) {
+            memcpy(keys.data() + 32 * (size_t)i, k + 32 * (size_t)seq[(size_t)i], 32);
+            nodes[(size_t)i] = h->h_nodes[seq[(size_t)i]];
+            if (i && memcmp(keys.data() + 32 * (size_t)i, keys.data() + 32 * (size_t)(i - 1), 32) == 0) {
+                info[2]++;
+                info[3] += nodes[(size_t)i] != nodes[(size_t)i - 1];
+            }
+        }
+        h->h_keys.swap(keys);
+        h->h_nodes.swap(nodes);
+        h->finished = true;
+        info[0] = n;
+        info[1] = h->n_passing;
+        return GS_OK;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t n = h->n_entries;
+    const size_t room = (size_t)std::max<int64_t>(n, 1);
+    size_t tmp_bytes = 0;
+    HIP_TRY(gs_accmap_sort_bytes(n, &tmp_bytes));
+    u64 *word = nullptr;      // word | word_alt
+    uint32_t *seq = nullptr;  // seq | seq_alt
+    void *tmp = nullptr;
+    uint8_t *keys = nullptr;
+    int32_t *nodes = nullptr;
+    hipError_t e = gs_dev_alloc(&word, 2 * room * sizeof(u64));
+    if (e == hipSuccess) e = gs_dev_alloc(&seq, 2 * room * sizeof(uint32_t));
+    if (e == hipSuccess) e = gs_dev_alloc(&tmp, std::max<size_t>(tmp_bytes, 1));
+    if (e == hipSuccess) e = gs_dev_alloc(&keys, room * 32);
+    if (e == hipSuccess) e = gs_dev_alloc(&nodes, room * sizeof(int32_t));
+    int rc = e == hipSuccess ? timer_start(h->timer, h->profile, h->stream) : hip_fail(e, "gs_accmap_finish");
+    uint32_t *seq_sorted = nullptr;
+    u64 counts[2] = {0, 0};
+    if (!rc) {
+        e = gs_accmap_sort_entries(h->d_keys, h->d_nodes, n, word, word + room, seq, seq + room, tmp, tmp_bytes, (uint32_t *)(h->d_small + AM_S_FLAG), keys, nodes,
+                             &seq_sorted, (unsigned long long *)h->d_small + AM_S_COUNTS, h->stream);
+        if (e == hipSuccess) rc = timer_stop(h->timer, h->profile, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(counts, h->d_small + AM_S_COUNTS, sizeof(counts), hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) rc = hip_fail(e, "gs_accmap_finish");
+    }
+    gs_dev_free(word);
+    gs_dev_free(seq);
+    gs_dev_free(tmp);
+    if (rc) {
+        gs_dev_free(keys);
+        gs_dev_free(nodes);
+        return rc;
+    }
+    gs_dev_free(h->d_keys);
+    gs_dev_free(h->d_nodes);
+    h->d_keys = keys;
+    h->d_nodes = nodes;
+    h->entry_cap = room;
+    h->finished = true;
+    info[0] = n;
+    info[1] = h->n_passing;
+    info[2] = (int64_t)counts[0];
+    info[3] = (int64_t)counts[1];
+    return timer_collect(h->timer);
+}
+GS_API_CATCH
+
+extern "C" int gs_accmap_fetch(gs_accmap *h, uint8_t *keys32, int32_t *nodes, int32_t *regions) try {
+    if (!h) return fail(GS_E_INVALID, "accmap is NULL");
+    if (!h->finished) return fail(GS_E_STATE, "gs_accmap_fetch comes behind gs_accmap_finish");
+    if (h->host_only) {
+        if (keys32 && h->n_entries) memcpy(keys32, h->h_keys.data(), h->h_keys.size());
+        if (nodes && h->n_entries) memcpy(nodes, h->h_nodes.data(), h->h_nodes.size() * sizeof(int32_t));
+        if (regions && h->n_nodes) memcpy(regions, h->host_regions.data(), h->host_regions.size() * sizeof(int32_t));
+        return GS_OK;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    if (keys32 && h->n_entries) HIP_TRY(hipMemcpy(keys32, h->d_keys, (size_t)h->n_entries * 32, hipMemcpyDeviceToHost));
+    if (nodes && h->n_entries) HIP_TRY(hipMemcpy(nodes, h->d_nodes, (size_t)h->n_entries * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (regions && h->n_nodes) {
+        HIP_TRY(hipMemcpy(regions, h->d_regions, (size_t)h->n_nodes * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int32_t i = 0; i < h->n_nodes; i++) regions[i] += h->host_regions[(size_t)i];
+    }
+    return GS_OK;
+}
+GS_API_CATCH
+
+// node_out[n] (device) for the n header lines at d_headers / d_off (device)
+static int am_lookup_device(gs_accmap *h, const uint8_t *d_headers, const u64 *d_off, int64_t n, int complete_only, int32_t *d_out, hipStream_t stream) {
+    int rc = timer_start(h->timer, h->profile, stream);
+    if (rc) return rc;
+    HIP_TRY(gs_launch_accmap_lookup(d_headers, d_off, n, complete_only != 0, h->d_keys, h->d_nodes, h->n_entries, d_out, stream));
+    return timer_stop(h->timer, h->profile, stream);
+}
+
+extern "C" int gs_accmap_lookup(gs_accmap *h, const uint8_t *headers, const uint64_t *header_off, int64_t n, int mem, int complete_only,
+                                int32_t *node_out) try {
+    if (!h) return fail(GS_E_INVALID, "accmap is NULL");
+    if (n < 0) return fail(GS_E_INVALID, "n < 0");
+    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    if (!header_off || (n > 0 && (!headers || !node_out))) return fail(GS_E_INVALID, "NULL argument");
+    if (!h->finished) return fail(GS_E_STATE, "gs_accmap_lookup comes behind gs_accmap_finish");
+    if (n == 0) return GS_OK;
+    if (h->host_only) {  // gs_am_lookup_kernel, line by line
+        if (mem != GS_MEM_HOST) return fail(GS_E_UNSUPPORTED, "a host-only accession map looks up host memory alone");
+        for (int64_t i = 0; i < n; i++) {
+            const uint8_t *line = headers + header_off[i];
+            const size_t size = (size_t)(header_off[i + 1] - header_off[i]);
+            const uint8_t *blank = size ? (const uint8_t *)memchr(line, ' ', size) : nullptr;
+            node_out[i] = -1;
+            const int64_t len = blank ? blank - line - 1 : -1;
+            if (len < 0 || len > GS_AM_MAX_KEY) continue;
+            if (complete_only) {
+                bool ok = false;
+                for (const char *pre : {"AC_", "NC_", "NZ_", "NM_", "XM_", "NR_", "XR_"}) ok = ok || (len >= 3 && memcmp(line + 1, pre, 3) == 0);
+                if (!ok) continue;
+            }
+            uint8_t probe[32] = {(uint8_t)len};
+            memcpy(probe + 1, line + 1, (size_t)len);
+            int64_t lo = 0, hi = h->n_entries;
+            while (lo < hi) {
+                const int64_t mid = (lo + hi) >> 1;
+                if (memcmp(h->h_keys.data() + 32 * (size_t)mid, probe, 32) < 0)
+                    lo = mid + 1;
+                else
+                    hi = mid;
+            }
+            if (lo < h->n_entries && memcmp(h->h_keys.data() + 32 * (size_t)lo, probe, 32) == 0) node_out[i] = h->h_nodes[(size_t)lo];
+        }
+        return GS_OK;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    int rc;
+    if (mem == GS_MEM_DEVICE) {
+        if ((rc = am_lookup_device(h, headers, (const u64 *)header_off, n, complete_only, node_out, h->stream))) return rc;
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        return timer_collect(h->timer);
+    }
+    for (int64_t i = 0; i < n; i++)
+        if (header_off[i + 1] < header_off[i]) return fail(GS_E_INVALID, "header_off must ascend");
+    const size_t n_bytes = (size_t)(header_off[n] - header_off[0]);
+    uint8_t *d_headers = nullptr;
+    u64 *d_off = nullptr;
+    int32_t *d_out = nullptr;
+    hipError_t e = gs_dev_alloc(&d_headers, std::max<size_t>(n_bytes, 1));
+    if (e == hipSuccess) e = gs_dev_alloc(&d_off, ((size_t)n + 1) * sizeof(u64));
+    if (e == hipSuccess) e = gs_dev_alloc(&d_out, (size_t)n * sizeof(int32_t));
+    std::vector<u64> off0((size_t)n + 1);  // the offsets from 0: the copy holds the header bytes alone
+    for (int64_t i = 0; i <= n; i++) off0[(size_t)i] = header_off[i] - header_off[0];
+    if (e == hipSuccess && n_bytes) e = hipMemcpyAsync(d_headers, headers + header_off[0], n_bytes, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_off, off0.data(), ((size_t)n + 1) * sizeof(u64), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // (off0 is a local)
+    rc = e == hipSuccess ? am_lookup_device(h, d_headers, d_off, n, complete_only, d_out, h->stream) : hip_fail(e, "gs_accmap_lookup");
+    if (!rc) {
+        e = hipMemcpyAsync(node_out, d_out, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) rc = hip_fail(e, "gs_accmap_lookup");
+    } else {
+        hipStreamSynchronize(h->stream);
+    }
+    gs_dev_free(d_headers);
+    gs_dev_free(d_off);
+    gs_dev_free(d_out);
+    return rc ? rc : timer_collect(h->timer);
+}
+GS_API_CATCH
+
+extern "C" int gs_accmap_lookup_genomes(gs_accmap *h, gs_genomes *g, int complete_only, int32_t *node_out) try {
+    if (!h || !g) return fail(GS_E_INVALID, "NULL argument");
+    if (!h->finished) return fail(GS_E_STATE, "gs_accmap_lookup_genomes comes behind gs_accmap_finish");
+    if (h->host_only) return fail(GS_E_UNSUPPORTED, "a host-only accession map looks up host memory alone");
+    if (g->state < 1) return fail(GS_E_STATE, "gs_accmap_lookup_genomes comes behind a gs_genomes_scan that took its chunk");
+    if (g->device != h->device) return fail(GS_E_INVALID, "the genomes handle lives on another device");
+    if (g->n_records == 0) return GS_OK;
+    if (!node_out) return fail(GS_E_INVALID, "node_out is NULL");
+    GsGenomesParams P{};
+    int rc = gn_device_headers(g, &P);
+    if (rc) return rc;
+    int32_t *d_out = nullptr;
+    HIP_TRY(gs_dev_alloc(&d_out, (size_t)g->n_records * sizeof(int32_t)));
+    // (on the genomes handle's stream, behind its header kernel; the map is at rest once finished)
+    rc = am_lookup_device(h, g->d_hdr, (const u64 *)P.hdr_off, g->n_records, complete_only, d_out, g->stream);
+    hipError_t e = rc ? hipSuccess : hipMemcpyAsync(node_out, d_out, (size_t)g->n_records * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
+    gs_dev_free(d_out);
+    if (rc) return rc;
+    if (e != hipSuccess) return hip_fail(e, "gs_accmap_lookup_genomes");
+    return timer_collect(h->timer);
+}
+GS_API_CATCH
+
+extern "C" int gs_accmap_kernel_time(gs_accmap *h, int profile, int64_t *launches, double *total_ms) try {
+    if (!h) return fail(GS_E_INVALID, "accmap is NULL");
+    if (h->host_only) {
+        if (launches) *launches = 0;
+        if (total_ms) *total_ms = 0;
+        return GS_OK;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    int rc = timer_collect(h->timer);
+    if (rc) return rc;
+    h->profile = profile != 0;
+    if (launches) *launches = h->timer.launches;
+    if (total_ms) *total_ms = h->timer.total_ms;
+    return GS_OK;
+}
+GS_API_CATCH

@@ -7,6 +7,7 @@
 #include "gs_chunk.h"
 #include "gs_krakenparse.h"
 #include "gs_genomeparse.h"
+#include "gs_accmapparse.h"
 
 #include "gs_control.h"
 
@@ -3599,6 +3600,207 @@ extern "C" int gs_host_kraken_count_files(int device, const char *const *paths, 
     return hfail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
 }
 
+// ---- RefSeq catalog files to the accession map (AccessionFileProcessor.processCatalog under AccessionMapSizeGoal / AccessionMapGoal;
+// gs_accmap on the device, gs_accmapparse.h for what it refuses)
+namespace {
+
+struct AmGuard {
+    gs_accmap *&am;
+    ~AmGuard() {
+        if (am) gs_accmap_destroy(am);
+        am = nullptr;
+    }
+};
+
+struct AmCtx {
+    gs_accmap *am = nullptr;  // the device's map, or (GS_HOST_FAST=0) a host-only one
+    bool keep = true;         // count_only == 0: entries go into am
+    AccmapExact exact;        // the line-by-line parser: its buffer and line number live across a file
+    int64_t flushed_passing = 0, dev_lines = 0;
+    gs_host_accmap_totals tot{};
+    int prog_file = 0;
+    int64_t prog_lines0 = 0;
+    std::vector<uint8_t> slots;
+    std::vector<int32_t> nodes;
+    int64_t lines() const { return exact.lines + dev_lines; }
+    bool report(int64_t pos, bool gz) {
+        if (!trk().chunk(prog_file, pos, gz, lines() - prog_lines0)) return false;
+        trk().stopped(prog_file, lines() - prog_lines0);
+        return true;
+    }
+};
+
+// what the parser has made since the last call goes into the map, in input order
+int am_flush(AmCtx &c, const std::string &path) {
+    const int64_t passing = c.exact.passing - c.flushed_passing;
+    c.flushed_passing = c.exact.passing;
+    c.tot.passing += passing;
+    c.tot.put += (int64_t)c.exact.entries.size();
+    if (c.keep) {
+        const size_t n = c.exact.entries.size();
+        c.slots.assign(32 * n + 32, 0);
+        c.nodes.assign(n + 1, 0);
+        for (size_t i = 0; i < n; i++) {
+            const std::string &key = c.exact.entries[i].key;
+            bool fits = key.size() <= 31;
+            for (unsigned char b : key) fits = fits && b < 0x80;
+            if (!fits) return hfail(GS_E_UNSUPPORTED, path + ": the accession '" + key + "' does not fit a key slot (31 bytes below 0x80)");
+            c.slots[32 * i] = (uint8_t)key.size();
+            memcpy(c.slots.data() + 32 * i + 1, key.data(), key.size());
+            c.nodes[i] = c.exact.entries[i].node;
+        }
+        if (gs_accmap_append(c.am, c.slots.data(), c.nodes.data(), (int64_t)n, passing) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
+    }
+    c.exact.entries.clear();
+    return GS_OK;
+}
+
+int am_feed(AmCtx &c, const std::string &path, const uint8_t *p, size_t n, bool last) {
+    if (!c.exact.feed(p, n, last)) return hfail(GS_E_INVALID, path + ": line " + std::to_string((long long)c.exact.line_no) + ": " + c.exact.error);
+    return am_flush(c, path);
+}
+
+// the rest of a stream, line by line: the file from `offset` on, or a memory range that ends the stream
+int am_cpu(AmCtx &c, const std::string &path, int64_t offset, const uint8_t *mem, size_t mem_n) {
+    c.tot.host_chunks++;
+    if (mem) {
+        const int err = am_feed(c, path, mem, mem_n, true);
+        return err ? err : c.report(0, false) ? cancelled_rc() : (int)GS_OK;
+    }
+    LineReader lr;
+    if (!lr.open(path, offset)) return hfail(GS_E_IO, "cannot open " + path);
+    std::vector<uint8_t> text;
+    for (bool eof = false; !eof;) {  // whole lines, some MiB at a time
+        text.clear();
+        while (text.size() < ((size_t)4 << 20)) {
+            if (lr.next_line(text) == 0) {
+                eof = true;
+                break;
+            }
+        }
+        // (next_line drops NUL bytes as the parser would; a final line without its newline is the stream's last)
+        if (!text.empty() && text.back() != '\n') eof = true;
+        const int err = am_feed(c, path, text.data(), text.size(), eof);
+        if (err) return err;
+        if (c.report(lr.raw_pos(), false)) return cancelled_rc();
+    }
+    return GS_OK;
+}
+
+// One file through the device: chunks that end behind a newline are scanned there; one that the device refuses goes through the
+// parser and its entries are appended, so the input order stays; the stream goes on behind it on the device.  A line that does not
+// fit a block sends the rest of the file through the parser; so does the unterminated tail.
+int am_device_file(AmCtx &c, const std::string &path, bool gzip) {
+    size_t block;
+    int readers = 0;
+    reader_shape(gzip, &block, &readers);
+    TextReader tr;
+    int err = tr.open(path, block, readers, gzip);
+    if (err) {
+        tr.close();
+        return err;
+    }
+    ChunkCutter cut;
+    cut.mode = ChunkCutter::LINES;
+    int64_t fallback_off = -1;
+    tr.start();
+    for (int64_t i = 0; !err; i++) {
+        TextSlot &sl = tr.wait_full(i);
+        if ((err = block_error(tr, sl, path))) break;
+        const bool eof = sl.eof;
+        const ChunkCutter::Cut what = cut_block(cut, tr, sl);
+        if (what == ChunkCutter::FALLBACK) {
+            fallback_off = cut.file_off;
+        } else if (what == ChunkCutter::CHUNK && cut.bytes > 0) {
+            int64_t rep[8];
+            if (gs_accmap_submit(c.am, cut.start, cut.bytes, GS_MEM_HOST, 0, rep) != GS_OK) {
+                err = hfail(GS_E_HIP, gs_last_error());
+                break;
+            }
+            if (rep[3] != 0) {  // refused: this chunk line by line
+                c.tot.host_chunks++;
+                err = am_feed(c, path, cut.start, (size_t)cut.bytes, false);
+            } else {
+                c.tot.device_chunks++;
+                c.dev_lines += rep[0];
+                c.tot.passing += rep[1];
+                c.tot.put += rep[2];
+                c.exact.line_no += rep[0];
+                c.exact.note_chunk(cut.start, (size_t)cut.bytes);  // (a later line of fewer than five tabs reads what these left behind)
+            }
+            cut.commit();
+            if (!err && c.report(cut.file_off, gzip)) err = cancelled_rc();  // (the record is out: the block may go back)
+        } else if (what == ChunkCutter::CHUNK) {
+            cut.commit();
+        }
+        tr.release(i);
+        if (eof || fallback_off >= 0) break;
+    }
+    tr.close();
+    if (err) return err;
+    if (fallback_off >= 0) return am_cpu(c, path, fallback_off, nullptr, 0);
+    if (!cut.carry.empty()) return am_cpu(c, path, 0, cut.carry.data(), cut.carry.size());
+    return GS_OK;
+}
+
+}  // namespace
+
+extern "C" int gs_host_accmap_files(const char *const *paths, int n_paths, int device, const gs_accmap_cfg *cfg, int count_only, gs_accmap **out,
+                                    gs_host_accmap_totals *totals) try {
+    if (out) *out = nullptr;
+    if (!paths || n_paths < 0 || !cfg || (!count_only && !out)) return hfail(GS_E_INVALID, "NULL argument");
+    for (int f = 0; f < n_paths; f++)
+        if (!paths[f]) return hfail(GS_E_INVALID, "NULL path");
+    bool fast = true;
+    if (const char *e = getenv("GS_HOST_FAST")) fast = atoi(e) != 0;
+    const double t_start = now_s();
+    AmCtx c;
+    AmGuard guard{c.am};
+    c.keep = !count_only;
+    // (the handle checks cfg; a host-only one, device -1, touches no device)
+    if (const int rc = gs_accmap_create(&c.am, fast ? device : -1, cfg)) return hfail(rc, gs_last_error());
+    c.exact.dna = cfg->dna != 0;
+    c.exact.rna = cfg->rna != 0;
+    c.exact.mrna = cfg->mrna != 0;
+    c.exact.categories.assign(cfg->categories, cfg->categories + cfg->n_categories);
+    c.exact.statuses.assign(cfg->statuses, cfg->statuses + cfg->n_statuses);
+    if (cfg->n_nodes) c.exact.known.assign(cfg->known_taxids, cfg->known_taxids + cfg->n_nodes);
+    int err = GS_OK;
+    TrackerScope progress(paths, n_paths);
+    Tracker &tk = progress.t;
+    for (int f = 0; f < n_paths && !err; f++) {
+        const std::string path(paths[f]);
+        c.exact.begin_stream();  // every file is a stream of its own, all of them go into one map
+        c.prog_file = f;
+        c.prog_lines0 = c.lines();
+        if (tk.file_start(f)) {
+            tk.stopped(f, 0);
+            err = cancelled_rc();
+            break;
+        }
+        const int kind = fast ? text_path_kind(path) : 0;
+        err = kind ? am_device_file(c, path, kind == 2 || kind == 4) : am_cpu(c, path, 0, nullptr, 0);
+        if (!err && tk.file_end(f, c.lines() - c.prog_lines0)) err = cancelled_rc();
+    }
+    if (!err && tk.close()) err = cancelled_rc();
+    c.tot.lines = c.lines();
+    if (!err && !count_only) {
+        int64_t info[4];
+        if (gs_accmap_finish(c.am, info) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
+        *out = c.am;
+        c.am = nullptr;  // (the caller's now)
+    }
+    if (totals) {
+        c.tot.seconds_total = now_s() - t_start;
+        *totals = c.tot;
+    }
+    return err;
+} catch (const std::bad_alloc &) {
+    return hfail(GS_E_NOMEM, "out of host memory");
+} catch (const std::exception &e) {
+    return hfail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
+}
+
 // ---- genome FASTA files to regions (AbstractFastaReader.readFasta under the store readers; gs_genomes on the device)
 namespace {
 
@@ -3615,6 +3817,11 @@ struct GnCtx {
     gs_genome_resolve_fn resolve = nullptr;
     gs_genome_sink_fn sink = nullptr;
     void *resolve_user = nullptr, *sink_user = nullptr;
+    // gs_host_genome_files_mapped: the map looks the header lines up, the resolver sees one node per record
+    gs_accmap *am = nullptr;
+    int complete_only = 0;
+    gs_genome_resolve_nodes_fn resolve_nodes = nullptr;
+    std::vector<int32_t> node;
     int file = 0;
     int64_t first_record = 0;  // records of the file in front of the chunk
     gs_host_genome_totals tot{};
@@ -3630,13 +3837,23 @@ struct GnCtx {
     }
 };
 
-// the caller's decision for the n records of a chunk -> keep[n], kvi (vi of the kept ones); a callback's own code comes back as it is
+// the caller's decision for the n records of a chunk -> keep[n], kvi (vi of the kept ones); a callback's own code comes back as it is.
+// With a map: hdr == nullptr says that the header lines are those of the chunk c.g has scanned, and stay on the device
 int gn_resolve(GnCtx &c, int64_t n, const uint8_t *hdr, const uint64_t *hoff) {
     c.vi.assign((size_t)n, -1);
     c.keep.assign((size_t)n, 0);
     c.kvi.clear();
     if (n == 0) return 0;
-    const int rc = c.resolve(c.resolve_user, c.file, c.first_record, n, hdr, hoff, c.vi.data());
+    int rc;
+    if (c.am) {
+        c.node.assign((size_t)n, -1);
+        rc = hdr ? gs_accmap_lookup(c.am, hdr, hoff, n, GS_MEM_HOST, c.complete_only, c.node.data())
+                 : gs_accmap_lookup_genomes(c.am, c.g, c.complete_only, c.node.data());
+        if (rc) return hfail(rc, gs_last_error());
+        rc = c.resolve_nodes(c.resolve_user, c.file, c.first_record, n, c.node.data(), c.vi.data());
+    } else {
+        rc = c.resolve(c.resolve_user, c.file, c.first_record, n, hdr, hoff, c.vi.data());
+    }
     if (rc) return rc;
     for (int64_t i = 0; i < n; i++)
         if (c.vi[(size_t)i] >= 0) {
@@ -3684,10 +3901,14 @@ int gn_chunk(GnCtx &c, const uint8_t *p, int64_t n) {
     c.tot.chunks++;
     c.tot.text_bytes += used;
     c.tot.max_line_bytes = std::max(c.tot.max_line_bytes, ml);
-    c.hdr.resize((size_t)hb + 1);
-    c.hoff.resize((size_t)nr + 1);
-    if ((rc = gs_genomes_headers(c.g, c.hdr.data(), c.hoff.data()))) return hfail(rc, gs_last_error());
-    if ((rc = gn_resolve(c, nr, c.hdr.data(), c.hoff.data())) || c.kvi.empty()) return rc;
+    if (c.am) {  // the header lines never leave the device
+        if ((rc = gn_resolve(c, nr, nullptr, nullptr)) || c.kvi.empty()) return rc;
+    } else {
+        c.hdr.resize((size_t)hb + 1);
+        c.hoff.resize((size_t)nr + 1);
+        if ((rc = gs_genomes_headers(c.g, c.hdr.data(), c.hoff.data()))) return hfail(rc, gs_last_error());
+        if ((rc = gn_resolve(c, nr, c.hdr.data(), c.hoff.data())) || c.kvi.empty()) return rc;
+    }
     int64_t n_regions = 0, n_bases = 0;
     const uint8_t *d_seq = nullptr;
     const uint64_t *d_off = nullptr;
@@ -3798,20 +4019,16 @@ int gn_device_file(GnCtx &c, const std::string &path, bool gzip) {
 
 }  // namespace
 
-extern "C" int gs_host_genome_files(const char *const *paths, int n_paths, int device, gs_genome_resolve_fn resolve, void *resolve_user,
-                                    gs_genome_sink_fn sink, void *sink_user, gs_host_genome_totals *totals) try {
-    if (!paths || n_paths < 0 || !resolve || !sink) return hfail(GS_E_INVALID, "NULL argument");
+namespace {
+
+// the walk over the files behind both front ends; c holds the resolver (header lines, or a map and nodes) and the sink
+int gn_files(GnCtx &c, const char *const *paths, int n_paths, int device, gs_host_genome_totals *totals) {
     for (int f = 0; f < n_paths; f++)
         if (!paths[f]) return hfail(GS_E_INVALID, "NULL path");
     bool fast = true;
     if (const char *e = getenv("GS_HOST_FAST")) fast = atoi(e) != 0;
     const double t_start = now_s();
-    GnCtx c;
     GnGuard guard{c.g};
-    c.resolve = resolve;
-    c.resolve_user = resolve_user;
-    c.sink = sink;
-    c.sink_user = sink_user;
     if (fast && gs_genomes_create(&c.g, device) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
     int err = GS_OK;
     TrackerScope progress(paths, n_paths);
@@ -3833,6 +4050,37 @@ extern "C" int gs_host_genome_files(const char *const *paths, int n_paths, int d
     c.tot.seconds_total = now_s() - t_start;
     if (totals) *totals = c.tot;
     return err;
+}
+
+}  // namespace
+
+extern "C" int gs_host_genome_files(const char *const *paths, int n_paths, int device, gs_genome_resolve_fn resolve, void *resolve_user,
+                                    gs_genome_sink_fn sink, void *sink_user, gs_host_genome_totals *totals) try {
+    if (!paths || n_paths < 0 || !resolve || !sink) return hfail(GS_E_INVALID, "NULL argument");
+    GnCtx c;
+    c.resolve = resolve;
+    c.resolve_user = resolve_user;
+    c.sink = sink;
+    c.sink_user = sink_user;
+    return gn_files(c, paths, n_paths, device, totals);
+} catch (const std::bad_alloc &) {
+    return hfail(GS_E_NOMEM, "out of host memory");
+} catch (const std::exception &e) {
+    return hfail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
+}
+
+extern "C" int gs_host_genome_files_mapped(const char *const *paths, int n_paths, int device, gs_accmap *am, int complete_only,
+                                           gs_genome_resolve_nodes_fn resolve, void *resolve_user, gs_genome_sink_fn sink, void *sink_user,
+                                           gs_host_genome_totals *totals) try {
+    if (!paths || n_paths < 0 || !am || !resolve || !sink) return hfail(GS_E_INVALID, "NULL argument");
+    GnCtx c;
+    c.am = am;
+    c.complete_only = complete_only;
+    c.resolve_nodes = resolve;
+    c.resolve_user = resolve_user;
+    c.sink = sink;
+    c.sink_user = sink_user;
+    return gn_files(c, paths, n_paths, device, totals);
 } catch (const std::bad_alloc &) {
     return hfail(GS_E_NOMEM, "out of host memory");
 } catch (const std::exception &e) {

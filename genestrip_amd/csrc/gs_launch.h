@@ -246,6 +246,18 @@ hipError_t gs_size_sort_bytes(int64_t n, int key_bits, size_t *tmp_bytes);
 hipError_t gs_size_sort(u64 *keys, u64 *keys_alt, int64_t n, int key_bits, void *tmp, size_t tmp_bytes, u64 **keys_out, hipStream_t stream);
 hipError_t gs_launch_size_heads(const u64 *keys, int64_t n, int radix_bits, u64 *n_distinct, u64 *buckets, int n_cu, hipStream_t stream);
 
+// ---- gs_accmap.hip: RefSeq catalog lines -> accession map
+hipError_t gs_launch_accmap_count(const GsAccmapParams *P, hipStream_t stream);
+hipError_t gs_launch_accmap_write(const GsAccmapParams *P, hipStream_t stream);
+hipError_t gs_accmap_sort_bytes(int64_t n, size_t *tmp_bytes);
+// entries [0, n) by key, ties in input order: keys_out / nodes_out / seq_out take them sorted; word / word_alt / seq_alt: n each;
+// flag: one word of device memory; counts: [2] adjacent equal keys, those of them with different nodes
+hipError_t gs_accmap_sort_entries(const uint8_t *keys, const int32_t *nodes, int64_t n, u64 *word, u64 *word_alt, uint32_t *seq, uint32_t *seq_alt,
+                            void *tmp, size_t tmp_bytes, uint32_t *flag, uint8_t *keys_out, int32_t *nodes_out, uint32_t **seq_out, u64 *counts,
+                            hipStream_t stream);
+hipError_t gs_launch_accmap_lookup(const uint8_t *headers, const u64 *header_off, int64_t n, int complete_only, const uint8_t *keys,
+                                   const int32_t *nodes, int64_t n_entries, int32_t *node_out, hipStream_t stream);
+
 }  // extern "C"
 
 // ---- gs_devcache.cpp: the device block cache.  Every device allocation of gs_api.cpp goes through these two, by name; hidden,

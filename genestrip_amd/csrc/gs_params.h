@@ -382,3 +382,39 @@ struct GsGenomesParams {
     unsigned long long *off;      // kept + 1: the regions' offsets
     uint8_t *seq;                 // their bases
 };
+
+// ---- gs_accmap.hip: RefSeq catalog lines -> accession map (the accmapsize / accmap goals)
+#define GS_AM_TILE 4096       // bytes per scan block: GS_SCAN_BLOCK threads, 16 bytes each
+#define GS_AM_MAX_LINE 2048   // bytes of a line with its newline beyond which AccessionFileProcessor throws
+#define GS_AM_MAX_KEY 31      // accession bytes a 32-byte slot holds behind its length byte
+#define GS_AM_MAX_PATTERNS 16 // category strings, and status strings
+#define GS_AM_MAX_PATTERN 32  // bytes of one of them
+#define GS_AM_NONE 0xffffffffu
+enum { GS_AM_BAD_LINE = 0,    // status: first line outside the grammar (GS_AM_NONE: none)
+       GS_AM_LONGEST = 1,     // the longest line, its newline included
+       GS_AM_WORDS = 2 };
+enum { GS_AM_C_LINES = 0, GS_AM_C_PASSING = 1, GS_AM_C_PUT = 2, GS_AM_C_WORDS = 4 };  // the chunk's counters
+struct GsAccmapPatterns {     // [0 .. n_cat): categories, [GS_AM_MAX_PATTERNS .. GS_AM_MAX_PATTERNS + n_stat): statuses
+    uint8_t len[2 * GS_AM_MAX_PATTERNS];
+    uint8_t text[2 * GS_AM_MAX_PATTERNS][GS_AM_MAX_PATTERN];
+};
+struct GsAccmapParams {
+    const uint8_t *text;          // n_bytes of whole lines, zero bytes behind them up to n_tiles * GS_AM_TILE + 64
+    int64_t n_bytes, n_tiles;
+    int32_t last;                 // != 0: the stream ends with this chunk, whose final line need not be terminated
+    int32_t dna, rna, mrna;       // the accession prefixes that pass
+    int32_t n_cat, n_stat;
+    const GsAccmapPatterns *pat;
+    const int32_t *known;         // n_nodes tax ids, ascending
+    int32_t n_nodes, pad;
+    unsigned long long *tile_lt;  // per tile: newlines | tabs << 32, then their exclusive prefix (gs_launch_scan_blocks)
+    uint32_t *tile_tail;          // per tile: (offset of its last newline + 1, 0: none) | tabs behind that newline << 16
+    unsigned long long *tile_put; // per tile: entries it puts, then their exclusive prefix
+    unsigned long long *scan_tot; // [2] the sums
+    uint32_t *status;             // GS_AM_WORDS
+    unsigned long long *chunk;    // GS_AM_C_WORDS
+    uint8_t *keys;                // the write pass: 32-byte slots, entry_cap of them ...
+    int32_t *nodes;               // ... their nodes
+    int64_t first_entry, entry_cap;  // the chunk's first entry goes to slot first_entry
+    int32_t *regions;             // n_nodes: entries per node
+};

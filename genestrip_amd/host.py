@@ -61,6 +61,8 @@ def lib():
         "gs_host_write_quality_csv": (ci, [C.c_char_p, vp, vp, vp]),
         "gs_host_kraken_count_files": (ci, [ci, vp, ci, vp, ci, C.c_char_p, vp, C.c_int32, vp, i64, vp, vp]),
         "gs_host_genome_files": (ci, [vp, ci, ci, vp, vp, vp, vp, vp]),
+        "gs_host_accmap_files": (ci, [vp, ci, ci, vp, ci, vp, vp]),
+        "gs_host_genome_files_mapped": (ci, [vp, ci, ci, vp, ci, vp, vp, vp, vp, vp]),
         "gs_host_write_kraken_csv": (ci, [C.c_char_p, vp, C.c_int32, vp, i64]),
         "gs_host_db2fastq": (ci, [vp, vp, C.c_char_p, C.c_int32, ci, C.c_char_p, vp]),
         "gs_host_last_error": (C.c_char_p, []), "gs_host_java_double": (ci, [C.c_double, vp, ci]),
@@ -470,11 +472,12 @@ class GenomeTotals(C.Structure):
 
 
 _RESOLVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
+_RESOLVE_NODES_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p)
 _SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int)
 _CALLBACK_RAISED = -1000
 
 
-def genome_files(paths, resolve, sink, device=0):
+def genome_files(paths, resolve, sink, device=0, _mapped=None):
     """gs_host_genome_files: genome FASTA files (plain, gzip, BGZF) -> the regions of a build.  resolve(file, first_record, headers)
     gets the header lines (a list of bytes, '>' included) of a batch of records and returns one value index per record (< 0: skip),
     or a non-zero int as its error code; sink(seq, offsets, vi) gets the kept regions -- seq / offsets as device views or numpy
@@ -516,14 +519,65 @@ def genome_files(paths, resolve, sink, device=0):
             raised.append(e)
             return _CALLBACK_RAISED
 
+    def _resolve_nodes(_user, file, first, n, node, vi):
+        try:
+            got = resolve(file, first, np.ctypeslib.as_array(C.cast(node, C.POINTER(C.c_int32)), (n,)).copy())
+            if isinstance(got, (int, np.integer)) and not isinstance(got, bool):
+                return int(got)
+            got = np.ascontiguousarray(got, dtype=np.int32)
+            if len(got) != n:
+                raise ValueError("resolve must return one value index per record")
+            C.memmove(vi, got.ctypes.data, 4 * n)
+            return 0
+        except BaseException as e:  # noqa: BLE001
+            raised.append(e)
+            return _CALLBACK_RAISED
+
     paths = [os.fspath(p) for p in paths]
     arr, n = _cstr_array(paths), len(paths)
     t = GenomeTotals()
-    r_fn, s_fn = _RESOLVE_FN(_resolve), _SINK_FN(_sink)
-    rc = lib().gs_host_genome_files(arr, n, device, r_fn, None, s_fn, None, C.byref(t))
+    s_fn = _SINK_FN(_sink)
+    if _mapped is None:
+        r_fn = _RESOLVE_FN(_resolve)
+        rc = lib().gs_host_genome_files(arr, n, device, r_fn, None, s_fn, None, C.byref(t))
+    else:
+        r_fn = _RESOLVE_NODES_FN(_resolve_nodes)
+        rc = lib().gs_host_genome_files_mapped(arr, n, device, _mapped[0].h, int(bool(_mapped[1])), r_fn, None, s_fn, None, C.byref(t))
     if raised:
         raise raised[0]
     if rc > 0 or rc < CANCELLED:
         raise _b.GsError(rc, "a callback of genome_files ended the walk with this code")
     _check(rc, totals=t)
     return t
+
+
+def genome_files_mapped(paths, accession_map, resolve, sink, complete_only=False, device=0):
+    """gs_host_genome_files_mapped: genome_files with an accession map (genestrip_amd.DeviceAccessionMap, finished) in front of the
+    resolver.  The header lines of a chunk are looked up on the device, where the scan left them; resolve(file, first_record, nodes)
+    gets one node per record (int32 array, -1: none) instead of header text and returns one value index per record as in
+    genome_files.  -> GenomeTotals"""
+    return genome_files(paths, resolve, sink, device=device, _mapped=(accession_map, complete_only))
+
+
+class AccmapTotals(C.Structure):
+    _fields_ = [("lines", C.c_int64), ("passing", C.c_int64), ("put", C.c_int64), ("device_chunks", C.c_int64), ("host_chunks", C.c_int64),
+                ("seconds_total", C.c_double)]
+
+
+def accmap_files(paths, known_taxids, categories, statuses, seq_type="GENOMIC", count_only=False, device=0, reserve_entries=0):
+    """gs_host_accmap_files: the accmapsize / accmap goals over RefSeq catalog files (plain, gzip, BGZF), all into one map ->
+    (DeviceAccessionMap or None if count_only, totals); totals["passing"] is the accmapsize number.  Chunks of whole lines are scanned
+    on the device, what it refuses by a line-by-line restatement of the reference; GS_HOST_FAST=0 sends everything through the latter
+    and gives a host-only map.  A stop on request raises Cancelled: no map."""
+    cfg, known = _b.DeviceAccessionMap.config(known_taxids, categories, statuses, seq_type, reserve_entries)
+    paths = [os.fspath(p) for p in paths]
+    tot = AccmapTotals()
+    h = C.c_void_p()
+    rc = lib().gs_host_accmap_files(_cstr_array(paths), len(paths), int(device), C.byref(cfg), int(bool(count_only)), C.byref(h), C.byref(tot))
+    totals = {f: getattr(tot, f) for f, _ in AccmapTotals._fields_}
+    _check(rc, totals=totals)
+    if count_only:
+        return None, totals
+    m = _b.DeviceAccessionMap._wrap(h, known)
+    m.n_entries, m.n_passing = totals["put"], totals["passing"]
+    return m, totals

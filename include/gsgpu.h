@@ -1083,6 +1083,71 @@ int gs_genomes_regions(gs_genomes *g, const uint8_t **d_seq, const uint64_t **d_
 int gs_genomes_kernel_time(gs_genomes *g, double *ms_scan, double *ms_gather);
 int gs_genomes_destroy(gs_genomes *g);
 
+/* ---------------------------------------------------------------------------------------------------
+ * accmap: lines of a RefSeq catalog to the accession map (genestrip_amd/csrc/gs_accmap.hip)
+ *
+ * Replaces AccessionFileProcessor.processCatalog (C/refseq/AccessionFileProcessor.java:96-131) under AccessionMapSizeGoal
+ * (C/goals/refseq/AccessionMapSizeGoal.java:70-103: the count of passing entries) and AccessionMapGoal
+ * (C/goals/refseq/AccessionMapGoal.java:82-114: the put of every passing entry whose tax id names a node), the sort of
+ * AccessionMapImpl.optimize (C/refseq/AccessionMapImpl.java:123-145) and the search of AccessionMapImpl.get (:59-74) under
+ * AbstractRefSeqFastaReader.updateNodeFromInfoLine (C/refseq/AbstractRefSeqFastaReader.java:228-239), for chunks of whole lines
+ * inside the grammar stated at the head of gs_accmap.hip.  A chunk outside it is REFUSED: it leaves the handle as it was, and the
+ * caller parses it line by line (genestrip_amd/csrc/gs_accmapparse.h) and hands its entries in through gs_accmap_append, so that
+ * the input order -- which decides among equal keys -- is kept.
+ *
+ * The tree reaches the handle as known_taxids[n_nodes]: ascending, distinct, positive.  A node is its index in that array; -1 is
+ * "none".  A key is a 32-byte slot: byte 0 the length of the accession (0..31), bytes 1..31 the accession, zero-padded.  Read as
+ * four big-endian 64-bit words, slots order as AccessionMapImpl.compareBytes orders keys (length, then bytes: all are below 0x80).
+ * The reference keeps equal keys and which of them a search finds depends on its quicksort; here gs_accmap_lookup answers with
+ * the entry that came FIRST in the input -- a deliberate choice.
+ *
+ * gs_accmap_create   cfg: the three prefix flags (SeqType GENOMIC: dna; RNA: rna; M_RNA: mrna; ALL_RNA: rna + mrna; ALL: all
+ *                    three), category and status strings (searched for as substrings of the fourth and fifth field; 1..32 bytes
+ *                    each, at most 16 of each kind, at least one of each), the tree, entries to make room for at once.
+ *                    device -1: a HOST-ONLY map, for callers without a device (include/gshost.h under GS_HOST_FAST=0): it touches
+ *                    no device, takes entries through gs_accmap_append alone (gs_accmap_submit and gs_accmap_lookup_genomes:
+ *                    GS_E_UNSUPPORTED), sorts and searches on the host and answers gs_accmap_lookup for host memory.
+ * gs_accmap_submit   text: n_bytes (at most 1 GiB) of whole lines in host or device memory (mem), free again on return.  last != 0:
+ *                    the stream ends here and its final line need not be terminated.  report: [0] lines, [1] passing entries (the
+ *                    accmapsize count), [2] entries put, [3] 1: refused (then [1] and [2] are 0 and the caller owes them),
+ *                    [4] the first bad line (0-based; -1: none), [5] the longest line with its newline, [6] [7] 0.
+ * gs_accmap_append   n entries made elsewhere: keys32 (n slots), nodes (n indices into known_taxids), host memory; n_passing: the
+ *                    passing entries of the same lines (those without a node included), added to the size count.
+ * gs_accmap_finish   sorts; info: [0] entries, [1] passing entries in all, [2] entries equal to the one in front of them,
+ *                    [3] those of them with another node.  Behind it submit and append are GS_E_STATE; in front of it fetch and
+ *                    the lookups are.
+ * gs_accmap_fetch    host arrays, any of them NULL: the sorted slots (32 * entries bytes), their nodes, regions[n_nodes] (entries per
+ *                    node: TaxIdNode.incRefSeqRegions).
+ * gs_accmap_lookup   n header lines headers[header_off[i] .. header_off[i + 1]) ('>' first; newline or not), mem: where headers,
+ *                    header_off and node_out live.  node_out[i]: the node of the accession [1, first blank), -1 if the line has no
+ *                    blank, if complete_only != 0 and the accession starts with none of AC_ NC_ NZ_ NM_ XM_ NR_ XR_, or if the
+ *                    map does not hold it.
+ * gs_accmap_lookup_genomes  the same over the header lines of the chunk that g has scanned (gs_genomes_scan; same device), which
+ *                    never leave the device; node_out: host, one per record.
+ * gs_accmap_kernel_time  profile != 0: from now on scan, finish and lookup run between events; what they add up to so far.
+ * NULL or negative arguments: GS_E_INVALID, before any device call.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct gs_accmap gs_accmap;
+typedef struct {
+    int32_t dna, rna, mrna;
+    int32_t n_categories, n_statuses;
+    int32_t n_nodes;
+    const char *const *categories;
+    const char *const *statuses;
+    const int32_t *known_taxids;
+    int64_t reserve_entries;
+} gs_accmap_cfg;
+int gs_accmap_create(gs_accmap **out, int device, const gs_accmap_cfg *cfg);
+int gs_accmap_submit(gs_accmap *am, const uint8_t *text, int64_t n_bytes, int mem, int last, int64_t report[8]);
+int gs_accmap_append(gs_accmap *am, const uint8_t *keys32, const int32_t *nodes, int64_t n, int64_t n_passing);
+int gs_accmap_finish(gs_accmap *am, int64_t info[4]);
+int gs_accmap_fetch(gs_accmap *am, uint8_t *keys32, int32_t *nodes, int32_t *regions);
+int gs_accmap_lookup(gs_accmap *am, const uint8_t *headers, const uint64_t *header_off, int64_t n, int mem, int complete_only, int32_t *node_out);
+int gs_accmap_lookup_genomes(gs_accmap *am, gs_genomes *g, int complete_only, int32_t *node_out);
+int gs_accmap_get_device(gs_accmap *am, int *device);
+int gs_accmap_kernel_time(gs_accmap *am, int profile, int64_t *launches, double *total_ms);
+int gs_accmap_destroy(gs_accmap *am);
+
 #ifdef __cplusplus
 }
 #endif

@@ -227,6 +227,35 @@ typedef struct {
 int gs_host_genome_files(const char *const *paths, int n_paths, int device, gs_genome_resolve_fn resolve, void *resolve_user,
                          gs_genome_sink_fn sink, void *sink_user, gs_host_genome_totals *totals);
 
+/* The accmapsize / accmap goals over RefSeq catalog files (AccessionFileProcessor.processCatalog, C/refseq/AccessionFileProcessor.java
+ * :96-131, under AccessionMapSizeGoal / AccessionMapGoal): every file (plain or gzip, BGZF included) is one stream, all of them go into
+ * one map.  Chunks of whole lines are scanned on the device (gs_accmap_submit, include/gsgpu.h); a chunk the device refuses, a line that
+ * does not fit a reader block with the rest of its file, the unterminated tail of a file and, under GS_HOST_FAST=0, everything go
+ * through the line-by-line restatement of the reference (genestrip_amd/csrc/gs_accmapparse.h), whose entries join the map in input
+ * order (gs_accmap_append).  Under GS_HOST_FAST=0 no device is used and *out is a host-only map (device -1: fetch and host lookups).
+ * count_only != 0 is the accmapsize goal: totals->passing is its number, no map is kept, *out is NULL (out may be NULL).  Otherwise
+ * *out is the finished map, the caller's to destroy.  Where the reference throws -- a line that does not fit its 2048-byte buffer, the
+ * put of an entry of two tabs -- the call fails with GS_E_INVALID and gs_host_last_error names the file and the 1-based line; an
+ * accession of more than 31 bytes, or with a byte from 0x80 on, in an entry that is put fails with GS_E_UNSUPPORTED naming it (RefSeq
+ * has none).  Progress records count lines; on GS_E_CANCELLED no map is returned. */
+typedef struct {
+    int64_t lines, passing, put;         /* lines read; entries that pass (the accmapsize number); entries put into the map */
+    int64_t device_chunks, host_chunks;  /* chunks the device scanned; chunks (and rests of files) the line-by-line parser took */
+    double seconds_total;
+} gs_host_accmap_totals;
+int gs_host_accmap_files(const char *const *paths, int n_paths, int device, const gs_accmap_cfg *cfg, int count_only, gs_accmap **out,
+                         gs_host_accmap_totals *totals);
+
+/* gs_host_genome_files with an accession map in front of the resolver: the header lines of a chunk are looked up where the scan left
+ * them (gs_accmap_lookup_genomes; a chunk that went through the host parser: gs_accmap_lookup on its header lines, the same rule), and
+ * `resolve` gets node[n_records] (-1: none; AbstractRefSeqFastaReader.updateNodeFromInfoLine with completeGenomesOnly = complete_only)
+ * instead of header text and answers vi[] as before.  The same walk, totals, progress and cancellation.  am: a finished map; with
+ * GS_HOST_FAST=0 a host-only one. */
+typedef int (*gs_genome_resolve_nodes_fn)(void *user, int file, int64_t first_record, int64_t n_records, const int32_t *node, int32_t *vi);
+int gs_host_genome_files_mapped(const char *const *paths, int n_paths, int device, gs_accmap *am, int complete_only,
+                                gs_genome_resolve_nodes_fn resolve, void *resolve_user, gs_genome_sink_fn sink, void *sink_user,
+                                gs_host_genome_totals *totals);
+
 /* ---- progress and cancellation of the file-level calls (what the reference does through ExecutionContext.setFastqProgress /
  * setTotalProgress, C/fastq/AbstractLoggingFastqStreamer.java:161-209,247-252, and FastqReaderInterruptedException).
  * A control is attached to a THREAD (gs_host_control_attach); the file-level calls that thread makes afterwards -- gs_host_match_files,
