@@ -24,6 +24,7 @@
 #include "gs_launch.h"
 #include "gs_layout.h"
 #include "gs_params.h"
+#include "gs_prefilter.h"
 
 // ---------------------------------------------------------------------------------------------------
 // errors
@@ -134,6 +135,10 @@ struct gs_db {
     unsigned present = 0;                      // bit q: stripe q is known
     std::shared_ptr<struct StripeGroup> group; // all stripes in one process: they are freed with the last handle
     std::vector<void *> ipc_opened;            // stripes of other processes (hipIpcOpenMemHandle)
+    // the 15-mer filter of the store (gs_prefilter.h): both levels in one allocation (exact level first), built by the first run
+    // that may use it (db_ensure_prefilter) and never written to the store file
+    uint32_t *d_pf = nullptr;
+    int64_t pf_set = -1;  // |S|, the set bits of the exact level; -1: not built yet
     bool striped() const { return n_parts > 1; }
     bool complete() const { return n_parts <= 1 || present == (1u << n_parts) - 1u; }
 };
@@ -173,6 +178,7 @@ static void db_free(gs_db *db) {
     if (!db->striped()) gs_dev_free(db->d_table);  // (a stripe's table buckets live behind its record lines)
     gs_dev_free(db->d_gate);
     gs_dev_free(db->d_mgate);
+    gs_dev_free(db->d_pf);
     if (!db->group) gs_dev_free(db->d_rec);
     gs_dev_free(db->d_tree);
     delete db;
@@ -2217,6 +2223,16 @@ struct gs_run {
     // the page-locked copy and reused by every later batch of that length
     GsQuotTable *d_quot = nullptr, *h_quot = nullptr;
     hipEvent_t quot_copied = nullptr;  // the upload has left h_quot
+    // the prefilter in front of the FIXED loop (gs_prefilter.hip): pf_mode is GS_PREFILTER (-1: the enabling rule decides); the
+    // survivor count of a batch travels to a page-locked word (pf_h[slot], ~0 while the copy is under way) with the batch itself
+    int pf_mode = -1;
+    uint32_t *pf_h = nullptr;          // GS_PF_SLOTS words
+    int64_t pf_slot_reads[4] = {0, 0, 0, 0};
+    bool pf_slot_pending[4] = {false, false, false, false};
+    int64_t pf_batches = 0;            // prefiltered batches so far (the next one takes slot pf_batches % 4)
+    int pf_pause = 0;                  // batches that still go without the prefilter (the feedback rule)
+    int64_t pf_last_survivors = -1, pf_last_reads = 0;  // of the last submitted batch; survivors -1: it went without the prefilter
+    int pf_last_slot = -1;
     int quot_max = 0;                  // what the table was built for: positions (0: none yet) and the two gate settings
     double quot_tax = 0, quot_class = 0;
     int stat_copies = 1;         // > 1: global-atomic counters spread over several copies (GsMatchParams::stat_copies)
@@ -2753,6 +2769,7 @@ static void run_free(gs_run *run) {
     gs_dev_free(run->d_stat_rec_count);
     gs_dev_free(run->d_quot);
     hipHostFree(run->h_quot);
+    hipHostFree(run->pf_h);
     if (run->quot_copied) hipEventDestroy(run->quot_copied);
     gs_dev_free(run->d_route_cursors);
     gs_dev_free(run->d_bitmap);
@@ -2795,6 +2812,67 @@ static void run_free(gs_run *run) {
     delete run;
 }
 
+// ---- the sampled 15-mer prefilter (gs_prefilter.h) -- THE ENABLING RULE, all of it:
+// a store gets a filter, and a batch of m samples per read goes through it, only if a read of uniform random bases is predicted to
+// pass with a probability below GS_PF_MAX_PASS: 1 - (1 - |S| / 2^29)^m (2^29 canonical 15-mers exist).  GS_PREFILTER=0 / 1 overrides
+// the rule (read per run: tests and A/B runs take both paths from one library).  Striped and partitioned stores and stores without
+// records get no filter.  The feedback rule for streams that are mostly hits is next to it: a batch of which more than
+// GS_PF_HIT_RICH of the reads survived sends the next GS_PF_PAUSE batches straight to the match kernel.
+#define GS_PF_MAX_PASS 0.5
+#define GS_PF_HIT_RICH 0.85
+#define GS_PF_PAUSE 15
+#define GS_PF_SLOTS 4
+static bool prefilter_rule(const gs_db *db, int mode, int samples) {
+    if (mode == 0 || !db->d_pf || db->pf_set < 0) return false;
+    if (mode > 0) return true;
+    return 1.0 - std::pow(1.0 - (double)db->pf_set / (double)(1LL << 29), (double)samples) < GS_PF_MAX_PASS;
+}
+static bool prefilter_eligible(const gs_db *db) { return db->d_rec != nullptr && !db->striped() && db->n_parts <= 1 && db->info.k >= GS_MIN_K; }
+
+// builds the filter of a store that has none yet: one sweep over the record lines and the table, then the popcount of the exact level
+static int db_ensure_prefilter(gs_db *db, int mode) {
+    if (mode == 0 || db->pf_set >= 0 || !prefilter_eligible(db)) return GS_OK;
+    const size_t l1_words = (size_t)1 << (GS_PF_L1_BITS - 5);
+    hipStream_t stream = nullptr;
+    HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    u64 *d_count = nullptr;
+    u64 count = 0;
+    hipError_t e = gs_dev_alloc((void **)&db->d_pf, sizeof(uint32_t) * (GS_PF_L2_WORDS + l1_words));
+    if (e == hipSuccess) e = gs_dev_alloc((void **)&d_count, sizeof(u64));
+    if (e == hipSuccess) e = hipMemsetAsync(db->d_pf, 0, sizeof(uint32_t) * (GS_PF_L2_WORDS + l1_words), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_count, 0, sizeof(u64), stream);
+    if (e == hipSuccess) {
+        GsPrefilterBuildParams B{};
+        B.rec = db->d_rec;
+        B.n_rec = db->n_rec;
+        B.tab = db->d_table;
+        B.n_tab = db->info.n_buckets;
+        B.bucket_bits = db->dev.bucket_bits;
+        B.vbits = db->dev.vbits;
+        B.k = db->info.k;
+        B.l2 = db->d_pf;
+        B.l1 = db->d_pf + GS_PF_L2_WORDS;
+        B.count = (unsigned long long *)d_count;
+        e = gs_launch_prefilter_build(&B, db->n_cu, stream);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&count, d_count, sizeof(u64), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    gs_dev_free(d_count);
+    hipStreamDestroy(stream);
+    if (e != hipSuccess) {
+        gs_dev_free(db->d_pf);
+        db->d_pf = nullptr;
+        return hip_fail(e, "prefilter build");
+    }
+    db->pf_set = (int64_t)count;
+    // a store too dense for the rule at the fewest samples a batch can have (L = 128) keeps |S| and gives the memory back
+    if (!prefilter_rule(db, mode, gs_pf_samples(128, db->info.k))) {
+        gs_dev_free(db->d_pf);
+        db->d_pf = nullptr;
+    }
+    return GS_OK;
+}
+
 extern "C" int gs_match_begin(gs_run **out, gs_db *db, const gs_match_cfg *cfg) {
     if (!out || !db || !cfg) return fail(GS_E_INVALID, "NULL argument");
     *out = nullptr;
@@ -2803,9 +2881,16 @@ extern "C" int gs_match_begin(gs_run **out, gs_db *db, const gs_match_cfg *cfg) 
     if (!db->complete()) return fail(GS_E_STATE, "striped store: not every stripe is attached yet (gs_db_stripe_attach)");
     if (cfg->count_unique && db->unique_owner && !db->striped())
         return fail(GS_E_STATE, "this store already has an active unique-counting run (the seen bits live in the table)");
+    int pf_mode = -1;
+    if (const char *ev = getenv("GS_PREFILTER")) pf_mode = atoi(ev) != 0 ? 1 : 0;
+    {
+        const int prc = db_ensure_prefilter(db, pf_mode);
+        if (prc) return prc;
+    }
     gs_run *run = new gs_run();
     run->db = db;
     run->cfg = *cfg;
+    run->pf_mode = pf_mode;
     const size_t nv = (size_t)db->info.n_values;
     run->bitmap_words = (db->n_slots() + 31) / 32 + db->n_rec;  // one word per record bucket behind the table slots' bits
     hipError_t e = hipStreamCreateWithFlags(&run->stream, hipStreamNonBlocking);
@@ -3050,7 +3135,52 @@ static int launch_batch(gs_run *run, const uint8_t *d_seq, const uint64_t *d_off
     const bool no_queues = off_stride == 0 && !d_nodes && fixed_len - run->db->info.k + 1 <= 128 && !huge;
     if (!no_queues) HIP_TRY(hipMemsetAsync(run->d_long_count, 0, 6 * sizeof(unsigned int), run->stream));
     if (huge && (rc = ensure_huge(run, &P))) return rc;
+    // The batches of the FIXED loop, and only those, may go through the prefilter first: the match kernel then takes the survivors
+    // from the list (queue 0 of the long-read list, which such a batch does not use) and their number from the word behind the queue
+    // counters.  Results do not depend on which way a batch goes.
+    run->pf_last_survivors = -1;
+    run->pf_last_reads = n_reads;
+    run->pf_last_slot = -1;
+    bool prefilter = P.quot != nullptr && fixed_len - run->db->info.k + 1 >= 65 && !d_skip && no_queues &&
+                     prefilter_rule(run->db, run->pf_mode, gs_pf_samples(fixed_len, run->db->info.k));
+    if (prefilter && run->pf_mode < 0) {  // the feedback rule (a forced prefilter is not paused)
+        for (int i = 0; i < GS_PF_SLOTS; i++)
+            if (run->pf_slot_pending[i] && run->pf_h[i] != 0xffffffffu) {
+                run->pf_slot_pending[i] = false;
+                if ((double)run->pf_h[i] > GS_PF_HIT_RICH * (double)run->pf_slot_reads[i]) run->pf_pause = GS_PF_PAUSE;
+            }
+        if (run->pf_pause > 0) {
+            run->pf_pause--;
+            prefilter = false;
+        }
+    }
+    int pf_slot = -1;
+    if (prefilter) {
+        if (!run->pf_h) {
+            HIP_TRY(hipHostMalloc((void **)&run->pf_h, sizeof(uint32_t) * GS_PF_SLOTS, hipHostMallocDefault));
+            for (int i = 0; i < GS_PF_SLOTS; i++) run->pf_h[i] = 0;
+        }
+        HIP_TRY(hipMemsetAsync(run->d_long_count + 6, 0, sizeof(unsigned int), run->stream));
+    }
     if ((rc = timer_start(run->timer, run->cfg.profile != 0, run->stream))) return rc;
+    if (prefilter) {
+        GsPrefilterParams F{};
+        F.seq = d_seq;
+        F.n_reads = n_reads;
+        F.L = fixed_len;
+        F.k = run->db->info.k;
+        F.l2 = run->db->d_pf;
+        F.l1 = run->db->d_pf + GS_PF_L2_WORDS;
+        F.list = run->d_long_list;
+        F.count = run->d_long_count + 6;
+        F.class_vi = d_class;
+        F.flags = d_flags;
+        HIP_TRY(gs_launch_prefilter(&F, run->stream));
+        P.surv_list = run->d_long_list;
+        P.surv_count = run->d_long_count + 6;
+        pf_slot = (int)(run->pf_batches % GS_PF_SLOTS);
+        if (run->pf_slot_pending[pf_slot] && run->pf_h[pf_slot] == 0xffffffffu) pf_slot = -1;  // (its copy of four batches ago is still under way)
+    }
     if (run->cfg.count_unique && !d_nodes) {
         run->seen_dirty = true;
         run->bitmap_merged = false;
@@ -3071,6 +3201,17 @@ static int launch_batch(gs_run *run, const uint8_t *d_seq, const uint64_t *d_off
         HIP_TRY(gs_launch_stat_reduce(P.stat_recs, run->d_stat_rec_count, rec_room, run->db->info.n_values, run->d_sums, run->d_max,
                                       run->d_dsums, run->d_stat_vi, run->stream));
     if ((rc = timer_stop(run->timer, run->cfg.profile != 0, run->stream))) return rc;
+    if (prefilter) {
+        run->pf_batches++;
+        run->pf_last_survivors = 0;  // (known once the batch is through: gs_match_prefilter_info)
+        if (pf_slot >= 0) {
+            run->pf_h[pf_slot] = 0xffffffffu;
+            run->pf_slot_reads[pf_slot] = n_reads;
+            run->pf_slot_pending[pf_slot] = true;
+            run->pf_last_slot = pf_slot;
+            HIP_TRY(hipMemcpyAsync(run->pf_h + pf_slot, run->d_long_count + 6, sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+        }
+    }
     const int pos_fixed = fixed_len - run->db->info.k + 1;
     if (all_long && pos_fixed <= 256 && ((P.wide_mask >> (pos_fixed <= 192 ? 0 : 1)) & 1)) {  // the whole batch in trips of three / four sub-rounds
         HIP_TRY(gs_launch_match_wide(&P, pos_fixed <= 192 ? 3 : 4, run->db->n_cu, run->stream));
@@ -5732,6 +5873,27 @@ extern "C" int gs_match_max_counts(gs_run *run, int16_t *out) {
                 update(c, out + nv * (size_t)N);
             }
         }
+    }
+    return GS_OK;
+}
+
+// info[0]: 1 if the run's store holds a 15-mer filter; info[1]: |S| (-1: never built); info[2], info[3]: survivors and reads of the
+// last submitted batch (survivors -1: that batch went to the match kernel without the prefilter).  Synchronises.
+extern "C" int gs_match_prefilter_info(gs_run *run, int64_t *info) {
+    if (!run || !info) return fail(GS_E_INVALID, "NULL argument");
+    HIP_TRY(hipSetDevice(run->db->device));
+    HIP_TRY(hipStreamSynchronize(run->stream));
+    info[0] = run->db->d_pf != nullptr ? 1 : 0;
+    info[1] = run->db->pf_set;
+    info[2] = run->pf_last_survivors;
+    info[3] = run->pf_last_reads;
+    if (run->pf_last_survivors >= 0) {
+        uint32_t n = 0;
+        if (run->pf_last_slot >= 0)
+            n = run->pf_h[run->pf_last_slot];
+        else
+            HIP_TRY(hipMemcpy(&n, run->d_long_count + 6, sizeof(n), hipMemcpyDeviceToHost));
+        info[2] = (int64_t)n;
     }
     return GS_OK;
 }

@@ -907,13 +907,23 @@ __global__ __launch_bounds__(GS_BLOCK) __attribute__((amdgpu_waves_per_eu(GS_WAV
         // FIXED: the wave's trips are counted down on the scalar unit (gfx9 has no scalar 64-bit ordered compare: `r < n_reads` is two
         // spill-lane reads, a vector compare and a branch on vcc per read).  A batch holds fewer than 2^32 reads (launch_batch)
         uint32_t trips = 0;
-        if (FIXED && wave_id < n_reads) trips = (uint32_t)(n_reads - wave_id - 1) / (uint32_t)n_waves + 1u;
-        for (int64_t r = wave_id; FIXED ? trips != 0 : r < n_reads; r += n_waves, po += po_step, trips--) {
+        // Behind the prefilter (gs_prefilter.hip) the launch takes the reads of a list: trip i reads surv_list[i], and the list's length
+        // is in device memory as *P.skip is.  Wave-uniform like fixed_batch, from the kernel's arguments: scalar loads, no other kernel.
+        typedef const __attribute__((address_space(4))) uint32_t *GsSurvPtr;
+        int64_t n_trips = n_reads;
+        if (FIXED && P.surv_list != nullptr) n_trips = (int64_t)*(GsSurvPtr)P.surv_count;
+        if (FIXED && wave_id < n_trips) trips = (uint32_t)(n_trips - wave_id - 1) / (uint32_t)n_waves + 1u;
+        // (the list pointer stays in two scalar registers across the loop: read from the kernarg segment once per trip like the other
+        // parameters, the instruction stream of the GENERAL loop moved with it and GS_BENCH_OFFSETS=array lost 0.10 ms)
+        const GsSurvPtr sl0 = FIXED ? (GsSurvPtr)P.surv_list : nullptr;
+        for (int64_t t = wave_id; FIXED ? trips != 0 : t < n_reads; t += n_waves, po += po_step, trips--) {
             GsKernargPtr kp = kp0;
 #ifndef GS_KERNARG_HOISTED  // (experiment, DESIGN 8.1 "kernarg re-reads": let the compiler keep the parameters live across the loop)
             asm volatile("" : "+s"(kp));
 #endif
             const GsMatchParams &Q = *(const GsMatchParams *)kp;
+            int64_t r = t;
+            if (FIXED && sl0 != nullptr) r = (int64_t)sl0[t];
             u64 off;
             int L;
             if (FIXED) {

@@ -220,6 +220,10 @@ hipError_t gs_launch_export_fastq(const GsFastqParams *P, void *scratch, size_t 
 // ---- gs_index.hip: the index filter of a store (count pass: P->put == 0; put pass: P->put != 0)
 hipError_t gs_launch_index(const GsIndexParams *P, int n_cu, hipStream_t stream);
 
+// ---- gs_prefilter.hip: the 15-mer filter of a store (both levels and |S|), and the reads of a fixed-length batch that pass it
+hipError_t gs_launch_prefilter_build(const GsPrefilterBuildParams *P, int n_cu, hipStream_t stream);
+hipError_t gs_launch_prefilter(const GsPrefilterParams *P, hipStream_t stream);
+
 // ---- gs_quality.hip
 hipError_t gs_launch_quality_tag(uint32_t *vals, int64_t n, const uint32_t *leaf_of_region, int64_t n_regions, hipStream_t stream);
 hipError_t gs_quality_sort_leaf(uint32_t *leaf, uint32_t *leaf_alt, u64 *keys, u64 *keys_alt, int64_t n, int bits, uint32_t **leaf_out,

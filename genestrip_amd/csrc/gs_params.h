@@ -109,6 +109,10 @@ struct GsMatchParams {
     int32_t huge_min;                  // k-mer positions from which a read goes this way
     int32_t huge_chunk_min;            // k-mer positions per chunk at least (a multiple of 128)
     int32_t pad1;
+    // The FIXED loop of gs_match_kernel behind the prefilter (gs_prefilter.hip): trip i of the launch takes read surv_list[i], and
+    // there are *surv_count of them (both written by gs_pf_kernel on the same stream).  nullptr: every read of the batch, in order.
+    const uint32_t *surv_list;
+    const uint32_t *surv_count;
 };
 #define GS_HUGE_MIN (1 << 15)
 #define GS_HUGE_SLOTS 256       // (= GS_BLOCK: one thread per slot where the chunks are counted)
@@ -248,6 +252,29 @@ struct GsIndexParams {
     const int64_t *factors;         // n_hashes hash factors; Blocked: factors[0] = the seed
     unsigned long long *words;
     unsigned long long *count;      // selected k-mers (one atomic per wave)
+};
+
+// gs_prefilter.hip: the 15-mer filter of a store (gs_prefilter.h) ...
+struct GsPrefilterBuildParams {
+    const unsigned long long *rec;  // the store's record lines, n_rec of them
+    int64_t n_rec;
+    const unsigned long long *tab;  // its table buckets, n_tab of them
+    int64_t n_tab;
+    uint32_t bucket_bits, vbits;
+    int32_t k, pad;
+    uint32_t *l1, *l2;              // both levels, zeroed by the caller
+    unsigned long long *count;      // |S|: the set bits of the exact level (zeroed by the caller)
+};
+// ... and the test of a batch of one read length against it
+struct GsPrefilterParams {
+    const uint8_t *seq;             // n_reads reads of L bytes, back to back
+    int64_t n_reads;
+    int32_t L, k;
+    const uint32_t *l1, *l2;
+    uint32_t *list;                 // the reads that pass, in no order (room for n_reads)
+    uint32_t *count;                // how many (zeroed by the caller)
+    int32_t *class_vi;              // per-read outputs of the batch or nullptr: a rejected read gets -1 / 0 here
+    uint8_t *flags;
 };
 
 struct GsSegParams {

@@ -667,6 +667,14 @@ int gs_match_text_read_bounds(gs_run *run, uint64_t *bounds);
 
 /* accumulated device time of the match kernel launches since gs_match_begin (cfg.profile != 0) */
 int gs_match_kernel_time(gs_run *run, int64_t *launches, double *total_ms);
+
+/* The sampled 15-mer prefilter in front of batches of one read length (gs_match_submit_fixed, 128 .. k + 127 bases): a read none
+ * of whose sampled 15-mers occurs in a stored k-mer holds no stored k-mer and is kept off the match kernel.  The filter is a
+ * function of the store alone, built on the device by the first run on a store whose density allows it, and never part of the
+ * store file; results do not depend on it.  GS_PREFILTER=0 / 1 in the environment (read by gs_match_begin) forces it off / on.
+ * info[0]: 1 if the run's store holds a filter; info[1]: distinct canonical 15-mers of the store (-1: never counted);
+ * info[2], info[3]: survivors and reads of the last submitted batch (survivors -1: it went without the prefilter).  Synchronises. */
+int gs_match_prefilter_info(gs_run *run, int64_t *info);
 /* the device the run's store lives on (for helpers that work beside a run: gs_inflater_create) */
 int gs_match_get_device(gs_run *run, int *device);
 
