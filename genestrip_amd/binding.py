@@ -64,6 +64,9 @@ ABI_SYMBOLS = (
     "gs_genomes_destroy",
     "gs_accmap_create", "gs_accmap_submit", "gs_accmap_append", "gs_accmap_finish", "gs_accmap_fetch", "gs_accmap_lookup",
     "gs_accmap_lookup_genomes", "gs_accmap_get_device", "gs_accmap_kernel_time", "gs_accmap_destroy",
+    "gs_taxtree_create", "gs_taxtree_submit_nodes", "gs_taxtree_append_nodes", "gs_taxtree_finish_nodes", "gs_taxtree_submit_names", "gs_taxtree_append_names", "gs_taxtree_finish_times",
+    "gs_taxtree_fetch", "gs_taxtree_fetch_names", "gs_taxtree_select", "gs_taxtree_small", "gs_taxtree_read_taxids",
+    "gs_taxtree_get_device", "gs_taxtree_kernel_time", "gs_taxtree_destroy",
 )
 
 
@@ -273,6 +276,13 @@ def lib():
         "gs_accmap_append": (ci, [vp, vp, vp, i64, i64]), "gs_accmap_finish": (ci, [vp, vp]), "gs_accmap_fetch": (ci, [vp, vp, vp, vp]),
         "gs_accmap_lookup": (ci, [vp, vp, vp, i64, ci, ci, vp]), "gs_accmap_lookup_genomes": (ci, [vp, vp, ci, vp]),
         "gs_accmap_get_device": (ci, [vp, vp]), "gs_accmap_kernel_time": (ci, [vp, ci, vp, vp]), "gs_accmap_destroy": (ci, [vp]),
+        "gs_taxtree_create": (ci, [vp, ci]), "gs_taxtree_submit_nodes": (ci, [vp, vp, i64, ci, ci, vp]),
+        "gs_taxtree_append_nodes": (ci, [vp, vp, i64, ci, vp]), "gs_taxtree_finish_nodes": (ci, [vp, vp]),
+        "gs_taxtree_append_names": (ci, [vp, vp, i64, ci]), "gs_taxtree_submit_names": (ci, [vp, vp, i64, ci, ci, vp]),
+        "gs_taxtree_finish_times": (ci, [vp, vp]), "gs_taxtree_fetch": (ci, [vp, vp, vp, vp, vp, vp, vp]),
+        "gs_taxtree_fetch_names": (ci, [vp, vp, vp, i64]), "gs_taxtree_select": (ci, [vp, vp, i64, vp, i64, ci, vp, vp]),
+        "gs_taxtree_small": (ci, [vp, vp, ci, ci, vp, vp, vp, vp, vp]), "gs_taxtree_read_taxids": (ci, [vp, i64, vp, vp, vp, vp, i64]),
+        "gs_taxtree_get_device": (ci, [vp, vp]), "gs_taxtree_kernel_time": (ci, [vp, ci, vp, vp]), "gs_taxtree_destroy": (ci, [vp]),
         "gs_genomes_create": (ci, [vp, ci]), "gs_genomes_scan": (ci, [vp, vp, i64, ci, ci, vp, vp, vp, vp]),
         "gs_genomes_headers": (ci, [vp, vp, vp]), "gs_genomes_gather": (ci, [vp, vp, vp, vp]), "gs_genomes_regions": (ci, [vp, vp, vp]),
         "gs_genomes_kernel_time": (ci, [vp, vp, vp]), "gs_genomes_destroy": (ci, [vp]),
@@ -1927,4 +1937,170 @@ class DeviceAccessionMap:
         """(launches, milliseconds) of the scan, finish and lookup kernels so far; switches their timing on or off"""
         n, ms = C.c_int64(), C.c_double()
         _check(lib().gs_accmap_kernel_time(self.h, int(profile), C.byref(n), C.byref(ms)))
+        return n.value, ms.value
+
+
+RANK_NAMES = ("cellular root", "acellular root", "superkingdom", "domain", "realm", "kingdom", "phylum", "subphylum", "superclass", "class",
+              "subclass", "superorder", "order", "suborder", "superfamily", "family", "subfamily", "tribe", "genus", "subgenus",
+              "species group", "species", "varietas", "subspecies", "serogroup", "biotype", "strain", "serotype", "genotype", "forma",
+              "forma specialis", "isolate", "clade", "no rank", "subkingdom", "section", "REFINED", "DATA", "FILE", "ID")
+
+
+def read_taxids(text):
+    """gs_taxtree_read_taxids: the bytes of a tax id file as TaxIdCollector.readFromFile reads them -> (requested, excluded) tax ids
+    as int32 arrays, in file order; a value that is no tax id of 1-9 digits is dropped, as an unknown id is"""
+    buf = np.frombuffer(bytes(text) or b"\0", dtype=np.uint8)
+    n = len(bytes(text))
+    cap = n // 2 + 1
+    req, exc = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
+    n_req, n_exc = C.c_int64(), C.c_int64()
+    _check(lib().gs_taxtree_read_taxids(_ptr(buf)[0], n, _ptr(req)[0], C.byref(n_req), _ptr(exc)[0], C.byref(n_exc), cap))
+    return req[:n_req.value], exc[:n_exc.value]
+
+
+class DeviceTaxTree:
+    """gs_taxtree: the lines of an NCBI nodes.dmp and names.dmp to the arrays of the tree (the taxtree goal), the taxnodes selection
+    and the tree a database carries.  A node is its index in the ascending array of distinct tax ids, so arrays()["taxids"] is the
+    known_taxids of DeviceAccessionMap.  submit_nodes() takes chunks of whole lines on the device; a chunk outside the device's
+    grammar is refused and leaves the tree as it was: the caller hands it to append_nodes(), which judges it line by line.
+    device -1: a host-only tree (append_nodes, finish, and every query from host memory)."""
+
+    def __init__(self, device=0):
+        self.h = C.c_void_p()
+        self.device = int(device)
+        self.n_nodes = self.n_reached = self.max_depth = self.n_duplicates = self.on_host = self.n_cycle_nodes = 0
+        _check(lib().gs_taxtree_create(C.byref(self.h), self.device))
+
+    @classmethod
+    def _wrap(cls, handle, report):
+        """a finished tree that the host layer made (host.taxtree_files); its device is -1 if it is a host-only one"""
+        t = cls.__new__(cls)
+        t.h = handle
+        dev = C.c_int(0)
+        _check(lib().gs_taxtree_get_device(t.h, C.byref(dev)))
+        t.device = dev.value
+        t.n_nodes, t.n_reached, t.n_duplicates, t.on_host = report["nodes"], report["reached"], report["duplicates"], report["on_host"]
+        t.n_cycle_nodes = 0
+        t.max_depth = int(t.arrays()["depth"].max()) if t.n_nodes else 0
+        return t
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().gs_taxtree_destroy(self.h)
+            self.h = C.c_void_p()
+
+    __del__ = close
+
+    @staticmethod
+    def _text(text):
+        if isinstance(text, (bytes, bytearray, memoryview)):
+            text = np.frombuffer(bytes(text), dtype=np.uint8)
+        return text, int(text.shape[0])
+
+    def submit_nodes(self, text, last=False):
+        """a chunk of whole nodes lines (bytes, a uint8 array, or a uint8 tensor on the handle's device) -> its report"""
+        text, n = self._text(text)
+        _ready(text)
+        p, mem = _ptr(text) if n else (None, MEM_HOST)
+        r = (C.c_int64 * 8)()
+        _check(lib().gs_taxtree_submit_nodes(self.h, p, n, mem, int(bool(last)), r))
+        return {"lines": r[0], "taken": r[2], "refused": r[3], "first_bad_line": r[4], "longest_line": r[5]}
+
+    def append_nodes(self, text, last=False):
+        """the same lines judged one by one on the host, at their place in the input order -> its report"""
+        text, n = self._text(text)
+        r = (C.c_int64 * 8)()
+        _check(lib().gs_taxtree_append_nodes(self.h, _ptr(text)[0] if n else None, n, int(bool(last)), r))
+        return {"lines": r[0], "taken": r[2], "refused": 0, "first_bad_line": -1, "longest_line": 0}
+
+    def finish(self):
+        """the tree -> {"nodes", "reached", "max_depth", "duplicates", "on_host", "cycle_nodes", "slots"}"""
+        info = (C.c_int64 * 8)()
+        _check(lib().gs_taxtree_finish_nodes(self.h, info))
+        self.n_nodes, self.n_reached, self.max_depth, self.n_duplicates, self.on_host, self.n_cycle_nodes = tuple(info)[:6]
+        return {"nodes": info[0], "reached": info[1], "max_depth": info[2], "duplicates": info[3], "on_host": info[4], "cycle_nodes": info[5],
+                "slots": info[6]}
+
+    def submit_names(self, text, last=False):
+        """a chunk of whole names lines (bytes, a uint8 array, or a uint8 tensor on the handle's device), behind finish(), scanned
+        on the device -> its report; a refused chunk wrote nothing and goes to append_names()"""
+        text, n = self._text(text)
+        _ready(text)
+        p, mem = _ptr(text) if n else (None, MEM_HOST)
+        r = (C.c_int64 * 8)()
+        _check(lib().gs_taxtree_submit_names(self.h, p, n, mem, int(bool(last)), r))
+        return {"lines": r[0], "taken": r[2], "refused": r[3], "first_bad_line": r[4], "longest_line": r[5]}
+
+    def append_names(self, text, last=False):
+        """the same lines judged one by one on the host, at their place in the input order (the only way on a tree that lives on
+        the host)"""
+        text, n = self._text(text)
+        _check(lib().gs_taxtree_append_names(self.h, _ptr(text)[0] if n else None, n, int(bool(last))))
+
+    def finish_times(self):
+        """milliseconds of the last finish between events, if kernel_time(True) came before it -> (distinct ids and parents,
+        child order, tree steps)"""
+        ms = (C.c_double * 3)()
+        _check(lib().gs_taxtree_finish_times(self.h, ms))
+        return tuple(ms)
+
+    def arrays(self):
+        """-> {"taxids", "parent", "depth", "position", "subtree", "rank"}: int32[n_nodes] each"""
+        out = {k: np.zeros(max(self.n_nodes, 1), dtype=np.int32) for k in ("taxids", "parent", "depth", "position", "subtree", "rank")}
+        _check(lib().gs_taxtree_fetch(self.h, *(_ptr(out[k])[0] for k in ("taxids", "parent", "depth", "position", "subtree", "rank"))))
+        return {k: v[:self.n_nodes] for k, v in out.items()}
+
+    def names(self):
+        """-> list of n_nodes names: bytes, or None for a node that no names line named"""
+        off = np.zeros(self.n_nodes + 1, dtype=np.int64)
+        _check(lib().gs_taxtree_fetch_names(self.h, _ptr(off)[0], None, 0))
+        total = int(off[self.n_nodes])
+        buf = np.zeros(max(total, 1), dtype=np.uint8)
+        _check(lib().gs_taxtree_fetch_names(self.h, _ptr(off)[0], _ptr(buf)[0], total))
+        raw = buf.tobytes()
+        ends = [int(o) if o >= 0 else -1 - int(o) for o in off]
+        return [raw[ends[i]:ends[i + 1]] if off[i] >= 0 else None for i in range(self.n_nodes)]
+
+    def nodes_of(self, taxids, known=None):
+        """tax ids -> their node indices; an id that names no node is dropped (TaxTree.getNodeByTaxId answers null)"""
+        known = self.arrays()["taxids"] if known is None else known
+        t = np.asarray(taxids, dtype=np.int64).reshape(-1)
+        i = np.searchsorted(known, t)
+        ok = (i < len(known)) & (known[np.minimum(i, len(known) - 1)] == t) if len(known) else np.zeros(len(t), dtype=bool)
+        return i[ok].astype(np.int32)
+
+    def select(self, requested, excluded=(), cut_rank=None):
+        """the taxnodes set: requested / excluded node indices, cut_rank a rank name, an ordinal or None -> uint8[n_nodes]"""
+        req = np.ascontiguousarray(requested, dtype=np.int32).reshape(-1)
+        exc = np.ascontiguousarray(excluded, dtype=np.int32).reshape(-1)
+        cut = -1 if cut_rank is None else RANK_NAMES.index(cut_rank) if isinstance(cut_rank, str) else int(cut_rank)
+        out = np.zeros(max(self.n_nodes, 1), dtype=np.uint8)
+        count = C.c_int64()
+        _check(lib().gs_taxtree_select(self.h, _ptr(req)[0] if len(req) else None, len(req), _ptr(exc)[0] if len(exc) else None, len(exc), cut,
+                                       _ptr(out)[0], C.byref(count)))
+        self.n_selected = count.value
+        return out[:self.n_nodes]
+
+    def small_tree(self, flagged):
+        """flagged: uint8[n_nodes] (host array or device tensor) or int32[n_nodes] with > 0 meaning flagged (the regions of an
+        accession map) -> {"node_of_vi", "parent_vi", "depth", "position"}: int32[n_small] each, the root first"""
+        if not hasattr(flagged, "device") or isinstance(flagged, np.ndarray):
+            flagged = np.ascontiguousarray(flagged)
+            if flagged.dtype not in (np.uint8, np.int32):
+                flagged = flagged.astype(np.uint8)
+        if int(flagged.shape[0]) != self.n_nodes:
+            raise ValueError("one flag per node")
+        _ready(flagged)
+        p, mem = _ptr(flagged)
+        size = int(flagged.element_size()) if hasattr(flagged, "element_size") else flagged.dtype.itemsize
+        cap = max(self.n_reached, 1)
+        out = {k: np.zeros(cap, dtype=np.int32) for k in ("node_of_vi", "parent_vi", "depth", "position")}
+        n_small = C.c_int32()
+        _check(lib().gs_taxtree_small(self.h, p, size, mem, C.byref(n_small), *(_ptr(out[k])[0] for k in ("node_of_vi", "parent_vi", "depth", "position"))))
+        return {k: v[:n_small.value] for k, v in out.items()}
+
+    def kernel_time(self, profile=True):
+        """(launches, milliseconds) of the scan, finish, select and small kernels so far; switches their timing on or off"""
+        n, ms = C.c_int64(), C.c_double()
+        _check(lib().gs_taxtree_kernel_time(self.h, int(profile), C.byref(n), C.byref(ms)))
         return n.value, ms.value

@@ -25,6 +25,7 @@
 #include "gs_layout.h"
 #include "gs_params.h"
 #include "gs_prefilter.h"
+#include "gs_taxparse.h"
 
 // ---------------------------------------------------------------------------------------------------
 // errors
@@ -7534,6 +7535,759 @@ extern "C" int gs_accmap_kernel_time(gs_accmap *h, int profile, int64_t *launche
     h->profile = profile != 0;
     if (launches) *launches = h->timer.launches;
     if (total_ms) *total_ms = h->timer.total_ms;
+    return GS_OK;
+}
+GS_API_CATCH
+
+// ---------------------------------------------------------------------------------------------------
+// taxtree: NCBI nodes.dmp / names.dmp to the arrays of the tree; taxnodes selection; small tree (gs_taxtree.hip, gs_taxparse.h)
+// ---------------------------------------------------------------------------------------------------
+
+struct gs_taxtree {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool host_only = false;  // device == -1
+    bool on_host = false;    // the finished tree lives in `tree`: a host-only handle, or a device handle that met duplicate ids
+    int state = 0;           // 0: nodes come in; 1: gs_taxtree_finish_nodes has succeeded
+    GsTaxRanks *d_ranks = nullptr;
+    uint8_t *d_text = nullptr;
+    size_t text_cap = 0;
+    u64 *d_tile = nullptr;
+    uint32_t *d_tail = nullptr;
+    size_t tile_cap = 0;
+    uint4 *d_slots = nullptr;
+    size_t slot_cap = 0;
+    int64_t n_slots = 0;
+    u64 *d_small = nullptr;  // status | scan sum | counts[6]
+    gs_host::TaxNodesExact nodes;  // the line-by-line reader of nodes; on a host-only handle its slots are the input
+    gs_host::TaxNamesExact names;
+    gs_host::TaxHostTree tree;     // on_host: all of it; else taxids, names and has_name alone
+    // the finished tree on the device
+    GsTaxTreeArrays A{};
+    int32_t *d_taxids = nullptr;
+    int32_t n_reach = 0, max_depth = 0;
+    int64_t n_cyc = 0;
+    std::vector<uint8_t> h_cyc;  // n_cyc > 0: the nodes on cycles
+    // names the device judged (gs_taxtree_submit_names): per node the winning key, and where its name lies in the pool
+    u64 *d_win = nullptr, *d_name_off = nullptr;
+    uint32_t *d_name_len = nullptr;
+    uint8_t *d_pool = nullptr;
+    size_t pool_cap = 0;
+    double finish_ms[3] = {0, 0, 0};  // the last finish under profile: distinct ids and parents | child order | tree steps
+    bool profile = false;
+    KernelTimer timer;
+};
+enum { TT_S_STATUS = 0, TT_S_SCAN = 1, TT_S_COUNTS = 2, TT_S_WORDS = TT_S_COUNTS + 6 };
+
+static void tt_free_tree(gs_taxtree *h) {
+    for (void *p : {(void *)h->d_win, (void *)h->d_name_off, (void *)h->d_name_len, (void *)h->d_pool}) gs_dev_free(p);
+    h->d_win = h->d_name_off = nullptr;
+    h->d_name_len = nullptr;
+    h->d_pool = nullptr;
+    h->pool_cap = 0;
+    for (void *p : {(void *)h->d_taxids, (void *)h->A.parent, (void *)h->A.rank, (void *)h->A.line_of, (void *)h->A.depth, (void *)h->A.position,
+                    (void *)h->A.subtree, (void *)h->A.node_at, (void *)h->A.cyc})
+        gs_dev_free(p);
+    h->A = GsTaxTreeArrays{};
+    h->d_taxids = nullptr;
+}
+
+extern "C" int gs_taxtree_destroy(gs_taxtree *h) try {
+    if (!h) return GS_OK;
+    if (!h->host_only) {
+        hipSetDevice(h->device);
+        if (h->stream) hipStreamSynchronize(h->stream);
+        timer_free(h->timer);
+        tt_free_tree(h);
+        for (void *p : {(void *)h->d_ranks, (void *)h->d_text, (void *)h->d_tile, (void *)h->d_tail, (void *)h->d_slots, (void *)h->d_small}) gs_dev_free(p);
+        if (h->stream) hipStreamDestroy(h->stream);
+    }
+    delete h;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_taxtree_create(gs_taxtree **out, int device) try {
+    if (!out) return fail(GS_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (device < -1) return fail(GS_E_INVALID, "device must be -1 (host only) or a device index");
+    int rc = device == -1 ? (int)GS_OK : use_device(device);
+    if (rc) return rc;
+    gs_taxtree *h = new gs_taxtree();
+    h->device = device;
+    h->host_only = device == -1;
+    if (h->host_only) {
+        *out = h;
+        return GS_OK;
+    }
+    GsTaxRanks ranks{};
+    for (int r = 0; r < GS_TT_N_RANKS; r++) {
+        const size_t len = strlen(gs_host::TAX_RANK_NAMES[r]);
+        ranks.len[r] = (uint8_t)len;
+        memcpy(ranks.text[r], gs_host::TAX_RANK_NAMES[r], len);
+    }
+    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = gs_dev_alloc(&h->d_ranks, sizeof(GsTaxRanks));
+    if (e == hipSuccess) e = gs_dev_alloc(&h->d_small, sizeof(u64) * TT_S_WORDS);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->d_ranks, &ranks, sizeof(ranks), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // (ranks is a local)
+    if (e != hipSuccess) {
+        gs_taxtree_destroy(h);
+        return hip_fail(e, "gs_taxtree_create");
+    }
+    *out = h;
+    return GS_OK;
+}
+GS_API_CATCH
+static_assert(GS_TT_N_RANKS == gs_host::TAX_N_RANKS, "one list of ranks");
+
+extern "C" int gs_taxtree_get_device(gs_taxtree *h, int *device) try {
+    if (!h || !device) return fail(GS_E_INVALID, "NULL argument");
+    *device = h->device;
+    return GS_OK;
+}
+GS_API_CATCH
+
+// room for `need` slots in all; what is there stays
+static int tt_slot_room(gs_taxtree *h, size_t need) {
+    if (need <= h->slot_cap) return GS_OK;
+    if (need > ((size_t)1 << 30)) return fail(GS_E_UNSUPPORTED, "a tree takes at most 2^30 lines");
+    const size_t cap = std::max(need, 2 * h->slot_cap);
+    uint4 *slots = nullptr;
+    hipError_t e = gs_dev_alloc(&slots, cap * sizeof(uint4));
+    if (e == hipSuccess && h->n_slots) e = hipMemcpyAsync(slots, h->d_slots, (size_t)h->n_slots * sizeof(uint4), hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        gs_dev_free(slots);
+        return hip_fail(e, "gs_taxtree: growing the slots");
+    }
+    gs_dev_free(h->d_slots);
+    h->d_slots = slots;
+    h->slot_cap = cap;
+    return GS_OK;
+}
+
+extern "C" int gs_taxtree_submit_nodes(gs_taxtree *h, const uint8_t *text, int64_t n_bytes, int mem, int last, int64_t report[8]) try {
+    if (!h || !report) return fail(GS_E_INVALID, "NULL argument");
+    if (n_bytes < 0 || n_bytes > ((int64_t)1 << 30)) return fail(GS_E_INVALID, "a chunk holds at most 1 GiB");
+    if (n_bytes > 0 && !text) return fail(GS_E_INVALID, "text is NULL");
+    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    if (h->state != 0) return fail(GS_E_STATE, "gs_taxtree_submit_nodes comes in front of gs_taxtree_finish_nodes");
+    if (h->host_only) return fail(GS_E_UNSUPPORTED, "a host-only tree (device -1) takes its lines through gs_taxtree_append_nodes alone");
+    for (int i = 0; i < 8; i++) report[i] = 0;
+    report[4] = -1;
+    if (n_bytes == 0) return GS_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t n_tiles = (n_bytes + GS_TT_TILE - 1) / GS_TT_TILE;
+    const size_t padded = (size_t)n_tiles * GS_TT_TILE + 64;
+    int rc;
+    if ((rc = grow(&h->d_text, &h->text_cap, padded, h->stream))) return rc;
+    if (h->tile_cap < (size_t)n_tiles + 1) {
+        const size_t cap = (size_t)n_tiles + 1 + (size_t)n_tiles / 4;
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->tile_cap = 0;
+        if ((rc = renew(&h->d_tile, cap))) return rc;
+        if ((rc = renew(&h->d_tail, cap))) return rc;
+        h->tile_cap = cap;
+    }
+    HIP_TRY(hipMemcpyAsync(h->d_text, text, (size_t)n_bytes, mem == GS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(h->d_text + n_bytes, 0, padded - (size_t)n_bytes, h->stream));
+    u64 small[TT_S_COUNTS] = {};
+    small[TT_S_STATUS] = (u64)GS_TT_NONE;  // bad line: none; longest line: 0
+    HIP_TRY(hipMemcpy(h->d_small, small, sizeof(small), hipMemcpyHostToDevice));  // (the stream is idle between calls)
+    GsTaxScanParams P{};
+    P.text = h->d_text;
+    P.n_bytes = n_bytes;
+    P.n_tiles = n_tiles;
+    P.last = last != 0;
+    P.ranks = h->d_ranks;
+    P.tile_lb = (unsigned long long *)h->d_tile;
+    P.tile_tail = h->d_tail;
+    P.scan_tot = (unsigned long long *)h->d_small + TT_S_SCAN;
+    P.status = (uint32_t *)(h->d_small + TT_S_STATUS);
+    if ((rc = timer_start(h->timer, h->profile, h->stream))) return rc;
+    HIP_TRY(gs_launch_taxtree_tiles(&P, h->stream));
+    if ((rc = timer_stop(h->timer, h->profile, h->stream))) return rc;
+    uint8_t tail = '\n';
+    HIP_TRY(hipMemcpyAsync(small, h->d_small, sizeof(small), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(&tail, h->d_text + n_bytes - 1, 1, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));  // the lines of the chunk: its slots need room
+    const int64_t n_lines = (int64_t)(uint32_t)small[TT_S_SCAN] + (tail != '\n');
+    if ((rc = tt_slot_room(h, (size_t)(h->n_slots + n_lines)))) return rc;
+    HIP_TRY(hipMemsetAsync(h->d_slots + h->n_slots, 0, (size_t)n_lines * sizeof(uint4), h->stream));
+    P.slots = h->d_slots;
+    P.first_line = h->n_slots;
+    P.slot_cap = h->n_slots + n_lines;
+    if ((rc = timer_start(h->timer, h->profile, h->stream))) return rc;
+    HIP_TRY(gs_launch_taxtree_scan(&P, h->stream));
+    if ((rc = timer_stop(h->timer, h->profile, h->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(small, h->d_small, sizeof(small), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const uint32_t bad = (uint32_t)small[TT_S_STATUS];
+    report[0] = n_lines;
+    report[5] = (int64_t)(small[TT_S_STATUS] >> 32);
+    if (bad != GS_TT_NONE) {  // what the scan wrote lies behind n_slots: the handle is as it was
+        report[3] = 1;
+        report[4] = (int64_t)bad;
+        return timer_collect(h->timer);
+    }
+    report[2] = n_lines;
+    h->n_slots += n_lines;
+    h->nodes.line_no += n_lines;
+    return timer_collect(h->timer);
+}
+GS_API_CATCH
+
+static int tt_parse_fail(const gs_host::TaxError &err, const char *what) {
+    return fail(err.code == 2 ? GS_E_UNSUPPORTED : GS_E_INVALID, std::string(what) + " line " + std::to_string(err.line) + ": " + err.what);
+}
+
+extern "C" int gs_taxtree_append_nodes(gs_taxtree *h, const uint8_t *text, int64_t n_bytes, int last, int64_t report[8]) try {
+    if (!h || !report) return fail(GS_E_INVALID, "NULL argument");
+    if (n_bytes < 0) return fail(GS_E_INVALID, "n_bytes < 0");
+    if (n_bytes > 0 && !text) return fail(GS_E_INVALID, "text is NULL");
+    if (h->state != 0) return fail(GS_E_STATE, "gs_taxtree_append_nodes comes in front of gs_taxtree_finish_nodes");
+    for (int i = 0; i < 8; i++) report[i] = 0;
+    report[4] = -1;
+    const int64_t line0 = h->nodes.line_no;
+    const size_t before = h->nodes.slots.size();
+    if (!h->nodes.feed(text, (size_t)n_bytes, last != 0)) {
+        h->nodes.slots.resize(before);
+        const gs_host::TaxError err = h->nodes.err;
+        h->nodes.line_no = line0;
+        return tt_parse_fail(err, "nodes");
+    }
+    report[0] = h->nodes.line_no - line0;
+    report[2] = (int64_t)(h->nodes.slots.size() - before);
+    if (h->host_only) {
+        h->n_slots = (int64_t)h->nodes.slots.size();
+        return GS_OK;
+    }
+    const size_t n = h->nodes.slots.size();
+    if (n) {
+        HIP_TRY(hipSetDevice(h->device));
+        int rc = tt_slot_room(h, (size_t)h->n_slots + n);
+        if (rc) return rc;
+        static_assert(sizeof(gs_host::TaxSlot) == sizeof(uint4), "a slot is 16 bytes on both sides");
+        HIP_TRY(hipMemcpyAsync(h->d_slots + h->n_slots, h->nodes.slots.data(), n * sizeof(uint4), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->n_slots += (int64_t)n;
+        h->nodes.slots.clear();
+    }
+    return GS_OK;
+}
+GS_API_CATCH
+
+// info: [0] nodes, [1] nodes the root reaches, [2] the deepest of them, [3] lines whose id had a line before, [4] 1: the tree
+// lives on the host, [5] nodes on a cycle of parent links, [6] slots
+static int tt_finish_host(gs_taxtree *h, const gs_host::TaxSlot *slots, size_t m, int64_t info[8]) {
+    std::string why;
+    if (!h->tree.build(slots, m, &why)) return fail(GS_E_INVALID, "gs_taxtree_finish_nodes: " + why);
+    h->on_host = true;
+    h->state = 1;
+    h->n_reach = 0;
+    h->max_depth = 0;
+    for (int32_t v = 0; v < h->tree.n; v++) {
+        h->n_reach += h->tree.position[(size_t)v] >= 0;
+        h->max_depth = std::max(h->max_depth, h->tree.depth[(size_t)v]);
+    }
+    info[0] = h->tree.n;
+    info[1] = h->n_reach;
+    info[2] = h->max_depth;
+    info[3] = h->tree.duplicates;
+    info[4] = 1;
+    info[6] = (int64_t)m;
+    return GS_OK;
+}
+
+extern "C" int gs_taxtree_finish_nodes(gs_taxtree *h, int64_t info[8]) try {
+    if (!h || !info) return fail(GS_E_INVALID, "NULL argument");
+    if (h->state != 0) return fail(GS_E_STATE, "gs_taxtree_finish_nodes was called before");
+    for (int i = 0; i < 8; i++) info[i] = 0;
+    if (h->host_only) return tt_finish_host(h, h->nodes.slots.data(), h->nodes.slots.size(), info);
+    const int64_t m = h->n_slots;
+    if (m == 0) return fail(GS_E_INVALID, "gs_taxtree_finish_nodes: no root: no line has the id 1 and the parent 1");
+    HIP_TRY(hipSetDevice(h->device));
+    u64 *counts_d = h->d_small + TT_S_COUNTS;
+    u64 counts[6] = {};
+    HIP_TRY(hipMemcpy(counts_d, counts, sizeof(counts), hipMemcpyHostToDevice));  // (the stream is idle between calls)
+    size_t tmp_bytes = 0;
+    HIP_TRY(gs_taxtree_sort_bytes(2 * m, &tmp_bytes));
+    // one block of scratch for every step: [0, 8m) words for the distinct step, reused by the steps behind it
+    uint32_t *w = nullptr;
+    void *tmp = nullptr;
+    int rc = GS_OK;
+    hipError_t e = gs_dev_alloc(&w, (size_t)8 * (size_t)m * sizeof(uint32_t));
+    if (e == hipSuccess) e = gs_dev_alloc(&tmp, std::max<size_t>(tmp_bytes, 1));
+    if (e == hipSuccess) e = gs_dev_alloc(&h->d_taxids, (size_t)2 * (size_t)m * sizeof(int32_t));
+    const size_t pair0 = h->timer.pending.size();
+    std::vector<int> phase_of;  // of the event pairs from pair0 on
+    auto timed = [&](int phase, bool begin) {
+        if (!begin && h->profile) phase_of.push_back(phase);
+        return begin ? timer_start(h->timer, h->profile, h->stream) : timer_stop(h->timer, h->profile, h->stream);
+    };
+    auto bail = [&](int code) {
+        hipStreamSynchronize(h->stream);
+        timer_collect(h->timer);  // (the pairs handed in so far; an open one is taken up by the next start)
+        gs_dev_free(w);
+        gs_dev_free(tmp);
+        tt_free_tree(h);
+        return code;
+    };
+    if (e != hipSuccess) return bail(hip_fail(e, "gs_taxtree_finish_nodes"));
+    if ((rc = timed(0, true))) return bail(rc);
+    e = gs_taxtree_distinct(h->d_slots, m, w, w + 2 * m, w + 4 * m, w + 6 * m, tmp, tmp_bytes, h->d_taxids, (unsigned long long *)counts_d, h->stream);
+    if (e == hipSuccess && (rc = timed(0, false))) return bail(rc);
+    if (e == hipSuccess) e = hipMemcpyAsync(counts, counts_d, sizeof(counts), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return bail(hip_fail(e, "gs_taxtree_finish_nodes: distinct ids"));
+    const int64_t n = (int64_t)(uint32_t)counts[4] + (int64_t)(counts[4] >> 32);
+    if (n <= 0) return bail(fail(GS_E_INVALID, "gs_taxtree_finish_nodes: no root: no line has the id 1 and the parent 1"));
+    gs_dev_free(w);
+    w = nullptr;
+    {  // the sorts and scans of n <= 2m nodes: what they ask for, should that be more than what 2m keys asked for
+        size_t again = 0;
+        e = gs_taxtree_sort_bytes(n, &again);
+        if (e == hipSuccess && again > tmp_bytes) {
+            gs_dev_free(tmp);
+            tmp = nullptr;
+            tmp_bytes = again;
+            e = gs_dev_alloc(&tmp, tmp_bytes);
+        }
+        if (e != hipSuccess) return bail(hip_fail(e, "gs_taxtree_finish_nodes"));
+    }
+    GsTaxTreeArrays &A = h->A;
+    A.n = (int32_t)n;
+    A.root = 0;  // ids are positive and ascending: the node "1" is the first or is not there
+    A.taxids = h->d_taxids;
+    for (int32_t **p : {&A.parent, &A.rank, &A.line_of, &A.depth, &A.position, &A.subtree, &A.node_at})
+        if (e == hipSuccess) e = gs_dev_alloc(p, (size_t)n * sizeof(int32_t));
+    if (e == hipSuccess) e = gs_dev_alloc(&A.cyc, (size_t)n);
+    // scratch of the tree steps, in words: key 2n | key_alt 2n | ord n | ord_alt n | first_child n | next_sib n |
+    // succ 2n+2 | succ_alt 2n+2 | val 4n+4 | val_alt 4n+4 | up n | up_alt n
+    const size_t N = (size_t)n;
+    if (e == hipSuccess) e = gs_dev_alloc(&w, (22 * N + 16) * sizeof(uint32_t));
+    if (e != hipSuccess) return bail(hip_fail(e, "gs_taxtree_finish_nodes"));
+    if ((rc = timed(0, true))) return bail(rc);
+    e = gs_taxtree_resolve(h->d_slots, m, &A, (unsigned long long *)counts_d, h->stream);
+    if (e == hipSuccess && (rc = timed(0, false))) return bail(rc);
+    int32_t first[3] = {0, 0, 0};  // taxids[0], parent[0], line_of[0]
+    if (e == hipSuccess) e = hipMemcpyAsync(counts, counts_d, sizeof(counts), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&first[0], h->d_taxids, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&first[1], A.parent, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&first[2], A.line_of, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return bail(hip_fail(e, "gs_taxtree_finish_nodes: resolve"));
+    if (counts[0] > 0) {
+        // two lines with one id: the reference lists the node twice and keeps its last parent.  The host's child lists say that.
+        std::vector<gs_host::TaxSlot> slots((size_t)m);
+        e = hipMemcpy(slots.data(), h->d_slots, (size_t)m * sizeof(uint4), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return bail(hip_fail(e, "gs_taxtree_finish_nodes: slots to the host"));
+        bail(0);
+        gs_dev_free(h->d_slots);  // (the tree lives on the host from here on)
+        h->d_slots = nullptr;
+        h->slot_cap = 0;
+        return tt_finish_host(h, slots.data(), slots.size(), info);
+    }
+    if (first[0] != 1 || first[1] != -1 || first[2] < 0)
+        return bail(fail(GS_E_INVALID, "gs_taxtree_finish_nodes: no root: no line has the id 1 and the parent 1"));
+    u64 *key = (u64 *)w;
+    uint32_t *ord = w + 4 * N, *succ = w + 8 * N;
+    int32_t *first_child = (int32_t *)(w + 6 * N), *next_sib = (int32_t *)(w + 7 * N);
+    u64 *val = (u64 *)(w + 8 * N + 2 * (2 * N + 2));  // (8N + 4N + 4 words in front: a multiple of two)
+    int32_t *up = (int32_t *)(w + 8 * N + 2 * (2 * N + 2) + 4 * (2 * N + 2));
+    if ((rc = timed(1, true))) return bail(rc);
+    e = gs_taxtree_children(&A, key, key + N, ord, ord + N, tmp, tmp_bytes, first_child, next_sib, h->stream);
+    if (e == hipSuccess && (rc = timed(1, false))) return bail(rc);
+    if (e == hipSuccess && (rc = timed(2, true))) return bail(rc);
+    if (e == hipSuccess) e = gs_taxtree_place(&A, first_child, next_sib, succ, succ + 2 * N + 2, val, val + 2 * N + 2, up, up + N, (unsigned long long *)counts_d, h->stream);
+    if (e == hipSuccess) rc = timed(2, false);
+    if (e == hipSuccess) e = hipMemcpyAsync(counts, counts_d, sizeof(counts), hipMemcpyDeviceToHost, h->stream);
+    h->tree.taxids.resize(N);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->tree.taxids.data(), h->d_taxids, N * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return bail(hip_fail(e, "gs_taxtree_finish_nodes: tree steps"));
+    if (rc) return bail(rc);
+    h->finish_ms[0] = h->finish_ms[1] = h->finish_ms[2] = 0;
+    for (size_t i = 0; i < phase_of.size() && pair0 + i < h->timer.pending.size(); i++) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, h->timer.pending[pair0 + i].first, h->timer.pending[pair0 + i].second) == hipSuccess) h->finish_ms[phase_of[i]] += ms;
+    }
+    h->n_reach = (int32_t)counts[1];
+    h->max_depth = (int32_t)counts[2];
+    h->n_cyc = 0;
+    if (counts[3] > 0) {
+        h->h_cyc.resize(N);
+        e = hipMemcpy(h->h_cyc.data(), A.cyc, N, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return bail(hip_fail(e, "gs_taxtree_finish_nodes: cycle flags"));
+        for (uint8_t c : h->h_cyc) h->n_cyc += c;
+    }
+    gs_dev_free(w);
+    gs_dev_free(tmp);
+    gs_dev_free(h->d_slots);
+    h->d_slots = nullptr;
+    h->slot_cap = 0;
+    h->tree.n = A.n;
+    h->tree.names.assign(N, std::string());
+    h->tree.has_name.assign(N, 0);
+    h->tree.name_key.assign(N, 0);
+    h->state = 1;
+    info[0] = n;
+    info[1] = h->n_reach;
+    info[2] = h->max_depth;
+    info[5] = h->n_cyc;
+    info[6] = m;
+    return timer_collect(h->timer);
+}
+GS_API_CATCH
+
+extern "C" int gs_taxtree_submit_names(gs_taxtree *h, const uint8_t *text, int64_t n_bytes, int mem, int last, int64_t report[8]) try {
+    if (!h || !report) return fail(GS_E_INVALID, "NULL argument");
+    if (n_bytes < 0 || n_bytes > ((int64_t)1 << 30)) return fail(GS_E_INVALID, "a chunk holds at most 1 GiB");
+    if (n_bytes > 0 && !text) return fail(GS_E_INVALID, "text is NULL");
+    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    if (h->state != 1) return fail(GS_E_STATE, "gs_taxtree_submit_names comes behind gs_taxtree_finish_nodes");
+    if (h->on_host) return fail(GS_E_UNSUPPORTED, "the tree lives on the host (device -1, or duplicate ids): names go through gs_taxtree_append_names");
+    for (int i = 0; i < 8; i++) report[i] = 0;
+    report[4] = -1;
+    if (n_bytes == 0) return GS_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t N = (size_t)h->tree.n;
+    u64 *pool_used_d = h->d_small + TT_S_COUNTS + 5;
+    int rc;
+    if (!h->d_win) {
+        hipError_t e = gs_dev_alloc(&h->d_win, N * sizeof(u64));
+        if (e == hipSuccess) e = gs_dev_alloc(&h->d_name_off, N * sizeof(u64));
+        if (e == hipSuccess) e = gs_dev_alloc(&h->d_name_len, N * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemsetAsync(h->d_win, 0, N * sizeof(u64), h->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(pool_used_d, 0, sizeof(u64), h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) {
+            gs_dev_free(h->d_win);
+            h->d_win = nullptr;
+            return hip_fail(e, "gs_taxtree_submit_names");
+        }
+    }
+    const int64_t n_tiles = (n_bytes + GS_TT_TILE - 1) / GS_TT_TILE;
+    const size_t padded = (size_t)n_tiles * GS_TT_TILE + 64;
+    if ((rc = grow(&h->d_text, &h->text_cap, padded, h->stream))) return rc;
+    if (h->tile_cap < (size_t)n_tiles + 1) {
+        const size_t cap = (size_t)n_tiles + 1 + (size_t)n_tiles / 4;
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->tile_cap = 0;
+        if ((rc = renew(&h->d_tile, cap))) return rc;
+        if ((rc = renew(&h->d_tail, cap))) return rc;
+        h->tile_cap = cap;
+    }
+    HIP_TRY(hipMemcpyAsync(h->d_text, text, (size_t)n_bytes, mem == GS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(h->d_text + n_bytes, 0, padded - (size_t)n_bytes, h->stream));
+    u64 small[TT_S_COUNTS] = {};
+    small[TT_S_STATUS] = (u64)GS_TT_NONE;
+    HIP_TRY(hipMemcpy(h->d_small, small, sizeof(small), hipMemcpyHostToDevice));  // (the stream is idle between calls)
+    GsTaxScanParams P{};
+    P.text = h->d_text;
+    P.n_bytes = n_bytes;
+    P.n_tiles = n_tiles;
+    P.last = last != 0;
+    P.tile_lb = (unsigned long long *)h->d_tile;
+    P.tile_tail = h->d_tail;
+    P.scan_tot = (unsigned long long *)h->d_small + TT_S_SCAN;
+    P.status = (uint32_t *)(h->d_small + TT_S_STATUS);
+    P.first_line = h->names.line_no;
+    P.taxids = h->d_taxids;
+    P.n_nodes = h->tree.n;
+    P.win = (unsigned long long *)h->d_win;
+    P.name_off = (unsigned long long *)h->d_name_off;
+    P.name_len = h->d_name_len;
+    P.pool_used = (unsigned long long *)pool_used_d;
+    if ((rc = timer_start(h->timer, h->profile, h->stream))) return rc;
+    HIP_TRY(gs_launch_taxtree_tiles(&P, h->stream));
+    HIP_TRY(gs_launch_taxtree_names(&P, 0, h->stream));
+    if ((rc = timer_stop(h->timer, h->profile, h->stream))) return rc;
+    uint8_t tail = '\n';
+    u64 used = 0;
+    HIP_TRY(hipMemcpyAsync(small, h->d_small, sizeof(small), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(&tail, h->d_text + n_bytes - 1, 1, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(&used, pool_used_d, sizeof(used), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));  // the one wait of a chunk: its verdict
+    const int64_t n_lines = (int64_t)(uint32_t)small[TT_S_SCAN] + (tail != '\n');
+    const uint32_t bad = (uint32_t)small[TT_S_STATUS];
+    report[0] = n_lines;
+    report[5] = (int64_t)(small[TT_S_STATUS] >> 32);
+    if (bad != GS_TT_NONE) {  // nothing was written: the handle is as it was
+        report[3] = 1;
+        report[4] = (int64_t)bad;
+        return timer_collect(h->timer);
+    }
+    // every name of the chunk has room, whoever wins; what the pool holds stays
+    const size_t need = (size_t)used + (size_t)n_bytes;
+    if (need > h->pool_cap) {
+        const size_t cap = std::max(need, 2 * h->pool_cap);
+        uint8_t *pool = nullptr;
+        hipError_t e = gs_dev_alloc(&pool, cap);
+        if (e == hipSuccess && used) e = hipMemcpyAsync(pool, h->d_pool, (size_t)used, hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) {
+            gs_dev_free(pool);
+            return hip_fail(e, "gs_taxtree_submit_names: growing the pool");
+        }
+        gs_dev_free(h->d_pool);
+        h->d_pool = pool;
+        h->pool_cap = cap;
+    }
+    P.pool = h->d_pool;
+    if ((rc = timer_start(h->timer, h->profile, h->stream))) return rc;
+    HIP_TRY(gs_launch_taxtree_names(&P, 1, h->stream));
+    HIP_TRY(gs_launch_taxtree_names(&P, 2, h->stream));
+    if ((rc = timer_stop(h->timer, h->profile, h->stream))) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    report[2] = n_lines;
+    h->names.line_no += n_lines;
+    return timer_collect(h->timer);
+}
+GS_API_CATCH
+
+extern "C" int gs_taxtree_append_names(gs_taxtree *h, const uint8_t *text, int64_t n_bytes, int last) try {
+    if (!h) return fail(GS_E_INVALID, "tree is NULL");
+    if (n_bytes < 0) return fail(GS_E_INVALID, "n_bytes < 0");
+    if (n_bytes > 0 && !text) return fail(GS_E_INVALID, "text is NULL");
+    if (h->state != 1) return fail(GS_E_STATE, "gs_taxtree_append_names comes behind gs_taxtree_finish_nodes");
+    if (!h->names.feed(h->tree, text, (size_t)n_bytes, last != 0)) return tt_parse_fail(h->names.err, "names");
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_taxtree_fetch(gs_taxtree *h, int32_t *taxids, int32_t *parent, int32_t *depth, int32_t *position, int32_t *subtree, int32_t *rank) try {
+    if (!h) return fail(GS_E_INVALID, "tree is NULL");
+    if (h->state != 1) return fail(GS_E_STATE, "gs_taxtree_fetch comes behind gs_taxtree_finish_nodes");
+    const size_t bytes = (size_t)h->tree.n * sizeof(int32_t);
+    if (taxids) memcpy(taxids, h->tree.taxids.data(), bytes);
+    if (h->on_host) {
+        if (parent) memcpy(parent, h->tree.parent.data(), bytes);
+        if (depth) memcpy(depth, h->tree.depth.data(), bytes);
+        if (position) memcpy(position, h->tree.position.data(), bytes);
+        if (subtree) memcpy(subtree, h->tree.subtree.data(), bytes);
+        if (rank) memcpy(rank, h->tree.rank.data(), bytes);
+        return GS_OK;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    if (parent) HIP_TRY(hipMemcpy(parent, h->A.parent, bytes, hipMemcpyDeviceToHost));
+    if (depth) HIP_TRY(hipMemcpy(depth, h->A.depth, bytes, hipMemcpyDeviceToHost));
+    if (position) HIP_TRY(hipMemcpy(position, h->A.position, bytes, hipMemcpyDeviceToHost));
+    if (subtree) HIP_TRY(hipMemcpy(subtree, h->A.subtree, bytes, hipMemcpyDeviceToHost));
+    if (rank) HIP_TRY(hipMemcpy(rank, h->A.rank, bytes, hipMemcpyDeviceToHost));
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_taxtree_fetch_names(gs_taxtree *h, int64_t *offsets, uint8_t *bytes, int64_t cap) try {
+    if (!h || !offsets) return fail(GS_E_INVALID, "NULL argument");
+    if (cap < 0) return fail(GS_E_INVALID, "cap < 0");
+    if (h->state != 1) return fail(GS_E_STATE, "gs_taxtree_fetch_names comes behind gs_taxtree_finish_nodes");
+    if (h->d_win) {  // what the device judged joins what the host judged: per node the higher key has the name
+        HIP_TRY(hipSetDevice(h->device));
+        const size_t N = (size_t)h->tree.n;
+        std::vector<u64> win(N), off(N);
+        std::vector<uint32_t> len(N);
+        u64 used = 0;
+        HIP_TRY(hipMemcpy(win.data(), h->d_win, N * sizeof(u64), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(off.data(), h->d_name_off, N * sizeof(u64), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(len.data(), h->d_name_len, N * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&used, h->d_small + TT_S_COUNTS + 5, sizeof(used), hipMemcpyDeviceToHost));
+        std::vector<uint8_t> pool((size_t)used + 1);
+        if (used) HIP_TRY(hipMemcpy(pool.data(), h->d_pool, (size_t)used, hipMemcpyDeviceToHost));
+        for (size_t v = 0; v < N; v++)
+            if (win[v] > h->tree.name_key[v]) {
+                if (off[v] + len[v] > used) return fail(GS_E_HIP, "gs_taxtree_fetch_names: a name lies outside the pool");
+                h->tree.names[v].assign((const char *)pool.data() + off[v], len[v]);
+                h->tree.has_name[v] = 1;
+                h->tree.name_key[v] = win[v];
+            }
+    }
+    int64_t at = 0;
+    for (int32_t v = 0; v < h->tree.n; v++) {
+        offsets[v] = h->tree.has_name[(size_t)v] ? at : -1 - at;  // (a node without a name: -1 - where the next one starts)
+        at += (int64_t)h->tree.names[(size_t)v].size();
+    }
+    offsets[h->tree.n] = at;
+    if (!bytes) return GS_OK;
+    if (cap < at) return fail(GS_E_INVALID, "bytes is too small: offsets[n_nodes] says what it takes");
+    at = 0;
+    for (int32_t v = 0; v < h->tree.n; v++) {
+        memcpy(bytes + at, h->tree.names[(size_t)v].data(), h->tree.names[(size_t)v].size());
+        at += (int64_t)h->tree.names[(size_t)v].size();
+    }
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_taxtree_select(gs_taxtree *h, const int32_t *requested, int64_t n_requested, const int32_t *excluded, int64_t n_excluded, int cut_rank,
+                                 uint8_t *out, int64_t *count) try {
+    if (!h || !out) return fail(GS_E_INVALID, "NULL argument");
+    if (n_requested < 0 || n_excluded < 0 || (n_requested > 0 && !requested) || (n_excluded > 0 && !excluded))
+        return fail(GS_E_INVALID, "a list is NULL or its length negative");
+    if (cut_rank < -1 || cut_rank >= GS_TT_N_RANKS) return fail(GS_E_INVALID, "cut_rank is -1 (none) or the ordinal of a rank");
+    if (h->state != 1) return fail(GS_E_STATE, "gs_taxtree_select comes behind gs_taxtree_finish_nodes");
+    const int32_t n = h->tree.n;
+    for (int k = 0; k < 2; k++)
+        for (int64_t i = 0; i < (k ? n_excluded : n_requested); i++) {
+            const int32_t v = (k ? excluded : requested)[i];
+            if (v < 0 || v >= n) return fail(GS_E_INVALID, "a requested or excluded node is no index into the tree");
+            if (!h->on_host && h->n_cyc && h->h_cyc[(size_t)v])
+                return fail(GS_E_INVALID, "a requested or excluded node lies on a cycle of parent links: the reference's descent does not end");
+        }
+    if (h->on_host) {
+        if (!h->tree.select(requested, n_requested, excluded, n_excluded, cut_rank, out))
+            return fail(GS_E_INVALID, "a requested or excluded node reaches a cycle: the reference's descent does not end");
+        if (count) {
+            *count = 0;
+            for (int32_t v = 0; v < n; v++) *count += out[v];
+        }
+        return GS_OK;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t N = (size_t)n, n_list = (size_t)(n_requested + n_excluded);
+    uint8_t *bytes = nullptr;  // marks n | out n
+    int32_t *words = nullptr;  // anc 3n | requested | excluded
+    hipError_t e = gs_dev_alloc(&bytes, 2 * N);
+    if (e == hipSuccess) e = gs_dev_alloc(&words, (3 * N + n_list + 1) * sizeof(int32_t));
+    int32_t *d_req = words + 3 * N, *d_exc = d_req + n_requested;
+    u64 *d_count = h->d_small + TT_S_COUNTS;
+    u64 c = 0;
+    if (e == hipSuccess && n_requested) e = hipMemcpyAsync(d_req, requested, (size_t)n_requested * sizeof(int32_t), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && n_excluded) e = hipMemcpyAsync(d_exc, excluded, (size_t)n_excluded * sizeof(int32_t), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpy(d_count, &c, sizeof(c), hipMemcpyHostToDevice);  // (the stream is idle between calls)
+    int rc = e == hipSuccess ? timer_start(h->timer, h->profile, h->stream) : hip_fail(e, "gs_taxtree_select");
+    if (!rc) {
+        e = gs_launch_taxtree_select(&h->A, d_req, n_requested, d_exc, n_excluded, cut_rank, bytes, words, bytes + N, (unsigned long long *)d_count, h->stream);
+        if (e == hipSuccess) rc = timer_stop(h->timer, h->profile, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(out, bytes + N, N, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&c, d_count, sizeof(c), hipMemcpyDeviceToHost, h->stream);
+        if (e != hipSuccess) rc = hip_fail(e, "gs_taxtree_select");
+    }
+    e = hipStreamSynchronize(h->stream);
+    if (!rc && e != hipSuccess) rc = hip_fail(e, "gs_taxtree_select");
+    gs_dev_free(bytes);
+    gs_dev_free(words);
+    if (rc) return rc;
+    if (count) *count = (int64_t)c;
+    return timer_collect(h->timer);
+}
+GS_API_CATCH
+
+extern "C" int gs_taxtree_small(gs_taxtree *h, const void *flagged, int flag_bytes, int mem, int32_t *n_small, int32_t *node_of_vi, int32_t *parent_vi,
+                                int32_t *depth, int32_t *position) try {
+    if (!h || !flagged || !n_small) return fail(GS_E_INVALID, "NULL argument");
+    if (flag_bytes != 1 && flag_bytes != 4) return fail(GS_E_INVALID, "flag_bytes is 1 (uint8) or 4 (int32, > 0 means flagged)");
+    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    if (h->state != 1) return fail(GS_E_STATE, "gs_taxtree_small comes behind gs_taxtree_finish_nodes");
+    if (h->host_only && mem != GS_MEM_HOST) return fail(GS_E_UNSUPPORTED, "a host-only tree reads host memory alone");
+    const int32_t n = h->tree.n;
+    const size_t N = (size_t)n;
+    if (h->on_host) {
+        std::vector<uint8_t> f8;
+        std::vector<int32_t> f32;
+        const void *f = flagged;
+        if (mem == GS_MEM_DEVICE) {
+            HIP_TRY(hipSetDevice(h->device));
+            if (flag_bytes == 1) {
+                f8.resize(N);
+                f = f8.data();
+            } else {
+                f32.resize(N);
+                f = f32.data();
+            }
+            HIP_TRY(hipMemcpy(const_cast<void *>(f), flagged, N * (size_t)flag_bytes, hipMemcpyDeviceToHost));
+        }
+        std::vector<int32_t> nodes, parents;
+        if (flag_bytes == 1)
+            h->tree.small((const uint8_t *)f, nodes, parents);
+        else
+            h->tree.small((const int32_t *)f, nodes, parents);
+        *n_small = (int32_t)nodes.size();
+        for (size_t i = 0; i < nodes.size(); i++) {
+            if (node_of_vi) node_of_vi[i] = nodes[i];
+            if (parent_vi) parent_vi[i] = parents[i];
+            if (depth) depth[i] = h->tree.depth[(size_t)nodes[i]];
+            if (position) position[i] = h->tree.position[(size_t)nodes[i]];
+        }
+        return GS_OK;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t R = (size_t)h->n_reach;
+    size_t tmp_bytes = 0;
+    HIP_TRY(gs_taxtree_sort_bytes((int64_t)R, &tmp_bytes));
+    uint32_t *w = nullptr;  // pre | sum | req | vi | node_of_vi | parent_vi | depth | position, R words each; then the flags
+    void *tmp = nullptr;
+    const size_t flag_words = mem == GS_MEM_HOST ? (N * (size_t)flag_bytes + 3) / 4 : 0;
+    hipError_t e = gs_dev_alloc(&w, (8 * R + flag_words + 1) * sizeof(uint32_t));
+    if (e == hipSuccess) e = gs_dev_alloc(&tmp, std::max<size_t>(tmp_bytes, 1));
+    const void *d_flag = flagged;
+    if (e == hipSuccess && mem == GS_MEM_HOST) {
+        e = hipMemcpyAsync(w + 8 * R, flagged, N * (size_t)flag_bytes, hipMemcpyHostToDevice, h->stream);
+        d_flag = w + 8 * R;
+    }
+    int rc = e == hipSuccess ? timer_start(h->timer, h->profile, h->stream) : hip_fail(e, "gs_taxtree_small");
+    uint32_t last[2] = {0, 0};
+    if (!rc) {
+        e = gs_launch_taxtree_small(&h->A, h->n_reach, flag_bytes == 1 ? (const uint8_t *)d_flag : nullptr, flag_bytes == 4 ? (const int32_t *)d_flag : nullptr, w,
+                                    w + R, w + 2 * R, w + 3 * R, tmp, tmp_bytes, (int32_t *)(w + 4 * R), (int32_t *)(w + 5 * R), (int32_t *)(w + 6 * R),
+                                    (int32_t *)(w + 7 * R), h->stream);
+        if (e == hipSuccess) rc = timer_stop(h->timer, h->profile, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&last[0], w + 3 * R - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream);  // req[R - 1]
+        if (e == hipSuccess) e = hipMemcpyAsync(&last[1], w + 4 * R - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream);  // vi[R - 1]
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        const size_t S = (size_t)last[0] + last[1];
+        *n_small = (int32_t)S;
+        if (e == hipSuccess && node_of_vi) e = hipMemcpyAsync(node_of_vi, w + 4 * R, S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess && parent_vi) e = hipMemcpyAsync(parent_vi, w + 5 * R, S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess && depth) e = hipMemcpyAsync(depth, w + 6 * R, S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess && position) e = hipMemcpyAsync(position, w + 7 * R, S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+        if (e != hipSuccess) rc = hip_fail(e, "gs_taxtree_small");
+    }
+    e = hipStreamSynchronize(h->stream);
+    if (!rc && e != hipSuccess) rc = hip_fail(e, "gs_taxtree_small");
+    gs_dev_free(w);
+    gs_dev_free(tmp);
+    return rc ? rc : timer_collect(h->timer);
+}
+GS_API_CATCH
+
+extern "C" int gs_taxtree_finish_times(gs_taxtree *h, double ms[3]) try {
+    if (!h || !ms) return fail(GS_E_INVALID, "NULL argument");
+    if (h->state != 1) return fail(GS_E_STATE, "gs_taxtree_finish_times comes behind gs_taxtree_finish_nodes");
+    for (int i = 0; i < 3; i++) ms[i] = h->finish_ms[i];
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_taxtree_kernel_time(gs_taxtree *h, int profile, int64_t *launches, double *total_ms) try {
+    if (!h) return fail(GS_E_INVALID, "tree is NULL");
+    if (h->host_only) {
+        if (launches) *launches = 0;
+        if (total_ms) *total_ms = 0;
+        return GS_OK;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    int rc = timer_collect(h->timer);
+    if (rc) return rc;
+    h->profile = profile != 0;
+    if (launches) *launches = h->timer.launches;
+    if (total_ms) *total_ms = h->timer.total_ms;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_taxtree_read_taxids(const uint8_t *text, int64_t n_bytes, int32_t *requested, int64_t *n_requested, int32_t *excluded, int64_t *n_excluded,
+                                      int64_t cap) try {
+    if (!n_requested || !n_excluded || n_bytes < 0 || cap < 0 || (n_bytes > 0 && !text)) return fail(GS_E_INVALID, "NULL or negative argument");
+    std::vector<int32_t> req, exc;
+    gs_host::tax_read_taxids(text, (size_t)n_bytes, req, exc);
+    *n_requested = (int64_t)req.size();
+    *n_excluded = (int64_t)exc.size();
+    if (requested && (int64_t)req.size() <= cap) memcpy(requested, req.data(), req.size() * sizeof(int32_t));
+    if (excluded && (int64_t)exc.size() <= cap) memcpy(excluded, exc.data(), exc.size() * sizeof(int32_t));
     return GS_OK;
 }
 GS_API_CATCH

@@ -3801,6 +3801,199 @@ extern "C" int gs_host_accmap_files(const char *const *paths, int n_paths, int d
     return hfail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
 }
 
+// ---- NCBI taxonomy dump files to the tree (TaxTree(File, boolean); gs_taxtree on the device, gs_taxparse.h inside the handle for
+// what the device refuses)
+namespace {
+
+struct TtGuard {
+    gs_taxtree *&t;
+    ~TtGuard() {
+        if (t) gs_taxtree_destroy(t);
+        t = nullptr;
+    }
+};
+
+struct TtCtx {
+    gs_taxtree *t = nullptr;
+    bool names = false;  // the names stream: gs_taxtree_submit_names / _append_names
+    int64_t lines = 0, device_chunks = 0, host_chunks = 0;
+    int prog_file = 0;
+    int64_t prog_lines0 = 0;
+    bool report(int64_t pos, bool gz) {
+        if (!trk().chunk(prog_file, pos, gz, lines - prog_lines0)) return false;
+        trk().stopped(prog_file, lines - prog_lines0);
+        return true;
+    }
+};
+
+// whole lines through the line-by-line restatement inside the handle, at their place in the input order
+int tt_feed(TtCtx &c, const std::string &path, const uint8_t *p, size_t n, bool last) {
+    if (c.names) {
+        const int rc = gs_taxtree_append_names(c.t, p, (int64_t)n, last);
+        if (rc != GS_OK) return hfail(rc, path + ": " + gs_last_error());
+        c.lines += (int64_t)std::count(p, p + n, (uint8_t)'\n') + (n && p[n - 1] != '\n');
+        return GS_OK;
+    }
+    int64_t rep[8];
+    const int rc = gs_taxtree_append_nodes(c.t, p, (int64_t)n, last, rep);
+    if (rc != GS_OK) return hfail(rc, path + ": " + gs_last_error());
+    c.lines += rep[0];
+    return GS_OK;
+}
+
+// the rest of a stream, line by line: the file from `offset` on, or a memory range that ends the stream
+int tt_cpu(TtCtx &c, const std::string &path, int64_t offset, const uint8_t *mem, size_t mem_n) {
+    c.host_chunks++;
+    if (mem) {
+        const int err = tt_feed(c, path, mem, mem_n, true);
+        return err ? err : c.report(0, false) ? cancelled_rc() : (int)GS_OK;
+    }
+    LineReader lr;
+    if (!lr.open(path, offset)) return hfail(GS_E_IO, "cannot open " + path);
+    std::vector<uint8_t> text;
+    for (bool eof = false; !eof;) {  // whole lines, some MiB at a time
+        text.clear();
+        while (text.size() < ((size_t)4 << 20)) {
+            if (lr.next_line(text) == 0) {
+                eof = true;
+                break;
+            }
+        }
+        // (next_line drops NUL bytes as the parser would; a final line without its newline is the stream's last)
+        if (!text.empty() && text.back() != '\n') eof = true;
+        const int err = tt_feed(c, path, text.data(), text.size(), eof);
+        if (err) return err;
+        if (c.report(lr.raw_pos(), false)) return cancelled_rc();
+    }
+    return GS_OK;
+}
+
+// A nodes or names file through the device: chunks that end behind a newline are scanned there; one that the device refuses goes through
+// the handle's parser, so the input order stays; the stream goes on behind it on the device.  A line that does not fit a block sends
+// the rest of the file through the parser; so does the unterminated tail.
+int tt_device_file(TtCtx &c, const std::string &path, bool gzip) {
+    size_t block;
+    int readers = 0;
+    reader_shape(gzip, &block, &readers);
+    TextReader tr;
+    int err = tr.open(path, block, readers, gzip);
+    if (err) {
+        tr.close();
+        return err;
+    }
+    ChunkCutter cut;
+    cut.mode = ChunkCutter::LINES;
+    int64_t fallback_off = -1;
+    tr.start();
+    for (int64_t i = 0; !err; i++) {
+        TextSlot &sl = tr.wait_full(i);
+        if ((err = block_error(tr, sl, path))) break;
+        const bool eof = sl.eof;
+        const ChunkCutter::Cut what = cut_block(cut, tr, sl);
+        if (what == ChunkCutter::FALLBACK) {
+            fallback_off = cut.file_off;
+        } else if (what == ChunkCutter::CHUNK && cut.bytes > 0) {
+            int64_t rep[8];
+            const int rc = c.names ? gs_taxtree_submit_names(c.t, cut.start, cut.bytes, GS_MEM_HOST, 0, rep)
+                                   : gs_taxtree_submit_nodes(c.t, cut.start, cut.bytes, GS_MEM_HOST, 0, rep);
+            if (rc != GS_OK) {
+                err = hfail(rc, path + ": " + gs_last_error());
+                break;
+            }
+            if (rep[3] != 0) {  // refused: this chunk line by line
+                c.host_chunks++;
+                err = tt_feed(c, path, cut.start, (size_t)cut.bytes, false);
+            } else {
+                c.device_chunks++;
+                c.lines += rep[0];
+            }
+            cut.commit();
+            if (!err && c.report(cut.file_off, gzip)) err = cancelled_rc();  // (the record is out: the block may go back)
+        } else if (what == ChunkCutter::CHUNK) {
+            cut.commit();
+        }
+        tr.release(i);
+        if (eof || fallback_off >= 0) break;
+    }
+    tr.close();
+    if (err) return err;
+    if (fallback_off >= 0) return tt_cpu(c, path, fallback_off, nullptr, 0);
+    if (!cut.carry.empty()) return tt_cpu(c, path, 0, cut.carry.data(), cut.carry.size());
+    return GS_OK;
+}
+
+}  // namespace
+
+extern "C" int gs_host_taxtree_files(int device, const char *nodes_path, const char *names_path, gs_taxtree **out, int64_t report[8]) try {
+    if (out) *out = nullptr;
+    if (!nodes_path || !out || !report) return hfail(GS_E_INVALID, "NULL argument");
+    for (int i = 0; i < 8; i++) report[i] = 0;
+    bool fast = true;
+    if (const char *e = getenv("GS_HOST_FAST")) fast = atoi(e) != 0;
+    TtCtx c;
+    TtGuard guard{c.t};
+    if (const int rc = gs_taxtree_create(&c.t, fast ? device : -1)) return hfail(rc, gs_last_error());
+    const char *paths[2] = {nodes_path, names_path};
+    const int n_paths = names_path ? 2 : 1;
+    int err = GS_OK;
+    TrackerScope progress(paths, n_paths);
+    Tracker &tk = progress.t;
+    for (int f = 0; f < n_paths && !err; f++) {
+        const std::string path(paths[f]);
+        c.names = f == 1;
+        c.prog_file = f;
+        c.prog_lines0 = c.lines;
+        if (tk.file_start(f)) {
+            tk.stopped(f, 0);
+            err = cancelled_rc();
+            break;
+        }
+        // (a tree that fell back to the host's lists -- duplicate ids -- takes its names line by line as well)
+        const int kind = fast && (f == 0 || report[7] == 0) ? text_path_kind(path) : 0;
+        err = kind ? tt_device_file(c, path, kind == 2 || kind == 4) : tt_cpu(c, path, 0, nullptr, 0);
+        if (!err && tk.file_end(f, c.lines - c.prog_lines0)) err = cancelled_rc();
+        if (!err && f == 0) {
+            report[0] = c.lines;
+            int64_t info[8];
+            const int rc = gs_taxtree_finish_nodes(c.t, info);
+            if (rc != GS_OK) return hfail(rc, path + ": " + gs_last_error());
+            report[4] = info[0];
+            report[5] = info[1];
+            report[6] = info[3];
+            report[7] = info[4];
+        }
+    }
+    if (!err && tk.close()) err = cancelled_rc();
+    report[1] = c.lines - report[0];
+    report[2] = c.device_chunks;
+    report[3] = c.host_chunks;
+    if (!err) {
+        *out = c.t;
+        c.t = nullptr;  // (the caller's now)
+    }
+    return err;
+} catch (const std::bad_alloc &) {
+    return hfail(GS_E_NOMEM, "out of host memory");
+} catch (const std::exception &e) {
+    return hfail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
+}
+
+// TaxIdCollector.readFromFile: the file (plain or gzip) as bytes through gs_taxtree_read_taxids
+extern "C" int gs_host_read_taxids_file(const char *path, int32_t *requested, int64_t *n_requested, int32_t *excluded, int64_t *n_excluded, int64_t cap) try {
+    if (!path || !n_requested || !n_excluded || cap < 0) return hfail(GS_E_INVALID, "NULL or negative argument");
+    LineReader lr;
+    if (!lr.open(path, 0)) return hfail(GS_E_IO, std::string("cannot open ") + path);
+    std::vector<uint8_t> text;
+    while (lr.next_line(text) != 0) {
+    }
+    const int rc = gs_taxtree_read_taxids(text.data(), (int64_t)text.size(), requested, n_requested, excluded, n_excluded, cap);
+    return rc ? hfail(rc, gs_last_error()) : (int)GS_OK;
+} catch (const std::bad_alloc &) {
+    return hfail(GS_E_NOMEM, "out of host memory");
+} catch (const std::exception &e) {
+    return hfail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
+}
+
 // ---- genome FASTA files to regions (AbstractFastaReader.readFasta under the store readers; gs_genomes on the device)
 namespace {
 

@@ -262,6 +262,24 @@ hipError_t gs_accmap_sort_entries(const uint8_t *keys, const int32_t *nodes, int
 hipError_t gs_launch_accmap_lookup(const uint8_t *headers, const u64 *header_off, int64_t n, int complete_only, const uint8_t *keys,
                                    const int32_t *nodes, int64_t n_entries, int32_t *node_out, hipStream_t stream);
 
+// ---- gs_taxtree.hip: nodes.dmp lines -> tree arrays; select; small tree
+hipError_t gs_launch_taxtree_tiles(const GsTaxScanParams *P, hipStream_t stream);
+hipError_t gs_launch_taxtree_scan(const GsTaxScanParams *P, hipStream_t stream);
+hipError_t gs_launch_taxtree_names(const GsTaxScanParams *P, int mode, hipStream_t stream);
+hipError_t gs_taxtree_sort_bytes(int64_t n_keys, size_t *tmp_bytes);
+hipError_t gs_taxtree_distinct(const uint4 *slots, int64_t m, uint32_t *keys, uint32_t *keys_alt, uint32_t *head, uint32_t *idx, void *tmp, size_t tmp_bytes,
+                               int32_t *taxids, u64 *counts, hipStream_t stream);
+hipError_t gs_taxtree_resolve(const uint4 *slots, int64_t m, const GsTaxTreeArrays *A, u64 *counts, hipStream_t stream);
+hipError_t gs_taxtree_children(const GsTaxTreeArrays *A, u64 *key, u64 *key_alt, uint32_t *ord, uint32_t *ord_alt, void *tmp, size_t tmp_bytes,
+                               int32_t *first_child, int32_t *next_sib, hipStream_t stream);
+hipError_t gs_taxtree_place(const GsTaxTreeArrays *A, const int32_t *first_child, const int32_t *next_sib, uint32_t *succ, uint32_t *succ_alt, u64 *val,
+                            u64 *val_alt, int32_t *up, int32_t *up_alt, u64 *counts, hipStream_t stream);
+hipError_t gs_launch_taxtree_select(const GsTaxTreeArrays *A, const int32_t *requested, int64_t n_req, const int32_t *excluded, int64_t n_exc, int cut,
+                                    uint8_t *marks, int32_t *anc, uint8_t *out, u64 *count, hipStream_t stream);
+hipError_t gs_launch_taxtree_small(const GsTaxTreeArrays *A, int32_t n_reach, const uint8_t *flag8, const int32_t *flag32, uint32_t *pre, uint32_t *sum,
+                                   uint32_t *req, uint32_t *vi, void *tmp, size_t tmp_bytes, int32_t *node_of_vi, int32_t *parent_vi, int32_t *depth,
+                                   int32_t *position, hipStream_t stream);
+
 }  // extern "C"
 
 // ---- gs_devcache.cpp: the device block cache.  Every device allocation of gs_api.cpp goes through these two, by name; hidden,

@@ -445,3 +445,45 @@ struct GsAccmapParams {
     int64_t first_entry, entry_cap;  // the chunk's first entry goes to slot first_entry
     int32_t *regions;             // n_nodes: entries per node
 };
+
+// ---- gs_taxtree.hip: nodes.dmp lines -> tree arrays (the taxtree / taxnodes goals)
+#define GS_TT_TILE 4096       // bytes per scan block: GS_SCAN_BLOCK threads, 16 bytes each
+#define GS_TT_MAX_LINE 4096   // the reference's line buffer: a longer line is split there
+#define GS_TT_N_RANKS 40      // C/tax/Rank.java
+#define GS_TT_RANK_BYTES 16   // the longest rank name has 15
+#define GS_TT_NONE 0xffffffffu
+enum { GS_TT_BAD_LINE = 0, GS_TT_LONGEST = 1, GS_TT_WORDS = 2 };
+struct GsTaxRanks {
+    uint8_t len[GS_TT_N_RANKS];
+    uint8_t text[GS_TT_N_RANKS][GS_TT_RANK_BYTES];
+};
+struct GsTaxScanParams {
+    const uint8_t *text;          // n_bytes of whole lines, zero bytes behind them up to n_tiles * GS_TT_TILE + 64
+    int64_t n_bytes, n_tiles;
+    int32_t last, pad;            // last != 0: the stream ends with this chunk, whose final line need not be terminated
+    const GsTaxRanks *ranks;
+    unsigned long long *tile_lb;  // per tile: newlines | bars << 32, then their exclusive prefix (gs_launch_scan_blocks)
+    uint32_t *tile_tail;          // per tile: (offset of its last newline + 1, 0: none) | bars behind that newline << 16
+    unsigned long long *scan_tot; // [1] the sum
+    uint32_t *status;             // GS_TT_WORDS
+    uint4 *slots;                 // (id, parent, rank ordinal, 0) per line; id 0: a line that yields nothing.  Zeroed by the caller
+    int64_t first_line, slot_cap; // the chunk's first line goes to slot first_line (names: its 1-based number in the stream, less one)
+    // the names scan (gs_tt_names_kernel)
+    const int32_t *taxids;        // n_nodes tax ids, ascending
+    int32_t n_nodes, pad2;
+    unsigned long long *win;      // per node: the key of the line whose name it has; 0: none (GS_TT_NAME_KEY)
+    unsigned long long *name_off; // per node: where its name lies in the pool ...
+    uint32_t *name_len;           // ... and its bytes
+    uint8_t *pool;                // names of the winners so far, dead ones among them
+    unsigned long long *pool_used;
+};
+// a scientific line with its line number is above every other line; among the others the lower line number is
+#define GS_TT_NAME_KEY(scientific, line) ((scientific) ? (1ull << 63) | (unsigned long long)(line) : 0x7fffffffffffffffull - (unsigned long long)(line))
+// the node arrays of a finished tree, all on the device, n entries each unless said otherwise
+struct GsTaxTreeArrays {
+    int32_t n, root;
+    const int32_t *taxids;
+    int32_t *parent, *rank, *line_of, *depth, *position, *subtree;
+    int32_t *node_at;             // node_at[position]: the node, for the nodes the root reaches
+    uint8_t *cyc;                 // != 0: the node lies on a cycle of parent links
+};

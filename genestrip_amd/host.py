@@ -63,6 +63,8 @@ def lib():
         "gs_host_genome_files": (ci, [vp, ci, ci, vp, vp, vp, vp, vp]),
         "gs_host_accmap_files": (ci, [vp, ci, ci, vp, ci, vp, vp]),
         "gs_host_genome_files_mapped": (ci, [vp, ci, ci, vp, ci, vp, vp, vp, vp, vp]),
+        "gs_host_taxtree_files": (ci, [ci, C.c_char_p, C.c_char_p, vp, vp]),
+        "gs_host_read_taxids_file": (ci, [C.c_char_p, vp, vp, vp, vp, i64]),
         "gs_host_write_kraken_csv": (ci, [C.c_char_p, vp, C.c_int32, vp, i64]),
         "gs_host_db2fastq": (ci, [vp, vp, C.c_char_p, C.c_int32, ci, C.c_char_p, vp]),
         "gs_host_last_error": (C.c_char_p, []), "gs_host_java_double": (ci, [C.c_double, vp, ci]),
@@ -581,3 +583,31 @@ def accmap_files(paths, known_taxids, categories, statuses, seq_type="GENOMIC", 
     m = _b.DeviceAccessionMap._wrap(h, known)
     m.n_entries, m.n_passing = totals["put"], totals["passing"]
     return m, totals
+
+
+def taxtree_files(nodes_path, names_path=None, device=0):
+    """gs_host_taxtree_files: the taxtree goal over nodes.dmp and (unless None) names.dmp, each plain, gzip or BGZF ->
+    (DeviceTaxTree, finished; report).  Chunks of whole nodes lines are scanned on the device, what it refuses by a line-by-line
+    restatement of the reference; names.dmp goes the same way.  GS_HOST_FAST=0 sends everything through the restatement and
+    gives a host-only tree.  A stop on request raises Cancelled: no tree."""
+    h = C.c_void_p()
+    r = (C.c_int64 * 8)()
+    rc = lib().gs_host_taxtree_files(int(device), os.fsencode(nodes_path), os.fsencode(names_path) if names_path is not None else None, C.byref(h), r)
+    report = {"nodes_lines": r[0], "names_lines": r[1], "device_chunks": r[2], "host_chunks": r[3], "nodes": r[4], "reached": r[5],
+              "duplicates": r[6], "on_host": r[7]}
+    _check(rc, report=report)
+    return _b.DeviceTaxTree._wrap(h, report), report
+
+
+def read_taxids_file(path):
+    """gs_host_read_taxids_file: a tax id file (plain or gzip) as TaxIdCollector.readFromFile reads it -> (requested, excluded) tax
+    ids as int32 arrays, in file order; what is no tax id of 1-9 digits is dropped, as an id that names no node is"""
+    cap = os.path.getsize(path) // 2 + 1  # (an id and its newline; an inflated file may hold more: the counts say so)
+    while True:
+        req, exc = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
+        n_req, n_exc = C.c_int64(), C.c_int64()
+        _check(lib().gs_host_read_taxids_file(os.fsencode(path), req.ctypes.data_as(C.c_void_p), C.byref(n_req), exc.ctypes.data_as(C.c_void_p),
+                                              C.byref(n_exc), cap))
+        if max(n_req.value, n_exc.value) <= cap:
+            return req[:n_req.value], exc[:n_exc.value]
+        cap = max(n_req.value, n_exc.value)

@@ -1156,6 +1156,94 @@ int gs_accmap_get_device(gs_accmap *am, int *device);
 int gs_accmap_kernel_time(gs_accmap *am, int profile, int64_t *launches, double *total_ms);
 int gs_accmap_destroy(gs_accmap *am);
 
+/* ---------------------------------------------------------------------------------------------------
+ * taxtree: NCBI nodes.dmp / names.dmp to the arrays of the tree, the taxnodes selection and the tree a database carries
+ * (genestrip_amd/csrc/gs_taxtree.hip, genestrip_amd/csrc/gs_taxparse.h)
+ *
+ * Replaces TaxTree(File, boolean) (C/tax/TaxTree.java:92-122, readNodesFromStream :226-254, readNamesFromStream :196-216,
+ * initPositions :491-502), TaxIdCollector.withDescendants under TaxNodesGoal (C/tax/TaxIdCollector.java:119-126,172-185,
+ * C/goals/TaxNodesGoal.java:74-94) and markRequired / SmallTaxTree(TaxTree) / Database.initStoreIndices (TaxTree.java:536-544,
+ * C/tax/SmallTaxTree.java:60-64,427-454, C/store/Database.java:107-128; the value indices are those of a store that has no values
+ * yet, and nothing else).  What the reference does on every kind of line is stated at the head of gs_taxparse.h, the grammar
+ * inside which the device takes a chunk of nodes lines at the head of gs_taxtree.hip.
+ *
+ * A node is its index in the ascending array of distinct tax ids -- of first fields and of parents: a parent that no line
+ * introduces is a node without rank and parent.  gs_taxtree_fetch's taxids are the known_taxids of gs_accmap_create.  The
+ * reference keys nodes by the string of the id; here a tax id is 1-9 digits without a leading zero, and a line whose id or parent
+ * is anything else made of digits fails with GS_E_UNSUPPORTED.  Where the reference throws, the call fails with GS_E_INVALID and
+ * names the 1-based line.
+ *
+ * gs_taxtree_create        device -1: a HOST-ONLY tree: it touches no device, takes lines through the append calls alone
+ *                          (gs_taxtree_submit_nodes: GS_E_UNSUPPORTED), builds the reference's child lists and walks them without
+ *                          recursion, and answers every call below from host memory (mem: GS_MEM_HOST alone).
+ * gs_taxtree_submit_nodes  text: n_bytes (at most 1 GiB) of whole nodes lines in host or device memory, free again on return.
+ *                          last != 0: the stream ends here and its final line need not be terminated.  report: [0] lines,
+ *                          [2] slots taken (one per line), [3] 1: REFUSED -- the handle is as it was and the caller owes the
+ *                          chunk to gs_taxtree_append_nodes, [4] the first line outside the grammar (0-based in the chunk; -1:
+ *                          none), [5] the longest line with its newline, [1] [6] [7] 0.
+ * gs_taxtree_append_nodes  the same lines judged one by one on the host, at their place in the input order.  report: [0] lines as
+ *                          the reference counts them (a line beyond 4096 bytes is two), [2] lines that were not skipped.  A
+ *                          failure leaves the handle as it was.
+ * gs_taxtree_finish_nodes  the tree: distinct ids, parents by search, child lists by one stable sort of (parent, line), depth,
+ *                          pre-order position and subtree size by pointer jumping over the Euler tour -- a number of launches
+ *                          that grows with log(nodes), not with the depth.  A node that the root does not reach (another
+ *                          self-parent node, a parent-only node, a cycle, and what hangs below them) has depth -1, position -1,
+ *                          subtree 0.  No line with id 1 and parent 1: GS_E_INVALID, "no root".  info: [0] nodes, [1] nodes the
+ *                          root reaches, [2] the deepest of them, [3] lines whose id had a line before -- the device's finish
+ *                          cannot say what the reference does with those (the node is listed twice and keeps its last parent),
+ *                          so the handle then builds the host's lists and [4] is 1: the tree lives on the host from here on,
+ *                          as it does on a host-only handle; [5] nodes on a cycle of parent links, [6] slots, [7] 0.
+ * gs_taxtree_submit_names  text: whole names lines in host or device memory, behind gs_taxtree_finish_nodes, scanned on the device
+ *                          inside the names grammar at the head of gs_taxtree.hip.  A node takes the name of the first line
+ *                          that names it, and of every later line that holds "scientific name" anywhere: one 64-bit atomicMax
+ *                          per line decides among the lines of the whole stream, and the names of a chunk's winners are
+ *                          gathered into a pool on the device before the call returns.  report as for
+ *                          gs_taxtree_submit_nodes; a REFUSED chunk wrote nothing and goes to gs_taxtree_append_names.  A tree
+ *                          that lives on the host: GS_E_UNSUPPORTED.
+ * gs_taxtree_append_names  the same lines judged one by one on the host, at their place in the input order (line numbers run
+ *                          through both calls, so a scientific line of either beats a synonym of the other).
+ * gs_taxtree_fetch         host arrays of n nodes each, any of them NULL: taxids, parent (node index; -1), depth, position,
+ *                          subtree, rank (ordinal of C/tax/Rank.java; -1).
+ * gs_taxtree_fetch_names   offsets[n + 1]: where the name of node i starts in bytes, or -1 - that if it has none;
+ *                          offsets[n]: the bytes in all.  bytes NULL: the offsets alone.  Names are the bytes of the line (the
+ *                          reference decodes them as UTF-8).
+ * gs_taxtree_select        the taxnodes set: requested and excluded are node indices (host); cut_rank is the ordinal of
+ *                          rankCompletionDepth or -1.  out[n] (host): 1 for a node of withDescendants(requested, cut) that is
+ *                          not in withDescendants(excluded, null); *count (may be NULL): how many.  Descent follows child lists
+ *                          whether the root reaches them or not.  A requested or excluded node on a cycle: GS_E_INVALID (the
+ *                          reference's recursion does not end).
+ * gs_taxtree_small         flagged[n]: uint8 (flag_bytes 1) or int32 (flag_bytes 4; > 0 means flagged: the regions of
+ *                          gs_accmap_fetch), host or device memory.  The nodes the root reaches that are flagged or have a
+ *                          flagged descendant, and the root, in pre-order: *n_small and, per value index, node_of_vi, parent_vi
+ *                          (-1 for the root: what gs_dbbuild_begin takes), depth, position (host, room for info[1] entries; any
+ *                          may be NULL).  position is the FULL tree's, as SmallTaxTree's constructor copies it.
+ * gs_taxtree_read_taxids   TaxIdCollector.readFromFile over the bytes of a tax id file: the ids (1-9 digits) of requested and
+ *                          of '-' lines; at most cap of each are written, the counts say how many there are.
+ * gs_taxtree_finish_times  ms[3] of the last finish between events, if profiling was on: distinct ids and parents (one key sort, one
+ *                          scan, the searches) | child order (one pair sort) | tree steps (Euler tour, jumping, cycles); zeros else.
+ * gs_taxtree_kernel_time   profile != 0: from now on scan, finish, select and small run between events; what they add up to.
+ * NULL or negative arguments: GS_E_INVALID, before any device call.  Calls out of order: GS_E_STATE.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct gs_taxtree gs_taxtree;
+int gs_taxtree_create(gs_taxtree **out, int device);
+int gs_taxtree_submit_nodes(gs_taxtree *t, const uint8_t *text, int64_t n_bytes, int mem, int last, int64_t report[8]);
+int gs_taxtree_append_nodes(gs_taxtree *t, const uint8_t *text, int64_t n_bytes, int last, int64_t report[8]);
+int gs_taxtree_finish_nodes(gs_taxtree *t, int64_t info[8]);
+int gs_taxtree_submit_names(gs_taxtree *t, const uint8_t *text, int64_t n_bytes, int mem, int last, int64_t report[8]);
+int gs_taxtree_append_names(gs_taxtree *t, const uint8_t *text, int64_t n_bytes, int last);
+int gs_taxtree_fetch(gs_taxtree *t, int32_t *taxids, int32_t *parent, int32_t *depth, int32_t *position, int32_t *subtree, int32_t *rank);
+int gs_taxtree_fetch_names(gs_taxtree *t, int64_t *offsets, uint8_t *bytes, int64_t cap);
+int gs_taxtree_select(gs_taxtree *t, const int32_t *requested, int64_t n_requested, const int32_t *excluded, int64_t n_excluded, int cut_rank,
+                      uint8_t *out, int64_t *count);
+int gs_taxtree_small(gs_taxtree *t, const void *flagged, int flag_bytes, int mem, int32_t *n_small, int32_t *node_of_vi, int32_t *parent_vi,
+                     int32_t *depth, int32_t *position);
+int gs_taxtree_read_taxids(const uint8_t *text, int64_t n_bytes, int32_t *requested, int64_t *n_requested, int32_t *excluded, int64_t *n_excluded,
+                           int64_t cap);
+int gs_taxtree_get_device(gs_taxtree *t, int *device);
+int gs_taxtree_finish_times(gs_taxtree *t, double ms[3]);
+int gs_taxtree_kernel_time(gs_taxtree *t, int profile, int64_t *launches, double *total_ms);
+int gs_taxtree_destroy(gs_taxtree *t);
+
 #ifdef __cplusplus
 }
 #endif
