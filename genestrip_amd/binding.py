@@ -31,7 +31,7 @@ ABI_SYMBOLS = (
     "gs_last_error", "gs_strerror", "gs_device_cache_trim", "gs_abi_version", "gs_device_count",
     "gs_match_merge", "gs_match_max_contig_reads", "gs_db_create", "gs_db_get_info", "gs_db_destroy", "gs_db_save", "gs_db_load",
     "gs_match_begin", "gs_match_submit", "gs_match_submit_async", "gs_match_wait", "gs_match_sync", "gs_match_finish", "gs_match_reset", "gs_match_destroy",
-    "gs_match_device_state", "gs_match_or_bitmap", "gs_match_kernel_time", "gs_match_prefilter_info", "gs_match_segments",
+    "gs_match_device_state", "gs_match_or_bitmap", "gs_match_kernel_time", "gs_match_prefilter_info", "gs_match_sn_info", "gs_match_segments",
     "gs_match_segments_fetch", "gs_match_max_counts", "gs_db_create_striped", "gs_db_create_stripe", "gs_db_stripe_export", "gs_db_stripe_attach", "gs_db_load_striped", "gs_db_load_stripe", "gs_dbbuild_begin", "gs_dbbuild_set_range", "gs_dbbuild_add", "gs_dbbuild_finish", "gs_dbbuild_fetch", "gs_dbbuild_to_db", "gs_dbbuild_destroy", "gs_db_create_part", "gs_match_encode", "gs_match_probe_keys", "gs_match_encode_route", "gs_match_route_geometry", "gs_unroute_region", "gs_match_reduce", "gs_route_keys",
     "gs_unroute_nodes",
     "gs_match_submit_text", "gs_match_submit_fasta", "gs_match_submit_fastq_ml", "gs_match_text_wait_copy", "gs_match_text_status", "gs_match_text_clear_error",
@@ -138,7 +138,7 @@ def lib():
         "gs_match_submit_async": (ci, [vp, vp, vp, i64, i64, vp, vp, vp]), "gs_match_wait": (ci, [vp, i64]),
         "gs_match_sync": (ci, [vp]), "gs_match_finish": (ci, [vp, vp, vp]), "gs_match_reset": (ci, [vp]),
         "gs_match_destroy": (ci, [vp]), "gs_match_device_state": (ci, [vp, vp, vp, vp, vp, vp]),
-        "gs_match_or_bitmap": (ci, [vp, vp, i64]), "gs_match_merge": (ci, [vp, ci]), "gs_match_max_contig_reads": (ci, [vp, vp]), "gs_match_kernel_time": (ci, [vp, vp, vp]), "gs_match_prefilter_info": (ci, [vp, vp]),
+        "gs_match_or_bitmap": (ci, [vp, vp, i64]), "gs_match_merge": (ci, [vp, ci]), "gs_match_max_contig_reads": (ci, [vp, vp]), "gs_match_kernel_time": (ci, [vp, vp, vp]), "gs_match_prefilter_info": (ci, [vp, vp]), "gs_match_sn_info": (ci, [vp, vp]),
         "gs_db_create_part": (ci, [vp, ci, ci, i64, vp, vp, i32, vp, ci, ci]),
         "gs_db_create_striped": (ci, [vp, vp, ci, ci, i64, vp, vp, i32, vp]),
         "gs_db_create_stripe": (ci, [vp, ci, ci, ci, ci, i64, vp, vp, i32, vp]),
@@ -1405,6 +1405,13 @@ class FastqKMerMatcher:
         info = (C.c_int64 * 4)()
         _check(lib().gs_match_prefilter_info(self.h, info))
         return {"built": bool(info[0]), "n_lmers": int(info[1]), "survivors": int(info[2]), "reads": int(info[3])}
+
+    def sn_info(self):
+        """Reads of one tax id that left the match kernel as records (fixed-length batches, counters in LDS): {"deferred": the last
+        submitted batch ran that way, "booked": the records the reduce kernel booked for it}.  Synchronises."""
+        info = (C.c_int64 * 2)()
+        _check(lib().gs_match_sn_info(self.h, info))
+        return {"deferred": bool(info[0]), "booked": int(info[1])}
 
     def close(self):
         if getattr(self, "h", None):

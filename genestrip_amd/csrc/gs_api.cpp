@@ -2234,6 +2234,13 @@ struct gs_run {
     int pf_pause = 0;                  // batches that still go without the prefilter (the feedback rule)
     int64_t pf_last_survivors = -1, pf_last_reads = 0;  // of the last submitted batch; survivors -1: it went without the prefilter
     int pf_last_slot = -1;
+    // reads of one tax id leave the FIXED loop as records (GsSnRec) that gs_sn_reduce_kernel works off: sn_mode is GS_SN_DEFER
+    // (-1: not set, which is on); only runs whose counters live in LDS (sn_lds) defer
+    int sn_mode = -1;
+    bool sn_lds = false;
+    GsSnRec *d_sn_recs = nullptr;
+    size_t sn_recs_cap = 0;
+    bool sn_last = false;              // the last submitted batch deferred (its count: word 7 of d_long_count)
     int quot_max = 0;                  // what the table was built for: positions (0: none yet) and the two gate settings
     double quot_tax = 0, quot_class = 0;
     int stat_copies = 1;         // > 1: global-atomic counters spread over several copies (GsMatchParams::stat_copies)
@@ -2768,6 +2775,7 @@ static void run_free(gs_run *run) {
     gs_dev_free(run->d_stat_recs);
     gs_dev_free(run->d_stat_vi);
     gs_dev_free(run->d_stat_rec_count);
+    gs_dev_free(run->d_sn_recs);
     gs_dev_free(run->d_quot);
     hipHostFree(run->h_quot);
     hipHostFree(run->pf_h);
@@ -2892,6 +2900,7 @@ extern "C" int gs_match_begin(gs_run **out, gs_db *db, const gs_match_cfg *cfg) 
     run->db = db;
     run->cfg = *cfg;
     run->pf_mode = pf_mode;
+    if (const char *ev = getenv("GS_SN_DEFER")) run->sn_mode = atoi(ev) != 0 ? 1 : 0;
     const size_t nv = (size_t)db->info.n_values;
     run->bitmap_words = (db->n_slots() + 31) / 32 + db->n_rec;  // one word per record bucket behind the table slots' bits
     hipError_t e = hipStreamCreateWithFlags(&run->stream, hipStreamNonBlocking);
@@ -2916,6 +2925,7 @@ extern "C" int gs_match_begin(gs_run **out, gs_db *db, const gs_match_cfg *cfg) 
         // and atomics on one line execute one after the other (~11 ns each: a tail of 0.1-0.2 ms behind the kernel).  16 copies here too.
         run->stat_copies = 16;
         if (const char *ev = getenv("GS_STAT_COPIES")) run->stat_copies = std::max(1, std::min(64, atoi(ev)));
+        run->sn_lds = true;
     }
     const size_t cp = (size_t)run->stat_copies;
     // sums | max keys | double sums | long-read queue counters in ONE allocation: one memset clears them (gs_match_reset)
@@ -3155,14 +3165,24 @@ static int launch_batch(gs_run *run, const uint8_t *d_seq, const uint64_t *d_off
             prefilter = false;
         }
     }
+    // The batches whose waves take the FIXED loop of gs_match_kernel<true, ..> (counters in LDS, one candidate path per lane, one
+    // store): their reads of one tax id go out as records.  Without room for the records the batch runs without deferral.
+    run->sn_last = false;
+    if (P.quot != nullptr && run->sn_lds && run->sn_mode != 0 && run->cfg.max_paths <= 64 && P.db.n_parts <= 1 && !d_skip &&
+        grow(&run->d_sn_recs, &run->sn_recs_cap, (size_t)n_reads, run->stream) == GS_OK) {
+        P.sn_recs = run->d_sn_recs;
+        run->sn_last = true;
+    }
     int pf_slot = -1;
     if (prefilter) {
         if (!run->pf_h) {
             HIP_TRY(hipHostMalloc((void **)&run->pf_h, sizeof(uint32_t) * GS_PF_SLOTS, hipHostMallocDefault));
             for (int i = 0; i < GS_PF_SLOTS; i++) run->pf_h[i] = 0;
         }
-        HIP_TRY(hipMemsetAsync(run->d_long_count + 6, 0, sizeof(unsigned int), run->stream));
     }
+    // (word 6 behind the queue counters: the survivors; word 7: the records booked.  One memset for both)
+    if (prefilter || P.sn_recs)
+        HIP_TRY(hipMemsetAsync(run->d_long_count + (prefilter ? 6 : 7), 0, sizeof(unsigned int) * ((prefilter ? 1 : 0) + (P.sn_recs ? 1 : 0)), run->stream));
     if ((rc = timer_start(run->timer, run->cfg.profile != 0, run->stream))) return rc;
     if (prefilter) {
         GsPrefilterParams F{};
@@ -3197,6 +3217,27 @@ static int launch_batch(gs_run *run, const uint8_t *d_seq, const uint64_t *d_off
         // reads of more than 128 positions into the queues of the kernels that take them (reads of one short length: there are none)
         if (off_stride != 0 || fixed_len - run->db->info.k + 1 > 128) HIP_TRY(gs_launch_classify(&P, run->stream));
         HIP_TRY(gs_launch_match(&P, grid, run->stream));
+        if (P.sn_recs) {  // (part of the timed region, as the deferred statistics below)
+            GsSnReduceParams S{};
+            S.recs = P.sn_recs;
+            S.count = P.surv_count;
+            S.n_reads = n_reads;
+            S.first_read_no = first_read_no;
+            S.c.max = fixed_len - run->db->info.k + 1;
+            S.c.read_len = fixed_len;
+            S.c.classify = P.classify;
+            S.c.threshold = P.threshold;
+            S.n_values = P.db.n_values;
+            S.stat_copies = P.stat_copies;
+            S.quot = P.quot;
+            S.sums = P.sums;
+            S.max_keys = P.max_keys;
+            S.dsums = P.dsums;
+            S.class_vi = d_class;
+            S.flags = d_flags;
+            S.booked = run->d_long_count + 7;
+            HIP_TRY(gs_launch_sn_reduce(&S, run->stream));
+        }
     }
     if (P.stat_recs && !all_long)  // (into copy 0 of the counters; part of the timed region)
         HIP_TRY(gs_launch_stat_reduce(P.stat_recs, run->d_stat_rec_count, rec_room, run->db->info.n_values, run->d_sums, run->d_max,
@@ -5895,6 +5936,21 @@ extern "C" int gs_match_prefilter_info(gs_run *run, int64_t *info) {
         else
             HIP_TRY(hipMemcpy(&n, run->d_long_count + 6, sizeof(n), hipMemcpyDeviceToHost));
         info[2] = (int64_t)n;
+    }
+    return GS_OK;
+}
+
+// info[0]: 1 if the last submitted batch deferred its reads of one tax id (GsSnRec); info[1]: the records it booked.  Synchronises.
+extern "C" int gs_match_sn_info(gs_run *run, int64_t *info) {
+    if (!run || !info) return fail(GS_E_INVALID, "NULL argument");
+    HIP_TRY(hipSetDevice(run->db->device));
+    HIP_TRY(hipStreamSynchronize(run->stream));
+    info[0] = run->sn_last ? 1 : 0;
+    info[1] = 0;
+    if (run->sn_last) {
+        uint32_t n = 0;
+        HIP_TRY(hipMemcpy(&n, run->d_long_count + 7, sizeof(n), hipMemcpyDeviceToHost));
+        info[1] = (int64_t)n;
     }
     return GS_OK;
 }

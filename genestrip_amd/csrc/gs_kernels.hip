@@ -98,6 +98,7 @@ __device__ __forceinline__ void gs_sc_store(int32_t *p, int v) { __hip_atomic_st
 // LONG = true: any length; tag/cnt are this wave's scratch rows of n_values ints, serial its read tag.
 // WIDE = true: maxClassificationPaths in 65..128 (C/GSConfigKey.java:350 allows 1..128): candidate path i lives in
 // lane i & 63 of register set i >> 6; with WIDE = false there is one set and lane = path.
+// slot (FIXED): the trip of the launch this read is, its place in P.sn_recs.
 // FIXED = true (!LONG): the caller's reads all have ONE length with 65 .. 128 k-mer positions (gs_match_kernel): sub-round 0 is
 // full, and the live positions of sub-round 1 come as `live1`, built once per wave; nothing here tests the length.
 // ---------------------------------------------------------------------------------------------------
@@ -105,7 +106,7 @@ template <bool LONG, bool FROM_NODES, int KC, bool WIDE, bool REC, bool STRIPED,
 __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const GsStats &st, int64_t r, u64 off, int L,
                                                 int lane, int (*s_dvi)[128], int (*s_dcnt)[128], int wave_in_block,
                                                 int32_t *tag, int32_t *cnt, int serial, const uint32_t (&pre)[3],
-                                                uint32_t *wave_g, unsigned long long *cur, u64 live1 = 0) {
+                                                uint32_t *wave_g, unsigned long long *cur, u64 live1 = 0, int64_t slot = 0) {
     static_assert(!FIXED || (!LONG && !FROM_NODES), "one iteration, probed here");
     const GsDbDev &db = P.db;
     const int k = KC ? KC : db.k;
@@ -113,6 +114,7 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
     const uint8_t *rd = P.seq + off;
     int out_class = -1;
     int out_flags = 0;
+    bool deferred_sn = false;  // the read went out as a GsSnRec: its outputs are the reduce kernel's
 
     if (FIXED || max > 0) {
         const int64_t read_no = P.first_read_no + r;
@@ -129,9 +131,9 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
         bool deferred = false;                                     // REC: its statistics go into a GsStatRec (P.stat_recs)
         int def_contigs = 0, def_max = 0, def_sq = 0;              // (at most 128 positions: 128^2 fits)
         int def_counted = 0, def_read_kmers = 0, def_tax_err = 0;
-        // counters in LDS, FIXED loop: a read with ONE distinct hit node books nothing on the way.  Its contigs are the runs of its
-        // hit masks, added up in scalar registers, and its statistics are one row of `sums`, one max key and one row of `dsums`:
-        // three LDS instructions at the end of the read
+        // counters in LDS, FIXED loop: a read with ONE distinct hit node and no non-CGAT byte books nothing.  It leaves the wave as
+        // a record of its hit masks (GsSnRec, P.sn_recs) that gs_sn_reduce_kernel turns into contigs, classification, one row of
+        // `sums`, one max key and one row of `dsums`, one lane per record
         constexpr bool SN = FIXED && !REC && !WIDE && (GS_ABLATE & 1) == 0;
         bool sn = false;
         constexpr int NP = WIDE ? 2 : 1;
@@ -227,111 +229,30 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
                 GS_FIRST_NODE()
                 deferred = (m0 | m1) == 0 && P.stat_recs != nullptr;  // one tax id, counters in HBM: no atomics, one record
             }
-            if (SN && (hit0 | hit1) != 0) {  // (as above: decided before anything is booked)
-                // (the first node again under names of this block's own: what the block shares with the code below is live on
-                // every path through the loop and costs the read that hits nothing a dozen scalar moves)
-                const int j1 = hit0 ? __builtin_ctzll(hit0) : 64 + __builtin_ctzll(hit1);
-                const int vi1 = j1 < 64 ? gs_readlane(node[0], j1) : gs_readlane(node[1], j1 - 64);
-                if (((hit0 & ~__ballot(node[0] == vi1)) | (hit1 & ~__ballot(node[1] == vi1))) == 0) {
-                    sn = true;
-                    const int one_vi = vi1, one_cnt = __popcll(hit0) + __popcll(hit1);  // (shadow the general path's)
-                    // every hit position holds one_vi, so a contig is a maximal run of set bits over the 128 positions (positions >= max
-                    // hold NONE and are no hits; the run that reaches max - 1 is the tail flush).  First and last position of every run,
-                    // per word; a run that crosses from word 0 into word 1 has its first position in s0 and its last in e1, so run i
-                    // of word 0 goes from the i-th bit of s0 to the i-th bit of e0 as long as e0 lasts, then comes the crossing run,
-                    // if s0 still holds its first position, then word 1 in the same way.  Lengths are taken one short (last - first):
-                    // sum (l + 1)^2 = sum l^2 + 2 sum l + n with sum l = one_cnt - n.  2 .. 3 trips on a read with 1 % errors
-                    u64 s0 = hit0 & ~(hit0 << 1), s1 = hit1 & ~((hit1 << 1) | (hit0 >> 63));
-                    u64 e0 = hit0 & ~((hit0 >> 1) | (hit1 << 63)), e1 = hit1 & ~(hit1 >> 1);
-                    const int sn_contigs = __popcll(s0) + __popcll(s1);
-                    int sq = 0, lmax = 0;
-#define GS_RUN(first, last)                \
-    {                                      \
-        const int l = (last) - (first);    \
-        sq += l * l;                       \
-        lmax = l > lmax ? l : lmax;        \
-    }
-                    while (e0 != 0) {
-                        const int ps = __builtin_ctzll(s0), pe = __builtin_ctzll(e0);
-                        s0 = gs_bitset0(s0, ps);
-                        e0 = gs_bitset0(e0, pe);
-                        GS_RUN(ps, pe)
-                    }
-                    if (s0 != 0) {
-                        const int ps = __builtin_ctzll(s0), pe = __builtin_ctzll(e1);
-                        e1 = gs_bitset0(e1, pe);
-                        GS_RUN(ps, 64 + pe)
-                    }
-                    while (e1 != 0) {
-                        const int ps = __builtin_ctzll(s1), pe = __builtin_ctzll(e1);
-                        s1 = gs_bitset0(s1, ps);
-                        e1 = gs_bitset0(e1, pe);
-                        GS_RUN(ps, pe)
-                    }
-#undef GS_RUN
-                    const int sn_sq = sq + 2 * one_cnt - sn_contigs, sn_max = lmax + 1;
-                    // classification in closed form, as in 4c below for a read of one node: the only candidate path is one_vi, its
-                    // sum is one_cnt, read_kmers is one_cnt
-                    out_flags = GS_F_FOUND | GS_F_RETURNED;
-                    int counted = 0, tax_err = 0, class_err = 0;
-                    typedef const __attribute__((address_space(4))) GsQuotTable *GsQuotPtr;
-                    const GsQuotPtr qt = (GsQuotPtr)P.quot;
-                    if (P.classify) {
-                        // (n_miss, bad_lo and bad_hi again, from masks the compiler cannot match with theirs: with a second use up
-                        // here their popcounts are no longer sunk into the classification below, and every read that hits nothing
-                        // pays some twenty scalar instructions for them.  FIXED: word 0 whole, of word 1 live1 >> 1, of word 2 none)
-                        // The miss masks are hidden by their compare VALUE, not as masks: a ballot whose compare lives in another block
-                        // comes back through the vector unit (v_cndmask 0/1 + v_cmp_ne per mask).  live1 is hidden too: its shifted
-                        // copy and the complement are otherwise built in front of the loop, spilled and read back lane by lane
-                        int miss = GS_NODE_MISS;
-                        u64 b0 = Bbad[0], b1 = Bbad[1], b2 = Bbad[2], l1 = live1;
-                        asm volatile("" : "+s"(miss), "+s"(b0), "+s"(b1), "+s"(b2), "+s"(l1));
-                        const u64 q0 = __ballot(node[0] == miss), q1 = __ballot(node[1] == miss);
-                        const u64 lo1 = l1 >> 1;
-                        tax_err = __popcll(q0) + __popcll(q1) + __popcll(b0) + __popcll(b1 & lo1) + ((((b1 & ~lo1) | b2) != 0) ? 1 : 0);
-                        if (((qt->tax_disabled[tax_err >> 5] >> (tax_err & 31)) & 1u) == 0) {
-                            out_class = (P.threshold <= 1 || one_cnt >= P.threshold) ? one_vi : -1;
-                            if (out_class < 0) {
-                                out_flags &= ~GS_F_RETURNED;
-                            } else {
-                                class_err = max - one_cnt;
-                                counted = (int)((qt->class_counted[class_err >> 5] >> (class_err & 31)) & 1u);
-                                if (counted) out_flags |= GS_F_COUNTED;
-                            }
+            if (SN) {  // (as above: decided before anything is booked)
+                GsSnRec *const recs = P.sn_recs;
+                if (recs != nullptr) {
+                    if ((hit0 | hit1) != 0 && (Bbad[0] | Bbad[1] | Bbad[2]) == 0) {
+                        // (the first node under names of this block's own: what the block shares with the code below is live on
+                        // every path through the loop and costs the read that hits nothing a dozen scalar moves)
+                        const int j1 = hit0 ? __builtin_ctzll(hit0) : 64 + __builtin_ctzll(hit1);
+                        const int vi1 = j1 < 64 ? gs_readlane(node[0], j1) : gs_readlane(node[1], j1 - 64);
+                        if (((hit0 & ~__ballot(node[0] == vi1)) | (hit1 & ~__ballot(node[1] == vi1))) == 0) {
+                            // every hit position holds vi1 and no window holds a bad base: the read is its two hit masks.  Lanes
+                            // 0 .. 5 take the six words of the record (v_writelane from the scalar values) and store them with one
+                            // instruction; the read books nothing and writes no output here
+                            sn = deferred_sn = true;
+                            int w = 0;
+                            w = gs_writelane<0>(w, (int)(uint32_t)hit0);
+                            w = gs_writelane<1>(w, (int)(uint32_t)(hit0 >> 32));
+                            w = gs_writelane<2>(w, (int)(uint32_t)hit1);
+                            w = gs_writelane<3>(w, (int)(uint32_t)(hit1 >> 32));
+                            w = gs_writelane<4>(w, vi1);
+                            w = gs_writelane<5>(w, (int)(uint32_t)r);
+                            if (GS_ACT(0x3fULL)) reinterpret_cast<int *>(recs + slot)[lane] = w;
                         }
                     }
-                    // the read's row: lane c holds column c of `sums` (v_writelane from the scalar totals), lanes 0 .. 6 add it with
-                    // one ds_add_u64; lane 7 takes the max key; lanes 0 .. 3 add the four doubles of a counted read.  The lane number
-                    // the addresses are built from is hidden from the compiler: with an address it can prove to be the same in every
-                    // active lane, each atomic is wrapped into the scaffold that elects one lane and multiplies by the number of
-                    // active ones
-                    int lz = lane;
-                    asm volatile("" : "+v"(lz));
-                    int row = 0;
-                    row = gs_writelane<GS_S_READS>(row, counted);
-                    row = gs_writelane<GS_S_READS_KMERS>(row, counted ? one_cnt : 0);
-                    row = gs_writelane<GS_S_KMERS>(row, one_cnt);
-                    row = gs_writelane<GS_S_CONTIGS>(row, sn_contigs);
-                    row = gs_writelane<GS_S_CONTIG_LEN_SQ_SUM>(row, sn_sq);
-                    row = gs_writelane<GS_S_READS_1KMER>(row, 1);
-                    row = gs_writelane<GS_S_READS_BPS>(row, counted ? L : 0);
-                    if (GS_ACT((1ULL << GS_N_SUMS) - 1ULL)) st.add(one_vi, lz, (u64)(uint32_t)row);
-                    if (GS_ACT(1ULL << GS_N_SUMS)) st.max(one_vi + lz - GS_N_SUMS, ((u64)sn_max << 40) | key_lo);
-                    if (counted) {
-                        int dlo = 0, dhi = 0;
-#define GS_DCOL(c, val)                                             \
-    {                                                               \
-        const u64 b = (u64)__double_as_longlong(val);               \
-        dlo = gs_writelane<c>(dlo, (int)(uint32_t)b);               \
-        dhi = gs_writelane<c>(dhi, (int)(uint32_t)(b >> 32));       \
-    }
-                        GS_DCOL(GS_D_ERR_SUM, qt->e[tax_err].q)
-                        GS_DCOL(GS_D_ERR_SQ_SUM, qt->e[tax_err].q2)
-                        GS_DCOL(GS_D_CLASS_ERR_SUM, qt->e[class_err].q)
-                        GS_DCOL(GS_D_CLASS_ERR_SQ_SUM, qt->e[class_err].q2)
-#undef GS_DCOL
-                        if (GS_ACT((1ULL << GS_N_DCOLS) - 1ULL)) st.dadd(one_vi, lz, __longlong_as_double((long long)(((u64)(uint32_t)dhi << 32) | (u64)(uint32_t)dlo)));
-                    }
+                    if (!sn && GS_ACT(1ULL)) recs[slot].vi = -1;
                 }
             }
             if ((GS_ABLATE & 1) == 0 && !(SN && sn) && ((hit0 | hit1) != 0 || carry_last >= 0)) {
@@ -702,7 +623,7 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
         // region, both pointers fetched together, lane 0 as a literal mask
         int32_t *const cv = P.class_vi;
         uint8_t *const fl = P.flags;
-        if (((uintptr_t)cv | (uintptr_t)fl) != 0 && GS_ACT(1ULL)) {
+        if (((uintptr_t)cv | (uintptr_t)fl) != 0 && !deferred_sn && GS_ACT(1ULL)) {  // (a deferred read's: gs_sn_reduce_kernel)
             if (cv) cv[r] = out_class;
             if (fl) fl[r] = (uint8_t)out_flags;
         }
@@ -953,7 +874,7 @@ __global__ __launch_bounds__(GS_BLOCK) __attribute__((amdgpu_waves_per_eu(GS_WAV
                 for (int w = 0; w < 3; w++) pre[w] = 64 * w + lane < L ? rd[64 * w + lane] : GS_FILL;
             }
             gs_process_read<false, FROM_NODES, KC, WIDE, !LDS_STATS, STRIPED, CTX, FIXED>(Q, st, r, off, L, lane, s_dvi, s_dcnt, wave_in_block, nullptr, nullptr, 0,
-                                                                                          pre, s_g[wave_in_block], s_cur[wave_in_block], fixed_live1);
+                                                                                          pre, s_g[wave_in_block], s_cur[wave_in_block], fixed_live1, t);
         }
     };
     if constexpr (CAN_FIX) {

@@ -99,6 +99,10 @@ hipError_t gs_launch_match_long(const GsMatchParams *P, int grid, int32_t *scrat
 hipError_t gs_launch_stat_reduce(const GsStatRec *recs, const void *count, int64_t n_max, int n_values, void *sums, void *maxk, void *dsums,
                                  int32_t *vi_scratch, hipStream_t stream);
 int gs_match_occupancy(int n_values);
+
+// ---- gs_snreduce.hip: the records of the reads of one tax id (GsSnRec) into the counters, behind gs_launch_match
+hipError_t gs_launch_sn_reduce(const GsSnReduceParams *P, hipStream_t stream);
+
 int gs_match_long_occupancy(int n_values);
 
 // ---- gs_route.hip: the DB-partitioned mode

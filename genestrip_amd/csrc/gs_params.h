@@ -4,6 +4,7 @@
 
 #include "../../include/gsgpu.h"
 #include "gs_layout.h"
+#include "gs_snrec.h"
 
 #define GS_BLOCK 256   // 4 waves per workgroup
 #ifndef GS_NV_LDS
@@ -32,22 +33,7 @@ struct GsStatRec {
 };
 static_assert(sizeof(GsStatRec) == 64, "GsStatRec");
 
-// What a batch of ONE read length (gs_match_submit_fixed, the FIXED loop of gs_match_kernel) knows before its first read: with
-// max = read_len - k + 1 <= 128 positions, tax_err and class_err are integers in 0 .. max, so both error gates are one bit per
-// value and both quotients one table entry.  Built on the host (launch_batch) with the very expressions of the general loop, in
-// plain double arithmetic: i / max is the correctly rounded quotient on the host as on the device.
-// (tax_err <= max: a window with a bad base is INVALID, never a MISS, so n_miss + bad_lo counts every position below max - 1 at
-// most once, and a bad base behind them (bad_hi) makes the last window INVALID.  class_err = max - read_kmers, 1 <= read_kmers.)
-#define GS_QUOT_ENTRIES 129
-#define GS_QUOT_WORDS ((GS_QUOT_ENTRIES + 31) / 32)
-struct GsQuotEntry {
-    double q, q2;  // i / max and its square
-};
-struct GsQuotTable {
-    GsQuotEntry e[GS_QUOT_ENTRIES];
-    uint32_t tax_disabled[GS_QUOT_WORDS];   // bit i: tax_err == i fails the max_read_tax_err gate
-    uint32_t class_counted[GS_QUOT_WORDS];  // bit i: class_err == i passes the max_read_class_err gate
-};
+// (GsQuotTable -- gates and quotients of a batch of one read length -- and GsSnRec: gs_snrec.h)
 
 struct GsMatchParams {
     GsDbDev db;
@@ -113,6 +99,27 @@ struct GsMatchParams {
     // there are *surv_count of them (both written by gs_pf_kernel on the same stream).  nullptr: every read of the batch, in order.
     const uint32_t *surv_list;
     const uint32_t *surv_count;
+    // The FIXED loop with counters in LDS: a read of one tax id without a non-CGAT byte writes sn_recs[t] (t: the trip, i.e. the index
+    // into surv_list, or the read's number) and books nothing; every other read writes vi = -1 there.  gs_sn_reduce_kernel follows
+    // on the same stream.  nullptr: nothing is deferred, every read is booked by the wave that probed it.
+    GsSnRec *sn_recs;
+};
+
+// gs_snreduce.hip: the records of a batch into the run's counters and per-read outputs, one lane per record
+struct GsSnReduceParams {
+    const GsSnRec *recs;
+    const uint32_t *count;     // records of the launch: *count (the survivors of the prefilter), nullptr: n_reads
+    int64_t n_reads;
+    int64_t first_read_no;
+    GsSnConst c;
+    int32_t n_values, stat_copies;
+    const GsQuotTable *quot;
+    int64_t *sums;             // the run's counters in stat_copies copies, as GsMatchParams
+    int64_t *max_keys;
+    double *dsums;
+    int32_t *class_vi;         // per-read outputs of the batch or nullptr
+    uint8_t *flags;
+    unsigned int *booked;      // += records with vi >= 0 (one atomic per workgroup)
 };
 #define GS_HUGE_MIN (1 << 15)
 #define GS_HUGE_SLOTS 256       // (= GS_BLOCK: one thread per slot where the chunks are counted)
