@@ -65,7 +65,7 @@ ABI_SYMBOLS = (
     "gs_accmap_create", "gs_accmap_submit", "gs_accmap_append", "gs_accmap_finish", "gs_accmap_fetch", "gs_accmap_lookup",
     "gs_accmap_lookup_genomes", "gs_accmap_get_device", "gs_accmap_kernel_time", "gs_accmap_destroy",
     "gs_taxtree_create", "gs_taxtree_submit_nodes", "gs_taxtree_append_nodes", "gs_taxtree_finish_nodes", "gs_taxtree_submit_names", "gs_taxtree_append_names", "gs_taxtree_finish_times",
-    "gs_taxtree_fetch", "gs_taxtree_fetch_names", "gs_taxtree_select", "gs_taxtree_small", "gs_taxtree_read_taxids",
+    "gs_taxtree_fetch", "gs_taxtree_fetch_names", "gs_taxtree_select", "gs_taxtree_small", "gs_taxtree_regions_below", "gs_taxtree_read_taxids",
     "gs_taxtree_get_device", "gs_taxtree_kernel_time", "gs_taxtree_destroy",
 )
 
@@ -282,6 +282,7 @@ def lib():
         "gs_taxtree_finish_times": (ci, [vp, vp]), "gs_taxtree_fetch": (ci, [vp, vp, vp, vp, vp, vp, vp]),
         "gs_taxtree_fetch_names": (ci, [vp, vp, vp, i64]), "gs_taxtree_select": (ci, [vp, vp, i64, vp, i64, ci, vp, vp]),
         "gs_taxtree_small": (ci, [vp, vp, ci, ci, vp, vp, vp, vp, vp]), "gs_taxtree_read_taxids": (ci, [vp, i64, vp, vp, vp, vp, i64]),
+        "gs_taxtree_regions_below": (ci, [vp, vp, ci, vp, i64, i32, ci, vp, vp, vp]),
         "gs_taxtree_get_device": (ci, [vp, vp]), "gs_taxtree_kernel_time": (ci, [vp, ci, vp, vp]), "gs_taxtree_destroy": (ci, [vp]),
         "gs_genomes_create": (ci, [vp, ci]), "gs_genomes_scan": (ci, [vp, vp, i64, ci, ci, vp, vp, vp, vp]),
         "gs_genomes_headers": (ci, [vp, vp, vp]), "gs_genomes_gather": (ci, [vp, vp, vp, vp]), "gs_genomes_regions": (ci, [vp, vp, vp]),
@@ -2106,8 +2107,38 @@ class DeviceTaxTree:
         _check(lib().gs_taxtree_small(self.h, p, size, mem, C.byref(n_small), *(_ptr(out[k])[0] for k in ("node_of_vi", "parent_vi", "depth", "position"))))
         return {k: v[:n_small.value] for k, v in out.items()}
 
+    def regions_below(self, regions, selected, limit, check_rank=None, refseq_db=True, rna_only=False):
+        """the taxfromgenbank set.  regions: int32[n_nodes], entries of an accession map per node itself (DeviceAccessionMap.fetch's
+        regions; a host array or a tensor on the tree's device); selected: the taxnodes set as node indices, or as select()'s
+        uint8[n_nodes]; limit: refSeq.limitForGenbankAccess; check_rank: refSeq.limitForGenbankRank as a rank name, an ordinal or
+        None for any rank -> (below, inclusive): the selected nodes of that rank whose count is below limit, ascending, and
+        int32[n_nodes], the count per node with everything below it.  What the goal puts in front is applied here: refseq_db False
+        (refseq.filldb off) gives the whole selection, rna_only (SeqType.RNA) or limit <= 0 an empty set"""
+        sel = np.asarray(selected)
+        if sel.dtype == np.uint8 and sel.shape == (self.n_nodes,):
+            sel = np.flatnonzero(sel)
+        sel = np.ascontiguousarray(sel, dtype=np.int32).reshape(-1)
+        if not hasattr(regions, "device") or isinstance(regions, np.ndarray):
+            regions = np.ascontiguousarray(regions, dtype=np.int32)
+        if int(regions.shape[0]) != self.n_nodes:
+            raise ValueError("one region count per node")
+        _ready(regions)
+        p, mem = _ptr(regions)
+        rank = -1 if check_rank is None else RANK_NAMES.index(check_rank) if isinstance(check_rank, str) else int(check_rank)
+        incl = np.zeros(max(self.n_nodes, 1), dtype=np.int32)
+        below = np.zeros(max(len(sel), 1), dtype=np.int32)
+        n_below = C.c_int64()
+        _check(lib().gs_taxtree_regions_below(self.h, p, mem, _ptr(sel)[0] if len(sel) else None, len(sel), int(limit), rank, _ptr(incl)[0],
+                                              _ptr(below)[0], C.byref(n_below)))
+        incl = incl[:self.n_nodes]
+        if not refseq_db:
+            return np.unique(sel), incl
+        if rna_only or limit <= 0:
+            return below[:0], incl
+        return below[:n_below.value], incl
+
     def kernel_time(self, profile=True):
-        """(launches, milliseconds) of the scan, finish, select and small kernels so far; switches their timing on or off"""
+        """(launches, milliseconds) of the scan, finish, select, small and regions kernels so far; switches their timing on or off"""
         n, ms = C.c_int64(), C.c_double()
         _check(lib().gs_taxtree_kernel_time(self.h, int(profile), C.byref(n), C.byref(ms)))
         return n.value, ms.value

@@ -8309,6 +8309,103 @@ extern "C" int gs_taxtree_small(gs_taxtree *h, const void *flagged, int flag_byt
 }
 GS_API_CATCH
 
+extern "C" int gs_taxtree_regions_below(gs_taxtree *h, const int32_t *regions, int mem, const int32_t *selected, int64_t n_selected, int32_t limit,
+                                        int check_rank, int32_t *inclusive, int32_t *below, int64_t *n_below) try {
+    if (!h || !regions) return fail(GS_E_INVALID, "NULL argument");
+    if (n_selected < 0 || (n_selected > 0 && !selected)) return fail(GS_E_INVALID, "the selection is NULL or its length negative");
+    if (check_rank < -1 || check_rank >= GS_TT_N_RANKS) return fail(GS_E_INVALID, "check_rank is -1 (any) or the ordinal of a rank");
+    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    if (h->state != 1) return fail(GS_E_STATE, "gs_taxtree_regions_below comes behind gs_taxtree_finish_nodes");
+    if (h->host_only && mem != GS_MEM_HOST) return fail(GS_E_UNSUPPORTED, "a host-only tree reads host memory alone");
+    const int32_t n = h->tree.n;
+    const size_t N = (size_t)n;
+    for (int64_t i = 0; i < n_selected; i++)
+        if (selected[i] < 0 || selected[i] >= n) return fail(GS_E_INVALID, "a selected node is no index into the tree");
+    if (mem == GS_MEM_HOST)
+        for (size_t v = 0; v < N; v++)
+            if (regions[v] < 0) return fail(GS_E_INVALID, "a region count is negative");
+    const char *cycle = "gs_taxtree_regions_below: a node with regions stands on or below a cycle of parent links: the reference's walk does not end";
+    std::vector<int32_t> incl(N), out;
+    if (h->on_host) {
+        if (mem == GS_MEM_DEVICE) {
+            HIP_TRY(hipSetDevice(h->device));
+            HIP_TRY(hipMemcpy(incl.data(), regions, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+        } else {
+            memcpy(incl.data(), regions, N * sizeof(int32_t));
+        }
+        const std::vector<int32_t> own(incl);
+        if (!gs_host::tax_regions_up(h->tree.parent.data(), n, own.data(), nullptr, incl.data())) return fail(GS_E_INVALID, cycle);
+        gs_host::tax_regions_below(incl.data(), h->tree.rank.data(), n, selected, n_selected, limit, check_rank, out);
+    } else {
+        HIP_TRY(hipSetDevice(h->device));
+        const size_t R = (size_t)h->n_reach, S = (size_t)n_selected;
+        size_t tmp_bytes = 0;
+        HIP_TRY(gs_taxtree_sort_bytes((int64_t)N, &tmp_bytes));
+        uint32_t *w = nullptr;  // pre R | sum R | incl N | flag N | idx N | out N | selected | regions, if they come from the host
+        uint8_t *marks = nullptr;
+        void *tmp = nullptr;
+        hipError_t e = gs_dev_alloc(&w, (2 * R + 4 * N + S + (mem == GS_MEM_HOST ? N : 0) + 1) * sizeof(uint32_t));
+        if (e == hipSuccess) e = gs_dev_alloc(&marks, N);
+        if (e == hipSuccess) e = gs_dev_alloc(&tmp, std::max<size_t>(tmp_bytes, 1));
+        int32_t *d_incl = (int32_t *)(w + 2 * R), *d_out = (int32_t *)(w + 2 * R + 3 * N), *d_sel = d_out + N;
+        uint32_t *d_flag = w + 2 * R + N, *d_idx = d_flag + N;
+        const int32_t *d_regions = regions;
+        if (e == hipSuccess && mem == GS_MEM_HOST) {
+            e = hipMemcpyAsync(d_sel + S, regions, N * sizeof(int32_t), hipMemcpyHostToDevice, h->stream);
+            d_regions = d_sel + S;
+        }
+        if (e == hipSuccess && S) e = hipMemcpyAsync(d_sel, selected, S * sizeof(int32_t), hipMemcpyHostToDevice, h->stream);
+        int rc = e == hipSuccess ? timer_start(h->timer, h->profile, h->stream) : hip_fail(e, "gs_taxtree_regions_below");
+        if (!rc) {
+            e = gs_launch_taxtree_regions(&h->A, h->n_reach, d_regions, w, w + R, tmp, tmp_bytes, d_incl, h->stream);
+            if (e == hipSuccess) rc = timer_stop(h->timer, h->profile, h->stream);
+            if (e != hipSuccess) rc = hip_fail(e, "gs_taxtree_regions_below");
+        }
+        if (!rc && R < N) {  // what the root does not reach: the parent walk, on the host
+            std::vector<int32_t> parent(N), position(N);
+            e = hipMemcpyAsync(incl.data(), d_incl, N * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(parent.data(), h->A.parent, N * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(position.data(), h->A.position, N * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+            if (e != hipSuccess) {
+                rc = hip_fail(e, "gs_taxtree_regions_below");
+            } else {
+                const std::vector<int32_t> own(incl);
+                if (!gs_host::tax_regions_up(parent.data(), n, own.data(), position.data(), incl.data())) rc = fail(GS_E_INVALID, cycle);
+            }
+            if (!rc) {
+                e = hipMemcpyAsync(d_incl, incl.data(), N * sizeof(int32_t), hipMemcpyHostToDevice, h->stream);
+                if (e != hipSuccess) rc = hip_fail(e, "gs_taxtree_regions_below");
+            }
+        }
+        uint32_t last[2] = {0, 0};
+        if (!rc) rc = timer_start(h->timer, h->profile, h->stream);
+        if (!rc) {
+            e = gs_launch_taxtree_below(&h->A, d_sel, n_selected, d_incl, limit, check_rank, marks, d_flag, d_idx, tmp, tmp_bytes, d_out, h->stream);
+            if (e == hipSuccess) rc = timer_stop(h->timer, h->profile, h->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(&last[0], d_flag + N - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(&last[1], d_idx + N - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess && inclusive && R == N) e = hipMemcpyAsync(incl.data(), d_incl, N * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+            out.resize((size_t)last[0] + last[1]);
+            if (e == hipSuccess && !out.empty()) e = hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+            if (e != hipSuccess) rc = hip_fail(e, "gs_taxtree_regions_below");
+        }
+        e = hipStreamSynchronize(h->stream);
+        if (!rc && e != hipSuccess) rc = hip_fail(e, "gs_taxtree_regions_below");
+        gs_dev_free(w);
+        gs_dev_free(marks);
+        gs_dev_free(tmp);
+        if (!rc) rc = timer_collect(h->timer);
+        if (rc) return rc;
+    }
+    if (inclusive) memcpy(inclusive, incl.data(), N * sizeof(int32_t));
+    if (below && !out.empty()) memcpy(below, out.data(), out.size() * sizeof(int32_t));
+    if (n_below) *n_below = (int64_t)out.size();
+    return GS_OK;
+}
+GS_API_CATCH
+
 extern "C" int gs_taxtree_finish_times(gs_taxtree *h, double ms[3]) try {
     if (!h || !ms) return fail(GS_E_INVALID, "NULL argument");
     if (h->state != 1) return fail(GS_E_STATE, "gs_taxtree_finish_times comes behind gs_taxtree_finish_nodes");

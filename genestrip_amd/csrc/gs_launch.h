@@ -283,6 +283,10 @@ hipError_t gs_launch_taxtree_select(const GsTaxTreeArrays *A, const int32_t *req
 hipError_t gs_launch_taxtree_small(const GsTaxTreeArrays *A, int32_t n_reach, const uint8_t *flag8, const int32_t *flag32, uint32_t *pre, uint32_t *sum,
                                    uint32_t *req, uint32_t *vi, void *tmp, size_t tmp_bytes, int32_t *node_of_vi, int32_t *parent_vi, int32_t *depth,
                                    int32_t *position, hipStream_t stream);
+hipError_t gs_launch_taxtree_regions(const GsTaxTreeArrays *A, int32_t n_reach, const int32_t *regions, uint32_t *pre, uint32_t *sum, void *tmp, size_t tmp_bytes,
+                                     int32_t *incl, hipStream_t stream);
+hipError_t gs_launch_taxtree_below(const GsTaxTreeArrays *A, const int32_t *selected, int64_t n_sel, const int32_t *incl, int32_t limit, int check_rank,
+                                   uint8_t *marks, uint32_t *flag, uint32_t *idx, void *tmp, size_t tmp_bytes, int32_t *out, hipStream_t stream);
 
 }  // extern "C"
 

@@ -163,6 +163,32 @@ struct TaxNodesExact : TaxLines {
     }
 };
 
+// TaxIdNode.incRefSeqRegions (C/tax/TaxTree.java:517-521) without the node itself: regions[v] of every node v -- with `only`, of
+// every node with only[v] < 0 -- is added to incl[u] for each u above v on its parent chain (mod 2^32).  false: a node with
+// regions stands on or below a cycle of parent links, where the reference's walk does not end
+inline bool tax_regions_up(const int32_t *parent, int32_t n, const int32_t *regions, const int32_t *only, int32_t *incl) {
+    for (int32_t v = 0; v < n; v++) {
+        if (regions[(size_t)v] == 0 || (only && only[(size_t)v] >= 0)) continue;
+        int32_t steps = 0;
+        for (int32_t u = parent[(size_t)v]; u != -1; u = parent[(size_t)u]) {
+            if (steps++ >= n) return false;
+            incl[(size_t)u] = (int32_t)((uint32_t)incl[(size_t)u] + (uint32_t)regions[(size_t)v]);
+        }
+    }
+    return true;
+}
+
+// TaxNodesFromGenbankGoal's loop (C/goals/genbank/TaxNodesFromGenbankGoal.java:86-92) over node indices: the selected nodes of the
+// rank asked for (check_rank < 0: any) whose count is below limit, once each, ascending
+inline void tax_regions_below(const int32_t *incl, const int32_t *rank, int32_t n, const int32_t *selected, int64_t n_sel, int32_t limit, int check_rank,
+                              std::vector<int32_t> &below) {
+    std::vector<uint8_t> marks((size_t)n, 0);
+    for (int64_t i = 0; i < n_sel; i++) marks[(size_t)selected[i]] = 1;
+    below.clear();
+    for (int32_t v = 0; v < n; v++)
+        if (marks[(size_t)v] && (check_rank < 0 || rank[(size_t)v] == check_rank) && incl[(size_t)v] < limit) below.push_back(v);
+}
+
 // the tree over slots, with the reference's literal child lists
 struct TaxHostTree {
     int32_t n = 0, root = -1;

@@ -49,6 +49,13 @@
 // small tree (markRequired, SmallTaxTree(TaxTree), initStoreIndices): a node the root reaches is required if a flag lies in
 // [position, position + subtree) of the flags in pre-order; the value index is the rank among the required nodes in pre-order.
 //   gs_tt_preflag_kernel, rocPRIM scan, gs_tt_required_kernel, rocPRIM scan, gs_tt_small_kernel
+// regions below (TaxIdNode.incRefSeqRegions, C/tax/TaxTree.java:517-521, counts an entry of the accession map for its node and for
+// every node of the parent chain; TaxNodesFromGenbankGoal, C/goals/genbank/TaxNodesFromGenbankGoal.java:86-92, keeps the selected
+// nodes whose count is below a limit): for a node the root reaches that count is the sum of the per-node counts over
+// [position, position + subtree) in pre-order -- one scatter, one scan, one difference.  Sums are kept mod 2^32: a count below 2^31
+// comes out exactly.  The selection is marked per node, so the nodes come out once each and in ascending index.
+//   gs_tt_regions_pre_kernel, rocPRIM scan, gs_tt_regions_incl_kernel; gs_tt_mark_kernel, gs_tt_below_flag_kernel, rocPRIM scan,
+//   gs_tt_below_out_kernel
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -798,5 +805,70 @@ extern "C" hipError_t gs_launch_taxtree_small(const GsTaxTreeArrays *A, int32_t 
     e = rocprim::exclusive_scan(tmp, tmp_bytes, req, vi, 0u, (size_t)n_reach, rocprim::plus<uint32_t>(), stream);
     if (e != hipSuccess) return e;
     TT_LAUNCH(gs_tt_small_kernel, n_reach, stream, *A, n_reach, req, vi, node_of_vi, parent_vi, depth, position);
+    return hipGetLastError();
+}
+
+// ---- regions with ancestors, and the selected nodes below a limit
+// pre[p] = the regions of the node at position p
+__global__ __launch_bounds__(256) void gs_tt_regions_pre_kernel(GsTaxTreeArrays A, int32_t n_reach, const int32_t *regions, uint32_t *pre) {
+    const int32_t p = (int32_t)(blockIdx.x * 256 + threadIdx.x);
+    if (p >= n_reach) return;
+    pre[p] = (uint32_t)regions[A.node_at[p]];
+}
+
+// sum: the exclusive scan of pre.  incl[v] = the regions in [position, position + subtree) for a node the root reaches; its own
+// regions else: what hangs below such a node is added on the host
+__global__ __launch_bounds__(256) void gs_tt_regions_incl_kernel(GsTaxTreeArrays A, const int32_t *regions, const uint32_t *pre, const uint32_t *sum, int32_t *incl) {
+    const int32_t v = (int32_t)(blockIdx.x * 256 + threadIdx.x);
+    if (v >= A.n) return;
+    const int32_t p = A.position[v];
+    if (p < 0) {
+        incl[v] = regions[v];
+        return;
+    }
+    const int32_t last = p + A.subtree[v] - 1;
+    incl[v] = (int32_t)(sum[last] + pre[last] - sum[p]);
+}
+
+// marks[v] != 0: v is in the selection.  flag[v] = 1 if it is, has the rank asked for (check_rank < 0: any) and incl[v] < limit
+__global__ __launch_bounds__(256) void gs_tt_below_flag_kernel(GsTaxTreeArrays A, const uint8_t *marks, const int32_t *incl, int32_t limit, int check_rank,
+                                                               uint32_t *flag) {
+    const int32_t v = (int32_t)(blockIdx.x * 256 + threadIdx.x);
+    if (v >= A.n) return;
+    flag[v] = marks[v] && (check_rank < 0 || A.rank[v] == check_rank) && incl[v] < limit;
+}
+
+// idx: the exclusive scan of flag
+__global__ __launch_bounds__(256) void gs_tt_below_out_kernel(int32_t n, const uint32_t *flag, const uint32_t *idx, int32_t *out) {
+    const int32_t v = (int32_t)(blockIdx.x * 256 + threadIdx.x);
+    if (v >= n || !flag[v]) return;
+    out[idx[v]] = v;
+}
+
+// incl[n] out of regions[n] (device); pre, sum: n_reach words each; tmp as gs_taxtree_sort_bytes(n) says
+extern "C" hipError_t gs_launch_taxtree_regions(const GsTaxTreeArrays *A, int32_t n_reach, const int32_t *regions, uint32_t *pre, uint32_t *sum, void *tmp,
+                                                size_t tmp_bytes, int32_t *incl, hipStream_t stream) {
+    if (n_reach > 0) {
+        TT_LAUNCH(gs_tt_regions_pre_kernel, n_reach, stream, *A, n_reach, regions, pre);
+        hipError_t e = rocprim::exclusive_scan(tmp, tmp_bytes, pre, sum, 0u, (size_t)n_reach, rocprim::plus<uint32_t>(), stream);
+        if (e != hipSuccess) return e;
+    }
+    TT_LAUNCH(gs_tt_regions_incl_kernel, A->n, stream, *A, regions, pre, sum, incl);
+    return hipGetLastError();
+}
+
+// selected: n_sel node indices on the device; marks: n bytes; flag, idx: n words each; out: n words, filled in ascending node
+// index; how many: idx[n - 1] + flag[n - 1]
+extern "C" hipError_t gs_launch_taxtree_below(const GsTaxTreeArrays *A, const int32_t *selected, int64_t n_sel, const int32_t *incl, int32_t limit,
+                                              int check_rank, uint8_t *marks, uint32_t *flag, uint32_t *idx, void *tmp, size_t tmp_bytes, int32_t *out,
+                                              hipStream_t stream) {
+    const int32_t n = A->n;
+    hipError_t e = hipMemsetAsync(marks, 0, (size_t)n, stream);
+    if (e != hipSuccess) return e;
+    if (n_sel > 0) TT_LAUNCH(gs_tt_mark_kernel, n_sel, stream, selected, n_sel, (uint8_t)1, marks);
+    TT_LAUNCH(gs_tt_below_flag_kernel, n, stream, *A, marks, incl, limit, check_rank, flag);
+    e = rocprim::exclusive_scan(tmp, tmp_bytes, flag, idx, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream);
+    if (e != hipSuccess) return e;
+    TT_LAUNCH(gs_tt_below_out_kernel, n, stream, n, flag, idx, out);
     return hipGetLastError();
 }

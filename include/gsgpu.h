@@ -1223,6 +1223,20 @@ int gs_accmap_destroy(gs_accmap *am);
  *                          flagged descendant, and the root, in pre-order: *n_small and, per value index, node_of_vi, parent_vi
  *                          (-1 for the root: what gs_dbbuild_begin takes), depth, position (host, room for info[1] entries; any
  *                          may be NULL).  position is the FULL tree's, as SmallTaxTree's constructor copies it.
+ * gs_taxtree_regions_below the taxfromgenbank set (C/goals/genbank/TaxNodesFromGenbankGoal.java:86-92).  regions[n]: entries of the
+ *                          accession map per node ITSELF, as gs_accmap_fetch gives them, host or device memory (host: a negative
+ *                          count is GS_E_INVALID; device: taken as it is).  The count the goal compares is the one of
+ *                          TaxIdNode.incRefSeqRegions (C/tax/TaxTree.java:517-521): the entries whose node is this node or has it
+ *                          on its parent chain.  For the nodes the root reaches the device scatters regions to pre-order, scans
+ *                          once and takes the difference over [position, position + subtree); what the root does not reach, a
+ *                          tree that lives on the host and a host-only tree walk parents on the host.  Sums are kept mod 2^32, so
+ *                          a count below 2^31 is exact.  A node with regions on or below a cycle of parent links: GS_E_INVALID
+ *                          (the reference's walk does not end).  selected: n_selected node indices (host; the taxnodes set).
+ *                          inclusive[n] (host, may be NULL): the count per node.  below (host, room for n_selected, may be NULL)
+ *                          and *n_below (may be NULL): the selected nodes with rank == check_rank (-1: any rank) and
+ *                          inclusive < limit, once each, in ascending node index (the reference's set has no order).  What the
+ *                          goal puts in front stays with the caller: without refseq.filldb the set is the whole selection; with
+ *                          SeqType.RNA, or with limit <= 0, it is empty (:74-84).
  * gs_taxtree_read_taxids   TaxIdCollector.readFromFile over the bytes of a tax id file: the ids (1-9 digits) of requested and
  *                          of '-' lines; at most cap of each are written, the counts say how many there are.
  * gs_taxtree_finish_times  ms[3] of the last finish between events, if profiling was on: distinct ids and parents (one key sort, one
@@ -1243,6 +1257,8 @@ int gs_taxtree_select(gs_taxtree *t, const int32_t *requested, int64_t n_request
                       uint8_t *out, int64_t *count);
 int gs_taxtree_small(gs_taxtree *t, const void *flagged, int flag_bytes, int mem, int32_t *n_small, int32_t *node_of_vi, int32_t *parent_vi,
                      int32_t *depth, int32_t *position);
+int gs_taxtree_regions_below(gs_taxtree *t, const int32_t *regions, int mem, const int32_t *selected, int64_t n_selected, int32_t limit, int check_rank,
+                             int32_t *inclusive, int32_t *below, int64_t *n_below);
 int gs_taxtree_read_taxids(const uint8_t *text, int64_t n_bytes, int32_t *requested, int64_t *n_requested, int32_t *excluded, int64_t *n_excluded,
                            int64_t cap);
 int gs_taxtree_get_device(gs_taxtree *t, int *device);
