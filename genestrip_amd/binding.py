@@ -1408,11 +1408,12 @@ class FastqKMerMatcher:
         return {"built": bool(info[0]), "n_lmers": int(info[1]), "survivors": int(info[2]), "reads": int(info[3])}
 
     def sn_info(self):
-        """Reads of one tax id that left the match kernel as records (fixed-length batches, counters in LDS): {"deferred": the last
-        submitted batch ran that way, "booked": the records the reduce kernel booked for it}.  Synchronises."""
-        info = (C.c_int64 * 2)()
+        """Reads that left the match kernel as records (fixed-length batches, counters in LDS): {"deferred": the last submitted
+        batch ran that way, "booked": the records of reads of one tax id the reduce kernel booked for it, "rows": the reads that
+        left as the node of every position (several tax ids, or a non-CGAT byte)}.  Synchronises."""
+        info = (C.c_int64 * 3)()
         _check(lib().gs_match_sn_info(self.h, info))
-        return {"deferred": bool(info[0]), "booked": int(info[1])}
+        return {"deferred": bool(info[0]), "booked": int(info[1]), "rows": int(info[2])}
 
     def close(self):
         if getattr(self, "h", None):

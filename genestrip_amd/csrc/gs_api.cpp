@@ -2234,12 +2234,17 @@ struct gs_run {
     int pf_pause = 0;                  // batches that still go without the prefilter (the feedback rule)
     int64_t pf_last_survivors = -1, pf_last_reads = 0;  // of the last submitted batch; survivors -1: it went without the prefilter
     int pf_last_slot = -1;
-    // reads of one tax id leave the FIXED loop as records (GsSnRec) that gs_sn_reduce_kernel works off: sn_mode is GS_SN_DEFER
-    // (-1: not set, which is on); only runs whose counters live in LDS (sn_lds) defer
+    // every read leaves the FIXED loop as a record (GsSnRec) or a row of node codes that gs_sn_reduce_kernel and gs_sn_walk_kernel
+    // work off: sn_mode is GS_SN_DEFER (-1: not set, which is on; 0: such a batch takes the general loop); only runs whose
+    // counters live in LDS (sn_lds) defer
     int sn_mode = -1;
     bool sn_lds = false;
     GsSnRec *d_sn_recs = nullptr;
     size_t sn_recs_cap = 0;
+    uint16_t *d_sn_nodes = nullptr;    // [reads][GS_SN_ROW] node codes, sized as d_sn_recs
+    size_t sn_nodes_cap = 0;
+    uint32_t *d_sn_list = nullptr;     // the slots whose reads left as rows
+    size_t sn_list_cap = 0;
     bool sn_last = false;              // the last submitted batch deferred (its count: word 7 of d_long_count)
     int quot_max = 0;                  // what the table was built for: positions (0: none yet) and the two gate settings
     double quot_tax = 0, quot_class = 0;
@@ -2776,6 +2781,8 @@ static void run_free(gs_run *run) {
     gs_dev_free(run->d_stat_vi);
     gs_dev_free(run->d_stat_rec_count);
     gs_dev_free(run->d_sn_recs);
+    gs_dev_free(run->d_sn_nodes);
+    gs_dev_free(run->d_sn_list);
     gs_dev_free(run->d_quot);
     hipHostFree(run->h_quot);
     hipHostFree(run->pf_h);
@@ -2929,7 +2936,7 @@ extern "C" int gs_match_begin(gs_run **out, gs_db *db, const gs_match_cfg *cfg) 
     }
     const size_t cp = (size_t)run->stat_copies;
     // sums | max keys | double sums | long-read queue counters in ONE allocation: one memset clears them (gs_match_reset)
-    if (e == hipSuccess) e = gs_dev_alloc((void **)&run->d_sums, sizeof(int64_t) * nv * (GS_N_SUMS + 1 + GS_N_DCOLS) * cp + 8 * sizeof(unsigned int));
+    if (e == hipSuccess) e = gs_dev_alloc((void **)&run->d_sums, sizeof(int64_t) * nv * (GS_N_SUMS + 1 + GS_N_DCOLS) * cp + GS_QUEUE_WORDS * sizeof(unsigned int));
     if (e == hipSuccess) {
         run->d_max = run->d_sums + nv * GS_N_SUMS * cp;
         run->d_dsums = reinterpret_cast<double *>(run->d_max + nv * cp);
@@ -3166,11 +3173,14 @@ static int launch_batch(gs_run *run, const uint8_t *d_seq, const uint64_t *d_off
         }
     }
     // The batches whose waves take the FIXED loop of gs_match_kernel<true, ..> (counters in LDS, one candidate path per lane, one
-    // store): their reads of one tax id go out as records.  Without room for the records the batch runs without deferral.
+    // store): every read goes out as a record or a row of node codes.  Without room for them the batch takes the general loop.
     run->sn_last = false;
     if (P.quot != nullptr && run->sn_lds && run->sn_mode != 0 && run->cfg.max_paths <= 64 && P.db.n_parts <= 1 && !d_skip &&
-        grow(&run->d_sn_recs, &run->sn_recs_cap, (size_t)n_reads, run->stream) == GS_OK) {
+        P.db.n_values <= GS_SN_CODE_MAX && grow(&run->d_sn_recs, &run->sn_recs_cap, (size_t)n_reads, run->stream) == GS_OK &&
+        grow(&run->d_sn_list, &run->sn_list_cap, (size_t)n_reads, run->stream) == GS_OK &&
+        grow(&run->d_sn_nodes, &run->sn_nodes_cap, (size_t)n_reads * GS_SN_ROW, run->stream) == GS_OK) {
         P.sn_recs = run->d_sn_recs;
+        P.sn_nodes = run->d_sn_nodes;
         run->sn_last = true;
     }
     int pf_slot = -1;
@@ -3180,9 +3190,10 @@ static int launch_batch(gs_run *run, const uint8_t *d_seq, const uint64_t *d_off
             for (int i = 0; i < GS_PF_SLOTS; i++) run->pf_h[i] = 0;
         }
     }
-    // (word 6 behind the queue counters: the survivors; word 7: the records booked.  One memset for both)
+    // (word 6 behind the queue counters: the survivors; word 7: the records booked; word 8: the rows of node codes listed.  One
+    // memset for all)
     if (prefilter || P.sn_recs)
-        HIP_TRY(hipMemsetAsync(run->d_long_count + (prefilter ? 6 : 7), 0, sizeof(unsigned int) * ((prefilter ? 1 : 0) + (P.sn_recs ? 1 : 0)), run->stream));
+        HIP_TRY(hipMemsetAsync(run->d_long_count + (prefilter ? 6 : 7), 0, sizeof(unsigned int) * ((prefilter ? 1 : 0) + (P.sn_recs ? 2 : 0)), run->stream));
     if ((rc = timer_start(run->timer, run->cfg.profile != 0, run->stream))) return rc;
     if (prefilter) {
         GsPrefilterParams F{};
@@ -3236,6 +3247,13 @@ static int launch_batch(gs_run *run, const uint8_t *d_seq, const uint64_t *d_off
             S.class_vi = d_class;
             S.flags = d_flags;
             S.booked = run->d_long_count + 7;
+            S.row_list = run->d_sn_list;
+            S.n_rows = run->d_long_count + 8;
+            S.nodes = P.sn_nodes;
+            S.parent = P.db.parent;
+            S.tin = P.db.tin;
+            S.tout = P.db.tout;
+            S.max_paths = P.max_paths;
             HIP_TRY(gs_launch_sn_reduce(&S, run->stream));
         }
     }
@@ -5940,17 +5958,19 @@ extern "C" int gs_match_prefilter_info(gs_run *run, int64_t *info) {
     return GS_OK;
 }
 
-// info[0]: 1 if the last submitted batch deferred its reads of one tax id (GsSnRec); info[1]: the records it booked.  Synchronises.
+// info[0]: 1 if the last submitted batch's reads left the match kernel as records (GsSnRec); info[1]: the records of reads of one
+// tax id that were booked; info[2]: the reads that left as rows of node codes.  Synchronises.
 extern "C" int gs_match_sn_info(gs_run *run, int64_t *info) {
     if (!run || !info) return fail(GS_E_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(run->db->device));
     HIP_TRY(hipStreamSynchronize(run->stream));
     info[0] = run->sn_last ? 1 : 0;
-    info[1] = 0;
+    info[1] = info[2] = 0;
     if (run->sn_last) {
-        uint32_t n = 0;
-        HIP_TRY(hipMemcpy(&n, run->d_long_count + 7, sizeof(n), hipMemcpyDeviceToHost));
-        info[1] = (int64_t)n;
+        uint32_t n[2] = {0, 0};
+        HIP_TRY(hipMemcpy(n, run->d_long_count + 7, sizeof(n), hipMemcpyDeviceToHost));
+        info[1] = (int64_t)n[0];
+        info[2] = (int64_t)n[1];
     }
     return GS_OK;
 }

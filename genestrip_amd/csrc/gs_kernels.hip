@@ -114,7 +114,6 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
     const uint8_t *rd = P.seq + off;
     int out_class = -1;
     int out_flags = 0;
-    bool deferred_sn = false;  // the read went out as a GsSnRec: its outputs are the reduce kernel's
 
     if (FIXED || max > 0) {
         const int64_t read_no = P.first_read_no + r;
@@ -131,11 +130,10 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
         bool deferred = false;                                     // REC: its statistics go into a GsStatRec (P.stat_recs)
         int def_contigs = 0, def_max = 0, def_sq = 0;              // (at most 128 positions: 128^2 fits)
         int def_counted = 0, def_read_kmers = 0, def_tax_err = 0;
-        // counters in LDS, FIXED loop: a read with ONE distinct hit node and no non-CGAT byte books nothing.  It leaves the wave as
-        // a record of its hit masks (GsSnRec, P.sn_recs) that gs_sn_reduce_kernel turns into contigs, classification, one row of
-        // `sums`, one max key and one row of `dsums`, one lane per record
-        constexpr bool SN = FIXED && !REC && !WIDE && (GS_ABLATE & 1) == 0;
-        bool sn = false;
+        // counters in LDS, FIXED loop: no read books anything.  A read with ONE distinct hit node and no non-CGAT byte leaves the
+        // wave as a record of its hit masks (GsSnRec, P.sn_recs), a read without a hit as a bare record, any other read as its row
+        // of node codes (P.sn_nodes); gs_sn_reduce_kernel and gs_sn_walk_kernel turn them into counters and outputs (gs_snrec.h)
+        constexpr bool SN = FIXED && !REC && !WIDE;
         constexpr int NP = WIDE ? 2 : 1;
 // "lane 0" on the paths the FIXED loop takes: a literal mask there (a compare's result is kept across the loop in a scalar pair)
 #define GS_LANE0 (FIXED ? GS_ACT(1ULL) : lane == 0)
@@ -229,33 +227,44 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
                 GS_FIRST_NODE()
                 deferred = (m0 | m1) == 0 && P.stat_recs != nullptr;  // one tax id, counters in HBM: no atomics, one record
             }
-            if (SN) {  // (as above: decided before anything is booked)
+            if constexpr (SN) {
+                // The loop looks k-mers up and nothing else: EVERY read leaves here as a record, and nothing below this block is
+                // compiled into the loop (gs_match_kernel enters it only with P.sn_recs and P.sn_nodes in place).
                 GsSnRec *const recs = P.sn_recs;
-                if (recs != nullptr) {
-                    if ((hit0 | hit1) != 0 && (Bbad[0] | Bbad[1] | Bbad[2]) == 0) {
-                        // (the first node under names of this block's own: what the block shares with the code below is live on
-                        // every path through the loop and costs the read that hits nothing a dozen scalar moves)
-                        const int j1 = hit0 ? __builtin_ctzll(hit0) : 64 + __builtin_ctzll(hit1);
-                        const int vi1 = j1 < 64 ? gs_readlane(node[0], j1) : gs_readlane(node[1], j1 - 64);
-                        if (((hit0 & ~__ballot(node[0] == vi1)) | (hit1 & ~__ballot(node[1] == vi1))) == 0) {
-                            // every hit position holds vi1 and no window holds a bad base: the read is its two hit masks.  Lanes
-                            // 0 .. 5 take the six words of the record (v_writelane from the scalar values) and store them with one
-                            // instruction; the read books nothing and writes no output here
-                            sn = deferred_sn = true;
-                            int w = 0;
-                            w = gs_writelane<0>(w, (int)(uint32_t)hit0);
-                            w = gs_writelane<1>(w, (int)(uint32_t)(hit0 >> 32));
-                            w = gs_writelane<2>(w, (int)(uint32_t)hit1);
-                            w = gs_writelane<3>(w, (int)(uint32_t)(hit1 >> 32));
-                            w = gs_writelane<4>(w, vi1);
-                            w = gs_writelane<5>(w, (int)(uint32_t)r);
-                            if (GS_ACT(0x3fULL)) reinterpret_cast<int *>(recs + slot)[lane] = w;
-                        }
+                const bool clean = (Bbad[0] | Bbad[1] | Bbad[2]) == 0;
+                int code = GS_SN_NODES;  // several nodes, or a non-CGAT byte: the read is its row of node codes
+                if (clean && (hit0 | hit1) == 0) code = GS_SN_NONE;
+                if (clean && (hit0 | hit1) != 0) {
+                    const int j1 = hit0 ? __builtin_ctzll(hit0) : 64 + __builtin_ctzll(hit1);
+                    const int vi1 = j1 < 64 ? gs_readlane(node[0], j1) : gs_readlane(node[1], j1 - 64);
+                    if (((hit0 & ~__ballot(node[0] == vi1)) | (hit1 & ~__ballot(node[1] == vi1))) == 0) {
+                        // every hit position holds vi1 and no window holds a bad base: the read is its two hit masks.  Lanes
+                        // 0 .. 5 take the six words of the record (v_writelane from the scalar values) and store them with one
+                        // instruction
+                        int w = 0;
+                        w = gs_writelane<0>(w, (int)(uint32_t)hit0);
+                        w = gs_writelane<1>(w, (int)(uint32_t)(hit0 >> 32));
+                        w = gs_writelane<2>(w, (int)(uint32_t)hit1);
+                        w = gs_writelane<3>(w, (int)(uint32_t)(hit1 >> 32));
+                        w = gs_writelane<4>(w, vi1);
+                        w = gs_writelane<5>(w, (int)(uint32_t)r);
+                        if (GS_ACT(0x3fULL)) reinterpret_cast<int *>(recs + slot)[lane] = w;
+                        GS_STAMP(7, w)
+                        return;
                     }
-                    if (!sn && GS_ACT(1ULL)) recs[slot].vi = -1;
                 }
+                // (vi, r, bad) by lanes 4 .. 6: the reduce side writes the outputs of a read without a hit and lists a row of codes
+                const int bad = bad_lo + (bad_hi ? 1 : 0);
+                if (GS_ACT(0x70ULL)) reinterpret_cast<int *>(recs + slot)[lane] = GS_ACT(0x10ULL) ? code : (GS_ACT(0x20ULL) ? (int)(uint32_t)r : bad);
+                if (code == GS_SN_NODES) {
+                    uint16_t *const row = P.sn_nodes + (size_t)slot * GS_SN_ROW;  // (n_values < 2^15: gs_launch_match)
+                    row[lane] = (uint16_t)node[0];
+                    row[64 + lane] = (uint16_t)node[1];
+                }
+                GS_STAMP(7, code)
+                return;
             }
-            if ((GS_ABLATE & 1) == 0 && !(SN && sn) && ((hit0 | hit1) != 0 || carry_last >= 0)) {
+            if ((GS_ABLATE & 1) == 0 && ((hit0 | hit1) != 0 || carry_last >= 0)) {
                 int prev[2];
                 {
                     const int up0 = __shfl_up(node[0], 1);
@@ -405,7 +414,7 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
             }
         }
 
-        if ((GS_ABLATE & 1) == 0 && found && !(SN && sn)) {
+        if ((GS_ABLATE & 1) == 0 && found) {
             out_flags = GS_F_FOUND | GS_F_RETURNED;
             // tail flush (:455-473): the last contig if it is a hit contig
             if (carry_last >= 0) {
@@ -623,7 +632,7 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
         // region, both pointers fetched together, lane 0 as a literal mask
         int32_t *const cv = P.class_vi;
         uint8_t *const fl = P.flags;
-        if (((uintptr_t)cv | (uintptr_t)fl) != 0 && !deferred_sn && GS_ACT(1ULL)) {  // (a deferred read's: gs_sn_reduce_kernel)
+        if (((uintptr_t)cv | (uintptr_t)fl) != 0 && GS_ACT(1ULL)) {
             if (cv) cv[r] = out_class;
             if (fl) fl[r] = (uint8_t)out_flags;
         }
@@ -819,7 +828,10 @@ __global__ __launch_bounds__(GS_BLOCK) __attribute__((amdgpu_waves_per_eu(GS_WAV
     constexpr bool CAN_FIX = !FROM_NODES && !WIDE && !STRIPED;
     const int fixed_L = P.fixed_len;
     // (launch_batch hands a GsQuotTable to exactly these batches; the FIXED loop reads its gates and quotients from it)
-    const bool fixed_batch = CAN_FIX && P.off_stride == 0 && fixed_L >= 128 && fixed_L - k + 1 <= 128 && P.quot != nullptr;
+    // (counters in LDS: that loop only looks k-mers up and every read leaves it as a record, so it needs room for the records and
+    // the rows of node codes; a batch without them -- GS_SN_DEFER=0 -- takes the general loop)
+    const bool fixed_batch = CAN_FIX && P.off_stride == 0 && fixed_L >= 128 && fixed_L - k + 1 <= 128 && P.quot != nullptr &&
+                             (!LDS_STATS || (P.sn_recs != nullptr && P.sn_nodes != nullptr));
     const u64 fixed_live1 = gs_low_mask(fixed_L - k + 1 - 64);
     auto reads = [&](auto fixed) {
         constexpr bool FIXED = decltype(fixed)::value;
@@ -832,12 +844,13 @@ __global__ __launch_bounds__(GS_BLOCK) __attribute__((amdgpu_waves_per_eu(GS_WAV
         // is in device memory as *P.skip is.  Wave-uniform like fixed_batch, from the kernel's arguments: scalar loads, no other kernel.
         typedef const __attribute__((address_space(4))) uint32_t *GsSurvPtr;
         int64_t n_trips = n_reads;
-        if (FIXED && P.surv_list != nullptr) n_trips = (int64_t)*(GsSurvPtr)P.surv_count;
+        // (a batch of one length that takes the general loop -- off_stride 0 -- takes the list too)
+        if (P.surv_list != nullptr) n_trips = (int64_t)*(GsSurvPtr)P.surv_count;
         if (FIXED && wave_id < n_trips) trips = (uint32_t)(n_trips - wave_id - 1) / (uint32_t)n_waves + 1u;
         // (the list pointer stays in two scalar registers across the loop: read from the kernarg segment once per trip like the other
         // parameters, the instruction stream of the GENERAL loop moved with it and GS_BENCH_OFFSETS=array lost 0.10 ms)
         const GsSurvPtr sl0 = FIXED ? (GsSurvPtr)P.surv_list : nullptr;
-        for (int64_t t = wave_id; FIXED ? trips != 0 : t < n_reads; t += n_waves, po += po_step, trips--) {
+        for (int64_t t = wave_id; FIXED ? trips != 0 : t < n_trips; t += n_waves, po += po_step, trips--) {
             GsKernargPtr kp = kp0;
 #ifndef GS_KERNARG_HOISTED  // (experiment, DESIGN 8.1 "kernarg re-reads": let the compiler keep the parameters live across the loop)
             asm volatile("" : "+s"(kp));
@@ -854,6 +867,7 @@ __global__ __launch_bounds__(GS_BLOCK) __attribute__((amdgpu_waves_per_eu(GS_WAV
                 L = Q.fixed_len;
                 off = (u64)r * (u64)(uint32_t)L;
             } else if (Q.off_stride == 0) {  // reads of one length, back to back: nothing to load
+                if (Q.surv_list != nullptr) r = (int64_t)Q.surv_list[t];
                 L = Q.fixed_len;
                 off = (u64)r * (u64)(uint32_t)L;
             } else {
@@ -1882,6 +1896,8 @@ extern "C" hipError_t gs_launch_match(const GsMatchParams *P, int grid, hipStrea
     const size_t lds = gs_stats_lds_bytes(P->db.n_values);
     const bool lds_stats = P->db.n_values <= GS_NV_LDS && !gs_force_global_stats();
     const bool ctx = P->db.mgate_ctx != 0;
+    // (a row of P.sn_nodes holds node codes in 16 bits: value indices below 2^15 next to the negative codes)
+    if (P->sn_nodes != nullptr && (!lds_stats || P->db.n_values > GS_SN_CODE_MAX)) return hipErrorInvalidValue;
     if (P->db.n_parts > 1) {  // striped store (always probed locally: nodes == nullptr)
         if (P->nodes != nullptr) return hipErrorInvalidValue;
         if (P->max_paths > 64)

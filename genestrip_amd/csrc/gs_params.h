@@ -99,10 +99,12 @@ struct GsMatchParams {
     // there are *surv_count of them (both written by gs_pf_kernel on the same stream).  nullptr: every read of the batch, in order.
     const uint32_t *surv_list;
     const uint32_t *surv_count;
-    // The FIXED loop with counters in LDS: a read of one tax id without a non-CGAT byte writes sn_recs[t] (t: the trip, i.e. the index
-    // into surv_list, or the read's number) and books nothing; every other read writes vi = -1 there.  gs_sn_reduce_kernel follows
-    // on the same stream.  nullptr: nothing is deferred, every read is booked by the wave that probed it.
+    // The FIXED loop with counters in LDS only looks k-mers up: every read writes sn_recs[t] (t: the trip, i.e. the index into
+    // surv_list, or the read's number) and books nothing; a read of several tax ids or with a non-CGAT byte also writes row t of
+    // sn_nodes (GS_SN_ROW 16-bit node codes, gs_snrec.h).  gs_sn_reduce_kernel and gs_sn_walk_kernel follow on the same stream.
+    // Either pointer nullptr: a batch of one length takes the general loop, where the wave that probed a read books it.
     GsSnRec *sn_recs;
+    uint16_t *sn_nodes;
 };
 
 // gs_snreduce.hip: the records of a batch into the run's counters and per-read outputs, one lane per record
@@ -120,7 +122,16 @@ struct GsSnReduceParams {
     int32_t *class_vi;         // per-read outputs of the batch or nullptr
     uint8_t *flags;
     unsigned int *booked;      // += records with vi >= 0 (one atomic per workgroup)
+    // the slots of the records with vi == GS_SN_NODES, densely, for gs_sn_walk_kernel (room for n_reads), and their number
+    uint32_t *row_list;
+    unsigned int *n_rows;      // += (one atomic per workgroup)
+    // gs_sn_walk_kernel alone: the rows of node codes and what the walk needs of the run's settings
+    const uint16_t *nodes;
+    const int32_t *parent, *tin, *tout;
+    int32_t max_paths, pad;
 };
+// words behind the run's counters: three queues x (entries, cursor), the prefilter's survivors, the records booked, the rows listed
+#define GS_QUEUE_WORDS 10
 #define GS_HUGE_MIN (1 << 15)
 #define GS_HUGE_SLOTS 256       // (= GS_BLOCK: one thread per slot where the chunks are counted)
 #define GS_HUGE_MAX_CHUNKS 8192

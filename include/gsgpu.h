@@ -675,11 +675,13 @@ int gs_match_kernel_time(gs_run *run, int64_t *launches, double *total_ms);
  * info[0]: 1 if the run's store holds a filter; info[1]: distinct canonical 15-mers of the store (-1: never counted);
  * info[2], info[3]: survivors and reads of the last submitted batch (survivors -1: it went without the prefilter).  Synchronises. */
 int gs_match_prefilter_info(gs_run *run, int64_t *info);
-/* In such a batch on a store whose counters live in LDS (at most 128 values), a read without a non-CGAT byte whose hit k-mers all
- * carry one tax id leaves the match kernel as a 32-byte record of its hit positions, and a second kernel behind it turns the records
- * into contigs, classification and counters, one lane per record; results do not depend on it.  GS_SN_DEFER=0 / 1 in the environment
- * (read by gs_match_begin) forces it off / on; the default is on.
- * info[0]: 1 if the last submitted batch deferred; info[1]: the records it booked (0 without deferral).  Synchronises. */
+/* In such a batch on a store whose counters live in LDS (at most 128 values) the match kernel only looks k-mers up.  A read without a
+ * non-CGAT byte whose hit k-mers all carry one tax id leaves it as a 32-byte record of its hit positions; a read of several tax ids
+ * or with a non-CGAT byte leaves it as the node of every k-mer position (256 bytes).  Two kernels behind it turn both into contigs,
+ * classification and counters, one lane per read; results do not depend on it.  GS_SN_DEFER=0 / 1 in the environment (read by
+ * gs_match_begin) forces it off / on; the default is on.  Off, such a batch goes through the kernel's general loop.
+ * info[0]: 1 if the last submitted batch went this way; info[1]: the records of reads of one tax id it booked; info[2]: the reads
+ * that left as nodes per position (both 0 when info[0] is 0).  info holds three values.  Synchronises. */
 int gs_match_sn_info(gs_run *run, int64_t *info);
 /* the device the run's store lives on (for helpers that work beside a run: gs_inflater_create) */
 int gs_match_get_device(gs_run *run, int *device);
