@@ -31,7 +31,7 @@ ABI_SYMBOLS = (
     "gs_last_error", "gs_strerror", "gs_device_cache_trim", "gs_abi_version", "gs_device_count",
     "gs_match_merge", "gs_match_max_contig_reads", "gs_db_create", "gs_db_get_info", "gs_db_destroy", "gs_db_save", "gs_db_load",
     "gs_match_begin", "gs_match_submit", "gs_match_submit_async", "gs_match_wait", "gs_match_sync", "gs_match_finish", "gs_match_reset", "gs_match_destroy",
-    "gs_match_device_state", "gs_match_or_bitmap", "gs_match_kernel_time", "gs_match_prefilter_info", "gs_match_sn_info", "gs_match_segments",
+    "gs_match_device_state", "gs_match_or_bitmap", "gs_match_kernel_time", "gs_match_prefilter_info", "gs_match_sn_info", "gs_match_gate_info", "gs_match_gate_rule", "gs_match_segments",
     "gs_match_segments_fetch", "gs_match_max_counts", "gs_db_create_striped", "gs_db_create_stripe", "gs_db_stripe_export", "gs_db_stripe_attach", "gs_db_load_striped", "gs_db_load_stripe", "gs_dbbuild_begin", "gs_dbbuild_set_range", "gs_dbbuild_add", "gs_dbbuild_finish", "gs_dbbuild_fetch", "gs_dbbuild_to_db", "gs_dbbuild_destroy", "gs_db_create_part", "gs_match_encode", "gs_match_probe_keys", "gs_match_encode_route", "gs_match_route_geometry", "gs_unroute_region", "gs_match_reduce", "gs_route_keys",
     "gs_unroute_nodes",
     "gs_match_submit_text", "gs_match_submit_fasta", "gs_match_submit_fastq_ml", "gs_match_text_wait_copy", "gs_match_text_status", "gs_match_text_clear_error",
@@ -139,6 +139,7 @@ def lib():
         "gs_match_sync": (ci, [vp]), "gs_match_finish": (ci, [vp, vp, vp]), "gs_match_reset": (ci, [vp]),
         "gs_match_destroy": (ci, [vp]), "gs_match_device_state": (ci, [vp, vp, vp, vp, vp, vp]),
         "gs_match_or_bitmap": (ci, [vp, vp, i64]), "gs_match_merge": (ci, [vp, ci]), "gs_match_max_contig_reads": (ci, [vp, vp]), "gs_match_kernel_time": (ci, [vp, vp, vp]), "gs_match_prefilter_info": (ci, [vp, vp]), "gs_match_sn_info": (ci, [vp, vp]),
+        "gs_match_gate_info": (ci, [vp, vp, vp]), "gs_match_gate_rule": (ci, [i64, ci, ci, vp]),
         "gs_db_create_part": (ci, [vp, ci, ci, i64, vp, vp, i32, vp, ci, ci]),
         "gs_db_create_striped": (ci, [vp, vp, ci, ci, i64, vp, vp, i32, vp]),
         "gs_db_create_stripe": (ci, [vp, ci, ci, ci, ci, i64, vp, vp, i32, vp]),
@@ -308,6 +309,15 @@ def device_count():
     n = C.c_int(0)
     rc = lib().gs_device_count(C.byref(n))
     return n.value if rc == 0 else 0
+
+
+def gate_rule(n_lmers, samples, mode=-1):
+    """The rule by which a prefiltered fixed-length batch drops the minimizer gate (gs_match_gate_rule, a pure function):
+    (gateless, predicted_pass) for a store of n_lmers distinct canonical 15-mers and `samples` sampled 15-mers per read;
+    mode is the value of GS_PF_GATE, -1 when unset."""
+    p = C.c_double(0)
+    g = lib().gs_match_gate_rule(int(n_lmers), int(samples), int(mode), C.byref(p))
+    return bool(g), p.value
 
 
 class InflateMember(C.Structure):
@@ -1414,6 +1424,13 @@ class FastqKMerMatcher:
         info = (C.c_int64 * 3)()
         _check(lib().gs_match_sn_info(self.h, info))
         return {"deferred": bool(info[0]), "booked": int(info[1]), "rows": int(info[2])}
+
+    def gate_info(self):
+        """Reads behind the prefilter skip the minimizer gate: {"gateless": the last submitted batch ran without the gate,
+        "predicted_pass": the pass probability of a random read the rule used for it (-1: the batch could not go that way)}."""
+        g, p = C.c_int(0), C.c_double(0)
+        _check(lib().gs_match_gate_info(self.h, C.byref(g), C.byref(p)))
+        return {"gateless": bool(g.value), "predicted_pass": p.value}
 
     def close(self):
         if getattr(self, "h", None):

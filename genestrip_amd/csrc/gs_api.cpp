@@ -2234,6 +2234,11 @@ struct gs_run {
     int pf_pause = 0;                  // batches that still go without the prefilter (the feedback rule)
     int64_t pf_last_survivors = -1, pf_last_reads = 0;  // of the last submitted batch; survivors -1: it went without the prefilter
     int pf_last_slot = -1;
+    // the FIXED loop without the minimizer gate (gate_rule): gate_mode is GS_PF_GATE (-1: the rule decides; 1: every batch keeps the
+    // gate; 0: every batch that can take that loop drops it); what the last submitted batch did, for gs_match_gate_info
+    int gate_mode = -1;
+    bool gate_last_gateless = false;
+    double gate_last_pass = -1.0;
     // every read leaves the FIXED loop as a record (GsSnRec) or a row of node codes that gs_sn_reduce_kernel and gs_sn_walk_kernel
     // work off: sn_mode is GS_SN_DEFER (-1: not set, which is on; 0: such a batch takes the general loop); only runs whose
     // counters live in LDS (sn_lds) defer
@@ -2838,10 +2843,29 @@ static void run_free(gs_run *run) {
 #define GS_PF_HIT_RICH 0.85
 #define GS_PF_PAUSE 15
 #define GS_PF_SLOTS 4
+// the predicted pass probability of a read of uniform random bases; a store whose 15-mers were never counted passes everything
+static double prefilter_pass(int64_t n_lmers, int samples) {
+    if (n_lmers < 0) return 1.0;
+    return 1.0 - std::pow(1.0 - (double)n_lmers / (double)(1LL << 29), (double)samples);
+}
 static bool prefilter_rule(const gs_db *db, int mode, int samples) {
     if (mode == 0 || !db->d_pf || db->pf_set < 0) return false;
     if (mode > 0) return true;
-    return 1.0 - std::pow(1.0 - (double)db->pf_set / (double)(1LL << 29), (double)samples) < GS_PF_MAX_PASS;
+    return prefilter_pass(db->pf_set, samples) < GS_PF_MAX_PASS;
+}
+// ---- THE GATE RULE, all of it: a batch that goes through the prefilter (or that the feedback rule sends past it, see launch_batch)
+// and can take the gate-less FIXED loop of gs_match_kernel takes it if the same predicted pass probability is below
+// GS_PF_NOGATE_MAX_PASS.  The survivors of such a store are nearly all reads from the store, for which the minimizer gate passes
+// nearly every lane; the background reads that survive pay for the record lines the gate would have kept them from, so the bound is
+// HALF the break-even pass rate of a half-and-half stream, Δg / Δb ("Survivors skip the gate", has both figures and the
+// arithmetic).  mode is GS_PF_GATE, read per run like GS_PREFILTER: 1 keeps the gate, 0 drops it for every FIXED batch that can take
+// the loop, anything else leaves it to the rule.
+#define GS_PF_NOGATE_MAX_PASS 0.2
+extern "C" int gs_match_gate_rule(int64_t n_lmers, int samples, int mode, double *predicted_pass) {
+    const double pass = prefilter_pass(n_lmers, samples);
+    if (predicted_pass) *predicted_pass = pass;
+    if (mode == 0 || mode == 1) return mode == 0 ? 1 : 0;
+    return pass < GS_PF_NOGATE_MAX_PASS ? 1 : 0;
 }
 static bool prefilter_eligible(const gs_db *db) { return db->d_rec != nullptr && !db->striped() && db->n_parts <= 1 && db->info.k >= GS_MIN_K; }
 
@@ -2907,6 +2931,7 @@ extern "C" int gs_match_begin(gs_run **out, gs_db *db, const gs_match_cfg *cfg) 
     run->db = db;
     run->cfg = *cfg;
     run->pf_mode = pf_mode;
+    if (const char *ev = getenv("GS_PF_GATE")) run->gate_mode = atoi(ev) != 0 ? 1 : 0;
     if (const char *ev = getenv("GS_SN_DEFER")) run->sn_mode = atoi(ev) != 0 ? 1 : 0;
     const size_t nv = (size_t)db->info.n_values;
     run->bitmap_words = (db->n_slots() + 31) / 32 + db->n_rec;  // one word per record bucket behind the table slots' bits
@@ -3161,6 +3186,7 @@ static int launch_batch(gs_run *run, const uint8_t *d_seq, const uint64_t *d_off
     run->pf_last_slot = -1;
     bool prefilter = P.quot != nullptr && fixed_len - run->db->info.k + 1 >= 65 && !d_skip && no_queues &&
                      prefilter_rule(run->db, run->pf_mode, gs_pf_samples(fixed_len, run->db->info.k));
+    bool paused = false;  // the rule sends this store's batches through the prefilter, the feedback rule sends this one past it
     if (prefilter && run->pf_mode < 0) {  // the feedback rule (a forced prefilter is not paused)
         for (int i = 0; i < GS_PF_SLOTS; i++)
             if (run->pf_slot_pending[i] && run->pf_h[i] != 0xffffffffu) {
@@ -3170,6 +3196,7 @@ static int launch_batch(gs_run *run, const uint8_t *d_seq, const uint64_t *d_off
         if (run->pf_pause > 0) {
             run->pf_pause--;
             prefilter = false;
+            paused = true;
         }
     }
     // The batches whose waves take the FIXED loop of gs_match_kernel<true, ..> (counters in LDS, one candidate path per lane, one
@@ -3182,6 +3209,17 @@ static int launch_batch(gs_run *run, const uint8_t *d_seq, const uint64_t *d_off
         P.sn_recs = run->d_sn_recs;
         P.sn_nodes = run->d_sn_nodes;
         run->sn_last = true;
+    }
+    // The gate rule (above prefilter_rule's neighbours): only a batch whose waves take the FIXED loop of the one-store, 64-path
+    // kernels whose gate is keyed by the minimizer alone, on a store with a gate and records, can drop the gate (gs_launch_match
+    // refuses the flag anywhere else).  A paused batch is, by the evidence that paused the prefilter, one the gate does nothing for.
+    run->gate_last_gateless = false;
+    run->gate_last_pass = -1.0;
+    if (P.quot != nullptr && !d_nodes && !d_skip && P.db.n_parts <= 1 && run->cfg.max_paths <= 64 && !P.db.mgate_ctx &&
+        P.db.mgate != nullptr && P.db.rec != nullptr && prefilter_eligible(run->db) && (!run->sn_lds || P.sn_recs != nullptr)) {
+        const int gateless = gs_match_gate_rule(run->db->pf_set, gs_pf_samples(fixed_len, run->db->info.k), run->gate_mode, &run->gate_last_pass);
+        run->gate_last_gateless = gateless != 0 && (run->gate_mode == 0 || prefilter || paused);
+        P.fixed_nogate = run->gate_last_gateless ? 1 : 0;
     }
     int pf_slot = -1;
     if (prefilter) {
@@ -5972,6 +6010,15 @@ extern "C" int gs_match_sn_info(gs_run *run, int64_t *info) {
         info[1] = (int64_t)n[0];
         info[2] = (int64_t)n[1];
     }
+    return GS_OK;
+}
+
+// *gateless: 1 if the last submitted batch went through the FIXED loop without the minimizer gate; *predicted_pass: the probability
+// the gate rule used for it (-1: the batch could not take that loop, nothing was asked).  Host state only: does not synchronise.
+extern "C" int gs_match_gate_info(gs_run *run, int *gateless, double *predicted_pass) {
+    if (!run || !gateless || !predicted_pass) return fail(GS_E_INVALID, "NULL argument");
+    *gateless = run->gate_last_gateless ? 1 : 0;
+    *predicted_pass = run->gate_last_pass;
     return GS_OK;
 }
 

@@ -102,12 +102,13 @@ __device__ __forceinline__ void gs_sc_store(int32_t *p, int v) { __hip_atomic_st
 // FIXED = true (!LONG): the caller's reads all have ONE length with 65 .. 128 k-mer positions (gs_match_kernel): sub-round 0 is
 // full, and the live positions of sub-round 1 come as `live1`, built once per wave; nothing here tests the length.
 // ---------------------------------------------------------------------------------------------------
-template <bool LONG, bool FROM_NODES, int KC, bool WIDE, bool REC, bool STRIPED, int CTX = 2, bool FIXED = false>
+template <bool LONG, bool FROM_NODES, int KC, bool WIDE, bool REC, bool STRIPED, int CTX = 2, bool FIXED = false, bool NOGATE = false>
 __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const GsStats &st, int64_t r, u64 off, int L,
                                                 int lane, int (*s_dvi)[128], int (*s_dcnt)[128], int wave_in_block,
                                                 int32_t *tag, int32_t *cnt, int serial, const uint32_t (&pre)[3],
                                                 uint32_t *wave_g, unsigned long long *cur, u64 live1 = 0, int64_t slot = 0) {
     static_assert(!FIXED || (!LONG && !FROM_NODES), "one iteration, probed here");
+    static_assert(!NOGATE || FIXED, "the gate-less probe belongs to the FIXED loop (gs_probe_planes)");
     const GsDbDev &db = P.db;
     const int k = KC ? KC : db.k;
     const int max = L - k + 1;
@@ -196,7 +197,7 @@ __device__ __forceinline__ void gs_process_read(const GsMatchParams &P, const Gs
 #define GS_AGG_ALL 0
 #endif
                 const u64 live[2] = {~0ULL, live1};
-                gs_probe_planes<KC, STRIPED, CTX, (REC || GS_AGG_ALL) && !LONG, 2, FIXED>(db, Bhi, Blo, Bbad, base, max, lane, node, wave_g, mk, FIXED ? live : nullptr);
+                gs_probe_planes<KC, STRIPED, CTX, (REC || GS_AGG_ALL) && !LONG, 2, FIXED, NOGATE>(db, Bhi, Blo, Bbad, base, max, lane, node, wave_g, mk, FIXED ? live : nullptr);
             }
 
             if (!LONG) GS_STAMP(5, node[0] ^ node[1])
@@ -833,8 +834,15 @@ __global__ __launch_bounds__(GS_BLOCK) __attribute__((amdgpu_waves_per_eu(GS_WAV
     const bool fixed_batch = CAN_FIX && P.off_stride == 0 && fixed_L >= 128 && fixed_L - k + 1 <= 128 && P.quot != nullptr &&
                              (!LDS_STATS || (P.sn_recs != nullptr && P.sn_nodes != nullptr));
     const u64 fixed_live1 = gs_low_mask(fixed_L - k + 1 - 64);
-    auto reads = [&](auto fixed) {
+    // A third variant of the loop: the FIXED loop whose probe leaves the minimizer gate out (gs_probe_planes<.., NOGATE>), for the
+    // batches launch_batch marks with P.fixed_nogate -- reads that passed the prefilter, for which the gate says "pass" in nearly
+    // every lane.  Only on a store that has both a gate and records (without records the gate saves a bucket line per k-mer), and
+    // only where the gate word's hint bits are not used (CTX == 0, one store).
+    constexpr bool CAN_NOGATE = CAN_FIX && CTX == 0;
+    const bool nogate_batch = CAN_NOGATE && fixed_batch && P.fixed_nogate != 0 && P.db.mgate != nullptr && P.db.rec != nullptr;
+    auto reads = [&](auto fixed, auto nogate) {
         constexpr bool FIXED = decltype(fixed)::value;
+        constexpr bool NOGATE = decltype(nogate)::value;
         const int64_t po_step = n_waves * P.off_stride;        // stride 1: running offsets; 2: (start, end) pairs
         const uint64_t *po = P.off + wave_id * P.off_stride;   // offsets of the current read
         // FIXED: the wave's trips are counted down on the scalar unit (gfx9 has no scalar 64-bit ordered compare: `r < n_reads` is two
@@ -887,17 +895,23 @@ __global__ __launch_bounds__(GS_BLOCK) __attribute__((amdgpu_waves_per_eu(GS_WAV
 #pragma unroll
                 for (int w = 0; w < 3; w++) pre[w] = 64 * w + lane < L ? rd[64 * w + lane] : GS_FILL;
             }
-            gs_process_read<false, FROM_NODES, KC, WIDE, !LDS_STATS, STRIPED, CTX, FIXED>(Q, st, r, off, L, lane, s_dvi, s_dcnt, wave_in_block, nullptr, nullptr, 0,
+            gs_process_read<false, FROM_NODES, KC, WIDE, !LDS_STATS, STRIPED, CTX, FIXED, NOGATE>(Q, st, r, off, L, lane, s_dvi, s_dcnt, wave_in_block, nullptr, nullptr, 0,
                                                                                           pre, s_g[wave_in_block], s_cur[wave_in_block], fixed_live1, t);
         }
     };
     if constexpr (CAN_FIX) {
-        if (fixed_batch)  // (wave-uniform, from the kernel's arguments)
-            reads(std::true_type());
-        else
-            reads(std::false_type());
+        if (fixed_batch) {  // (wave-uniform, from the kernel's arguments)
+            if constexpr (CAN_NOGATE) {
+                if (nogate_batch)
+                    reads(std::true_type(), std::true_type());
+                else
+                    reads(std::true_type(), std::false_type());
+            } else
+                reads(std::true_type(), std::false_type());
+        } else
+            reads(std::false_type(), std::false_type());
     } else
-        reads(std::false_type());
+        reads(std::false_type(), std::false_type());
 #if GS_PHASE
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     if (lane < 15) atomicAdd(&gs_phase_acc[lane], gs_phase_row()[lane]);
@@ -1898,6 +1912,13 @@ extern "C" hipError_t gs_launch_match(const GsMatchParams *P, int grid, hipStrea
     const bool ctx = P->db.mgate_ctx != 0;
     // (a row of P.sn_nodes holds node codes in 16 bits: value indices below 2^15 next to the negative codes)
     if (P->sn_nodes != nullptr && (!lds_stats || P->db.n_values > GS_SN_CODE_MAX)) return hipErrorInvalidValue;
+    // (the gate-less loop is the FIXED loop of the one-store, 64-path kernels whose gate is keyed by the minimizer alone, on a store
+    // with a gate and records: anywhere else the flag would be ignored in silence)
+    if (P->fixed_nogate != 0 &&
+        (P->db.n_parts > 1 || P->nodes != nullptr || P->max_paths > 64 || ctx || P->db.mgate == nullptr || P->db.rec == nullptr ||
+         P->off_stride != 0 || P->quot == nullptr || P->fixed_len < 128 || P->fixed_len - P->db.k + 1 > 128 ||
+         (lds_stats && (P->sn_recs == nullptr || P->sn_nodes == nullptr))))
+        return hipErrorInvalidValue;
     if (P->db.n_parts > 1) {  // striped store (always probed locally: nodes == nullptr)
         if (P->nodes != nullptr) return hipErrorInvalidValue;
         if (P->max_paths > 64)

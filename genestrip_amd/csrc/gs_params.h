@@ -62,7 +62,9 @@ struct GsMatchParams {
     // round trip in front of the bases' (14 % of a wave's cycles on a store that does not fit the caches) is gone
     int32_t off_stride;
     int32_t fixed_len;
-    int32_t pad0;
+    // != 0: the waves take the FIXED loop WITHOUT the minimizer gate (gs_probe_planes<.., NOGATE>): set by launch_batch for batches
+    // behind the prefilter; gs_launch_match refuses it where that loop cannot be taken
+    int32_t fixed_nogate;
     // direct global-atomic counters (n_values > GS_NV_LDS) exist in `stat_copies` copies, one per group of workgroups
     // (blockIdx % stat_copies): the atomics of one tax id are spread over that many cache lines; the copies are
     // folded into copy 0 before anything reads the accumulators

@@ -374,11 +374,16 @@ __device__ __forceinline__ u64 gs_low_mask(int n) { return n >= 64 ? ~0ULL : (n 
 // a minimizer run OR their offset bits into a word of the wave's LDS rows (free again after the minimizer scan), the lane that owns
 // the lowest bit sends the word: ~13 atomics per read from the store instead of ~60.
 // LIT: the caller is the FIXED loop -- lane predicates that are constants of the wave are written as literal masks
-template <int KC, bool STRIPED, int CTX = 2, bool AGG = false, int NS = 2, bool LIT = false>
+// NOGATE: the caller's reads have passed the prefilter, or come from a stream the feedback rule found hit-rich (launch_batch,
+// DESIGN 4): the minimizer gate, which passes nearly every lane of such a read, is neither addressed, loaded nor tested, and act[s]
+// stays "live and not an INVALID window".  The caller has looked: the store has a gate and records (db.mgate, db.rec).  Results do
+// not depend on it -- the gate has no false negatives and the record compare is exact.
+template <int KC, bool STRIPED, int CTX = 2, bool AGG = false, int NS = 2, bool LIT = false, bool NOGATE = false>
 __device__ __forceinline__ void gs_probe_planes(const GsDbDev &db, const u64 (&Bhi)[NS + 1], const u64 (&Blo)[NS + 1],
                                                 const u64 (&Bbad)[NS + 1], int base, int max, int lane, int (&node)[NS],
                                                 uint32_t *wave_g, const GsMark &mk, const u64 *live = nullptr) {
     static_assert(NS == 2 || !AGG, "the seen-bit accumulators are laid out for two sub-rounds");
+    static_assert(!NOGATE || (LIT && !STRIPED && CTX == 0 && NS == 2), "every other variant uses the hint bits of the gate word");
     const int k = KC ? KC : db.k;  // KC = compile-time k of the specialised kernels (0: any k)
     const uint32_t kmask = (1u << k) - 1u;
     const uint32_t vmask2 = 2u * ((1u << db.vbits) - 1u);
@@ -406,7 +411,7 @@ __device__ __forceinline__ void gs_probe_planes(const GsDbDev &db, const u64 (&B
             node[s] = GS_ACT(wb) ? GS_NODE_INVALID : node[s];
         }
     }
-    if (db.mgate != nullptr) {
+    if (NOGATE || db.mgate != nullptr) {
         // minimizer gate: lanes that share a minimizer read the same gate word -> one request
         int mp[NS];
         uint32_t cf[NS];
@@ -431,7 +436,7 @@ __device__ __forceinline__ void gs_probe_planes(const GsDbDev &db, const u64 (&B
         u64 two[NS];
 #pragma unroll
         for (int s = 0; s < NS; s++) two[s] = ~0ULL;
-        if ((GS_ABLATE & 4) == 0) {
+        if (!NOGATE && (GS_ABLATE & 4) == 0) {
             // the gate words of both sub-rounds are requested together (lanes without a live k-mer read word 0): one round
             // trip, no exec-mask regions
             uint32_t gw[NS];
@@ -455,7 +460,7 @@ __device__ __forceinline__ void gs_probe_planes(const GsDbDev &db, const u64 (&B
                 if (GS_ACT(act[s]) && (gh[s] ^ ohi[s] ^ olo[s] ^ (uint32_t)j[s]) == 0x12345u) node[s] = 0;
             return;
         }
-        if (STRIPED || db.rec != nullptr) {
+        if (NOGATE || STRIPED || db.rec != nullptr) {
             // ---- super-k-mer records: per candidate bucket of the minimizer one 16-byte load of the window planes + the
             // 8-byte word that holds this offset's value.  The first bucket always; the second one only where the gate word
             // carries the key's hint bit (two windows in three sit in their first bucket: a third fewer line requests, which

@@ -683,6 +683,17 @@ int gs_match_prefilter_info(gs_run *run, int64_t *info);
  * info[0]: 1 if the last submitted batch went this way; info[1]: the records of reads of one tax id it booked; info[2]: the reads
  * that left as nodes per position (both 0 when info[0] is 0).  info holds three values.  Synchronises. */
 int gs_match_sn_info(gs_run *run, int64_t *info);
+/* Reads that passed the prefilter skip the minimizer gate: for a read from the store the gate passes nearly every k-mer, so a batch
+ * behind the prefilter (or one the prefilter's feedback rule sends past it) on a store whose predicted pass probability of a random
+ * read is small goes through a loop of the match kernel that never asks the gate; results do not depend on it.  GS_PF_GATE=1 / 0 in
+ * the environment (read by gs_match_begin) keeps / drops the gate for every batch that can take that loop.
+ * *gateless: 1 if the last submitted batch ran without the gate; *predicted_pass: the probability the rule used for it (-1: the
+ * batch could not take that loop).  Does not synchronise. */
+int gs_match_gate_info(gs_run *run, int *gateless, double *predicted_pass);
+/* The rule itself, a pure function: would a prefiltered batch of `samples` sampled 15-mers per read on a store of n_lmers distinct
+ * canonical 15-mers (-1: never counted) drop the gate?  mode: the value of GS_PF_GATE, -1 when unset.  Returns 1 / 0 and, where
+ * predicted_pass is not NULL, the probability 1 - (1 - n_lmers / 2^29)^samples it compares with its bound. */
+int gs_match_gate_rule(int64_t n_lmers, int samples, int mode, double *predicted_pass);
 /* the device the run's store lives on (for helpers that work beside a run: gs_inflater_create) */
 int gs_match_get_device(gs_run *run, int *device);
 
