@@ -64,6 +64,8 @@ ABI_SYMBOLS = (
     "gs_genomes_destroy",
     "gs_accmap_create", "gs_accmap_submit", "gs_accmap_append", "gs_accmap_finish", "gs_accmap_fetch", "gs_accmap_lookup",
     "gs_accmap_lookup_genomes", "gs_accmap_get_device", "gs_accmap_kernel_time", "gs_accmap_destroy",
+    "gs_asmsum_create", "gs_asmsum_submit", "gs_asmsum_append", "gs_asmsum_finish", "gs_asmsum_fetch", "gs_asmsum_file_name",
+    "gs_asmsum_get_device", "gs_asmsum_kernel_time", "gs_asmsum_destroy",
     "gs_taxtree_create", "gs_taxtree_submit_nodes", "gs_taxtree_append_nodes", "gs_taxtree_finish_nodes", "gs_taxtree_submit_names", "gs_taxtree_append_names", "gs_taxtree_finish_times",
     "gs_taxtree_fetch", "gs_taxtree_fetch_names", "gs_taxtree_select", "gs_taxtree_small", "gs_taxtree_regions_below", "gs_taxtree_read_taxids",
     "gs_taxtree_get_device", "gs_taxtree_kernel_time", "gs_taxtree_destroy",
@@ -277,6 +279,10 @@ def lib():
         "gs_accmap_append": (ci, [vp, vp, vp, i64, i64]), "gs_accmap_finish": (ci, [vp, vp]), "gs_accmap_fetch": (ci, [vp, vp, vp, vp]),
         "gs_accmap_lookup": (ci, [vp, vp, vp, i64, ci, ci, vp]), "gs_accmap_lookup_genomes": (ci, [vp, vp, ci, vp]),
         "gs_accmap_get_device": (ci, [vp, vp]), "gs_accmap_kernel_time": (ci, [vp, ci, vp, vp]), "gs_accmap_destroy": (ci, [vp]),
+        "gs_asmsum_create": (ci, [vp, ci, vp]), "gs_asmsum_submit": (ci, [vp, vp, i64, ci, ci, vp]),
+        "gs_asmsum_append": (ci, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64]), "gs_asmsum_finish": (ci, [vp, i32, vp]),
+        "gs_asmsum_fetch": (ci, [vp, vp, vp, vp, vp, vp, vp]), "gs_asmsum_file_name": (i64, [C.c_char_p, i64, vp, i64]),
+        "gs_asmsum_get_device": (ci, [vp, vp]), "gs_asmsum_kernel_time": (ci, [vp, ci, vp, vp]), "gs_asmsum_destroy": (ci, [vp]),
         "gs_taxtree_create": (ci, [vp, ci]), "gs_taxtree_submit_nodes": (ci, [vp, vp, i64, ci, ci, vp]),
         "gs_taxtree_append_nodes": (ci, [vp, vp, i64, ci, vp]), "gs_taxtree_finish_nodes": (ci, [vp, vp]),
         "gs_taxtree_append_names": (ci, [vp, vp, i64, ci]), "gs_taxtree_submit_names": (ci, [vp, vp, i64, ci, ci, vp]),
@@ -1963,6 +1969,148 @@ class DeviceAccessionMap:
         """(launches, milliseconds) of the scan, finish and lookup kernels so far; switches their timing on or off"""
         n, ms = C.c_int64(), C.c_double()
         _check(lib().gs_accmap_kernel_time(self.h, int(profile), C.byref(n), C.byref(ms)))
+        return n.value, ms.value
+
+
+class _AsmsumCfg(C.Structure):
+    _fields_ = [("n_nodes", C.c_int32), ("known_taxids", C.c_void_p), ("filter", C.c_void_p), ("quality_mask", C.c_int32),
+                ("reference_only", C.c_int32), ("use_species_taxid", C.c_int32), ("reserve_entries", C.c_int64)]
+
+
+ASSEMBLY_QUALITIES = ("ADDITIONAL", "COMPLETE_LATEST", "COMPLETE", "CHROMOSOME_LATEST", "CHROMOSOME", "SCAFFOLD_LATEST", "SCAFFOLD",
+                      "CONTIG_LATEST", "CONTIG", "LATEST", "NONE")
+
+
+def quality_mask(qualities):
+    """a list of AssemblyQuality names or ordinals -> the mask of gs_asmsum_cfg; None (the reference's null list) -> -1: all"""
+    if qualities is None:
+        return -1
+    mask = 0
+    for q in qualities:
+        mask |= 1 << (ASSEMBLY_QUALITIES.index(q) if isinstance(q, str) else int(q))
+    return mask
+
+
+def file_name_of(ftp):
+    """gs_asmsum_file_name: AssemblyEntry's file name of an ftp path (bytes or str) -> bytes"""
+    ftp = ftp.encode() if isinstance(ftp, str) else bytes(ftp)
+    out = np.zeros(len(ftp) + 16, dtype=np.uint8)
+    n = lib().gs_asmsum_file_name(ftp, len(ftp), out.ctypes.data_as(C.c_void_p), len(out))
+    if n < 0:
+        _check(int(n))
+    return out[:n].tobytes()
+
+
+class DeviceAssemblySummary:
+    """gs_asmsum: the lines of a Genbank assembly summary to the picks per tree node on the device (the fastasgenbank goal).  A node is
+    an index into known_taxids (ascending, distinct, positive).  submit() takes chunks of whole lines; a chunk outside the device's
+    grammar is refused and leaves the handle as it was: the caller parses it and hands its entries in through append().  finish()
+    applies the cap; fetch() gives the picked entries, nodes ascending."""
+
+    @classmethod
+    def config(cls, known_taxids, filter=None, qualities=("COMPLETE_LATEST", "CHROMOSOME_LATEST"), reference_only=False, use_species_taxid=False,
+               reserve_entries=0):
+        """-> gs_asmsum_cfg; the structure keeps the arrays it points to alive.  filter: node flags (uint8[n_nodes]) or None"""
+        known = np.ascontiguousarray(known_taxids, dtype=np.int32)
+        flt = None if filter is None else np.ascontiguousarray(filter, dtype=np.uint8)
+        if flt is not None and len(flt) != len(known):
+            raise ValueError("one filter flag per node")
+        cfg = _AsmsumCfg(len(known), known.ctypes.data_as(C.c_void_p) if len(known) else None,
+                         flt.ctypes.data_as(C.c_void_p) if flt is not None and len(flt) else None, quality_mask(qualities),
+                         int(bool(reference_only)), int(bool(use_species_taxid)), int(reserve_entries))
+        cfg._keep = (known, flt)
+        return cfg
+
+    def __init__(self, known_taxids, filter=None, qualities=("COMPLETE_LATEST", "CHROMOSOME_LATEST"), reference_only=False,
+                 use_species_taxid=False, device=0, reserve_entries=0):
+        """device -1: a host-only handle (append, finish, fetch; no device is touched)"""
+        self.h = C.c_void_p()
+        self.device = int(device)
+        self.info = None
+        cfg = self.config(known_taxids, filter, qualities, reference_only, use_species_taxid, reserve_entries)
+        _check(lib().gs_asmsum_create(C.byref(self.h), self.device, C.byref(cfg)))
+
+    @classmethod
+    def _wrap(cls, handle, info=None):
+        """a finished handle that the host layer made (host.assembly_summary_files)"""
+        m = cls.__new__(cls)
+        m.h = handle
+        dev = C.c_int(0)
+        _check(lib().gs_asmsum_get_device(m.h, C.byref(dev)))
+        m.device = dev.value
+        m.info = info
+        return m
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().gs_asmsum_destroy(self.h)
+            self.h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def submit(self, text, last=False):
+        """a chunk of whole lines (bytes, a uint8 array, or a uint8 tensor on the handle's device); last: the stream ends here and
+        its final line need not be terminated -> its report"""
+        if isinstance(text, (bytes, bytearray, memoryview)):
+            text = np.frombuffer(bytes(text), dtype=np.uint8)
+        n = int(text.shape[0])
+        _ready(text)
+        p, mem = _ptr(text) if n else (None, MEM_HOST)
+        r = (C.c_int64 * 8)()
+        _check(lib().gs_asmsum_submit(self.h, p, n, mem, int(bool(last)), r))
+        return {"counted": r[0], "kept": r[1], "short": r[2], "refused": r[3], "first_bad_line": r[4], "longest_line": r[5], "skipped": r[6],
+                "pool_bytes": r[7]}
+
+    def append(self, entries, n_counted=None, n_lines=None):
+        """entries made elsewhere, in input order: (node, taxid, species_taxid, ftp, quality, is_ref, line) each, the three strings as
+        bytes; n_counted: the counted records of the same lines (default: len(entries)); n_lines: those lines (default: n_counted)"""
+        n = len(entries)
+        nodes = np.array([e[0] for e in entries], dtype=np.int32)
+        quality = np.array([e[4] for e in entries], dtype=np.uint8)
+        is_ref = np.array([bool(e[5]) for e in entries], dtype=np.uint8)
+        lines = np.array([e[6] for e in entries], dtype=np.int64)
+        strs = [bytes(s) for e in entries for s in (e[1], e[2], e[3])]
+        off = np.concatenate([np.zeros(1, np.uint64), np.cumsum([len(s) for s in strs], dtype=np.uint64)]).astype(np.uint64)
+        pool = np.frombuffer(b"".join(strs) + b"\0", dtype=np.uint8)
+        n_counted = n if n_counted is None else int(n_counted)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _check(lib().gs_asmsum_append(self.h, vp(nodes), vp(quality), vp(is_ref), vp(lines), vp(off), vp(pool), n, n_counted,
+                                      n_counted if n_lines is None else int(n_lines)))
+
+    def finish(self, max_per_node=1):
+        """the cap -> (kept entries, picked entries, nodes with entries, counted records in all)"""
+        info = (C.c_int64 * 4)()
+        _check(lib().gs_asmsum_finish(self.h, int(max_per_node), info))
+        self.info = tuple(info)
+        return self.info
+
+    def fetch(self):
+        """-> the picked entries, nodes ascending, inside a node in the reference's list order:
+        [(node, taxid, species_taxid, ftp, quality, is_ref, line)], the three strings as bytes"""
+        m = self.info[1] if self.info else 0  # (in front of finish() the library refuses the call)
+        nodes = np.zeros(max(m, 1), dtype=np.int32)
+        quality = np.zeros(max(m, 1), dtype=np.uint8)
+        is_ref = np.zeros(max(m, 1), dtype=np.uint8)
+        lines = np.zeros(max(m, 1), dtype=np.int64)
+        off = np.zeros(3 * m + 1, dtype=np.uint64)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _check(lib().gs_asmsum_fetch(self.h, vp(nodes), vp(quality), vp(is_ref), vp(lines), vp(off), None))
+        pool = np.zeros(max(int(off[3 * m]), 1), dtype=np.uint8)
+        _check(lib().gs_asmsum_fetch(self.h, None, None, None, None, None, vp(pool)))
+        raw = pool.tobytes()
+        s = lambda i: raw[int(off[i]):int(off[i + 1])]  # noqa: E731
+        return [(int(nodes[j]), s(3 * j), s(3 * j + 1), s(3 * j + 2), int(quality[j]), bool(is_ref[j]), int(lines[j])) for j in range(m)]
+
+    def kernel_time(self, profile=True):
+        """(launches, milliseconds) of the scan and finish kernels so far; switches their timing on or off"""
+        n, ms = C.c_int64(), C.c_double()
+        _check(lib().gs_asmsum_kernel_time(self.h, int(profile), C.byref(n), C.byref(ms)))
         return n.value, ms.value
 
 

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "gs_absmod.h"
+#include "gs_asmsumparse.h"
 #include "gs_checksum.h"
 #include "gs_indexfile.h"
 #include "gs_launch.h"
@@ -7646,6 +7647,449 @@ GS_API_CATCH
 
 extern "C" int gs_accmap_kernel_time(gs_accmap *h, int profile, int64_t *launches, double *total_ms) try {
     if (!h) return fail(GS_E_INVALID, "accmap is NULL");
+    if (h->host_only) {
+        if (launches) *launches = 0;
+        if (total_ms) *total_ms = 0;
+        return GS_OK;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    int rc = timer_collect(h->timer);
+    if (rc) return rc;
+    h->profile = profile != 0;
+    if (launches) *launches = h->timer.launches;
+    if (total_ms) *total_ms = h->timer.total_ms;
+    return GS_OK;
+}
+GS_API_CATCH
+
+// ---------------------------------------------------------------------------------------------------
+// asmsum: Genbank assembly summary lines to the picks per tree node (gs_asmsum.hip, gs_asmsumparse.h)
+// ---------------------------------------------------------------------------------------------------
+struct gs_asmsum {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool finished = false;
+    bool host_only = false;  // device == -1: no device is touched; the entries live in `store`
+    int32_t n_nodes = 0, quality_mask = -1, reference_only = 0, key_field = 5;
+    int32_t *d_known = nullptr;
+    uint8_t *d_filter = nullptr;  // nullptr: every node
+    uint8_t *d_text = nullptr;
+    size_t text_cap = 0;
+    u64 *d_tile = nullptr;
+    uint32_t *d_tail = nullptr;
+    size_t tile_cap = 0;
+    uint16_t *d_slots = nullptr;  // per line of a chunk: its slot, its high-byte mark, its verdict
+    uint8_t *d_high = nullptr;
+    u64 *d_verdict = nullptr;
+    size_t line_cap = 0;
+    u64 *d_line_blk = nullptr;
+    size_t blk_cap = 0;
+    uint32_t *d_put_line = nullptr;
+    size_t put_cap = 0;
+    GsAsmEntry *d_entries = nullptr;  // kept entries in input order; their strings in d_pool
+    size_t entry_cap = 0;
+    uint8_t *d_pool = nullptr;
+    size_t pool_cap = 0;
+    int64_t n_entries = 0, pool_used = 0, n_counted = 0, n_lines = 0;
+    u64 *d_small = nullptr;  // status, chunk counters, scan sums, finish counts (AS_S_*)
+    // finished: the picked entries, nodes ascending
+    int64_t n_picked = 0, nodes_with_entries = 0, out_pool_bytes = 0;
+    GsAsmEntry *d_out = nullptr;
+    u64 *d_str_off = nullptr;
+    uint8_t *d_out_pool = nullptr;
+    gs_host::AsmsumStore store;
+    bool profile = false;
+    KernelTimer timer;
+};
+enum { AS_S_STATUS = 0, AS_S_CHUNK = 1, AS_S_SCAN = AS_S_CHUNK + GS_AS_C_WORDS, AS_S_COUNTS = AS_S_SCAN + 2, AS_S_WORDS = AS_S_COUNTS + 2 };
+static_assert(GS_AS_WORDS == 2, "the status words fill one 64-bit word of d_small");
+
+extern "C" int gs_asmsum_destroy(gs_asmsum *h) try {
+    if (!h) return GS_OK;
+    if (h->host_only) {
+        delete h;
+        return GS_OK;
+    }
+    hipSetDevice(h->device);
+    if (h->stream) hipStreamSynchronize(h->stream);
+    timer_free(h->timer);
+    for (void *p : {(void *)h->d_known, (void *)h->d_filter, (void *)h->d_text, (void *)h->d_tile, (void *)h->d_tail, (void *)h->d_slots, (void *)h->d_high,
+                    (void *)h->d_verdict, (void *)h->d_line_blk, (void *)h->d_put_line, (void *)h->d_entries, (void *)h->d_pool, (void *)h->d_small,
+                    (void *)h->d_out, (void *)h->d_str_off, (void *)h->d_out_pool})
+        gs_dev_free(p);
+    if (h->stream) hipStreamDestroy(h->stream);
+    delete h;
+    return GS_OK;
+}
+GS_API_CATCH
+
+// room for `need` elements in all; the first `used` stay
+template <typename T>
+static int as_room(gs_asmsum *h, T **p, size_t *cap, size_t used, size_t need) {
+    if (need <= *cap) return GS_OK;
+    const size_t n = std::max(need, 2 * *cap);
+    T *fresh = nullptr;
+    hipError_t e = gs_dev_alloc(&fresh, n * sizeof(T));
+    if (e == hipSuccess && used) e = hipMemcpyAsync(fresh, *p, used * sizeof(T), hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        gs_dev_free(fresh);
+        return hip_fail(e, "gs_asmsum: growing the entry arrays");
+    }
+    gs_dev_free(*p);
+    *p = fresh;
+    *cap = n;
+    return GS_OK;
+}
+
+static int as_entry_room(gs_asmsum *h, int64_t more_entries, int64_t more_bytes) {
+    if (h->n_entries + more_entries > ((int64_t)1 << 31)) return fail(GS_E_UNSUPPORTED, "an assembly summary handle holds at most 2^31 entries");
+    int rc = as_room(h, &h->d_entries, &h->entry_cap, (size_t)h->n_entries, (size_t)(h->n_entries + more_entries));
+    if (!rc) rc = as_room(h, &h->d_pool, &h->pool_cap, (size_t)h->pool_used, (size_t)(h->pool_used + more_bytes));
+    return rc;
+}
+
+extern "C" int gs_asmsum_create(gs_asmsum **out, int device, const gs_asmsum_cfg *cfg) try {
+    if (!out) return fail(GS_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!cfg) return fail(GS_E_INVALID, "cfg is NULL");
+    if (cfg->n_nodes < 0 || (cfg->n_nodes > 0 && !cfg->known_taxids)) return fail(GS_E_INVALID, "known_taxids is NULL or n_nodes < 0");
+    if (cfg->reserve_entries < 0 || cfg->reserve_entries > ((int64_t)1 << 31)) return fail(GS_E_INVALID, "reserve_entries must be in [0, 2^31]");
+    if (cfg->quality_mask != -1 && (cfg->quality_mask & ~0x7ff)) return fail(GS_E_INVALID, "quality_mask is -1 or has bits 0..10 alone");
+    for (int32_t i = 0; i < cfg->n_nodes; i++)
+        if (cfg->known_taxids[i] <= 0 || cfg->known_taxids[i] > 999999999 || (i && cfg->known_taxids[i] <= cfg->known_taxids[i - 1]))
+            return fail(GS_E_INVALID, "known_taxids must be positive, ascending, distinct and of at most 9 digits");
+    int rc = device == -1 ? (int)GS_OK : use_device(device);
+    if (rc) return rc;
+    gs_asmsum *h = new gs_asmsum();
+    h->device = device;
+    h->host_only = device == -1;
+    h->n_nodes = cfg->n_nodes;
+    h->quality_mask = cfg->quality_mask;
+    h->reference_only = cfg->reference_only != 0;
+    h->key_field = cfg->use_species_taxid ? 6 : 5;
+    if (h->host_only) {
+        *out = h;
+        return GS_OK;
+    }
+    const size_t nodes = (size_t)std::max(cfg->n_nodes, 1);
+    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = gs_dev_alloc(&h->d_known, sizeof(int32_t) * nodes);
+    if (e == hipSuccess) e = gs_dev_alloc(&h->d_small, sizeof(u64) * AS_S_WORDS);
+    if (e == hipSuccess && cfg->filter && cfg->n_nodes) e = gs_dev_alloc(&h->d_filter, nodes);
+    if (e == hipSuccess && cfg->n_nodes) e = hipMemcpyAsync(h->d_known, cfg->known_taxids, sizeof(int32_t) * nodes, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && h->d_filter) e = hipMemcpyAsync(h->d_filter, cfg->filter, nodes, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        gs_asmsum_destroy(h);
+        return hip_fail(e, "gs_asmsum_create");
+    }
+    if ((rc = as_entry_room(h, std::max<int64_t>(cfg->reserve_entries, 1), std::max<int64_t>(cfg->reserve_entries * 128, 1)))) {
+        gs_asmsum_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_asmsum_get_device(gs_asmsum *h, int *device) try {
+    if (!h || !device) return fail(GS_E_INVALID, "NULL argument");
+    *device = h->device;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_asmsum_submit(gs_asmsum *h, const uint8_t *text, int64_t n_bytes, int mem, int last, int64_t report[8]) try {
+    if (!h || !report) return fail(GS_E_INVALID, "NULL argument");
+    if (n_bytes < 0 || n_bytes > ((int64_t)1 << 30)) return fail(GS_E_INVALID, "a chunk holds at most 1 GiB");
+    if (n_bytes > 0 && !text) return fail(GS_E_INVALID, "text is NULL");
+    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    if (h->finished) return fail(GS_E_STATE, "gs_asmsum_submit comes in front of gs_asmsum_finish");
+    if (h->host_only) return fail(GS_E_UNSUPPORTED, "a host-only assembly summary handle (device -1) takes entries through gs_asmsum_append alone");
+    for (int i = 0; i < 8; i++) report[i] = 0;
+    report[4] = -1;
+    if (n_bytes == 0) return GS_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t n_tiles = (n_bytes + GS_AS_TILE - 1) / GS_AS_TILE;
+    const size_t padded = (size_t)n_tiles * GS_AS_TILE + 64;
+    int rc;
+    if ((rc = grow(&h->d_text, &h->text_cap, padded, h->stream))) return rc;
+    if (h->tile_cap < (size_t)n_tiles + 1) {
+        const size_t cap = (size_t)n_tiles + 1 + (size_t)n_tiles / 4;
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->tile_cap = 0;
+        if ((rc = renew(&h->d_tile, cap))) return rc;
+        if ((rc = renew(&h->d_tail, cap))) return rc;
+        h->tile_cap = cap;
+    }
+    HIP_TRY(hipMemcpyAsync(h->d_text, text, (size_t)n_bytes, mem == GS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(h->d_text + n_bytes, 0, padded - (size_t)n_bytes, h->stream));
+    u64 small[AS_S_COUNTS] = {};
+    small[AS_S_STATUS] = (u64)GS_AS_NONE;  // bad line: none; longest line: 0
+    HIP_TRY(hipMemcpy(h->d_small, small, sizeof(small), hipMemcpyHostToDevice));  // (the stream is idle between calls)
+    GsAsmsumParams P{};
+    P.text = h->d_text;
+    P.n_bytes = n_bytes;
+    P.n_tiles = n_tiles;
+    P.last = last != 0;
+    P.key_field = h->key_field;
+    P.quality_mask = h->quality_mask;
+    P.reference_only = h->reference_only;
+    P.known = h->d_known;
+    P.filter = h->d_filter;
+    P.n_nodes = h->n_nodes;
+    P.tile_lt = (unsigned long long *)h->d_tile;
+    P.tile_tail = h->d_tail;
+    P.scan_tot = (unsigned long long *)h->d_small + AS_S_SCAN;
+    P.status = (uint32_t *)(h->d_small + AS_S_STATUS);
+    P.chunk = (unsigned long long *)h->d_small + AS_S_CHUNK;
+    if ((rc = timer_start(h->timer, h->profile, h->stream))) return rc;
+    HIP_TRY(gs_launch_asmsum_tiles(&P, h->stream));
+    if ((rc = timer_stop(h->timer, h->profile, h->stream))) return rc;
+    u64 lines_tabs = 0;
+    uint8_t last_byte = 0;
+    HIP_TRY(hipMemcpyAsync(&lines_tabs, h->d_small + AS_S_SCAN, sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(&last_byte, h->d_text + n_bytes - 1, 1, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));  // the first wait of a chunk: its lines size the slots
+    const int64_t n_lines = (int64_t)(lines_tabs & 0xffffffffull) + (last_byte != '\n');
+    const int64_t n_blocks = (n_lines + GS_AS_LINE_BLOCK - 1) / GS_AS_LINE_BLOCK;
+    if (h->line_cap < (size_t)n_lines) {
+        const size_t cap = (size_t)n_lines + (size_t)n_lines / 4;
+        h->line_cap = 0;
+        if ((rc = renew(&h->d_slots, cap * GS_AS_SLOT))) return rc;
+        if ((rc = renew(&h->d_high, cap))) return rc;
+        if ((rc = renew(&h->d_verdict, cap))) return rc;
+        h->line_cap = cap;
+    }
+    if ((rc = grow(&h->d_line_blk, &h->blk_cap, (size_t)n_blocks + 1, h->stream))) return rc;
+    HIP_TRY(hipMemsetAsync(h->d_high, 0, (size_t)n_lines, h->stream));
+    P.n_lines = n_lines;
+    P.slots = h->d_slots;
+    P.high = h->d_high;
+    P.verdict = (unsigned long long *)h->d_verdict;
+    P.line_blk = (unsigned long long *)h->d_line_blk;
+    if ((rc = timer_start(h->timer, h->profile, h->stream))) return rc;
+    HIP_TRY(gs_launch_asmsum_judge(&P, h->stream));
+    if ((rc = timer_stop(h->timer, h->profile, h->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(small, h->d_small, sizeof(small), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));  // the second: its verdict and its counts, in front of the write pass
+    const uint32_t bad = (uint32_t)small[AS_S_STATUS];
+    report[5] = (int64_t)(small[AS_S_STATUS] >> 32);
+    if (bad != GS_AS_NONE) {
+        report[3] = 1;
+        report[4] = (int64_t)bad;
+        return timer_collect(h->timer);
+    }
+    const int64_t n_put = (int64_t)small[AS_S_CHUNK + GS_AS_C_KEPT], n_pool = (int64_t)small[AS_S_CHUNK + GS_AS_C_POOL];
+    report[0] = (int64_t)small[AS_S_CHUNK + GS_AS_C_COUNTED];
+    report[1] = n_put;
+    report[2] = (int64_t)small[AS_S_CHUNK + GS_AS_C_SHORT];
+    report[6] = (int64_t)small[AS_S_CHUNK + GS_AS_C_SKIPPED];
+    report[7] = n_pool;
+    if (n_put > 0) {
+        if ((rc = as_entry_room(h, n_put, n_pool))) return rc;
+        if ((rc = grow(&h->d_put_line, &h->put_cap, (size_t)n_put, h->stream))) return rc;
+        P.entries = h->d_entries;
+        P.first_entry = h->n_entries;
+        P.entry_cap = (int64_t)h->entry_cap;
+        P.first_line = h->n_lines;
+        P.pool = h->d_pool;
+        P.pool_used = (unsigned long long)h->pool_used;
+        P.pool_cap = (unsigned long long)h->pool_cap;
+        P.put_line = h->d_put_line;
+        if ((rc = timer_start(h->timer, h->profile, h->stream))) return rc;
+        HIP_TRY(gs_launch_asmsum_write(&P, n_put, h->stream));
+        if ((rc = timer_stop(h->timer, h->profile, h->stream))) return rc;
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    h->n_entries += n_put;
+    h->pool_used += n_pool;
+    h->n_counted += report[0];
+    h->n_lines += n_lines;
+    return timer_collect(h->timer);
+}
+GS_API_CATCH
+
+extern "C" int gs_asmsum_append(gs_asmsum *h, const int32_t *nodes, const uint8_t *quality, const uint8_t *is_ref, const int64_t *lines,
+                                const uint64_t *str_off, const uint8_t *pool, int64_t n, int64_t n_counted, int64_t n_lines) try {
+    if (!h) return fail(GS_E_INVALID, "asmsum is NULL");
+    if (n < 0 || n_counted < n || n_lines < n_counted) return fail(GS_E_INVALID, "n < 0, n_counted < n or n_lines < n_counted");
+    if (n > 0 && (!nodes || !quality || !is_ref || !lines || !str_off)) return fail(GS_E_INVALID, "NULL argument");
+    if (h->finished) return fail(GS_E_STATE, "gs_asmsum_append comes in front of gs_asmsum_finish");
+    for (int64_t i = 0; i < n; i++) {
+        if (nodes[i] < 0 || nodes[i] >= h->n_nodes) return fail(GS_E_INVALID, "a node is no index into known_taxids");
+        if (quality[i] < 1 || quality[i] > 10) return fail(GS_E_INVALID, "a quality is an ordinal from 1 to 10");
+        if (lines[i] < 0) return fail(GS_E_INVALID, "a line is negative");
+        for (int k = 0; k < 3; k++)
+            if (str_off[3 * i + k + 1] < str_off[3 * i + k]) return fail(GS_E_INVALID, "str_off must ascend");
+        if (str_off[3 * i + 3] == str_off[3 * i + 2]) return fail(GS_E_INVALID, "an entry has an empty ftp path");
+    }
+    const size_t n_pool = n > 0 ? (size_t)(str_off[3 * n] - str_off[0]) : 0;
+    if (n_pool > 0 && !pool) return fail(GS_E_INVALID, "pool is NULL");
+    if (n > 0 && h->host_only) {
+        for (int64_t i = 0; i < n; i++) {
+            gs_host::AsmsumEntry e;
+            e.node = nodes[i];
+            e.quality = quality[i];
+            e.is_ref = is_ref[i] != 0;
+            e.line = lines[i];
+            const char *s = (const char *)pool;
+            e.taxid.assign(s + str_off[3 * i], s + str_off[3 * i + 1]);
+            e.species.assign(s + str_off[3 * i + 1], s + str_off[3 * i + 2]);
+            e.ftp.assign(s + str_off[3 * i + 2], s + str_off[3 * i + 3]);
+            h->store.entries.push_back(std::move(e));
+        }
+        h->n_entries += n;
+    } else if (n > 0) {
+        HIP_TRY(hipSetDevice(h->device));
+        int rc = as_entry_room(h, n, (int64_t)n_pool);
+        if (rc) return rc;
+        std::vector<GsAsmEntry> ent((size_t)n);
+        for (int64_t i = 0; i < n; i++) {
+            GsAsmEntry &e = ent[(size_t)i];
+            e.node = nodes[i];
+            e.meta = (uint32_t)quality[i] | (is_ref[i] ? 1u << 8 : 0u);
+            e.line = lines[i];
+            e.pool_off = (unsigned long long)h->pool_used + (str_off[3 * i] - str_off[0]);
+            for (int k = 0; k < 3; k++) e.len[k] = (uint32_t)(str_off[3 * i + k + 1] - str_off[3 * i + k]);
+            e.pad = 0;
+        }
+        HIP_TRY(hipMemcpyAsync(h->d_entries + h->n_entries, ent.data(), (size_t)n * sizeof(GsAsmEntry), hipMemcpyHostToDevice, h->stream));
+        if (n_pool) HIP_TRY(hipMemcpyAsync(h->d_pool + h->pool_used, pool + str_off[0], n_pool, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->n_entries += n;
+        h->pool_used += (int64_t)n_pool;
+    }
+    h->n_counted += n_counted;
+    h->n_lines += n_lines;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_asmsum_finish(gs_asmsum *h, int32_t max_per_node, int64_t info[4]) try {
+    if (!h || !info) return fail(GS_E_INVALID, "NULL argument");
+    if (h->finished) return fail(GS_E_STATE, "gs_asmsum_finish was called before");
+    if (h->host_only) {
+        h->store.finish(max_per_node);
+        h->n_picked = (int64_t)h->store.picked.size();
+        h->nodes_with_entries = h->store.nodes_with_entries;
+    } else {
+        HIP_TRY(hipSetDevice(h->device));
+        const int64_t n = h->n_entries;
+        const size_t room = (size_t)std::max<int64_t>(n, 1), words = (size_t)h->n_nodes + 1;
+        size_t tmp_bytes = 0;
+        HIP_TRY(gs_asmsum_cap_bytes(n, h->n_nodes, &tmp_bytes));
+        uint32_t *node_words = nullptr, *seq = nullptr, *perm = nullptr;  // seq | seq_alt
+        u64 *key = nullptr, *lens = nullptr;                              // key | key_alt
+        void *tmp = nullptr;
+        GsAsmEntry *out = nullptr;
+        u64 *str_off = nullptr;
+        uint8_t *out_pool = nullptr;
+        u64 counts[2] = {0, 0}, pool_bytes = 0;
+        hipError_t e = gs_dev_alloc(&node_words, 4 * words * sizeof(uint32_t));
+        if (e == hipSuccess) e = gs_dev_alloc(&key, 2 * room * sizeof(u64));
+        if (e == hipSuccess) e = gs_dev_alloc(&seq, 2 * room * sizeof(uint32_t));
+        if (e == hipSuccess) e = gs_dev_alloc(&perm, room * sizeof(uint32_t));
+        if (e == hipSuccess) e = gs_dev_alloc(&tmp, std::max<size_t>(tmp_bytes, 1));
+        int rc = e == hipSuccess ? timer_start(h->timer, h->profile, h->stream) : hip_fail(e, "gs_asmsum_finish");
+        if (!rc) {
+            e = gs_asmsum_cap(h->d_entries, n, h->n_nodes, max_per_node, node_words, key, key + room, seq, seq + room, tmp, tmp_bytes, perm,
+                              (unsigned long long *)h->d_small + AS_S_COUNTS, h->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(counts, h->d_small + AS_S_COUNTS, sizeof(counts), hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+            const size_t m = (size_t)counts[0];
+            if (e == hipSuccess) e = gs_dev_alloc(&lens, (3 * m + 1) * sizeof(u64));
+            if (e == hipSuccess) e = gs_dev_alloc(&str_off, (3 * m + 1) * sizeof(u64));
+            if (e == hipSuccess) e = gs_dev_alloc(&out, std::max<size_t>(m, 1) * sizeof(GsAsmEntry));
+            if (e == hipSuccess) e = gs_asmsum_pick_sizes(h->d_entries, perm, (int64_t)m, lens, str_off, tmp, tmp_bytes, h->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(&pool_bytes, str_off + 3 * m, sizeof(u64), hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+            if (e == hipSuccess) e = gs_dev_alloc(&out_pool, std::max<size_t>((size_t)pool_bytes, 1));
+            if (e == hipSuccess) e = gs_asmsum_pick_gather(h->d_entries, perm, (int64_t)m, str_off, h->d_pool, out, out_pool, h->stream);
+            if (e == hipSuccess) rc = timer_stop(h->timer, h->profile, h->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+            if (e != hipSuccess) rc = hip_fail(e, "gs_asmsum_finish");
+        }
+        for (void *p : {(void *)node_words, (void *)key, (void *)seq, (void *)perm, (void *)tmp, (void *)lens}) gs_dev_free(p);
+        if (rc) {
+            for (void *p : {(void *)out, (void *)str_off, (void *)out_pool}) gs_dev_free(p);
+            return rc;
+        }
+        h->d_out = out;
+        h->d_str_off = str_off;
+        h->d_out_pool = out_pool;
+        h->n_picked = (int64_t)counts[0];
+        h->nodes_with_entries = (int64_t)counts[1];
+        h->out_pool_bytes = (int64_t)pool_bytes;
+        gs_dev_free(h->d_entries);  // (the picks stand for them from here on)
+        gs_dev_free(h->d_pool);
+        h->d_entries = nullptr;
+        h->d_pool = nullptr;
+        h->entry_cap = h->pool_cap = 0;
+        if ((rc = timer_collect(h->timer))) return rc;
+    }
+    h->finished = true;
+    info[0] = h->n_entries;
+    info[1] = h->n_picked;
+    info[2] = h->nodes_with_entries;
+    info[3] = h->n_counted;
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int gs_asmsum_fetch(gs_asmsum *h, int32_t *nodes, uint8_t *quality, uint8_t *is_ref, int64_t *lines, uint64_t *str_off, uint8_t *pool) try {
+    if (!h) return fail(GS_E_INVALID, "asmsum is NULL");
+    if (!h->finished) return fail(GS_E_STATE, "gs_asmsum_fetch comes behind gs_asmsum_finish");
+    const int64_t m = h->n_picked;
+    if (h->host_only) {
+        uint64_t at = 0;
+        for (int64_t j = 0; j < m; j++) {
+            const gs_host::AsmsumEntry &e = h->store.entries[h->store.picked[(size_t)j]];
+            if (nodes) nodes[j] = e.node;
+            if (quality) quality[j] = e.quality;
+            if (is_ref) is_ref[j] = e.is_ref;
+            if (lines) lines[j] = e.line;
+            for (const std::string *s : {&e.taxid, &e.species, &e.ftp}) {
+                if (str_off) str_off[3 * j + (s == &e.taxid ? 0 : s == &e.species ? 1 : 2)] = at;
+                if (pool && !s->empty()) memcpy(pool + at, s->data(), s->size());
+                at += s->size();
+            }
+        }
+        if (str_off) str_off[3 * m] = at;
+        return GS_OK;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    if (m && (nodes || quality || is_ref || lines)) {
+        std::vector<GsAsmEntry> ent((size_t)m);
+        HIP_TRY(hipMemcpy(ent.data(), h->d_out, (size_t)m * sizeof(GsAsmEntry), hipMemcpyDeviceToHost));
+        for (int64_t j = 0; j < m; j++) {
+            const GsAsmEntry &e = ent[(size_t)j];
+            if (nodes) nodes[j] = e.node;
+            if (quality) quality[j] = (uint8_t)(e.meta & 0xffu);
+            if (is_ref) is_ref[j] = (uint8_t)(e.meta >> 8 & 1u);
+            if (lines) lines[j] = e.line;
+        }
+    }
+    if (str_off) HIP_TRY(hipMemcpy(str_off, h->d_str_off, (size_t)(3 * m + 1) * sizeof(u64), hipMemcpyDeviceToHost));
+    if (pool && h->out_pool_bytes) HIP_TRY(hipMemcpy(pool, h->d_out_pool, (size_t)h->out_pool_bytes, hipMemcpyDeviceToHost));
+    return GS_OK;
+}
+GS_API_CATCH
+
+extern "C" int64_t gs_asmsum_file_name(const uint8_t *ftp, int64_t n, uint8_t *out, int64_t cap) {
+    if (!ftp || n <= 0 || cap < 0 || (cap > 0 && !out)) return fail(GS_E_INVALID, "an ftp path has at least one byte (the reference throws on an empty one)");
+    size_t from = 0, to = 0;
+    gs_host::asmsum_base_name(ftp, (size_t)n, &from, &to);
+    static const char suffix[] = "_genomic.fna.gz";
+    const int64_t base = (int64_t)(to - from), len = base + (int64_t)sizeof(suffix) - 1;
+    for (int64_t i = 0; i < len && i < cap; i++) out[i] = i < base ? ftp[from + (size_t)i] : (uint8_t)suffix[i - base];
+    return len;
+}
+
+extern "C" int gs_asmsum_kernel_time(gs_asmsum *h, int profile, int64_t *launches, double *total_ms) try {
+    if (!h) return fail(GS_E_INVALID, "asmsum is NULL");
     if (h->host_only) {
         if (launches) *launches = 0;
         if (total_ms) *total_ms = 0;

@@ -8,6 +8,7 @@
 #include "gs_krakenparse.h"
 #include "gs_genomeparse.h"
 #include "gs_accmapparse.h"
+#include "gs_asmsumparse.h"
 
 #include "gs_control.h"
 
@@ -3789,6 +3790,221 @@ extern "C" int gs_host_accmap_files(const char *const *paths, int n_paths, int d
         if (gs_accmap_finish(c.am, info) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
         *out = c.am;
         c.am = nullptr;  // (the caller's now)
+    }
+    if (totals) {
+        c.tot.seconds_total = now_s() - t_start;
+        *totals = c.tot;
+    }
+    return err;
+} catch (const std::bad_alloc &) {
+    return hfail(GS_E_NOMEM, "out of host memory");
+} catch (const std::exception &e) {
+    return hfail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
+}
+
+// ---- Genbank assembly summary files to the picks per node (AssemblySummaryReader.getRelevantEntries under FastaFilesFromGenbankGoal;
+// gs_asmsum on the device, gs_asmsumparse.h for what it refuses)
+namespace {
+
+struct AsGuard {
+    gs_asmsum *&as;
+    ~AsGuard() {
+        if (as) gs_asmsum_destroy(as);
+        as = nullptr;
+    }
+};
+
+struct AsCtx {
+    gs_asmsum *as = nullptr;  // the device's handle, or (GS_HOST_FAST=0) a host-only one
+    AsmsumExact exact;        // the record-by-record parser: its line number is the current file's
+    int64_t file_line0 = 0;   // the lines of the files in front of it
+    int64_t flushed_counted = 0, flushed_lines = 0;
+    gs_host_asmsum_totals tot{};
+    int prog_file = 0;
+    std::vector<int32_t> nodes;
+    std::vector<uint8_t> quality, is_ref, pool;
+    std::vector<int64_t> lines;
+    std::vector<uint64_t> str_off;
+    bool report(int64_t pos, bool gz) {
+        if (!trk().chunk(prog_file, pos, gz, exact.line_no)) return false;
+        trk().stopped(prog_file, exact.line_no);
+        return true;
+    }
+};
+
+// what the parser has made since the last call goes into the handle, in input order
+int as_flush(AsCtx &c) {
+    const size_t n = c.exact.entries.size();
+    c.nodes.assign(n + 1, 0);
+    c.quality.assign(n + 1, 0);
+    c.is_ref.assign(n + 1, 0);
+    c.lines.assign(n + 1, 0);
+    c.str_off.assign(3 * n + 1, 0);
+    c.pool.clear();
+    for (size_t i = 0; i < n; i++) {
+        const AsmsumEntry &e = c.exact.entries[i];
+        c.nodes[i] = e.node;
+        c.quality[i] = e.quality;
+        c.is_ref[i] = e.is_ref;
+        c.lines[i] = c.file_line0 + e.line;
+        for (const std::string *s : {&e.taxid, &e.species, &e.ftp}) {
+            c.pool.insert(c.pool.end(), s->begin(), s->end());
+            c.str_off[3 * i + (s == &e.taxid ? 1 : s == &e.species ? 2 : 3)] = c.pool.size();
+        }
+    }
+    c.pool.push_back(0);
+    const int64_t counted = c.exact.counted - c.flushed_counted, n_lines = c.exact.line_no - c.flushed_lines;
+    c.flushed_counted = c.exact.counted;
+    c.flushed_lines = c.exact.line_no;
+    c.tot.counted += counted;
+    c.tot.kept += (int64_t)n;
+    if (gs_asmsum_append(c.as, c.nodes.data(), c.quality.data(), c.is_ref.data(), c.lines.data(), c.str_off.data(), c.pool.data(), (int64_t)n, counted,
+                         n_lines) != GS_OK)
+        return hfail(GS_E_HIP, gs_last_error());
+    c.exact.entries.clear();
+    return GS_OK;
+}
+
+int as_feed(AsCtx &c, const std::string &path, const uint8_t *p, size_t n, bool last) {
+    if (!c.exact.feed(p, n, last)) return hfail(GS_E_INVALID, path + ": line " + std::to_string((long long)c.exact.line_no) + ": " + c.exact.error);
+    return as_flush(c);
+}
+
+// the rest of a stream, record by record: the file from `offset` on (in its text), or a memory range that ends the stream.  The bytes
+// go to the parser as they are: NUL bytes are data here, and CR ends a line
+int as_cpu(AsCtx &c, const std::string &path, int64_t offset, const uint8_t *mem, size_t mem_n) {
+    c.tot.host_chunks++;
+    if (mem) {
+        const int err = as_feed(c, path, mem, mem_n, true);
+        return err ? err : c.report(0, false) ? cancelled_rc() : (int)GS_OK;
+    }
+    gzFile gz = gzopen(path.c_str(), "rb");  // (zlib reads plain files transparently, gzip by content, member after member)
+    if (!gz) return hfail(GS_E_IO, "cannot open " + path);
+    gzbuffer(gz, 1 << 20);
+    if (offset != 0 && gzseek(gz, (z_off_t)offset, SEEK_SET) != (z_off_t)offset) {
+        gzclose(gz);
+        return hfail(GS_E_IO, "cannot seek in " + path);
+    }
+    size_t piece = (size_t)4 << 20;
+    if (const char *e = getenv("GS_HOST_BLOCK_BYTES")) piece = (size_t)std::max<long long>(1, atoll(e));
+    std::vector<uint8_t> text(piece);
+    int err = GS_OK;
+    for (bool eof = false; !eof && !err;) {
+        const int got = gzread(gz, text.data(), (unsigned)text.size());
+        if (got < 0) {
+            err = hfail(GS_E_IO, "cannot read " + path);
+            break;
+        }
+        eof = got == 0;
+        err = as_feed(c, path, text.data(), (size_t)got, eof);
+        if (!err && c.report((int64_t)gzoffset(gz), false)) err = cancelled_rc();
+    }
+    gzclose(gz);
+    return err;
+}
+
+// One file through the device, as am_device_file: a chunk the device refuses goes through the parser and its entries are appended,
+// so the input order stays; a line that does not fit a block sends the rest of the file through the parser; so does the
+// unterminated tail.
+int as_device_file(AsCtx &c, const std::string &path, bool gzip) {
+    size_t block;
+    int readers = 0;
+    reader_shape(gzip, &block, &readers);
+    TextReader tr;
+    int err = tr.open(path, block, readers, gzip);
+    if (err) {
+        tr.close();
+        return err;
+    }
+    ChunkCutter cut;
+    cut.mode = ChunkCutter::LINES;
+    int64_t fallback_off = -1;
+    tr.start();
+    for (int64_t i = 0; !err; i++) {
+        TextSlot &sl = tr.wait_full(i);
+        if ((err = block_error(tr, sl, path))) break;
+        const bool eof = sl.eof;
+        const ChunkCutter::Cut what = cut_block(cut, tr, sl);
+        if (what == ChunkCutter::FALLBACK) {
+            fallback_off = cut.file_off;
+        } else if (what == ChunkCutter::CHUNK && cut.bytes > 0) {
+            int64_t rep[8];
+            if (gs_asmsum_submit(c.as, cut.start, cut.bytes, GS_MEM_HOST, 0, rep) != GS_OK) {
+                err = hfail(GS_E_HIP, gs_last_error());
+                break;
+            }
+            if (rep[3] != 0) {  // refused: this chunk record by record
+                c.tot.host_chunks++;
+                err = as_feed(c, path, cut.start, (size_t)cut.bytes, false);
+            } else {
+                c.tot.device_chunks++;
+                c.tot.counted += rep[0];
+                c.tot.kept += rep[1];
+                c.exact.line_no += rep[0] + rep[2] + rep[6];
+                c.flushed_lines = c.exact.line_no;
+            }
+            cut.commit();
+            if (!err && c.report(cut.file_off, gzip)) err = cancelled_rc();  // (the record is out: the block may go back)
+        } else if (what == ChunkCutter::CHUNK) {
+            cut.commit();
+        }
+        tr.release(i);
+        if (eof || fallback_off >= 0) break;
+    }
+    tr.close();
+    if (err) return err;
+    if (fallback_off >= 0) return as_cpu(c, path, fallback_off, nullptr, 0);
+    if (!cut.carry.empty()) return as_cpu(c, path, 0, cut.carry.data(), cut.carry.size());
+    return GS_OK;
+}
+
+}  // namespace
+
+extern "C" int gs_host_asmsum_files(const char *const *paths, int n_paths, int device, const gs_asmsum_cfg *cfg, int32_t max_per_node, gs_asmsum **out,
+                                    gs_host_asmsum_totals *totals) try {
+    if (out) *out = nullptr;
+    if (!paths || n_paths < 0 || !cfg || !out) return hfail(GS_E_INVALID, "NULL argument");
+    for (int f = 0; f < n_paths; f++)
+        if (!paths[f]) return hfail(GS_E_INVALID, "NULL path");
+    bool fast = true;
+    if (const char *e = getenv("GS_HOST_FAST")) fast = atoi(e) != 0;
+    const double t_start = now_s();
+    AsCtx c;
+    AsGuard guard{c.as};
+    // (the handle checks cfg; a host-only one, device -1, touches no device)
+    if (const int rc = gs_asmsum_create(&c.as, fast ? device : -1, cfg)) return hfail(rc, gs_last_error());
+    if (cfg->n_nodes) c.exact.known.assign(cfg->known_taxids, cfg->known_taxids + cfg->n_nodes);
+    if (cfg->filter && cfg->n_nodes) c.exact.filter.assign(cfg->filter, cfg->filter + cfg->n_nodes);
+    c.exact.quality_mask = cfg->quality_mask;
+    c.exact.reference_only = cfg->reference_only != 0;
+    c.exact.use_species = cfg->use_species_taxid != 0;
+    int err = GS_OK;
+    TrackerScope progress(paths, n_paths);
+    Tracker &tk = progress.t;
+    for (int f = 0; f < n_paths && !err; f++) {
+        const std::string path(paths[f]);
+        c.file_line0 += c.exact.line_no;
+        c.exact.begin_stream();  // every file is a stream of its own, all of them go into one handle
+        c.flushed_lines = 0;
+        c.prog_file = f;
+        if (tk.file_start(f)) {
+            tk.stopped(f, 0);
+            err = cancelled_rc();
+            break;
+        }
+        const int kind = fast ? text_path_kind(path) : 0;
+        err = kind ? as_device_file(c, path, kind == 2 || kind == 4) : as_cpu(c, path, 0, nullptr, 0);
+        if (!err && tk.file_end(f, c.exact.line_no)) err = cancelled_rc();
+    }
+    if (!err && tk.close()) err = cancelled_rc();
+    c.tot.lines = c.file_line0 + c.exact.line_no;
+    if (!err) {
+        int64_t info[4];
+        if (gs_asmsum_finish(c.as, max_per_node, info) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
+        c.tot.picked = info[1];
+        c.tot.nodes = info[2];
+        *out = c.as;
+        c.as = nullptr;  // (the caller's now)
     }
     if (totals) {
         c.tot.seconds_total = now_s() - t_start;

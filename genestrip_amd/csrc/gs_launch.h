@@ -266,6 +266,26 @@ hipError_t gs_accmap_sort_entries(const uint8_t *keys, const int32_t *nodes, int
 hipError_t gs_launch_accmap_lookup(const uint8_t *headers, const u64 *header_off, int64_t n, int complete_only, const uint8_t *keys,
                                    const int32_t *nodes, int64_t n_entries, int32_t *node_out, hipStream_t stream);
 
+// ---- gs_asmsum.hip: assembly summary lines -> per-node picks
+// tiles and their scan: scan_tot[0] = newlines | tabs << 32 of the chunk
+hipError_t gs_launch_asmsum_tiles(const GsAsmsumParams *P, hipStream_t stream);
+// slots of every line, the verdicts, the chunk's counters and the prefix of line_blk: what the write pass would store
+hipError_t gs_launch_asmsum_judge(const GsAsmsumParams *P, hipStream_t stream);
+// for a chunk that was not refused and whose entries and strings have room
+hipError_t gs_launch_asmsum_write(const GsAsmsumParams *P, int64_t n_put, hipStream_t stream);
+hipError_t gs_asmsum_cap_bytes(int64_t n, int32_t n_nodes, size_t *tmp_bytes);
+// the cap: node_words: 4 * (n_nodes + 1) words (entries per node, their prefix, picks per node, their prefix); key / key_alt / seq /
+// seq_alt / perm: n each; counts: [2] picked entries, nodes with entries.  perm[0 .. picked) are the entry numbers, nodes ascending,
+// inside a node the reference's list order
+hipError_t gs_asmsum_cap(const GsAsmEntry *entries, int64_t n, int32_t n_nodes, int32_t max_per_node, uint32_t *node_words, u64 *key, u64 *key_alt,
+                         uint32_t *seq, uint32_t *seq_alt, void *tmp, size_t tmp_bytes, uint32_t *perm, u64 *counts, hipStream_t stream);
+// lens: 3 m + 1 words of scratch; str_off: 3 m + 1 offsets into pool_out, which takes the strings; out[j] = entries[perm[j]] with
+// pool_off = str_off[3 j]
+hipError_t gs_asmsum_pick_sizes(const GsAsmEntry *entries, const uint32_t *perm, int64_t m, u64 *lens, u64 *str_off, void *tmp, size_t tmp_bytes,
+                                hipStream_t stream);
+hipError_t gs_asmsum_pick_gather(const GsAsmEntry *entries, const uint32_t *perm, int64_t m, const u64 *str_off, const uint8_t *pool, GsAsmEntry *out,
+                                 uint8_t *pool_out, hipStream_t stream);
+
 // ---- gs_taxtree.hip: nodes.dmp lines -> tree arrays; select; small tree
 hipError_t gs_launch_taxtree_tiles(const GsTaxScanParams *P, hipStream_t stream);
 hipError_t gs_launch_taxtree_scan(const GsTaxScanParams *P, hipStream_t stream);

@@ -466,6 +466,51 @@ struct GsAccmapParams {
     int32_t *regions;             // n_nodes: entries per node
 };
 
+// ---- gs_asmsum.hip: Genbank assembly summary lines -> per-node picks (the fastasgenbank goal)
+#define GS_AS_TILE 4096       // bytes per scan block: GS_SCAN_BLOCK threads, 16 bytes each
+#define GS_AS_MAX_LINE 4096   // bytes of a line with its newline beyond which the device refuses the chunk
+#define GS_AS_NONE 0xffffffffu
+#define GS_AS_LINE_BLOCK 256  // lines per judging block (GS_SCAN_BLOCK)
+#define GS_AS_SLOT 16         // 16-bit words of a line's slot (GS_AS_S_*)
+enum { GS_AS_S_START = 0,     // slot: the line's first byte in the chunk (two words)
+       GS_AS_S_TABS = 2,      // its tabs
+       GS_AS_S_LEN = 3,       // its bytes without the terminator
+       GS_AS_S_TAB = 4 };     // nine words: tabs number 4 5 6 7 10 11 12 19 20, as offsets from the line's first byte
+enum { GS_AS_BAD_LINE = 0, GS_AS_LONGEST = 1, GS_AS_WORDS = 2 };
+enum { GS_AS_C_COUNTED = 0, GS_AS_C_KEPT = 1, GS_AS_C_SHORT = 2, GS_AS_C_SKIPPED = 3, GS_AS_C_POOL = 4, GS_AS_C_WORDS = 6 };  // the chunk's counters
+#define GS_AS_KEPT (1ull << 63)  // verdict of a line: kept | is_ref << 40 | quality << 32 | node
+struct GsAsmEntry {           // one kept entry, 40 bytes
+    int32_t node;
+    uint32_t meta;            // quality | is_ref << 8
+    int64_t line;             // 0-based, of the whole stream
+    unsigned long long pool_off;  // where its three strings lie in the pool, back to back: tax id, species tax id, ftp path
+    uint32_t len[3], pad;
+};
+struct GsAsmsumParams {
+    const uint8_t *text;          // n_bytes of whole lines, zero bytes behind them up to n_tiles * GS_AS_TILE + 64
+    int64_t n_bytes, n_tiles, n_lines;  // n_lines: newlines, and one more for an unterminated tail
+    int32_t last;                 // != 0: the stream ends with this chunk, whose final line need not be terminated
+    int32_t key_field;            // 5 or 6
+    int32_t quality_mask, reference_only;
+    const int32_t *known;         // n_nodes tax ids, ascending
+    const uint8_t *filter;        // n_nodes flags, or nullptr
+    int32_t n_nodes, pad;
+    unsigned long long *tile_lt;  // per tile: newlines | tabs << 32, then their exclusive prefix (gs_launch_scan_blocks)
+    uint32_t *tile_tail;          // per tile: (offset of its last newline + 1, 0: none) | tabs behind that newline << 16
+    unsigned long long *scan_tot; // [2] the sums: of tile_lt, of line_blk
+    uint32_t *status;             // GS_AS_WORDS
+    unsigned long long *chunk;    // GS_AS_C_WORDS
+    uint16_t *slots;              // n_lines slots of GS_AS_SLOT words
+    uint8_t *high;                // n_lines: != 0: a byte from 0x80 on in the line's key field.  Zeroed by the caller
+    unsigned long long *verdict;  // n_lines
+    unsigned long long *line_blk; // per block of GS_SCAN_BLOCK lines: kept entries | their pool bytes << 32, then the exclusive prefix
+    uint32_t *put_line;           // the write pass: per entry of the chunk, its line in the chunk
+    GsAsmEntry *entries;          // the write pass: entry_cap of them
+    int64_t first_entry, entry_cap, first_line;
+    uint8_t *pool;                // pool_cap bytes
+    unsigned long long pool_used, pool_cap;
+};
+
 // ---- gs_taxtree.hip: nodes.dmp lines -> tree arrays (the taxtree / taxnodes goals)
 #define GS_TT_TILE 4096       // bytes per scan block: GS_SCAN_BLOCK threads, 16 bytes each
 #define GS_TT_MAX_LINE 4096   // the reference's line buffer: a longer line is split there

@@ -62,6 +62,7 @@ def lib():
         "gs_host_kraken_count_files": (ci, [ci, vp, ci, vp, ci, C.c_char_p, vp, C.c_int32, vp, i64, vp, vp]),
         "gs_host_genome_files": (ci, [vp, ci, ci, vp, vp, vp, vp, vp]),
         "gs_host_accmap_files": (ci, [vp, ci, ci, vp, ci, vp, vp]),
+        "gs_host_asmsum_files": (ci, [vp, ci, ci, vp, C.c_int32, vp, vp]),
         "gs_host_genome_files_mapped": (ci, [vp, ci, ci, vp, ci, vp, vp, vp, vp, vp]),
         "gs_host_taxtree_files": (ci, [ci, C.c_char_p, C.c_char_p, vp, vp]),
         "gs_host_read_taxids_file": (ci, [C.c_char_p, vp, vp, vp, vp, i64]),
@@ -583,6 +584,43 @@ def accmap_files(paths, known_taxids, categories, statuses, seq_type="GENOMIC", 
     m = _b.DeviceAccessionMap._wrap(h, known)
     m.n_entries, m.n_passing = totals["put"], totals["passing"]
     return m, totals
+
+
+class AsmsumTotals(C.Structure):
+    _fields_ = [("lines", C.c_int64), ("counted", C.c_int64), ("kept", C.c_int64), ("picked", C.c_int64), ("nodes", C.c_int64),
+                ("device_chunks", C.c_int64), ("host_chunks", C.c_int64), ("seconds_total", C.c_double)]
+
+
+def assembly_summary_files(paths, known_taxids, selected=None, qualities=("COMPLETE_LATEST", "CHROMOSOME_LATEST"), reference_only=False,
+                           use_species_taxid=False, max_per_taxid=1, device=0):
+    """gs_host_asmsum_files: the fastasgenbank goal over Genbank assembly summary files (plain, gzip, BGZF) ->
+    ({node: [entry, ...]}, total, totals).  An entry is a dict of taxid, species_taxid, ftp_url, file_name (bytes), quality (the name
+    of the AssemblyQuality), is_reference and line; a node is an index into known_taxids; total is the number of records of 20 fields
+    and more.  selected: the nodes of the taxfromgenbank set (any iterable of nodes) or None for every node; given and empty, the
+    answer is {} and no file is opened, as in the goal.  qualities None allows every quality.  Chunks of whole lines are judged on the
+    device, what it refuses by a record-by-record restatement of the reference; GS_HOST_FAST=0 sends everything through the latter.  A
+    stop on request raises Cancelled."""
+    known = np.ascontiguousarray(known_taxids, dtype=np.int32)
+    flt = None
+    if selected is not None:
+        selected = [int(x) for x in selected]
+        if not selected:
+            return {}, 0, {f: 0 for f, _ in AsmsumTotals._fields_}
+        flt = np.zeros(len(known), dtype=np.uint8)
+        flt[np.asarray(selected, dtype=np.int64)] = 1
+    cfg = _b.DeviceAssemblySummary.config(known, flt, qualities, reference_only, use_species_taxid)
+    paths = [os.fspath(p) for p in paths]
+    tot = AsmsumTotals()
+    h = C.c_void_p()
+    rc = lib().gs_host_asmsum_files(_cstr_array(paths), len(paths), int(device), C.byref(cfg), int(max_per_taxid), C.byref(h), C.byref(tot))
+    totals = {f: getattr(tot, f) for f, _ in AsmsumTotals._fields_}
+    _check(rc, totals=totals)
+    out = {}
+    with _b.DeviceAssemblySummary._wrap(h, (totals["kept"], totals["picked"], totals["nodes"], totals["counted"])) as a:
+        for node, taxid, species, ftp, quality, is_ref, line in a.fetch():
+            out.setdefault(node, []).append({"taxid": taxid, "species_taxid": species, "ftp_url": ftp, "file_name": _b.file_name_of(ftp),
+                                             "quality": _b.ASSEMBLY_QUALITIES[quality], "is_reference": is_ref, "line": line})
+    return out, totals["counted"], totals
 
 
 def taxtree_files(nodes_path, names_path=None, device=0):

@@ -1176,6 +1176,68 @@ int gs_accmap_kernel_time(gs_accmap *am, int profile, int64_t *launches, double 
 int gs_accmap_destroy(gs_accmap *am);
 
 /* ---------------------------------------------------------------------------------------------------
+ * asmsum: lines of a Genbank assembly summary to the picks per tree node (genestrip_amd/csrc/gs_asmsum.hip)
+ *
+ * Replaces AssemblySummaryReader.getRelevantEntries (C/genbank/AssemblySummaryReader.java:104-144) and the cap of
+ * FastaFilesFromGenbankGoal (C/goals/genbank/FastaFilesFromGenbankGoal.java:101-150), the fastasgenbank goal, for chunks of whole
+ * lines inside the grammar stated at the head of gs_asmsum.hip: no CR, no line above 4096 bytes with its newline, no byte from 0x80
+ * on in the key field of a record of 20 fields and more, no kept entry with an empty ftp field.  A chunk outside it is REFUSED: it
+ * leaves the handle as it was, and the caller parses it record by record (genestrip_amd/csrc/gs_asmsumparse.h) and hands its
+ * entries in through gs_asmsum_append, so that the input order -- which decides at the cut of the cap -- is kept.
+ *
+ * The tree reaches the handle as known_taxids[n_nodes]: ascending, distinct, positive, at most 9 digits.  A node is its index in that
+ * array.  A quality is the ordinal of AssemblyQuality: 1 COMPLETE_LATEST, 2 COMPLETE, 3 CHROMOSOME_LATEST, 4 CHROMOSOME,
+ * 5 SCAFFOLD_LATEST, 6 SCAFFOLD, 7 CONTIG_LATEST, 8 CONTIG, 9 LATEST, 10 NONE.  A line is 0-based and counts every line of the stream,
+ * comment and empty ones too.  The reference's result is a HashMap; here the nodes come out in ascending order, and the tax id,
+ * species tax id and ftp path of an entry are the file's bytes, not decoded strings.
+ *
+ * gs_asmsum_create   cfg: the tree; filter: n_nodes flags (the taxfromgenbank set) or NULL for every node; quality_mask: bit q allows
+ *                    ordinal q, -1 is the reference's null list (all), 0 allows none; reference_only; use_species_taxid: the key is
+ *                    field 6, not field 5; entries to make room for at once.  device -1: a HOST-ONLY handle: it touches no device,
+ *                    takes entries through gs_asmsum_append alone (gs_asmsum_submit: GS_E_UNSUPPORTED), and finishes and fetches
+ *                    on the host.
+ * gs_asmsum_submit   text: n_bytes (at most 1 GiB) of whole lines in host or device memory (mem), free again on return.  last != 0:
+ *                    the stream ends here and its final line need not be terminated.  report: [0] counted records (20 fields and
+ *                    more), [1] kept entries, [2] records of fewer than 20 fields, [3] 1: refused (then [0] [1] [2] are 0 and the
+ *                    caller owes them), [4] the first line outside the grammar (0-based in the chunk; -1: none), [5] the longest
+ *                    line with its newline, [6] comment and empty lines, [7] bytes added to the string pool.
+ * gs_asmsum_append   n entries made elsewhere, host memory, in input order: nodes, quality, is_ref, lines (of the whole stream),
+ *                    str_off[3 n + 1] into pool (tax id, species tax id, ftp path of each; the ftp path is not empty).  n_counted:
+ *                    the counted records of the same lines; n_lines: those lines, all of them: the next submit's first line
+ *                    follows them.
+ * gs_asmsum_finish   the cap: per node, if max_per_node > 0 and the node has more entries, they are sorted stably, highest ordinal
+ *                    first, and cut from the front until max_per_node remain; a node that is not cut keeps input order.  info:
+ *                    [0] kept entries, [1] picked entries, [2] nodes with entries, [3] counted records in all.  Behind it submit
+ *                    and append are GS_E_STATE; in front of it fetch is.
+ * gs_asmsum_fetch    host arrays, any of them NULL: the picked entries grouped by ascending node, inside a node in the reference's
+ *                    list order: nodes, quality, is_ref, lines (info[1] each), str_off[3 * info[1] + 1] into pool.
+ * gs_asmsum_file_name  AssemblyEntry's file name of an ftp path of n >= 1 bytes: the bytes behind its last '/', or, if that is its
+ *                    last byte, between the '/' in front of it and it, and "_genomic.fna.gz".  Returns the name's length, of which
+ *                    min(length, cap) bytes are written to out; negative: an error code.
+ * gs_asmsum_kernel_time  profile != 0: from now on scan and finish run between events; what they add up to so far.
+ * NULL or negative arguments: GS_E_INVALID, before any device call.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct gs_asmsum gs_asmsum;
+typedef struct {
+    int32_t n_nodes;
+    const int32_t *known_taxids;
+    const uint8_t *filter;
+    int32_t quality_mask;
+    int32_t reference_only, use_species_taxid;
+    int64_t reserve_entries;
+} gs_asmsum_cfg;
+int gs_asmsum_create(gs_asmsum **out, int device, const gs_asmsum_cfg *cfg);
+int gs_asmsum_submit(gs_asmsum *as, const uint8_t *text, int64_t n_bytes, int mem, int last, int64_t report[8]);
+int gs_asmsum_append(gs_asmsum *as, const int32_t *nodes, const uint8_t *quality, const uint8_t *is_ref, const int64_t *lines,
+                     const uint64_t *str_off, const uint8_t *pool, int64_t n, int64_t n_counted, int64_t n_lines);
+int gs_asmsum_finish(gs_asmsum *as, int32_t max_per_node, int64_t info[4]);
+int gs_asmsum_fetch(gs_asmsum *as, int32_t *nodes, uint8_t *quality, uint8_t *is_ref, int64_t *lines, uint64_t *str_off, uint8_t *pool);
+int64_t gs_asmsum_file_name(const uint8_t *ftp, int64_t n, uint8_t *out, int64_t cap);
+int gs_asmsum_get_device(gs_asmsum *as, int *device);
+int gs_asmsum_kernel_time(gs_asmsum *as, int profile, int64_t *launches, double *total_ms);
+int gs_asmsum_destroy(gs_asmsum *as);
+
+/* ---------------------------------------------------------------------------------------------------
  * taxtree: NCBI nodes.dmp / names.dmp to the arrays of the tree, the taxnodes selection and the tree a database carries
  * (genestrip_amd/csrc/gs_taxtree.hip, genestrip_amd/csrc/gs_taxparse.h)
  *

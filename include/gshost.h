@@ -246,6 +246,27 @@ typedef struct {
 int gs_host_accmap_files(const char *const *paths, int n_paths, int device, const gs_accmap_cfg *cfg, int count_only, gs_accmap **out,
                          gs_host_accmap_totals *totals);
 
+/* The fastasgenbank goal over Genbank assembly summary files (AssemblySummaryReader.getRelevantEntries, C/genbank/
+ * AssemblySummaryReader.java:104-144, under the cap of FastaFilesFromGenbankGoal, C/goals/genbank/FastaFilesFromGenbankGoal.java:101-150):
+ * every file (plain or gzip, BGZF included) is one stream, all of them go into one handle, and a line's number counts the lines of the
+ * files in front of it too.  Chunks of whole lines are judged on the device (gs_asmsum_submit, include/gsgpu.h); a chunk the device
+ * refuses (a CR, a line above 4096 bytes, a byte from 0x80 on in a key field), a line that does not fit a reader block with the rest of
+ * its file, the unterminated tail of a file and, under GS_HOST_FAST=0, everything go through the record-by-record restatement of the
+ * reference (genestrip_amd/csrc/gs_asmsumparse.h), whose entries join the handle in input order (gs_asmsum_append).  Under
+ * GS_HOST_FAST=0 no device is used and *out is a host-only handle (device -1).  *out is the finished handle (gs_asmsum_finish with
+ * max_per_node; gs_asmsum_fetch gives the picks), the caller's to destroy.  Where the reference throws -- a kept entry with an empty ftp
+ * path -- the call fails with GS_E_INVALID and gs_host_last_error names the file and the 1-based line of that file.  Progress records
+ * count lines; on GS_E_CANCELLED no handle is returned.  The goal's early exit (an empty taxfromgenbank set: no file is read) is the
+ * caller's. */
+typedef struct {
+    int64_t lines, counted, kept;        /* lines read; records of 20 fields and more; entries kept in front of the cap */
+    int64_t picked, nodes;               /* entries behind the cap; nodes with entries */
+    int64_t device_chunks, host_chunks;  /* chunks the device judged; chunks (and rests of files) the record-by-record parser took */
+    double seconds_total;
+} gs_host_asmsum_totals;
+int gs_host_asmsum_files(const char *const *paths, int n_paths, int device, const gs_asmsum_cfg *cfg, int32_t max_per_node, gs_asmsum **out,
+                         gs_host_asmsum_totals *totals);
+
 /* The taxtree goal over an NCBI taxonomy dump (TaxTree(File, boolean), C/tax/TaxTree.java:92-122): nodes_path (nodes.dmp) and, unless
  * NULL, names_path (names.dmp), each plain or gzip, BGZF included.  Chunks of whole nodes lines are scanned on the device
  * (gs_taxtree_submit_nodes, include/gsgpu.h); a chunk the device refuses, a line that does not fit a reader block with the rest of its
