@@ -7192,20 +7192,145 @@ extern "C" int gs_krakencount_kernel_time(gs_krakencount *h, int profile, int64_
 }
 
 // ---------------------------------------------------------------------------------------------------
-// accmap: RefSeq catalog lines to the accession map (gs_accmap.hip)
+// chunks of whole lines: what the accmap, asmsum and taxtree handles share
 // ---------------------------------------------------------------------------------------------------
-struct gs_accmap {
+// What the handles that take chunks of whole lines share (gs_accmap, gs_asmsum, gs_taxtree): the stream, the padded text of the chunk
+// under way, the scan words of its tiles, the small words -- the first of them the status: bad line | longest line << 32 -- and the
+// kernel timer.  Each handle is one of these in front of its own members.
+struct LineStage {
     int device = 0;
     hipStream_t stream = nullptr;
+    uint8_t *d_text = nullptr;
+    size_t text_cap = 0;
+    u64 *d_tile = nullptr;  // tile_cap entries per scan word
+    uint32_t *d_tail = nullptr;
+    size_t tile_cap = 0;
+    u64 *d_small = nullptr;
+    bool profile = false;
+    KernelTimer timer;
+};
+enum { LINES_SMALL_MAX = 16 };  // the small words a chunk resets are fewer
+
+static void lines_free(LineStage &s) {
+    timer_free(s.timer);
+    for (void *p : {(void *)s.d_text, (void *)s.d_tile, (void *)s.d_tail, (void *)s.d_small}) gs_dev_free(p);
+    if (s.stream) hipStreamDestroy(s.stream);
+}
+
+// the argument checks in front of a chunk; the handle's own checks (its state, host only) follow them in its entry point
+static int lines_args(const void *h, const uint8_t *text, int64_t n_bytes, int mem, const int64_t *report) {
+    if (!h || !report) return fail(GS_E_INVALID, "NULL argument");
+    if (n_bytes < 0 || n_bytes > ((int64_t)1 << 30)) return fail(GS_E_INVALID, "a chunk holds at most 1 GiB");
+    if (n_bytes > 0 && !text) return fail(GS_E_INVALID, "text is NULL");
+    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    return GS_OK;
+}
+
+// The opening of a chunk: the report of an empty chunk; then, unless the chunk is empty, room for its text in tiles of `tile` bytes and
+// for `words` scan words per tile, the text behind zero padding, and the first n_small small words reset with `none` as the bad line.
+static int lines_open(LineStage &s, const uint8_t *text, int64_t n_bytes, int mem, int64_t report[8], int tile, int words, uint32_t none, int n_small,
+                      int64_t *tiles) {
+    for (int i = 0; i < 8; i++) report[i] = 0;
+    report[4] = -1;
+    if (n_bytes == 0) return GS_OK;
+    HIP_TRY(hipSetDevice(s.device));
+    const int64_t n_tiles = *tiles = (n_bytes + tile - 1) / tile;
+    const size_t padded = (size_t)n_tiles * (size_t)tile + 64;
+    int rc;
+    if ((rc = grow(&s.d_text, &s.text_cap, padded, s.stream))) return rc;
+    if (s.tile_cap < (size_t)n_tiles + 1) {
+        const size_t cap = (size_t)n_tiles + 1 + (size_t)n_tiles / 4;
+        HIP_TRY(hipStreamSynchronize(s.stream));
+        s.tile_cap = 0;
+        if ((rc = renew(&s.d_tile, (size_t)words * cap))) return rc;
+        if ((rc = renew(&s.d_tail, cap))) return rc;
+        s.tile_cap = cap;
+    }
+    HIP_TRY(hipMemcpyAsync(s.d_text, text, (size_t)n_bytes, mem == GS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s.stream));
+    HIP_TRY(hipMemsetAsync(s.d_text + n_bytes, 0, padded - (size_t)n_bytes, s.stream));
+    u64 small[LINES_SMALL_MAX] = {};
+    small[0] = (u64)none;  // bad line: none; longest line: 0
+    HIP_TRY(hipMemcpy(s.d_small, small, (size_t)n_small * sizeof(u64), hipMemcpyHostToDevice));  // (the stream is idle between calls)
+    return GS_OK;
+}
+
+// the verdict of a chunk out of its status word: report[5] its longest line, and of a refused chunk report[3] and the bad line in
+// report[4].  true: refused
+static bool lines_refused(u64 status, uint32_t none, int64_t report[8]) {
+    const uint32_t bad = (uint32_t)status;
+    report[5] = (int64_t)(status >> 32);
+    if (bad == none) return false;
+    report[3] = 1;
+    report[4] = (int64_t)bad;
+    return true;
+}
+
+// the kernel time so far, and whether the launches from here on are timed
+static int lines_kernel_time(LineStage &s, bool host_only, int profile, int64_t *launches, double *total_ms) {
+    if (host_only) {
+        if (launches) *launches = 0;
+        if (total_ms) *total_ms = 0;
+        return GS_OK;
+    }
+    HIP_TRY(hipSetDevice(s.device));
+    HIP_TRY(hipStreamSynchronize(s.stream));
+    int rc = timer_collect(s.timer);
+    if (rc) return rc;
+    s.profile = profile != 0;
+    if (launches) *launches = s.timer.launches;
+    if (total_ms) *total_ms = s.timer.total_ms;
+    return GS_OK;
+}
+
+static int lines_get_device(const LineStage *s, int *device) {
+    if (!s || !device) return fail(GS_E_INVALID, "NULL argument");
+    *device = s->device;
+    return GS_OK;
+}
+
+// Room for `need` elements in all in every array of a set that shares one capacity, by doubling; the first `used` elements of each
+// stay.  All or nothing: no array of the set has moved when this fails.  `what` names the arrays in the failure's message.
+struct KeptArray {
+    void **p;
+    size_t elem;  // bytes per element
+};
+static int grow_keep(std::initializer_list<KeptArray> arrays, size_t *cap, size_t used, size_t need, hipStream_t stream, const char *what) {
+    if (need <= *cap) return GS_OK;
+    const size_t n = std::max(need, 2 * *cap);
+    std::vector<void *> fresh(arrays.size(), nullptr);
+    hipError_t e = hipSuccess;
+    size_t i = 0;
+    for (const KeptArray &a : arrays) {
+        if (e == hipSuccess) e = gs_dev_alloc(&fresh[i], n * a.elem);
+        if (e == hipSuccess && used) e = hipMemcpyAsync(fresh[i], *a.p, used * a.elem, hipMemcpyDeviceToDevice, stream);
+        i++;
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) {
+        for (void *p : fresh) gs_dev_free(p);
+        return hip_fail(e, what);
+    }
+    i = 0;
+    for (const KeptArray &a : arrays) {
+        gs_dev_free(*a.p);
+        *a.p = fresh[i++];
+    }
+    *cap = n;
+    return GS_OK;
+}
+template <typename T>
+static int grow_keep(T **p, size_t *cap, size_t used, size_t need, hipStream_t stream, const char *what) {
+    return grow_keep({{(void **)p, sizeof(T)}}, cap, used, need, stream, what);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// accmap: RefSeq catalog lines to the accession map (gs_accmap.hip)
+// ---------------------------------------------------------------------------------------------------
+struct gs_accmap : LineStage {
     bool finished = false;
     int32_t dna = 0, rna = 0, mrna = 0, n_cat = 0, n_stat = 0, n_nodes = 0;
     GsAccmapPatterns *d_pat = nullptr;
-    int32_t *d_known = nullptr, *d_regions = nullptr;
-    uint8_t *d_text = nullptr;
-    size_t text_cap = 0;
-    u64 *d_tile = nullptr;  // tile_lt | tile_put, tile_cap entries each
-    uint32_t *d_tail = nullptr;
-    size_t tile_cap = 0;
+    int32_t *d_known = nullptr, *d_regions = nullptr;  // (d_tile: tile_lt | tile_put)
     uint8_t *d_keys = nullptr;  // entry_cap slots of 32 bytes; sorted once finished
     int32_t *d_nodes = nullptr;
     size_t entry_cap = 0;
@@ -7214,12 +7339,10 @@ struct gs_accmap {
     bool host_only = false;             // device == -1: no device is touched; the entries live in h_keys / h_nodes, sorted once finished
     std::vector<uint8_t> h_keys;
     std::vector<int32_t> h_nodes;
-    u64 *d_small = nullptr;             // status, chunk counters, scan sums, finish counts, flag (AM_S_*)
-    bool profile = false;
-    KernelTimer timer;
 };
+// d_small: status, chunk counters, scan sums, finish counts, flag
 enum { AM_S_STATUS = 0, AM_S_CHUNK = 1, AM_S_SCAN = AM_S_CHUNK + GS_AM_C_WORDS, AM_S_COUNTS = AM_S_SCAN + 2, AM_S_FLAG = AM_S_COUNTS + 2, AM_S_WORDS };
-static_assert(GS_AM_WORDS == 2, "the status words fill one 64-bit word of d_small");
+static_assert(GS_AM_WORDS == 2 && AM_S_STATUS == 0 && AM_S_SCAN <= LINES_SMALL_MAX, "the status words fill the first 64-bit word of d_small");
 
 extern "C" int gs_accmap_destroy(gs_accmap *h) try {
     if (!h) return GS_OK;
@@ -7229,11 +7352,8 @@ extern "C" int gs_accmap_destroy(gs_accmap *h) try {
     }
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
-    timer_free(h->timer);
-    for (void *p : {(void *)h->d_pat, (void *)h->d_known, (void *)h->d_regions, (void *)h->d_text, (void *)h->d_tile, (void *)h->d_tail, (void *)h->d_keys,
-                    (void *)h->d_nodes, (void *)h->d_small})
-        gs_dev_free(p);
-    if (h->stream) hipStreamDestroy(h->stream);
+    for (void *p : {(void *)h->d_pat, (void *)h->d_known, (void *)h->d_regions, (void *)h->d_keys, (void *)h->d_nodes}) gs_dev_free(p);
+    lines_free(*h);
     delete h;
     return GS_OK;
 }
@@ -7241,27 +7361,9 @@ GS_API_CATCH
 
 // room for `need` entries in all; what is there stays
 static int am_entry_room(gs_accmap *h, size_t need) {
-    if (need <= h->entry_cap) return GS_OK;
-    if (need > ((size_t)1 << 31)) return fail(GS_E_UNSUPPORTED, "an accession map holds at most 2^31 entries");
-    const size_t cap = std::max(need, 2 * h->entry_cap);
-    uint8_t *keys = nullptr;
-    int32_t *nodes = nullptr;
-    hipError_t e = gs_dev_alloc(&keys, cap * 32);
-    if (e == hipSuccess) e = gs_dev_alloc(&nodes, cap * sizeof(int32_t));
-    if (e == hipSuccess && h->n_entries) e = hipMemcpyAsync(keys, h->d_keys, (size_t)h->n_entries * 32, hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess && h->n_entries) e = hipMemcpyAsync(nodes, h->d_nodes, (size_t)h->n_entries * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {
-        gs_dev_free(keys);
-        gs_dev_free(nodes);
-        return hip_fail(e, "gs_accmap: growing the entry arrays");
-    }
-    gs_dev_free(h->d_keys);
-    gs_dev_free(h->d_nodes);
-    h->d_keys = keys;
-    h->d_nodes = nodes;
-    h->entry_cap = cap;
-    return GS_OK;
+    if (need > h->entry_cap && need > ((size_t)1 << 31)) return fail(GS_E_UNSUPPORTED, "an accession map holds at most 2^31 entries");
+    return grow_keep({{(void **)&h->d_keys, 32}, {(void **)&h->d_nodes, sizeof(int32_t)}}, &h->entry_cap, (size_t)h->n_entries, need, h->stream,
+                     "gs_accmap: growing the entry arrays");
 }
 
 extern "C" int gs_accmap_create(gs_accmap **out, int device, const gs_accmap_cfg *cfg) try {
@@ -7327,40 +7429,19 @@ extern "C" int gs_accmap_create(gs_accmap **out, int device, const gs_accmap_cfg
 GS_API_CATCH
 
 extern "C" int gs_accmap_get_device(gs_accmap *h, int *device) try {
-    if (!h || !device) return fail(GS_E_INVALID, "NULL argument");
-    *device = h->device;
-    return GS_OK;
+    return lines_get_device(h, device);
 }
 GS_API_CATCH
 
 extern "C" int gs_accmap_submit(gs_accmap *h, const uint8_t *text, int64_t n_bytes, int mem, int last, int64_t report[8]) try {
-    if (!h || !report) return fail(GS_E_INVALID, "NULL argument");
-    if (n_bytes < 0 || n_bytes > ((int64_t)1 << 30)) return fail(GS_E_INVALID, "a chunk holds at most 1 GiB");
-    if (n_bytes > 0 && !text) return fail(GS_E_INVALID, "text is NULL");
-    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    int rc = lines_args(h, text, n_bytes, mem, report);
+    if (rc) return rc;
     if (h->finished) return fail(GS_E_STATE, "gs_accmap_submit comes in front of gs_accmap_finish");
     if (h->host_only) return fail(GS_E_UNSUPPORTED, "a host-only accession map (device -1) takes entries through gs_accmap_append alone");
-    for (int i = 0; i < 8; i++) report[i] = 0;
-    report[4] = -1;
-    if (n_bytes == 0) return GS_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    const int64_t n_tiles = (n_bytes + GS_AM_TILE - 1) / GS_AM_TILE;
-    const size_t padded = (size_t)n_tiles * GS_AM_TILE + 64;
-    int rc;
-    if ((rc = grow(&h->d_text, &h->text_cap, padded, h->stream))) return rc;
-    if (h->tile_cap < (size_t)n_tiles + 1) {
-        const size_t cap = (size_t)n_tiles + 1 + (size_t)n_tiles / 4;
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        h->tile_cap = 0;
-        if ((rc = renew(&h->d_tile, 2 * cap))) return rc;
-        if ((rc = renew(&h->d_tail, cap))) return rc;
-        h->tile_cap = cap;
-    }
-    HIP_TRY(hipMemcpyAsync(h->d_text, text, (size_t)n_bytes, mem == GS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(h->d_text + n_bytes, 0, padded - (size_t)n_bytes, h->stream));
-    u64 small[AM_S_SCAN] = {};
-    small[AM_S_STATUS] = (u64)GS_AM_NONE;  // bad line: none; longest line: 0
-    HIP_TRY(hipMemcpy(h->d_small, small, sizeof(small), hipMemcpyHostToDevice));  // (the stream is idle between calls)
+    int64_t n_tiles = 0;
+    u64 small[AM_S_SCAN];
+    rc = lines_open(*h, text, n_bytes, mem, report, GS_AM_TILE, 2, GS_AM_NONE, AM_S_SCAN, &n_tiles);  // (tile_lt | tile_put)
+    if (rc || n_bytes == 0) return rc;
     GsAccmapParams P{};
     P.text = h->d_text;
     P.n_bytes = n_bytes;
@@ -7386,14 +7467,8 @@ extern "C" int gs_accmap_submit(gs_accmap *h, const uint8_t *text, int64_t n_byt
     if ((rc = timer_stop(h->timer, h->profile, h->stream))) return rc;
     HIP_TRY(hipMemcpyAsync(small, h->d_small, sizeof(small), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));  // the one wait of a chunk: its verdict and its counts, between the passes
-    const uint32_t bad = (uint32_t)small[AM_S_STATUS];
     report[0] = (int64_t)small[AM_S_CHUNK + GS_AM_C_LINES];
-    report[5] = (int64_t)(small[AM_S_STATUS] >> 32);
-    if (bad != GS_AM_NONE) {
-        report[3] = 1;
-        report[4] = (int64_t)bad;
-        return timer_collect(h->timer);
-    }
+    if (lines_refused(small[AM_S_STATUS], GS_AM_NONE, report)) return timer_collect(h->timer);
     const int64_t n_put = (int64_t)small[AM_S_CHUNK + GS_AM_C_PUT];
     report[1] = (int64_t)small[AM_S_CHUNK + GS_AM_C_PASSING];
     report[2] = n_put;
@@ -7647,38 +7722,19 @@ GS_API_CATCH
 
 extern "C" int gs_accmap_kernel_time(gs_accmap *h, int profile, int64_t *launches, double *total_ms) try {
     if (!h) return fail(GS_E_INVALID, "accmap is NULL");
-    if (h->host_only) {
-        if (launches) *launches = 0;
-        if (total_ms) *total_ms = 0;
-        return GS_OK;
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    int rc = timer_collect(h->timer);
-    if (rc) return rc;
-    h->profile = profile != 0;
-    if (launches) *launches = h->timer.launches;
-    if (total_ms) *total_ms = h->timer.total_ms;
-    return GS_OK;
+    return lines_kernel_time(*h, h->host_only, profile, launches, total_ms);
 }
 GS_API_CATCH
 
 // ---------------------------------------------------------------------------------------------------
 // asmsum: Genbank assembly summary lines to the picks per tree node (gs_asmsum.hip, gs_asmsumparse.h)
 // ---------------------------------------------------------------------------------------------------
-struct gs_asmsum {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct gs_asmsum : LineStage {
     bool finished = false;
     bool host_only = false;  // device == -1: no device is touched; the entries live in `store`
     int32_t n_nodes = 0, quality_mask = -1, reference_only = 0, key_field = 5;
     int32_t *d_known = nullptr;
     uint8_t *d_filter = nullptr;  // nullptr: every node
-    uint8_t *d_text = nullptr;
-    size_t text_cap = 0;
-    u64 *d_tile = nullptr;
-    uint32_t *d_tail = nullptr;
-    size_t tile_cap = 0;
     uint16_t *d_slots = nullptr;  // per line of a chunk: its slot, its high-byte mark, its verdict
     uint8_t *d_high = nullptr;
     u64 *d_verdict = nullptr;
@@ -7692,18 +7748,16 @@ struct gs_asmsum {
     uint8_t *d_pool = nullptr;
     size_t pool_cap = 0;
     int64_t n_entries = 0, pool_used = 0, n_counted = 0, n_lines = 0;
-    u64 *d_small = nullptr;  // status, chunk counters, scan sums, finish counts (AS_S_*)
     // finished: the picked entries, nodes ascending
     int64_t n_picked = 0, nodes_with_entries = 0, out_pool_bytes = 0;
     GsAsmEntry *d_out = nullptr;
     u64 *d_str_off = nullptr;
     uint8_t *d_out_pool = nullptr;
     gs_host::AsmsumStore store;
-    bool profile = false;
-    KernelTimer timer;
 };
+// d_small: status, chunk counters, scan sums, finish counts
 enum { AS_S_STATUS = 0, AS_S_CHUNK = 1, AS_S_SCAN = AS_S_CHUNK + GS_AS_C_WORDS, AS_S_COUNTS = AS_S_SCAN + 2, AS_S_WORDS = AS_S_COUNTS + 2 };
-static_assert(GS_AS_WORDS == 2, "the status words fill one 64-bit word of d_small");
+static_assert(GS_AS_WORDS == 2 && AS_S_STATUS == 0 && AS_S_COUNTS <= LINES_SMALL_MAX, "the status words fill the first 64-bit word of d_small");
 
 extern "C" int gs_asmsum_destroy(gs_asmsum *h) try {
     if (!h) return GS_OK;
@@ -7713,40 +7767,20 @@ extern "C" int gs_asmsum_destroy(gs_asmsum *h) try {
     }
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
-    timer_free(h->timer);
-    for (void *p : {(void *)h->d_known, (void *)h->d_filter, (void *)h->d_text, (void *)h->d_tile, (void *)h->d_tail, (void *)h->d_slots, (void *)h->d_high,
-                    (void *)h->d_verdict, (void *)h->d_line_blk, (void *)h->d_put_line, (void *)h->d_entries, (void *)h->d_pool, (void *)h->d_small,
-                    (void *)h->d_out, (void *)h->d_str_off, (void *)h->d_out_pool})
+    for (void *p : {(void *)h->d_known, (void *)h->d_filter, (void *)h->d_slots, (void *)h->d_high, (void *)h->d_verdict, (void *)h->d_line_blk,
+                    (void *)h->d_put_line, (void *)h->d_entries, (void *)h->d_pool, (void *)h->d_out, (void *)h->d_str_off, (void *)h->d_out_pool})
         gs_dev_free(p);
-    if (h->stream) hipStreamDestroy(h->stream);
+    lines_free(*h);
     delete h;
     return GS_OK;
 }
 GS_API_CATCH
 
-// room for `need` elements in all; the first `used` stay
-template <typename T>
-static int as_room(gs_asmsum *h, T **p, size_t *cap, size_t used, size_t need) {
-    if (need <= *cap) return GS_OK;
-    const size_t n = std::max(need, 2 * *cap);
-    T *fresh = nullptr;
-    hipError_t e = gs_dev_alloc(&fresh, n * sizeof(T));
-    if (e == hipSuccess && used) e = hipMemcpyAsync(fresh, *p, used * sizeof(T), hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {
-        gs_dev_free(fresh);
-        return hip_fail(e, "gs_asmsum: growing the entry arrays");
-    }
-    gs_dev_free(*p);
-    *p = fresh;
-    *cap = n;
-    return GS_OK;
-}
-
 static int as_entry_room(gs_asmsum *h, int64_t more_entries, int64_t more_bytes) {
     if (h->n_entries + more_entries > ((int64_t)1 << 31)) return fail(GS_E_UNSUPPORTED, "an assembly summary handle holds at most 2^31 entries");
-    int rc = as_room(h, &h->d_entries, &h->entry_cap, (size_t)h->n_entries, (size_t)(h->n_entries + more_entries));
-    if (!rc) rc = as_room(h, &h->d_pool, &h->pool_cap, (size_t)h->pool_used, (size_t)(h->pool_used + more_bytes));
+    const char *what = "gs_asmsum: growing the entry arrays";
+    int rc = grow_keep(&h->d_entries, &h->entry_cap, (size_t)h->n_entries, (size_t)(h->n_entries + more_entries), h->stream, what);
+    if (!rc) rc = grow_keep(&h->d_pool, &h->pool_cap, (size_t)h->pool_used, (size_t)(h->pool_used + more_bytes), h->stream, what);
     return rc;
 }
 
@@ -7795,40 +7829,19 @@ extern "C" int gs_asmsum_create(gs_asmsum **out, int device, const gs_asmsum_cfg
 GS_API_CATCH
 
 extern "C" int gs_asmsum_get_device(gs_asmsum *h, int *device) try {
-    if (!h || !device) return fail(GS_E_INVALID, "NULL argument");
-    *device = h->device;
-    return GS_OK;
+    return lines_get_device(h, device);
 }
 GS_API_CATCH
 
 extern "C" int gs_asmsum_submit(gs_asmsum *h, const uint8_t *text, int64_t n_bytes, int mem, int last, int64_t report[8]) try {
-    if (!h || !report) return fail(GS_E_INVALID, "NULL argument");
-    if (n_bytes < 0 || n_bytes > ((int64_t)1 << 30)) return fail(GS_E_INVALID, "a chunk holds at most 1 GiB");
-    if (n_bytes > 0 && !text) return fail(GS_E_INVALID, "text is NULL");
-    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    int rc = lines_args(h, text, n_bytes, mem, report);
+    if (rc) return rc;
     if (h->finished) return fail(GS_E_STATE, "gs_asmsum_submit comes in front of gs_asmsum_finish");
     if (h->host_only) return fail(GS_E_UNSUPPORTED, "a host-only assembly summary handle (device -1) takes entries through gs_asmsum_append alone");
-    for (int i = 0; i < 8; i++) report[i] = 0;
-    report[4] = -1;
-    if (n_bytes == 0) return GS_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    const int64_t n_tiles = (n_bytes + GS_AS_TILE - 1) / GS_AS_TILE;
-    const size_t padded = (size_t)n_tiles * GS_AS_TILE + 64;
-    int rc;
-    if ((rc = grow(&h->d_text, &h->text_cap, padded, h->stream))) return rc;
-    if (h->tile_cap < (size_t)n_tiles + 1) {
-        const size_t cap = (size_t)n_tiles + 1 + (size_t)n_tiles / 4;
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        h->tile_cap = 0;
-        if ((rc = renew(&h->d_tile, cap))) return rc;
-        if ((rc = renew(&h->d_tail, cap))) return rc;
-        h->tile_cap = cap;
-    }
-    HIP_TRY(hipMemcpyAsync(h->d_text, text, (size_t)n_bytes, mem == GS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(h->d_text + n_bytes, 0, padded - (size_t)n_bytes, h->stream));
-    u64 small[AS_S_COUNTS] = {};
-    small[AS_S_STATUS] = (u64)GS_AS_NONE;  // bad line: none; longest line: 0
-    HIP_TRY(hipMemcpy(h->d_small, small, sizeof(small), hipMemcpyHostToDevice));  // (the stream is idle between calls)
+    int64_t n_tiles = 0;
+    u64 small[AS_S_COUNTS];
+    rc = lines_open(*h, text, n_bytes, mem, report, GS_AS_TILE, 1, GS_AS_NONE, AS_S_COUNTS, &n_tiles);
+    if (rc || n_bytes == 0) return rc;
     GsAsmsumParams P{};
     P.text = h->d_text;
     P.n_bytes = n_bytes;
@@ -7875,13 +7888,7 @@ extern "C" int gs_asmsum_submit(gs_asmsum *h, const uint8_t *text, int64_t n_byt
     if ((rc = timer_stop(h->timer, h->profile, h->stream))) return rc;
     HIP_TRY(hipMemcpyAsync(small, h->d_small, sizeof(small), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));  // the second: its verdict and its counts, in front of the write pass
-    const uint32_t bad = (uint32_t)small[AS_S_STATUS];
-    report[5] = (int64_t)(small[AS_S_STATUS] >> 32);
-    if (bad != GS_AS_NONE) {
-        report[3] = 1;
-        report[4] = (int64_t)bad;
-        return timer_collect(h->timer);
-    }
+    if (lines_refused(small[AS_S_STATUS], GS_AS_NONE, report)) return timer_collect(h->timer);
     const int64_t n_put = (int64_t)small[AS_S_CHUNK + GS_AS_C_KEPT], n_pool = (int64_t)small[AS_S_CHUNK + GS_AS_C_POOL];
     report[0] = (int64_t)small[AS_S_CHUNK + GS_AS_C_COUNTED];
     report[1] = n_put;
@@ -8090,19 +8097,7 @@ extern "C" int64_t gs_asmsum_file_name(const uint8_t *ftp, int64_t n, uint8_t *o
 
 extern "C" int gs_asmsum_kernel_time(gs_asmsum *h, int profile, int64_t *launches, double *total_ms) try {
     if (!h) return fail(GS_E_INVALID, "asmsum is NULL");
-    if (h->host_only) {
-        if (launches) *launches = 0;
-        if (total_ms) *total_ms = 0;
-        return GS_OK;
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    int rc = timer_collect(h->timer);
-    if (rc) return rc;
-    h->profile = profile != 0;
-    if (launches) *launches = h->timer.launches;
-    if (total_ms) *total_ms = h->timer.total_ms;
-    return GS_OK;
+    return lines_kernel_time(*h, h->host_only, profile, launches, total_ms);
 }
 GS_API_CATCH
 
@@ -8110,22 +8105,14 @@ GS_API_CATCH
 // taxtree: NCBI nodes.dmp / names.dmp to the arrays of the tree; taxnodes selection; small tree (gs_taxtree.hip, gs_taxparse.h)
 // ---------------------------------------------------------------------------------------------------
 
-struct gs_taxtree {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct gs_taxtree : LineStage {
     bool host_only = false;  // device == -1
     bool on_host = false;    // the finished tree lives in `tree`: a host-only handle, or a device handle that met duplicate ids
     int state = 0;           // 0: nodes come in; 1: gs_taxtree_finish_nodes has succeeded
     GsTaxRanks *d_ranks = nullptr;
-    uint8_t *d_text = nullptr;
-    size_t text_cap = 0;
-    u64 *d_tile = nullptr;
-    uint32_t *d_tail = nullptr;
-    size_t tile_cap = 0;
     uint4 *d_slots = nullptr;
     size_t slot_cap = 0;
     int64_t n_slots = 0;
-    u64 *d_small = nullptr;  // status | scan sum | counts[6]
     gs_host::TaxNodesExact nodes;  // the line-by-line reader of nodes; on a host-only handle its slots are the input
     gs_host::TaxNamesExact names;
     gs_host::TaxHostTree tree;     // on_host: all of it; else taxids, names and has_name alone
@@ -8141,10 +8128,10 @@ struct gs_taxtree {
     uint8_t *d_pool = nullptr;
     size_t pool_cap = 0;
     double finish_ms[3] = {0, 0, 0};  // the last finish under profile: distinct ids and parents | child order | tree steps
-    bool profile = false;
-    KernelTimer timer;
 };
+// d_small: status | scan sum | counts[6]
 enum { TT_S_STATUS = 0, TT_S_SCAN = 1, TT_S_COUNTS = 2, TT_S_WORDS = TT_S_COUNTS + 6 };
+static_assert(TT_S_STATUS == 0 && TT_S_COUNTS <= LINES_SMALL_MAX, "the status is the first word of d_small");
 
 static void tt_free_tree(gs_taxtree *h) {
     for (void *p : {(void *)h->d_win, (void *)h->d_name_off, (void *)h->d_name_len, (void *)h->d_pool}) gs_dev_free(p);
@@ -8164,10 +8151,10 @@ extern "C" int gs_taxtree_destroy(gs_taxtree *h) try {
     if (!h->host_only) {
         hipSetDevice(h->device);
         if (h->stream) hipStreamSynchronize(h->stream);
-        timer_free(h->timer);
         tt_free_tree(h);
-        for (void *p : {(void *)h->d_ranks, (void *)h->d_text, (void *)h->d_tile, (void *)h->d_tail, (void *)h->d_slots, (void *)h->d_small}) gs_dev_free(p);
-        if (h->stream) hipStreamDestroy(h->stream);
+        gs_dev_free(h->d_ranks);
+        gs_dev_free(h->d_slots);
+        lines_free(*h);
     }
     delete h;
     return GS_OK;
@@ -8209,59 +8196,25 @@ GS_API_CATCH
 static_assert(GS_TT_N_RANKS == gs_host::TAX_N_RANKS, "one list of ranks");
 
 extern "C" int gs_taxtree_get_device(gs_taxtree *h, int *device) try {
-    if (!h || !device) return fail(GS_E_INVALID, "NULL argument");
-    *device = h->device;
-    return GS_OK;
+    return lines_get_device(h, device);
 }
 GS_API_CATCH
 
 // room for `need` slots in all; what is there stays
 static int tt_slot_room(gs_taxtree *h, size_t need) {
-    if (need <= h->slot_cap) return GS_OK;
-    if (need > ((size_t)1 << 30)) return fail(GS_E_UNSUPPORTED, "a tree takes at most 2^30 lines");
-    const size_t cap = std::max(need, 2 * h->slot_cap);
-    uint4 *slots = nullptr;
-    hipError_t e = gs_dev_alloc(&slots, cap * sizeof(uint4));
-    if (e == hipSuccess && h->n_slots) e = hipMemcpyAsync(slots, h->d_slots, (size_t)h->n_slots * sizeof(uint4), hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {
-        gs_dev_free(slots);
-        return hip_fail(e, "gs_taxtree: growing the slots");
-    }
-    gs_dev_free(h->d_slots);
-    h->d_slots = slots;
-    h->slot_cap = cap;
-    return GS_OK;
+    if (need > h->slot_cap && need > ((size_t)1 << 30)) return fail(GS_E_UNSUPPORTED, "a tree takes at most 2^30 lines");
+    return grow_keep(&h->d_slots, &h->slot_cap, (size_t)h->n_slots, need, h->stream, "gs_taxtree: growing the slots");
 }
 
 extern "C" int gs_taxtree_submit_nodes(gs_taxtree *h, const uint8_t *text, int64_t n_bytes, int mem, int last, int64_t report[8]) try {
-    if (!h || !report) return fail(GS_E_INVALID, "NULL argument");
-    if (n_bytes < 0 || n_bytes > ((int64_t)1 << 30)) return fail(GS_E_INVALID, "a chunk holds at most 1 GiB");
-    if (n_bytes > 0 && !text) return fail(GS_E_INVALID, "text is NULL");
-    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    int rc = lines_args(h, text, n_bytes, mem, report);
+    if (rc) return rc;
     if (h->state != 0) return fail(GS_E_STATE, "gs_taxtree_submit_nodes comes in front of gs_taxtree_finish_nodes");
     if (h->host_only) return fail(GS_E_UNSUPPORTED, "a host-only tree (device -1) takes its lines through gs_taxtree_append_nodes alone");
-    for (int i = 0; i < 8; i++) report[i] = 0;
-    report[4] = -1;
-    if (n_bytes == 0) return GS_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    const int64_t n_tiles = (n_bytes + GS_TT_TILE - 1) / GS_TT_TILE;
-    const size_t padded = (size_t)n_tiles * GS_TT_TILE + 64;
-    int rc;
-    if ((rc = grow(&h->d_text, &h->text_cap, padded, h->stream))) return rc;
-    if (h->tile_cap < (size_t)n_tiles + 1) {
-        const size_t cap = (size_t)n_tiles + 1 + (size_t)n_tiles / 4;
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        h->tile_cap = 0;
-        if ((rc = renew(&h->d_tile, cap))) return rc;
-        if ((rc = renew(&h->d_tail, cap))) return rc;
-        h->tile_cap = cap;
-    }
-    HIP_TRY(hipMemcpyAsync(h->d_text, text, (size_t)n_bytes, mem == GS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(h->d_text + n_bytes, 0, padded - (size_t)n_bytes, h->stream));
-    u64 small[TT_S_COUNTS] = {};
-    small[TT_S_STATUS] = (u64)GS_TT_NONE;  // bad line: none; longest line: 0
-    HIP_TRY(hipMemcpy(h->d_small, small, sizeof(small), hipMemcpyHostToDevice));  // (the stream is idle between calls)
+    int64_t n_tiles = 0;
+    u64 small[TT_S_COUNTS];
+    rc = lines_open(*h, text, n_bytes, mem, report, GS_TT_TILE, 1, GS_TT_NONE, TT_S_COUNTS, &n_tiles);
+    if (rc || n_bytes == 0) return rc;
     GsTaxScanParams P{};
     P.text = h->d_text;
     P.n_bytes = n_bytes;
@@ -8290,14 +8243,9 @@ extern "C" int gs_taxtree_submit_nodes(gs_taxtree *h, const uint8_t *text, int64
     if ((rc = timer_stop(h->timer, h->profile, h->stream))) return rc;
     HIP_TRY(hipMemcpyAsync(small, h->d_small, sizeof(small), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    const uint32_t bad = (uint32_t)small[TT_S_STATUS];
     report[0] = n_lines;
-    report[5] = (int64_t)(small[TT_S_STATUS] >> 32);
-    if (bad != GS_TT_NONE) {  // what the scan wrote lies behind n_slots: the handle is as it was
-        report[3] = 1;
-        report[4] = (int64_t)bad;
-        return timer_collect(h->timer);
-    }
+    // (of a refused chunk, what the scan wrote lies behind n_slots: the handle is as it was)
+    if (lines_refused(small[TT_S_STATUS], GS_TT_NONE, report)) return timer_collect(h->timer);
     report[2] = n_lines;
     h->n_slots += n_lines;
     h->nodes.line_no += n_lines;
@@ -8509,20 +8457,17 @@ extern "C" int gs_taxtree_finish_nodes(gs_taxtree *h, int64_t info[8]) try {
 GS_API_CATCH
 
 extern "C" int gs_taxtree_submit_names(gs_taxtree *h, const uint8_t *text, int64_t n_bytes, int mem, int last, int64_t report[8]) try {
-    if (!h || !report) return fail(GS_E_INVALID, "NULL argument");
-    if (n_bytes < 0 || n_bytes > ((int64_t)1 << 30)) return fail(GS_E_INVALID, "a chunk holds at most 1 GiB");
-    if (n_bytes > 0 && !text) return fail(GS_E_INVALID, "text is NULL");
-    if (mem != GS_MEM_HOST && mem != GS_MEM_DEVICE) return fail(GS_E_INVALID, "mem must be GS_MEM_HOST or GS_MEM_DEVICE");
+    int rc = lines_args(h, text, n_bytes, mem, report);
+    if (rc) return rc;
     if (h->state != 1) return fail(GS_E_STATE, "gs_taxtree_submit_names comes behind gs_taxtree_finish_nodes");
     if (h->on_host) return fail(GS_E_UNSUPPORTED, "the tree lives on the host (device -1, or duplicate ids): names go through gs_taxtree_append_names");
-    for (int i = 0; i < 8; i++) report[i] = 0;
-    report[4] = -1;
-    if (n_bytes == 0) return GS_OK;
-    HIP_TRY(hipSetDevice(h->device));
+    int64_t n_tiles = 0;
+    u64 small[TT_S_COUNTS];
+    rc = lines_open(*h, text, n_bytes, mem, report, GS_TT_TILE, 1, GS_TT_NONE, TT_S_COUNTS, &n_tiles);
+    if (rc || n_bytes == 0) return rc;
     const size_t N = (size_t)h->tree.n;
     u64 *pool_used_d = h->d_small + TT_S_COUNTS + 5;
-    int rc;
-    if (!h->d_win) {
+    if (!h->d_win) {  // the first chunk of names
         hipError_t e = gs_dev_alloc(&h->d_win, N * sizeof(u64));
         if (e == hipSuccess) e = gs_dev_alloc(&h->d_name_off, N * sizeof(u64));
         if (e == hipSuccess) e = gs_dev_alloc(&h->d_name_len, N * sizeof(uint32_t));
@@ -8535,22 +8480,6 @@ extern "C" int gs_taxtree_submit_names(gs_taxtree *h, const uint8_t *text, int64
             return hip_fail(e, "gs_taxtree_submit_names");
         }
     }
-    const int64_t n_tiles = (n_bytes + GS_TT_TILE - 1) / GS_TT_TILE;
-    const size_t padded = (size_t)n_tiles * GS_TT_TILE + 64;
-    if ((rc = grow(&h->d_text, &h->text_cap, padded, h->stream))) return rc;
-    if (h->tile_cap < (size_t)n_tiles + 1) {
-        const size_t cap = (size_t)n_tiles + 1 + (size_t)n_tiles / 4;
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        h->tile_cap = 0;
-        if ((rc = renew(&h->d_tile, cap))) return rc;
-        if ((rc = renew(&h->d_tail, cap))) return rc;
-        h->tile_cap = cap;
-    }
-    HIP_TRY(hipMemcpyAsync(h->d_text, text, (size_t)n_bytes, mem == GS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(h->d_text + n_bytes, 0, padded - (size_t)n_bytes, h->stream));
-    u64 small[TT_S_COUNTS] = {};
-    small[TT_S_STATUS] = (u64)GS_TT_NONE;
-    HIP_TRY(hipMemcpy(h->d_small, small, sizeof(small), hipMemcpyHostToDevice));  // (the stream is idle between calls)
     GsTaxScanParams P{};
     P.text = h->d_text;
     P.n_bytes = n_bytes;
@@ -8578,30 +8507,11 @@ extern "C" int gs_taxtree_submit_names(gs_taxtree *h, const uint8_t *text, int64
     HIP_TRY(hipMemcpyAsync(&used, pool_used_d, sizeof(used), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));  // the one wait of a chunk: its verdict
     const int64_t n_lines = (int64_t)(uint32_t)small[TT_S_SCAN] + (tail != '\n');
-    const uint32_t bad = (uint32_t)small[TT_S_STATUS];
     report[0] = n_lines;
-    report[5] = (int64_t)(small[TT_S_STATUS] >> 32);
-    if (bad != GS_TT_NONE) {  // nothing was written: the handle is as it was
-        report[3] = 1;
-        report[4] = (int64_t)bad;
-        return timer_collect(h->timer);
-    }
+    if (lines_refused(small[TT_S_STATUS], GS_TT_NONE, report)) return timer_collect(h->timer);  // (nothing was written: the handle is as it was)
     // every name of the chunk has room, whoever wins; what the pool holds stays
     const size_t need = (size_t)used + (size_t)n_bytes;
-    if (need > h->pool_cap) {
-        const size_t cap = std::max(need, 2 * h->pool_cap);
-        uint8_t *pool = nullptr;
-        hipError_t e = gs_dev_alloc(&pool, cap);
-        if (e == hipSuccess && used) e = hipMemcpyAsync(pool, h->d_pool, (size_t)used, hipMemcpyDeviceToDevice, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) {
-            gs_dev_free(pool);
-            return hip_fail(e, "gs_taxtree_submit_names: growing the pool");
-        }
-        gs_dev_free(h->d_pool);
-        h->d_pool = pool;
-        h->pool_cap = cap;
-    }
+    if ((rc = grow_keep(&h->d_pool, &h->pool_cap, (size_t)used, need, h->stream, "gs_taxtree_submit_names: growing the pool"))) return rc;
     P.pool = h->d_pool;
     if ((rc = timer_start(h->timer, h->profile, h->stream))) return rc;
     HIP_TRY(gs_launch_taxtree_names(&P, 1, h->stream));
@@ -8927,19 +8837,7 @@ GS_API_CATCH
 
 extern "C" int gs_taxtree_kernel_time(gs_taxtree *h, int profile, int64_t *launches, double *total_ms) try {
     if (!h) return fail(GS_E_INVALID, "tree is NULL");
-    if (h->host_only) {
-        if (launches) *launches = 0;
-        if (total_ms) *total_ms = 0;
-        return GS_OK;
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    int rc = timer_collect(h->timer);
-    if (rc) return rc;
-    h->profile = profile != 0;
-    if (launches) *launches = h->timer.launches;
-    if (total_ms) *total_ms = h->timer.total_ms;
-    return GS_OK;
+    return lines_kernel_time(*h, h->host_only, profile, launches, total_ms);
 }
 GS_API_CATCH
 

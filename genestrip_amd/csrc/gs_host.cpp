@@ -3100,11 +3100,13 @@ extern "C" int gs_host_db2fastq(gs_db *db, const char *const *taxids, const char
 namespace {
 // the gs_reads handle of a goal's context goes on every way out of the call, an exception included; declared behind the context,
 // so the handle is gone before the context's writers are
-struct ReadsGuard {
-    gs_reads *&rd;
-    ~ReadsGuard() {
-        if (rd) gs_reads_destroy(rd);
-        rd = nullptr;
+// a handle of the C ABI that a file-level call made: destroyed on every way out, unless the call has handed it on (h = nullptr)
+template <class H, int (*destroy)(H *)>
+struct HandleGuard {
+    H *&h;
+    ~HandleGuard() {
+        if (h) destroy(h);
+        h = nullptr;
     }
 };
 }  // namespace
@@ -3116,7 +3118,7 @@ extern "C" int gs_host_extract_files(int device, const char *key, int k, const c
     if (!key || !paths || n_paths < 0 || !out_path) return hfail(GS_E_INVALID, "NULL argument");
     if (k < 1 || k > 31) return hfail(GS_E_INVALID, "k must be in [1,31]");
     FilterCtx c;
-    ReadsGuard guard{c.rd};
+    HandleGuard<gs_reads, gs_reads_destroy> guard{c.rd};
     c.key = key;
     if (c.key.empty()) return hfail(GS_E_INVALID, "the key is empty");
     for (unsigned char ch : c.key)  // (Java compares byte != char: a byte >= 0x80 never matches)
@@ -3324,7 +3326,7 @@ extern "C" int gs_host_fasta2fastq(int device, const char *const *paths, int n_p
     Tracker &tk = progress.t;
     {
         F2fCtx c;
-        ReadsGuard guard{c.reads};
+        HandleGuard<gs_reads, gs_reads_destroy> guard{c.reads};
         c.device = device;
         if (!c.out.open(out_path)) return hfail(GS_E_IO, std::string("cannot open ") + out_path);
         if (fast && gs_reads_create(&c.reads, device) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
@@ -3373,66 +3375,109 @@ extern "C" int gs_host_fasta2fastq(int device, const char *const *paths, int n_p
 }
 
 // ---- krakencount (C/goals/kraken/KrakenResCountGoal.java:133-157)
+// ---- What the line-catalog goals share (krakencount, accmap, asmsum, taxtree): files of lines, chunks of whole lines to
+// the device, what it refuses through the goal's exact parser at its place in the input order.  One loop of each kind over a per-goal
+// struct G, whose members are the contract of the next such goal:
+//   G::Reader                     how lines_cpu reads a file: WholeLines or RawPieces
+//   begin_file(f)                 a file is a stream of its own: the parser's state, and where the file's line count starts
+//   on_device(f)                  false: the file goes line by line although the call runs on a device
+//   submit(path, cut, &refused)   a chunk to the device; one it took is booked here
+//   feed(path, p, n, last)        whole lines through the host parser, and what it made of them into the handle
+//   file_lines()                  the lines of the current file that are in the state: the count of its progress records
+//   ended()                       the stream ends in front of the end of its file
+//   end_file(f, path)             behind a file that went through without an error or a stop
 namespace {
 
-struct KcGuard {
-    gs_krakencount *&kc;
-    ~KcGuard() {
-        if (kc) gs_krakencount_destroy(kc);
-        kc = nullptr;
-    }
-};
-
-struct KcCtx {
-    gs_krakencount *kc = nullptr;
-    KrakenExact exact;  // rows of what the line-by-line loop took; its lines / tokens
-    int64_t dev_tot[4] = {0, 0, 0, 0};
+struct LineGoal {  // the base of every G: its counters, and the answers most goals give
     int64_t device_chunks = 0, host_chunks = 0;
-    int prog_file = 0;  // progress records: the file being read, and the lines counted when it began
-    int64_t prog_lines0 = 0;
-    int64_t file_lines() const { return exact.lines + dev_tot[0] - prog_lines0; }
-    // after a chunk; true: stop -- the chunk has been waited for (gs_krakencount_chunk) or was counted here, the record is out
-    bool report(int64_t pos, bool gz) {
-        if (!trk().chunk(prog_file, pos, gz, file_lines())) return false;
-        trk().stopped(prog_file, file_lines());
-        return true;
-    }
+    int prog_file = 0;  // progress records: the file being read
+    bool on_device(int) const { return true; }
+    bool ended() const { return false; }
+    int end_file(int, const std::string &) { return GS_OK; }
 };
 
-int kc_format_error(const KcCtx &c, const std::string &path) {
-    return hfail(GS_E_INVALID, path + ": line " + std::to_string((long long)c.exact.line_no) + ": " + c.exact.error);
+// after a chunk; true: stop -- the chunk is in the state, the record of the stop is out
+template <class G>
+bool report(G &g, int64_t pos, bool gz) {
+    if (!trk().chunk(g.prog_file, pos, gz, g.file_lines())) return false;
+    trk().stopped(g.prog_file, g.file_lines());
+    return true;
 }
 
-// the rest of a stream, line by line: the file from `offset` on, or a memory range that ends the stream
-int kc_cpu(KcCtx &c, const std::string &path, int64_t offset, const uint8_t *mem, size_t mem_n) {
-    c.host_chunks++;
-    if (mem) {
-        if (!c.exact.feed(mem, mem_n, true)) return kc_format_error(c, path);
-        return c.report(0, false) ? cancelled_rc() : (int)GS_OK;
-    }
+// The two ways lines_cpu reads a file from `offset` on.  next() makes [data(), data() + size()) the next piece of the stream and sets
+// *eof with its last one; pos(): how far the file has been read, in its stored bytes.
+struct WholeLines {  // whole lines, some MiB at a time, NUL bytes dropped (LineReader)
     LineReader lr;
-    if (!lr.open(path, offset)) return hfail(GS_E_IO, "cannot open " + path);
     std::vector<uint8_t> text;
-    for (bool eof = false; !eof && !c.exact.ended;) {  // whole lines, some MiB at a time
+    int open(const std::string &path, int64_t offset) { return lr.open(path, offset) ? (int)GS_OK : hfail(GS_E_IO, "cannot open " + path); }
+    int next(const std::string &, bool *eof) {
         text.clear();
         while (text.size() < ((size_t)4 << 20)) {
             if (lr.next_line(text) == 0) {
-                eof = true;
+                *eof = true;
                 break;
             }
         }
         // (next_line drops NUL bytes as the parser would; a final line without its newline is the stream's last)
-        if (!text.empty() && text.back() != '\n') eof = true;
-        if (!c.exact.feed(text.data(), text.size(), eof)) return kc_format_error(c, path);
-        if (c.report(lr.raw_pos(), false)) return cancelled_rc();
+        if (!text.empty() && text.back() != '\n') *eof = true;
+        return GS_OK;
     }
-    return GS_OK;
+    const uint8_t *data() const { return text.data(); }
+    size_t size() const { return text.size(); }
+    int64_t pos() const { return lr.raw_pos(); }
+};
+struct RawPieces {  // the text as it is, GS_HOST_BLOCK_BYTES at a time: NUL bytes are data, and the parser sees every CR
+    gzFile gz = nullptr;
+    std::vector<uint8_t> text;
+    size_t n = 0;
+    ~RawPieces() {
+        if (gz) gzclose(gz);
+    }
+    int open(const std::string &path, int64_t offset) {
+        gz = gzopen(path.c_str(), "rb");  // (zlib reads plain files transparently, gzip by content, member after member)
+        if (!gz) return hfail(GS_E_IO, "cannot open " + path);
+        gzbuffer(gz, 1 << 20);
+        if (offset != 0 && gzseek(gz, (z_off_t)offset, SEEK_SET) != (z_off_t)offset) return hfail(GS_E_IO, "cannot seek in " + path);
+        size_t piece = (size_t)4 << 20;
+        if (const char *e = getenv("GS_HOST_BLOCK_BYTES")) piece = (size_t)std::max<long long>(1, atoll(e));
+        text.resize(piece);
+        return GS_OK;
+    }
+    int next(const std::string &path, bool *eof) {
+        const int got = gzread(gz, text.data(), (unsigned)text.size());
+        if (got < 0) return hfail(GS_E_IO, "cannot read " + path);
+        n = (size_t)got;
+        *eof = got == 0;
+        return GS_OK;
+    }
+    const uint8_t *data() const { return text.data(); }
+    size_t size() const { return n; }
+    int64_t pos() const { return (int64_t)gzoffset(gz); }
+};
+
+// the rest of a stream through the host parser: the file from `offset` on (in its text), or a memory range that ends the stream
+template <class G>
+int lines_cpu(G &g, const std::string &path, int64_t offset, const uint8_t *mem, size_t mem_n) {
+    g.host_chunks++;
+    if (mem) {
+        const int err = g.feed(path, mem, mem_n, true);
+        return err ? err : report(g, 0, false) ? cancelled_rc() : (int)GS_OK;
+    }
+    typename G::Reader rd;
+    int err = rd.open(path, offset);
+    for (bool eof = false; !err && !eof && !g.ended();) {
+        if ((err = rd.next(path, &eof))) break;
+        err = g.feed(path, rd.data(), rd.size(), eof);
+        if (!err && report(g, rd.pos(), false)) err = cancelled_rc();
+    }
+    return err;
 }
 
-// One file through the device: chunks that end behind a newline are counted there; one that the device refuses goes through
-// the line-by-line loop, and the stream goes on behind it on the device.  A line that does not fit a block sends the rest of the
-// file through that loop; so does the unterminated tail.
-int kc_device_file(KcCtx &c, const std::string &path, bool gzip) {
+// One file through the device: chunks that end behind a newline go there; one that the device refuses goes through the host parser,
+// so the input order stays, and the stream goes on behind it on the device.  A line that does not fit a block sends the rest of the
+// file through that parser; so does the unterminated tail.
+template <class G>
+int lines_device_file(G &g, const std::string &path, bool gzip) {
     size_t block;
     int readers = 0;
     reader_shape(gzip, &block, &readers);
@@ -3454,42 +3499,96 @@ int kc_device_file(KcCtx &c, const std::string &path, bool gzip) {
         if (what == ChunkCutter::FALLBACK) {
             fallback_off = cut.file_off;
         } else if (what == ChunkCutter::CHUNK && cut.bytes > 0) {
-            int64_t ticket = 0, rep[8];
-            if (gs_krakencount_submit(c.kc, cut.start, cut.bytes, GS_MEM_HOST, &ticket) != GS_OK || gs_krakencount_chunk(c.kc, ticket, rep) != GS_OK) {
-                err = hfail(GS_E_HIP, gs_last_error());
-                break;
-            }
-            if (rep[0] != 0) {  // refused: this chunk line by line
-                c.host_chunks++;
-                if (!c.exact.feed(cut.start, (size_t)cut.bytes, false)) err = kc_format_error(c, path);
+            bool refused = false;
+            if ((err = g.submit(path, cut, &refused))) break;
+            if (refused) {  // this chunk through the host parser
+                g.host_chunks++;
+                err = g.feed(path, cut.start, (size_t)cut.bytes, false);
             } else {
-                c.device_chunks++;
-                g_krakencount_chunks++;
-                for (int j = 0; j < 4; j++) c.dev_tot[j] += rep[4 + j];
-                if (rep[2] >= 0) {
-                    c.exact.ended = true;  // an empty line: the stream ends there
-                } else {
-                    c.exact.line_no += cut.lines;
-                    // (a later line without a class field has the class of the line before it, wherever that line was counted)
-                    const uint8_t *e = cut.start + cut.bytes - 1, *b = e;
-                    while (b > cut.start && b[-1] != '\n') b--;
-                    c.exact.set_class_of(b, (size_t)(e - b));
-                }
+                g.device_chunks++;
             }
             cut.commit();
-            if (!err && c.report(cut.file_off, gzip)) err = cancelled_rc();  // (the record is out: the block may go back)
+            if (!err && report(g, cut.file_off, gzip)) err = cancelled_rc();  // (the record is out: the block may go back)
         } else if (what == ChunkCutter::CHUNK) {
             cut.commit();
         }
         tr.release(i);
-        if (eof || fallback_off >= 0 || c.exact.ended) break;
+        if (eof || fallback_off >= 0 || g.ended()) break;
     }
     tr.close();
-    if (err || c.exact.ended) return err;
-    if (fallback_off >= 0) return kc_cpu(c, path, fallback_off, nullptr, 0);
-    if (!cut.carry.empty()) return kc_cpu(c, path, 0, cut.carry.data(), cut.carry.size());
+    if (err || g.ended()) return err;
+    if (fallback_off >= 0) return lines_cpu(g, path, fallback_off, nullptr, 0);
+    if (!cut.carry.empty()) return lines_cpu(g, path, 0, cut.carry.data(), cut.carry.size());
     return GS_OK;
 }
+
+// the files of a call, one after the other, under its progress records: GS_OK, GS_E_CANCELLED (the record of the stop is out) or
+// what went wrong.  fast: chunks go to a device
+template <class G>
+int lines_files(G &g, const char *const *paths, int n_paths, bool fast) {
+    int err = GS_OK;
+    TrackerScope progress(paths, n_paths);
+    Tracker &tk = progress.t;
+    for (int f = 0; f < n_paths && !err; f++) {
+        const std::string path(paths[f]);
+        g.prog_file = f;
+        g.begin_file(f);
+        if (tk.file_start(f)) {
+            tk.stopped(f, 0);
+            err = cancelled_rc();
+            break;
+        }
+        const int kind = fast && g.on_device(f) ? text_path_kind(path) : 0;
+        err = kind ? lines_device_file(g, path, kind == 2 || kind == 4) : lines_cpu(g, path, 0, nullptr, 0);
+        if (!err && tk.file_end(f, g.file_lines())) err = cancelled_rc();
+        if (!err) err = g.end_file(f, path);
+    }
+    if (!err && tk.close()) err = cancelled_rc();
+    return err;
+}
+
+}  // namespace
+
+// ---- krakencount (C/goals/kraken/KrakenResCountGoal.java:133-157)
+namespace {
+
+struct KcGoal : LineGoal {
+    using Reader = WholeLines;
+    gs_krakencount *kc = nullptr;
+    KrakenExact exact;  // rows of what the line-by-line loop took; its lines / tokens
+    int64_t dev_tot[4] = {0, 0, 0, 0};
+    int64_t prog_lines0 = 0;  // the lines counted when the file began
+    int64_t file_lines() const { return exact.lines + dev_tot[0] - prog_lines0; }
+    bool ended() const { return exact.ended; }  // an empty line: the stream ends there
+    void begin_file(int) {  // every file is a stream of its own, all of them count into one table
+        exact.ended = false;
+        exact.line_no = 0;
+        exact.forget_class();
+        prog_lines0 = exact.lines + dev_tot[0];
+    }
+    int feed(const std::string &path, const uint8_t *p, size_t n, bool last) {
+        if (exact.feed(p, n, last)) return GS_OK;
+        return hfail(GS_E_INVALID, path + ": line " + std::to_string((long long)exact.line_no) + ": " + exact.error);
+    }
+    int submit(const std::string &, const ChunkCutter &cut, bool *refused) {
+        int64_t ticket = 0, rep[8];
+        if (gs_krakencount_submit(kc, cut.start, cut.bytes, GS_MEM_HOST, &ticket) != GS_OK || gs_krakencount_chunk(kc, ticket, rep) != GS_OK)
+            return hfail(GS_E_HIP, gs_last_error());
+        if ((*refused = rep[0] != 0)) return GS_OK;
+        g_krakencount_chunks++;
+        for (int j = 0; j < 4; j++) dev_tot[j] += rep[4 + j];
+        if (rep[2] >= 0) {
+            exact.ended = true;
+        } else {
+            exact.line_no += cut.lines;
+            // (a later line without a class field has the class of the line before it, wherever that line was counted)
+            const uint8_t *e = cut.start + cut.bytes - 1, *b = e;
+            while (b > cut.start && b[-1] != '\n') b--;
+            exact.set_class_of(b, (size_t)(e - b));
+        }
+        return GS_OK;
+    }
+};
 
 }  // namespace
 
@@ -3503,37 +3602,15 @@ extern "C" int gs_host_kraken_count_files(int device, const char *const *paths, 
     int64_t max_taxids = (int64_t)1 << 18;
     if (const char *e = getenv("GS_KRAKEN_MAX_TAXIDS")) max_taxids = std::max<long long>(1, atoll(e));
     const double t_start = now_s();
-    KcCtx c;
-    KcGuard guard{c.kc};
+    KcGoal c;
+    HandleGuard<gs_krakencount, gs_krakencount_destroy> guard{c.kc};
     c.exact.filtered = n_only > 0;
     if (fast && gs_krakencount_create(&c.kc, device, max_taxids) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
-    std::map<std::string, KrakenRow> rows;
-    TrackerScope progress(paths, n_paths);
-    Tracker &tk = progress.t;
-    bool stopped = false;  // a stop on request: the rows of the lines counted so far are fetched all the same, no CSV is written
-    for (int f = 0; f < n_paths && !stopped; f++) {
-        const std::string path(paths[f]);
-        c.exact.ended = false;  // every file is a stream of its own, all of them count into one table
-        c.exact.line_no = 0;
-        c.exact.forget_class();
-        c.prog_file = f;
-        c.prog_lines0 = c.exact.lines + c.dev_tot[0];
-        if (tk.file_start(f)) {
-            tk.stopped(f, 0);
-            stopped = true;
-            break;
-        }
-        const int kind = fast ? text_path_kind(path) : 0;
-        const int err = kind ? kc_device_file(c, path, kind == 2 || kind == 4) : kc_cpu(c, path, 0, nullptr, 0);
-        if (err == GS_E_CANCELLED) {
-            stopped = true;
-            break;
-        }
-        if (err) return err;
-        stopped = tk.file_end(f, c.file_lines());
-    }
-    if (!stopped) stopped = tk.close();
-    rows = c.exact.rows;
+    const int walked = lines_files(c, paths, n_paths, fast);
+    // a stop on request: the rows of the lines counted so far are fetched all the same, no CSV is written
+    const bool stopped = walked == GS_E_CANCELLED;
+    if (walked && !stopped) return walked;
+    std::map<std::string, KrakenRow> rows = c.exact.rows;
     if (c.kc) {
         int64_t n = 0;
         if (gs_krakencount_fetch(c.kc, nullptr, nullptr, 0, &n) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
@@ -3605,144 +3682,62 @@ extern "C" int gs_host_kraken_count_files(int device, const char *const *paths, 
 // gs_accmap on the device, gs_accmapparse.h for what it refuses)
 namespace {
 
-struct AmGuard {
-    gs_accmap *&am;
-    ~AmGuard() {
-        if (am) gs_accmap_destroy(am);
-        am = nullptr;
-    }
-};
-
-struct AmCtx {
+struct AmGoal : LineGoal {
+    using Reader = WholeLines;
     gs_accmap *am = nullptr;  // the device's map, or (GS_HOST_FAST=0) a host-only one
     bool keep = true;         // count_only == 0: entries go into am
     AccmapExact exact;        // the line-by-line parser: its buffer and line number live across a file
     int64_t flushed_passing = 0, dev_lines = 0;
     gs_host_accmap_totals tot{};
-    int prog_file = 0;
     int64_t prog_lines0 = 0;
     std::vector<uint8_t> slots;
     std::vector<int32_t> nodes;
     int64_t lines() const { return exact.lines + dev_lines; }
-    bool report(int64_t pos, bool gz) {
-        if (!trk().chunk(prog_file, pos, gz, lines() - prog_lines0)) return false;
-        trk().stopped(prog_file, lines() - prog_lines0);
-        return true;
+    int64_t file_lines() const { return lines() - prog_lines0; }
+    void begin_file(int) {  // every file is a stream of its own, all of them go into one map
+        exact.begin_stream();
+        prog_lines0 = lines();
+    }
+    // what the parser has made since the last call goes into the map, in input order
+    int flush(const std::string &path) {
+        const int64_t passing = exact.passing - flushed_passing;
+        flushed_passing = exact.passing;
+        tot.passing += passing;
+        tot.put += (int64_t)exact.entries.size();
+        if (keep) {
+            const size_t n = exact.entries.size();
+            slots.assign(32 * n + 32, 0);
+            nodes.assign(n + 1, 0);
+            for (size_t i = 0; i < n; i++) {
+                const std::string &key = exact.entries[i].key;
+                bool fits = key.size() <= 31;
+                for (unsigned char b : key) fits = fits && b < 0x80;
+                if (!fits) return hfail(GS_E_UNSUPPORTED, path + ": the accession '" + key + "' does not fit a key slot (31 bytes below 0x80)");
+                slots[32 * i] = (uint8_t)key.size();
+                memcpy(slots.data() + 32 * i + 1, key.data(), key.size());
+                nodes[i] = exact.entries[i].node;
+            }
+            if (gs_accmap_append(am, slots.data(), nodes.data(), (int64_t)n, passing) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
+        }
+        exact.entries.clear();
+        return GS_OK;
+    }
+    int feed(const std::string &path, const uint8_t *p, size_t n, bool last) {
+        if (!exact.feed(p, n, last)) return hfail(GS_E_INVALID, path + ": line " + std::to_string((long long)exact.line_no) + ": " + exact.error);
+        return flush(path);
+    }
+    int submit(const std::string &, const ChunkCutter &cut, bool *refused) {
+        int64_t rep[8];
+        if (gs_accmap_submit(am, cut.start, cut.bytes, GS_MEM_HOST, 0, rep) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
+        if ((*refused = rep[3] != 0)) return GS_OK;
+        dev_lines += rep[0];
+        tot.passing += rep[1];
+        tot.put += rep[2];
+        exact.line_no += rep[0];
+        exact.note_chunk(cut.start, (size_t)cut.bytes);  // (a later line of fewer than five tabs reads what these left behind)
+        return GS_OK;
     }
 };
-
-// what the parser has made since the last call goes into the map, in input order
-int am_flush(AmCtx &c, const std::string &path) {
-    const int64_t passing = c.exact.passing - c.flushed_passing;
-    c.flushed_passing = c.exact.passing;
-    c.tot.passing += passing;
-    c.tot.put += (int64_t)c.exact.entries.size();
-    if (c.keep) {
-        const size_t n = c.exact.entries.size();
-        c.slots.assign(32 * n + 32, 0);
-        c.nodes.assign(n + 1, 0);
-        for (size_t i = 0; i < n; i++) {
-            const std::string &key = c.exact.entries[i].key;
-            bool fits = key.size() <= 31;
-            for (unsigned char b : key) fits = fits && b < 0x80;
-            if (!fits) return hfail(GS_E_UNSUPPORTED, path + ": the accession '" + key + "' does not fit a key slot (31 bytes below 0x80)");
-            c.slots[32 * i] = (uint8_t)key.size();
-            memcpy(c.slots.data() + 32 * i + 1, key.data(), key.size());
-            c.nodes[i] = c.exact.entries[i].node;
-        }
-        if (gs_accmap_append(c.am, c.slots.data(), c.nodes.data(), (int64_t)n, passing) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
-    }
-    c.exact.entries.clear();
-    return GS_OK;
-}
-
-int am_feed(AmCtx &c, const std::string &path, const uint8_t *p, size_t n, bool last) {
-    if (!c.exact.feed(p, n, last)) return hfail(GS_E_INVALID, path + ": line " + std::to_string((long long)c.exact.line_no) + ": " + c.exact.error);
-    return am_flush(c, path);
-}
-
-// the rest of a stream, line by line: the file from `offset` on, or a memory range that ends the stream
-int am_cpu(AmCtx &c, const std::string &path, int64_t offset, const uint8_t *mem, size_t mem_n) {
-    c.tot.host_chunks++;
-    if (mem) {
-        const int err = am_feed(c, path, mem, mem_n, true);
-        return err ? err : c.report(0, false) ? cancelled_rc() : (int)GS_OK;
-    }
-    LineReader lr;
-    if (!lr.open(path, offset)) return hfail(GS_E_IO, "cannot open " + path);
-    std::vector<uint8_t> text;
-    for (bool eof = false; !eof;) {  // whole lines, some MiB at a time
-        text.clear();
-        while (text.size() < ((size_t)4 << 20)) {
-            if (lr.next_line(text) == 0) {
-                eof = true;
-                break;
-            }
-        }
-        // (next_line drops NUL bytes as the parser would; a final line without its newline is the stream's last)
-        if (!text.empty() && text.back() != '\n') eof = true;
-        const int err = am_feed(c, path, text.data(), text.size(), eof);
-        if (err) return err;
-        if (c.report(lr.raw_pos(), false)) return cancelled_rc();
-    }
-    return GS_OK;
-}
-
-// One file through the device: chunks that end behind a newline are scanned there; one that the device refuses goes through the
-// parser and its entries are appended, so the input order stays; the stream goes on behind it on the device.  A line that does not
-// fit a block sends the rest of the file through the parser; so does the unterminated tail.
-int am_device_file(AmCtx &c, const std::string &path, bool gzip) {
-    size_t block;
-    int readers = 0;
-    reader_shape(gzip, &block, &readers);
-    TextReader tr;
-    int err = tr.open(path, block, readers, gzip);
-    if (err) {
-        tr.close();
-        return err;
-    }
-    ChunkCutter cut;
-    cut.mode = ChunkCutter::LINES;
-    int64_t fallback_off = -1;
-    tr.start();
-    for (int64_t i = 0; !err; i++) {
-        TextSlot &sl = tr.wait_full(i);
-        if ((err = block_error(tr, sl, path))) break;
-        const bool eof = sl.eof;
-        const ChunkCutter::Cut what = cut_block(cut, tr, sl);
-        if (what == ChunkCutter::FALLBACK) {
-            fallback_off = cut.file_off;
-        } else if (what == ChunkCutter::CHUNK && cut.bytes > 0) {
-            int64_t rep[8];
-            if (gs_accmap_submit(c.am, cut.start, cut.bytes, GS_MEM_HOST, 0, rep) != GS_OK) {
-                err = hfail(GS_E_HIP, gs_last_error());
-                break;
-            }
-            if (rep[3] != 0) {  // refused: this chunk line by line
-                c.tot.host_chunks++;
-                err = am_feed(c, path, cut.start, (size_t)cut.bytes, false);
-            } else {
-                c.tot.device_chunks++;
-                c.dev_lines += rep[0];
-                c.tot.passing += rep[1];
-                c.tot.put += rep[2];
-                c.exact.line_no += rep[0];
-                c.exact.note_chunk(cut.start, (size_t)cut.bytes);  // (a later line of fewer than five tabs reads what these left behind)
-            }
-            cut.commit();
-            if (!err && c.report(cut.file_off, gzip)) err = cancelled_rc();  // (the record is out: the block may go back)
-        } else if (what == ChunkCutter::CHUNK) {
-            cut.commit();
-        }
-        tr.release(i);
-        if (eof || fallback_off >= 0) break;
-    }
-    tr.close();
-    if (err) return err;
-    if (fallback_off >= 0) return am_cpu(c, path, fallback_off, nullptr, 0);
-    if (!cut.carry.empty()) return am_cpu(c, path, 0, cut.carry.data(), cut.carry.size());
-    return GS_OK;
-}
 
 }  // namespace
 
@@ -3755,8 +3750,8 @@ extern "C" int gs_host_accmap_files(const char *const *paths, int n_paths, int d
     bool fast = true;
     if (const char *e = getenv("GS_HOST_FAST")) fast = atoi(e) != 0;
     const double t_start = now_s();
-    AmCtx c;
-    AmGuard guard{c.am};
+    AmGoal c;
+    HandleGuard<gs_accmap, gs_accmap_destroy> guard{c.am};
     c.keep = !count_only;
     // (the handle checks cfg; a host-only one, device -1, touches no device)
     if (const int rc = gs_accmap_create(&c.am, fast ? device : -1, cfg)) return hfail(rc, gs_last_error());
@@ -3766,25 +3761,10 @@ extern "C" int gs_host_accmap_files(const char *const *paths, int n_paths, int d
     c.exact.categories.assign(cfg->categories, cfg->categories + cfg->n_categories);
     c.exact.statuses.assign(cfg->statuses, cfg->statuses + cfg->n_statuses);
     if (cfg->n_nodes) c.exact.known.assign(cfg->known_taxids, cfg->known_taxids + cfg->n_nodes);
-    int err = GS_OK;
-    TrackerScope progress(paths, n_paths);
-    Tracker &tk = progress.t;
-    for (int f = 0; f < n_paths && !err; f++) {
-        const std::string path(paths[f]);
-        c.exact.begin_stream();  // every file is a stream of its own, all of them go into one map
-        c.prog_file = f;
-        c.prog_lines0 = c.lines();
-        if (tk.file_start(f)) {
-            tk.stopped(f, 0);
-            err = cancelled_rc();
-            break;
-        }
-        const int kind = fast ? text_path_kind(path) : 0;
-        err = kind ? am_device_file(c, path, kind == 2 || kind == 4) : am_cpu(c, path, 0, nullptr, 0);
-        if (!err && tk.file_end(f, c.lines() - c.prog_lines0)) err = cancelled_rc();
-    }
-    if (!err && tk.close()) err = cancelled_rc();
+    const int err = lines_files(c, paths, n_paths, fast);
     c.tot.lines = c.lines();
+    c.tot.device_chunks = c.device_chunks;
+    c.tot.host_chunks = c.host_chunks;
     if (!err && !count_only) {
         int64_t info[4];
         if (gs_accmap_finish(c.am, info) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
@@ -3806,157 +3786,69 @@ extern "C" int gs_host_accmap_files(const char *const *paths, int n_paths, int d
 // gs_asmsum on the device, gs_asmsumparse.h for what it refuses)
 namespace {
 
-struct AsGuard {
-    gs_asmsum *&as;
-    ~AsGuard() {
-        if (as) gs_asmsum_destroy(as);
-        as = nullptr;
-    }
-};
-
-struct AsCtx {
-    gs_asmsum *as = nullptr;  // the device's handle, or (GS_HOST_FAST=0) a host-only one
-    AsmsumExact exact;        // the record-by-record parser: its line number is the current file's
-    int64_t file_line0 = 0;   // the lines of the files in front of it
+struct AsGoal : LineGoal {
+    using Reader = RawPieces;  // NUL bytes are data here, and CR ends a line
+    gs_asmsum *as = nullptr;   // the device's handle, or (GS_HOST_FAST=0) a host-only one
+    AsmsumExact exact;         // the record-by-record parser: its line number is the current file's
+    int64_t file_line0 = 0;    // the lines of the files in front of it
     int64_t flushed_counted = 0, flushed_lines = 0;
     gs_host_asmsum_totals tot{};
-    int prog_file = 0;
     std::vector<int32_t> nodes;
     std::vector<uint8_t> quality, is_ref, pool;
     std::vector<int64_t> lines;
     std::vector<uint64_t> str_off;
-    bool report(int64_t pos, bool gz) {
-        if (!trk().chunk(prog_file, pos, gz, exact.line_no)) return false;
-        trk().stopped(prog_file, exact.line_no);
-        return true;
+    int64_t file_lines() const { return exact.line_no; }
+    void begin_file(int) {  // every file is a stream of its own, all of them go into one handle
+        file_line0 += exact.line_no;
+        exact.begin_stream();
+        flushed_lines = 0;
+    }
+    // what the parser has made since the last call goes into the handle, in input order
+    int flush() {
+        const size_t n = exact.entries.size();
+        nodes.assign(n + 1, 0);
+        quality.assign(n + 1, 0);
+        is_ref.assign(n + 1, 0);
+        lines.assign(n + 1, 0);
+        str_off.assign(3 * n + 1, 0);
+        pool.clear();
+        for (size_t i = 0; i < n; i++) {
+            const AsmsumEntry &e = exact.entries[i];
+            nodes[i] = e.node;
+            quality[i] = e.quality;
+            is_ref[i] = e.is_ref;
+            lines[i] = file_line0 + e.line;
+            for (const std::string *s : {&e.taxid, &e.species, &e.ftp}) {
+                pool.insert(pool.end(), s->begin(), s->end());
+                str_off[3 * i + (s == &e.taxid ? 1 : s == &e.species ? 2 : 3)] = pool.size();
+            }
+        }
+        pool.push_back(0);
+        const int64_t counted = exact.counted - flushed_counted, n_lines = exact.line_no - flushed_lines;
+        flushed_counted = exact.counted;
+        flushed_lines = exact.line_no;
+        tot.counted += counted;
+        tot.kept += (int64_t)n;
+        if (gs_asmsum_append(as, nodes.data(), quality.data(), is_ref.data(), lines.data(), str_off.data(), pool.data(), (int64_t)n, counted, n_lines) != GS_OK)
+            return hfail(GS_E_HIP, gs_last_error());
+        exact.entries.clear();
+        return GS_OK;
+    }
+    int feed(const std::string &path, const uint8_t *p, size_t n, bool last) {
+        if (!exact.feed(p, n, last)) return hfail(GS_E_INVALID, path + ": line " + std::to_string((long long)exact.line_no) + ": " + exact.error);
+        return flush();
+    }
+    int submit(const std::string &, const ChunkCutter &cut, bool *refused) {
+        int64_t rep[8];
+        if (gs_asmsum_submit(as, cut.start, cut.bytes, GS_MEM_HOST, 0, rep) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
+        if ((*refused = rep[3] != 0)) return GS_OK;
+        tot.counted += rep[0];
+        tot.kept += rep[1];
+        exact.line_no += rep[0] + rep[2] + rep[6];
+        flushed_lines = exact.line_no;
+        return GS_OK;
     }
 };
-
-// what the parser has made since the last call goes into the handle, in input order
-int as_flush(AsCtx &c) {
-    const size_t n = c.exact.entries.size();
-    c.nodes.assign(n + 1, 0);
-    c.quality.assign(n + 1, 0);
-    c.is_ref.assign(n + 1, 0);
-    c.lines.assign(n + 1, 0);
-    c.str_off.assign(3 * n + 1, 0);
-    c.pool.clear();
-    for (size_t i = 0; i < n; i++) {
-        const AsmsumEntry &e = c.exact.entries[i];
-        c.nodes[i] = e.node;
-        c.quality[i] = e.quality;
-        c.is_ref[i] = e.is_ref;
-        c.lines[i] = c.file_line0 + e.line;
-        for (const std::string *s : {&e.taxid, &e.species, &e.ftp}) {
-            c.pool.insert(c.pool.end(), s->begin(), s->end());
-            c.str_off[3 * i + (s == &e.taxid ? 1 : s == &e.species ? 2 : 3)] = c.pool.size();
-        }
-    }
-    c.pool.push_back(0);
-    const int64_t counted = c.exact.counted - c.flushed_counted, n_lines = c.exact.line_no - c.flushed_lines;
-    c.flushed_counted = c.exact.counted;
-    c.flushed_lines = c.exact.line_no;
-    c.tot.counted += counted;
-    c.tot.kept += (int64_t)n;
-    if (gs_asmsum_append(c.as, c.nodes.data(), c.quality.data(), c.is_ref.data(), c.lines.data(), c.str_off.data(), c.pool.data(), (int64_t)n, counted,
-                         n_lines) != GS_OK)
-        return hfail(GS_E_HIP, gs_last_error());
-    c.exact.entries.clear();
-    return GS_OK;
-}
-
-int as_feed(AsCtx &c, const std::string &path, const uint8_t *p, size_t n, bool last) {
-    if (!c.exact.feed(p, n, last)) return hfail(GS_E_INVALID, path + ": line " + std::to_string((long long)c.exact.line_no) + ": " + c.exact.error);
-    return as_flush(c);
-}
-
-// the rest of a stream, record by record: the file from `offset` on (in its text), or a memory range that ends the stream.  The bytes
-// go to the parser as they are: NUL bytes are data here, and CR ends a line
-int as_cpu(AsCtx &c, const std::string &path, int64_t offset, const uint8_t *mem, size_t mem_n) {
-    c.tot.host_chunks++;
-    if (mem) {
-        const int err = as_feed(c, path, mem, mem_n, true);
-        return err ? err : c.report(0, false) ? cancelled_rc() : (int)GS_OK;
-    }
-    gzFile gz = gzopen(path.c_str(), "rb");  // (zlib reads plain files transparently, gzip by content, member after member)
-    if (!gz) return hfail(GS_E_IO, "cannot open " + path);
-    gzbuffer(gz, 1 << 20);
-    if (offset != 0 && gzseek(gz, (z_off_t)offset, SEEK_SET) != (z_off_t)offset) {
-        gzclose(gz);
-        return hfail(GS_E_IO, "cannot seek in " + path);
-    }
-    size_t piece = (size_t)4 << 20;
-    if (const char *e = getenv("GS_HOST_BLOCK_BYTES")) piece = (size_t)std::max<long long>(1, atoll(e));
-    std::vector<uint8_t> text(piece);
-    int err = GS_OK;
-    for (bool eof = false; !eof && !err;) {
-        const int got = gzread(gz, text.data(), (unsigned)text.size());
-        if (got < 0) {
-            err = hfail(GS_E_IO, "cannot read " + path);
-            break;
-        }
-        eof = got == 0;
-        err = as_feed(c, path, text.data(), (size_t)got, eof);
-        if (!err && c.report((int64_t)gzoffset(gz), false)) err = cancelled_rc();
-    }
-    gzclose(gz);
-    return err;
-}
-
-// One file through the device, as am_device_file: a chunk the device refuses goes through the parser and its entries are appended,
-// so the input order stays; a line that does not fit a block sends the rest of the file through the parser; so does the
-// unterminated tail.
-int as_device_file(AsCtx &c, const std::string &path, bool gzip) {
-    size_t block;
-    int readers = 0;
-    reader_shape(gzip, &block, &readers);
-    TextReader tr;
-    int err = tr.open(path, block, readers, gzip);
-    if (err) {
-        tr.close();
-        return err;
-    }
-    ChunkCutter cut;
-    cut.mode = ChunkCutter::LINES;
-    int64_t fallback_off = -1;
-    tr.start();
-    for (int64_t i = 0; !err; i++) {
-        TextSlot &sl = tr.wait_full(i);
-        if ((err = block_error(tr, sl, path))) break;
-        const bool eof = sl.eof;
-        const ChunkCutter::Cut what = cut_block(cut, tr, sl);
-        if (what == ChunkCutter::FALLBACK) {
-            fallback_off = cut.file_off;
-        } else if (what == ChunkCutter::CHUNK && cut.bytes > 0) {
-            int64_t rep[8];
-            if (gs_asmsum_submit(c.as, cut.start, cut.bytes, GS_MEM_HOST, 0, rep) != GS_OK) {
-                err = hfail(GS_E_HIP, gs_last_error());
-                break;
-            }
-            if (rep[3] != 0) {  // refused: this chunk record by record
-                c.tot.host_chunks++;
-                err = as_feed(c, path, cut.start, (size_t)cut.bytes, false);
-            } else {
-                c.tot.device_chunks++;
-                c.tot.counted += rep[0];
-                c.tot.kept += rep[1];
-                c.exact.line_no += rep[0] + rep[2] + rep[6];
-                c.flushed_lines = c.exact.line_no;
-            }
-            cut.commit();
-            if (!err && c.report(cut.file_off, gzip)) err = cancelled_rc();  // (the record is out: the block may go back)
-        } else if (what == ChunkCutter::CHUNK) {
-            cut.commit();
-        }
-        tr.release(i);
-        if (eof || fallback_off >= 0) break;
-    }
-    tr.close();
-    if (err) return err;
-    if (fallback_off >= 0) return as_cpu(c, path, fallback_off, nullptr, 0);
-    if (!cut.carry.empty()) return as_cpu(c, path, 0, cut.carry.data(), cut.carry.size());
-    return GS_OK;
-}
 
 }  // namespace
 
@@ -3969,8 +3861,8 @@ extern "C" int gs_host_asmsum_files(const char *const *paths, int n_paths, int d
     bool fast = true;
     if (const char *e = getenv("GS_HOST_FAST")) fast = atoi(e) != 0;
     const double t_start = now_s();
-    AsCtx c;
-    AsGuard guard{c.as};
+    AsGoal c;
+    HandleGuard<gs_asmsum, gs_asmsum_destroy> guard{c.as};
     // (the handle checks cfg; a host-only one, device -1, touches no device)
     if (const int rc = gs_asmsum_create(&c.as, fast ? device : -1, cfg)) return hfail(rc, gs_last_error());
     if (cfg->n_nodes) c.exact.known.assign(cfg->known_taxids, cfg->known_taxids + cfg->n_nodes);
@@ -3978,26 +3870,10 @@ extern "C" int gs_host_asmsum_files(const char *const *paths, int n_paths, int d
     c.exact.quality_mask = cfg->quality_mask;
     c.exact.reference_only = cfg->reference_only != 0;
     c.exact.use_species = cfg->use_species_taxid != 0;
-    int err = GS_OK;
-    TrackerScope progress(paths, n_paths);
-    Tracker &tk = progress.t;
-    for (int f = 0; f < n_paths && !err; f++) {
-        const std::string path(paths[f]);
-        c.file_line0 += c.exact.line_no;
-        c.exact.begin_stream();  // every file is a stream of its own, all of them go into one handle
-        c.flushed_lines = 0;
-        c.prog_file = f;
-        if (tk.file_start(f)) {
-            tk.stopped(f, 0);
-            err = cancelled_rc();
-            break;
-        }
-        const int kind = fast ? text_path_kind(path) : 0;
-        err = kind ? as_device_file(c, path, kind == 2 || kind == 4) : as_cpu(c, path, 0, nullptr, 0);
-        if (!err && tk.file_end(f, c.exact.line_no)) err = cancelled_rc();
-    }
-    if (!err && tk.close()) err = cancelled_rc();
+    const int err = lines_files(c, paths, n_paths, fast);
     c.tot.lines = c.file_line0 + c.exact.line_no;
+    c.tot.device_chunks = c.device_chunks;
+    c.tot.host_chunks = c.host_chunks;
     if (!err) {
         int64_t info[4];
         if (gs_asmsum_finish(c.as, max_per_node, info) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
@@ -4021,122 +3897,57 @@ extern "C" int gs_host_asmsum_files(const char *const *paths, int n_paths, int d
 // what the device refuses)
 namespace {
 
-struct TtGuard {
-    gs_taxtree *&t;
-    ~TtGuard() {
-        if (t) gs_taxtree_destroy(t);
-        t = nullptr;
-    }
-};
-
-struct TtCtx {
+struct TtGoal : LineGoal {
+    using Reader = WholeLines;
     gs_taxtree *t = nullptr;
-    bool names = false;  // the names stream: gs_taxtree_submit_names / _append_names
-    int64_t lines = 0, device_chunks = 0, host_chunks = 0;
-    int prog_file = 0;
-    int64_t prog_lines0 = 0;
-    bool report(int64_t pos, bool gz) {
-        if (!trk().chunk(prog_file, pos, gz, lines - prog_lines0)) return false;
-        trk().stopped(prog_file, lines - prog_lines0);
-        return true;
+    int64_t *rep = nullptr;  // the call's report: what finish_nodes says goes there behind file 0
+    bool names = false;      // the names stream: gs_taxtree_submit_names / _append_names
+    bool finish_failed = false;
+    int64_t lines = 0, prog_lines0 = 0;
+    int64_t file_lines() const { return lines - prog_lines0; }
+    void begin_file(int f) {
+        names = f == 1;
+        prog_lines0 = lines;
     }
-};
-
-// whole lines through the line-by-line restatement inside the handle, at their place in the input order
-int tt_feed(TtCtx &c, const std::string &path, const uint8_t *p, size_t n, bool last) {
-    if (c.names) {
-        const int rc = gs_taxtree_append_names(c.t, p, (int64_t)n, last);
+    // (a tree that fell back to the host's lists -- duplicate ids -- takes its names line by line as well)
+    bool on_device(int f) const { return f == 0 || rep[7] == 0; }
+    // whole lines through the line-by-line restatement inside the handle, at their place in the input order
+    int feed(const std::string &path, const uint8_t *p, size_t n, bool last) {
+        if (names) {
+            const int rc = gs_taxtree_append_names(t, p, (int64_t)n, last);
+            if (rc != GS_OK) return hfail(rc, path + ": " + gs_last_error());
+            lines += (int64_t)std::count(p, p + n, (uint8_t)'\n') + (n && p[n - 1] != '\n');
+            return GS_OK;
+        }
+        int64_t r[8];
+        const int rc = gs_taxtree_append_nodes(t, p, (int64_t)n, last, r);
         if (rc != GS_OK) return hfail(rc, path + ": " + gs_last_error());
-        c.lines += (int64_t)std::count(p, p + n, (uint8_t)'\n') + (n && p[n - 1] != '\n');
+        lines += r[0];
         return GS_OK;
     }
-    int64_t rep[8];
-    const int rc = gs_taxtree_append_nodes(c.t, p, (int64_t)n, last, rep);
-    if (rc != GS_OK) return hfail(rc, path + ": " + gs_last_error());
-    c.lines += rep[0];
-    return GS_OK;
-}
-
-// the rest of a stream, line by line: the file from `offset` on, or a memory range that ends the stream
-int tt_cpu(TtCtx &c, const std::string &path, int64_t offset, const uint8_t *mem, size_t mem_n) {
-    c.host_chunks++;
-    if (mem) {
-        const int err = tt_feed(c, path, mem, mem_n, true);
-        return err ? err : c.report(0, false) ? cancelled_rc() : (int)GS_OK;
+    int submit(const std::string &path, const ChunkCutter &cut, bool *refused) {
+        int64_t r[8];
+        const int rc = names ? gs_taxtree_submit_names(t, cut.start, cut.bytes, GS_MEM_HOST, 0, r) : gs_taxtree_submit_nodes(t, cut.start, cut.bytes, GS_MEM_HOST, 0, r);
+        if (rc != GS_OK) return hfail(rc, path + ": " + gs_last_error());
+        if (!(*refused = r[3] != 0)) lines += r[0];
+        return GS_OK;
     }
-    LineReader lr;
-    if (!lr.open(path, offset)) return hfail(GS_E_IO, "cannot open " + path);
-    std::vector<uint8_t> text;
-    for (bool eof = false; !eof;) {  // whole lines, some MiB at a time
-        text.clear();
-        while (text.size() < ((size_t)4 << 20)) {
-            if (lr.next_line(text) == 0) {
-                eof = true;
-                break;
-            }
+    int end_file(int f, const std::string &path) {  // behind the nodes: the tree
+        if (f != 0) return GS_OK;
+        rep[0] = lines;
+        int64_t info[8];
+        const int rc = gs_taxtree_finish_nodes(t, info);
+        if (rc != GS_OK) {
+            finish_failed = true;
+            return hfail(rc, path + ": " + gs_last_error());
         }
-        // (next_line drops NUL bytes as the parser would; a final line without its newline is the stream's last)
-        if (!text.empty() && text.back() != '\n') eof = true;
-        const int err = tt_feed(c, path, text.data(), text.size(), eof);
-        if (err) return err;
-        if (c.report(lr.raw_pos(), false)) return cancelled_rc();
+        rep[4] = info[0];
+        rep[5] = info[1];
+        rep[6] = info[3];
+        rep[7] = info[4];
+        return GS_OK;
     }
-    return GS_OK;
-}
-
-// A nodes or names file through the device: chunks that end behind a newline are scanned there; one that the device refuses goes through
-// the handle's parser, so the input order stays; the stream goes on behind it on the device.  A line that does not fit a block sends
-// the rest of the file through the parser; so does the unterminated tail.
-int tt_device_file(TtCtx &c, const std::string &path, bool gzip) {
-    size_t block;
-    int readers = 0;
-    reader_shape(gzip, &block, &readers);
-    TextReader tr;
-    int err = tr.open(path, block, readers, gzip);
-    if (err) {
-        tr.close();
-        return err;
-    }
-    ChunkCutter cut;
-    cut.mode = ChunkCutter::LINES;
-    int64_t fallback_off = -1;
-    tr.start();
-    for (int64_t i = 0; !err; i++) {
-        TextSlot &sl = tr.wait_full(i);
-        if ((err = block_error(tr, sl, path))) break;
-        const bool eof = sl.eof;
-        const ChunkCutter::Cut what = cut_block(cut, tr, sl);
-        if (what == ChunkCutter::FALLBACK) {
-            fallback_off = cut.file_off;
-        } else if (what == ChunkCutter::CHUNK && cut.bytes > 0) {
-            int64_t rep[8];
-            const int rc = c.names ? gs_taxtree_submit_names(c.t, cut.start, cut.bytes, GS_MEM_HOST, 0, rep)
-                                   : gs_taxtree_submit_nodes(c.t, cut.start, cut.bytes, GS_MEM_HOST, 0, rep);
-            if (rc != GS_OK) {
-                err = hfail(rc, path + ": " + gs_last_error());
-                break;
-            }
-            if (rep[3] != 0) {  // refused: this chunk line by line
-                c.host_chunks++;
-                err = tt_feed(c, path, cut.start, (size_t)cut.bytes, false);
-            } else {
-                c.device_chunks++;
-                c.lines += rep[0];
-            }
-            cut.commit();
-            if (!err && c.report(cut.file_off, gzip)) err = cancelled_rc();  // (the record is out: the block may go back)
-        } else if (what == ChunkCutter::CHUNK) {
-            cut.commit();
-        }
-        tr.release(i);
-        if (eof || fallback_off >= 0) break;
-    }
-    tr.close();
-    if (err) return err;
-    if (fallback_off >= 0) return tt_cpu(c, path, fallback_off, nullptr, 0);
-    if (!cut.carry.empty()) return tt_cpu(c, path, 0, cut.carry.data(), cut.carry.size());
-    return GS_OK;
-}
+};
 
 }  // namespace
 
@@ -4146,40 +3957,13 @@ extern "C" int gs_host_taxtree_files(int device, const char *nodes_path, const c
     for (int i = 0; i < 8; i++) report[i] = 0;
     bool fast = true;
     if (const char *e = getenv("GS_HOST_FAST")) fast = atoi(e) != 0;
-    TtCtx c;
-    TtGuard guard{c.t};
+    TtGoal c;
+    HandleGuard<gs_taxtree, gs_taxtree_destroy> guard{c.t};
+    c.rep = report;
     if (const int rc = gs_taxtree_create(&c.t, fast ? device : -1)) return hfail(rc, gs_last_error());
     const char *paths[2] = {nodes_path, names_path};
-    const int n_paths = names_path ? 2 : 1;
-    int err = GS_OK;
-    TrackerScope progress(paths, n_paths);
-    Tracker &tk = progress.t;
-    for (int f = 0; f < n_paths && !err; f++) {
-        const std::string path(paths[f]);
-        c.names = f == 1;
-        c.prog_file = f;
-        c.prog_lines0 = c.lines;
-        if (tk.file_start(f)) {
-            tk.stopped(f, 0);
-            err = cancelled_rc();
-            break;
-        }
-        // (a tree that fell back to the host's lists -- duplicate ids -- takes its names line by line as well)
-        const int kind = fast && (f == 0 || report[7] == 0) ? text_path_kind(path) : 0;
-        err = kind ? tt_device_file(c, path, kind == 2 || kind == 4) : tt_cpu(c, path, 0, nullptr, 0);
-        if (!err && tk.file_end(f, c.lines - c.prog_lines0)) err = cancelled_rc();
-        if (!err && f == 0) {
-            report[0] = c.lines;
-            int64_t info[8];
-            const int rc = gs_taxtree_finish_nodes(c.t, info);
-            if (rc != GS_OK) return hfail(rc, path + ": " + gs_last_error());
-            report[4] = info[0];
-            report[5] = info[1];
-            report[6] = info[3];
-            report[7] = info[4];
-        }
-    }
-    if (!err && tk.close()) err = cancelled_rc();
+    const int err = lines_files(c, paths, names_path ? 2 : 1, fast);
+    if (c.finish_failed) return err;
     report[1] = c.lines - report[0];
     report[2] = c.device_chunks;
     report[3] = c.host_chunks;
@@ -4212,14 +3996,6 @@ extern "C" int gs_host_read_taxids_file(const char *path, int32_t *requested, in
 
 // ---- genome FASTA files to regions (AbstractFastaReader.readFasta under the store readers; gs_genomes on the device)
 namespace {
-
-struct GnGuard {
-    gs_genomes *&g;
-    ~GnGuard() {
-        if (g) gs_genomes_destroy(g);
-        g = nullptr;
-    }
-};
 
 struct GnCtx {
     gs_genomes *g = nullptr;
@@ -4437,7 +4213,7 @@ int gn_files(GnCtx &c, const char *const *paths, int n_paths, int device, gs_hos
     bool fast = true;
     if (const char *e = getenv("GS_HOST_FAST")) fast = atoi(e) != 0;
     const double t_start = now_s();
-    GnGuard guard{c.g};
+    HandleGuard<gs_genomes, gs_genomes_destroy> guard{c.g};
     if (fast && gs_genomes_create(&c.g, device) != GS_OK) return hfail(GS_E_HIP, gs_last_error());
     int err = GS_OK;
     TrackerScope progress(paths, n_paths);
