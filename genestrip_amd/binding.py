@@ -63,7 +63,7 @@ ABI_SYMBOLS = (
     "gs_genomes_create", "gs_genomes_scan", "gs_genomes_headers", "gs_genomes_gather", "gs_genomes_regions", "gs_genomes_kernel_time",
     "gs_genomes_destroy",
     "gs_accmap_create", "gs_accmap_submit", "gs_accmap_append", "gs_accmap_finish", "gs_accmap_fetch", "gs_accmap_lookup",
-    "gs_accmap_lookup_genomes", "gs_accmap_get_device", "gs_accmap_kernel_time", "gs_accmap_destroy",
+    "gs_accmap_lookup_genomes", "gs_accmap_get_device", "gs_accmap_get_n_nodes", "gs_accmap_kernel_time", "gs_accmap_destroy",
     "gs_asmsum_create", "gs_asmsum_submit", "gs_asmsum_append", "gs_asmsum_finish", "gs_asmsum_fetch", "gs_asmsum_file_name",
     "gs_asmsum_get_device", "gs_asmsum_kernel_time", "gs_asmsum_destroy",
     "gs_taxtree_create", "gs_taxtree_submit_nodes", "gs_taxtree_append_nodes", "gs_taxtree_finish_nodes", "gs_taxtree_submit_names", "gs_taxtree_append_names", "gs_taxtree_finish_times",
@@ -278,7 +278,7 @@ def lib():
         "gs_accmap_create": (ci, [vp, ci, vp]), "gs_accmap_submit": (ci, [vp, vp, i64, ci, ci, vp]),
         "gs_accmap_append": (ci, [vp, vp, vp, i64, i64]), "gs_accmap_finish": (ci, [vp, vp]), "gs_accmap_fetch": (ci, [vp, vp, vp, vp]),
         "gs_accmap_lookup": (ci, [vp, vp, vp, i64, ci, ci, vp]), "gs_accmap_lookup_genomes": (ci, [vp, vp, ci, vp]),
-        "gs_accmap_get_device": (ci, [vp, vp]), "gs_accmap_kernel_time": (ci, [vp, ci, vp, vp]), "gs_accmap_destroy": (ci, [vp]),
+        "gs_accmap_get_device": (ci, [vp, vp]), "gs_accmap_get_n_nodes": (ci, [vp, vp]), "gs_accmap_kernel_time": (ci, [vp, ci, vp, vp]), "gs_accmap_destroy": (ci, [vp]),
         "gs_asmsum_create": (ci, [vp, ci, vp]), "gs_asmsum_submit": (ci, [vp, vp, i64, ci, ci, vp]),
         "gs_asmsum_append": (ci, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64]), "gs_asmsum_finish": (ci, [vp, i32, vp]),
         "gs_asmsum_fetch": (ci, [vp, vp, vp, vp, vp, vp, vp]), "gs_asmsum_file_name": (i64, [C.c_char_p, i64, vp, i64]),

@@ -7433,6 +7433,13 @@ extern "C" int gs_accmap_get_device(gs_accmap *h, int *device) try {
 }
 GS_API_CATCH
 
+extern "C" int gs_accmap_get_n_nodes(gs_accmap *h, int32_t *n_nodes) try {
+    if (!h || !n_nodes) return fail(GS_E_INVALID, "NULL argument");
+    *n_nodes = h->n_nodes;
+    return GS_OK;
+}
+GS_API_CATCH
+
 extern "C" int gs_accmap_submit(gs_accmap *h, const uint8_t *text, int64_t n_bytes, int mem, int last, int64_t report[8]) try {
     int rc = lines_args(h, text, n_bytes, mem, report);
     if (rc) return rc;

@@ -4006,6 +4006,7 @@ struct GnCtx {
     gs_accmap *am = nullptr;
     int complete_only = 0;
     gs_genome_resolve_nodes_fn resolve_nodes = nullptr;
+    const int32_t *node_of_file = nullptr;  // gs_host_genome_files_into: >= 0: the node of every record of that file, no lookup
     std::vector<int32_t> node;
     int file = 0;
     int64_t first_record = 0;  // records of the file in front of the chunk
@@ -4030,10 +4031,12 @@ int gn_resolve(GnCtx &c, int64_t n, const uint8_t *hdr, const uint64_t *hoff) {
     c.kvi.clear();
     if (n == 0) return 0;
     int rc;
-    if (c.am) {
-        c.node.assign((size_t)n, -1);
-        rc = hdr ? gs_accmap_lookup(c.am, hdr, hoff, n, GS_MEM_HOST, c.complete_only, c.node.data())
-                 : gs_accmap_lookup_genomes(c.am, c.g, c.complete_only, c.node.data());
+    if (c.resolve_nodes) {
+        const int32_t fixed = c.node_of_file ? std::max(c.node_of_file[c.file], -1) : -1;
+        c.node.assign((size_t)n, fixed);
+        rc = fixed >= 0 ? (int)GS_OK
+             : hdr      ? gs_accmap_lookup(c.am, hdr, hoff, n, GS_MEM_HOST, c.complete_only, c.node.data())
+                        : gs_accmap_lookup_genomes(c.am, c.g, c.complete_only, c.node.data());
         if (rc) return hfail(rc, gs_last_error());
         rc = c.resolve_nodes(c.resolve_user, c.file, c.first_record, n, c.node.data(), c.vi.data());
     } else {
@@ -4086,7 +4089,7 @@ int gn_chunk(GnCtx &c, const uint8_t *p, int64_t n) {
     c.tot.chunks++;
     c.tot.text_bytes += used;
     c.tot.max_line_bytes = std::max(c.tot.max_line_bytes, ml);
-    if (c.am) {  // the header lines never leave the device
+    if (c.resolve_nodes) {  // the header lines never leave the device
         if ((rc = gn_resolve(c, nr, nullptr, nullptr)) || c.kvi.empty()) return rc;
     } else {
         c.hdr.resize((size_t)hb + 1);
@@ -4265,6 +4268,76 @@ extern "C" int gs_host_genome_files_mapped(const char *const *paths, int n_paths
     c.resolve_user = resolve_user;
     c.sink = sink;
     c.sink_user = sink_user;
+    return gn_files(c, paths, n_paths, device, totals);
+} catch (const std::bad_alloc &) {
+    return hfail(GS_E_NOMEM, "out of host memory");
+} catch (const std::exception &e) {
+    return hfail(GS_E_INVALID, std::string("unexpected exception: ") + e.what());
+}
+
+// ---- gs_host_genome_files_into: the loop of gs_host_genome_files_mapped with the common resolver and sink built in
+namespace {
+
+struct GnInto {
+    const int32_t *vi_of_node = nullptr;
+    int32_t n_nodes = 0;
+    int kind = 0, update = 0;
+    void *handle = nullptr;
+};
+
+int gn_into_resolve(void *user, int, int64_t, int64_t n, const int32_t *node, int32_t *vi) {
+    const GnInto &t = *static_cast<const GnInto *>(user);
+    for (int64_t i = 0; i < n; i++) vi[i] = node[i] >= 0 && node[i] < t.n_nodes ? std::max(t.vi_of_node[node[i]], -1) : -1;
+    return 0;
+}
+
+int gn_into_sink(void *user, const uint8_t *seq, const uint64_t *off, const int32_t *vi, int64_t n_regions, int mem) {
+    const GnInto &t = *static_cast<const GnInto *>(user);
+    int rc = GS_E_INVALID;
+    switch (t.kind) {
+    case GS_HOST_INTO_SIZE: rc = gs_dbsize_add(static_cast<gs_dbsize *>(t.handle), seq, off, vi, n_regions, mem); break;
+    case GS_HOST_INTO_BUILD: rc = gs_dbbuild_add(static_cast<gs_dbbuild *>(t.handle), seq, off, vi, n_regions, mem, t.update); break;
+    case GS_HOST_INTO_UPDATE: rc = gs_dbupdate_add(static_cast<gs_dbupdate *>(t.handle), seq, off, vi, n_regions, mem); break;
+    case GS_HOST_INTO_QUALITY: rc = gs_dbquality_add(static_cast<gs_dbquality *>(t.handle), seq, off, vi, n_regions, mem); break;
+    }
+    return rc ? hfail(rc, gs_last_error()) : 0;
+}
+
+}  // namespace
+
+extern "C" int gs_host_genome_files_into(const char *const *paths, int n_paths, int device, gs_accmap *am, int complete_only,
+                                         const int32_t *node_of_file, const int32_t *vi_of_node, int32_t n_nodes, int kind, void *handle,
+                                         int update, gs_host_genome_totals *totals) try {
+    if (!paths || n_paths < 0 || n_nodes < 0 || (n_nodes > 0 && !vi_of_node)) return hfail(GS_E_INVALID, "NULL or negative argument");
+    if (!handle) return hfail(GS_E_INVALID, "NULL target handle");
+    if (kind != GS_HOST_INTO_SIZE && kind != GS_HOST_INTO_BUILD && kind != GS_HOST_INTO_UPDATE && kind != GS_HOST_INTO_QUALITY)
+        return hfail(GS_E_INVALID, "unknown target kind " + std::to_string(kind));
+    if (am) {
+        int32_t map_nodes = -1;
+        const int rc = gs_accmap_get_n_nodes(am, &map_nodes);
+        if (rc) return hfail(rc, gs_last_error());
+        if (map_nodes != n_nodes)
+            return hfail(GS_E_INVALID, "vi_of_node has " + std::to_string(n_nodes) + " nodes, the accession map " + std::to_string(map_nodes));
+    }
+    for (int f = 0; f < n_paths; f++) {
+        const int32_t fixed = node_of_file ? node_of_file[f] : -1;
+        if (fixed < 0 && !am) return hfail(GS_E_INVALID, "file " + std::to_string(f) + " needs a lookup and there is no accession map");
+        if (fixed >= n_nodes) return hfail(GS_E_INVALID, "node_of_file[" + std::to_string(f) + "] is no node");
+    }
+    GnInto t;
+    t.vi_of_node = vi_of_node;
+    t.n_nodes = n_nodes;
+    t.kind = kind;
+    t.update = update ? 1 : 0;
+    t.handle = handle;
+    GnCtx c;
+    c.am = am;
+    c.complete_only = complete_only;
+    c.node_of_file = node_of_file;
+    c.resolve_nodes = gn_into_resolve;
+    c.resolve_user = &t;
+    c.sink = gn_into_sink;
+    c.sink_user = &t;
     return gn_files(c, paths, n_paths, device, totals);
 } catch (const std::bad_alloc &) {
     return hfail(GS_E_NOMEM, "out of host memory");

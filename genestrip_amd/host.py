@@ -64,6 +64,7 @@ def lib():
         "gs_host_accmap_files": (ci, [vp, ci, ci, vp, ci, vp, vp]),
         "gs_host_asmsum_files": (ci, [vp, ci, ci, vp, C.c_int32, vp, vp]),
         "gs_host_genome_files_mapped": (ci, [vp, ci, ci, vp, ci, vp, vp, vp, vp, vp]),
+        "gs_host_genome_files_into": (ci, [vp, ci, ci, vp, ci, vp, vp, C.c_int32, ci, vp, ci, vp]),
         "gs_host_taxtree_files": (ci, [ci, C.c_char_p, C.c_char_p, vp, vp]),
         "gs_host_read_taxids_file": (ci, [C.c_char_p, vp, vp, vp, vp, i64]),
         "gs_host_write_kraken_csv": (ci, [C.c_char_p, vp, C.c_int32, vp, i64]),
@@ -136,7 +137,8 @@ def _attached():
 
 class Control:
     """Progress and cancellation of the file-level calls (match_files, match_run, match_files_into, filter_files, extract_files,
-    fasta2fastq, kraken_count_files, genome_files) that THIS thread makes inside the `with` block:
+    fasta2fastq, kraken_count_files, genome_files, genome_files_mapped, genome_files_into, accmap_files, assembly_summary_files,
+    taxtree_files) that THIS thread makes inside the `with` block:
 
         with host.Control(callback=lambda p: p.total_reads > 10**9, every_ms=200) as ctl:
             table, dtable, tot = host.match_files(store, paths)
@@ -560,6 +562,35 @@ def genome_files_mapped(paths, accession_map, resolve, sink, complete_only=False
     gets one node per record (int32 array, -1: none) instead of header text and returns one value index per record as in
     genome_files.  -> GenomeTotals"""
     return genome_files(paths, resolve, sink, device=device, _mapped=(accession_map, complete_only))
+
+
+INTO_SIZE, INTO_BUILD, INTO_UPDATE, INTO_QUALITY = 0, 1, 2, 3  # GS_HOST_INTO_*
+_INTO_KINDS = {"DeviceDbSizer": INTO_SIZE, "DeviceDbBuilder": INTO_BUILD, "DeviceDbUpdater": INTO_UPDATE, "DeviceDbQuality": INTO_QUALITY}
+
+
+def genome_files_into(paths, target, vi_of_node, accession_map=None, node_of_file=None, complete_only=False, update=False, kind=None,
+                      device=0):
+    """gs_host_genome_files_into: genome_files_mapped without callbacks.  vi_of_node: the value index per tree node (< 0: skip);
+    node_of_file: None, or per file a node (>= 0: every record of the file counts for it, no lookup; < 0: look the record up in
+    accession_map, a finished DeviceAccessionMap); target: a DeviceDbSizer, DeviceDbBuilder (update: its add's flag),
+    DeviceDbUpdater or DeviceDbQuality, whose add receives the kept regions (kind: one of INTO_* for any other object with a
+    handle `h`).  Limits per tax id and the finer-node options are not served.  -> GenomeTotals"""
+    if kind is None:
+        kind = _INTO_KINDS.get(type(target).__name__)
+        if kind is None:
+            raise TypeError("target must be a DeviceDbSizer, DeviceDbBuilder, DeviceDbUpdater or DeviceDbQuality (or give kind)")
+    paths = [os.fspath(p) for p in paths]
+    vi = np.ascontiguousarray(vi_of_node, dtype=np.int32)
+    nof = None if node_of_file is None else np.ascontiguousarray(node_of_file, dtype=np.int32)
+    if nof is not None and len(nof) != len(paths):
+        raise ValueError("one node_of_file entry per path")
+    t = GenomeTotals()
+    rc = lib().gs_host_genome_files_into(_cstr_array(paths), len(paths), int(device), accession_map.h if accession_map is not None else None,
+                                         int(bool(complete_only)), nof.ctypes.data_as(C.c_void_p) if nof is not None and len(nof) else None,
+                                         vi.ctypes.data_as(C.c_void_p) if len(vi) else None, len(vi), int(kind),
+                                         getattr(target, "h", None), int(bool(update)), C.byref(t))
+    _check(rc, totals=t)
+    return t
 
 
 class AccmapTotals(C.Structure):

@@ -1151,6 +1151,7 @@ int gs_genomes_destroy(gs_genomes *g);
  *                    map does not hold it.
  * gs_accmap_lookup_genomes  the same over the header lines of the chunk that g has scanned (gs_genomes_scan; same device), which
  *                    never leave the device; node_out: host, one per record.
+ * gs_accmap_get_n_nodes  the n_nodes of the cfg the map was created with: what a table per node must have.
  * gs_accmap_kernel_time  profile != 0: from now on scan, finish and lookup run between events; what they add up to so far.
  * NULL or negative arguments: GS_E_INVALID, before any device call.
  * ------------------------------------------------------------------------------------------------- */
@@ -1172,6 +1173,7 @@ int gs_accmap_fetch(gs_accmap *am, uint8_t *keys32, int32_t *nodes, int32_t *reg
 int gs_accmap_lookup(gs_accmap *am, const uint8_t *headers, const uint64_t *header_off, int64_t n, int mem, int complete_only, int32_t *node_out);
 int gs_accmap_lookup_genomes(gs_accmap *am, gs_genomes *g, int complete_only, int32_t *node_out);
 int gs_accmap_get_device(gs_accmap *am, int *device);
+int gs_accmap_get_n_nodes(gs_accmap *am, int32_t *n_nodes);
 int gs_accmap_kernel_time(gs_accmap *am, int profile, int64_t *launches, double *total_ms);
 int gs_accmap_destroy(gs_accmap *am);
 

@@ -17,6 +17,8 @@
  *   gs_host_write_quality_csv  the dbquality goal's CSV (DBQualityCountsGoal's rank aggregation + DBQualityCSVGoal.makeFile)
  *   gs_host_genome_files  genome FASTA files -> the regions of a build (the walk of AbstractFastaReader.readFasta under the
  *                         store readers), records found and bases gathered on the device, the selection left to a callback
+ *   gs_host_genome_files_into  the same without callbacks: accession map, a table of value indices per node, one of the four region
+ *                         handles as the target -- what the JNI shim binds
  *   gs_host_control_*     progress records and cancellation of the file-level calls above (ExecutionContext.setFastqProgress /
  *                         setTotalProgress, FastqReaderInterruptedException), through a control attached to the calling thread
  * (C/ = core/src/main/java/org/metagene/genestrip/, B/ = base/src/main/java/org/metagene/genestrip/)
@@ -295,10 +297,32 @@ int gs_host_genome_files_mapped(const char *const *paths, int n_paths, int devic
                                 gs_genome_resolve_nodes_fn resolve, void *resolve_user, gs_genome_sink_fn sink, void *sink_user,
                                 gs_host_genome_totals *totals);
 
+/* gs_host_genome_files_mapped without callbacks, for the common case in which they do what a table can do -- and the form a host
+ * behind a foreign-function layer without upcalls (the JNI shim) can call.  It is that call's loop with a resolver and a sink built in:
+ * chunking, device scan, lookup where the scan left the header lines, host-parser fallbacks, GS_HOST_FAST=0, totals, progress and
+ * cancellation are the same code.
+ *   node_of_file[n_paths] or NULL: >= 0: every record of that file counts for that node, no lookup (ignoreAccessionMap of the additional
+ *     FASTA files, C/goals/FastaReaderGoal.java:140-145); < 0 (and NULL): its records are looked up in `am` as above.
+ *   vi_of_node[n_nodes]: the value index per tree node, < 0: skip the record (the taxNodes test of AbstractRefSeqFastaReader.infoLine,
+ *     C/refseq/AbstractRefSeqFastaReader.java:180, as a table).  A record whose node is -1 is skipped.
+ *   kind / handle: where the kept regions go -- gs_dbsize_add, gs_dbbuild_add (with `update`), gs_dbupdate_add or gs_dbquality_add of
+ *     the handle, with the memory kind the loop delivers (device memory for chunks the device scanned).  A failing _add ends the walk and
+ *     its code is returned; gs_host_last_error carries its message.
+ * am: a finished map, or NULL if no file needs a lookup.  Checked before any device call, GS_E_INVALID: a file that needs a lookup
+ * while am is NULL; n_nodes other than the map's (gs_accmap_get_n_nodes); a node_of_file entry >= n_nodes; an unknown kind; a NULL
+ * handle, paths or (n_nodes > 0) vi_of_node.
+ * NOT served: maxGenomesPerTaxid / maxKMersPerTaxid / maxPerTaxidRank (the limits of AbstractStoreFastaReader) and idNodes / fileNodes /
+ * dataNodes (the finer-node options): a caller that configures any of them keeps gs_host_genome_files_mapped or its own reader. */
+enum { GS_HOST_INTO_SIZE = 0, GS_HOST_INTO_BUILD = 1, GS_HOST_INTO_UPDATE = 2, GS_HOST_INTO_QUALITY = 3 };
+int gs_host_genome_files_into(const char *const *paths, int n_paths, int device, gs_accmap *am, int complete_only,
+                              const int32_t *node_of_file, const int32_t *vi_of_node, int32_t n_nodes, int kind, void *handle, int update,
+                              gs_host_genome_totals *totals);
+
 /* ---- progress and cancellation of the file-level calls (what the reference does through ExecutionContext.setFastqProgress /
  * setTotalProgress, C/fastq/AbstractLoggingFastqStreamer.java:161-209,247-252, and FastqReaderInterruptedException).
  * A control is attached to a THREAD (gs_host_control_attach); the file-level calls that thread makes afterwards -- gs_host_match_files,
- * _match_run, _match_into, _filter_files, _extract_files, _fasta2fastq, _kraken_count_files, _genome_files -- publish records to it and
+ * _match_run, _match_into, _filter_files, _extract_files, _fasta2fastq, _kraken_count_files, _genome_files, _genome_files_mapped,
+ * _genome_files_into, _accmap_files, _asmsum_files, _taxtree_files -- publish records to it and
  * look at its cancel flag after every chunk.  Their signatures are unchanged, and a thread without a control behaves as before.
  * Records: one at the start of each file (file_bytes_done = 0), one after every chunk or batch whose results are in the handle's
  * state, a last one per file (file_done = 1, file_bytes_done == file_bytes_total) and a closing one (files_done == n_files).  Files

@@ -9,10 +9,18 @@
  * from the same goals, which createGoals has registered by then (FASTQ_MAP_TRANSFORM; FASTA_MAP_TRANSFORM, SETUP,
  * FASTA_DOWNLOAD).  createGoals runs inside Maker's constructor, before `device` is assigned here, so the two goals take the
  * device as a supplier and read it when they are made.
+ *
+ * The database chain enters the same way: `accmapsize`, `accmap`, `taxfromgenbank` and `fastasgenbank` are constructed inline too
+ * (:269-287), each from the goal in front of it.  registerGoal puts GpuAccessionMapSizeGoal, GpuAccessionMapGoal,
+ * GpuTaxNodesFromGenbankGoal and GpuFastaFilesFromGenbankGoal in their place, each built from the goals REGISTERED by then, so the
+ * four hang together and a goal made by its key runs on the device.  What createGoals builds behind them (fastasgenbankdl, fillsize,
+ * filldb, db, ...) got the reference's instances as constructor arguments before registerGoal saw them and keeps those: the seam for
+ * them is a factory method upstream, as match and filter have one.
  */
 package org.metagene.genestrip;
 
 import java.util.Map;
+import java.util.Set;
 
 import org.metagene.genestrip.goals.ExtractGoal;
 import org.metagene.genestrip.goals.Fasta2FastqGoal;
@@ -27,9 +35,23 @@ import org.metagene.genestrip.goals.GpuMatchResultGoal;
 import org.metagene.genestrip.goals.LoadDBGoal;
 import org.metagene.genestrip.goals.LoadIndexGoal;
 import org.metagene.genestrip.goals.MatchResultGoal;
+import org.metagene.genestrip.goals.genbank.FastaFilesFromGenbankGoal;
+import org.metagene.genestrip.goals.genbank.GpuFastaFilesFromGenbankGoal;
+import org.metagene.genestrip.goals.genbank.GpuTaxNodesFromGenbankGoal;
+import org.metagene.genestrip.goals.genbank.TaxNodesFromGenbankGoal;
+import org.metagene.genestrip.goals.refseq.AccessionMapGoal;
+import org.metagene.genestrip.goals.refseq.AccessionMapSizeGoal;
+import org.metagene.genestrip.goals.refseq.GpuAccessionMapGoal;
+import org.metagene.genestrip.goals.refseq.GpuAccessionMapSizeGoal;
+import org.metagene.genestrip.goals.refseq.RefSeqCatalogDownloadGoal;
 import org.metagene.genestrip.io.StreamingResourceStream;
+import org.metagene.genestrip.make.FileGoal;
 import org.metagene.genestrip.make.Goal;
 import org.metagene.genestrip.make.ObjectGoal;
+import org.metagene.genestrip.refseq.AccessionMap;
+import org.metagene.genestrip.refseq.RefSeqCategory;
+import org.metagene.genestrip.tax.TaxTree;
+import org.metagene.genestrip.tax.TaxTree.TaxIdNode;
 
 public class GpuGSMaker<P extends GSProject> extends GSMaker<P> {
 	private final int device;
@@ -50,6 +72,24 @@ public class GpuGSMaker<P extends GSProject> extends GSMaker<P> {
 			goal = new GpuFasta2FastqGoal<P>(getProject(), goal.getKey(),
 					(ObjectGoal<Map<String, StreamingResourceStream>, P>) (ObjectGoal) getGoal(GSGoalKey.FASTA_MAP_TRANSFORM),
 					() -> device, getGoal(GSGoalKey.SETUP), getGoal(GSGoalKey.FASTA_DOWNLOAD));
+		} else if (goal instanceof AccessionMapSizeGoal && !(goal instanceof GpuAccessionMapSizeGoal)) {
+			goal = new GpuAccessionMapSizeGoal<P>(getProject(),
+					(ObjectGoal<Set<RefSeqCategory>, P>) (ObjectGoal) getGoal(GSGoalKey.CATEGORIES),
+					(RefSeqCatalogDownloadGoal) getGoal(GSGoalKey.REFSEQCAT), () -> device);
+		} else if (goal instanceof AccessionMapGoal && !(goal instanceof GpuAccessionMapGoal)) {
+			goal = new GpuAccessionMapGoal<P>(getProject(),
+					(ObjectGoal<Set<RefSeqCategory>, P>) (ObjectGoal) getGoal(GSGoalKey.CATEGORIES),
+					(ObjectGoal<TaxTree, P>) (ObjectGoal) getGoal(GSGoalKey.TAXTREE), (RefSeqCatalogDownloadGoal) getGoal(GSGoalKey.REFSEQCAT),
+					(ObjectGoal<Integer, P>) (ObjectGoal) getGoal(GSGoalKey.ACCMAPSIZE), () -> device);
+		} else if (goal instanceof TaxNodesFromGenbankGoal && !(goal instanceof GpuTaxNodesFromGenbankGoal)) {
+			goal = new GpuTaxNodesFromGenbankGoal<P>(getProject(),
+					(ObjectGoal<Set<RefSeqCategory>, P>) (ObjectGoal) getGoal(GSGoalKey.CATEGORIES),
+					(ObjectGoal<Set<TaxIdNode>, P>) (ObjectGoal) getGoal(GSGoalKey.TAXNODES),
+					(ObjectGoal<AccessionMap, P>) (ObjectGoal) getGoal(GSGoalKey.ACCMAP));
+		} else if (goal instanceof FastaFilesFromGenbankGoal && !(goal instanceof GpuFastaFilesFromGenbankGoal)) {
+			goal = new GpuFastaFilesFromGenbankGoal<P>(getProject(), (ObjectGoal<TaxTree, P>) (ObjectGoal) getGoal(GSGoalKey.TAXTREE),
+					(FileGoal<P>) getGoal(GSGoalKey.ASSEMBLYDOWNLOAD),
+					(ObjectGoal<Set<TaxIdNode>, P>) (ObjectGoal) getGoal(GSGoalKey.TAXFROMGENBANK), () -> device);
 		}
 		super.registerGoal(goal);
 	}

@@ -316,6 +316,157 @@ public final class GsGpuNative {
 	/** gs_host_release_pools: page-locked blocks and device decoders the host layer keeps from call to call go back to the system */
 	public static native void hostReleasePools();
 
+	// ---- the database-construction chain: gs_genomes_*, gs_accmap_*, gs_asmsum_*, gs_taxtree_* and their file-level calls.
+	// Arguments in C order.  Every direct buffer (native order) is followed by its capacity in ELEMENTS of its type -- for an int32
+	// array buffer.capacity() / 4, for text, keys32 and pools the bytes -- and a call that needs more throws
+	// IllegalArgumentException before the library is entered.  The handles of these four families are good for the natives of
+	// their family, for accmapLookupGenomes and for hostGenomeFilesInto.  The file-level calls (host*) run under the control the
+	// calling thread attached (hostControlAttach) and throw the "cancelled" RuntimeException when it stops them.
+
+	/** gs_genomes_create */
+	public static native long genomesCreate(int device);
+
+	/** gs_genomes_scan with GS_MEM_HOST; out[4] = n_records, consumed_bytes, header_bytes, max_line_bytes */
+	public static native void genomesScan(long genomes, ByteBuffer text, long textCap, long nBytes, boolean last, long[] out);
+
+	/** gs_genomes_headers: headers = header_bytes, headerOff = n_records + 1 x int64 */
+	public static native void genomesHeaders(long genomes, ByteBuffer headers, long headersCap, ByteBuffer headerOff, long headerOffCap);
+
+	/** gs_genomes_gather: keep = n_records bytes or null (every record); out[2] = n_regions, n_bases */
+	public static native void genomesGather(long genomes, ByteBuffer keep, long keepCap, long[] out);
+
+	/** gs_genomes_regions: out[2] = the DEVICE addresses of seq and off of the last gather */
+	public static native void genomesRegions(long genomes, long[] out);
+
+	public static native void genomesDestroy(long genomes);
+
+	/** gs_accmap_create: knownTaxids = nNodes x int32 ascending; categories / statuses: substrings searched for in fields 4 and 5 */
+	public static native long accmapCreate(int device, boolean dna, boolean rna, boolean mrna, String[] categories, String[] statuses,
+			ByteBuffer knownTaxids, long knownTaxidsCap, int nNodes, long reserveEntries);
+
+	/** gs_accmap_submit with GS_MEM_HOST; report[8] as the C call's ([3] = 1: refused, the chunk is the caller's) */
+	public static native void accmapSubmit(long accmap, ByteBuffer text, long textCap, long nBytes, boolean last, long[] report);
+
+	/** gs_accmap_append: keys32 = n x 32 bytes, nodes = n x int32 */
+	public static native void accmapAppend(long accmap, ByteBuffer keys32, long keys32Cap, ByteBuffer nodes, long nodesCap, long n, long nPassing);
+
+	/** gs_accmap_finish: info[4] = entries, passing entries in all, entries equal to the one in front, those with another node */
+	public static native void accmapFinish(long accmap, long[] info);
+
+	/** gs_accmap_fetch: keys32 = entries x 32 bytes, nodes = entries x int32, regions = nNodes x int32; any may be null */
+	public static native void accmapFetch(long accmap, ByteBuffer keys32, long keys32Cap, ByteBuffer nodes, long nodesCap, ByteBuffer regions,
+			long regionsCap);
+
+	/** gs_accmap_lookup with GS_MEM_HOST: headerOff = n + 1 x int64 into headers, nodeOut = n x int32 */
+	public static native void accmapLookup(long accmap, ByteBuffer headers, long headersCap, ByteBuffer headerOff, long headerOffCap, long n,
+			boolean completeOnly, ByteBuffer nodeOut, long nodeOutCap);
+
+	/** gs_accmap_lookup_genomes: the header lines of the chunk `genomes` has scanned; nodeOut = n_records x int32 */
+	public static native void accmapLookupGenomes(long accmap, long genomes, boolean completeOnly, ByteBuffer nodeOut, long nodeOutCap);
+
+	public static native int accmapGetDevice(long accmap);
+
+	/** gs_accmap_get_n_nodes */
+	public static native int accmapGetNNodes(long accmap);
+
+	public static native void accmapDestroy(long accmap);
+
+	/** gs_host_accmap_files: the accmapsize (countOnly: returns 0, totals[1] is the number) and accmap goals over catalog files;
+	 *  totals[5] = lines, passing, put, device_chunks, host_chunks; returns the finished map */
+	public static native long hostAccmapFiles(String[] paths, int device, boolean dna, boolean rna, boolean mrna, String[] categories,
+			String[] statuses, ByteBuffer knownTaxids, long knownTaxidsCap, int nNodes, long reserveEntries, boolean countOnly, long[] totals);
+
+	/** gs_asmsum_create: filter = nNodes bytes or null (every node); qualityMask: bit q allows ordinal q, -1 all */
+	public static native long asmsumCreate(int device, ByteBuffer knownTaxids, long knownTaxidsCap, int nNodes, ByteBuffer filter, long filterCap,
+			int qualityMask, boolean referenceOnly, boolean useSpeciesTaxid, long reserveEntries);
+
+	/** gs_asmsum_submit with GS_MEM_HOST; report[8] as the C call's */
+	public static native void asmsumSubmit(long asmsum, ByteBuffer text, long textCap, long nBytes, boolean last, long[] report);
+
+	/** gs_asmsum_append: nodes n x int32, quality / isRef n bytes, lines n x int64, strOff 3 n + 1 x int64 into pool */
+	public static native void asmsumAppend(long asmsum, ByteBuffer nodes, long nodesCap, ByteBuffer quality, long qualityCap, ByteBuffer isRef,
+			long isRefCap, ByteBuffer lines, long linesCap, ByteBuffer strOff, long strOffCap, ByteBuffer pool, long poolCap, long n, long nCounted,
+			long nLines);
+
+	/** gs_asmsum_finish: info[4] = kept entries, picked entries, nodes with entries, counted records */
+	public static native void asmsumFinish(long asmsum, int maxPerNode, long[] info);
+
+	/** gs_asmsum_fetch: arrays of `picked` elements as for asmsumAppend; any may be null; pool = strOff[3 x picked] bytes */
+	public static native void asmsumFetch(long asmsum, ByteBuffer nodes, long nodesCap, ByteBuffer quality, long qualityCap, ByteBuffer isRef,
+			long isRefCap, ByteBuffer lines, long linesCap, ByteBuffer strOff, long strOffCap, ByteBuffer pool, long poolCap);
+
+	/** gs_asmsum_file_name: returns the length of AssemblyEntry's file name of ftp[0, n); min(length, outCap) bytes are written */
+	public static native long asmsumFileName(ByteBuffer ftp, long ftpCap, long n, ByteBuffer out, long outCap);
+
+	public static native int asmsumGetDevice(long asmsum);
+
+	public static native void asmsumDestroy(long asmsum);
+
+	/** gs_host_asmsum_files: the fastasgenbank goal over assembly summary files; totals[7] = lines, counted, kept, picked, nodes,
+	 *  device_chunks, host_chunks; returns the finished handle (asmsumFetch) */
+	public static native long hostAsmsumFiles(String[] paths, int device, ByteBuffer knownTaxids, long knownTaxidsCap, int nNodes, ByteBuffer filter,
+			long filterCap, int qualityMask, boolean referenceOnly, boolean useSpeciesTaxid, long reserveEntries, int maxPerNode, long[] totals);
+
+	/** gs_taxtree_create */
+	public static native long taxtreeCreate(int device);
+
+	/** gs_taxtree_submit_nodes with GS_MEM_HOST; report[8] as the C call's */
+	public static native void taxtreeSubmitNodes(long taxtree, ByteBuffer text, long textCap, long nBytes, boolean last, long[] report);
+
+	public static native void taxtreeAppendNodes(long taxtree, ByteBuffer text, long textCap, long nBytes, boolean last, long[] report);
+
+	/** gs_taxtree_finish_nodes: info[8], [0] = nodes, [1] = nodes the root reaches */
+	public static native void taxtreeFinishNodes(long taxtree, long[] info);
+
+	public static native void taxtreeSubmitNames(long taxtree, ByteBuffer text, long textCap, long nBytes, boolean last, long[] report);
+
+	public static native void taxtreeAppendNames(long taxtree, ByteBuffer text, long textCap, long nBytes, boolean last);
+
+	/** gs_taxtree_fetch: nodes x int32 each, any may be null */
+	public static native void taxtreeFetch(long taxtree, ByteBuffer taxids, long taxidsCap, ByteBuffer parent, long parentCap, ByteBuffer depth,
+			long depthCap, ByteBuffer position, long positionCap, ByteBuffer subtree, long subtreeCap, ByteBuffer rank, long rankCap);
+
+	/** gs_taxtree_fetch_names: offsets = nodes + 1 x int64 (offsets[nodes] = the bytes in all); bytes null: the offsets alone */
+	public static native void taxtreeFetchNames(long taxtree, ByteBuffer offsets, long offsetsCap, ByteBuffer bytes, long bytesCap);
+
+	/** gs_taxtree_select: the taxnodes set; out = nodes bytes; returns how many are set */
+	public static native long taxtreeSelect(long taxtree, int[] requested, long nRequested, int[] excluded, long nExcluded, int cutRank,
+			ByteBuffer out, long outCap);
+
+	/** gs_taxtree_small with GS_MEM_HOST: flagged = nodes x flagBytes (1 or 4); outputs = room for the nodes the root reaches, any may be
+	 *  null; returns n_small */
+	public static native int taxtreeSmall(long taxtree, ByteBuffer flagged, long flaggedCap, int flagBytes, ByteBuffer nodeOfVi, long nodeOfViCap,
+			ByteBuffer parentVi, long parentViCap, ByteBuffer depth, long depthCap, ByteBuffer position, long positionCap);
+
+	/** gs_taxtree_regions_below with GS_MEM_HOST: regions / inclusive = nodes x int32, below = nSelected x int32; returns n_below */
+	public static native long taxtreeRegionsBelow(long taxtree, ByteBuffer regions, long regionsCap, int[] selected, long nSelected, int limit,
+			int checkRank, ByteBuffer inclusive, long inclusiveCap, ByteBuffer below, long belowCap);
+
+	/** gs_taxtree_read_taxids: counts[2] = requested, excluded ids there are; at most cap of each are written */
+	public static native void taxtreeReadTaxids(ByteBuffer text, long textCap, long nBytes, ByteBuffer requested, long requestedCap,
+			ByteBuffer excluded, long excludedCap, long cap, long[] counts);
+
+	public static native int taxtreeGetDevice(long taxtree);
+
+	public static native void taxtreeDestroy(long taxtree);
+
+	/** gs_host_taxtree_files: the taxtree goal over nodes.dmp and (unless null) names.dmp; report[8] as the C call's; returns the
+	 *  finished tree */
+	public static native long hostTaxtreeFiles(int device, String nodesPath, String namesPath, long[] report);
+
+	/** gs_host_read_taxids_file: counts as taxtreeReadTaxids */
+	public static native void hostReadTaxidsFile(String path, ByteBuffer requested, long requestedCap, ByteBuffer excluded, long excludedCap,
+			long cap, long[] counts);
+
+	/** gs_host_genome_files_into: genome FASTA files straight into a sizer, builder, updater or quality handle.  accmap: a finished
+	 *  map or 0 when nodeOfFile gives every file's node; nodeOfFile: null, or per path a node (>= 0: no lookup) or -1; viOfNode =
+	 *  nNodes x int32 (< 0: skip); kind: INTO_*; totals[7] = records, kept_records, text_bytes, kept_bases, chunks, host_chunks,
+	 *  max_line_bytes.  Limits per tax id and finer nodes are not served. */
+	public static native void hostGenomeFilesInto(String[] paths, int device, long accmap, boolean completeOnly, int[] nodeOfFile,
+			ByteBuffer viOfNode, long viOfNodeCap, int nNodes, int kind, long handle, boolean update, long[] totals);
+
+	public static final int INTO_SIZE = 0, INTO_BUILD = 1, INTO_UPDATE = 2, INTO_QUALITY = 3;
+
 	// column indices of the integer table (include/gsgpu.h, GS_C_*)
 	public static final int C_READS = 0, C_READS_KMERS = 1, C_KMERS = 2, C_UNIQUE_KMERS = 3, C_CONTIGS = 4,
 			C_CONTIG_LEN_SQ_SUM = 5, C_MAX_CONTIG_LEN = 6, C_READS_1KMER = 7, C_READS_BPS = 8,

@@ -12,13 +12,18 @@
  */
 package org.metagene.genestrip.refseq;
 
+import java.io.File;
 import java.nio.ByteBuffer;
 import java.nio.ByteOrder;
+import java.util.List;
 import java.util.Map;
 import java.util.Set;
 
+import org.metagene.genestrip.gpu.GpuAccessionMap;
+import org.metagene.genestrip.gpu.GpuTaxTree;
 import org.metagene.genestrip.gpu.GsGpuNative;
 import org.metagene.genestrip.tax.Rank;
+import org.metagene.genestrip.tax.TaxTree;
 import org.metagene.genestrip.tax.TaxTree.TaxIdNode;
 
 public class GpuStoreFastaReader extends AbstractRefSeqFastaReader {
@@ -32,6 +37,7 @@ public class GpuStoreFastaReader extends AbstractRefSeqFastaReader {
 	private final ByteBuffer offsets;
 	private final ByteBuffer nodes;
 	private final int maxRegions;
+	private final boolean completeOnly;
 	private int regions;
 	private boolean open;
 
@@ -53,6 +59,7 @@ public class GpuStoreFastaReader extends AbstractRefSeqFastaReader {
 		this.allRegions = allRegions;
 		this.valueIndexOfNode = valueIndexOfNode;
 		this.maxRegions = Math.max(1024, batchBytes / 256);
+		this.completeOnly = completeGenomesOnly;
 		this.bases = ByteBuffer.allocateDirect(batchBytes);
 		this.offsets = ByteBuffer.allocateDirect(8 * (maxRegions + 1)).order(ByteOrder.nativeOrder());
 		this.nodes = ByteBuffer.allocateDirect(4 * maxRegions).order(ByteOrder.nativeOrder());
@@ -146,6 +153,59 @@ public class GpuStoreFastaReader extends AbstractRefSeqFastaReader {
 		nodes.putInt(4 * regions, valueIndexOfNode.get(node));
 		regions++;
 		offsets.putLong(8 * regions, bases.position());
+	}
+
+	/**
+	 * The files of a pass without this reader's line walk: gs_host_genome_files_into (GsGpuNative.hostGenomeFilesInto) cuts them into
+	 * chunks of whole records, finds the records and gathers the bases on the device, looks the header lines up in the device map
+	 * where the scan left them and hands the kept regions to this reader's handle -- sizer, updater or builder -- in device memory.
+	 * What infoLine() decides travels as a table: per node of the device tree the value index, or -1 where infoLine() would not
+	 * include the region (taxNodes, valueIndexOfNode; with update and allRegions every node that has a value index).
+	 *
+	 * The call does not serve what needs a look at every record in file order: a limit (maxGenomesPerTaxId / maxKMersPerTaxId below
+	 * their maxima -- maxGenomesPerTaxIdRank only matters with one) or finer nodes (idNodes / fileNodes / dataNodes: the caller says so,
+	 * reworkNode() is the goal's).  Then, and for a file node the dump does not hold, nothing is done and false comes back: the
+	 * caller reads the files with readFasta() as before.  regionsPerTaxid is not counted on this path (nothing reads it without a
+	 * limit), and the reference's "buffer is too small for data line" is not raised: totals[6] holds the longest line.
+	 *
+	 * @param files      the pass's FASTA files in order (plain, gzip or BGZF)
+	 * @param fileNodes  null, or per file the node of ignoreAccessionMap(node) for an additional FASTA file and null for a RefSeq file
+	 * @param tree       the tree the value indices were made from
+	 * @param deviceTree the same dump on the device: its node indices are the map's
+	 * @param deviceMap  the accession map on the device, or null if every file has a node
+	 * @param finerNodes true if idNodes, fileNodes or dataNodes is configured
+	 * @param totals     null, or long[7] as GsGpuNative.hostGenomeFilesInto fills it
+	 * @return true if the files went through the call
+	 */
+	public boolean filesInto(int device, List<File> files, List<TaxIdNode> fileNodes, TaxTree tree, GpuTaxTree deviceTree, GpuAccessionMap deviceMap,
+			boolean finerNodes, long[] totals) {
+		if (finerNodes || maxGenomesPerTaxId != Integer.MAX_VALUE || maxKmersPerTaxId != Long.MAX_VALUE) {
+			return false;
+		}
+		String[] paths = new String[files.size()];
+		int[] nodeOfFile = new int[paths.length];
+		for (int i = 0; i < paths.length; i++) {
+			paths[i] = files.get(i).getPath();
+			TaxIdNode given = fileNodes == null ? null : fileNodes.get(i);
+			nodeOfFile[i] = given == null ? -1 : deviceTree.nodeOf(given.getTaxId());
+			if ((given != null && nodeOfFile[i] < 0) || (given == null && deviceMap == null)) {
+				return false;
+			}
+		}
+		int[] taxIds = deviceTree.taxIds();
+		ByteBuffer viOfNode = ByteBuffer.allocateDirect(4 * Math.max(taxIds.length, 1)).order(ByteOrder.nativeOrder());
+		for (int i = 0; i < taxIds.length; i++) {
+			TaxIdNode n = tree.getNodeByTaxId(Integer.toString(taxIds[i]));
+			Integer vi = n == null ? null : valueIndexOfNode.get(n);
+			boolean wanted = (update && allRegions) || taxNodes.isEmpty() || taxNodes.contains(n);
+			viOfNode.putInt(4 * i, vi != null && wanted ? vi : -1);
+		}
+		flush();
+		int kind = sizer != 0L ? GsGpuNative.INTO_SIZE : updater != 0L ? GsGpuNative.INTO_UPDATE : GsGpuNative.INTO_BUILD;
+		long handle = sizer != 0L ? sizer : updater != 0L ? updater : builder;
+		GsGpuNative.hostGenomeFilesInto(paths, device, deviceMap == null ? 0L : deviceMap.handle(), completeOnly, nodeOfFile, viOfNode, taxIds.length,
+				taxIds.length, kind, handle, update, totals == null ? new long[7] : totals);
+		return true;
 	}
 
 	/** hands the collected regions to the device (also called by the goal after the last file of a pass) */

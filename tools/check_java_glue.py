@@ -15,7 +15,7 @@ For every class under java/src it checks, against an index of the reference's de
     or the result of a previous member in a chain): the member exists on that type (or its ancestors / interfaces) and
     is visible; `new X(...)` of a reference class: a constructor of that arity exists; `X.CONSTANT` on reference
     classes and enums.
-Types that come from the JDK are skipped.  It is a name / arity / visibility check, not a type checker.
+Types that come from the JDK are skipped, and so are the methods of java.lang.Object and java.lang.Enum on reference types.  It is a name / arity / visibility check, not a type checker.
 
     python tools/check_java_glue.py [--reference /root/reference] [--glue java/src]      exit code 1 on findings
 """
@@ -29,6 +29,9 @@ KEYWORDS = {"if", "else", "for", "while", "do", "switch", "case", "return", "new
             "byte", "short", "char", "void", "final", "static", "public", "protected", "private", "abstract", "class",
             "interface", "enum", "extends", "implements", "import", "package", "synchronized", "volatile", "transient",
             "native", "break", "continue", "default", "assert", "var"}
+# methods every reference type has without declaring them: java.lang.Object's, and those the compiler gives an enum
+OBJECT_METHODS = {"equals", "hashCode", "toString", "getClass"}
+ENUM_METHODS = {"values", "valueOf", "ordinal", "name", "compareTo"}
 MODS = {"public", "protected", "private", "static", "final", "abstract", "synchronized", "volatile", "transient", "native",
         "default", "strictfp"}
 
@@ -441,7 +444,9 @@ def check_class(idx, cls, problems, line_shift=0):
                 if hit:
                     break
             if hit is None:
-                bad(line, f"@Override {name}/{len(params)}: no ancestor declares it")
+                # (a supertype from the JDK -- AutoCloseable, Runnable -- may declare it: skipped like every JDK type)
+                if all(idx.resolve(t, cls) is not None for t in ([cls.extends] if cls.extends else []) + cls.implements):
+                    bad(line, f"@Override {name}/{len(params)}: no ancestor declares it")
             else:
                 a, mods = hit
                 if "final" in mods or "static" in mods or "private" in mods:
@@ -549,6 +554,8 @@ def check_class(idx, cls, problems, line_shift=0):
                 hit = find_member(idx, cur, name_, want)
                 if hit is None:
                     if want == "field" and name_ == "length":
+                        break
+                    if want == "method" and (name_ in OBJECT_METHODS or (cur.kind == "enum" and name_ in ENUM_METHODS)):
                         break
                     bad(ln, f"{cur.name}.{name_}{'(...)' if want == 'method' else ''}: no such {want} in {cur.qual} or its ancestors")
                     break

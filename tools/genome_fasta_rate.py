@@ -1,7 +1,8 @@
 """Genome FASTA text -> build regions (developer tool): the kernels of gs_genomes alone, and files through
 gs_host_genome_files into gs_dbbuild_add, on the synthetic collection tools/build_db_rate.py uses.
 
-    python tools/genome_fasta_rate.py [genera] [rounds]      (20 species per genus, 100 kbp each; default 25 genera, 5 rounds)
+    python tools/genome_fasta_rate.py [genera] [rounds] [parts]      (20 species per genus, 100 kbp each; default 25 genera, 5 rounds,
+                                                                      parts kernels,files,into)
 
 1. Kernels alone, between events on the handle's stream (DeviceGenomes.kernel_time), the text resident on the device: scan and
    select + gather as GB/s of TEXT for 60-base LF lines, 80-base CRLF lines and unwrapped records, keep = all and one in ten;
@@ -10,6 +11,9 @@ gs_host_genome_files into gs_dbbuild_add, on the synthetic collection tools/buil
 2. File to builder: a plain, a gzip and a BGZF file of the 60-base text through host.genome_files into DeviceDbBuilder.add (fill
    walk), against a Python line loop that feeds the same builder from host memory (what examples/build_db.py did), and against
    the line-by-line parser of the host layer forced for every chunk (GS_HOST_FAST=0).
+3. Callbacks or none: the plain file into DeviceDbBuilder.add through host.genome_files_into (an accession map on the device, a
+   table of value indices, no callback) and through host.genome_files with its two ctypes callbacks, by turns.  They share one
+   loop: the expectation is equality within the spread of the runs.
 Every figure: the fastest of `rounds` runs taken by turns, with the spread (slowest / fastest - 1).  One JSON line per part."""
 import ctypes as C
 import gzip
@@ -62,12 +66,22 @@ def read_fasta(path):
 def main():
     genera = int(sys.argv[1]) if len(sys.argv) > 1 else 25
     rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    parts = sys.argv[3].split(",") if len(sys.argv) > 3 else ["kernels", "files", "into"]
     db = synth.SynthDB(genera=genera, species_per_genus=20)
     n_gen, bases = db.genomes.shape[0], int(db.genomes.size)
     shapes = {"lf60": fasta_text(db.genomes, 60, b"\n"), "crlf80": fasta_text(db.genomes, 80, b"\r\n"), "unwrapped": fasta_text(db.genomes, 0, b"\n")}
     keeps = {"all": None, "one_in_ten": np.arange(n_gen) % 10 == 0}
 
-    # ---- 1. kernels alone
+    if "kernels" in parts:
+        kernels_alone(db, shapes, keeps, rounds)
+    if "files" in parts:
+        file_to_builder(db, shapes["lf60"], rounds)
+    if "into" in parts:
+        callbacks_or_none(db, shapes["lf60"], rounds)
+
+
+def kernels_alone(db, shapes, keeps, rounds):
+    n_gen, bases = db.genomes.shape[0], int(db.genomes.size)
     g = ga.DeviceGenomes()
     upd = ga.DeviceDbUpdater.from_arrays(31, db.kmers[:1], db.value_idx[:1], db.n_values, db.parent_vi)
     dev = {name: torch.from_numpy(np.frombuffer(t, dtype=np.uint8).copy()).cuda() for name, t in shapes.items()}
@@ -131,9 +145,11 @@ def main():
     upd.close()
     del dev
 
-    # ---- 2. file to builder
+
+
+def file_to_builder(db, text, rounds):
+    n_gen, bases = db.genomes.shape[0], int(db.genomes.size)
     with tempfile.TemporaryDirectory() as tmp:
-        text = shapes["lf60"]
         files = {"plain": os.path.join(tmp, "g.fasta"), "gzip": os.path.join(tmp, "g.gz.fasta.gz"), "bgzf": os.path.join(tmp, "g.bgzf.fasta.gz")}
         open(files["plain"], "wb").write(text)
         open(files["gzip"], "wb").write(gzip.compress(text, 1))
@@ -174,6 +190,42 @@ def main():
                     secs[w].append(dt)
         out = {w: dict(best(v), mbases_per_s=round(bases / min(v) / 1e6, 1)) for w, v in secs.items()}
         print(json.dumps({"part": "file_to_builder", "text_mb": round(len(text) / 1e6, 1), "bases": bases, "seconds": out}), flush=True)
+
+
+def callbacks_or_none(db, text, rounds):
+    n_gen, bases = db.genomes.shape[0], int(db.genomes.size)
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "g.fasta")
+        open(path, "wb").write(text)
+        # node i = genome i; the accession of ">g7|synthetic genome 7" is what stands in front of the first blank
+        amap = ga.DeviceAccessionMap(np.arange(1, n_gen + 1), ["x"], ["x"])
+        amap.append([b"g%d|synthetic" % i for i in range(n_gen)], np.arange(n_gen))
+        amap.finish()
+        vi_of_node = np.ascontiguousarray(db.species_vi, dtype=np.int32)
+        vi_of = {b"g%d" % i: int(db.species_vi[i]) for i in range(n_gen)}
+        resolve = lambda f, first, headers: [vi_of[h[1:].split(b"|")[0]] for h in headers]
+
+        def run(into):
+            b = ga.DeviceDbBuilder(31, db.n_values, db.parent_vi)
+            t0 = time.time()
+            if into:
+                t = host.genome_files_into([path], b, vi_of_node, accession_map=amap)
+            else:
+                t = host.genome_files([path], resolve, lambda s, o, v: b.add(s, o, v))
+            dt = time.time() - t0
+            b.close()
+            assert t.kept_bases == bases and t.kept_records == n_gen and t.host_chunks == 0, (t.kept_bases, t.kept_records, t.host_chunks)
+            return dt
+
+        secs = {"genome_files_into": [], "genome_files with callbacks": []}
+        for r in range(rounds + 1):  # (round 0 warms up)
+            for w in secs:
+                dt = run(w == "genome_files_into")
+                if r:
+                    secs[w].append(dt)
+        amap.close()
+        out = {w: {"fastest": round(min(v), 4), "slowest": round(max(v), 4), "mbases_per_s": round(bases / min(v) / 1e6, 1)} for w, v in secs.items()}
+        print(json.dumps({"part": "callbacks_or_none", "text_mb": round(len(text) / 1e6, 1), "bases": bases, "runs": rounds, "seconds": out}), flush=True)
 
 
 if __name__ == "__main__":
